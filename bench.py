@@ -7,10 +7,15 @@ on the workload BASELINE.json's metric is quoted on: Ising C_64, n=51, maxrank 3
 inputs resident in HBM.  For N>1 the SAME problem is split over N GPUs by bond groups (strong scaling).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c64|c16|d32|d256|mvn128|ort|svd...] [--arith exact|fast]
+                    [--full] [--dump-outputs DIR]
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` for the dominant kernel (the rook half-step:
-fiber evaluation + residual + arg-max), `cpu_baseline` = the genuine reference (oracle/_ref, kind
-"reference") or the C oracle (kind "port") timed on the host cores on the same workload.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline figures
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`) with the run's configuration.  `--full` adds the
+side measurements, each of which takes runs of its own: `roofline` for the dominant kernel (the rook half-step: fiber
+evaluation + residual + arg-max) from a profiled pass, `k1_evaluation`, `latency_model`, `k2_streaming`, `single_group`,
+the N > 1 single-process check, and `cpu_baseline` = the genuine reference (oracle/_ref, kind "reference") or the C oracle
+(kind "port") timed on the host cores on the same workload.  `--dump-outputs DIR` writes what the last timed step computed
+(see dump_outputs()).
 """
 import argparse
 import json
@@ -41,6 +46,26 @@ WORKLOADS["d64"] = (("ising", "d", 64, 51, 32, 2), "Ising D_64 n=51 r=32 piv=2 (
 LONG_WORKLOADS = {"d256", "mvn128"}     # one CPU run takes minutes: cpu_baseline times a bounded prefix of one run
 FP64_VECTOR_PEAK_TFLOPS = 78.0      # MI355X fp64 vector (non-matrix) peak, SURVEY 8(d)
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_MAX_CORE_VALUES = 7 << 19      # --dump-outputs: trains up to 28 MB are written whole (C_64: 25.5 MB), larger ones as a fixed sample (56 MB with positions)
+
+
+def dump_outputs(out_dir, tt, **scalars):
+    """--dump-outputs: the result of the last timed step as a caller of dtt_dmrgg / dtt_ort / dtt_svd receives it, float64 .npy:
+      cores.npy       every core arg%u(k)%p, k = 1..d, column-major, concatenated (trains above DUMP_MAX_CORE_VALUES doubles:
+                      a sample of that many values at fixed positions, seed 0, and their positions in cores_index.npy)
+      ranks.npy       r(0..d)
+      <name>.npy      one array per keyword argument (integral, neval, per-sweep values, ...)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cores = np.concatenate([tt.core(k).ravel(order="F") for k in range(1, tt.d + 1)])
+    if cores.size > DUMP_MAX_CORE_VALUES:
+        idx = np.sort(np.random.default_rng(0).choice(cores.size, DUMP_MAX_CORE_VALUES, replace=False))
+        np.save(os.path.join(out_dir, "cores_index.npy"), idx.astype(np.float64))
+        cores = cores[idx]
+    np.save(os.path.join(out_dir, "cores.npy"), cores.astype(np.float64))
+    np.save(os.path.join(out_dir, "ranks.npy"), tt.ranks().astype(np.float64))
+    for name, v in scalars.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.atleast_1d(np.asarray(v, dtype=np.float64)))
 
 
 def _time_reference(cmd, env, budget_s, max_runs=15):
@@ -200,6 +225,8 @@ def bench_utility(a, D, E):
             times.append(dt)
         out_ranks = t.ranks()
         nrm = t.norm()
+        if it == a.warmup + a.steps - 1 and a.dump_outputs:
+            dump_outputs(a.dump_outputs, t, norm=nrm)
         t.close()
     sz = sum(c.size for c in cores)
     passes = 2 if op == "ort" else 4
@@ -213,7 +240,7 @@ def bench_utility(a, D, E):
                          "unit": "GB/s", "frac": passes * 8.0 * sz / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None,
                          "algorithmic_bytes_per_step": passes * 8.0 * sz, "householder_flops_per_step": flops,
                          "note": "63 dependent per-core stages of < 0.5 MB each: launch- and latency-bound, see DESIGN.md section 8"}}
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         # cpu_baseline: the GENUINE reference's dtt_ort / dtt_svd (LAPACK through MKL sequential, as the reference links it) on the
         # IDENTICAL train -- written here with ttx_write in the reference's stream format, read there with its own dtt_read --
         # by oracle/_ref/ref_tt_timing (our own small timing driver around the reference's modules; bench infrastructure)
@@ -365,9 +392,12 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="c64", choices=sorted(WORKLOADS) + sorted(UTIL_WORKLOADS))
-    ap.add_argument("--no-extras", action="store_true", help="skip the k2_streaming and single_group side measurements (profiler runs: only the workload's own launches)")
+    ap.add_argument("--full", action="store_true", help="also the side measurements that take runs of their own: roofline / kernel times (profiled pass), "
+                    "latency model, k2_streaming, single_group, the N>1 single-process check, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the k2_streaming and single_group side measurements (profiler runs: only the workload's own launches)")
     ap.add_argument("--groups", type=int, default=0, help="bond groups = MPI ranks of the reference's domain split; default 8 (config 3 of BASELINE.json) at every N")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--arith", default="exact", choices=["exact", "fast"], help="TTX_ARITH: exact (default; every fp64 operation of the integrand in the reference's order) "
                     "or fast (Ising D/E, mvn: re-associated O(d) evaluation, tolerance-checked)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend for N>1 (gloo: rehearsal with several ranks on one GPU)")
@@ -476,7 +506,37 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     value = tt.quad(s["quad"])
-    nsweeps = len(tt.sweeps()) - 1
+    sweeps = tt.sweeps()
+    nsweeps = len(sweeps) - 1
+    if a.dump_outputs:      # the last timed step's train (N > 1: gathered onto every rank, collective), integral and sweep records
+        whole = tt.replicate() if world > 1 else tt
+        if rank == 0:
+            dump_outputs(a.dump_outputs, whole, integral=value, neval=tt.neval, sweep_values=[w["val"] for w in sweeps],
+                         sweep_eranks=[w["erank"] for w in sweeps], sweep_nevals=[w["neval"] for w in sweeps])
+        if whole is not tt:
+            whole.close()
+    out = {
+        "metric": "fiber evals/s (neval / wall time of dtt_dmrgg), " + desc,
+        "value": neval / dt, "unit": "evals/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic (integrand evaluated on the fly; Gauss-Legendre nodes/weights; flang-compatible lottery RNG stream)",
+        "config": {"workload": desc, "driver": ("test_crs_ising " + " ".join(str(x) for x in argv[1:])) if argv[0] == "ising" else ("test_crs_mvn " + " ".join(str(x) for x in argv[2:])), "bond_groups": groups, "transport": transport,
+                   "arith": tt.arith, "sweep_path": tt.sweep_path(),
+                   "neval_per_step": neval // a.steps, "sweeps": nsweeps, "integral": value,
+                   "rel_err_vs_analytic": abs(1 - value / s["tru"]) if s["tru"] else None},
+    }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(out))
+        return
+    full_measurements(a, out, tt, s, argv, groups, local, rank, world, neval, dt)
+
+
+def full_measurements(a, out, tt, s, argv, groups, local, rank, world, neval, dt):
+    """--full: the side measurements after the timed steps, each with runs of its own; they add their objects to `out`,
+    which rank 0 prints."""
+    from ttcross_amd import engine as E
+    value = out["config"]["integral"]
     # N > 1: the result depends only on the number of bond groups, not on how they are spread over GPUs -- rank 0 repeats
     # the job as ONE process and the integral must come out bit-identical (the transport between GPUs moved the right bytes)
     multi_check = None
@@ -530,8 +590,8 @@ def main():
             t1.close()
     if rank != 0:
         return
-    path = tt.sweep_path()
-    arith = tt.arith
+    path = out["config"]["sweep_path"]
+    arith = out["config"]["arith"]
     heavy = (argv[0] == "ising" and argv[1] in ("d", "e")) or argv[0] == "mvn"
     # the chain path's half-step kernel by integrand and arithmetic: the wave-per-pivot kernels of Ising D/E and mvn (exact), the generic
     # kernel with the table evaluators of ttx_fast.h (fast), the generic kernel otherwise
@@ -573,16 +633,8 @@ def main():
     except Exception:  # noqa: BLE001
         traffic = None
     hbm = {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS}
-    out = {
-        "metric": "fiber evals/s (neval / wall time of dtt_dmrgg), " + desc,
-        "value": neval / dt, "unit": "evals/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic (integrand evaluated on the fly; Gauss-Legendre nodes/weights; flang-compatible lottery RNG stream)",
-        "multi_gpu_check": multi_check,
-        "config": {"workload": desc, "driver": ("test_crs_ising " + " ".join(str(x) for x in argv[1:])) if argv[0] == "ising" else ("test_crs_mvn " + " ".join(str(x) for x in argv[2:])), "bond_groups": groups, "transport": transport,
-                   "arith": arith, "sweep_path": path,
-                   "neval_per_step": neval // a.steps, "sweeps": nsweeps, "integral": value,
-                   "rel_err_vs_analytic": abs(1 - value / s["tru"]) if s["tru"] else None},
+    out["multi_gpu_check"] = multi_check
+    out.update({
         # `bound` names what limits the dominant kernel on THIS path: "hbm" where the half-step is its residual sweep K2 (fast mode of
         # the heavy integrands, generic chain), "fp64-valu" where it is the integrand's dependent fp64 chain (exact Ising D/E, mvn),
         # "latency" for the whole-sweep kernels (a launch moves ~4 MB in ~300 us: achieved / peak are then the measured launch time and
@@ -591,7 +643,7 @@ def main():
                          avg_launch_us=avg_us, launches_per_step=hs["launches"] / max(1, min(a.steps, 3)),
                          algorithmic_bytes_per_launch=bytes_per_launch),
         "kernel_ms_per_step": {k: v["ms"] / max(1, min(a.steps, 3)) for k, v in agg.items()},
-    }
+    })
     # K1 (fiber evaluation) as fp64 vector work, SURVEY 8(d): algorithmic flops per evaluation of the integrand
     dd = len(s["n"])
     fl = (5 * dd + 1) if argv[1] == "c" else (2 * dd * dd + dd + 20) if argv[0] == "mvn" else (6 * dd * (dd + 1) // 2 + 5 * dd)

@@ -23,7 +23,7 @@ P
 fi
 G=${3:-0}
 O=$R/gpurun_out/r03_${WL}_${AR}; mkdir -p $O
-CMD="python3 $R/bench.py --workload $WL --arith $AR --steps 1 --warmup 0 --no-cpu-baseline --no-extras"
+CMD="python3 $R/bench.py --full --workload $WL --arith $AR --steps 1 --warmup 0 --no-cpu-baseline --no-extras"
 if [ "$G" != "0" ]; then CMD="$CMD --groups $G"; fi
 rm -rf /tmp/st_$WL$AR /tmp/pf_$WL$AR /tmp/pw_$WL$AR /tmp/ps_$WL$AR
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/st_$WL$AR -- $CMD > $O/bench_under_rocprof.json 2> $O/rocprof_stats.err

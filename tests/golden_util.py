@@ -4,6 +4,16 @@ import os
 import re
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+ENGINE_LIBDIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ttcross_amd", "lib")
+
+
+def engine_env(env=None):
+    """Environment for a binary linked with libttx.so (the reference's drivers on the engine, oracle/_ref/dropin_*): this
+    tree's ttcross_amd/lib first on LD_LIBRARY_PATH.  The binaries' RUNPATH ($ORIGIN-relative) follows the real location
+    of the file, which need not lie inside this tree when oracle/_ref is linked or copied in from elsewhere."""
+    env = dict(os.environ if env is None else env)
+    env["LD_LIBRARY_PATH"] = os.pathsep.join([ENGINE_LIBDIR] + [p for p in env.get("LD_LIBRARY_PATH", "").split(os.pathsep) if p])
+    return env
 
 
 def parse_log(txt):

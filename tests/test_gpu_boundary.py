@@ -10,7 +10,7 @@ import pytest
 
 import oracle_lib as O
 from conftest import ROOT, fortran_exe
-from golden_util import GOLDEN, parse_log
+from golden_util import GOLDEN, engine_env, parse_log
 from ttcross_amd import drivers as D
 from ttcross_amd import engine as E
 
@@ -284,7 +284,7 @@ def test_reference_drivers_unchanged_on_the_engine(drv, name):
     if not os.path.exists(exe):
         pytest.skip("oracle/_ref/dropin_test_crs_* not built (needs /root/reference + amdflang: make -C oracle dropin)")
     argv = name.split("_")[1:]
-    p = subprocess.run([exe] + argv, capture_output=True, text=True, timeout=600)
+    p = subprocess.run([exe] + argv, capture_output=True, text=True, timeout=600, env=engine_env())
     assert p.returncode == 0, p.stdout + p.stderr
     g_rows, g_val, g_nev = parse_log(open(os.path.join(GOLDEN, name + ".txt")).read())
     o_rows, o_val, o_nev = parse_log(p.stdout)

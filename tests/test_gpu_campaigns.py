@@ -176,13 +176,13 @@ def test_fuzz_reference_driver_on_the_engine_vs_genuine_reference():
     reference sums with MKL (and inverts the mvn covariance with LAPACK), so a near-tie may turn a later pivot: the first three
     sweeps (stdnorm: two, mvn: the first) must agree in (erank, n_evals) and to 2e-13 in the value; the number of cases that agree in EVERY sweep
     is reported."""
-    from golden_util import parse_log
+    from golden_util import engine_env, parse_log
     exe = lambda pre, drv: os.path.join(ROOT, "oracle", "_ref", f"{pre}test_crs_{drv}")
     if not all(os.path.exists(exe(pre, drv)) for pre in ("", "dropin_") for drv in ("ising", "stdnorm", "mvn")):
         pytest.skip("oracle/_ref binaries not built (needs /root/reference + amdflang: make -C oracle ref dropin)")
     ncases = int(os.environ.get("TTX_REFFUZZ_CASES", "3"))
     rng = np.random.default_rng(int(os.environ.get("TTX_FUZZ_SEED", "20261004")) + 3)
-    env = dict(os.environ, MKL_THREADING_LAYER="SEQUENTIAL", OMP_NUM_THREADS="4")
+    env = engine_env(dict(os.environ, MKL_THREADING_LAYER="SEQUENTIAL", OMP_NUM_THREADS="4"))
     full, bad = 0, []
     for _ in range(ncases):
         drv = str(rng.choice(["ising", "ising", "ising", "stdnorm", "mvn"]))
