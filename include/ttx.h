@@ -31,6 +31,11 @@ extern "C" {
 #define TTX_FUN_STDNORM 2  /* integrand, test_crs_stdnorm.f90:154-170                                     */
 #define TTX_FUN_MVN 3      /* integrand -> mvn_pdf, test_crs_mvn.f90:156-172, lib/mvn_pdf.f90:63-83       */
 #define TTX_FUN_HOST 4     /* any user `fun` (lib/dmrgg.f90:18), evaluated on the HOST: ttx_set_integrand_host */
+/* calc_coefficient, the fork's COS coefficients (test_crs_coscoeff.f90, lib/coefficients.f90): evaluated on the device
+ * (ttx_coscoeff.h).  aux = [mu(1:d), Sigma(1:d,1:d) column-major, a, b], naux = d + d*d + 2; par unused.  ttx_create refuses
+ * (TTX_EINVAL) a wrong naux, non-finite aux, a >= b, d > 20, and problems whose bound on |t'mu| or |a sum t| over the index
+ * box exceeds the range of the integrand's own sin / cos (2^19).  Mode sizes may differ.  TTX_ARITH=fast leaves it exact. */
+#define TTX_FUN_COSCOEFF 5
 
 #define TTX_ARITH_EXACT 0
 #define TTX_ARITH_FAST 1
@@ -224,7 +229,8 @@ int ttx_k_residual_argmax(int32_t device, int32_t m, int32_t r, const double *a,
  * (m*r*8 bytes, generated on the device); returns the average kernel time over `iters` launches measured with
  * HIP events, and the algorithmic bytes 8*(m*r + r + 2*m) one launch moves. */
 int ttx_k_residual_bench(int32_t device, int64_t m, int32_t r, int32_t iters, double *avg_ms, double *bytes);
-/* K1: batch integrand evaluation, ind = npts x d (row-major, 1-based indices) */
+/* K1: batch integrand evaluation, ind = npts x d (row-major, 1-based indices); fun_id ISING, STDNORM, MVN or COSCOEFF
+ * (anything else, and a COSCOEFF aux that ttx_create would refuse, is TTX_EINVAL before any device call) */
 int ttx_k_eval(int32_t device, int32_t fun_id, int32_t d, const int32_t *n, const double *par, int32_t npar,
                const double *aux, int32_t naux, int64_t npts, const int32_t *ind, double *out);
 /* the same with the arithmetic named (TTX_ARITH_FAST: the re-associated one-thread evaluator of ttx_fast.h; Ising D/E, nodes in [0,1]) */

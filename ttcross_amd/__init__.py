@@ -4,4 +4,4 @@ Python is plumbing only: `engine` binds the C-ABI of libttx.so (include/ttx.h) w
 mirrors the command-line drivers test_crs_ising / test_crs_mvn / test_crs_stdnorm.  All computation happens
 in hand-written HIP kernels (ttcross_amd/csrc); there is no CPU fallback.
 """
-from .engine import (TTX_FUN_ISING, TTX_FUN_MVN, TTX_FUN_STDNORM, TTCross, TTXError, dtt_dmrgg, lib_path, load_library)  # noqa: F401
+from .engine import (TTX_FUN_COSCOEFF, TTX_FUN_ISING, TTX_FUN_MVN, TTX_FUN_STDNORM, TTCross, TTXError, dtt_dmrgg, lib_path, load_library)  # noqa: F401

@@ -162,6 +162,9 @@ struct DevProb {
     // hreq[slot] and stops before any side effect; the host calls `fun`; pass 2 (hostpass = 2) reads hval[slot].
     // All three arrays live in pinned host memory; a group's slots are [g*HS, (g+1)*HS).
     int hostpass, HS;
+    // TTX_FUN_COSCOEFF runs the same two passes, but the three arrays are device memory and k_coscoeff_slots (ttx_coscoeff.h)
+    // evaluates the requested slots between them on the stream: no host round trip (slot_dev = 1)
+    int slot_dev;
     int zbase;                     // full pivoting with a host integrand: first superblock column (k,q) of this launch (one column per launch)
     short *hidx;
     double *hval;

@@ -37,6 +37,7 @@
 #include "ttx_ttops.h"
 #include "ttx_fused.h"
 #include "ttx_cluster.h"
+#include "ttx_coscoeff.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const char *fmt, ...)
@@ -268,6 +269,43 @@ static int host_eval(ttx_engine *h)
     return TTX_OK;
 }
 
+// between the two passes of an evaluating kernel: the host's `fun` (host_eval), or for TTX_FUN_COSCOEFF the device evaluator over
+// the requested slots, enqueued on the stream behind pass 1 (no synchronisation)
+static int slot_eval(ttx_engine *h)
+{
+    DevProb &P = h->P;
+    if (!P.slot_dev) return host_eval(h);
+    const long long nslot = (long long)h->G * h->HS;
+    const unsigned grid = (unsigned)std::min<long long>((nslot + TTX_CC_WAVES - 1) / TTX_CC_WAVES, 1024);
+    hipLaunchKernelGGL(k_coscoeff_slots, dim3(grid), dim3(64 * TTX_CC_WAVES), sizeof(double) * TTX_CC_WAVES * TTX_CC_LDS(P.d), h->stream,
+                       P.d, P.aux, nslot, (const short *)P.hidx, P.hreq, P.hval);
+    return TTX_OK;
+}
+
+// TTX_FUN_COSCOEFF: aux = [mu(1:d), Sigma(1:d,1:d), a, b].  Refused before anything reaches the device: a wrong naux, non-finite
+// data, a >= b, d > TTX_COSCOEFF_MAXD, and an index box on which |t'mu| or |a sum t| could leave the range of ttx_sin / ttx_cos.
+static int coscoeff_check(const char *who, int d, const int32_t *n, const double *aux, int naux)
+{
+    if (d > TTX_COSCOEFF_MAXD) return fail(TTX_EINVAL, "%s: coscoeff: at most %d dimensions (2^(d-1) sign vectors per element), got %d", who, TTX_COSCOEFF_MAXD, d);
+    if (!aux || naux != d + d * d + 2) return fail(TTX_EINVAL, "%s: coscoeff: aux must hold mu(1:d), Sigma(1:d,1:d), a, b: %d values (got %d)", who, d + d * d + 2, naux);
+    for (int k = 0; k < naux; k++) if (!std::isfinite(aux[k])) return fail(TTX_EINVAL, "%s: coscoeff: aux(%d) is not finite", who, k + 1);
+    const double a = aux[d + d * d], b = aux[d + d * d + 1];
+    if (!(a < b)) return fail(TTX_EINVAL, "%s: coscoeff: lower bound %g must be below upper bound %g", who, a, b);
+    const double ob = 1.0 / (b - a);
+    if (!std::isfinite(ob)) return fail(TTX_EINVAL, "%s: coscoeff: 1/(b-a) is not finite", who);
+    // |t_j| <= pi (n_j - 1) / (b - a): bounds of |dot_mu| and |a sum t| (and of every partial sum), with room for rounding
+    double bmu = 0.0, bst = 0.0;
+    for (int j = 0; j < d; j++) {
+        const double tj = TTX_COSCOEFF_PI * (double)std::max(n[j] - 1, 0) * ob;
+        bmu += tj * std::fabs(aux[j]); bst += tj;
+    }
+    bst *= std::fabs(a);
+    if (!(bmu * (1 + 1e-9) <= TTX_TRIG_MAX) || !(bst * (1 + 1e-9) <= TTX_TRIG_MAX))
+        return fail(TTX_EINVAL, "%s: coscoeff: the arguments of sin/cos can reach %g (|t'mu|) and %g (|a sum t|), beyond the supported %g",
+                    who, bmu, bst, (double)TTX_TRIG_MAX);
+    return TTX_OK;
+}
+
 template <class T>
 static int dev_alloc(ttx_engine *h, T **p, size_t count)
 {
@@ -310,16 +348,18 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
     if (cfg->maxrank < 1 || cfg->maxrank > 128) return fail(TTX_EINVAL, "ttx_create: maxrank must be in 1..128 (got %d)", cfg->maxrank);
     if (cfg->pivoting < -1) return fail(TTX_EINVAL, "dtt_dmrgg: unknown pivoting: %d", cfg->pivoting);   // lib/dmrgg.f90:590-592
     if (2 * cfg->pivoting + 2 > TTX_MAXH) return fail(TTX_EINVAL, "dtt_dmrgg: pivoting %d too large", cfg->pivoting);
-    if (!(nofun && cfg->fun_id == 0) && (cfg->fun_id < 1 || cfg->fun_id > 4)) return fail(TTX_EINVAL, "ttx_create: unknown fun_id %d", cfg->fun_id);
+    if (!(nofun && cfg->fun_id == 0) && (cfg->fun_id < 1 || cfg->fun_id > 5)) return fail(TTX_EINVAL, "ttx_create: unknown fun_id %d", cfg->fun_id);
     if (cfg->npar < 0 || (cfg->npar > 0 && !cfg->par)) return fail(TTX_EINVAL, "ttx_create: par missing");
     if (cfg->fun_id == TTX_FUN_ISING && (cfg->npar < 2 * cfg->n[0] + 1)) return fail(TTX_EINVAL, "ttx_create: the Ising integrand needs par(1:2n+1) (nodes, weights, id)");
     if ((cfg->fun_id == TTX_FUN_STDNORM || cfg->fun_id == TTX_FUN_MVN) && cfg->npar < cfg->n[0]) return fail(TTX_EINVAL, "ttx_create: the integrand needs the nodes par(1:n)");
     // the built-in integrands address par(ind) (and the Ising weights par(n(1) + ind)): no mode may be larger than the first
     // (test_crs_ising.f90:181-183); with the reference this is the caller's business, here it would be a read outside the parameter vector
-    if (cfg->fun_id != TTX_FUN_HOST && cfg->fun_id != 0)
+    // (the COS coefficients do not index par)
+    if (cfg->fun_id != TTX_FUN_HOST && cfg->fun_id != TTX_FUN_COSCOEFF && cfg->fun_id != 0)
         for (int k = 1; k < cfg->d; k++)
             if (cfg->n[k] > cfg->n[0]) return fail(TTX_EINVAL, "ttx_create: mode %d has %d points, more than the first mode (%d): the built-in integrands index par by n(1)", k + 1, cfg->n[k], cfg->n[0]);
     if (cfg->fun_id == TTX_FUN_HOST && cfg->d > 2048) return fail(TTX_EINVAL, "ttx_create: host integrand: at most 2048 dimensions (tt_size)");
+    if (cfg->fun_id == TTX_FUN_COSCOEFF) { if (int rc0 = coscoeff_check("ttx_create", cfg->d, cfg->n, cfg->aux, cfg->naux)) return rc0; }
     const int W = cfg->world_size < 1 ? 1 : cfg->world_size;
     const int nproc = std::max(cfg->nproc < 1 ? 1 : cfg->nproc, 1);
     if (nproc >= cfg->d) return fail(TTX_EINVAL, "nproc exceeds or equal dimension, cannot proceed");   // lib/dmrgg.f90:114-117
@@ -686,17 +726,23 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
             h->lot_rows = h->lot_wave ? ((getenv("TTX_LOTTERY_ROWS") && atoi(getenv("TTX_LOTTERY_ROWS")) == 2) ? 2 : 1) : 0;
         }
     }
-    if (cfg->fun_id == TTX_FUN_HOST) {
+    if (cfg->fun_id == TTX_FUN_HOST || cfg->fun_id == TTX_FUN_COSCOEFF) {
         // slots of one group: the largest point set any evaluating kernel asks for in one launch
         int nn = h->n1[1];
         for (int k = 2; k <= d; k++) nn = std::min(nn, h->n1[k]);
         const size_t snum = (size_t)std::max(8, nproc);
         h->HS = std::max<size_t>({(size_t)h->RM * NM, (size_t)nn * snum, (size_t)h->NC * NM, (size_t)2 * h->RM + 2 * NM, (size_t)2 * NM, (size_t)256});
         const size_t nslot = (size_t)h->G * h->HS;
+        if (cfg->fun_id == TTX_FUN_COSCOEFF) {
+            // device slots (zero-filled, owned by allocs): the evaluator runs on the stream between the two passes
+            P.slot_dev = 1;
+            if ((rc = dev_alloc(h, &P.hidx, nslot * d)) || (rc = dev_alloc(h, &P.hval, nslot)) || (rc = dev_alloc(h, &P.hreq, nslot))) { ttx_destroy(h); return rc; }
+        } else {
         HIPCHECK(hipHostMalloc((void **)&P.hidx, sizeof(short) * nslot * d));
         HIPCHECK(hipHostMalloc((void **)&P.hval, sizeof(double) * nslot));
         HIPCHECK(hipHostMalloc((void **)&P.hreq, nslot));
         memset(P.hreq, 0, nslot); memset(P.hval, 0, sizeof(double) * nslot);
+        }
         P.HS = (int)h->HS; P.hostpass = 0;
     }
     *out = h;
@@ -720,9 +766,11 @@ extern "C" void ttx_destroy(ttx_engine *h)
     if (h->red_mem) (void)hipHostFree(h->red_mem);
     shm_close(h);
     if (h->h_abort) (void)hipHostFree(h->h_abort);
-    if (h->P.hidx) (void)hipHostFree(h->P.hidx);
-    if (h->P.hval) (void)hipHostFree(h->P.hval);
-    if (h->P.hreq) (void)hipHostFree(h->P.hreq);
+    if (!h->P.slot_dev) {                   // device slots are in allocs
+        if (h->P.hidx) (void)hipHostFree(h->P.hidx);
+        if (h->P.hval) (void)hipHostFree(h->P.hval);
+        if (h->P.hreq) (void)hipHostFree(h->P.hreq);
+    }
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1264,7 +1312,7 @@ static int run_impl(ttx_engine *h)
         if (FUN != FUN_HOST) { launch(P); return TTX_OK; }
         DevProb Q = P;
         Q.hostpass = 1; launch(Q);
-        if (int rc_ = host_eval(h)) return rc_;
+        if (int rc_ = slot_eval(h)) return rc_;
         Q.hostpass = 2; launch(Q);
         return TTX_OK;
     };
@@ -1436,7 +1484,7 @@ static int run_impl(ttx_engine *h)
                         Q.zbase = z;
                         Q.hostpass = 1;
                         hipLaunchKernelGGL(k_halfstep<FUN>, dim3(nfb, G, 1), dim3(TTX_BLK), h->lds_half, st, Q, 0, dir, 3, 0);
-                        if (int rc_ = host_eval(h)) return rc_;
+                        if (int rc_ = slot_eval(h)) return rc_;
                         Q.hostpass = 2;
                         hipLaunchKernelGGL(k_halfstep<FUN>, dim3(nfb, G, 1), dim3(TTX_BLK), h->lds_half, st, Q, 0, dir, 3, 0);
                     }
@@ -1680,6 +1728,9 @@ extern "C" int ttx_run(ttx_engine *h)
         case TTX_FUN_STDNORM: return run_impl<FUN_STDNORM>(h);
         case TTX_FUN_HOST:
             if (!h->hfun) return fail(TTX_ESTATE, "ttx_run: call ttx_set_integrand_host first");
+            h->host_calls = 0;
+            return run_impl<FUN_HOST>(h);
+        case TTX_FUN_COSCOEFF:                  // the host integrand's two passes with the device evaluator between them (slot_eval)
             h->host_calls = 0;
             return run_impl<FUN_HOST>(h);
         default: return run_impl<FUN_MVN>(h);
@@ -2109,7 +2160,7 @@ static int accchk_impl(ttx_engine *h, int nlot, double *einf, double *efro, doub
             DevProb Q = P;
             Q.hostpass = 1;
             hipLaunchKernelGGL(k_accchk<FUN>, dim3(cnt), dim3(64), lds, h->stream, Q, (unsigned long long)g0s.rngpos, nlot, (const int *)downer, dout, dind, il0);
-            if (int rc_ = host_eval(h)) return rc_;
+            if (int rc_ = slot_eval(h)) return rc_;
             Q.hostpass = 2;
             hipLaunchKernelGGL(k_accchk<FUN>, dim3(cnt), dim3(64), lds, h->stream, Q, (unsigned long long)g0s.rngpos, nlot, (const int *)downer, dout, dind, il0);
         }
@@ -2149,6 +2200,7 @@ extern "C" int ttx_accchk(ttx_engine *h, int32_t nlot, double *einf, double *efr
         case TTX_FUN_HOST:
             if (!h->hfun) return fail(TTX_ESTATE, "dtt_accchk: call ttx_set_integrand_host first");
             return accchk_impl<FUN_HOST>(h, nlot, einf, efro, ainf, afro, pivot);
+        case TTX_FUN_COSCOEFF: return accchk_impl<FUN_HOST>(h, nlot, einf, efro, ainf, afro, pivot);
         default: return accchk_impl<FUN_MVN>(h, nlot, einf, efro, ainf, afro, pivot);
     }
 }
@@ -2840,6 +2892,30 @@ extern "C" int ttx_k_eval_arith(int32_t device, int32_t fun_id, int32_t d, const
 static int k_eval_impl(int32_t device, int32_t fun_id, int32_t d, const int32_t *n, const double *par, int32_t npar,
                        const double *aux, int32_t naux, int64_t npts, const int32_t *ind, double *out, int arith)
 {
+    if (fun_id != TTX_FUN_ISING && fun_id != TTX_FUN_STDNORM && fun_id != TTX_FUN_MVN && fun_id != TTX_FUN_COSCOEFF)
+        return fail(TTX_EINVAL, "ttx_k_eval: unknown fun_id %d", fun_id);
+    if (d < 1 || !n || npts < 0 || (npts > 0 && !ind) || (npts > 0 && !out)) return fail(TTX_EINVAL, "ttx_k_eval: bad arguments");
+    if (fun_id == TTX_FUN_COSCOEFF) {
+        if (int rc0 = coscoeff_check("ttx_k_eval", d, n, aux, naux)) return rc0;
+        for (int64_t p = 0; p < npts * d; p++)
+            if (ind[p] < 1 || ind[p] > n[p % d]) return fail(TTX_EINVAL, "ttx_k_eval: index %d outside 1..n", ind[p]);
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TTX_ENODEV, "no HIP device");
+        HIPCHECK(hipSetDevice(device));
+        if (npts == 0) return TTX_OK;
+        int *dind; double *daux, *dout;
+        HIPCHECK(hipMalloc((void **)&dind, sizeof(int) * npts * d)); HIPCHECK(hipMalloc((void **)&dout, sizeof(double) * npts));
+        HIPCHECK(hipMalloc((void **)&daux, sizeof(double) * naux));
+        HIPCHECK(hipMemcpy(dind, ind, sizeof(int) * npts * d, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(daux, aux, sizeof(double) * naux, hipMemcpyHostToDevice));
+        const unsigned grid = (unsigned)std::min<int64_t>((npts + TTX_CC_WAVES - 1) / TTX_CC_WAVES, 1024);
+        hipLaunchKernelGGL(k_coscoeff_list, dim3(grid), dim3(64 * TTX_CC_WAVES), sizeof(double) * TTX_CC_WAVES * TTX_CC_LDS(d), 0,
+                           d, (const double *)daux, (long long)npts, (const int *)dind, dout);
+        HIPCHECK(hipDeviceSynchronize());
+        HIPCHECK(hipMemcpy(out, dout, sizeof(double) * npts, hipMemcpyDeviceToHost));
+        (void)hipFree(dind); (void)hipFree(dout); (void)hipFree(daux);
+        return TTX_OK;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TTX_ENODEV, "no HIP device");
     HIPCHECK(hipSetDevice(device));

@@ -5,13 +5,14 @@ runs on the GPU through ttcross_amd.engine.  Usage:
     python -m ttcross_amd.drivers ising KIND INDEX N RANK PIV [NGROUPS]
     python -m ttcross_amd.drivers stdnorm D N RANK PIV [NGROUPS]
     python -m ttcross_amd.drivers mvn D N RANK PIV [NGROUPS]
+    python -m ttcross_amd.drivers coscoeff D N RANK PIV [NGROUPS]
 """
 import math
 import sys
 
 import numpy as np
 
-from .engine import TTX_FUN_ISING, TTX_FUN_MVN, TTX_FUN_STDNORM, TTCross
+from .engine import TTX_FUN_COSCOEFF, TTX_FUN_ISING, TTX_FUN_MVN, TTX_FUN_STDNORM, TTCross
 
 EPS = 2.220446049250313e-16
 TPI = 6.283185307179586476925286766559
@@ -95,8 +96,35 @@ def box_setup(kind, d, n):
                 fun_id=TTX_FUN_STDNORM if kind == "stdnorm" else TTX_FUN_MVN, aux=mvn_init(d) if kind == "mvn" else None)
 
 
+COS_A, COS_B = 0.525170185988090843, 8.52517018598809173     # test_crs_coscoeff.f90: init_coefficients(lower=, upper=)
+
+
+def coscoeff_setup(d, n, sigma=0.4, corr=0.5, X0=math.log(100.0), rate=0.0, T=1.0, a=COS_A, b=COS_B):
+    """test_crs_coscoeff.f90:75-168: the mean and covariance of the log-prices, [a, b], acc = 500 eps; the integrand is
+    calc_coefficient (TTX_FUN_COSCOEFF) with aux = [mu, Sigma column-major, a, b].  No quadrature: the driver keeps the train."""
+    if n % 2 == 0:
+        n += 1
+    mu = np.array([X0 + (rate - 0.5 * (sigma * sigma)) * T for _ in range(d)])
+    cov = np.empty((d, d))
+    for i in range(d):
+        for j in range(d):
+            cov[i, j] = (sigma * sigma) * T if i == j else ((sigma * corr) * sigma) * T
+    aux = np.concatenate([mu, cov.ravel(order="F"), [a, b]])
+    return dict(n=[n] * d, par=np.zeros(0), quad=None, tru=None, acc=500 * EPS, rescale=False, fun_id=TTX_FUN_COSCOEFF, aux=aux)
+
+
 def run_driver(argv, device=0, verbose=True):
     drv = argv[0]
+    if drv == "coscoeff":
+        m, n, r, piv = int(argv[1]), int(argv[2]), int(argv[3]), int(argv[4])
+        ng = int(argv[5]) if len(argv) > 5 else 1
+        s = coscoeff_setup(m, n)
+        tt = TTCross(s["n"], s["fun_id"], s["par"], r, pivoting=piv, accuracy=s["acc"], aux=s["aux"], nproc=ng, device=device,
+                     verbose=verbose)
+        tt.run()
+        if verbose:
+            print("...with%12d evaluations completed in %12.4E sec." % (tt.neval, tt.seconds))
+        return tt, None, s
     if drv == "ising":
         kind, m, n, r, piv = argv[1], int(argv[2]), int(argv[3]), int(argv[4]), int(argv[5])
         ng = int(argv[6]) if len(argv) > 6 else 1

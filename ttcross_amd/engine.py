@@ -13,6 +13,7 @@ from ctypes import POINTER, c_char_p, c_double, c_int32, c_int64, c_uint8, c_uin
 import numpy as np
 
 TTX_FUN_ISING, TTX_FUN_STDNORM, TTX_FUN_MVN, TTX_FUN_HOST = 1, 2, 3, 4
+TTX_FUN_COSCOEFF = 5       # calc_coefficient of test_crs_coscoeff.f90: aux = [mu, Sigma column-major, a, b], par unused
 K_NAMES = ("lottery", "halfstep", "accept", "exchange", "quad", "other")
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -313,6 +314,13 @@ class TTCross:
     @property
     def host_calls(self):
         return int(load_library().ttx_host_calls(self._h))
+
+    @property
+    def fun_id(self):
+        """TTX_FUN_* the engine was created with (include/ttx.h: ttx_fun_id)."""
+        L = load_library()
+        L.ttx_fun_id.argtypes = [c_void_p]
+        return L.ttx_fun_id(self._h)
 
     @property
     def arith(self):

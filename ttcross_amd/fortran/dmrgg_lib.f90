@@ -12,6 +12,18 @@ module dmrgg_lib
  use ttx_c
  implicit none
  private :: identify,ising_value,ttx_world,ttx_comm_init_file,ttx_comm_init_shm_env
+ ! recogniser of the COS-coefficient integrand, registered by coefficients_mod (init_coefficients); see identify_nopar
+ abstract interface
+  subroutine coscoeff_identify_if(fun,m,n,fid,aux)
+   import :: c_double
+   double precision,external :: fun
+   integer,intent(in) :: m,n(*)
+   integer,intent(out) :: fid
+   real(c_double),allocatable,intent(out) :: aux(:)
+  end subroutine
+ end interface
+ procedure(coscoeff_identify_if),pointer :: coscoeff_identify=>null()
+
 contains
  subroutine dtt_dmrgg(arg,fun,par,accuracy,maxrank,mybonds,pivoting,neval,quad,tru)
   type(dtt),intent(inout),target :: arg
@@ -38,7 +50,7 @@ contains
   if(present(par))then
    call identify(fun,m,arg%n,par,fid,npar,aux,pcopy)
   else
-   fid=TTX_FUN_HOST; npar=0
+   call identify_nopar(fun,m,arg%n,fid,aux); npar=0
   end if
   allocate(nn(m)); nn=arg%n(1:m)
   cfg%d=m; cfg%n=c_loc(nn); cfg%fun_id=fid; cfg%par=c_null_ptr; cfg%npar=npar
@@ -206,8 +218,9 @@ contains
     if(pick.lt.1.or.pick.gt.3)then;write(*,*)'dtt_dmrgg: TTX_INTEGRAND=ising needs par(2n+1) in 1..3';stop;endif
    case('stdnorm'); pick=4
    case('mvn'); pick=5
+   case('coscoeff'); call identify_nopar(fun,m,n,fid,aux); npar=0; return
    case('auto')
-   case default; write(*,*)'dtt_dmrgg: TTX_INTEGRAND must be auto, host, ising, stdnorm or mvn: ',trim(env); stop
+   case default; write(*,*)'dtt_dmrgg: TTX_INTEGRAND must be auto, host, ising, stdnorm, mvn or coscoeff: ',trim(env); stop
   end select
   if(pick.eq.0)then
    have=.true.; have(5)=allocated(mvn_data%mu).and.mvn_data%n.eq.m
@@ -252,6 +265,24 @@ contains
    case default
     fid=TTX_FUN_HOST; npar=0
   end select
+ end subroutine
+ subroutine identify_nopar(fun,m,n,fid,aux)
+  ! `fun` without par: the fork's calc_coefficient (test_crs_coscoeff.f90) is the one device integrand called that way.  Its
+  ! recogniser lives in coefficients_mod and registers itself here (coscoeff_identify) when init_coefficients runs, so this
+  ! module needs nothing of coefficients_mod at link time; without it every such `fun` is the user's own (host callback).
+  double precision,external :: fun
+  integer,intent(in) :: m,n(*)
+  integer,intent(out) :: fid
+  real(c_double),allocatable,intent(out) :: aux(:)
+  integer :: stat
+  character(len=32) :: env
+  fid=TTX_FUN_HOST
+  if(associated(coscoeff_identify))then
+   call coscoeff_identify(fun,m,n,fid,aux)
+  else
+   call get_environment_variable('TTX_INTEGRAND',env,status=stat)
+   if(stat.eq.0 .and. trim(env).eq.'coscoeff')then;write(*,*)'dtt_dmrgg: TTX_INTEGRAND=coscoeff needs init_coefficients';stop;endif
+  end if
  end subroutine
  double precision function ising_value(id,m,n1,ind,par) result(g)
   ! the Ising-class integrands on the node grid (test_crs_ising.f90:176-218), host arithmetic for the probe only

@@ -3,7 +3,7 @@
 module ttx_c
  use iso_c_binding
  implicit none
- integer(c_int32_t),parameter :: TTX_FUN_ISING=1, TTX_FUN_STDNORM=2, TTX_FUN_MVN=3, TTX_FUN_HOST=4
+ integer(c_int32_t),parameter :: TTX_FUN_ISING=1, TTX_FUN_STDNORM=2, TTX_FUN_MVN=3, TTX_FUN_HOST=4, TTX_FUN_COSCOEFF=5
  type,bind(C) :: ttx_config
   integer(c_int32_t) :: d
   type(c_ptr) :: n
