@@ -150,7 +150,8 @@ int ttx_accchk(ttx_engine *h, int32_t nlot, double *einf, double *efro, double *
  * multi-process engine are COLLECTIVE (ztt_quad folds per-process partial products, lib/dmrgg.f90:1418-1523; the others work on a
  * replica, ttx_replicate); ttx_ort / ttx_svd / ttx_ijk change or address single cores and take single-process engines (or a replica).
  * ttx_ort  : dtt_ort  (lib/tt.f90:130-198)  left-to-right Householder QR, in place
- * ttx_svd  : dtt_svd  (lib/tt.f90:307-368)  rounding: ort, then truncated SVD right-to-left; tol relative
+ * ttx_svd  : dtt_svd  (lib/tt.f90:307-368)  rounding: ort, then truncated SVD right-to-left; tol relative (>= 0; a NaN or negative
+ *            tol, or rmax < 0, is TTX_EINVAL; at tol >= 1 every rank stops at 1)
  *            (lib/mat.f90:433-458 chop), rmax <= 0: absent
  * ttx_norm : dtt_norm (lib/tt.f90:1074-1092) Frobenius norm, tol < 0: absent (the TT itself is left unchanged)
  * ttx_dot  : dtt_dot  (lib/tt.f90:1155-1175) scalar product of two resident TTs with equal mode sizes
@@ -158,6 +159,9 @@ int ttx_accchk(ttx_engine *h, int32_t nlot, double *einf, double *efro, double *
 int ttx_ort(ttx_engine *h);
 int ttx_svd(ttx_engine *h, double tol, int32_t rmax);
 int ttx_norm(ttx_engine *h, double tol, double *val);
+/* ttx_lognrm: dtt_lognrm (lib/tt.f90:1114-1132) log10 of the Frobenius norm, computed as d log10 of the norm of the core that carries
+ * it after the norm equalisation (tol < 0: absent, as ttx_norm) -- finite for trains whose norm lies outside the double range */
+int ttx_lognrm(ttx_engine *h, double tol, double *val);
 int ttx_dot(ttx_engine *hx, ttx_engine *hy, double *val);
 int ttx_ijk(ttx_engine *h, const int32_t *ind, double *val);
 /* ztt_quad (lib/dmrgg.f90:1418-1523) of the (real) resident TT with COMPLEX rank-1 weights, batched over nf weight

@@ -13,7 +13,22 @@
 #include <stdlib.h>
 #include <string.h>
 
-static double nrm2(size_t n, const double *x) { double s = 0.0; for (size_t i = 0; i < n; i++) s += x[i] * x[i]; return sqrt(s); }
+/* dnrm2: the plain sum of squares while it stays inside [1e-280, 1e280], the window of the device kernels (no square that
+ * matters can have over- or underflowed there); otherwise, as LAPACK's scaled dnrm2, again on x times the power of two that brings max |x| to
+ * [0.5, 1) -- an exact scaling, so the plain sum keeps its value bit for bit wherever it is used */
+static double nrm2(size_t n, const double *x)
+{
+    double s = 0.0;
+    for (size_t i = 0; i < n; i++) s += x[i] * x[i];
+    if (s > 1e-280 && s < 1e280) return sqrt(s);
+    double m = 0.0;
+    for (size_t i = 0; i < n; i++) if (fabs(x[i]) > m) m = fabs(x[i]);
+    if (m == 0.0 || !isfinite(m)) return sqrt(s);
+    int e; (void)frexp(m, &e);
+    s = 0.0;
+    for (size_t i = 0; i < n; i++) { const double y = ldexp(x[i], -e); s += y * y; }
+    return ldexp(sqrt(s), e);
+}
 
 /* dgeqr2: A (m x n, ld m) -> R in the upper triangle, reflectors below; tau[min(m,n)] */
 static void geqr2(int m, int n, double *a, double *tau)
@@ -73,7 +88,9 @@ static void jacobi_svd(int p, int q, double *x, double *s, double *v)
             for (int b = a + 1; b < q; b++) {
                 double *xa = x + (size_t)p * a, *xb = x + (size_t)p * b, al = 0, be = 0, ga = 0;
                 for (int i = 0; i < p; i++) { al += xa[i] * xa[i]; be += xb[i] * xb[i]; ga += xa[i] * xb[i]; }
-                if (fabs(ga) <= 1e-16 * sqrt(al * be) || ga == 0.0) continue;
+                /* al * be over- or underflows for columns beyond ~1e+-77: the square roots one at a time there */
+                const double ab = al * be, sab = (ab > 1e-280 && ab < 1e280) ? sqrt(ab) : sqrt(al) * sqrt(be);
+                if (fabs(ga) <= 1e-16 * sab || ga == 0.0) continue;
                 rot++;
                 double zeta = (be - al) / (2.0 * ga);
                 double t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
@@ -99,13 +116,19 @@ static void jacobi_svd(int p, int q, double *x, double *s, double *v)
 /* lib/mat.f90:433-458 */
 static int chop(int n, const double *s, int has_tol, double tol, int rmax, double *err)
 {
+    /* the squares are taken of s times a power of two that keeps them in range (1 for singular values in [1e-100, 1e100],
+     * where nothing changes); the rank never drops below 1 (lib/mat.f90 would read s(0) for tol >= 1) */
+    double sc = 1.0;
+    if (n > 0 && s[0] > 0.0 && (s[0] < 1e-100 || s[0] > 1e100)) { int e; (void)frexp(s[0], &e); sc = ldexp(1.0, -e); }
     int r = n; double er2 = 0.0;
-    if (rmax > 0 && rmax < r) { for (int i = rmax; i < r; i++) er2 += s[i] * s[i]; r = rmax; }
+    if (rmax > 0 && rmax < r) { for (int i = rmax; i < r; i++) er2 += (sc * s[i]) * (sc * s[i]); r = rmax; }
     if (has_tol) {
-        double nrm = nrm2((size_t)n, s), bound = tol * tol * nrm * nrm, er = er2 + s[r - 1] * s[r - 1];
-        while (er < bound) { er2 = er; r--; er = er + s[r - 1] * s[r - 1]; }
+        double nrm = 0.0; for (int i = 0; i < n; i++) nrm += (sc * s[i]) * (sc * s[i]);
+        nrm = sqrt(nrm);
+        double bound = tol * tol * nrm * nrm, er = er2 + (sc * s[r - 1]) * (sc * s[r - 1]);
+        while (r > 1 && er < bound) { er2 = er; r--; er = er + (sc * s[r - 1]) * (sc * s[r - 1]); }
     }
-    if (err) *err = sqrt(er2);
+    if (err) *err = sqrt(er2) / sc;
     return r;
 }
 

@@ -258,6 +258,8 @@ def test_fortran_tt_generics(tmp_path):
     nrm = elem * np.sqrt(120.0)
     assert abs(float(out["norm"][0]) - nrm) < 1e-5 and abs(float(out["lognrm"][0]) - np.log10(nrm)) < 1e-5
     assert abs(float(out["dot"][0]) - nrm ** 2) < 1e-4
+    # dtt_lognrm of a d = 40 rank-1 train with core norms 1e10 / 1e-10 (|b| = 1e+-400): d log10 of the core norm, as the reference
+    assert abs(float(out["lognrm_long"][0]) - 400.0) <= 1e-12 * 400 and abs(float(out["lognrm_long_small"][0]) + 400.0) <= 1e-12 * 400
     assert [int(v) for v in out["svd_ranks"]] == [1, 1, 1, 1, 1] and abs(float(out["svd_norm"][0]) - 2 * nrm) < 1e-5
     assert float(out["zeros_sumall"][0]) == 0.0 and abs(float(out["copy_sumall"][0]) - tot) < 1e-9
     assert float(out["matinv_err"][0]) < 1e-14 and float(out["svd_err"][0]) < 1e-13 and int(out["chop"][0]) == 2

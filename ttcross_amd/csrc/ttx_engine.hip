@@ -2366,13 +2366,30 @@ static int jacobi(ttx_engine *h, int p, int q, double *X, double *V, double *sv,
     hipLaunchKernelGGL(k_jacobi_svd, dim3(1), dim3(tt_threads("TTX_JAC_THREADS", 256)), in_lds ? lds : 0, h->stream, p, q, X, V, sv, perm, info, 1, tol, rmax, in_lds);
     return TTX_OK;
 }
-static int sumsq(ttx_engine *h, size_t n, const double *x, double *out_host)
+// ||x||_2 = sqrt(*s2) 2^*e (e = 0 unless the plain sum of squares left [1e-280, 1e280], ttx_ttops.h)
+static int sumsq(ttx_engine *h, size_t n, const double *x, double *s2, int *e)
 {
-    double *d = h->Sm + 8 * (size_t)h->RM * h->RM + 4 * h->RM;      // scratch scalar
+    double *d = h->Sm + 8 * (size_t)h->RM * h->RM + 4 * h->RM + 4;  // scratch scalars (acc of ort_impl: + 2, + 3)
+    double out[2];
     hipLaunchKernelGGL(k_sumsq, dim3(1), dim3(1024), 0, h->stream, n, x, d);
-    HIPCHECK(hipMemcpyAsync(out_host, d, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(out, d, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
+    *s2 = out[0]; *e = (int)out[1];
     return TTX_OK;
+}
+// sqrt(sum v[j]^2) on the host with the same rescaled second pass
+static double host_norm(const double *v, int n)
+{
+    double s2 = 0.0;
+    for (int j = 0; j < n; j++) s2 += v[j] * v[j];
+    if (s2 > 1e-280 && s2 < 1e280) return std::sqrt(s2);
+    double m = 0.0;
+    for (int j = 0; j < n; j++) m = std::max(m, std::fabs(v[j]));
+    if (m == 0.0 || !std::isfinite(m)) return std::sqrt(s2);
+    int e; (void)std::frexp(m, &e);
+    double p = 0.0;
+    for (int j = 0; j < n; j++) { const double y = std::ldexp(v[j], -e); p += y * y; }
+    return std::ldexp(std::sqrt(p), e);
 }
 
 static int ort_impl(ttx_engine *h)
@@ -2410,7 +2427,7 @@ static int ort_impl(ttx_engine *h)
 // rank, Jacobi sweeps and singular values of the core just decomposed: written by the device into pinned memory, polled here
 static int svd_fetch(ttx_engine *h, const double *sv, const int *info, int q, int *inf2, double *svh)
 {
-    if (!h->h_svd) HIPCHECK(hipHostMalloc((void **)&h->h_svd, sizeof(double) * ((size_t)h->RM + 8)));
+    if (!h->h_svd) { HIPCHECK(hipHostMalloc((void **)&h->h_svd, sizeof(double) * ((size_t)h->RM + 8))); h->h_svd[0] = 0.0; }
     if (getenv("TTX_SVD_POLL") && atoi(getenv("TTX_SVD_POLL")) == 0) {
         HIPCHECK(hipMemcpyAsync(inf2, info, sizeof(int) * 2, hipMemcpyDeviceToHost, h->stream));
         HIPCHECK(hipMemcpyAsync(svh, sv, sizeof(double) * q, hipMemcpyDeviceToHost, h->stream));
@@ -2419,12 +2436,17 @@ static int svd_fetch(ttx_engine *h, const double *sv, const int *info, int q, in
     }
     h->svd_seq += 1.0;
     hipLaunchKernelGGL(k_svd_report, dim3(1), dim3(64), 0, h->stream, sv, info, q, (volatile double *)h->h_svd, h->svd_seq);
+    HIPCHECK(hipGetLastError());
     volatile double *hv = h->h_svd;
     const auto t0 = std::chrono::steady_clock::now();
     unsigned spins = 0;
     while (hv[0] != h->svd_seq) {
         if ((++spins & 0xfff) == 0) {
-            if (hipStreamQuery(h->stream) == hipSuccess && hv[0] != h->svd_seq) { HIPCHECK(hipStreamSynchronize(h->stream)); break; }   // (kernel failed to launch: do not spin for ever)
+            if (hipStreamQuery(h->stream) == hipSuccess && hv[0] != h->svd_seq) {                   // (kernel failed to launch: do not spin for ever)
+                HIPCHECK(hipStreamSynchronize(h->stream));
+                if (hv[0] != h->svd_seq) return fail(TTX_EHIP, "dtt_svd: the device never reported rank and singular values");
+                break;
+            }
             if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 30.0) return fail(TTX_EHIP, "dtt_svd: no report from the device within 30 s");
         }
     }
@@ -2444,6 +2466,7 @@ static int svd_impl(ttx_engine *h, double tol, int rmax)
     double *tau = h->Sm + 8 * (size_t)RM * RM, *sv = tau + RM;
     int *perm = h->Si, *info = h->Si + RM;
     double lognrm = 0.0, s2;
+    int e2 = 0;
     std::vector<double> svh(RM);
     for (int k = d; k >= 2; k--) {                                      // lib/tt.f90:329-356
         const int mm = r[k - 1], n = h->n1[k], nn = n * r[k], kk = r[k - 2] * h->n1[k - 1];
@@ -2456,8 +2479,7 @@ static int svd_impl(ttx_engine *h, double tol, int rmax)
             int inf2[2];
             if ((rc = svd_fetch(h, sv, info, nn, inf2, svh.data()))) return rc;
             const int rr = inf2[0];
-            s2 = 0.0; for (int j = 0; j < rr; j++) s2 += svh[j] * svh[j];
-            const double nrm = std::sqrt(s2);
+            const double nrm = host_norm(svh.data(), rr);
             if (nrm != 0.0) lognrm += std::log(nrm);
             hipLaunchKernelGGL(k_take_cols, g1((size_t)nn * rr), dim3(256), 0, h->stream, nn, rr, Rm, nn, perm, sv, nrm != 0.0 ? 1.0 / nrm : 1.0, US);
             gemm(h, mm, rr, nn, h->Wa, mm, US, nn, h->Wd, mm);          // Q Ub S  (mm x rr)
@@ -2478,8 +2500,7 @@ static int svd_impl(ttx_engine *h, double tol, int rmax)
         if ((rc = svd_fetch(h, sv, info, mm, inf, svh.data()))) return rc;
         const int rr = inf[0];
         if (getenv("TTX_JAC_TRACE")) fprintf(stderr, "svd core %d: %d x %d, %d Jacobi sweeps, rank %d\n", k, mm, mm, inf[1], rr);
-        s2 = 0.0; for (int j = 0; j < rr; j++) s2 += svh[j] * svh[j];
-        const double nrm = std::sqrt(s2);
+        const double nrm = host_norm(svh.data(), rr);
         if (nrm != 0.0) lognrm += std::log(nrm);
         hipLaunchKernelGGL(k_take_cols, g1((size_t)mm * rr), dim3(256), 0, h->stream, mm, rr, Rt, mm, perm, sv, nrm != 0.0 ? 1.0 / nrm : 1.0, US);
         hipLaunchKernelGGL(k_pack_core, g1((size_t)kk * mm), dim3(256), 0, h->stream, core_dev(h, k - 1), h->Wb, r[k - 2], h->n1[k - 1], mm, RM, SS, 0);
@@ -2492,8 +2513,8 @@ static int svd_impl(ttx_engine *h, double tol, int rmax)
     }
     const size_t first = (size_t)r[0] * h->n1[1] * r[1];
     hipLaunchKernelGGL(k_pack_core, g1(first), dim3(256), 0, h->stream, core_dev(h, 1), h->Wa, r[0], h->n1[1], r[1], RM, SS, 0);
-    if ((rc = sumsq(h, first, h->Wa, &s2))) return rc;
-    double nf = std::sqrt(s2), firstscale = 1.0;
+    if ((rc = sumsq(h, first, h->Wa, &s2, &e2))) return rc;
+    double nf = std::ldexp(std::sqrt(s2), e2), firstscale = 1.0;
     if (nf != 0.0) { firstscale = 1.0 / nf; lognrm += std::log(nf); }
     lognrm /= d;
     const double nrm = std::exp(lognrm);
@@ -2508,37 +2529,57 @@ static int svd_impl(ttx_engine *h, double tol, int rmax)
 // (ort / svd change the train in place: on a multi-process engine that would mean redistributing cores whose ranks have changed;
 //  take a replica with ttx_replicate and work on that)
 extern "C" int ttx_ort(ttx_engine *h) { int rc = tt_prepare(h, "dtt_ort"); return rc ? rc : ort_impl(h); }
-extern "C" int ttx_svd(ttx_engine *h, double tol, int32_t rmax) { int rc = tt_prepare(h, "dtt_svd"); return rc ? rc : svd_impl(h, tol, rmax); }
-
-extern "C" int ttx_norm(ttx_engine *h, double tol, double *val)
+extern "C" int ttx_svd(ttx_engine *h, double tol, int32_t rmax)
 {
-    if (h && h->ran && h->W > 1) return with_replica(h, [&](ttx_engine *e) { return ttx_norm(e, tol, val); });
-    int rc = tt_prepare(h, "dtt_norm");
+    if (!(tol >= 0.0)) return fail(TTX_EINVAL, "dtt_svd: tol must be a number >= 0 (got %g)", tol);
+    if (rmax < 0) return fail(TTX_EINVAL, "dtt_svd: rmax must be >= 0 (0: absent; got %d)", (int)rmax);
+    int rc = tt_prepare(h, "dtt_svd");
+    return rc ? rc : svd_impl(h, tol, rmax);
+}
+
+// dtt_norm / dtt_lognrm: the norm of the core that carries it after svd (tol >= 0) or ort (tol < 0), as sqrt(*s2) 2^*e
+static int core_norm_impl(ttx_engine *h, double tol, double *s2_out, int *e_out, const char *who)
+{
+    int rc = tt_prepare(h, who);
     if (rc) return rc;
-    if (!val) return fail(TTX_EINVAL, "dtt_norm: null result");
     // the reference works on a copy (tmp = arg, lib/tt.f90:1082): back the cores and ranks up, restore afterwards
     const size_t tot = (size_t)h->G * h->NC * h->P.CS;
     if (!h->bak) { if ((rc = dev_alloc(h, &h->bak, tot))) return rc; }
     HIPCHECK(hipMemcpyAsync(h->bak, h->P.arg, sizeof(double) * tot, hipMemcpyDeviceToDevice, h->stream));
     std::vector<int32_t> rsave = h->rfinal;
     const int d = h->d;
-    double s2 = 0.0;
     if (tol >= 0.0) {
         rc = svd_impl(h, tol, 0);
         if (!rc) { const size_t sz = (size_t)h->rfinal[0] * h->n1[1] * h->rfinal[1];
                    hipLaunchKernelGGL(k_pack_core, g1(sz), dim3(256), 0, h->stream, core_dev(h, 1), h->Wa, h->rfinal[0], h->n1[1], h->rfinal[1], h->RM, h->P.SS, 0);
-                   rc = sumsq(h, sz, h->Wa, &s2); }
+                   rc = sumsq(h, sz, h->Wa, s2_out, e_out); }
     } else {
         rc = ort_impl(h);
         if (!rc) { const size_t sz = (size_t)h->rfinal[d - 1] * h->n1[d] * h->rfinal[d];
                    hipLaunchKernelGGL(k_pack_core, g1(sz), dim3(256), 0, h->stream, core_dev(h, d), h->Wa, h->rfinal[d - 1], h->n1[d], h->rfinal[d], h->RM, h->P.SS, 0);
-                   rc = sumsq(h, sz, h->Wa, &s2); }
+                   rc = sumsq(h, sz, h->Wa, s2_out, e_out); }
     }
     HIPCHECK(hipMemcpyAsync(h->P.arg, h->bak, sizeof(double) * tot, hipMemcpyDeviceToDevice, h->stream));
     h->rfinal = rsave;
     push_ranks(h);
-    if (rc) return rc;
-    *val = std::pow(std::sqrt(s2), d);                                  // :1089
+    return rc;
+}
+extern "C" int ttx_norm(ttx_engine *h, double tol, double *val)
+{
+    if (h && h->ran && h->W > 1) return with_replica(h, [&](ttx_engine *e) { return ttx_norm(e, tol, val); });
+    if (!val) return fail(TTX_EINVAL, "dtt_norm: null result");
+    double s2 = 0.0; int e = 0;
+    if (int rc = core_norm_impl(h, tol, &s2, &e, "dtt_norm")) return rc;
+    *val = std::pow(std::ldexp(std::sqrt(s2), e), h->d);               // :1089
+    return TTX_OK;
+}
+extern "C" int ttx_lognrm(ttx_engine *h, double tol, double *val)
+{
+    if (h && h->ran && h->W > 1) return with_replica(h, [&](ttx_engine *e) { return ttx_lognrm(e, tol, val); });
+    if (!val) return fail(TTX_EINVAL, "dtt_lognrm: null result");
+    double s2 = 0.0; int e = 0;
+    if (int rc = core_norm_impl(h, tol, &s2, &e, "dtt_lognrm")) return rc;
+    *val = ((0.5 * std::log(s2) + e * std::log(2.0)) / std::log(10.0)) * h->d;    // :1114-1132, d log10 of the core's norm
     return TTX_OK;
 }
 

@@ -42,6 +42,48 @@ __device__ __forceinline__ double tt_block_sum(double v, double *sh)
     return r;
 }
 
+__device__ __forceinline__ double tt_block_max(double v, double *sh)
+{
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[w] = v;
+    __syncthreads();
+    double r = 0.0;
+    for (int x = 0; x < nw; x++) r = fmax(r, sh[x]);
+    return r;
+}
+// Scale: a plain sum of squares is used while it lies inside [1e-280, 1e280] -- no square that matters can have
+// over- or underflowed there.  Outside, the sum is taken again of x * 2^-e, 2^e the power of two just above max |x| (LAPACK's
+// dnrm2 scales the same way), and the norm is sqrt(sum) * 2^e.  A power of two is exact, so the plain path and every result on
+// trains of ordinary range stay bit for bit what they were; only the out-of-range cases pay for the second pass.
+__device__ __forceinline__ bool tt_sumsq_in_range(double s) { return s > 1e-280 && s < 1e280; }
+__device__ __forceinline__ int tt_pow2_above(double m) { int e = 0; if (m > 0.0 && m <= 1.7976931348623157e308) (void)frexp(m, &e); return e; }
+// the norm of x[0..len) with the rescaled second pass, one workgroup (every thread returns it); sh: 16 doubles
+__device__ __forceinline__ double tt_block_norm_scaled(const double *x, size_t len, double *sh, int *e_out)
+{
+    double m = 0.0;
+    for (size_t i = threadIdx.x; i < len; i += blockDim.x) m = fmax(m, fabs(x[i]));
+    const int e = tt_pow2_above(tt_block_max(m, sh));
+    double p = 0.0;
+    for (size_t i = threadIdx.x; i < len; i += blockDim.x) { const double y = ldexp(x[i], -e); p += y * y; }
+    p = tt_block_sum(p, sh);
+    if (e_out) *e_out = e;
+    return ldexp(sqrt(p), e);
+}
+// the same for one wave over x[0..len) (stride 1)
+__device__ __forceinline__ double tt_wave_norm_scaled(const double *x, int len, int lane)
+{
+    double m = 0.0;
+    for (int i = lane; i < len; i += 64) m = fmax(m, fabs(x[i]));
+    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+    const int e = tt_pow2_above(m);
+    double p = 0.0;
+    for (int i = lane; i < len; i += 64) { const double y = ldexp(x[i], -e); p += y * y; }
+    for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
+    return ldexp(sqrt(p), e);
+}
+
 // Householder QR of A (m x n, compact, in place), LAPACK dgeqr2 / dlarfg / dlarf then dorg2r, one 1024-thread
 // workgroup: the reflector lives in LDS; Rout (mn x n) gets the upper trapezoid (zeros below the diagonal); on exit A
 // holds the first mn columns of Q.
@@ -132,14 +174,19 @@ __device__ __forceinline__ void qr_lds3(double *A, int m, int n, double *vsh, do
     for (int i = 0; i < mn; i++) {
         double *x = A + i + (size_t)m * i;
         const int len = m - i;
-        if (tid == 0) {
-            const double alpha = x[0], xn = sqrt(s_xn2);
-            if (xn == 0.0) { s_tau = 0.0; s_beta = alpha; s_scale = 0.0; }
-            else {
-                const double beta = -copysign(hypot(alpha, xn), alpha);
-                s_tau = (beta - alpha) / beta; s_beta = beta; s_scale = 1.0 / (alpha - beta);
+        if (wv == 0) {
+            const double xn2 = s_xn2;
+            double xn = sqrt(xn2);
+            if (!tt_sumsq_in_range(xn2)) xn = tt_wave_norm_scaled(x + 1, len - 1, lane);     // (wave-uniform branch)
+            if (lane == 0) {
+                const double alpha = x[0];
+                if (xn == 0.0) { s_tau = 0.0; s_beta = alpha; s_scale = 0.0; }
+                else {
+                    const double beta = -copysign(hypot(alpha, xn), alpha);
+                    s_tau = (beta - alpha) / beta; s_beta = beta; s_scale = 1.0 / (alpha - beta);
+                }
+                tauv[i] = s_tau;
             }
-            tauv[i] = s_tau;
         }
         __syncthreads();                                                                        // (1) tau, beta, scale
         const double sc = s_scale, tau = s_tau;
@@ -240,9 +287,25 @@ __global__ __launch_bounds__(1024) void k_qr_own(int rows, int n, int rbs, const
                                                   (unsigned int)__builtin_amdgcn_readlane((int)cb, al_lane));
         const double xn2 = jac_group_sum(q, 64, lane);
         double tau = 0.0, beta = alpha, sc = 0.0;
-        if (xn2 != 0.0) {
-            const double s2 = alpha * alpha + xn2;
-            const double nrm = (s2 > 1e-280 && s2 < 1e280) ? sqrt(s2) : hypot(alpha, sqrt(xn2));
+        const double s2 = alpha * alpha + xn2;
+        double nrm = 0.0;
+        if (xn2 != 0.0 && s2 > 1e-280 && s2 < 1e280) nrm = sqrt(s2);
+        else if (i + 1 < m) {
+            // a column beyond the range of plain squares (or one whose squares all underflowed): dlapy2 of alpha and the norm of
+            // the rescaled second pass (wave-uniform branch, off the path that ordinary trains take)
+            double mx = 0.0;
+#pragma unroll
+            for (int j = 0; j < MR; j++) { const int r = lane + 64 * j; if (r > i) mx = fmax(mx, fabs(col[j])); }
+            for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+            const int e = tt_pow2_above(mx);
+            double p = 0.0;
+#pragma unroll
+            for (int j = 0; j < MR; j++) { const int r = lane + 64 * j; if (r > i) { const double y = ldexp(col[j], -e); p += y * y; } }
+            for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
+            const double xn = ldexp(sqrt(p), e);
+            if (xn != 0.0) nrm = hypot(alpha, xn);
+        }
+        if (nrm != 0.0) {
             beta = -copysign(nrm, alpha);
             tau = (beta - alpha) / beta; sc = 1.0 / (alpha - beta);
         }
@@ -350,8 +413,10 @@ __global__ __launch_bounds__(1024) void k_qr(int m, int n, double *Ag, double *R
         double p = 0.0;
         for (int r = 1 + tid; r < len; r += nt) p += x[r] * x[r];
         const double xn2 = tt_block_sum(p, red);
+        double xn = sqrt(xn2);
+        if (!tt_sumsq_in_range(xn2)) xn = tt_block_norm_scaled(x + 1, (size_t)(len - 1), red, nullptr);   // (uniform branch)
         if (tid == 0) {
-            const double alpha = x[0], xn = sqrt(xn2);
+            const double alpha = x[0];
             if (xn == 0.0) { s_tau = 0.0; s_beta = alpha; s_scale = 0.0; }
             else {
                 const double beta = -copysign(hypot(alpha, xn), alpha);
@@ -459,14 +524,23 @@ __global__ __launch_bounds__(256) void k_gemm_mfma(int M, int N, int K, const do
     }
 }
 
-// ||x||_2^2 of n doubles -> out[0] (single block)
+// ||x||_2^2 of n doubles -> out[0] (single block); out[1] = e: the norm is sqrt(out[0]) 2^e (e = 0 while the plain sum is in range)
 __global__ __launch_bounds__(1024) void k_sumsq(size_t n, const double *x, double *out)
 {
     __shared__ double red[16];
     double p = 0.0;
     for (size_t i = threadIdx.x; i < n; i += blockDim.x) p += x[i] * x[i];
     p = tt_block_sum(p, red);
-    if (threadIdx.x == 0) out[0] = p;
+    int e = 0;
+    if (!tt_sumsq_in_range(p)) {
+        double m = 0.0;
+        for (size_t i = threadIdx.x; i < n; i += blockDim.x) m = fmax(m, fabs(x[i]));
+        e = tt_pow2_above(tt_block_max(m, red));
+        p = 0.0;
+        for (size_t i = threadIdx.x; i < n; i += blockDim.x) { const double y = ldexp(x[i], -e); p += y * y; }
+        p = tt_block_sum(p, red);
+    }
+    if (threadIdx.x == 0) { out[0] = p; out[1] = (double)e; }
 }
 // norm equalisation of dtt_ort without a host round trip (lib/tt.f90:166-172, 184-188): nrm = ||x||_2; x *= 1/nrm;
 // acc[0] += log(nrm).  scale_x = 0: x is left alone and 1/nrm is kept in acc[1] (the last core, scaled at the end).
@@ -477,8 +551,8 @@ __global__ __launch_bounds__(1024) void k_norm_log(size_t n, double *x, double *
     double p = 0.0;
     for (size_t i = threadIdx.x; i < n; i += blockDim.x) p += x[i] * x[i];
     p = tt_block_sum(p, red);
+    const double nrm = tt_sumsq_in_range(p) ? sqrt(p) : tt_block_norm_scaled(x, n, red, nullptr);
     if (threadIdx.x == 0) {
-        const double nrm = sqrt(p);
         s_inv = (nrm != 0.0) ? 1.0 / nrm : 1.0;
         if (nrm != 0.0) acc[0] += log(nrm);
         if (!scale_x) acc[1] = s_inv;
@@ -539,6 +613,8 @@ __device__ __forceinline__ double jac_group_sum(double v, int tpp, int lane)
     v = v + dpp_d<0x143, 0xc>(v);                          // rows 2 and 3: + the first half
     return readlane63(v);
 }
+__device__ __noinline__ bool jac_orth_scaled(double al, double be, double ga, double jtol) { return fabs(ga) <= jtol * sqrt(al) * sqrt(be); }
+__device__ __noinline__ double jac_tan_scaled(double dd, double g2) { return (dd >= 0.0 ? g2 : -g2) / (fabs(dd) + hypot(dd, g2)); }
 // in_lds: X and V live in dynamic LDS ((p + q) q doubles) for the whole iteration -- a rotation round is a dependent chain of
 // column reads, a reduction and column writes, ~3.5 us per round out of L2 (0.9 ms for a 32 x 32 matrix), a tenth of that in LDS
 __global__ __launch_bounds__(1024) void k_jacobi_svd(int p, int q, double *Xg, double *Vg, double *sout, int *perm, int *info,
@@ -586,12 +662,21 @@ __global__ __launch_bounds__(1024) void k_jacobi_svd(int p, int q, double *Xg, d
                         // the test and the rotation with three long operations (sqrt, division, rsqrt) in the dependent chain of a round
                         // instead of six: t = tan of the rotation angle, the smaller root of t^2 + 2 zeta t - 1 = 0 with
                         // zeta = (be - al) / (2 ga), written without forming zeta
+                        // columns whose squared norms leave [1e-100, 1e150] (al * be, dd^2 or ga^2 could over- or underflow): the test
+                        // with the square roots one at a time and the rotation through hypot -- for a uniformly tiny matrix both sides
+                        // of ga^2 <= jtol^2 al be underflow to 0 and no pair would ever rotate
+                        // (out of line, so that the compiler does not speculate them into every round's dependent chain)
                         const double ab = al * be;
-                        const bool orth = (ab < 1e300) ? (ga * ga <= jtol * jtol * ab) : (fabs(ga) <= jtol * sqrt(al) * sqrt(be));
+                        const bool safe = fmax(al, be) < 1e150 && fmin(al, be) > 1e-100;
+                        bool orth;
+                        if (safe) orth = ga * ga <= jtol * jtol * ab;
+                        else orth = jac_orth_scaled(al, be, ga, jtol);
                         if (!(orth || ga == 0.0)) {
                             if (sub == 0) atomicAdd(&s_rot, 1);
                             const double dd = be - al, g2 = 2.0 * ga;
-                            const double t = (dd >= 0.0 ? g2 : -g2) / (fabs(dd) + sqrt(dd * dd + g2 * g2));
+                            double t;
+                            if (safe) t = (dd >= 0.0 ? g2 : -g2) / (fabs(dd) + sqrt(dd * dd + g2 * g2));
+                            else t = jac_tan_scaled(dd, g2);
                             const double c = rsqrt(1.0 + t * t), sn = c * t;
                             for (int i = sub; i < p; i += tpp) { double u = xa[i], w = xb[i]; xa[i] = c * u - sn * w; xb[i] = sn * u + c * w; }
                             double *va = V + (size_t)q * a, *vb = V + (size_t)q * b;
@@ -611,7 +696,7 @@ __global__ __launch_bounds__(1024) void k_jacobi_svd(int p, int q, double *Xg, d
         double *xj = X + (size_t)p * j; double s2 = 0.0;
         for (int i = tid & 63; i < p; i += 64) s2 += xj[i] * xj[i];
         for (int o = 32; o > 0; o >>= 1) s2 += __shfl_xor(s2, o, 64);
-        const double s = sqrt(s2);
+        const double s = tt_sumsq_in_range(s2) ? sqrt(s2) : tt_wave_norm_scaled(xj, p, tid & 63);
         if ((tid & 63) == 0) ssh[j] = s;
         if (s > 0.0) for (int i = tid & 63; i < p; i += 64) xj[i] /= s;
     }
@@ -628,14 +713,17 @@ __global__ __launch_bounds__(1024) void k_jacobi_svd(int p, int q, double *Xg, d
             int t = psh[j]; psh[j] = psh[mx]; psh[mx] = t;
         }
         for (int j = 0; j < q; j++) { perm[j] = psh[j]; sout[j] = ssh[psh[j]]; }
-        // chop (lib/mat.f90:433-458)
+        // chop (lib/mat.f90:433-458) on the singular values times a power of two that keeps their squares in range (1 for a
+        // largest one in [1e-100, 1e100]); the rank stops at 1 (the reference would read before the spectrum at tol >= 1)
+        const double s0 = q > 0 ? sout[0] : 0.0;
+        const double sc = (s0 > 0.0 && (s0 < 1e-100 || s0 > 1e100)) ? ldexp(1.0, -tt_pow2_above(s0)) : 1.0;
         int r = q; double er2 = 0.0;
-        if (rmax > 0 && rmax < r) { for (int i = rmax; i < r; i++) er2 += sout[i] * sout[i]; r = rmax; }
+        if (rmax > 0 && rmax < r) { for (int i = rmax; i < r; i++) er2 += (sc * sout[i]) * (sc * sout[i]); r = rmax; }
         if (has_tol) {
-            double nrm = 0.0; for (int i = 0; i < q; i++) nrm += sout[i] * sout[i];
+            double nrm = 0.0; for (int i = 0; i < q; i++) nrm += (sc * sout[i]) * (sc * sout[i]);
             const double bound = tol * tol * nrm;
-            double er = er2 + sout[r - 1] * sout[r - 1];
-            while (er < bound) { er2 = er; r--; er = er + sout[r - 1] * sout[r - 1]; }
+            double er = er2 + (sc * sout[r - 1]) * (sc * sout[r - 1]);
+            while (r > 1 && er < bound) { er2 = er; r--; er = er + (sc * sout[r - 1]) * (sc * sout[r - 1]); }
         }
         info[0] = r; info[1] = sweeps;
     }

@@ -87,6 +87,7 @@ def load_library():
     L.ttx_ort.argtypes = [c_void_p]
     L.ttx_svd.argtypes = [c_void_p, c_double, c_int32]
     L.ttx_norm.argtypes = [c_void_p, c_double, POINTER(c_double)]
+    L.ttx_lognrm.argtypes = [c_void_p, c_double, POINTER(c_double)]
     L.ttx_dot.argtypes = [c_void_p, c_void_p, POINTER(c_double)]
     L.ttx_ijk.argtypes = [c_void_p, POINTER(c_int32), POINTER(c_double)]
     L.ttx_zquad.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
@@ -424,6 +425,12 @@ class TTCross:
     def norm(self, tol=None):
         v = c_double()
         _check(load_library().ttx_norm(self._h, -1.0 if tol is None else float(tol), ctypes.byref(v)))
+        return v.value
+
+    def lognorm(self, tol=None):
+        """dtt_lognrm: log10 of the norm, finite where norm() over- or underflows"""
+        v = c_double()
+        _check(load_library().ttx_lognrm(self._h, -1.0 if tol is None else float(tol), ctypes.byref(v)))
         return v.value
 
     def dot(self, other):

@@ -36,6 +36,11 @@ program main
  write(*,'(a,f14.6)') 'norm ',nrm
  write(*,'(a,f14.6)') 'lognrm ',lognrm(a)
  write(*,'(a,f14.6)') 'dot ',dot_product(a,a)
+ b%l=1; b%m=40; b%n(1:40)=3; call ones(b)   ! d = 40, every core of norm 1e10 (then 1e-10): |b| = 1e+-400, beyond the double range
+ do k=1,40; b%u(k)%p=1.d10/sqrt(3.d0); end do
+ write(*,'(a,es24.16)') 'lognrm_long ',lognrm(b)
+ do k=1,40; b%u(k)%p=1.d-10/sqrt(3.d0); end do
+ write(*,'(a,es24.16)') 'lognrm_long_small ',lognrm(b)
  c=a+a
  call svd(c,1.d-12)                    ! rounding of a+a on the device: ranks back to 1
  write(*,'(a,5i3)') 'svd_ranks ',c%r(0:4)

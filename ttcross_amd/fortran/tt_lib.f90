@@ -221,10 +221,16 @@ contains
   if(temp)call ttx_destroy(h)
  end function
  double precision function dtt_lognrm(arg,tol) result(nrm)
-  ! lib/tt.f90:1114: log10 of the Frobenius norm
+  ! lib/tt.f90:1114: log10 of the Frobenius norm as d log10 of the equalised core norm (finite beyond the double range)
+  use ttx_c
   type(dtt),intent(in) :: arg
   double precision,intent(in),optional :: tol
-  nrm=log10(dtt_norm(arg,tol))
+  real(c_double) :: t
+  type(c_ptr) :: h
+  logical :: temp
+  t=-1.d0; if(present(tol))t=tol
+  call dtt_stage(arg,h,temp,'dtt_lognrm'); call ttx_check(ttx_lognrm(h,t,nrm),'dtt_lognrm')
+  if(temp)call ttx_destroy(h)
  end function
  double precision function dtt_dot(x,y) result(dot)
   use ttx_c

@@ -87,6 +87,9 @@ module ttx_c
   function ttx_norm(h,tol,val) bind(C,name='ttx_norm') result(rc)
    import; type(c_ptr),value :: h; real(c_double),value :: tol; real(c_double),intent(out) :: val; integer(c_int) :: rc
   end function
+  function ttx_lognrm(h,tol,val) bind(C,name='ttx_lognrm') result(rc)
+   import; type(c_ptr),value :: h; real(c_double),value :: tol; real(c_double),intent(out) :: val; integer(c_int) :: rc
+  end function
   function ttx_dot(hx,hy,val) bind(C,name='ttx_dot') result(rc)
    import; type(c_ptr),value :: hx,hy; real(c_double),intent(out) :: val; integer(c_int) :: rc
   end function
