@@ -25,8 +25,9 @@ extern "C" {
 #define TTX_EHIP 3     /* HIP / RCCL runtime error                                                       */
 #define TTX_ESTATE 4   /* call out of order                                                              */
 
-/* built-in integrands (device code).  A user `fun` of the reference (lib/dmrgg.f90:18) cannot run on the
- * GPU; the drivers' integrands are provided natively and selected by id. */
+/* integrands.  The drivers' integrands are built in (device code) and selected by id; a user `fun` of the
+ * reference (lib/dmrgg.f90:18) runs either on the host through a callback (TTX_FUN_HOST) or on the GPU, written as a HIP
+ * __device__ function against include/ttx_device_fun.h and loaded as a code object (TTX_FUN_DEVICE). */
 #define TTX_FUN_ISING 1    /* dfunc_ising_discr, test_crs_ising.f90:176-218 (par(2n+1) = 1/2/3 -> C/D/E) */
 #define TTX_FUN_STDNORM 2  /* integrand, test_crs_stdnorm.f90:154-170                                     */
 #define TTX_FUN_MVN 3      /* integrand -> mvn_pdf, test_crs_mvn.f90:156-172, lib/mvn_pdf.f90:63-83       */
@@ -36,6 +37,7 @@ extern "C" {
  * (TTX_EINVAL) a wrong naux, non-finite aux, a >= b, d > 20, and problems whose bound on |t'mu| or |a sum t| over the index
  * box exceeds the range of the integrand's own sin / cos (2^19).  Mode sizes may differ.  TTX_ARITH=fast leaves it exact. */
 #define TTX_FUN_COSCOEFF 5
+#define TTX_FUN_DEVICE 6   /* any user `fun`, evaluated on the DEVICE by a code object the caller supplies: ttx_set_integrand_device */
 
 #define TTX_ARITH_EXACT 0
 #define TTX_ARITH_FAST 1
@@ -82,7 +84,7 @@ typedef struct ttx_sweep_rec {
 } ttx_sweep_rec;
 
 const char *ttx_last_error(void);
-int ttx_version(void);
+int ttx_version(void);   /* 2: TTX_FUN_DEVICE and the three entry points of loadable device integrands */
 
 /* allocate device state for one dtt_dmrgg problem (replaces the implicit set-up of lib/dmrgg.f90:58-148) */
 int ttx_create(ttx_engine **out, const ttx_config *cfg);
@@ -122,6 +124,27 @@ typedef double (*ttx_host_fun)(const int32_t *m, const int32_t *ind, const int32
  * Fortran dtt_accchk does, with the fun / par it was given: lib/dmrgg.f90:1081 checks against ITS arguments). */
 int ttx_set_integrand_host(ttx_engine *h, ttx_host_fun fun, const double *par);
 int64_t ttx_host_calls(const ttx_engine *h);                      /* calls of `fun` made by the last ttx_run */
+
+/* The user's `fun` on the DEVICE, for an engine created with fun_id = TTX_FUN_DEVICE (ttx_config.par / npar are not used by it).
+ * The integrand is a __device__ function turned into kernels by TTX_DEVICE_INTEGRAND(name) / TTX_DEVICE_INTEGRAND_WAVE(name) of
+ * include/ttx_device_fun.h and compiled with `hipcc --genco --offload-arch=gfx950 -O3 -ffp-contract=off`.  The sweep is the one
+ * of TTX_FUN_HOST -- every evaluating kernel runs in two passes -- but between the passes the integrand's slot kernel runs on the
+ * engine's stream: no value crosses to the host, ttx_host_calls stays 0, nothing is synchronised.
+ *   image, nbytes : the code object in memory, whatever hipModuleLoadData accepts (a gfx950 ELF or the offload bundle hipcc
+ *                   --genco writes); the engine keeps its own copy
+ *   name          : the integrand's name as given to the header macro (one code object may hold several)
+ *   par(1:npar)   : the caller's parameter array.  UNLIKE ttx_set_integrand_host, which keeps the caller's pointer, the engine
+ *                   COPIES par to the device here: later changes of the caller's array are not seen (set the integrand again)
+ * TTX_ESTATE: engine not created with TTX_FUN_DEVICE.  TTX_EINVAL: null / empty image, unreadable file, bytes that are no code
+ * object, a code object the runtime refuses (e.g. built for another GPU), no integrand `name` in it, an integrand compiled against
+ * another TTX_DEVFUN_ABI, more than 64 KB of LDS per workgroup, npar < 0 or par missing.  After a refusal the engine is as before.
+ * Setting an integrand again replaces the first and unloads its module; ttx_destroy unloads it and frees the par copy; a replica
+ * (ttx_replicate, ttx_accchk on a multi-process engine) shares both.  ttx_run / ttx_accchk before an integrand is set: TTX_ESTATE. */
+int ttx_set_integrand_device(ttx_engine *h, const void *image, int64_t nbytes, const char *name, const double *par, int32_t npar);
+int ttx_set_integrand_device_file(ttx_engine *h, const char *path, const char *name, const double *par, int32_t npar);
+/* the loaded integrand at npts multi-indices (ind row-major, 1-based; out of range: TTX_EINVAL), through the code object's list
+ * kernel: check that a device function computes what its author thinks before a sweep depends on it */
+int ttx_eval_device(ttx_engine *h, int64_t npts, const int32_t *ind /* [npts][d] */, double *out /* [npts] */);
 
 /* dtt_dmrgg itself: initial cross, sweeps until maxrank / 3 strikes, finalisation dtt_lua (lib/dmrgg.f90:151-1049) */
 int ttx_run(ttx_engine *h);
@@ -234,7 +257,8 @@ int ttx_k_residual_argmax(int32_t device, int32_t m, int32_t r, const double *a,
  * HIP events, and the algorithmic bytes 8*(m*r + r + 2*m) one launch moves. */
 int ttx_k_residual_bench(int32_t device, int64_t m, int32_t r, int32_t iters, double *avg_ms, double *bytes);
 /* K1: batch integrand evaluation, ind = npts x d (row-major, 1-based indices); fun_id ISING, STDNORM, MVN or COSCOEFF
- * (anything else, and a COSCOEFF aux that ttx_create would refuse, is TTX_EINVAL before any device call) */
+ * (anything else, and a COSCOEFF aux that ttx_create would refuse, is TTX_EINVAL before any device call; a loaded integrand,
+ * TTX_FUN_DEVICE, belongs to an engine: ttx_eval_device) */
 int ttx_k_eval(int32_t device, int32_t fun_id, int32_t d, const int32_t *n, const double *par, int32_t npar,
                const double *aux, int32_t naux, int64_t npts, const int32_t *ind, double *out);
 /* the same with the arithmetic named (TTX_ARITH_FAST: the re-associated one-thread evaluator of ttx_fast.h; Ising D/E, nodes in [0,1]) */

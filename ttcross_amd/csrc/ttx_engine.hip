@@ -9,6 +9,7 @@
 
 #include <chrono>
 #include <cmath>
+#include <cerrno>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +17,7 @@
 #include <condition_variable>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <random>
 #include <string>
@@ -31,6 +33,7 @@
 #include <rccl/rccl.h>   // types and enums only: the library is dlopen()ed by ttx_comm_init
 
 #include "../../include/ttx.h"
+#include "../../include/ttx_device_fun.h"   // the slot ABI of loadable device integrands (TTX_FUN_DEVICE)
 #include "ttx_kernels.h"
 #include "ttx_de.h"
 #include "ttx_mvn.h"
@@ -50,7 +53,7 @@ static int fail(int code, const char *fmt, ...)
 #define HIPCHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(TTX_EHIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 extern "C" const char *ttx_last_error(void) { return g_err.c_str(); }
-extern "C" int ttx_version(void) { return 1; }
+extern "C" int ttx_version(void) { return 2; }      // 2: TTX_FUN_DEVICE, ttx_set_integrand_device[_file], ttx_eval_device
 
 
 // RCCL entry points, resolved at run time (single-GPU users never load librccl)
@@ -83,6 +86,7 @@ static int rccl_load()
 }
 #define NCCLCHECK(x) do { ncclResult_t e_ = (x); if (e_ != ncclSuccess) return fail(TTX_EHIP, "%s failed: %s", #x, g_rccl.GetErrorString(e_)); } while (0)
 
+struct DevFun;                          // a loaded device integrand (TTX_FUN_DEVICE), defined with slot_eval
 struct ttx_engine {
     ttx_config cfg;
     std::vector<int32_t> n1;            // 1-based n, size d+2
@@ -168,6 +172,8 @@ struct ttx_engine {
     // user integrand evaluated on the host (TTX_FUN_HOST): see DevProb::hostpass
     ttx_host_fun hfun = nullptr;
     const double *hfun_par = nullptr;   // the caller's par(*), passed through untouched
+    // user integrand evaluated on the device by a code object the caller loaded (TTX_FUN_DEVICE): shared with replicas
+    std::shared_ptr<DevFun> dfun;
     size_t HS = 0;
     int64_t host_calls = 0;
     int64_t n_resid = 0;                // rook half-steps of the last run that took a residual (all groups)
@@ -269,12 +275,52 @@ static int host_eval(ttx_engine *h)
     return TTX_OK;
 }
 
+// ---- TTX_FUN_DEVICE: the integrand is a code object the caller compiled against include/ttx_device_fun.h ---------------------
+// The module, its two kernels and the device copy of the caller's par; an engine and its replicas (ttx_replicate) share one.
+struct DevFun {
+    int device = 0;
+    hipModule_t mod = nullptr;
+    hipFunction_t slots = nullptr, list = nullptr;
+    ttx_devfun_info info{};
+    double *par = nullptr;
+    std::string name;
+    std::vector<unsigned char> image;           // the loader's private copy of the code object: lives as long as the module
+    ~DevFun()
+    {
+        (void)hipSetDevice(device);
+        if (par) (void)hipFree(par);                // hipFree waits for the device: no kernel of the module is in flight after it
+        else (void)hipDeviceSynchronize();
+        if (mod) (void)hipModuleUnload(mod);
+    }
+};
+#define DEVFUN_LAUNCHCHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(TTX_EHIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+// the loaded slot kernel over all slots of this process, on the stream behind pass 1 (no synchronisation).  Launch shape (the
+// header's contract): workgroups of info.block threads; lane form one lane per slot, wave
+// form one wave per slot; both capped (the kernels stride), with info.lds_per_wave bytes of LDS per wave
+static int devfun_slots(ttx_engine *h)
+{
+    DevFun &f = *h->dfun;
+    DevProb &P = h->P;
+    int d = P.d;
+    long long nslot = (long long)h->G * h->HS;
+    const int *n = P.n + 1;
+    const double *par = f.par;
+    const short *hidx = P.hidx; unsigned char *hreq = P.hreq; double *hval = P.hval;
+    const int waves = f.info.block / 64;
+    const long long want = f.info.kind == TTX_DEVFUN_KIND_WAVE ? (nslot + waves - 1) / waves : (nslot + f.info.block - 1) / f.info.block;
+    const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(want, 4096));
+    void *args[] = {&d, &n, &par, &nslot, &hidx, &hreq, &hval};
+    DEVFUN_LAUNCHCHECK(hipModuleLaunchKernel(f.slots, grid, 1, 1, (unsigned)f.info.block, 1, 1, (unsigned)(f.info.lds_per_wave * waves), h->stream, args, nullptr));
+    return TTX_OK;
+}
+
 // between the two passes of an evaluating kernel: the host's `fun` (host_eval), or for TTX_FUN_COSCOEFF the device evaluator over
 // the requested slots, enqueued on the stream behind pass 1 (no synchronisation)
 static int slot_eval(ttx_engine *h)
 {
     DevProb &P = h->P;
     if (!P.slot_dev) return host_eval(h);
+    if (h->cfg.fun_id == TTX_FUN_DEVICE) return devfun_slots(h);
     const long long nslot = (long long)h->G * h->HS;
     const unsigned grid = (unsigned)std::min<long long>((nslot + TTX_CC_WAVES - 1) / TTX_CC_WAVES, 1024);
     hipLaunchKernelGGL(k_coscoeff_slots, dim3(grid), dim3(64 * TTX_CC_WAVES), sizeof(double) * TTX_CC_WAVES * TTX_CC_LDS(P.d), h->stream,
@@ -348,17 +394,18 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
     if (cfg->maxrank < 1 || cfg->maxrank > 128) return fail(TTX_EINVAL, "ttx_create: maxrank must be in 1..128 (got %d)", cfg->maxrank);
     if (cfg->pivoting < -1) return fail(TTX_EINVAL, "dtt_dmrgg: unknown pivoting: %d", cfg->pivoting);   // lib/dmrgg.f90:590-592
     if (2 * cfg->pivoting + 2 > TTX_MAXH) return fail(TTX_EINVAL, "dtt_dmrgg: pivoting %d too large", cfg->pivoting);
-    if (!(nofun && cfg->fun_id == 0) && (cfg->fun_id < 1 || cfg->fun_id > 5)) return fail(TTX_EINVAL, "ttx_create: unknown fun_id %d", cfg->fun_id);
+    if (!(nofun && cfg->fun_id == 0) && (cfg->fun_id < 1 || cfg->fun_id > 6)) return fail(TTX_EINVAL, "ttx_create: unknown fun_id %d", cfg->fun_id);
     if (cfg->npar < 0 || (cfg->npar > 0 && !cfg->par)) return fail(TTX_EINVAL, "ttx_create: par missing");
     if (cfg->fun_id == TTX_FUN_ISING && (cfg->npar < 2 * cfg->n[0] + 1)) return fail(TTX_EINVAL, "ttx_create: the Ising integrand needs par(1:2n+1) (nodes, weights, id)");
     if ((cfg->fun_id == TTX_FUN_STDNORM || cfg->fun_id == TTX_FUN_MVN) && cfg->npar < cfg->n[0]) return fail(TTX_EINVAL, "ttx_create: the integrand needs the nodes par(1:n)");
     // the built-in integrands address par(ind) (and the Ising weights par(n(1) + ind)): no mode may be larger than the first
     // (test_crs_ising.f90:181-183); with the reference this is the caller's business, here it would be a read outside the parameter vector
     // (the COS coefficients do not index par)
-    if (cfg->fun_id != TTX_FUN_HOST && cfg->fun_id != TTX_FUN_COSCOEFF && cfg->fun_id != 0)
+    if (cfg->fun_id != TTX_FUN_HOST && cfg->fun_id != TTX_FUN_COSCOEFF && cfg->fun_id != TTX_FUN_DEVICE && cfg->fun_id != 0)
         for (int k = 1; k < cfg->d; k++)
             if (cfg->n[k] > cfg->n[0]) return fail(TTX_EINVAL, "ttx_create: mode %d has %d points, more than the first mode (%d): the built-in integrands index par by n(1)", k + 1, cfg->n[k], cfg->n[0]);
     if (cfg->fun_id == TTX_FUN_HOST && cfg->d > 2048) return fail(TTX_EINVAL, "ttx_create: host integrand: at most 2048 dimensions (tt_size)");
+    if (cfg->fun_id == TTX_FUN_DEVICE && cfg->d > 2048) return fail(TTX_EINVAL, "ttx_create: device integrand: at most 2048 dimensions (tt_size)");
     if (cfg->fun_id == TTX_FUN_COSCOEFF) { if (int rc0 = coscoeff_check("ttx_create", cfg->d, cfg->n, cfg->aux, cfg->naux)) return rc0; }
     const int W = cfg->world_size < 1 ? 1 : cfg->world_size;
     const int nproc = std::max(cfg->nproc < 1 ? 1 : cfg->nproc, 1);
@@ -726,14 +773,14 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
             h->lot_rows = h->lot_wave ? ((getenv("TTX_LOTTERY_ROWS") && atoi(getenv("TTX_LOTTERY_ROWS")) == 2) ? 2 : 1) : 0;
         }
     }
-    if (cfg->fun_id == TTX_FUN_HOST || cfg->fun_id == TTX_FUN_COSCOEFF) {
+    if (cfg->fun_id == TTX_FUN_HOST || cfg->fun_id == TTX_FUN_COSCOEFF || cfg->fun_id == TTX_FUN_DEVICE) {
         // slots of one group: the largest point set any evaluating kernel asks for in one launch
         int nn = h->n1[1];
         for (int k = 2; k <= d; k++) nn = std::min(nn, h->n1[k]);
         const size_t snum = (size_t)std::max(8, nproc);
         h->HS = std::max<size_t>({(size_t)h->RM * NM, (size_t)nn * snum, (size_t)h->NC * NM, (size_t)2 * h->RM + 2 * NM, (size_t)2 * NM, (size_t)256});
         const size_t nslot = (size_t)h->G * h->HS;
-        if (cfg->fun_id == TTX_FUN_COSCOEFF) {
+        if (cfg->fun_id == TTX_FUN_COSCOEFF || cfg->fun_id == TTX_FUN_DEVICE) {
             // device slots (zero-filled, owned by allocs): the evaluator runs on the stream between the two passes
             P.slot_dev = 1;
             if ((rc = dev_alloc(h, &P.hidx, nslot * d)) || (rc = dev_alloc(h, &P.hval, nslot)) || (rc = dev_alloc(h, &P.hreq, nslot))) { ttx_destroy(h); return rc; }
@@ -754,6 +801,7 @@ static void shm_close(ttx_engine *h);
 extern "C" void ttx_destroy(ttx_engine *h)
 {
     if (!h) return;
+    if (h->dfun) { (void)hipSetDevice(h->cfg.device); if (h->stream) (void)hipStreamSynchronize(h->stream); h->dfun.reset(); }   // the last owner unloads the module
     if (h->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(h->comm);
     for (void *p : h->allocs) (void)hipFree(p);
     if (h->h_sum_base) (void)hipHostFree(h->h_sum_base);
@@ -1051,6 +1099,135 @@ extern "C" int ttx_set_integrand_host(ttx_engine *h, ttx_host_fun fun, const dou
     return TTX_OK;
 }
 extern "C" int64_t ttx_host_calls(const ttx_engine *h) { return h ? h->host_calls : 0; }
+
+// what hipModuleLoadData accepts: a code-object ELF, or the (plain or compressed) offload bundle of hipcc --genco.  Anything else
+// is refused here, so that arbitrary bytes never reach the runtime's loader
+static bool devfun_image_plausible(const unsigned char *p, size_t nbytes)
+{
+    static const char bundle[] = "__CLANG_OFFLOAD_BUNDLE__";
+    const size_t bl = sizeof(bundle) - 1;
+    auto u64 = [&](size_t at) { uint64_t v; memcpy(&v, p + at, 8); return v; };
+    if (nbytes >= 64 && memcmp(p, "\177ELF", 4) == 0) {
+        // ELF64 header: program and section header tables inside the image
+        if (p[4] != 2) return false;
+        uint16_t phes, phn, shes, shn;
+        memcpy(&phes, p + 54, 2); memcpy(&phn, p + 56, 2); memcpy(&shes, p + 58, 2); memcpy(&shn, p + 60, 2);
+        const uint64_t phoff = u64(32), shoff = u64(40);
+        return phoff <= nbytes && (uint64_t)phes * phn <= nbytes - phoff && shoff <= nbytes && (uint64_t)shes * shn <= nbytes - shoff;
+    }
+    if (nbytes >= bl + 8 && memcmp(p, bundle, bl) == 0) {
+        // uncompressed bundle: entry count, then per entry {offset, size, id length, id}; every entry inside the image
+        const uint64_t ne = u64(bl);
+        if (ne == 0 || ne > 1024) return false;
+        size_t at = bl + 8;
+        for (uint64_t i = 0; i < ne; i++) {
+            if (at + 24 > nbytes) return false;
+            const uint64_t off = u64(at), sz = u64(at + 8), idl = u64(at + 16);
+            if (off > nbytes || sz > nbytes - off || idl > nbytes - at - 24) return false;
+            at += 24 + (size_t)idl;
+        }
+        return true;
+    }
+    return nbytes >= 24 && memcmp(p, "CCOB", 4) == 0;
+}
+extern "C" int ttx_set_integrand_device(ttx_engine *h, const void *image, int64_t nbytes, const char *name, const double *par, int32_t npar)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_set_integrand_device: null handle");
+    if (h->cfg.fun_id != TTX_FUN_DEVICE) return fail(TTX_ESTATE, "ttx_set_integrand_device: the engine was not created with fun_id = TTX_FUN_DEVICE");
+    if (!image || nbytes <= 0) return fail(TTX_EINVAL, "ttx_set_integrand_device: empty code object image");
+    if (!name || !*name || strlen(name) > 200) return fail(TTX_EINVAL, "ttx_set_integrand_device: integrand name missing (or longer than 200 characters)");
+    if (npar < 0 || (npar > 0 && !par)) return fail(TTX_EINVAL, "ttx_set_integrand_device: par missing (npar = %d)", npar);
+    if (!devfun_image_plausible((const unsigned char *)image, (size_t)nbytes))
+        return fail(TTX_EINVAL, "ttx_set_integrand_device: the image is neither a complete code object (ELF) nor a complete offload bundle of hipcc --genco");
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    // the runtime may keep pointers into the image: the loader gets a private copy that lives as long as the module
+    auto f = std::make_shared<DevFun>();
+    f->device = h->cfg.device; f->name = name;
+    f->image.assign((const unsigned char *)image, (const unsigned char *)image + nbytes);
+    f->image.push_back(0);
+    hipError_t e = hipModuleLoadData(&f->mod, f->image.data());
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); f->mod = nullptr;
+        return fail(TTX_EINVAL, "ttx_set_integrand_device: the runtime refused the code object (%s): is it built for this GPU (--offload-arch=gfx950)?", hipGetErrorString(e));
+    }
+    const std::string sn = std::string("ttx_devfun_slots_") + name, ln = std::string("ttx_devfun_list_") + name, in = std::string("ttx_devfun_info_") + name;
+    hipDeviceptr_t ip = nullptr; size_t ib = 0;
+    if ((e = hipModuleGetGlobal(&ip, &ib, f->mod, in.c_str())) != hipSuccess || hipModuleGetFunction(&f->slots, f->mod, sn.c_str()) != hipSuccess ||
+        hipModuleGetFunction(&f->list, f->mod, ln.c_str()) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(TTX_EINVAL, "ttx_set_integrand_device: the code object has no integrand '%s' (symbols %s, %s, %s: see TTX_DEVICE_INTEGRAND in ttx_device_fun.h)",
+                    name, in.c_str(), sn.c_str(), ln.c_str());
+    }
+    if (ib < sizeof(int)) return fail(TTX_EINVAL, "ttx_set_integrand_device: %s is not a ttx_devfun_info", in.c_str());
+    HIPCHECK(hipMemcpy(&f->info, (const void *)ip, std::min(ib, sizeof(f->info)), hipMemcpyDeviceToHost));
+    if (f->info.abi != TTX_DEVFUN_ABI || ib != sizeof(f->info))
+        return fail(TTX_EINVAL, "ttx_set_integrand_device: integrand '%s' was compiled against slot ABI version %d, this engine speaks version %d: recompile it with this engine's ttx_device_fun.h",
+                    name, f->info.abi, TTX_DEVFUN_ABI);
+    if ((f->info.kind != TTX_DEVFUN_KIND_LANE && f->info.kind != TTX_DEVFUN_KIND_WAVE) || f->info.block < 64 || f->info.block > 1024 || f->info.block % 64)
+        return fail(TTX_EINVAL, "ttx_set_integrand_device: integrand '%s': bad kind / block size (%d / %d)", name, f->info.kind, f->info.block);
+    const long long lds = (long long)f->info.lds_per_wave * (f->info.block / 64);
+    if (f->info.lds_per_wave < 0 || lds > 64 * 1024)
+        return fail(TTX_EINVAL, "ttx_set_integrand_device: integrand '%s' asks for %lld bytes of LDS per workgroup (%d per wave), more than 64 KB", name, lds, f->info.lds_per_wave);
+    HIPCHECK(hipMalloc((void **)&f->par, sizeof(double) * (size_t)(npar + 1)));
+    if (npar > 0) HIPCHECK(hipMemcpy(f->par, par, sizeof(double) * (size_t)npar, hipMemcpyHostToDevice));
+    HIPCHECK(hipStreamSynchronize(h->stream));          // nothing of an earlier integrand is in flight when its module goes
+    h->dfun = std::move(f);
+    return TTX_OK;
+}
+extern "C" int ttx_set_integrand_device_file(ttx_engine *h, const char *path, const char *name, const double *par, int32_t npar)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_set_integrand_device_file: null handle");
+    if (h->cfg.fun_id != TTX_FUN_DEVICE) return fail(TTX_ESTATE, "ttx_set_integrand_device_file: the engine was not created with fun_id = TTX_FUN_DEVICE");
+    if (!path || !*path) return fail(TTX_EINVAL, "ttx_set_integrand_device_file: path missing");
+    FILE *fp = fopen(path, "rb");
+    if (!fp) return fail(TTX_EINVAL, "ttx_set_integrand_device_file: cannot read %s: %s", path, strerror(errno));
+    std::vector<unsigned char> buf;
+    unsigned char chunk[65536];
+    size_t got;
+    while ((got = fread(chunk, 1, sizeof chunk, fp)) > 0) {
+        buf.insert(buf.end(), chunk, chunk + got);
+        if (buf.size() > ((size_t)1 << 30)) break;
+    }
+    const bool bad = ferror(fp) != 0;
+    fclose(fp);
+    if (bad) return fail(TTX_EINVAL, "ttx_set_integrand_device_file: cannot read %s", path);
+    if (buf.empty()) return fail(TTX_EINVAL, "ttx_set_integrand_device_file: %s is empty", path);
+    return ttx_set_integrand_device(h, buf.data(), (int64_t)buf.size(), name, par, npar);
+}
+// the loaded integrand at a list of multi-indices, through the code object's list kernel
+extern "C" int ttx_eval_device(ttx_engine *h, int64_t npts, const int32_t *ind, double *out)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_eval_device: null handle");
+    if (h->cfg.fun_id != TTX_FUN_DEVICE) return fail(TTX_ESTATE, "ttx_eval_device: the engine was not created with fun_id = TTX_FUN_DEVICE");
+    if (!h->dfun) return fail(TTX_ESTATE, "ttx_eval_device: call ttx_set_integrand_device first");
+    if (npts < 0 || (npts > 0 && (!ind || !out))) return fail(TTX_EINVAL, "ttx_eval_device: null argument");
+    if (npts == 0) return TTX_OK;
+    int d = h->d;
+    for (int64_t p = 0; p < npts; p++)
+        for (int k = 0; k < d; k++)
+            if (ind[p * d + k] < 1 || ind[p * d + k] > h->n1[k + 1])
+                return fail(TTX_EINVAL, "ttx_eval_device: point %lld: index %d of mode %d is outside 1..%d", (long long)p, ind[p * d + k], k + 1, h->n1[k + 1]);
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    DevFun &f = *h->dfun;
+    int *dind = nullptr; double *dout = nullptr;
+    HIPCHECK(hipMalloc((void **)&dind, sizeof(int) * (size_t)npts * d));
+    if (hipMalloc((void **)&dout, sizeof(double) * (size_t)npts) != hipSuccess) { (void)hipFree(dind); return fail(TTX_EHIP, "ttx_eval_device: out of device memory"); }
+    int rc = TTX_OK;
+    long long np = npts;
+    const int *n = h->P.n + 1;
+    const double *par = f.par;
+    const int waves = f.info.block / 64;
+    const long long want = f.info.kind == TTX_DEVFUN_KIND_WAVE ? (np + waves - 1) / waves : (np + f.info.block - 1) / f.info.block;
+    const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(want, 4096));
+    void *args[] = {&d, &n, &par, &np, &dind, &dout};
+    hipError_t e = hipMemcpyAsync(dind, ind, sizeof(int) * (size_t)npts * d, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipModuleLaunchKernel(f.list, grid, 1, 1, (unsigned)f.info.block, 1, 1, (unsigned)(f.info.lds_per_wave * waves), h->stream, args, nullptr);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, sizeof(double) * (size_t)npts, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) rc = fail(TTX_EHIP, "ttx_eval_device: %s", hipGetErrorString(e));
+    (void)hipFree(dind); (void)hipFree(dout);
+    return rc;
+}
 
 // host functions of the stream-ordered host transport (run on a runtime thread when the stream reaches them; no HIP calls)
 static void hostfn_xfer(void *ud)
@@ -1733,6 +1910,10 @@ extern "C" int ttx_run(ttx_engine *h)
         case TTX_FUN_COSCOEFF:                  // the host integrand's two passes with the device evaluator between them (slot_eval)
             h->host_calls = 0;
             return run_impl<FUN_HOST>(h);
+        case TTX_FUN_DEVICE:                    // the same, the evaluator being the slot kernel of the caller's code object
+            if (!h->dfun) return fail(TTX_ESTATE, "ttx_run: call ttx_set_integrand_device first");
+            h->host_calls = 0;
+            return run_impl<FUN_HOST>(h);
         default: return run_impl<FUN_MVN>(h);
     }
 }
@@ -1818,6 +1999,7 @@ extern "C" int ttx_replicate(ttx_engine *h, ttx_engine **out)
     int rc = create_impl(&e, &c, h->cfg.fun_id == 0);
     if (rc) return rc;
     e->hfun = h->hfun; e->hfun_par = h->hfun_par;
+    e->dfun = h->dfun;                              // same process, same device: the replica shares the module and the par copy
     if (e->RM != h->RM || e->NM != h->NM) { ttx_destroy(e); return fail(TTX_EHIP, "ttx_replicate: layout mismatch"); }
     const size_t CS = h->P.CS;
     // slots of the other processes' cores hold -0.0: x + (-0.0) = x for EVERY x, also for x = -0.0 (x + (+0.0) would turn it into +0.0)
@@ -2201,6 +2383,9 @@ extern "C" int ttx_accchk(ttx_engine *h, int32_t nlot, double *einf, double *efr
             if (!h->hfun) return fail(TTX_ESTATE, "dtt_accchk: call ttx_set_integrand_host first");
             return accchk_impl<FUN_HOST>(h, nlot, einf, efro, ainf, afro, pivot);
         case TTX_FUN_COSCOEFF: return accchk_impl<FUN_HOST>(h, nlot, einf, efro, ainf, afro, pivot);
+        case TTX_FUN_DEVICE:
+            if (!h->dfun) return fail(TTX_ESTATE, "dtt_accchk: call ttx_set_integrand_device first");
+            return accchk_impl<FUN_HOST>(h, nlot, einf, efro, ainf, afro, pivot);
         default: return accchk_impl<FUN_MVN>(h, nlot, einf, efro, ainf, afro, pivot);
     }
 }

@@ -6,13 +6,21 @@ runs on the GPU through ttcross_amd.engine.  Usage:
     python -m ttcross_amd.drivers stdnorm D N RANK PIV [NGROUPS]
     python -m ttcross_amd.drivers mvn D N RANK PIV [NGROUPS]
     python -m ttcross_amd.drivers coscoeff D N RANK PIV [NGROUPS]
+    python -m ttcross_amd.drivers devfun D N RANK PIV [NGROUPS] [device|host|wave] [SOURCE.hip NAME]
+
+devfun: the rational example integrand (examples/devfun/rational.hip) as a LOADED device integrand (TTX_FUN_DEVICE), in its
+wave form, or -- host -- its C twin through the host callback (TTX_FUN_HOST; needs gcc); SOURCE.hip NAME loads another
+integrand over the same box set-up.
 """
 import math
 import sys
 
 import numpy as np
 
-from .engine import TTX_FUN_COSCOEFF, TTX_FUN_ISING, TTX_FUN_MVN, TTX_FUN_STDNORM, TTCross
+import os
+
+from .engine import (DEVFUN_DIR, TTX_FUN_COSCOEFF, TTX_FUN_DEVICE, TTX_FUN_HOST, TTX_FUN_ISING, TTX_FUN_MVN, TTX_FUN_STDNORM, TTCross,
+                     compile_device_fun)
 
 EPS = 2.220446049250313e-16
 TPI = 6.283185307179586476925286766559
@@ -113,8 +121,71 @@ def coscoeff_setup(d, n, sigma=0.4, corr=0.5, X0=math.log(100.0), rate=0.0, T=1.
     return dict(n=[n] * d, par=np.zeros(0), quad=None, tru=None, acc=500 * EPS, rescale=False, fun_id=TTX_FUN_COSCOEFF, aux=aux)
 
 
+def devfun_setup(d, n):
+    """test_crs_box.inc on [0, 1]: Gauss-Legendre nodes and weights, par = [nodes(1:n), weights(1:n), 0] (2n+1 entries, the
+    drivers' convention), quadrature with the weights, acc = 500 eps.  The integrand is the rational example function."""
+    if n % 2 == 0:
+        n += 1
+    x, w = lgwt(n)
+    par = np.zeros(2 * n + 1)
+    par[:n] = 0.5 * (x + 1.0)
+    par[n:2 * n] = 0.5 * w
+    return dict(n=[n] * d, par=par, quad=[par[n:2 * n].copy()] * d, tru=None, acc=500 * EPS, rescale=False, fun_id=TTX_FUN_DEVICE, aux=None)
+
+
+_RATIONAL_C = """#include <stdint.h>
+double ttx_rational(const int32_t *m, const int32_t *ind, const int32_t *n, const double *par)
+{ double s1 = 0.0, s2 = 0.0; (void)n; for (int i = 0; i < *m; i++) { const double x = par[ind[i] - 1]; s1 = s1 + x; s2 = s2 + x * x; } return s1 / (1.0 + s2); }
+"""
+_host_keep = []
+
+
+def _rational_host_addr():
+    """The C twin of rational.hip as a host callback (for the device-vs-host comparison of the devfun workload): compiled with gcc
+    into the user's cache directory."""
+    import ctypes
+    import subprocess
+    import tempfile
+    bdir = os.path.join(os.environ.get("XDG_CACHE_HOME") or tempfile.gettempdir(), "ttcross_amd_devfun")
+    os.makedirs(bdir, exist_ok=True)
+    src, so = os.path.join(bdir, "rational.c"), os.path.join(bdir, "librational.so")
+    if not os.path.exists(so):
+        with open(src, "w") as f:
+            f.write(_RATIONAL_C)
+        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-fPIC", "-shared", src, "-o", so + f".{os.getpid()}"], check=True)
+        os.replace(so + f".{os.getpid()}", so)
+    lib = ctypes.CDLL(so)
+    _host_keep.append(lib)
+    return ctypes.cast(lib.ttx_rational, ctypes.c_void_p).value
+
+
+def run_devfun(argv, device=0, verbose=True):
+    m, n, r, piv = int(argv[0]), int(argv[1]), int(argv[2]), int(argv[3])
+    rest = list(argv[4:])
+    ng = int(rest.pop(0)) if rest and rest[0].isdigit() else 1
+    how = rest.pop(0) if rest and rest[0] in ("device", "host", "wave") else "device"
+    s = devfun_setup(m, n)
+    if how == "host":
+        tt = TTCross(s["n"], TTX_FUN_HOST, [], r, pivoting=piv, accuracy=s["acc"], quad=s["quad"], nproc=ng, device=device, verbose=verbose)
+        tt.set_integrand_host(_rational_host_addr(), s["par"])
+    else:
+        src, name = (rest[0], rest[1]) if len(rest) >= 2 else \
+            (os.path.join(DEVFUN_DIR, "rational_wave.hip" if how == "wave" else "rational.hip"), "rational_wave" if how == "wave" else "rational")
+        tt = TTCross(s["n"], TTX_FUN_DEVICE, [], r, pivoting=piv, accuracy=s["acc"], quad=s["quad"], nproc=ng, device=device, verbose=verbose)
+        tt.set_integrand_device(compile_device_fun(src), name, s["par"])
+    tt.run()
+    val = tt.quad(s["quad"])
+    if verbose:
+        print("...with%12d evaluations completed in %12.4E sec." % (tt.neval, tt.seconds))
+        print("computed value: %.16e" % val)
+        print("integrand: %s, host calls %d" % (how, tt.host_calls))
+    return tt, val, s
+
+
 def run_driver(argv, device=0, verbose=True):
     drv = argv[0]
+    if drv == "devfun":
+        return run_devfun(argv[1:], device=device, verbose=verbose)
     if drv == "coscoeff":
         m, n, r, piv = int(argv[1]), int(argv[2]), int(argv[3]), int(argv[4])
         ng = int(argv[5]) if len(argv) > 5 else 1

@@ -8,12 +8,15 @@ meaning and error behaviour (the reference prints and stops; here TTXError carri
 """
 import ctypes
 import os
+import shutil
+import subprocess
 from ctypes import POINTER, c_char_p, c_double, c_int32, c_int64, c_uint8, c_uint64, c_void_p
 
 import numpy as np
 
 TTX_FUN_ISING, TTX_FUN_STDNORM, TTX_FUN_MVN, TTX_FUN_HOST = 1, 2, 3, 4
 TTX_FUN_COSCOEFF = 5       # calc_coefficient of test_crs_coscoeff.f90: aux = [mu, Sigma column-major, a, b], par unused
+TTX_FUN_DEVICE = 6         # any user `fun` on the device: a code object written against include/ttx_device_fun.h (set_integrand_device)
 K_NAMES = ("lottery", "halfstep", "accept", "exchange", "quad", "other")
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -107,10 +110,44 @@ def load_library():
     L.ttx_set_integrand_host.argtypes = [c_void_p, c_void_p, POINTER(c_double)]
     L.ttx_host_calls.argtypes = [c_void_p]
     L.ttx_host_calls.restype = c_int64
+    L.ttx_set_integrand_device.argtypes = [c_void_p, c_char_p, c_int64, c_char_p, POINTER(c_double), c_int32]
+    L.ttx_set_integrand_device_file.argtypes = [c_void_p, c_char_p, c_char_p, POINTER(c_double), c_int32]
+    L.ttx_eval_device.argtypes = [c_void_p, c_int64, POINTER(c_int32), POINTER(c_double)]
     L.ttx_k_exp.argtypes = [c_int32, c_int64, POINTER(c_double), POINTER(c_double)]
     L.ttx_exp_host.argtypes = [c_int64, POINTER(c_double), POINTER(c_double)]
     _lib = L
     return L
+
+
+INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")      # ttx.h, ttx_device_fun.h
+DEVFUN_DIR = os.path.join(os.path.dirname(_HERE), "examples", "devfun")    # example device integrands (source)
+
+
+def compile_device_fun(source_path, out_path=None, extra_flags=()):
+    """Compile a device integrand (a .hip file written against include/ttx_device_fun.h) to a gfx950 code object with
+    `hipcc --genco --offload-arch=gfx950 -O3 -ffp-contract=off -I <repo>/include`; returns the path of the code object
+    (default: the source path with the suffix .hsaco).  Rebuilds only when the code object is older than the source or
+    the header; when no hipcc is found an existing code object is used as it is.  Raises TTXError with the compiler's
+    stderr on failure."""
+    source_path = os.fspath(source_path)
+    out_path = os.fspath(out_path) if out_path else os.path.splitext(source_path)[0] + ".hsaco"
+    deps = [source_path, os.path.join(INCLUDE_DIR, "ttx_device_fun.h")]
+    if not os.path.exists(source_path):
+        raise TTXError(f"compile_device_fun: {source_path} not found")
+    fresh = os.path.exists(out_path) and all(os.path.getmtime(out_path) >= os.path.getmtime(f) for f in deps)
+    if fresh:
+        return out_path
+    hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
+    if hipcc is None:
+        if os.path.exists(out_path):
+            return out_path
+        raise TTXError(f"compile_device_fun: no hipcc on this machine and no code object {out_path}")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    cmd = [hipcc, "--genco", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-I", INCLUDE_DIR, *extra_flags, source_path, "-o", out_path]
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    if p.returncode != 0 or not os.path.exists(out_path):
+        raise TTXError("compile_device_fun: " + " ".join(cmd) + " failed:\n" + p.stderr[-4000:])
+    return out_path
 
 
 def _check(rc):
@@ -311,6 +348,26 @@ class TTCross:
         self._hpar = None if par is None else np.ascontiguousarray(par, dtype=np.float64)
         _check(load_library().ttx_set_integrand_host(self._h, c_void_p(fun_addr), _dp(self._hpar)))
         return self
+
+    def set_integrand_device(self, image_or_path, name, par=None):
+        """The user's `fun` on the DEVICE for an engine created with fun_id = TTX_FUN_DEVICE (include/ttx.h): a code object --
+        bytes, or the path of a file compile_device_fun wrote -- that holds the integrand `name` (TTX_DEVICE_INTEGRAND(name) of
+        include/ttx_device_fun.h).  par is COPIED to the device.  Setting an integrand again replaces the first."""
+        L = load_library()
+        p = np.zeros(0) if par is None else np.ascontiguousarray(par, dtype=np.float64)
+        if isinstance(image_or_path, (bytes, bytearray, memoryview)):
+            img = bytes(image_or_path)
+            _check(L.ttx_set_integrand_device(self._h, img, len(img), name.encode(), _dp(p) if p.size else None, p.size))
+        else:
+            _check(L.ttx_set_integrand_device_file(self._h, os.fsencode(image_or_path), name.encode(), _dp(p) if p.size else None, p.size))
+        return self
+
+    def eval_device(self, ind):
+        """The loaded device integrand at the multi-indices ind (npts x d, 1-based), through the code object's list kernel."""
+        ind = np.ascontiguousarray(ind, dtype=np.int32).reshape(-1, self.d)
+        out = np.zeros(ind.shape[0])
+        _check(load_library().ttx_eval_device(self._h, ind.shape[0], _ip(ind), _dp(out)))
+        return out
 
     @property
     def host_calls(self):

@@ -42,6 +42,9 @@ contains
   real(c_double),allocatable,target :: qw(:),aux(:),pcopy(:)
   integer :: l,m,k,off,fid,npar,ngroups,stat,rmx,wrank,wsize
   character(len=32) :: env
+  character(len=4096) :: dfpath
+  character(len=256) :: dfname
+  integer :: dfnpar
   if(arg%l.gt.arg%m)then;write(*,*)subnam,': l,m: ',arg%l,arg%m;stop;endif
   if(arg%l.ne.1)then;write(*,*)subnam,': only l=1 is supported (as in every driver)';stop;endif
   l=arg%l; m=arg%m
@@ -51,6 +54,13 @@ contains
    call identify(fun,m,arg%n,par,fid,npar,aux,pcopy)
   else
    call identify_nopar(fun,m,arg%n,fid,aux); npar=0
+  end if
+  ! a `fun` that is not built in moves to the DEVICE when TTX_DEVICE_FUN=<code object>:<name> names its device twin (written
+  ! against include/ttx_device_fun.h); TTX_INTEGRAND=host still forces the host callback
+  dfnpar=0
+  if(fid.eq.TTX_FUN_HOST)then
+   call device_fun_env(dfpath,dfname,dfnpar,2*maxval(arg%n(1:m)),present(par))
+   if(len_trim(dfpath).gt.0)then; fid=TTX_FUN_DEVICE; npar=0; endif
   end if
   allocate(nn(m)); nn=arg%n(1:m)
   cfg%d=m; cfg%n=c_loc(nn); cfg%fun_id=fid; cfg%par=c_null_ptr; cfg%npar=npar
@@ -95,6 +105,13 @@ contains
     call ttx_check(ttx_set_integrand_host(arg%ttx,c_funloc(fun),c_loc(par)),subnam)
    else
     call ttx_check(ttx_set_integrand_host(arg%ttx,c_funloc(fun),c_null_ptr),subnam)
+   end if
+  end if
+  if(fid.eq.TTX_FUN_DEVICE)then
+   if(present(par).and.dfnpar.gt.0)then
+    call ttx_check(ttx_set_integrand_device_file(arg%ttx,trim(dfpath)//c_null_char,trim(dfname)//c_null_char,c_loc(par),int(dfnpar,c_int32_t)),subnam)
+   else
+    call ttx_check(ttx_set_integrand_device_file(arg%ttx,trim(dfpath)//c_null_char,trim(dfname)//c_null_char,c_null_ptr,0_c_int32_t),subnam)
    end if
   end if
   if(wsize.gt.1)then
@@ -187,6 +204,33 @@ contains
   end if
   call ttx_check(ttx_accchk(arg%ttx,int(nlot,c_int32_t),einf,efro,ainf,afro,pv),'dtt_accchk')
   if(present(pivot))pivot(1:arg%m)=pv(1:arg%m)
+ end subroutine
+
+ subroutine device_fun_env(path,name,npar,npar_default,have_par)
+  ! TTX_DEVICE_FUN=<code object path>:<name> (split at the LAST colon); empty path: not set, or TTX_INTEGRAND=host.
+  ! How much of par(*) goes to the device: TTX_DEVICE_FUN_NPAR when set, else par(1:2*max(n)) -- nodes and weights, what every
+  ! driver allocates (and what the probes of identify read); nothing when the caller passed no par.
+  character(len=*),intent(out) :: path,name
+  integer,intent(out) :: npar
+  integer,intent(in) :: npar_default
+  logical,intent(in) :: have_par
+  character(len=4400) :: env
+  character(len=32) :: e2
+  integer :: stat,k
+  path=''; name=''; npar=0
+  call get_environment_variable('TTX_INTEGRAND',e2,status=stat)
+  if(stat.eq.0 .and. trim(e2).eq.'host')return
+  call get_environment_variable('TTX_DEVICE_FUN',env,status=stat)
+  if(stat.ne.0 .or. len_trim(env).eq.0)return
+  k=index(trim(env),':',back=.true.)
+  if(k.le.1 .or. k.ge.len_trim(env))then;write(*,*)'dtt_dmrgg: TTX_DEVICE_FUN must be <code object path>:<name>, got ',trim(env);stop;endif
+  path=env(1:k-1); name=env(k+1:len_trim(env))
+  if(have_par)then
+   npar=npar_default
+   call get_environment_variable('TTX_DEVICE_FUN_NPAR',e2,status=stat)
+   if(stat.eq.0 .and. len_trim(e2).gt.0)read(e2,*)npar
+   if(npar.lt.0)then;write(*,*)'dtt_dmrgg: TTX_DEVICE_FUN_NPAR must not be negative';stop;endif
+  end if
  end subroutine
 
  subroutine identify(fun,m,n,par,fid,npar,aux,pcopy)

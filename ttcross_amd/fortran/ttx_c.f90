@@ -3,7 +3,7 @@
 module ttx_c
  use iso_c_binding
  implicit none
- integer(c_int32_t),parameter :: TTX_FUN_ISING=1, TTX_FUN_STDNORM=2, TTX_FUN_MVN=3, TTX_FUN_HOST=4, TTX_FUN_COSCOEFF=5
+ integer(c_int32_t),parameter :: TTX_FUN_ISING=1, TTX_FUN_STDNORM=2, TTX_FUN_MVN=3, TTX_FUN_HOST=4, TTX_FUN_COSCOEFF=5, TTX_FUN_DEVICE=6
  type,bind(C) :: ttx_config
   integer(c_int32_t) :: d
   type(c_ptr) :: n
@@ -38,6 +38,18 @@ module ttx_c
   end subroutine
   function ttx_set_integrand_host(h,fun,par) bind(C,name='ttx_set_integrand_host') result(rc)   ! the user's `fun`, lib/dmrgg.f90:18
    import; type(c_ptr),value :: h; type(c_funptr),value :: fun; type(c_ptr),value :: par; integer(c_int) :: rc
+  end function
+  ! the user's `fun` on the device: a code object written against include/ttx_device_fun.h (the engine COPIES par)
+  function ttx_set_integrand_device(h,image,nbytes,name,par,npar) bind(C,name='ttx_set_integrand_device') result(rc)
+   import; type(c_ptr),value :: h; type(c_ptr),value :: image; integer(c_int64_t),value :: nbytes; character(kind=c_char) :: name(*)
+   type(c_ptr),value :: par; integer(c_int32_t),value :: npar; integer(c_int) :: rc
+  end function
+  function ttx_set_integrand_device_file(h,path,name,par,npar) bind(C,name='ttx_set_integrand_device_file') result(rc)
+   import; type(c_ptr),value :: h; character(kind=c_char) :: path(*),name(*); type(c_ptr),value :: par; integer(c_int32_t),value :: npar
+   integer(c_int) :: rc
+  end function
+  function ttx_eval_device(h,npts,ind,out) bind(C,name='ttx_eval_device') result(rc)
+   import; type(c_ptr),value :: h; integer(c_int64_t),value :: npts; integer(c_int32_t) :: ind(*); real(c_double) :: out(*); integer(c_int) :: rc
   end function
   function ttx_getppid() bind(C,name='getppid') result(p)      ! libc: the launcher's pid, shared by the ranks of a job
    import; integer(c_int) :: p
