@@ -84,7 +84,7 @@ typedef struct ttx_sweep_rec {
 } ttx_sweep_rec;
 
 const char *ttx_last_error(void);
-int ttx_version(void);   /* 2: TTX_FUN_DEVICE and the three entry points of loadable device integrands */
+int ttx_version(void);   /* 2: loadable device integrands; 3: ttx_ijk_batch, ttx_ijk_batch_dev, ttx_value_batch */
 
 /* allocate device state for one dtt_dmrgg problem (replaces the implicit set-up of lib/dmrgg.f90:58-148) */
 int ttx_create(ttx_engine **out, const ttx_config *cfg);
@@ -187,6 +187,32 @@ int ttx_norm(ttx_engine *h, double tol, double *val);
 int ttx_lognrm(ttx_engine *h, double tol, double *val);
 int ttx_dot(ttx_engine *hx, ttx_engine *hy, double *val);
 int ttx_ijk(ttx_engine *h, const int32_t *ind, double *val);
+/* The train at a BATCH of multi-indices or coordinate vectors, evaluated on the device by kernels of their own (ttx_ijk above
+ * costs about 2 d launches per element).  The engines ttx_ijk takes; a multi-process engine is refused as by ttx_ijk.  The train is
+ * not modified and the work space is the engine's own (allocated on first use, freed by ttx_destroy); batches are processed in
+ * chunks of TTX_IJK_CHUNK points (environment; default 2^18, 2^17 above maxrank 64), so memory stays bounded.
+ *   mode : TTX_EVAL_EXACT  one wave per point, the operation sequence of dtt_ijk's matmul chain in index order (sums from 0 over
+ *                          ascending k, separate multiply and add): bit-identical to the oracle's restatement
+ *          TTX_EVAL_MFMA   per mode the points are sorted by their index and all points of one index multiply the same core slice
+ *                          as a GEMM on the fp64 matrix cores: equal to EXACT to rounding (another summation order); a point's value
+ *                          does not depend on the other points of the batch
+ *          TTX_EVAL_AUTO   the engine chooses (ttx_eval_last_mode tells what ran)
+ *   ind  : npts rows of d 1-based indices.  A point with an entry outside 1..n(k) gets -3.0 (lib/tt.f90:638); no core is read for it.
+ *   The engine holds trains of at least two cores (ttx_create, ttx_from_tt): there is no resident train of one core to evaluate.
+ *   npts = 0 succeeds and launches nothing; a null pointer with npts > 0, npts < 0 or an unknown mode: TTX_EINVAL.
+ * ttx_ijk_batch_dev takes pointers on the engine's device (e.g. torch tensors), enqueues on the engine's stream and synchronises
+ * before it returns: no index crosses the host link.
+ * ttx_value_batch is dtt_value (lib/tt.f90:702-728) for npts coordinate vectors x(1:dd) (row-major): the index digits are formed on
+ * the device as the reference forms them (mm = d / dd digits per coordinate, last mode of a group first, i = int(n xx), i = n
+ * clamped to n - 1, xx = xx n - i; xx > 1 reduced by xx - int(xx)); a negative coordinate gives 0.0, modes left without a digit
+ * give the -3.0 of dtt_ijk.  Coordinates must be below 2^31 (NaN included: TTX_EINVAL). */
+#define TTX_EVAL_EXACT 0
+#define TTX_EVAL_MFMA 1
+#define TTX_EVAL_AUTO 2
+int ttx_ijk_batch(ttx_engine *h, int64_t npts, const int32_t *ind /* [npts][d], 1-based */, double *out /* [npts] */, int32_t mode);
+int ttx_ijk_batch_dev(ttx_engine *h, int64_t npts, const int32_t *ind_dev, double *out_dev, int32_t mode);
+int ttx_value_batch(ttx_engine *h, int64_t npts, int32_t dd, const double *x /* [npts][dd] */, double *out, int32_t mode);
+int ttx_eval_last_mode(const ttx_engine *h);       /* TTX_EVAL_EXACT or TTX_EVAL_MFMA: what the last batch ran with (-1: none yet) */
 /* ztt_quad (lib/dmrgg.f90:1418-1523) of the (real) resident TT with COMPLEX rank-1 weights, batched over nf weight
  * sets (the 32 frequencies of test_crs_chf.f90:153-168 in one call): w = nf blocks of sum(n) interleaved (re, im)
  * doubles, out = nf (re, im) pairs.  Multi-process engines: collective, the value on every process. */

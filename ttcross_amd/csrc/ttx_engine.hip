@@ -41,6 +41,7 @@
 #include "ttx_fused.h"
 #include "ttx_cluster.h"
 #include "ttx_coscoeff.h"
+#include "ttx_eval.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const char *fmt, ...)
@@ -53,7 +54,7 @@ static int fail(int code, const char *fmt, ...)
 #define HIPCHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(TTX_EHIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 extern "C" const char *ttx_last_error(void) { return g_err.c_str(); }
-extern "C" int ttx_version(void) { return 2; }      // 2: TTX_FUN_DEVICE, ttx_set_integrand_device[_file], ttx_eval_device
+extern "C" int ttx_version(void) { return 3; }      // 2: loadable device integrands; 3: ttx_ijk_batch, ttx_ijk_batch_dev, ttx_value_batch
 
 
 // RCCL entry points, resolved at run time (single-GPU users never load librccl)
@@ -177,6 +178,12 @@ struct ttx_engine {
     size_t HS = 0;
     int64_t host_calls = 0;
     int64_t n_resid = 0;                // rook half-steps of the last run that took a residual (all groups)
+    // batched evaluation (ttx_eval.h): work space of its own, grown on demand, freed in ttx_destroy
+    struct EvBuf { void *p = nullptr; size_t bytes = 0; };
+    enum { EV_META, EV_IND, EV_OUT, EV_FLAG, EV_XV, EV_XA, EV_XB, EV_SORT, EV_NBUF };
+    EvBuf ev[EV_NBUF];
+    std::vector<char> ev_meta_host;
+    int ev_last_mode = -1;              // TTX_EVAL_* the last batch ran with
 };
 
 // ---- worker threads for the host integrand (the reference evaluates `fun` inside !$OMP PARALLEL DO regions,
@@ -804,6 +811,7 @@ extern "C" void ttx_destroy(ttx_engine *h)
     if (h->dfun) { (void)hipSetDevice(h->cfg.device); if (h->stream) (void)hipStreamSynchronize(h->stream); h->dfun.reset(); }   // the last owner unloads the module
     if (h->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(h->comm);
     for (void *p : h->allocs) (void)hipFree(p);
+    for (auto &b : h->ev) if (b.p) (void)hipFree(b.p);
     if (h->h_sum_base) (void)hipHostFree(h->h_sum_base);
     if (h->h_val) (void)hipHostFree(h->h_val);
     if (h->h_svd) (void)hipHostFree(h->h_svd);
@@ -2904,6 +2912,182 @@ extern "C" int ttx_ijk(ttx_engine *h, const int32_t *ind, double *val)
     HIPCHECK(hipMemcpyAsync(val, xv, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
     HIPCHECK(hipGetLastError());
+    return TTX_OK;
+}
+
+// ---- the train at a batch of multi-indices (ttx_eval.h) -------------------------------------------------------------------------
+static int ev_reserve(ttx_engine *h, int which, size_t bytes)
+{
+    auto &b = h->ev[which];
+    if (b.p && b.bytes >= bytes) return TTX_OK;
+    if (b.p) { HIPCHECK(hipStreamSynchronize(h->stream)); (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; }
+    HIPCHECK(hipMalloc(&b.p, bytes + 64));
+    b.bytes = bytes;
+    return TTX_OK;
+}
+// points per chunk: bounds the work space (two state buffers of chunk x max rank doubles on the MFMA path, the index block of the host entry)
+static size_t ev_chunk(const ttx_engine *h)
+{
+    if (const char *e = getenv("TTX_IJK_CHUNK")) { const long long v = atoll(e); if (v >= 1) return (size_t)std::min<long long>(v, 1ll << 24); }
+    return h->RM <= 64 ? (size_t)1 << 18 : (size_t)1 << 17;
+}
+// TTX_EVAL_AUTO, a cost model fitted to the measurement in DESIGN.md 4.5, with w = sum r(k-1) r(k) (slice elements a point touches).
+// The MFMA path pays a fixed cost whatever the batch (four launches per mode and the staging of the slices): 1.46 / 1.47 / 9.2 ms at
+// (d, w) = (63, 6.8 k) / (63, 62 k) / (255, 1.04 M), modelled as 23 us d + 3.2 ns w.  Per point it saves 27.7 / 106 / 1317 ns against
+// the exact kernel, modelled as 1.25 ps w + 0.286 ns d.  MFMA is taken where the saving covers the fixed cost; the model's break-evens
+// are 55 k / 17 k / 6.7 k points on the three trains, the measured ones 52 k / 14 k / 7 k.
+static int ev_auto(const ttx_engine *h, int64_t npts)
+{
+    double w = 0.0;
+    for (int k = 1; k <= h->d; k++) w += (double)h->rfinal[k - 1] * h->rfinal[k];
+    return (double)npts * (1.25e-12 * w + 0.286e-9 * h->d) >= 23.0e-6 * h->d + 3.2e-9 * w ? TTX_EVAL_MFMA : TTX_EVAL_EXACT;
+}
+// core pointers, ranks and mode sizes of the train as it stands now, in one device block
+static int ev_train(ttx_engine *h, EvTrain *T)
+{
+    const int d = h->d;
+    h->ev_meta_host.resize(sizeof(double *) * d + sizeof(int) * (2 * d + 1));
+    const double **cp = (const double **)h->ev_meta_host.data();
+    int *r = (int *)(cp + d), *n = r + d + 1, rmax = 1;
+    for (int k = 1; k <= d; k++) { cp[k - 1] = core_dev(h, k); n[k - 1] = h->n1[k]; }
+    for (int k = 0; k <= d; k++) { r[k] = h->rfinal[k]; rmax = std::max(rmax, r[k]); }
+    if (rmax > 128) return fail(TTX_EINVAL, "ttx_ijk_batch: ranks up to 128 only (got %d)", rmax);
+    if (int rc = ev_reserve(h, ttx_engine::EV_META, h->ev_meta_host.size())) return rc;
+    char *m = (char *)h->ev[ttx_engine::EV_META].p;
+    HIPCHECK(hipMemcpyAsync(m, h->ev_meta_host.data(), h->ev_meta_host.size(), hipMemcpyHostToDevice, h->stream));
+    T->d = d; T->RM = h->RM; T->ldx = (rmax + 3) & ~3; T->SS = h->P.SS;
+    T->core = (const double *const *)m; T->r = (const int *)(m + sizeof(double *) * d); T->n = T->r + d + 1;
+    return TTX_OK;
+}
+template <int MR>
+static int ev_gemm_launch(ttx_engine *h, const EvTrain &T, int i, int nmode, int grid, size_t lds, const int *off, const int *tile, const int *perm, const double *X, double *Z)
+{
+    // the attribute belongs to the current device (the engine's): set whenever a slice image needs more than the default 64 KB
+    if (lds > 64 * 1024) HIPCHECK(hipFuncSetAttribute((const void *)k_ev_gemm<MR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_ev_gemm<MR>, dim3(grid), dim3(256), lds, h->stream, T, i, nmode, off, tile, perm, X, Z);
+    return TTX_OK;
+}
+// c points whose index rows (and, for ttx_value_batch, flags) are on the device -> out (device), enqueued on the engine's stream
+static int ev_run(ttx_engine *h, const EvTrain &T, int mode, int c, const int *ind, const int *flag, double *out)
+{
+    const int d = h->d;
+    int ncu = 256;
+    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
+    if (mode == TTX_EVAL_EXACT) {
+        // one wave per point, 4 waves per workgroup; the grid is capped at 8 workgroups per CU and strides over the batch (66 VGPRs:
+        // 7 waves per SIMD are resident); the chain is a dependent sequence, throughput comes from the waves in flight
+        const size_t lds = 4 * sizeof(double) * (2 * (size_t)T.ldx + (((size_t)d + 1) >> 1));
+        const int grid = (int)std::min<long long>(((long long)c + 3) / 4, (long long)ncu * 8);
+        hipLaunchKernelGGL(k_ev_exact, dim3(grid), dim3(256), lds, h->stream, T, (long long)c, ind, flag, out);
+        return TTX_OK;
+    }
+    const size_t NM = h->NM;
+    int rc;
+    if ((rc = ev_reserve(h, ttx_engine::EV_XA, sizeof(double) * (size_t)c * T.ldx)) || (rc = ev_reserve(h, ttx_engine::EV_XB, sizeof(double) * (size_t)c * T.ldx)) ||
+        (rc = ev_reserve(h, ttx_engine::EV_SORT, sizeof(int) * (2 * (size_t)c + 4 * NM + 8)))) return rc;
+    double *X = (double *)h->ev[ttx_engine::EV_XA].p, *Z = (double *)h->ev[ttx_engine::EV_XB].p;
+    int *valid = (int *)h->ev[ttx_engine::EV_SORT].p, *perm = valid + c, *cnt = perm + c, *off = cnt + NM, *tile = off + NM + 1, *cur = tile + NM + 1;
+    hipLaunchKernelGGL(k_ev_init, dim3(std::min((c + 3) / 4, ncu * 8)), dim3(256), 0, h->stream, T, c, ind, flag, valid, X, out);
+    const int nb = std::max(1, std::min((c + 1023) / 1024, 1024));
+    for (int i = d - 2; i >= 0; i--) {
+        const int nmode = h->n1[i + 1], q0 = h->rfinal[i], q1 = h->rfinal[i + 1];
+        const size_t hl = nmode <= TTX_EV_LDSHIST ? sizeof(int) * nmode : 0;
+        HIPCHECK(hipMemsetAsync(cnt, 0, sizeof(int) * nmode, h->stream));
+        hipLaunchKernelGGL(k_ev_hist, dim3(nb), dim3(256), hl, h->stream, d, i, nmode, c, ind, (const int *)valid, cnt);
+        hipLaunchKernelGGL(k_ev_scan, dim3(1), dim3(1024), 0, h->stream, nmode, (const int *)cnt, off, tile, cur);
+        hipLaunchKernelGGL(k_ev_scatter, dim3(nb), dim3(256), hl, h->stream, d, i, nmode, c, ind, (const int *)valid, cur, perm);
+        const int grid = c / TTX_EV_TP + std::min(nmode, c);
+        const size_t lds = ev_gemm_lds(q0, q1);
+        if ((rc = q0 <= 16 ? ev_gemm_launch<1>(h, T, i, nmode, grid, lds, off, tile, perm, X, Z)
+                : q0 <= 32 ? ev_gemm_launch<2>(h, T, i, nmode, grid, lds, off, tile, perm, X, Z)
+                : q0 <= 64 ? ev_gemm_launch<4>(h, T, i, nmode, grid, lds, off, tile, perm, X, Z)
+                           : ev_gemm_launch<8>(h, T, i, nmode, grid, lds, off, tile, perm, X, Z))) return rc;
+        std::swap(X, Z);
+    }
+    hipLaunchKernelGGL(k_ev_final, dim3(std::max(1, std::min((c + 255) / 256, 1024))), dim3(256), 0, h->stream, c, T.ldx, (const int *)valid, (const double *)X, out);
+    return TTX_OK;
+}
+static int ev_mode(ttx_engine *h, const char *who, int64_t npts, int32_t mode, int *eff)
+{
+    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    *eff = mode == TTX_EVAL_AUTO ? ev_auto(h, npts) : mode;
+    return TTX_OK;
+}
+extern "C" int ttx_eval_last_mode(const ttx_engine *h) { return h ? h->ev_last_mode : -1; }
+
+extern "C" int ttx_ijk_batch_dev(ttx_engine *h, int64_t npts, const int32_t *ind_dev, double *out_dev, int32_t mode)
+{
+    int rc = tt_prepare(h, "dtt_ijk"), eff = 0;
+    if (rc) return rc;
+    if (npts < 0 || (npts > 0 && (!ind_dev || !out_dev))) return fail(TTX_EINVAL, "ttx_ijk_batch_dev: null argument or negative npts");
+    if ((rc = ev_mode(h, "ttx_ijk_batch_dev", npts, mode, &eff))) return rc;
+    if (npts == 0) { h->ev_last_mode = eff; return TTX_OK; }
+    EvTrain T;
+    if ((rc = ev_train(h, &T))) return rc;
+    const size_t chunk = ev_chunk(h), d = h->d;
+    for (int64_t o = 0; o < npts; o += (int64_t)chunk) {
+        const int c = (int)std::min<int64_t>((int64_t)chunk, npts - o);
+        if ((rc = ev_run(h, T, eff, c, ind_dev + (size_t)o * d, nullptr, out_dev + o))) return rc;
+    }
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipGetLastError());
+    h->ev_last_mode = eff;
+    return TTX_OK;
+}
+
+extern "C" int ttx_ijk_batch(ttx_engine *h, int64_t npts, const int32_t *ind, double *out, int32_t mode)
+{
+    int rc = tt_prepare(h, "dtt_ijk"), eff = 0;
+    if (rc) return rc;
+    if (npts < 0 || (npts > 0 && (!ind || !out))) return fail(TTX_EINVAL, "ttx_ijk_batch: null argument or negative npts");
+    if ((rc = ev_mode(h, "ttx_ijk_batch", npts, mode, &eff))) return rc;
+    if (npts == 0) { h->ev_last_mode = eff; return TTX_OK; }
+    EvTrain T;
+    if ((rc = ev_train(h, &T))) return rc;
+    const size_t chunk = std::min<size_t>(ev_chunk(h), (size_t)npts), d = h->d;
+    if ((rc = ev_reserve(h, ttx_engine::EV_IND, sizeof(int) * chunk * d)) || (rc = ev_reserve(h, ttx_engine::EV_OUT, sizeof(double) * chunk))) return rc;
+    int *dind = (int *)h->ev[ttx_engine::EV_IND].p;
+    double *dout = (double *)h->ev[ttx_engine::EV_OUT].p;
+    for (int64_t o = 0; o < npts; o += (int64_t)chunk) {
+        const int c = (int)std::min<int64_t>((int64_t)chunk, npts - o);
+        HIPCHECK(hipMemcpyAsync(dind, ind + (size_t)o * d, sizeof(int) * (size_t)c * d, hipMemcpyHostToDevice, h->stream));
+        if ((rc = ev_run(h, T, eff, c, dind, nullptr, dout))) return rc;
+        HIPCHECK(hipMemcpyAsync(out + o, dout, sizeof(double) * c, hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(hipStreamSynchronize(h->stream));
+    }
+    HIPCHECK(hipGetLastError());
+    h->ev_last_mode = eff;
+    return TTX_OK;
+}
+
+// dtt_value (lib/tt.f90:702-728) for npts coordinate vectors: the digits are formed on the device (k_ev_digits), then dtt_ijk
+extern "C" int ttx_value_batch(ttx_engine *h, int64_t npts, int32_t dd, const double *x, double *out, int32_t mode)
+{
+    int rc = tt_prepare(h, "dtt_value"), eff = 0;
+    if (rc) return rc;
+    if (npts < 0 || (npts > 0 && (!x || !out))) return fail(TTX_EINVAL, "ttx_value_batch: null argument or negative npts");
+    if (dd < 1) return fail(TTX_EINVAL, "ttx_value_batch: %d coordinates per point", dd);
+    if ((rc = ev_mode(h, "ttx_value_batch", npts, mode, &eff))) return rc;
+    if (npts == 0) return TTX_OK;
+    // int(xx) of the reference is defined below 2^31 only
+    for (size_t e = 0; e < (size_t)npts * dd; e++) if (!(x[e] < 2147483648.0)) return fail(TTX_EINVAL, "ttx_value_batch: coordinate %g of point %lld is not below 2^31", x[e], (long long)(e / dd));
+    EvTrain T;
+    if ((rc = ev_train(h, &T))) return rc;
+    const size_t chunk = std::min<size_t>(ev_chunk(h), (size_t)npts), d = h->d;
+    if ((rc = ev_reserve(h, ttx_engine::EV_IND, sizeof(int) * chunk * d)) || (rc = ev_reserve(h, ttx_engine::EV_OUT, sizeof(double) * chunk)) ||
+        (rc = ev_reserve(h, ttx_engine::EV_FLAG, sizeof(int) * chunk)) || (rc = ev_reserve(h, ttx_engine::EV_XV, sizeof(double) * chunk * dd))) return rc;
+    int *dind = (int *)h->ev[ttx_engine::EV_IND].p, *dflag = (int *)h->ev[ttx_engine::EV_FLAG].p;
+    double *dout = (double *)h->ev[ttx_engine::EV_OUT].p, *dx = (double *)h->ev[ttx_engine::EV_XV].p;
+    for (int64_t o = 0; o < npts; o += (int64_t)chunk) {
+        const int c = (int)std::min<int64_t>((int64_t)chunk, npts - o);
+        HIPCHECK(hipMemcpyAsync(dx, x + (size_t)o * dd, sizeof(double) * (size_t)c * dd, hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(k_ev_digits, g1((size_t)c), dim3(256), 0, h->stream, (int)d, T.n, (int)dd, (long long)c, (const double *)dx, dind, dflag);
+        if ((rc = ev_run(h, T, eff, c, dind, dflag, dout))) return rc;
+        HIPCHECK(hipMemcpyAsync(out + o, dout, sizeof(double) * c, hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(hipStreamSynchronize(h->stream));
+    }
+    HIPCHECK(hipGetLastError());
+    h->ev_last_mode = eff;
     return TTX_OK;
 }
 

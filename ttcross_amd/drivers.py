@@ -7,6 +7,7 @@ runs on the GPU through ttcross_amd.engine.  Usage:
     python -m ttcross_amd.drivers mvn D N RANK PIV [NGROUPS]
     python -m ttcross_amd.drivers coscoeff D N RANK PIV [NGROUPS]
     python -m ttcross_amd.drivers devfun D N RANK PIV [NGROUPS] [device|host|wave] [SOURCE.hip NAME]
+    python -m ttcross_amd.drivers tijk WORKLOAD NPTS MODE      (batched element evaluation: c64 | d64 | rand256 | a file of dtt_write)
 
 devfun: the rational example integrand (examples/devfun/rational.hip) as a LOADED device integrand (TTX_FUN_DEVICE), in its
 wave form, or -- host -- its C twin through the host callback (TTX_FUN_HOST; needs gcc); SOURCE.hip NAME loads another
@@ -266,8 +267,59 @@ def run_chf(argv, device=0, verbose=True):
     return tt, vals, s
 
 
+TIJK_WORKLOADS = {"c64": ("c", 64, 51, 32, 2), "d64": ("d", 64, 51, 32, 2), "c8": ("c", 8, 33, 12, 2)}
+
+
+def tijk_train(workload, device=0):
+    """The train of a tijk measurement: the result of an Ising sweep (c64, d64, c8: 8 bond groups as the benchmark runs them
+    where the train is long enough), a random train of the D_256 shape (rand256: d = 255, n = 101, r = 64, entries scaled so
+    that elements stay of order one) or a file written by dtt_write."""
+    if workload in TIJK_WORKLOADS:
+        kind, m, n, r, piv = TIJK_WORKLOADS[workload]
+        s = ising_setup(kind, m, n)
+        return TTCross(s["n"], s["fun_id"], s["par"], r, pivoting=piv, accuracy=s["acc"], quad=s["quad"], tru=s["tru"],
+                       nproc=8 if m >= 32 else 1, device=device).run()
+    if workload.startswith("rand"):
+        d = int(workload[4:]) - 1
+        rng = np.random.default_rng(256)
+        r = [1] + [64] * (d - 1) + [1]
+        return TTCross.from_cores([rng.uniform(0.0, 1.0, (r[k], 101, r[k + 1])) / (0.5 * r[k + 1]) for k in range(d)], device=device)
+    return TTCross.read(workload, device=device)
+
+
+def run_tijk(argv, device=0, repeats=5, tt=None):
+    """tijk WORKLOAD NPTS MODE: npts seeded multi-indices drawn ON the device, one warm-up and `repeats` timed batches through
+    the device-pointer entry (outputs stay on the device); prints one JSON line with the median."""
+    import json
+    import time
+    import torch
+    torch.cuda.init()          # a torch that brings its own HIP runtime must initialise its device before the engine's library does
+    workload, npts, mode = argv[0], int(float(argv[1])), argv[2]
+    tt = tt or tijk_train(workload, device=device)
+    dev = torch.device("cuda", device)
+    g = torch.Generator(device=dev)
+    g.manual_seed(20240607)
+    n = torch.tensor(np.asarray(tt._n), dtype=torch.int32, device=dev)
+    ind = (torch.randint(0, 2 ** 31 - 1, (npts, tt.d), dtype=torch.int32, device=dev, generator=g) % n + 1).contiguous()
+    torch.cuda.synchronize(dev)
+    out = tt.tijk_batch(ind, mode)
+    ms = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        out = tt.tijk_batch(ind, mode)            # synchronises before it returns
+        ms.append((time.perf_counter() - t0) * 1e3)
+    med = float(np.median(ms))
+    res = dict(workload=workload, npts=npts, mode_asked=mode, mode=tt.eval_last_mode, d=tt.d, max_rank=int(tt.ranks().max()),
+               ms=med, ms_all=[round(x, 4) for x in ms], points_per_s=npts / (med * 1e-3) if med > 0 else None,
+               checksum=float(out.sum().item()), invalid=int((out == -3.0).sum().item()))
+    print(json.dumps(res))
+    return tt, ind, out, res
+
+
 if __name__ == "__main__":
-    if sys.argv[1] == "chf":
+    if sys.argv[1] == "tijk":
+        run_tijk(sys.argv[2:])
+    elif sys.argv[1] == "chf":
         run_chf(sys.argv[2:])
     elif sys.argv[1] == "pdf":
         run_pdf(sys.argv[2:])

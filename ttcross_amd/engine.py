@@ -17,6 +17,8 @@ import numpy as np
 TTX_FUN_ISING, TTX_FUN_STDNORM, TTX_FUN_MVN, TTX_FUN_HOST = 1, 2, 3, 4
 TTX_FUN_COSCOEFF = 5       # calc_coefficient of test_crs_coscoeff.f90: aux = [mu, Sigma column-major, a, b], par unused
 TTX_FUN_DEVICE = 6         # any user `fun` on the device: a code object written against include/ttx_device_fun.h (set_integrand_device)
+TTX_EVAL_EXACT, TTX_EVAL_MFMA, TTX_EVAL_AUTO = 0, 1, 2
+EVAL_MODES = {"exact": TTX_EVAL_EXACT, "mfma": TTX_EVAL_MFMA, "auto": TTX_EVAL_AUTO}
 K_NAMES = ("lottery", "halfstep", "accept", "exchange", "quad", "other")
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -93,6 +95,10 @@ def load_library():
     L.ttx_lognrm.argtypes = [c_void_p, c_double, POINTER(c_double)]
     L.ttx_dot.argtypes = [c_void_p, c_void_p, POINTER(c_double)]
     L.ttx_ijk.argtypes = [c_void_p, POINTER(c_int32), POINTER(c_double)]
+    L.ttx_ijk_batch.argtypes = [c_void_p, c_int64, POINTER(c_int32), POINTER(c_double), c_int32]
+    L.ttx_ijk_batch_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_int32]
+    L.ttx_value_batch.argtypes = [c_void_p, c_int64, c_int32, POINTER(c_double), POINTER(c_double), c_int32]
+    L.ttx_eval_last_mode.argtypes = [c_void_p]
     L.ttx_zquad.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
     L.ttx_accchk.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
     L.ttx_from_tt.argtypes = [POINTER(c_void_p), c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), c_int32]
@@ -161,6 +167,45 @@ def _dp(a):
 
 def _ip(a):
     return a.ctypes.data_as(POINTER(c_int32)) if a is not None else None
+
+
+def _eval_mode(mode):
+    if mode in EVAL_MODES:
+        return EVAL_MODES[mode]
+    if mode in EVAL_MODES.values():
+        return int(mode)
+    raise ValueError(f"mode must be one of {sorted(EVAL_MODES)} (got {mode!r})")
+
+
+def value_indices(n, x):
+    """The index digits dtt_value (lib/tt.f90:702-728) forms for coordinate vectors x (npts, dd) of a train with mode sizes
+    n(1:d), restated on the host in plain float64: mm = d // dd digits per coordinate, written from the LAST mode of the
+    coordinate's group backwards; i = int(n xx), i = n clamped to n - 1, xx = xx n - i; xx > 1 is first reduced by
+    xx - int(xx).  Returns (ind, neg): ind (npts, d) int32, 1-based, 0 where a mode got no digit (d not divisible by dd;
+    dtt_ijk answers -3.0 there); neg (npts,) bool, true where a coordinate is negative (dtt_value answers 0.0)."""
+    n = np.asarray(n, dtype=np.int64).ravel()
+    x = np.atleast_2d(np.asarray(x, dtype=np.float64))
+    if not np.all(x < 2147483648.0):
+        raise ValueError("value_indices: coordinates must be below 2^31")
+    d, (npts, dd) = n.size, x.shape
+    mm = d // dd
+    ind = np.zeros((npts, d), dtype=np.int32)
+    neg = np.zeros(npts, dtype=bool)
+    for c in range(dd):
+        xx = x[:, c].copy()
+        neg |= xx < 0.0              # dtt_value returns at the first negative coordinate: the digits no longer matter
+        big = xx > 1.0
+        xx[big] = xx[big] - np.trunc(xx[big])
+        for j in range(1, mm + 1):
+            pos = c * mm + mm - j
+            nn = float(n[pos])
+            with np.errstate(invalid="ignore"):
+                i = np.trunc(nn * xx)
+            i[i == nn] = nn - 1.0
+            ind[:, pos] = np.where(neg, 0, i).astype(np.int32) + 1
+            xx = xx * nn - i
+    ind[neg] = 0
+    return ind, neg
 
 
 def split_groups(nproc, world_rank, world_size):
@@ -243,15 +288,17 @@ class TTCross:
         self.world_rank, self.world_size = int(world_rank), int(world_size)
         c.verbose = 1 if verbose else 0
         c.arith = 1 if arith in (1, "fast") else 0      # None / "exact": exact unless TTX_ARITH=fast is set
+        self.device = int(device)
         self._h = c_void_p()
         _check(L.ttx_create(ctypes.byref(self._h), ctypes.byref(c)))
 
     # ---- trains that do not come from a sweep (lib/ttio.f90) -----------------------------------
     @classmethod
-    def _adopt(cls, handle):
+    def _adopt(cls, handle, device=0):
         L = load_library()
         self = cls.__new__(cls)
         self._h = handle
+        self.device = int(device)
         d = c_int32()
         _check(L.ttx_get_modes(handle, ctypes.byref(d), None))
         self.d = d.value
@@ -269,14 +316,14 @@ class TTCross:
         flat = np.ascontiguousarray(np.concatenate([c.ravel(order="F") for c in cores]))
         h = c_void_p()
         _check(load_library().ttx_from_tt(ctypes.byref(h), len(cores), _ip(n), _ip(r), _dp(flat), int(device)))
-        return cls._adopt(h)
+        return cls._adopt(h, device)
 
     @classmethod
     def read(cls, path, device=0):
         """dtt_read (lib/ttio.f90:196-297): load the reference's stream file onto the device."""
         h = c_void_p()
         _check(load_library().ttx_read(ctypes.byref(h), os.fsencode(path), int(device)))
-        return cls._adopt(h)
+        return cls._adopt(h, device)
 
     def write_hdf5(self, path):
         """save_dtt_to_hdf5 (lib/utils.f90:8-57): group TT with modes, ranks and core_k."""
@@ -290,7 +337,7 @@ class TTCross:
         L.ttx_read_hdf5.argtypes = [POINTER(c_void_p), ctypes.c_char_p, c_int32]
         h = c_void_p()
         _check(L.ttx_read_hdf5(ctypes.byref(h), os.fsencode(path), int(device)))
-        return cls._adopt(h)
+        return cls._adopt(h, device)
 
     def replicate(self):
         """The train of a multi-process job gathered onto this process as a new single-process engine (collective; include/ttx.h)."""
@@ -298,7 +345,7 @@ class TTCross:
         L.ttx_replicate.argtypes = [c_void_p, POINTER(c_void_p)]
         h = c_void_p()
         _check(L.ttx_replicate(self._h, ctypes.byref(h)))
-        return TTCross._adopt(h)
+        return TTCross._adopt(h, self.device)
 
     def write(self, path):
         """dtt_write (lib/ttio.f90:29-108): the resident train in the reference's stream format."""
@@ -511,6 +558,47 @@ class TTCross:
         v = c_double()
         _check(load_library().ttx_ijk(self._h, _ip(a), ctypes.byref(v)))
         return v.value
+
+    def tijk_batch(self, ind, mode="auto"):
+        """dtt_ijk at a batch of multi-indices (include/ttx.h: ttx_ijk_batch): ind (npts, d), 1-based; mode "exact", "mfma" or
+        "auto".  A host array gives a numpy array; a contiguous int32 torch tensor on the engine's device is passed by pointer
+        (ttx_ijk_batch_dev: nothing crosses the host link) and gives a float64 torch tensor on that device.  Points with an
+        entry outside 1..n(k) get -3.0."""
+        L, m = load_library(), _eval_mode(mode)
+        if type(ind).__module__.split(".")[0] == "torch":
+            import torch
+            if not ind.is_cuda:
+                return torch.from_numpy(self.tijk_batch(ind.numpy(), mode))
+            if ind.device.index != self.device:
+                raise ValueError(f"tijk_batch: the tensor lies on {ind.device}, the engine on device {self.device}")
+            if ind.dtype != torch.int32 or not ind.is_contiguous() or ind.dim() != 2 or ind.shape[1] != self.d:
+                raise ValueError(f"tijk_batch: a contiguous int32 tensor of shape (npts, {self.d}) expected")
+            out = torch.empty(ind.shape[0], dtype=torch.float64, device=ind.device)
+            torch.cuda.current_stream(ind.device).synchronize()      # the engine runs on a stream of its own
+            _check(L.ttx_ijk_batch_dev(self._h, ind.shape[0], c_void_p(ind.data_ptr()), c_void_p(out.data_ptr()), m))
+            return out
+        a = np.ascontiguousarray(ind, dtype=np.int32)
+        if a.ndim != 2 or a.shape[1] != self.d:
+            raise ValueError(f"tijk_batch: an array of shape (npts, {self.d}) expected")
+        out = np.zeros(a.shape[0])
+        _check(L.ttx_ijk_batch(self._h, a.shape[0], _ip(a), _dp(out), m))
+        return out
+
+    def value_batch(self, x, mode="auto"):
+        """dtt_value (lib/tt.f90:702-728) at a batch of coordinate vectors x (npts, dd) in [0,1]^dd; the digits are formed on the
+        device (value_indices restates them on the host).  A negative coordinate gives 0.0."""
+        xa = np.ascontiguousarray(x, dtype=np.float64)
+        if xa.ndim != 2 or xa.shape[1] < 1:
+            raise ValueError("value_batch: an array of shape (npts, dd) expected")
+        out = np.zeros(xa.shape[0])
+        _check(load_library().ttx_value_batch(self._h, xa.shape[0], xa.shape[1], _dp(xa), _dp(out), _eval_mode(mode)))
+        return out
+
+    @property
+    def eval_last_mode(self):
+        """'exact' or 'mfma': what the last tijk_batch / value_batch ran with (None before the first)."""
+        v = load_library().ttx_eval_last_mode(self._h)
+        return {0: "exact", 1: "mfma"}.get(v)
 
     def accchk(self, nlot):
         """dtt_accchk (lib/dmrgg.f90:1081): dict(einf, efro, ainf, afro, pivot) from nlot random samples."""

@@ -63,7 +63,7 @@ module tt_lib
  interface svd;         module procedure dtt_svd;  end interface
  interface norm;        module procedure dtt_norm; end interface
  interface dot_product; module procedure dtt_dot;  end interface
- interface tijk;        module procedure dtt_ijk;  end interface
+ interface tijk;        module procedure dtt_ijk,dtt_ijk_many;  end interface
 contains
  subroutine ztt_alloc(arg)
   type(ztt),intent(inout) :: arg
@@ -240,6 +240,28 @@ contains
   call dtt_stage(x,hx,tx,'dtt_dot'); call dtt_stage(y,hy,ty,'dtt_dot'); call ttx_check(ttx_dot(hx,hy,dot),'dtt_dot')
   if(tx)call ttx_destroy(hx)
   if(ty)call ttx_destroy(hy)
+ end function
+ function dtt_ijk_many(arg,ind) result(a)
+  ! tijk at many multi-indices, ind(d,npts): one batched call on the device (ttx_ijk_batch, the engine chooses the path); a host
+  ! train is staged for the call like for norm / dot_product; trains the engine does not hold (l /= 1, one core) go point by point
+  use ttx_c
+  type(dtt),intent(in) :: arg
+  integer,intent(in) :: ind(:,:)
+  double precision :: a(size(ind,2))
+  integer(c_int32_t),allocatable :: ix(:,:)
+  type(c_ptr) :: h
+  logical :: temp
+  integer :: p
+  if(size(ind,2).eq.0)return
+  if(.not.c_associated(arg%ttx) .and. (arg%l.ne.1 .or. arg%m.lt.2))then
+   do p=1,size(ind,2); a(p)=dtt_ijk(arg,ind(:,p)); end do
+   return
+  end if
+  allocate(ix(arg%m,size(ind,2))); ix=ind(1:arg%m,:)
+  call dtt_stage(arg,h,temp,'dtt_ijk')
+  call ttx_check(ttx_ijk_batch(h,int(size(ind,2),c_int64_t),ix,a,2_c_int32_t),'dtt_ijk')
+  if(temp)call ttx_destroy(h)
+  deallocate(ix)
  end function
  double precision function dtt_ijk(arg,ind) result(a)
   ! lib/tt.f90:630-652: one element; a resident train is asked on the device, a host train is contracted here

@@ -108,6 +108,18 @@ module ttx_c
   function ttx_ijk(h,ind,val) bind(C,name='ttx_ijk') result(rc)
    import; type(c_ptr),value :: h; integer(c_int32_t),intent(in) :: ind(*); real(c_double),intent(out) :: val; integer(c_int) :: rc
   end function
+  ! the train at a batch of multi-indices / coordinate vectors (include/ttx.h); mode: 0 exact, 1 MFMA, 2 auto
+  function ttx_ijk_batch(h,npts,ind,out,mode) bind(C,name='ttx_ijk_batch') result(rc)
+   import; type(c_ptr),value :: h; integer(c_int64_t),value :: npts; integer(c_int32_t),intent(in) :: ind(*)
+   real(c_double),intent(out) :: out(*); integer(c_int32_t),value :: mode; integer(c_int) :: rc
+  end function
+  function ttx_ijk_batch_dev(h,npts,ind_dev,out_dev,mode) bind(C,name='ttx_ijk_batch_dev') result(rc)
+   import; type(c_ptr),value :: h,ind_dev,out_dev; integer(c_int64_t),value :: npts; integer(c_int32_t),value :: mode; integer(c_int) :: rc
+  end function
+  function ttx_value_batch(h,npts,dd,x,out,mode) bind(C,name='ttx_value_batch') result(rc)
+   import; type(c_ptr),value :: h; integer(c_int64_t),value :: npts; integer(c_int32_t),value :: dd,mode
+   real(c_double),intent(in) :: x(*); real(c_double),intent(out) :: out(*); integer(c_int) :: rc
+  end function
   function ttx_accchk(h,nlot,einf,efro,ainf,afro,pivot) bind(C,name='ttx_accchk') result(rc)
    import; type(c_ptr),value :: h; integer(c_int32_t),value :: nlot; real(c_double),intent(out) :: einf,efro,ainf,afro
    integer(c_int32_t),intent(out) :: pivot(*); integer(c_int) :: rc
