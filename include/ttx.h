@@ -258,6 +258,11 @@ int ttx_set_profile(ttx_engine *h, int on);
  * 0 multi-kernel chain (k_lottery / k_halfstep / k_accept per bond), 1 one workgroup per bond group for the whole
  * sweep (k_sweep_fused), 2 a cluster of workgroups per bond group for the whole sweep (k_sweep_cluster) */
 int ttx_sweep_path(const ttx_engine *h);
+/* the integrand evaluator inside the cluster kernel (one instantiation of k_sweep_cluster each): 0 the engine is not on the cluster
+ * path, 1 exact chains with predicated remainders (any node values; TTX_CL_PAD=0 asks for it), 2 exact chains over rows padded to
+ * whole chunks of 8 with neutral elements (the default where every Ising node lies in [0,1]; same bits), 3 the closed form of
+ * TTX_ARITH_FAST */
+int ttx_cluster_eval(const ttx_engine *h);
 /* the arithmetic this engine evaluates its integrand with (TTX_ARITH_*): FAST only where ttx_config.arith / TTX_ARITH asked for
  * it AND the integrand has a re-associated evaluator (Ising D/E with all nodes in [0,1], mvn); everything else runs exact */
 int ttx_arith(const ttx_engine *h);

@@ -29,10 +29,6 @@
 #include "ttx_mvn.h"       // mvn_lane: one double of a wave by v_readlane
 
 #define CB 256      // threads of a cluster workgroup
-#ifndef TTX_CL_CF
-#define TTX_CL_CF 0    // factor entries of the residual requested before the evaluation (measured: 16 -> +1.4 % run time, registers)
-#endif
-#define F_ISING_CL f_ising_c4p
 #ifndef TTX_CL_UNR
 #define TTX_CL_UNR 16   // factor loads of the residual in flight per batch (8: +0.6 % run time, 32: no further gain)
 #endif
@@ -49,24 +45,57 @@ __device__ __forceinline__ double f_ising_c4p(int m, int A, const double *an, co
     double v = pv, w = pw, vk = pvk, wk = pwk;
     auto vstep = [&](double xv) { vk = vk * xv; v = v + vk; };
     auto wstep = [&](double xv) { wk = wk * xv; w = w + wk; };
-#ifndef TTX_CL_PIPE
-#define TTX_CL_PIPE 0      // 1: chain8p (LDS reads one chunk ahead of the dependent steps; measured 4 % slower: registers), 0: chain8v
-#endif
-#if TTX_CL_PIPE
-#define CHAIN8 chain8p
-#else
-#define CHAIN8 chain8v
-#endif
     vstep(s2n); vstep(s1n);
-    CHAIN8<true>(an, A, vstep);
+    chain8v<true>(an, A, vstep);
     wstep(s1n); wstep(s2n);
-    CHAIN8<false>(bn, nb, wstep);
+    chain8v<false>(bn, nb, wstep);
     double b = 1.0 / (v * w);
     double f = 2 * b;
     auto fstep = [&](double xv) { f = f * xv; };
-    CHAIN8<false>(aw, A, fstep);
+    chain8v<false>(aw, A, fstep);
     fstep(s1w); fstep(s2w);
-    CHAIN8<false>(bw, nb, fstep);
+    chain8v<false>(bw, nb, fstep);
+    return f;
+}
+
+// The same integrand from rows PADDED to whole chunks of 8 with neutral elements (staged so by k_sweep_cluster<false, true>): the
+// chains take chunk COUNTS (cA over the left row, cB over the right row) and hold no remainder and no test.
+//   * weight rows end in 1.0:  f * 1.0 == f, always;
+//   * node rows end in 0.0 BEHIND the last entry in processing order: vk = vk * 0.0 is +-0 while vk is finite and v + (+-0) == v
+//     for every v but -0 (v starts at 1.0 or at a prefix state that did, and only grows by products of nodes >= 0), so v and w come
+//     out bit for bit; vk and wk are dead behind the chain.  inf * 0.0 is NaN: the host takes this evaluator only after it has seen
+//     every node in [0,1] (all running products finite).
+// an is the left node row in PROCESSING order of the descending sum (dimension A first); aw, bn, bw are in dimension order.
+// One loop form: a chunk is four ds_read_b128 and 16 dependent instructions.  (A two-register-set form with the reads of chunk c+1
+// issued ahead of the steps of chunk c measured the same: profiles/HISTORY.md.)
+template <class STEP>
+__device__ __forceinline__ void chain8w(const double *p, int nc, STEP step)
+{
+#pragma unroll 1
+    for (int ch = 0; ch < nc; ch++) {
+        double x[8];
+        ld8d(p + 8 * ch, x);
+#pragma unroll
+        for (int k = 0; k < 8; k++) step(x[k]);
+    }
+}
+__device__ __forceinline__ double f_ising_c4w(int cA, int cB, const double *an, const double *aw, double s1n, double s1w,
+                                              double s2n, double s2w, const double *bn, const double *bw,
+                                              double pv, double pvk, double pw, double pwk)
+{
+    double v = pv, w = pw, vk = pvk, wk = pwk;
+    auto vstep = [&](double xv) { vk = vk * xv; v = v + vk; };
+    auto wstep = [&](double xv) { wk = wk * xv; w = w + wk; };
+    vstep(s2n); vstep(s1n);
+    chain8w(an, cA, vstep);
+    wstep(s1n); wstep(s2n);
+    chain8w(bn, cB, wstep);
+    double b = 1.0 / (v * w);
+    double f = 2 * b;
+    auto fstep = [&](double xv) { f = f * xv; };
+    chain8w(aw, cA, fstep);
+    fstep(s1w); fstep(s2w);
+    chain8w(bw, cB, fstep);
     return f;
 }
 
@@ -162,6 +191,10 @@ __device__ __forceinline__ bool cluster_sync(unsigned *ctr, unsigned target, int
 #define CST_END()
 #endif
 
+// CFAST: the closed form of TTX_ARITH=fast (f_ising_cfast) instead of the chains; CPAD: rows padded to whole chunks with neutral
+// elements and f_ising_c4w instead of f_ising_c4p.  Both are fixed for the life of an engine, so they are compiled in: the exact
+// kernels hold no closed-form arm and no fSL .. fWR, the fast kernel no chains in its hot loops.
+template <bool CFAST, bool CPAD>
 __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int nsteps, int NB, int ldsinv, int epoch, int zkeep)
 {
     extern __shared__ __align__(16) double dyn[];
@@ -172,8 +205,9 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
     __shared__ double pLw[64], pLk[64], pRv[64], pRk[64];   // prefix states of the two running sums per left / right row
     // TTX_ARITH=fast: per pivot row the sum of the partial products that start at the bond (left: descending, right: ascending) and
     // the product of its weights -- with them the integrand is a closed form of the two free nodes (f_ising_cfast)
-    __shared__ double fSL[64], fWL[64], fSR[64], fWR[64];
-    const bool cfast = P.arith != 0;
+    static_assert(!(CFAST && CPAD), "the closed form reads the rows in dimension order");
+    constexpr int NFT = CFAST ? 64 : 1;
+    __shared__ double fSL[NFT], fWL[NFT], fSR[NFT], fWR[NFT];
     // results of the rook loop, handed from wave 0 to the waves of the workgroup that own no fiber element at the current ranks
     __shared__ struct { int ii, jj, kk, qq, hcount, rc_k, rc_q, rr_i, rr_j; double pivot, amax, bytes_half; long long neval, n_resid; } s_rook;
     const int bid = blockIdx.x;
@@ -283,6 +317,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         double *Cp = core_ptr(P, P.col, g, p, first), *Wq = core_ptr(P, P.row, g, p + 1, first);
         double *Ap = core_ptr(P, P.arg, g, p, first), *Aq = core_ptr(P, P.arg, g, p + 1, first);
         const short *Lt = L_ptr(P, g, p - 1, first), *Rt = R_ptr(P, g, p + 1, first);
+        const int cA = (p - 1 + 7) >> 3, cB = (m - p - 1 + 7) >> 3;      // chunks of the left / right rows (f_ising_c4w)
         // ---- stage the value tables of both pivot sets (only the dimensions that exist on either side, rounded up to
         //      the 8-wide chunks the integrand reads; the walk over (row, dim) needs no division) ----
         {
@@ -291,8 +326,15 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                 int c = tid / AL, o = tid - c * AL;
                 const int dc = CB / AL, dO = CB - dc * AL;
                 while (c < r0) {
-                    const int ix = (o < p - 1) ? (int)Lt[(size_t)o * RM + c] : 1;
-                    XL[(size_t)c * RS + o] = par[ix - 1]; XL[(size_t)c * RS + VS + o] = par[n1m + ix - 1];
+                    if constexpr (CPAD) {          // nodes in the order the hot chain walks them (dimension p-1 first), neutral tails
+                        if (o < p - 1) {
+                            const int ix = (int)Lt[(size_t)o * RM + c];
+                            XL[(size_t)c * RS + (p - 2 - o)] = par[ix - 1]; XL[(size_t)c * RS + VS + o] = par[n1m + ix - 1];
+                        } else { XL[(size_t)c * RS + o] = 0.0; XL[(size_t)c * RS + VS + o] = 1.0; }
+                    } else {
+                        const int ix = (o < p - 1) ? (int)Lt[(size_t)o * RM + c] : 1;
+                        XL[(size_t)c * RS + o] = par[ix - 1]; XL[(size_t)c * RS + VS + o] = par[n1m + ix - 1];
+                    }
                     c += dc; o += dO; if (o >= AL) { o -= AL; c++; }
                 }
             }
@@ -300,8 +342,11 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                 int c = tid / AR, o = tid - c * AR;
                 const int dc = CB / AR, dO = CB - dc * AR;
                 while (c < r2) {
-                    const int ix = (o < m - p - 1) ? (int)Rt[(size_t)o * RM + c] : 1;
-                    XR[(size_t)c * RS + o] = par[ix - 1]; XR[(size_t)c * RS + VS + o] = par[n1m + ix - 1];
+                    if (CPAD && o >= m - p - 1) { XR[(size_t)c * RS + o] = 0.0; XR[(size_t)c * RS + VS + o] = 1.0; }
+                    else {
+                        const int ix = (o < m - p - 1) ? (int)Rt[(size_t)o * RM + c] : 1;
+                        XR[(size_t)c * RS + o] = par[ix - 1]; XR[(size_t)c * RS + VS + o] = par[n1m + ix - 1];
+                    }
                     c += dc; o += dO; if (o >= AR) { o -= AR; c++; }
                 }
             }
@@ -355,9 +400,11 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         if (tid < r0) {                                // ascending sum over the left row (dims 1..p-1)
             double w = 1.0, wk = 1.0;
             auto wstep = [&](double xv) { wk = wk * xv; w = w + wk; };
-            chain8v<false>(XL + (size_t)tid * RS, p - 1, wstep);
+            // (exact length: the final wk is kept.  Padded rows hold the nodes reversed: descending storage = ascending dimensions)
+            if constexpr (CPAD) chain8v<true>(XL + (size_t)tid * RS, p - 1, wstep);
+            else chain8v<false>(XL + (size_t)tid * RS, p - 1, wstep);
             pLw[tid] = w; pLk[tid] = wk;
-            if (cfast) {
+            if constexpr (CFAST) {
                 double sk = 1.0, ss = 0.0, ww = 1.0;
                 auto sstep = [&](double xv) { sk = sk * xv; ss = ss + sk; };
                 auto pstep = [&](double xv) { ww = ww * xv; };
@@ -371,7 +418,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
             auto vstep = [&](double xv) { vk = vk * xv; v = v + vk; };
             chain8v<true>(XR + (size_t)c * RS, m - p - 1, vstep);
             pRv[c] = v; pRk[c] = vk;
-            if (cfast) {
+            if constexpr (CFAST) {
                 double sk = 1.0, ss = 0.0, ww = 1.0;
                 auto sstep = [&](double xv) { sk = sk * xv; ss = ss + sk; };
                 auto pstep = [&](double xv) { ww = ww * xv; };
@@ -392,8 +439,10 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
             const int i = (x - 1) % r0 + 1, j = (x - 1) / r0 + 1, k = (y - 1) % n2 + 1, q = (y - 1) / n2 + 1;
             lot[4 * il] = i; lot[4 * il + 1] = j; lot[4 * il + 2] = k; lot[4 * il + 3] = q;
             const double *rl = XL + (size_t)(i - 1) * RS, *rq = XR + (size_t)(q - 1) * RS;
-            const double f = cfast ? f_ising_cfast(par[j - 1], par[n1m + j - 1], par[k - 1], par[n1m + k - 1], pRv[q - 1], pRk[q - 1], pLw[i - 1], pLk[i - 1], fSL[i - 1], fWL[i - 1], fSR[q - 1], fWR[q - 1])
-                                   : F_ISING_CL(m, p - 1, rl, rl + VS, par[j - 1], par[n1m + j - 1], par[k - 1], par[n1m + k - 1], rq, rq + VS, pRv[q - 1], pRk[q - 1], pLw[i - 1], pLk[i - 1]);
+            double f;
+            if constexpr (CFAST) f = f_ising_cfast(par[j - 1], par[n1m + j - 1], par[k - 1], par[n1m + k - 1], pRv[q - 1], pRk[q - 1], pLw[i - 1], pLk[i - 1], fSL[i - 1], fWL[i - 1], fSR[q - 1], fWR[q - 1]);
+            else if constexpr (CPAD) f = f_ising_c4w(cA, cB, rl, rl + VS, par[j - 1], par[n1m + j - 1], par[k - 1], par[n1m + k - 1], rq, rq + VS, pRv[q - 1], pRk[q - 1], pLw[i - 1], pLk[i - 1]);
+            else f = f_ising_c4p(m, p - 1, rl, rl + VS, par[j - 1], par[n1m + j - 1], par[k - 1], par[n1m + k - 1], rq, rq + VS, pRv[q - 1], pRk[q - 1], pLw[i - 1], pLk[i - 1]);
             ma = fmax(ma, fabs(f));
             CST(4);
             const double *c = Cp + (i - 1) + (size_t)RM * (j - 1), *w = Wq + (k - 1) + (size_t)NM * (q - 1);
@@ -462,24 +511,14 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                     const int i = u % r0, j = jlo + u / r0, t = i + r0 * j;
                     const double *rl = XL + (size_t)i * RS, *rq = XR + (size_t)(qq - 1) * RS;
                     const double *c = Cp + i + (size_t)RM * j;
-#if TTX_CL_CF
-                    double cf[TTX_CL_CF];                // the factor entries of this element's residual, requested BEFORE the evaluation
-                    if (resid) {
-#pragma unroll
-                        for (int s = 0; s < TTX_CL_CF; s++) if (s < r1u) cf[s] = c[P.SS * s];
-                    }
-#endif
-                    a = cfast ? f_ising_cfast(par[j], par[n1m + j], par[kk - 1], par[n1m + kk - 1], pRv[qq - 1], pRk[qq - 1], pLw[i], pLk[i], fSL[i], fWL[i], fSR[qq - 1], fWR[qq - 1])
-                              : F_ISING_CL(m, p - 1, rl, rl + VS, par[j], par[n1m + j], par[kk - 1], par[n1m + kk - 1], rq, rq + VS, pRv[qq - 1], pRk[qq - 1], pLw[i], pLk[i]);
+                    if constexpr (CFAST) a = f_ising_cfast(par[j], par[n1m + j], par[kk - 1], par[n1m + kk - 1], pRv[qq - 1], pRk[qq - 1], pLw[i], pLk[i], fSL[i], fWL[i], fSR[qq - 1], fWR[qq - 1]);
+                    else if constexpr (CPAD) a = f_ising_c4w(cA, cB, rl, rl + VS, par[j], par[n1m + j], par[kk - 1], par[n1m + kk - 1], rq, rq + VS, pRv[qq - 1], pRk[qq - 1], pLw[i], pLk[i]);
+                    else a = f_ising_c4p(m, p - 1, rl, rl + VS, par[j], par[n1m + j], par[kk - 1], par[n1m + kk - 1], rq, rq + VS, pRv[qq - 1], pRk[qq - 1], pLw[i], pLk[i]);
                     fib[u] = a;
                     if (resid) {
                         double b = a;
-#if TTX_CL_CF
-#pragma unroll
-                        for (int s = 0; s < TTX_CL_CF; s++) if (s < r1u) b = b + (-mvn_lane(xsv, s)) * cf[s];
-#endif
 #pragma unroll TTX_CL_UNR
-                        for (int s = TTX_CL_CF; s < r1u; s++) b = b + (-mvn_lane(xsv, s)) * c[P.SS * s];
+                        for (int s = 0; s < r1u; s++) b = b + (-mvn_lane(xsv, s)) * c[P.SS * s];
                         resc[u] = b;
                         const double aa = fabs(b);
                         if (aa > ab || (aa == ab && t < ix)) { ab = aa; bb = b; ix = t; }
@@ -488,24 +527,14 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                     const int k = klo + u % nk, q = u / nk, t = k + n2 * q;
                     const double *rl = XL + (size_t)(ii - 1) * RS, *rq = XR + (size_t)q * RS;
                     const double *w = Wq + k + (size_t)NM * q;
-#if TTX_CL_CF
-                    double cf[TTX_CL_CF];
-                    if (resid) {
-#pragma unroll
-                        for (int s = 0; s < TTX_CL_CF; s++) if (s < r1u) cf[s] = w[P.SW * s];
-                    }
-#endif
-                    a = cfast ? f_ising_cfast(par[jj - 1], par[n1m + jj - 1], par[k], par[n1m + k], pRv[q], pRk[q], pLw[ii - 1], pLk[ii - 1], fSL[ii - 1], fWL[ii - 1], fSR[q], fWR[q])
-                              : F_ISING_CL(m, p - 1, rl, rl + VS, par[jj - 1], par[n1m + jj - 1], par[k], par[n1m + k], rq, rq + VS, pRv[q], pRk[q], pLw[ii - 1], pLk[ii - 1]);
+                    if constexpr (CFAST) a = f_ising_cfast(par[jj - 1], par[n1m + jj - 1], par[k], par[n1m + k], pRv[q], pRk[q], pLw[ii - 1], pLk[ii - 1], fSL[ii - 1], fWL[ii - 1], fSR[q], fWR[q]);
+                    else if constexpr (CPAD) a = f_ising_c4w(cA, cB, rl, rl + VS, par[jj - 1], par[n1m + jj - 1], par[k], par[n1m + k], rq, rq + VS, pRv[q], pRk[q], pLw[ii - 1], pLk[ii - 1]);
+                    else a = f_ising_c4p(m, p - 1, rl, rl + VS, par[jj - 1], par[n1m + jj - 1], par[k], par[n1m + k], rq, rq + VS, pRv[q], pRk[q], pLw[ii - 1], pLk[ii - 1]);
                     fib[u] = a;
                     if (resid) {
                         double tt = 0.0;
-#if TTX_CL_CF
-#pragma unroll
-                        for (int s = 0; s < TTX_CL_CF; s++) if (s < r1u) tt = tt + cf[s] * mvn_lane(xsv, s);
-#endif
 #pragma unroll TTX_CL_UNR
-                        for (int s = TTX_CL_CF; s < r1u; s++) tt = tt + w[P.SW * s] * mvn_lane(xsv, s);
+                        for (int s = 0; s < r1u; s++) tt = tt + w[P.SW * s] * mvn_lane(xsv, s);
                         const double b = a + (-1.0) * tt;
                         resr[u] = b;
                         const double aa = fabs(b);

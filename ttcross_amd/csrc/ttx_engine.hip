@@ -40,6 +40,12 @@
 #include "ttx_ttops.h"
 #include "ttx_fused.h"
 #include "ttx_cluster.h"
+// the instantiation of the cluster kernel an engine runs (ttx_engine::cluster_var)
+typedef void (*cluster_kernel_t)(DevProb, int, int, int, int, int, int);
+static cluster_kernel_t cluster_kernel(int var)
+{
+    return var == 2 ? k_sweep_cluster<true, false> : var == 1 ? k_sweep_cluster<false, true> : k_sweep_cluster<false, false>;
+}
 #include "ttx_coscoeff.h"
 #include "ttx_eval.h"
 
@@ -165,6 +171,8 @@ struct ttx_engine {
     int cluster_zkeep = 0;              // cluster kernel keeps the sorted pivot lists of all own bonds in LDS
     int cluster_ldsinv = 0;             // cluster kernel keeps the neighbour LU factors in LDS
     int cluster = 0;                    // workgroups per bond group of the cluster sweep kernel (ttx_cluster.h); 0: not used
+    int cluster_var = 0;                // its instantiation (cluster_kernel): 0 exact, remainders predicated; 1 exact, rows padded to whole chunks; 2 closed form
+    bool unit_nodes = false;            // Ising: every node the integrand can read lies in [0,1]
     size_t lds_cluster = 0;
     int *h_abort = nullptr;             // pinned, device-visible: the cluster kernel's barrier-timeout flag
     int cluster_coop = 0;               // launch the cluster kernel with hipLaunchCooperativeKernel
@@ -390,6 +398,7 @@ static double powi(double a, int b)
 }
 
 static int ensure_lds(const void *fn, size_t need, size_t &cur);
+static int ensure_lds_cluster(ttx_engine *h);
 
 // nofun: an engine that only holds a tensor train (ttx_from_tt / ttx_read): no integrand, ttx_run refused
 static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
@@ -504,6 +513,7 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
         nnode = std::min(nnode, (int)cfg->npar);
         bool unit = true;               // Ising: all nodes in [0,1] (every running product non-increasing: the cut at 2^-54 is valid)
         if (cfg->fun_id == TTX_FUN_ISING) for (int j = 0; j < nnode; j++) if (!(cfg->par[j] >= 0.0 && cfg->par[j] <= 1.0)) unit = false;
+        h->unit_nodes = cfg->fun_id == TTX_FUN_ISING && unit;
         P.arith = (want && !nofun && ((cfg->fun_id == TTX_FUN_ISING && P.ising_id != 1 && unit) || cfg->fun_id == TTX_FUN_MVN)) ? 1 : 0;
         if (P.arith) {
             P.FD = d + 1;
@@ -708,13 +718,18 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
             const size_t zk = sizeof(int) * ((size_t)h->nbmax * 2 * RM + 2 * h->nbmax + 4);
             if (h->lds_cluster + zk <= 150 * 1024) { h->cluster_zkeep = 1; h->lds_cluster += zk; }
         }
+        // instantiation of the cluster kernel: the closed form where fast arithmetic was asked for; else rows padded to whole chunks
+        // (f_ising_c4w) where the pad is neutral -- every node in [0,1], so that no running product overflows (inf * 0.0 is NaN) --
+        // unless TTX_CL_PAD=0 asks for the predicated remainders (f_ising_c4p), which hold for any node (ttx_cluster_eval tells)
+        const bool cfastc = h->want_fast && cfg->fun_id == TTX_FUN_ISING && P.ising_id == 1;
+        if (const char *e = getenv("TTX_CL_PAD")) if (strcmp(e, "0") && strcmp(e, "1")) { ttx_destroy(h); return fail(TTX_EINVAL, "TTX_CL_PAD must be 0 or 1 (got %s)", e); }
+        h->cluster_var = cfastc ? 2 : (h->unit_nodes && !(getenv("TTX_CL_PAD") && atoi(getenv("TTX_CL_PAD")) == 0)) ? 1 : 0;
         bool cluster_ok = fastc && h->RM <= 64 && NB >= 2 && h->G * NB <= prop.multiProcessorCount && h->lds_cluster <= 150 * 1024;
         if (cluster_ok) {
             // residency: what the device can hold of THIS kernel with THIS much dynamic LDS; the grid may use half of it
-            static size_t a_cl0 = 0;
-            if ((rc = ensure_lds(reinterpret_cast<const void *>(k_sweep_cluster), h->lds_cluster, a_cl0))) { ttx_destroy(h); return rc; }
+            if ((rc = ensure_lds_cluster(h))) { ttx_destroy(h); return rc; }
             int occ = 0;
-            HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_sweep_cluster, CB, h->lds_cluster));
+            HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cluster_kernel(h->cluster_var), CB, h->lds_cluster));
             const long long cap = (long long)occ * prop.multiProcessorCount;
             const long long grid = 8LL * NB * ((h->G + 7) / 8);
             if (grid * 2 > cap) cluster_ok = false;
@@ -730,7 +745,7 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
         else if (want == "auto") { if (cluster_ok) h->cluster = NB; else if (fused_ok && h->G == 1) h->fused = 1; }
         else if (want != "chain") { ttx_destroy(h); return fail(TTX_EINVAL, "TTX_SWEEP must be auto, chain, fused or cluster (got %s)", want.c_str()); }
         // TTX_ARITH=fast for Ising C: a closed form inside the cluster kernel (f_ising_cfast); the other paths evaluate C exactly
-        if (h->cluster && h->want_fast && cfg->fun_id == TTX_FUN_ISING && P.ising_id == 1) P.arith = 1;
+        if (h->cluster && cfastc) P.arith = 1;
         if (h->cluster) {
             unsigned *ctr; ClPart *cp;
             rc = dev_alloc(h, &ctr, (size_t)h->G); if (rc) { ttx_destroy(h); return rc; }
@@ -1434,6 +1449,12 @@ static int ensure_lds(const void *fn, size_t need, size_t &cur)
     return TTX_OK;
 }
 
+static int ensure_lds_cluster(ttx_engine *h)
+{
+    static size_t a_cluster[3] = {0, 0, 0};        // per instantiation
+    return ensure_lds(reinterpret_cast<const void *>(cluster_kernel(h->cluster_var)), h->lds_cluster, a_cluster[h->cluster_var]);
+}
+
 // the whole-sweep cluster kernel: cooperative launch (the runtime guarantees -- or refuses -- co-residency of the grid)
 static int launch_cluster(ttx_engine *h, int dir, int epoch)
 {
@@ -1442,9 +1463,9 @@ static int launch_cluster(ttx_engine *h, int dir, int epoch)
     const dim3 grid(8 * h->cluster * ((h->G + 7) / 8)), block(CB);
     if (h->cluster_coop) {
         void *args[] = {&P, &dir, &nsteps, &NB, &ldsinv, &epoch, &zkeep};
-        HIPCHECK(hipLaunchCooperativeKernel(reinterpret_cast<const void *>(k_sweep_cluster), grid, block, args, (unsigned)h->lds_cluster, h->stream));
+        HIPCHECK(hipLaunchCooperativeKernel(reinterpret_cast<const void *>(cluster_kernel(h->cluster_var)), grid, block, args, (unsigned)h->lds_cluster, h->stream));
     } else
-        hipLaunchKernelGGL(k_sweep_cluster, grid, block, h->lds_cluster, h->stream, P, dir, nsteps, NB, ldsinv, epoch, zkeep);
+        hipLaunchKernelGGL(cluster_kernel(h->cluster_var), grid, block, h->lds_cluster, h->stream, P, dir, nsteps, NB, ldsinv, epoch, zkeep);
     return TTX_OK;
 }
 
@@ -1462,11 +1483,11 @@ static int run_impl(ttx_engine *h)
 
     // kernels that may stage more than the default 64 KB of dynamic LDS (160 KB per CU on gfx950)
     {   // the dynamic-LDS ceiling is a property of the FUNCTION: raise it when an engine needs more than any before it
-        static size_t a_half = 0, a_lot = 0, a_fused = 0, a_cluster = 0;        // per instantiation (FUN) of this template
+        static size_t a_half = 0, a_lot = 0, a_fused = 0;        // per instantiation (FUN) of this template
         if ((rc = ensure_lds(reinterpret_cast<const void *>(k_halfstep<FUN>), h->lds_half, a_half))) return rc;
         if ((rc = ensure_lds(reinterpret_cast<const void *>(k_lottery<FUN>), h->lds_lot, a_lot))) return rc;
         if (h->fused && (rc = ensure_lds(reinterpret_cast<const void *>(k_sweep_fused), h->lds_fused, a_fused))) return rc;
-        if (h->cluster && (rc = ensure_lds(reinterpret_cast<const void *>(k_sweep_cluster), h->lds_cluster, a_cluster))) return rc;
+        if (h->cluster && (rc = ensure_lds_cluster(h))) return rc;
         static size_t a_de0 = 0, a_de1 = 0;
         static size_t a_dec = 0;
         static size_t a_dlc = 0, a_dlp = 0;
@@ -3094,6 +3115,7 @@ extern "C" int ttx_value_batch(ttx_engine *h, int64_t npts, int32_t dd, const do
 extern "C" int ttx_arith(const ttx_engine *h) { return h ? h->P.arith : -1; }
 extern "C" int ttx_sweep_path(const ttx_engine *h) { return !h ? -1 : h->cluster ? 2 : h->fused ? 1 : 0; }
 extern "C" int64_t ttx_resid_halfsteps(const ttx_engine *h) { return h ? h->n_resid : 0; }
+extern "C" int ttx_cluster_eval(const ttx_engine *h) { return !h ? -1 : h->cluster ? 1 + h->cluster_var : 0; }
 extern "C" int ttx_cluster_fallbacks(const ttx_engine *h) { return h ? h->cluster_fallbacks : 0; }
 extern "C" int ttx_det_fallbacks(const ttx_engine *h) { return h ? h->det_fallbacks + h->de5_fallbacks : 0; }
 extern "C" int ttx_fun_id(const ttx_engine *h) { return h ? h->cfg.fun_id : -1; }

@@ -440,6 +440,14 @@ class TTCross:
         L.ttx_sweep_path.argtypes = [c_void_p]
         return ("chain", "fused", "cluster")[L.ttx_sweep_path(self._h)]
 
+    def cluster_eval(self):
+        """Integrand evaluator of the cluster sweep kernel: 'none' (not on that path), 'predicated' (exact, remainders of the
+        chains tested per step: TTX_CL_PAD=0 or a node outside [0,1]), 'chunks' (exact, rows padded to whole chunks) or 'closed'
+        (TTX_ARITH=fast) (include/ttx.h: ttx_cluster_eval)."""
+        L = load_library()
+        L.ttx_cluster_eval.argtypes = [c_void_p]
+        return ("none", "predicated", "chunks", "closed")[L.ttx_cluster_eval(self._h)]
+
     @property
     def resid_halfsteps(self):
         L = load_library()
