@@ -84,7 +84,8 @@ typedef struct ttx_sweep_rec {
 } ttx_sweep_rec;
 
 const char *ttx_last_error(void);
-int ttx_version(void);   /* 2: loadable device integrands; 3: ttx_ijk_batch, ttx_ijk_batch_dev, ttx_value_batch */
+int ttx_version(void);   /* 2: loadable device integrands; 3: ttx_ijk_batch, ttx_ijk_batch_dev, ttx_value_batch (ttx_contract and
+                          * ttx_marginals came later without a new number: look the symbols up) */
 
 /* allocate device state for one dtt_dmrgg problem (replaces the implicit set-up of lib/dmrgg.f90:58-148) */
 int ttx_create(ttx_engine **out, const ttx_config *cfg);
@@ -217,6 +218,30 @@ int ttx_eval_last_mode(const ttx_engine *h);       /* TTX_EVAL_EXACT or TTX_EVAL
  * sets (the 32 frequencies of test_crs_chf.f90:153-168 in one call): w = nf blocks of sum(n) interleaved (re, im)
  * doubles, out = nf (re, im) pairs.  Multi-process engines: collective, the value on every process. */
 int ttx_zquad(ttx_engine *h, int32_t nf, const double *w, double *out);
+
+/* Partial contraction of the resident train with rank-1 weights.
+ *   keep : d entries, 1 = the mode survives, 0 = it is summed against its weights
+ *   w    : d blocks of n[k] weights as for ttx_quad (blocks of kept modes are ignored); NULL = all ones (plain sums)
+ *   *out : a new single-process engine without integrand (as ttx_from_tt: everything but ttx_run / ttx_accchk works),
+ *          owned by the caller.  The source engine and its work space are not modified.
+ * A slice is the same operation with a unit vector as the weight of the fixed mode.
+ * The result: let the kept modes be k_1 < ... < k_m and M_k = sum_i w_k(i) G_k(:, i, :) for a contracted mode.  New core j is
+ * P_j G_(k_j), P_j the ordered product of the M_k between k_(j-1) and k_j (none: no product is formed); the M_k after k_m are
+ * multiplied into the last new core from the right.  Ranks: r'(0) = 1, r'(j) = r(k_j) for j < m, r'(m) = 1.  With nothing
+ * contracted the result is a bit-identical deep copy.
+ * Arithmetic is plain double, as ttx_quad: there is NO running exponent, a train whose partial products leave the double range
+ * over- or underflows.  Weights are not inspected: NaN and Inf propagate.  Sums have a fixed order: a call repeats bit for bit.
+ * Everything is enqueued on the source engine's stream and the call synchronises before it returns; the new cores are written
+ * device to device into storage sized by the new train's own largest rank and mode: no core crosses the host link.
+ * TTX_EINVAL: null keep / out, a keep entry other than 0 or 1, fewer than two kept modes (the engine holds trains of at least two
+ * cores: ttx_marginals gives one-mode marginals, ttx_quad the full sum); TTX_ESTATE: an engine without a train; a multi-process
+ * engine is refused as by ttx_ijk (a replica, ttx_replicate, is accepted).  After a refusal *out is NULL and nothing stays allocated. */
+int ttx_contract(ttx_engine *h, const int32_t *keep, const double *w, ttx_engine **out);
+/* all d one-mode marginals in one call: out = d blocks of n[k], block k(i) = sum over every other mode against its weights */
+int ttx_marginals(ttx_engine *h, const double *w, double *out);
+/* the mode-sum kernel of the last ttx_contract / ttx_marginals on this engine: its milliseconds (HIP events) and the bytes of the
+ * cores it summed, 8 sum r(k-1) n(k) r(k) over the contracted modes (0 ms when nothing was contracted) */
+int ttx_contract_modesum(const ttx_engine *h, double *ms, double *bytes);
 
 /* The finalised train of a MULTI-PROCESS job gathered onto EVERY process as a new single-process engine (same integrand, ranks,
  * RNG position; *out is owned by the caller: ttx_destroy).  Collective over the job's transport (each process contributes the

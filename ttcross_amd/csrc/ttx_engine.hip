@@ -48,6 +48,7 @@ static cluster_kernel_t cluster_kernel(int var)
 }
 #include "ttx_coscoeff.h"
 #include "ttx_eval.h"
+#include "ttx_contract.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const char *fmt, ...)
@@ -60,7 +61,7 @@ static int fail(int code, const char *fmt, ...)
 #define HIPCHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(TTX_EHIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 extern "C" const char *ttx_last_error(void) { return g_err.c_str(); }
-extern "C" int ttx_version(void) { return 3; }      // 2: loadable device integrands; 3: ttx_ijk_batch, ttx_ijk_batch_dev, ttx_value_batch
+extern "C" int ttx_version(void) { return 3; }      // 2: loadable device integrands; 3: ttx_ijk_batch, ttx_ijk_batch_dev, ttx_value_batch (ttx_contract, ttx_marginals: added without a new number)
 
 
 // RCCL entry points, resolved at run time (single-GPU users never load librccl)
@@ -192,6 +193,12 @@ struct ttx_engine {
     EvBuf ev[EV_NBUF];
     std::vector<char> ev_meta_host;
     int ev_last_mode = -1;              // TTX_EVAL_* the last batch ran with
+    // partial contraction (ttx_contract.h): the M matrices, run products and vectors, grown on demand, freed in ttx_destroy
+    enum { CT_META, CT_W, CT_M, CT_P, CT_SCR, CT_VEC, CT_OUT, CT_NBUF };
+    EvBuf ct[CT_NBUF];
+    std::vector<char> ct_meta_host;
+    hipEvent_t ct_ev[2] = {nullptr, nullptr};   // around the mode-sum kernel of the last call (ttx_contract_modesum_ms)
+    double ct_ms = 0.0, ct_bytes = 0.0;
 };
 
 // ---- worker threads for the host integrand (the reference evaluates `fun` inside !$OMP PARALLEL DO regions,
@@ -827,6 +834,8 @@ extern "C" void ttx_destroy(ttx_engine *h)
     if (h->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(h->comm);
     for (void *p : h->allocs) (void)hipFree(p);
     for (auto &b : h->ev) if (b.p) (void)hipFree(b.p);
+    for (auto &b : h->ct) if (b.p) (void)hipFree(b.p);
+    for (auto &e : h->ct_ev) if (e) (void)hipEventDestroy(e);
     if (h->h_sum_base) (void)hipHostFree(h->h_sum_base);
     if (h->h_val) (void)hipHostFree(h->h_val);
     if (h->h_svd) (void)hipHostFree(h->h_svd);
@@ -2101,13 +2110,13 @@ extern "C" int ttx_get_modes(const ttx_engine *h, int32_t *d, int32_t *n)
     return TTX_OK;
 }
 
-extern "C" int ttx_from_tt(ttx_engine **out, int32_t d, const int32_t *n, const int32_t *r, const double *cores, int32_t device)
+// a new single-process engine without integrand whose resident train has the given modes and ranks; the cores are the caller's to fill
+static int train_shell(ttx_engine **out, const char *who, int32_t d, const int32_t *n, const int32_t *r, int32_t device)
 {
-    if (!out || !n || !r || !cores) return fail(TTX_EINVAL, "ttx_from_tt: null argument");
     *out = nullptr;
-    if (d < 2) return fail(TTX_EINVAL, "ttx_from_tt: at least two cores are needed (got %d)", d);
+    if (d < 2) return fail(TTX_EINVAL, "%s: at least two cores are needed (got %d)", who, d);
     int rmax = 1;
-    for (int k = 0; k <= d; k++) { if (r[k] < 1) return fail(TTX_EINVAL, "ttx_from_tt: rank r(%d)=%d", k, r[k]); rmax = std::max(rmax, (int)r[k]); }
+    for (int k = 0; k <= d; k++) { if (r[k] < 1) return fail(TTX_EINVAL, "%s: rank r(%d)=%d", who, k, r[k]); rmax = std::max(rmax, (int)r[k]); }
     // ort/svd may pass through r(k) = min(r(k-1)*n(k), ...) <= the incoming ranks, so max(r) is enough storage
     ttx_config c{};
     c.d = d; c.n = n; c.fun_id = 0; c.accuracy = -1.0; c.maxrank = rmax; c.pivoting = 0; c.nproc = 1; c.device = device; c.world_size = 1;
@@ -2118,23 +2127,34 @@ extern "C" int ttx_from_tt(ttx_engine **out, int32_t d, const int32_t *n, const 
     g0->first = 1; g0->last = d - 1; g0->gglobal = 0;
     hipError_t e = hipMemcpy(h->P.gs, g0, offsetof(GroupState, S), hipMemcpyHostToDevice);
     free(g0);
-    if (e != hipSuccess) { ttx_destroy(h); return fail(TTX_EHIP, "ttx_from_tt: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { ttx_destroy(h); return fail(TTX_EHIP, "%s: %s", who, hipGetErrorString(e)); }
     h->rfinal.assign(r, r + d + 1);
+    std::vector<int32_t> rr((size_t)(d + 2), 1);
+    for (int p = 0; p <= d; p++) rr[p] = r[p];
+    e = hipMemcpy(h->P.r, rr.data(), sizeof(int32_t) * rr.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { ttx_destroy(h); return fail(TTX_EHIP, "%s: %s", who, hipGetErrorString(e)); }
+    h->ran = true;
+    *out = h;
+    return TTX_OK;
+}
+
+extern "C" int ttx_from_tt(ttx_engine **out, int32_t d, const int32_t *n, const int32_t *r, const double *cores, int32_t device)
+{
+    if (!out || !n || !r || !cores) return fail(TTX_EINVAL, "ttx_from_tt: null argument");
+    ttx_engine *h = nullptr;
+    int rc = train_shell(&h, "ttx_from_tt", d, n, r, device);
+    *out = nullptr;
+    if (rc) return rc;
     size_t off = 0;
     for (int k = 1; k <= d; k++) {
         const int r0 = r[k - 1], r1 = r[k], nk = n[k - 1];
         double *dst = h->P.arg + (size_t)(k - 1) * h->P.CS;
         for (int s = 0; s < r1; s++) {        // compact host -> padded device slabs (inverse of ttx_get_core)
-            e = hipMemcpy2D(dst + h->P.SS * s, sizeof(double) * h->RM, cores + off + (size_t)r0 * nk * s, sizeof(double) * r0, sizeof(double) * r0, nk, hipMemcpyHostToDevice);
+            hipError_t e = hipMemcpy2D(dst + h->P.SS * s, sizeof(double) * h->RM, cores + off + (size_t)r0 * nk * s, sizeof(double) * r0, sizeof(double) * r0, nk, hipMemcpyHostToDevice);
             if (e != hipSuccess) { ttx_destroy(h); return fail(TTX_EHIP, "ttx_from_tt: %s", hipGetErrorString(e)); }
         }
         off += (size_t)r0 * nk * r1;
     }
-    std::vector<int32_t> rr((size_t)(d + 2), 1);
-    for (int p = 0; p <= d; p++) rr[p] = r[p];
-    e = hipMemcpy(h->P.r, rr.data(), sizeof(int32_t) * rr.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { ttx_destroy(h); return fail(TTX_EHIP, "ttx_from_tt: %s", hipGetErrorString(e)); }
-    h->ran = true;
     *out = h;
     return TTX_OK;
 }
@@ -2937,15 +2957,15 @@ extern "C" int ttx_ijk(ttx_engine *h, const int32_t *ind, double *val)
 }
 
 // ---- the train at a batch of multi-indices (ttx_eval.h) -------------------------------------------------------------------------
-static int ev_reserve(ttx_engine *h, int which, size_t bytes)
+static int buf_reserve(ttx_engine *h, ttx_engine::EvBuf &b, size_t bytes)
 {
-    auto &b = h->ev[which];
     if (b.p && b.bytes >= bytes) return TTX_OK;
     if (b.p) { HIPCHECK(hipStreamSynchronize(h->stream)); (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; }
     HIPCHECK(hipMalloc(&b.p, bytes + 64));
     b.bytes = bytes;
     return TTX_OK;
 }
+static int ev_reserve(ttx_engine *h, int which, size_t bytes) { return buf_reserve(h, h->ev[which], bytes); }
 // points per chunk: bounds the work space (two state buffers of chunk x max rank doubles on the MFMA path, the index block of the host entry)
 static size_t ev_chunk(const ttx_engine *h)
 {
@@ -3120,6 +3140,190 @@ extern "C" int ttx_cluster_fallbacks(const ttx_engine *h) { return h ? h->cluste
 extern "C" int ttx_det_fallbacks(const ttx_engine *h) { return h ? h->det_fallbacks + h->de5_fallbacks : 0; }
 extern "C" int ttx_fun_id(const ttx_engine *h) { return h ? h->cfg.fun_id : -1; }
 extern "C" int ttx_set_profile(ttx_engine *h, int on) { if (!h) return fail(TTX_EINVAL, "null"); h->profile = on != 0; return TTX_OK; }
+// ---- chosen modes contracted with rank-1 weights (ttx_contract.h) ---------------------------------------------------------------
+namespace {
+struct CtPlan {
+    std::vector<CtCore> cores;          // every source core
+    std::vector<CtTile> tiles;          // mode-sum tiles of the contracted ones
+    std::vector<int> r;                 // r(0:d)
+    std::vector<size_t> moff;
+    size_t msize = 0, wsize = 0;
+    double bytes = 0.0;                 // 8 sum r0 n r1 over the contracted cores
+};
+// device image of the call's tables: arrays appended at 16-byte boundaries, uploaded in one copy
+struct CtMeta {
+    std::vector<char> &buf;
+    explicit CtMeta(std::vector<char> &b) : buf(b) { buf.clear(); }
+    template <class T> size_t put(const std::vector<T> &v)
+    {
+        const size_t off = (buf.size() + 15) & ~(size_t)15;
+        buf.resize(off + sizeof(T) * std::max<size_t>(v.size(), 1));
+        if (!v.empty()) memcpy(buf.data() + off, v.data(), sizeof(T) * v.size());
+        return off;
+    }
+};
+}
+static void ct_plan(ttx_engine *h, const std::vector<char> &contracted, CtPlan &pl)
+{
+    const int d = h->d;
+    pl.r.assign(h->rfinal.begin(), h->rfinal.begin() + d + 1);
+    pl.cores.resize(d); pl.moff.assign(d, 0);
+    for (int k = 0; k < d; k++) {
+        CtCore &c = pl.cores[k];
+        c.src = core_dev(h, k + 1); c.r0 = pl.r[k]; c.n = h->n1[k + 1]; c.r1 = pl.r[k + 1];
+        c.ta = 1; while (c.ta < 64 && c.ta < c.r0) c.ta <<= 1;
+        c.woff = pl.wsize; pl.wsize += c.n;
+        c.moff = 0;
+        if (!contracted[k]) continue;
+        c.moff = pl.moff[k] = pl.msize; pl.msize += (size_t)c.r0 * c.r1;
+        pl.bytes += 8.0 * c.r0 * c.n * c.r1;
+        const int tb = 256 / c.ta;
+        for (int b0 = 0; b0 < c.r1; b0 += tb) for (int a0 = 0; a0 < c.r0; a0 += c.ta) pl.tiles.push_back(CtTile{k, a0, b0, 0});
+    }
+}
+// weights to the device (NULL: ones) and the mode-sum launch, bracketed by the engine's two events
+static int ct_modesum(ttx_engine *h, const CtPlan &pl, const double *w, const CtCore *dcores, const CtTile *dtiles)
+{
+    int rc;
+    if ((rc = buf_reserve(h, h->ct[ttx_engine::CT_W], sizeof(double) * pl.wsize)) || (rc = buf_reserve(h, h->ct[ttx_engine::CT_M], sizeof(double) * std::max<size_t>(pl.msize, 1)))) return rc;
+    std::vector<double> ones;
+    if (!w) { ones.assign(pl.wsize, 1.0); w = ones.data(); }
+    HIPCHECK(hipMemcpyAsync(h->ct[ttx_engine::CT_W].p, w, sizeof(double) * pl.wsize, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));                                  // `ones` leaves scope
+    for (auto &e : h->ct_ev) if (!e) HIPCHECK(hipEventCreate(&e));
+    h->ct_ms = 0.0; h->ct_bytes = pl.bytes;
+    if (pl.tiles.empty()) return TTX_OK;
+    HIPCHECK(hipEventRecord(h->ct_ev[0], h->stream));
+    hipLaunchKernelGGL(k_ct_modesum, dim3((unsigned)pl.tiles.size()), dim3(256), 0, h->stream, dcores, dtiles, h->RM, h->P.SS,
+                       (const double *)h->ct[ttx_engine::CT_W].p, (double *)h->ct[ttx_engine::CT_M].p);
+    HIPCHECK(hipEventRecord(h->ct_ev[1], h->stream));
+    return TTX_OK;
+}
+static int ct_finish(ttx_engine *h, bool timed)
+{
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipGetLastError());
+    if (timed) { float ms = 0.f; HIPCHECK(hipEventElapsedTime(&ms, h->ct_ev[0], h->ct_ev[1])); h->ct_ms = ms; }
+    return TTX_OK;
+}
+// the engines ttx_ijk takes: a train, one process (a multi-process engine gets tt_prepare's answer)
+static int ct_check(ttx_engine *h, const char *who)
+{
+    if (!h || !h->ran) return fail(TTX_ESTATE, "%s: no tensor train (run dtt_dmrgg first)", who);
+    if (h->W > 1) return tt_prepare(h, who);
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    return TTX_OK;
+}
+// everything of ttx_contract that works on the new engine e: a failure leaves e to the caller to destroy
+static int ct_fill(ttx_engine *h, ttx_engine *e, const std::vector<int> &kept, const double *w)
+{
+    const int d = h->d, m = (int)kept.size();
+    std::vector<char> contracted(d, 1);
+    for (int k : kept) contracted[k] = 0;
+    CtPlan pl;
+    ct_plan(h, contracted, pl);
+    const std::vector<int> &r = pl.r;
+    // maximal runs of contracted modes: before the first kept mode, between two kept modes, after the last
+    std::vector<CtRun> runs;
+    std::vector<int> run_left(m, -1);           // run ending just before kept mode j
+    int run_trail = -1;
+    size_t psize = 0, ssize = 0;
+    for (int j = 0; j <= m; j++) {
+        const int a = j ? kept[j - 1] + 1 : 0, b = (j < m ? kept[j] : d) - 1;
+        if (b < a) continue;
+        CtRun R{};
+        R.k0 = a; R.cnt = b - a + 1; R.kind = j == 0 ? 0 : j == m ? 1 : 2; R.wmax = 1;
+        for (int k = a; k <= b; k++) R.wmax = std::max(R.wmax, r[k + 1]);
+        R.poff = psize; R.soff = ssize;
+        psize += R.kind == 2 ? (size_t)r[a] * r[b + 1] : R.kind == 0 ? (size_t)r[b + 1] : (size_t)r[a];
+        if (R.kind == 2 && 2 * (size_t)r[a] * R.wmax > TTX_CT_LDS) ssize += 2 * (size_t)r[a] * R.wmax;
+        if (j < m) run_left[j] = (int)runs.size(); else run_trail = (int)runs.size();
+        runs.push_back(R);
+    }
+    int rc;
+    if ((rc = buf_reserve(h, h->ct[ttx_engine::CT_P], sizeof(double) * std::max<size_t>(psize, 1))) ||
+        (rc = buf_reserve(h, h->ct[ttx_engine::CT_SCR], sizeof(double) * std::max<size_t>(ssize, 1)))) return rc;
+    const double *Pb = (const double *)h->ct[ttx_engine::CT_P].p;
+    std::vector<CtKeep> keeps(m);
+    long long items = 0;
+    for (int j = 0; j < m; j++) {
+        const int k = kept[j];
+        CtKeep &K = keeps[j];
+        K.src = pl.cores[k].src; K.dst = core_dev(e, j + 1);
+        K.r0 = r[k]; K.n = h->n1[k + 1]; K.r1 = r[k + 1];
+        K.P = run_left[j] >= 0 ? Pb + runs[run_left[j]].poff : nullptr;
+        K.q0 = run_left[j] >= 0 ? r[runs[run_left[j]].k0] : K.r0;
+        K.t = (j == m - 1 && run_trail >= 0) ? Pb + runs[run_trail].poff : nullptr;
+        K.ncol = (K.n + 15) / 16; K.first = items; K.pad = 0;
+        items += (long long)K.ncol * (K.t ? 1 : K.r1);
+    }
+    if (items > 0x7fffffffll) return fail(TTX_EINVAL, "ttx_contract: too many column tiles (%lld)", items);
+    CtMeta meta(h->ct_meta_host);
+    const size_t o_cores = meta.put(pl.cores), o_tiles = meta.put(pl.tiles), o_runs = meta.put(runs), o_r = meta.put(r), o_moff = meta.put(pl.moff), o_keeps = meta.put(keeps);
+    if ((rc = buf_reserve(h, h->ct[ttx_engine::CT_META], h->ct_meta_host.size()))) return rc;
+    char *dm = (char *)h->ct[ttx_engine::CT_META].p;
+    HIPCHECK(hipMemcpyAsync(dm, h->ct_meta_host.data(), h->ct_meta_host.size(), hipMemcpyHostToDevice, h->stream));
+    if ((rc = ct_modesum(h, pl, w, (const CtCore *)(dm + o_cores), (const CtTile *)(dm + o_tiles)))) return rc;
+    if (!runs.empty())
+        hipLaunchKernelGGL(k_ct_runs, dim3((unsigned)runs.size()), dim3(1024), 0, h->stream, (const CtRun *)(dm + o_runs), (const int *)(dm + o_r), (const size_t *)(dm + o_moff),
+                           (const double *)h->ct[ttx_engine::CT_M].p, (double *)h->ct[ttx_engine::CT_P].p, (double *)h->ct[ttx_engine::CT_SCR].p);
+    hipLaunchKernelGGL(k_ct_absorb, dim3((unsigned)items), dim3(64), 0, h->stream, (const CtKeep *)(dm + o_keeps), m, h->RM, h->P.SS, e->RM, e->P.SS);
+    return ct_finish(h, !pl.tiles.empty());
+}
+extern "C" int ttx_contract(ttx_engine *h, const int32_t *keep, const double *w, ttx_engine **out)
+{
+    if (out) *out = nullptr;
+    if (!keep || !out) return fail(TTX_EINVAL, "ttx_contract: null argument");
+    int rc = ct_check(h, "ttx_contract");
+    if (rc) return rc;
+    const int d = h->d;
+    std::vector<int> kept;
+    for (int k = 0; k < d; k++) {
+        if (keep[k] != 0 && keep[k] != 1) return fail(TTX_EINVAL, "ttx_contract: keep(%d) = %d (0 or 1 expected)", k + 1, keep[k]);
+        if (keep[k]) kept.push_back(k);
+    }
+    const int m = (int)kept.size();
+    if (m < 2) return fail(TTX_EINVAL, "ttx_contract: %d kept mode%s, but the engine holds trains of at least two cores: ttx_marginals gives the one-mode marginals, ttx_quad the full sum", m, m == 1 ? "" : "s");
+    // new ranks: r'(0) = 1, r'(j) = r(k_j) for j < m, r'(m) = 1
+    std::vector<int32_t> nn(m), rr(m + 1, 1);
+    for (int j = 0; j < m; j++) { nn[j] = h->n1[kept[j] + 1]; if (j < m - 1) rr[j + 1] = h->rfinal[kept[j] + 1]; }
+    rr[0] = kept[0] == 0 ? h->rfinal[0] : 1; rr[m] = kept[m - 1] == d - 1 ? h->rfinal[d] : 1;
+    ttx_engine *e = nullptr;
+    if ((rc = train_shell(&e, "ttx_contract", m, nn.data(), rr.data(), h->cfg.device))) return rc;
+    if ((rc = ct_fill(h, e, kept, w))) { const std::string msg = g_err; ttx_destroy(e); g_err = msg; return rc; }
+    *out = e;
+    return TTX_OK;
+}
+extern "C" int ttx_marginals(ttx_engine *h, const double *w, double *out)
+{
+    if (!out) return fail(TTX_EINVAL, "ttx_marginals: null argument");
+    int rc = ct_check(h, "ttx_marginals");
+    if (rc) return rc;
+    const int d = h->d;
+    CtPlan pl;
+    ct_plan(h, std::vector<char>(d, 1), pl);
+    const int ldv = h->RM;
+    CtMeta meta(h->ct_meta_host);
+    const size_t o_cores = meta.put(pl.cores), o_tiles = meta.put(pl.tiles), o_r = meta.put(pl.r), o_moff = meta.put(pl.moff);
+    if ((rc = buf_reserve(h, h->ct[ttx_engine::CT_META], h->ct_meta_host.size())) || (rc = buf_reserve(h, h->ct[ttx_engine::CT_VEC], sizeof(double) * (2 * (size_t)d + 4) * ldv)) ||
+        (rc = buf_reserve(h, h->ct[ttx_engine::CT_OUT], sizeof(double) * pl.wsize))) return rc;
+    char *dm = (char *)h->ct[ttx_engine::CT_META].p;
+    HIPCHECK(hipMemcpyAsync(dm, h->ct_meta_host.data(), h->ct_meta_host.size(), hipMemcpyHostToDevice, h->stream));
+    if ((rc = ct_modesum(h, pl, w, (const CtCore *)(dm + o_cores), (const CtTile *)(dm + o_tiles)))) return rc;
+    double *L = (double *)h->ct[ttx_engine::CT_VEC].p, *S = L + (size_t)d * ldv, *dout = (double *)h->ct[ttx_engine::CT_OUT].p;   // L: vectors 0 .. d-1, S: 2 .. d+1 at S + k ldv
+    hipLaunchKernelGGL(k_ct_chains, dim3(2), dim3(1024), 0, h->stream, d, (const int *)(dm + o_r), (const size_t *)(dm + o_moff), (const double *)h->ct[ttx_engine::CT_M].p, L, S, ldv);
+    hipLaunchKernelGGL(k_ct_marg, dim3((unsigned)((pl.wsize + 3) / 4)), dim3(256), 0, h->stream, d, (const CtCore *)(dm + o_cores), (long long)pl.wsize, h->RM, h->P.SS,
+                       (const double *)L, (const double *)S, ldv, dout);
+    HIPCHECK(hipMemcpyAsync(out, dout, sizeof(double) * pl.wsize, hipMemcpyDeviceToHost, h->stream));
+    return ct_finish(h, true);
+}
+extern "C" int ttx_contract_modesum(const ttx_engine *h, double *ms, double *bytes)
+{
+    if (!h || !ms || !bytes) return fail(TTX_EINVAL, "ttx_contract_modesum: null argument");
+    *ms = h->ct_ms; *bytes = h->ct_bytes;
+    return TTX_OK;
+}
+
 extern "C" int ttx_kernel_stats(const ttx_engine *h, int64_t launches[TTX_K_NKINDS], double ms[TTX_K_NKINDS], double bytes[TTX_K_NKINDS])
 {
     if (!h) return fail(TTX_EINVAL, "null");

@@ -316,9 +316,80 @@ def run_tijk(argv, device=0, repeats=5, tt=None):
     return tt, ind, out, res
 
 
+def keep_flags(spec, d):
+    """KEEPSPEC of the contract sub-command: 'ends' (first and last mode), 'mid' (the two middle modes), 'everyN' (modes N, 2N,
+    ...), or 1-based mode numbers separated by commas"""
+    if spec == "ends":
+        kept = {1, d}
+    elif spec == "mid":
+        kept = {d // 2, d // 2 + 1}
+    elif spec.startswith("every"):
+        kept = set(range(int(spec[5:]), d + 1, int(spec[5:])))
+    else:
+        kept = {int(x) for x in spec.split(",")}
+    return [int(k + 1 in kept) for k in range(d)]
+
+
+def contract_host(tt, keep, w):
+    """what a user does without ttx_contract: every core to the host, the contraction in numpy, the result back to the device"""
+    cores = [tt.core(k) for k in range(1, tt.d + 1)]
+    out, p = [], None
+    for c, kp, q in zip(cores, keep, w):
+        if kp:
+            out.append(c if p is None else np.einsum("ab,bjc->ajc", p, c))
+            p = None
+        else:
+            m = np.einsum("ajb,j->ab", c, q)
+            p = m if p is None else p @ m
+    if p is not None:
+        out[-1] = np.einsum("ajb,bc->ajc", out[-1], p)
+    return TTCross.from_cores(out, device=tt.device)
+
+
+def run_contract(argv, device=0, tt=None):
+    """contract WORKLOAD KEEPSPEC [REPS]: the trains of the tijk sub-command; contract(keep) and marginals() with plain-sum
+    weights of 1 / n, one warm-up and the median of REPS (default 10) calls each; per call the milliseconds, and the
+    milliseconds and bytes / s of the mode-sum kernel (8 sum r0 n r1 over the contracted cores); then the host route once.
+    Prints one JSON line."""
+    import json
+    import time
+    workload, spec = argv[0], argv[1]
+    reps = int(argv[2]) if len(argv) > 2 else 10
+    tt = tt or tijk_train(workload, device=device)
+    keep = keep_flags(spec, tt.d)
+    w = [np.full(int(nk), 1.0 / int(nk)) for nk in tt._n]
+
+    def timed(fn):
+        fn()
+        ms, ks = [], []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()                                   # synchronises before it returns
+            ms.append((time.perf_counter() - t0) * 1e3)
+            ks.append(tt.contract_modesum())
+        kms = float(np.median([k[0] for k in ks]))
+        return dict(ms=float(np.median(ms)), ms_min=float(min(ms)), modesum_ms=kms, modesum_bytes=ks[0][1],
+                    modesum_bytes_per_s=ks[0][1] / (kms * 1e-3) if kms > 0 else None)
+
+    res = dict(workload=workload, keep=spec, kept=int(sum(keep)), d=tt.d, max_rank=int(tt.ranks().max()), reps=reps)
+    res["contract"] = timed(lambda: tt.contract(keep, w).close())
+    res["marginals"] = timed(lambda: tt.marginals(w))
+    t0 = time.perf_counter()
+    ref = contract_host(tt, keep, w)
+    res["host_route_ms"] = (time.perf_counter() - t0) * 1e3
+    ct = tt.contract(keep, w)
+    wk = [q for q, kp in zip(w, keep) if kp]
+    res["quad"] = dict(source=tt.quad(w), contracted=ct.quad(wk), host_route=ref.quad(wk))
+    res["ranks"] = ct.ranks().tolist()
+    print(json.dumps(res))
+    return res
+
+
 if __name__ == "__main__":
     if sys.argv[1] == "tijk":
         run_tijk(sys.argv[2:])
+    elif sys.argv[1] == "contract":
+        run_contract(sys.argv[2:])
     elif sys.argv[1] == "chf":
         run_chf(sys.argv[2:])
     elif sys.argv[1] == "pdf":

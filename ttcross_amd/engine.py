@@ -99,6 +99,9 @@ def load_library():
     L.ttx_ijk_batch_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_int32]
     L.ttx_value_batch.argtypes = [c_void_p, c_int64, c_int32, POINTER(c_double), POINTER(c_double), c_int32]
     L.ttx_eval_last_mode.argtypes = [c_void_p]
+    L.ttx_contract.argtypes = [c_void_p, POINTER(c_int32), POINTER(c_double), POINTER(c_void_p)]
+    L.ttx_marginals.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double)]
+    L.ttx_contract_modesum.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double)]
     L.ttx_zquad.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
     L.ttx_accchk.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
     L.ttx_from_tt.argtypes = [POINTER(c_void_p), c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), c_int32]
@@ -515,15 +518,46 @@ class TTCross:
         _check(L.ttx_get_core(self._h, k, _dp(buf)))
         return buf.reshape((r[k - 1], self._n[k - 1], r[k]), order="F")
 
+    def _weights(self, w, who):
+        """per-mode weight vectors as the concatenated block the C entry points take (on trust, as the reference takes its rank-1 train)"""
+        if w is None:
+            return None
+        if len(w) != self.d or any(np.size(q) != int(nk) for q, nk in zip(w, self._n)):
+            raise ValueError(f"{who}: {self.d} weight vectors of lengths {list(map(int, self._n))} expected")
+        return np.ascontiguousarray(np.concatenate([np.asarray(q, dtype=np.float64).ravel() for q in w]))
+
     def quad(self, w=None):
         """dtt_quad(arg, quad) (lib/dmrgg.f90:1261); w = list of per-mode weight vectors or None."""
         v = c_double()
-        if w is not None:     # the C entry point takes the concatenated vectors on trust (as the reference takes its rank-1 train)
-            if len(w) != self.d or any(np.size(q) != int(nk) for q, nk in zip(w, self._n)):
-                raise ValueError(f"quad: {self.d} weight vectors of lengths {list(map(int, self._n))} expected")
-        wa = None if w is None else np.ascontiguousarray(np.concatenate([np.asarray(q, dtype=np.float64).ravel() for q in w]))
+        wa = self._weights(w, "quad")
         _check(load_library().ttx_quad(self._h, _dp(wa), ctypes.byref(v)))
         return v.value
+
+    def contract(self, keep, w=None):
+        """The train with the modes where keep is 0 / False summed against their weights (include/ttx.h: ttx_contract), as a new
+        engine on the same device; keep: d booleans or 0 / 1, at least two kept; w as for quad (the vectors of kept modes are
+        ignored), None = plain sums.  A slice is a contraction with a unit vector.  No core crosses the host link."""
+        k = np.asarray(keep)
+        if k.ndim != 1 or k.size != self.d:
+            raise ValueError(f"contract: {self.d} keep flags expected")
+        k = np.ascontiguousarray(k.astype(np.int32))
+        wa = self._weights(w, "contract")
+        h = c_void_p()
+        _check(load_library().ttx_contract(self._h, _ip(k), _dp(wa), ctypes.byref(h)))
+        return TTCross._adopt(h, self.device)
+
+    def marginals(self, w=None):
+        """All d one-mode marginals (include/ttx.h: ttx_marginals): a list of d arrays, entry k of length n(k) = the train summed
+        over every other mode against its weights (w as for quad, None = plain sums)."""
+        out = np.zeros(int(self._n.sum()))
+        _check(load_library().ttx_marginals(self._h, _dp(self._weights(w, "marginals")), _dp(out)))
+        return [a.copy() for a in np.split(out, np.cumsum(self._n)[:-1])]
+
+    def contract_modesum(self):
+        """(milliseconds, bytes) of the mode-sum kernel of the last contract / marginals (include/ttx.h: ttx_contract_modesum)"""
+        ms, by = c_double(), c_double()
+        _check(load_library().ttx_contract_modesum(self._h, ctypes.byref(ms), ctypes.byref(by)))
+        return ms.value, by.value
 
     # ---- tt_lib utilities on the resident TT (lib/tt.f90: ort, svd, norm, dot_product, tijk) --------------
     def ort(self):

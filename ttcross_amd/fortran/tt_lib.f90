@@ -64,6 +64,9 @@ module tt_lib
  interface norm;        module procedure dtt_norm; end interface
  interface dot_product; module procedure dtt_dot;  end interface
  interface tijk;        module procedure dtt_ijk,dtt_ijk_many;  end interface
+ ! partial contraction on the device (not in the reference): contract(arg,keep,res,w), marginals(arg,marg,w)
+ interface contract;    module procedure dtt_contract;  end interface
+ interface marginals;   module procedure dtt_marginals; end interface
 contains
  subroutine ztt_alloc(arg)
   type(ztt),intent(inout) :: arg
@@ -263,6 +266,63 @@ contains
   if(temp)call ttx_destroy(h)
   deallocate(ix)
  end function
+ subroutine dtt_weights(arg,w,ww)
+  ! the rank-1 train w (as the quad argument of dtt_quad) as d blocks of n(k) weights
+  type(dtt),intent(in) :: arg,w
+  real(c_double),allocatable,intent(out) :: ww(:)
+  integer :: k,off
+  allocate(ww(sum(arg%n(1:arg%m)))); off=0
+  do k=1,arg%m; ww(off+1:off+arg%n(k))=w%u(k)%p(1,1:arg%n(k),1); off=off+arg%n(k); end do
+ end subroutine
+ subroutine dtt_contract(arg,keep,res,w)
+  ! res = arg with every mode k where keep(k) = 0 summed against the weights w%u(k)%p(1,:,1) (w absent: plain sums); at least two
+  ! modes are kept.  One call on the device (ttx_contract); a host train is staged for the call like for norm / dot_product.
+  ! res holds the new train on the device and, pulled, in res%u.
+  use ttx_c
+  type(dtt),intent(in) :: arg
+  integer,intent(in) :: keep(:)
+  type(dtt),intent(inout) :: res
+  type(dtt),intent(in),optional :: w
+  integer(c_int32_t) :: kp(tt_size)
+  real(c_double),allocatable,target :: ww(:)
+  type(c_ptr) :: h,hn,wp
+  logical :: temp
+  integer :: k
+  call dtt_dealloc(res)
+  kp(1:arg%m)=keep(1:arg%m)
+  wp=c_null_ptr
+  if(present(w))then; call dtt_weights(arg,w,ww); wp=c_loc(ww); endif
+  call dtt_stage(arg,h,temp,'dtt_contract')
+  hn=c_null_ptr
+  call ttx_check(ttx_contract(h,kp,wp,hn),'dtt_contract')
+  if(temp)call ttx_destroy(h)
+  res%l=1; res%m=0
+  do k=1,arg%m
+   if(keep(k).ne.0)then; res%m=res%m+1; res%n(res%m)=arg%n(k); endif
+  end do
+  res%ttx=hn; call dtt_pull(res)
+ end subroutine
+ subroutine dtt_marginals(arg,marg,w)
+  ! marg(i,k), i = 1..n(k): arg summed over every mode but k against the weights (w absent: plain sums); marg has at least
+  ! maxval(n) rows and m columns, entries beyond n(k) are set to zero.  One call on the device (ttx_marginals).
+  use ttx_c
+  type(dtt),intent(in) :: arg
+  double precision,intent(out) :: marg(:,:)
+  type(dtt),intent(in),optional :: w
+  real(c_double),allocatable,target :: ww(:)
+  real(c_double),allocatable :: o(:)
+  type(c_ptr) :: h,wp
+  logical :: temp
+  integer :: k,off
+  wp=c_null_ptr
+  if(present(w))then; call dtt_weights(arg,w,ww); wp=c_loc(ww); endif
+  allocate(o(sum(arg%n(1:arg%m))))
+  call dtt_stage(arg,h,temp,'dtt_marginals')
+  call ttx_check(ttx_marginals(h,wp,o),'dtt_marginals')
+  if(temp)call ttx_destroy(h)
+  marg=0.d0; off=0
+  do k=1,arg%m; marg(1:arg%n(k),k)=o(off+1:off+arg%n(k)); off=off+arg%n(k); end do
+ end subroutine
  double precision function dtt_ijk(arg,ind) result(a)
   ! lib/tt.f90:630-652: one element; a resident train is asked on the device, a host train is contracted here
   use ttx_c

@@ -120,6 +120,13 @@ module ttx_c
    import; type(c_ptr),value :: h; integer(c_int64_t),value :: npts; integer(c_int32_t),value :: dd,mode
    real(c_double),intent(in) :: x(*); real(c_double),intent(out) :: out(*); integer(c_int) :: rc
   end function
+  ! chosen modes of the train contracted with rank-1 weights (include/ttx.h); w: d blocks of n(k) weights or c_null_ptr (ones)
+  function ttx_contract(h,keep,w,out) bind(C,name='ttx_contract') result(rc)
+   import; type(c_ptr),value :: h,w; integer(c_int32_t),intent(in) :: keep(*); type(c_ptr) :: out; integer(c_int) :: rc
+  end function
+  function ttx_marginals(h,w,out) bind(C,name='ttx_marginals') result(rc)
+   import; type(c_ptr),value :: h,w; real(c_double),intent(out) :: out(*); integer(c_int) :: rc
+  end function
   function ttx_accchk(h,nlot,einf,efro,ainf,afro,pivot) bind(C,name='ttx_accchk') result(rc)
    import; type(c_ptr),value :: h; integer(c_int32_t),value :: nlot; real(c_double),intent(out) :: einf,efro,ainf,afro
    integer(c_int32_t),intent(out) :: pivot(*); integer(c_int) :: rc
