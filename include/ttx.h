@@ -84,8 +84,9 @@ typedef struct ttx_sweep_rec {
 } ttx_sweep_rec;
 
 const char *ttx_last_error(void);
-int ttx_version(void);   /* 2: loadable device integrands; 3: ttx_ijk_batch, ttx_ijk_batch_dev, ttx_value_batch (ttx_contract and
-                          * ttx_marginals came later without a new number: look the symbols up) */
+int ttx_version(void);   /* 2: loadable device integrands; 3: ttx_ijk_batch, ttx_ijk_batch_dev, ttx_value_batch (ttx_contract,
+                          * ttx_marginals, ttx_lincomb, ttx_hadamard and ttx_algebra_last came later without a new number:
+                          * look the symbols up) */
 
 /* allocate device state for one dtt_dmrgg problem (replaces the implicit set-up of lib/dmrgg.f90:58-148) */
 int ttx_create(ttx_engine **out, const ttx_config *cfg);
@@ -242,6 +243,33 @@ int ttx_marginals(ttx_engine *h, const double *w, double *out);
 /* the mode-sum kernel of the last ttx_contract / ttx_marginals on this engine: its milliseconds (HIP events) and the bytes of the
  * cores it summed, 8 sum r(k-1) n(k) r(k) over the contracted modes (0 ms when nothing was contracted) */
 int ttx_contract_modesum(const ttx_engine *h, double *ms, double *bytes);
+
+/* Sums and elementwise products of resident trains, assembled on the device (ttcross_amd/csrc/ttx_algebra.h).  Every element of a
+ * new core is a copy, a zero or ONE rounded product, so the results are predictable bit for bit.
+ * ttx_lincomb : sum_t coef[t] x[t] for m >= 1 trains with equal d and mode sizes: dtt_plus_dtt for m terms composed with dtt_mul_dt
+ *               (lib/tt.f90:928-946, 989-998).  Ranks r'(0) = r'(d) = 1, r'(k) = sum_t r_t(k) on interior bonds.  Core 1 is the
+ *               terms' first cores side by side, each multiplied by its coef[t] (the only multiply, as the dscal of dtt_mul_dt);
+ *               interior cores are block diagonal in term order with explicit 0.0 off the blocks; core d is the terms' last cores
+ *               stacked.  The same engine may appear several times (x + x, x - x).  Coefficients are not inspected: 0, NaN and Inf
+ *               act as the multiply makes them act.  m = 1 is a scaled deep copy.
+ * ttx_hadamard: z(i) = x(i) y(i).  Ranks r'(k) = r_x(k) r_y(k); 0-based, core k is
+ *               Z[ib rx0 + ia, j, kb rx1 + ka] = X[ia, j, ka] Y[ib, j, kb] -- the x index runs fastest on both bonds, one multiply
+ *               per element.  x and y may be the same engine.
+ * *out is a new single-process engine without integrand (as ttx_contract's), owned by the caller; the operands and their work
+ * space are not modified.  Every new rank must be <= 128, the engine's cap: a larger sum or product is TTX_EINVAL with the bond
+ * and the value in the message.  The cap is NOT lifted and nothing is rounded on the fly: round the operands (ttx_svd) first,
+ * or the result afterwards.  A tile count above 2^31 - 1 is TTX_EINVAL.
+ * Everything is enqueued on x[0]'s stream (x's for ttx_hadamard) and the call synchronises before it returns; the OTHER operands
+ * must be idle -- under the rule of one host thread per engine, no call on them may be in flight in another thread.
+ * TTX_EINVAL: null pointers, m < 1, unequal d or mode sizes, engines on different devices (all pointer and count checks come
+ * before any device call); TTX_ESTATE: an engine without a train; a multi-process engine is refused as by ttx_ijk (a replica,
+ * ttx_replicate, is accepted).  After a refusal *out is NULL and nothing stays allocated.
+ * ttx_algebra_last, called with x[0] (x for ttx_hadamard): the assembly kernel of the last ttx_lincomb / ttx_hadamard on that
+ * engine -- its milliseconds (HIP events), 8 x the source core elements it read, 8 x sum r'(k-1) n(k) r'(k) it wrote.
+ * Added without a new ttx_version: look the symbols up. */
+int ttx_lincomb(int32_t m, const double *coef /* [m] */, ttx_engine *const *x /* [m] */, ttx_engine **out);
+int ttx_hadamard(ttx_engine *x, ttx_engine *y, ttx_engine **out);
+int ttx_algebra_last(const ttx_engine *h, double *ms, double *bytes_read, double *bytes_written);
 
 /* The finalised train of a MULTI-PROCESS job gathered onto EVERY process as a new single-process engine (same integrand, ranks,
  * RNG position; *out is owned by the caller: ttx_destroy).  Collective over the job's transport (each process contributes the

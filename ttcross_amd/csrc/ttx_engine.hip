@@ -49,6 +49,7 @@ static cluster_kernel_t cluster_kernel(int var)
 #include "ttx_coscoeff.h"
 #include "ttx_eval.h"
 #include "ttx_contract.h"
+#include "ttx_algebra.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const char *fmt, ...)
@@ -199,6 +200,10 @@ struct ttx_engine {
     std::vector<char> ct_meta_host;
     hipEvent_t ct_ev[2] = {nullptr, nullptr};   // around the mode-sum kernel of the last call (ttx_contract_modesum_ms)
     double ct_ms = 0.0, ct_bytes = 0.0;
+    // sums and elementwise products of trains (ttx_algebra.h): the block table and the figures of the last call with this engine first
+    EvBuf alg_meta;
+    hipEvent_t alg_ev[2] = {nullptr, nullptr};
+    double alg_ms = 0.0, alg_rd = 0.0, alg_wr = 0.0;
 };
 
 // ---- worker threads for the host integrand (the reference evaluates `fun` inside !$OMP PARALLEL DO regions,
@@ -836,6 +841,8 @@ extern "C" void ttx_destroy(ttx_engine *h)
     for (auto &b : h->ev) if (b.p) (void)hipFree(b.p);
     for (auto &b : h->ct) if (b.p) (void)hipFree(b.p);
     for (auto &e : h->ct_ev) if (e) (void)hipEventDestroy(e);
+    if (h->alg_meta.p) (void)hipFree(h->alg_meta.p);
+    for (auto &e : h->alg_ev) if (e) (void)hipEventDestroy(e);
     if (h->h_sum_base) (void)hipHostFree(h->h_sum_base);
     if (h->h_val) (void)hipHostFree(h->h_val);
     if (h->h_svd) (void)hipHostFree(h->h_svd);
@@ -3321,6 +3328,161 @@ extern "C" int ttx_contract_modesum(const ttx_engine *h, double *ms, double *byt
 {
     if (!h || !ms || !bytes) return fail(TTX_EINVAL, "ttx_contract_modesum: null argument");
     *ms = h->ct_ms; *bytes = h->ct_bytes;
+    return TTX_OK;
+}
+
+// ---- sums and elementwise products of resident trains (ttx_algebra.h) -----------------------------------------------------------
+static bool alg_even16(const void *p, int RM, size_t SS) { return ((uintptr_t)p & 15) == 0 && RM % 2 == 0 && SS % 2 == 0; }
+static int alg_ta(int rows, int vec)
+{
+    const int need = vec ? (rows + 1) / 2 : rows;
+    int ta = 1;
+    while (ta < 64 && ta < need) ta <<= 1;
+    return ta;
+}
+// what both operations ask of their operands, before any device call: every engine holds a train (one that spreads it over
+// processes gets ttx_ijk's answer), same modes, same device, boundary ranks 1
+static int alg_check(const char *who, int m, ttx_engine *const *x)
+{
+    for (int t = 0; t < m; t++) if (!x[t]) return fail(TTX_EINVAL, "%s: null engine (operand %d)", who, t + 1);
+    for (int t = 0; t < m; t++) {
+        if (!x[t]->ran) return fail(TTX_ESTATE, "%s: no tensor train in operand %d (run dtt_dmrgg first)", who, t + 1);
+        if (x[t]->W > 1) return tt_prepare(x[t], who);
+    }
+    const ttx_engine *h = x[0];
+    for (int t = 0; t < m; t++) {
+        if (x[t]->d != h->d) return fail(TTX_EINVAL, "%s: dimensions not match (operand %d has %d modes, operand 1 %d)", who, t + 1, x[t]->d, h->d);
+        for (int k = 1; k <= h->d; k++) if (x[t]->n1[k] != h->n1[k]) return fail(TTX_EINVAL, "%s: sizes not match (mode %d: operand %d has %d, operand 1 %d)", who, k, t + 1, x[t]->n1[k], h->n1[k]);
+        if (x[t]->cfg.device != h->cfg.device) return fail(TTX_EINVAL, "%s: all tensor trains must live on the same GPU", who);
+        if (x[t]->rfinal[0] != 1 || x[t]->rfinal[h->d] != 1) return fail(TTX_EINVAL, "%s: boundary ranks of operand %d are not 1", who, t + 1);
+    }
+    return TTX_OK;
+}
+// the block table to the device, the one launch between the engine's two events, the wait
+static int alg_launch(ttx_engine *h, ttx_engine *e, const std::vector<AlgBlk> &blks, long long tiles, bool hadamard, double rd, double wr)
+{
+    int rc;
+    if ((rc = buf_reserve(h, h->alg_meta, sizeof(AlgBlk) * blks.size()))) return rc;
+    HIPCHECK(hipMemcpyAsync(h->alg_meta.p, blks.data(), sizeof(AlgBlk) * blks.size(), hipMemcpyHostToDevice, h->stream));
+    for (auto &ev : h->alg_ev) if (!ev) HIPCHECK(hipEventCreate(&ev));
+    h->alg_ms = 0.0; h->alg_rd = rd; h->alg_wr = wr;
+    HIPCHECK(hipEventRecord(h->alg_ev[0], h->stream));
+    if (hadamard) hipLaunchKernelGGL(k_alg_hadamard, dim3((unsigned)tiles), dim3(256), 0, h->stream, (const AlgBlk *)h->alg_meta.p, (int)blks.size(), e->RM, e->P.SS);
+    else hipLaunchKernelGGL(k_alg_lincomb, dim3((unsigned)tiles), dim3(256), 0, h->stream, (const AlgBlk *)h->alg_meta.p, (int)blks.size(), e->RM, e->P.SS);
+    HIPCHECK(hipEventRecord(h->alg_ev[1], h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipGetLastError());
+    float ms = 0.f;
+    HIPCHECK(hipEventElapsedTime(&ms, h->alg_ev[0], h->alg_ev[1]));
+    h->alg_ms = ms;
+    return TTX_OK;
+}
+static int alg_lincomb_fill(int m, const double *coef, ttx_engine *const *x, ttx_engine *e)
+{
+    ttx_engine *h = x[0];
+    const int d = h->d;
+    std::vector<AlgBlk> blks;
+    blks.reserve((size_t)d * m);
+    long long tiles = 0;
+    double rd = 0.0, wr = 0.0;
+    for (int k = 0; k < d; k++) {
+        const int n = h->n1[k + 1], R0 = e->rfinal[k];
+        wr += 8.0 * R0 * n * e->rfinal[k + 1];
+        int ro = 0, co = 0;
+        for (int t = 0; t < m; t++) {
+            AlgBlk B{};
+            B.x = core_dev(x[t], k + 1); B.xRM = x[t]->RM; B.xSS = x[t]->P.SS;
+            B.dst = core_dev(e, k + 1) + e->P.SS * (size_t)co;
+            B.coef = coef[t]; B.scale = k == 0; B.fill = k < d - 1;
+            B.R0 = R0; B.ro = ro; B.r0 = x[t]->rfinal[k]; B.n = n; B.r1 = x[t]->rfinal[k + 1];
+            B.vec = alg_even16(B.x, B.xRM, B.xSS) && alg_even16(B.dst, e->RM, e->P.SS) && ro % 2 == 0;
+            B.ta = alg_ta(B.fill ? R0 : B.r0, B.vec);
+            B.first = tiles;
+            const long long per = (long long)(256 / B.ta) * TTX_ALG_U;
+            tiles += ((long long)n * B.r1 + per - 1) / per;
+            rd += 8.0 * B.r0 * n * B.r1;
+            blks.push_back(B);
+            if (k > 0) ro += B.r0;
+            if (k < d - 1) co += B.r1;
+        }
+    }
+    if (tiles > 0x7fffffffll) return fail(TTX_EINVAL, "ttx_lincomb: too many tiles (%lld)", tiles);
+    return alg_launch(h, e, blks, tiles, false, rd, wr);
+}
+extern "C" int ttx_lincomb(int32_t m, const double *coef, ttx_engine *const *x, ttx_engine **out)
+{
+    if (out) *out = nullptr;
+    if (!coef || !x || !out) return fail(TTX_EINVAL, "ttx_lincomb: null argument");
+    if (m < 1) return fail(TTX_EINVAL, "ttx_lincomb: %d terms (at least one expected)", m);
+    int rc = alg_check("ttx_lincomb", m, x);
+    if (rc) return rc;
+    ttx_engine *h = x[0];
+    const int d = h->d;
+    std::vector<int32_t> nn(h->n1.begin() + 1, h->n1.begin() + 1 + d), rr(d + 1, 1);
+    for (int k = 1; k < d; k++) {
+        long long s = 0;
+        for (int t = 0; t < m; t++) s += x[t]->rfinal[k];
+        if (s > 128) return fail(TTX_EINVAL, "ttx_lincomb: the ranks at bond %d add up to %lld, the engine holds ranks up to 128 (round the terms first: ttx_svd)", k, s);
+        rr[k] = (int32_t)s;
+    }
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    ttx_engine *e = nullptr;
+    if ((rc = train_shell(&e, "ttx_lincomb", d, nn.data(), rr.data(), h->cfg.device))) return rc;
+    if ((rc = alg_lincomb_fill(m, coef, x, e))) { const std::string msg = g_err; ttx_destroy(e); g_err = msg; return rc; }
+    *out = e;
+    return TTX_OK;
+}
+static int alg_hadamard_fill(ttx_engine *x, ttx_engine *y, ttx_engine *e)
+{
+    const int d = x->d;
+    std::vector<AlgBlk> blks(d);
+    long long tiles = 0;
+    double rd = 0.0, wr = 0.0;
+    for (int k = 0; k < d; k++) {
+        AlgBlk &B = blks[k];
+        B = AlgBlk{};
+        B.x = core_dev(x, k + 1); B.xRM = x->RM; B.xSS = x->P.SS;
+        B.y = core_dev(y, k + 1); B.yRM = y->RM; B.ySS = y->P.SS;
+        B.dst = core_dev(e, k + 1);
+        B.n = x->n1[k + 1]; B.r0 = x->rfinal[k]; B.r1 = x->rfinal[k + 1]; B.ry0 = y->rfinal[k]; B.ry1 = y->rfinal[k + 1];
+        B.R0 = B.r0 * B.ry0;
+        B.vec = B.r0 % 2 == 0 && alg_even16(B.x, B.xRM, B.xSS) && alg_even16(B.dst, e->RM, e->P.SS);
+        B.ta = alg_ta(B.R0, B.vec);
+        B.ntk = (B.r1 + TTX_ALG_KC - 1) / TTX_ALG_KC;
+        B.first = tiles;
+        const long long cpw = 256 / B.ta;
+        tiles += (((long long)B.n * B.ry1 + cpw - 1) / cpw) * B.ntk;
+        rd += 8.0 * B.n * ((double)B.r0 * B.r1 + (double)B.ry0 * B.ry1);
+        wr += 8.0 * B.R0 * B.n * ((double)B.r1 * B.ry1);
+    }
+    if (tiles > 0x7fffffffll) return fail(TTX_EINVAL, "ttx_hadamard: too many tiles (%lld)", tiles);
+    return alg_launch(x, e, blks, tiles, true, rd, wr);
+}
+extern "C" int ttx_hadamard(ttx_engine *x, ttx_engine *y, ttx_engine **out)
+{
+    if (out) *out = nullptr;
+    if (!x || !y || !out) return fail(TTX_EINVAL, "ttx_hadamard: null argument");
+    ttx_engine *const xy[2] = {x, y};
+    int rc = alg_check("ttx_hadamard", 2, xy);
+    if (rc) return rc;
+    const int d = x->d;
+    std::vector<int32_t> nn(x->n1.begin() + 1, x->n1.begin() + 1 + d), rr(d + 1, 1);
+    for (int k = 1; k < d; k++) {
+        const int p = x->rfinal[k] * y->rfinal[k];
+        if (p > 128) return fail(TTX_EINVAL, "ttx_hadamard: the ranks at bond %d multiply to %d (%d x %d), the engine holds ranks up to 128 (round the factors first: ttx_svd)", k, p, x->rfinal[k], y->rfinal[k]);
+        rr[k] = p;
+    }
+    HIPCHECK(hipSetDevice(x->cfg.device));
+    ttx_engine *e = nullptr;
+    if ((rc = train_shell(&e, "ttx_hadamard", d, nn.data(), rr.data(), x->cfg.device))) return rc;
+    if ((rc = alg_hadamard_fill(x, y, e))) { const std::string msg = g_err; ttx_destroy(e); g_err = msg; return rc; }
+    *out = e;
+    return TTX_OK;
+}
+extern "C" int ttx_algebra_last(const ttx_engine *h, double *ms, double *bytes_read, double *bytes_written)
+{
+    if (!h || !ms || !bytes_read || !bytes_written) return fail(TTX_EINVAL, "ttx_algebra_last: null argument");
+    *ms = h->alg_ms; *bytes_read = h->alg_rd; *bytes_written = h->alg_wr;
     return TTX_OK;
 }
 

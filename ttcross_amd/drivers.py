@@ -8,6 +8,7 @@ runs on the GPU through ttcross_amd.engine.  Usage:
     python -m ttcross_amd.drivers coscoeff D N RANK PIV [NGROUPS]
     python -m ttcross_amd.drivers devfun D N RANK PIV [NGROUPS] [device|host|wave] [SOURCE.hip NAME]
     python -m ttcross_amd.drivers tijk WORKLOAD NPTS MODE      (batched element evaluation: c64 | d64 | rand256 | a file of dtt_write)
+    python -m ttcross_amd.drivers algebra WORKLOAD [REPS]      (x + x, x - x, x o w, x o x, dist on the device and by the host route)
 
 devfun: the rational example integrand (examples/devfun/rational.hip) as a LOADED device integrand (TTX_FUN_DEVICE), in its
 wave form, or -- host -- its C twin through the host callback (TTX_FUN_HOST; needs gcc); SOURCE.hip NAME loads another
@@ -21,7 +22,7 @@ import numpy as np
 import os
 
 from .engine import (DEVFUN_DIR, TTX_FUN_COSCOEFF, TTX_FUN_DEVICE, TTX_FUN_HOST, TTX_FUN_ISING, TTX_FUN_MVN, TTX_FUN_STDNORM, TTCross,
-                     compile_device_fun)
+                     TTXError, compile_device_fun)
 
 EPS = 2.220446049250313e-16
 TPI = 6.283185307179586476925286766559
@@ -385,11 +386,106 @@ def run_contract(argv, device=0, tt=None):
     return res
 
 
+def algebra_host(coefs, trains):
+    """what a user does without ttx_lincomb: every core to the host, the block cores in numpy, the result back to the device"""
+    src = [[t.core(k) for k in range(1, t.d + 1)] for t in trains]
+    d, out = trains[0].d, []
+    for k in range(d):
+        r0 = 1 if k == 0 else sum(x[k].shape[0] for x in src)
+        r1 = 1 if k == d - 1 else sum(x[k].shape[2] for x in src)
+        z = np.zeros((r0, src[0][k].shape[1], r1))
+        ro = co = 0
+        for c, x in zip(coefs, src):
+            g = x[k]
+            z[ro:ro + g.shape[0], :, co:co + g.shape[2]] = c * g if k == 0 else g
+            ro += g.shape[0] if k > 0 else 0
+            co += g.shape[2] if k < d - 1 else 0
+        out.append(z)
+    return TTCross.from_cores(out, device=trains[0].device)
+
+
+def hadamard_host(x, y):
+    """the host route of x.hadamard(y)"""
+    out = []
+    for k in range(1, x.d + 1):
+        a, b = x.core(k), y.core(k)
+        z = b[:, None, :, :, None] * a[None, :, :, None, :]             # plain products: a sum-of-products routine would turn -0.0 into +0.0
+        out.append(z.reshape(b.shape[0] * a.shape[0], a.shape[1], b.shape[2] * a.shape[2]))
+    return TTCross.from_cores(out, device=x.device)
+
+
+def run_algebra(argv, device=0, tt=None):
+    """algebra WORKLOAD [REPS]: the trains of the tijk sub-command; x + x, x - x, x o w with a rank-1 weight train w (1 / n), x o x
+    where the squared ranks fit, and dist of the exact against the fast-arithmetic train where the workload is an Ising sweep.
+    Per case: one warm-up and the median of REPS (default 10) calls, the assembly kernel's milliseconds and bytes through
+    ttx_algebra_last, its rate as a fraction of the bandwidth probe (ttx_k_residual_bench on rows x 64 of the same byte count),
+    and the host route once.  Prints one JSON line."""
+    import json
+    import time
+    from .engine import k_residual_bench
+    workload = argv[0]
+    reps = int(argv[1]) if len(argv) > 1 else 10
+    tt = tt or tijk_train(workload, device=device)
+    rmax = int(tt.ranks().max())
+    w = TTCross.from_cores([np.full((1, int(nk), 1), 1.0 / int(nk)) for nk in tt._n], device=device)
+
+    def timed(fn, host):
+        try:
+            fn().close()
+        except TTXError as e:                       # e.g. a result the engine cannot hold (its storage for d cores of the new rank)
+            return dict(error=str(e))
+        ms, ks = [], []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            r = fn()                                # synchronises before it returns
+            ms.append((time.perf_counter() - t0) * 1e3)
+            ks.append(tt.algebra_last())
+            r.close()
+        kms, rd, wr = float(np.median([k[0] for k in ks])), ks[0][1], ks[0][2]
+        probe_ms, probe_bytes = k_residual_bench(max(1, int((rd + wr) / (8 * 64))), 64, 20, device=device)
+        rate, probe = (rd + wr) / (kms * 1e-3), probe_bytes / (probe_ms * 1e-3)
+        t0 = time.perf_counter()
+        ref = host()
+        host_ms = (time.perf_counter() - t0) * 1e3
+        r = fn()
+        same = all(r.core(k).tobytes() == ref.core(k).tobytes() for k in range(1, r.d + 1))
+        out = dict(ms=float(np.median(ms)), kernel_ms=kms, bytes_read=rd, bytes_written=wr, bytes_per_s=rate, probe_bytes_per_s=probe,
+                   fraction_of_probe=rate / probe, host_route_ms=host_ms, same_bytes_as_host_route=same, ranks_max=int(r.ranks().max()))
+        r.close()
+        ref.close()
+        return out
+
+    res = dict(workload=workload, d=tt.d, max_rank=rmax, reps=reps)
+    if 2 * rmax <= 128:
+        res["x_plus_x"] = timed(lambda: TTCross.lincomb([1.0, 1.0], [tt, tt]), lambda: algebra_host([1.0, 1.0], [tt, tt]))
+        res["x_minus_x"] = timed(lambda: TTCross.lincomb([1.0, -1.0], [tt, tt]), lambda: algebra_host([1.0, -1.0], [tt, tt]))
+    res["x_times_w"] = timed(lambda: tt.hadamard(w), lambda: hadamard_host(tt, w))
+    if rmax * rmax <= 128:
+        res["x_times_x"] = timed(lambda: tt.hadamard(tt), lambda: hadamard_host(tt, tt))
+    if workload in TIJK_WORKLOADS and 2 * rmax <= 128:
+        kind, m, n, r, piv = TIJK_WORKLOADS[workload]
+        s = ising_setup(kind, m, n)
+        fast = TTCross(s["n"], s["fun_id"], s["par"], r, pivoting=piv, accuracy=s["acc"], quad=s["quad"], tru=s["tru"],
+                       nproc=8 if m >= 32 else 1, device=device, arith="fast").run()
+        if fast.arith == "fast" and all(int(a) + int(b) <= 128 for a, b in zip(tt.ranks()[1:-1], fast.ranks()[1:-1])):
+            t0 = time.perf_counter()
+            dist = tt.dist(fast)
+            ms = (time.perf_counter() - t0) * 1e3
+            nx, ny, xy = tt.norm(), fast.norm(), tt.dot(fast)
+            res["dist_exact_fast"] = dict(dist=dist, ms=ms, norm_exact=nx, norm_fast=ny,
+                                          by_dots=float(np.sqrt(max(nx * nx - 2.0 * xy + ny * ny, 0.0))))
+        fast.close()
+    print(json.dumps(res))
+    return res
+
+
 if __name__ == "__main__":
     if sys.argv[1] == "tijk":
         run_tijk(sys.argv[2:])
     elif sys.argv[1] == "contract":
         run_contract(sys.argv[2:])
+    elif sys.argv[1] == "algebra":
+        run_algebra(sys.argv[2:])
     elif sys.argv[1] == "chf":
         run_chf(sys.argv[2:])
     elif sys.argv[1] == "pdf":

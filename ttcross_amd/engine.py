@@ -102,6 +102,9 @@ def load_library():
     L.ttx_contract.argtypes = [c_void_p, POINTER(c_int32), POINTER(c_double), POINTER(c_void_p)]
     L.ttx_marginals.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double)]
     L.ttx_contract_modesum.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double)]
+    L.ttx_lincomb.argtypes = [c_int32, POINTER(c_double), POINTER(c_void_p), POINTER(c_void_p)]
+    L.ttx_hadamard.argtypes = [c_void_p, c_void_p, POINTER(c_void_p)]
+    L.ttx_algebra_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double)]
     L.ttx_zquad.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
     L.ttx_accchk.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
     L.ttx_from_tt.argtypes = [POINTER(c_void_p), c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), c_int32]
@@ -558,6 +561,57 @@ class TTCross:
         ms, by = c_double(), c_double()
         _check(load_library().ttx_contract_modesum(self._h, ctypes.byref(ms), ctypes.byref(by)))
         return ms.value, by.value
+
+    # ---- sums and elementwise products of resident trains (include/ttx.h: ttx_lincomb, ttx_hadamard) -----
+    @staticmethod
+    def lincomb(coefs, trains):
+        """sum_t coefs[t] * trains[t] as a new engine on the same device: ranks add on the interior bonds, the first cores are
+        multiplied by their coefficients, everything else is copied (block diagonal cores with explicit zeros).  The same train
+        may appear several times.  Rank sums above 128 are refused: round the terms, or fewer of them, first (svd).  No core
+        crosses the host link."""
+        trains = list(trains)
+        c = np.ascontiguousarray(np.asarray(coefs, dtype=np.float64).ravel())
+        if not trains or c.size != len(trains):
+            raise ValueError(f"lincomb: one coefficient per train expected (got {c.size} and {len(trains)})")
+        hs = (c_void_p * len(trains))(*[t._h for t in trains])
+        h = c_void_p()
+        _check(load_library().ttx_lincomb(len(trains), _dp(c), hs, ctypes.byref(h)))
+        return TTCross._adopt(h, trains[0].device)
+
+    def axpby(self, alpha, beta, y):
+        """alpha * self + beta * y (lincomb of two trains)"""
+        return TTCross.lincomb([alpha, beta], [self, y])
+
+    def hadamard(self, y):
+        """The elementwise product self(i) * y(i) as a new engine on the same device: ranks multiply (products above 128 are
+        refused), the index of self runs fastest on both bonds; y may be self."""
+        h = c_void_p()
+        _check(load_library().ttx_hadamard(self._h, y._h, ctypes.byref(h)))
+        return TTCross._adopt(h, self.device)
+
+    def dist(self, y):
+        """|self - y| in the Frobenius norm as norm(self - y): the QR-based norm of the difference train keeps what
+        sqrt(dot(x,x) - 2 dot(x,y) + dot(y,y)) loses to cancellation below sqrt(2^-53) |x|"""
+        t = TTCross.lincomb([1.0, -1.0], [self, y])
+        try:
+            return t.norm()
+        finally:
+            t.close()
+
+    def wdot(self, y, w=None):
+        """sum_i w(i) self(i) y(i) with rank-1 weights w as for quad (None: plain sum): quad of the elementwise product"""
+        t = self.hadamard(y)
+        try:
+            return t.quad(w)
+        finally:
+            t.close()
+
+    def algebra_last(self):
+        """(milliseconds, bytes read, bytes written) of the assembly kernel of the last lincomb / hadamard that had this engine
+        as its first operand (include/ttx.h: ttx_algebra_last)"""
+        ms, rd, wr = c_double(), c_double(), c_double()
+        _check(load_library().ttx_algebra_last(self._h, ctypes.byref(ms), ctypes.byref(rd), ctypes.byref(wr)))
+        return ms.value, rd.value, wr.value
 
     # ---- tt_lib utilities on the resident TT (lib/tt.f90: ort, svd, norm, dot_product, tijk) --------------
     def ort(self):

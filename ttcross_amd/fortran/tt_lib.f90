@@ -67,7 +67,55 @@ module tt_lib
  ! partial contraction on the device (not in the reference): contract(arg,keep,res,w), marginals(arg,marg,w)
  interface contract;    module procedure dtt_contract;  end interface
  interface marginals;   module procedure dtt_marginals; end interface
+ ! sums and elementwise products on the device (not in the reference; its host + and * above stay as they are):
+ ! axpby(alpha,x,beta,y) = alpha*x + beta*y, hadamard(x,y) = x(i)*y(i).  Both return a dtt that holds the new train on the device
+ ! and, pulled, in %u; the variable the result is assigned to takes the device train over (dtt_assign)
+ interface axpby;       module procedure dtt_axpby;    end interface
+ interface hadamard;    module procedure dtt_hadamard; end interface
+ type(c_ptr),private,save :: tt_pending=c_null_ptr      ! the device train of the last axpby / hadamard result, until it is assigned
 contains
+ subroutine dtt_result(res,hn,arg)
+  ! res = the new device train hn with the modes of arg, pulled.  A function result cannot be dealloc'ed by the caller: its
+  ! device train goes to the variable it is assigned to; one that never was assigned is released by the next result
+  use ttx_c
+  type(dtt),intent(inout) :: res
+  type(c_ptr),intent(in) :: hn
+  type(dtt),intent(in) :: arg
+  if(c_associated(tt_pending))call ttx_destroy(tt_pending)
+  res%l=1; res%m=arg%m; res%n(1:arg%m)=arg%n(1:arg%m)
+  res%ttx=hn; call dtt_pull(res); tt_pending=hn
+ end subroutine
+ function dtt_axpby(alpha,x,beta,y) result(c)
+  ! c = alpha*x + beta*y in one call on the device (ttx_lincomb): the cores of the host alpha*x + beta*y bit for bit -- the same
+  ! block layout, the same single multiply of the first cores; host trains are staged for the call like for norm / dot_product
+  use ttx_c
+  double precision,intent(in) :: alpha,beta
+  type(dtt),intent(in) :: x,y
+  type(dtt) :: c
+  type(c_ptr) :: hs(2),hn
+  real(c_double) :: cf(2)
+  logical :: tx,ty
+  call dtt_stage(x,hs(1),tx,'dtt_axpby'); call dtt_stage(y,hs(2),ty,'dtt_axpby')
+  cf(1)=alpha; cf(2)=beta; hn=c_null_ptr
+  call ttx_check(ttx_lincomb(2_c_int32_t,cf,hs,hn),'dtt_axpby')
+  if(tx)call ttx_destroy(hs(1))
+  if(ty)call ttx_destroy(hs(2))
+  call dtt_result(c,hn,x)
+ end function
+ function dtt_hadamard(x,y) result(c)
+  ! c(i) = x(i)*y(i) in one call on the device (ttx_hadamard): ranks multiply, the index of x runs fastest on both bonds
+  use ttx_c
+  type(dtt),intent(in) :: x,y
+  type(dtt) :: c
+  type(c_ptr) :: hx,hy,hn
+  logical :: tx,ty
+  call dtt_stage(x,hx,tx,'dtt_hadamard'); call dtt_stage(y,hy,ty,'dtt_hadamard')
+  hn=c_null_ptr
+  call ttx_check(ttx_hadamard(hx,hy,hn),'dtt_hadamard')
+  if(tx)call ttx_destroy(hx)
+  if(ty)call ttx_destroy(hy)
+  call dtt_result(c,hn,x)
+ end function
  subroutine ztt_alloc(arg)
   type(ztt),intent(inout) :: arg
   integer :: k,ierr
@@ -362,7 +410,8 @@ contains
  end subroutine
  subroutine dtt_assign(b,a)
   ! lib/tt.f90:1012-1020: b = a is a DEEP copy of the cores.  The device train stays with a: b is a host train (its own
-  ! storage, no handle), so dealloc(a) and dealloc(b) each release only what they own
+  ! storage, no handle), so dealloc(a) and dealloc(b) each release only what they own (the one exception, below: a is the
+  ! result of axpby / hadamard, which nobody else can release)
   type(dtt),intent(inout) :: b
   type(dtt),intent(in) :: a
   integer :: k
@@ -370,6 +419,10 @@ contains
   b%l=a%l; b%m=a%m; b%n(a%l:a%m)=a%n(a%l:a%m); b%r(a%l-1:a%m)=a%r(a%l-1:a%m)
   call dtt_alloc(b)
   do k=a%l,a%m; b%u(k)%p=a%u(k)%p; end do
+  ! the result of axpby / hadamard hands its device train to the variable it is assigned to
+  if(c_associated(a%ttx))then
+   if(c_associated(a%ttx,tt_pending))then; b%ttx=a%ttx; tt_pending=c_null_ptr; endif
+  end if
  end subroutine
  subroutine ztt_assign(b,a)
   ! lib/tt.f90:1021-1032

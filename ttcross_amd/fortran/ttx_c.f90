@@ -127,6 +127,16 @@ module ttx_c
   function ttx_marginals(h,w,out) bind(C,name='ttx_marginals') result(rc)
    import; type(c_ptr),value :: h,w; real(c_double),intent(out) :: out(*); integer(c_int) :: rc
   end function
+  ! sums and elementwise products of resident trains (include/ttx.h): out is a new engine owned by the caller
+  function ttx_lincomb(m,coef,x,out) bind(C,name='ttx_lincomb') result(rc)
+   import; integer(c_int32_t),value :: m; real(c_double),intent(in) :: coef(*); type(c_ptr),intent(in) :: x(*); type(c_ptr) :: out; integer(c_int) :: rc
+  end function
+  function ttx_hadamard(x,y,out) bind(C,name='ttx_hadamard') result(rc)
+   import; type(c_ptr),value :: x,y; type(c_ptr) :: out; integer(c_int) :: rc
+  end function
+  function ttx_algebra_last(h,ms,bytes_read,bytes_written) bind(C,name='ttx_algebra_last') result(rc)
+   import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms,bytes_read,bytes_written; integer(c_int) :: rc
+  end function
   function ttx_accchk(h,nlot,einf,efro,ainf,afro,pivot) bind(C,name='ttx_accchk') result(rc)
    import; type(c_ptr),value :: h; integer(c_int32_t),value :: nlot; real(c_double),intent(out) :: einf,efro,ainf,afro
    integer(c_int32_t),intent(out) :: pivot(*); integer(c_int) :: rc
