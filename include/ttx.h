@@ -271,6 +271,51 @@ int ttx_lincomb(int32_t m, const double *coef /* [m] */, ttx_engine *const *x /*
 int ttx_hadamard(ttx_engine *x, ttx_engine *y, ttx_engine **out);
 int ttx_algebra_last(const ttx_engine *h, double *ms, double *bytes_read, double *bytes_written);
 
+/* Samples drawn from the resident train by sequential conditional sampling, on the device (ttcross_amd/csrc/ttx_sample.h).
+ * Modes are 1-based, G_k is core k, r_0 = r_d = 1.
+ *   u     : npts rows of d uniforms, row-major [npts][d]; u_k draws mode k
+ *   w     : d blocks of n_k weights as for ttx_quad; NULL = all ones
+ *   fixed : d entries, 0 = the mode is drawn, f in 1..n_k = the mode is held at index f (its u_k is not looked at); NULL = all drawn
+ *   ind   : [npts][d], 1-based, the layout ttx_ijk_batch reads;  logq, val : [npts], each may be NULL
+ * Definition.  Effective weight e_k(i): w_k(i) for a drawn mode; for a fixed mode 1 at i = f_k and 0 elsewhere (the quadrature
+ * weight of a fixed mode does not enter).  Prefix vectors: l_0 = [1], l_k = l_(k-1) M_k with M_k = sum_i e_k(i) G_k(:, i, :), formed
+ * by the kernels of ttx_marginals in their summation order.  Head table of a drawn mode: H_k(i, b) = w_k(i) * sum_a l_(k-1)(a) G_k(a, i, b),
+ * the sum over ascending a from 0.0 with a separate multiply and add, the weight multiplied in last.
+ * Modes are drawn from the LAST to the first, so the running state is dtt_ijk's own chain.  x_(d+1) = [1]; for k = d .. 1:
+ *   m_k(i) = sum_b H_k(i, b) x_(k+1)(b)  (ascending b from 0.0, separate multiply and add);  p_k(i) = |m_k(i)|
+ *   c_k(i) = the inclusive running sum of p_k.  Its association order depends on i alone: indices are taken in blocks of 64,
+ *            i = 64 j + l; inside a block s(l) is formed in six doubling steps o = 1, 2, 4, .. 32, s(l) <- s(l - o) + s(l) for l >= o
+ *            (all l at once, from s = p), and c(64 j + l) = c(64 j - 1) + s(l), c(-1) = 0.  Not the grid, the chunk or the other
+ *            samples enter.  In floating point such a sum need not be monotone, hence the p > 0 in the next line.
+ *   t = u_k c_k(n_k);  i_k = the smallest i with p_k(i) > 0 and t < c_k(i); if there is none, or u_k >= 1, the largest i with
+ *   p_k(i) > 0.  An index with p_k(i) = 0 is never chosen.  A fixed mode takes i_k = f_k and computes no p.
+ *   x_k = G_k(:, i_k, :) x_(k+1) in the operation sequence of ttx_ijk_batch's TTX_EVAL_EXACT (sums from 0.0 over ascending b,
+ *   separate multiply and add, two rows per lane above rank 64; x_d is a copy of G_d(:, i_d, 1)).
+ * Outputs: ind = (i_1 .. i_d); val = x_1(1), the train's element at ind, equal bit for bit to ttx_ijk_batch(ind, TTX_EVAL_EXACT);
+ * logq = sum over the drawn modes, k = d .. 1, of log(p_k(i_k) / c_k(n_k)): the log of the probability with which ind was drawn.
+ * Distribution: for a train and weights without sign changes the samples follow |T(i)| w(i) / Z exactly, up to rounding.  For a
+ * signed train they follow the product of the ABSOLUTE conditional marginals, which is not |T| w / Z: exp(logq) is the proposal
+ * density to reweight with, E_q[val w(ind) / exp(logq)] = sum_i T(i) w(i) over the drawn modes at the fixed indices.
+ * Failed samples: c_k(n_k) is 0, NaN or Inf at some mode, or the u_k of a drawn mode is NaN or negative (-0.0 counts as 0).  A
+ * failed sample gets an index row of zeros, logq = NaN and val = 0.0, and is counted (ttx_sample_last); the others are untouched.
+ * Safety: an index is formed from lane numbers, never from a value, so whatever the cores, weights and u hold (NaN included)
+ * every index written lies in 0..n_k and no read leaves its table.  Arithmetic is plain double without a running exponent.
+ * A mode of up to 1024 indices keeps its row of p in LDS, a longer one in a per-wave row of the call's global work space.
+ * Samples go in chunks of TTX_SAMPLE_CHUNK (environment, default 2^18); the tables are built once per call; no atomics; a
+ * sample does not depend on its neighbours or on the chunk, and a call repeats bit for bit.  The train is not modified; the work
+ * space is the engine's own (the vectors of ttx_marginals are shared), allocated on first use and freed by ttx_destroy.
+ * ttx_sample_dev: u, ind, logq and val are pointers on the engine's device, w and fixed stay host pointers; it enqueues on the
+ * engine's stream and synchronises before it returns.  No sample crosses the host link: ind can go into ttx_ijk_batch_dev.
+ * npts = 0 succeeds and launches nothing.  TTX_EINVAL: npts < 0, null u / ind with npts > 0 (both before the engine is looked
+ * at), a fixed entry outside 0..n_k (before any device call), ranks above 128; TTX_ESTATE: an engine without a train; a
+ * multi-process engine is refused as by ttx_ijk (a replica, ttx_replicate, is accepted).
+ * ttx_sample_last: of the last call on this engine, the milliseconds (HIP events) of k_sm_head and of k_sm_draw (summed over the
+ * chunks), the bytes of the cores k_sm_head read (8 sum r(k-1) n(k) r(k) over the drawn modes) and the failed samples; any
+ * pointer may be NULL.  Added without a new ttx_version: look the symbols up. */
+int ttx_sample(ttx_engine *h, int64_t npts, const double *u /* [npts][d] */, const double *w, const int32_t *fixed, int32_t *ind, double *logq, double *val);
+int ttx_sample_dev(ttx_engine *h, int64_t npts, const double *u, const double *w, const int32_t *fixed, int32_t *ind, double *logq, double *val);
+int ttx_sample_last(const ttx_engine *h, double *ms_head, double *bytes_head, double *ms_draw, int64_t *nfailed);
+
 /* The finalised train of a MULTI-PROCESS job gathered onto EVERY process as a new single-process engine (same integrand, ranks,
  * RNG position; *out is owned by the caller: ttx_destroy).  Collective over the job's transport (each process contributes the
  * cores it holds; the others arrive by a SUM all-reduce into zero-filled slots, which is exact).  The reference's dtt_accchk,

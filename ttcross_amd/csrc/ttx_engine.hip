@@ -50,6 +50,7 @@ static cluster_kernel_t cluster_kernel(int var)
 #include "ttx_eval.h"
 #include "ttx_contract.h"
 #include "ttx_algebra.h"
+#include "ttx_sample.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const char *fmt, ...)
@@ -204,6 +205,13 @@ struct ttx_engine {
     EvBuf alg_meta;
     hipEvent_t alg_ev[2] = {nullptr, nullptr};
     double alg_ms = 0.0, alg_rd = 0.0, alg_wr = 0.0;
+    // sampling (ttx_sample.h): the head tables, the chunk buffers of the host entry, the global rows of long modes and the failure
+    // counter, grown on demand, freed in ttx_destroy; the figures of the last call
+    enum { SM_H, SM_U, SM_IND, SM_LQ, SM_VAL, SM_ROW, SM_CNT, SM_NBUF };
+    EvBuf sm[SM_NBUF];
+    hipEvent_t sm_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around k_sm_head; around the k_sm_draw of a chunk
+    double sm_ms_head = 0.0, sm_bytes = 0.0, sm_ms_draw = 0.0;
+    int64_t sm_failed = 0;
 };
 
 // ---- worker threads for the host integrand (the reference evaluates `fun` inside !$OMP PARALLEL DO regions,
@@ -843,6 +851,8 @@ extern "C" void ttx_destroy(ttx_engine *h)
     for (auto &e : h->ct_ev) if (e) (void)hipEventDestroy(e);
     if (h->alg_meta.p) (void)hipFree(h->alg_meta.p);
     for (auto &e : h->alg_ev) if (e) (void)hipEventDestroy(e);
+    for (auto &b : h->sm) if (b.p) (void)hipFree(b.p);
+    for (auto &e : h->sm_ev) if (e) (void)hipEventDestroy(e);
     if (h->h_sum_base) (void)hipHostFree(h->h_sum_base);
     if (h->h_val) (void)hipHostFree(h->h_val);
     if (h->h_svd) (void)hipHostFree(h->h_svd);
@@ -3328,6 +3338,139 @@ extern "C" int ttx_contract_modesum(const ttx_engine *h, double *ms, double *byt
 {
     if (!h || !ms || !bytes) return fail(TTX_EINVAL, "ttx_contract_modesum: null argument");
     *ms = h->ct_ms; *bytes = h->ct_bytes;
+    return TTX_OK;
+}
+
+// ---- samples from the resident train (ttx_sample.h) -------------------------------------------------------------------------------
+static size_t sm_chunk()
+{
+    if (const char *e = getenv("TTX_SAMPLE_CHUNK")) { const long long v = atoll(e); if (v >= 1) return (size_t)std::min<long long>(v, 1ll << 24); }
+    return (size_t)1 << 18;
+}
+// both entries: u, ind, logq, val are host pointers (dev false: staged chunk by chunk) or pointers on the engine's device
+static int sm_run(ttx_engine *h, const char *who, int64_t npts, const double *u, const double *w, const int32_t *fixed, int32_t *ind, double *logq, double *val, bool dev)
+{
+    if (npts < 0 || (npts > 0 && (!u || !ind))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
+    if (!h || !h->ran) return fail(TTX_ESTATE, "%s: no tensor train (run dtt_dmrgg first)", who);
+    if (h->W > 1) return tt_prepare(h, who);
+    const int d = h->d;
+    if (fixed) for (int k = 0; k < d; k++) if (fixed[k] < 0 || fixed[k] > h->n1[k + 1]) return fail(TTX_EINVAL, "%s: fixed(%d) = %d (0 .. %d expected)", who, k + 1, fixed[k], h->n1[k + 1]);
+    h->sm_ms_head = h->sm_ms_draw = h->sm_bytes = 0.0; h->sm_failed = 0;
+    if (npts == 0) return TTX_OK;
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    int rc;
+    EvTrain T;
+    if ((rc = ev_train(h, &T))) return rc;
+    // the prefix vectors: mode sums with the effective weights (a fixed mode: the unit vector of its index), then the l chain
+    CtPlan pl;
+    ct_plan(h, std::vector<char>(d, 1), pl);
+    std::vector<double> eff(pl.wsize, 1.0);
+    if (w) memcpy(eff.data(), w, sizeof(double) * pl.wsize);
+    std::vector<int> fx(d, 0);
+    std::vector<size_t> hoff(d, 0);
+    std::vector<SmTile> tiles;
+    size_t hsize = 0;
+    int nrow = 0;
+    for (int k = 0; k < d; k++) {
+        const CtCore &c = pl.cores[k];
+        if (fixed && fixed[k]) {
+            fx[k] = fixed[k];
+            for (int i = 0; i < c.n; i++) eff[c.woff + i] = i == fixed[k] - 1 ? 1.0 : 0.0;
+            continue;
+        }
+        hoff[k] = hsize; hsize += (size_t)c.n * c.r1;
+        nrow = std::max(nrow, c.n);
+        h->sm_bytes += 8.0 * c.r0 * c.n * c.r1;
+        const int ti = sm_tile_rows(c.r0);
+        for (int b = 0; b < c.r1; b++) for (int i0 = 0; i0 < c.n; i0 += ti) tiles.push_back(SmTile{k, b, i0, std::min(ti, c.n - i0)});
+    }
+    if (tiles.size() > 0x7fffffffull) return fail(TTX_EINVAL, "%s: too many head tiles (%zu)", who, tiles.size());
+    const int ldv = h->RM;
+    CtMeta meta(h->ct_meta_host);
+    const size_t o_cores = meta.put(pl.cores), o_tiles = meta.put(pl.tiles), o_r = meta.put(pl.r), o_moff = meta.put(pl.moff),
+                 o_sm = meta.put(tiles), o_hoff = meta.put(hoff), o_fx = meta.put(fx);
+    if ((rc = buf_reserve(h, h->ct[ttx_engine::CT_META], h->ct_meta_host.size())) || (rc = buf_reserve(h, h->ct[ttx_engine::CT_VEC], sizeof(double) * (2 * (size_t)d + 4) * ldv)) ||
+        (rc = buf_reserve(h, h->sm[ttx_engine::SM_H], sizeof(double) * std::max<size_t>(hsize, 1))) || (rc = buf_reserve(h, h->sm[ttx_engine::SM_CNT], sizeof(long long)))) return rc;
+    char *dm = (char *)h->ct[ttx_engine::CT_META].p;
+    HIPCHECK(hipMemcpyAsync(dm, h->ct_meta_host.data(), h->ct_meta_host.size(), hipMemcpyHostToDevice, h->stream));
+    const double ct_ms = h->ct_ms, ct_bytes = h->ct_bytes;                      // ttx_contract_modesum keeps reporting its own last call
+    rc = ct_modesum(h, pl, eff.data(), (const CtCore *)(dm + o_cores), (const CtTile *)(dm + o_tiles));
+    h->ct_ms = ct_ms; h->ct_bytes = ct_bytes;
+    if (rc) return rc;
+    double *L = (double *)h->ct[ttx_engine::CT_VEC].p, *S = L + (size_t)d * ldv, *H = (double *)h->sm[ttx_engine::SM_H].p;
+    long long *dcnt = (long long *)h->sm[ttx_engine::SM_CNT].p;
+    hipLaunchKernelGGL(k_ct_chains, dim3(2), dim3(1024), 0, h->stream, d, (const int *)(dm + o_r), (const size_t *)(dm + o_moff), (const double *)h->ct[ttx_engine::CT_M].p, L, S, ldv);
+    for (auto &e : h->sm_ev) if (!e) HIPCHECK(hipEventCreate(&e));
+    HIPCHECK(hipMemsetAsync(dcnt, 0, sizeof(long long), h->stream));
+    if (!tiles.empty()) {
+        HIPCHECK(hipEventRecord(h->sm_ev[0], h->stream));
+        hipLaunchKernelGGL(k_sm_head, dim3((unsigned)tiles.size()), dim3(256), 0, h->stream, (const CtCore *)(dm + o_cores), (const SmTile *)(dm + o_sm), h->RM, h->P.SS,
+                           (const double *)h->ct[ttx_engine::CT_W].p, (const double *)L, ldv, (const size_t *)(dm + o_hoff), H);
+        HIPCHECK(hipEventRecord(h->sm_ev[1], h->stream));
+    }
+    // the draw: one wave per sample, 4 waves per workgroup, the grid capped at 8 workgroups per CU as k_ev_exact's
+    const size_t chunk = std::min<size_t>(sm_chunk(), (size_t)npts);
+    int ncu = 256;
+    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
+    const int gridmax = (int)std::min<long long>(((long long)chunk + 3) / 4, (long long)ncu * 8);
+    const int ldsrow = std::min(nrow, TTX_SM_LDSROW);
+    const size_t growlen = nrow > TTX_SM_LDSROW ? (size_t)nrow : 0;
+    const size_t lds = 4 * sizeof(double) * (2 * (size_t)T.ldx + d + (((size_t)d + 1) >> 1) + ldsrow);
+    if (lds > 160 * 1024) return fail(TTX_EINVAL, "%s: %d modes need %zu bytes of LDS per workgroup (160 KB at most)", who, d, lds);
+    if (lds > 64 * 1024) HIPCHECK(hipFuncSetAttribute((const void *)k_sm_draw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (growlen && (rc = buf_reserve(h, h->sm[ttx_engine::SM_ROW], sizeof(double) * growlen * 4 * gridmax))) return rc;
+    double *grow = growlen ? (double *)h->sm[ttx_engine::SM_ROW].p : nullptr;
+    if (!dev && ((rc = buf_reserve(h, h->sm[ttx_engine::SM_U], sizeof(double) * chunk * d)) || (rc = buf_reserve(h, h->sm[ttx_engine::SM_IND], sizeof(int) * chunk * d)) ||
+                 (rc = buf_reserve(h, h->sm[ttx_engine::SM_LQ], sizeof(double) * chunk)) || (rc = buf_reserve(h, h->sm[ttx_engine::SM_VAL], sizeof(double) * chunk)))) return rc;
+    for (int64_t o = 0; o < npts; o += (int64_t)chunk) {
+        const size_t c = (size_t)std::min<int64_t>((int64_t)chunk, npts - o);
+        const double *du = u + (size_t)o * d;
+        int *di = ind + (size_t)o * d;
+        double *dl = logq ? logq + o : nullptr, *dv = val ? val + o : nullptr;
+        if (!dev) {
+            HIPCHECK(hipMemcpyAsync(h->sm[ttx_engine::SM_U].p, du, sizeof(double) * c * d, hipMemcpyHostToDevice, h->stream));
+            du = (const double *)h->sm[ttx_engine::SM_U].p; di = (int *)h->sm[ttx_engine::SM_IND].p;
+            if (logq) dl = (double *)h->sm[ttx_engine::SM_LQ].p;
+            if (val) dv = (double *)h->sm[ttx_engine::SM_VAL].p;
+        }
+        const int grid = (int)std::min<long long>(((long long)c + 3) / 4, (long long)gridmax);
+        HIPCHECK(hipEventRecord(h->sm_ev[2], h->stream));
+        hipLaunchKernelGGL(k_sm_draw, dim3(grid), dim3(256), lds, h->stream, T, (const size_t *)(dm + o_hoff), (const int *)(dm + o_fx), (const double *)H, ldsrow, grow, growlen,
+                           (long long)c, du, di, dl, dv);
+        HIPCHECK(hipEventRecord(h->sm_ev[3], h->stream));
+        hipLaunchKernelGGL(k_sm_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const int *)di, dcnt);
+        if (!dev) {
+            HIPCHECK(hipMemcpyAsync(ind + (size_t)o * d, di, sizeof(int) * c * d, hipMemcpyDeviceToHost, h->stream));
+            if (logq) HIPCHECK(hipMemcpyAsync(logq + o, dl, sizeof(double) * c, hipMemcpyDeviceToHost, h->stream));
+            if (val) HIPCHECK(hipMemcpyAsync(val + o, dv, sizeof(double) * c, hipMemcpyDeviceToHost, h->stream));
+        }
+        HIPCHECK(hipStreamSynchronize(h->stream));
+        HIPCHECK(hipGetLastError());
+        float ms = 0.f;
+        HIPCHECK(hipEventElapsedTime(&ms, h->sm_ev[2], h->sm_ev[3]));
+        h->sm_ms_draw += ms;
+    }
+    long long nf = 0;
+    HIPCHECK(hipMemcpy(&nf, dcnt, sizeof(long long), hipMemcpyDeviceToHost));
+    h->sm_failed = nf;
+    if (!tiles.empty()) { float ms = 0.f; HIPCHECK(hipEventElapsedTime(&ms, h->sm_ev[0], h->sm_ev[1])); h->sm_ms_head = ms; }
+    return TTX_OK;
+}
+extern "C" int ttx_sample(ttx_engine *h, int64_t npts, const double *u, const double *w, const int32_t *fixed, int32_t *ind, double *logq, double *val)
+{
+    return sm_run(h, "ttx_sample", npts, u, w, fixed, ind, logq, val, false);
+}
+extern "C" int ttx_sample_dev(ttx_engine *h, int64_t npts, const double *u, const double *w, const int32_t *fixed, int32_t *ind, double *logq, double *val)
+{
+    return sm_run(h, "ttx_sample_dev", npts, u, w, fixed, ind, logq, val, true);
+}
+extern "C" int ttx_sample_last(const ttx_engine *h, double *ms_head, double *bytes_head, double *ms_draw, int64_t *nfailed)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_sample_last: null engine");
+    if (ms_head) *ms_head = h->sm_ms_head;
+    if (bytes_head) *bytes_head = h->sm_bytes;
+    if (ms_draw) *ms_draw = h->sm_ms_draw;
+    if (nfailed) *nfailed = h->sm_failed;
     return TTX_OK;
 }
 

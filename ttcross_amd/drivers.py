@@ -479,9 +479,97 @@ def run_algebra(argv, device=0, tt=None):
     return res
 
 
+def sample_host(tt, u, w=None):
+    """what a user does without ttx_sample: every core to the host with core(k), then the conditional marginals walked in
+    numpy from the last mode to the first.  Returns (ind, logq, val) of the definition in include/ttx.h, in numpy's own
+    summation order."""
+    cores = [tt.core(k) for k in range(1, tt.d + 1)]
+    w = [np.ones(c.shape[1]) for c in cores] if w is None else [np.asarray(q, dtype=np.float64) for q in w]
+    u = np.asarray(u, dtype=np.float64)
+    npts, d = u.shape
+    lv, heads = np.ones(1), []
+    for c, q in zip(cores, w):
+        heads.append(np.einsum("a,aib->ib", lv, c) * q[:, None])
+        lv = lv @ np.einsum("aib,i->ab", c, q)
+    x = np.ones((npts, 1))
+    ind, logq, rows = np.zeros((npts, d), dtype=np.int32), np.zeros(npts), np.arange(npts)
+    for k in range(d - 1, -1, -1):
+        p = np.abs(x @ heads[k].T)
+        c = np.cumsum(p, axis=1)
+        hit = (p > 0) & (u[:, k:k + 1] * c[:, -1:] < c)
+        i = np.where(hit.any(1), hit.argmax(1), p.shape[1] - 1 - (p[:, ::-1] > 0).argmax(1))
+        logq += np.log(p[rows, i] / c[:, -1])
+        ind[:, k] = i + 1
+        x = np.einsum("asb,sb->sa", cores[k][:, i, :], x)
+    return ind, logq, x[:, 0]
+
+
+def run_sample(argv, device=0, repeats=5, tt=None, host_npts=1000):
+    """sample WORKLOAD NPTS[,NPTS...]: the trains of the tijk sub-command, weights 1 / n, seeded uniforms made ON the device; per
+    sample count one warm-up and the median of `repeats` calls through the device-pointer entry: the call, the two kernels
+    (HIP events, ttx_sample_last), k_sm_head's bytes / s next to the bandwidth probe at the same byte count, samples per second
+    of k_sm_draw, and tijk_batch(ind, "exact") on the drawn indices; then the host route sample_host once at host_npts
+    samples.  Prints one JSON line per sample count."""
+    import json
+    import time
+    import torch
+    from . import engine as E
+    torch.cuda.init()          # a torch that brings its own HIP runtime must initialise its device before the engine's library does
+    workload = argv[0]
+    tt = tt or tijk_train(workload, device=device)
+    dev = torch.device("cuda", device)
+    w = [np.full(int(nk), 1.0 / int(nk)) for nk in tt._n]
+    out = []
+    for npts in [int(float(x)) for x in argv[1].split(",")]:
+        g = torch.Generator(device=dev)
+        g.manual_seed(20240607)
+        u = torch.rand((npts, tt.d), dtype=torch.float64, device=dev, generator=g)
+        torch.cuda.synchronize(dev)
+        res = tt.sample(u, w)
+        ms, last = [], []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            res = tt.sample(u, w)                  # synchronises before it returns
+            ms.append((time.perf_counter() - t0) * 1e3)
+            last.append(tt.sample_last())
+        head = float(np.median([x["ms_head"] for x in last]))
+        draw = float(np.median([x["ms_draw"] for x in last]))
+        by = last[0]["bytes_head"]
+        probe_ms, probe_by = E.k_residual_bench(max(int(by // 512), 1), 64, 20, device=device)
+        tt.tijk_batch(res["ind"], "exact")
+        tj = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            val = tt.tijk_batch(res["ind"], "exact")
+            tj.append((time.perf_counter() - t0) * 1e3)
+        tijk = float(np.median(tj))
+        r = dict(workload=workload, npts=npts, d=tt.d, max_rank=int(tt.ranks().max()), call_ms=float(np.median(ms)), head_ms=head,
+                 head_bytes=by, head_bytes_per_s=by / (head * 1e-3) if head > 0 else None,
+                 probe_bytes_per_s=probe_by / (probe_ms * 1e-3) if probe_ms > 0 else None, draw_ms=draw,
+                 draw_samples_per_s=npts / (draw * 1e-3) if draw > 0 else None, tijk_exact_ms=tijk,
+                 tijk_points_per_s=npts / (tijk * 1e-3) if tijk > 0 else None, draw_over_tijk=draw / tijk if tijk > 0 else None,
+                 failed=last[-1]["failed"], val_is_tijk=bool(torch.equal(val, res["val"])), mean_logq=float(res["logq"].mean().item()))
+        if r["head_bytes_per_s"] and r["probe_bytes_per_s"]:
+            r["head_fraction_of_probe"] = r["head_bytes_per_s"] / r["probe_bytes_per_s"]
+        print(json.dumps(r), flush=True)
+        out.append(r)
+    uh = np.random.default_rng(7).random((host_npts, tt.d))
+    t0 = time.perf_counter()
+    hi, hq, hv = sample_host(tt, uh, w)
+    host_ms = (time.perf_counter() - t0) * 1e3
+    di = tt.sample(uh, w)["ind"]
+    r = dict(workload=workload, host_route_npts=host_npts, host_route_ms=host_ms, host_samples_per_s=host_npts / (host_ms * 1e-3),
+             host_rows_equal_device=int(np.all(hi == di, axis=1).sum()))
+    print(json.dumps(r), flush=True)
+    out.append(r)
+    return out
+
+
 if __name__ == "__main__":
     if sys.argv[1] == "tijk":
         run_tijk(sys.argv[2:])
+    elif sys.argv[1] == "sample":
+        run_sample(sys.argv[2:])
     elif sys.argv[1] == "contract":
         run_contract(sys.argv[2:])
     elif sys.argv[1] == "algebra":

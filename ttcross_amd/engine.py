@@ -105,6 +105,9 @@ def load_library():
     L.ttx_lincomb.argtypes = [c_int32, POINTER(c_double), POINTER(c_void_p), POINTER(c_void_p)]
     L.ttx_hadamard.argtypes = [c_void_p, c_void_p, POINTER(c_void_p)]
     L.ttx_algebra_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double)]
+    L.ttx_sample.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
+    L.ttx_sample_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(c_double), POINTER(c_int32), c_void_p, c_void_p, c_void_p]
+    L.ttx_sample_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
     L.ttx_zquad.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
     L.ttx_accchk.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
     L.ttx_from_tt.argtypes = [POINTER(c_void_p), c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), c_int32]
@@ -612,6 +615,67 @@ class TTCross:
         ms, rd, wr = c_double(), c_double(), c_double()
         _check(load_library().ttx_algebra_last(self._h, ctypes.byref(ms), ctypes.byref(rd), ctypes.byref(wr)))
         return ms.value, rd.value, wr.value
+
+    # ---- samples from the resident train (include/ttx.h: ttx_sample) -------------------------------------
+    def sample(self, u_or_npts, w=None, fixed=None, seed=None, want=("ind", "logq", "val")):
+        """Indices drawn from the train by sequential conditional sampling on the device (include/ttx.h: ttx_sample): for a train
+        and weights without sign changes they follow |T(i)| w(i) / Z.  u_or_npts: uniforms of shape (npts, d), or a count, for
+        which the uniforms come from numpy.random.default_rng(seed); w as for quad; fixed: d entries, 0 = drawn, f = held at the
+        1-based index f.  Returns a dict with the entries named in want: ind (npts, d) int32, 1-based; logq, the log of the
+        probability of the drawn index; val, the train's element there (tijk_batch(ind, "exact")).  A failed sample (all its
+        conditional weights zero, a NaN or negative u) has an index row of zeros, logq NaN and val 0; sample_last() counts them.
+        A contiguous float64 torch tensor on the engine's device is passed by pointer (ttx_sample_dev) and gives torch tensors
+        on that device: ind can go straight into tijk_batch."""
+        L = load_library()
+        bad = set(want) - {"ind", "logq", "val"}
+        if bad:
+            raise ValueError(f"sample: unknown output {sorted(bad)}")
+        wa = self._weights(w, "sample")
+        fx = None
+        if fixed is not None:
+            fx = np.ascontiguousarray(fixed, dtype=np.int32).ravel()
+            if fx.size != self.d:
+                raise ValueError(f"sample: {self.d} fixed entries expected")
+        if type(u_or_npts).__module__.split(".")[0] == "torch":
+            import torch
+            u = u_or_npts
+            if not u.is_cuda:
+                return {k: torch.from_numpy(v) for k, v in self.sample(u.numpy(), w, fixed, seed, want).items()}
+            if u.device.index != self.device:
+                raise ValueError(f"sample: the tensor lies on {u.device}, the engine on device {self.device}")
+            if u.dtype != torch.float64 or not u.is_contiguous() or u.dim() != 2 or u.shape[1] != self.d:
+                raise ValueError(f"sample: a contiguous float64 tensor of shape (npts, {self.d}) expected")
+            npts = u.shape[0]
+            ind = torch.empty((npts, self.d), dtype=torch.int32, device=u.device)
+            lq = torch.empty(npts, dtype=torch.float64, device=u.device) if "logq" in want else None
+            va = torch.empty(npts, dtype=torch.float64, device=u.device) if "val" in want else None
+            torch.cuda.current_stream(u.device).synchronize()        # the engine runs on a stream of its own
+            _check(L.ttx_sample_dev(self._h, npts, c_void_p(u.data_ptr()), _dp(wa), _ip(fx), c_void_p(ind.data_ptr()),
+                                    c_void_p(lq.data_ptr()) if lq is not None else None, c_void_p(va.data_ptr()) if va is not None else None))
+            out = dict(ind=ind, logq=lq, val=va)
+            return {k: out[k] for k in ("ind", "logq", "val") if k in want}
+        if np.ndim(u_or_npts) == 0:
+            npts = int(u_or_npts)
+            if npts < 0:
+                raise ValueError("sample: a negative count")
+            u = np.random.default_rng(seed).random((npts, self.d))
+        else:
+            u = np.ascontiguousarray(u_or_npts, dtype=np.float64)
+            if u.ndim != 2 or u.shape[1] != self.d:
+                raise ValueError(f"sample: an array of shape (npts, {self.d}) expected")
+        npts = u.shape[0]
+        ind = np.zeros((npts, self.d), dtype=np.int32)
+        lq = np.zeros(npts) if "logq" in want else None
+        va = np.zeros(npts) if "val" in want else None
+        _check(L.ttx_sample(self._h, npts, _dp(u), _dp(wa), _ip(fx), _ip(ind), _dp(lq), _dp(va)))
+        out = dict(ind=ind, logq=lq, val=va)
+        return {k: out[k] for k in ("ind", "logq", "val") if k in want}
+
+    def sample_last(self):
+        """dict(ms_head, bytes_head, ms_draw, failed) of the last sample() on this engine (include/ttx.h: ttx_sample_last)"""
+        a, b, c, n = c_double(), c_double(), c_double(), c_int64()
+        _check(load_library().ttx_sample_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(n)))
+        return dict(ms_head=a.value, bytes_head=b.value, ms_draw=c.value, failed=int(n.value))
 
     # ---- tt_lib utilities on the resident TT (lib/tt.f90: ort, svd, norm, dot_product, tijk) --------------
     def ort(self):

@@ -67,6 +67,8 @@ module tt_lib
  ! partial contraction on the device (not in the reference): contract(arg,keep,res,w), marginals(arg,marg,w)
  interface contract;    module procedure dtt_contract;  end interface
  interface marginals;   module procedure dtt_marginals; end interface
+ ! samples drawn from the train on the device (not in the reference): sample(arg,u,ind,w,fixed,logq,val)
+ interface sample;      module procedure dtt_sample;    end interface
  ! sums and elementwise products on the device (not in the reference; its host + and * above stay as they are):
  ! axpby(alpha,x,beta,y) = alpha*x + beta*y, hadamard(x,y) = x(i)*y(i).  Both return a dtt that holds the new train on the device
  ! and, pulled, in %u; the variable the result is assigned to takes the device train over (dtt_assign)
@@ -370,6 +372,40 @@ contains
   if(temp)call ttx_destroy(h)
   marg=0.d0; off=0
   do k=1,arg%m; marg(1:arg%n(k),k)=o(off+1:off+arg%n(k)); off=off+arg%n(k); end do
+ end subroutine
+ subroutine dtt_sample(arg,u,ind,w,fixed,logq,val)
+  ! ind(:,p) = a multi-index drawn from arg with the uniforms u(:,p) by sequential conditional sampling, the last mode first
+  ! (include/ttx.h: ttx_sample): for a train and weights without sign changes the indices follow |arg(i)| w(i) / Z.  w: rank-1
+  ! weights as the quad argument of dtt_quad (absent: ones); fixed(k) = 0 draws mode k, f holds it at index f (absent: all drawn);
+  ! logq(p) = log of the probability of ind(:,p), val(p) = arg at ind(:,p).  A failed sample has ind(:,p) = 0, logq NaN, val 0.
+  ! One call on the device; a host train is staged for the call like for norm / dot_product.
+  use ttx_c
+  type(dtt),intent(in) :: arg
+  double precision,intent(in) :: u(:,:)
+  integer,intent(out) :: ind(:,:)
+  type(dtt),intent(in),optional :: w
+  integer,intent(in),optional :: fixed(:)
+  double precision,intent(out),target,optional :: logq(:),val(:)
+  real(c_double),allocatable,target :: ww(:)
+  real(c_double),allocatable :: uu(:,:)
+  integer(c_int32_t),allocatable :: ix(:,:)
+  integer(c_int32_t),target :: fx(tt_size)
+  type(c_ptr) :: h,wp,fp,lp,vp
+  logical :: temp
+  integer :: npts
+  npts=size(u,2)
+  if(npts.eq.0)return
+  wp=c_null_ptr; fp=c_null_ptr; lp=c_null_ptr; vp=c_null_ptr
+  if(present(w))then; call dtt_weights(arg,w,ww); wp=c_loc(ww); endif
+  if(present(fixed))then; fx(1:arg%m)=fixed(1:arg%m); fp=c_loc(fx); endif
+  if(present(logq))lp=c_loc(logq)
+  if(present(val))vp=c_loc(val)
+  allocate(uu(arg%m,npts),ix(arg%m,npts)); uu=u(1:arg%m,1:npts)
+  call dtt_stage(arg,h,temp,'dtt_sample')
+  call ttx_check(ttx_sample(h,int(npts,c_int64_t),uu,wp,fp,ix,lp,vp),'dtt_sample')
+  if(temp)call ttx_destroy(h)
+  ind(1:arg%m,1:npts)=ix
+  deallocate(uu,ix)
  end subroutine
  double precision function dtt_ijk(arg,ind) result(a)
   ! lib/tt.f90:630-652: one element; a resident train is asked on the device, a host train is contracted here

@@ -137,6 +137,17 @@ module ttx_c
   function ttx_algebra_last(h,ms,bytes_read,bytes_written) bind(C,name='ttx_algebra_last') result(rc)
    import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms,bytes_read,bytes_written; integer(c_int) :: rc
   end function
+  ! samples drawn from the resident train (include/ttx.h); u(d,npts), ind(d,npts); w, fixed, logq, val: c_null_ptr where not wanted
+  function ttx_sample(h,npts,u,w,fixed,ind,logq,val) bind(C,name='ttx_sample') result(rc)
+   import; type(c_ptr),value :: h,w,fixed,logq,val; integer(c_int64_t),value :: npts; real(c_double),intent(in) :: u(*)
+   integer(c_int32_t),intent(out) :: ind(*); integer(c_int) :: rc
+  end function
+  function ttx_sample_dev(h,npts,u,w,fixed,ind,logq,val) bind(C,name='ttx_sample_dev') result(rc)
+   import; type(c_ptr),value :: h,u,w,fixed,ind,logq,val; integer(c_int64_t),value :: npts; integer(c_int) :: rc
+  end function
+  function ttx_sample_last(h,ms_head,bytes_head,ms_draw,nfailed) bind(C,name='ttx_sample_last') result(rc)
+   import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms_head,bytes_head,ms_draw; integer(c_int64_t),intent(out) :: nfailed; integer(c_int) :: rc
+  end function
   function ttx_accchk(h,nlot,einf,efro,ainf,afro,pivot) bind(C,name='ttx_accchk') result(rc)
    import; type(c_ptr),value :: h; integer(c_int32_t),value :: nlot; real(c_double),intent(out) :: einf,efro,ainf,afro
    integer(c_int32_t),intent(out) :: pivot(*); integer(c_int) :: rc
