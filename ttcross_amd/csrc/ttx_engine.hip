@@ -96,6 +96,30 @@ static int rccl_load()
 }
 #define NCCLCHECK(x) do { ncclResult_t e_ = (x); if (e_ != ncclSuccess) return fail(TTX_EHIP, "%s failed: %s", #x, g_rccl.GetErrorString(e_)); } while (0)
 
+// Operations on the resident train (ttx_eval.h, ttx_contract.h, ttx_algebra.h, ttx_sample.h) share one table of device work space
+// per engine, grown on demand (buf_reserve), freed in ttx_destroy.  A slot belongs to one role; two roles share a slot only where no
+// single call uses both, because a second buf_reserve of a slot may move what the first one handed out.  ttx_sample is the widest
+// call: SC_TRAIN, SC_META, SC_W, SC_M, SC_VEC, SC_H, SC_ROW, SC_CNT and the staging slots are all live in it.
+enum {
+    SC_TRAIN,                           // the EvTrain block (ev_train): evaluation and sampling
+    SC_META,                            // a call's tables (OpMeta): contraction, marginals, sampling; the AlgBlk table of the algebra
+    SC_IND, SC_OUT, SC_X,               // staging of the host entries: index rows, values (also the marginals), coordinates or uniforms
+    SC_FLAG, SC_LQ,                     // ttx_value_batch's flags, ttx_sample's logq
+    SC_XA, SC_XB, SC_SORT,              // MFMA evaluation: the two state buffers, the bucket sort
+    SC_W, SC_M, SC_P, SC_SCR, SC_VEC,   // contraction: weights, M matrices, run products, their overflow, the l and s vectors
+    SC_H, SC_ROW, SC_CNT,               // sampling: head tables, global rows of long modes, the failure counter
+    SC_NBUF
+};
+struct EvBuf { void *p = nullptr; size_t bytes = 0; };
+// an event pair around a launch, created on first use
+struct OpTimer {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int start(hipStream_t s) { for (auto &e : ev) if (!e) HIPCHECK(hipEventCreate(&e)); HIPCHECK(hipEventRecord(ev[0], s)); return TTX_OK; }
+    int stop(hipStream_t s) { HIPCHECK(hipEventRecord(ev[1], s)); return TTX_OK; }
+    int ms(double *out) { float t = 0.f; HIPCHECK(hipEventElapsedTime(&t, ev[0], ev[1])); *out = t; return TTX_OK; }   // after a synchronise
+};
+enum { TM_MODESUM, TM_ALG, TM_HEAD, TM_DRAW, TM_N };    // k_ct_modesum, the algebra launch, k_sm_head, the k_sm_draw of a chunk
+
 struct DevFun;                          // a loaded device integrand (TTX_FUN_DEVICE), defined with slot_eval
 struct ttx_engine {
     ttx_config cfg;
@@ -189,28 +213,15 @@ struct ttx_engine {
     size_t HS = 0;
     int64_t host_calls = 0;
     int64_t n_resid = 0;                // rook half-steps of the last run that took a residual (all groups)
-    // batched evaluation (ttx_eval.h): work space of its own, grown on demand, freed in ttx_destroy
-    struct EvBuf { void *p = nullptr; size_t bytes = 0; };
-    enum { EV_META, EV_IND, EV_OUT, EV_FLAG, EV_XV, EV_XA, EV_XB, EV_SORT, EV_NBUF };
-    EvBuf ev[EV_NBUF];
-    std::vector<char> ev_meta_host;
+    // operations on the resident train: work space (SC_*), the host images behind SC_TRAIN and SC_META, timers (TM_*), last figures
+    EvBuf scratch[SC_NBUF];
+    std::vector<char> train_host, meta_host;
+    OpTimer timer[TM_N];
+    int ncu = 0;                        // compute units of the device, asked for once (dev_ncu)
     int ev_last_mode = -1;              // TTX_EVAL_* the last batch ran with
-    // partial contraction (ttx_contract.h): the M matrices, run products and vectors, grown on demand, freed in ttx_destroy
-    enum { CT_META, CT_W, CT_M, CT_P, CT_SCR, CT_VEC, CT_OUT, CT_NBUF };
-    EvBuf ct[CT_NBUF];
-    std::vector<char> ct_meta_host;
-    hipEvent_t ct_ev[2] = {nullptr, nullptr};   // around the mode-sum kernel of the last call (ttx_contract_modesum_ms)
-    double ct_ms = 0.0, ct_bytes = 0.0;
-    // sums and elementwise products of trains (ttx_algebra.h): the block table and the figures of the last call with this engine first
-    EvBuf alg_meta;
-    hipEvent_t alg_ev[2] = {nullptr, nullptr};
-    double alg_ms = 0.0, alg_rd = 0.0, alg_wr = 0.0;
-    // sampling (ttx_sample.h): the head tables, the chunk buffers of the host entry, the global rows of long modes and the failure
-    // counter, grown on demand, freed in ttx_destroy; the figures of the last call
-    enum { SM_H, SM_U, SM_IND, SM_LQ, SM_VAL, SM_ROW, SM_CNT, SM_NBUF };
-    EvBuf sm[SM_NBUF];
-    hipEvent_t sm_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around k_sm_head; around the k_sm_draw of a chunk
-    double sm_ms_head = 0.0, sm_bytes = 0.0, sm_ms_draw = 0.0;
+    double ct_ms = 0.0, ct_bytes = 0.0;                 // the mode-sum kernel of the last ttx_contract / ttx_marginals
+    double alg_ms = 0.0, alg_rd = 0.0, alg_wr = 0.0;    // the last ttx_lincomb / ttx_hadamard with this engine first
+    double sm_ms_head = 0.0, sm_bytes = 0.0, sm_ms_draw = 0.0;  // the last ttx_sample
     int64_t sm_failed = 0;
 };
 
@@ -846,13 +857,8 @@ extern "C" void ttx_destroy(ttx_engine *h)
     if (h->dfun) { (void)hipSetDevice(h->cfg.device); if (h->stream) (void)hipStreamSynchronize(h->stream); h->dfun.reset(); }   // the last owner unloads the module
     if (h->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(h->comm);
     for (void *p : h->allocs) (void)hipFree(p);
-    for (auto &b : h->ev) if (b.p) (void)hipFree(b.p);
-    for (auto &b : h->ct) if (b.p) (void)hipFree(b.p);
-    for (auto &e : h->ct_ev) if (e) (void)hipEventDestroy(e);
-    if (h->alg_meta.p) (void)hipFree(h->alg_meta.p);
-    for (auto &e : h->alg_ev) if (e) (void)hipEventDestroy(e);
-    for (auto &b : h->sm) if (b.p) (void)hipFree(b.p);
-    for (auto &e : h->sm_ev) if (e) (void)hipEventDestroy(e);
+    for (auto &b : h->scratch) if (b.p) (void)hipFree(b.p);
+    for (auto &t : h->timer) for (auto &e : t.ev) if (e) (void)hipEventDestroy(e);
     if (h->h_sum_base) (void)hipHostFree(h->h_sum_base);
     if (h->h_val) (void)hipHostFree(h->h_val);
     if (h->h_svd) (void)hipHostFree(h->h_svd);
@@ -2031,6 +2037,9 @@ static int allreduce_big(ttx_engine *h, double *buf, size_t count)
     }
     return TTX_OK;
 }
+static std::vector<int32_t> modes_of(const ttx_engine *h) { return std::vector<int32_t>(h->n1.begin() + 1, h->n1.begin() + 1 + h->d); }
+// destroy an engine that an operation made and then failed on: the operation's error text stays the last error
+static void destroy_keep_error(ttx_engine *e) { const std::string msg = g_err; ttx_destroy(e); g_err = msg; }
 // The finalised train of a MULTI-PROCESS job on every process, as a new single-process engine with the same integrand (`out`):
 // each process copies the cores it holds into its slots of the new engine's core array and a SUM all-reduce over the job's transport
 // fills in the others (their slots hold -0.0 here, the neutral element of fp addition for every value).  dtt_accchk, norm, dot_product, ort, svd and dtt_write of the
@@ -2044,7 +2053,7 @@ extern "C" int ttx_replicate(ttx_engine *h, ttx_engine **out)
     HIPCHECK(hipSetDevice(h->cfg.device));
     const int d = h->d;
     ttx_config c = h->cfg;
-    std::vector<int32_t> nn(h->n1.begin() + 1, h->n1.begin() + 1 + d);
+    const std::vector<int32_t> nn = modes_of(h);
     std::vector<double> qw;
     c.n = nn.data(); c.par = h->par.empty() ? nullptr : h->par.data(); c.aux = h->aux.empty() ? nullptr : h->aux.data(); c.naux = (int32_t)h->aux.size();
     c.quadw = nullptr;
@@ -2093,9 +2102,7 @@ static int with_replica(ttx_engine *h, FN fn)
     int rc = ttx_replicate(h, &e);
     if (rc) return rc;
     rc = fn(e);
-    const std::string msg = g_err;
-    ttx_destroy(e);
-    if (rc) g_err = msg;
+    if (rc) destroy_keep_error(e); else ttx_destroy(e);
     return rc;
 }
 
@@ -2140,40 +2147,52 @@ static int train_shell(ttx_engine **out, const char *who, int32_t d, const int32
     ttx_engine *h = nullptr;
     int rc = create_impl(&h, &c, true);
     if (rc) return rc;
+    auto to_dev = [&](void *dst, const void *src, size_t bytes) {
+        const hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
+        return e == hipSuccess ? TTX_OK : fail(TTX_EHIP, "%s: %s", who, hipGetErrorString(e));
+    };
     GroupState *g0 = (GroupState *)calloc(1, sizeof(GroupState));     // only the bond range is read by the quad kernels
     g0->first = 1; g0->last = d - 1; g0->gglobal = 0;
-    hipError_t e = hipMemcpy(h->P.gs, g0, offsetof(GroupState, S), hipMemcpyHostToDevice);
-    free(g0);
-    if (e != hipSuccess) { ttx_destroy(h); return fail(TTX_EHIP, "%s: %s", who, hipGetErrorString(e)); }
-    h->rfinal.assign(r, r + d + 1);
     std::vector<int32_t> rr((size_t)(d + 2), 1);
     for (int p = 0; p <= d; p++) rr[p] = r[p];
-    e = hipMemcpy(h->P.r, rr.data(), sizeof(int32_t) * rr.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { ttx_destroy(h); return fail(TTX_EHIP, "%s: %s", who, hipGetErrorString(e)); }
+    if (!(rc = to_dev(h->P.gs, g0, offsetof(GroupState, S)))) rc = to_dev(h->P.r, rr.data(), sizeof(int32_t) * rr.size());
+    free(g0);
+    if (rc) { destroy_keep_error(h); return rc; }
+    h->rfinal.assign(r, r + d + 1);
     h->ran = true;
     *out = h;
+    return TTX_OK;
+}
+// a new train out of an operation: the shell, then fill(e) writes its cores; a fill that fails takes the shell with it and its error
+// text stays, a fill that succeeds hands the engine to *out
+template <class FN>
+static int new_train(ttx_engine **out, const char *who, int32_t d, const int32_t *n, const int32_t *r, int32_t device, FN fill)
+{
+    *out = nullptr;
+    ttx_engine *e = nullptr;
+    int rc = train_shell(&e, who, d, n, r, device);
+    if (rc) return rc;
+    if ((rc = fill(e))) { destroy_keep_error(e); return rc; }
+    *out = e;
     return TTX_OK;
 }
 
 extern "C" int ttx_from_tt(ttx_engine **out, int32_t d, const int32_t *n, const int32_t *r, const double *cores, int32_t device)
 {
     if (!out || !n || !r || !cores) return fail(TTX_EINVAL, "ttx_from_tt: null argument");
-    ttx_engine *h = nullptr;
-    int rc = train_shell(&h, "ttx_from_tt", d, n, r, device);
-    *out = nullptr;
-    if (rc) return rc;
-    size_t off = 0;
-    for (int k = 1; k <= d; k++) {
-        const int r0 = r[k - 1], r1 = r[k], nk = n[k - 1];
-        double *dst = h->P.arg + (size_t)(k - 1) * h->P.CS;
-        for (int s = 0; s < r1; s++) {        // compact host -> padded device slabs (inverse of ttx_get_core)
-            hipError_t e = hipMemcpy2D(dst + h->P.SS * s, sizeof(double) * h->RM, cores + off + (size_t)r0 * nk * s, sizeof(double) * r0, sizeof(double) * r0, nk, hipMemcpyHostToDevice);
-            if (e != hipSuccess) { ttx_destroy(h); return fail(TTX_EHIP, "ttx_from_tt: %s", hipGetErrorString(e)); }
+    return new_train(out, "ttx_from_tt", d, n, r, device, [&](ttx_engine *h) {
+        size_t off = 0;
+        for (int k = 1; k <= d; k++) {
+            const int r0 = r[k - 1], r1 = r[k], nk = n[k - 1];
+            double *dst = h->P.arg + (size_t)(k - 1) * h->P.CS;
+            for (int s = 0; s < r1; s++) {        // compact host -> padded device slabs (inverse of ttx_get_core)
+                hipError_t e = hipMemcpy2D(dst + h->P.SS * s, sizeof(double) * h->RM, cores + off + (size_t)r0 * nk * s, sizeof(double) * r0, sizeof(double) * r0, nk, hipMemcpyHostToDevice);
+                if (e != hipSuccess) return fail(TTX_EHIP, "ttx_from_tt: %s", hipGetErrorString(e));
+            }
+            off += (size_t)r0 * nk * r1;
         }
-        off += (size_t)r0 * nk * r1;
-    }
-    *out = h;
-    return TTX_OK;
+        return (int)TTX_OK;
+    });
 }
 
 // lib/ttio.f90:10-17 `tthead`: 'TT      ', ver(2)=(1,0), inf(4)=(tt_size,0,0,0), comment*64, i(8) with i(1:2)=(l,m); 128 bytes
@@ -2973,22 +2992,60 @@ extern "C" int ttx_ijk(ttx_engine *h, const int32_t *ind, double *val)
     return TTX_OK;
 }
 
-// ---- the train at a batch of multi-indices (ttx_eval.h) -------------------------------------------------------------------------
-static int buf_reserve(ttx_engine *h, ttx_engine::EvBuf &b, size_t bytes)
+// ---- plumbing of the operations on the resident train: work space, tables, preflight --------------------------------------------
+static int buf_reserve(ttx_engine *h, int slot, size_t bytes)
 {
+    EvBuf &b = h->scratch[slot];
     if (b.p && b.bytes >= bytes) return TTX_OK;
     if (b.p) { HIPCHECK(hipStreamSynchronize(h->stream)); (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; }
     HIPCHECK(hipMalloc(&b.p, bytes + 64));
     b.bytes = bytes;
     return TTX_OK;
 }
-static int ev_reserve(ttx_engine *h, int which, size_t bytes) { return buf_reserve(h, h->ev[which], bytes); }
-// points per chunk: bounds the work space (two state buffers of chunk x max rank doubles on the MFMA path, the index block of the host entry)
-static size_t ev_chunk(const ttx_engine *h)
-{
-    if (const char *e = getenv("TTX_IJK_CHUNK")) { const long long v = atoll(e); if (v >= 1) return (size_t)std::min<long long>(v, 1ll << 24); }
-    return h->RM <= 64 ? (size_t)1 << 18 : (size_t)1 << 17;
+template <class T> static T *buf(ttx_engine *h, int slot) { return (T *)h->scratch[slot].p; }
+namespace {
+// device image of a call's tables: arrays appended at 16-byte boundaries in a host vector of the engine, uploaded in one copy
+struct OpMeta {
+    std::vector<char> &host;
+    explicit OpMeta(std::vector<char> &b) : host(b) { host.clear(); }
+    template <class T> size_t put(const std::vector<T> &v)
+    {
+        const size_t off = (host.size() + 15) & ~(size_t)15;
+        host.resize(off + sizeof(T) * std::max<size_t>(v.size(), 1));
+        if (!v.empty()) memcpy(host.data() + off, v.data(), sizeof(T) * v.size());
+        return off;
+    }
+    // the image into the slot, on the engine's stream; *base: where it starts on the device
+    int upload(ttx_engine *h, int slot, char **base)
+    {
+        if (int rc = buf_reserve(h, slot, host.size())) return rc;
+        *base = buf<char>(h, slot);
+        HIPCHECK(hipMemcpyAsync(*base, host.data(), host.size(), hipMemcpyHostToDevice, h->stream));
+        return TTX_OK;
+    }
+};
 }
+// points per chunk of a batched call, from the environment (read on every call) or the call's default
+static size_t env_chunk(const char *name, size_t dflt)
+{
+    if (const char *e = getenv(name)) { const long long v = atoll(e); if (v >= 1) return (size_t)std::min<long long>(v, 1ll << 24); }
+    return dflt;
+}
+static int dev_ncu(ttx_engine *h)
+{
+    if (!h->ncu) { h->ncu = 256; (void)hipDeviceGetAttribute(&h->ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device); }
+    return h->ncu;
+}
+// the engines ttx_ijk takes: a train, one process (a multi-process engine gets tt_prepare's answer); makes its device current
+static int check_train_one_process(ttx_engine *h, const char *who)
+{
+    if (!h || !h->ran) return fail(TTX_ESTATE, "%s: no tensor train (run dtt_dmrgg first)", who);
+    if (h->W > 1) return tt_prepare(h, who);
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    return TTX_OK;
+}
+
+// ---- the train at a batch of multi-indices (ttx_eval.h) -------------------------------------------------------------------------
 // TTX_EVAL_AUTO, a cost model fitted to the measurement in DESIGN.md 4.5, with w = sum r(k-1) r(k) (slice elements a point touches).
 // The MFMA path pays a fixed cost whatever the batch (four launches per mode and the staging of the slices): 1.46 / 1.47 / 9.2 ms at
 // (d, w) = (63, 6.8 k) / (63, 62 k) / (255, 1.04 M), modelled as 23 us d + 3.2 ns w.  Per point it saves 27.7 / 106 / 1317 ns against
@@ -3004,17 +3061,17 @@ static int ev_auto(const ttx_engine *h, int64_t npts)
 static int ev_train(ttx_engine *h, EvTrain *T)
 {
     const int d = h->d;
-    h->ev_meta_host.resize(sizeof(double *) * d + sizeof(int) * (2 * d + 1));
-    const double **cp = (const double **)h->ev_meta_host.data();
-    int *r = (int *)(cp + d), *n = r + d + 1, rmax = 1;
-    for (int k = 1; k <= d; k++) { cp[k - 1] = core_dev(h, k); n[k - 1] = h->n1[k]; }
-    for (int k = 0; k <= d; k++) { r[k] = h->rfinal[k]; rmax = std::max(rmax, r[k]); }
+    std::vector<const double *> cp(d);
+    std::vector<int> r(h->rfinal.begin(), h->rfinal.begin() + d + 1), n(h->n1.begin() + 1, h->n1.begin() + 1 + d);
+    for (int k = 1; k <= d; k++) cp[k - 1] = core_dev(h, k);
+    const int rmax = std::max(1, *std::max_element(r.begin(), r.end()));
     if (rmax > 128) return fail(TTX_EINVAL, "ttx_ijk_batch: ranks up to 128 only (got %d)", rmax);
-    if (int rc = ev_reserve(h, ttx_engine::EV_META, h->ev_meta_host.size())) return rc;
-    char *m = (char *)h->ev[ttx_engine::EV_META].p;
-    HIPCHECK(hipMemcpyAsync(m, h->ev_meta_host.data(), h->ev_meta_host.size(), hipMemcpyHostToDevice, h->stream));
+    OpMeta meta(h->train_host);
+    const size_t o_core = meta.put(cp), o_r = meta.put(r), o_n = meta.put(n);
+    char *m;
+    if (int rc = meta.upload(h, SC_TRAIN, &m)) return rc;
     T->d = d; T->RM = h->RM; T->ldx = (rmax + 3) & ~3; T->SS = h->P.SS;
-    T->core = (const double *const *)m; T->r = (const int *)(m + sizeof(double *) * d); T->n = T->r + d + 1;
+    T->core = (const double *const *)(m + o_core); T->r = (const int *)(m + o_r); T->n = (const int *)(m + o_n);
     return TTX_OK;
 }
 template <int MR>
@@ -3028,9 +3085,7 @@ static int ev_gemm_launch(ttx_engine *h, const EvTrain &T, int i, int nmode, int
 // c points whose index rows (and, for ttx_value_batch, flags) are on the device -> out (device), enqueued on the engine's stream
 static int ev_run(ttx_engine *h, const EvTrain &T, int mode, int c, const int *ind, const int *flag, double *out)
 {
-    const int d = h->d;
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
+    const int d = h->d, ncu = dev_ncu(h);
     if (mode == TTX_EVAL_EXACT) {
         // one wave per point, 4 waves per workgroup; the grid is capped at 8 workgroups per CU and strides over the batch (66 VGPRs:
         // 7 waves per SIMD are resident); the chain is a dependent sequence, throughput comes from the waves in flight
@@ -3041,10 +3096,10 @@ static int ev_run(ttx_engine *h, const EvTrain &T, int mode, int c, const int *i
     }
     const size_t NM = h->NM;
     int rc;
-    if ((rc = ev_reserve(h, ttx_engine::EV_XA, sizeof(double) * (size_t)c * T.ldx)) || (rc = ev_reserve(h, ttx_engine::EV_XB, sizeof(double) * (size_t)c * T.ldx)) ||
-        (rc = ev_reserve(h, ttx_engine::EV_SORT, sizeof(int) * (2 * (size_t)c + 4 * NM + 8)))) return rc;
-    double *X = (double *)h->ev[ttx_engine::EV_XA].p, *Z = (double *)h->ev[ttx_engine::EV_XB].p;
-    int *valid = (int *)h->ev[ttx_engine::EV_SORT].p, *perm = valid + c, *cnt = perm + c, *off = cnt + NM, *tile = off + NM + 1, *cur = tile + NM + 1;
+    if ((rc = buf_reserve(h, SC_XA, sizeof(double) * (size_t)c * T.ldx)) || (rc = buf_reserve(h, SC_XB, sizeof(double) * (size_t)c * T.ldx)) ||
+        (rc = buf_reserve(h, SC_SORT, sizeof(int) * (2 * (size_t)c + 4 * NM + 8)))) return rc;
+    double *X = buf<double>(h, SC_XA), *Z = buf<double>(h, SC_XB);
+    int *valid = buf<int>(h, SC_SORT), *perm = valid + c, *cnt = perm + c, *off = cnt + NM, *tile = off + NM + 1, *cur = tile + NM + 1;
     hipLaunchKernelGGL(k_ev_init, dim3(std::min((c + 3) / 4, ncu * 8)), dim3(256), 0, h->stream, T, c, ind, flag, valid, X, out);
     const int nb = std::max(1, std::min((c + 1023) / 1024, 1024));
     for (int i = d - 2; i >= 0; i--) {
@@ -3073,80 +3128,63 @@ static int ev_mode(ttx_engine *h, const char *who, int64_t npts, int32_t mode, i
 }
 extern "C" int ttx_eval_last_mode(const ttx_engine *h) { return h ? h->ev_last_mode : -1; }
 
+// the three entries differ in where a chunk's index rows come from and where its values go
+enum EvStage { EV_ON_DEVICE, EV_HOST_INDEX, EV_HOST_COORD };   // caller's device pointers; host rows staged; host coordinates -> k_ev_digits
+// `in`: npts x d index rows (int32) or, EV_HOST_COORD, npts x dd coordinates (double); lib/tt.f90:702-728 forms the digits, then dtt_ijk
+static int ev_batch(ttx_engine *h, const char *who, EvStage st, int64_t npts, int32_t dd, const void *in, double *out, int32_t mode)
+{
+    int rc = tt_prepare(h, st == EV_HOST_COORD ? "dtt_value" : "dtt_ijk"), eff = 0;
+    if (rc) return rc;
+    if (npts < 0 || (npts > 0 && (!in || !out))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
+    if (st == EV_HOST_COORD && dd < 1) return fail(TTX_EINVAL, "%s: %d coordinates per point", who, dd);
+    if ((rc = ev_mode(h, who, npts, mode, &eff))) return rc;
+    // an asymmetry of the entries, kept: an empty ttx_value_batch leaves ev_last_mode as it was, the two index entries record theirs
+    if (npts == 0) { if (st != EV_HOST_COORD) h->ev_last_mode = eff; return TTX_OK; }
+    const int32_t *ind = (const int32_t *)in;
+    const double *x = (const double *)in;
+    // int(xx) of the reference is defined below 2^31 only
+    if (st == EV_HOST_COORD)
+        for (size_t e = 0; e < (size_t)npts * dd; e++) if (!(x[e] < 2147483648.0)) return fail(TTX_EINVAL, "%s: coordinate %g of point %lld is not below 2^31", who, x[e], (long long)(e / dd));
+    EvTrain T;
+    if ((rc = ev_train(h, &T))) return rc;
+    const size_t chunk = std::min<size_t>(env_chunk("TTX_IJK_CHUNK", h->RM <= 64 ? (size_t)1 << 18 : (size_t)1 << 17), (size_t)npts), d = h->d;
+    // the chunk bounds the work space: two state buffers of chunk x max rank doubles on the MFMA path, the staging blocks of the host entries
+    if (st != EV_ON_DEVICE && ((rc = buf_reserve(h, SC_IND, sizeof(int) * chunk * d)) || (rc = buf_reserve(h, SC_OUT, sizeof(double) * chunk)))) return rc;
+    if (st == EV_HOST_COORD && ((rc = buf_reserve(h, SC_FLAG, sizeof(int) * chunk)) || (rc = buf_reserve(h, SC_X, sizeof(double) * chunk * dd)))) return rc;
+    int *sind = buf<int>(h, SC_IND), *sflag = st == EV_HOST_COORD ? buf<int>(h, SC_FLAG) : nullptr;
+    double *sout = buf<double>(h, SC_OUT), *sx = buf<double>(h, SC_X);
+    for (int64_t o = 0; o < npts; o += (int64_t)chunk) {
+        const int c = (int)std::min<int64_t>((int64_t)chunk, npts - o);
+        if (st == EV_ON_DEVICE) {
+            if ((rc = ev_run(h, T, eff, c, ind + (size_t)o * d, nullptr, out + o))) return rc;
+            continue;                                                           // one wait after the last chunk
+        }
+        if (st == EV_HOST_INDEX) HIPCHECK(hipMemcpyAsync(sind, ind + (size_t)o * d, sizeof(int) * (size_t)c * d, hipMemcpyHostToDevice, h->stream));
+        else {
+            HIPCHECK(hipMemcpyAsync(sx, x + (size_t)o * dd, sizeof(double) * (size_t)c * dd, hipMemcpyHostToDevice, h->stream));
+            hipLaunchKernelGGL(k_ev_digits, g1((size_t)c), dim3(256), 0, h->stream, (int)d, T.n, (int)dd, (long long)c, (const double *)sx, sind, sflag);
+        }
+        if ((rc = ev_run(h, T, eff, c, sind, sflag, sout))) return rc;
+        HIPCHECK(hipMemcpyAsync(out + o, sout, sizeof(double) * c, hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(hipStreamSynchronize(h->stream));                              // the staging blocks are reused by the next chunk
+    }
+    if (st == EV_ON_DEVICE) HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipGetLastError());
+    h->ev_last_mode = eff;
+    return TTX_OK;
+}
 extern "C" int ttx_ijk_batch_dev(ttx_engine *h, int64_t npts, const int32_t *ind_dev, double *out_dev, int32_t mode)
 {
-    int rc = tt_prepare(h, "dtt_ijk"), eff = 0;
-    if (rc) return rc;
-    if (npts < 0 || (npts > 0 && (!ind_dev || !out_dev))) return fail(TTX_EINVAL, "ttx_ijk_batch_dev: null argument or negative npts");
-    if ((rc = ev_mode(h, "ttx_ijk_batch_dev", npts, mode, &eff))) return rc;
-    if (npts == 0) { h->ev_last_mode = eff; return TTX_OK; }
-    EvTrain T;
-    if ((rc = ev_train(h, &T))) return rc;
-    const size_t chunk = ev_chunk(h), d = h->d;
-    for (int64_t o = 0; o < npts; o += (int64_t)chunk) {
-        const int c = (int)std::min<int64_t>((int64_t)chunk, npts - o);
-        if ((rc = ev_run(h, T, eff, c, ind_dev + (size_t)o * d, nullptr, out_dev + o))) return rc;
-    }
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    HIPCHECK(hipGetLastError());
-    h->ev_last_mode = eff;
-    return TTX_OK;
+    return ev_batch(h, "ttx_ijk_batch_dev", EV_ON_DEVICE, npts, 0, ind_dev, out_dev, mode);
 }
-
 extern "C" int ttx_ijk_batch(ttx_engine *h, int64_t npts, const int32_t *ind, double *out, int32_t mode)
 {
-    int rc = tt_prepare(h, "dtt_ijk"), eff = 0;
-    if (rc) return rc;
-    if (npts < 0 || (npts > 0 && (!ind || !out))) return fail(TTX_EINVAL, "ttx_ijk_batch: null argument or negative npts");
-    if ((rc = ev_mode(h, "ttx_ijk_batch", npts, mode, &eff))) return rc;
-    if (npts == 0) { h->ev_last_mode = eff; return TTX_OK; }
-    EvTrain T;
-    if ((rc = ev_train(h, &T))) return rc;
-    const size_t chunk = std::min<size_t>(ev_chunk(h), (size_t)npts), d = h->d;
-    if ((rc = ev_reserve(h, ttx_engine::EV_IND, sizeof(int) * chunk * d)) || (rc = ev_reserve(h, ttx_engine::EV_OUT, sizeof(double) * chunk))) return rc;
-    int *dind = (int *)h->ev[ttx_engine::EV_IND].p;
-    double *dout = (double *)h->ev[ttx_engine::EV_OUT].p;
-    for (int64_t o = 0; o < npts; o += (int64_t)chunk) {
-        const int c = (int)std::min<int64_t>((int64_t)chunk, npts - o);
-        HIPCHECK(hipMemcpyAsync(dind, ind + (size_t)o * d, sizeof(int) * (size_t)c * d, hipMemcpyHostToDevice, h->stream));
-        if ((rc = ev_run(h, T, eff, c, dind, nullptr, dout))) return rc;
-        HIPCHECK(hipMemcpyAsync(out + o, dout, sizeof(double) * c, hipMemcpyDeviceToHost, h->stream));
-        HIPCHECK(hipStreamSynchronize(h->stream));
-    }
-    HIPCHECK(hipGetLastError());
-    h->ev_last_mode = eff;
-    return TTX_OK;
+    return ev_batch(h, "ttx_ijk_batch", EV_HOST_INDEX, npts, 0, ind, out, mode);
 }
-
-// dtt_value (lib/tt.f90:702-728) for npts coordinate vectors: the digits are formed on the device (k_ev_digits), then dtt_ijk
+// dtt_value for npts coordinate vectors of dd entries each
 extern "C" int ttx_value_batch(ttx_engine *h, int64_t npts, int32_t dd, const double *x, double *out, int32_t mode)
 {
-    int rc = tt_prepare(h, "dtt_value"), eff = 0;
-    if (rc) return rc;
-    if (npts < 0 || (npts > 0 && (!x || !out))) return fail(TTX_EINVAL, "ttx_value_batch: null argument or negative npts");
-    if (dd < 1) return fail(TTX_EINVAL, "ttx_value_batch: %d coordinates per point", dd);
-    if ((rc = ev_mode(h, "ttx_value_batch", npts, mode, &eff))) return rc;
-    if (npts == 0) return TTX_OK;
-    // int(xx) of the reference is defined below 2^31 only
-    for (size_t e = 0; e < (size_t)npts * dd; e++) if (!(x[e] < 2147483648.0)) return fail(TTX_EINVAL, "ttx_value_batch: coordinate %g of point %lld is not below 2^31", x[e], (long long)(e / dd));
-    EvTrain T;
-    if ((rc = ev_train(h, &T))) return rc;
-    const size_t chunk = std::min<size_t>(ev_chunk(h), (size_t)npts), d = h->d;
-    if ((rc = ev_reserve(h, ttx_engine::EV_IND, sizeof(int) * chunk * d)) || (rc = ev_reserve(h, ttx_engine::EV_OUT, sizeof(double) * chunk)) ||
-        (rc = ev_reserve(h, ttx_engine::EV_FLAG, sizeof(int) * chunk)) || (rc = ev_reserve(h, ttx_engine::EV_XV, sizeof(double) * chunk * dd))) return rc;
-    int *dind = (int *)h->ev[ttx_engine::EV_IND].p, *dflag = (int *)h->ev[ttx_engine::EV_FLAG].p;
-    double *dout = (double *)h->ev[ttx_engine::EV_OUT].p, *dx = (double *)h->ev[ttx_engine::EV_XV].p;
-    for (int64_t o = 0; o < npts; o += (int64_t)chunk) {
-        const int c = (int)std::min<int64_t>((int64_t)chunk, npts - o);
-        HIPCHECK(hipMemcpyAsync(dx, x + (size_t)o * dd, sizeof(double) * (size_t)c * dd, hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(k_ev_digits, g1((size_t)c), dim3(256), 0, h->stream, (int)d, T.n, (int)dd, (long long)c, (const double *)dx, dind, dflag);
-        if ((rc = ev_run(h, T, eff, c, dind, dflag, dout))) return rc;
-        HIPCHECK(hipMemcpyAsync(out + o, dout, sizeof(double) * c, hipMemcpyDeviceToHost, h->stream));
-        HIPCHECK(hipStreamSynchronize(h->stream));
-    }
-    HIPCHECK(hipGetLastError());
-    h->ev_last_mode = eff;
-    return TTX_OK;
+    return ev_batch(h, "ttx_value_batch", EV_HOST_COORD, npts, dd, x, out, mode);
 }
 
 extern "C" int ttx_arith(const ttx_engine *h) { return h ? h->P.arith : -1; }
@@ -3167,18 +3205,6 @@ struct CtPlan {
     size_t msize = 0, wsize = 0;
     double bytes = 0.0;                 // 8 sum r0 n r1 over the contracted cores
 };
-// device image of the call's tables: arrays appended at 16-byte boundaries, uploaded in one copy
-struct CtMeta {
-    std::vector<char> &buf;
-    explicit CtMeta(std::vector<char> &b) : buf(b) { buf.clear(); }
-    template <class T> size_t put(const std::vector<T> &v)
-    {
-        const size_t off = (buf.size() + 15) & ~(size_t)15;
-        buf.resize(off + sizeof(T) * std::max<size_t>(v.size(), 1));
-        if (!v.empty()) memcpy(buf.data() + off, v.data(), sizeof(T) * v.size());
-        return off;
-    }
-};
 }
 static void ct_plan(ttx_engine *h, const std::vector<char> &contracted, CtPlan &pl)
 {
@@ -3198,38 +3224,28 @@ static void ct_plan(ttx_engine *h, const std::vector<char> &contracted, CtPlan &
         for (int b0 = 0; b0 < c.r1; b0 += tb) for (int a0 = 0; a0 < c.r0; a0 += c.ta) pl.tiles.push_back(CtTile{k, a0, b0, 0});
     }
 }
-// weights to the device (NULL: ones) and the mode-sum launch, bracketed by the engine's two events
-static int ct_modesum(ttx_engine *h, const CtPlan &pl, const double *w, const CtCore *dcores, const CtTile *dtiles)
+// weights to the device (NULL: ones) and the mode-sum launch, between the timer's events where the caller reports its time
+static int ct_modesum(ttx_engine *h, const CtPlan &pl, const double *w, const CtCore *dcores, const CtTile *dtiles, OpTimer *tm)
 {
     int rc;
-    if ((rc = buf_reserve(h, h->ct[ttx_engine::CT_W], sizeof(double) * pl.wsize)) || (rc = buf_reserve(h, h->ct[ttx_engine::CT_M], sizeof(double) * std::max<size_t>(pl.msize, 1)))) return rc;
+    if ((rc = buf_reserve(h, SC_W, sizeof(double) * pl.wsize)) || (rc = buf_reserve(h, SC_M, sizeof(double) * std::max<size_t>(pl.msize, 1)))) return rc;
     std::vector<double> ones;
     if (!w) { ones.assign(pl.wsize, 1.0); w = ones.data(); }
-    HIPCHECK(hipMemcpyAsync(h->ct[ttx_engine::CT_W].p, w, sizeof(double) * pl.wsize, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(buf<double>(h, SC_W), w, sizeof(double) * pl.wsize, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));                                  // `ones` leaves scope
-    for (auto &e : h->ct_ev) if (!e) HIPCHECK(hipEventCreate(&e));
-    h->ct_ms = 0.0; h->ct_bytes = pl.bytes;
     if (pl.tiles.empty()) return TTX_OK;
-    HIPCHECK(hipEventRecord(h->ct_ev[0], h->stream));
+    if (tm && (rc = tm->start(h->stream))) return rc;
     hipLaunchKernelGGL(k_ct_modesum, dim3((unsigned)pl.tiles.size()), dim3(256), 0, h->stream, dcores, dtiles, h->RM, h->P.SS,
-                       (const double *)h->ct[ttx_engine::CT_W].p, (double *)h->ct[ttx_engine::CT_M].p);
-    HIPCHECK(hipEventRecord(h->ct_ev[1], h->stream));
-    return TTX_OK;
+                       (const double *)buf<double>(h, SC_W), buf<double>(h, SC_M));
+    return tm ? tm->stop(h->stream) : TTX_OK;
 }
-static int ct_finish(ttx_engine *h, bool timed)
+// the end of ttx_contract and ttx_marginals: the wait, then the figures of ttx_contract_modesum
+static int ct_finish(ttx_engine *h, const CtPlan &pl)
 {
     HIPCHECK(hipStreamSynchronize(h->stream));
     HIPCHECK(hipGetLastError());
-    if (timed) { float ms = 0.f; HIPCHECK(hipEventElapsedTime(&ms, h->ct_ev[0], h->ct_ev[1])); h->ct_ms = ms; }
-    return TTX_OK;
-}
-// the engines ttx_ijk takes: a train, one process (a multi-process engine gets tt_prepare's answer)
-static int ct_check(ttx_engine *h, const char *who)
-{
-    if (!h || !h->ran) return fail(TTX_ESTATE, "%s: no tensor train (run dtt_dmrgg first)", who);
-    if (h->W > 1) return tt_prepare(h, who);
-    HIPCHECK(hipSetDevice(h->cfg.device));
-    return TTX_OK;
+    h->ct_ms = 0.0; h->ct_bytes = pl.bytes;
+    return pl.tiles.empty() ? TTX_OK : h->timer[TM_MODESUM].ms(&h->ct_ms);
 }
 // everything of ttx_contract that works on the new engine e: a failure leaves e to the caller to destroy
 static int ct_fill(ttx_engine *h, ttx_engine *e, const std::vector<int> &kept, const double *w)
@@ -3258,9 +3274,9 @@ static int ct_fill(ttx_engine *h, ttx_engine *e, const std::vector<int> &kept, c
         runs.push_back(R);
     }
     int rc;
-    if ((rc = buf_reserve(h, h->ct[ttx_engine::CT_P], sizeof(double) * std::max<size_t>(psize, 1))) ||
-        (rc = buf_reserve(h, h->ct[ttx_engine::CT_SCR], sizeof(double) * std::max<size_t>(ssize, 1)))) return rc;
-    const double *Pb = (const double *)h->ct[ttx_engine::CT_P].p;
+    if ((rc = buf_reserve(h, SC_P, sizeof(double) * std::max<size_t>(psize, 1))) ||
+        (rc = buf_reserve(h, SC_SCR, sizeof(double) * std::max<size_t>(ssize, 1)))) return rc;
+    const double *Pb = buf<double>(h, SC_P);
     std::vector<CtKeep> keeps(m);
     long long items = 0;
     for (int j = 0; j < m; j++) {
@@ -3275,23 +3291,22 @@ static int ct_fill(ttx_engine *h, ttx_engine *e, const std::vector<int> &kept, c
         items += (long long)K.ncol * (K.t ? 1 : K.r1);
     }
     if (items > 0x7fffffffll) return fail(TTX_EINVAL, "ttx_contract: too many column tiles (%lld)", items);
-    CtMeta meta(h->ct_meta_host);
+    OpMeta meta(h->meta_host);
     const size_t o_cores = meta.put(pl.cores), o_tiles = meta.put(pl.tiles), o_runs = meta.put(runs), o_r = meta.put(r), o_moff = meta.put(pl.moff), o_keeps = meta.put(keeps);
-    if ((rc = buf_reserve(h, h->ct[ttx_engine::CT_META], h->ct_meta_host.size()))) return rc;
-    char *dm = (char *)h->ct[ttx_engine::CT_META].p;
-    HIPCHECK(hipMemcpyAsync(dm, h->ct_meta_host.data(), h->ct_meta_host.size(), hipMemcpyHostToDevice, h->stream));
-    if ((rc = ct_modesum(h, pl, w, (const CtCore *)(dm + o_cores), (const CtTile *)(dm + o_tiles)))) return rc;
+    char *dm;
+    if ((rc = meta.upload(h, SC_META, &dm)) ||
+        (rc = ct_modesum(h, pl, w, (const CtCore *)(dm + o_cores), (const CtTile *)(dm + o_tiles), &h->timer[TM_MODESUM]))) return rc;
     if (!runs.empty())
         hipLaunchKernelGGL(k_ct_runs, dim3((unsigned)runs.size()), dim3(1024), 0, h->stream, (const CtRun *)(dm + o_runs), (const int *)(dm + o_r), (const size_t *)(dm + o_moff),
-                           (const double *)h->ct[ttx_engine::CT_M].p, (double *)h->ct[ttx_engine::CT_P].p, (double *)h->ct[ttx_engine::CT_SCR].p);
+                           (const double *)buf<double>(h, SC_M), buf<double>(h, SC_P), buf<double>(h, SC_SCR));
     hipLaunchKernelGGL(k_ct_absorb, dim3((unsigned)items), dim3(64), 0, h->stream, (const CtKeep *)(dm + o_keeps), m, h->RM, h->P.SS, e->RM, e->P.SS);
-    return ct_finish(h, !pl.tiles.empty());
+    return ct_finish(h, pl);
 }
 extern "C" int ttx_contract(ttx_engine *h, const int32_t *keep, const double *w, ttx_engine **out)
 {
     if (out) *out = nullptr;
     if (!keep || !out) return fail(TTX_EINVAL, "ttx_contract: null argument");
-    int rc = ct_check(h, "ttx_contract");
+    int rc = check_train_one_process(h, "ttx_contract");
     if (rc) return rc;
     const int d = h->d;
     std::vector<int> kept;
@@ -3305,34 +3320,29 @@ extern "C" int ttx_contract(ttx_engine *h, const int32_t *keep, const double *w,
     std::vector<int32_t> nn(m), rr(m + 1, 1);
     for (int j = 0; j < m; j++) { nn[j] = h->n1[kept[j] + 1]; if (j < m - 1) rr[j + 1] = h->rfinal[kept[j] + 1]; }
     rr[0] = kept[0] == 0 ? h->rfinal[0] : 1; rr[m] = kept[m - 1] == d - 1 ? h->rfinal[d] : 1;
-    ttx_engine *e = nullptr;
-    if ((rc = train_shell(&e, "ttx_contract", m, nn.data(), rr.data(), h->cfg.device))) return rc;
-    if ((rc = ct_fill(h, e, kept, w))) { const std::string msg = g_err; ttx_destroy(e); g_err = msg; return rc; }
-    *out = e;
-    return TTX_OK;
+    return new_train(out, "ttx_contract", m, nn.data(), rr.data(), h->cfg.device, [&](ttx_engine *e) { return ct_fill(h, e, kept, w); });
 }
 extern "C" int ttx_marginals(ttx_engine *h, const double *w, double *out)
 {
     if (!out) return fail(TTX_EINVAL, "ttx_marginals: null argument");
-    int rc = ct_check(h, "ttx_marginals");
+    int rc = check_train_one_process(h, "ttx_marginals");
     if (rc) return rc;
     const int d = h->d;
     CtPlan pl;
     ct_plan(h, std::vector<char>(d, 1), pl);
     const int ldv = h->RM;
-    CtMeta meta(h->ct_meta_host);
+    OpMeta meta(h->meta_host);
     const size_t o_cores = meta.put(pl.cores), o_tiles = meta.put(pl.tiles), o_r = meta.put(pl.r), o_moff = meta.put(pl.moff);
-    if ((rc = buf_reserve(h, h->ct[ttx_engine::CT_META], h->ct_meta_host.size())) || (rc = buf_reserve(h, h->ct[ttx_engine::CT_VEC], sizeof(double) * (2 * (size_t)d + 4) * ldv)) ||
-        (rc = buf_reserve(h, h->ct[ttx_engine::CT_OUT], sizeof(double) * pl.wsize))) return rc;
-    char *dm = (char *)h->ct[ttx_engine::CT_META].p;
-    HIPCHECK(hipMemcpyAsync(dm, h->ct_meta_host.data(), h->ct_meta_host.size(), hipMemcpyHostToDevice, h->stream));
-    if ((rc = ct_modesum(h, pl, w, (const CtCore *)(dm + o_cores), (const CtTile *)(dm + o_tiles)))) return rc;
-    double *L = (double *)h->ct[ttx_engine::CT_VEC].p, *S = L + (size_t)d * ldv, *dout = (double *)h->ct[ttx_engine::CT_OUT].p;   // L: vectors 0 .. d-1, S: 2 .. d+1 at S + k ldv
-    hipLaunchKernelGGL(k_ct_chains, dim3(2), dim3(1024), 0, h->stream, d, (const int *)(dm + o_r), (const size_t *)(dm + o_moff), (const double *)h->ct[ttx_engine::CT_M].p, L, S, ldv);
+    char *dm;
+    if ((rc = meta.upload(h, SC_META, &dm)) || (rc = buf_reserve(h, SC_VEC, sizeof(double) * (2 * (size_t)d + 4) * ldv)) ||
+        (rc = buf_reserve(h, SC_OUT, sizeof(double) * pl.wsize)) ||
+        (rc = ct_modesum(h, pl, w, (const CtCore *)(dm + o_cores), (const CtTile *)(dm + o_tiles), &h->timer[TM_MODESUM]))) return rc;
+    double *L = buf<double>(h, SC_VEC), *S = L + (size_t)d * ldv, *dout = buf<double>(h, SC_OUT);   // L: vectors 0 .. d-1, S: 2 .. d+1 at S + k ldv
+    hipLaunchKernelGGL(k_ct_chains, dim3(2), dim3(1024), 0, h->stream, d, (const int *)(dm + o_r), (const size_t *)(dm + o_moff), (const double *)buf<double>(h, SC_M), L, S, ldv);
     hipLaunchKernelGGL(k_ct_marg, dim3((unsigned)((pl.wsize + 3) / 4)), dim3(256), 0, h->stream, d, (const CtCore *)(dm + o_cores), (long long)pl.wsize, h->RM, h->P.SS,
                        (const double *)L, (const double *)S, ldv, dout);
     HIPCHECK(hipMemcpyAsync(out, dout, sizeof(double) * pl.wsize, hipMemcpyDeviceToHost, h->stream));
-    return ct_finish(h, true);
+    return ct_finish(h, pl);
 }
 extern "C" int ttx_contract_modesum(const ttx_engine *h, double *ms, double *bytes)
 {
@@ -3342,23 +3352,16 @@ extern "C" int ttx_contract_modesum(const ttx_engine *h, double *ms, double *byt
 }
 
 // ---- samples from the resident train (ttx_sample.h) -------------------------------------------------------------------------------
-static size_t sm_chunk()
-{
-    if (const char *e = getenv("TTX_SAMPLE_CHUNK")) { const long long v = atoll(e); if (v >= 1) return (size_t)std::min<long long>(v, 1ll << 24); }
-    return (size_t)1 << 18;
-}
 // both entries: u, ind, logq, val are host pointers (dev false: staged chunk by chunk) or pointers on the engine's device
 static int sm_run(ttx_engine *h, const char *who, int64_t npts, const double *u, const double *w, const int32_t *fixed, int32_t *ind, double *logq, double *val, bool dev)
 {
     if (npts < 0 || (npts > 0 && (!u || !ind))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
-    if (!h || !h->ran) return fail(TTX_ESTATE, "%s: no tensor train (run dtt_dmrgg first)", who);
-    if (h->W > 1) return tt_prepare(h, who);
+    int rc = check_train_one_process(h, who);
+    if (rc) return rc;
     const int d = h->d;
     if (fixed) for (int k = 0; k < d; k++) if (fixed[k] < 0 || fixed[k] > h->n1[k + 1]) return fail(TTX_EINVAL, "%s: fixed(%d) = %d (0 .. %d expected)", who, k + 1, fixed[k], h->n1[k + 1]);
     h->sm_ms_head = h->sm_ms_draw = h->sm_bytes = 0.0; h->sm_failed = 0;
     if (npts == 0) return TTX_OK;
-    HIPCHECK(hipSetDevice(h->cfg.device));
-    int rc;
     EvTrain T;
     if ((rc = ev_train(h, &T))) return rc;
     // the prefix vectors: mode sums with the effective weights (a fixed mode: the unit vector of its index), then the l chain
@@ -3386,58 +3389,52 @@ static int sm_run(ttx_engine *h, const char *who, int64_t npts, const double *u,
     }
     if (tiles.size() > 0x7fffffffull) return fail(TTX_EINVAL, "%s: too many head tiles (%zu)", who, tiles.size());
     const int ldv = h->RM;
-    CtMeta meta(h->ct_meta_host);
+    OpMeta meta(h->meta_host);
     const size_t o_cores = meta.put(pl.cores), o_tiles = meta.put(pl.tiles), o_r = meta.put(pl.r), o_moff = meta.put(pl.moff),
                  o_sm = meta.put(tiles), o_hoff = meta.put(hoff), o_fx = meta.put(fx);
-    if ((rc = buf_reserve(h, h->ct[ttx_engine::CT_META], h->ct_meta_host.size())) || (rc = buf_reserve(h, h->ct[ttx_engine::CT_VEC], sizeof(double) * (2 * (size_t)d + 4) * ldv)) ||
-        (rc = buf_reserve(h, h->sm[ttx_engine::SM_H], sizeof(double) * std::max<size_t>(hsize, 1))) || (rc = buf_reserve(h, h->sm[ttx_engine::SM_CNT], sizeof(long long)))) return rc;
-    char *dm = (char *)h->ct[ttx_engine::CT_META].p;
-    HIPCHECK(hipMemcpyAsync(dm, h->ct_meta_host.data(), h->ct_meta_host.size(), hipMemcpyHostToDevice, h->stream));
-    const double ct_ms = h->ct_ms, ct_bytes = h->ct_bytes;                      // ttx_contract_modesum keeps reporting its own last call
-    rc = ct_modesum(h, pl, eff.data(), (const CtCore *)(dm + o_cores), (const CtTile *)(dm + o_tiles));
-    h->ct_ms = ct_ms; h->ct_bytes = ct_bytes;
-    if (rc) return rc;
-    double *L = (double *)h->ct[ttx_engine::CT_VEC].p, *S = L + (size_t)d * ldv, *H = (double *)h->sm[ttx_engine::SM_H].p;
-    long long *dcnt = (long long *)h->sm[ttx_engine::SM_CNT].p;
-    hipLaunchKernelGGL(k_ct_chains, dim3(2), dim3(1024), 0, h->stream, d, (const int *)(dm + o_r), (const size_t *)(dm + o_moff), (const double *)h->ct[ttx_engine::CT_M].p, L, S, ldv);
-    for (auto &e : h->sm_ev) if (!e) HIPCHECK(hipEventCreate(&e));
+    char *dm;
+    if ((rc = meta.upload(h, SC_META, &dm)) || (rc = buf_reserve(h, SC_VEC, sizeof(double) * (2 * (size_t)d + 4) * ldv)) ||
+        (rc = buf_reserve(h, SC_H, sizeof(double) * std::max<size_t>(hsize, 1))) || (rc = buf_reserve(h, SC_CNT, sizeof(long long))) ||
+        (rc = ct_modesum(h, pl, eff.data(), (const CtCore *)(dm + o_cores), (const CtTile *)(dm + o_tiles), nullptr))) return rc;   // untimed: ttx_contract_modesum keeps its own last call
+    double *L = buf<double>(h, SC_VEC), *S = L + (size_t)d * ldv, *H = buf<double>(h, SC_H);
+    long long *dcnt = buf<long long>(h, SC_CNT);
+    OpTimer &t_head = h->timer[TM_HEAD], &t_draw = h->timer[TM_DRAW];
+    hipLaunchKernelGGL(k_ct_chains, dim3(2), dim3(1024), 0, h->stream, d, (const int *)(dm + o_r), (const size_t *)(dm + o_moff), (const double *)buf<double>(h, SC_M), L, S, ldv);
     HIPCHECK(hipMemsetAsync(dcnt, 0, sizeof(long long), h->stream));
     if (!tiles.empty()) {
-        HIPCHECK(hipEventRecord(h->sm_ev[0], h->stream));
+        if ((rc = t_head.start(h->stream))) return rc;
         hipLaunchKernelGGL(k_sm_head, dim3((unsigned)tiles.size()), dim3(256), 0, h->stream, (const CtCore *)(dm + o_cores), (const SmTile *)(dm + o_sm), h->RM, h->P.SS,
-                           (const double *)h->ct[ttx_engine::CT_W].p, (const double *)L, ldv, (const size_t *)(dm + o_hoff), H);
-        HIPCHECK(hipEventRecord(h->sm_ev[1], h->stream));
+                           (const double *)buf<double>(h, SC_W), (const double *)L, ldv, (const size_t *)(dm + o_hoff), H);
+        if ((rc = t_head.stop(h->stream))) return rc;
     }
     // the draw: one wave per sample, 4 waves per workgroup, the grid capped at 8 workgroups per CU as k_ev_exact's
-    const size_t chunk = std::min<size_t>(sm_chunk(), (size_t)npts);
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
-    const int gridmax = (int)std::min<long long>(((long long)chunk + 3) / 4, (long long)ncu * 8);
+    const size_t chunk = std::min<size_t>(env_chunk("TTX_SAMPLE_CHUNK", (size_t)1 << 18), (size_t)npts);
+    const int gridmax = (int)std::min<long long>(((long long)chunk + 3) / 4, (long long)dev_ncu(h) * 8);
     const int ldsrow = std::min(nrow, TTX_SM_LDSROW);
     const size_t growlen = nrow > TTX_SM_LDSROW ? (size_t)nrow : 0;
     const size_t lds = 4 * sizeof(double) * (2 * (size_t)T.ldx + d + (((size_t)d + 1) >> 1) + ldsrow);
     if (lds > 160 * 1024) return fail(TTX_EINVAL, "%s: %d modes need %zu bytes of LDS per workgroup (160 KB at most)", who, d, lds);
     if (lds > 64 * 1024) HIPCHECK(hipFuncSetAttribute((const void *)k_sm_draw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (growlen && (rc = buf_reserve(h, h->sm[ttx_engine::SM_ROW], sizeof(double) * growlen * 4 * gridmax))) return rc;
-    double *grow = growlen ? (double *)h->sm[ttx_engine::SM_ROW].p : nullptr;
-    if (!dev && ((rc = buf_reserve(h, h->sm[ttx_engine::SM_U], sizeof(double) * chunk * d)) || (rc = buf_reserve(h, h->sm[ttx_engine::SM_IND], sizeof(int) * chunk * d)) ||
-                 (rc = buf_reserve(h, h->sm[ttx_engine::SM_LQ], sizeof(double) * chunk)) || (rc = buf_reserve(h, h->sm[ttx_engine::SM_VAL], sizeof(double) * chunk)))) return rc;
+    if (growlen && (rc = buf_reserve(h, SC_ROW, sizeof(double) * growlen * 4 * gridmax))) return rc;
+    double *grow = growlen ? buf<double>(h, SC_ROW) : nullptr;
+    if (!dev && ((rc = buf_reserve(h, SC_X, sizeof(double) * chunk * d)) || (rc = buf_reserve(h, SC_IND, sizeof(int) * chunk * d)) ||
+                 (rc = buf_reserve(h, SC_LQ, sizeof(double) * chunk)) || (rc = buf_reserve(h, SC_OUT, sizeof(double) * chunk)))) return rc;
     for (int64_t o = 0; o < npts; o += (int64_t)chunk) {
         const size_t c = (size_t)std::min<int64_t>((int64_t)chunk, npts - o);
         const double *du = u + (size_t)o * d;
         int *di = ind + (size_t)o * d;
         double *dl = logq ? logq + o : nullptr, *dv = val ? val + o : nullptr;
         if (!dev) {
-            HIPCHECK(hipMemcpyAsync(h->sm[ttx_engine::SM_U].p, du, sizeof(double) * c * d, hipMemcpyHostToDevice, h->stream));
-            du = (const double *)h->sm[ttx_engine::SM_U].p; di = (int *)h->sm[ttx_engine::SM_IND].p;
-            if (logq) dl = (double *)h->sm[ttx_engine::SM_LQ].p;
-            if (val) dv = (double *)h->sm[ttx_engine::SM_VAL].p;
+            HIPCHECK(hipMemcpyAsync(buf<double>(h, SC_X), du, sizeof(double) * c * d, hipMemcpyHostToDevice, h->stream));
+            du = buf<double>(h, SC_X); di = buf<int>(h, SC_IND);
+            if (logq) dl = buf<double>(h, SC_LQ);
+            if (val) dv = buf<double>(h, SC_OUT);
         }
         const int grid = (int)std::min<long long>(((long long)c + 3) / 4, (long long)gridmax);
-        HIPCHECK(hipEventRecord(h->sm_ev[2], h->stream));
+        if ((rc = t_draw.start(h->stream))) return rc;
         hipLaunchKernelGGL(k_sm_draw, dim3(grid), dim3(256), lds, h->stream, T, (const size_t *)(dm + o_hoff), (const int *)(dm + o_fx), (const double *)H, ldsrow, grow, growlen,
                            (long long)c, du, di, dl, dv);
-        HIPCHECK(hipEventRecord(h->sm_ev[3], h->stream));
+        if ((rc = t_draw.stop(h->stream))) return rc;
         hipLaunchKernelGGL(k_sm_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const int *)di, dcnt);
         if (!dev) {
             HIPCHECK(hipMemcpyAsync(ind + (size_t)o * d, di, sizeof(int) * c * d, hipMemcpyDeviceToHost, h->stream));
@@ -3446,15 +3443,14 @@ static int sm_run(ttx_engine *h, const char *who, int64_t npts, const double *u,
         }
         HIPCHECK(hipStreamSynchronize(h->stream));
         HIPCHECK(hipGetLastError());
-        float ms = 0.f;
-        HIPCHECK(hipEventElapsedTime(&ms, h->sm_ev[2], h->sm_ev[3]));
+        double ms = 0.0;
+        if ((rc = t_draw.ms(&ms))) return rc;
         h->sm_ms_draw += ms;
     }
     long long nf = 0;
     HIPCHECK(hipMemcpy(&nf, dcnt, sizeof(long long), hipMemcpyDeviceToHost));
     h->sm_failed = nf;
-    if (!tiles.empty()) { float ms = 0.f; HIPCHECK(hipEventElapsedTime(&ms, h->sm_ev[0], h->sm_ev[1])); h->sm_ms_head = ms; }
-    return TTX_OK;
+    return tiles.empty() ? TTX_OK : t_head.ms(&h->sm_ms_head);
 }
 extern "C" int ttx_sample(ttx_engine *h, int64_t npts, const double *u, const double *w, const int32_t *fixed, int32_t *ind, double *logq, double *val)
 {
@@ -3501,24 +3497,23 @@ static int alg_check(const char *who, int m, ttx_engine *const *x)
     }
     return TTX_OK;
 }
-// the block table to the device, the one launch between the engine's two events, the wait
+// the block table to the device, the one launch between the timer's events, the wait
 static int alg_launch(ttx_engine *h, ttx_engine *e, const std::vector<AlgBlk> &blks, long long tiles, bool hadamard, double rd, double wr)
 {
     int rc;
-    if ((rc = buf_reserve(h, h->alg_meta, sizeof(AlgBlk) * blks.size()))) return rc;
-    HIPCHECK(hipMemcpyAsync(h->alg_meta.p, blks.data(), sizeof(AlgBlk) * blks.size(), hipMemcpyHostToDevice, h->stream));
-    for (auto &ev : h->alg_ev) if (!ev) HIPCHECK(hipEventCreate(&ev));
+    OpMeta meta(h->meta_host);
+    meta.put(blks);
+    char *dm;
+    if ((rc = meta.upload(h, SC_META, &dm))) return rc;
+    OpTimer &tm = h->timer[TM_ALG];
     h->alg_ms = 0.0; h->alg_rd = rd; h->alg_wr = wr;
-    HIPCHECK(hipEventRecord(h->alg_ev[0], h->stream));
-    if (hadamard) hipLaunchKernelGGL(k_alg_hadamard, dim3((unsigned)tiles), dim3(256), 0, h->stream, (const AlgBlk *)h->alg_meta.p, (int)blks.size(), e->RM, e->P.SS);
-    else hipLaunchKernelGGL(k_alg_lincomb, dim3((unsigned)tiles), dim3(256), 0, h->stream, (const AlgBlk *)h->alg_meta.p, (int)blks.size(), e->RM, e->P.SS);
-    HIPCHECK(hipEventRecord(h->alg_ev[1], h->stream));
+    if ((rc = tm.start(h->stream))) return rc;
+    if (hadamard) hipLaunchKernelGGL(k_alg_hadamard, dim3((unsigned)tiles), dim3(256), 0, h->stream, (const AlgBlk *)dm, (int)blks.size(), e->RM, e->P.SS);
+    else hipLaunchKernelGGL(k_alg_lincomb, dim3((unsigned)tiles), dim3(256), 0, h->stream, (const AlgBlk *)dm, (int)blks.size(), e->RM, e->P.SS);
+    if ((rc = tm.stop(h->stream))) return rc;
     HIPCHECK(hipStreamSynchronize(h->stream));
     HIPCHECK(hipGetLastError());
-    float ms = 0.f;
-    HIPCHECK(hipEventElapsedTime(&ms, h->alg_ev[0], h->alg_ev[1]));
-    h->alg_ms = ms;
-    return TTX_OK;
+    return tm.ms(&h->alg_ms);
 }
 static int alg_lincomb_fill(int m, const double *coef, ttx_engine *const *x, ttx_engine *e)
 {
@@ -3561,7 +3556,7 @@ extern "C" int ttx_lincomb(int32_t m, const double *coef, ttx_engine *const *x, 
     if (rc) return rc;
     ttx_engine *h = x[0];
     const int d = h->d;
-    std::vector<int32_t> nn(h->n1.begin() + 1, h->n1.begin() + 1 + d), rr(d + 1, 1);
+    std::vector<int32_t> nn = modes_of(h), rr(d + 1, 1);
     for (int k = 1; k < d; k++) {
         long long s = 0;
         for (int t = 0; t < m; t++) s += x[t]->rfinal[k];
@@ -3569,11 +3564,7 @@ extern "C" int ttx_lincomb(int32_t m, const double *coef, ttx_engine *const *x, 
         rr[k] = (int32_t)s;
     }
     HIPCHECK(hipSetDevice(h->cfg.device));
-    ttx_engine *e = nullptr;
-    if ((rc = train_shell(&e, "ttx_lincomb", d, nn.data(), rr.data(), h->cfg.device))) return rc;
-    if ((rc = alg_lincomb_fill(m, coef, x, e))) { const std::string msg = g_err; ttx_destroy(e); g_err = msg; return rc; }
-    *out = e;
-    return TTX_OK;
+    return new_train(out, "ttx_lincomb", d, nn.data(), rr.data(), h->cfg.device, [&](ttx_engine *e) { return alg_lincomb_fill(m, coef, x, e); });
 }
 static int alg_hadamard_fill(ttx_engine *x, ttx_engine *y, ttx_engine *e)
 {
@@ -3609,18 +3600,14 @@ extern "C" int ttx_hadamard(ttx_engine *x, ttx_engine *y, ttx_engine **out)
     int rc = alg_check("ttx_hadamard", 2, xy);
     if (rc) return rc;
     const int d = x->d;
-    std::vector<int32_t> nn(x->n1.begin() + 1, x->n1.begin() + 1 + d), rr(d + 1, 1);
+    std::vector<int32_t> nn = modes_of(x), rr(d + 1, 1);
     for (int k = 1; k < d; k++) {
         const int p = x->rfinal[k] * y->rfinal[k];
         if (p > 128) return fail(TTX_EINVAL, "ttx_hadamard: the ranks at bond %d multiply to %d (%d x %d), the engine holds ranks up to 128 (round the factors first: ttx_svd)", k, p, x->rfinal[k], y->rfinal[k]);
         rr[k] = p;
     }
     HIPCHECK(hipSetDevice(x->cfg.device));
-    ttx_engine *e = nullptr;
-    if ((rc = train_shell(&e, "ttx_hadamard", d, nn.data(), rr.data(), x->cfg.device))) return rc;
-    if ((rc = alg_hadamard_fill(x, y, e))) { const std::string msg = g_err; ttx_destroy(e); g_err = msg; return rc; }
-    *out = e;
-    return TTX_OK;
+    return new_train(out, "ttx_hadamard", d, nn.data(), rr.data(), x->cfg.device, [&](ttx_engine *e) { return alg_hadamard_fill(x, y, e); });
 }
 extern "C" int ttx_algebra_last(const ttx_engine *h, double *ms, double *bytes_read, double *bytes_written)
 {
