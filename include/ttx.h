@@ -356,6 +356,16 @@ int ttx_set_profile(ttx_engine *h, int on);
  * 0 multi-kernel chain (k_lottery / k_halfstep / k_accept per bond), 1 one workgroup per bond group for the whole
  * sweep (k_sweep_fused), 2 a cluster of workgroups per bond group for the whole sweep (k_sweep_cluster) */
 int ttx_sweep_path(const ttx_engine *h);
+/* the kernels this engine would launch now, one line per stage, as NUL-terminated text in buf (cap bytes; TTX_EINVAL if too small).
+ * Read-only, usable right after ttx_create; a fallback of ttx_run changes it.  Kernels by their source names with the template
+ * arguments that select behaviour; "-": the stage launches nothing.
+ *     path: chain|fused|cluster
+ *     tables: <kernel or ->
+ *     lottery: <kernel>                    or  <kernel> + <candidate evaluator> + <kernel>   (-: full pivoting draws none)
+ *     halfstep: <kernel>[<=N], <kernel>[<=M], <kernel>    (a tier is taken while the sweep's units * groups are at most its bound)
+ *     fullpiv: plain|mfma|columns          (pivoting -1 only: every column at once, the dense MFMA step, one column per host pass)
+ * The last lines describe the multi-kernel chain also where a whole-sweep kernel is in use: they are what a fallback runs. */
+int ttx_plan_describe(const ttx_engine *h, char *buf, int64_t cap);
 /* the integrand evaluator inside the cluster kernel (one instantiation of k_sweep_cluster each): 0 the engine is not on the cluster
  * path, 1 exact chains with predicated remainders (any node values; TTX_CL_PAD=0 asks for it), 2 exact chains over rows padded to
  * whole chunks of 8 with neutral elements (the default where every Ising node lies in [0,1]; same bits), 3 the closed form of

@@ -22,6 +22,7 @@
 #include <random>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include <atomic>
@@ -34,6 +35,7 @@
 
 #include "../../include/ttx.h"
 #include "../../include/ttx_device_fun.h"   // the slot ABI of loadable device integrands (TTX_FUN_DEVICE)
+#include "ttx_lds.h"
 #include "ttx_kernels.h"
 #include "ttx_de.h"
 #include "ttx_mvn.h"
@@ -61,6 +63,20 @@ static int fail(int code, const char *fmt, ...)
     return code;
 }
 #define HIPCHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(TTX_EHIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+
+
+// switches from the environment: an integer (or the default where the variable is unset), "set to 0"
+static int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
+static bool env_off(const char *name) { const char *e = getenv(name); return e && atoi(e) == 0; }
+
+// raise a kernel's dynamic-LDS ceiling on `device` (the current one) to `need` bytes, unless an earlier request there was as large
+static int ensure_lds(int device, const void *fn, size_t need)
+{
+    return ttx_lds_raise(device, fn, need, [](const void *fn, size_t need) -> int {
+        HIPCHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
+        return TTX_OK;
+    });
+}
 
 extern "C" const char *ttx_last_error(void) { return g_err.c_str(); }
 extern "C" int ttx_version(void) { return 3; }      // 2: loadable device integrands; 3: ttx_ijk_batch, ttx_ijk_batch_dev, ttx_value_batch (ttx_contract, ttx_marginals: added without a new number)
@@ -428,8 +444,10 @@ static double powi(double a, int b)
     return r;
 }
 
-static int ensure_lds(const void *fn, size_t need, size_t &cur);
-static int ensure_lds_cluster(ttx_engine *h);
+static int ensure_lds(const ttx_engine *h, const void *fn, size_t need) { return ensure_lds(h->cfg.device, fn, need); }
+static int ensure_lds_cluster(ttx_engine *h) { return ensure_lds(h, reinterpret_cast<const void *>(cluster_kernel(h->cluster_var)), h->lds_cluster); }
+
+static void destroy_keep_error(ttx_engine *e) { const std::string msg = g_err; ttx_destroy(e); g_err = msg; }
 
 // nofun: an engine that only holds a tensor train (ttx_from_tt / ttx_read): no integrand, ttx_run refused
 static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
@@ -466,6 +484,9 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
     HIPCHECK(hipSetDevice(cfg->device));
 
     ttx_engine *h = new ttx_engine();
+    // every early return below destroys the engine and what it holds so far; the error text is set before and survives
+    struct Guard { ttx_engine *h; ~Guard() { if (h) destroy_keep_error(h); } } guard{h};
+#define A_(call) do { if (int rc_ = (call)) return rc_; } while (0)
     h->cfg = *cfg;
     h->cfg.nproc = nproc;
     h->W = W; h->wrank = cfg->world_rank;
@@ -473,17 +494,17 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
     h->d = d; h->RM = cfg->maxrank;
     h->n1.assign(d + 2, 1);
     int NM = 1;
-    for (int k = 1; k <= d; k++) { h->n1[k] = cfg->n[k - 1]; if (cfg->n[k - 1] < 1 || cfg->n[k - 1] > 32000) { delete h; return fail(TTX_EINVAL, "bad mode size"); } NM = std::max(NM, cfg->n[k - 1]); }
+    for (int k = 1; k <= d; k++) { h->n1[k] = cfg->n[k - 1]; if (cfg->n[k - 1] < 1 || cfg->n[k - 1] > 32000) return fail(TTX_EINVAL, "bad mode size"); NM = std::max(NM, cfg->n[k - 1]); }
     h->NM = NM;
-    if ((long long)h->RM * NM > (long long)TTX_MAXPART * TTX_BLK) { delete h; return fail(TTX_EINVAL, "maxrank*n too large"); }
+    if ((long long)h->RM * NM > (long long)TTX_MAXPART * TTX_BLK) return fail(TTX_EINVAL, "maxrank*n too large");
     if (cfg->npar > 0) h->par.assign(cfg->par, cfg->par + cfg->npar);
     if (cfg->aux && cfg->naux > 0) h->aux.assign(cfg->aux, cfg->aux + cfg->naux);
     if (cfg->mybonds) h->own.assign(cfg->mybonds, cfg->mybonds + nproc + 1);
     else share(1, d - 1, nproc, h->own);                               // lib/dmrgg.f90:126-130
-    for (int g = 0; g < nproc; g++) if (h->own[g + 1] <= h->own[g]) { delete h; return fail(TTX_EINVAL, "mybonds: empty group %d", g); }
+    for (int g = 0; g < nproc; g++) if (h->own[g + 1] <= h->own[g]) return fail(TTX_EINVAL, "mybonds: empty group %d", g);
     // the groups must tile the bonds 1 .. d-1 (own(0) = 1, own(nproc) = d, lib/default.f90:78-97): anything else would address
     // cores that do not exist or leave bonds without an owner
-    if (h->own[0] != 1 || h->own[nproc] != d) { const int a = h->own[0], b = h->own[nproc]; delete h; return fail(TTX_EINVAL, "mybonds: must run from 1 to d = %d (got %d .. %d)", d, a, b); }
+    if (h->own[0] != 1 || h->own[nproc] != d) return fail(TTX_EINVAL, "mybonds: must run from 1 to d = %d (got %d .. %d)", d, h->own[0], h->own[nproc]);
     // bond groups are dealt contiguously to the GPUs of the job
     h->g0 = (int)((long long)nproc * h->wrank / W);
     h->G = (int)((long long)nproc * (h->wrank + 1) / W) - h->g0;
@@ -498,24 +519,20 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
     P.d = d; P.RM = h->RM; P.NM = NM; P.G = h->G; P.NC = h->NC; P.g0 = h->g0;
     P.fun_id = cfg->fun_id; P.piv = cfg->pivoting; P.npar = cfg->npar; P.nprocs = nproc;
     P.ising_id = (cfg->fun_id == TTX_FUN_ISING) ? (int)cfg->par[2 * cfg->n[0]] : 0;
+    const bool isDE = cfg->fun_id == TTX_FUN_ISING && P.ising_id != 1;     // Ising D or E: the long dependent chains of ttx_de.h
     P.has_quad = cfg->quadw != nullptr;
     P.small_element = 10 * 2.220446049250313e-16; P.small_pivot = 1.e-5;   // lib/dmrgg.f90:70-71
     P.mvn_norm = 1.0;
     if (cfg->fun_id == TTX_FUN_MVN) {
-        if (cfg->naux < d + d * d + 1) { delete h; return fail(TTX_EINVAL, "mvn: aux too short"); }
+        if (cfg->naux < d + d * d + 1) return fail(TTX_EINVAL, "mvn: aux too short");
         P.mvn_norm = std::sqrt(powi(2.0 * 3.141592653589793, d) * cfg->aux[d + (size_t)d * d]);   // lib/mvn_pdf.f90:82
-        if (!(P.mvn_norm > 0.0) || !std::isfinite(P.mvn_norm)) {
-            const double nrm = P.mvn_norm, det = cfg->aux[d + (size_t)d * d];
-            delete h;
+        if (!(P.mvn_norm > 0.0) || !std::isfinite(P.mvn_norm))
             return fail(TTX_EINVAL, "ttx_create: mvn normalisation sqrt((2 pi)^d det) = %g is not a positive finite number (det = %g under- or overflows at d = %d)",
-                        nrm, det, d);
-        }
+                        P.mvn_norm, cfg->aux[d + (size_t)d * d], d);
     }
     P.SS = (size_t)h->RM * NM; P.SW = (size_t)NM * h->RM; P.CS = (size_t)h->RM * NM * h->RM;
     const size_t G = h->G, NC = h->NC, RM = h->RM;
-    int rc;
     int *dn; double *dpar, *daux = nullptr, *dq = nullptr;
-#define A_(call) if ((rc = (call)) != TTX_OK) { ttx_destroy(h); return rc; }
     A_(dev_alloc(h, &dn, d + 2));
     A_(dev_alloc(h, &dpar, cfg->npar + 1));
     HIPCHECK(hipMemcpy(dn, h->n1.data(), sizeof(int) * (d + 2), hipMemcpyHostToDevice));
@@ -531,27 +548,26 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
     P.n = dn; P.par = dpar; P.aux = daux; P.quadw = dq;
     {   // TTX_ARITH: exact (default) or fast; fast is effective where a re-associated evaluator exists (ttx_fast.h)
         bool want = cfg->arith == TTX_ARITH_FAST;
-        if (cfg->arith != TTX_ARITH_EXACT && cfg->arith != TTX_ARITH_FAST) { ttx_destroy(h); return fail(TTX_EINVAL, "ttx_create: arith must be TTX_ARITH_EXACT or TTX_ARITH_FAST (got %d)", cfg->arith); }
+        if (cfg->arith != TTX_ARITH_EXACT && cfg->arith != TTX_ARITH_FAST) return fail(TTX_EINVAL, "ttx_create: arith must be TTX_ARITH_EXACT or TTX_ARITH_FAST (got %d)", cfg->arith);
         if (const char *e = getenv("TTX_ARITH")) {
             const std::string v = e;
             if (v == "fast") want = true;
             else if (v == "exact") want = (cfg->arith == TTX_ARITH_FAST);
-            else { ttx_destroy(h); return fail(TTX_EINVAL, "TTX_ARITH must be exact or fast (got %s)", e); }
+            else return fail(TTX_EINVAL, "TTX_ARITH must be exact or fast (got %s)", e);
         }
         h->want_fast = want && !nofun;
-        // the integrand reads node par[ind - 1] for ind up to the LARGEST mode size (lib: nodes + ind), whatever n(1) is
-        int nnode = 0; for (int k = 0; k < d; k++) nnode = std::max(nnode, (int)cfg->n[k]);
-        nnode = std::min(nnode, (int)cfg->npar);
-        bool unit = true;               // Ising: all nodes in [0,1] (every running product non-increasing: the cut at 2^-54 is valid)
-        if (cfg->fun_id == TTX_FUN_ISING) for (int j = 0; j < nnode; j++) if (!(cfg->par[j] >= 0.0 && cfg->par[j] <= 1.0)) unit = false;
-        h->unit_nodes = cfg->fun_id == TTX_FUN_ISING && unit;
-        P.arith = (want && !nofun && ((cfg->fun_id == TTX_FUN_ISING && P.ising_id != 1 && unit) || cfg->fun_id == TTX_FUN_MVN)) ? 1 : 0;
+        // Ising: all nodes in [0,1] (every running product stays in [0,1] and is non-increasing: the cut at 2^-54 is valid, fdiv_unit
+        // is exact).  The integrand reads node par[ind - 1] for ind up to the LARGEST mode size (lib: nodes + ind), whatever n(1) is
+        bool unit = cfg->fun_id == TTX_FUN_ISING;
+        for (int j = 0; unit && j < std::min(NM, (int)cfg->npar); j++) unit = cfg->par[j] >= 0.0 && cfg->par[j] <= 1.0;
+        h->unit_nodes = unit;
+        P.arith = (want && !nofun && ((isDE && unit) || cfg->fun_id == TTX_FUN_MVN)) ? 1 : 0;
         if (P.arith) {
             P.FD = d + 1;
             // tables per bond, kept for the whole run and extended incrementally (ttx_fast.h); TTX_FAST_PERSIST=0: mvn rebuilds the
             // tables of a bond step's two pivot sets with k_fast_tables instead (the first version, kept as a cross-check)
             P.fpersist = 1;
-            if (cfg->fun_id == TTX_FUN_MVN && getenv("TTX_FAST_PERSIST") && atoi(getenv("TTX_FAST_PERSIST")) == 0) P.fpersist = 0;
+            if (cfg->fun_id == TTX_FUN_MVN && env_off("TTX_FAST_PERSIST")) P.fpersist = 0;
             const size_t slots = P.fpersist ? G * NC : G;
             for (int sd = 0; sd < 2; sd++) {
                 A_(dev_alloc(h, &P.fNear[sd], slots * (size_t)P.FD * RM));
@@ -569,37 +585,30 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
             }
         }
     }
-    const bool de_lane = getenv("TTX_DE_LANE") && atoi(getenv("TTX_DE_LANE")) == 1;
-    if (cfg->fun_id == TTX_FUN_ISING && P.ising_id != 1 && !P.arith && de_lane) {
-        // one fiber element per lane, every pair by division, rows ended at the unit cut (f_ising_de with `unit`): no tables, no teams
-        P.de_unit = 1;
-        for (int j = 0; j < std::min((int)cfg->npar, std::max((int)cfg->n[0], (int)NM)); j++) if (!(cfg->par[j] >= 0.0 && cfg->par[j] <= 1.0)) P.de_unit = 0;
-    }
-    if (cfg->fun_id == TTX_FUN_ISING && P.ising_id != 1 && !P.arith && !de_lane && !(getenv("TTX_DE_TABLES") && atoi(getenv("TTX_DE_TABLES")) == 0)) {
+    const bool de_lane = env_int("TTX_DE_LANE", 0) == 1;
+    // one fiber element per lane, every pair by division, rows ended at the unit cut (f_ising_de with `unit`): no tables, no teams
+    if (isDE && !P.arith && de_lane) P.de_unit = h->unit_nodes;
+    if (isDE && !P.arith && !de_lane && !env_off("TTX_DE_TABLES")) {
         P.de_npair = d * (d + 1) / 2;
         A_(dev_alloc(h, &P.deTL, G * (size_t)P.de_npair * RM)); A_(dev_alloc(h, &P.deTR, G * (size_t)P.de_npair * RM));
         A_(dev_alloc(h, &P.deUL, G * (size_t)(d + 1) * RM));
-        P.de_unit = 1;                  // nodes in [0,1]: every running product stays in [0,1] and fdiv_unit is exact
-        for (int j = 0; j < std::min((int)cfg->npar, std::max((int)cfg->n[0], (int)NM)); j++) if (!(cfg->par[j] >= 0.0 && cfg->par[j] <= 1.0)) P.de_unit = 0;
-        if (getenv("TTX_DE_FASTDIV") && atoi(getenv("TTX_DE_FASTDIV")) == 0) P.de_unit = 0;
+        P.de_unit = h->unit_nodes && !env_off("TTX_DE_FASTDIV");
         // nodes in [0,1]: compact tables, every row of the pair triangle ends at the unit cut (k_de_ctables, k_halfstep_dec; same bits).
         // TTX_DE_CUT=0: the full tables and the kernels of round 2 (wave teams, row-wise lottery)
-        P.de_cut = (P.de_unit && !(getenv("TTX_DE_CUT") && atoi(getenv("TTX_DE_CUT")) == 0)) ? 1 : 0;
+        P.de_cut = (P.de_unit && !env_off("TTX_DE_CUT")) ? 1 : 0;
         if (P.de_cut) { A_(dev_alloc(h, &P.deCL, G * (size_t)(d + 1) * RM)); A_(dev_alloc(h, &P.deCR, G * (size_t)(d + 1) * RM)); }
-        h->de_lot_point = d <= 160;
-        if (const char *e = getenv("TTX_DE_LOT_POINT")) h->de_lot_point = atoi(e) != 0;
+        h->de_lot_point = env_int("TTX_DE_LOT_POINT", d <= 160) != 0;
         h->de_slots = (int)RM * ((NM + 63) / 64);
         h->lds_de = sizeof(double) * (5 * (size_t)(((d + 7) & ~7) + 8) + 256) + (P.de_cut ? sizeof(int) * (size_t)(((d + 7) & ~7) + 8) : 0);
-        h->de_v2 = cfg->pivoting >= 0 && h->de_slots <= TTX_MAXPART && h->lds_de <= 150 * 1024 &&
-                   !(getenv("TTX_DE_V2") && atoi(getenv("TTX_DE_V2")) == 0);
+        h->de_v2 = cfg->pivoting >= 0 && h->de_slots <= TTX_MAXPART && h->lds_de <= 150 * 1024 && !env_off("TTX_DE_V2");
         h->lds_det = sizeof(double) * det_lds_doubles(d, 3);
         h->lds_det6 = sizeof(double) * det_lds_doubles(d, 1);
-        if (getenv("TTX_DE_TEAM6_UNITS")) h->de_team6_units = atoi(getenv("TTX_DE_TEAM6_UNITS"));
-        h->de_team = h->de_v2 && !P.de_cut && h->lds_det <= 150 * 1024 && !(getenv("TTX_DE_TEAM") && atoi(getenv("TTX_DE_TEAM")) == 0);
-        if (getenv("TTX_DE_TEAM_UNITS")) h->de_team_units = atoi(getenv("TTX_DE_TEAM_UNITS"));
-        if (getenv("TTX_DE_TEST_FAULT")) h->de_test_fault = atoi(getenv("TTX_DE_TEST_FAULT"));
+        h->de_team = h->de_v2 && !P.de_cut && h->lds_det <= 150 * 1024 && !env_off("TTX_DE_TEAM");
+        h->de_team_units = env_int("TTX_DE_TEAM_UNITS", h->de_team_units);
+        h->de_team6_units = env_int("TTX_DE_TEAM6_UNITS", h->de_team6_units);
+        h->de_test_fault = env_int("TTX_DE_TEST_FAULT", 0);
         h->lds_de5 = sizeof(double) * de5_lds_doubles(d);
-        h->de_v5 = h->de_v2 && !P.de_cut && de5_fits(d) && h->lds_de5 <= 150 * 1024 && getenv("TTX_DE_V5") && atoi(getenv("TTX_DE_V5")) == 1;
+        h->de_v5 = h->de_v2 && !P.de_cut && de5_fits(d) && h->lds_de5 <= 150 * 1024 && env_int("TTX_DE_V5", 0) == 1;
     }
     if (cfg->fun_id == TTX_FUN_MVN) {
         std::vector<double> t((size_t)d * d);
@@ -621,7 +630,7 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
         for (size_t g = 0; g < G; g++) {
             g0s->first = h->own[h->g0 + g]; g0s->last = h->own[h->g0 + g + 1] - 1; g0s->gglobal = h->g0 + (int)g;
             hipError_t e = hipMemcpy(P.gs + g, g0s, offsetof(GroupState, S), hipMemcpyHostToDevice);
-            if (e != hipSuccess) { free(g0s); ttx_destroy(h); return fail(TTX_EHIP, "ttx_create: %s", hipGetErrorString(e)); }
+            if (e != hipSuccess) { free(g0s); return fail(TTX_EHIP, "ttx_create: %s", hipGetErrorString(e)); }
         }
         free(g0s);
     }
@@ -659,11 +668,10 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
         HIPCHECK(hipMemcpy(P.inL, il.data(), sizeof(char *) * G, hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(P.inR, ir.data(), sizeof(char *) * G, hipMemcpyHostToDevice));
     }
-#undef A_
     {
         int *ctl, *rq;
-        rc = dev_alloc(h, &ctl, (size_t)4); if (rc) { ttx_destroy(h); return rc; }
-        rc = dev_alloc(h, &rq, (size_t)G * (d + 2)); if (rc) { ttx_destroy(h); return rc; }
+        A_(dev_alloc(h, &ctl, (size_t)4));
+        A_(dev_alloc(h, &rq, (size_t)G * (d + 2)));
         P.ctl = ctl; P.rq = rq; P.accuracy = cfg->accuracy; P.maxrank = cfg->maxrank;
     }
     HIPCHECK(hipHostMalloc((void **)&h->h_sum_base, sizeof(double) * 2 * h->SB));
@@ -693,8 +701,8 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
             }
             if (ok) {
                 ttx_cdfseg *dt; int *dn_;
-                rc = dev_alloc(h, &dt, tab.size()); if (rc) { ttx_destroy(h); return rc; }
-                rc = dev_alloc(h, &dn_, ns.size()); if (rc) { ttx_destroy(h); return rc; }
+                A_(dev_alloc(h, &dt, tab.size()));
+                A_(dev_alloc(h, &dn_, ns.size()));
                 HIPCHECK(hipMemcpy(dt, tab.data(), sizeof(ttx_cdfseg) * tab.size(), hipMemcpyHostToDevice));
                 HIPCHECK(hipMemcpy(dn_, ns.data(), sizeof(int) * ns.size(), hipMemcpyHostToDevice));
                 P.cdf_tab = dt; P.cdf_ns = dn_; P.cdf_kmax = kmax;
@@ -738,9 +746,7 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
         // a cluster of NB 256-thread workgroups per group, all resident at once (G*NB <= number of CUs)
         hipDeviceProp_t prop;
         HIPCHECK(hipGetDeviceProperties(&prop, cfg->device));
-        int NB = 8;
-        if (const char *e = getenv("TTX_CLUSTER_NB")) NB = atoi(e);
-        NB = std::max(1, std::min(NB, TTX_CLMAX));
+        int NB = std::max(1, std::min(env_int("TTX_CLUSTER_NB", 8), TTX_CLMAX));
         while (NB > 1 && h->G * NB > prop.multiProcessorCount / 2) NB--;        // leave room for other processes on the card
         const size_t SL = (size_t)RM * ((NM + NB - 1) / NB + 1);
         h->lds_cluster = sizeof(double) * (cfg->npar + 4 + 2 * RM * (2 * VS + 2) + 4 * SL + 2 * RM + 8) + sizeof(int) * 4 * (nlotmax + 4);
@@ -753,12 +759,12 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
         // (f_ising_c4w) where the pad is neutral -- every node in [0,1], so that no running product overflows (inf * 0.0 is NaN) --
         // unless TTX_CL_PAD=0 asks for the predicated remainders (f_ising_c4p), which hold for any node (ttx_cluster_eval tells)
         const bool cfastc = h->want_fast && cfg->fun_id == TTX_FUN_ISING && P.ising_id == 1;
-        if (const char *e = getenv("TTX_CL_PAD")) if (strcmp(e, "0") && strcmp(e, "1")) { ttx_destroy(h); return fail(TTX_EINVAL, "TTX_CL_PAD must be 0 or 1 (got %s)", e); }
-        h->cluster_var = cfastc ? 2 : (h->unit_nodes && !(getenv("TTX_CL_PAD") && atoi(getenv("TTX_CL_PAD")) == 0)) ? 1 : 0;
+        if (const char *e = getenv("TTX_CL_PAD")) if (strcmp(e, "0") && strcmp(e, "1")) return fail(TTX_EINVAL, "TTX_CL_PAD must be 0 or 1 (got %s)", e);
+        h->cluster_var = cfastc ? 2 : (h->unit_nodes && !env_off("TTX_CL_PAD")) ? 1 : 0;
         bool cluster_ok = fastc && h->RM <= 64 && NB >= 2 && h->G * NB <= prop.multiProcessorCount && h->lds_cluster <= 150 * 1024;
         if (cluster_ok) {
             // residency: what the device can hold of THIS kernel with THIS much dynamic LDS; the grid may use half of it
-            if ((rc = ensure_lds_cluster(h))) { ttx_destroy(h); return rc; }
+            A_(ensure_lds_cluster(h));
             int occ = 0;
             HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cluster_kernel(h->cluster_var), CB, h->lds_cluster));
             const long long cap = (long long)occ * prop.multiProcessorCount;
@@ -769,61 +775,60 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
             // plain launch by default: with the occupancy gate above every workgroup is placed as soon as the launch starts;
             // the cooperative launch (TTX_CLUSTER_COOP=1) adds the runtime's own refusal of oversized grids but costs
             // ~30 us per launch on this stack (C_64: 5.28 -> 5.80 ms per run, measured)
-            h->cluster_coop = coop && getenv("TTX_CLUSTER_COOP") && atoi(getenv("TTX_CLUSTER_COOP")) == 1;
+            h->cluster_coop = coop && env_int("TTX_CLUSTER_COOP", 0) == 1;
         }
         if (want == "cluster") { if (cluster_ok) h->cluster = NB; }
         else if (want == "fused") { if (fused_ok) h->fused = 1; }
         else if (want == "auto") { if (cluster_ok) h->cluster = NB; else if (fused_ok && h->G == 1) h->fused = 1; }
-        else if (want != "chain") { ttx_destroy(h); return fail(TTX_EINVAL, "TTX_SWEEP must be auto, chain, fused or cluster (got %s)", want.c_str()); }
+        else if (want != "chain") return fail(TTX_EINVAL, "TTX_SWEEP must be auto, chain, fused or cluster (got %s)", want.c_str());
         // TTX_ARITH=fast for Ising C: a closed form inside the cluster kernel (f_ising_cfast); the other paths evaluate C exactly
         if (h->cluster && cfastc) P.arith = 1;
         if (h->cluster) {
             unsigned *ctr; ClPart *cp;
-            rc = dev_alloc(h, &ctr, (size_t)h->G); if (rc) { ttx_destroy(h); return rc; }
-            rc = dev_alloc(h, &cp, (size_t)2 * h->G * TTX_CLREC); if (rc) { ttx_destroy(h); return rc; }
+            A_(dev_alloc(h, &ctr, (size_t)h->G));
+            A_(dev_alloc(h, &cp, (size_t)2 * h->G * TTX_CLREC));
             P.cl_ctr = ctr; P.cl_part = cp;
 #ifdef TTX_STAMPS
-            if (getenv("TTX_DBG_WAVES")) { long long *dbg; rc = dev_alloc(h, &dbg, (size_t)8 * 64 * 8); if (rc) { ttx_destroy(h); return rc; } P.dbg = dbg; }
+            if (getenv("TTX_DBG_WAVES")) { long long *dbg; A_(dev_alloc(h, &dbg, (size_t)8 * 64 * 8)); P.dbg = dbg; }
 #endif
             HIPCHECK(hipHostMalloc((void **)&h->h_abort, sizeof(int)));
             *h->h_abort = 0;
             P.cl_abort = h->h_abort;
-            if (const char *e = getenv("TTX_CLUSTER_TEST_ABORT")) P.cl_test_abort = atoi(e);
+            P.cl_test_abort = env_int("TTX_CLUSTER_TEST_ABORT", P.cl_test_abort);
         }
     }
-    if (h->lds_half > 160 * 1024 || h->lds_lot > 120 * 1024) { ttx_destroy(h); return fail(TTX_EINVAL, "problem too large for LDS staging (d*maxrank)"); }
+    if (h->lds_half > 160 * 1024 || h->lds_lot > 120 * 1024) return fail(TTX_EINVAL, "problem too large for LDS staging (d*maxrank)");
     {   // lottery: one wave of candidates per workgroup where one evaluation is a long dependent chain (Ising D/E, mvn)
-        const bool heavy = (cfg->fun_id == TTX_FUN_ISING && P.ising_id != 1) || cfg->fun_id == TTX_FUN_MVN;
+        const bool heavy = isDE || cfg->fun_id == TTX_FUN_MVN;
         const int nlotmax = 2 * h->RM + 2 * NM;
         P.lot_nb = 1;
-        if (heavy && !(getenv("TTX_LOTTERY_NB") && atoi(getenv("TTX_LOTTERY_NB")) == 1)) P.lot_nb = std::min((nlotmax + 63) / 64, 64);
+        if (heavy && env_int("TTX_LOTTERY_NB", 0) != 1) P.lot_nb = std::min((nlotmax + 63) / 64, 64);
         if (P.lot_nb > 1 && (nlotmax + P.lot_nb - 1) / P.lot_nb > 64) P.lot_nb = 1;      // more candidates than 64 blocks x 64: keep one block
         LotPart *lp; unsigned *lc;
-        rc = dev_alloc(h, &lp, (size_t)h->G * P.lot_nb); if (rc) { ttx_destroy(h); return rc; }
-        rc = dev_alloc(h, &lc, (size_t)h->G); if (rc) { ttx_destroy(h); return rc; }
+        A_(dev_alloc(h, &lp, (size_t)h->G * P.lot_nb));
+        A_(dev_alloc(h, &lc, (size_t)h->G));
         P.lotp = lp; P.lot_ctr = lc;
         P.lot_max = nlotmax;
-        if (cfg->fun_id == TTX_FUN_MVN && d <= 64 * MVN_MAXQ && cfg->pivoting >= 0 && (int)RM * ((NM + 63) / 64) <= TTX_MAXPART &&
-            !(getenv("TTX_MVN_V2") && atoi(getenv("TTX_MVN_V2")) == 0)) {
+        if (cfg->fun_id == TTX_FUN_MVN && d <= 64 * MVN_MAXQ && cfg->pivoting >= 0 && (int)RM * ((NM + 63) / 64) <= TTX_MAXPART && !env_off("TTX_MVN_V2")) {
             int *lcd; double *lf;
-            rc = dev_alloc(h, &lcd, (size_t)h->G * nlotmax * 4); if (rc) { ttx_destroy(h); return rc; }
-            rc = dev_alloc(h, &lf, (size_t)h->G * nlotmax); if (rc) { ttx_destroy(h); return rc; }
+            A_(dev_alloc(h, &lcd, (size_t)h->G * nlotmax * 4));
+            A_(dev_alloc(h, &lf, (size_t)h->G * nlotmax));
             P.lotc = lcd; P.lotf = lf;
             h->mvn_v2 = 1; h->de_slots = (int)RM * ((NM + 63) / 64);
             P.bnd_wave = 1;
             h->lds_mvn = sizeof(double) * (3 * (size_t)d + 8);
         }
-        if (cfg->fun_id == TTX_FUN_ISING && P.ising_id != 1 && P.arith) P.bnd_wave = 1;     // boundary corners by de_fast_point_wave
-        if (cfg->fun_id == TTX_FUN_ISING && P.ising_id != 1 && P.deTL) {
+        if (isDE && P.arith) P.bnd_wave = 1;     // boundary corners by de_fast_point_wave
+        if (isDE && P.deTL) {
             int *lcd; double *lf;
-            rc = dev_alloc(h, &lcd, (size_t)h->G * nlotmax * 4); if (rc) { ttx_destroy(h); return rc; }
-            rc = dev_alloc(h, &lf, (size_t)h->G * nlotmax); if (rc) { ttx_destroy(h); return rc; }
+            A_(dev_alloc(h, &lcd, (size_t)h->G * nlotmax * 4));
+            A_(dev_alloc(h, &lf, (size_t)h->G * nlotmax));
             P.lotc = lcd; P.lotf = lf;
             // candidates and boundary corners by the row-wise wave evaluator (ttx_de.h); TTX_LOTTERY_WAVE=0: one lane per element
             h->lds_der = sizeof(double) * de_rows_lds_doubles(d);
-            h->lot_wave = h->de_v2 && !P.de_cut && h->lds_der <= 150 * 1024 && !(getenv("TTX_LOTTERY_WAVE") && atoi(getenv("TTX_LOTTERY_WAVE")) == 0);
+            h->lot_wave = h->de_v2 && !P.de_cut && h->lds_der <= 150 * 1024 && !env_off("TTX_LOTTERY_WAVE");
             P.bnd_wave = h->lot_wave || (P.de_cut && h->de_v2 && h->lds_der <= 150 * 1024);    // boundary corners by one wave per corner
-            h->lot_rows = h->lot_wave ? ((getenv("TTX_LOTTERY_ROWS") && atoi(getenv("TTX_LOTTERY_ROWS")) == 2) ? 2 : 1) : 0;
+            h->lot_rows = h->lot_wave ? (env_int("TTX_LOTTERY_ROWS", 0) == 2 ? 2 : 1) : 0;
         }
     }
     if (cfg->fun_id == TTX_FUN_HOST || cfg->fun_id == TTX_FUN_COSCOEFF || cfg->fun_id == TTX_FUN_DEVICE) {
@@ -836,7 +841,7 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
         if (cfg->fun_id == TTX_FUN_COSCOEFF || cfg->fun_id == TTX_FUN_DEVICE) {
             // device slots (zero-filled, owned by allocs): the evaluator runs on the stream between the two passes
             P.slot_dev = 1;
-            if ((rc = dev_alloc(h, &P.hidx, nslot * d)) || (rc = dev_alloc(h, &P.hval, nslot)) || (rc = dev_alloc(h, &P.hreq, nslot))) { ttx_destroy(h); return rc; }
+            A_(dev_alloc(h, &P.hidx, nslot * d)); A_(dev_alloc(h, &P.hval, nslot)); A_(dev_alloc(h, &P.hreq, nslot));
         } else {
         HIPCHECK(hipHostMalloc((void **)&P.hidx, sizeof(short) * nslot * d));
         HIPCHECK(hipHostMalloc((void **)&P.hval, sizeof(double) * nslot));
@@ -845,6 +850,8 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
         }
         P.HS = (int)h->HS; P.hostpass = 0;
     }
+#undef A_
+    guard.h = nullptr;
     *out = h;
     return TTX_OK;
 }
@@ -1457,35 +1464,145 @@ static std::vector<int32_t> rank0_view(ttx_engine *h, int it)
     return r;
 }
 
-// quadrature of the current cores: per-core matrices, per-group chains, gather over GPUs, tree
-static int launch_quad(ttx_engine *h, int mode, const double *w)
+// dynamic LDS of the kernels that update the persistent tables of the fast arithmetic next to their own work
+static inline size_t lds_fpersist(const DevProb &P) { return (P.arith && P.fpersist) ? sizeof(double) * 4 * (P.d + 8) : 0; }
+
+// quadrature of the cores as Q sees them, with the weights w, on the stream sq: per-core matrices, per-group chains, gather over
+// GPUs, tree (the gather travels on the engine's stream: with several processes sq is that stream)
+static int launch_quad(ttx_engine *h, hipStream_t sq, const DevProb &Q, int mode, const double *w)
 {
-    DevProb &P = h->P;
     const size_t lds_q = sizeof(double) * ((size_t)h->RM * h->RM + 2);
-    hipLaunchKernelGGL(k_quad_build, dim3(h->NC, h->G), dim3(256), lds_q, h->stream, P, mode, w);
-    hipLaunchKernelGGL(k_quad_chain, dim3(h->G), dim3(256), P.qscr ? 0 : 2 * lds_q, h->stream, P);
+    hipLaunchKernelGGL(k_quad_build, dim3(h->NC, h->G), dim3(256), lds_q, sq, Q, mode, w);
+    hipLaunchKernelGGL(k_quad_chain, dim3(h->G), dim3(256), Q.qscr ? 0 : 2 * lds_q, sq, Q);
     if (h->cfg.nproc > 1) {
-        int rc = allreduce_dev(h, P.qsend, P.qall, h->QB, 0);
+        int rc = allreduce_dev(h, Q.qsend, Q.qall, h->QB, 0);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_quad_tree, dim3(1), dim3(256), 0, h->stream, P);
+        hipLaunchKernelGGL(k_quad_tree, dim3(1), dim3(256), 0, sq, Q);
     }
     return TTX_OK;
 }
 
-// raise a kernel's dynamic-LDS ceiling to `need` bytes if no earlier launch asked for as much (`cur`: the caller's record)
-static int ensure_lds(const void *fn, size_t need, size_t &cur)
+// ---- the launch plan of the chain path -------------------------------------------------------------------------------------------
+// One launch: the kernel, its source name with the template arguments that select behaviour (ttx_plan_describe), its shape, its
+// dynamic LDS, and whether that LDS can exceed the default ceiling (the plan's builder then raises it, ensure_lds).
+struct KLaunch {
+    const void *fn = nullptr; const char *name = "-"; dim3 grid, block; size_t lds = 0; bool raise = false;
+    explicit operator bool() const { return fn != nullptr; }
+};
+template <class F>
+static KLaunch kl(F *fn, const char *name, dim3 grid, dim3 block, size_t lds, bool raise = false)
 {
-    if (need <= cur) return TTX_OK;
-    HIPCHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-    cur = need;
-    return TTX_OK;
+    KLaunch k; k.fn = reinterpret_cast<const void *>(fn); k.name = name; k.grid = grid; k.block = block; k.lds = lds; k.raise = raise;
+    return k;
 }
-
-static int ensure_lds_cluster(ttx_engine *h)
+// the arguments exactly as the kernel declares them (a DevProb, then ints); like a <<< >>> launch, an error is left to the next hipGetLastError
+template <class... A>
+static void launch(hipStream_t st, const KLaunch &k, const A &...a)
 {
-    static size_t a_cluster[3] = {0, 0, 0};        // per instantiation
-    return ensure_lds(reinterpret_cast<const void *>(cluster_kernel(h->cluster_var)), h->lds_cluster, a_cluster[h->cluster_var]);
+    static_assert(((std::is_same<A, DevProb>::value || std::is_same<A, int>::value) && ...), "the chain kernels take a DevProb and ints");
+    void *args[] = {(void *)&a...};
+    (void)hipLaunchKernel(k.fn, k.grid, k.block, args, k.lds, st);
 }
+// What one run of the chain path launches per bond step, decided once from the engine's flags (chain_plan): the one place a kernel
+// variant is wired in.  Built per run, because a fallback of ttx_run can retire the teams, the relay or the cluster path in between.
+struct ChainPlan {
+    KLaunch tables;                     // before the lottery: k_de_ctables, k_de_tables, k_fast_tables<FUN>, or none
+    KLaunch lottery, lot_eval;          // one k_lottery<FUN> launch; with lot_eval: drawing launch, candidate evaluator, scoring launch
+    int lot_vals = 0;
+    struct Tier { KLaunch k; int upto = 0; };   // before the last tier: a grid of the sweep's units, taken while units * G <= upto
+    Tier half[3]; int ntier = 0;        // the half-step: the first tier that applies; the last one always does
+    int half_vals = -1;                 // the fifth argument of k_halfstep<FUN>; -1: the tiers' kernels take four
+    KLaunch base; int base_vals = 0;    // k_halfstep<FUN>: full pivoting goes through it whatever the tiers are
+    enum { FP_PLAIN, FP_MFMA, FP_COLUMNS } fullpiv = FP_PLAIN;      // piv = -1: all columns at once, dense MFMA, or one column per host pass
+    KLaunch accept, init_samples, init_fibers, exch_boundary, fin_luar, fin_lual;
+    int nfb = 0, srows = 0, fl = 0;
+    std::vector<const KLaunch *> all() const
+    {
+        std::vector<const KLaunch *> v = {&tables, &lottery, &lot_eval, &base, &accept, &init_samples, &init_fibers, &exch_boundary, &fin_luar, &fin_lual};
+        for (int t = 0; t < ntier; t++) v.push_back(&half[t].k);
+        return v;
+    }
+};
+#define KFUN_(k) (FUN == FUN_ISING ? #k "<ISING>" : FUN == FUN_STDNORM ? #k "<STDNORM>" : FUN == FUN_MVN ? #k "<MVN>" : #k "<HOST>")
+#define KUNIT_(k, ...) (P.de_unit ? kl(k<true>, #k "<true>", __VA_ARGS__) : kl(k<false>, #k "<false>", __VA_ARGS__))
+#define KUNIT2_(k, x, ...) (P.de_unit ? kl(k<true, x>, #k "<true," #x ">", __VA_ARGS__) : kl(k<false, x>, #k "<false," #x ">", __VA_ARGS__))
+template <int FUN>
+static ChainPlan chain_plan(const ttx_engine *h)
+{
+    const DevProb &P = h->P;
+    const int d = h->d, G = h->G, RM = h->RM, NM = h->NM, nproc = h->cfg.nproc;
+    const bool isDE = FUN == FUN_ISING && P.ising_id != 1;
+    const bool fastk = P.arith && (FUN == FUN_MVN || isDE);         // TTX_ARITH=fast with a re-associated evaluator (ttx_fast.h)
+    const size_t VS = ((d + 7) & ~7) + 8;
+    ChainPlan p;
+    p.nfb = (RM * NM + TTX_BLK - 1) / TTX_BLK;
+    p.base = kl(k_halfstep<FUN>, KFUN_(k_halfstep), dim3(p.nfb, G), dim3(TTX_BLK), h->lds_half, true);
+    p.base_vals = fastk ? 0 : h->half_vals;
+    p.lottery = kl(k_lottery<FUN>, "k_lottery", dim3(P.lot_nb, G), dim3(P.lot_nb == 1 ? 512 : 256), h->lds_lot, true);
+    p.lot_vals = fastk ? h->fast_cap : h->lot_vals;
+    // the Ising D/E kernels of ttx_de.h, by the division they use (de_unit: the short sequence for nodes in [0,1])
+    const dim3 slots(h->de_slots, G), cand(P.lot_max, G), cand4((P.lot_max + 3) / 4, G);
+    const KLaunch de = KUNIT_(k_halfstep_de, slots, dim3(64), h->lds_de, true);
+    const KLaunch det3 = KUNIT2_(k_halfstep_det, 3, dim3(1, G), dim3(64 * 14), h->lds_det, true);
+    const KLaunch det1 = KUNIT2_(k_halfstep_det, 1, dim3(1, G), dim3(64 * 6), h->lds_det6, true);
+    const KLaunch de5 = KUNIT_(k_halfstep_de5, slots, dim3(64 * DE5_W), h->lds_de5, true);
+    const KLaunch rows = KUNIT2_(k_lottery_eval_de_rows, false, cand4, dim3(64), h->lds_der, true);
+    const KLaunch rows_tab = KUNIT2_(k_lottery_eval_de_rows, true, cand4, dim3(64), h->lds_der, true);
+    // lottery candidates by one wave each between the drawing and the scoring launch: mvn; D/E with compact tables, row-parallel
+    // without tables up to d = 160 (measured: 23 % less lottery time at D_64, even at D_256), from the tables beyond
+    // (TTX_DE_LOT_POINT=0/1 forces one); D/E with full tables four candidates per wave (TTX_LOTTERY_ROWS=2: with the pivots' factor
+    // tables, measured slower: HBM latency)
+    if (fastk) p.lot_eval = KLaunch();
+    else if (FUN == FUN_MVN && h->mvn_v2) p.lot_eval = kl(k_lottery_eval_mvn, "k_lottery_eval_mvn", cand, dim3(64), h->lds_mvn);
+    else if (FUN == FUN_ISING && P.de_cut && h->de_v2 && P.lotc)
+        p.lot_eval = h->de_lot_point ? kl(k_lottery_eval_decp, "k_lottery_eval_decp", cand, dim3(64), sizeof(double) * (2 * (size_t)(d + 64) + 2048), true)
+                                     : kl(k_lottery_eval_dec, "k_lottery_eval_dec", cand, dim3(64), h->lds_de, true);
+    else if (FUN == FUN_ISING && h->lot_wave) p.lot_eval = h->lot_rows == 2 ? rows_tab : rows;
+    if (p.lot_eval) { p.lottery.grid = dim3(1, G); p.lottery.block = dim3(512); }
+    // half-step.  D/E with full tables: while the ranks are small (at most it + 1 during sweep it) a unit gets a team of 14 waves on
+    // a CU of its own, up to de_team6_units a team of 6 waves (three such teams fit a CU), beyond that one wave -- or a relay of four
+    if (fastk) { p.half[p.ntier++].k = p.base; p.half_vals = 0; }
+    else if (FUN == FUN_MVN && h->mvn_v2) p.half[p.ntier++].k = kl(k_halfstep_mvn, "k_halfstep_mvn", slots, dim3(64), h->lds_mvn);
+    else if (FUN == FUN_ISING && h->de_v2) {
+        if (h->de_team && !h->de_v5) { p.half[p.ntier++] = {det3, h->de_team_units}; p.half[p.ntier++] = {det1, h->de_team6_units}; }
+        p.half[p.ntier++].k = h->de_v5 ? de5 : P.de_cut ? kl(k_halfstep_dec, "k_halfstep_dec", slots, dim3(64), h->lds_de, true) : de;
+    } else { p.half[p.ntier++].k = p.base; p.half_vals = h->half_vals; }
+    p.fullpiv = FUN == FUN_HOST ? ChainPlan::FP_COLUMNS : P.fp_mfma ? ChainPlan::FP_MFMA : ChainPlan::FP_PLAIN;
+    // roles A/B of k_accept: x[RM]; C/D: the staged LU
+    p.accept = kl(k_accept, "k_accept", dim3(2 * p.nfb + 2 * NM + 1, G), dim3(TTX_BLK), sizeof(double) * std::max<size_t>(RM + 2, (size_t)std::min<int>(RM, 64) * std::min<int>(RM, 64)));
+    {   // initial samples: index rows in LDS where they fit
+        const size_t lds_s = h->lds_par + 16 + sizeof(short) * 256 * VS;
+        p.srows = lds_s <= 150 * 1024 ? 1 : 0;
+        p.init_samples = kl(k_init_samples<FUN>, KFUN_(k_init_samples), dim3(G), dim3(256), p.srows ? lds_s : h->lds_par, p.srows != 0);
+        p.init_fibers = kl(k_init_fibers<FUN>, KFUN_(k_init_fibers), dim3(h->NC, G), dim3(256), h->lds_par);
+    }
+    // before a bond step's lottery.  Ising D/E: pair factors of the bond that do not span it (shared by all elements through a pivot),
+    // compact where the nodes allow the unit cut; TTX_ARITH=fast, mvn with TTX_FAST_PERSIST=0: the per-pivot tables of the bond step
+    // (Ising D/E keeps its fast tables per bond)
+    if (P.deTL) p.tables = P.de_cut ? kl(k_de_ctables, "k_de_ctables", dim3(2 * RM, G), dim3(256), sizeof(double) * (size_t)(d + 2))
+                                    : kl(k_de_tables, "k_de_tables", dim3((2 * (d + 1) * RM + 255) / 256, G), dim3(256), 0);
+    else if (fastk && !P.fpersist) p.tables = kl(k_fast_tables<FUN>, KFUN_(k_fast_tables), dim3(2 * RM, G), dim3(64), sizeof(double) * 2 * (d + 8));
+    if (nproc > 1) {    // boundary corners; D/E: two value rows; mvn: 3 d + 1 doubles
+        const size_t lds_b = h->lds_par + 16 + sizeof(short) * 2 * VS + sizeof(double) * (64 * 64 + 4) +
+                             (P.bnd_wave ? sizeof(double) * (std::max<size_t>(2 * (size_t)de_rows_stride(d), 3 * (size_t)d + 2) + 8 + (P.de_cut ? 64 * 32 : 0)) : 0);
+        p.exch_boundary = kl(k_exch_boundary<FUN>, KFUN_(k_exch_boundary), dim3(2 * NM, G), dim3(TTX_BLK), lds_b, true);
+    }
+    {   // finalisation.  Threads (= columns) per workgroup: as many as fit the LDS next to the LU panel (256, 128 or 64); the columns
+        // of a core are spread over grid.z (at maxrank 64 the 256-thread staging did not fit: the kernels then ran out of L2 with one
+        // workgroup per core, 6 ms at D_256)
+        int ft = 256;
+        while (ft > 64 && sizeof(double) * ((size_t)RM * RM + (size_t)ft * RM) > 96 * 1024) ft >>= 1;
+        const size_t lds_f = sizeof(double) * ((size_t)RM * RM + (size_t)ft * RM);
+        p.fl = lds_f <= 150 * 1024 ? 1 : 0;
+        const dim3 gr(h->NC, G, std::max(1, std::min(64, (NM * RM + ft - 1) / ft)));
+        p.fin_luar = kl(k_fin_luar, "k_fin_luar", gr, dim3(ft), p.fl ? lds_f : 0, p.fl != 0);
+        p.fin_lual = kl(k_fin_lual, "k_fin_lual", gr, dim3(ft), p.fl ? lds_f : 0, p.fl != 0);
+    }
+    return p;
+}
+#undef KFUN_
+#undef KUNIT_
+#undef KUNIT2_
 
 // the whole-sweep cluster kernel: cooperative launch (the runtime guarantees -- or refuses -- co-residency of the grid)
 static int launch_cluster(ttx_engine *h, int dir, int epoch)
@@ -1513,45 +1630,20 @@ static int run_impl(ttx_engine *h)
     h->recs.clear(); h->tapes.clear();
     int rc;
 
-    // kernels that may stage more than the default 64 KB of dynamic LDS (160 KB per CU on gfx950)
-    {   // the dynamic-LDS ceiling is a property of the FUNCTION: raise it when an engine needs more than any before it
-        static size_t a_half = 0, a_lot = 0, a_fused = 0;        // per instantiation (FUN) of this template
-        if ((rc = ensure_lds(reinterpret_cast<const void *>(k_halfstep<FUN>), h->lds_half, a_half))) return rc;
-        if ((rc = ensure_lds(reinterpret_cast<const void *>(k_lottery<FUN>), h->lds_lot, a_lot))) return rc;
-        if (h->fused && (rc = ensure_lds(reinterpret_cast<const void *>(k_sweep_fused), h->lds_fused, a_fused))) return rc;
-        if (h->cluster && (rc = ensure_lds_cluster(h))) return rc;
-        static size_t a_de0 = 0, a_de1 = 0;
-        static size_t a_dec = 0;
-        static size_t a_dlc = 0, a_dlp = 0;
-        if (h->de_v2 && P.de_cut && ((rc = ensure_lds(reinterpret_cast<const void *>(k_halfstep_dec), h->lds_de, a_dec)) ||
-                                     (rc = ensure_lds(reinterpret_cast<const void *>(k_lottery_eval_dec), h->lds_de, a_dlc)) ||
-                                     (rc = ensure_lds(reinterpret_cast<const void *>(k_lottery_eval_decp), sizeof(double) * (2 * (size_t)(d + 64) + 2048), a_dlp)))) return rc;
-        if (h->de_v2 && ((rc = ensure_lds(reinterpret_cast<const void *>(k_halfstep_de<true>), h->lds_de, a_de0)) ||
-                         (rc = ensure_lds(reinterpret_cast<const void *>(k_halfstep_de<false>), h->lds_de, a_de1)))) return rc;
-        static size_t a_dt0 = 0, a_dt1 = 0;
-        if (h->de_team && ((rc = ensure_lds(reinterpret_cast<const void *>(k_halfstep_det<true, 3>), h->lds_det, a_dt0)) ||
-                           (rc = ensure_lds(reinterpret_cast<const void *>(k_halfstep_det<false, 3>), h->lds_det, a_dt1)))) return rc;
-        static size_t a_dt2 = 0, a_dt3 = 0;
-        if (h->de_team && ((rc = ensure_lds(reinterpret_cast<const void *>(k_halfstep_det<true, 1>), h->lds_det6, a_dt2)) ||
-                           (rc = ensure_lds(reinterpret_cast<const void *>(k_halfstep_det<false, 1>), h->lds_det6, a_dt3)))) return rc;
-        static size_t a_d50 = 0, a_d51 = 0;
-        if (h->de_v5 && ((rc = ensure_lds(reinterpret_cast<const void *>(k_halfstep_de5<true>), h->lds_de5, a_d50)) ||
-                         (rc = ensure_lds(reinterpret_cast<const void *>(k_halfstep_de5<false>), h->lds_de5, a_d51)))) return rc;
-        static size_t a_lr0 = 0, a_lr1 = 0;
-        static size_t a_lr2 = 0, a_lr3 = 0;
-        if (h->lot_rows && ((rc = ensure_lds(reinterpret_cast<const void *>(k_lottery_eval_de_rows<true, false>), h->lds_der, a_lr0)) ||
-                            (rc = ensure_lds(reinterpret_cast<const void *>(k_lottery_eval_de_rows<false, false>), h->lds_der, a_lr1)) ||
-                            (rc = ensure_lds(reinterpret_cast<const void *>(k_lottery_eval_de_rows<true, true>), h->lds_der, a_lr2)) ||
-                            (rc = ensure_lds(reinterpret_cast<const void *>(k_lottery_eval_de_rows<false, true>), h->lds_der, a_lr3)))) return rc;
-    }
+    // what this run launches on the chain path; its kernels, and the whole-sweep kernel where one is used, may stage more than the
+    // default 64 KB of dynamic LDS (160 KB per CU on gfx950)
+    const ChainPlan plan = chain_plan<FUN>(h);
+    for (const KLaunch *k : plan.all()) if (k->raise && (rc = ensure_lds(h, k->fn, k->lds))) return rc;
+    if (h->fused && (rc = ensure_lds(h, reinterpret_cast<const void *>(k_sweep_fused), h->lds_fused))) return rc;
+    if (h->cluster && (rc = ensure_lds_cluster(h))) return rc;
     if (h->cluster) *h->h_abort = 0;
     // an evaluating kernel: once with the device integrand; with a host integrand twice around the host's calls
-    auto EV = [&](auto &&launch) -> int {
-        if (FUN != FUN_HOST) { launch(P); return TTX_OK; }
+    auto EV = [&](const KLaunch &k, auto... a) -> int {
+        if (FUN != FUN_HOST) { launch(st, k, P, a...); return TTX_OK; }
         DevProb Q = P;
-        Q.hostpass = 1; launch(Q);
+        Q.hostpass = 1; launch(st, k, Q, a...);
         if (int rc_ = slot_eval(h)) return rc_;
-        Q.hostpass = 2; launch(Q);
+        Q.hostpass = 2; launch(st, k, Q, a...);
         return TTX_OK;
     };
     // ---- reset state (lib/dmrgg.f90:96-100, 141-148, 279-288) ----
@@ -1562,13 +1654,9 @@ static int run_impl(ttx_engine *h)
     for (int k = 2; k <= d; k++) nn = std::min(nn, h->n1[k]);
     {
         KScope ks(h, TTX_K_OTHER, 4);
-        const size_t lds_s = h->lds_par + 16 + sizeof(short) * 256 * (size_t)(((d + 7) & ~7) + 8);
-        const int srows = lds_s <= 150 * 1024 ? 1 : 0;
-        static size_t a_samp = 0;
-        if (srows && (rc = ensure_lds(reinterpret_cast<const void *>(k_init_samples<FUN>), lds_s, a_samp))) return rc;
-        if ((rc = EV([&](const DevProb &Q) { hipLaunchKernelGGL(k_init_samples<FUN>, dim3(G), dim3(256), srows ? lds_s : h->lds_par, st, Q, snum, nn, FUN == FUN_HOST ? 0 : srows, 0); }))) return rc;
-        if ((rc = EV([&](const DevProb &Q) { hipLaunchKernelGGL(k_init_fibers<FUN>, dim3(h->NC, G), dim3(256), h->lds_par, st, Q); }))) return rc;
-        hipLaunchKernelGGL(k_init_factors, dim3(h->NC, G), dim3(256), (P.arith && P.fpersist) ? sizeof(double) * 4 * (d + 8) : 0, st, P);
+        if ((rc = EV(plan.init_samples, snum, nn, FUN == FUN_HOST ? 0 : plan.srows, 0))) return rc;
+        if ((rc = EV(plan.init_fibers))) return rc;
+        hipLaunchKernelGGL(k_init_factors, dim3(h->NC, G), dim3(256), lds_fpersist(P), st, P);
         hipLaunchKernelGGL(k_init_final, dim3(G), dim3(256), 0, st, P);
     }
     // Single-process whole-sweep path: the first sweep kernel is enqueued right behind the initial cross, and the host
@@ -1604,8 +1692,6 @@ static int run_impl(ttx_engine *h)
     // ---- main loop (:309-1020) ----
     int it = 0, strike = 0;
     bool ready = (it + 1 >= h->cfg.maxrank);
-    const int nfb = (h->RM * h->NM + TTX_BLK - 1) / TTX_BLK;
-    const size_t lds_acc = sizeof(double) * std::max<size_t>(h->RM + 2, (size_t)std::min<int>(h->RM, 64) * std::min<int>(h->RM, 64));   // roles A/B: x[RM]; C/D: the staged LU
     // Pipelined mode (whole-sweep kernels, one process): the stopping rule also runs on the device (k_sweep_end), so
     // sweep it+1 is enqueued BEFORE the host has read the summary of sweep it -- the GPU never waits for the host.  When the rule fires, the one sweep that is already enqueued finds the stop flag and does nothing.
     // On a single GPU the per-sweep quadrature (only reported, never fed back) runs on its own stream next to the
@@ -1613,7 +1699,7 @@ static int run_impl(ttx_engine *h)
     // With several processes the exchange and the summary travel by stream-ordered collectives (RCCL, or the host transport's
     // host functions), so the same loop applies; only the fork of the quadrature is single-process (one communicator must
     // not be driven from two streams at once).
-    const bool pipe = (h->cluster || h->fused) && !h->profile && !(getenv("TTX_PIPELINE") && atoi(getenv("TTX_PIPELINE")) == 0);
+    const bool pipe = (h->cluster || h->fused) && !h->profile && !env_off("TTX_PIPELINE");
     const bool forkq = pipe && P.has_quad && h->W == 1;
     DevProb Pq = P;
     if (pipe) Pq.r = P.rq;
@@ -1629,112 +1715,60 @@ static int run_impl(ttx_engine *h)
             KScope ks(h, TTX_K_HALFSTEP, 1);
             hipLaunchKernelGGL(k_sweep_fused, dim3(G), dim3(FB), h->lds_fused, st, P, dir, h->nbmax);
         }
+        // the ranks are at most it_ + 1 in sweep it_: the units of a team half-step, and the columns of full pivoting by host passes
+        const int rb = std::min((int)h->RM, it_ + 1);
+        const int units = (h->de_test_fault && it_ == h->de_test_fault) ? 1 : rb * ((h->NM + 63) / 64);
+        KLaunch half = plan.half[plan.ntier - 1].k;
+        for (int t = plan.ntier - 2; t >= 0; t--) if (units * G <= plan.half[t].upto) { half = plan.half[t].k; half.grid.x = units; }
         for (int pp = 1; pp <= h->nbmax && !h->fused && !h->cluster; pp++) {
-            if (P.deTL) {   // Ising D/E: pair factors of this bond that do not span it (shared by all elements through a pivot)
-                KScope ks(h, TTX_K_OTHER);
-                if (P.de_cut) hipLaunchKernelGGL(k_de_ctables, dim3(2 * h->RM, G), dim3(256), sizeof(double) * (size_t)(d + 2), st, P, dir, pp);
-                else hipLaunchKernelGGL(k_de_tables, dim3((2 * (d + 1) * h->RM + 255) / 256, G), dim3(256), 0, st, P, dir, pp);
-            }
-            const bool fastk = P.arith && (FUN == FUN_MVN || (FUN == FUN_ISING && P.ising_id != 1));
-            if (fastk && !P.fpersist) {    // TTX_ARITH=fast, mvn: per-pivot tables of this bond step (ttx_fast.h; Ising D/E keeps its tables per bond)
-                KScope ks(h, TTX_K_OTHER);
-                hipLaunchKernelGGL(k_fast_tables<FUN>, dim3(2 * h->RM, G), dim3(64), sizeof(double) * 2 * (d + 8), st, P, dir, pp);
-            }
+            if (plan.tables) { KScope ks(h, TTX_K_OTHER); launch(st, plan.tables, P, dir, pp); }
             if (h->cfg.pivoting >= 0) {
-                if (fastk) {
-                    KScope ks(h, TTX_K_LOTTERY);
-                    hipLaunchKernelGGL(k_lottery<FUN>, dim3(P.lot_nb, G), dim3(P.lot_nb == 1 ? 512 : 256), h->lds_lot, st, P, dir, pp, h->fast_cap, 0);
-                } else if (FUN == FUN_MVN && h->mvn_v2) {
+                if (plan.lot_eval) {
                     KScope ks(h, TTX_K_LOTTERY, 3);
-                    hipLaunchKernelGGL(k_lottery<FUN>, dim3(1, G), dim3(512), h->lds_lot, st, P, dir, pp, h->lot_vals, 1);
-                    hipLaunchKernelGGL(k_lottery_eval_mvn, dim3(P.lot_max, G), dim3(64), h->lds_mvn, st, P);
-                    hipLaunchKernelGGL(k_lottery<FUN>, dim3(1, G), dim3(512), h->lds_lot, st, P, dir, pp, h->lot_vals, 2);
-                } else if (FUN == FUN_ISING && P.de_cut && h->de_v2 && P.lotc) {
-                    // compact tables: one wave per candidate between the drawing and the scoring launch
-                    KScope ks(h, TTX_K_LOTTERY, 3);
-                    hipLaunchKernelGGL(k_lottery<FUN>, dim3(1, G), dim3(512), h->lds_lot, st, P, dir, pp, h->lot_vals, 1);
-                    // one wave per candidate: row-parallel without tables up to d = 160 (measured: 23 % less lottery time at D_64, even at
-                    // D_256), from the compact tables beyond (TTX_DE_LOT_POINT=0/1 forces one)
-                    if (h->de_lot_point) hipLaunchKernelGGL(k_lottery_eval_decp, dim3(P.lot_max, G), dim3(64), sizeof(double) * (2 * (size_t)(d + 64) + 2048), st, P);
-                    else hipLaunchKernelGGL(k_lottery_eval_dec, dim3(P.lot_max, G), dim3(64), h->lds_de, st, P);
-                    hipLaunchKernelGGL(k_lottery<FUN>, dim3(1, G), dim3(512), h->lds_lot, st, P, dir, pp, h->lot_vals, 2);
-                } else if (FUN == FUN_ISING && h->lot_wave) {
-                    KScope ks(h, TTX_K_LOTTERY, 3);
-                    hipLaunchKernelGGL(k_lottery<FUN>, dim3(1, G), dim3(512), h->lds_lot, st, P, dir, pp, h->lot_vals, 1);
-                    {
-                        const dim3 gr((P.lot_max + 3) / 4, G);
-                        if (h->lot_rows == 2) {         // TTX_LOTTERY_ROWS=2: with the pivots' factor tables (measured slower: HBM latency)
-                            if (P.de_unit) hipLaunchKernelGGL((k_lottery_eval_de_rows<true, true>), gr, dim3(64), h->lds_der, st, P);
-                            else hipLaunchKernelGGL((k_lottery_eval_de_rows<false, true>), gr, dim3(64), h->lds_der, st, P);
-                        } else if (P.de_unit) hipLaunchKernelGGL((k_lottery_eval_de_rows<true, false>), gr, dim3(64), h->lds_der, st, P);
-                        else hipLaunchKernelGGL((k_lottery_eval_de_rows<false, false>), gr, dim3(64), h->lds_der, st, P);
-                    }
-                    hipLaunchKernelGGL(k_lottery<FUN>, dim3(1, G), dim3(512), h->lds_lot, st, P, dir, pp, h->lot_vals, 2);
-                } else
-                { KScope ks(h, TTX_K_LOTTERY); if (int rc_ = EV([&](const DevProb &Q) { hipLaunchKernelGGL(k_lottery<FUN>, dim3(P.lot_nb, G), dim3(P.lot_nb == 1 ? 512 : 256), h->lds_lot, st, Q, dir, pp, h->lot_vals, 0); })) return rc_; }
+                    launch(st, plan.lottery, P, dir, pp, plan.lot_vals, 1);
+                    launch(st, plan.lot_eval, P);
+                    launch(st, plan.lottery, P, dir, pp, plan.lot_vals, 2);
+                } else { KScope ks(h, TTX_K_LOTTERY); if (int rc_ = EV(plan.lottery, dir, pp, plan.lot_vals, 0)) return rc_; }
                 KScope ks(h, TTX_K_HALFSTEP, h->H);
-                if (fastk) {
-                    for (int hh = 0; hh < h->H; hh++) hipLaunchKernelGGL(k_halfstep<FUN>, dim3(nfb, G), dim3(TTX_BLK), h->lds_half, st, P, hh, dir, h->mode, 0);
-                } else if (FUN == FUN_MVN && h->mvn_v2) {
-                    for (int hh = 0; hh < h->H; hh++) hipLaunchKernelGGL(k_halfstep_mvn, dim3(h->de_slots, G), dim3(64), h->lds_mvn, st, P, hh, dir, h->mode);
-                } else if (FUN == FUN_ISING && h->de_v2) {
-                    // while the ranks are small (at most it_ + 1 during sweep it_) a unit gets a team of 14 waves on a CU of its own, up to
-                    // 1024 units a team of 6 waves (three such teams fit a CU), beyond that one wave
-                    const int rb = std::min((int)h->RM, it_ + 1);
-                    const int team_slots = (h->de_test_fault && it_ == h->de_test_fault) ? 1 : rb * ((h->NM + 63) / 64);
-                    const bool team = h->de_team && !h->de_v5 && team_slots * G <= h->de_team_units;
-                    const bool team6 = h->de_team && !h->de_v5 && !team && team_slots * G <= h->de_team6_units;
-                    for (int hh = 0; hh < h->H; hh++) {
-                        if (team) {
-                            if (P.de_unit) hipLaunchKernelGGL((k_halfstep_det<true, 3>), dim3(team_slots, G), dim3(64 * 14), h->lds_det, st, P, hh, dir, h->mode);
-                            else hipLaunchKernelGGL((k_halfstep_det<false, 3>), dim3(team_slots, G), dim3(64 * 14), h->lds_det, st, P, hh, dir, h->mode);
-                        } else if (team6) {
-                            if (P.de_unit) hipLaunchKernelGGL((k_halfstep_det<true, 1>), dim3(team_slots, G), dim3(64 * 6), h->lds_det6, st, P, hh, dir, h->mode);
-                            else hipLaunchKernelGGL((k_halfstep_det<false, 1>), dim3(team_slots, G), dim3(64 * 6), h->lds_det6, st, P, hh, dir, h->mode);
-                        } else if (h->de_v5) {
-                            if (P.de_unit) hipLaunchKernelGGL(k_halfstep_de5<true>, dim3(h->de_slots, G), dim3(64 * DE5_W), h->lds_de5, st, P, hh, dir, h->mode);
-                            else hipLaunchKernelGGL(k_halfstep_de5<false>, dim3(h->de_slots, G), dim3(64 * DE5_W), h->lds_de5, st, P, hh, dir, h->mode);
-                        } else if (P.de_cut) hipLaunchKernelGGL(k_halfstep_dec, dim3(h->de_slots, G), dim3(64), h->lds_de, st, P, hh, dir, h->mode);
-                        else if (P.de_unit) hipLaunchKernelGGL(k_halfstep_de<true>, dim3(h->de_slots, G), dim3(64), h->lds_de, st, P, hh, dir, h->mode);
-                        else hipLaunchKernelGGL(k_halfstep_de<false>, dim3(h->de_slots, G), dim3(64), h->lds_de, st, P, hh, dir, h->mode);
-                    }
-                } else
-                for (int hh = 0; hh < h->H; hh++)
-                    if (int rc_ = EV([&](const DevProb &Q) { hipLaunchKernelGGL(k_halfstep<FUN>, dim3(nfb, G), dim3(TTX_BLK), h->lds_half, st, Q, hh, dir, h->mode, h->half_vals); })) return rc_;
+                for (int hh = 0; hh < h->H; hh++) {
+                    if (plan.half_vals < 0) launch(st, half, P, hh, dir, h->mode);
+                    else if (int rc_ = EV(half, hh, dir, h->mode, plan.half_vals)) return rc_;
+                }
             } else {
                 // full pivoting (:341-408): every superblock column through the half-step kernel, global arg-max,
                 // then the cross through the winner (evaluation only)
                 KScope ks(h, TTX_K_HALFSTEP, 5);
+                KLaunch cols = plan.base;
+                cols.grid.z = h->NM * h->RM;
                 hipLaunchKernelGGL(k_bond_begin, dim3(G), dim3(64), 0, st, P, dir, pp);
-                if (P.fp_mfma && FUN != FUN_HOST) {
+                if (plan.fullpiv == ChainPlan::FP_MFMA) {
                     // one dense step: evaluate the superblock once, residual by fp64 MFMA fused with the arg-max
                     const int side = h->RM * h->NM, gx = (side + 63) / 64;
-                    hipLaunchKernelGGL(k_halfstep<FUN>, dim3(nfb, G, h->NM * h->RM), dim3(TTX_BLK), h->lds_half, st, P, 0, dir, 4, fastk ? 0 : h->half_vals);
+                    launch(st, cols, P, 0, dir, 4, plan.base_vals);
                     hipLaunchKernelGGL(k_full_gemm_argmax, dim3(gx, gx, G), dim3(256), 0, st, P);
                     hipLaunchKernelGGL(k_full_resolve2, dim3(G), dim3(256), 0, st, P, gx, gx);
-                } else if (FUN == FUN_HOST) {
+                } else if (plan.fullpiv == ChainPlan::FP_COLUMNS) {
                     // the user's `fun` with full pivoting (:341-408 works with any fun): one superblock column (k,q) per launch pair --
-                    // pass 1 hands the column's multi-indices to the host, pass 2 takes the values, residual and partial arg-max; the
-                    // ranks are at most it_ + 1 in sweep it_, columns beyond n2 r2 return at once
-                    const int zmax = h->NM * std::min((int)h->RM, it_ + 1);
-                    for (int z = 0; z < zmax; z++) {
+                    // pass 1 hands the column's multi-indices to the host, pass 2 takes the values, residual and partial arg-max;
+                    // columns beyond n2 r2 return at once
+                    for (int z = 0; z < h->NM * rb; z++) {
                         DevProb Q = P;
                         Q.zbase = z;
                         Q.hostpass = 1;
-                        hipLaunchKernelGGL(k_halfstep<FUN>, dim3(nfb, G, 1), dim3(TTX_BLK), h->lds_half, st, Q, 0, dir, 3, 0);
+                        launch(st, plan.base, Q, 0, dir, 3, 0);
                         if (int rc_ = slot_eval(h)) return rc_;
                         Q.hostpass = 2;
-                        hipLaunchKernelGGL(k_halfstep<FUN>, dim3(nfb, G, 1), dim3(TTX_BLK), h->lds_half, st, Q, 0, dir, 3, 0);
+                        launch(st, plan.base, Q, 0, dir, 3, 0);
                     }
                     hipLaunchKernelGGL(k_full_resolve, dim3(G), dim3(256), 0, st, P);
                 } else {
-                hipLaunchKernelGGL(k_halfstep<FUN>, dim3(nfb, G, h->NM * h->RM), dim3(TTX_BLK), h->lds_half, st, P, 0, dir, 3, fastk ? 0 : h->half_vals);
-                hipLaunchKernelGGL(k_full_resolve, dim3(G), dim3(256), 0, st, P);
+                    launch(st, cols, P, 0, dir, 3, plan.base_vals);
+                    hipLaunchKernelGGL(k_full_resolve, dim3(G), dim3(256), 0, st, P);
                 }
-                if (int rc_ = EV([&](const DevProb &Q) { hipLaunchKernelGGL(k_halfstep<FUN>, dim3(nfb, G), dim3(TTX_BLK), h->lds_half, st, Q, 0, dir, 2, fastk ? 0 : h->half_vals); })) return rc_;
-                if (int rc_ = EV([&](const DevProb &Q) { hipLaunchKernelGGL(k_halfstep<FUN>, dim3(nfb, G), dim3(TTX_BLK), h->lds_half, st, Q, 1, dir, 2, fastk ? 0 : h->half_vals); })) return rc_;
+                if (int rc_ = EV(plan.base, 0, dir, 2, plan.base_vals)) return rc_;
+                if (int rc_ = EV(plan.base, 1, dir, 2, plan.base_vals)) return rc_;
             }
-            { KScope ks(h, TTX_K_ACCEPT); hipLaunchKernelGGL(k_accept, dim3(2 * nfb + 2 * h->NM + 1, G), dim3(TTX_BLK), lds_acc, st, P, h->H, nfb); }
+            { KScope ks(h, TTX_K_ACCEPT); launch(st, plan.accept, P, h->H, plan.nfb); }
         }
         }
         if (!(part & 2)) return TTX_OK;
@@ -1747,15 +1781,8 @@ static int run_impl(ttx_engine *h)
                 if (int rc_ = xfer_neighbours(h)) return rc_;
                 if (int rc_ = allreduce_dev(h, P.redsend, P.redrecv, 4, 1)) return rc_;
             }
-            hipLaunchKernelGGL(k_exch_max_apply, dim3(G), dim3(256), (P.arith && P.fpersist) ? sizeof(double) * 4 * (d + 8) : 0, st, P, h->W > 1 ? 1 : 0, nproc > 1 ? 1 : 0);
-            if (nproc > 1) {
-                const size_t VSb = ((d + 7) & ~7) + 8;
-                const size_t lds_b = h->lds_par + 16 + sizeof(short) * 2 * VSb + sizeof(double) * (64 * 64 + 4) +
-                                     (P.bnd_wave ? sizeof(double) * (std::max<size_t>(2 * (size_t)de_rows_stride(d), 3 * (size_t)d + 2) + 8 + (P.de_cut ? 64 * 32 : 0)) : 0);    // D/E: two value rows; mvn: 3 d + 1 doubles
-                static size_t a_bnd = 0;
-                if (int rc_ = ensure_lds(reinterpret_cast<const void *>(k_exch_boundary<FUN>), lds_b, a_bnd)) return rc_;
-                if (int rc_ = EV([&](const DevProb &Q) { hipLaunchKernelGGL(k_exch_boundary<FUN>, dim3(2 * h->NM, G), dim3(TTX_BLK), lds_b, st, Q); })) return rc_;
-            }
+            hipLaunchKernelGGL(k_exch_max_apply, dim3(G), dim3(256), lds_fpersist(P), st, P, h->W > 1 ? 1 : 0, nproc > 1 ? 1 : 0);
+            if (nproc > 1) { if (int rc_ = EV(plan.exch_boundary)) return rc_; }
         }
         if (pipe && h->W == 1) hipLaunchKernelGGL(k_sweep_end, dim3(1), dim3(256), 0, st, P, it_, h->h_sum_base + (size_t)slot * h->SB);
         if (pipe && h->W > 1) {      // this GPU's part -> SUM all-reduce -> pinned slot, all stream-ordered
@@ -1768,13 +1795,7 @@ static int run_impl(ttx_engine *h)
             hipStream_t sq = forkq ? h->qstream : st;
             if (forkq) HIPCHECK(hipStreamWaitEvent(sq, h->ev_sum[slot], 0));    // fork point = end of the sweep's main-stream work
             KScope ks(h, TTX_K_QUAD, nproc > 1 ? 3 : 2);
-            const size_t lds_q = sizeof(double) * ((size_t)h->RM * h->RM + 2);
-            hipLaunchKernelGGL(k_quad_build, dim3(h->NC, G), dim3(256), lds_q, sq, pipe ? Pq : P, 0, P.quadw);
-            hipLaunchKernelGGL(k_quad_chain, dim3(G), dim3(256), P.qscr ? 0 : 2 * lds_q, sq, pipe ? Pq : P);
-            if (nproc > 1) {
-                if (int rc_ = allreduce_dev(h, P.qsend, P.qall, h->QB, 0)) return rc_;     // W > 1: sq is the main stream
-                hipLaunchKernelGGL(k_quad_tree, dim3(1), dim3(256), 0, sq, pipe ? Pq : P);
-            }
+            if (int rc_ = launch_quad(h, sq, pipe ? Pq : P, 0, P.quadw)) return rc_;
             if (pipe) {
                 HIPCHECK(hipMemcpyAsync(h->h_val + slot, &P.gs[0].val, sizeof(double), hipMemcpyDeviceToHost, sq));
                 HIPCHECK(hipEventRecord(h->ev_val[slot], sq));
@@ -1796,23 +1817,10 @@ static int run_impl(ttx_engine *h)
         if (nproc > 1) {
             hipLaunchKernelGGL(k_exch_pack, dim3(G), dim3(256), 0, st, P);
             if (int rc_ = xfer_neighbours(h)) return rc_;
-            hipLaunchKernelGGL(k_exch_apply, dim3(G), dim3(256), (P.arith && P.fpersist) ? sizeof(double) * 4 * (d + 8) : 0, st, P);
+            hipLaunchKernelGGL(k_exch_apply, dim3(G), dim3(256), lds_fpersist(P), st, P);
         }
-        // threads (= columns) per workgroup: as many as fit the LDS next to the LU panel (256, 128 or 64); the columns of a core are
-        // spread over grid.z (at maxrank 64 the 256-thread staging did not fit: the kernels then ran out of L2 with one workgroup per
-        // core, 6 ms at D_256)
-        int ft = 256;
-        while (ft > 64 && sizeof(double) * ((size_t)h->RM * h->RM + (size_t)ft * h->RM) > 96 * 1024) ft >>= 1;
-        const size_t lds_f = sizeof(double) * ((size_t)h->RM * h->RM + (size_t)ft * h->RM);
-        const int fl = lds_f <= 150 * 1024 ? 1 : 0;
-        const int fz = std::max(1, std::min(64, (h->NM * (int)h->RM + ft - 1) / ft));
-        if (fl) {
-            static size_t a_luar = 0, a_lual = 0;
-            if (int rc_ = ensure_lds(reinterpret_cast<const void *>(k_fin_luar), lds_f, a_luar)) return rc_;
-            if (int rc_ = ensure_lds(reinterpret_cast<const void *>(k_fin_lual), lds_f, a_lual)) return rc_;
-        }
-        hipLaunchKernelGGL(k_fin_luar, dim3(h->NC, G, fz), dim3(ft), fl ? lds_f : 0, st, P, fl);
-        hipLaunchKernelGGL(k_fin_lual, dim3(h->NC, G, fz), dim3(ft), fl ? lds_f : 0, st, P, fl);
+        launch(st, plan.fin_luar, P, plan.fl);
+        launch(st, plan.fin_lual, P, plan.fl);
         return TTX_OK;
     };
     // host side of a finished sweep: record, tapes, log line, stopping rule (identical to k_sweep_end)
@@ -1909,74 +1917,102 @@ static int run_impl(ttx_engine *h)
     return TTX_OK;
 }
 
+// f(std::integral_constant<int, FUN>) for the instantiation an engine's integrand runs with: the host's `fun`, the COS coefficients
+// and a loaded device integrand share the two-pass kernels of FUN_HOST (slot_eval tells them apart).  `who` names the caller
+// where the integrand has not been set yet.
+template <class F>
+static int with_fun(const ttx_engine *h, const char *who, F f)
+{
+    switch (h->cfg.fun_id) {
+        case TTX_FUN_ISING: return f(std::integral_constant<int, FUN_ISING>());
+        case TTX_FUN_STDNORM: return f(std::integral_constant<int, FUN_STDNORM>());
+        case TTX_FUN_HOST:
+            if (who && !h->hfun) return fail(TTX_ESTATE, "%s: call ttx_set_integrand_host first", who);
+            return f(std::integral_constant<int, FUN_HOST>());
+        case TTX_FUN_COSCOEFF: return f(std::integral_constant<int, FUN_HOST>());
+        case TTX_FUN_DEVICE:
+            if (who && !h->dfun) return fail(TTX_ESTATE, "%s: call ttx_set_integrand_device first", who);
+            return f(std::integral_constant<int, FUN_HOST>());
+        default: return f(std::integral_constant<int, FUN_MVN>());
+    }
+}
+
+static void reset_kernel_stats(ttx_engine *h)
+{
+    for (int k = 0; k < TTX_K_NKINDS; k++) { h->k_launches[k] = 0; h->k_ms[k] = 0; h->k_bytes[k] = 0; }
+}
+static void drain(ttx_engine *h) { (void)hipStreamSynchronize(h->stream); (void)hipStreamSynchronize(h->qstream); }
+// ctl[3] after a run: what the team and relay half-steps counted (cleared by k_reset at the start of a run only; the finalisation
+// leaves it alone)
+static int read_fault_counter(ttx_engine *h)
+{
+    int faults = 0;
+    drain(h);
+    if (hipMemcpy(&faults, h->P.ctl + 3, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) faults = 0;
+    return faults;
+}
+// Nothing of the run behind is kept, whatever it returned: drain both streams (kernels behind an aborted one see ctl[0] and do
+// nothing), clear the sticky error, retire what failed for this engine and run again -- all implementations give identical results.
+static int replay(ttx_engine *h, void (*retire)(ttx_engine *))
+{
+    drain(h);
+    (void)hipGetLastError();
+    retire(h);
+    reset_kernel_stats(h);
+    return run_impl<FUN_ISING>(h);
+}
+
 extern "C" int ttx_run(ttx_engine *h)
 {
     if (!h) return fail(TTX_EINVAL, "ttx_run: null handle");
     HIPCHECK(hipSetDevice(h->cfg.device));
     if (h->cfg.fun_id == 0) return fail(TTX_ESTATE, "ttx_run: this engine holds a loaded tensor train and has no integrand");
-    for (int k = 0; k < TTX_K_NKINDS; k++) { h->k_launches[k] = 0; h->k_ms[k] = 0; h->k_bytes[k] = 0; }
-    switch (h->cfg.fun_id) {
-        case TTX_FUN_ISING: {
-            h->cluster_aborted = false;
-            int rc = run_impl<FUN_ISING>(h);
-            if (rc && h->cluster_aborted) {
-                // A wait inside the cluster kernel timed out.  Nothing of the run is kept: drain both streams (kernels behind
-                // the aborted one see ctl[0] and do nothing), retire the cluster path for this engine and replay the run on
-                // the multi-kernel chain -- all sweep implementations produce the identical result.
-                (void)hipStreamSynchronize(h->stream);
-                (void)hipStreamSynchronize(h->qstream);
-                (void)hipGetLastError();
-                *h->h_abort = 0;
-                h->cluster = 0; h->cluster_aborted = false; h->cluster_fallbacks++;
-                if (h->P.ising_id == 1) h->P.arith = 0;        // the closed form of Ising C lives in the cluster kernel only
-                for (int k = 0; k < TTX_K_NKINDS; k++) { h->k_launches[k] = 0; h->k_ms[k] = 0; h->k_bytes[k] = 0; }
-                rc = run_impl<FUN_ISING>(h);
-            }
-            if (h->de_team && !h->de_v5) {
-                // k_halfstep_det found more units than the grid the host sized from its bound on the ranks (never expected):
-                // nothing of the run is kept -- whatever it returned --, the teams are retired for this engine and the run is repeated.
-                // (ctl[3] is cleared by k_reset at the start of a run only; the finalisation leaves it alone.)
-                int faults = 0;
-                (void)hipStreamSynchronize(h->stream); (void)hipStreamSynchronize(h->qstream);
-                if (hipMemcpy(&faults, h->P.ctl + 3, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) faults = 0;
-                if (faults) {
-                    (void)hipGetLastError();
-                    if (h->W > 1) return fail(TTX_EHIP, "ttx_run: k_halfstep_det met a rank above the host's bound; set TTX_DE_TEAM=0");
-                    h->de_team = 0; h->det_fallbacks++;
-                    for (int k = 0; k < TTX_K_NKINDS; k++) { h->k_launches[k] = 0; h->k_ms[k] = 0; h->k_bytes[k] = 0; }
-                    rc = run_impl<FUN_ISING>(h);
-                }
-            }
-            if (h->de_v5) {
-                // the relay of k_halfstep_de5 reports a broken hand-over (bounded waits) in ctl[3]: nothing of such a run is
-                // kept, the relay is retired for this engine and the run repeated with k_halfstep_de (identical results)
-                int faults = 0;
-                (void)hipStreamSynchronize(h->stream); (void)hipStreamSynchronize(h->qstream);
-                if (hipMemcpy(&faults, h->P.ctl + 3, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) faults = 0;
-                if (faults) {
-                    (void)hipGetLastError();
-                    if (h->W > 1) return fail(TTX_EHIP, "ttx_run: the wave relay of k_halfstep_de5 broke (%d hand-overs); set TTX_DE_V5=0", faults);
-                    h->de_v5 = 0; h->de5_fallbacks++;
-                    for (int k = 0; k < TTX_K_NKINDS; k++) { h->k_launches[k] = 0; h->k_ms[k] = 0; h->k_bytes[k] = 0; }
-                    rc = run_impl<FUN_ISING>(h);
-                }
-            }
-            return rc;
-        }
-        case TTX_FUN_STDNORM: return run_impl<FUN_STDNORM>(h);
-        case TTX_FUN_HOST:
-            if (!h->hfun) return fail(TTX_ESTATE, "ttx_run: call ttx_set_integrand_host first");
-            h->host_calls = 0;
-            return run_impl<FUN_HOST>(h);
-        case TTX_FUN_COSCOEFF:                  // the host integrand's two passes with the device evaluator between them (slot_eval)
-            h->host_calls = 0;
-            return run_impl<FUN_HOST>(h);
-        case TTX_FUN_DEVICE:                    // the same, the evaluator being the slot kernel of the caller's code object
-            if (!h->dfun) return fail(TTX_ESTATE, "ttx_run: call ttx_set_integrand_device first");
-            h->host_calls = 0;
-            return run_impl<FUN_HOST>(h);
-        default: return run_impl<FUN_MVN>(h);
+    reset_kernel_stats(h);
+    if (h->cfg.fun_id != TTX_FUN_ISING)
+        return with_fun(h, "ttx_run", [&](auto fun) { h->host_calls = 0; return run_impl<decltype(fun)::value>(h); });
+    h->cluster_aborted = false;
+    int rc = run_impl<FUN_ISING>(h);
+    // a wait inside the cluster kernel timed out: replay on the multi-kernel chain
+    if (rc && h->cluster_aborted)
+        rc = replay(h, [](ttx_engine *e) {
+            *e->h_abort = 0;
+            e->cluster = 0; e->cluster_aborted = false; e->cluster_fallbacks++;
+            if (e->P.ising_id == 1) e->P.arith = 0;        // the closed form of Ising C lives in the cluster kernel only
+        });
+    // k_halfstep_det found more units than the grid the host sized from its bound on the ranks (never expected): replay without teams
+    if (h->de_team && !h->de_v5 && read_fault_counter(h)) {
+        (void)hipGetLastError();
+        if (h->W > 1) return fail(TTX_EHIP, "ttx_run: k_halfstep_det met a rank above the host's bound; set TTX_DE_TEAM=0");
+        rc = replay(h, [](ttx_engine *e) { e->de_team = 0; e->det_fallbacks++; });
     }
+    // the relay of k_halfstep_de5 reports a broken hand-over (bounded waits): replay with k_halfstep_de
+    if (h->de_v5) if (const int faults = read_fault_counter(h)) {
+        (void)hipGetLastError();
+        if (h->W > 1) return fail(TTX_EHIP, "ttx_run: the wave relay of k_halfstep_de5 broke (%d hand-overs); set TTX_DE_V5=0", faults);
+        rc = replay(h, [](ttx_engine *e) { e->de_v5 = 0; e->de5_fallbacks++; });
+    }
+    return rc;
+}
+
+// one line per stage of the sweep an engine would run now (the chain path's lines also where a whole-sweep kernel is in use: they
+// are what a fallback runs); usable right after ttx_create
+extern "C" int ttx_plan_describe(const ttx_engine *h, char *buf, int64_t cap)
+{
+    if (!h || !buf || cap < 1) return fail(TTX_EINVAL, "ttx_plan_describe: null argument");
+    if (h->cfg.fun_id == 0) return fail(TTX_ESTATE, "ttx_plan_describe: this engine holds a loaded tensor train and has no integrand");
+    return with_fun(h, nullptr, [&](auto fun) {
+        const ChainPlan p = chain_plan<decltype(fun)::value>(h);
+        std::string s = std::string("path: ") + (h->cluster ? "cluster" : h->fused ? "fused" : "chain") + "\ntables: " + p.tables.name + "\nlottery: ";
+        if (h->cfg.pivoting < 0) s += "-";
+        else s += p.lot_eval ? std::string(p.lottery.name) + " + " + p.lot_eval.name + " + " + p.lottery.name : std::string(p.lottery.name);
+        s += "\nhalfstep: ";
+        for (int t = 0; t < p.ntier; t++) s += std::string(t ? ", " : "") + p.half[t].k.name + (t + 1 < p.ntier ? "[<=" + std::to_string(p.half[t].upto) + "]" : "");
+        if (h->cfg.pivoting < 0) s += std::string("\nfullpiv: ") + (p.fullpiv == ChainPlan::FP_MFMA ? "mfma" : p.fullpiv == ChainPlan::FP_COLUMNS ? "columns" : "plain");
+        s += "\n";
+        if ((int64_t)s.size() + 1 > cap) return fail(TTX_EINVAL, "ttx_plan_describe: the text needs %zu bytes", s.size() + 1);
+        memcpy(buf, s.c_str(), s.size() + 1);
+        return (int)TTX_OK;
+    });
 }
 
 extern "C" int ttx_num_sweeps(const ttx_engine *h) { return h ? (int)h->recs.size() : 0; }
@@ -2039,7 +2075,6 @@ static int allreduce_big(ttx_engine *h, double *buf, size_t count)
 }
 static std::vector<int32_t> modes_of(const ttx_engine *h) { return std::vector<int32_t>(h->n1.begin() + 1, h->n1.begin() + 1 + h->d); }
 // destroy an engine that an operation made and then failed on: the operation's error text stays the last error
-static void destroy_keep_error(ttx_engine *e) { const std::string msg = g_err; ttx_destroy(e); g_err = msg; }
 // The finalised train of a MULTI-PROCESS job on every process, as a new single-process engine with the same integrand (`out`):
 // each process copies the cores it holds into its slots of the new engine's core array and a SUM all-reduce over the job's transport
 // fills in the others (their slots hold -0.0 here, the neutral element of fp addition for every value).  dtt_accchk, norm, dot_product, ort, svd and dtt_write of the
@@ -2395,7 +2430,7 @@ extern "C" int ttx_quad(ttx_engine *h, const double *w, double *val)
         HIPCHECK(hipMalloc((void **)&dw, sizeof(double) * wp.size()));
         HIPCHECK(hipMemcpy(dw, wp.data(), sizeof(double) * wp.size(), hipMemcpyHostToDevice));
     }
-    int rc = launch_quad(h, 1, dw);
+    int rc = launch_quad(h, h->stream, h->P, 1, dw);
     if (!rc) rc = readback(h);
     if (dw) (void)hipFree(dw);
     if (rc) return rc;
@@ -2461,18 +2496,7 @@ extern "C" int ttx_accchk(ttx_engine *h, int32_t nlot, double *einf, double *efr
     if (nlot < 1) return fail(TTX_EINVAL, "dtt_accchk: nlot must be positive");
     if (h->cfg.fun_id == 0) return fail(TTX_ESTATE, "dtt_accchk: this engine holds a loaded tensor train and has no integrand");
     HIPCHECK(hipSetDevice(h->cfg.device));
-    switch (h->cfg.fun_id) {
-        case TTX_FUN_ISING: return accchk_impl<FUN_ISING>(h, nlot, einf, efro, ainf, afro, pivot);
-        case TTX_FUN_STDNORM: return accchk_impl<FUN_STDNORM>(h, nlot, einf, efro, ainf, afro, pivot);
-        case TTX_FUN_HOST:
-            if (!h->hfun) return fail(TTX_ESTATE, "dtt_accchk: call ttx_set_integrand_host first");
-            return accchk_impl<FUN_HOST>(h, nlot, einf, efro, ainf, afro, pivot);
-        case TTX_FUN_COSCOEFF: return accchk_impl<FUN_HOST>(h, nlot, einf, efro, ainf, afro, pivot);
-        case TTX_FUN_DEVICE:
-            if (!h->dfun) return fail(TTX_ESTATE, "dtt_accchk: call ttx_set_integrand_device first");
-            return accchk_impl<FUN_HOST>(h, nlot, einf, efro, ainf, afro, pivot);
-        default: return accchk_impl<FUN_MVN>(h, nlot, einf, efro, ainf, afro, pivot);
-    }
+    return with_fun(h, "dtt_accchk", [&](auto fun) { return accchk_impl<decltype(fun)::value>(h, nlot, einf, efro, ainf, afro, pivot); });
 }
 
 // ---- tt_lib utilities (ort / svd / norm / dot) -------------------------------------------------------------
@@ -2535,12 +2559,7 @@ static bool qr_own_launch(ttx_engine *h, const QrOwnShape &s, int rows, int n, i
     QRO(2, 1) QRO(4, 1) QRO(8, 1) QRO(2, 2) QRO(4, 2) QRO(8, 2) QRO(2, 4) QRO(4, 4) QRO(2, 8) QRO(4, 8)
 #undef QRO
     if (!fn) return false;
-    {   // the dynamic-LDS limit set so far per instantiation (engines may be driven from several host threads)
-        static std::map<const void *, size_t> lds_set;
-        static std::mutex lds_mu;
-        std::lock_guard<std::mutex> lk(lds_mu);
-        if ((*rc_out = ensure_lds(fn, lds, lds_set[fn]))) return true;
-    }
+    if ((*rc_out = ensure_lds(h, fn, lds))) return true;
     void *args[] = {&rows, &n, &rbs, &M, &ldm, &Q, &ldq, &R, &ldr, &rstep, &tau};
     hipError_t e = hipLaunchKernel(fn, dim3(P), dim3(s.nt), args, lds, h->stream);
     if (e != hipSuccess) *rc_out = fail(TTX_EHIP, "k_qr_own: %s", hipGetErrorString(e));
@@ -2575,7 +2594,6 @@ static bool qr_tsqr(ttx_engine *h, int m, int n, double *A, double *R, double *t
         M = Sbuf; Sbuf += (size_t)P * n * n; rows = P * n;
     }
     if (lv.empty()) return false;
-    static size_t a_qp = 0, a_q1 = 0;
     for (size_t l = 0; l < lv.size(); l++) {
         const Lvl &L = lv[l];
         double *Rst = (l + 1 < lv.size()) ? lv[l + 1].M : M;                    // the next level's matrix (P n x n)
@@ -2584,13 +2602,13 @@ static bool qr_tsqr(ttx_engine *h, int m, int n, double *A, double *R, double *t
             continue;
         }
         const size_t lds = sizeof(double) * qr_panel_lds_doubles(L.rbs, n);
-        if ((*rc_out = ensure_lds(reinterpret_cast<const void *>(k_qr_panel), lds, a_qp))) return true;
+        if ((*rc_out = ensure_lds(h, reinterpret_cast<const void *>(k_qr_panel), lds))) return true;
         hipLaunchKernelGGL(k_qr_panel, dim3(L.P), dim3(tt_threads("TTX_QR_THREADS", 1024)), lds, h->stream, L.rows, n, L.rbs, L.M, L.Q, Rst, L.P * n);
     }
     // top: one workgroup, in place: M -> Q_top (rows x n), R (n x n)
     if (!(use_own && qr_own_launch(h, own, rows, n, rows, 1, M, rows, M, rows, R, std::min(rows, n), 0, tau, rc_out))) {
         const size_t lds_all = sizeof(double) * ((size_t)rows + 2 * n + 4 + (size_t)rows * n);
-        if ((*rc_out = ensure_lds(reinterpret_cast<const void *>(k_qr<true>), lds_all, a_q1))) return true;
+        if ((*rc_out = ensure_lds(h, reinterpret_cast<const void *>(k_qr<true>), lds_all))) return true;
         hipLaunchKernelGGL(k_qr<true>, dim3(1), dim3(tt_threads("TTX_QRTOP_THREADS", 1024)), lds_all, h->stream, rows, n, M, R, tau);
     }
     if (*rc_out) return true;
@@ -2617,12 +2635,11 @@ static int qr(ttx_engine *h, int m, int n, double *A, double *R, double *tau)
     if (lds > 150 * 1024) return fail(TTX_EINVAL, "dtt_ort: unfolding with %d rows does not fit the LDS-staged reflector", m);
     // small unfoldings are factored entirely inside LDS; larger ones stream the panel from L2 with threads mapped to rows
     const size_t lds_all = lds + sizeof(double) * ((size_t)m * n + n);
-    static size_t a_q0 = 0, a_q1 = 0;
     if (lds_all <= 150 * 1024) {
-        if (int rc = ensure_lds(reinterpret_cast<const void *>(k_qr<true>), lds_all, a_q1)) return rc;
+        if (int rc = ensure_lds(h, reinterpret_cast<const void *>(k_qr<true>), lds_all)) return rc;
         hipLaunchKernelGGL(k_qr<true>, dim3(1), dim3(tt_threads("TTX_QR_THREADS", 1024)), lds_all, h->stream, m, n, A, R, tau);
     } else {
-        if (int rc = ensure_lds(reinterpret_cast<const void *>(k_qr<false>), lds, a_q0)) return rc;
+        if (int rc = ensure_lds(h, reinterpret_cast<const void *>(k_qr<false>), lds)) return rc;
         hipLaunchKernelGGL(k_qr<false>, dim3(1), dim3(1024), lds, h->stream, m, n, A, R, tau);
     }
     return TTX_OK;
@@ -2631,8 +2648,7 @@ static int jacobi(ttx_engine *h, int p, int q, double *X, double *V, double *sv,
 {
     const size_t lds = sizeof(double) * ((size_t)p + q) * q;
     const int in_lds = lds <= 140 * 1024;
-    static size_t a_j = 0;
-    if (in_lds) { if (int rc = ensure_lds(reinterpret_cast<const void *>(k_jacobi_svd), lds, a_j)) return rc; }
+    if (in_lds) { if (int rc = ensure_lds(h, reinterpret_cast<const void *>(k_jacobi_svd), lds)) return rc; }
     hipLaunchKernelGGL(k_jacobi_svd, dim3(1), dim3(tt_threads("TTX_JAC_THREADS", 256)), in_lds ? lds : 0, h->stream, p, q, X, V, sv, perm, info, 1, tol, rmax, in_lds);
     return TTX_OK;
 }
@@ -2920,9 +2936,8 @@ static int zquad_multi(ttx_engine *h, int32_t nf, const double *w, double *out)
     HIPCHECK(hipMemcpy(ddims, dims.data(), sizeof(int) * 2 * W, hipMemcpyHostToDevice));
     HIPCHECK(hipMemsetAsync(dpart, 0, sizeof(double) * npart, h->stream));
     hipLaunchKernelGGL(k_zquad_build, dim3(d, nf), dim3(256), 0, h->stream, d, RM, h->NM, h->P.SS, h->P.n, (const int *)dr, (const double *const *)dcp, (const double *)dw, 2 * sumn, dtq);
-    static size_t a_zs = 0, a_zf = 0;
-    if (int rc_ = ensure_lds(reinterpret_cast<const void *>(k_zquad_chain_seg), lds, a_zs)) return rc_;
-    if (int rc_ = ensure_lds(reinterpret_cast<const void *>(k_zquad_fold), lds, a_zf)) return rc_;
+    if (int rc_ = ensure_lds(h, reinterpret_cast<const void *>(k_zquad_chain_seg), lds)) return rc_;
+    if (int rc_ = ensure_lds(h, reinterpret_cast<const void *>(k_zquad_fold), lds)) return rc_;
     hipLaunchKernelGGL(k_zquad_chain_seg, dim3(nf), dim3(256), lds, h->stream, d, RM, (const int *)dr, (const double *)dtq, plo, phi, h->wrank, W, dpart);
     if (int rc_ = allreduce_big(h, dpart, npart)) return rc_;
     hipLaunchKernelGGL(k_zquad_fold, dim3(nf), dim3(256), lds, h->stream, RM, W, (const int *)ddims, (const double *)dpart, dout);
@@ -2960,8 +2975,7 @@ extern "C" int ttx_zquad(ttx_engine *h, int32_t nf, const double *w, double *out
     HIPCHECK(hipMemcpy(dcp, cp.data(), sizeof(double *) * (d + 2), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(dr, rr.data(), sizeof(int) * (d + 1), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_zquad_build, dim3(d, nf), dim3(256), 0, h->stream, d, RM, h->NM, h->P.SS, h->P.n, (const int *)dr, (const double *const *)dcp, (const double *)dw, 2 * sumn, dtq);
-    static size_t a_zq = 0;
-    if (int rc_ = ensure_lds(reinterpret_cast<const void *>(k_zquad_chain), lds, a_zq)) return rc_;
+    if (int rc_ = ensure_lds(h, reinterpret_cast<const void *>(k_zquad_chain), lds)) return rc_;
     hipLaunchKernelGGL(k_zquad_chain, dim3(nf), dim3(256), lds, h->stream, d, RM, (const int *)dr, (const double *)dtq, dout);
     HIPCHECK(hipMemcpyAsync(out, dout, sizeof(double) * 2 * nf, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
@@ -3077,8 +3091,7 @@ static int ev_train(ttx_engine *h, EvTrain *T)
 template <int MR>
 static int ev_gemm_launch(ttx_engine *h, const EvTrain &T, int i, int nmode, int grid, size_t lds, const int *off, const int *tile, const int *perm, const double *X, double *Z)
 {
-    // the attribute belongs to the current device (the engine's): set whenever a slice image needs more than the default 64 KB
-    if (lds > 64 * 1024) HIPCHECK(hipFuncSetAttribute((const void *)k_ev_gemm<MR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > 64 * 1024) { if (int rc = ensure_lds(h, reinterpret_cast<const void *>(k_ev_gemm<MR>), lds)) return rc; }     // a slice image above the default 64 KB
     hipLaunchKernelGGL(k_ev_gemm<MR>, dim3(grid), dim3(256), lds, h->stream, T, i, nmode, off, tile, perm, X, Z);
     return TTX_OK;
 }
@@ -3414,7 +3427,7 @@ static int sm_run(ttx_engine *h, const char *who, int64_t npts, const double *u,
     const size_t growlen = nrow > TTX_SM_LDSROW ? (size_t)nrow : 0;
     const size_t lds = 4 * sizeof(double) * (2 * (size_t)T.ldx + d + (((size_t)d + 1) >> 1) + ldsrow);
     if (lds > 160 * 1024) return fail(TTX_EINVAL, "%s: %d modes need %zu bytes of LDS per workgroup (160 KB at most)", who, d, lds);
-    if (lds > 64 * 1024) HIPCHECK(hipFuncSetAttribute((const void *)k_sm_draw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > 64 * 1024 && (rc = ensure_lds(h, reinterpret_cast<const void *>(k_sm_draw), lds))) return rc;
     if (growlen && (rc = buf_reserve(h, SC_ROW, sizeof(double) * growlen * 4 * gridmax))) return rc;
     double *grow = growlen ? buf<double>(h, SC_ROW) : nullptr;
     if (!dev && ((rc = buf_reserve(h, SC_X, sizeof(double) * chunk * d)) || (rc = buf_reserve(h, SC_IND, sizeof(int) * chunk * d)) ||

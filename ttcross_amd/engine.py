@@ -449,6 +449,15 @@ class TTCross:
         L.ttx_sweep_path.argtypes = [c_void_p]
         return ("chain", "fused", "cluster")[L.ttx_sweep_path(self._h)]
 
+    def plan(self):
+        """The kernels the engine would launch now, stage by stage: {'path': .., 'tables': .., 'lottery': .., 'halfstep': ..} (and
+        'fullpiv' with pivoting -1), the values as include/ttx.h writes them (ttx_plan_describe)."""
+        L = load_library()
+        L.ttx_plan_describe.argtypes = [c_void_p, c_char_p, c_int64]
+        buf = ctypes.create_string_buffer(1024)
+        _check(L.ttx_plan_describe(self._h, buf, len(buf)))
+        return dict(line.split(": ", 1) for line in buf.value.decode().splitlines())
+
     def cluster_eval(self):
         """Integrand evaluator of the cluster sweep kernel: 'none' (not on that path), 'predicated' (exact, remainders of the
         chains tested per step: TTX_CL_PAD=0 or a node outside [0,1]), 'chunks' (exact, rows padded to whole chunks) or 'closed'
