@@ -36,6 +36,7 @@
 #include "../../include/ttx.h"
 #include "../../include/ttx_device_fun.h"   // the slot ABI of loadable device integrands (TTX_FUN_DEVICE)
 #include "ttx_lds.h"
+#include "ttx_qr_plan.h"
 #include "ttx_kernels.h"
 #include "ttx_de.h"
 #include "ttx_mvn.h"
@@ -2417,22 +2418,33 @@ extern "C" int ttx_read(ttx_engine **out, const char *path, int32_t device)
     return ttx_from_tt(out, d, n.data(), r.data(), x.data(), device);
 }
 
+// per-call device temporaries: released on every path out of the function that holds the guard
+struct DevTmp {
+    std::vector<void *> p;
+    ~DevTmp() { for (void *q : p) (void)hipFree(q); }
+    template <class T> hipError_t alloc(T **q, size_t count)
+    {
+        hipError_t e = hipMalloc((void **)q, sizeof(T) * count);
+        if (e == hipSuccess) p.push_back((void *)*q);
+        return e;
+    }
+};
+
 extern "C" int ttx_quad(ttx_engine *h, const double *w, double *val)
 {
     if (!h || !val || !h->ran) return fail(TTX_ESTATE, "ttx_quad: run first");
     HIPCHECK(hipSetDevice(h->cfg.device));
+    DevTmp tmp;
     double *dw = nullptr;
-    std::vector<double> wp;
     if (w) {
-        wp.assign((size_t)(h->d + 1) * h->NM, 0.0);
+        std::vector<double> wp((size_t)(h->d + 1) * h->NM, 0.0);
         size_t off = 0;
         for (int k = 1; k <= h->d; k++) { for (int j = 0; j < h->n1[k]; j++) wp[(size_t)k * h->NM + j] = w[off + j]; off += h->n1[k]; }
-        HIPCHECK(hipMalloc((void **)&dw, sizeof(double) * wp.size()));
+        HIPCHECK(tmp.alloc(&dw, wp.size()));
         HIPCHECK(hipMemcpy(dw, wp.data(), sizeof(double) * wp.size(), hipMemcpyHostToDevice));
     }
     int rc = launch_quad(h, h->stream, h->P, 1, dw);
     if (!rc) rc = readback(h);
-    if (dw) (void)hipFree(dw);
     if (rc) return rc;
     HIPCHECK(hipGetLastError());
     *val = h->h_sum[SUM_VAL];
@@ -2449,11 +2461,14 @@ static int accchk_impl(ttx_engine *h, int nlot, double *einf, double *efro, doub
     // the stream position where dtt_dmrgg left the run-time generator (rank 0 of the reference = group 0)
     GroupState g0s;
     HIPCHECK(hipMemcpy(&g0s, P.gs, sizeof(GroupState), hipMemcpyDeviceToHost));
+    DevTmp tmp;
     int *downer, *dind; double *dout;
-    HIPCHECK(hipMalloc((void **)&downer, sizeof(int) * (d + 2))); HIPCHECK(hipMalloc((void **)&dind, sizeof(int) * (size_t)nlot * d));
-    HIPCHECK(hipMalloc((void **)&dout, sizeof(double) * 4 * (size_t)nlot));
+    HIPCHECK(tmp.alloc(&downer, d + 2)); HIPCHECK(tmp.alloc(&dind, (size_t)nlot * d)); HIPCHECK(tmp.alloc(&dout, 4 * (size_t)nlot));
     HIPCHECK(hipMemcpy(downer, owner.data(), sizeof(int) * (d + 2), hipMemcpyHostToDevice));
-    size_t lds = sizeof(double) * (h->par.size() + 2 * h->RM + 4) + sizeof(int) * (d + 4);
+    const size_t lds = sizeof(double) * (h->par.size() + 2 * h->RM + 4) + sizeof(int) * (d + 4);
+    auto check = [&](const DevProb &Q, int count, int il0) {
+        hipLaunchKernelGGL(k_accchk<FUN>, dim3(count), dim3(64), lds, h->stream, Q, (unsigned long long)g0s.rngpos, nlot, (const int *)downer, dout, dind, il0);
+    };
     if (FUN == FUN_HOST) {
         // chunks of at most G*HS samples: index pass, the user's function on the host, value pass
         const int chunk = (int)std::min<size_t>((size_t)h->G * h->HS, 65535);
@@ -2461,13 +2476,13 @@ static int accchk_impl(ttx_engine *h, int nlot, double *einf, double *efro, doub
             const int cnt = std::min(chunk, nlot - il0);
             DevProb Q = P;
             Q.hostpass = 1;
-            hipLaunchKernelGGL(k_accchk<FUN>, dim3(cnt), dim3(64), lds, h->stream, Q, (unsigned long long)g0s.rngpos, nlot, (const int *)downer, dout, dind, il0);
+            check(Q, cnt, il0);
             if (int rc_ = slot_eval(h)) return rc_;
             Q.hostpass = 2;
-            hipLaunchKernelGGL(k_accchk<FUN>, dim3(cnt), dim3(64), lds, h->stream, Q, (unsigned long long)g0s.rngpos, nlot, (const int *)downer, dout, dind, il0);
+            check(Q, cnt, il0);
         }
     } else
-    hipLaunchKernelGGL(k_accchk<FUN>, dim3(nlot), dim3(64), lds, h->stream, P, (unsigned long long)g0s.rngpos, nlot, (const int *)downer, dout, dind, 0);
+        check(P, nlot, 0);
     std::vector<double> o(4 * (size_t)nlot);
     std::vector<int> ind((size_t)nlot * d);
     HIPCHECK(hipMemcpyAsync(o.data(), dout, sizeof(double) * o.size(), hipMemcpyDeviceToHost, h->stream));
@@ -2484,7 +2499,6 @@ static int accchk_impl(ttx_engine *h, int nlot, double *einf, double *efro, doub
     }
     *einf = e1; *efro = std::sqrt(e2); *ainf = a1; *afro = std::sqrt(a2);
     if (pivot && worst >= 0) for (int i = 0; i < d; i++) pivot[i] = ind[(size_t)worst * d + i];
-    (void)hipFree(downer); (void)hipFree(dind); (void)hipFree(dout);
     return TTX_OK;
 }
 
@@ -2500,6 +2514,22 @@ extern "C" int ttx_accchk(ttx_engine *h, int32_t nlot, double *einf, double *efr
 }
 
 // ---- tt_lib utilities (ort / svd / norm / dot) -------------------------------------------------------------
+// The factorisation scratch Sm (doubles) and Si (ints): five RM x RM matrices (three more are spare), then vectors and scalars
+struct TtScratch {
+    double *Rm, *Rt, *Vb, *US, *Vs;     // R of a QR, its transpose, V of the Jacobi SVD, the kept U S and V columns
+    double *tau, *sv;                   // reflector scales, singular values (RM each)
+    double *acc, *sums;                 // ort_impl: sum of log norms, last 1/norm; sumsq: sum of squares, exponent
+    int *perm, *info;                   // Jacobi: order of the singular values; rank and sweeps
+    static size_t doubles(size_t RM) { return 8 * RM * RM + 4 * RM + 16; }
+    static size_t ints(size_t RM) { return 2 * RM + 16; }
+    explicit TtScratch(const ttx_engine *h)
+    {
+        const size_t RM = h->RM, M = RM * RM;
+        Rm = h->Sm; Rt = Rm + M; Vb = Rm + 2 * M; US = Rm + 3 * M; Vs = Rm + 4 * M;
+        tau = Rm + 8 * M; sv = tau + RM; acc = tau + 4 * RM + 2; sums = tau + 4 * RM + 4;
+        perm = h->Si; info = h->Si + RM;
+    }
+};
 static int tt_prepare(ttx_engine *h, const char *who)
 {
     if (!h || !h->ran) return fail(TTX_ESTATE, "%s: run dtt_dmrgg first", who);
@@ -2509,145 +2539,114 @@ static int tt_prepare(ttx_engine *h, const char *who)
         const size_t CS = h->P.CS, RM = h->RM;
         int rc;
         if ((rc = dev_alloc(h, &h->Wa, CS)) || (rc = dev_alloc(h, &h->Wb, CS)) || (rc = dev_alloc(h, &h->Wc, CS)) || (rc = dev_alloc(h, &h->Wd, CS))) return rc;
-        if ((rc = dev_alloc(h, &h->Sm, 8 * RM * RM + 4 * RM + 16)) || (rc = dev_alloc(h, &h->Si, 2 * RM + 16))) return rc;
+        if ((rc = dev_alloc(h, &h->Sm, TtScratch::doubles(RM))) || (rc = dev_alloc(h, &h->Si, TtScratch::ints(RM)))) return rc;
     }
     return TTX_OK;
 }
 static inline dim3 g1(size_t n) { return dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)); }
+// core k between its place in the train and a dense column-major r0 n x r1 matrix (trans: its transpose); e's current ranks
+static size_t core_elems(const ttx_engine *e, int k) { return (size_t)e->rfinal[k - 1] * e->n1[k] * e->rfinal[k]; }
+static void pack_core(hipStream_t st, const ttx_engine *e, int k, double *dst, int trans = 0)
+{
+    hipLaunchKernelGGL(k_pack_core, g1(core_elems(e, k)), dim3(256), 0, st, core_dev(e, k), dst, e->rfinal[k - 1], e->n1[k], e->rfinal[k], e->RM, e->P.SS, trans);
+}
+static void unpack_core(ttx_engine *h, int k, const double *src, int r0, int r1, int trans = 0)
+{
+    hipLaunchKernelGGL(k_unpack_core, g1((size_t)r0 * h->n1[k] * r1), dim3(256), 0, h->stream, core_dev(h, k), src, r0, h->n1[k], r1, h->RM, h->P.SS, trans, 1.0);
+}
+static void scal_core(ttx_engine *h, int k, double a)
+{
+    hipLaunchKernelGGL(k_scal_core, g1(core_elems(h, k)), dim3(256), 0, h->stream, core_dev(h, k), h->rfinal[k - 1], h->n1[k], h->rfinal[k], h->RM, h->P.SS, a);
+}
+// out (rows x rr) = the columns perm[0..rr) of X (rows x rows), each times sv[perm[j]] (if given) and sdiv
+static void take_cols(ttx_engine *h, int rows, int rr, const double *X, const int *perm, const double *sv, double sdiv, double *out)
+{
+    hipLaunchKernelGGL(k_take_cols, g1((size_t)rows * rr), dim3(256), 0, h->stream, rows, rr, X, rows, perm, sv, sdiv, out);
+}
 // threads of the one-workgroup factorisation kernels (a multiple of 64, at most 1024): the kernels are chains of short phases
 // separated by workgroup barriers, whose cost grows with the number of waves -- TTX_QR_THREADS / TTX_JAC_THREADS override
-static int tt_threads(const char *env, int dflt)
-{
-    int v = dflt;
-    if (const char *e = getenv(env)) v = atoi(e);
-    v = std::max(64, std::min(1024, v)) & ~63;
-    return v;
-}
+static int tt_threads(const char *env, int dflt) { return std::max(64, std::min(1024, env_int(env, dflt))) & ~63; }
 static int gemm(ttx_engine *h, int M, int N, int K, const double *A, int lda, const double *B, int ldb, double *C, int ldc)
 {
     hipLaunchKernelGGL(k_gemm_mfma, dim3((N + 63) / 64, (M + 15) / 16), dim3(256), 0, h->stream, M, N, K, A, lda, B, ldb, C, ldc);
     return TTX_OK;
 }
-// ---- QR of an unfolding ------------------------------------------------------------------------------------------------
-// k_qr_own<MR, NC> (matrix in registers, one barrier per reflector, ttx_ttops.h): NC = columns per wave, MR = rows per lane
-struct QrOwnShape { int nt, mr, nc, rows_cap; };
-static QrOwnShape qr_own_shape(int n)
+// core k-1 times B (r[k-1] x rr): the new bond rank rr is the caller's to record (lib/tt.f90:344)
+static void push_left(ttx_engine *h, int k, const double *B, int rr)
 {
-    QrOwnShape s{0, 0, 0, 0};
-    if (n < 1 || n > 128 || (getenv("TTX_QR_OWN") && atoi(getenv("TTX_QR_OWN")) == 0)) return s;
-    s.nt = tt_threads("TTX_QR_THREADS", 1024);
-    const int nw = s.nt / 64;
-    int nc = 1; while (nc * nw < n) nc *= 2;
-    if (nc > 8) return QrOwnShape{0, 0, 0, 0};
-    s.nc = nc;
-    s.mr = nc <= 2 ? 8 : 4;                                                  // rows per lane the instantiations hold without spilling
-    const size_t budget = 150 * 1024 / sizeof(double);
-    const long lds_rows = (long)((budget - (size_t)n - 4) / (size_t)n);
-    s.rows_cap = (int)std::min<long>(64L * s.mr, lds_rows);
-    return s;
+    const int mm = h->rfinal[k - 1], kk = h->rfinal[k - 2] * h->n1[k - 1];
+    pack_core(h->stream, h, k - 1, h->Wb);
+    gemm(h, kk, rr, mm, h->Wb, kk, B, mm, h->Wc, kk);
+    unpack_core(h, k - 1, h->Wc, h->rfinal[k - 2], rr);
 }
-// one launch over P panels of rbs rows (P = 1, rbs = rows: the whole matrix); false: shape not covered
-static bool qr_own_launch(ttx_engine *h, const QrOwnShape &s, int rows, int n, int rbs, int P, const double *M, int ldm, double *Q, int ldq,
-                          double *R, int ldr, int rstep, double *tau, int *rc_out)
+// B (mn x r[k]) times core k+1, and r[k] = mn (:175)
+static void push_right(ttx_engine *h, int k, const double *B, int mn)
 {
-    int mr = 1; while (mr * 64 < rbs) mr *= 2;
-    if (mr < 2) mr = 2;
-    if (mr > s.mr) return false;
-    const size_t lds = sizeof(double) * qr_own_lds_doubles(rbs, n);
-    const void *fn = nullptr;
-#define QRO(MRv, NCv) if (mr == MRv && s.nc == NCv) fn = reinterpret_cast<const void *>(k_qr_own<MRv, NCv>);
-    QRO(2, 1) QRO(4, 1) QRO(8, 1) QRO(2, 2) QRO(4, 2) QRO(8, 2) QRO(2, 4) QRO(4, 4) QRO(2, 8) QRO(4, 8)
+    const int nn = h->rfinal[k], kk = h->n1[k + 1] * h->rfinal[k + 1];
+    pack_core(h->stream, h, k + 1, h->Wb);
+    gemm(h, mn, kk, nn, B, mn, h->Wb, nn, h->Wc, mn);
+    h->rfinal[k] = mn;
+    unpack_core(h, k + 1, h->Wc, mn, h->rfinal[k + 1]);
+}
+// ---- QR of an unfolding: the plan of ttx_qr_plan.h, its LDS ceilings, its launches in order ------------------------------------
+static const void *qr_kernel(const QrLaunch &L)
+{
+    if (L.kernel == QRK_OWN) {
+#define QRO(MRv, NCv) if (L.mr == MRv && L.nc == NCv) return reinterpret_cast<const void *>(k_qr_own<MRv, NCv>);
+        QRO(2, 1) QRO(4, 1) QRO(8, 1) QRO(2, 2) QRO(4, 2) QRO(8, 2) QRO(2, 4) QRO(4, 4) QRO(2, 8) QRO(4, 8)
 #undef QRO
-    if (!fn) return false;
-    if ((*rc_out = ensure_lds(h, fn, lds))) return true;
-    void *args[] = {&rows, &n, &rbs, &M, &ldm, &Q, &ldq, &R, &ldr, &rstep, &tau};
-    hipError_t e = hipLaunchKernel(fn, dim3(P), dim3(s.nt), args, lds, h->stream);
-    if (e != hipSuccess) *rc_out = fail(TTX_EHIP, "k_qr_own: %s", hipGetErrorString(e));
-    return true;
+    }
+    if (L.kernel == QRK_PANEL) return reinterpret_cast<const void *>(k_qr_panel);
+    if (L.kernel == QRK_LDS) return reinterpret_cast<const void *>(k_qr<true>);
+    if (L.kernel == QRK_STREAM) return reinterpret_cast<const void *>(k_qr<false>);
+    return nullptr;
 }
-// Tall-skinny QR of A (m x n, m >> n) over several workgroups (ttx_ttops.h): levels of panel factorisations side by side, then
-// the explicit Q from the top level down.  Scratch: Wb (Q panels of level 0), Wc (stacked triangles of the levels / their
-// accumulated Q), Wd (Q panels of the levels >= 1) -- all free while a qr() is running.  false: shape not eligible.
-static bool qr_tsqr(ttx_engine *h, int m, int n, double *A, double *R, double *tau, int *rc_out)
+// one launch of the plan: M (rows x n, P panels of rbs rows) -> Q (M itself for a top launch), triangles to R (leading dimension ldr)
+static int qr_launch(ttx_engine *h, const QrLaunch &L, int n, const double *M, double *Q, double *R, int ldr, int rstep, double *tau)
 {
-    *rc_out = TTX_OK;
-    if (A != h->Wa || n > 96 || m < 4 * n || (getenv("TTX_TSQR") && atoi(getenv("TTX_TSQR")) == 0)) return false;
-    const QrOwnShape own = qr_own_shape(n);
-    const bool use_own = own.nt && own.rows_cap >= 2 * n;
-    const size_t budget = 150 * 1024 / sizeof(double);
-    // rows of a panel: the register kernel's time per reflector grows with the rows per lane, so its panels are short (4 n rows,
-    // at least 256 -- measured optimum for n = 32); the LDS kernel takes what fits with its reflector
-    int RB = use_own ? std::min(own.rows_cap, std::max(256, 4 * n)) : (int)((budget - 2 * n - 2) / (size_t)(n + 1));
-    if (const char *e = getenv("TTX_QR_PANEL")) if (use_own && atoi(e) >= 2 * n) RB = std::min(own.rows_cap, atoi(e));
-    if (RB < 2 * n) return false;
-    struct Lvl { int rows, P, rbs; double *M, *Q; };
-    std::vector<Lvl> lv;
-    double *Sbuf = h->Wc, *Tbuf = h->Wd;
-    int rows = m; double *M = A;
-    auto top_fits = [&](int rws) { return use_own ? rws <= own.rows_cap : (size_t)rws * n + rws + 2 * n + 4 <= budget; };
-    while (!top_fits(rows)) {                                                   // until one workgroup takes the rest
-        const int P = (rows + RB - 1) / RB, rbs = (rows + P - 1) / P;
-        if (rows - (P - 1) * rbs < n) return false;                             // a last panel shorter than n: keep the one-workgroup path
-        Lvl L{rows, P, rbs, M, lv.empty() ? h->Wb : Tbuf};
-        if (!lv.empty()) Tbuf += (size_t)rows * n;
-        lv.push_back(L);
-        M = Sbuf; Sbuf += (size_t)P * n * n; rows = P * n;
-    }
-    if (lv.empty()) return false;
-    for (size_t l = 0; l < lv.size(); l++) {
-        const Lvl &L = lv[l];
-        double *Rst = (l + 1 < lv.size()) ? lv[l + 1].M : M;                    // the next level's matrix (P n x n)
-        if (use_own && qr_own_launch(h, own, L.rows, n, L.rbs, L.P, L.M, L.rows, L.Q, L.rows, Rst, L.P * n, n, nullptr, rc_out)) {
-            if (*rc_out) return true;
-            continue;
-        }
-        const size_t lds = sizeof(double) * qr_panel_lds_doubles(L.rbs, n);
-        if ((*rc_out = ensure_lds(h, reinterpret_cast<const void *>(k_qr_panel), lds))) return true;
-        hipLaunchKernelGGL(k_qr_panel, dim3(L.P), dim3(tt_threads("TTX_QR_THREADS", 1024)), lds, h->stream, L.rows, n, L.rbs, L.M, L.Q, Rst, L.P * n);
-    }
-    // top: one workgroup, in place: M -> Q_top (rows x n), R (n x n)
-    if (!(use_own && qr_own_launch(h, own, rows, n, rows, 1, M, rows, M, rows, R, std::min(rows, n), 0, tau, rc_out))) {
-        const size_t lds_all = sizeof(double) * ((size_t)rows + 2 * n + 4 + (size_t)rows * n);
-        if ((*rc_out = ensure_lds(h, reinterpret_cast<const void *>(k_qr<true>), lds_all))) return true;
-        hipLaunchKernelGGL(k_qr<true>, dim3(1), dim3(tt_threads("TTX_QRTOP_THREADS", 1024)), lds_all, h->stream, rows, n, M, R, tau);
-    }
-    if (*rc_out) return true;
-    // explicit Q, top down: Qacc(level l) = blockdiag(Q_p) * Qacc(level l+1); level l's own matrix buffer takes the result
-    const double *Qup = M; int ldup = rows;
-    for (int l = (int)lv.size() - 1; l >= 0; l--) {
-        const Lvl &L = lv[l];
-        double *out = L.M;                                                      // level 0: A itself
-        hipLaunchKernelGGL(k_gemm_mfma_panels, dim3((n + 63) / 64, (L.rbs + 15) / 16, L.P), dim3(256), 0, h->stream,
-                           L.rows, n, L.rbs, (const double *)L.Q, L.rows, Qup, ldup, out, L.rows);
-        Qup = out; ldup = L.rows;
-    }
-    return true;
+    const void *fn = qr_kernel(L);
+    const bool agree = L.kernel == QRK_OWN ? L.lds == sizeof(double) * qr_own_lds_doubles(L.rbs, n) :
+                       L.kernel == QRK_PANEL ? L.lds == sizeof(double) * qr_panel_lds_doubles(L.rbs, n) : true;
+    if (!fn || !agree) return fail(TTX_EHIP, "qr: the plan of %d x %d names no kernel or disagrees with it on LDS", L.rows, n);
+    int rows = L.rows, rbs = L.rbs;
+    void *own[] = {&rows, &n, &rbs, &M, &rows, &Q, &rows, &R, &ldr, &rstep, &tau}, *panel[] = {&rows, &n, &rbs, &M, &Q, &R, &ldr}, *whole[] = {&rows, &n, &Q, &R, &tau};
+    hipError_t e = hipLaunchKernel(fn, dim3(L.P), dim3(L.threads), L.kernel == QRK_OWN ? own : L.kernel == QRK_PANEL ? panel : whole, L.lds, h->stream);
+    if (e != hipSuccess && L.kernel == QRK_OWN) return fail(TTX_EHIP, "k_qr_own: %s", hipGetErrorString(e));
+    return TTX_OK;
 }
+// A (m x n) -> Q in place, R (min(m, n) x n).  The tall-skinny route keeps the Q panels of level 0 in Wb, the stacked triangles of
+// the levels (then their accumulated Q) in Wc and the Q panels of the levels >= 1 in Wd -- all free while a qr() is running.
 static int qr(ttx_engine *h, int m, int n, double *A, double *R, double *tau)
 {
-    { int rc = TTX_OK; if (qr_tsqr(h, m, n, A, R, tau, &rc)) return rc; }
-    {   // small unfoldings: one workgroup, matrix in registers
-        const QrOwnShape own = qr_own_shape(n);
-        int rc = TTX_OK;
-        if (own.nt && m <= own.rows_cap && qr_own_launch(h, own, m, n, m, 1, A, m, A, m, R, std::min(m, n), 0, tau, &rc)) return rc;
+    QrEnv env;
+    env.own_off = env_off("TTX_QR_OWN"); env.tsqr_off = env_off("TTX_TSQR"); env.panel = env_int("TTX_QR_PANEL", 0);
+    env.threads = tt_threads("TTX_QR_THREADS", 1024); env.top_threads = tt_threads("TTX_QRTOP_THREADS", 1024);
+    const QrPlan p = qr_plan(m, n, A == h->Wa, env);
+    if (p.route == QR_REFUSED) return fail(TTX_EINVAL, "dtt_ort: unfolding with %d rows does not fit the LDS-staged reflector", m);
+    int rc;
+    for (const QrLevel &L : p.lv) if ((rc = ensure_lds(h, qr_kernel(L), L.lds))) return rc;
+    if ((rc = ensure_lds(h, qr_kernel(p.top), p.top.lds))) return rc;
+    for (size_t l = 0; l < p.lv.size(); l++) {                                  // a level's triangles are the next level's matrix (P n x n)
+        const QrLevel &L = p.lv[l];
+        if ((rc = qr_launch(h, L, n, l ? h->Wc + L.m_off : A, l ? h->Wd + L.q_off : h->Wb, h->Wc + L.r_off, L.P * n, n, nullptr))) return rc;
     }
-    const size_t lds = sizeof(double) * ((size_t)m + n + 4);
-    if (lds > 150 * 1024) return fail(TTX_EINVAL, "dtt_ort: unfolding with %d rows does not fit the LDS-staged reflector", m);
-    // small unfoldings are factored entirely inside LDS; larger ones stream the panel from L2 with threads mapped to rows
-    const size_t lds_all = lds + sizeof(double) * ((size_t)m * n + n);
-    if (lds_all <= 150 * 1024) {
-        if (int rc = ensure_lds(h, reinterpret_cast<const void *>(k_qr<true>), lds_all)) return rc;
-        hipLaunchKernelGGL(k_qr<true>, dim3(1), dim3(tt_threads("TTX_QR_THREADS", 1024)), lds_all, h->stream, m, n, A, R, tau);
-    } else {
-        if (int rc = ensure_lds(h, reinterpret_cast<const void *>(k_qr<false>), lds)) return rc;
-        hipLaunchKernelGGL(k_qr<false>, dim3(1), dim3(1024), lds, h->stream, m, n, A, R, tau);
+    double *top = p.lv.empty() ? A : h->Wc + p.top_off;                         // one workgroup, in place: top -> Q_top (rows x n), R (n x n)
+    if ((rc = qr_launch(h, p.top, n, top, top, R, std::min(p.top.rows, n), 0, tau))) return rc;
+    // explicit Q, top down: Qacc(level l) = blockdiag(Q_p) * Qacc(level l+1); level l's own matrix buffer takes the result
+    const double *Qup = top; int ldup = p.top.rows;
+    for (int l = (int)p.lv.size() - 1; l >= 0; l--) {
+        const QrLevel &L = p.lv[l];
+        double *out = l ? h->Wc + L.m_off : A;
+        hipLaunchKernelGGL(k_gemm_mfma_panels, dim3((n + 63) / 64, (L.rbs + 15) / 16, L.P), dim3(256), 0, h->stream,
+                           L.rows, n, L.rbs, (const double *)(l ? h->Wd + L.q_off : h->Wb), L.rows, Qup, ldup, out, L.rows);
+        Qup = out; ldup = L.rows;
     }
     return TTX_OK;
 }
 static int jacobi(ttx_engine *h, int p, int q, double *X, double *V, double *sv, int *perm, int *info, double tol, int rmax)
 {
     const size_t lds = sizeof(double) * ((size_t)p + q) * q;
-    const int in_lds = lds <= 140 * 1024;
+    const int in_lds = lds <= TTX_LDS_JACOBI;
     if (in_lds) { if (int rc = ensure_lds(h, reinterpret_cast<const void *>(k_jacobi_svd), lds)) return rc; }
     hipLaunchKernelGGL(k_jacobi_svd, dim3(1), dim3(tt_threads("TTX_JAC_THREADS", 256)), in_lds ? lds : 0, h->stream, p, q, X, V, sv, perm, info, 1, tol, rmax, in_lds);
     return TTX_OK;
@@ -2655,7 +2654,7 @@ static int jacobi(ttx_engine *h, int p, int q, double *X, double *V, double *sv,
 // ||x||_2 = sqrt(*s2) 2^*e (e = 0 unless the plain sum of squares left [1e-280, 1e280], ttx_ttops.h)
 static int sumsq(ttx_engine *h, size_t n, const double *x, double *s2, int *e)
 {
-    double *d = h->Sm + 8 * (size_t)h->RM * h->RM + 4 * h->RM + 4;  // scratch scalars (acc of ort_impl: + 2, + 3)
+    double *d = TtScratch(h).sums;
     double out[2];
     hipLaunchKernelGGL(k_sumsq, dim3(1), dim3(1024), 0, h->stream, n, x, d);
     HIPCHECK(hipMemcpyAsync(out, d, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2680,31 +2679,26 @@ static double host_norm(const double *v, int n)
 
 static int ort_impl(ttx_engine *h)
 {
-    const int d = h->d, RM = h->RM; const size_t SS = h->P.SS;
+    const int d = h->d;
     std::vector<int32_t> &r = h->rfinal;
-    double *Rm = h->Sm, *tau = h->Sm + 8 * (size_t)RM * RM;
-    double *acc = h->Sm + 8 * (size_t)RM * RM + 4 * RM + 2;             // device scalars: sum of log norms, last 1/norm
+    const TtScratch s(h);
     int rc;
-    HIPCHECK(hipMemsetAsync(acc, 0, 2 * sizeof(double), h->stream));
+    HIPCHECK(hipMemsetAsync(s.acc, 0, 2 * sizeof(double), h->stream));
     // the whole left-to-right pass is enqueued without a host round trip: the new ranks min(r0*n, r1) are known on the
     // host, the norm equalisation (log of each R's norm, final rescaling) stays on the device
     for (int k = 1; k <= d - 1; k++) {                                  // lib/tt.f90:149-181
-        const int r0 = r[k - 1], n = h->n1[k], r1 = r[k], mm = r0 * n, nn = r1, mn = std::min(mm, nn), kk = h->n1[k + 1] * r[k + 1];
-        hipLaunchKernelGGL(k_pack_core, g1((size_t)mm * nn), dim3(256), 0, h->stream, core_dev(h, k), h->Wa, r0, n, r1, RM, SS, 0);
-        if ((rc = qr(h, mm, nn, h->Wa, Rm, tau))) return rc;
-        hipLaunchKernelGGL(k_norm_log, dim3(1), dim3(1024), 0, h->stream, (size_t)mn * nn, Rm, acc, 1);
-        hipLaunchKernelGGL(k_unpack_core, g1((size_t)mm * mn), dim3(256), 0, h->stream, core_dev(h, k), h->Wa, r0, n, mn, RM, SS, 0, 1.0);
-        hipLaunchKernelGGL(k_pack_core, g1((size_t)nn * kk), dim3(256), 0, h->stream, core_dev(h, k + 1), h->Wb, nn, h->n1[k + 1], r[k + 1], RM, SS, 0);
-        gemm(h, mn, kk, nn, Rm, mn, h->Wb, nn, h->Wc, mn);             // R pushed into the next core (:175), fp64 MFMA
-        r[k] = mn;
-        hipLaunchKernelGGL(k_unpack_core, g1((size_t)mn * kk), dim3(256), 0, h->stream, core_dev(h, k + 1), h->Wc, mn, h->n1[k + 1], r[k + 1], RM, SS, 0, 1.0);
+        const int r0 = r[k - 1], mm = r0 * h->n1[k], nn = r[k], mn = std::min(mm, nn);
+        pack_core(h->stream, h, k, h->Wa);
+        if ((rc = qr(h, mm, nn, h->Wa, s.Rm, s.tau))) return rc;
+        hipLaunchKernelGGL(k_norm_log, dim3(1), dim3(1024), 0, h->stream, (size_t)mn * nn, s.Rm, s.acc, 1);
+        unpack_core(h, k, h->Wa, r0, mn);
+        push_right(h, k, s.Rm, mn);                                     // R pushed into the next core, fp64 MFMA
     }
-    const size_t last = (size_t)r[d - 1] * h->n1[d] * r[d];
-    hipLaunchKernelGGL(k_pack_core, g1(last), dim3(256), 0, h->stream, core_dev(h, d), h->Wa, r[d - 1], h->n1[d], r[d], RM, SS, 0);
-    hipLaunchKernelGGL(k_norm_log, dim3(1), dim3(1024), 0, h->stream, last, h->Wa, acc, 0);     // :184-188
+    pack_core(h->stream, h, d, h->Wa);
+    hipLaunchKernelGGL(k_norm_log, dim3(1), dim3(1024), 0, h->stream, core_elems(h, d), h->Wa, s.acc, 0);     // :184-188
     for (int k = 1; k <= d; k++)                                        // :190-194
-        hipLaunchKernelGGL(k_scal_core_acc, g1((size_t)r[k - 1] * h->n1[k] * r[k]), dim3(256), 0, h->stream, core_dev(h, k), r[k - 1], h->n1[k], r[k], RM, SS,
-                           acc, d, (k == d) ? 1 : 0);
+        hipLaunchKernelGGL(k_scal_core_acc, g1(core_elems(h, k)), dim3(256), 0, h->stream, core_dev(h, k), r[k - 1], h->n1[k], r[k], h->RM, h->P.SS,
+                           s.acc, d, (k == d) ? 1 : 0);
     push_ranks(h);
     HIPCHECK(hipGetLastError());
     return TTX_OK;
@@ -2714,7 +2708,7 @@ static int ort_impl(ttx_engine *h)
 static int svd_fetch(ttx_engine *h, const double *sv, const int *info, int q, int *inf2, double *svh)
 {
     if (!h->h_svd) { HIPCHECK(hipHostMalloc((void **)&h->h_svd, sizeof(double) * ((size_t)h->RM + 8))); h->h_svd[0] = 0.0; }
-    if (getenv("TTX_SVD_POLL") && atoi(getenv("TTX_SVD_POLL")) == 0) {
+    if (env_off("TTX_SVD_POLL")) {
         HIPCHECK(hipMemcpyAsync(inf2, info, sizeof(int) * 2, hipMemcpyDeviceToHost, h->stream));
         HIPCHECK(hipMemcpyAsync(svh, sv, sizeof(double) * q, hipMemcpyDeviceToHost, h->stream));
         HIPCHECK(hipStreamSynchronize(h->stream));
@@ -2743,70 +2737,47 @@ static int svd_fetch(ttx_engine *h, const double *sv, const int *info, int q, in
 }
 static int svd_impl(ttx_engine *h, double tol, int rmax)
 {
-    const int d = h->d, RM = h->RM; const size_t SS = h->P.SS;
+    const int d = h->d;
     if (d <= 1) return TTX_OK;
     int rc = ort_impl(h);
     if (rc) return rc;
     std::vector<int32_t> &r = h->rfinal;
-    double *Rm = h->Sm, *Rt = Rm + (size_t)RM * RM, *Vb = Rt + (size_t)RM * RM, *US = Vb + (size_t)RM * RM, *Vs = US + (size_t)RM * RM;
-    double *tau = h->Sm + 8 * (size_t)RM * RM, *sv = tau + RM;
-    int *perm = h->Si, *info = h->Si + RM;
+    const TtScratch s(h);
     double lognrm = 0.0, s2;
     int e2 = 0;
-    std::vector<double> svh(RM);
+    std::vector<double> svh(h->RM);
     for (int k = d; k >= 2; k--) {                                      // lib/tt.f90:329-356
-        const int mm = r[k - 1], n = h->n1[k], nn = n * r[k], kk = r[k - 2] * h->n1[k - 1];
-        if (mm > nn) {
-            // tall unfolding (only possible for trains that do not come from a cross): A (mm x nn) = Q R, R = Ub S Vb^T
-            //   =>  A = (Q Ub S) Vb^T: Q Ub S goes into the previous core, Vb^T is the new core
-            hipLaunchKernelGGL(k_pack_core, g1((size_t)mm * nn), dim3(256), 0, h->stream, core_dev(h, k), h->Wa, mm, n, r[k], RM, SS, 0);
-            if ((rc = qr(h, mm, nn, h->Wa, Rm, tau))) return rc;        // Wa -> Q (mm x nn), Rm = R (nn x nn)
-            if ((rc = jacobi(h, nn, nn, Rm, Vb, sv, perm, info, tol, rmax))) return rc;
-            int inf2[2];
-            if ((rc = svd_fetch(h, sv, info, nn, inf2, svh.data()))) return rc;
-            const int rr = inf2[0];
-            const double nrm = host_norm(svh.data(), rr);
-            if (nrm != 0.0) lognrm += std::log(nrm);
-            hipLaunchKernelGGL(k_take_cols, g1((size_t)nn * rr), dim3(256), 0, h->stream, nn, rr, Rm, nn, perm, sv, nrm != 0.0 ? 1.0 / nrm : 1.0, US);
-            gemm(h, mm, rr, nn, h->Wa, mm, US, nn, h->Wd, mm);          // Q Ub S  (mm x rr)
-            hipLaunchKernelGGL(k_pack_core, g1((size_t)kk * mm), dim3(256), 0, h->stream, core_dev(h, k - 1), h->Wb, r[k - 2], h->n1[k - 1], mm, RM, SS, 0);
-            gemm(h, kk, rr, mm, h->Wb, kk, h->Wd, mm, h->Wc, kk);
-            hipLaunchKernelGGL(k_unpack_core, g1((size_t)kk * rr), dim3(256), 0, h->stream, core_dev(h, k - 1), h->Wc, r[k - 2], h->n1[k - 1], rr, RM, SS, 0, 1.0);
-            hipLaunchKernelGGL(k_take_cols, g1((size_t)nn * rr), dim3(256), 0, h->stream, nn, rr, Vb, nn, perm, (const double *)nullptr, 1.0, Vs);
-            hipLaunchKernelGGL(k_unpack_core, g1((size_t)rr * nn), dim3(256), 0, h->stream, core_dev(h, k), Vs, rr, n, r[k], RM, SS, 1, 1.0);
-            r[k - 1] = rr;
-            continue;
-        }
-        // A (mm x nn) = R1^T Q1^T with A^T = Q1 R1 ; R1^T = Ub S Vb^T  =>  A = Ub S (Q1 Vb)^T
-        hipLaunchKernelGGL(k_pack_core, g1((size_t)mm * nn), dim3(256), 0, h->stream, core_dev(h, k), h->Wa, mm, n, r[k], RM, SS, 1);
-        if ((rc = qr(h, nn, mm, h->Wa, Rm, tau))) return rc;            // Wa -> Q1 (nn x mm), Rm = R1 (mm x mm)
-        hipLaunchKernelGGL(k_transpose, g1((size_t)mm * mm), dim3(256), 0, h->stream, mm, mm, Rm, Rt);
-        if ((rc = jacobi(h, mm, mm, Rt, Vb, sv, perm, info, tol, rmax))) return rc;
+        const int mm = r[k - 1], nn = h->n1[k] * r[k], q = std::min(mm, nn);
+        // the unfolding A (mm x nn) of core k, with a q x q triangle X = Ub S Vb^T for the Jacobi step:
+        //   tall (mm > nn, only possible for trains that do not come from a cross): A = Q R, X = R  =>  A = (Q Ub S) Vb^T
+        //   wide: A^T = Q1 R1, X = R1^T                                                            =>  A = (Ub S) (Q1 Vb)^T
+        const bool tall = mm > nn;
+        double *X = tall ? s.Rm : s.Rt;
+        pack_core(h->stream, h, k, h->Wa, tall ? 0 : 1);
+        if ((rc = qr(h, std::max(mm, nn), q, h->Wa, s.Rm, s.tau))) return rc;   // Wa -> Q (mm x nn) or Q1 (nn x mm), Rm = R or R1
+        if (!tall) hipLaunchKernelGGL(k_transpose, g1((size_t)mm * mm), dim3(256), 0, h->stream, mm, mm, s.Rm, s.Rt);
+        if ((rc = jacobi(h, q, q, X, s.Vb, s.sv, s.perm, s.info, tol, rmax))) return rc;
         int inf[2];
-        if ((rc = svd_fetch(h, sv, info, mm, inf, svh.data()))) return rc;
+        if ((rc = svd_fetch(h, s.sv, s.info, q, inf, svh.data()))) return rc;
         const int rr = inf[0];
-        if (getenv("TTX_JAC_TRACE")) fprintf(stderr, "svd core %d: %d x %d, %d Jacobi sweeps, rank %d\n", k, mm, mm, inf[1], rr);
+        if (getenv("TTX_JAC_TRACE")) fprintf(stderr, "svd core %d: %d x %d, %d Jacobi sweeps, rank %d\n", k, q, q, inf[1], rr);
         const double nrm = host_norm(svh.data(), rr);
         if (nrm != 0.0) lognrm += std::log(nrm);
-        hipLaunchKernelGGL(k_take_cols, g1((size_t)mm * rr), dim3(256), 0, h->stream, mm, rr, Rt, mm, perm, sv, nrm != 0.0 ? 1.0 / nrm : 1.0, US);
-        hipLaunchKernelGGL(k_pack_core, g1((size_t)kk * mm), dim3(256), 0, h->stream, core_dev(h, k - 1), h->Wb, r[k - 2], h->n1[k - 1], mm, RM, SS, 0);
-        gemm(h, kk, rr, mm, h->Wb, kk, US, mm, h->Wc, kk);              // U S pushed into the previous core (:344)
-        hipLaunchKernelGGL(k_unpack_core, g1((size_t)kk * rr), dim3(256), 0, h->stream, core_dev(h, k - 1), h->Wc, r[k - 2], h->n1[k - 1], rr, RM, SS, 0, 1.0);
-        hipLaunchKernelGGL(k_take_cols, g1((size_t)mm * rr), dim3(256), 0, h->stream, mm, rr, Vb, mm, perm, (const double *)nullptr, 1.0, Vs);
-        gemm(h, nn, rr, mm, h->Wa, nn, Vs, mm, h->Wd, nn);              // Y = Q1 Vb(:, kept)  (nn x rr)
-        hipLaunchKernelGGL(k_unpack_core, g1((size_t)rr * nn), dim3(256), 0, h->stream, core_dev(h, k), h->Wd, rr, n, r[k], RM, SS, 1, 1.0);
+        take_cols(h, q, rr, X, s.perm, s.sv, nrm != 0.0 ? 1.0 / nrm : 1.0, s.US);
+        if (tall) gemm(h, mm, rr, nn, h->Wa, mm, s.US, nn, h->Wd, mm);  // Q Ub S  (mm x rr)
+        push_left(h, k, tall ? h->Wd : s.US, rr);                       // into the previous core
+        take_cols(h, q, rr, s.Vb, s.perm, nullptr, 1.0, s.Vs);
+        if (!tall) gemm(h, nn, rr, mm, h->Wa, nn, s.Vs, mm, h->Wd, nn); // Y = Q1 Vb(:, kept)  (nn x rr)
+        unpack_core(h, k, tall ? s.Vs : h->Wd, rr, r[k], 1);            // the new core k is the transpose of Vb(:, kept) or of Y
         r[k - 1] = rr;
     }
-    const size_t first = (size_t)r[0] * h->n1[1] * r[1];
-    hipLaunchKernelGGL(k_pack_core, g1(first), dim3(256), 0, h->stream, core_dev(h, 1), h->Wa, r[0], h->n1[1], r[1], RM, SS, 0);
-    if ((rc = sumsq(h, first, h->Wa, &s2, &e2))) return rc;
+    pack_core(h->stream, h, 1, h->Wa);
+    if ((rc = sumsq(h, core_elems(h, 1), h->Wa, &s2, &e2))) return rc;
     double nf = std::ldexp(std::sqrt(s2), e2), firstscale = 1.0;
     if (nf != 0.0) { firstscale = 1.0 / nf; lognrm += std::log(nf); }
     lognrm /= d;
     const double nrm = std::exp(lognrm);
-    for (int k = 1; k <= d; k++)
-        hipLaunchKernelGGL(k_scal_core, g1((size_t)r[k - 1] * h->n1[k] * r[k]), dim3(256), 0, h->stream, core_dev(h, k), r[k - 1], h->n1[k], r[k], RM, SS,
-                           (k == 1) ? nrm * firstscale : nrm);
+    for (int k = 1; k <= d; k++) scal_core(h, k, (k == 1) ? nrm * firstscale : nrm);
     push_ranks(h);
     HIPCHECK(hipGetLastError());
     return TTX_OK;
@@ -2823,32 +2794,34 @@ extern "C" int ttx_svd(ttx_engine *h, double tol, int32_t rmax)
     return rc ? rc : svd_impl(h, tol, rmax);
 }
 
-// dtt_norm / dtt_lognrm: the norm of the core that carries it after svd (tol >= 0) or ort (tol < 0), as sqrt(*s2) 2^*e
+// dtt_norm / dtt_lognrm: the norm of the core that carries it after svd (tol >= 0: core 1) or ort (tol < 0: core d), as sqrt(*s2) 2^*e
 static int core_norm_impl(ttx_engine *h, double tol, double *s2_out, int *e_out, const char *who)
 {
     int rc = tt_prepare(h, who);
     if (rc) return rc;
-    // the reference works on a copy (tmp = arg, lib/tt.f90:1082): back the cores and ranks up, restore afterwards
+    // the reference works on a copy (tmp = arg, lib/tt.f90:1082): back the cores and ranks up; they come back on every path out
     const size_t tot = (size_t)h->G * h->NC * h->P.CS;
     if (!h->bak) { if ((rc = dev_alloc(h, &h->bak, tot))) return rc; }
     HIPCHECK(hipMemcpyAsync(h->bak, h->P.arg, sizeof(double) * tot, hipMemcpyDeviceToDevice, h->stream));
-    std::vector<int32_t> rsave = h->rfinal;
-    const int d = h->d;
-    if (tol >= 0.0) {
-        rc = svd_impl(h, tol, 0);
-        if (!rc) { const size_t sz = (size_t)h->rfinal[0] * h->n1[1] * h->rfinal[1];
-                   hipLaunchKernelGGL(k_pack_core, g1(sz), dim3(256), 0, h->stream, core_dev(h, 1), h->Wa, h->rfinal[0], h->n1[1], h->rfinal[1], h->RM, h->P.SS, 0);
-                   rc = sumsq(h, sz, h->Wa, s2_out, e_out); }
-    } else {
-        rc = ort_impl(h);
-        if (!rc) { const size_t sz = (size_t)h->rfinal[d - 1] * h->n1[d] * h->rfinal[d];
-                   hipLaunchKernelGGL(k_pack_core, g1(sz), dim3(256), 0, h->stream, core_dev(h, d), h->Wa, h->rfinal[d - 1], h->n1[d], h->rfinal[d], h->RM, h->P.SS, 0);
-                   rc = sumsq(h, sz, h->Wa, s2_out, e_out); }
-    }
-    HIPCHECK(hipMemcpyAsync(h->P.arg, h->bak, sizeof(double) * tot, hipMemcpyDeviceToDevice, h->stream));
-    h->rfinal = rsave;
-    push_ranks(h);
-    return rc;
+    struct Restore {
+        ttx_engine *h; size_t tot; std::vector<int32_t> ranks; bool done = false;
+        int run()
+        {
+            done = true;
+            const hipError_t e = hipMemcpyAsync(h->P.arg, h->bak, sizeof(double) * tot, hipMemcpyDeviceToDevice, h->stream);
+            h->rfinal = ranks;
+            push_ranks(h);
+            HIPCHECK(e);
+            return TTX_OK;
+        }
+        ~Restore() { if (!done) (void)run(); }
+    } restore{h, tot, h->rfinal};
+    const int kn = tol >= 0.0 ? 1 : h->d;
+    if ((rc = tol >= 0.0 ? svd_impl(h, tol, 0) : ort_impl(h))) return rc;
+    pack_core(h->stream, h, kn, h->Wa);
+    rc = sumsq(h, core_elems(h, kn), h->Wa, s2_out, e_out);
+    const int back = restore.run();
+    return rc ? rc : back;
 }
 extern "C" int ttx_norm(ttx_engine *h, double tol, double *val)
 {
@@ -2882,19 +2855,19 @@ extern "C" int ttx_dot(ttx_engine *x, ttx_engine *y, double *val)
     for (int k = 1; k <= x->d; k++) if (x->n1[k] != y->n1[k]) return fail(TTX_EINVAL, "dtt_dot: sizes not match");
     if (x->cfg.device != y->cfg.device) return fail(TTX_EINVAL, "dtt_dot: both tensor trains must live on the same GPU");
     const int d = x->d;
-    double *phi = x->Sm, *phi2 = x->Sm + (size_t)x->RM * x->RM;        // needs rx*ry <= RM_x^2: checked below
+    double *phi = TtScratch(x).Rm, *phi2 = TtScratch(x).Rt;           // the r x r interface matrices: rx*ry <= RM_x^2 is checked below
     const double one = 1.0;
     HIPCHECK(hipMemcpyAsync(phi, &one, sizeof(double), hipMemcpyHostToDevice, x->stream));
     HIPCHECK(hipStreamSynchronize(y->stream));
     for (int i = 1; i <= d; i++) {
         const int rx0 = x->rfinal[i - 1], rx1 = x->rfinal[i], ry0 = y->rfinal[i - 1], ry1 = y->rfinal[i], n = x->n1[i];
-        // x's scratch holds: core i of y packed (ry0*n*ry1 -> Wb), phi*core (rx0*n*ry1 -> Wc), the r x r interface matrices (Sm)
+        // x's scratch holds: core i of y packed (ry0*n*ry1 -> Wb), phi*core (rx0*n*ry1 -> Wc), the interface matrices
         if ((size_t)rx1 * ry1 > (size_t)x->RM * x->RM || (size_t)rx0 * ry0 > (size_t)x->RM * x->RM || (size_t)rx0 * n * ry1 > x->P.CS ||
             (size_t)ry0 * n * ry1 > x->P.CS)
             return fail(TTX_EINVAL, "dtt_dot: ranks of y exceed the work space of x (call dot_product(y, x) or raise maxrank of x)");
-        hipLaunchKernelGGL(k_pack_core, g1((size_t)ry0 * n * ry1), dim3(256), 0, x->stream, core_dev(y, i), x->Wb, ry0, n, ry1, y->RM, y->P.SS, 0);
+        pack_core(x->stream, y, i, x->Wb);
         gemm(x, rx0, n * ry1, ry0, phi, rx0, x->Wb, ry0, x->Wc, rx0);                       // :1169
-        hipLaunchKernelGGL(k_pack_core, g1((size_t)rx0 * n * rx1), dim3(256), 0, x->stream, core_dev(x, i), x->Wa, rx0, n, rx1, x->RM, x->P.SS, 0);
+        pack_core(x->stream, x, i, x->Wa);
         hipLaunchKernelGGL(k_transpose, g1((size_t)rx0 * n * rx1), dim3(256), 0, x->stream, rx0 * n, rx1, x->Wa, x->Wd);
         gemm(x, rx1, ry1, rx0 * n, x->Wd, rx1, x->Wc, rx0 * n, phi2, rx1);                  // :1170
         std::swap(phi, phi2);
@@ -2905,6 +2878,35 @@ extern "C" int ttx_dot(ttx_engine *x, ttx_engine *y, double *val)
     return TTX_OK;
 }
 
+// ztt_quad, the part both entry points share: the per-core matrices sum_j w(j) U_k(:, j, :) of cores lo..hi for nf weight vectors
+struct ZquadStage { size_t lds; int *dr; double *dtq, *dout; };
+static int zquad_stage(ttx_engine *h, int32_t nf, const double *w, int lo, int hi, DevTmp &tmp, ZquadStage &z)
+{
+    const int d = h->d, RM = h->RM;
+    // the chain kernels keep two complex RM x RM matrices in LDS
+    z.lds = sizeof(double) * 4 * (size_t)RM * RM;
+    if (z.lds > TTX_LDS_DEVICE) return fail(TTX_EINVAL, "ztt_quad: maxrank %d needs %zu bytes of LDS for the chain (limit 160 KB, maxrank <= 71)", RM, z.lds);
+    size_t sumn = 0;
+    for (int k = 1; k <= d; k++) sumn += h->n1[k];
+    std::vector<const double *> cp(d + 2, nullptr);
+    for (int k = lo; k <= hi; k++) cp[k] = core_dev(h, k);
+    const std::vector<int> rr(h->rfinal.begin(), h->rfinal.end());
+    double *dw; const double **dcp;
+    HIPCHECK(tmp.alloc(&dw, 2 * sumn * nf)); HIPCHECK(tmp.alloc(&z.dtq, (size_t)nf * (d + 1) * 2 * RM * RM));
+    HIPCHECK(tmp.alloc(&z.dout, 2 * (size_t)nf)); HIPCHECK(tmp.alloc(&dcp, d + 2)); HIPCHECK(tmp.alloc(&z.dr, d + 1));
+    HIPCHECK(hipMemcpy(dw, w, sizeof(double) * 2 * sumn * nf, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(dcp, cp.data(), sizeof(double *) * (d + 2), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(z.dr, rr.data(), sizeof(int) * (d + 1), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_zquad_build, dim3(d, nf), dim3(256), 0, h->stream, d, RM, h->NM, h->P.SS, h->P.n, (const int *)z.dr, (const double *const *)dcp, (const double *)dw, 2 * sumn, z.dtq);
+    return TTX_OK;
+}
+static int zquad_finish(ttx_engine *h, int32_t nf, const ZquadStage &z, double *out)
+{
+    HIPCHECK(hipMemcpyAsync(out, z.dout, sizeof(double) * 2 * nf, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipGetLastError());
+    return TTX_OK;
+}
 // ztt_quad of a MULTI-PROCESS job (lib/dmrgg.f90:1418-1523 is collective over mybonds): every process chains the matrices of the
 // cores it holds, the partial products travel by a SUM all-reduce into zero-padded slots, every process folds them in rank order
 static int zquad_multi(ttx_engine *h, int32_t nf, const double *w, double *out)
@@ -2912,75 +2914,41 @@ static int zquad_multi(ttx_engine *h, int32_t nf, const double *w, double *out)
     if (!h->ran) return fail(TTX_ESTATE, "ztt_quad: run dtt_dmrgg first");
     HIPCHECK(hipSetDevice(h->cfg.device));
     const int d = h->d, RM = h->RM, W = h->W, nproc = h->cfg.nproc;
-    const size_t lds = sizeof(double) * 4 * (size_t)RM * RM;
-    if (lds > 160 * 1024) return fail(TTX_EINVAL, "ztt_quad: maxrank %d needs %zu bytes of LDS for the chain (limit 160 KB, maxrank <= 71)", RM, lds);
-    size_t sumn = 0;
-    for (int k = 1; k <= d; k++) sumn += h->n1[k];
     auto lo_of = [&](int wr) { return h->own[(int)((long long)nproc * wr / W)]; };
     auto hi_of = [&](int wr) { const int ge = (int)((long long)nproc * (wr + 1) / W); return ge == nproc ? d : h->own[ge] - 1; };
     const int plo = lo_of(h->wrank), phi = hi_of(h->wrank);
-    std::vector<const double *> cp(d + 2, nullptr);
-    for (int k = plo; k <= phi; k++) cp[k] = core_dev(h, k);
-    std::vector<int> rr(h->rfinal.begin(), h->rfinal.end()), dims(2 * W);
-    for (int wr = 0; wr < W; wr++) { dims[2 * wr] = rr[lo_of(wr) - 1]; dims[2 * wr + 1] = rr[hi_of(wr)]; }
-    struct Tmp { std::vector<void *> p; ~Tmp() { for (void *q : p) (void)hipFree(q); } } tmp;
-    auto dalloc = [&](void **q, size_t bytes) -> hipError_t { hipError_t e = hipMalloc(q, bytes); if (e == hipSuccess) tmp.p.push_back(*q); return e; };
-    double *dw, *dtq, *dout, *dpart; const double **dcp; int *dr, *ddims;
+    std::vector<int> dims(2 * W);
+    for (int wr = 0; wr < W; wr++) { dims[2 * wr] = h->rfinal[lo_of(wr) - 1]; dims[2 * wr + 1] = h->rfinal[hi_of(wr)]; }
+    DevTmp tmp;
+    double *dpart; int *ddims;
     const size_t npart = (size_t)nf * W * 2 * RM * RM;
-    HIPCHECK(dalloc((void **)&dw, sizeof(double) * 2 * sumn * nf)); HIPCHECK(dalloc((void **)&dtq, sizeof(double) * (size_t)nf * (d + 1) * 2 * RM * RM));
-    HIPCHECK(dalloc((void **)&dout, sizeof(double) * 2 * nf)); HIPCHECK(dalloc((void **)&dcp, sizeof(double *) * (d + 2))); HIPCHECK(dalloc((void **)&dr, sizeof(int) * (d + 1)));
-    HIPCHECK(dalloc((void **)&dpart, sizeof(double) * npart)); HIPCHECK(dalloc((void **)&ddims, sizeof(int) * 2 * W));
-    HIPCHECK(hipMemcpy(dw, w, sizeof(double) * 2 * sumn * nf, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(dcp, cp.data(), sizeof(double *) * (d + 2), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(dr, rr.data(), sizeof(int) * (d + 1), hipMemcpyHostToDevice));
+    HIPCHECK(tmp.alloc(&dpart, npart)); HIPCHECK(tmp.alloc(&ddims, 2 * (size_t)W));
     HIPCHECK(hipMemcpy(ddims, dims.data(), sizeof(int) * 2 * W, hipMemcpyHostToDevice));
     HIPCHECK(hipMemsetAsync(dpart, 0, sizeof(double) * npart, h->stream));
-    hipLaunchKernelGGL(k_zquad_build, dim3(d, nf), dim3(256), 0, h->stream, d, RM, h->NM, h->P.SS, h->P.n, (const int *)dr, (const double *const *)dcp, (const double *)dw, 2 * sumn, dtq);
-    if (int rc_ = ensure_lds(h, reinterpret_cast<const void *>(k_zquad_chain_seg), lds)) return rc_;
-    if (int rc_ = ensure_lds(h, reinterpret_cast<const void *>(k_zquad_fold), lds)) return rc_;
-    hipLaunchKernelGGL(k_zquad_chain_seg, dim3(nf), dim3(256), lds, h->stream, d, RM, (const int *)dr, (const double *)dtq, plo, phi, h->wrank, W, dpart);
-    if (int rc_ = allreduce_big(h, dpart, npart)) return rc_;
-    hipLaunchKernelGGL(k_zquad_fold, dim3(nf), dim3(256), lds, h->stream, RM, W, (const int *)ddims, (const double *)dpart, dout);
-    HIPCHECK(hipMemcpyAsync(out, dout, sizeof(double) * 2 * nf, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    HIPCHECK(hipGetLastError());
+    ZquadStage z;
+    int rc = zquad_stage(h, nf, w, plo, phi, tmp, z);
+    if (rc) return rc;
+    if ((rc = ensure_lds(h, reinterpret_cast<const void *>(k_zquad_chain_seg), z.lds)) || (rc = ensure_lds(h, reinterpret_cast<const void *>(k_zquad_fold), z.lds))) return rc;
+    hipLaunchKernelGGL(k_zquad_chain_seg, dim3(nf), dim3(256), z.lds, h->stream, d, RM, (const int *)z.dr, (const double *)z.dtq, plo, phi, h->wrank, W, dpart);
+    if ((rc = allreduce_big(h, dpart, npart))) return rc;
+    hipLaunchKernelGGL(k_zquad_fold, dim3(nf), dim3(256), z.lds, h->stream, RM, W, (const int *)ddims, (const double *)dpart, z.dout);
+    if ((rc = zquad_finish(h, nf, z, out))) return rc;
     if (h->cb_error) return fail(TTX_EHIP, "host transport: a sendrecv / allreduce callback failed");
     return TTX_OK;
 }
 
 extern "C" int ttx_zquad(ttx_engine *h, int32_t nf, const double *w, double *out)
 {
-    if (h && h->W > 1) { if (nf < 1 || !w || !out) return fail(TTX_EINVAL, "ztt_quad: bad argument"); return zquad_multi(h, nf, w, out); }
-    int rc = tt_prepare(h, "ztt_quad");
-    if (rc) return rc;
+    const bool multi = h && h->W > 1;
+    if (!multi) if (int rc = tt_prepare(h, "ztt_quad")) return rc;
     if (nf < 1 || !w || !out) return fail(TTX_EINVAL, "ztt_quad: bad argument");
-    const int d = h->d, RM = h->RM;
-    size_t sumn = 0;
-    for (int k = 1; k <= d; k++) sumn += h->n1[k];
-    std::vector<const double *> cp(d + 2, nullptr);
-    for (int k = 1; k <= d; k++) cp[k] = core_dev(h, k);
-    std::vector<int> rr(h->rfinal.begin(), h->rfinal.end());
-    // the chain kernel keeps two complex r x r matrices of the LARGEST OCCURRING rank in LDS
-    int rmax = 1;
-    for (int k = 0; k <= d; k++) rmax = std::max(rmax, rr[k]);
-    const size_t lds = sizeof(double) * 4 * (size_t)RM * RM;
-    if (lds > 160 * 1024) return fail(TTX_EINVAL, "ztt_quad: maxrank %d needs %zu bytes of LDS for the chain (limit 160 KB, maxrank <= 71)", RM, lds);
-    // the five temporaries are released on every path out of this function
-    struct Tmp { std::vector<void *> p; ~Tmp() { for (void *q : p) (void)hipFree(q); } } tmp;
-    auto dalloc = [&](void **q, size_t bytes) -> hipError_t { hipError_t e = hipMalloc(q, bytes); if (e == hipSuccess) tmp.p.push_back(*q); return e; };
-    double *dw, *dtq, *dout; const double **dcp; int *dr;
-    HIPCHECK(dalloc((void **)&dw, sizeof(double) * 2 * sumn * nf)); HIPCHECK(dalloc((void **)&dtq, sizeof(double) * (size_t)nf * (d + 1) * 2 * RM * RM));
-    HIPCHECK(dalloc((void **)&dout, sizeof(double) * 2 * nf)); HIPCHECK(dalloc((void **)&dcp, sizeof(double *) * (d + 2))); HIPCHECK(dalloc((void **)&dr, sizeof(int) * (d + 1)));
-    HIPCHECK(hipMemcpy(dw, w, sizeof(double) * 2 * sumn * nf, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(dcp, cp.data(), sizeof(double *) * (d + 2), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(dr, rr.data(), sizeof(int) * (d + 1), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_zquad_build, dim3(d, nf), dim3(256), 0, h->stream, d, RM, h->NM, h->P.SS, h->P.n, (const int *)dr, (const double *const *)dcp, (const double *)dw, 2 * sumn, dtq);
-    if (int rc_ = ensure_lds(h, reinterpret_cast<const void *>(k_zquad_chain), lds)) return rc_;
-    hipLaunchKernelGGL(k_zquad_chain, dim3(nf), dim3(256), lds, h->stream, d, RM, (const int *)dr, (const double *)dtq, dout);
-    HIPCHECK(hipMemcpyAsync(out, dout, sizeof(double) * 2 * nf, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    HIPCHECK(hipGetLastError());
-    return TTX_OK;
+    if (multi) return zquad_multi(h, nf, w, out);
+    DevTmp tmp;
+    ZquadStage z;
+    int rc = zquad_stage(h, nf, w, 1, h->d, tmp, z);
+    if (rc || (rc = ensure_lds(h, reinterpret_cast<const void *>(k_zquad_chain), z.lds))) return rc;
+    hipLaunchKernelGGL(k_zquad_chain, dim3(nf), dim3(256), z.lds, h->stream, h->d, h->RM, (const int *)z.dr, (const double *)z.dtq, z.dout);
+    return zquad_finish(h, nf, z, out);
 }
 
 extern "C" int ttx_ijk(ttx_engine *h, const int32_t *ind, double *val)
@@ -2991,12 +2959,12 @@ extern "C" int ttx_ijk(ttx_engine *h, const int32_t *ind, double *val)
     const int d = h->d;
     for (int k = 1; k <= d; k++) if (ind[k - 1] <= 0 || ind[k - 1] > h->n1[k]) { *val = -3.0; return TTX_OK; }   // lib/tt.f90:639
     // x = U_d(:, ind_d, 1); for i = d-1..1: x = U_i(:, ind_i, :) x -- matrix-vector steps through the GEMM kernel
-    double *xv = h->Sm, *zv = h->Sm + h->RM;
-    hipLaunchKernelGGL(k_pack_core, g1((size_t)h->rfinal[d - 1] * h->n1[d] * h->rfinal[d]), dim3(256), 0, h->stream, core_dev(h, d), h->Wa, h->rfinal[d - 1], h->n1[d], h->rfinal[d], h->RM, h->P.SS, 0);
+    double *xv = TtScratch(h).Rm, *zv = xv + h->RM;                   // two vectors of RM at the head of the scratch
+    pack_core(h->stream, h, d, h->Wa);
     HIPCHECK(hipMemcpyAsync(xv, h->Wa + (size_t)h->rfinal[d - 1] * (ind[d - 1] - 1), sizeof(double) * h->rfinal[d - 1], hipMemcpyDeviceToDevice, h->stream));
     for (int i = d - 1; i >= 1; i--) {
         const int q0 = h->rfinal[i - 1], q1 = h->rfinal[i], n = h->n1[i];
-        hipLaunchKernelGGL(k_pack_core, g1((size_t)q0 * n * q1), dim3(256), 0, h->stream, core_dev(h, i), h->Wa, q0, n, q1, h->RM, h->P.SS, 0);
+        pack_core(h->stream, h, i, h->Wa);
         gemm(h, q0, 1, q1, h->Wa + (size_t)q0 * (ind[i - 1] - 1), q0 * n, xv, q1, zv, q0);
         std::swap(xv, zv);
     }
