@@ -38,6 +38,7 @@ extern "C" {
  * box exceeds the range of the integrand's own sin / cos (2^19).  Mode sizes may differ.  TTX_ARITH=fast leaves it exact. */
 #define TTX_FUN_COSCOEFF 5
 #define TTX_FUN_DEVICE 6   /* any user `fun`, evaluated on the DEVICE by a code object the caller supplies: ttx_set_integrand_device */
+#define TTX_FUN_TRAINS 7   /* fun(i) = g(x_1(i), ..., x_m(i)), x_t resident trains on the engine's device: ttx_set_integrand_trains */
 
 #define TTX_ARITH_EXACT 0
 #define TTX_ARITH_FAST 1
@@ -145,8 +146,46 @@ int64_t ttx_host_calls(const ttx_engine *h);                      /* calls of `f
 int ttx_set_integrand_device(ttx_engine *h, const void *image, int64_t nbytes, const char *name, const double *par, int32_t npar);
 int ttx_set_integrand_device_file(ttx_engine *h, const char *path, const char *name, const double *par, int32_t npar);
 /* the loaded integrand at npts multi-indices (ind row-major, 1-based; out of range: TTX_EINVAL), through the code object's list
- * kernel: check that a device function computes what its author thinks before a sweep depends on it */
+ * kernel: check that a device function computes what its author thinks before a sweep depends on it.  An engine created with
+ * TTX_FUN_TRAINS is served too: the m operands at the listed indices, then the combiner. */
 int ttx_eval_device(ttx_engine *h, int64_t npts, const int32_t *ind /* [npts][d] */, double *out /* [npts] */);
+
+/* Cross approximation of a FUNCTION OF RESIDENT TRAINS, fun(i) = g(x_1(i), ..., x_m(i)), for an engine created with fun_id =
+ * TTX_FUN_TRAINS (ttx_config.par / npar are not used; d <= 2048; one process, any number of bond groups): squares and products whose
+ * Hadamard ranks pass 128, quotients, roots, products of three and more trains, without a core leaving the device (TT-Toolbox:
+ * multifuncrs).  The sweep is the one of TTX_FUN_DEVICE; between the two passes of every evaluating kernel one kernel (k_tf_slots,
+ * ttcross_amd/csrc/ttx_trainfun.h) evaluates every operand at the requested multi-indices, one wave per element, in the operation
+ * sequence of ttx_ijk_batch's TTX_EVAL_EXACT, and applies the combiner: the value of operand t is ttx_ijk_batch(x[t], ind,
+ * TTX_EVAL_EXACT) bit for bit, and a run equals, bit for bit, a TTX_FUN_HOST run whose callback walks the same cores in that order.
+ * The built-in combiners are plain IEEE operations in the order written here; TTX_ARITH=fast leaves the integrand exact.
+ *   m, x  : 1 <= m <= TTX_TRAINS_MAX engines that hold a train on the engine's device, with the engine's mode sizes n(1:d) and ranks
+ *           up to 128; the same engine may appear several times (x * x).  The engine records the HANDLES.  At the start of every
+ *           ttx_run, ttx_accchk and ttx_eval_device it looks at the operands again and rebuilds their device blocks (core pointers,
+ *           ranks) in its own work space: an operand that was ttx_ort-ed or ttx_svd-ed in between is seen with its new ranks, and
+ *           an operand stays free for calls of its own between runs.
+ *           LIFETIME: the caller keeps every operand alive, and leaves it unchanged, while such a call is running, and does not
+ *           destroy an operand before the engine (or sets other operands first).
+ *   image, nbytes / path, name, par, npar : a loaded combiner, TTX_DEVICE_COMBINER(name) of include/ttx_device_fun.h, with the
+ *           conventions and refusals of ttx_set_integrand_device (par is COPIED to the device)
+ * TTX_ESTATE: engine not created with TTX_FUN_TRAINS; an operand without a train.  TTX_EINVAL: m outside 1..TTX_TRAINS_MAX, an op
+ * that does not fit m, a null operand, an operand spread over processes (as ttx_ijk refuses it), on another device, with other mode
+ * sizes, or the engine itself; every message names the operand.  After a refusal the engine is as before.  Setting again replaces
+ * the operands and the combiner; a replica (ttx_replicate) shares them.  ttx_run / ttx_accchk / ttx_eval_device before a
+ * successful set, and ttx_comm_init / ttx_comm_init_shm / ttx_set_transport on such an engine: TTX_ESTATE.
+ * ttx_trainfun_last: of the last ttx_run or ttx_eval_device, the launches of the slot (list) kernel, the elements it evaluated and,
+ * with ttx_set_profile on, its milliseconds (HIP events; 0 otherwise).  Any pointer may be NULL.
+ * Added without a new ttx_version: look the symbols up. */
+#define TTX_TRAINS_MAX 8
+#define TTX_TOP_PRODUCT 1     /* p = v[0]; p = p * v[t], t = 1 .. m-1 (1 <= m <= TTX_TRAINS_MAX) */
+#define TTX_TOP_RATIO   2     /* v[0] / v[1]           (m == 2)                                  */
+#define TTX_TOP_SQRTABS 3     /* sqrt(fabs(v[0]))      (m == 1)                                  */
+#define TTX_TOP_DEVICE  4     /* a loaded combiner: ttx_set_integrand_trains_device              */
+int ttx_set_integrand_trains(ttx_engine *h, int32_t m, ttx_engine *const *x, int32_t op);
+int ttx_set_integrand_trains_device(ttx_engine *h, int32_t m, ttx_engine *const *x, const void *image, int64_t nbytes,
+                                    const char *name, const double *par, int32_t npar);
+int ttx_set_integrand_trains_device_file(ttx_engine *h, int32_t m, ttx_engine *const *x, const char *path,
+                                         const char *name, const double *par, int32_t npar);
+int ttx_trainfun_last(const ttx_engine *h, double *ms, int64_t *launches, int64_t *elements);
 
 /* dtt_dmrgg itself: initial cross, sweeps until maxrank / 3 strikes, finalisation dtt_lua (lib/dmrgg.f90:151-1049) */
 int ttx_run(ttx_engine *h);

@@ -199,4 +199,40 @@ __device__ __forceinline__ unsigned ttx_devfun_flags16(const unsigned char *hreq
         }                                                                                                                         \
     }
 
+/* ---- combiner of an integrand of trains (TTX_FUN_TRAINS, TTX_TOP_DEVICE) ----------------------------------------------------------
+ * TTX_DEVICE_COMBINER(name) for
+ *     __device__ double name(int m, const double *v, int d, ttx_ind ind, const int *n, const double *par)
+ * v[0 .. m-1] are the values of the m operand trains at the multi-index ind, computed by the engine (each bit for bit what
+ * ttx_ijk_batch gives in its exact mode); the function returns g(v, ind).  Lane form.  The macro generates
+ *   ttx_devcomb_info_NAME   a ttx_devfun_info as above
+ *   ttx_devcomb_slots_NAME  (int m, int d, const int *n, const double *par, long long nslot, const short *hidx, unsigned char *hreq,
+ *                            const double *tval, double *hval): tval[nslot][m] holds the operand values of every raised slot.  The
+ *                           contract of ttx_devfun_slots_NAME: write hval[s], THEN clear hreq[s]; touch no other slot; any grid.
+ *   ttx_devcomb_list_NAME   (int m, int d, const int *n, const double *par, long long npts, const int *ind, const double *tval,
+ *                            double *out): the 32-bit list twin, tval[npts][m]
+ * and the file is handed to ttx_set_integrand_trains_device[_file] (include/ttx.h).  For a pivot sequence equal to a host run keep
+ * to + - * / and sqrt, in the host code's order (BIT REPRODUCIBILITY above). */
+#define TTX_DEVICE_COMBINER(NAME)                                                                                                 \
+    extern "C" __device__ __attribute__((used, visibility("default"))) const ttx_devfun_info ttx_devcomb_info_##NAME =             \
+        {TTX_DEVFUN_ABI, TTX_DEVFUN_KIND_LANE, TTX_DEVFUN_BLOCK, 0};                                                              \
+    extern "C" __global__ __launch_bounds__(TTX_DEVFUN_BLOCK) void ttx_devcomb_slots_##NAME(                                      \
+        int m, int d, const int *n, const double *par, long long nslot, const short *hidx, unsigned char *hreq, const double *tval, \
+        double *hval)                                                                                                             \
+    {                                                                                                                             \
+        for (long long s = (long long)blockIdx.x * TTX_DEVFUN_BLOCK + threadIdx.x; s < nslot; s += (long long)gridDim.x * TTX_DEVFUN_BLOCK) { \
+            if (!hreq[s]) continue;                                                                                               \
+            const ttx_ind ix = {hidx + (size_t)s * d, nullptr};                                                                   \
+            hval[s] = NAME(m, tval + (size_t)s * m, d, ix, n, par);                                                               \
+            hreq[s] = 0;                                                                                                          \
+        }                                                                                                                         \
+    }                                                                                                                             \
+    extern "C" __global__ __launch_bounds__(TTX_DEVFUN_BLOCK) void ttx_devcomb_list_##NAME(                                       \
+        int m, int d, const int *n, const double *par, long long npts, const int *ind, const double *tval, double *out)           \
+    {                                                                                                                             \
+        for (long long p = (long long)blockIdx.x * TTX_DEVFUN_BLOCK + threadIdx.x; p < npts; p += (long long)gridDim.x * TTX_DEVFUN_BLOCK) { \
+            const ttx_ind ix = {nullptr, ind + (size_t)p * d};                                                                    \
+            out[p] = NAME(m, tval + (size_t)p * m, d, ix, n, par);                                                                \
+        }                                                                                                                         \
+    }
+
 #endif

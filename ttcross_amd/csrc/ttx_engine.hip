@@ -54,6 +54,7 @@ static cluster_kernel_t cluster_kernel(int var)
 #include "ttx_contract.h"
 #include "ttx_algebra.h"
 #include "ttx_sample.h"
+#include "ttx_trainfun.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const char *fmt, ...)
@@ -125,6 +126,7 @@ enum {
     SC_XA, SC_XB, SC_SORT,              // MFMA evaluation: the two state buffers, the bucket sort
     SC_W, SC_M, SC_P, SC_SCR, SC_VEC,   // contraction: weights, M matrices, run products, their overflow, the l and s vectors
     SC_H, SC_ROW, SC_CNT,               // sampling: head tables, global rows of long modes, the failure counter
+    SC_TFUN, SC_TVAL,                   // TTX_FUN_TRAINS: the operands' blocks (core pointers, ranks) of a run, the values for a loaded combiner
     SC_NBUF
 };
 struct EvBuf { void *p = nullptr; size_t bytes = 0; };
@@ -138,6 +140,7 @@ struct OpTimer {
 enum { TM_MODESUM, TM_ALG, TM_HEAD, TM_DRAW, TM_N };    // k_ct_modesum, the algebra launch, k_sm_head, the k_sm_draw of a chunk
 
 struct DevFun;                          // a loaded device integrand (TTX_FUN_DEVICE), defined with slot_eval
+struct TrainFun;                        // the operands and the combiner of TTX_FUN_TRAINS, defined with slot_eval
 struct ttx_engine {
     ttx_config cfg;
     std::vector<int32_t> n1;            // 1-based n, size d+2
@@ -227,6 +230,15 @@ struct ttx_engine {
     const double *hfun_par = nullptr;   // the caller's par(*), passed through untouched
     // user integrand evaluated on the device by a code object the caller loaded (TTX_FUN_DEVICE): shared with replicas
     std::shared_ptr<DevFun> dfun;
+    // integrand g(x_1(i), .., x_m(i)) of resident trains (TTX_FUN_TRAINS): operand handles and combiner, shared with replicas; the
+    // operands' device blocks as this engine's run sees them (tf_prepare), the figures of ttx_trainfun_last
+    std::shared_ptr<TrainFun> tfun;
+    TfOps tf_ops{};
+    std::vector<char> tf_host;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> tf_evs;
+    bool tf_figures = false;            // the call in flight records the figures of ttx_trainfun_last (ttx_run, ttx_eval_device; not ttx_accchk)
+    int64_t tf_launches = 0, tf_elements = 0;
+    double tf_ms = 0.0;
     size_t HS = 0;
     int64_t host_calls = 0;
     int64_t n_resid = 0;                // rook half-steps of the last run that took a residual (all groups)
@@ -377,6 +389,56 @@ static int devfun_slots(ttx_engine *h)
     return TTX_OK;
 }
 
+// ---- TTX_FUN_TRAINS: fun(i) = g(x_1(i), .., x_m(i)) for resident trains x_t (ttx_trainfun.h) ------------------------------------
+// The operands are recorded as handles; their device blocks are rebuilt by tf_prepare at the start of every call that evaluates.
+struct TrainFun {
+    std::vector<ttx_engine *> x;
+    int op = 0;
+    std::shared_ptr<DevFun> comb;           // TTX_TOP_DEVICE: the loaded combiner (ttx_devcomb_* symbols)
+};
+static int tf_grid(ttx_engine *h, long long items);
+static int tf_prepare(ttx_engine *h, const char *who, bool figures);
+static int tf_finish(ttx_engine *h);
+static int tf_eval_list(ttx_engine *h, int64_t npts, const int32_t *ind, double *out);
+// with ttx_set_profile on, an event pair around the launches of one slot evaluation (collected by tf_finish)
+struct TfScope {
+    ttx_engine *h; hipEvent_t a = nullptr, b = nullptr;
+    bool on;
+    explicit TfScope(ttx_engine *h_) : h(h_), on(h_->profile && h_->tf_figures) { if (on) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, h->stream); } }
+    ~TfScope() { if (on) { (void)hipEventRecord(b, h->stream); h->tf_evs.push_back({a, b}); } }
+};
+// k_tf_slots over all slots of this process behind pass 1, and for a loaded combiner its slot kernel behind that: no synchronisation
+static int tf_slots(ttx_engine *h)
+{
+    const TrainFun &f = *h->tfun;
+    DevProb &P = h->P;
+    long long nslot = (long long)h->G * h->HS;
+    const TfOps &O = h->tf_ops;
+    const size_t lds = sizeof(double) * TTX_TF_WAVES * tf_lds_doubles(O.ldx, O.d);
+    const dim3 grid(tf_grid(h, nslot)), block(64 * TTX_TF_WAVES);
+    const short *hidx = P.hidx; unsigned char *hreq = P.hreq; double *hval = P.hval;
+    double *tval = (double *)h->scratch[SC_TVAL].p;
+    unsigned long long *cnt = (unsigned long long *)h->scratch[SC_CNT].p;
+    if (h->tf_figures) h->tf_launches++;
+    TfScope timed(h);
+    switch (f.op) {
+        case TTX_TOP_PRODUCT: hipLaunchKernelGGL(k_tf_slots<TF_PRODUCT>, grid, block, lds, h->stream, O, nslot, hidx, hreq, hval, tval, cnt); break;
+        case TTX_TOP_RATIO: hipLaunchKernelGGL(k_tf_slots<TF_RATIO>, grid, block, lds, h->stream, O, nslot, hidx, hreq, hval, tval, cnt); break;
+        case TTX_TOP_SQRTABS: hipLaunchKernelGGL(k_tf_slots<TF_SQRTABS>, grid, block, lds, h->stream, O, nslot, hidx, hreq, hval, tval, cnt); break;
+        default: {
+            hipLaunchKernelGGL(k_tf_slots<TF_DEVICE>, grid, block, lds, h->stream, O, nslot, hidx, hreq, hval, tval, cnt);
+            DevFun &c = *f.comb;
+            int m = O.m, d = O.d;
+            const int *n = P.n + 1;
+            const double *par = c.par, *tv = tval;
+            const unsigned cg = (unsigned)std::max<long long>(1, std::min<long long>((nslot + c.info.block - 1) / c.info.block, 4096));
+            void *args[] = {&m, &d, &n, &par, &nslot, &hidx, &hreq, &tv, &hval};
+            DEVFUN_LAUNCHCHECK(hipModuleLaunchKernel(c.slots, cg, 1, 1, (unsigned)c.info.block, 1, 1, 0, h->stream, args, nullptr));
+        }
+    }
+    return TTX_OK;
+}
+
 // between the two passes of an evaluating kernel: the host's `fun` (host_eval), or for TTX_FUN_COSCOEFF the device evaluator over
 // the requested slots, enqueued on the stream behind pass 1 (no synchronisation)
 static int slot_eval(ttx_engine *h)
@@ -384,6 +446,7 @@ static int slot_eval(ttx_engine *h)
     DevProb &P = h->P;
     if (!P.slot_dev) return host_eval(h);
     if (h->cfg.fun_id == TTX_FUN_DEVICE) return devfun_slots(h);
+    if (h->cfg.fun_id == TTX_FUN_TRAINS) return tf_slots(h);
     const long long nslot = (long long)h->G * h->HS;
     const unsigned grid = (unsigned)std::min<long long>((nslot + TTX_CC_WAVES - 1) / TTX_CC_WAVES, 1024);
     hipLaunchKernelGGL(k_coscoeff_slots, dim3(grid), dim3(64 * TTX_CC_WAVES), sizeof(double) * TTX_CC_WAVES * TTX_CC_LDS(P.d), h->stream,
@@ -460,20 +523,22 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
     if (cfg->maxrank < 1 || cfg->maxrank > 128) return fail(TTX_EINVAL, "ttx_create: maxrank must be in 1..128 (got %d)", cfg->maxrank);
     if (cfg->pivoting < -1) return fail(TTX_EINVAL, "dtt_dmrgg: unknown pivoting: %d", cfg->pivoting);   // lib/dmrgg.f90:590-592
     if (2 * cfg->pivoting + 2 > TTX_MAXH) return fail(TTX_EINVAL, "dtt_dmrgg: pivoting %d too large", cfg->pivoting);
-    if (!(nofun && cfg->fun_id == 0) && (cfg->fun_id < 1 || cfg->fun_id > 6)) return fail(TTX_EINVAL, "ttx_create: unknown fun_id %d", cfg->fun_id);
+    if (!(nofun && cfg->fun_id == 0) && (cfg->fun_id < 1 || cfg->fun_id > TTX_FUN_TRAINS)) return fail(TTX_EINVAL, "ttx_create: unknown fun_id %d", cfg->fun_id);
     if (cfg->npar < 0 || (cfg->npar > 0 && !cfg->par)) return fail(TTX_EINVAL, "ttx_create: par missing");
     if (cfg->fun_id == TTX_FUN_ISING && (cfg->npar < 2 * cfg->n[0] + 1)) return fail(TTX_EINVAL, "ttx_create: the Ising integrand needs par(1:2n+1) (nodes, weights, id)");
     if ((cfg->fun_id == TTX_FUN_STDNORM || cfg->fun_id == TTX_FUN_MVN) && cfg->npar < cfg->n[0]) return fail(TTX_EINVAL, "ttx_create: the integrand needs the nodes par(1:n)");
     // the built-in integrands address par(ind) (and the Ising weights par(n(1) + ind)): no mode may be larger than the first
     // (test_crs_ising.f90:181-183); with the reference this is the caller's business, here it would be a read outside the parameter vector
     // (the COS coefficients do not index par)
-    if (cfg->fun_id != TTX_FUN_HOST && cfg->fun_id != TTX_FUN_COSCOEFF && cfg->fun_id != TTX_FUN_DEVICE && cfg->fun_id != 0)
+    if (cfg->fun_id != TTX_FUN_HOST && cfg->fun_id != TTX_FUN_COSCOEFF && cfg->fun_id != TTX_FUN_DEVICE && cfg->fun_id != TTX_FUN_TRAINS && cfg->fun_id != 0)
         for (int k = 1; k < cfg->d; k++)
             if (cfg->n[k] > cfg->n[0]) return fail(TTX_EINVAL, "ttx_create: mode %d has %d points, more than the first mode (%d): the built-in integrands index par by n(1)", k + 1, cfg->n[k], cfg->n[0]);
     if (cfg->fun_id == TTX_FUN_HOST && cfg->d > 2048) return fail(TTX_EINVAL, "ttx_create: host integrand: at most 2048 dimensions (tt_size)");
     if (cfg->fun_id == TTX_FUN_DEVICE && cfg->d > 2048) return fail(TTX_EINVAL, "ttx_create: device integrand: at most 2048 dimensions (tt_size)");
+    if (cfg->fun_id == TTX_FUN_TRAINS && cfg->d > 2048) return fail(TTX_EINVAL, "ttx_create: integrand of trains: at most 2048 dimensions (tt_size)");
     if (cfg->fun_id == TTX_FUN_COSCOEFF) { if (int rc0 = coscoeff_check("ttx_create", cfg->d, cfg->n, cfg->aux, cfg->naux)) return rc0; }
     const int W = cfg->world_size < 1 ? 1 : cfg->world_size;
+    if (cfg->fun_id == TTX_FUN_TRAINS && W > 1) return fail(TTX_EINVAL, "ttx_create: an integrand of trains (TTX_FUN_TRAINS) runs in one process: bond groups (nproc) work, world_size %d does not", W);
     const int nproc = std::max(cfg->nproc < 1 ? 1 : cfg->nproc, 1);
     if (nproc >= cfg->d) return fail(TTX_EINVAL, "nproc exceeds or equal dimension, cannot proceed");   // lib/dmrgg.f90:114-117
     if (nproc < W) return fail(TTX_EINVAL, "ttx_create: %d bond groups cannot be spread over %d GPUs", nproc, W);
@@ -832,14 +897,14 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
             h->lot_rows = h->lot_wave ? (env_int("TTX_LOTTERY_ROWS", 0) == 2 ? 2 : 1) : 0;
         }
     }
-    if (cfg->fun_id == TTX_FUN_HOST || cfg->fun_id == TTX_FUN_COSCOEFF || cfg->fun_id == TTX_FUN_DEVICE) {
+    if (cfg->fun_id == TTX_FUN_HOST || cfg->fun_id == TTX_FUN_COSCOEFF || cfg->fun_id == TTX_FUN_DEVICE || cfg->fun_id == TTX_FUN_TRAINS) {
         // slots of one group: the largest point set any evaluating kernel asks for in one launch
         int nn = h->n1[1];
         for (int k = 2; k <= d; k++) nn = std::min(nn, h->n1[k]);
         const size_t snum = (size_t)std::max(8, nproc);
         h->HS = std::max<size_t>({(size_t)h->RM * NM, (size_t)nn * snum, (size_t)h->NC * NM, (size_t)2 * h->RM + 2 * NM, (size_t)2 * NM, (size_t)256});
         const size_t nslot = (size_t)h->G * h->HS;
-        if (cfg->fun_id == TTX_FUN_COSCOEFF || cfg->fun_id == TTX_FUN_DEVICE) {
+        if (cfg->fun_id == TTX_FUN_COSCOEFF || cfg->fun_id == TTX_FUN_DEVICE || cfg->fun_id == TTX_FUN_TRAINS) {
             // device slots (zero-filled, owned by allocs): the evaluator runs on the stream between the two passes
             P.slot_dev = 1;
             A_(dev_alloc(h, &P.hidx, nslot * d)); A_(dev_alloc(h, &P.hval, nslot)); A_(dev_alloc(h, &P.hreq, nslot));
@@ -863,10 +928,12 @@ extern "C" void ttx_destroy(ttx_engine *h)
 {
     if (!h) return;
     if (h->dfun) { (void)hipSetDevice(h->cfg.device); if (h->stream) (void)hipStreamSynchronize(h->stream); h->dfun.reset(); }   // the last owner unloads the module
+    if (h->tfun) { (void)hipSetDevice(h->cfg.device); if (h->stream) (void)hipStreamSynchronize(h->stream); h->tfun.reset(); }   // ... and a loaded combiner's
     if (h->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(h->comm);
     for (void *p : h->allocs) (void)hipFree(p);
     for (auto &b : h->scratch) if (b.p) (void)hipFree(b.p);
     for (auto &t : h->timer) for (auto &e : t.ev) if (e) (void)hipEventDestroy(e);
+    for (auto &e : h->tf_evs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     if (h->h_sum_base) (void)hipHostFree(h->h_sum_base);
     if (h->h_val) (void)hipHostFree(h->h_val);
     if (h->h_svd) (void)hipHostFree(h->h_svd);
@@ -900,6 +967,7 @@ extern "C" int ttx_comm_unique_id(uint8_t id[128])
 extern "C" int ttx_comm_init(ttx_engine *h, const uint8_t id[128])
 {
     if (!h) return fail(TTX_EINVAL, "ttx_comm_init: null handle");
+    if (h->cfg.fun_id == TTX_FUN_TRAINS) return fail(TTX_ESTATE, "ttx_comm_init: an engine with an integrand of trains (TTX_FUN_TRAINS) runs in one process");
     if (h->W == 1) return TTX_OK;
     int rc = rccl_load();
     if (rc) return rc;
@@ -1059,6 +1127,7 @@ static void shm_close(ttx_engine *h)
 extern "C" int ttx_comm_init_shm(ttx_engine *h, const char *name)
 {
     if (!h || !name || !*name) return fail(TTX_EINVAL, "ttx_comm_init_shm: null argument");
+    if (h->cfg.fun_id == TTX_FUN_TRAINS) return fail(TTX_ESTATE, "ttx_comm_init_shm: an engine with an integrand of trains (TTX_FUN_TRAINS) runs in one process");
     if (h->W == 1) return TTX_OK;
     if (h->shm) return fail(TTX_ESTATE, "ttx_comm_init_shm: already initialised");
     ShmTransport *T = new ShmTransport();
@@ -1150,6 +1219,7 @@ extern "C" int ttx_comm_init_shm(ttx_engine *h, const char *name)
 extern "C" int ttx_set_transport(ttx_engine *h, const ttx_transport *t)
 {
     if (!h || !t || !t->sendrecv || !t->allreduce) return fail(TTX_EINVAL, "ttx_set_transport: null argument");
+    if (h->cfg.fun_id == TTX_FUN_TRAINS) return fail(TTX_ESTATE, "ttx_set_transport: an engine with an integrand of trains (TTX_FUN_TRAINS) runs in one process");
     h->cb = *t; h->have_cb = true;
     return TTX_OK;
 }
@@ -1193,15 +1263,16 @@ static bool devfun_image_plausible(const unsigned char *p, size_t nbytes)
     }
     return nbytes >= 24 && memcmp(p, "CCOB", 4) == 0;
 }
-extern "C" int ttx_set_integrand_device(ttx_engine *h, const void *image, int64_t nbytes, const char *name, const double *par, int32_t npar)
+// a code object into a DevFun: the module, the three symbols <prefix>{info,slots,list}_<name>, the device copy of par.  `who` names
+// the entry in the messages, `macro` the header macro that generates the symbols.  Nothing of the engine changes here.
+static int devfun_load(const char *who, const char *prefix, const char *macro, const char *what, ttx_engine *h, const void *image, int64_t nbytes, const char *name,
+                       const double *par, int32_t npar, std::shared_ptr<DevFun> *out)
 {
-    if (!h) return fail(TTX_EINVAL, "ttx_set_integrand_device: null handle");
-    if (h->cfg.fun_id != TTX_FUN_DEVICE) return fail(TTX_ESTATE, "ttx_set_integrand_device: the engine was not created with fun_id = TTX_FUN_DEVICE");
-    if (!image || nbytes <= 0) return fail(TTX_EINVAL, "ttx_set_integrand_device: empty code object image");
-    if (!name || !*name || strlen(name) > 200) return fail(TTX_EINVAL, "ttx_set_integrand_device: integrand name missing (or longer than 200 characters)");
-    if (npar < 0 || (npar > 0 && !par)) return fail(TTX_EINVAL, "ttx_set_integrand_device: par missing (npar = %d)", npar);
+    if (!image || nbytes <= 0) return fail(TTX_EINVAL, "%s: empty code object image", who);
+    if (!name || !*name || strlen(name) > 200) return fail(TTX_EINVAL, "%s: integrand name missing (or longer than 200 characters)", who);
+    if (npar < 0 || (npar > 0 && !par)) return fail(TTX_EINVAL, "%s: par missing (npar = %d)", who, npar);
     if (!devfun_image_plausible((const unsigned char *)image, (size_t)nbytes))
-        return fail(TTX_EINVAL, "ttx_set_integrand_device: the image is neither a complete code object (ELF) nor a complete offload bundle of hipcc --genco");
+        return fail(TTX_EINVAL, "%s: the image is neither a complete code object (ELF) nor a complete offload bundle of hipcc --genco", who);
     HIPCHECK(hipSetDevice(h->cfg.device));
     // the runtime may keep pointers into the image: the loader gets a private copy that lives as long as the module
     auto f = std::make_shared<DevFun>();
@@ -1211,40 +1282,47 @@ extern "C" int ttx_set_integrand_device(ttx_engine *h, const void *image, int64_
     hipError_t e = hipModuleLoadData(&f->mod, f->image.data());
     if (e != hipSuccess) {
         (void)hipGetLastError(); f->mod = nullptr;
-        return fail(TTX_EINVAL, "ttx_set_integrand_device: the runtime refused the code object (%s): is it built for this GPU (--offload-arch=gfx950)?", hipGetErrorString(e));
+        return fail(TTX_EINVAL, "%s: the runtime refused the code object (%s): is it built for this GPU (--offload-arch=gfx950)?", who, hipGetErrorString(e));
     }
-    const std::string sn = std::string("ttx_devfun_slots_") + name, ln = std::string("ttx_devfun_list_") + name, in = std::string("ttx_devfun_info_") + name;
+    const std::string sn = std::string(prefix) + "slots_" + name, ln = std::string(prefix) + "list_" + name, in = std::string(prefix) + "info_" + name;
     hipDeviceptr_t ip = nullptr; size_t ib = 0;
     if ((e = hipModuleGetGlobal(&ip, &ib, f->mod, in.c_str())) != hipSuccess || hipModuleGetFunction(&f->slots, f->mod, sn.c_str()) != hipSuccess ||
         hipModuleGetFunction(&f->list, f->mod, ln.c_str()) != hipSuccess) {
         (void)hipGetLastError();
-        return fail(TTX_EINVAL, "ttx_set_integrand_device: the code object has no integrand '%s' (symbols %s, %s, %s: see TTX_DEVICE_INTEGRAND in ttx_device_fun.h)",
-                    name, in.c_str(), sn.c_str(), ln.c_str());
+        return fail(TTX_EINVAL, "%s: the code object has no %s '%s' (symbols %s, %s, %s: see %s in ttx_device_fun.h)",
+                    who, what, name, in.c_str(), sn.c_str(), ln.c_str(), macro);
     }
-    if (ib < sizeof(int)) return fail(TTX_EINVAL, "ttx_set_integrand_device: %s is not a ttx_devfun_info", in.c_str());
+    if (ib < sizeof(int)) return fail(TTX_EINVAL, "%s: %s is not a ttx_devfun_info", who, in.c_str());
     HIPCHECK(hipMemcpy(&f->info, (const void *)ip, std::min(ib, sizeof(f->info)), hipMemcpyDeviceToHost));
     if (f->info.abi != TTX_DEVFUN_ABI || ib != sizeof(f->info))
-        return fail(TTX_EINVAL, "ttx_set_integrand_device: integrand '%s' was compiled against slot ABI version %d, this engine speaks version %d: recompile it with this engine's ttx_device_fun.h",
-                    name, f->info.abi, TTX_DEVFUN_ABI);
+        return fail(TTX_EINVAL, "%s: integrand '%s' was compiled against slot ABI version %d, this engine speaks version %d: recompile it with this engine's ttx_device_fun.h",
+                    who, name, f->info.abi, TTX_DEVFUN_ABI);
     if ((f->info.kind != TTX_DEVFUN_KIND_LANE && f->info.kind != TTX_DEVFUN_KIND_WAVE) || f->info.block < 64 || f->info.block > 1024 || f->info.block % 64)
-        return fail(TTX_EINVAL, "ttx_set_integrand_device: integrand '%s': bad kind / block size (%d / %d)", name, f->info.kind, f->info.block);
+        return fail(TTX_EINVAL, "%s: integrand '%s': bad kind / block size (%d / %d)", who, name, f->info.kind, f->info.block);
     const long long lds = (long long)f->info.lds_per_wave * (f->info.block / 64);
     if (f->info.lds_per_wave < 0 || lds > 64 * 1024)
-        return fail(TTX_EINVAL, "ttx_set_integrand_device: integrand '%s' asks for %lld bytes of LDS per workgroup (%d per wave), more than 64 KB", name, lds, f->info.lds_per_wave);
+        return fail(TTX_EINVAL, "%s: integrand '%s' asks for %lld bytes of LDS per workgroup (%d per wave), more than 64 KB", who, name, lds, f->info.lds_per_wave);
     HIPCHECK(hipMalloc((void **)&f->par, sizeof(double) * (size_t)(npar + 1)));
     if (npar > 0) HIPCHECK(hipMemcpy(f->par, par, sizeof(double) * (size_t)npar, hipMemcpyHostToDevice));
+    *out = std::move(f);
+    return TTX_OK;
+}
+extern "C" int ttx_set_integrand_device(ttx_engine *h, const void *image, int64_t nbytes, const char *name, const double *par, int32_t npar)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_set_integrand_device: null handle");
+    if (h->cfg.fun_id != TTX_FUN_DEVICE) return fail(TTX_ESTATE, "ttx_set_integrand_device: the engine was not created with fun_id = TTX_FUN_DEVICE");
+    std::shared_ptr<DevFun> f;
+    if (int rc = devfun_load("ttx_set_integrand_device", "ttx_devfun_", "TTX_DEVICE_INTEGRAND", "integrand", h, image, nbytes, name, par, npar, &f)) return rc;
     HIPCHECK(hipStreamSynchronize(h->stream));          // nothing of an earlier integrand is in flight when its module goes
     h->dfun = std::move(f);
     return TTX_OK;
 }
-extern "C" int ttx_set_integrand_device_file(ttx_engine *h, const char *path, const char *name, const double *par, int32_t npar)
+// a code object file into memory
+static int devfun_read_file(const char *who, const char *path, std::vector<unsigned char> &buf)
 {
-    if (!h) return fail(TTX_EINVAL, "ttx_set_integrand_device_file: null handle");
-    if (h->cfg.fun_id != TTX_FUN_DEVICE) return fail(TTX_ESTATE, "ttx_set_integrand_device_file: the engine was not created with fun_id = TTX_FUN_DEVICE");
-    if (!path || !*path) return fail(TTX_EINVAL, "ttx_set_integrand_device_file: path missing");
+    if (!path || !*path) return fail(TTX_EINVAL, "%s: path missing", who);
     FILE *fp = fopen(path, "rb");
-    if (!fp) return fail(TTX_EINVAL, "ttx_set_integrand_device_file: cannot read %s: %s", path, strerror(errno));
-    std::vector<unsigned char> buf;
+    if (!fp) return fail(TTX_EINVAL, "%s: cannot read %s: %s", who, path, strerror(errno));
     unsigned char chunk[65536];
     size_t got;
     while ((got = fread(chunk, 1, sizeof chunk, fp)) > 0) {
@@ -1253,14 +1331,23 @@ extern "C" int ttx_set_integrand_device_file(ttx_engine *h, const char *path, co
     }
     const bool bad = ferror(fp) != 0;
     fclose(fp);
-    if (bad) return fail(TTX_EINVAL, "ttx_set_integrand_device_file: cannot read %s", path);
-    if (buf.empty()) return fail(TTX_EINVAL, "ttx_set_integrand_device_file: %s is empty", path);
+    if (bad) return fail(TTX_EINVAL, "%s: cannot read %s", who, path);
+    if (buf.empty()) return fail(TTX_EINVAL, "%s: %s is empty", who, path);
+    return TTX_OK;
+}
+extern "C" int ttx_set_integrand_device_file(ttx_engine *h, const char *path, const char *name, const double *par, int32_t npar)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_set_integrand_device_file: null handle");
+    if (h->cfg.fun_id != TTX_FUN_DEVICE) return fail(TTX_ESTATE, "ttx_set_integrand_device_file: the engine was not created with fun_id = TTX_FUN_DEVICE");
+    std::vector<unsigned char> buf;
+    if (int rc = devfun_read_file("ttx_set_integrand_device_file", path, buf)) return rc;
     return ttx_set_integrand_device(h, buf.data(), (int64_t)buf.size(), name, par, npar);
 }
 // the loaded integrand at a list of multi-indices, through the code object's list kernel
 extern "C" int ttx_eval_device(ttx_engine *h, int64_t npts, const int32_t *ind, double *out)
 {
     if (!h) return fail(TTX_EINVAL, "ttx_eval_device: null handle");
+    if (h->cfg.fun_id == TTX_FUN_TRAINS) return tf_eval_list(h, npts, ind, out);
     if (h->cfg.fun_id != TTX_FUN_DEVICE) return fail(TTX_ESTATE, "ttx_eval_device: the engine was not created with fun_id = TTX_FUN_DEVICE");
     if (!h->dfun) return fail(TTX_ESTATE, "ttx_eval_device: call ttx_set_integrand_device first");
     if (npts < 0 || (npts > 0 && (!ind || !out))) return fail(TTX_EINVAL, "ttx_eval_device: null argument");
@@ -1934,6 +2021,9 @@ static int with_fun(const ttx_engine *h, const char *who, F f)
         case TTX_FUN_DEVICE:
             if (who && !h->dfun) return fail(TTX_ESTATE, "%s: call ttx_set_integrand_device first", who);
             return f(std::integral_constant<int, FUN_HOST>());
+        case TTX_FUN_TRAINS:
+            if (who && !h->tfun) return fail(TTX_ESTATE, "%s: call ttx_set_integrand_trains first", who);
+            return f(std::integral_constant<int, FUN_HOST>());
         default: return f(std::integral_constant<int, FUN_MVN>());
     }
 }
@@ -1969,6 +2059,12 @@ extern "C" int ttx_run(ttx_engine *h)
     HIPCHECK(hipSetDevice(h->cfg.device));
     if (h->cfg.fun_id == 0) return fail(TTX_ESTATE, "ttx_run: this engine holds a loaded tensor train and has no integrand");
     reset_kernel_stats(h);
+    if (h->cfg.fun_id == TTX_FUN_TRAINS) {
+        // the operands' blocks as they stand now, then the sweep of a device integrand; the figures of ttx_trainfun_last at the end
+        if (int rc = tf_prepare(h, "ttx_run", true)) return rc;
+        if (int rc = run_impl<FUN_HOST>(h)) return rc;
+        return tf_finish(h);
+    }
     if (h->cfg.fun_id != TTX_FUN_ISING)
         return with_fun(h, "ttx_run", [&](auto fun) { h->host_calls = 0; return run_impl<decltype(fun)::value>(h); });
     h->cluster_aborted = false;
@@ -2100,6 +2196,7 @@ extern "C" int ttx_replicate(ttx_engine *h, ttx_engine **out)
     if (rc) return rc;
     e->hfun = h->hfun; e->hfun_par = h->hfun_par;
     e->dfun = h->dfun;                              // same process, same device: the replica shares the module and the par copy
+    e->tfun = h->tfun;                              // ... and the operand list of TTX_FUN_TRAINS
     if (e->RM != h->RM || e->NM != h->NM) { ttx_destroy(e); return fail(TTX_EHIP, "ttx_replicate: layout mismatch"); }
     const size_t CS = h->P.CS;
     // slots of the other processes' cores hold -0.0: x + (-0.0) = x for EVERY x, also for x = -0.0 (x + (+0.0) would turn it into +0.0)
@@ -2504,12 +2601,14 @@ static int accchk_impl(ttx_engine *h, int nlot, double *einf, double *efro, doub
 
 extern "C" int ttx_accchk(ttx_engine *h, int32_t nlot, double *einf, double *efro, double *ainf, double *afro, int32_t *pivot)
 {
+    if (h && h->cfg.fun_id == TTX_FUN_TRAINS && !h->tfun) return fail(TTX_ESTATE, "ttx_accchk: call ttx_set_integrand_trains first");
     if (!h || !einf || !efro || !ainf || !afro || !h->ran) return fail(TTX_ESTATE, "ttx_accchk: run first");
     if (h->W > 1)       // every rank needs all cores: the check runs on a replica of the job's train (identical result on every process)
         return with_replica(h, [&](ttx_engine *e) { return ttx_accchk(e, nlot, einf, efro, ainf, afro, pivot); });
     if (nlot < 1) return fail(TTX_EINVAL, "dtt_accchk: nlot must be positive");
     if (h->cfg.fun_id == 0) return fail(TTX_ESTATE, "dtt_accchk: this engine holds a loaded tensor train and has no integrand");
     HIPCHECK(hipSetDevice(h->cfg.device));
+    if (h->cfg.fun_id == TTX_FUN_TRAINS) if (int rc = tf_prepare(h, "dtt_accchk", false)) return rc;
     return with_fun(h, "dtt_accchk", [&](auto fun) { return accchk_impl<decltype(fun)::value>(h, nlot, einf, efro, ainf, afro, pivot); });
 }
 
@@ -3025,6 +3124,194 @@ static int check_train_one_process(ttx_engine *h, const char *who)
     if (h->W > 1) return tt_prepare(h, who);
     HIPCHECK(hipSetDevice(h->cfg.device));
     return TTX_OK;
+}
+
+// ---- TTX_FUN_TRAINS: operands, their device blocks, the list entry (kernels in ttx_trainfun.h) ------------------------------------
+// one wave per item, TTX_TF_WAVES per workgroup, at most 8 workgroups per CU (the launch shape of k_ev_exact); the kernels stride
+static int tf_grid(ttx_engine *h, long long items)
+{
+    return (int)std::max<long long>(1, std::min<long long>((items + TTX_TF_WAVES - 1) / TTX_TF_WAVES, (long long)dev_ncu(h) * 8));
+}
+// what an operand must be, for the set call and again before every evaluation (the caller may have changed it in between)
+static int tf_check_operand(ttx_engine *h, ttx_engine *x, int t, const char *who)
+{
+    char w[160];
+    snprintf(w, sizeof w, "%s: operand %d", who, t + 1);
+    if (!x) return fail(TTX_EINVAL, "%s is null", w);
+    if (x == h) return fail(TTX_EINVAL, "%s is the engine itself: its train is what the run writes", w);
+    if (int rc = check_train_one_process(x, w)) return rc;
+    if (x->cfg.device != h->cfg.device) return fail(TTX_EINVAL, "%s lives on device %d, the engine on device %d", w, x->cfg.device, h->cfg.device);
+    if (x->d != h->d) return fail(TTX_EINVAL, "%s has %d modes, the engine %d", w, x->d, h->d);
+    for (int k = 1; k <= h->d; k++) if (x->n1[k] != h->n1[k]) return fail(TTX_EINVAL, "%s: mode %d has %d points, the engine's %d", w, k, x->n1[k], h->n1[k]);
+    for (int k = 0; k <= h->d; k++) if (x->rfinal[k] < 1 || x->rfinal[k] > 128) return fail(TTX_EINVAL, "%s: rank %d at bond %d (1..128 expected)", w, x->rfinal[k], k);
+    if (x->rfinal[0] != 1 || x->rfinal[h->d] != 1) return fail(TTX_EINVAL, "%s: boundary ranks are not 1", w);
+    return TTX_OK;
+}
+// The operands' blocks -- core pointers and ranks of every operand as they stand NOW, the engine's mode sizes -- into this engine's
+// own scratch (SC_TFUN), so that an operand that was ort-ed or svd-ed since the last run is seen with its new ranks and stays free
+// for calls of its own between runs.  One wait: the operands' streams have finished what wrote their cores, the engine's stream has
+// the blocks.  The counter of evaluated elements (SC_CNT) and, for a loaded combiner, the value rows (SC_TVAL) are made ready too.
+// figures: the call records what ttx_trainfun_last reports (ttx_accchk leaves the last run's figures as they are).
+static int tf_prepare(ttx_engine *h, const char *who, bool figures)
+{
+    if (!h->tfun) return fail(TTX_ESTATE, "%s: call ttx_set_integrand_trains first", who);
+    const TrainFun &f = *h->tfun;
+    const int m = (int)f.x.size(), d = h->d;
+    for (int t = 0; t < m; t++) if (int rc = tf_check_operand(h, f.x[t], t, who)) return rc;
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    OpMeta meta(h->tf_host);
+    size_t o_core[TTX_TF_MAX], o_r[TTX_TF_MAX];
+    int rmax = 1;
+    for (int t = 0; t < m; t++) {
+        const ttx_engine *x = f.x[t];
+        std::vector<const double *> cp(d);
+        for (int k = 1; k <= d; k++) cp[k - 1] = core_dev(x, k);
+        const std::vector<int> r(x->rfinal.begin(), x->rfinal.begin() + d + 1);
+        rmax = std::max(rmax, *std::max_element(r.begin(), r.end()));
+        o_core[t] = meta.put(cp); o_r[t] = meta.put(r);
+    }
+    const size_t o_n = meta.put(std::vector<int>(h->n1.begin() + 1, h->n1.begin() + 1 + d));
+    for (int t = 0; t < m; t++) HIPCHECK(hipStreamSynchronize(f.x[t]->stream));
+    char *dm;
+    int rc;
+    if ((rc = meta.upload(h, SC_TFUN, &dm)) || (rc = buf_reserve(h, SC_CNT, sizeof(long long)))) return rc;
+    if (f.op == TTX_TOP_DEVICE && (rc = buf_reserve(h, SC_TVAL, sizeof(double) * (size_t)h->G * h->HS * m))) return rc;
+    HIPCHECK(hipMemsetAsync(buf<char>(h, SC_CNT), 0, sizeof(long long), h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    TfOps &O = h->tf_ops;
+    O = TfOps{};
+    O.m = m; O.d = d; O.ldx = (rmax + 3) & ~3; O.n = (const int *)(dm + o_n);
+    for (int t = 0; t < m; t++) {
+        O.t[t].RM = f.x[t]->RM; O.t[t].SS = f.x[t]->P.SS;
+        O.t[t].core = (const double *const *)(dm + o_core[t]); O.t[t].r = (const int *)(dm + o_r[t]);
+    }
+    h->tf_figures = figures;
+    if (!figures) return TTX_OK;
+    h->tf_launches = 0; h->tf_elements = 0; h->tf_ms = 0.0;
+    for (auto &e : h->tf_evs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    h->tf_evs.clear();
+    return TTX_OK;
+}
+// after the last launch of a call: the elements the slot kernel evaluated and, with ttx_set_profile on, its milliseconds
+static int tf_finish(ttx_engine *h)
+{
+    unsigned long long c = 0;
+    HIPCHECK(hipMemcpyAsync(&c, buf<char>(h, SC_CNT), sizeof c, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    h->tf_elements = (int64_t)c;
+    for (auto &e : h->tf_evs) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) h->tf_ms += ms;
+        (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second);
+    }
+    h->tf_evs.clear();
+    return TTX_OK;
+}
+static int tf_set(const char *who, ttx_engine *h, int32_t m, ttx_engine *const *x, int32_t op, std::shared_ptr<DevFun> comb)
+{
+    if (m < 1 || m > TTX_TRAINS_MAX) return fail(TTX_EINVAL, "%s: %d operands (1..%d expected)", who, m, TTX_TRAINS_MAX);
+    if (!x) return fail(TTX_EINVAL, "%s: operand list missing", who);
+    if (op < TTX_TOP_PRODUCT || op > TTX_TOP_DEVICE) return fail(TTX_EINVAL, "%s: unknown op %d", who, op);
+    if (op == TTX_TOP_RATIO && m != 2) return fail(TTX_EINVAL, "%s: TTX_TOP_RATIO takes 2 operands (got %d)", who, m);
+    if (op == TTX_TOP_SQRTABS && m != 1) return fail(TTX_EINVAL, "%s: TTX_TOP_SQRTABS takes 1 operand (got %d)", who, m);
+    for (int t = 0; t < m; t++) if (int rc = tf_check_operand(h, x[t], t, who)) return rc;
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    auto f = std::make_shared<TrainFun>();
+    f->x.assign(x, x + m); f->op = op; f->comb = std::move(comb);
+    HIPCHECK(hipStreamSynchronize(h->stream));          // nothing of an earlier combiner is in flight when its module goes
+    h->tfun = std::move(f);
+    return TTX_OK;
+}
+extern "C" int ttx_set_integrand_trains(ttx_engine *h, int32_t m, ttx_engine *const *x, int32_t op)
+{
+    const char *who = "ttx_set_integrand_trains";
+    if (!h) return fail(TTX_EINVAL, "%s: null handle", who);
+    if (h->cfg.fun_id != TTX_FUN_TRAINS) return fail(TTX_ESTATE, "%s: the engine was not created with fun_id = TTX_FUN_TRAINS", who);
+    if (op == TTX_TOP_DEVICE) return fail(TTX_EINVAL, "%s: TTX_TOP_DEVICE needs a code object: ttx_set_integrand_trains_device", who);
+    return tf_set(who, h, m, x, op, nullptr);
+}
+extern "C" int ttx_set_integrand_trains_device(ttx_engine *h, int32_t m, ttx_engine *const *x, const void *image, int64_t nbytes,
+                                               const char *name, const double *par, int32_t npar)
+{
+    const char *who = "ttx_set_integrand_trains_device";
+    if (!h) return fail(TTX_EINVAL, "%s: null handle", who);
+    if (h->cfg.fun_id != TTX_FUN_TRAINS) return fail(TTX_ESTATE, "%s: the engine was not created with fun_id = TTX_FUN_TRAINS", who);
+    if (m < 1 || m > TTX_TRAINS_MAX) return fail(TTX_EINVAL, "%s: %d operands (1..%d expected)", who, m, TTX_TRAINS_MAX);
+    if (!x) return fail(TTX_EINVAL, "%s: operand list missing", who);
+    for (int t = 0; t < m; t++) if (int rc = tf_check_operand(h, x[t], t, who)) return rc;     // before the code object is loaded
+    std::shared_ptr<DevFun> c;
+    if (int rc = devfun_load(who, "ttx_devcomb_", "TTX_DEVICE_COMBINER", "combiner", h, image, nbytes, name, par, npar, &c)) return rc;
+    if (c->info.kind != TTX_DEVFUN_KIND_LANE) return fail(TTX_EINVAL, "%s: combiner '%s' is not of the lane form", who, name);
+    return tf_set(who, h, m, x, TTX_TOP_DEVICE, std::move(c));
+}
+extern "C" int ttx_set_integrand_trains_device_file(ttx_engine *h, int32_t m, ttx_engine *const *x, const char *path, const char *name,
+                                                    const double *par, int32_t npar)
+{
+    const char *who = "ttx_set_integrand_trains_device_file";
+    if (!h) return fail(TTX_EINVAL, "%s: null handle", who);
+    if (h->cfg.fun_id != TTX_FUN_TRAINS) return fail(TTX_ESTATE, "%s: the engine was not created with fun_id = TTX_FUN_TRAINS", who);
+    std::vector<unsigned char> img;
+    if (int rc = devfun_read_file(who, path, img)) return rc;
+    return ttx_set_integrand_trains_device(h, m, x, img.data(), (int64_t)img.size(), name, par, npar);
+}
+extern "C" int ttx_trainfun_last(const ttx_engine *h, double *ms, int64_t *launches, int64_t *elements)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_trainfun_last: null handle");
+    if (ms) *ms = h->tf_ms;
+    if (launches) *launches = h->tf_launches;
+    if (elements) *elements = h->tf_elements;
+    return TTX_OK;
+}
+// ttx_eval_device of a TTX_FUN_TRAINS engine: k_tf_list over the staged rows, in chunks; a loaded combiner's list kernel behind it
+static int tf_eval_list(ttx_engine *h, int64_t npts, const int32_t *ind, double *out)
+{
+    if (npts < 0 || (npts > 0 && (!ind || !out))) return fail(TTX_EINVAL, "ttx_eval_device: null argument");
+    int rc = tf_prepare(h, "ttx_eval_device", true);
+    if (rc) return rc;
+    if (npts == 0) return TTX_OK;
+    const int d = h->d;
+    for (int64_t p = 0; p < npts; p++)
+        for (int k = 0; k < d; k++)
+            if (ind[p * d + k] < 1 || ind[p * d + k] > h->n1[k + 1])
+                return fail(TTX_EINVAL, "ttx_eval_device: point %lld: index %d of mode %d is outside 1..%d", (long long)p, ind[p * d + k], k + 1, h->n1[k + 1]);
+    const TrainFun &f = *h->tfun;
+    const TfOps &O = h->tf_ops;
+    const size_t chunk = (size_t)std::min<int64_t>(npts, 1 << 16);
+    if ((rc = buf_reserve(h, SC_IND, sizeof(int) * chunk * d)) || (rc = buf_reserve(h, SC_OUT, sizeof(double) * chunk))) return rc;
+    if (f.op == TTX_TOP_DEVICE && (rc = buf_reserve(h, SC_TVAL, sizeof(double) * std::max(chunk, (size_t)h->G * h->HS) * O.m))) return rc;
+    int *sind = buf<int>(h, SC_IND);
+    double *sout = buf<double>(h, SC_OUT), *tval = buf<double>(h, SC_TVAL);
+    unsigned long long *cnt = buf<unsigned long long>(h, SC_CNT);
+    const size_t lds = sizeof(double) * TTX_TF_WAVES * tf_lds_doubles(O.ldx, O.d);
+    const dim3 block(64 * TTX_TF_WAVES);
+    for (int64_t o = 0; o < npts; o += (int64_t)chunk) {
+        long long c = std::min<int64_t>((int64_t)chunk, npts - o);
+        const dim3 grid(tf_grid(h, c));
+        HIPCHECK(hipMemcpyAsync(sind, ind + (size_t)o * d, sizeof(int) * (size_t)c * d, hipMemcpyHostToDevice, h->stream));
+        h->tf_launches++;
+        {
+            TfScope timed(h);
+            switch (f.op) {
+                case TTX_TOP_PRODUCT: hipLaunchKernelGGL(k_tf_list<TF_PRODUCT>, grid, block, lds, h->stream, O, c, (const int *)sind, sout, tval, cnt); break;
+                case TTX_TOP_RATIO: hipLaunchKernelGGL(k_tf_list<TF_RATIO>, grid, block, lds, h->stream, O, c, (const int *)sind, sout, tval, cnt); break;
+                case TTX_TOP_SQRTABS: hipLaunchKernelGGL(k_tf_list<TF_SQRTABS>, grid, block, lds, h->stream, O, c, (const int *)sind, sout, tval, cnt); break;
+                default: {
+                    hipLaunchKernelGGL(k_tf_list<TF_DEVICE>, grid, block, lds, h->stream, O, c, (const int *)sind, sout, tval, cnt);
+                    DevFun &cb = *f.comb;
+                    int m = O.m, dd = d;
+                    const int *n = h->P.n + 1, *ip = sind;
+                    const double *par = cb.par, *tv = tval;
+                    const unsigned cg = (unsigned)std::max<long long>(1, std::min<long long>((c + cb.info.block - 1) / cb.info.block, 4096));
+                    void *args[] = {&m, &dd, &n, &par, &c, &ip, &tv, &sout};
+                    DEVFUN_LAUNCHCHECK(hipModuleLaunchKernel(cb.list, cg, 1, 1, (unsigned)cb.info.block, 1, 1, 0, h->stream, args, nullptr));
+                }
+            }
+        }
+        HIPCHECK(hipMemcpyAsync(out + o, sout, sizeof(double) * (size_t)c, hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(hipStreamSynchronize(h->stream));
+    }
+    HIPCHECK(hipGetLastError());
+    return tf_finish(h);
 }
 
 // ---- the train at a batch of multi-indices (ttx_eval.h) -------------------------------------------------------------------------

@@ -9,6 +9,7 @@ runs on the GPU through ttcross_amd.engine.  Usage:
     python -m ttcross_amd.drivers devfun D N RANK PIV [NGROUPS] [device|host|wave] [SOURCE.hip NAME]
     python -m ttcross_amd.drivers tijk WORKLOAD NPTS MODE      (batched element evaluation: c64 | d64 | rand256 | a file of dtt_write)
     python -m ttcross_amd.drivers algebra WORKLOAD [REPS]      (x + x, x - x, x o w, x o x, dist on the device and by the host route)
+    python -m ttcross_amd.drivers compose WORKLOAD OP [MAXRANK] (cross approximation of product | ratio | sqrtabs of the workload's train)
 
 devfun: the rational example integrand (examples/devfun/rational.hip) as a LOADED device integrand (TTX_FUN_DEVICE), in its
 wave form, or -- host -- its C twin through the host callback (TTX_FUN_HOST; needs gcc); SOURCE.hip NAME loads another
@@ -317,6 +318,90 @@ def run_tijk(argv, device=0, repeats=5, tt=None):
     return tt, ind, out, res
 
 
+def _trainfun_twin(trains, op):
+    """The host twin of an integrand of trains (tests/trainfun_ref.c of this tree, compiled with gcc into the user's cache
+    directory) loaded with the trains' cores; returns the callback's address, or None where the source or gcc is missing."""
+    import ctypes
+    import shutil
+    import subprocess
+    import tempfile
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "trainfun_ref.c")
+    if not os.path.exists(src) or not shutil.which("gcc"):
+        return None
+    bdir = os.path.join(os.environ.get("XDG_CACHE_HOME") or tempfile.gettempdir(), "ttcross_amd_devfun")
+    os.makedirs(bdir, exist_ok=True)
+    so = os.path.join(bdir, "libtrainfun_ref.so")
+    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
+        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-fPIC", "-shared", src, "-o", so + f".{os.getpid()}", "-lm"], check=True)
+        os.replace(so + f".{os.getpid()}", so)
+    lib = ctypes.CDLL(so)
+    _host_keep.append(lib)
+    ip, dp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
+    for t, x in enumerate(trains):
+        r = np.ascontiguousarray(x.ranks(), dtype=np.int32)
+        n = np.ascontiguousarray(x._n, dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate([x.core(k).ravel(order="F") for k in range(1, x.d + 1)]))
+        if lib.trainfun_set(t, x.d, n.ctypes.data_as(ip), r.ctypes.data_as(ip), flat.ctypes.data_as(dp)):
+            raise TTXError("compose: the host twin refused a train")
+    lib.trainfun_count(len(trains))
+    return ctypes.cast(getattr(lib, "trainfun_" + op), ctypes.c_void_p).value
+
+
+def run_compose(argv, device=0, tt=None, npts=1 << 18):
+    """compose WORKLOAD OP [MAXRANK]: the cross approximation of product (x x), ratio (x / (x + x)) or sqrtabs (sqrt |x|) of the
+    workload's train x (tijk_train) as an integrand of trains (TTX_FUN_TRAINS); prints one JSON line: the run, neval, the slot
+    kernel's elements per second (a second, profiled run), the same run through the host callback with the host twin, and
+    tijk_batch(.., "exact") points per second on the same operand."""
+    import json
+    import time
+    import torch
+    torch.cuda.init()          # as run_tijk: torch's device first
+    workload, op = argv[0], argv[1]
+    x = tt or tijk_train(workload, device=device)
+    r = int(argv[2]) if len(argv) > 2 else int(x.ranks().max())
+    y = x.axpby(1.0, 1.0, x) if op == "ratio" else None
+    trains = {"product": [x, x], "ratio": [x, y], "sqrtabs": [x]}[op]
+    nproc = 8 if x.d >= 31 else 1
+    quad = [np.full(int(nk), 1.0 / int(nk)) for nk in x._n]
+    kw = dict(accuracy=500 * EPS, pivoting=2, quad=quad, nproc=nproc)
+    c = TTCross.of_trains(trains, op, r, device=device, **kw).run()
+    c.run()                                             # the timed run: the first one carries the first-launch costs
+    res = dict(workload=workload, op=op, m=len(trains), d=x.d, maxrank=r, operand_max_rank=int(max(t.ranks().max() for t in trains)),
+               run_ms=c.seconds * 1e3, neval=c.neval, value=c.quad(quad), ranks_max=int(c.ranks().max()))
+    c.set_profile(True)
+    c.run()
+    last = c.trainfun_last()
+    res.update(slot_ms=last["ms"], slot_launches=last["launches"], slot_elements=last["elements"],
+               slot_elements_per_s=last["elements"] / (last["ms"] * 1e-3) if last["ms"] > 0 else None)
+    addr = _trainfun_twin(trains, op)
+    if addr is not None:
+        hh = TTCross(x._n, TTX_FUN_HOST, [], r, device=device, **kw)
+        hh.set_integrand_host(addr, [0.0]).run()
+        res.update(host_run_ms=hh.seconds * 1e3, host_calls=hh.host_calls, host_same_value=hh.quad(quad) == res["value"],
+                   host_same_tapes=bool(np.array_equal(hh.tapes(), c.tapes())))
+        hh.close()
+    else:
+        res["host_route"] = "not run: the host twin (tests/trainfun_ref.c of the source tree, compiled with gcc) is not available here"
+        print("compose: no host twin (tests/trainfun_ref.c or gcc missing): the host-callback comparison is left out", file=sys.stderr)
+    rng = np.random.default_rng(1)
+    ind = np.stack([rng.integers(1, int(nk) + 1, size=npts) for nk in x._n], axis=1).astype(np.int32)
+    ti = torch.from_numpy(ind).to(torch.device("cuda", device))
+    x.tijk_batch(ti, "exact")
+    ms = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        x.tijk_batch(ti, "exact")
+        ms.append((time.perf_counter() - t0) * 1e3)
+    res.update(tijk_exact_points_per_s=npts / (float(np.median(ms)) * 1e-3))
+    if res.get("slot_elements_per_s"):
+        res["slot_vs_tijk_per_operand"] = res["slot_elements_per_s"] / (res["tijk_exact_points_per_s"] / len(trains))
+    print(json.dumps(res))
+    c.close()
+    if y is not None:
+        y.close()
+    return res
+
+
 def keep_flags(spec, d):
     """KEEPSPEC of the contract sub-command: 'ends' (first and last mode), 'mid' (the two middle modes), 'everyN' (modes N, 2N,
     ...), or 1-based mode numbers separated by commas"""
@@ -568,6 +653,8 @@ def run_sample(argv, device=0, repeats=5, tt=None, host_npts=1000):
 if __name__ == "__main__":
     if sys.argv[1] == "tijk":
         run_tijk(sys.argv[2:])
+    elif sys.argv[1] == "compose":
+        run_compose(sys.argv[2:])
     elif sys.argv[1] == "sample":
         run_sample(sys.argv[2:])
     elif sys.argv[1] == "contract":

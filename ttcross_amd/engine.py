@@ -17,6 +17,10 @@ import numpy as np
 TTX_FUN_ISING, TTX_FUN_STDNORM, TTX_FUN_MVN, TTX_FUN_HOST = 1, 2, 3, 4
 TTX_FUN_COSCOEFF = 5       # calc_coefficient of test_crs_coscoeff.f90: aux = [mu, Sigma column-major, a, b], par unused
 TTX_FUN_DEVICE = 6         # any user `fun` on the device: a code object written against include/ttx_device_fun.h (set_integrand_device)
+TTX_FUN_TRAINS = 7         # fun(i) = g(x_1(i), .., x_m(i)) of resident trains (TTCross.of_trains, set_integrand_trains)
+TTX_TRAINS_MAX = 8
+TTX_TOP_PRODUCT, TTX_TOP_RATIO, TTX_TOP_SQRTABS, TTX_TOP_DEVICE = 1, 2, 3, 4
+TRAIN_OPS = {"product": TTX_TOP_PRODUCT, "ratio": TTX_TOP_RATIO, "sqrtabs": TTX_TOP_SQRTABS}
 TTX_EVAL_EXACT, TTX_EVAL_MFMA, TTX_EVAL_AUTO = 0, 1, 2
 EVAL_MODES = {"exact": TTX_EVAL_EXACT, "mfma": TTX_EVAL_MFMA, "auto": TTX_EVAL_AUTO}
 K_NAMES = ("lottery", "halfstep", "accept", "exchange", "quad", "other")
@@ -128,6 +132,10 @@ def load_library():
     L.ttx_set_integrand_device.argtypes = [c_void_p, c_char_p, c_int64, c_char_p, POINTER(c_double), c_int32]
     L.ttx_set_integrand_device_file.argtypes = [c_void_p, c_char_p, c_char_p, POINTER(c_double), c_int32]
     L.ttx_eval_device.argtypes = [c_void_p, c_int64, POINTER(c_int32), POINTER(c_double)]
+    L.ttx_set_integrand_trains.argtypes = [c_void_p, c_int32, POINTER(c_void_p), c_int32]
+    L.ttx_set_integrand_trains_device.argtypes = [c_void_p, c_int32, POINTER(c_void_p), c_char_p, c_int64, c_char_p, POINTER(c_double), c_int32]
+    L.ttx_set_integrand_trains_device_file.argtypes = [c_void_p, c_int32, POINTER(c_void_p), c_char_p, c_char_p, POINTER(c_double), c_int32]
+    L.ttx_trainfun_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int64), POINTER(c_int64)]
     L.ttx_k_exp.argtypes = [c_int32, c_int64, POINTER(c_double), POINTER(c_double)]
     L.ttx_exp_host.argtypes = [c_int64, POINTER(c_double), POINTER(c_double)]
     _lib = L
@@ -418,8 +426,55 @@ class TTCross:
             _check(L.ttx_set_integrand_device_file(self._h, os.fsencode(image_or_path), name.encode(), _dp(p) if p.size else None, p.size))
         return self
 
+    @classmethod
+    def of_trains(cls, trains, op, maxrank, accuracy=None, pivoting=3, quad=None, nproc=1, combiner=None, par=None, device=None):
+        """An engine whose integrand is a function of resident trains, fun(i) = g(x_1(i), .., x_m(i)) (include/ttx.h:
+        TTX_FUN_TRAINS): mode sizes from trains[0], the integrand set (set_integrand_trains); .run() is the cross sweep.
+        op: TTX_TOP_PRODUCT / _RATIO / _SQRTABS or their names in TRAIN_OPS; with combiner = (image_or_path, name) the loaded
+        combiner of include/ttx_device_fun.h (TTX_DEVICE_COMBINER) is used instead and op is ignored."""
+        trains = list(trains)
+        if not trains:
+            raise ValueError("of_trains: at least one train")
+        tt = cls(trains[0]._n, TTX_FUN_TRAINS, [], maxrank, pivoting=pivoting, accuracy=accuracy, quad=quad, nproc=nproc,
+                 device=trains[0].device if device is None else device)
+        try:
+            return tt.set_integrand_trains(trains, combiner if combiner is not None else op, par)
+        except Exception:
+            tt.close()
+            raise
+
+    def set_integrand_trains(self, trains, op, par=None):
+        """The operands and the combiner of an engine created with fun_id = TTX_FUN_TRAINS (include/ttx.h).  op: a TTX_TOP_* value,
+        its name in TRAIN_OPS, or (image_or_path, name) for a loaded combiner, whose par is COPIED to the device.  The engine records
+        the operands' handles and looks at them again at the start of every run / accchk / eval_device; this wrapper keeps the
+        operand objects referenced so that they cannot be collected while registered."""
+        L = load_library()
+        trains = list(trains)
+        hs = (c_void_p * max(len(trains), 1))(*[t._h if t is not None else None for t in trains])
+        if isinstance(op, (tuple, list)):
+            image_or_path, name = op
+            p = np.zeros(0) if par is None else np.ascontiguousarray(par, dtype=np.float64)
+            pp = _dp(p) if p.size else None
+            if isinstance(image_or_path, (bytes, bytearray, memoryview)):
+                img = bytes(image_or_path)
+                _check(L.ttx_set_integrand_trains_device(self._h, len(trains), hs, img, len(img), name.encode(), pp, p.size))
+            else:
+                _check(L.ttx_set_integrand_trains_device_file(self._h, len(trains), hs, os.fsencode(image_or_path), name.encode(), pp, p.size))
+        else:
+            _check(L.ttx_set_integrand_trains(self._h, len(trains), hs, int(TRAIN_OPS.get(op, op))))
+        self._operands = trains
+        return self
+
+    def trainfun_last(self):
+        """Of the last run / eval_device of a TTX_FUN_TRAINS engine: {'ms', 'launches', 'elements'} of the slot kernel (ms needs
+        set_profile(True)) (include/ttx.h: ttx_trainfun_last)."""
+        ms, nl, ne = c_double(), c_int64(), c_int64()
+        _check(load_library().ttx_trainfun_last(self._h, ctypes.byref(ms), ctypes.byref(nl), ctypes.byref(ne)))
+        return dict(ms=ms.value, launches=nl.value, elements=ne.value)
+
     def eval_device(self, ind):
-        """The loaded device integrand at the multi-indices ind (npts x d, 1-based), through the code object's list kernel."""
+        """The loaded device integrand at the multi-indices ind (npts x d, 1-based), through the code object's list kernel; for a
+        TTX_FUN_TRAINS engine the operands at those indices and the combiner."""
         ind = np.ascontiguousarray(ind, dtype=np.int32).reshape(-1, self.d)
         out = np.zeros(ind.shape[0])
         _check(load_library().ttx_eval_device(self._h, ind.shape[0], _ip(ind), _dp(out)))

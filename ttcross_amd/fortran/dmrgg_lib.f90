@@ -140,6 +140,74 @@ contains
   if(present(neval))neval=ttx_neval(arg%ttx)
  end subroutine
 
+ subroutine dtt_dmrgg_trains(arg,x,op,accuracy,maxrank,pivoting,neval,quad)
+  ! Cross approximation of a function of trains (not in the reference; TT-Toolbox: multifuncrs): arg(i) = g(x(1)(i), .., x(m)(i)),
+  ! g = TTX_TOP_PRODUCT / TTX_TOP_RATIO / TTX_TOP_SQRTABS of ttx_c, evaluated on the device (TTX_FUN_TRAINS, include/ttx.h).
+  ! arg takes l = 1, m and n from x(1).  Resident operands are used where they are; host trains are staged for the call as
+  ! contract / axpby stage them.  With a staged operand the result comes back as a host train (the engine that ran the sweep
+  ! would otherwise keep the handle of a train that is gone); with resident operands only, arg keeps the device train, and the
+  ! caller keeps the operands alive as long as arg is asked to run or check again.
+  type(dtt),intent(inout),target :: arg
+  type(dtt),intent(in) :: x(:)
+  integer,intent(in) :: op
+  double precision,intent(in),optional :: accuracy
+  integer,intent(in),optional :: maxrank
+  integer,intent(in),optional :: pivoting
+  integer(kind=8),intent(out),optional :: neval
+  type(dtt),intent(in),optional :: quad
+  character(len=*),parameter :: subnam='dtt_dmrgg_trains'
+  type(ttx_config) :: cfg
+  integer(c_int32_t),allocatable,target :: nn(:),rk(:)
+  real(c_double),allocatable,target :: qw(:)
+  type(c_ptr) :: hs(TTX_TRAINS_MAX)
+  logical :: tmp(TTX_TRAINS_MAX)
+  integer :: m,k,t,nx,off,ngroups,stat
+  character(len=32) :: env
+  nx=size(x)
+  if(nx.lt.1 .or. nx.gt.TTX_TRAINS_MAX)then;write(*,*)subnam,': 1 ..',TTX_TRAINS_MAX,' operands expected, got ',nx;stop;endif
+  if(x(1)%l.ne.1)then;write(*,*)subnam,': only l=1 is supported (as in every driver)';stop;endif
+  m=x(1)%m
+  do t=2,nx
+   if(x(t)%l.ne.1 .or. x(t)%m.ne.m)then;write(*,*)subnam,': dimensions not match, operand ',t;stop;endif
+   if(any(x(t)%n(1:m).ne.x(1)%n(1:m)))then;write(*,*)subnam,': sizes not match, operand ',t;stop;endif
+  end do
+  arg%l=1; arg%m=m; arg%n(1:m)=x(1)%n(1:m)
+  allocate(nn(m)); nn=arg%n(1:m)
+  cfg%d=m; cfg%n=c_loc(nn); cfg%fun_id=TTX_FUN_TRAINS; cfg%par=c_null_ptr; cfg%npar=0
+  cfg%aux=c_null_ptr; cfg%naux=0; cfg%quadw=c_null_ptr
+  if(present(quad))then
+   allocate(qw(sum(arg%n(1:m)))); off=0
+   do k=1,m; qw(off+1:off+arg%n(k))=quad%u(k)%p(1,1:arg%n(k),1); off=off+arg%n(k); end do
+   cfg%quadw=c_loc(qw)
+  end if
+  cfg%accuracy=-1.d0; if(present(accuracy))cfg%accuracy=accuracy
+  cfg%maxrank=128; if(present(maxrank))cfg%maxrank=maxrank
+  cfg%pivoting=default(3,pivoting)
+  cfg%tru=0.d0; cfg%has_tru=0
+  cfg%mybonds=c_null_ptr; ngroups=1
+  call get_environment_variable('TTX_NGROUPS',env,status=stat)
+  if(stat.eq.0)read(env,*)ngroups
+  cfg%nproc=ngroups
+  cfg%device=0; cfg%world_rank=0; cfg%world_size=1; cfg%verbose=1; cfg%arith=0
+  call get_environment_variable('TTX_DEVICE',env,status=stat)
+  if(stat.eq.0)read(env,*)cfg%device
+  if(c_associated(arg%ttx))then; call ttx_destroy(arg%ttx); arg%ttx=c_null_ptr; endif
+  call ttx_check(ttx_create(arg%ttx,cfg),subnam)
+  do t=1,nx; call dtt_stage(x(t),hs(t),tmp(t),subnam); end do
+  call ttx_check(ttx_set_integrand_trains(arg%ttx,int(nx,c_int32_t),hs,int(op,c_int32_t)),subnam)
+  call ttx_check(ttx_run(arg%ttx),subnam)
+  allocate(rk(0:m))
+  call ttx_check(ttx_get_ranks(arg%ttx,rk),subnam)
+  arg%r(0:m)=rk(0:m)
+  call alloc(arg)
+  do k=1,m; call ttx_check(ttx_get_core(arg%ttx,int(k,c_int),arg%u(k)%p),subnam); end do
+  if(present(neval))neval=ttx_neval(arg%ttx)
+  if(any(tmp(1:nx)))then
+   call ttx_destroy(arg%ttx); arg%ttx=c_null_ptr
+   do t=1,nx; if(tmp(t))call ttx_destroy(hs(t)); end do
+  end if
+ end subroutine
+
  double precision function dtt_quad(arg,quad,mybonds) result(val)
   ! lib/dmrgg.f90:1261: rank-1 quadrature of the TT held by the engine (quad absent: sum over all modes)
   type(dtt),intent(in),target :: arg

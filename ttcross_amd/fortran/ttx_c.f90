@@ -3,7 +3,8 @@
 module ttx_c
  use iso_c_binding
  implicit none
- integer(c_int32_t),parameter :: TTX_FUN_ISING=1, TTX_FUN_STDNORM=2, TTX_FUN_MVN=3, TTX_FUN_HOST=4, TTX_FUN_COSCOEFF=5, TTX_FUN_DEVICE=6
+ integer(c_int32_t),parameter :: TTX_FUN_ISING=1, TTX_FUN_STDNORM=2, TTX_FUN_MVN=3, TTX_FUN_HOST=4, TTX_FUN_COSCOEFF=5, TTX_FUN_DEVICE=6, TTX_FUN_TRAINS=7
+ integer(c_int32_t),parameter :: TTX_TRAINS_MAX=8, TTX_TOP_PRODUCT=1, TTX_TOP_RATIO=2, TTX_TOP_SQRTABS=3, TTX_TOP_DEVICE=4
  type,bind(C) :: ttx_config
   integer(c_int32_t) :: d
   type(c_ptr) :: n
@@ -47,6 +48,17 @@ module ttx_c
   function ttx_set_integrand_device_file(h,path,name,par,npar) bind(C,name='ttx_set_integrand_device_file') result(rc)
    import; type(c_ptr),value :: h; character(kind=c_char) :: path(*),name(*); type(c_ptr),value :: par; integer(c_int32_t),value :: npar
    integer(c_int) :: rc
+  end function
+  ! integrand of resident trains (TTX_FUN_TRAINS, include/ttx.h): x = m engine handles
+  function ttx_set_integrand_trains(h,m,x,op) bind(C,name='ttx_set_integrand_trains') result(rc)
+   import; type(c_ptr),value :: h; integer(c_int32_t),value :: m,op; type(c_ptr),intent(in) :: x(*); integer(c_int) :: rc
+  end function
+  function ttx_set_integrand_trains_device_file(h,m,x,path,name,par,npar) bind(C,name='ttx_set_integrand_trains_device_file') result(rc)
+   import; type(c_ptr),value :: h; integer(c_int32_t),value :: m; type(c_ptr),intent(in) :: x(*); character(kind=c_char) :: path(*),name(*)
+   type(c_ptr),value :: par; integer(c_int32_t),value :: npar; integer(c_int) :: rc
+  end function
+  function ttx_trainfun_last(h,ms,launches,elements) bind(C,name='ttx_trainfun_last') result(rc)
+   import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms; integer(c_int64_t),intent(out) :: launches,elements; integer(c_int) :: rc
   end function
   function ttx_eval_device(h,npts,ind,out) bind(C,name='ttx_eval_device') result(rc)
    import; type(c_ptr),value :: h; integer(c_int64_t),value :: npts; integer(c_int32_t) :: ind(*); real(c_double) :: out(*); integer(c_int) :: rc
