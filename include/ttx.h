@@ -86,7 +86,7 @@ typedef struct ttx_sweep_rec {
 
 const char *ttx_last_error(void);
 int ttx_version(void);   /* 2: loadable device integrands; 3: ttx_ijk_batch, ttx_ijk_batch_dev, ttx_value_batch (ttx_contract,
-                          * ttx_marginals, ttx_lincomb, ttx_hadamard and ttx_algebra_last came later without a new number:
+                          * ttx_marginals, ttx_lincomb, ttx_hadamard, ttx_algebra_last and ttx_mode_apply came later without a new number:
                           * look the symbols up) */
 
 /* allocate device state for one dtt_dmrgg problem (replaces the implicit set-up of lib/dmrgg.f90:58-148) */
@@ -309,6 +309,35 @@ int ttx_contract_modesum(const ttx_engine *h, double *ms, double *bytes);
 int ttx_lincomb(int32_t m, const double *coef /* [m] */, ttx_engine *const *x /* [m] */, ttx_engine **out);
 int ttx_hadamard(ttx_engine *x, ttx_engine *y, ttx_engine **out);
 int ttx_algebra_last(const ttx_engine *h, double *ms, double *bytes_read, double *bytes_written);
+
+/* Matrices applied to chosen modes of the resident train, on the device (ttcross_amd/csrc/ttx_modeapply.h): the n-mode product,
+ * G'_k(a, j, b) = sum_i A_k(j, i) G_k(a, i, b) with A_k of m_k x n_k (TT-Toolbox: ttm).  COS coefficients to values on a grid,
+ * regridding, cumulative sums and differentiation along a mode.  ttx_contract is the case m_k = 1 followed by dropping the mode.
+ *   m    : d entries; 0 = mode k is left alone, m_k >= 1 = mode k gets m_k indices
+ *   A    : the matrices of the applied modes only, concatenated in mode order; block k is m_k x n_k, column-major: A_k(j, i) lies at
+ *          j + m_k i (a Fortran a(m, n) passes as it is).  Entries are not inspected: NaN and Inf propagate.
+ *   mode : TTX_EVAL_EXACT  s = 0.0; for i = 0 .. n_k-1: s = s + A_k(j, i) * G_k(a, i, b) -- ascending i, separate multiply and add
+ *          TTX_EVAL_MFMA   the same sums on the fp64 matrix cores, in the instruction's own order: equal to EXACT to rounding.  An
+ *                          element does not depend on the tiling of other cores or on the grid; no atomics, no split of the sum
+ *                          across workgroups: a call repeats bit for bit
+ *          TTX_EVAL_AUTO   the engine chooses by the work of the call (ttx_mode_apply_last tells what ran)
+ *   *out : a new single-process engine without integrand (as ttx_contract's), owned by the caller.  Ranks are unchanged, mode sizes
+ *          are m_k where applied and n_k elsewhere, storage is sized by the new train's own largest mode.  A core that is not
+ *          applied is a bit-identical device-to-device copy; with every m(k) = 0 the result is a bit-identical deep copy.  The
+ *          source engine and its work space are not modified.
+ * Everything is enqueued on the source engine's stream and the call synchronises before it returns; the matrices go to the device
+ * once per call (ttx_mode_apply_dev reads them in place, on the engine's device); no core crosses the host link.
+ * TTX_EINVAL, each before any device call: a null h, m or out; a null A while some m(k) > 0; a negative m(k); an unknown mode; a
+ * new mode size the engine's limits refuse, m_k > 32000 or largest rank times m_k > 131072 (the message names the mode and the
+ * value).  TTX_ESTATE: an engine without a train; a multi-process engine is refused as by ttx_ijk (a replica, ttx_replicate, is
+ * accepted).  After a refusal *out is NULL and nothing stays allocated.
+ * ttx_mode_apply_last: the apply launch of the last call on this engine -- its milliseconds (HIP events; 0 when no mode was
+ * applied), bytes_read = 8 sum r0 n_k r1 over the applied modes plus the matrices, bytes_written = 8 sum r0 m_k r1, flops =
+ * 2 sum r0 r1 n_k m_k, and the mode that ran (-1: none yet).  Any pointer may be NULL.
+ * Added without a new ttx_version: look the symbols up. */
+int ttx_mode_apply    (ttx_engine *h, const int32_t *m /* [d] */, const double *A, int32_t mode, ttx_engine **out);
+int ttx_mode_apply_dev(ttx_engine *h, const int32_t *m, const double *A_dev, int32_t mode, ttx_engine **out);
+int ttx_mode_apply_last(const ttx_engine *h, double *ms, double *bytes_read, double *bytes_written, double *flops, int32_t *mode_ran);
 
 /* Samples drawn from the resident train by sequential conditional sampling, on the device (ttcross_amd/csrc/ttx_sample.h).
  * Modes are 1-based, G_k is core k, r_0 = r_d = 1.

@@ -52,6 +52,7 @@ static cluster_kernel_t cluster_kernel(int var)
 #include "ttx_coscoeff.h"
 #include "ttx_eval.h"
 #include "ttx_contract.h"
+#include "ttx_modeapply.h"
 #include "ttx_algebra.h"
 #include "ttx_sample.h"
 #include "ttx_trainfun.h"
@@ -114,7 +115,7 @@ static int rccl_load()
 }
 #define NCCLCHECK(x) do { ncclResult_t e_ = (x); if (e_ != ncclSuccess) return fail(TTX_EHIP, "%s failed: %s", #x, g_rccl.GetErrorString(e_)); } while (0)
 
-// Operations on the resident train (ttx_eval.h, ttx_contract.h, ttx_algebra.h, ttx_sample.h) share one table of device work space
+// Operations on the resident train (ttx_eval.h, ttx_contract.h, ttx_algebra.h, ttx_sample.h, ttx_modeapply.h) share one table of device work space
 // per engine, grown on demand (buf_reserve), freed in ttx_destroy.  A slot belongs to one role; two roles share a slot only where no
 // single call uses both, because a second buf_reserve of a slot may move what the first one handed out.  ttx_sample is the widest
 // call: SC_TRAIN, SC_META, SC_W, SC_M, SC_VEC, SC_H, SC_ROW, SC_CNT and the staging slots are all live in it.
@@ -127,6 +128,7 @@ enum {
     SC_W, SC_M, SC_P, SC_SCR, SC_VEC,   // contraction: weights, M matrices, run products, their overflow, the l and s vectors
     SC_H, SC_ROW, SC_CNT,               // sampling: head tables, global rows of long modes, the failure counter
     SC_TFUN, SC_TVAL,                   // TTX_FUN_TRAINS: the operands' blocks (core pointers, ranks) of a run, the values for a loaded combiner
+    SC_MAT,                             // ttx_mode_apply: the matrices of the applied modes (its tables go to SC_META)
     SC_NBUF
 };
 struct EvBuf { void *p = nullptr; size_t bytes = 0; };
@@ -137,7 +139,7 @@ struct OpTimer {
     int stop(hipStream_t s) { HIPCHECK(hipEventRecord(ev[1], s)); return TTX_OK; }
     int ms(double *out) { float t = 0.f; HIPCHECK(hipEventElapsedTime(&t, ev[0], ev[1])); *out = t; return TTX_OK; }   // after a synchronise
 };
-enum { TM_MODESUM, TM_ALG, TM_HEAD, TM_DRAW, TM_N };    // k_ct_modesum, the algebra launch, k_sm_head, the k_sm_draw of a chunk
+enum { TM_MODESUM, TM_ALG, TM_HEAD, TM_DRAW, TM_APPLY, TM_N };    // k_ct_modesum, the algebra launch, k_sm_head, the k_sm_draw of a chunk, k_ma_apply
 
 struct DevFun;                          // a loaded device integrand (TTX_FUN_DEVICE), defined with slot_eval
 struct TrainFun;                        // the operands and the combiner of TTX_FUN_TRAINS, defined with slot_eval
@@ -252,6 +254,8 @@ struct ttx_engine {
     double alg_ms = 0.0, alg_rd = 0.0, alg_wr = 0.0;    // the last ttx_lincomb / ttx_hadamard with this engine first
     double sm_ms_head = 0.0, sm_bytes = 0.0, sm_ms_draw = 0.0;  // the last ttx_sample
     int64_t sm_failed = 0;
+    double ma_ms = 0.0, ma_rd = 0.0, ma_wr = 0.0, ma_flops = 0.0;   // the apply launch of the last ttx_mode_apply
+    int ma_mode = -1;
 };
 
 // ---- worker threads for the host integrand (the reference evaluates `fun` inside !$OMP PARALLEL DO regions,
@@ -3881,6 +3885,119 @@ extern "C" int ttx_algebra_last(const ttx_engine *h, double *ms, double *bytes_r
 {
     if (!h || !ms || !bytes_read || !bytes_written) return fail(TTX_EINVAL, "ttx_algebra_last: null argument");
     *ms = h->alg_ms; *bytes_read = h->alg_rd; *bytes_written = h->alg_wr;
+    return TTX_OK;
+}
+
+// ---- matrices applied to chosen modes (ttx_modeapply.h) -------------------------------------------------------------------------
+// TTX_EVAL_AUTO: a break-even in flops per call (TTX_MA_AUTO_FLOPS, ttx_modeapply.h; profiles/modeapply_mi355x.txt)
+static int ma_auto(double flops)
+{
+    return flops >= TTX_MA_AUTO_FLOPS ? TTX_EVAL_MFMA : TTX_EVAL_EXACT;
+}
+static void ma_core(MaCore &c, long long *tiles)
+{
+    c.nab = (c.r0 + 15) / 16; c.npan = (c.m + TTX_MA_JP - 1) / TTX_MA_JP;
+    c.ngrp = (int)(((long long)c.nab * c.r1 + TTX_MA_UNITS - 1) / TTX_MA_UNITS); c.pad = 0;
+    c.first = *tiles;
+    *tiles += (long long)c.ngrp * c.npan;
+}
+// everything of ttx_mode_apply that works on the new engine e: a failure leaves e to the caller to destroy
+static int ma_fill(ttx_engine *h, ttx_engine *e, const int32_t *m, const double *A, bool dev, int mode)
+{
+    const int d = h->d;
+    std::vector<MaCore> app, cpy;
+    long long tapp = 0, tcpy = 0;
+    std::vector<size_t> aoff;                                                   // of every applied mode's block in the matrices
+    size_t asize = 0;
+    double rd = 0.0, wr = 0.0, fl = 0.0;
+    for (int k = 0; k < d; k++) {
+        MaCore c{};
+        c.src = core_dev(h, k + 1); c.dst = core_dev(e, k + 1);
+        c.r0 = h->rfinal[k]; c.n = h->n1[k + 1]; c.r1 = h->rfinal[k + 1];
+        if (m[k] > 0) {
+            c.m = m[k];
+            aoff.push_back(asize);
+            asize += (size_t)c.m * c.n;
+            rd += 8.0 * c.r0 * c.n * c.r1 + 8.0 * c.m * c.n; wr += 8.0 * c.r0 * c.m * c.r1; fl += 2.0 * c.r0 * c.r1 * c.n * c.m;
+            ma_core(c, &tapp);
+            app.push_back(c);
+        } else {
+            c.m = c.n; c.A = nullptr;
+            ma_core(c, &tcpy);
+            cpy.push_back(c);
+        }
+    }
+    if (tapp > 0x7fffffffll || tcpy > 0x7fffffffll) return fail(TTX_EINVAL, "ttx_mode_apply: too many tiles (%lld)", std::max(tapp, tcpy));
+    int rc;
+    const double *dA = A;
+    if (!dev && asize) {
+        if ((rc = buf_reserve(h, SC_MAT, sizeof(double) * asize))) return rc;
+        HIPCHECK(hipMemcpyAsync(buf<double>(h, SC_MAT), A, sizeof(double) * asize, hipMemcpyHostToDevice, h->stream));
+        dA = buf<double>(h, SC_MAT);
+    }
+    for (size_t t = 0; t < app.size(); t++) app[t].A = dA + aoff[t];
+    const int eff = mode == TTX_EVAL_AUTO ? ma_auto(fl) : mode;
+    OpMeta meta(h->meta_host);
+    const size_t o_app = meta.put(app), o_cpy = meta.put(cpy);
+    char *dm;
+    if ((rc = meta.upload(h, SC_META, &dm))) return rc;
+    h->ma_ms = 0.0; h->ma_rd = rd; h->ma_wr = wr; h->ma_flops = fl; h->ma_mode = eff;
+    if (!cpy.empty())
+        hipLaunchKernelGGL(k_ma_copy, dim3((unsigned)tcpy), dim3(256), 0, h->stream, (const MaCore *)(dm + o_cpy), (int)cpy.size(), h->RM, h->P.SS, e->RM, e->P.SS);
+    OpTimer &tm = h->timer[TM_APPLY];
+    if (!app.empty()) {
+        if ((rc = tm.start(h->stream))) return rc;
+        if (eff == TTX_EVAL_MFMA)
+            hipLaunchKernelGGL(k_ma_apply<true>, dim3((unsigned)tapp), dim3(256), 0, h->stream, (const MaCore *)(dm + o_app), (int)app.size(), h->RM, h->P.SS, e->RM, e->P.SS);
+        else
+            hipLaunchKernelGGL(k_ma_apply<false>, dim3((unsigned)tapp), dim3(256), 0, h->stream, (const MaCore *)(dm + o_app), (int)app.size(), h->RM, h->P.SS, e->RM, e->P.SS);
+        if ((rc = tm.stop(h->stream))) return rc;
+    }
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipGetLastError());
+    return app.empty() ? TTX_OK : tm.ms(&h->ma_ms);
+}
+static int ma_run(ttx_engine *h, const int32_t *m, const double *A, int32_t mode, ttx_engine **out, bool dev, const char *who)
+{
+    if (out) *out = nullptr;
+    if (!h || !m || !out) return fail(TTX_EINVAL, "%s: null argument", who);
+    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    const int d = h->d;
+    bool any = false;
+    for (int k = 0; k < d; k++) {
+        if (m[k] < 0) return fail(TTX_EINVAL, "%s: m(%d) = %d (0 = the mode is left alone, or a positive size)", who, k + 1, m[k]);
+        any = any || m[k] > 0;
+    }
+    if (any && !A) return fail(TTX_EINVAL, "%s: null matrices", who);
+    if (!h->ran) return fail(TTX_ESTATE, "%s: no tensor train (run dtt_dmrgg first)", who);
+    const int rmax = std::max(1, (int)*std::max_element(h->rfinal.begin(), h->rfinal.begin() + d + 1));
+    std::vector<int32_t> nn = modes_of(h), rr(h->rfinal.begin(), h->rfinal.begin() + d + 1);
+    for (int k = 0; k < d; k++) {
+        if (m[k] == 0) continue;
+        if (m[k] > 32000) return fail(TTX_EINVAL, "%s: m(%d) = %d, the engine holds modes up to 32000", who, k + 1, m[k]);
+        if ((long long)rmax * m[k] > (long long)TTX_MAXPART * TTX_BLK)
+            return fail(TTX_EINVAL, "%s: m(%d) = %d times the largest rank %d is %lld, the engine holds up to %d", who, k + 1, m[k], rmax, (long long)rmax * m[k], TTX_MAXPART * TTX_BLK);
+        nn[k] = m[k];
+    }
+    if (int rc = check_train_one_process(h, who)) return rc;
+    return new_train(out, who, d, nn.data(), rr.data(), h->cfg.device, [&](ttx_engine *e) { return ma_fill(h, e, m, A, dev, mode); });
+}
+extern "C" int ttx_mode_apply(ttx_engine *h, const int32_t *m, const double *A, int32_t mode, ttx_engine **out)
+{
+    return ma_run(h, m, A, mode, out, false, "ttx_mode_apply");
+}
+extern "C" int ttx_mode_apply_dev(ttx_engine *h, const int32_t *m, const double *A_dev, int32_t mode, ttx_engine **out)
+{
+    return ma_run(h, m, A_dev, mode, out, true, "ttx_mode_apply_dev");
+}
+extern "C" int ttx_mode_apply_last(const ttx_engine *h, double *ms, double *bytes_read, double *bytes_written, double *flops, int32_t *mode_ran)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_mode_apply_last: null engine");
+    if (ms) *ms = h->ma_ms;
+    if (bytes_read) *bytes_read = h->ma_rd;
+    if (bytes_written) *bytes_written = h->ma_wr;
+    if (flops) *flops = h->ma_flops;
+    if (mode_ran) *mode_ran = h->ma_mode;
     return TTX_OK;
 }
 

@@ -564,6 +564,83 @@ def run_algebra(argv, device=0, tt=None):
     return res
 
 
+def cos_matrix(xs, n_terms, a, b):
+    """The synthesis matrix of a cosine expansion on [a, b]: entry (j, k) = cos(k pi (xs[j] - a) / (b - a)), k = 0 .. n_terms-1.
+    Applied to a mode of a train of COS coefficients (TTCross.mode_apply) it gives the values at the points xs; the coefficients
+    carry the halved first term and the factor 2 / (b - a) themselves, as the c of cos_approximate."""
+    xs = np.asarray(xs, dtype=np.float64).ravel()
+    return np.cos(np.outer(xs - a, np.arange(int(n_terms)) * (math.pi / (b - a))))
+
+
+def mode_apply_host(tt, mats):
+    """what a user does without ttx_mode_apply: every core to the host, the products in numpy (the sums over ascending i with a
+    separate multiply and add, the order of TTX_EVAL_EXACT), the result back to the device"""
+    out = []
+    for k, a in enumerate(mats):
+        g = tt.core(k + 1)
+        if a is None:
+            out.append(g)
+            continue
+        a = np.asarray(a, dtype=np.float64)
+        z = np.zeros((g.shape[0], a.shape[0], g.shape[2]))
+        for i in range(g.shape[1]):
+            z = z + a[None, :, i, None] * g[:, None, i, :]
+        out.append(z)
+    return TTCross.from_cores(out, device=tt.device)
+
+
+def run_modeapply(argv, device=0, tt=None):
+    """modeapply WORKLOAD M [MODE] [REPS]: the trains of the tijk sub-command; an M x n matrix of seeded standard normals applied
+    to every mode in MODE (exact, mfma or auto; default mfma), one warm-up and the median of REPS (default 10) calls: per call the
+    milliseconds with the new engine's creation, the apply kernel's milliseconds, bytes and flops through ttx_mode_apply_last, its
+    rates and its share of the bandwidth probe (ttx_k_residual_bench on rows x 64 of the same byte count); then the host route
+    once and the comparison with it: bit for bit in exact, against 2 (n + 1) u sum |A| |G| otherwise.  Prints one JSON line."""
+    import json
+    import time
+    from .engine import k_residual_bench
+    workload, M = argv[0], int(argv[1])
+    mode = argv[2] if len(argv) > 2 else "mfma"
+    reps = int(argv[3]) if len(argv) > 3 else 10
+    tt = tt or tijk_train(workload, device=device)
+    rng = np.random.default_rng(M)
+    mats = [rng.standard_normal((M, int(nk))) for nk in tt._n]
+    tt.mode_apply(mats, mode).close()
+    ms, ks = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        r = tt.mode_apply(mats, mode)               # synchronises before it returns
+        ms.append((time.perf_counter() - t0) * 1e3)
+        ks.append(tt.mode_apply_last())
+        r.close()
+    kms = float(np.median([k["ms"] for k in ks]))
+    rd, wr, fl = ks[0]["bytes_read"], ks[0]["bytes_written"], ks[0]["flops"]
+    probe_ms, probe_bytes = k_residual_bench(max(1, int((rd + wr) / (8 * 64))), 64, 20, device=device)
+    rate, probe = (rd + wr) / (kms * 1e-3), probe_bytes / (probe_ms * 1e-3)
+    res = dict(workload=workload, d=tt.d, max_rank=int(tt.ranks().max()), M=M, mode=mode, mode_ran=ks[0]["mode"], reps=reps,
+               ms=float(np.median(ms)), ms_min=float(min(ms)), kernel_ms=kms, kernel_ms_min=float(min(k["ms"] for k in ks)),
+               bytes_read=rd, bytes_written=wr, flops=fl, bytes_per_s=rate, probe_bytes_per_s=probe, fraction_of_probe=rate / probe,
+               flops_per_s=fl / (kms * 1e-3))
+    t0 = time.perf_counter()
+    ref = mode_apply_host(tt, mats)
+    res["host_route_ms"] = (time.perf_counter() - t0) * 1e3
+    r = tt.mode_apply(mats, mode)
+    if ks[0]["mode"] == "exact":
+        res["same_bytes_as_host_route"] = all(r.core(k).tobytes() == ref.core(k).tobytes() for k in range(1, r.d + 1))
+    else:
+        worst = 0.0
+        for k in range(1, r.d + 1):
+            g, n = np.abs(tt.core(k)), int(tt._n[k - 1])
+            S = np.einsum("ji,aib->ajb", np.abs(mats[k - 1]), g)
+            diff = np.abs(r.core(k) - ref.core(k))
+            worst = max(worst, float(np.max(diff / (2.0 * (n + 1) * 2.0 ** -53 * np.where(S > 0, S, 1.0)))))
+        res["max_diff_over_bound"] = worst
+        res["within_bound"] = worst <= 1.0
+    r.close()
+    ref.close()
+    print(json.dumps(res))
+    return res
+
+
 def sample_host(tt, u, w=None):
     """what a user does without ttx_sample: every core to the host with core(k), then the conditional marginals walked in
     numpy from the last mode to the first.  Returns (ind, logq, val) of the definition in include/ttx.h, in numpy's own
@@ -661,6 +738,8 @@ if __name__ == "__main__":
         run_contract(sys.argv[2:])
     elif sys.argv[1] == "algebra":
         run_algebra(sys.argv[2:])
+    elif sys.argv[1] == "modeapply":
+        run_modeapply(sys.argv[2:])
     elif sys.argv[1] == "chf":
         run_chf(sys.argv[2:])
     elif sys.argv[1] == "pdf":

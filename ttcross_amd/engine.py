@@ -109,6 +109,9 @@ def load_library():
     L.ttx_lincomb.argtypes = [c_int32, POINTER(c_double), POINTER(c_void_p), POINTER(c_void_p)]
     L.ttx_hadamard.argtypes = [c_void_p, c_void_p, POINTER(c_void_p)]
     L.ttx_algebra_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double)]
+    L.ttx_mode_apply.argtypes = [c_void_p, POINTER(c_int32), POINTER(c_double), c_int32, POINTER(c_void_p)]
+    L.ttx_mode_apply_dev.argtypes = [c_void_p, POINTER(c_int32), c_void_p, c_int32, POINTER(c_void_p)]
+    L.ttx_mode_apply_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
     L.ttx_sample.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
     L.ttx_sample_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(c_double), POINTER(c_int32), c_void_p, c_void_p, c_void_p]
     L.ttx_sample_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
@@ -679,6 +682,56 @@ class TTCross:
         ms, rd, wr = c_double(), c_double(), c_double()
         _check(load_library().ttx_algebra_last(self._h, ctypes.byref(ms), ctypes.byref(rd), ctypes.byref(wr)))
         return ms.value, rd.value, wr.value
+
+    # ---- matrices applied to chosen modes (include/ttx.h: ttx_mode_apply) --------------------------------
+    def mode_apply(self, mats, mode="auto"):
+        """The train with a matrix applied to chosen modes, G'_k(a, j, b) = sum_i A_k[j, i] G_k(a, i, b) (include/ttx.h:
+        ttx_mode_apply), as a new engine on the same device: ranks stay, mode k gets m_k indices.  mats: d entries, None = the mode
+        is left alone (its core is copied bit for bit), otherwise an (m_k, n_k) array; or a dict {mode (1-based): array}.  mode:
+        "exact" (ascending i, separate multiply and add), "mfma" (fp64 matrix cores) or "auto"; mode_apply_last() tells what ran.
+        When every matrix is a float64 torch tensor on the engine's device they are passed by pointer (ttx_mode_apply_dev).
+        No core crosses the host link."""
+        L, md = load_library(), _eval_mode(mode)
+        if isinstance(mats, dict):
+            bad = [k for k in mats if not (isinstance(k, (int, np.integer)) and 1 <= k <= self.d)]
+            if bad:
+                raise ValueError(f"mode_apply: modes 1..{self.d} expected as keys (got {bad})")
+            mats = [mats.get(k) for k in range(1, self.d + 1)]
+        mats = list(mats)
+        if len(mats) != self.d:
+            raise ValueError(f"mode_apply: {self.d} entries expected (None leaves a mode alone), got {len(mats)}")
+        is_torch = [a is not None and type(a).__module__.split(".")[0] == "torch" for a in mats]
+        for k, a in enumerate(mats):
+            if a is None:
+                continue
+            shape = tuple(a.shape)
+            if len(shape) != 2 or shape[0] < 1 or shape[1] != int(self._n[k]):
+                raise ValueError(f"mode_apply: the matrix of mode {k + 1} has shape {shape}, (m, {int(self._n[k])}) with m >= 1 expected")
+        m = np.ascontiguousarray([0 if a is None else int(a.shape[0]) for a in mats], dtype=np.int32)
+        h = c_void_p()
+        if any(is_torch) and all(t or a is None for t, a in zip(is_torch, mats)) and all(a.is_cuda for a in mats if a is not None):
+            import torch
+            ts = [a for a in mats if a is not None]
+            if any(a.device.index != self.device for a in ts):
+                raise ValueError(f"mode_apply: the matrices lie on another device than the engine's ({self.device})")
+            if any(a.dtype != torch.float64 for a in ts):
+                raise ValueError("mode_apply: float64 tensors expected")
+            flat = torch.cat([a.t().contiguous().reshape(-1) for a in ts])    # column-major blocks, assembled on the device
+            torch.cuda.current_stream(flat.device).synchronize()             # the engine runs on a stream of its own
+            _check(L.ttx_mode_apply_dev(self._h, _ip(m), c_void_p(flat.data_ptr()), md, ctypes.byref(h)))
+            return TTCross._adopt(h, self.device)
+        blocks = [np.asarray(a.cpu().numpy() if t else a, dtype=np.float64).ravel(order="F") for a, t in zip(mats, is_torch) if a is not None]
+        flat = np.ascontiguousarray(np.concatenate(blocks)) if blocks else None
+        _check(L.ttx_mode_apply(self._h, _ip(m), _dp(flat), md, ctypes.byref(h)))
+        return TTCross._adopt(h, self.device)
+
+    def mode_apply_last(self):
+        """dict(ms, bytes_read, bytes_written, flops, mode) of the apply launch of the last mode_apply on this engine (include/ttx.h:
+        ttx_mode_apply_last); mode is "exact" or "mfma" (None before the first call)"""
+        ms, rd, wr, fl, md = c_double(), c_double(), c_double(), c_double(), c_int32()
+        _check(load_library().ttx_mode_apply_last(self._h, ctypes.byref(ms), ctypes.byref(rd), ctypes.byref(wr), ctypes.byref(fl), ctypes.byref(md)))
+        names = {v: k for k, v in EVAL_MODES.items()}
+        return dict(ms=ms.value, bytes_read=rd.value, bytes_written=wr.value, flops=fl.value, mode=names.get(md.value))
 
     # ---- samples from the resident train (include/ttx.h: ttx_sample) -------------------------------------
     def sample(self, u_or_npts, w=None, fixed=None, seed=None, want=("ind", "logq", "val")):

@@ -67,6 +67,8 @@ module tt_lib
  ! partial contraction on the device (not in the reference): contract(arg,keep,res,w), marginals(arg,marg,w)
  interface contract;    module procedure dtt_contract;  end interface
  interface marginals;   module procedure dtt_marginals; end interface
+ ! matrices applied to chosen modes on the device (not in the reference): modeapply(arg,m,a,res,mode)
+ interface modeapply;   module procedure dtt_modeapply; end interface
  ! samples drawn from the train on the device (not in the reference): sample(arg,u,ind,w,fixed,logq,val)
  interface sample;      module procedure dtt_sample;    end interface
  ! sums and elementwise products on the device (not in the reference; its host + and * above stay as they are):
@@ -349,6 +351,35 @@ contains
   res%l=1; res%m=0
   do k=1,arg%m
    if(keep(k).ne.0)then; res%m=res%m+1; res%n(res%m)=arg%n(k); endif
+  end do
+  res%ttx=hn; call dtt_pull(res)
+ end subroutine
+ subroutine dtt_modeapply(arg,m,a,res,mode)
+  ! res = arg with a matrix applied to every mode k where m(k) > 0: res(.., j, ..) = sum_i A_k(j,i) arg(.., i, ..), mode k gets m(k)
+  ! indices, the ranks stay; m(k) = 0 leaves mode k alone.  a holds the blocks A_k(m(k),n(k)) of the applied modes one after the
+  ! other in mode order, each as Fortran stores an array a(m,n).  mode: 0 the sums over ascending i with a separate multiply and
+  ! add, 1 the fp64 matrix cores, 2 (the default) the engine chooses.  One call on the device (ttx_mode_apply); a host train is
+  ! staged for the call like for norm / dot_product.  res holds the new train on the device and, pulled, in res%u.
+  use ttx_c
+  type(dtt),intent(in) :: arg
+  integer,intent(in) :: m(:)
+  double precision,intent(in) :: a(*)
+  type(dtt),intent(inout) :: res
+  integer,intent(in),optional :: mode
+  integer(c_int32_t) :: mm(tt_size),md
+  type(c_ptr) :: h,hn
+  logical :: temp
+  integer :: k
+  call dtt_dealloc(res)
+  mm(1:arg%m)=m(1:arg%m)
+  md=2; if(present(mode))md=mode
+  call dtt_stage(arg,h,temp,'dtt_modeapply')
+  hn=c_null_ptr
+  call ttx_check(ttx_mode_apply(h,mm,a,md,hn),'dtt_modeapply')
+  if(temp)call ttx_destroy(h)
+  res%l=1; res%m=arg%m
+  do k=1,arg%m
+   res%n(k)=arg%n(k); if(m(k).gt.0)res%n(k)=m(k)
   end do
   res%ttx=hn; call dtt_pull(res)
  end subroutine

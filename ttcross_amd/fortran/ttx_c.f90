@@ -149,6 +149,14 @@ module ttx_c
   function ttx_algebra_last(h,ms,bytes_read,bytes_written) bind(C,name='ttx_algebra_last') result(rc)
    import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms,bytes_read,bytes_written; integer(c_int) :: rc
   end function
+  ! matrices applied to chosen modes (include/ttx.h): a = the column-major blocks m(k) x n(k) of the applied modes, one after the other
+  function ttx_mode_apply(h,m,a,mode,out) bind(C,name='ttx_mode_apply') result(rc)
+   import; type(c_ptr),value :: h; integer(c_int32_t),intent(in) :: m(*); real(c_double),intent(in) :: a(*); integer(c_int32_t),value :: mode
+   type(c_ptr) :: out; integer(c_int) :: rc
+  end function
+  function ttx_mode_apply_last(h,ms,bytes_read,bytes_written,flops,mode_ran) bind(C,name='ttx_mode_apply_last') result(rc)
+   import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms,bytes_read,bytes_written,flops; integer(c_int32_t),intent(out) :: mode_ran; integer(c_int) :: rc
+  end function
   ! samples drawn from the resident train (include/ttx.h); u(d,npts), ind(d,npts); w, fixed, logq, val: c_null_ptr where not wanted
   function ttx_sample(h,npts,u,w,fixed,ind,logq,val) bind(C,name='ttx_sample') result(rc)
    import; type(c_ptr),value :: h,w,fixed,logq,val; integer(c_int64_t),value :: npts; real(c_double),intent(in) :: u(*)
