@@ -44,6 +44,9 @@ def test_bad_arguments_mirror_reference_errors(libttx):
         E.TTCross(s["n"], s["fun_id"], s["par"], 8, pivoting=2, nproc=5)
     with pytest.raises(E.TTXError):
         E.TTCross(s["n"], s["fun_id"], s["par"], 0, pivoting=2)
+    # an integrand of trains runs in one process: refused with the arguments, before the device is asked for
+    with pytest.raises(E.TTXError, match=r"integrand of trains \(TTX_FUN_TRAINS\) runs in one process: bond groups \(nproc\) work, world_size 2 does not"):
+        E.TTCross([5] * 4, 7, [], 3, pivoting=2, nproc=2, world_size=2)
 
 
 def test_driver_setup_matches_oracle_setup(oracle_built):

@@ -19,6 +19,7 @@
 // de_pairs_tab, hence of the oracle: results stay bit-identical.
 #pragma once
 #include "ttx_kernels.h"
+#include "ttx_create_plan.h"    // the kernels' LDS formulas: de5_lds_doubles, de_rows_stride, det_lds_doubles, ... (shared with the host's plan)
 
 // a = (..((a OP p[0]) OP p[1]) ..) OP p[len-1] for an LDS row read with a wave-uniform address (broadcasts), OP = * or +.
 // A lone wave has nobody to hide the LDS latency behind (~130 cycles for four 16-byte broadcast reads), so the loop is
@@ -637,11 +638,8 @@ __device__ __forceinline__ double de_finish_vals(int id, double a, int m, const 
 // token hop costs 140-165 ns.  Two waves with 32-column segments: 5.42 s; 64-column segments in registers (305 registers,
 // one wave per SIMD): 8.5 s.
 // ------------------------------------------------------------------------------------------------------------------
-#define DE5_W 4
-#define DE5_SEG 16               // columns of a row's body per wave and round
+// DE5_W waves, DE5_SEG columns of a row's body per wave and round; LDS: de5_lds_doubles, de5_fits (ttx_create_plan.h)
 #define DE5_SENT 0xfff85a5a00000001ull
-__host__ __device__ inline size_t de5_lds_doubles(int m) { const int VS = ((m + 7) & ~7) + 8 + DE5_SEG; return (size_t)5 * VS + 128 + (size_t)DE5_W * 64; }
-__host__ __device__ inline bool de5_fits(int m) { return m >= 3; }
 
 __device__ __forceinline__ void de5_send(unsigned long long *box, int lane, double a)
 {
@@ -889,8 +887,7 @@ struct RStream {
     }
 };
 // LDS per DPP row: xv | wv | UL, each RSW doubles; RSW = 16 mod 32 so that the four rows' 16-lane reads hit disjoint bank halves
-__host__ __device__ inline int de_rows_stride(int m) { const int s = m + 56; return ((s + 31) & ~31) + 16; }
-__host__ __device__ inline size_t de_rows_lds_doubles(int m) { return (size_t)12 * de_rows_stride(m); }
+// (de_rows_stride, de_rows_lds_doubles: ttx_create_plan.h)
 
 // One row of the pair triangle for the four candidates of a wave: a = a * t(u0 xs[0]) * t(u0 xs[0] xs[1]) * ... (L factors,
 // t(u) = ((u-1)/(u+1))^2); `neutral0`: the first column is the neutral 1.0 (the row that starts after dim p).
@@ -1039,8 +1036,7 @@ __global__ __launch_bounds__(64) void k_lottery_eval_de_rows(DevProb P)
 // bit-identical.
 // ------------------------------------------------------------------------------------------------------------------
 // NBK blocks of 16 slots per chunk, four dividing waves per block: 3 (14 waves, one team per CU) or 1 (6 waves, several teams per CU)
-__host__ __device__ inline int det_vs(int m) { return ((m + 7) & ~7) + 8; }
-__host__ __device__ inline size_t det_lds_doubles(int m, int nbk) { return (size_t)4 * det_vs(m) + 256 + (det_vs(m) + 48) + (size_t)3 * nbk * 16 * 64; }
+// (det_vs, det_lds_doubles: ttx_create_plan.h)
 
 #ifdef TTX_STAMPS
 #ifndef DET_STAMPG

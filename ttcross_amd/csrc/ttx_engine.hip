@@ -37,6 +37,7 @@
 #include "../../include/ttx_device_fun.h"   // the slot ABI of loadable device integrands (TTX_FUN_DEVICE)
 #include "ttx_lds.h"
 #include "ttx_qr_plan.h"
+#include "ttx_create_plan.h"
 #include "ttx_kernels.h"
 #include "ttx_de.h"
 #include "ttx_mvn.h"
@@ -195,38 +196,23 @@ struct ttx_engine {
     // tt_lib utilities: compact work buffers, allocated on first use
     double *Wa = nullptr, *Wb = nullptr, *Wc = nullptr, *Wd = nullptr, *Sm = nullptr, *bak = nullptr;
     int *Si = nullptr;
-    size_t lds_half = 0, lds_lot = 0, lds_par = 0;
-    int half_vals = 0, lot_vals = 0;
-    int de_v2 = 0;                      // Ising D/E: wave-per-pivot half-step kernel k_halfstep_de (ttx_de.h)
-    int de_v5 = 0; size_t lds_de5 = 0;  // ... as a relay of four waves (k_halfstep_de5): the default where it fits
-    int de5_fallbacks = 0;
-    int de_slots = 0; size_t lds_de = 0;
-    int de_team = 0, de_team_units = 256, det_fallbacks = 0; size_t lds_det = 0;
-    int de_test_fault = 0;              // test hook (TTX_DE_TEST_FAULT=<sweep>): the team half-steps of that sweep get a grid of one unit
-    int de_team6_units = 1024; size_t lds_det6 = 0;                                      // ... and by teams of 6 waves, several per CU, for the launches above that   // ... by a team of 14 waves per unit (k_halfstep_det) while the ranks are small
-    int lot_rows = 0; size_t lds_der = 0;   // ... four candidates per wave, one per DPP row (k_lottery_eval_de_rows)
+    // what creation decided (ttx_create_plan.h): derived sizes, kernel variants, LDS sizes.  Fixed for the life of the engine; what a
+    // fallback of ttx_run takes out of use is recorded in `retired`, and the readers ask through the three functions below
+    CreatePlan sel;
+    struct Retired { bool cluster = false, de_team = false, de_v5 = false; } retired;   // with the cluster path goes Ising C's P.arith (ttx_run)
+    int cluster_nb() const { return retired.cluster ? 0 : sel.cluster; }   // workgroups per bond group of the cluster sweep kernel; 0: not used
+    bool de_team() const { return sel.de_team && !retired.de_team; }       // Ising D/E half-steps by wave teams (k_halfstep_det)
+    bool de_v5() const { return sel.de_v5 && !retired.de_v5; }             // ... by a relay of four waves (k_halfstep_de5)
+    int arith() const { return P.arith; }                                  // sel.arith, less Ising C's closed form once the cluster path is retired
+    int cluster_fallbacks = 0;          // runs replayed on the chain path after a cluster abort
+    int det_fallbacks = 0, de5_fallbacks = 0;   // ... without teams, without the relay
+    bool cluster_aborted = false;
     double *h_svd = nullptr; double svd_seq = 0.0;   // pinned: [seq, rank, sweeps, sv...] of the core dtt_svd works on (k_svd_report)
-    int de_lot_point = 0;                   // Ising D/E, unit-cut path: lottery candidates row-parallel without tables (k_lottery_eval_decp)
-    int lot_wave = 0;                       // Ising D/E: lottery candidates and boundary corners by the row-wise wave evaluator (ttx_de.h)
-    int mvn_v2 = 0; size_t lds_mvn = 0;     // mvn: wave-per-pivot half-step and wave-per-candidate lottery (ttx_mvn.h)
-    int fast_cap = 0;                       // TTX_ARITH=fast: rows of each decay table the lottery kernel keeps in LDS
-    bool want_fast = false;                 // fast arithmetic was asked for (ttx_config.arith / TTX_ARITH); P.arith says where it is effective
-    int fused = 0;                      // whole-sweep kernel (ttx_fused.h) usable for this problem
-    size_t lds_fused = 0;
     hipStream_t qstream = nullptr;      // forked per-sweep quadrature (single-process runs)
     hipEvent_t ev_sum[2] = {nullptr, nullptr}, ev_val[2] = {nullptr, nullptr};
     double *h_sum_base = nullptr;       // pinned [2][SB]: summaries of the two sweeps in flight
     double *h_val = nullptr;            // pinned [2]: per-sweep quadrature values
-    int cluster_zkeep = 0;              // cluster kernel keeps the sorted pivot lists of all own bonds in LDS
-    int cluster_ldsinv = 0;             // cluster kernel keeps the neighbour LU factors in LDS
-    int cluster = 0;                    // workgroups per bond group of the cluster sweep kernel (ttx_cluster.h); 0: not used
-    int cluster_var = 0;                // its instantiation (cluster_kernel): 0 exact, remainders predicated; 1 exact, rows padded to whole chunks; 2 closed form
-    bool unit_nodes = false;            // Ising: every node the integrand can read lies in [0,1]
-    size_t lds_cluster = 0;
     int *h_abort = nullptr;             // pinned, device-visible: the cluster kernel's barrier-timeout flag
-    int cluster_coop = 0;               // launch the cluster kernel with hipLaunchCooperativeKernel
-    int cluster_fallbacks = 0;          // runs replayed on the chain path after a cluster abort
-    bool cluster_aborted = false;
     // user integrand evaluated on the host (TTX_FUN_HOST): see DevProb::hostpass
     ttx_host_fun hfun = nullptr;
     const double *hfun_par = nullptr;   // the caller's par(*), passed through untouched
@@ -241,7 +227,6 @@ struct ttx_engine {
     bool tf_figures = false;            // the call in flight records the figures of ttx_trainfun_last (ttx_run, ttx_eval_device; not ttx_accchk)
     int64_t tf_launches = 0, tf_elements = 0;
     double tf_ms = 0.0;
-    size_t HS = 0;
     int64_t host_calls = 0;
     int64_t n_resid = 0;                // rook half-steps of the last run that took a residual (all groups)
     // operations on the resident train: work space (SC_*), the host images behind SC_TRAIN and SC_META, timers (TM_*), last figures
@@ -339,7 +324,7 @@ static int host_eval(ttx_engine *h)
     HIPCHECK(hipStreamSynchronize(h->stream));
     HIPCHECK(hipGetLastError());
     DevProb &P = h->P;
-    const size_t nslot = (size_t)h->G * h->HS;
+    const size_t nslot = (size_t)h->G * h->sel.HS;
     std::vector<uint32_t> todo;
     for (size_t s = 0; s < nslot; s++) if (P.hreq[s]) { todo.push_back((uint32_t)s); P.hreq[s] = 0; }
     const int32_t d = h->d;
@@ -381,7 +366,7 @@ static int devfun_slots(ttx_engine *h)
     DevFun &f = *h->dfun;
     DevProb &P = h->P;
     int d = P.d;
-    long long nslot = (long long)h->G * h->HS;
+    long long nslot = (long long)h->G * h->sel.HS;
     const int *n = P.n + 1;
     const double *par = f.par;
     const short *hidx = P.hidx; unsigned char *hreq = P.hreq; double *hval = P.hval;
@@ -416,7 +401,7 @@ static int tf_slots(ttx_engine *h)
 {
     const TrainFun &f = *h->tfun;
     DevProb &P = h->P;
-    long long nslot = (long long)h->G * h->HS;
+    long long nslot = (long long)h->G * h->sel.HS;
     const TfOps &O = h->tf_ops;
     const size_t lds = sizeof(double) * TTX_TF_WAVES * tf_lds_doubles(O.ldx, O.d);
     const dim3 grid(tf_grid(h, nslot)), block(64 * TTX_TF_WAVES);
@@ -451,7 +436,7 @@ static int slot_eval(ttx_engine *h)
     if (!P.slot_dev) return host_eval(h);
     if (h->cfg.fun_id == TTX_FUN_DEVICE) return devfun_slots(h);
     if (h->cfg.fun_id == TTX_FUN_TRAINS) return tf_slots(h);
-    const long long nslot = (long long)h->G * h->HS;
+    const long long nslot = (long long)h->G * h->sel.HS;
     const unsigned grid = (unsigned)std::min<long long>((nslot + TTX_CC_WAVES - 1) / TTX_CC_WAVES, 1024);
     hipLaunchKernelGGL(k_coscoeff_slots, dim3(grid), dim3(64 * TTX_CC_WAVES), sizeof(double) * TTX_CC_WAVES * TTX_CC_LDS(P.d), h->stream,
                        P.d, P.aux, nslot, (const short *)P.hidx, P.hreq, P.hval);
@@ -496,26 +481,220 @@ static int dev_alloc(ttx_engine *h, T **p, size_t count)
     return TTX_OK;
 }
 
-// lib/default.f90:78-97 share(): own(p) = first + int(dble(last-first+1)*dble(p)/nproc)
-static void share(int first, int last, int nproc, std::vector<int32_t> &own)
-{
-    own.assign(nproc + 1, 0);
-    own[0] = first;
-    for (int p = 1; p < nproc; p++) own[p] = first + (int)((double)(last - first + 1) * (double)p / nproc);
-    own[nproc] = last + 1;
-}
-
-static double powi(double a, int b)
-{
-    double r = 1.0;
-    for (;;) { if (b & 1) r *= a; b /= 2; if (b == 0) break; a *= a; }
-    return r;
-}
+// the restated figures of ttx_create_plan.h against the kernel headers'
+static_assert(TTX_PLAN_FB == FB && TTX_PLAN_FNR == TTX_FNR && TTX_PLAN_MVN_MAXQ == MVN_MAXQ, "ttx_create_plan.h restates FB, TTX_FNR, MVN_MAXQ");
 
 static int ensure_lds(const ttx_engine *h, const void *fn, size_t need) { return ensure_lds(h->cfg.device, fn, need); }
-static int ensure_lds_cluster(ttx_engine *h) { return ensure_lds(h, reinterpret_cast<const void *>(cluster_kernel(h->cluster_var)), h->lds_cluster); }
+static int ensure_lds_cluster(ttx_engine *h) { return ensure_lds(h, reinterpret_cast<const void *>(cluster_kernel(h->sel.cluster_var)), h->sel.lds_cluster); }
 
 static void destroy_keep_error(ttx_engine *e) { const std::string msg = g_err; ttx_destroy(e); g_err = msg; }
+
+// the environment switches of engine creation: the one place of the create path that calls getenv
+static CreateEnv create_env() { return create_env_from([](const char *name) -> const char * { return getenv(name); }); }
+
+// ---- what creation allocates, by purpose; every size comes from the plan (h->sel) ------------------------------------------------
+#define A_(call) do { if (int rc_ = (call)) return rc_; } while (0)
+template <class T>
+static int dev_upload(ttx_engine *h, T **p, const T *src, size_t count)
+{
+    A_(dev_alloc(h, p, count));
+    HIPCHECK(hipMemcpy(*p, src, sizeof(T) * count, hipMemcpyHostToDevice));
+    return TTX_OK;
+}
+// the problem as the caller gave it: mode sizes, par, aux, quadrature weights; DevProb's scalars, filled from the plan here
+static int create_problem(ttx_engine *h)
+{
+    const CreatePlan &s = h->sel;
+    const ttx_config &cfg = h->cfg;
+    DevProb &P = h->P;
+    const int d = s.d, NM = s.NM;
+    P.d = d; P.RM = s.RM; P.NM = NM; P.G = s.G; P.NC = s.NC; P.g0 = s.g0;
+    P.fun_id = cfg.fun_id; P.piv = cfg.pivoting; P.npar = cfg.npar; P.nprocs = s.nproc;
+    P.ising_id = s.ising_id;
+    P.has_quad = cfg.quadw != nullptr;
+    P.small_element = 10 * 2.220446049250313e-16; P.small_pivot = 1.e-5;   // lib/dmrgg.f90:70-71
+    P.mvn_norm = s.mvn_norm;
+    P.SS = s.SS; P.SW = s.SW; P.CS = s.CS;
+    P.arith = s.arith; P.FD = s.FD; P.fpersist = s.fpersist;
+    P.de_npair = s.de_npair; P.de_unit = s.de_unit; P.de_cut = s.de_cut;
+    P.nfb = s.nfb; P.fp_mfma = s.fp_mfma; P.fp_tiles = s.fp_tiles;
+    P.XD = s.XD; P.IOFF = s.IOFF; P.MSZ = s.MSZ;
+    P.accuracy = cfg.accuracy; P.maxrank = cfg.maxrank;
+    P.lot_nb = s.lot_nb; P.lot_max = s.nlotmax; P.bnd_wave = s.bnd_wave;
+    h->n1.assign(d + 2, 1);
+    for (int k = 1; k <= d; k++) h->n1[k] = cfg.n[k - 1];
+    if (cfg.npar > 0) h->par.assign(cfg.par, cfg.par + cfg.npar);
+    if (cfg.aux && cfg.naux > 0) h->aux.assign(cfg.aux, cfg.aux + cfg.naux);
+    int *dn; double *dpar, *daux = nullptr, *dq = nullptr;
+    A_(dev_upload(h, &dn, h->n1.data(), (size_t)d + 2));
+    A_(dev_alloc(h, &dpar, cfg.npar + 1));
+    if (cfg.npar > 0) HIPCHECK(hipMemcpy(dpar, h->par.data(), sizeof(double) * cfg.npar, hipMemcpyHostToDevice));
+    if (!h->aux.empty()) A_(dev_upload(h, &daux, h->aux.data(), h->aux.size()));
+    if (cfg.quadw) {
+        h->quadw.assign((size_t)(d + 1) * NM, 0.0);
+        size_t off = 0;
+        for (int k = 1; k <= d; k++) { for (int j = 0; j < h->n1[k]; j++) h->quadw[(size_t)k * NM + j] = cfg.quadw[off + j]; off += h->n1[k]; }
+        A_(dev_upload(h, &dq, h->quadw.data(), h->quadw.size()));
+    }
+    P.n = dn; P.par = dpar; P.aux = daux; P.quadw = dq;
+    return TTX_OK;
+}
+// tables of one integrand: fast arithmetic (ttx_fast.h), Ising D/E pair factors (ttx_de.h), mvn's transposed inverse covariance
+static int create_integrand_tables(ttx_engine *h)
+{
+    const CreatePlan &s = h->sel;
+    DevProb &P = h->P;
+    const int d = s.d;
+    const size_t G = s.G, NC = s.NC, RM = s.RM;
+    const bool mvn = h->cfg.fun_id == TTX_FUN_MVN;
+    if (s.fast_tables) {
+        const size_t slots = s.fpersist ? G * NC : G;
+        for (int sd = 0; sd < 2; sd++) {
+            A_(dev_alloc(h, &P.fNear[sd], slots * (size_t)s.FD * RM));
+            A_(dev_alloc(h, &P.fPiv[sd], slots * (size_t)TTX_FS * RM));
+            if (mvn) A_(dev_alloc(h, &P.fDv[sd], slots * (size_t)s.FD * RM));
+        }
+        if (mvn) {
+            std::vector<double> sy((size_t)d * d);
+            const double *ic = h->aux.data() + d;
+            for (int i = 0; i < d; i++) for (int j = 0; j < d; j++) sy[i + (size_t)d * j] = 0.5 * (ic[i + (size_t)d * j] + ic[j + (size_t)d * i]);
+            double *ds;
+            A_(dev_upload(h, &ds, sy.data(), sy.size()));
+            P.auxS = ds;
+        }
+    }
+    if (s.de_npair) {
+        A_(dev_alloc(h, &P.deTL, G * (size_t)s.de_npair * RM)); A_(dev_alloc(h, &P.deTR, G * (size_t)s.de_npair * RM));
+        A_(dev_alloc(h, &P.deUL, G * (size_t)(d + 1) * RM));
+        if (s.de_cut) { A_(dev_alloc(h, &P.deCL, G * (size_t)(d + 1) * RM)); A_(dev_alloc(h, &P.deCR, G * (size_t)(d + 1) * RM)); }
+    }
+    if (mvn) {
+        std::vector<double> t((size_t)d * d);
+        for (int i = 0; i < d; i++) for (int j = 0; j < d; j++) t[j + (size_t)d * i] = h->aux[d + i + (size_t)d * j];
+        double *dt;
+        A_(dev_upload(h, &dt, t.data(), t.size()));
+        P.auxT = dt;
+    }
+    return TTX_OK;
+}
+// cores, factors, index tables and per-group state; the searches' records; the lottery's CDF tables and work space
+static int create_cores(ttx_engine *h)
+{
+    const CreatePlan &s = h->sel;
+    DevProb &P = h->P;
+    const size_t d = s.d, G = s.G, NC = s.NC, RM = s.RM, NM = s.NM;
+    A_(dev_alloc(h, &P.arg, G * NC * P.CS)); A_(dev_alloc(h, &P.col, G * NC * P.CS)); A_(dev_alloc(h, &P.row, G * NC * P.CS));
+    A_(dev_alloc(h, &P.inv, G * NC * RM * RM)); A_(dev_alloc(h, &P.vip, G * NC * 4 * RM));
+    A_(dev_alloc(h, &P.L, G * NC * d * RM)); A_(dev_alloc(h, &P.R, G * NC * d * RM));
+    A_(dev_alloc(h, &P.r, G * (d + 2))); A_(dev_alloc(h, &P.rr, G * (d + 2))); A_(dev_alloc(h, &P.upd, G * (d + 2))); A_(dev_alloc(h, &P.tape, G * (d + 2) * 4));
+    A_(dev_alloc(h, &P.acol, G * RM * NM)); A_(dev_alloc(h, &P.arow, G * RM * NM));
+    A_(dev_alloc(h, &P.Tq, G * NC * RM * RM));
+    A_(dev_alloc(h, &P.ind0, d + 2)); A_(dev_alloc(h, &P.gs, G));
+    for (size_t g = 0; g < G; g++) {    // the bond range of every local group is fixed for the life of the engine (k_reset leaves it alone)
+        GroupState g0s{};
+        g0s.first = h->own[h->g0 + g]; g0s.last = h->own[h->g0 + g + 1] - 1; g0s.gglobal = h->g0 + (int)g;
+        const hipError_t e = hipMemcpy(P.gs + g, &g0s, offsetof(GroupState, S), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(TTX_EHIP, "ttx_create: %s", hipGetErrorString(e));
+    }
+    if (s.pfull) A_(dev_alloc(h, &P.pfull, G * NM * RM * (size_t)s.nfb));
+    if (s.fp_mfma) { A_(dev_alloc(h, &P.sb, G * (RM * NM) * (RM * NM))); A_(dev_alloc(h, &P.pfull2, G * (size_t)s.fp_tiles)); }
+    if (s.cdf_kmax >= 0) {
+        CdfTables t;
+        if (!cdf_tables(s.cdf_kmax, t)) return fail(TTX_EINVAL, "ttx_create: no CDF tables up to K = %d", s.cdf_kmax);     // cdf_table_fits says there are
+        ttx_cdfseg *dt; int *dn_;
+        A_(dev_upload(h, &dt, t.tab.data(), t.tab.size()));
+        A_(dev_upload(h, &dn_, t.ns.data(), t.ns.size()));
+        P.cdf_tab = dt; P.cdf_ns = dn_; P.cdf_kmax = s.cdf_kmax;
+    }
+    LotPart *lp; unsigned *lc;
+    A_(dev_alloc(h, &lp, G * s.lot_nb));
+    A_(dev_alloc(h, &lc, G));
+    P.lotp = lp; P.lot_ctr = lc;
+    if (s.lot_cand) { A_(dev_alloc(h, &P.lotc, G * s.nlotmax * 4)); A_(dev_alloc(h, &P.lotf, G * s.nlotmax)); }
+    if (s.cluster) {
+        unsigned *ctr; ClPart *cp;
+        A_(dev_alloc(h, &ctr, G));
+        A_(dev_alloc(h, &cp, 2 * G * TTX_CLREC));
+        P.cl_ctr = ctr; P.cl_part = cp;
+#ifdef TTX_STAMPS
+        if (s.dbg_waves) { long long *dbg; A_(dev_alloc(h, &dbg, (size_t)8 * 64 * 8)); P.dbg = dbg; }
+#endif
+        HIPCHECK(hipHostMalloc((void **)&h->h_abort, sizeof(int)));
+        *h->h_abort = 0;
+        P.cl_abort = h->h_abort;
+        P.cl_test_abort = s.cl_test_abort;
+    }
+    return TTX_OK;
+}
+// neighbour messages and their routing, the reductions of a sweep, the quadrature's gather
+static int create_exchange(ttx_engine *h)
+{
+    const CreatePlan &s = h->sel;
+    DevProb &P = h->P;
+    const size_t G = s.G, RM = s.RM, d = s.d;
+    const int nproc = s.nproc;
+    A_(dev_alloc(h, &P.msgR, G * P.MSZ)); A_(dev_alloc(h, &P.msgL, G * P.MSZ));
+    A_(dev_alloc(h, &h->recvL, P.MSZ)); A_(dev_alloc(h, &h->recvR, P.MSZ));
+    A_(dev_alloc(h, &P.inL, G)); A_(dev_alloc(h, &P.inR, G));
+    A_(dev_alloc(h, &P.red, G * 4)); A_(dev_alloc(h, &P.redsend, 4));
+    A_(dev_alloc(h, &P.qsend, h->QB)); A_(dev_alloc(h, &P.qwork, ((size_t)nproc + 2) * RM * RM)); A_(dev_alloc(h, &P.sumsend, h->SB));
+    P.qscr = nullptr;
+    if (s.qscr) A_(dev_alloc(h, &P.qscr, G * 2 * RM * RM));
+    if (s.W > 1) { A_(dev_alloc(h, &P.redrecv, 4)); A_(dev_alloc(h, &P.qall, h->QB)); A_(dev_alloc(h, &P.sumrecv, h->SB)); }
+    else { P.redrecv = P.redsend; P.qall = P.qsend; P.sumrecv = P.sumsend; }     // one GPU: results alias the inputs
+    {   // message routing: neighbour on this GPU -> its send buffer; on another GPU -> the receive buffer
+        std::vector<char *> il(G, nullptr), ir(G, nullptr);
+        for (size_t g = 0; g < G; g++) {
+            if (g > 0) il[g] = P.msgR + (g - 1) * P.MSZ; else if (h->g0 > 0) il[g] = h->recvL;
+            if (g + 1 < G) ir[g] = P.msgL + (g + 1) * P.MSZ; else if (h->g0 + (int)G < nproc) ir[g] = h->recvR;
+        }
+        HIPCHECK(hipMemcpy(P.inL, il.data(), sizeof(char *) * G, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(P.inR, ir.data(), sizeof(char *) * G, hipMemcpyHostToDevice));
+    }
+    int *ctl, *rq;
+    A_(dev_alloc(h, &ctl, (size_t)4));
+    A_(dev_alloc(h, &rq, G * (d + 2)));
+    P.ctl = ctl; P.rq = rq;
+    return TTX_OK;
+}
+// pinned staging of the per-sweep summaries and of the host transports, the quadrature's stream, the events of the pipelined sweep
+static int create_staging(ttx_engine *h)
+{
+    HIPCHECK(hipHostMalloc((void **)&h->h_sum_base, sizeof(double) * 2 * h->SB));
+    h->h_sum = h->h_sum_base;
+    memset(h->h_sum_base, 0, sizeof(double) * 2 * h->SB);
+    HIPCHECK(hipHostMalloc((void **)&h->h_val, sizeof(double) * 2));
+    HIPCHECK(hipStreamCreateWithFlags(&h->qstream, hipStreamNonBlocking));
+    for (int x = 0; x < 2; x++) { HIPCHECK(hipEventCreateWithFlags(&h->ev_sum[x], hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&h->ev_val[x], hipEventDisableTiming)); }
+    HIPCHECK(hipHostMalloc((void **)&h->h_msg, 4 * h->P.MSZ));
+    HIPCHECK(hipHostMalloc((void **)&h->h_tmp, sizeof(double) * std::max(h->QB, h->SB)));
+    if (h->W > 1) {
+        h->red_cap = std::max<size_t>(std::max(h->QB, h->SB), 8);
+        HIPCHECK(hipHostMalloc((void **)&h->red_mem, sizeof(double) * h->red_cap * ttx_engine::NRED));
+    }
+    return TTX_OK;
+}
+// slots of a two-pass integrand: pinned for the host's `fun`; device memory (zero-filled, owned by allocs) where the evaluator
+// runs on the stream between the two passes
+static int create_slots(ttx_engine *h)
+{
+    const CreatePlan &s = h->sel;
+    DevProb &P = h->P;
+    if (s.slots == SLOTS_NONE) return TTX_OK;
+    const size_t nslot = (size_t)s.G * s.HS, d = s.d;
+    if (s.slots == SLOTS_DEVICE) {
+        P.slot_dev = 1;
+        A_(dev_alloc(h, &P.hidx, nslot * d)); A_(dev_alloc(h, &P.hval, nslot)); A_(dev_alloc(h, &P.hreq, nslot));
+    } else {
+        HIPCHECK(hipHostMalloc((void **)&P.hidx, sizeof(short) * nslot * d));
+        HIPCHECK(hipHostMalloc((void **)&P.hval, sizeof(double) * nslot));
+        HIPCHECK(hipHostMalloc((void **)&P.hreq, nslot));
+        memset(P.hreq, 0, nslot); memset(P.hval, 0, sizeof(double) * nslot);
+    }
+    P.HS = (int)s.HS; P.hostpass = 0;
+    return TTX_OK;
+}
+#undef A_
 
 // nofun: an engine that only holds a tensor train (ttx_from_tt / ttx_read): no integrand, ttx_run refused
 static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
@@ -552,375 +731,42 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TTX_ENODEV, "ttx_create: no HIP device (the engine has no CPU path)");
     if (cfg->device < 0 || cfg->device >= ndev) return fail(TTX_ENODEV, "ttx_create: device %d not present", cfg->device);
     HIPCHECK(hipSetDevice(cfg->device));
+    DevCaps caps;
+    {
+        hipDeviceProp_t prop;
+        HIPCHECK(hipGetDeviceProperties(&prop, cfg->device));
+        int coop = 0;
+        HIPCHECK(hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, cfg->device));
+        caps.ncu = prop.multiProcessorCount; caps.coop = coop != 0;
+    }
+
+    // every decision, before anything is allocated: a refusal leaves nothing behind
+    ttx_config c = *cfg;
+    c.nproc = nproc;
+    CreatePlan plan = create_plan(c, nofun, create_env(), caps);
+    if (plan.err) return fail(plan.err, "%s", plan.errtext.c_str());
+    if (plan.cluster_cand) {
+        // residency: what the device can hold of THIS kernel with THIS much dynamic LDS
+        const void *fn = reinterpret_cast<const void *>(cluster_kernel(plan.cluster_var));
+        if (int rc = ensure_lds(cfg->device, fn, plan.lds_cluster)) return rc;
+        int occ = 0;
+        HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cluster_kernel(plan.cluster_var), CB, plan.lds_cluster));
+        create_admit(plan, occ);
+    } else create_admit(plan, 0);
 
     ttx_engine *h = new ttx_engine();
     // every early return below destroys the engine and what it holds so far; the error text is set before and survives
     struct Guard { ttx_engine *h; ~Guard() { if (h) destroy_keep_error(h); } } guard{h};
-#define A_(call) do { if (int rc_ = (call)) return rc_; } while (0)
-    h->cfg = *cfg;
-    h->cfg.nproc = nproc;
-    h->W = W; h->wrank = cfg->world_rank;
-    const int d = cfg->d;
-    h->d = d; h->RM = cfg->maxrank;
-    h->n1.assign(d + 2, 1);
-    int NM = 1;
-    for (int k = 1; k <= d; k++) { h->n1[k] = cfg->n[k - 1]; if (cfg->n[k - 1] < 1 || cfg->n[k - 1] > 32000) return fail(TTX_EINVAL, "bad mode size"); NM = std::max(NM, cfg->n[k - 1]); }
-    h->NM = NM;
-    if ((long long)h->RM * NM > (long long)TTX_MAXPART * TTX_BLK) return fail(TTX_EINVAL, "maxrank*n too large");
-    if (cfg->npar > 0) h->par.assign(cfg->par, cfg->par + cfg->npar);
-    if (cfg->aux && cfg->naux > 0) h->aux.assign(cfg->aux, cfg->aux + cfg->naux);
-    if (cfg->mybonds) h->own.assign(cfg->mybonds, cfg->mybonds + nproc + 1);
-    else share(1, d - 1, nproc, h->own);                               // lib/dmrgg.f90:126-130
-    for (int g = 0; g < nproc; g++) if (h->own[g + 1] <= h->own[g]) return fail(TTX_EINVAL, "mybonds: empty group %d", g);
-    // the groups must tile the bonds 1 .. d-1 (own(0) = 1, own(nproc) = d, lib/default.f90:78-97): anything else would address
-    // cores that do not exist or leave bonds without an owner
-    if (h->own[0] != 1 || h->own[nproc] != d) return fail(TTX_EINVAL, "mybonds: must run from 1 to d = %d (got %d .. %d)", d, h->own[0], h->own[nproc]);
-    // bond groups are dealt contiguously to the GPUs of the job
-    h->g0 = (int)((long long)nproc * h->wrank / W);
-    h->G = (int)((long long)nproc * (h->wrank + 1) / W) - h->g0;
-    h->nbmax = 0;
-    for (int g = 0; g < nproc; g++) h->nbmax = std::max(h->nbmax, h->own[g + 1] - h->own[g]);   // same launch shape on every GPU
-    h->NC = h->nbmax + 1;
-    h->mode = (cfg->pivoting == 0) ? 1 : (cfg->pivoting < 0) ? 2 : 0;
-    h->H = (cfg->pivoting <= 0) ? 2 : 2 * cfg->pivoting;
+    h->cfg = c;
+    h->sel = std::move(plan);
+    const CreatePlan &s = h->sel;
+    h->W = s.W; h->wrank = s.wrank; h->d = s.d; h->RM = s.RM; h->NM = s.NM; h->own = s.own;
+    h->g0 = s.g0; h->G = s.G; h->nbmax = s.nbmax; h->NC = s.NC; h->mode = s.mode; h->H = s.H;
+    h->QB = s.QB; h->SB = s.SB;
     HIPCHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-
-    DevProb &P = h->P;
-    P.d = d; P.RM = h->RM; P.NM = NM; P.G = h->G; P.NC = h->NC; P.g0 = h->g0;
-    P.fun_id = cfg->fun_id; P.piv = cfg->pivoting; P.npar = cfg->npar; P.nprocs = nproc;
-    P.ising_id = (cfg->fun_id == TTX_FUN_ISING) ? (int)cfg->par[2 * cfg->n[0]] : 0;
-    const bool isDE = cfg->fun_id == TTX_FUN_ISING && P.ising_id != 1;     // Ising D or E: the long dependent chains of ttx_de.h
-    P.has_quad = cfg->quadw != nullptr;
-    P.small_element = 10 * 2.220446049250313e-16; P.small_pivot = 1.e-5;   // lib/dmrgg.f90:70-71
-    P.mvn_norm = 1.0;
-    if (cfg->fun_id == TTX_FUN_MVN) {
-        if (cfg->naux < d + d * d + 1) return fail(TTX_EINVAL, "mvn: aux too short");
-        P.mvn_norm = std::sqrt(powi(2.0 * 3.141592653589793, d) * cfg->aux[d + (size_t)d * d]);   // lib/mvn_pdf.f90:82
-        if (!(P.mvn_norm > 0.0) || !std::isfinite(P.mvn_norm))
-            return fail(TTX_EINVAL, "ttx_create: mvn normalisation sqrt((2 pi)^d det) = %g is not a positive finite number (det = %g under- or overflows at d = %d)",
-                        P.mvn_norm, cfg->aux[d + (size_t)d * d], d);
-    }
-    P.SS = (size_t)h->RM * NM; P.SW = (size_t)NM * h->RM; P.CS = (size_t)h->RM * NM * h->RM;
-    const size_t G = h->G, NC = h->NC, RM = h->RM;
-    int *dn; double *dpar, *daux = nullptr, *dq = nullptr;
-    A_(dev_alloc(h, &dn, d + 2));
-    A_(dev_alloc(h, &dpar, cfg->npar + 1));
-    HIPCHECK(hipMemcpy(dn, h->n1.data(), sizeof(int) * (d + 2), hipMemcpyHostToDevice));
-    if (cfg->npar > 0) HIPCHECK(hipMemcpy(dpar, h->par.data(), sizeof(double) * cfg->npar, hipMemcpyHostToDevice));
-    if (!h->aux.empty()) { A_(dev_alloc(h, &daux, h->aux.size())); HIPCHECK(hipMemcpy(daux, h->aux.data(), sizeof(double) * h->aux.size(), hipMemcpyHostToDevice)); }
-    if (cfg->quadw) {
-        h->quadw.assign((size_t)(d + 1) * NM, 0.0);
-        size_t off = 0;
-        for (int k = 1; k <= d; k++) { for (int j = 0; j < h->n1[k]; j++) h->quadw[(size_t)k * NM + j] = cfg->quadw[off + j]; off += h->n1[k]; }
-        A_(dev_alloc(h, &dq, h->quadw.size()));
-        HIPCHECK(hipMemcpy(dq, h->quadw.data(), sizeof(double) * h->quadw.size(), hipMemcpyHostToDevice));
-    }
-    P.n = dn; P.par = dpar; P.aux = daux; P.quadw = dq;
-    {   // TTX_ARITH: exact (default) or fast; fast is effective where a re-associated evaluator exists (ttx_fast.h)
-        bool want = cfg->arith == TTX_ARITH_FAST;
-        if (cfg->arith != TTX_ARITH_EXACT && cfg->arith != TTX_ARITH_FAST) return fail(TTX_EINVAL, "ttx_create: arith must be TTX_ARITH_EXACT or TTX_ARITH_FAST (got %d)", cfg->arith);
-        if (const char *e = getenv("TTX_ARITH")) {
-            const std::string v = e;
-            if (v == "fast") want = true;
-            else if (v == "exact") want = (cfg->arith == TTX_ARITH_FAST);
-            else return fail(TTX_EINVAL, "TTX_ARITH must be exact or fast (got %s)", e);
-        }
-        h->want_fast = want && !nofun;
-        // Ising: all nodes in [0,1] (every running product stays in [0,1] and is non-increasing: the cut at 2^-54 is valid, fdiv_unit
-        // is exact).  The integrand reads node par[ind - 1] for ind up to the LARGEST mode size (lib: nodes + ind), whatever n(1) is
-        bool unit = cfg->fun_id == TTX_FUN_ISING;
-        for (int j = 0; unit && j < std::min(NM, (int)cfg->npar); j++) unit = cfg->par[j] >= 0.0 && cfg->par[j] <= 1.0;
-        h->unit_nodes = unit;
-        P.arith = (want && !nofun && ((isDE && unit) || cfg->fun_id == TTX_FUN_MVN)) ? 1 : 0;
-        if (P.arith) {
-            P.FD = d + 1;
-            // tables per bond, kept for the whole run and extended incrementally (ttx_fast.h); TTX_FAST_PERSIST=0: mvn rebuilds the
-            // tables of a bond step's two pivot sets with k_fast_tables instead (the first version, kept as a cross-check)
-            P.fpersist = 1;
-            if (cfg->fun_id == TTX_FUN_MVN && env_off("TTX_FAST_PERSIST")) P.fpersist = 0;
-            const size_t slots = P.fpersist ? G * NC : G;
-            for (int sd = 0; sd < 2; sd++) {
-                A_(dev_alloc(h, &P.fNear[sd], slots * (size_t)P.FD * RM));
-                A_(dev_alloc(h, &P.fPiv[sd], slots * (size_t)TTX_FS * RM));
-                if (cfg->fun_id == TTX_FUN_MVN) A_(dev_alloc(h, &P.fDv[sd], slots * (size_t)P.FD * RM));
-            }
-            if (cfg->fun_id == TTX_FUN_MVN) {
-                std::vector<double> sy((size_t)d * d);
-                const double *ic = h->aux.data() + d;
-                for (int i = 0; i < d; i++) for (int j = 0; j < d; j++) sy[i + (size_t)d * j] = 0.5 * (ic[i + (size_t)d * j] + ic[j + (size_t)d * i]);
-                double *ds;
-                A_(dev_alloc(h, &ds, sy.size()));
-                HIPCHECK(hipMemcpy(ds, sy.data(), sizeof(double) * sy.size(), hipMemcpyHostToDevice));
-                P.auxS = ds;
-            }
-        }
-    }
-    const bool de_lane = env_int("TTX_DE_LANE", 0) == 1;
-    // one fiber element per lane, every pair by division, rows ended at the unit cut (f_ising_de with `unit`): no tables, no teams
-    if (isDE && !P.arith && de_lane) P.de_unit = h->unit_nodes;
-    if (isDE && !P.arith && !de_lane && !env_off("TTX_DE_TABLES")) {
-        P.de_npair = d * (d + 1) / 2;
-        A_(dev_alloc(h, &P.deTL, G * (size_t)P.de_npair * RM)); A_(dev_alloc(h, &P.deTR, G * (size_t)P.de_npair * RM));
-        A_(dev_alloc(h, &P.deUL, G * (size_t)(d + 1) * RM));
-        P.de_unit = h->unit_nodes && !env_off("TTX_DE_FASTDIV");
-        // nodes in [0,1]: compact tables, every row of the pair triangle ends at the unit cut (k_de_ctables, k_halfstep_dec; same bits).
-        // TTX_DE_CUT=0: the full tables and the kernels of round 2 (wave teams, row-wise lottery)
-        P.de_cut = (P.de_unit && !env_off("TTX_DE_CUT")) ? 1 : 0;
-        if (P.de_cut) { A_(dev_alloc(h, &P.deCL, G * (size_t)(d + 1) * RM)); A_(dev_alloc(h, &P.deCR, G * (size_t)(d + 1) * RM)); }
-        h->de_lot_point = env_int("TTX_DE_LOT_POINT", d <= 160) != 0;
-        h->de_slots = (int)RM * ((NM + 63) / 64);
-        h->lds_de = sizeof(double) * (5 * (size_t)(((d + 7) & ~7) + 8) + 256) + (P.de_cut ? sizeof(int) * (size_t)(((d + 7) & ~7) + 8) : 0);
-        h->de_v2 = cfg->pivoting >= 0 && h->de_slots <= TTX_MAXPART && h->lds_de <= 150 * 1024 && !env_off("TTX_DE_V2");
-        h->lds_det = sizeof(double) * det_lds_doubles(d, 3);
-        h->lds_det6 = sizeof(double) * det_lds_doubles(d, 1);
-        h->de_team = h->de_v2 && !P.de_cut && h->lds_det <= 150 * 1024 && !env_off("TTX_DE_TEAM");
-        h->de_team_units = env_int("TTX_DE_TEAM_UNITS", h->de_team_units);
-        h->de_team6_units = env_int("TTX_DE_TEAM6_UNITS", h->de_team6_units);
-        h->de_test_fault = env_int("TTX_DE_TEST_FAULT", 0);
-        h->lds_de5 = sizeof(double) * de5_lds_doubles(d);
-        h->de_v5 = h->de_v2 && !P.de_cut && de5_fits(d) && h->lds_de5 <= 150 * 1024 && env_int("TTX_DE_V5", 0) == 1;
-    }
-    if (cfg->fun_id == TTX_FUN_MVN) {
-        std::vector<double> t((size_t)d * d);
-        for (int i = 0; i < d; i++) for (int j = 0; j < d; j++) t[j + (size_t)d * i] = h->aux[d + i + (size_t)d * j];
-        double *dt;
-        A_(dev_alloc(h, &dt, t.size()));
-        HIPCHECK(hipMemcpy(dt, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
-        P.auxT = dt;
-    }
-    A_(dev_alloc(h, &P.arg, G * NC * P.CS)); A_(dev_alloc(h, &P.col, G * NC * P.CS)); A_(dev_alloc(h, &P.row, G * NC * P.CS));
-    A_(dev_alloc(h, &P.inv, G * NC * RM * RM)); A_(dev_alloc(h, &P.vip, G * NC * 4 * RM));
-    A_(dev_alloc(h, &P.L, G * NC * d * RM)); A_(dev_alloc(h, &P.R, G * NC * d * RM));
-    A_(dev_alloc(h, &P.r, G * (d + 2))); A_(dev_alloc(h, &P.rr, G * (d + 2))); A_(dev_alloc(h, &P.upd, G * (d + 2))); A_(dev_alloc(h, &P.tape, G * (d + 2) * 4));
-    A_(dev_alloc(h, &P.acol, G * RM * NM)); A_(dev_alloc(h, &P.arow, G * RM * NM));
-    A_(dev_alloc(h, &P.Tq, G * NC * RM * RM));
-    A_(dev_alloc(h, &P.ind0, d + 2)); A_(dev_alloc(h, &P.gs, G));
-    {   // the bond range of every local group is fixed for the life of the engine (k_reset leaves it alone)
-        GroupState *g0s = (GroupState *)calloc(1, sizeof(GroupState));
-        for (size_t g = 0; g < G; g++) {
-            g0s->first = h->own[h->g0 + g]; g0s->last = h->own[h->g0 + g + 1] - 1; g0s->gglobal = h->g0 + (int)g;
-            hipError_t e = hipMemcpy(P.gs + g, g0s, offsetof(GroupState, S), hipMemcpyHostToDevice);
-            if (e != hipSuccess) { free(g0s); return fail(TTX_EHIP, "ttx_create: %s", hipGetErrorString(e)); }
-        }
-        free(g0s);
-    }
-    P.nfb = (int)((RM * NM + TTX_BLK - 1) / TTX_BLK);
-    if (cfg->pivoting < 0) A_(dev_alloc(h, &P.pfull, G * NM * RM * (size_t)P.nfb));
-    if (cfg->pivoting < 0 && getenv("TTX_FULLPIV") && std::string(getenv("TTX_FULLPIV")) == "mfma" && RM <= 64 &&
-        (long long)(RM * NM) * (long long)(RM * NM) < (1LL << 31)) {
-        // dense full pivoting: the whole superblock resident (8 (RM NM)^2 bytes per group: 21 MB at r=32, n=51; 334 MB at r=64, n=101)
-        const size_t side = RM * NM, tiles = ((side + 63) / 64) * ((side + 63) / 64);
-        A_(dev_alloc(h, &P.sb, G * side * side));
-        A_(dev_alloc(h, &P.pfull2, G * tiles));
-        P.fp_mfma = 1; P.fp_tiles = (int)tiles;
-    }
-    // exchange buffers
-    P.XD = RM * NM + RM * RM;
-    P.IOFF = (sizeof(int) * (XH + d + 2) + 15) & ~(size_t)15;
-    P.MSZ = (P.IOFF + sizeof(double) * P.XD + 15) & ~(size_t)15;
-    A_(dev_alloc(h, &P.msgR, G * P.MSZ)); A_(dev_alloc(h, &P.msgL, G * P.MSZ));
-    A_(dev_alloc(h, &h->recvL, P.MSZ)); A_(dev_alloc(h, &h->recvR, P.MSZ));
-    A_(dev_alloc(h, &P.inL, G)); A_(dev_alloc(h, &P.inR, G));
-    A_(dev_alloc(h, &P.red, G * 4)); A_(dev_alloc(h, &P.redsend, 4));
-    h->QB = (size_t)nproc * RM * RM + 2 * nproc;
-    h->SB = SUM_HDR + nproc + 5 * (size_t)(d + 1);
-    A_(dev_alloc(h, &P.qsend, h->QB)); A_(dev_alloc(h, &P.qwork, ((size_t)nproc + 2) * RM * RM)); A_(dev_alloc(h, &P.sumsend, h->SB));
-    P.qscr = nullptr;
-    if (2 * sizeof(double) * ((size_t)RM * RM + 2) > 150 * 1024) A_(dev_alloc(h, &P.qscr, (size_t)G * 2 * RM * RM));
-    if (W > 1) { A_(dev_alloc(h, &P.redrecv, 4)); A_(dev_alloc(h, &P.qall, h->QB)); A_(dev_alloc(h, &P.sumrecv, h->SB)); }
-    else { P.redrecv = P.redsend; P.qall = P.qsend; P.sumrecv = P.sumsend; }     // one GPU: results alias the inputs
-    {   // message routing: neighbour on this GPU -> its send buffer; on another GPU -> the receive buffer
-        std::vector<char *> il(G, nullptr), ir(G, nullptr);
-        for (size_t g = 0; g < G; g++) {
-            if (g > 0) il[g] = P.msgR + (g - 1) * P.MSZ; else if (h->g0 > 0) il[g] = h->recvL;
-            if (g + 1 < G) ir[g] = P.msgL + (g + 1) * P.MSZ; else if (h->g0 + (int)G < nproc) ir[g] = h->recvR;
-        }
-        HIPCHECK(hipMemcpy(P.inL, il.data(), sizeof(char *) * G, hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(P.inR, ir.data(), sizeof(char *) * G, hipMemcpyHostToDevice));
-    }
-    {
-        int *ctl, *rq;
-        A_(dev_alloc(h, &ctl, (size_t)4));
-        A_(dev_alloc(h, &rq, (size_t)G * (d + 2)));
-        P.ctl = ctl; P.rq = rq; P.accuracy = cfg->accuracy; P.maxrank = cfg->maxrank;
-    }
-    HIPCHECK(hipHostMalloc((void **)&h->h_sum_base, sizeof(double) * 2 * h->SB));
-    h->h_sum = h->h_sum_base;
-    memset(h->h_sum_base, 0, sizeof(double) * 2 * h->SB);
-    HIPCHECK(hipHostMalloc((void **)&h->h_val, sizeof(double) * 2));
-    HIPCHECK(hipStreamCreateWithFlags(&h->qstream, hipStreamNonBlocking));
-    for (int x = 0; x < 2; x++) { HIPCHECK(hipEventCreateWithFlags(&h->ev_sum[x], hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&h->ev_val[x], hipEventDisableTiming)); }
-    HIPCHECK(hipHostMalloc((void **)&h->h_msg, 4 * P.MSZ));
-    HIPCHECK(hipHostMalloc((void **)&h->h_tmp, sizeof(double) * std::max(h->QB, h->SB)));
-    if (W > 1) {
-        h->red_cap = std::max<size_t>(std::max(h->QB, h->SB), 8);
-        HIPCHECK(hipHostMalloc((void **)&h->red_mem, sizeof(double) * h->red_cap * ttx_engine::NRED));
-    }
-    {   // lottery CDF segment tables for every K that can occur (K <= maxrank*n): pure function of K, see ttx_cdf.h
-        const int kmax = h->RM * NM;
-        if (kmax <= 16384) {
-            std::vector<ttx_cdfseg> tab((size_t)(kmax + 1) * TTX_TABSEG);
-            std::vector<int> ns(kmax + 1, 0);
-            std::vector<ttx_cdfseg> tmp(TTX_MAXSEG);
-            bool ok = true;
-            for (int K = 1; K <= kmax && ok; K++) {
-                int n_ = ttx_cdf_build(K, tmp.data());
-                if (n_ > TTX_TABSEG) { ok = false; break; }
-                ns[K] = n_;
-                memcpy(&tab[(size_t)K * TTX_TABSEG], tmp.data(), sizeof(ttx_cdfseg) * n_);
-            }
-            if (ok) {
-                ttx_cdfseg *dt; int *dn_;
-                A_(dev_alloc(h, &dt, tab.size()));
-                A_(dev_alloc(h, &dn_, ns.size()));
-                HIPCHECK(hipMemcpy(dt, tab.data(), sizeof(ttx_cdfseg) * tab.size(), hipMemcpyHostToDevice));
-                HIPCHECK(hipMemcpy(dn_, ns.data(), sizeof(int) * ns.size(), hipMemcpyHostToDevice));
-                P.cdf_tab = dt; P.cdf_ns = dn_; P.cdf_kmax = kmax;
-            }
-        }
-    }
-    h->lds_par = sizeof(double) * (cfg->npar + 2);
-    {   // half-step LDS: index rows always fit the limit checked below; value rows (Ising C fast path) if <= 96 KB
-        const size_t VS = ((d + 7) & ~7) + 8;
-        const size_t base = sizeof(double) * (cfg->npar + RM + 4);
-        const size_t idx_bytes = sizeof(short) * ((RM + 1) * VS + 16), val_bytes = sizeof(double) * ((RM + 1) * 2 * VS + 4);
-        h->half_vals = (cfg->fun_id == TTX_FUN_ISING && P.ising_id == 1 && base + val_bytes <= 100 * 1024) ? 1 : 0;
-        h->lds_half = base + (h->half_vals ? val_bytes : idx_bytes);
-        const size_t dif_bytes = sizeof(double) * ((RM + 1) * VS + 4);          // mvn: rows of differences x - mu
-        if (cfg->fun_id == TTX_FUN_MVN && base + dif_bytes <= 140 * 1024) { h->half_vals = 1; h->lds_half = base + dif_bytes; }
-        if (P.arith) h->lds_half = std::max(h->lds_half, base + sizeof(double) * ((size_t)std::max(P.FD, TTX_FNR) + 4 + RM + 2));   // far[] + cross terms
-    }
-    {
-        const int nlotmax = 2 * h->RM + 2 * NM;
-        const size_t VS = ((d + 7) & ~7) + 8;
-        h->lds_lot = sizeof(double) * (cfg->npar + 4) + sizeof(int) * 4 * (nlotmax + 4) + sizeof(short) * (2 * RM * VS + 16);
-        const size_t lot_dif = sizeof(double) * (cfg->npar + 4) + sizeof(int) * 4 * (nlotmax + 4) + sizeof(double) * (2 * RM * VS + 4);
-        if (cfg->fun_id == TTX_FUN_MVN && lot_dif <= 120 * 1024) { h->lot_vals = 1; h->lds_lot = lot_dif; }
-        if (P.arith && cfg->fun_id == TTX_FUN_ISING) {
-            // fast mode: the leading rows of the two decay tables ([row][RM] doubles each) instead of the index rows
-            const size_t hdr = sizeof(double) * (cfg->npar + 4) + sizeof(int) * 4 * (nlotmax + 4) + 32;
-            const size_t rowb = 2 * sizeof(double) * RM;
-            h->fast_cap = (int)std::min<size_t>(std::min<size_t>(40, (size_t)d + 1), hdr < 100 * 1024 ? (100 * 1024 - hdr) / rowb : 0);
-            h->lds_lot = std::max(h->lds_lot, hdr + rowb * h->fast_cap);
-        }
-    }
-    {   // whole-sweep kernels (Ising C): TTX_SWEEP = auto | chain | fused | cluster
-        const size_t VS = ((d + 7) & ~7) + 8;
-        const int nlotmax = 2 * h->RM + 2 * NM;
-        const char *env = getenv("TTX_SWEEP");
-        const std::string want = env ? env : "auto";
-        const bool fastc = cfg->fun_id == TTX_FUN_ISING && P.ising_id == 1 && cfg->pivoting >= 0 && P.cdf_tab != nullptr;
-        // one 1024-thread workgroup per group: everything of a bond step in one CU's LDS
-        h->lds_fused = sizeof(double) * (cfg->npar + 4 + 4 * RM * VS + 2 * RM * NM + RM + 4) + sizeof(int) * 4 * (nlotmax + 4);
-        const bool fused_ok = fastc && h->RM <= 64 && nlotmax <= FB && h->lds_fused <= 150 * 1024;
-        // a cluster of NB 256-thread workgroups per group, all resident at once (G*NB <= number of CUs)
-        hipDeviceProp_t prop;
-        HIPCHECK(hipGetDeviceProperties(&prop, cfg->device));
-        int NB = std::max(1, std::min(env_int("TTX_CLUSTER_NB", 8), TTX_CLMAX));
-        while (NB > 1 && h->G * NB > prop.multiProcessorCount / 2) NB--;        // leave room for other processes on the card
-        const size_t SL = (size_t)RM * ((NM + NB - 1) / NB + 1);
-        h->lds_cluster = sizeof(double) * (cfg->npar + 4 + 2 * RM * (2 * VS + 2) + 4 * SL + 2 * RM + 8) + sizeof(int) * 4 * (nlotmax + 4);
-        if (h->lds_cluster + sizeof(double) * 2 * RM * RM <= 150 * 1024) { h->cluster_ldsinv = 1; h->lds_cluster += sizeof(double) * 2 * RM * RM; }
-        {
-            const size_t zk = sizeof(int) * ((size_t)h->nbmax * 2 * RM + 2 * h->nbmax + 4);
-            if (h->lds_cluster + zk <= 150 * 1024) { h->cluster_zkeep = 1; h->lds_cluster += zk; }
-        }
-        // instantiation of the cluster kernel: the closed form where fast arithmetic was asked for; else rows padded to whole chunks
-        // (f_ising_c4w) where the pad is neutral -- every node in [0,1], so that no running product overflows (inf * 0.0 is NaN) --
-        // unless TTX_CL_PAD=0 asks for the predicated remainders (f_ising_c4p), which hold for any node (ttx_cluster_eval tells)
-        const bool cfastc = h->want_fast && cfg->fun_id == TTX_FUN_ISING && P.ising_id == 1;
-        if (const char *e = getenv("TTX_CL_PAD")) if (strcmp(e, "0") && strcmp(e, "1")) return fail(TTX_EINVAL, "TTX_CL_PAD must be 0 or 1 (got %s)", e);
-        h->cluster_var = cfastc ? 2 : (h->unit_nodes && !env_off("TTX_CL_PAD")) ? 1 : 0;
-        bool cluster_ok = fastc && h->RM <= 64 && NB >= 2 && h->G * NB <= prop.multiProcessorCount && h->lds_cluster <= 150 * 1024;
-        if (cluster_ok) {
-            // residency: what the device can hold of THIS kernel with THIS much dynamic LDS; the grid may use half of it
-            A_(ensure_lds_cluster(h));
-            int occ = 0;
-            HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cluster_kernel(h->cluster_var), CB, h->lds_cluster));
-            const long long cap = (long long)occ * prop.multiProcessorCount;
-            const long long grid = 8LL * NB * ((h->G + 7) / 8);
-            if (grid * 2 > cap) cluster_ok = false;
-            int coop = 0;
-            HIPCHECK(hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, cfg->device));
-            // plain launch by default: with the occupancy gate above every workgroup is placed as soon as the launch starts;
-            // the cooperative launch (TTX_CLUSTER_COOP=1) adds the runtime's own refusal of oversized grids but costs
-            // ~30 us per launch on this stack (C_64: 5.28 -> 5.80 ms per run, measured)
-            h->cluster_coop = coop && env_int("TTX_CLUSTER_COOP", 0) == 1;
-        }
-        if (want == "cluster") { if (cluster_ok) h->cluster = NB; }
-        else if (want == "fused") { if (fused_ok) h->fused = 1; }
-        else if (want == "auto") { if (cluster_ok) h->cluster = NB; else if (fused_ok && h->G == 1) h->fused = 1; }
-        else if (want != "chain") return fail(TTX_EINVAL, "TTX_SWEEP must be auto, chain, fused or cluster (got %s)", want.c_str());
-        // TTX_ARITH=fast for Ising C: a closed form inside the cluster kernel (f_ising_cfast); the other paths evaluate C exactly
-        if (h->cluster && cfastc) P.arith = 1;
-        if (h->cluster) {
-            unsigned *ctr; ClPart *cp;
-            A_(dev_alloc(h, &ctr, (size_t)h->G));
-            A_(dev_alloc(h, &cp, (size_t)2 * h->G * TTX_CLREC));
-            P.cl_ctr = ctr; P.cl_part = cp;
-#ifdef TTX_STAMPS
-            if (getenv("TTX_DBG_WAVES")) { long long *dbg; A_(dev_alloc(h, &dbg, (size_t)8 * 64 * 8)); P.dbg = dbg; }
-#endif
-            HIPCHECK(hipHostMalloc((void **)&h->h_abort, sizeof(int)));
-            *h->h_abort = 0;
-            P.cl_abort = h->h_abort;
-            P.cl_test_abort = env_int("TTX_CLUSTER_TEST_ABORT", P.cl_test_abort);
-        }
-    }
-    if (h->lds_half > 160 * 1024 || h->lds_lot > 120 * 1024) return fail(TTX_EINVAL, "problem too large for LDS staging (d*maxrank)");
-    {   // lottery: one wave of candidates per workgroup where one evaluation is a long dependent chain (Ising D/E, mvn)
-        const bool heavy = isDE || cfg->fun_id == TTX_FUN_MVN;
-        const int nlotmax = 2 * h->RM + 2 * NM;
-        P.lot_nb = 1;
-        if (heavy && env_int("TTX_LOTTERY_NB", 0) != 1) P.lot_nb = std::min((nlotmax + 63) / 64, 64);
-        if (P.lot_nb > 1 && (nlotmax + P.lot_nb - 1) / P.lot_nb > 64) P.lot_nb = 1;      // more candidates than 64 blocks x 64: keep one block
-        LotPart *lp; unsigned *lc;
-        A_(dev_alloc(h, &lp, (size_t)h->G * P.lot_nb));
-        A_(dev_alloc(h, &lc, (size_t)h->G));
-        P.lotp = lp; P.lot_ctr = lc;
-        P.lot_max = nlotmax;
-        if (cfg->fun_id == TTX_FUN_MVN && d <= 64 * MVN_MAXQ && cfg->pivoting >= 0 && (int)RM * ((NM + 63) / 64) <= TTX_MAXPART && !env_off("TTX_MVN_V2")) {
-            int *lcd; double *lf;
-            A_(dev_alloc(h, &lcd, (size_t)h->G * nlotmax * 4));
-            A_(dev_alloc(h, &lf, (size_t)h->G * nlotmax));
-            P.lotc = lcd; P.lotf = lf;
-            h->mvn_v2 = 1; h->de_slots = (int)RM * ((NM + 63) / 64);
-            P.bnd_wave = 1;
-            h->lds_mvn = sizeof(double) * (3 * (size_t)d + 8);
-        }
-        if (isDE && P.arith) P.bnd_wave = 1;     // boundary corners by de_fast_point_wave
-        if (isDE && P.deTL) {
-            int *lcd; double *lf;
-            A_(dev_alloc(h, &lcd, (size_t)h->G * nlotmax * 4));
-            A_(dev_alloc(h, &lf, (size_t)h->G * nlotmax));
-            P.lotc = lcd; P.lotf = lf;
-            // candidates and boundary corners by the row-wise wave evaluator (ttx_de.h); TTX_LOTTERY_WAVE=0: one lane per element
-            h->lds_der = sizeof(double) * de_rows_lds_doubles(d);
-            h->lot_wave = h->de_v2 && !P.de_cut && h->lds_der <= 150 * 1024 && !env_off("TTX_LOTTERY_WAVE");
-            P.bnd_wave = h->lot_wave || (P.de_cut && h->de_v2 && h->lds_der <= 150 * 1024);    // boundary corners by one wave per corner
-            h->lot_rows = h->lot_wave ? (env_int("TTX_LOTTERY_ROWS", 0) == 2 ? 2 : 1) : 0;
-        }
-    }
-    if (cfg->fun_id == TTX_FUN_HOST || cfg->fun_id == TTX_FUN_COSCOEFF || cfg->fun_id == TTX_FUN_DEVICE || cfg->fun_id == TTX_FUN_TRAINS) {
-        // slots of one group: the largest point set any evaluating kernel asks for in one launch
-        int nn = h->n1[1];
-        for (int k = 2; k <= d; k++) nn = std::min(nn, h->n1[k]);
-        const size_t snum = (size_t)std::max(8, nproc);
-        h->HS = std::max<size_t>({(size_t)h->RM * NM, (size_t)nn * snum, (size_t)h->NC * NM, (size_t)2 * h->RM + 2 * NM, (size_t)2 * NM, (size_t)256});
-        const size_t nslot = (size_t)h->G * h->HS;
-        if (cfg->fun_id == TTX_FUN_COSCOEFF || cfg->fun_id == TTX_FUN_DEVICE || cfg->fun_id == TTX_FUN_TRAINS) {
-            // device slots (zero-filled, owned by allocs): the evaluator runs on the stream between the two passes
-            P.slot_dev = 1;
-            A_(dev_alloc(h, &P.hidx, nslot * d)); A_(dev_alloc(h, &P.hval, nslot)); A_(dev_alloc(h, &P.hreq, nslot));
-        } else {
-        HIPCHECK(hipHostMalloc((void **)&P.hidx, sizeof(short) * nslot * d));
-        HIPCHECK(hipHostMalloc((void **)&P.hval, sizeof(double) * nslot));
-        HIPCHECK(hipHostMalloc((void **)&P.hreq, nslot));
-        memset(P.hreq, 0, nslot); memset(P.hval, 0, sizeof(double) * nslot);
-        }
-        P.HS = (int)h->HS; P.hostpass = 0;
-    }
-#undef A_
+    int rc;
+    if ((rc = create_problem(h)) || (rc = create_integrand_tables(h)) || (rc = create_cores(h)) || (rc = create_exchange(h)) ||
+        (rc = create_staging(h)) || (rc = create_slots(h))) return rc;
     guard.h = nullptr;
     *out = h;
     return TTX_OK;
@@ -1622,60 +1468,60 @@ template <int FUN>
 static ChainPlan chain_plan(const ttx_engine *h)
 {
     const DevProb &P = h->P;
+    const CreatePlan &s = h->sel;
     const int d = h->d, G = h->G, RM = h->RM, NM = h->NM, nproc = h->cfg.nproc;
-    const bool isDE = FUN == FUN_ISING && P.ising_id != 1;
-    const bool fastk = P.arith && (FUN == FUN_MVN || isDE);         // TTX_ARITH=fast with a re-associated evaluator (ttx_fast.h)
-    const size_t VS = ((d + 7) & ~7) + 8;
+    const bool fastk = P.arith && (FUN == FUN_MVN || s.isDE);       // TTX_ARITH=fast with a re-associated evaluator (ttx_fast.h)
+    const size_t VS = s.VS;
     ChainPlan p;
-    p.nfb = (RM * NM + TTX_BLK - 1) / TTX_BLK;
-    p.base = kl(k_halfstep<FUN>, KFUN_(k_halfstep), dim3(p.nfb, G), dim3(TTX_BLK), h->lds_half, true);
-    p.base_vals = fastk ? 0 : h->half_vals;
-    p.lottery = kl(k_lottery<FUN>, "k_lottery", dim3(P.lot_nb, G), dim3(P.lot_nb == 1 ? 512 : 256), h->lds_lot, true);
-    p.lot_vals = fastk ? h->fast_cap : h->lot_vals;
+    p.nfb = s.nfb;
+    p.base = kl(k_halfstep<FUN>, KFUN_(k_halfstep), dim3(p.nfb, G), dim3(TTX_BLK), s.lds_half, true);
+    p.base_vals = fastk ? 0 : s.half_vals;
+    p.lottery = kl(k_lottery<FUN>, "k_lottery", dim3(P.lot_nb, G), dim3(P.lot_nb == 1 ? 512 : 256), s.lds_lot, true);
+    p.lot_vals = fastk ? s.fast_cap : s.lot_vals;
     // the Ising D/E kernels of ttx_de.h, by the division they use (de_unit: the short sequence for nodes in [0,1])
-    const dim3 slots(h->de_slots, G), cand(P.lot_max, G), cand4((P.lot_max + 3) / 4, G);
-    const KLaunch de = KUNIT_(k_halfstep_de, slots, dim3(64), h->lds_de, true);
-    const KLaunch det3 = KUNIT2_(k_halfstep_det, 3, dim3(1, G), dim3(64 * 14), h->lds_det, true);
-    const KLaunch det1 = KUNIT2_(k_halfstep_det, 1, dim3(1, G), dim3(64 * 6), h->lds_det6, true);
-    const KLaunch de5 = KUNIT_(k_halfstep_de5, slots, dim3(64 * DE5_W), h->lds_de5, true);
-    const KLaunch rows = KUNIT2_(k_lottery_eval_de_rows, false, cand4, dim3(64), h->lds_der, true);
-    const KLaunch rows_tab = KUNIT2_(k_lottery_eval_de_rows, true, cand4, dim3(64), h->lds_der, true);
+    const dim3 slots(s.de_slots, G), cand(P.lot_max, G), cand4((P.lot_max + 3) / 4, G);
+    const KLaunch de = KUNIT_(k_halfstep_de, slots, dim3(64), s.lds_de, true);
+    const KLaunch det3 = KUNIT2_(k_halfstep_det, 3, dim3(1, G), dim3(64 * 14), s.lds_det, true);
+    const KLaunch det1 = KUNIT2_(k_halfstep_det, 1, dim3(1, G), dim3(64 * 6), s.lds_det6, true);
+    const KLaunch de5 = KUNIT_(k_halfstep_de5, slots, dim3(64 * DE5_W), s.lds_de5, true);
+    const KLaunch rows = KUNIT2_(k_lottery_eval_de_rows, false, cand4, dim3(64), s.lds_der, true);
+    const KLaunch rows_tab = KUNIT2_(k_lottery_eval_de_rows, true, cand4, dim3(64), s.lds_der, true);
     // lottery candidates by one wave each between the drawing and the scoring launch: mvn; D/E with compact tables, row-parallel
     // without tables up to d = 160 (measured: 23 % less lottery time at D_64, even at D_256), from the tables beyond
     // (TTX_DE_LOT_POINT=0/1 forces one); D/E with full tables four candidates per wave (TTX_LOTTERY_ROWS=2: with the pivots' factor
     // tables, measured slower: HBM latency)
     if (fastk) p.lot_eval = KLaunch();
-    else if (FUN == FUN_MVN && h->mvn_v2) p.lot_eval = kl(k_lottery_eval_mvn, "k_lottery_eval_mvn", cand, dim3(64), h->lds_mvn);
-    else if (FUN == FUN_ISING && P.de_cut && h->de_v2 && P.lotc)
-        p.lot_eval = h->de_lot_point ? kl(k_lottery_eval_decp, "k_lottery_eval_decp", cand, dim3(64), sizeof(double) * (2 * (size_t)(d + 64) + 2048), true)
-                                     : kl(k_lottery_eval_dec, "k_lottery_eval_dec", cand, dim3(64), h->lds_de, true);
-    else if (FUN == FUN_ISING && h->lot_wave) p.lot_eval = h->lot_rows == 2 ? rows_tab : rows;
+    else if (FUN == FUN_MVN && s.mvn_v2) p.lot_eval = kl(k_lottery_eval_mvn, "k_lottery_eval_mvn", cand, dim3(64), s.lds_mvn);
+    else if (FUN == FUN_ISING && P.de_cut && s.de_v2 && s.lot_cand)
+        p.lot_eval = s.de_lot_point ? kl(k_lottery_eval_decp, "k_lottery_eval_decp", cand, dim3(64), sizeof(double) * (2 * (size_t)(d + 64) + 2048), true)
+                                    : kl(k_lottery_eval_dec, "k_lottery_eval_dec", cand, dim3(64), s.lds_de, true);
+    else if (FUN == FUN_ISING && s.lot_wave) p.lot_eval = s.lot_rows == 2 ? rows_tab : rows;
     if (p.lot_eval) { p.lottery.grid = dim3(1, G); p.lottery.block = dim3(512); }
     // half-step.  D/E with full tables: while the ranks are small (at most it + 1 during sweep it) a unit gets a team of 14 waves on
     // a CU of its own, up to de_team6_units a team of 6 waves (three such teams fit a CU), beyond that one wave -- or a relay of four
     if (fastk) { p.half[p.ntier++].k = p.base; p.half_vals = 0; }
-    else if (FUN == FUN_MVN && h->mvn_v2) p.half[p.ntier++].k = kl(k_halfstep_mvn, "k_halfstep_mvn", slots, dim3(64), h->lds_mvn);
-    else if (FUN == FUN_ISING && h->de_v2) {
-        if (h->de_team && !h->de_v5) { p.half[p.ntier++] = {det3, h->de_team_units}; p.half[p.ntier++] = {det1, h->de_team6_units}; }
-        p.half[p.ntier++].k = h->de_v5 ? de5 : P.de_cut ? kl(k_halfstep_dec, "k_halfstep_dec", slots, dim3(64), h->lds_de, true) : de;
-    } else { p.half[p.ntier++].k = p.base; p.half_vals = h->half_vals; }
+    else if (FUN == FUN_MVN && s.mvn_v2) p.half[p.ntier++].k = kl(k_halfstep_mvn, "k_halfstep_mvn", slots, dim3(64), s.lds_mvn);
+    else if (FUN == FUN_ISING && s.de_v2) {
+        if (h->de_team() && !h->de_v5()) { p.half[p.ntier++] = {det3, s.de_team_units}; p.half[p.ntier++] = {det1, s.de_team6_units}; }
+        p.half[p.ntier++].k = h->de_v5() ? de5 : P.de_cut ? kl(k_halfstep_dec, "k_halfstep_dec", slots, dim3(64), s.lds_de, true) : de;
+    } else { p.half[p.ntier++].k = p.base; p.half_vals = s.half_vals; }
     p.fullpiv = FUN == FUN_HOST ? ChainPlan::FP_COLUMNS : P.fp_mfma ? ChainPlan::FP_MFMA : ChainPlan::FP_PLAIN;
     // roles A/B of k_accept: x[RM]; C/D: the staged LU
     p.accept = kl(k_accept, "k_accept", dim3(2 * p.nfb + 2 * NM + 1, G), dim3(TTX_BLK), sizeof(double) * std::max<size_t>(RM + 2, (size_t)std::min<int>(RM, 64) * std::min<int>(RM, 64)));
     {   // initial samples: index rows in LDS where they fit
-        const size_t lds_s = h->lds_par + 16 + sizeof(short) * 256 * VS;
-        p.srows = lds_s <= 150 * 1024 ? 1 : 0;
-        p.init_samples = kl(k_init_samples<FUN>, KFUN_(k_init_samples), dim3(G), dim3(256), p.srows ? lds_s : h->lds_par, p.srows != 0);
-        p.init_fibers = kl(k_init_fibers<FUN>, KFUN_(k_init_fibers), dim3(h->NC, G), dim3(256), h->lds_par);
+        const size_t lds_s = s.lds_par + 16 + sizeof(short) * 256 * VS;
+        p.srows = lds_s <= TTX_LDS_WORK ? 1 : 0;
+        p.init_samples = kl(k_init_samples<FUN>, KFUN_(k_init_samples), dim3(G), dim3(256), p.srows ? lds_s : s.lds_par, p.srows != 0);
+        p.init_fibers = kl(k_init_fibers<FUN>, KFUN_(k_init_fibers), dim3(h->NC, G), dim3(256), s.lds_par);
     }
     // before a bond step's lottery.  Ising D/E: pair factors of the bond that do not span it (shared by all elements through a pivot),
     // compact where the nodes allow the unit cut; TTX_ARITH=fast, mvn with TTX_FAST_PERSIST=0: the per-pivot tables of the bond step
     // (Ising D/E keeps its fast tables per bond)
-    if (P.deTL) p.tables = P.de_cut ? kl(k_de_ctables, "k_de_ctables", dim3(2 * RM, G), dim3(256), sizeof(double) * (size_t)(d + 2))
+    if (s.de_npair) p.tables = P.de_cut ? kl(k_de_ctables, "k_de_ctables", dim3(2 * RM, G), dim3(256), sizeof(double) * (size_t)(d + 2))
                                     : kl(k_de_tables, "k_de_tables", dim3((2 * (d + 1) * RM + 255) / 256, G), dim3(256), 0);
     else if (fastk && !P.fpersist) p.tables = kl(k_fast_tables<FUN>, KFUN_(k_fast_tables), dim3(2 * RM, G), dim3(64), sizeof(double) * 2 * (d + 8));
     if (nproc > 1) {    // boundary corners; D/E: two value rows; mvn: 3 d + 1 doubles
-        const size_t lds_b = h->lds_par + 16 + sizeof(short) * 2 * VS + sizeof(double) * (64 * 64 + 4) +
+        const size_t lds_b = s.lds_par + 16 + sizeof(short) * 2 * VS + sizeof(double) * (64 * 64 + 4) +
                              (P.bnd_wave ? sizeof(double) * (std::max<size_t>(2 * (size_t)de_rows_stride(d), 3 * (size_t)d + 2) + 8 + (P.de_cut ? 64 * 32 : 0)) : 0);
         p.exch_boundary = kl(k_exch_boundary<FUN>, KFUN_(k_exch_boundary), dim3(2 * NM, G), dim3(TTX_BLK), lds_b, true);
     }
@@ -1683,9 +1529,9 @@ static ChainPlan chain_plan(const ttx_engine *h)
         // of a core are spread over grid.z (at maxrank 64 the 256-thread staging did not fit: the kernels then ran out of L2 with one
         // workgroup per core, 6 ms at D_256)
         int ft = 256;
-        while (ft > 64 && sizeof(double) * ((size_t)RM * RM + (size_t)ft * RM) > 96 * 1024) ft >>= 1;
+        while (ft > 64 && sizeof(double) * ((size_t)RM * RM + (size_t)ft * RM) > TTX_LDS_FIN) ft >>= 1;
         const size_t lds_f = sizeof(double) * ((size_t)RM * RM + (size_t)ft * RM);
-        p.fl = lds_f <= 150 * 1024 ? 1 : 0;
+        p.fl = lds_f <= TTX_LDS_WORK ? 1 : 0;
         const dim3 gr(h->NC, G, std::max(1, std::min(64, (NM * RM + ft - 1) / ft)));
         p.fin_luar = kl(k_fin_luar, "k_fin_luar", gr, dim3(ft), p.fl ? lds_f : 0, p.fl != 0);
         p.fin_lual = kl(k_fin_lual, "k_fin_lual", gr, dim3(ft), p.fl ? lds_f : 0, p.fl != 0);
@@ -1700,13 +1546,14 @@ static ChainPlan chain_plan(const ttx_engine *h)
 static int launch_cluster(ttx_engine *h, int dir, int epoch)
 {
     DevProb P = h->P;
-    int nsteps = h->nbmax, NB = h->cluster, ldsinv = h->cluster_ldsinv, zkeep = h->cluster_zkeep;
-    const dim3 grid(8 * h->cluster * ((h->G + 7) / 8)), block(CB);
-    if (h->cluster_coop) {
+    const CreatePlan &s = h->sel;
+    int nsteps = h->nbmax, NB = s.cluster, ldsinv = s.cluster_ldsinv, zkeep = s.cluster_zkeep;
+    const dim3 grid(8 * NB * ((h->G + 7) / 8)), block(CB);
+    if (s.cluster_coop) {
         void *args[] = {&P, &dir, &nsteps, &NB, &ldsinv, &epoch, &zkeep};
-        HIPCHECK(hipLaunchCooperativeKernel(reinterpret_cast<const void *>(cluster_kernel(h->cluster_var)), grid, block, args, (unsigned)h->lds_cluster, h->stream));
+        HIPCHECK(hipLaunchCooperativeKernel(reinterpret_cast<const void *>(cluster_kernel(s.cluster_var)), grid, block, args, (unsigned)s.lds_cluster, h->stream));
     } else
-        hipLaunchKernelGGL(cluster_kernel(h->cluster_var), grid, block, h->lds_cluster, h->stream, P, dir, nsteps, NB, ldsinv, epoch, zkeep);
+        hipLaunchKernelGGL(cluster_kernel(s.cluster_var), grid, block, s.lds_cluster, h->stream, P, dir, nsteps, NB, ldsinv, epoch, zkeep);
     return TTX_OK;
 }
 
@@ -1718,6 +1565,8 @@ static int run_impl(ttx_engine *h)
     auto since = [&]() { return std::chrono::duration<double>(clk::now() - t0).count(); };
     DevProb &P = h->P;
     const int d = h->d, G = h->G, nproc = h->cfg.nproc;
+    const int cluster = h->cluster_nb(), fused = h->sel.fused;      // the whole-sweep kernel this run uses, if any
+    const size_t lds_fused = h->sel.lds_fused;
     hipStream_t st = h->stream;
     h->recs.clear(); h->tapes.clear();
     int rc;
@@ -1726,9 +1575,9 @@ static int run_impl(ttx_engine *h)
     // default 64 KB of dynamic LDS (160 KB per CU on gfx950)
     const ChainPlan plan = chain_plan<FUN>(h);
     for (const KLaunch *k : plan.all()) if (k->raise && (rc = ensure_lds(h, k->fn, k->lds))) return rc;
-    if (h->fused && (rc = ensure_lds(h, reinterpret_cast<const void *>(k_sweep_fused), h->lds_fused))) return rc;
-    if (h->cluster && (rc = ensure_lds_cluster(h))) return rc;
-    if (h->cluster) *h->h_abort = 0;
+    if (fused && (rc = ensure_lds(h, reinterpret_cast<const void *>(k_sweep_fused), lds_fused))) return rc;
+    if (cluster && (rc = ensure_lds_cluster(h))) return rc;
+    if (cluster) *h->h_abort = 0;
     // an evaluating kernel: once with the device integrand; with a host integrand twice around the host's calls
     auto EV = [&](const KLaunch &k, auto... a) -> int {
         if (FUN != FUN_HOST) { launch(st, k, P, a...); return TTX_OK; }
@@ -1741,9 +1590,7 @@ static int run_impl(ttx_engine *h)
     // ---- reset state (lib/dmrgg.f90:96-100, 141-148, 279-288) ----
     hipLaunchKernelGGL(k_reset, dim3(64), dim3(256), 0, st, P, h->SB, h->QB);
     // ---- initial cross (:151-301) ----
-    const int smin = 8, snum = std::max(smin, nproc);
-    int nn = h->n1[1];
-    for (int k = 2; k <= d; k++) nn = std::min(nn, h->n1[k]);
+    const int snum = h->sel.snum, nn = h->sel.nn;
     {
         KScope ks(h, TTX_K_OTHER, 4);
         if ((rc = EV(plan.init_samples, snum, nn, FUN == FUN_HOST ? 0 : plan.srows, 0))) return rc;
@@ -1753,7 +1600,7 @@ static int run_impl(ttx_engine *h)
     }
     // Single-process whole-sweep path: the first sweep kernel is enqueued right behind the initial cross, and the host
     // waits only for the copy of the initial summary (an event), not for the stream.
-    const bool pipe0 = (h->cluster || h->fused) && h->W == 1 && !h->profile;
+    const bool pipe0 = (cluster || fused) && h->W == 1 && !h->profile;
     bool head1 = false;
     if (pipe0) {
         hipLaunchKernelGGL(k_collect, dim3(1), dim3(256), 0, st, P);
@@ -1761,8 +1608,8 @@ static int run_impl(ttx_engine *h)
         HIPCHECK(hipMemcpyAsync(h->h_sum, P.sumrecv, sizeof(double) * h->SB, hipMemcpyDeviceToHost, st));
         HIPCHECK(hipEventRecord(h->ev_sum[0], st));
         if (1 < h->cfg.maxrank) {
-            if (h->cluster) { if ((rc = launch_cluster(h, 1, 1))) return rc; }
-            else hipLaunchKernelGGL(k_sweep_fused, dim3(G), dim3(FB), h->lds_fused, st, P, 1, h->nbmax);
+            if (cluster) { if ((rc = launch_cluster(h, 1, 1))) return rc; }
+            else hipLaunchKernelGGL(k_sweep_fused, dim3(G), dim3(FB), lds_fused, st, P, 1, h->nbmax);
             h->k_launches[TTX_K_HALFSTEP] += 1;
             head1 = true;
         }
@@ -1791,7 +1638,7 @@ static int run_impl(ttx_engine *h)
     // With several processes the exchange and the summary travel by stream-ordered collectives (RCCL, or the host transport's
     // host functions), so the same loop applies; only the fork of the quadrature is single-process (one communicator must
     // not be driven from two streams at once).
-    const bool pipe = (h->cluster || h->fused) && !h->profile && !env_off("TTX_PIPELINE");
+    const bool pipe = (cluster || fused) && !h->profile && !env_off("TTX_PIPELINE");
     const bool forkq = pipe && P.has_quad && h->W == 1;
     DevProb Pq = P;
     if (pipe) Pq.r = P.rq;
@@ -1800,19 +1647,19 @@ static int run_impl(ttx_engine *h)
     auto enqueue_sweep = [&](int it_, int part) -> int {
         const int dir = 2 - it_ % 2, slot = it_ & 1;
         if (part & 1) {
-        if (h->cluster) {
+        if (cluster) {
             KScope ks(h, TTX_K_HALFSTEP, 1);
             if (int rc_ = launch_cluster(h, dir, it_)) return rc_;
-        } else if (h->fused) {
+        } else if (fused) {
             KScope ks(h, TTX_K_HALFSTEP, 1);
-            hipLaunchKernelGGL(k_sweep_fused, dim3(G), dim3(FB), h->lds_fused, st, P, dir, h->nbmax);
+            hipLaunchKernelGGL(k_sweep_fused, dim3(G), dim3(FB), lds_fused, st, P, dir, h->nbmax);
         }
         // the ranks are at most it_ + 1 in sweep it_: the units of a team half-step, and the columns of full pivoting by host passes
         const int rb = std::min((int)h->RM, it_ + 1);
-        const int units = (h->de_test_fault && it_ == h->de_test_fault) ? 1 : rb * ((h->NM + 63) / 64);
+        const int units = (h->sel.de_test_fault && it_ == h->sel.de_test_fault) ? 1 : rb * ((h->NM + 63) / 64);
         KLaunch half = plan.half[plan.ntier - 1].k;
         for (int t = plan.ntier - 2; t >= 0; t--) if (units * G <= plan.half[t].upto) { half = plan.half[t].k; half.grid.x = units; }
-        for (int pp = 1; pp <= h->nbmax && !h->fused && !h->cluster; pp++) {
+        for (int pp = 1; pp <= h->nbmax && !fused && !cluster; pp++) {
             if (plan.tables) { KScope ks(h, TTX_K_OTHER); launch(st, plan.tables, P, dir, pp); }
             if (h->cfg.pivoting >= 0) {
                 if (plan.lot_eval) {
@@ -1867,7 +1714,7 @@ static int run_impl(ttx_engine *h)
         if (forkq) HIPCHECK(hipStreamWaitEvent(st, h->ev_val[slot ^ 1], 0));   // the previous quadrature is done with the boundaries
         {   // per-sweep exchange between bond groups (:763-961)
             KScope ks(h, TTX_K_EXCHANGE, (h->W > 1 ? 4 : 2) + (nproc > 1 ? 1 : 0));
-            if (!h->cluster) hipLaunchKernelGGL(k_exch_pack, dim3(G), dim3(256), 0, st, P);     // the cluster kernel packs at its end
+            if (!cluster) hipLaunchKernelGGL(k_exch_pack, dim3(G), dim3(256), 0, st, P);     // the cluster kernel packs at its end
             if (h->W > 1) {
                 hipLaunchKernelGGL(k_exch_localmax, dim3(1), dim3(64), 0, st, P);
                 if (int rc_ = xfer_neighbours(h)) return rc_;
@@ -1932,7 +1779,7 @@ static int run_impl(ttx_engine *h)
             if (P.has_quad) val = h->h_sum[SUM_VAL];      // every GPU ran the same tree on the same gathered matrices
         }
         HIPCHECK(hipGetLastError());
-        if (h->cluster && *(volatile int *)h->h_abort) { h->cluster_aborted = true; return fail(TTX_EHIP, "cluster sweep kernel: barrier timed out (workgroups of a bond group were not co-resident)"); }
+        if (cluster && *(volatile int *)h->h_abort) { h->cluster_aborted = true; return fail(TTX_EHIP, "cluster sweep kernel: barrier timed out (workgroups of a bond group were not co-resident)"); }
         ttx_sweep_rec r{};
         r.it = it_; r.dir = dir; r.erank = erank_host(h, rank0_view(h, it_).data()); r.neval = (int64_t)h->h_sum[SUM_NEVAL]; r.val = val;
         r.amax = h->h_sum[SUM_AMAX]; r.pivotmax = h->h_sum[SUM_PMAX]; r.pivotmin = h->h_sum[SUM_PMIN]; r.seconds = since();
@@ -2077,20 +1924,20 @@ extern "C" int ttx_run(ttx_engine *h)
     if (rc && h->cluster_aborted)
         rc = replay(h, [](ttx_engine *e) {
             *e->h_abort = 0;
-            e->cluster = 0; e->cluster_aborted = false; e->cluster_fallbacks++;
+            e->retired.cluster = true; e->cluster_aborted = false; e->cluster_fallbacks++;
             if (e->P.ising_id == 1) e->P.arith = 0;        // the closed form of Ising C lives in the cluster kernel only
         });
     // k_halfstep_det found more units than the grid the host sized from its bound on the ranks (never expected): replay without teams
-    if (h->de_team && !h->de_v5 && read_fault_counter(h)) {
+    if (h->de_team() && !h->de_v5() && read_fault_counter(h)) {
         (void)hipGetLastError();
         if (h->W > 1) return fail(TTX_EHIP, "ttx_run: k_halfstep_det met a rank above the host's bound; set TTX_DE_TEAM=0");
-        rc = replay(h, [](ttx_engine *e) { e->de_team = 0; e->det_fallbacks++; });
+        rc = replay(h, [](ttx_engine *e) { e->retired.de_team = true; e->det_fallbacks++; });
     }
     // the relay of k_halfstep_de5 reports a broken hand-over (bounded waits): replay with k_halfstep_de
-    if (h->de_v5) if (const int faults = read_fault_counter(h)) {
+    if (h->de_v5()) if (const int faults = read_fault_counter(h)) {
         (void)hipGetLastError();
         if (h->W > 1) return fail(TTX_EHIP, "ttx_run: the wave relay of k_halfstep_de5 broke (%d hand-overs); set TTX_DE_V5=0", faults);
-        rc = replay(h, [](ttx_engine *e) { e->de_v5 = 0; e->de5_fallbacks++; });
+        rc = replay(h, [](ttx_engine *e) { e->retired.de_v5 = true; e->de5_fallbacks++; });
     }
     return rc;
 }
@@ -2103,7 +1950,7 @@ extern "C" int ttx_plan_describe(const ttx_engine *h, char *buf, int64_t cap)
     if (h->cfg.fun_id == 0) return fail(TTX_ESTATE, "ttx_plan_describe: this engine holds a loaded tensor train and has no integrand");
     return with_fun(h, nullptr, [&](auto fun) {
         const ChainPlan p = chain_plan<decltype(fun)::value>(h);
-        std::string s = std::string("path: ") + (h->cluster ? "cluster" : h->fused ? "fused" : "chain") + "\ntables: " + p.tables.name + "\nlottery: ";
+        std::string s = std::string("path: ") + (h->cluster_nb() ? "cluster" : h->sel.fused ? "fused" : "chain") + "\ntables: " + p.tables.name + "\nlottery: ";
         if (h->cfg.pivoting < 0) s += "-";
         else s += p.lot_eval ? std::string(p.lottery.name) + " + " + p.lot_eval.name + " + " + p.lottery.name : std::string(p.lottery.name);
         s += "\nhalfstep: ";
@@ -2194,7 +2041,7 @@ extern "C" int ttx_replicate(ttx_engine *h, ttx_engine **out)
     c.n = nn.data(); c.par = h->par.empty() ? nullptr : h->par.data(); c.aux = h->aux.empty() ? nullptr : h->aux.data(); c.naux = (int32_t)h->aux.size();
     c.quadw = nullptr;
     if (!h->quadw.empty()) { for (int k = 1; k <= d; k++) for (int j = 0; j < h->n1[k]; j++) qw.push_back(h->quadw[(size_t)k * h->NM + j]); c.quadw = qw.data(); }
-    c.nproc = 1; c.mybonds = nullptr; c.world_rank = 0; c.world_size = 1; c.verbose = 0; c.arith = h->P.arith;
+    c.nproc = 1; c.mybonds = nullptr; c.world_rank = 0; c.world_size = 1; c.verbose = 0; c.arith = h->arith();
     ttx_engine *e = nullptr;
     int rc = create_impl(&e, &c, h->cfg.fun_id == 0);
     if (rc) return rc;
@@ -2288,12 +2135,11 @@ static int train_shell(ttx_engine **out, const char *who, int32_t d, const int32
         const hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
         return e == hipSuccess ? TTX_OK : fail(TTX_EHIP, "%s: %s", who, hipGetErrorString(e));
     };
-    GroupState *g0 = (GroupState *)calloc(1, sizeof(GroupState));     // only the bond range is read by the quad kernels
-    g0->first = 1; g0->last = d - 1; g0->gglobal = 0;
+    GroupState g0{};                    // only the bond range is read by the quad kernels
+    g0.first = 1; g0.last = d - 1; g0.gglobal = 0;
     std::vector<int32_t> rr((size_t)(d + 2), 1);
     for (int p = 0; p <= d; p++) rr[p] = r[p];
-    if (!(rc = to_dev(h->P.gs, g0, offsetof(GroupState, S)))) rc = to_dev(h->P.r, rr.data(), sizeof(int32_t) * rr.size());
-    free(g0);
+    if (!(rc = to_dev(h->P.gs, &g0, offsetof(GroupState, S)))) rc = to_dev(h->P.r, rr.data(), sizeof(int32_t) * rr.size());
     if (rc) { destroy_keep_error(h); return rc; }
     h->rfinal.assign(r, r + d + 1);
     h->ran = true;
@@ -2572,7 +2418,7 @@ static int accchk_impl(ttx_engine *h, int nlot, double *einf, double *efro, doub
     };
     if (FUN == FUN_HOST) {
         // chunks of at most G*HS samples: index pass, the user's function on the host, value pass
-        const int chunk = (int)std::min<size_t>((size_t)h->G * h->HS, 65535);
+        const int chunk = (int)std::min<size_t>((size_t)h->G * h->sel.HS, 65535);
         for (int il0 = 0; il0 < nlot; il0 += chunk) {
             const int cnt = std::min(chunk, nlot - il0);
             DevProb Q = P;
@@ -3179,7 +3025,7 @@ static int tf_prepare(ttx_engine *h, const char *who, bool figures)
     char *dm;
     int rc;
     if ((rc = meta.upload(h, SC_TFUN, &dm)) || (rc = buf_reserve(h, SC_CNT, sizeof(long long)))) return rc;
-    if (f.op == TTX_TOP_DEVICE && (rc = buf_reserve(h, SC_TVAL, sizeof(double) * (size_t)h->G * h->HS * m))) return rc;
+    if (f.op == TTX_TOP_DEVICE && (rc = buf_reserve(h, SC_TVAL, sizeof(double) * (size_t)h->G * h->sel.HS * m))) return rc;
     HIPCHECK(hipMemsetAsync(buf<char>(h, SC_CNT), 0, sizeof(long long), h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
     TfOps &O = h->tf_ops;
@@ -3282,7 +3128,7 @@ static int tf_eval_list(ttx_engine *h, int64_t npts, const int32_t *ind, double 
     const TfOps &O = h->tf_ops;
     const size_t chunk = (size_t)std::min<int64_t>(npts, 1 << 16);
     if ((rc = buf_reserve(h, SC_IND, sizeof(int) * chunk * d)) || (rc = buf_reserve(h, SC_OUT, sizeof(double) * chunk))) return rc;
-    if (f.op == TTX_TOP_DEVICE && (rc = buf_reserve(h, SC_TVAL, sizeof(double) * std::max(chunk, (size_t)h->G * h->HS) * O.m))) return rc;
+    if (f.op == TTX_TOP_DEVICE && (rc = buf_reserve(h, SC_TVAL, sizeof(double) * std::max(chunk, (size_t)h->G * h->sel.HS) * O.m))) return rc;
     int *sind = buf<int>(h, SC_IND);
     double *sout = buf<double>(h, SC_OUT), *tval = buf<double>(h, SC_TVAL);
     unsigned long long *cnt = buf<unsigned long long>(h, SC_CNT);
@@ -3459,10 +3305,10 @@ extern "C" int ttx_value_batch(ttx_engine *h, int64_t npts, int32_t dd, const do
     return ev_batch(h, "ttx_value_batch", EV_HOST_COORD, npts, dd, x, out, mode);
 }
 
-extern "C" int ttx_arith(const ttx_engine *h) { return h ? h->P.arith : -1; }
-extern "C" int ttx_sweep_path(const ttx_engine *h) { return !h ? -1 : h->cluster ? 2 : h->fused ? 1 : 0; }
+extern "C" int ttx_arith(const ttx_engine *h) { return h ? h->arith() : -1; }
+extern "C" int ttx_sweep_path(const ttx_engine *h) { return !h ? -1 : h->cluster_nb() ? 2 : h->sel.fused ? 1 : 0; }
 extern "C" int64_t ttx_resid_halfsteps(const ttx_engine *h) { return h ? h->n_resid : 0; }
-extern "C" int ttx_cluster_eval(const ttx_engine *h) { return !h ? -1 : h->cluster ? 1 + h->cluster_var : 0; }
+extern "C" int ttx_cluster_eval(const ttx_engine *h) { return !h ? -1 : h->cluster_nb() ? 1 + h->sel.cluster_var : 0; }
 extern "C" int ttx_cluster_fallbacks(const ttx_engine *h) { return h ? h->cluster_fallbacks : 0; }
 extern "C" int ttx_det_fallbacks(const ttx_engine *h) { return h ? h->det_fallbacks + h->de5_fallbacks : 0; }
 extern "C" int ttx_fun_id(const ttx_engine *h) { return h ? h->cfg.fun_id : -1; }
@@ -3685,7 +3531,7 @@ static int sm_run(ttx_engine *h, const char *who, int64_t npts, const double *u,
     const int ldsrow = std::min(nrow, TTX_SM_LDSROW);
     const size_t growlen = nrow > TTX_SM_LDSROW ? (size_t)nrow : 0;
     const size_t lds = 4 * sizeof(double) * (2 * (size_t)T.ldx + d + (((size_t)d + 1) >> 1) + ldsrow);
-    if (lds > 160 * 1024) return fail(TTX_EINVAL, "%s: %d modes need %zu bytes of LDS per workgroup (160 KB at most)", who, d, lds);
+    if (lds > TTX_LDS_DEVICE) return fail(TTX_EINVAL, "%s: %d modes need %zu bytes of LDS per workgroup (160 KB at most)", who, d, lds);
     if (lds > 64 * 1024 && (rc = ensure_lds(h, reinterpret_cast<const void *>(k_sm_draw), lds))) return rc;
     if (growlen && (rc = buf_reserve(h, SC_ROW, sizeof(double) * growlen * 4 * gridmax))) return rc;
     double *grow = growlen ? buf<double>(h, SC_ROW) : nullptr;

@@ -8,10 +8,14 @@
 #include <cstddef>
 #include <vector>
 
-// dynamic-LDS budgets of the tt_lib utilities, in bytes
-constexpr size_t TTX_LDS_DEVICE = 160 * 1024;       // what a workgroup of the device can have
-constexpr size_t TTX_LDS_WORK = 150 * 1024;         // what the one-workgroup QR kernels ask for at most
+// dynamic-LDS budgets, in bytes: of the tt_lib utilities, and of the sweep's kernels as engine creation sizes them (ttx_create_plan.h)
+constexpr size_t TTX_LDS_DEVICE = 160 * 1024;       // what a workgroup of the device can have; the half-step's staging may take all of it
+constexpr size_t TTX_LDS_WORK = 150 * 1024;         // what a kernel's working set asks for at most: the one-workgroup QR kernels, the sweep's variants
 constexpr size_t TTX_LDS_JACOBI = 140 * 1024;       // up to here the Jacobi SVD keeps X and V in LDS
+constexpr size_t TTX_LDS_HALF_DIFF = 140 * 1024;    // up to here the mvn half-step keeps rows of differences x - mu instead of index rows
+constexpr size_t TTX_LDS_LOTTERY = 120 * 1024;      // what the lottery kernel may stage; a problem that needs more is refused
+constexpr size_t TTX_LDS_VALUES = 100 * 1024;       // up to here the Ising C half-step keeps value rows, and the fast lottery its decay-table rows
+constexpr size_t TTX_LDS_FIN = 96 * 1024;           // the finalisation halves its workgroup until the LU panel and its columns are below this
 
 // the switches, read per call by the engine (threads already clamped to a multiple of 64 in 64..1024)
 struct QrEnv {
