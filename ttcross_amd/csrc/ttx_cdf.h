@@ -130,6 +130,65 @@ TTX_HD int ttx_lottery_index(const ttx_cdfseg *seg, int ns, int K, int m, const 
     return ttx_select_nonzero(kmax + 1, zeros, nz);
 }
 
+// Both lottery indices of one candidate: x = ttx_lottery_index(segx, ...), y = ttx_lottery_index(segy, ...), equal to the two
+// calls for every input, but written as ONE dependent chain with as few instructions as the two could be made to share.  A
+// lone wave pays an LDS round trip per step of a binary search and runs the integer code of ttx_units / ttx_divfloor at one
+// instruction per issue slot; here
+//   * the two searches advance together, every step tests x and y side by side, and no branch depends on a lane: a search is
+//     a descent by powers of two over the count of leading entries that satisfy a monotone predicate (a0 <= draw for the
+//     segments, zeros[t] - t <= kth for the zero list).  The first stride is the largest power of two not above the longer of
+//     the two lists (at most SEGCAP / ZCAP, the capacities the caller guarantees: ns <= SEGCAP, nz <= ZCAP), so the trip
+//     count is the same for x and y and for every lane that passes the same list lengths;
+//   * the quotient inside a segment is taken in fp64 without the detour through integer units: with the draw d in [a0, alast)
+//     of a segment, d, a0 and delta are multiples of the binade's ulp u, A = d - a0 is exact (same binade), and A / delta is
+//     the same real number as ttx_cdf_kmax's N / D (N = A / u, D = delta / u).  floor(N / D) < 2^53 is a double and rounding
+//     is monotone, so trunc(fl(A / delta)) is floor(N / D) or one more (never less: no upward step); the sign of A - q delta, which decides, is exact from
+//     one fused multiply-add (a single rounding never changes the sign of a non-zero multiple of u >= 2^-1074).  Where
+//     ttx_cdf_kmax does not divide, the operands are 0 / 1.
+// A precondition ttx_lottery_index does not have: every list must be readable at index 0 even when it is empty (the value is
+// then ignored), because the loads carry no test.  The LDS arrays of the cluster kernel are.
+struct ttx_pair { int x, y; };
+TTX_HD int ttx_pow2floor(int v) { return v > 0 ? 1 << (31 - __builtin_clz((unsigned)v)) : 0; }   // 0 for an empty list: no step
+template <int SEGCAP, int ZCAP>
+TTX_HD ttx_pair ttx_lottery_index2(const ttx_cdfseg *segx, int nsx, int Kx, int mx, const int32_t *zx, int nzx, double dx,
+                                   const ttx_cdfseg *segy, int nsy, int Ky, int my, const int32_t *zy, int nzy, double dy)
+{
+    static_assert((SEGCAP & (SEGCAP - 1)) == 0 && (ZCAP & (ZCAP - 1)) == 0, "capacities are powers of two");
+    // number of segments with a0 <= draw
+    int px = 0, py = 0;
+    const int nsm = nsx > nsy ? nsx : nsy;
+    for (int st = nsm >= SEGCAP ? SEGCAP : ttx_pow2floor(nsm); st >= 1; st >>= 1) {
+        const int tx = px + st, ty = py + st;
+        const int ux = (tx <= nsx ? tx : nsx) - 1, uy = (ty <= nsy ? ty : nsy) - 1;
+        const double ax = segx[ux > 0 ? ux : 0].a0, ay = segy[uy > 0 ? uy : 0].a0;
+        px = (tx <= nsx && ax <= dx) ? tx : px;
+        py = (ty <= nsy && ay <= dy) ? ty : py;
+    }
+    const ttx_cdfseg sx = segx[px > 0 ? px - 1 : 0], sy = segy[py > 0 ? py - 1 : 0];
+    const bool vx = px > 0 && sx.cnt != 1 && dx < sx.alast, vy = py > 0 && sy.cnt != 1 && dy < sy.alast;   // divide
+    const double Ax = vx ? dx - sx.a0 : 0.0, Ay = vy ? dy - sy.a0 : 0.0, Ex = vx ? sx.delta : 1.0, Ey = vy ? sy.delta : 1.0;
+    int qx = (int)(Ax / Ex), qy = (int)(Ay / Ey);
+    qx -= (__builtin_fma(-(double)qx, Ex, Ax) < 0.0); qy -= (__builtin_fma(-(double)qy, Ey, Ay) < 0.0);
+    const int kx = vx ? sx.k0 + qx : (px > 0 ? sx.k0 + sx.cnt - 1 : 0);
+    const int ky = vy ? sy.k0 + qy : (py > 0 ? sy.k0 + sy.cnt - 1 : 0);
+    // position of non-zero weight number k + 1: k + 1 + #{t : zeros[t] - t <= k + 1}
+    const int ex = kx + 1, ey = ky + 1;
+    int cx = 0, cy = 0;
+    const int nzm = nzx > nzy ? nzx : nzy;
+    for (int st = nzm >= ZCAP ? ZCAP : ttx_pow2floor(nzm); st >= 1; st >>= 1) {
+        const int tx = cx + st, ty = cy + st;
+        const int ux = (tx <= nzx ? tx : nzx) - 1, uy = (ty <= nzy ? ty : nzy) - 1;
+        const int wx = ux > 0 ? ux : 0, wy = uy > 0 ? uy : 0;
+        const int fx = zx[wx] - wx, fy = zy[wy] - wy;
+        cx = (tx <= nzx && fx <= ex) ? tx : cx;
+        cy = (ty <= nzy && fy <= ey) ? ty : cy;
+    }
+    ttx_pair r;
+    r.x = (kx >= Kx) ? mx : ex + cx;
+    r.y = (ky >= Ky) ? my : ey + cy;
+    return r;
+}
+
 // minstd power 48271^e mod (2^31-1)
 TTX_HD uint64_t ttx_minstd_pow(uint64_t e)
 {

@@ -304,6 +304,12 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
     int hcount = 0;                                    // half-steps exchanged so far (selects the record buffer)
     const unsigned long long bil0 = ttx_minstd_pow(2ull * tid);     // RNG jump of this thread's first lottery candidate
     unsigned long long sA0 = ttx_minstd_pow(2 * rngpos + 1);
+    // the generator step of a bond step, 48271^(2 nlot), without the square-and-multiply loop per step (8 rounds of two 64-bit
+    // products on every lane): lane l keeps 48271^(2 l), and 48271^(2 (64 a + b)) = 48271^(2 b) * (48271^128)^a -- one lane
+    // exchange and a <= 7 products below 512 candidates (the same residue: modular products are exact).  The bound 512 is
+    // reasoned, not measured: the loop runs about ten rounds of two products for such nlot, so seven products are still fewer.
+    const int bl0 = (int)ttx_minstd_pow(2ull * lane);
+    const unsigned long long c64 = ttx_minstd_pow(128);
     CST_DECL;
 
     for (int pp = 1; pp <= nsteps; pp++) {
@@ -311,13 +317,27 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         const int p = (dir == 1) ? first + pp - 1 : last + 1 - pp;          // :330-331
         const int r0 = r[p - 1], r1 = r[p], r2 = r[p + 1], n1 = P.n[p], n2 = P.n[p + 1];
         const int nlot = r0 + n1 + n2 + r2;
-        const int jlo = (int)((long long)cb * n1 / NB), jhi = (int)((long long)(cb + 1) * n1 / NB);   // own columns j of acol1
-        const int klo = (int)((long long)cb * n2 / NB), khi = (int)((long long)(cb + 1) * n2 / NB);   // own rows k of arow1
+        // slice bounds floor(c * n / NB): c <= NB <= 16 and n <= NM, so the product fits 32 bits (a 64-bit division is a long
+        // per-lane instruction sequence; these are evaluated twelve times per bond step)
+        auto slice = [&](int c, int n) { return (int)((unsigned)c * (unsigned)n / (unsigned)NB); };
+        const int jlo = slice(cb, n1), jhi = slice(cb + 1, n1);   // own columns j of acol1
+        const int klo = slice(cb, n2), khi = slice(cb + 1, n2);   // own rows k of arow1
         const int nj = jhi - jlo, nk = khi - klo;
         double *Cp = core_ptr(P, P.col, g, p, first), *Wq = core_ptr(P, P.row, g, p + 1, first);
         double *Ap = core_ptr(P, P.arg, g, p, first), *Aq = core_ptr(P, P.arg, g, p + 1, first);
         const short *Lt = L_ptr(P, g, p - 1, first), *Rt = R_ptr(P, g, p + 1, first);
         const int cA = (p - 1 + 7) >> 3, cB = (m - p - 1 + 7) >> 3;      // chunks of the left / right rows (f_ising_c4w)
+        // The lottery's CDF segments are fetched by the two waves that have no prefix chain to run (waves 2, 3: column / row lottery),
+        // count and segment in ONE round trip: the row of the table is read at full width (rows are TTX_TABSEG long, zero behind
+        // the count) and only the valid part is stored.  Held in plain registers until the lists are built.
+        const int sside = (tid >> 6) & 1, sseg = tid & 63;
+        double sg_a0 = 0.0, sg_al = 0.0, sg_de = 0.0; int sg_k0 = 0, sg_cn = 0, myns = 0;
+        auto seg_issue = [&](int Kc_, int Kr_) {
+            if (tid >= 128) {
+                const int K = sside ? Kr_ : Kc_; const ttx_cdfseg *sp = P.cdf_tab + (size_t)K * TTX_TABSEG + sseg;
+                myns = P.cdf_ns[K]; sg_a0 = sp->a0; sg_al = sp->alast; sg_de = sp->delta; sg_k0 = sp->k0; sg_cn = sp->cnt;
+            }
+        };
         // ---- stage the value tables of both pivot sets (only the dimensions that exist on either side, rounded up to
         //      the 8-wide chunks the integrand reads; the walk over (row, dim) needs no division) ----
         {
@@ -356,11 +376,16 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
             if (p < last)  { const double *gU = inv_ptr(P, g, p + 1, first); for (int x = tid; x < r2 * r2; x += CB) GU[x] = gU[x]; }
         }
         CST(0);
+        if (zkeep) seg_issue(r0 * n1 - ZN[2 * (p - first)], n2 * r2 - ZN[2 * (p - first) + 1]);
         // ---- lottery (:410-484): every block draws and scores all candidates (identical results, no traffic) ----
         // generator words of the two draw columns: 48271^(2*rngpos+1) and 48271^(2*(rngpos+nlot)+1), advanced from
         // step to step by the small power 48271^(2*nlot) (every thread keeps them; no shared state, no barrier)
         if (tid == 0) s_ok = 1;                            // (read behind the rook loop; several barriers lie in between)
-        const unsigned long long stepmul = ttx_minstd_pow(2ull * nlot);
+        unsigned long long stepmul;
+        if (nlot < 512) {
+            stepmul = (unsigned long long)(unsigned)__shfl(bl0, nlot & 63);
+            for (int a = 0; a < (nlot >> 6); a++) stepmul = ttx_mulmod31(stepmul, c64);
+        } else stepmul = ttx_minstd_pow(2ull * nlot);       // (modes in the hundreds: as before)
         const unsigned long long sA1 = ttx_mulmod31(sA0, stepmul);
         if (zkeep) {
             const int b = p - first;
@@ -395,8 +420,14 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         }
         CST(1);
         const int Kc = r0 * n1 - nzc, Kr = n2 * r2 - nzr;
-        if (tid < 64) { if (tid < P.cdf_ns[Kc]) segc[tid] = P.cdf_tab[(size_t)Kc * TTX_TABSEG + tid]; if (tid == 0) nsc = P.cdf_ns[Kc]; }
-        else if (tid < 128) { const int t2 = tid - 64; if (t2 < P.cdf_ns[Kr]) segr[t2] = P.cdf_tab[(size_t)Kr * TTX_TABSEG + t2]; if (t2 == 0) nsr = P.cdf_ns[Kr]; }
+        // (waves 2 and 3 store their segment while waves 0 and 1 run the prefix chains; without zkeep the lengths are known only
+        // here, so nothing is hidden, but count and row still come in one round trip instead of two)
+        if (!zkeep) seg_issue(Kc, Kr);
+        if (tid >= 128) {
+            ttx_cdfseg *dst = sside ? segr : segc;
+            if (sseg < myns) { dst[sseg].a0 = sg_a0; dst[sseg].alast = sg_al; dst[sseg].delta = sg_de; dst[sseg].k0 = sg_k0; dst[sseg].cnt = sg_cn; }
+            if (sseg == 0) { if (sside) nsr = myns; else nsc = myns; }
+        }
         if (tid < r0) {                                // ascending sum over the left row (dims 1..p-1)
             double w = 1.0, wk = 1.0;
             auto wstep = [&](double xv) { wk = wk * xv; w = w + wk; };
@@ -430,11 +461,15 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         __syncthreads();
         CST(2);
         double ma = 0.0, ba = -1.0, bv = 0.0; int bi = INT_MAX;
+        // list lengths as wave-uniform values: the two searches of ttx_lottery_index2 then run a uniform number of steps
+        const int nscu = __builtin_amdgcn_readfirstlane(nsc), nsru = __builtin_amdgcn_readfirstlane(nsr);
+        const int nzcu = __builtin_amdgcn_readfirstlane(nzc), nzru = __builtin_amdgcn_readfirstlane(nzr);
         for (int il = tid; il < nlot; il += CB) {
             const unsigned long long bil = (il == tid) ? bil0 : ttx_minstd_pow(2ull * il);
             const double d1 = ttx_flang_from_word(ttx_mulmod31(sA0, bil)), d2 = ttx_flang_from_word(ttx_mulmod31(sA1, bil));
-            const int x = ttx_lottery_index(segc, nsc, Kc, r0 * n1, zc, nzc, d1);
-            const int y = ttx_lottery_index(segr, nsr, Kr, n2 * r2, zr, nzr, d2);
+            // (the lists hold at most r1 <= RM <= 64 entries on this path)
+            const ttx_pair xy = ttx_lottery_index2<TTX_TABSEG, 64>(segc, nscu, Kc, r0 * n1, zc, nzcu, d1, segr, nsru, Kr, n2 * r2, zr, nzru, d2);
+            const int x = xy.x, y = xy.y;
             CST(3);
             const int i = (x - 1) % r0 + 1, j = (x - 1) / r0 + 1, k = (y - 1) % n2 + 1, q = (y - 1) / n2 + 1;
             lot[4 * il] = i; lot[4 * il + 1] = j; lot[4 * il + 2] = k; lot[4 * il + 3] = q;
@@ -480,7 +515,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         // against ~1000 in isolation: profiles/probes/probe_exchange.hip).  The others wait at the barrier behind the loop and take
         // the results from LDS.  wact(c): participating waves of workgroup c -- the same number on every wave of the cluster.
         auto wact = [&](int c) {
-            const int njc = (int)((long long)(c + 1) * n1 / NB) - (int)((long long)c * n1 / NB), nkc = (int)((long long)(c + 1) * n2 / NB) - (int)((long long)c * n2 / NB);
+            const int njc = slice(c + 1, n1) - slice(c, n1), nkc = slice(c + 1, n2) - slice(c, n2);
             const int e = max(r0 * njc, nkc * r2);
             return min(CB / 64, max(1, (e + 63) >> 6));
         };
