@@ -9,17 +9,12 @@
 
 #include <chrono>
 #include <cmath>
-#include <cerrno>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
-#include <functional>
 #include <map>
 #include <memory>
-#include <mutex>
-#include <random>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -27,10 +22,6 @@
 
 #include <atomic>
 #include <dlfcn.h>
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 #include <rccl/rccl.h>   // types and enums only: the library is dlopen()ed by ttx_comm_init
 
 #include "../../include/ttx.h"
@@ -38,6 +29,9 @@
 #include "ttx_lds.h"
 #include "ttx_qr_plan.h"
 #include "ttx_create_plan.h"
+#include "ttx_shm.h"
+#include "ttx_host_pool.h"
+#include "ttx_files.h"
 #include "ttx_kernels.h"
 #include "ttx_de.h"
 #include "ttx_mvn.h"
@@ -178,7 +172,7 @@ struct ttx_engine {
         red_next = (red_next + 1) % NRED;
         return j;
     }
-    struct ShmTransport *shm = nullptr; // built-in node-local transport (ttx_comm_init_shm)
+    ShmTransport *shm = nullptr;        // built-in node-local transport (ttx_comm_init_shm)
     std::vector<ttx_sweep_rec> recs;
     std::vector<int32_t> tapes;         // [nsweeps-1][d+1][4]
     std::vector<int32_t> rfinal;
@@ -243,79 +237,11 @@ struct ttx_engine {
     int ma_mode = -1;
 };
 
-// ---- worker threads for the host integrand (the reference evaluates `fun` inside !$OMP PARALLEL DO regions,
-//      lib/dmrgg.f90:169,222,455,520,553; `fun` must be thread-safe there and here) ----------------------------
-namespace {
-class HostPool {
-  public:
-    static HostPool &get() { static HostPool p; return p; }
-    int threads() const { return (int)workers.size() + 1; }
-    // fn(i) for i in [0, n): the calling thread takes part; returns when all are done.  The pool is one per process:
-    // engines driven from different host threads take turns on it, one batch at a time (`turn`).
-    void run(size_t n, const std::function<void(size_t)> &fn)
-    {
-        if (n == 0) return;
-        if (workers.empty() || n < 32) { for (size_t i = 0; i < n; i++) fn(i); return; }
-        std::lock_guard<std::mutex> one_batch(turn);
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            job = &fn; total = n; next = 0; pending = workers.size(); gen++;
-        }
-        cv.notify_all();
-        work();
-        std::unique_lock<std::mutex> lk(mu);
-        done.wait(lk, [&] { return pending == 0; });
-        job = nullptr;
-    }
-  private:
-    HostPool()
-    {
-        int nt = 0;
-        if (const char *e = getenv("TTX_HOST_THREADS")) nt = atoi(e);
-        else if (const char *e2 = getenv("OMP_NUM_THREADS")) nt = atoi(e2);
-        if (nt <= 0) nt = (int)std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
-        for (int t = 1; t < nt; t++) workers.emplace_back([this] { loop(); });
-    }
-    ~HostPool()
-    {
-        { std::lock_guard<std::mutex> lk(mu); quit = true; gen++; }
-        cv.notify_all();
-        for (auto &w : workers) w.join();
-    }
-    void work()
-    {
-        for (;;) {
-            size_t lo, hi;
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                if (next >= total) return;
-                lo = next; hi = std::min(total, lo + std::max<size_t>(1, total / (8 * (workers.size() + 1)))); next = hi;
-            }
-            for (size_t i = lo; i < hi; i++) (*job)(i);
-        }
-    }
-    void loop()
-    {
-        unsigned long long seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return gen != seen; });
-                seen = gen;
-                if (quit) return;
-            }
-            work();
-            { std::lock_guard<std::mutex> lk(mu); if (--pending == 0) done.notify_all(); }
-        }
-    }
-    std::vector<std::thread> workers;
-    std::mutex mu, turn;
-    std::condition_variable cv, done;
-    const std::function<void(size_t)> *job = nullptr;
-    size_t total = 0, next = 0, pending = 0;
-    unsigned long long gen = 0;
-    bool quit = false;
-};
+// the process-wide pool of the host integrand (ttx_host_pool.h): engines driven from different host threads take turns on it
+static HostPool &host_pool()
+{
+    static HostPool p(host_pool_threads(getenv("TTX_HOST_THREADS"), getenv("OMP_NUM_THREADS"), std::thread::hardware_concurrency()));
+    return p;
 }
 
 // after the index pass of a kernel: wait for it, call the user's function for every requested slot, clear the requests
@@ -329,7 +255,7 @@ static int host_eval(ttx_engine *h)
     for (size_t s = 0; s < nslot; s++) if (P.hreq[s]) { todo.push_back((uint32_t)s); P.hreq[s] = 0; }
     const int32_t d = h->d;
     const int32_t *nn = h->n1.data() + 1;
-    HostPool::get().run(todo.size(), [&](size_t i) {
+    host_pool().run(todo.size(), [&](size_t i) {
         int32_t ind[2048];
         const short *row = P.hidx + (size_t)todo[i] * d;
         for (int k = 0; k < d; k++) ind[k] = row[k];
@@ -773,7 +699,6 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
 }
 extern "C" int ttx_create(ttx_engine **out, const ttx_config *cfg) { return create_impl(out, cfg, false); }
 
-static void shm_close(ttx_engine *h);
 extern "C" void ttx_destroy(ttx_engine *h)
 {
     if (!h) return;
@@ -792,7 +717,7 @@ extern "C" void ttx_destroy(ttx_engine *h)
     if (h->h_msg) (void)hipHostFree(h->h_msg);
     if (h->h_tmp) (void)hipHostFree(h->h_tmp);
     if (h->red_mem) (void)hipHostFree(h->red_mem);
-    shm_close(h);
+    if (h->shm) { shm_close(h->shm); delete h->shm; }
     if (h->h_abort) (void)hipHostFree(h->h_abort);
     if (!h->P.slot_dev) {                   // device slots are in allocs
         if (h->P.hidx) (void)hipHostFree(h->P.hidx);
@@ -881,99 +806,7 @@ extern "C" int ttx_k_rccl_selftest(int32_t device, int64_t msg_bytes, int32_t ns
     return TTX_OK;
 }
 
-// ---- built-in node-local host transport over POSIX shared memory ------------------------------------------------
-// For jobs whose processes share a node but cannot use RCCL (several ranks on ONE GPU -- RCCL refuses that -- or no
-// librccl), and for launchers without MPI (the Fortran drop-in layer): the ttx_transport primitives implemented on a
-// shared segment.  Point-to-point: one mailbox per (receiver, side) with a sequence / acknowledge pair; all-reduce: every
-// rank deposits its vector, a sense-reversing barrier, every rank folds the W vectors in rank order (so all ranks get
-// the identical bits), a second barrier before the slots are reused.  Waits are bounded (60 s) and report failure.
-// Attaching is a handshake on a per-initialisation NONCE, so that a rank can never end up on a segment that rank 0 did not
-// create in THIS call (a segment left by a crashed job, or the one of the previous dtt_dmrgg of the same job, still carries
-// ready = 1 and old counters): rank 0 unlinks the name, creates a fresh segment and publishes a random nonce; rank r copies the
-// nonce it sees into hello[r] and waits for go == that nonce, which rank 0 sets once every hello matches.  A segment whose go
-// is already set before the rank said hello is stale by construction; while it waits, a rank re-checks that the NAME still
-// leads to the inode it has mapped (rank 0's unlink + create changes it) and starts over if not.
-struct ShmHeader {
-    std::atomic<uint32_t> ready, arrived, sense;
-    uint32_t W; uint64_t msz, redcap;
-    std::atomic<uint64_t> nonce, go;
-    std::atomic<uint64_t> hello[256];
-};
-static_assert(sizeof(ShmHeader) <= 4096, "the header shares the first page of the segment");
-struct ShmBox { std::atomic<uint64_t> seq, ack; uint64_t bytes; };
-struct ShmTransport {
-    void *base = nullptr; size_t size = 0; std::string name; int rank = 0, W = 1; bool owner = false;
-    ShmHeader *hd = nullptr;
-    size_t msz = 0, redcap = 0;
-    uint32_t my_sense = 0;
-    ShmBox *box(int r, int side) const { return (ShmBox *)((char *)base + 4096 + ((size_t)r * 2 + side) * (64 + msz)); }   // side 0: from the left, 1: from the right
-    char *boxdata(int r, int side) const { return (char *)box(r, side) + 64; }
-    double *red(int r) const { return (double *)((char *)base + 4096 + (size_t)W * 2 * (64 + msz) + (size_t)r * redcap * sizeof(double)); }
-};
-static bool shm_wait(const std::function<bool()> &cond)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0;; spins++) {
-        if (cond()) return true;
-        if ((spins & 1023u) == 1023u) {
-            if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 60.0) return false;
-            std::this_thread::yield();
-        }
-    }
-}
-static int shm_barrier(ShmTransport *T)
-{
-    T->my_sense ^= 1u;
-    if (T->hd->arrived.fetch_add(1u, std::memory_order_acq_rel) + 1u == (uint32_t)T->W) {
-        T->hd->arrived.store(0u, std::memory_order_relaxed);
-        T->hd->sense.store(T->my_sense, std::memory_order_release);
-        return 0;
-    }
-    return shm_wait([&] { return T->hd->sense.load(std::memory_order_acquire) == T->my_sense; }) ? 0 : 1;
-}
-static int shm_sendrecv(void *ctx, int to, const void *sbuf, int64_t ns, int from, void *rbuf, int64_t nr)
-{
-    ShmTransport *T = (ShmTransport *)ctx;
-    if ((size_t)ns > T->msz || (size_t)nr > T->msz) return 1;
-    if (to >= 0) {                                   // I am the left neighbour of `to` when to == rank + 1: its side-0 box
-        const int side = (to == T->rank + 1) ? 0 : 1;
-        ShmBox *b = T->box(to, side);
-        if (!shm_wait([&] { return b->ack.load(std::memory_order_acquire) == b->seq.load(std::memory_order_relaxed); })) return 1;
-        memcpy(T->boxdata(to, side), sbuf, (size_t)ns);
-        b->bytes = (uint64_t)ns;
-        b->seq.fetch_add(1u, std::memory_order_release);
-    }
-    if (from >= 0) {
-        const int side = (from == T->rank - 1) ? 0 : 1;
-        ShmBox *b = T->box(T->rank, side);
-        if (!shm_wait([&] { return b->seq.load(std::memory_order_acquire) != b->ack.load(std::memory_order_relaxed); })) return 1;
-        memcpy(rbuf, T->boxdata(T->rank, side), (size_t)std::min<uint64_t>((uint64_t)nr, b->bytes));
-        b->ack.fetch_add(1u, std::memory_order_release);
-    }
-    return 0;
-}
-static int shm_allreduce(void *ctx, double *buf, int64_t count, int op)
-{
-    ShmTransport *T = (ShmTransport *)ctx;
-    if ((size_t)count > T->redcap) return 1;
-    memcpy(T->red(T->rank), buf, sizeof(double) * (size_t)count);
-    if (shm_barrier(T)) return 1;
-    for (int64_t i = 0; i < count; i++) {
-        double a = T->red(0)[i];
-        for (int r = 1; r < T->W; r++) a = op ? std::max(a, T->red(r)[i]) : a + T->red(r)[i];
-        buf[i] = a;
-    }
-    return shm_barrier(T);
-}
-static void shm_close(ttx_engine *h)
-{
-    ShmTransport *T = h->shm;
-    if (!T) return;
-    if (T->base) munmap(T->base, T->size);
-    if (T->owner) shm_unlink(T->name.c_str());
-    delete T;
-    h->shm = nullptr;
-}
+// ---- built-in node-local host transport over POSIX shared memory (ttx_shm.h) -----------------------------------------
 extern "C" int ttx_comm_init_shm(ttx_engine *h, const char *name)
 {
     if (!h || !name || !*name) return fail(TTX_EINVAL, "ttx_comm_init_shm: null argument");
@@ -981,83 +814,10 @@ extern "C" int ttx_comm_init_shm(ttx_engine *h, const char *name)
     if (h->W == 1) return TTX_OK;
     if (h->shm) return fail(TTX_ESTATE, "ttx_comm_init_shm: already initialised");
     ShmTransport *T = new ShmTransport();
-    T->name = std::string(name[0] == '/' ? "" : "/") + name;
-    T->rank = h->wrank; T->W = h->W;
-    T->msz = (h->P.MSZ + 63) & ~(size_t)63;
-    T->redcap = std::max<size_t>(std::max(h->QB, h->SB), 8);
-    T->size = 4096 + (size_t)T->W * 2 * (64 + T->msz) + (size_t)T->W * T->redcap * sizeof(double);
-    const auto t_start = std::chrono::steady_clock::now();
-    auto elapsed = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
-    if (T->rank == 0) {
-        shm_unlink(T->name.c_str());
-        int fd = shm_open(T->name.c_str(), O_CREAT | O_EXCL | O_RDWR, 0600);
-        if (fd < 0 || ftruncate(fd, (off_t)T->size) != 0) { if (fd >= 0) close(fd); delete T; return fail(TTX_EHIP, "ttx_comm_init_shm: cannot create %s", name); }
-        T->owner = true;
-        T->base = mmap(nullptr, T->size, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-        close(fd);
-        if (T->base == MAP_FAILED) { T->base = nullptr; shm_unlink(T->name.c_str()); delete T; return fail(TTX_EHIP, "ttx_comm_init_shm: mmap failed"); }
-        T->hd = (ShmHeader *)T->base;          // a fresh segment is zero-filled: sequence numbers, counters, sense, go and hello start at 0
-        T->hd->W = (uint32_t)T->W; T->hd->msz = T->msz; T->hd->redcap = T->redcap;
-        std::random_device rd;
-        uint64_t nonce = ((uint64_t)rd() << 32) ^ (uint64_t)rd() ^ ((uint64_t)getpid() << 17) ^ (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count();
-        if (nonce == 0) nonce = 1;
-        T->hd->nonce.store(nonce, std::memory_order_relaxed);
-        T->hd->ready.store(1u, std::memory_order_release);
-        const bool all = shm_wait([&] {
-            for (int r = 1; r < T->W; r++) if (T->hd->hello[r].load(std::memory_order_acquire) != nonce) return false;
-            return true;
-        });
-        if (!all) { munmap(T->base, T->size); shm_unlink(T->name.c_str()); delete T; return fail(TTX_EHIP, "ttx_comm_init_shm: not all %d ranks attached to %s", T->W, name); }
-        T->hd->go.store(nonce, std::memory_order_release);
-    } else {
-        bool joined = false, mismatch = false;
-        while (!joined && elapsed() < 60.0) {
-            int fd = shm_open(T->name.c_str(), O_RDWR, 0600);
-            struct stat st;
-            if (fd < 0 || fstat(fd, &st) != 0 || (size_t)st.st_size < T->size) { if (fd >= 0) close(fd); std::this_thread::sleep_for(std::chrono::milliseconds(2)); continue; }
-            const ino_t ino = st.st_ino;
-            void *base = mmap(nullptr, T->size, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-            close(fd);
-            if (base == MAP_FAILED) { delete T; return fail(TTX_EHIP, "ttx_comm_init_shm: mmap failed"); }
-            ShmHeader *hd = (ShmHeader *)base;
-            auto still_current = [&] {          // does the name still lead to the segment that is mapped here?
-                int f2 = shm_open(T->name.c_str(), O_RDWR, 0600);
-                struct stat s2;
-                const bool same = f2 >= 0 && fstat(f2, &s2) == 0 && s2.st_ino == ino;
-                if (f2 >= 0) close(f2);
-                return same;
-            };
-            bool restart = false, said = false;
-            uint64_t nonce = 0;
-            auto t_chk = std::chrono::steady_clock::now();
-            while (!restart && elapsed() < 60.0) {
-                if (!said && hd->ready.load(std::memory_order_acquire) == 1u) {
-                    mismatch = hd->W != (uint32_t)T->W || hd->msz != T->msz || hd->redcap != T->redcap;
-                    nonce = hd->nonce.load(std::memory_order_relaxed);
-                    if (mismatch || hd->go.load(std::memory_order_acquire) == nonce) {
-                        // another problem's segment, or one whose initialisation is over: not ours -- wait for rank 0 to replace the name
-                        while (elapsed() < 60.0 && still_current()) std::this_thread::sleep_for(std::chrono::milliseconds(2));
-                        restart = true;
-                        break;
-                    }
-                    hd->hello[T->rank].store(nonce, std::memory_order_release);
-                    said = true;
-                }
-                if (said && hd->go.load(std::memory_order_acquire) == nonce) { joined = true; break; }
-                if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_chk).count() > 0.02) {
-                    t_chk = std::chrono::steady_clock::now();
-                    if (!still_current()) restart = true;
-                }
-                std::this_thread::yield();
-            }
-            if (joined) { T->base = base; T->hd = hd; }
-            else munmap(base, T->size);
-        }
-        if (!joined) {
-            delete T;
-            return mismatch ? fail(TTX_EINVAL, "ttx_comm_init_shm: the ranks disagree about the problem (or %s belongs to another job)", name)
-                            : fail(TTX_EHIP, "ttx_comm_init_shm: rank 0 did not create %s (or never saw every rank)", name);
-        }
+    std::string text;
+    if (int rc = shm_attach(name, h->wrank, h->W, (h->P.MSZ + 63) & ~(size_t)63, std::max<size_t>(std::max(h->QB, h->SB), 8), T, &text)) {
+        delete T;
+        return fail(rc, "%s", text.c_str());
     }
     h->shm = T;
     h->cb.ctx = T; h->cb.sendrecv = shm_sendrecv; h->cb.allreduce = shm_allreduce; h->have_cb = true;
@@ -1083,36 +843,6 @@ extern "C" int ttx_set_integrand_host(ttx_engine *h, ttx_host_fun fun, const dou
 }
 extern "C" int64_t ttx_host_calls(const ttx_engine *h) { return h ? h->host_calls : 0; }
 
-// what hipModuleLoadData accepts: a code-object ELF, or the (plain or compressed) offload bundle of hipcc --genco.  Anything else
-// is refused here, so that arbitrary bytes never reach the runtime's loader
-static bool devfun_image_plausible(const unsigned char *p, size_t nbytes)
-{
-    static const char bundle[] = "__CLANG_OFFLOAD_BUNDLE__";
-    const size_t bl = sizeof(bundle) - 1;
-    auto u64 = [&](size_t at) { uint64_t v; memcpy(&v, p + at, 8); return v; };
-    if (nbytes >= 64 && memcmp(p, "\177ELF", 4) == 0) {
-        // ELF64 header: program and section header tables inside the image
-        if (p[4] != 2) return false;
-        uint16_t phes, phn, shes, shn;
-        memcpy(&phes, p + 54, 2); memcpy(&phn, p + 56, 2); memcpy(&shes, p + 58, 2); memcpy(&shn, p + 60, 2);
-        const uint64_t phoff = u64(32), shoff = u64(40);
-        return phoff <= nbytes && (uint64_t)phes * phn <= nbytes - phoff && shoff <= nbytes && (uint64_t)shes * shn <= nbytes - shoff;
-    }
-    if (nbytes >= bl + 8 && memcmp(p, bundle, bl) == 0) {
-        // uncompressed bundle: entry count, then per entry {offset, size, id length, id}; every entry inside the image
-        const uint64_t ne = u64(bl);
-        if (ne == 0 || ne > 1024) return false;
-        size_t at = bl + 8;
-        for (uint64_t i = 0; i < ne; i++) {
-            if (at + 24 > nbytes) return false;
-            const uint64_t off = u64(at), sz = u64(at + 8), idl = u64(at + 16);
-            if (off > nbytes || sz > nbytes - off || idl > nbytes - at - 24) return false;
-            at += 24 + (size_t)idl;
-        }
-        return true;
-    }
-    return nbytes >= 24 && memcmp(p, "CCOB", 4) == 0;
-}
 // a code object into a DevFun: the module, the three symbols <prefix>{info,slots,list}_<name>, the device copy of par.  `who` names
 // the entry in the messages, `macro` the header macro that generates the symbols.  Nothing of the engine changes here.
 static int devfun_load(const char *who, const char *prefix, const char *macro, const char *what, ttx_engine *h, const void *image, int64_t nbytes, const char *name,
@@ -1167,30 +897,13 @@ extern "C" int ttx_set_integrand_device(ttx_engine *h, const void *image, int64_
     h->dfun = std::move(f);
     return TTX_OK;
 }
-// a code object file into memory
-static int devfun_read_file(const char *who, const char *path, std::vector<unsigned char> &buf)
-{
-    if (!path || !*path) return fail(TTX_EINVAL, "%s: path missing", who);
-    FILE *fp = fopen(path, "rb");
-    if (!fp) return fail(TTX_EINVAL, "%s: cannot read %s: %s", who, path, strerror(errno));
-    unsigned char chunk[65536];
-    size_t got;
-    while ((got = fread(chunk, 1, sizeof chunk, fp)) > 0) {
-        buf.insert(buf.end(), chunk, chunk + got);
-        if (buf.size() > ((size_t)1 << 30)) break;
-    }
-    const bool bad = ferror(fp) != 0;
-    fclose(fp);
-    if (bad) return fail(TTX_EINVAL, "%s: cannot read %s", who, path);
-    if (buf.empty()) return fail(TTX_EINVAL, "%s: %s is empty", who, path);
-    return TTX_OK;
-}
 extern "C" int ttx_set_integrand_device_file(ttx_engine *h, const char *path, const char *name, const double *par, int32_t npar)
 {
     if (!h) return fail(TTX_EINVAL, "ttx_set_integrand_device_file: null handle");
     if (h->cfg.fun_id != TTX_FUN_DEVICE) return fail(TTX_ESTATE, "ttx_set_integrand_device_file: the engine was not created with fun_id = TTX_FUN_DEVICE");
     std::vector<unsigned char> buf;
-    if (int rc = devfun_read_file("ttx_set_integrand_device_file", path, buf)) return rc;
+    std::string text;
+    if (int rc = devfun_read_file("ttx_set_integrand_device_file", path, buf, &text)) return fail(rc, "%s", text.c_str());
     return ttx_set_integrand_device(h, buf.data(), (int64_t)buf.size(), name, par, npar);
 }
 // the loaded integrand at a list of multi-indices, through the code object's list kernel
@@ -2178,10 +1891,14 @@ extern "C" int ttx_from_tt(ttx_engine **out, int32_t d, const int32_t *n, const 
     });
 }
 
-// lib/ttio.f90:10-17 `tthead`: 'TT      ', ver(2)=(1,0), inf(4)=(tt_size,0,0,0), comment*64, i(8) with i(1:2)=(l,m); 128 bytes
-namespace {
-struct TTFileHead { char txt[8]; int32_t ver[2]; int32_t inf[4]; char comment[64]; int32_t i[8]; };
-static_assert(sizeof(TTFileHead) == 128, "stream header is 128 bytes");
+// the resident train of a single-process engine on the host, as the writers of ttx_files.h take it: the cores one after the other
+static int train_to_host(const ttx_engine *h, std::vector<double> &x)
+{
+    size_t sz = 0, off = 0;
+    for (int k = 1; k <= h->d; k++) sz += (size_t)ttx_core_size(h, k);
+    x.resize(sz);
+    for (int k = 1; k <= h->d; k++) { int rc = ttx_get_core(h, k, x.data() + off); if (rc) return rc; off += (size_t)ttx_core_size(h, k); }
+    return TTX_OK;
 }
 extern "C" int ttx_write(const ttx_engine *h, const char *path)
 {
@@ -2190,148 +1907,30 @@ extern "C" int ttx_write(const ttx_engine *h, const char *path)
         ttx_engine *hh = const_cast<ttx_engine *>(h);
         return with_replica(hh, [&](ttx_engine *e) { return hh->wrank == 0 ? ttx_write(e, path) : TTX_OK; });
     }
-    const int d = h->d;
-    size_t sz = 0;
-    for (int k = 1; k <= d; k++) sz += (size_t)h->rfinal[k - 1] * h->n1[k] * h->rfinal[k];
-    if (sz == 0) return fail(TTX_EINVAL, "dtt_write: tt structure has invalid size: 0");      // lib/ttio.f90:60-61
-    std::vector<double> x(sz);
-    size_t off = 0;
-    for (int k = 1; k <= d; k++) { int rc = ttx_get_core(h, k, x.data() + off); if (rc) return rc; off += (size_t)ttx_core_size(h, k); }
-    FILE *f = fopen(path, "wb");
-    if (!f) return fail(TTX_EINVAL, "dtt_write: error opening file: %s", path);                // :85-88
-    TTFileHead hd;
-    memset(&hd, 0, sizeof hd);
-    memcpy(hd.txt, "TT      ", 8);
-    hd.ver[0] = 1; hd.ver[1] = 0; hd.inf[0] = 2048;
-    hd.i[0] = 1; hd.i[1] = d;
-    const int32_t lm[2] = {1, d};
-    bool ok = fwrite(&hd, sizeof hd, 1, f) == 1 && fwrite(lm, sizeof lm, 1, f) == 1;          // :75-76
-    ok = ok && fwrite(&h->n1[1], sizeof(int32_t), d, f) == (size_t)d && fwrite(h->rfinal.data(), sizeof(int32_t), d + 1, f) == (size_t)d + 1;   // :77
-    ok = ok && fwrite(x.data(), sizeof(double), sz, f) == sz;                                 // :78
-    ok = (fclose(f) == 0) && ok;
-    if (!ok) return fail(TTX_EINVAL, "dtt_write: error writing file: %s", path);
+    std::vector<double> x;
+    std::string text;
+    if (int rc = train_to_host(h, x)) return rc;
+    if (int rc = ttfile_write(path, h->d, &h->n1[1], h->rfinal.data(), x.data(), &text)) return fail(rc, "%s", text.c_str());
     return TTX_OK;
-}
-
-// ---- HDF5 layout of lib/utils.f90:8-57 (save_dtt_to_hdf5): group "TT", datasets "modes" (m ints), "ranks" (m+1 ints),
-//      "core_k" (k = 0..m-1) with the Fortran shape (r(k-1), n(k), r(k)) -- i.e. the C dataspace (r(k), n(k), r(k-1)) over the
-//      column-major bytes.  libhdf5 is an optional run-time dependency, resolved with dlopen like librccl.
-namespace {
-typedef int64_t hid_t_; typedef int herr_t_; typedef unsigned long long hsize_t_;
-struct Hdf5Api {
-    void *lib = nullptr;
-    herr_t_ (*open)() = nullptr;
-    hid_t_ (*Fcreate)(const char *, unsigned, hid_t_, hid_t_) = nullptr;
-    hid_t_ (*Fopen)(const char *, unsigned, hid_t_) = nullptr;
-    herr_t_ (*Fclose)(hid_t_) = nullptr;
-    hid_t_ (*Gcreate2)(hid_t_, const char *, hid_t_, hid_t_, hid_t_) = nullptr;
-    herr_t_ (*Gclose)(hid_t_) = nullptr;
-    hid_t_ (*Screate_simple)(int, const hsize_t_ *, const hsize_t_ *) = nullptr;
-    herr_t_ (*Sclose)(hid_t_) = nullptr;
-    hid_t_ (*Dcreate2)(hid_t_, const char *, hid_t_, hid_t_, hid_t_, hid_t_, hid_t_) = nullptr;
-    hid_t_ (*Dopen2)(hid_t_, const char *, hid_t_) = nullptr;
-    hid_t_ (*Dget_space)(hid_t_) = nullptr;
-    int (*Sget_simple_extent_dims)(hid_t_, hsize_t_ *, hsize_t_ *) = nullptr;
-    herr_t_ (*Dwrite)(hid_t_, hid_t_, hid_t_, hid_t_, hid_t_, const void *) = nullptr;
-    herr_t_ (*Dread)(hid_t_, hid_t_, hid_t_, hid_t_, hid_t_, void *) = nullptr;
-    herr_t_ (*Dclose)(hid_t_) = nullptr;
-    herr_t_ (*Eset_auto2)(hid_t_, void *, void *) = nullptr;
-    hid_t_ t_int = -1, t_double = -1;
-};
-Hdf5Api g_h5;
-int hdf5_load()
-{
-    if (g_h5.lib) return TTX_OK;
-    void *L = nullptr;
-    for (const char *nm : {"libhdf5.so", "libhdf5.so.103", "/opt/conda/lib/libhdf5.so", "libhdf5_serial.so"}) if ((L = dlopen(nm, RTLD_NOW | RTLD_LOCAL))) break;
-    if (!L) return fail(TTX_EINVAL, "save_dtt_to_hdf5: libhdf5.so not found (%s)", dlerror());
-#define H5_(f, name) *(void **)(&g_h5.f) = dlsym(L, name); if (!g_h5.f) return fail(TTX_EINVAL, "libhdf5.so lacks %s", name);
-    H5_(open, "H5open") H5_(Fcreate, "H5Fcreate") H5_(Fopen, "H5Fopen") H5_(Fclose, "H5Fclose") H5_(Gcreate2, "H5Gcreate2") H5_(Gclose, "H5Gclose")
-    H5_(Screate_simple, "H5Screate_simple") H5_(Sclose, "H5Sclose") H5_(Dcreate2, "H5Dcreate2") H5_(Dopen2, "H5Dopen2") H5_(Dget_space, "H5Dget_space")
-    H5_(Sget_simple_extent_dims, "H5Sget_simple_extent_dims") H5_(Dwrite, "H5Dwrite") H5_(Dread, "H5Dread") H5_(Dclose, "H5Dclose") H5_(Eset_auto2, "H5Eset_auto2")
-#undef H5_
-    if (g_h5.open() < 0) return fail(TTX_EINVAL, "H5open failed");
-    hid_t_ *ti = (hid_t_ *)dlsym(L, "H5T_NATIVE_INT_g"), *td = (hid_t_ *)dlsym(L, "H5T_NATIVE_DOUBLE_g");
-    if (!ti || !td) return fail(TTX_EINVAL, "libhdf5.so lacks the native type ids");
-    g_h5.t_int = *ti; g_h5.t_double = *td;
-    g_h5.Eset_auto2(0, nullptr, nullptr);                      // errors are reported through return codes here
-    g_h5.lib = L;
-    return TTX_OK;
-}
 }
 extern "C" int ttx_write_hdf5(const ttx_engine *h, const char *path)
 {
     if (!h || !path || !h->ran) return fail(TTX_ESTATE, "save_dtt_to_hdf5: no tensor train to write");
     if (h->W > 1) return fail(TTX_EINVAL, "save_dtt_to_hdf5: single-process engines only");
-    int rc = hdf5_load();
-    if (rc) return rc;
-    const int d = h->d;
-    const hid_t_ f = g_h5.Fcreate(path, 2u /* H5F_ACC_TRUNC */, 0, 0);
-    if (f < 0) return fail(TTX_EINVAL, "save_dtt_to_hdf5: cannot create %s", path);
-    const hid_t_ grp = g_h5.Gcreate2(f, "TT", 0, 0, 0);
-    bool ok = grp >= 0;
-    auto put = [&](const char *name, int rank, const hsize_t_ *dims, hid_t_ type, const void *buf) {
-        const hid_t_ sp = g_h5.Screate_simple(rank, dims, nullptr);
-        const hid_t_ ds = (sp >= 0) ? g_h5.Dcreate2(grp, name, type, sp, 0, 0, 0) : -1;
-        if (ds < 0 || g_h5.Dwrite(ds, type, 0, 0, 0, buf) < 0) ok = false;
-        if (ds >= 0) g_h5.Dclose(ds);
-        if (sp >= 0) g_h5.Sclose(sp);
-    };
-    if (ok) {
-        hsize_t_ d1 = (hsize_t_)d;
-        put("modes", 1, &d1, g_h5.t_int, &h->n1[1]);                                 // utils.f90:25-30
-        d1 = (hsize_t_)d + 1;
-        put("ranks", 1, &d1, g_h5.t_int, h->rfinal.data());                          // :32-37
-        std::vector<double> x;
-        for (int k = 1; k <= d && ok; k++) {                                         // :40-51
-            x.resize((size_t)ttx_core_size(h, k));
-            if ((rc = ttx_get_core(h, k, x.data()))) { ok = false; break; }
-            const hsize_t_ d3[3] = {(hsize_t_)h->rfinal[k], (hsize_t_)h->n1[k], (hsize_t_)h->rfinal[k - 1]};   // Fortran (r0, n, r1) reversed
-            char nm[32]; snprintf(nm, sizeof nm, "core_%d", k - 1);
-            put(nm, 3, d3, g_h5.t_double, x.data());
-        }
-    }
-    if (grp >= 0) g_h5.Gclose(grp);
-    g_h5.Fclose(f);
-    if (!ok) return rc ? rc : fail(TTX_EINVAL, "save_dtt_to_hdf5: error writing %s", path);
+    std::vector<double> x;
+    std::string text;
+    if (int rc = train_to_host(h, x)) return rc;
+    if (int rc = hdf5_write_tt(path, h->d, &h->n1[1], h->rfinal.data(), x.data(), &text)) return fail(rc, "%s", text.c_str());
     return TTX_OK;
 }
 extern "C" int ttx_read_hdf5(ttx_engine **out, const char *path, int32_t device)
 {
     if (!out || !path) return fail(TTX_EINVAL, "ttx_read_hdf5: null argument");
     *out = nullptr;
-    int rc = hdf5_load();
-    if (rc) return rc;
-    const hid_t_ f = g_h5.Fopen(path, 0u /* H5F_ACC_RDONLY */, 0);
-    if (f < 0) return fail(TTX_EINVAL, "ttx_read_hdf5: cannot open %s", path);
-    auto dims_of = [&](const char *name, int want, hsize_t_ *dims) -> hid_t_ {
-        const hid_t_ ds = g_h5.Dopen2(f, name, 0);
-        if (ds < 0) return -1;
-        const hid_t_ sp = g_h5.Dget_space(ds);
-        const int nd = (sp >= 0) ? g_h5.Sget_simple_extent_dims(sp, dims, nullptr) : -1;
-        if (sp >= 0) g_h5.Sclose(sp);
-        if (nd != want) { g_h5.Dclose(ds); return -1; }
-        return ds;
-    };
-    hsize_t_ dm[3];
     std::vector<int32_t> n, r;
     std::vector<double> cores;
-    bool ok = true;
-    hid_t_ ds = dims_of("/TT/modes", 1, dm);
-    if (ds < 0) ok = false;
-    else { n.resize(dm[0]); ok = g_h5.Dread(ds, g_h5.t_int, 0, 0, 0, n.data()) >= 0; g_h5.Dclose(ds); }
-    if (ok) { ds = dims_of("/TT/ranks", 1, dm); if (ds < 0 || dm[0] != n.size() + 1) ok = false; if (ds >= 0) { r.resize(dm[0]); ok = ok && g_h5.Dread(ds, g_h5.t_int, 0, 0, 0, r.data()) >= 0; g_h5.Dclose(ds); } }
-    for (size_t k = 0; ok && k < n.size(); k++) {
-        char nm[40]; snprintf(nm, sizeof nm, "/TT/core_%zu", k);
-        ds = dims_of(nm, 3, dm);
-        if (ds < 0 || (int)dm[0] != r[k + 1] || (int)dm[1] != n[k] || (int)dm[2] != r[k]) { ok = false; if (ds >= 0) g_h5.Dclose(ds); break; }
-        const size_t off = cores.size(), sz = (size_t)r[k] * n[k] * r[k + 1];
-        cores.resize(off + sz);
-        ok = g_h5.Dread(ds, g_h5.t_double, 0, 0, 0, cores.data() + off) >= 0;
-        g_h5.Dclose(ds);
-    }
-    g_h5.Fclose(f);
-    if (!ok) return fail(TTX_EINVAL, "ttx_read_hdf5: %s does not hold a tensor train in the layout of lib/utils.f90", path);
+    std::string text;
+    if (int rc = hdf5_read_tt(path, n, r, cores, &text)) return fail(rc, "%s", text.c_str());
     return ttx_from_tt(out, (int32_t)n.size(), n.data(), r.data(), cores.data(), device);
 }
 
@@ -2339,30 +1938,11 @@ extern "C" int ttx_read(ttx_engine **out, const char *path, int32_t device)
 {
     if (!out || !path) return fail(TTX_EINVAL, "dtt_read: null argument");
     *out = nullptr;
-    FILE *f = fopen(path, "rb");
-    if (!f) return fail(TTX_EINVAL, "dtt_read: file not exist: %s", path);                     // lib/ttio.f90:210-214
-    TTFileHead hd;
-    int32_t lm[2];
-    auto bad = [&](const char *what) { fclose(f); return fail(TTX_EINVAL, "dtt_read: %s: %s", what, path); };
-    if (fread(&hd, sizeof hd, 1, f) != 1) return bad("error reading header");                // :276-279
-    if (hd.txt[0] != 'T' || hd.txt[1] != 'T') return bad("not TT header in file");            // :236-240
-    if (hd.ver[0] != 1) return bad("not correct version of TT file");                         // :241-245
-    if (fread(lm, sizeof lm, 1, f) != 1) return bad("error reading lm");
-    const int l = lm[0], m = lm[1];
-    if (l < 1 || m < l || m > 2048) return bad("read strange l,m");                           // :249-251, tt_size
-    const int d = m - l + 1;
-    std::vector<int32_t> n(d), r(d + 1);
-    if (fread(n.data(), sizeof(int32_t), d, f) != (size_t)d || fread(r.data(), sizeof(int32_t), d + 1, f) != (size_t)d + 1) return bad("error reading nr");
-    size_t sz = 0;
-    for (int k = 0; k < d; k++) {
-        if (n[k] < 1 || r[k] < 1 || r[k + 1] < 1 || n[k] > 32000 || r[k] > 128 || r[k + 1] > 128) return bad("tt structure has invalid size");
-        sz += (size_t)r[k] * n[k] * r[k + 1];
-    }
-    std::vector<double> x(sz);
-    if (fread(x.data(), sizeof(double), sz, f) != sz) return bad("error reading cores");
-    fclose(f);
-    // the device engine numbers cores 1..d; a file with l > 1 keeps its shape but loses the offset (every driver has l = 1)
-    return ttx_from_tt(out, d, n.data(), r.data(), x.data(), device);
+    std::vector<int32_t> n, r;
+    std::vector<double> x;
+    std::string text;
+    if (int rc = ttfile_read(path, n, r, x, &text)) return fail(rc, "%s", text.c_str());
+    return ttx_from_tt(out, (int32_t)n.size(), n.data(), r.data(), x.data(), device);
 }
 
 // per-call device temporaries: released on every path out of the function that holds the guard
@@ -3101,7 +2681,8 @@ extern "C" int ttx_set_integrand_trains_device_file(ttx_engine *h, int32_t m, tt
     if (!h) return fail(TTX_EINVAL, "%s: null handle", who);
     if (h->cfg.fun_id != TTX_FUN_TRAINS) return fail(TTX_ESTATE, "%s: the engine was not created with fun_id = TTX_FUN_TRAINS", who);
     std::vector<unsigned char> img;
-    if (int rc = devfun_read_file(who, path, img)) return rc;
+    std::string text;
+    if (int rc = devfun_read_file(who, path, img, &text)) return fail(rc, "%s", text.c_str());
     return ttx_set_integrand_trains_device(h, m, x, img.data(), (int64_t)img.size(), name, par, npar);
 }
 extern "C" int ttx_trainfun_last(const ttx_engine *h, double *ms, int64_t *launches, int64_t *elements)
