@@ -12,9 +12,12 @@ from ttcross_amd import engine as E
 pytestmark = pytest.mark.gpu
 
 
-def _run_both(s, r, piv, nproc=1):
+def _run_both(s, r, piv, nproc=1, path=None):
     tt = E.TTCross(s["n"], s["fun_id"], s["par"], r, pivoting=piv, accuracy=s["acc"], quad=s["quad"], tru=s["tru"],
-                   aux=s["aux"], nproc=nproc).run()
+                   aux=s["aux"], nproc=nproc)
+    if path is not None:
+        assert tt.sweep_path() == path
+    tt.run()
     oo = O.dmrgg(s["n"], s["fun_id"], s["par"], r, piv=piv, accuracy=s["acc"], quad=s["quad"], tru=s["tru"], aux=s["aux"],
                  nproc=nproc)
     return tt, oo
@@ -598,14 +601,19 @@ def test_zquad_complex_weights():
         assert abs(got[k] - want) <= 1e-12 * abs(want)
 
 
+# the last two: piv = 1 and ranks above 32 (full-width triangular solves) on every path; for them the path asked for must be the one
+# that runs (a silent fall-back to the chain would hide the other two)
+PATH_CHECKED = [("c", 15, 2, 3, 1, 1), ("c", 6, 9, 48, 1, 4)]
+
+
 @pytest.mark.parametrize("fused", ["chain", "fused", "cluster"])
-@pytest.mark.parametrize("kind,m,n,r,piv,nproc", [("c", 16, 51, 32, 2, 1), ("c", 64, 51, 32, 2, 8), ("c", 8, 25, 12, 3, 2), ("c", 5, 17, 8, 0, 1), ("c", 16, 33, 24, 0, 5)])
+@pytest.mark.parametrize("kind,m,n,r,piv,nproc", [("c", 16, 51, 32, 2, 1), ("c", 64, 51, 32, 2, 8), ("c", 8, 25, 12, 3, 2), ("c", 5, 17, 8, 0, 1), ("c", 16, 33, 24, 0, 5)] + PATH_CHECKED)
 def test_both_sweep_paths_bit_exact(monkeypatch, fused, kind, m, n, r, piv, nproc):
     """The three sweep implementations -- multi-kernel chain, one workgroup per group (ttx_fused.h), a cluster of
     workgroups per group (ttx_cluster.h) -- selected with TTX_SWEEP, each bit for bit against the oracle."""
     monkeypatch.setenv("TTX_SWEEP", fused)
     s = D.ising_setup(kind, m, n)
-    tt, oo = _run_both(s, r, piv, nproc=nproc)
+    tt, oo = _run_both(s, r, piv, nproc=nproc, path=fused if (kind, m, n, r, piv, nproc) in PATH_CHECKED else None)
     assert np.array_equal(tt.tapes()[:, 1:tt.d], oo["tapes"][:, 1:tt.d])
     assert [a["val"] for a in tt.sweeps()] == [b["val"] for b in oo["sweeps"]]
     assert [a["neval"] for a in tt.sweeps()] == [b["neval"] for b in oo["sweeps"]]

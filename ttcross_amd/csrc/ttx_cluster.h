@@ -253,10 +253,9 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
     int *ZK = (int *)(ldsinv ? GU + (size_t)RM * RM : GL);   // [nsteps][2][RM]
     int *ZN = ZK + (size_t)nsteps * 2 * RM;                  // [nsteps][2]
     for (int x = tid; x < P.npar; x += CB) par[x] = P.par[x];
-    if (cb == 0 && tid == 0) {                         // sweep start, :325-327
-        int *rr = P.rr + (size_t)g * (m + 2);
-        for (int s = 0; s <= m; s++) rr[s] = r[s];
-    }
+    // (sweep_start also puts -1 into gs.pivotmax / gs.pivotmin, which this kernel keeps in registers and writes at its end: they
+    // differ from before only after an aborted launch, whose run is replayed from k_reset on the chain path)
+    if (cb == 0 && tid == 0) sweep_start(P, g);
     __syncthreads();
     if (zkeep) {
         int *TMP = (int *)XL;                          // XL is staged later; free scratch for now: [nsteps][2][RM]
@@ -394,30 +393,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
             if (tid < ZN[2 * b]) zc[tid] = ((kc[tid] & 0xffff) - 1) + r0 * ((kc[tid] >> 16) - 1) + 1;
             if (tid < ZN[2 * b + 1]) zr[tid] = ((kr[tid] & 0xffff) - 1) + n2 * ((kr[tid] >> 16) - 1) + 1;
             __syncthreads();
-        } else {
-        const int *vp = vip_ptr(P, g, p, first);
-        if (tid < r1) {
-            zc[tid] = (vp[4 * tid + 0] - 1) + r0 * (vp[4 * tid + 1] - 1) + 1;
-            zr[tid] = (vp[4 * tid + 2] - 1) + n2 * (vp[4 * tid + 3] - 1) + 1;
-        }
-        __syncthreads();
-        if (tid < r1) {
-            int a = zc[tid], b = zr[tid], ra = 0, rb = 0;
-            for (int u = 0; u < r1; u++) { ra += (zc[u] < a) || (zc[u] == a && u < tid); rb += (zr[u] < b) || (zr[u] == b && u < tid); }
-            zcs[ra] = a; zrs[rb] = b;
-        }
-        __syncthreads();
-        if (tid < r1) { keepc[tid] = (tid == 0) || (zcs[tid] != zcs[tid - 1]); keepr[tid] = (tid == 0) || (zrs[tid] != zrs[tid - 1]); }
-        __syncthreads();
-        if (tid < r1) {
-            int pc = 0, pr = 0;
-            for (int u = 0; u < tid; u++) { pc += keepc[u]; pr += keepr[u]; }
-            if (keepc[tid]) zc[pc] = zcs[tid];
-            if (keepr[tid]) zr[pr] = zrs[tid];
-            if (tid == r1 - 1) { nzc = pc + keepc[tid]; nzr = pr + keepr[tid]; }
-        }
-        __syncthreads();
-        }
+        } else bond_zero_lists(vip_ptr(P, g, p, first), r1, r0, n2, tid, zc, zr, zcs, zrs, keepc, keepr, &nzc, &nzr);
         CST(1);
         const int Kc = r0 * n1 - nzc, Kr = n2 * r2 - nzr;
         // (waves 2 and 3 store their segment while waves 0 and 1 run the prefix chains; without zkeep the lengths are known only
@@ -523,6 +499,9 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         const bool slot_on = (lane < NB * (CB / 64)) && ((lane & (CB / 64 - 1)) < wact(lane / (CB / 64)));      // lane = record slot
         if (rook_active) {
         for (int h = 0; h < H && !done; h++) {
+            // (the rook turn, the traffic count and the pivot taking below are this kernel's own copies of rook_turn,
+            // halfstep_traffic and take_pivot of ttx_bondstep.h: through the shared functions the <false, false> instance
+            // needs 262 registers instead of the 256 it has room for.  A change of those rules is made here as well.)
             const bool iscol = (P.piv == 0) ? (h == 0) : (((h + (dir == 2 ? 1 : 0)) & 1) == 0);
             const int nf = iscol ? r0 * n1 : n2 * r2;
             const int nsl = iscol ? r0 * nj : nk * r2;
@@ -680,7 +659,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         CST(10);
         // ---- acceptance and in-place append (:598-758): every block appends its own slice ----
         int *tape = P.tape + ((size_t)g * (m + 2) + p) * 4;
-        const bool upd = (fabs(pivot) > P.small_element * amax) && (fabs(pivot) > P.small_pivot * pivotmax_prev);
+        const bool upd = accept_pivot(pivot, amax, pivotmax_prev, P.small_element, P.small_pivot);
         if (!upd) {
             if (cb == 0 && tid == 0) { tape[0] = tape[1] = tape[2] = tape[3] = -1; P.upd[(size_t)g * (m + 2) + p] = 0; }
         } else {
@@ -732,14 +711,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                 for (int base = wv * pk; base < nj; base += (CB / 64) * pk) {
                     const int jl = base + sub, j = jlo + jl;
                     const bool on = (jl < nj) && (l < r0);
-                    const double a = on ? acol[l + r0 * jl] : 0.0;
-                    double tmp = 0.0, xf = 0.0;
-                    for (int s = 0; s < r0; s++) {
-                        const double cand = (s == 0) ? a : a + (-1.0) * tmp;
-                        const double xsv = __shfl(cand, s, lw);
-                        if (l == s) xf = xsv;
-                        if (l > s && l < r0) tmp = tmp + xsv * gL[l * l + s];
-                    }
+                    const double xf = wave_solve_L(gL, r0, on ? acol[l + r0 * jl] : 0.0, l, lw);
                     if (on) Wp[j + (size_t)NM * r1 + P.SW * l] = xf;
                 }
             }
@@ -749,33 +721,19 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                 const double *gU = ldsinv ? GU : inv_ptr(P, g, p + 1, first);
                 double *Cq = core_ptr(P, P.col, g, p + 1, first);
                 const int pk = (r2 <= 32) ? 2 : 1, lw = 64 / pk, l = lane & (lw - 1), sub = lane / lw;
-                const double rdg = (l < r2) ? 1.0 / gU[(l + 1) * (l + 1) - 1] : 0.0;   // 1/U(s,s) held by lane s
+                const double rdg = wave_solve_rdg(gU, r2, l);
                 for (int base = wv * pk; base < nk; base += (CB / 64) * pk) {
                     const int kl = base + sub, k = klo + kl;
                     const bool on = (kl < nk) && (l < r2);
-                    double y = on ? arow[kl + nk * l] : 0.0;
-                    for (int s = 0; s < r2; s++) {
-                        const double cand = rdg * y;          // only lane s's product is used: (1.0 / U(s,s)) * y_s
-                        const double ys = __shfl(cand, s, lw);
-                        if (l == s) y = ys;
-                        if (l > s && l < r2) y = y + (-gU[l * l + l + s]) * ys;
-                    }
+                    const double y = wave_solve_U(gU, r2, on ? arow[kl + nk * l] : 0.0, rdg, l, lw);
                     if (on) Cq[r1 + (size_t)RM * k + P.SS * l] = y;
                 }
             }
             CST(13);
             // role E: index tables, pivot set, scalars (:604-635)
             if (cb == 0) {
-                short *Ln = L_ptr(P, g, p, first), *Rn = R_ptr(P, g, p, first);
-                for (int x = tid; x < p; x += CB) Ln[(size_t)x * RM + r1] = (x < p - 1) ? Lt[(size_t)x * RM + i0] : (short)(j0 + 1);
-                for (int x = tid; x < m - p; x += CB) Rn[(size_t)x * RM + r1] = (x == 0) ? (short)(k0 + 1) : Rt[(size_t)(x - 1) * RM + q0];
-                if (tid == 0) {
-                    gI[(r1 + 1) * (r1 + 1) - 1] = pivot;
-                    int *vq = vip_ptr(P, g, p, first) + 4 * r1;
-                    vq[0] = tape[0] = ii; vq[1] = tape[1] = jj; vq[2] = tape[2] = kk; vq[3] = tape[3] = qq;
-                    P.upd[(size_t)g * (m + 2) + p] = 1;
-                    r[p] = r1 + 1;                                                      // :752
-                }
+                append_tables(P, g, p, first, r1, ii, jj, kk, qq, tid, CB);
+                if (tid == 0) append_scalars(P, g, p, first, r1, ii, jj, kk, qq, pivot);
             }
             if (zkeep && wv < 2) {                     // keep the sorted distinct lists of this bond current:
                 const int b = p - first;               // wave 0 inserts the pivot row, wave 1 the pivot column (RM <= 64)
@@ -790,9 +748,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                     if (lane == 0) { kl[pos] = key; ZN[2 * b + wv] = nl + 1; }
                 }
             }
-            const double ap = fabs(pivot);
-            pivotmax = (pivotmax < 0.0) ? ap : fmax(pivotmax, ap);
-            pivotmin = (pivotmin < 0.0) ? ap : fmin(pivotmin, ap);
+            pivot_range(pivotmax, pivotmin, fabs(pivot));
         }
         CST(14);
         // end of the bond step: appends and the new rank become visible to the whole cluster (every block read r[] of

@@ -280,30 +280,17 @@ __global__ __launch_bounds__(64) void k_halfstep_de(DevProb P, int h, int dir, i
     if (lane == 0) { cur = gs.S[h]; resolve_state(cur, gs.Pt[(h + 1) & 1]); }
     __syncthreads();
     if (!cur.active || cur.done) { if (blockIdx.x == 0 && lane == 0) gs.S[h + 1] = cur; return; }
-    const bool iscol = (mode == 1 || mode == 2) ? (h == 0) : (((h + (dir == 2 ? 1 : 0)) & 1) == 0);    // :517,550
+    const RookTurn turn = rook_turn(P.piv, mode, h, dir, UNI(cur.crs), UNI(cur.havecol), UNI(cur.haverow));
+    const bool iscol = turn.iscol, resid = turn.resid;    // :517,550 / :534,567
     // what steers the control flow is made wave-uniform explicitly (values read from LDS / global memory are per-lane
     // registers to the compiler: loop counters and branches would otherwise run on the vector unit)
-#define UNI(x) __builtin_amdgcn_readfirstlane(x)
     const int p = UNI(cur.p), r0 = UNI(cur.r0), r1 = UNI(cur.r1), r2 = UNI(cur.r2), n1 = UNI(cur.n1), n2 = UNI(cur.n2), first = UNI(gs.first);
     const int c_ii = UNI(cur.ii), c_jj = UNI(cur.jj), c_kk = UNI(cur.kk), c_qq = UNI(cur.qq);
     const int nf = iscol ? r0 * n1 : n2 * r2;
     const int nv = iscol ? r0 : r2, nm = iscol ? n1 : n2, nch = (nm + 63) >> 6;
     const int npart = nv * nch;
     const int w = blockIdx.x;
-    const int crs = UNI(cur.crs) + 1;
-    const int havecol = UNI(cur.havecol) | (iscol ? 1 : 0), haverow = UNI(cur.haverow) | (iscol ? 0 : 1);
-    const int done = (mode == 1 || mode == 2) ? (h == 1) : (havecol && haverow && (crs >= 2 * P.piv));   // :534 / :567
-    const bool resid = (mode == 0) && !done;
-    if (w == 0 && lane == 0) {
-        StepState nx = cur;
-        nx.crs = crs; nx.havecol = havecol; nx.haverow = haverow; nx.done = done;
-        nx.pending = resid ? (iscol ? 1 : 2) : 0;
-        nx.npart = npart;
-        gs.S[h + 1] = nx;
-        if (mode != 2) gs.neval += nf;                                        // :527 / :560 / :509
-        gs.bytes_half += resid ? 8.0 * ((double)nf * r1 + r1 + 2.0 * nf) : 8.0 * nf;
-        gs.n_resid += resid ? 1 : 0;
-    }
+    if (w == 0 && lane == 0) halfstep_publish(gs, h, cur, turn, mode, nf, r1, npart);
     if (w >= npart) return;
     const int pv = w / nch, vmode = (w - pv * nch) * 64 + lane;        // varying pivot, mode index (0-based)
     const bool live = vmode < nm;
@@ -386,9 +373,7 @@ __global__ __launch_bounds__(64) void k_halfstep_de(DevProb P, int h, int dir, i
         if (lane == 0) { Partial pr; pr.absmax = ab; pr.val = bb; pr.idx = bi; pr.pad = 0; gs.Pt[h & 1][w] = pr; }
     }
 }
-#undef UNI
 
-#define UNI(x) __builtin_amdgcn_readfirstlane(x)
 // the bond-spanning tail of a row as de_run, ended where every lane's running product has reached the unit cut (the factors of a
 // lane that is already there are exactly 1)
 __device__ __forceinline__ void de_run_cut(double &a, double u, double x2, const double *xr, int B)
@@ -537,30 +522,17 @@ __global__ __launch_bounds__(64) void k_halfstep_dec(DevProb P, int h, int dir, 
     if (lane == 0) { cur = gs.S[h]; resolve_state(cur, gs.Pt[(h + 1) & 1]); }
     __syncthreads();
     if (!cur.active || cur.done) { if (blockIdx.x == 0 && lane == 0) gs.S[h + 1] = cur; return; }
-    const bool iscol = (mode == 1 || mode == 2) ? (h == 0) : (((h + (dir == 2 ? 1 : 0)) & 1) == 0);    // :517,550
+    const RookTurn turn = rook_turn(P.piv, mode, h, dir, UNI(cur.crs), UNI(cur.havecol), UNI(cur.haverow));
+    const bool iscol = turn.iscol, resid = turn.resid;    // :517,550 / :534,567
     // what steers the control flow is made wave-uniform explicitly (values read from LDS / global memory are per-lane
     // registers to the compiler: loop counters and branches would otherwise run on the vector unit)
-#define UNI(x) __builtin_amdgcn_readfirstlane(x)
     const int p = UNI(cur.p), r0 = UNI(cur.r0), r1 = UNI(cur.r1), r2 = UNI(cur.r2), n1 = UNI(cur.n1), n2 = UNI(cur.n2), first = UNI(gs.first);
     const int c_ii = UNI(cur.ii), c_jj = UNI(cur.jj), c_kk = UNI(cur.kk), c_qq = UNI(cur.qq);
     const int nf = iscol ? r0 * n1 : n2 * r2;
     const int nv = iscol ? r0 : r2, nm = iscol ? n1 : n2, nch = (nm + 63) >> 6;
     const int npart = nv * nch;
     const int w = blockIdx.x;
-    const int crs = UNI(cur.crs) + 1;
-    const int havecol = UNI(cur.havecol) | (iscol ? 1 : 0), haverow = UNI(cur.haverow) | (iscol ? 0 : 1);
-    const int done = (mode == 1 || mode == 2) ? (h == 1) : (havecol && haverow && (crs >= 2 * P.piv));   // :534 / :567
-    const bool resid = (mode == 0) && !done;
-    if (w == 0 && lane == 0) {
-        StepState nx = cur;
-        nx.crs = crs; nx.havecol = havecol; nx.haverow = haverow; nx.done = done;
-        nx.pending = resid ? (iscol ? 1 : 2) : 0;
-        nx.npart = npart;
-        gs.S[h + 1] = nx;
-        if (mode != 2) gs.neval += nf;                                        // :527 / :560 / :509
-        gs.bytes_half += resid ? 8.0 * ((double)nf * r1 + r1 + 2.0 * nf) : 8.0 * nf;
-        gs.n_resid += resid ? 1 : 0;
-    }
+    if (w == 0 && lane == 0) halfstep_publish(gs, h, cur, turn, mode, nf, r1, npart);
     if (w >= npart) return;
     const int pv = w / nch, vmode = (w - pv * nch) * 64 + lane;        // varying pivot, mode index (0-based)
     const bool live = vmode < nm;
@@ -596,7 +568,6 @@ __global__ __launch_bounds__(64) void k_halfstep_dec(DevProb P, int h, int dir, 
         if (lane == 0) { Partial pr; pr.absmax = ab; pr.val = bb; pr.idx = bi; pr.pad = 0; gs.Pt[h & 1][w] = pr; }
     }
 }
-#undef UNI
 
 // b-part (id 2) and weights (test_crs_ising.f90:197-218) from per-dimension value arrays xv / wv (0-based dims)
 __device__ __forceinline__ double de_finish_vals(int id, double a, int m, const double *xv, const double *wv)
@@ -677,26 +648,14 @@ __global__ __launch_bounds__(64 * DE5_W) void k_halfstep_de5(DevProb P, int h, i
     if (tid == 0) { cur = gs.S[h]; resolve_state(cur, gs.Pt[(h + 1) & 1]); giveup = 0; }
     __syncthreads();
     if (!cur.active || cur.done) { if (blockIdx.x == 0 && tid == 0) gs.S[h + 1] = cur; return; }
-    const bool iscol = (mode == 1 || mode == 2) ? (h == 0) : (((h + (dir == 2 ? 1 : 0)) & 1) == 0);    // :517,550
+    const RookTurn turn = rook_turn(P.piv, mode, h, dir, cur.crs, cur.havecol, cur.haverow);
+    const bool iscol = turn.iscol, resid = turn.resid;    // :517,550 / :534,567
     const int p = cur.p, r0 = cur.r0, r1 = cur.r1, r2 = cur.r2, n1 = cur.n1, n2 = cur.n2, first = gs.first;
     const int nf = iscol ? r0 * n1 : n2 * r2;
     const int nv = iscol ? r0 : r2, nm = iscol ? n1 : n2, nch = (nm + 63) >> 6;
     const int npart = nv * nch;
     const int w = blockIdx.x;
-    const int crs = cur.crs + 1;
-    const int havecol = cur.havecol | (iscol ? 1 : 0), haverow = cur.haverow | (iscol ? 0 : 1);
-    const int done = (mode == 1 || mode == 2) ? (h == 1) : (havecol && haverow && (crs >= 2 * P.piv));   // :534 / :567
-    const bool resid = (mode == 0) && !done;
-    if (w == 0 && tid == 0) {
-        StepState nx = cur;
-        nx.crs = crs; nx.havecol = havecol; nx.haverow = haverow; nx.done = done;
-        nx.pending = resid ? (iscol ? 1 : 2) : 0;
-        nx.npart = npart;
-        gs.S[h + 1] = nx;
-        if (mode != 2) gs.neval += nf;                                        // :527 / :560 / :509
-        gs.bytes_half += resid ? 8.0 * ((double)nf * r1 + r1 + 2.0 * nf) : 8.0 * nf;
-        gs.n_resid += resid ? 1 : 0;
-    }
+    if (w == 0 && tid == 0) halfstep_publish(gs, h, cur, turn, mode, nf, r1, npart);
     if (w >= npart) return;
     const int pv = w / nch, vmode = (w - pv * nch) * 64 + lane;
     const bool live = vmode < nm;
@@ -1056,37 +1015,24 @@ __global__ __launch_bounds__(64 * (4 * NBK + 2)) void k_halfstep_det(DevProb P, 
     constexpr int ND = 4 * NBK, CHS = ND * 4, NT_ = 64 * (ND + 2);
     // everything that steers the control flow is made wave-uniform explicitly (values read from LDS / global memory are
     // per-lane registers to the compiler: loop counters and branches would otherwise run on the vector unit)
-#define UNI(x) __builtin_amdgcn_readfirstlane(x)
     const int g = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = UNI(tid >> 6), m = P.d;
     GroupState &gs = P.gs[g];
     if (tid == 0) { cur = gs.S[h]; resolve_state(cur, gs.Pt[(h + 1) & 1]); }
     __syncthreads();
     if (!cur.active || cur.done) { if (blockIdx.x == 0 && tid == 0) gs.S[h + 1] = cur; return; }
-    const bool iscol = (mode == 1 || mode == 2) ? (h == 0) : (((h + (dir == 2 ? 1 : 0)) & 1) == 0);    // :517,550
+    const RookTurn turn = rook_turn(P.piv, mode, h, dir, UNI(cur.crs), UNI(cur.havecol), UNI(cur.haverow));
+    const bool iscol = turn.iscol, resid = turn.resid;    // :517,550 / :534,567
     const int p = UNI(cur.p), r0 = UNI(cur.r0), r1 = UNI(cur.r1), r2 = UNI(cur.r2), n1 = UNI(cur.n1), n2 = UNI(cur.n2), first = UNI(gs.first);
     const int c_ii = UNI(cur.ii), c_jj = UNI(cur.jj), c_kk = UNI(cur.kk), c_qq = UNI(cur.qq);
     const int nf = iscol ? r0 * n1 : n2 * r2;
     const int nv = iscol ? r0 : r2, nm = iscol ? n1 : n2, nch = (nm + 63) >> 6;
     const int npart = nv * nch;
     const int w = blockIdx.x;
-    const int crs = UNI(cur.crs) + 1;
-    const int havecol = UNI(cur.havecol) | (iscol ? 1 : 0), haverow = UNI(cur.haverow) | (iscol ? 0 : 1);
-    const int done = (mode == 1 || mode == 2) ? (h == 1) : (havecol && haverow && (crs >= 2 * P.piv));   // :534 / :567
-    const bool resid = (mode == 0) && !done;
     if (npart > (int)gridDim.x) {       // the host sized the grid from its bound on the ranks: never expected; the run is repeated without teams
         if (w == 0 && tid == 0) { atomicAdd(&P.ctl[3], 1); P.ctl[0] = 1; }
         return;
     }
-    if (w == 0 && tid == 0) {
-        StepState nx = cur;
-        nx.crs = crs; nx.havecol = havecol; nx.haverow = haverow; nx.done = done;
-        nx.pending = resid ? (iscol ? 1 : 2) : 0;
-        nx.npart = npart;
-        gs.S[h + 1] = nx;
-        if (mode != 2) gs.neval += nf;                                        // :527 / :560 / :509
-        gs.bytes_half += resid ? 8.0 * ((double)nf * r1 + r1 + 2.0 * nf) : 8.0 * nf;
-        gs.n_resid += resid ? 1 : 0;
-    }
+    if (w == 0 && tid == 0) halfstep_publish(gs, h, cur, turn, mode, nf, r1, npart);
     if (w >= npart) return;
     const int pv = w / nch, vmode = (w - pv * nch) * 64 + lane;        // varying pivot, mode index (0-based)
     const bool live = vmode < nm;
@@ -1311,4 +1257,3 @@ __global__ __launch_bounds__(64 * (4 * NBK + 2)) void k_halfstep_det(DevProb P, 
     }
     DET_ACC(9);
 }
-#undef UNI

@@ -73,11 +73,7 @@ __global__ __launch_bounds__(FB) void k_sweep_fused(DevProb P, int dir, int nste
     double *xs = arow + (size_t)RM * NM;               // RM
     int *lot = (int *)(xs + ((RM + 1) & ~1));          // 4 * nlotmax
     for (int x = tid; x < P.npar; x += FB) par[x] = P.par[x];
-    if (tid == 0) {                                    // sweep start, :325-327
-        gs.pivotmax = -1.0; gs.pivotmin = -1.0;
-        int *rr = P.rr + (size_t)g * (m + 2);
-        for (int s = 0; s <= m; s++) rr[s] = r[s];
-    }
+    if (tid == 0) sweep_start(P, g);
     __syncthreads();
     double amax = gs.amax, pivotmax = gs.pivotmax, pivotmin = gs.pivotmin;
     const double pivotmax_prev = gs.pivotmax_prev;
@@ -108,28 +104,7 @@ __global__ __launch_bounds__(FB) void k_sweep_fused(DevProb P, int dir, int nste
         if (tid == 32) sA[0] = ttx_minstd_pow(2 * rngpos + 1);
         if (tid == 33) sA[1] = ttx_minstd_pow(2 * (rngpos + nlot) + 1);
         const unsigned long long bil = ttx_minstd_pow(2ull * tid);
-        const int *vp = vip_ptr(P, g, p, first);
-        if (tid < r1) {
-            zc[tid] = (vp[4 * tid + 0] - 1) + r0 * (vp[4 * tid + 1] - 1) + 1;
-            zr[tid] = (vp[4 * tid + 2] - 1) + n2 * (vp[4 * tid + 3] - 1) + 1;
-        }
-        __syncthreads();
-        if (tid < r1) {
-            int a = zc[tid], b = zr[tid], ra = 0, rb = 0;
-            for (int u = 0; u < r1; u++) { ra += (zc[u] < a) || (zc[u] == a && u < tid); rb += (zr[u] < b) || (zr[u] == b && u < tid); }
-            zcs[ra] = a; zrs[rb] = b;
-        }
-        __syncthreads();
-        if (tid < r1) { keepc[tid] = (tid == 0) || (zcs[tid] != zcs[tid - 1]); keepr[tid] = (tid == 0) || (zrs[tid] != zrs[tid - 1]); }
-        __syncthreads();
-        if (tid < r1) {
-            int pc = 0, pr = 0;
-            for (int u = 0; u < tid; u++) { pc += keepc[u]; pr += keepr[u]; }
-            if (keepc[tid]) zc[pc] = zcs[tid];
-            if (keepr[tid]) zr[pr] = zrs[tid];
-            if (tid == r1 - 1) { nzc = pc + keepc[tid]; nzr = pr + keepr[tid]; }
-        }
-        __syncthreads();
+        bond_zero_lists(vip_ptr(P, g, p, first), r1, r0, n2, tid, zc, zr, zcs, zrs, keepc, keepr, &nzc, &nzr);
         const int Kc = r0 * n1 - nzc, Kr = n2 * r2 - nzr;
         if (tid < 64) { if (tid < P.cdf_ns[Kc]) segc[tid] = P.cdf_tab[(size_t)Kc * TTX_TABSEG + tid]; if (tid == 0) nsc = P.cdf_ns[Kc]; }
         else if (tid < 128) { const int t2 = tid - 64; if (t2 < P.cdf_ns[Kr]) segr[t2] = P.cdf_tab[(size_t)Kr * TTX_TABSEG + t2]; if (t2 == 0) nsr = P.cdf_ns[Kr]; }
@@ -162,15 +137,13 @@ __global__ __launch_bounds__(FB) void k_sweep_fused(DevProb P, int dir, int nste
         int havecol = 0, haverow = 0, crs = 0, done = 0;
         const int H = (P.piv == 0) ? 2 : 2 * P.piv;
         for (int h = 0; h < H && !done; h++) {
-            const bool iscol = (P.piv == 0) ? (h == 0) : (((h + (dir == 2 ? 1 : 0)) & 1) == 0);
+            const RookTurn turn = rook_turn(P.piv, P.piv == 0 ? 1 : 0, h, dir, crs, havecol, haverow);
+            const bool iscol = turn.iscol, resid = turn.resid;
+            crs = turn.crs; havecol = turn.havecol; haverow = turn.haverow;
             const int nf = iscol ? r0 * n1 : n2 * r2;
             double *fib = iscol ? acol : arow;
             if (iscol) for (int s = tid; s < r1; s += FB) xs[s] = Wq[(kk - 1) + (size_t)NM * (qq - 1) + P.SW * s];
             else       for (int s = tid; s < r1; s += FB) xs[s] = Cp[(ii - 1) + (size_t)RM * (jj - 1) + P.SS * s];
-            crs++;
-            if (iscol) havecol = 1; else haverow = 1;
-            const int dn = (P.piv == 0) ? (h == 1) : (havecol && haverow && (crs >= 2 * P.piv));
-            const bool resid = (P.piv != 0) && !dn;
             __syncthreads();
             double mx = 0.0, ab = -1.0, bb = 0.0; int ix = INT_MAX;
             for (int t = tid; t < nf; t += FB) {
@@ -208,21 +181,19 @@ __global__ __launch_bounds__(FB) void k_sweep_fused(DevProb P, int dir, int nste
             mx = block_max(mx, sha);
             if (P.piv != 0) amax = fmax(amax, mx);           // the piv = 0 branch (:492-513) does not touch amax
             neval += nf;
-            bytes_half += resid ? 8.0 * ((double)nf * r1 + r1 + 2.0 * nf) : 8.0 * nf;
+            bytes_half += halfstep_traffic(nf, r1, resid);
             n_resid += resid ? 1 : 0;
-            done = dn;
+            done = turn.done;
             if (resid) {
                 fused_argmax(ab, bb, ix, sha, shv, shi);
-                if (ix == INT_MAX) ix = 0;
-                if (iscol) { const int i = ix % r0 + 1, j = ix / r0 + 1; done = havecol && haverow && (i == ii && j == jj); ii = i; jj = j; }
-                else       { const int k = ix % n2 + 1, q = ix / n2 + 1; done = havecol && haverow && (k == kk && q == qq); kk = k; qq = q; }
+                done = take_pivot(iscol, ix, r0, n2, havecol, haverow, ii, jj, kk, qq);
                 pivot = bb;
             }
         }
         __syncthreads();
         // ---- acceptance and in-place append (:598-758) ----
         int *tape = P.tape + ((size_t)g * (m + 2) + p) * 4;
-        const bool upd = (fabs(pivot) > P.small_element * amax) && (fabs(pivot) > P.small_pivot * pivotmax_prev);
+        const bool upd = accept_pivot(pivot, amax, pivotmax_prev, P.small_element, P.small_pivot);
         if (!upd) {
             if (tid == 0) { tape[0] = tape[1] = tape[2] = tape[3] = -1; P.upd[(size_t)g * (m + 2) + p] = 0; }
         } else {
@@ -262,18 +233,12 @@ __global__ __launch_bounds__(FB) void k_sweep_fused(DevProb P, int dir, int nste
                 const double *gL = inv_ptr(P, g, p - 1, first);
                 double *Wp = core_ptr(P, P.row, g, p, first);
                 for (int j = wv; j < n1; j += FB / 64) {
-                    const double a = (lane < r0) ? acol[lane + r0 * j] : 0.0;
-                    double tmp = 0.0, xf = 0.0;
-                    for (int s = 0; s < r0; s++) {
-                        const double cand = (s == 0) ? a : a + (-1.0) * tmp;
-                        const double xsv = __shfl(cand, s, 64);
-                        if (lane == s) xf = xsv;
-                        if (lane > s && lane < r0) tmp = tmp + xsv * gL[lane * lane + s];
-                    }
+                    const double xf = wave_solve_L(gL, r0, (lane < r0) ? acol[lane + r0 * j] : 0.0, lane, 64);
                     if (lane < r0) Wp[j + (size_t)NM * r1 + P.SW * lane] = xf;
                 }
             }
-            // role D: col(p+1)(r1+1, k, :) = arow1(k, :) U(p+1)^-1  (:730-749)
+            // role D: col(p+1)(r1+1, k, :) = arow1(k, :) U(p+1)^-1  (:730-749).  Own copy of wave_solve_U (ttx_bondstep.h) with
+            // the reciprocal taken per step: holding it per lane across the loop costs this kernel another spilled register
             if (p < last) {
                 const double *gU = inv_ptr(P, g, p + 1, first);
                 double *Cq = core_ptr(P, P.col, g, p + 1, first);
@@ -290,19 +255,9 @@ __global__ __launch_bounds__(FB) void k_sweep_fused(DevProb P, int dir, int nste
                 }
             }
             // role E: index tables, pivot set, scalars (:604-635)
-            short *Ln = L_ptr(P, g, p, first), *Rn = R_ptr(P, g, p, first);
-            for (int x = tid; x < p; x += FB) Ln[(size_t)x * RM + r1] = (x < p - 1) ? Lt[(size_t)x * RM + i0] : (short)(j0 + 1);
-            for (int x = tid; x < m - p; x += FB) Rn[(size_t)x * RM + r1] = (x == 0) ? (short)(k0 + 1) : Rt[(size_t)(x - 1) * RM + q0];
-            if (tid == 0) {
-                gI[(r1 + 1) * (r1 + 1) - 1] = pivot;
-                int *vq = vip_ptr(P, g, p, first) + 4 * r1;
-                vq[0] = tape[0] = ii; vq[1] = tape[1] = jj; vq[2] = tape[2] = kk; vq[3] = tape[3] = qq;
-                P.upd[(size_t)g * (m + 2) + p] = 1;
-                r[p] = r1 + 1;                                                          // :752
-            }
-            const double ap = fabs(pivot);
-            pivotmax = (pivotmax < 0.0) ? ap : fmax(pivotmax, ap);
-            pivotmin = (pivotmin < 0.0) ? ap : fmin(pivotmin, ap);
+            append_tables(P, g, p, first, r1, ii, jj, kk, qq, tid, FB);
+            if (tid == 0) append_scalars(P, g, p, first, r1, ii, jj, kk, qq, pivot);
+            pivot_range(pivotmax, pivotmin, fabs(pivot));
         }
         __threadfence_block();
         __syncthreads();

@@ -37,6 +37,7 @@ __device__ __forceinline__ short *L_ptr(const DevProb &P, int g, int s, int firs
 __device__ __forceinline__ short *R_ptr(const DevProb &P, int g, int s, int first)      // bond s in first..last+1
 { return P.R + ((size_t)g * P.NC + (s - first)) * (size_t)P.d * P.RM; }
 
+#include "ttx_bondstep.h" // the rules of a bond step shared by every sweep kernel
 #include "ttx_fast.h"     // TTX_ARITH=fast: re-associated evaluation of the heavy integrands (tolerance-checked mode)
 
 // ------------------------------------------------------------------------------------------------
@@ -766,16 +767,7 @@ __device__ inline void resolve_state(StepState &c, const Partial *pt)
         double a = pt[b].absmax; int ix = pt[b].idx;
         if (a > ba || (a == ba && ix < bi)) { ba = a; bv = pt[b].val; bi = ix; }
     }
-    if (bi == INT_MAX) bi = 0;      // nothing compared (every residual a NaN): the first position, as idamax returns (no wild index)
-    if (c.pending == 1) {
-        int i = bi % c.r0 + 1, j = bi / c.r0 + 1;
-        c.done = c.havecol && c.haverow && (i == c.ii && j == c.jj);
-        c.ii = i; c.jj = j;
-    } else {
-        int k = bi % c.n2 + 1, q = bi / c.n2 + 1;
-        c.done = c.havecol && c.haverow && (k == c.kk && q == c.qq);
-        c.kk = k; c.qq = q;
-    }
+    c.done = take_pivot(c.pending == 1, bi, c.r0, c.n2, c.havecol, c.haverow, c.ii, c.jj, c.kk, c.qq);
     c.pivot = bv;
     c.pending = 0;
 }
@@ -795,16 +787,7 @@ __device__ inline void resolve_state_wave(StepState &c, const StepState &src, co
     if (lane != 0) return;
     c = src;
     if (!pend) return;
-    if (bi == INT_MAX) bi = 0;
-    if (c.pending == 1) {
-        int i = bi % c.r0 + 1, j = bi / c.r0 + 1;
-        c.done = c.havecol && c.haverow && (i == c.ii && j == c.jj);
-        c.ii = i; c.jj = j;
-    } else {
-        int k = bi % c.n2 + 1, q = bi / c.n2 + 1;
-        c.done = c.havecol && c.haverow && (k == c.kk && q == c.qq);
-        c.kk = k; c.qq = q;
-    }
+    c.done = take_pivot(c.pending == 1, bi, c.r0, c.n2, c.havecol, c.haverow, c.ii, c.jj, c.kk, c.qq);
     c.pivot = bv;
     c.pending = 0;
 }
@@ -1036,11 +1019,7 @@ __device__ inline void bond_state(const DevProb &P, int g, int dir, int pp, Step
     GroupState &gs = P.gs[g];
     const int m = P.d;
     int *r = P.r + (size_t)g * (m + 2);
-    if (pp == 1) {                                        // sweep start, :325-327
-        gs.pivotmax = -1.0; gs.pivotmin = -1.0;
-        int *rr = P.rr + (size_t)g * (m + 2);
-        for (int s = 0; s <= m; s++) rr[s] = r[s];
-    }
+    if (pp == 1) sweep_start(P, g);
     int nb = gs.last - gs.first + 1;
     st.active = (pp <= nb);
     st.done = 0; st.havecol = 0; st.haverow = 0; st.crs = 0; st.pending = 0; st.npart = 0; st.pivot = 0.0;
@@ -1351,31 +1330,7 @@ __global__ __launch_bounds__(512) void k_lottery(DevProb P, int dir, int pp, int
     if (tid == 33) sA[1] = ttx_minstd_pow(2 * (gs.rngpos + nlot) + 1);
     bil = ttx_minstd_pow(2ull * (unsigned long long)il_first);
     // zero-weight positions (existing pivots), :432-439
-    const int *vp = vip_ptr(P, g, p, first);
-    if (tid < r1) {
-        zc[tid] = (vp[4 * tid + 0] - 1) + r0 * (vp[4 * tid + 1] - 1) + 1;
-        zr[tid] = (vp[4 * tid + 2] - 1) + n2 * (vp[4 * tid + 3] - 1) + 1;
-    }
-    __syncthreads();
-    if (tid < r1) {          // rank sort (total order with index tie-break)
-        int a = zc[tid], b = zr[tid], ra = 0, rb = 0;
-        for (int u = 0; u < r1; u++) {
-            ra += (zc[u] < a) || (zc[u] == a && u < tid);
-            rb += (zr[u] < b) || (zr[u] == b && u < tid);
-        }
-        zcs[ra] = a; zrs[rb] = b;
-    }
-    __syncthreads();
-    if (tid < r1) { keepc[tid] = (tid == 0) || (zcs[tid] != zcs[tid - 1]); keepr[tid] = (tid == 0) || (zrs[tid] != zrs[tid - 1]); }
-    __syncthreads();
-    if (tid < r1) {          // compaction of distinct values into zc / zr
-        int pc = 0, pr = 0;
-        for (int u = 0; u < tid; u++) { pc += keepc[u]; pr += keepr[u]; }
-        if (keepc[tid]) zc[pc] = zcs[tid];
-        if (keepr[tid]) zr[pr] = zrs[tid];
-        if (tid == r1 - 1) { nzc = pc + keepc[tid]; nzr = pr + keepr[tid]; }
-    }
-    __syncthreads();
+    bond_zero_lists(vip_ptr(P, g, p, first), r1, r0, n2, tid, zc, zr, zcs, zrs, keepc, keepr, &nzc, &nzr);
     STAMP(gs, 0);   // 1: tables + powers + zero lists
     Kc = r0 * n1 - nzc; Kr = n2 * r2 - nzr;
     if (P.cdf_tab && Kc <= P.cdf_kmax && Kr <= P.cdf_kmax) {
@@ -1514,7 +1469,7 @@ __global__ __launch_bounds__(TTX_BLK) void k_halfstep(DevProb P, int h, int dir,
     if (mode == 3 || mode == 4) { if (!cur.active || zcol >= cur.n2 * cur.r2) return; }
     else if (!cur.active || cur.done) { if (blockIdx.x == 0 && tid == 0) gs.S[h + 1] = cur; return; }
     STAMP(gs, 1);   // 0: resolve
-    const bool iscol = (mode == 3 || mode == 4) ? true : (mode == 1 || mode == 2) ? (h == 0) : (((h + (dir == 2 ? 1 : 0)) & 1) == 0);    // :517,550
+    const bool iscol = (mode == 3 || mode == 4) ? true : rook_iscol(mode, h, dir);
     const int p = cur.p, r0 = cur.r0, r1 = cur.r1, r2 = cur.r2, n1 = cur.n1, n2 = cur.n2, first = gs.first;
     const int nf = iscol ? r0 * n1 : n2 * r2;
     if ((int)(blockIdx.x * TTX_BLK) >= nf) return;
@@ -1672,10 +1627,8 @@ __global__ __launch_bounds__(TTX_BLK) void k_halfstep(DevProb P, int h, int dir,
     if (HOST_PASS1(FUN, P)) return;
     double mx = block_max(live ? fabs(a) : 0.0, sha);
     if (tid == 0 && mode != 1) atomic_max_pos(&gs.amax, mx);                  // :531 / :564 (the piv = 0 branch :492-513 does not touch amax)
-    const int crs = cur.crs + 1;
-    const int havecol = cur.havecol | (iscol ? 1 : 0), haverow = cur.haverow | (iscol ? 0 : 1);
-    const int done = (mode == 1 || mode == 2) ? (h == 1) : (havecol && haverow && (crs >= 2 * P.piv));   // :534 / :567
-    const bool resid = (mode == 3) || ((mode == 0) && !done);
+    const RookTurn turn = rook_turn(P.piv, mode, h, dir, cur.crs, cur.havecol, cur.haverow);     // (modes 3, 4: resid = false, the rest unused -- they return before the publish)
+    const bool resid = (mode == 3) || turn.resid;
     if (resid) {
         double b = a, ab = -1.0; int bi = INT_MAX;
         if (live) {
@@ -1706,17 +1659,7 @@ __global__ __launch_bounds__(TTX_BLK) void k_halfstep(DevProb P, int h, int dir,
         if (blockIdx.x == 0 && zcol == 0 && tid == 0 && P.hostpass != 1) gs.neval += (long long)r0 * n1 * n2 * r2;   // :372
         return;
     }
-    if (blockIdx.x == 0 && tid == 0) {
-        StepState nx = cur;
-        nx.crs = crs; nx.havecol = havecol; nx.haverow = haverow; nx.done = done;
-        nx.pending = resid ? (iscol ? 1 : 2) : 0;
-        nx.npart = (nf + TTX_BLK - 1) / TTX_BLK;
-        gs.S[h + 1] = nx;
-        if (mode != 2) gs.neval += nf;                                        // :527 / :560 / :509
-        // algorithmic traffic: factor slabs + vector + fiber in/out when a residual is taken, else the fiber
-        gs.bytes_half += resid ? 8.0 * ((double)nf * r1 + r1 + 2.0 * nf) : 8.0 * nf;
-        gs.n_resid += resid ? 1 : 0;
-    }
+    if (blockIdx.x == 0 && tid == 0) halfstep_publish(gs, h, cur, turn, mode, nf, r1, (nf + TTX_BLK - 1) / TTX_BLK);
     STAMP(gs, 1);   // 4: argmax + state
     STAMP_END(gs, 1);
 }
@@ -1737,7 +1680,7 @@ __global__ __launch_bounds__(TTX_BLK) void k_accept(DevProb P, int H, int nA)
     GroupState &gs = P.gs[g];
     if (tid < 64) resolve_state_wave(cur, gs.S[H], gs.Pt[(H + 1) & 1], tid);
     if (tid == 0) {
-        s_upd = cur.active && (fabs(cur.pivot) > P.small_element * gs.amax) && (fabs(cur.pivot) > P.small_pivot * gs.pivotmax_prev);  // :599-600
+        s_upd = cur.active && accept_pivot(cur.pivot, gs.amax, gs.pivotmax_prev, P.small_element, P.small_pivot);
     }
     __syncthreads();
     if (!cur.active) return;
@@ -1794,13 +1737,7 @@ __global__ __launch_bounds__(TTX_BLK) void k_accept(DevProb P, int H, int nA)
             double *lu = dyn;
             for (int x = tid; x < r0 * r0; x += TTX_BLK) lu[x] = gI[x];
             __syncthreads();
-            if (tid < 64)
-                for (int s = 0; s < r0; s++) {
-                    const double cand = (s == 0) ? a : a + (-1.0) * tmp;
-                    const double xsv = __shfl(cand, s, 64);
-                    if (tid == s) xf = xsv;
-                    if (tid > s && tid < r0) tmp = tmp + xsv * lu[tid * tid + s];
-                }
+            if (tid < 64) xf = wave_solve_L(lu, r0, a, tid, 64);
         } else
         for (int s = 0; s < r0; s++) {
             if (tid == s) { xf = a + (-1.0) * tmp; if (s == 0) xf = a; s_bc = xf; }
@@ -1820,15 +1757,7 @@ __global__ __launch_bounds__(TTX_BLK) void k_accept(DevProb P, int H, int nA)
             double *lu = dyn;
             for (int x = tid; x < r2 * r2; x += TTX_BLK) lu[x] = gI[x];
             __syncthreads();
-            if (tid < 64) {
-                const double rdg = (tid < r2) ? 1.0 / lu[(tid + 1) * (tid + 1) - 1] : 0.0;
-                for (int s = 0; s < r2; s++) {
-                    const double cand = rdg * y;          // only lane s's product is used
-                    const double ys = __shfl(cand, s, 64);
-                    if (tid == s) y = ys;
-                    if (tid > s && tid < r2) y = y + (-lu[tid * tid + tid + s]) * ys;
-                }
-            }
+            if (tid < 64) y = wave_solve_U(lu, r2, y, wave_solve_rdg(lu, r2, tid), tid, 64);
         } else
         for (int s = 0; s < r2; s++) {
             if (tid == s) { y = (1.0 / gI[(s + 1) * (s + 1) - 1]) * y; s_bc = y; }
@@ -1844,10 +1773,7 @@ __global__ __launch_bounds__(TTX_BLK) void k_accept(DevProb P, int H, int nA)
             gI[r1 * r1 + s] = Cp[ii + (size_t)P.RM * jj + P.SS * s];
             gI[r1 * r1 + r1 + s] = Wq[kk + (size_t)P.NM * qq + P.SW * s];
         }
-        short *Ln = L_ptr(P, g, p, first), *Rn = R_ptr(P, g, p, first);
-        const short *Lo = L_ptr(P, g, p - 1, first), *Ro = R_ptr(P, g, p + 1, first);
-        for (int x = tid; x < p; x += TTX_BLK) Ln[(size_t)x * P.RM + r1] = (x < p - 1) ? Lo[(size_t)x * P.RM + ii] : (short)(jj + 1);
-        for (int x = tid; x < m - p; x += TTX_BLK) Rn[(size_t)x * P.RM + r1] = (x == 0) ? (short)(kk + 1) : Ro[(size_t)(x - 1) * P.RM + qq];
+        append_tables(P, g, p, first, r1, cur.ii, cur.jj, cur.kk, cur.qq, tid, TTX_BLK);
         if (P.arith && P.fpersist && tid < 128) {
             // TTX_ARITH=fast, Ising D/E: the table entries of the new pivot as a LEFT multi-index of bond p (parent: left pivot ii of bond
             // p-1, extended by node jj) and as a RIGHT multi-index of bond p (parent: right pivot qq of bond p+1, extended by node kk)
@@ -1863,14 +1789,8 @@ __global__ __launch_bounds__(TTX_BLK) void k_accept(DevProb P, int H, int nA)
             fast_entry_child(pn, pp_, P.par[nd], P.par[P.n[1] + nd], fast_near(P, sd, g, p, first) + r1, fast_piv(P, sd, g, p, first) + r1, P.RM, lane_);
         }
         if (tid == 0) {
-            gI[(r1 + 1) * (r1 + 1) - 1] = cur.pivot;
-            int *vp = vip_ptr(P, g, p, first) + 4 * r1;
-            vp[0] = tape[0] = ii + 1; vp[1] = tape[1] = jj + 1; vp[2] = tape[2] = kk + 1; vp[3] = tape[3] = qq + 1;
-            double ap = fabs(cur.pivot);
-            gs.pivotmax = (gs.pivotmax < 0.0) ? ap : fmax(gs.pivotmax, ap);
-            gs.pivotmin = (gs.pivotmin < 0.0) ? ap : fmin(gs.pivotmin, ap);
-            P.upd[(size_t)g * (m + 2) + p] = 1;
-            P.r[(size_t)g * (m + 2) + p] = r1 + 1;                                      // :752
+            append_scalars(P, g, p, first, r1, cur.ii, cur.jj, cur.kk, cur.qq, cur.pivot);
+            pivot_range(gs.pivotmax, gs.pivotmin, fabs(cur.pivot));
         }
     }
 }
@@ -2409,13 +2329,7 @@ __global__ __launch_bounds__(TTX_BLK) void k_exch_boundary(DevProb P)
             __syncthreads();
             for (int x = tid; x < rp * rp; x += TTX_BLK) lu[x] = gI[x];
             __syncthreads();
-            if (tid < 64)
-                for (int s = 0; s < rp; s++) {
-                    const double cand = (s == 0) ? a : a + (-1.0) * tmp;
-                    const double xsv = __shfl(cand, s, 64);
-                    if (tid == s) xf = xsv;
-                    if (tid > s && tid < rp) tmp = tmp + xsv * lu[tid * tid + s];
-                }
+            if (tid < 64) xf = wave_solve_L(lu, rp, a, tid, 64);
         } else
         for (int s = 0; s < rp; s++) {
             if (tid == s) { xf = (s == 0) ? a : a + (-1.0) * tmp; s_bc = xf; }
@@ -2463,15 +2377,7 @@ __global__ __launch_bounds__(TTX_BLK) void k_exch_boundary(DevProb P)
             __syncthreads();
             for (int x = tid; x < rp * rp; x += TTX_BLK) lu[x] = gI[x];
             __syncthreads();
-            if (tid < 64) {
-                const double rdg = (tid < rp) ? 1.0 / lu[(tid + 1) * (tid + 1) - 1] : 0.0;
-                for (int s = 0; s < rp; s++) {
-                    const double cand = rdg * y;          // only lane s's product is used
-                    const double ys = __shfl(cand, s, 64);
-                    if (tid == s) y = ys;
-                    if (tid > s && tid < rp) y = y + (-lu[tid * tid + tid + s]) * ys;
-                }
-            }
+            if (tid < 64) y = wave_solve_U(lu, rp, y, wave_solve_rdg(lu, rp, tid), tid, 64);
         } else
         for (int s = 0; s < rp; s++) {
             if (tid == s) { y = (1.0 / gI[(s + 1) * (s + 1) - 1]) * y; s_bc = y; }

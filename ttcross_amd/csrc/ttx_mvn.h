@@ -190,26 +190,14 @@ __global__ __launch_bounds__(64) void k_halfstep_mvn(DevProb P, int h, int dir, 
     if (lane == 0) { cur = gs.S[h]; resolve_state(cur, gs.Pt[(h + 1) & 1]); }
     __syncthreads();
     if (!cur.active || cur.done) { if (blockIdx.x == 0 && lane == 0) gs.S[h + 1] = cur; return; }
-    const bool iscol = (mode == 1 || mode == 2) ? (h == 0) : (((h + (dir == 2 ? 1 : 0)) & 1) == 0);    // :517,550
+    const RookTurn turn = rook_turn(P.piv, mode, h, dir, cur.crs, cur.havecol, cur.haverow);
+    const bool iscol = turn.iscol, resid = turn.resid;    // :517,550 / :534,567
     const int p = cur.p, r0 = cur.r0, r1 = cur.r1, r2 = cur.r2, n1 = cur.n1, n2 = cur.n2, first = gs.first;
     const int nf = iscol ? r0 * n1 : n2 * r2;
     const int nv = iscol ? r0 : r2, nm = iscol ? n1 : n2, nch = (nm + 63) >> 6;
     const int npart = nv * nch;
     const int w = blockIdx.x;
-    const int crs = cur.crs + 1;
-    const int havecol = cur.havecol | (iscol ? 1 : 0), haverow = cur.haverow | (iscol ? 0 : 1);
-    const int done = (mode == 1 || mode == 2) ? (h == 1) : (havecol && haverow && (crs >= 2 * P.piv));   // :534 / :567
-    const bool resid = (mode == 0) && !done;
-    if (w == 0 && lane == 0) {
-        StepState nx = cur;
-        nx.crs = crs; nx.havecol = havecol; nx.haverow = haverow; nx.done = done;
-        nx.pending = resid ? (iscol ? 1 : 2) : 0;
-        nx.npart = npart;
-        gs.S[h + 1] = nx;
-        if (mode != 2) gs.neval += nf;                                        // :527 / :560 / :509
-        gs.bytes_half += resid ? 8.0 * ((double)nf * r1 + r1 + 2.0 * nf) : 8.0 * nf;
-        gs.n_resid += resid ? 1 : 0;
-    }
+    if (w == 0 && lane == 0) halfstep_publish(gs, h, cur, turn, mode, nf, r1, npart);
     if (w >= npart) return;
     const int pv = w / nch, vmode = (w - pv * nch) * 64 + lane;
     const bool live = vmode < nm;
