@@ -673,6 +673,63 @@ def test_ising_de_kernel_variants_bit_exact(env, monkeypatch):
         assert tt.neval == oo["neval"] and tt.quad(s["quad"]) == oo["value"]
 
 
+# the wave half-steps (one wave per pivot and 64-mode chunk): kernel -> (switches, what plan()["halfstep"] says or begins with)
+WAVE_KERNELS = {
+    "dec": ({}, "k_halfstep_dec"),
+    "de_true": ({"TTX_DE_CUT": "0", "TTX_DE_TEAM": "0"}, "k_halfstep_de<true>"),
+    "de_false": ({"TTX_DE_CUT": "0", "TTX_DE_TEAM": "0", "TTX_DE_FASTDIV": "0"}, "k_halfstep_de<false>"),
+    "det_true_3": ({"TTX_DE_CUT": "0", "TTX_DE_TEAM_UNITS": "1000000"}, "k_halfstep_det<true,3>[<=1000000], "),
+    "det_true_1": ({"TTX_DE_CUT": "0", "TTX_DE_TEAM_UNITS": "0", "TTX_DE_TEAM6_UNITS": "1000000"},
+                   "k_halfstep_det<true,3>[<=0], k_halfstep_det<true,1>[<=1000000], "),
+    "de5_true": ({"TTX_DE_CUT": "0", "TTX_DE_V5": "1"}, "k_halfstep_de5<true>"),
+    "mvn": ({}, "k_halfstep_mvn"),
+}
+# (kind, m or d, n, r, piv, groups).  d: two chunks, the second with 5 live lanes -- rook search, then piv = 0 (modes 1 and 2, no
+# residual, amax untouched in mode 1); e: three chunks, id 3 without the b-part, two bond groups, pivots in the second chunk
+WAVE_ISING_SHAPES = [("d", 9, 69, 3, 2, 1), ("d", 9, 69, 3, 0, 1), ("e", 8, 129, 3, 1, 2)]
+WAVE_MVN_SHAPES = [("mvn", 6, 69, 3, 2, 1), ("mvn", 6, 69, 3, 0, 2)]
+
+
+@pytest.fixture(scope="module")
+def wave_oracle():
+    """The oracle's run per shape, made once, shared by the kernels and left unchanged."""
+    runs = {}
+
+    def run(shape, s):
+        if shape not in runs:
+            kind, m, n, r, piv, ng = shape
+            runs[shape] = O.dmrgg(s["n"], s["fun_id"], s["par"], r, piv=piv, accuracy=s["acc"], quad=s["quad"], tru=s["tru"], aux=s["aux"], nproc=ng)
+        return runs[shape]
+    return run
+
+
+@pytest.mark.parametrize("kernel", list(WAVE_KERNELS))
+def test_wave_halfsteps_at_several_chunks_bit_exact(kernel, monkeypatch, wave_oracle):
+    """k_halfstep_dec, _de, _det, _de5 and _mvn with n = 69 and n = 129: a pivot's fiber takes two or three waves, so the split
+    of the slot w into (pivot, chunk), a last chunk with few live lanes and the linear index t of a later chunk are exercised --
+    the other tests of these kernels have at most 64 modes, except k_halfstep_dec at the full D_256 (mvn: n = 33).  The kernel
+    asked for must be the one the plan names, on the chain path.  The cores are compared with the oracle's: at these shapes most
+    pivots lie below mode 64 (only the E shape takes some above), so a wrong store of a later chunk shows in the cores."""
+    env, halfstep = WAVE_KERNELS[kernel]
+    monkeypatch.setenv("TTX_SWEEP", "chain")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    for shape in (WAVE_MVN_SHAPES if kernel == "mvn" else WAVE_ISING_SHAPES):
+        kind, m, n, r, piv, ng = shape
+        s = D.box_setup("mvn", m, n) if kind == "mvn" else D.ising_setup(kind, m, n)
+        tt = E.TTCross(s["n"], s["fun_id"], s["par"], r, pivoting=piv, accuracy=s["acc"], quad=s["quad"], tru=s["tru"], aux=s["aux"], nproc=ng)
+        assert tt.sweep_path() == "chain"
+        hs = tt.plan()["halfstep"]
+        assert hs.startswith(halfstep) if halfstep.endswith(", ") else hs == halfstep, hs
+        tt.run()
+        oo = wave_oracle(shape, s)
+        assert len(oo["sweeps"]) == 3 and max(oo["r"]) == r      # the initial cross and two sweeps; the ranks reach r
+        _assert_identical(tt, oo, cores=True)
+        assert tt.quad(s["quad"]) == oo["value"]
+        if kernel == "de5_true":
+            assert tt.det_fallbacks == 0         # a silent replay on k_halfstep_de must not pass for the relay
+
+
 def test_full_size_d256_against_reference_value():
     """BASELINE config 5 at FULL size (Ising D_256, n=101, r=64, PIV=5; 255 cores, 7.4e7 O(d^2) evaluations), 8 bond
     groups on one GPU.  No oracle run at this size (minutes of CPU): the size-independent property is the integral

@@ -5,7 +5,10 @@
 // must agree on lives here: whose turn it is and when the rook search stops, how a pivot is taken from an arg-max, the
 // acceptance test and the pivot range, the traffic count, and the cold device code around them (publishing the next
 // step state, the lottery's zero-weight lists, the two triangular wave solves of the append, the tables and scalars
-// of an accepted pivot, the start of a sweep).  The kernels keep their evaluation, reduction and exchange.
+// of an accepted pivot, the start of a sweep).  The kernels keep their evaluation, reduction and exchange -- except the four
+// Ising half-steps with one wave per (pivot, 64-mode chunk) slot (_de, _dec, _de5, _det), which keep the evaluation only: their
+// slot, reduction and Partial record are ttx_wavestep.h, on top of this file and ttx_kernels.h (_mvn, the fifth of that kind,
+// keeps a copy of that frame: measured, see ttx_mvn.h).
 //
 // The rule part is plain functions of values and compiles on the host (tests/bondstep_main.cpp); values that must be
 // wave-uniform are made so by the caller.  The device part is included by ttx_kernels.h behind its address helpers.

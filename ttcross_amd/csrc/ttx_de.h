@@ -19,6 +19,7 @@
 // de_pairs_tab, hence of the oracle: results stay bit-identical.
 #pragma once
 #include "ttx_kernels.h"
+#include "ttx_wavestep.h"     // the frame of the wave half-steps: slot, staging, b-part and weights, finish
 #include "ttx_create_plan.h"    // the kernels' LDS formulas: de5_lds_doubles, de_rows_stride, det_lds_doubles, ... (shared with the host's plan)
 
 // a = (..((a OP p[0]) OP p[1]) ..) OP p[len-1] for an LDS row read with a wave-uniform address (broadcasts), OP = * or +.
@@ -280,22 +281,10 @@ __global__ __launch_bounds__(64) void k_halfstep_de(DevProb P, int h, int dir, i
     if (lane == 0) { cur = gs.S[h]; resolve_state(cur, gs.Pt[(h + 1) & 1]); }
     __syncthreads();
     if (!cur.active || cur.done) { if (blockIdx.x == 0 && lane == 0) gs.S[h + 1] = cur; return; }
-    const RookTurn turn = rook_turn(P.piv, mode, h, dir, UNI(cur.crs), UNI(cur.havecol), UNI(cur.haverow));
-    const bool iscol = turn.iscol, resid = turn.resid;    // :517,550 / :534,567
-    // what steers the control flow is made wave-uniform explicitly (values read from LDS / global memory are per-lane
-    // registers to the compiler: loop counters and branches would otherwise run on the vector unit)
-    const int p = UNI(cur.p), r0 = UNI(cur.r0), r1 = UNI(cur.r1), r2 = UNI(cur.r2), n1 = UNI(cur.n1), n2 = UNI(cur.n2), first = UNI(gs.first);
-    const int c_ii = UNI(cur.ii), c_jj = UNI(cur.jj), c_kk = UNI(cur.kk), c_qq = UNI(cur.qq);
-    const int nf = iscol ? r0 * n1 : n2 * r2;
-    const int nv = iscol ? r0 : r2, nm = iscol ? n1 : n2, nch = (nm + 63) >> 6;
-    const int npart = nv * nch;
-    const int w = blockIdx.x;
-    if (w == 0 && lane == 0) halfstep_publish(gs, h, cur, turn, mode, nf, r1, npart);
-    if (w >= npart) return;
-    const int pv = w / nch, vmode = (w - pv * nch) * 64 + lane;        // varying pivot, mode index (0-based)
-    const bool live = vmode < nm;
-    const int A = p - 1, B = m - p - 1;
-    const int pl = iscol ? pv : c_ii - 1, qr = iscol ? c_qq - 1 : pv;         // left / right pivot of this wave
+    const WaveSlot s = wave_slot(P, gs, cur, h, dir, mode, lane);
+    if (s.w == 0 && lane == 0) halfstep_publish(gs, h, cur, s.turn, mode, s.nf, s.r1, s.npart);
+    if (s.w >= s.npart) return;
+    const int p = s.p, first = s.first, pl = s.pl, qr = s.qr, A = p - 1, B = m - p - 1;
     const int n1m = UNI(P.n[1]);
     const double *nodes = P.par, *weights = P.par + n1m;                          // 0-based here
     // LDS: UL[VS] | xl[VS] | wl[VS] | xr[VS] | wr[VS] | ring L[128] | ring R[128]
@@ -304,12 +293,9 @@ __global__ __launch_bounds__(64) void k_halfstep_de(DevProb P, int h, int dir, i
     const size_t NP = (size_t)P.de_npair, tsz = NP * P.RM;
     const double *TLg = P.deTL + (size_t)g * tsz + (size_t)pl * NP, *TRg = P.deTR + (size_t)g * tsz + (size_t)qr * NP;
     const double *ULg = P.deUL + ((size_t)g * P.RM + pl) * (m + 1);
-    const short *Lt = L_ptr(P, g, p - 1, first), *Rt = R_ptr(P, g, p + 1, first);
-    for (int x = lane; x < A; x += 64) { const int ix = Lt[(size_t)x * P.RM + pl] - 1; xl[x] = nodes[ix]; wl[x] = weights[ix]; }
-    for (int x = lane; x < B; x += 64) { const int ix = Rt[(size_t)x * P.RM + qr] - 1; xr[x] = nodes[ix]; wr[x] = weights[ix]; }
+    stage_pivot_rows(P, L_ptr(P, g, p - 1, first), R_ptr(P, g, p + 1, first), pl, qr, A, B, lane, 64, nodes, weights, xl, wl, xr, wr);
     for (int x = lane; x <= A; x += 64) UL[x] = ULg[x];
-    const int i1 = iscol ? (live ? vmode : 0) : c_jj - 1, i2 = iscol ? c_kk - 1 : (live ? vmode : 0);   // node index of dim p / p+1
-    const double x1 = nodes[i1], x2 = nodes[i2], w1 = weights[i1], w2 = weights[i2];
+    const double x1 = nodes[s.i1], x2 = nodes[s.i2], w1 = weights[s.i1], w2 = weights[s.i2];
     WStreamD<2> sl, sr;                                                // tabulated factors by DPP row broadcasts (end of round 2; LDS broadcasts before)
     sl.init(TLg, A * (A + 1) / 2, ringL, lane);
     sr.init(TRg, B * (B + 1) / 2, ringR, lane);
@@ -324,54 +310,8 @@ __global__ __launch_bounds__(64) void k_halfstep_de(DevProb P, int h, int dir, i
     }
     de_run<FAST>(a, 1.0, x2, xr, B);                                   // i = A+1: starts after dim p
     a = sr.chain_from_boundary(a, B * (B + 1) / 2, lane);
-    // ---- b-part (id 2) and the weights (:197-218), order of de_finish ----
-    const int id = P.ising_id;
-    double b = 0.0;
-    if (id == 2) {
-        double v = 1.0, ww = 1.0, vk = 1.0, wk = 1.0;
-        for (int j = B - 1; j >= 0; j--) { vk = vk * xr[j]; v = v + vk; }
-        vk = vk * x2; v = v + vk;
-        vk = vk * x1; v = v + vk;
-        for (int j = A - 1; j >= 0; j--) { vk = vk * xl[j]; v = v + vk; }
-        for (int j = 0; j < A; j++) { wk = wk * xl[j]; ww = ww + wk; }
-        wk = wk * x1; ww = ww + wk;
-        wk = wk * x2; ww = ww + wk;
-        for (int j = 0; j < B; j++) { wk = wk * xr[j]; ww = ww + wk; }
-        b = 1.0 / (v * ww);
-    }
-    double f = (id == 2) ? 2 * a * b : 2 * a;
-    for (int j = 0; j < A; j++) f = f * wl[j];
-    f = f * w1; f = f * w2;
-    for (int j = 0; j < B; j++) f = f * wr[j];
-    a = f;
-    // ---- fiber store, amax, residual, arg-max: as k_halfstep, on the fiber's linear index t ----
-    const int u_ = iscol ? pv : vmode, v_ = iscol ? vmode : pv;        // col: (i, j) ; row: (k, q), 0-based
-    const int t = iscol ? (u_ + r0 * v_) : (u_ + n2 * v_);
-    if (live) (iscol ? P.acol : P.arow)[(size_t)g * P.RM * P.NM + t] = a;
-    const double mx = wave_max(live ? fabs(a) : 0.0);
-    if (lane == 0 && mode != 1) atomic_max_pos(&gs.amax, mx);          // :531 / :564 (the piv = 0 branch :492-513 does not touch amax)
-    if (resid) {
-        const double *Cp = core_ptr(P, P.col, g, p, first), *Wq = core_ptr(P, P.row, g, p + 1, first);
-        double bb = a, ab = -1.0; int bi = INT_MAX;
-        if (live) {
-            if (iscol) {   // dgemv 'n', alpha=-1 (:538): b += (-x_s) * col(:, s), x_s = row(p+1)(s, kk, qq)
-                const double *c = Cp + u_ + (size_t)P.RM * v_;
-                const double *xq = Wq + (c_kk - 1) + (size_t)P.NM * (c_qq - 1);
-#pragma unroll 8
-                for (int s = 0; s < r1; s++) bb = bb + (-xq[P.SW * s]) * c[P.SS * s];
-            } else {       // dgemv 't', alpha=-1 (:571): b += -1 * sum_s row(s, kq) * x_s, x_s = col(p)(ii, jj, s)
-                const double *wv = Wq + u_ + (size_t)P.NM * v_;
-                const double *xc = Cp + (c_ii - 1) + (size_t)P.RM * (c_jj - 1);
-                double tt = 0.0;
-#pragma unroll 8
-                for (int s = 0; s < r1; s++) tt = tt + wv[P.SW * s] * xc[P.SS * s];
-                bb = bb + (-1.0) * tt;
-            }
-            ab = fabs(bb); bi = t;
-        }
-        wave_argmax(ab, bb, bi);
-        if (lane == 0) { Partial pr; pr.absmax = ab; pr.val = bb; pr.idx = bi; pr.pad = 0; gs.Pt[h & 1][w] = pr; }
-    }
+    a = de_finish_split(P.ising_id, a, A, B, x1, x2, w1, w2, xl, wl, xr, wr);
+    wave_finish(P, gs, g, s, h, mode, a, lane);
 }
 
 // the bond-spanning tail of a row as de_run, ended where every lane's running product has reached the unit cut (the factors of a
@@ -417,9 +357,7 @@ __device__ __forceinline__ double dec_value(const DevProb &P, int g, int p, int 
     const size_t NP = (size_t)P.de_npair, tsz = NP * P.RM;
     const double *TLg = P.deTL + (size_t)g * tsz + (size_t)pl * NP, *TRg = P.deTR + (size_t)g * tsz + (size_t)qr * NP;
     const double *ULg = P.deUL + ((size_t)g * P.RM + pl) * (m + 1);
-    const short *Lt = L_ptr(P, g, p - 1, first), *Rt = R_ptr(P, g, p + 1, first);
-    for (int x = lane; x < A; x += 64) { const int ix = Lt[(size_t)x * P.RM + pl] - 1; xl[x] = nodes[ix]; wl[x] = weights[ix]; }
-    for (int x = lane; x < B; x += 64) { const int ix = Rt[(size_t)x * P.RM + qr] - 1; xr[x] = nodes[ix]; wr[x] = weights[ix]; }
+    stage_pivot_rows(P, L_ptr(P, g, p - 1, first), R_ptr(P, g, p + 1, first), pl, qr, A, B, lane, 64, nodes, weights, xl, wl, xr, wr);
     for (int x = lane; x <= A; x += 64) UL[x] = ULg[x];
     const int *CLg = P.deCL + ((size_t)g * P.RM + pl) * (m + 1), *CRg = P.deCR + ((size_t)g * P.RM + qr) * (m + 1);
     for (int x = lane; x < A; x += 64) cntL[x] = CLg[x];
@@ -443,6 +381,7 @@ __device__ __forceinline__ double dec_value(const DevProb &P, int g, int p, int 
     a = sr.chain_from_boundary(a, totR, lane);
     // ---- b-part (id 2) and the weights (:197-218), order of de_finish.  v >= 1 and the running product vk never grows: once
     //      vk <= 2^-54 every further v + vk returns v (half an ulp of v is at least 2^-53) -- the sums end there, bit for bit ----
+    // (its own form, not de_finish_split: that one runs every sum to its end, these stop at the unit cut)
     const int id = P.ising_id;
     double b = 0.0;
     if (id == 2) {
@@ -517,56 +456,16 @@ __global__ __launch_bounds__(64) void k_halfstep_dec(DevProb P, int h, int dir, 
 {
     extern __shared__ __align__(16) double dyn[];
     __shared__ StepState cur;
-    const int g = blockIdx.y, lane = threadIdx.x, m = P.d;
+    const int g = blockIdx.y, lane = threadIdx.x;
     GroupState &gs = P.gs[g];
     if (lane == 0) { cur = gs.S[h]; resolve_state(cur, gs.Pt[(h + 1) & 1]); }
     __syncthreads();
     if (!cur.active || cur.done) { if (blockIdx.x == 0 && lane == 0) gs.S[h + 1] = cur; return; }
-    const RookTurn turn = rook_turn(P.piv, mode, h, dir, UNI(cur.crs), UNI(cur.havecol), UNI(cur.haverow));
-    const bool iscol = turn.iscol, resid = turn.resid;    // :517,550 / :534,567
-    // what steers the control flow is made wave-uniform explicitly (values read from LDS / global memory are per-lane
-    // registers to the compiler: loop counters and branches would otherwise run on the vector unit)
-    const int p = UNI(cur.p), r0 = UNI(cur.r0), r1 = UNI(cur.r1), r2 = UNI(cur.r2), n1 = UNI(cur.n1), n2 = UNI(cur.n2), first = UNI(gs.first);
-    const int c_ii = UNI(cur.ii), c_jj = UNI(cur.jj), c_kk = UNI(cur.kk), c_qq = UNI(cur.qq);
-    const int nf = iscol ? r0 * n1 : n2 * r2;
-    const int nv = iscol ? r0 : r2, nm = iscol ? n1 : n2, nch = (nm + 63) >> 6;
-    const int npart = nv * nch;
-    const int w = blockIdx.x;
-    if (w == 0 && lane == 0) halfstep_publish(gs, h, cur, turn, mode, nf, r1, npart);
-    if (w >= npart) return;
-    const int pv = w / nch, vmode = (w - pv * nch) * 64 + lane;        // varying pivot, mode index (0-based)
-    const bool live = vmode < nm;
-    const int pl = iscol ? pv : c_ii - 1, qr = iscol ? c_qq - 1 : pv;         // left / right pivot of this wave
-    const int i1 = iscol ? (live ? vmode : 0) : c_jj - 1, i2 = iscol ? c_kk - 1 : (live ? vmode : 0);   // node index of dim p / p+1
-    double a = dec_value<DEC_HALF_STREAM>(P, g, p, first, pl, qr, i1, i2, dyn, lane);
-    // ---- fiber store, amax, residual, arg-max: as k_halfstep, on the fiber's linear index t ----
-    const int u_ = iscol ? pv : vmode, v_ = iscol ? vmode : pv;        // col: (i, j) ; row: (k, q), 0-based
-    const int t = iscol ? (u_ + r0 * v_) : (u_ + n2 * v_);
-    if (live) (iscol ? P.acol : P.arow)[(size_t)g * P.RM * P.NM + t] = a;
-    const double mx = wave_max(live ? fabs(a) : 0.0);
-    if (lane == 0 && mode != 1) atomic_max_pos(&gs.amax, mx);          // :531 / :564 (the piv = 0 branch :492-513 does not touch amax)
-    if (resid) {
-        const double *Cp = core_ptr(P, P.col, g, p, first), *Wq = core_ptr(P, P.row, g, p + 1, first);
-        double bb = a, ab = -1.0; int bi = INT_MAX;
-        if (live) {
-            if (iscol) {   // dgemv 'n', alpha=-1 (:538): b += (-x_s) * col(:, s), x_s = row(p+1)(s, kk, qq)
-                const double *c = Cp + u_ + (size_t)P.RM * v_;
-                const double *xq = Wq + (c_kk - 1) + (size_t)P.NM * (c_qq - 1);
-#pragma unroll 8
-                for (int s = 0; s < r1; s++) bb = bb + (-xq[P.SW * s]) * c[P.SS * s];
-            } else {       // dgemv 't', alpha=-1 (:571): b += -1 * sum_s row(s, kq) * x_s, x_s = col(p)(ii, jj, s)
-                const double *wv = Wq + u_ + (size_t)P.NM * v_;
-                const double *xc = Cp + (c_ii - 1) + (size_t)P.RM * (c_jj - 1);
-                double tt = 0.0;
-#pragma unroll 8
-                for (int s = 0; s < r1; s++) tt = tt + wv[P.SW * s] * xc[P.SS * s];
-                bb = bb + (-1.0) * tt;
-            }
-            ab = fabs(bb); bi = t;
-        }
-        wave_argmax(ab, bb, bi);
-        if (lane == 0) { Partial pr; pr.absmax = ab; pr.val = bb; pr.idx = bi; pr.pad = 0; gs.Pt[h & 1][w] = pr; }
-    }
+    const WaveSlot s = wave_slot(P, gs, cur, h, dir, mode, lane);
+    if (s.w == 0 && lane == 0) halfstep_publish(gs, h, cur, s.turn, mode, s.nf, s.r1, s.npart);
+    if (s.w >= s.npart) return;
+    const double a = dec_value<DEC_HALF_STREAM>(P, g, s.p, s.first, s.pl, s.qr, s.i1, s.i2, dyn, lane);
+    wave_finish(P, gs, g, s, h, mode, a, lane);
 }
 
 // b-part (id 2) and weights (test_crs_ising.f90:197-218) from per-dimension value arrays xv / wv (0-based dims)
@@ -648,19 +547,10 @@ __global__ __launch_bounds__(64 * DE5_W) void k_halfstep_de5(DevProb P, int h, i
     if (tid == 0) { cur = gs.S[h]; resolve_state(cur, gs.Pt[(h + 1) & 1]); giveup = 0; }
     __syncthreads();
     if (!cur.active || cur.done) { if (blockIdx.x == 0 && tid == 0) gs.S[h + 1] = cur; return; }
-    const RookTurn turn = rook_turn(P.piv, mode, h, dir, cur.crs, cur.havecol, cur.haverow);
-    const bool iscol = turn.iscol, resid = turn.resid;    // :517,550 / :534,567
-    const int p = cur.p, r0 = cur.r0, r1 = cur.r1, r2 = cur.r2, n1 = cur.n1, n2 = cur.n2, first = gs.first;
-    const int nf = iscol ? r0 * n1 : n2 * r2;
-    const int nv = iscol ? r0 : r2, nm = iscol ? n1 : n2, nch = (nm + 63) >> 6;
-    const int npart = nv * nch;
-    const int w = blockIdx.x;
-    if (w == 0 && tid == 0) halfstep_publish(gs, h, cur, turn, mode, nf, r1, npart);
-    if (w >= npart) return;
-    const int pv = w / nch, vmode = (w - pv * nch) * 64 + lane;
-    const bool live = vmode < nm;
-    const int A = p - 1, B = m - p - 1;
-    const int pl = iscol ? pv : cur.ii - 1, qr = iscol ? cur.qq - 1 : pv;
+    const WaveSlot s = wave_slot(P, gs, cur, h, dir, mode, lane);
+    if (s.w == 0 && tid == 0) halfstep_publish(gs, h, cur, s.turn, mode, s.nf, s.r1, s.npart);
+    if (s.w >= s.npart) return;
+    const int p = s.p, first = s.first, pl = s.pl, qr = s.qr, A = p - 1, B = m - p - 1;
     const int n1m = P.n[1];
     const double *nodes = P.par, *weights = P.par + n1m;
     const int VS = ((m + 7) & ~7) + 8 + DE5_SEG;
@@ -669,14 +559,11 @@ __global__ __launch_bounds__(64 * DE5_W) void k_halfstep_de5(DevProb P, int h, i
     const size_t NP = (size_t)P.de_npair, tsz = NP * P.RM;
     const double *TLg = P.deTL + (size_t)g * tsz + (size_t)pl * NP, *TRg = P.deTR + (size_t)g * tsz + (size_t)qr * NP;
     const double *ULg = P.deUL + ((size_t)g * P.RM + pl) * (m + 1);
-    const short *Lt = L_ptr(P, g, p - 1, first), *Rt = R_ptr(P, g, p + 1, first);
-    for (int x = tid; x < A; x += 64 * DE5_W) { const int ix = Lt[(size_t)x * P.RM + pl] - 1; xl[x] = nodes[ix]; wl[x] = weights[ix]; }
-    for (int x = tid; x < B; x += 64 * DE5_W) { const int ix = Rt[(size_t)x * P.RM + qr] - 1; xr[x] = nodes[ix]; wr[x] = weights[ix]; }
+    stage_pivot_rows(P, L_ptr(P, g, p - 1, first), R_ptr(P, g, p + 1, first), pl, qr, A, B, tid, 64 * DE5_W, nodes, weights, xl, wl, xr, wr);
     for (int x = B + tid; x < B + DE5_SEG; x += 64 * DE5_W) xr[x] = 1.0;       // the division batches of eight may run past B
     for (int x = tid; x <= A; x += 64 * DE5_W) UL[x] = ULg[x];
     box[tid] = DE5_SENT;
-    const int i1 = iscol ? (live ? vmode : 0) : cur.jj - 1, i2 = iscol ? cur.kk - 1 : (live ? vmode : 0);
-    const double x1 = nodes[i1], x2 = nodes[i2], w1 = weights[i1], w2 = weights[i2];
+    const double x1 = nodes[s.i1], x2 = nodes[s.i2], w1 = weights[s.i1], w2 = weights[s.i2];
     __syncthreads();
     // the body xr[0..B) of a row in segments of 16 columns, dealt round robin to nact waves; R rounds per row
     const int nact = max(1, min(DE5_W, (B + DE5_SEG - 1) / DE5_SEG));
@@ -729,53 +616,8 @@ __global__ __launch_bounds__(64 * DE5_W) void k_halfstep_de5(DevProb P, int h, i
     if (wv != 0) return;
     if (nact > 1 && !de5_recv(mybox, lane, a, &giveup)) DE5_FAIL();
     a = sr.chain(a, B * (B + 1) / 2, lane);
-    // ---- b-part (id 2) and the weights (:197-218), order of de_finish ----
-    const int id = P.ising_id;
-    double b = 0.0;
-    if (id == 2) {
-        double v = 1.0, ww = 1.0, vk = 1.0, wk = 1.0;
-        for (int j = B - 1; j >= 0; j--) { vk = vk * xr[j]; v = v + vk; }
-        vk = vk * x2; v = v + vk;
-        vk = vk * x1; v = v + vk;
-        for (int j = A - 1; j >= 0; j--) { vk = vk * xl[j]; v = v + vk; }
-        for (int j = 0; j < A; j++) { wk = wk * xl[j]; ww = ww + wk; }
-        wk = wk * x1; ww = ww + wk;
-        wk = wk * x2; ww = ww + wk;
-        for (int j = 0; j < B; j++) { wk = wk * xr[j]; ww = ww + wk; }
-        b = 1.0 / (v * ww);
-    }
-    double fv = (id == 2) ? 2 * a * b : 2 * a;
-    for (int j = 0; j < A; j++) fv = fv * wl[j];
-    fv = fv * w1; fv = fv * w2;
-    for (int j = 0; j < B; j++) fv = fv * wr[j];
-    a = fv;
-    const int u_ = iscol ? pv : vmode, v_ = iscol ? vmode : pv;
-    const int t = iscol ? (u_ + r0 * v_) : (u_ + n2 * v_);
-    if (live) (iscol ? P.acol : P.arow)[(size_t)g * P.RM * P.NM + t] = a;
-    const double mx = wave_max(live ? fabs(a) : 0.0);
-    if (lane == 0 && mode != 1) atomic_max_pos(&gs.amax, mx);
-    if (resid) {
-        const double *Cp = core_ptr(P, P.col, g, p, first), *Wq = core_ptr(P, P.row, g, p + 1, first);
-        double bb = a, ab = -1.0; int bi = INT_MAX;
-        if (live) {
-            if (iscol) {
-                const double *c = Cp + u_ + (size_t)P.RM * v_;
-                const double *xq = Wq + (cur.kk - 1) + (size_t)P.NM * (cur.qq - 1);
-#pragma unroll 8
-                for (int s = 0; s < r1; s++) bb = bb + (-xq[P.SW * s]) * c[P.SS * s];
-            } else {
-                const double *wvp = Wq + u_ + (size_t)P.NM * v_;
-                const double *xc = Cp + (cur.ii - 1) + (size_t)P.RM * (cur.jj - 1);
-                double tt = 0.0;
-#pragma unroll 8
-                for (int s = 0; s < r1; s++) tt = tt + wvp[P.SW * s] * xc[P.SS * s];
-                bb = bb + (-1.0) * tt;
-            }
-            ab = fabs(bb); bi = t;
-        }
-        wave_argmax(ab, bb, bi);
-        if (lane == 0) { Partial pr; pr.absmax = ab; pr.val = bb; pr.idx = bi; pr.pad = 0; gs.Pt[h & 1][w] = pr; }
-    }
+    a = de_finish_split(P.ising_id, a, A, B, x1, x2, w1, w2, xl, wl, xr, wr);
+    wave_finish(P, gs, g, s, h, mode, a, lane);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1020,24 +862,14 @@ __global__ __launch_bounds__(64 * (4 * NBK + 2)) void k_halfstep_det(DevProb P, 
     if (tid == 0) { cur = gs.S[h]; resolve_state(cur, gs.Pt[(h + 1) & 1]); }
     __syncthreads();
     if (!cur.active || cur.done) { if (blockIdx.x == 0 && tid == 0) gs.S[h + 1] = cur; return; }
-    const RookTurn turn = rook_turn(P.piv, mode, h, dir, UNI(cur.crs), UNI(cur.havecol), UNI(cur.haverow));
-    const bool iscol = turn.iscol, resid = turn.resid;    // :517,550 / :534,567
-    const int p = UNI(cur.p), r0 = UNI(cur.r0), r1 = UNI(cur.r1), r2 = UNI(cur.r2), n1 = UNI(cur.n1), n2 = UNI(cur.n2), first = UNI(gs.first);
-    const int c_ii = UNI(cur.ii), c_jj = UNI(cur.jj), c_kk = UNI(cur.kk), c_qq = UNI(cur.qq);
-    const int nf = iscol ? r0 * n1 : n2 * r2;
-    const int nv = iscol ? r0 : r2, nm = iscol ? n1 : n2, nch = (nm + 63) >> 6;
-    const int npart = nv * nch;
-    const int w = blockIdx.x;
-    if (npart > (int)gridDim.x) {       // the host sized the grid from its bound on the ranks: never expected; the run is repeated without teams
-        if (w == 0 && tid == 0) { atomicAdd(&P.ctl[3], 1); P.ctl[0] = 1; }
+    const WaveSlot s = wave_slot(P, gs, cur, h, dir, mode, lane);
+    if (s.npart > (int)gridDim.x) {     // the host sized the grid from its bound on the ranks: never expected; the run is repeated without teams
+        if (s.w == 0 && tid == 0) { atomicAdd(&P.ctl[3], 1); P.ctl[0] = 1; }
         return;
     }
-    if (w == 0 && tid == 0) halfstep_publish(gs, h, cur, turn, mode, nf, r1, npart);
-    if (w >= npart) return;
-    const int pv = w / nch, vmode = (w - pv * nch) * 64 + lane;        // varying pivot, mode index (0-based)
-    const bool live = vmode < nm;
-    const int A = p - 1, B = m - p - 1;
-    const int pl = iscol ? pv : c_ii - 1, qr = iscol ? c_qq - 1 : pv;         // left / right pivot of this unit
+    if (s.w == 0 && tid == 0) halfstep_publish(gs, h, cur, s.turn, mode, s.nf, s.r1, s.npart);
+    if (s.w >= s.npart) return;
+    const int p = s.p, first = s.first, pl = s.pl, qr = s.qr, A = p - 1, B = m - p - 1;      // pl, qr: left / right pivot of this unit
     const int n1m = UNI(P.n[1]);
     const double *nodes = P.par, *weights = P.par + n1m;                          // 0-based here
     // rows i = 0..A+1 of the triangle, RL slots each (slot 0: pair with dim p -- absent in row A+1 --, slot 1: with dim p+1,
@@ -1050,14 +882,11 @@ __global__ __launch_bounds__(64 * (4 * NBK + 2)) void k_halfstep_det(DevProb P, 
     const size_t NP = (size_t)P.de_npair, tsz = NP * P.RM;
     const double *TLg = P.deTL + (size_t)g * tsz + (size_t)pl * NP, *TRg = P.deTR + (size_t)g * tsz + (size_t)qr * NP;
     const double *ULg = P.deUL + ((size_t)g * P.RM + pl) * (m + 1);
-    const short *Lt = L_ptr(P, g, p - 1, first), *Rt = R_ptr(P, g, p + 1, first);
-    for (int x = tid; x < A; x += NT_) { const int ix = Lt[(size_t)x * P.RM + pl] - 1; xl[x] = nodes[ix]; wl[x] = weights[ix]; }
-    for (int x = tid; x < B; x += NT_) { const int ix = Rt[(size_t)x * P.RM + qr] - 1; xr[x] = nodes[ix]; wr[x] = weights[ix]; }
+    stage_pivot_rows(P, L_ptr(P, g, p - 1, first), R_ptr(P, g, p + 1, first), pl, qr, A, B, tid, NT_, nodes, weights, xl, wl, xr, wr);
     for (int x = RL + tid; x < 16 * BPR + 32; x += NT_) V[x] = 0.0;
     if (tid < 2) V[tid] = 0.0;
     for (int x = tid; x <= A + 2; x += NT_) UL[x] = (x <= A) ? ULg[x] : 1.0;
-    const int i1 = iscol ? (live ? vmode : 0) : c_jj - 1, i2 = iscol ? c_kk - 1 : (live ? vmode : 0);   // node index of dim p / p+1
-    const double x1 = nodes[i1], x2 = nodes[i2];
+    const double x1 = nodes[s.i1], x2 = nodes[s.i2];
     const int n16 = lane & 15;
     WStreamD<2> sl;
     double a = 1.0, u = 0.0, uln = 0.0;
@@ -1069,7 +898,7 @@ __global__ __launch_bounds__(64 * (4 * NBK + 2)) void k_halfstep_det(DevProb P, 
     if (wv == 1) uln = UL[0];
     if (wv < 2) __builtin_amdgcn_s_setprio(3);                        // the two serial roles go first on their SIMDs
 #ifdef TTX_STAMPS
-    const bool st_on = (g == DET_STAMPG % (int)gridDim.y) && w == 0;
+    const bool st_on = (g == DET_STAMPG % (int)gridDim.y) && s.w == 0;
     if (st_on && tid == 0) atomicAdd((unsigned long long *)&P.gs[0].nstamp[1], 1ull);
 #endif
     DET_T0();
@@ -1206,54 +1035,7 @@ __global__ __launch_bounds__(64 * (4 * NBK + 2)) void k_halfstep_det(DevProb P, 
     sr.init(TRg, B * (B + 1) / 2, ringR, lane);
     a = sr.chain_from_boundary(a, B * (B + 1) / 2, lane);
     DET_ACC(8);
-    const double w1 = weights[i1], w2 = weights[i2];
-    // ---- b-part (id 2) and the weights (:197-218), order of de_finish ----
-    const int id = P.ising_id;
-    double b = 0.0;
-    if (id == 2) {
-        double v = 1.0, ww = 1.0, vk = 1.0, wk = 1.0;
-        for (int j = B - 1; j >= 0; j--) { vk = vk * xr[j]; v = v + vk; }
-        vk = vk * x2; v = v + vk;
-        vk = vk * x1; v = v + vk;
-        for (int j = A - 1; j >= 0; j--) { vk = vk * xl[j]; v = v + vk; }
-        for (int j = 0; j < A; j++) { wk = wk * xl[j]; ww = ww + wk; }
-        wk = wk * x1; ww = ww + wk;
-        wk = wk * x2; ww = ww + wk;
-        for (int j = 0; j < B; j++) { wk = wk * xr[j]; ww = ww + wk; }
-        b = 1.0 / (v * ww);
-    }
-    double f = (id == 2) ? 2 * a * b : 2 * a;
-    for (int j = 0; j < A; j++) f = f * wl[j];
-    f = f * w1; f = f * w2;
-    for (int j = 0; j < B; j++) f = f * wr[j];
-    a = f;
-    // ---- fiber store, amax, residual, arg-max: as k_halfstep_de ----
-    const int u_ = iscol ? pv : vmode, v_ = iscol ? vmode : pv;        // col: (i, j) ; row: (k, q), 0-based
-    const int t = iscol ? (u_ + r0 * v_) : (u_ + n2 * v_);
-    if (live) (iscol ? P.acol : P.arow)[(size_t)g * P.RM * P.NM + t] = a;
-    const double mx = wave_max(live ? fabs(a) : 0.0);
-    if (lane == 0 && mode != 1) atomic_max_pos(&gs.amax, mx);          // :531 / :564
-    if (resid) {
-        const double *Cp = core_ptr(P, P.col, g, p, first), *Wq = core_ptr(P, P.row, g, p + 1, first);
-        double bb = a, ab = -1.0; int bi = INT_MAX;
-        if (live) {
-            if (iscol) {   // dgemv 'n', alpha=-1 (:538)
-                const double *c = Cp + u_ + (size_t)P.RM * v_;
-                const double *xq = Wq + (c_kk - 1) + (size_t)P.NM * (c_qq - 1);
-#pragma unroll 8
-                for (int s = 0; s < r1; s++) bb = bb + (-xq[P.SW * s]) * c[P.SS * s];
-            } else {       // dgemv 't', alpha=-1 (:571)
-                const double *wvp = Wq + u_ + (size_t)P.NM * v_;
-                const double *xc = Cp + (c_ii - 1) + (size_t)P.RM * (c_jj - 1);
-                double tt = 0.0;
-#pragma unroll 8
-                for (int s = 0; s < r1; s++) tt = tt + wvp[P.SW * s] * xc[P.SS * s];
-                bb = bb + (-1.0) * tt;
-            }
-            ab = fabs(bb); bi = t;
-        }
-        wave_argmax(ab, bb, bi);
-        if (lane == 0) { Partial pr; pr.absmax = ab; pr.val = bb; pr.idx = bi; pr.pad = 0; gs.Pt[h & 1][w] = pr; }
-    }
+    a = de_finish_split(P.ising_id, a, A, B, x1, x2, weights[s.i1], weights[s.i2], xl, wl, xr, wr);
+    wave_finish(P, gs, g, s, h, mode, a, lane);
     DET_ACC(9);
 }

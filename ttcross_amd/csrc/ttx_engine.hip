@@ -33,6 +33,7 @@
 #include "ttx_host_pool.h"
 #include "ttx_files.h"
 #include "ttx_kernels.h"
+#include "ttx_wavestep.h"
 #include "ttx_de.h"
 #include "ttx_mvn.h"
 #include "ttx_ttops.h"

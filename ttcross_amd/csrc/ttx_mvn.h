@@ -181,6 +181,11 @@ __device__ __forceinline__ double mvn_quadform(int m, const double *dv, int L, d
 }
 
 // grid = (RM * ceil(NM/64) wave slots, groups), 64 threads.  Same contract as k_halfstep (modes 0, 1, 2).
+// Its own copy of the wave half-step's frame (ttx_wavestep.h: wave_slot, wave_finish), kept on purpose: the quadratic form holds
+// 61 spilled SGPRs across its 16 000 instructions, and every shared form changed that and cost mvn128 time.  Per run of mvn128
+// exact, own text 1168.6 ms (parent 1168.7): slot and finish shared 1170.7, the slot filled a second time behind the quadratic
+// form 1178.4, slot as loaded (not wave-uniform) and finish shared 1171.7, slot shared and own finish 1170.6
+// (profiles/wavestep_frame_mi355x.txt).  A change to the frame is made there and here.
 __global__ __launch_bounds__(64) void k_halfstep_mvn(DevProb P, int h, int dir, int mode)
 {
     extern __shared__ __align__(16) double dyn[];
