@@ -474,6 +474,25 @@ int ttx_k_eval_arith(int32_t device, int32_t fun_id, int32_t d, const int32_t *n
 /* lottery2 (lib/rnd.f90:105-126) with unit weights except zero at the listed 1-based positions */
 int ttx_k_lottery(int32_t device, int32_t npnt, int32_t m, int32_t n, int32_t nz, const int32_t *zcol,
                   const int32_t *zrow, uint64_t rngpos, int32_t *points /* [2*npnt] */);
+/* The table evaluators of TTX_ARITH=fast (ttx_fast.h) on one hand-made bond p of a d-dimensional problem with n nodes per mode,
+ * element by element (tests/test_gpu_fast_elements.py).  fun_id ISING (D or E, nodes in [0,1]; par = nodes[n], weights[n], id) or
+ * MVN (par = nodes, aux as ttx_create takes it).  Lidx [rL][p-1] / Ridx [rR][d-p-1]: the pivots' 1-based mode indices.  chain 0:
+ * every table entry from scratch; 1: grown one dimension at a time towards the bond by the child update.  cap: rows of the decay
+ * tables the lottery route finds in LDS (0..d+1).  pts [npts][d]: full multi-indices for the one-wave point evaluator.
+ * Out, with FD = d+1, RM = max(rL, rR): near, dv [2][FD][RM] (side, row, pivot; near = decay vector / mvn: Y), piv [2][8][RM]
+ * (rows FP_T .. FP_N), the block [rL][n][n][rR] by the lottery route (lot), by column fibers (colf) and by row fibers (rowf),
+ * nfar [n*rR + rL*n]: far-vector entries above the cut per column fiber (k + n*q), then per row fiber (i + rL*j), pnt [npts]. */
+int ttx_k_fast_block(int32_t device, int32_t fun_id, int32_t d, int32_t n, const double *par, int32_t npar, const double *aux, int32_t naux,
+                     int32_t p, int32_t rL, const int32_t *Lidx, int32_t rR, const int32_t *Ridx, int32_t cap, int32_t chain,
+                     int64_t npts, const int32_t *pts, double *near, double *dv, double *piv, double *lot, double *colf, double *rowf,
+                     double *nfar, double *pnt);
+/* The same tables as a fast-mode run left them (read-only, after ttx_run): side 0 = left pivots of `bond` (first-1 .. last of the
+ * local group), side 1 = right pivots of `bond` (first .. last+1).  info = {r: live pivots of the bond, first, last}; with idx = NULL
+ * only first and last are set.  Compact copies of the live columns: idx [d][r] (row x = x-th dimension of the multi-index: dims 1..
+ * on the left, bond+1.. on the right), near / dv [d+1][r], piv [8][r]; cols = columns the buffers hold (maxrank is enough).  dv is
+ * written for mvn only. */
+int ttx_fast_tables(const ttx_engine *h, int32_t group, int32_t side, int32_t bond, int32_t cols, int32_t *info, int32_t *idx, double *near,
+                    double *dv, double *piv);
 
 /* exp() of the integrands (test_crs_stdnorm.f90:168, lib/mvn_pdf.f90:82): the device code restates the run-time
  * library's algorithm operation for operation (ttx_exp.h).  ttx_k_exp evaluates it on the device, ttx_exp_host the same

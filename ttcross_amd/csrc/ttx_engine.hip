@@ -3739,3 +3739,251 @@ extern "C" int ttx_k_lottery(int32_t device, int32_t npnt, int32_t m, int32_t n,
     (void)hipFree(dzc); (void)hipFree(dzr); (void)hipFree(dp);
     return TTX_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// ttx_k_fast_block: the table evaluators of TTX_ARITH=fast (ttx_fast.h) on one hand-made bond, element by element.  A minimal
+// DevProb (one group, one table slot per side: fpersist = 0) stands in for an engine; every value comes from the device functions
+// the sweep kernels call -- the kernels below only stage their inputs and store their results.
+// ------------------------------------------------------------------------------------------------
+struct FbArgs {
+    const int *Lidx, *Ridx;            // [rL][p-1], [rR][d-p-1] mode indices (1-based) of the pivots
+    int rL, rR, p, chain;
+    double *tNear[2], *tDv[2], *tPiv[2];   // second set of tables: a child entry is never written over its parent's
+};
+// one wave per pivot (grid 2*RM).  chain = 0: the entry from scratch; 1: the dimension farthest from the bond from scratch, then
+// one child step per dimension towards the bond, parent and child alternating between the two sets of tables so that the last
+// step lands in the tables proper
+template <int FUN>
+__global__ __launch_bounds__(64) void k_fb_tables(DevProb P, FbArgs A)
+{
+    extern __shared__ __align__(16) double dyn[];
+    const int lane = threadIdx.x, m = P.d, RM = P.RM, p = A.p;
+    const int side = (int)blockIdx.x / RM, c = (int)blockIdx.x % RM;
+    if (c >= (side == 0 ? A.rL : A.rR)) return;
+    const int len = side == 0 ? p - 1 : m - p - 1, d0 = side == 0 ? 0 : p + 1;      // d0: 0-based dimension of entry 0
+    const int *ix = (side == 0 ? A.Lidx : A.Ridx) + (size_t)c * len;
+    double *xs = dyn, *ws = dyn + m + 8;
+    double *nr[2] = {P.fNear[side] + c, A.tNear[side] + c}, *pv[2] = {P.fPiv[side] + c, A.tPiv[side] + c};
+    double *dv[2] = {FUN == FUN_MVN ? P.fDv[side] + c : nullptr, FUN == FUN_MVN ? A.tDv[side] + c : nullptr};
+    for (int k = lane; k < len; k += 64) {
+        if (FUN == FUN_MVN) xs[k] = P.par[ix[k] - 1] - P.aux[d0 + k];
+        else { xs[k] = P.par[ix[k] - 1]; ws[k] = P.par[P.n[1] + ix[k] - 1]; }
+    }
+    __syncthreads();
+    if (!A.chain || len == 0) {
+        if (FUN == FUN_MVN) mvn_entry_scratch(P, xs, len, d0, dv[0], nr[0], pv[0], lane);
+        else fast_entry_scratch(xs, ws, len, side, nr[0], pv[0], RM, lane);
+        return;
+    }
+    int e = side == 0 ? 0 : len - 1, b = (len - 1) & 1;
+    if (FUN == FUN_MVN) mvn_entry_scratch(P, xs + e, 1, d0 + e, dv[b], nr[b], pv[b], lane);
+    else fast_entry_scratch(xs + e, ws + e, 1, side, nr[b], pv[b], RM, lane);
+    for (int k = 1; k < len; k++) {
+        __syncthreads();                                   // the parent's entry is complete and visible to the wave
+        e = side == 0 ? k : len - 1 - k;
+        const int nb = b ^ 1;
+        if (FUN == FUN_MVN) mvn_entry_child(P, side, dv[b], nr[b], pv[b], k, d0 + e, xs[e], dv[nb], nr[nb], pv[nb], lane);
+        else fast_entry_child(nr[b], pv[b], xs[e], ws[e], nr[nb], pv[nb], RM, lane);
+        b = nb;
+    }
+}
+// lottery route: every element (i, j, k, q) of the block as one candidate; cap rows of the two decay tables in LDS
+template <int FUN>
+__global__ __launch_bounds__(TTX_BLK) void k_fb_lottery(DevProb P, FbArgs A, int cap, double *out)
+{
+    extern __shared__ __align__(16) double dyn[];
+    const int tid = threadIdx.x, RM = P.RM, n = P.n[1], p = A.p;
+    double *sNL = dyn, *sNR = dyn + (size_t)cap * RM;
+    if (FUN == FUN_ISING) {
+        const double *nL = P.fNear[0], *nR = P.fNear[1];
+        for (int x = tid; x < cap * RM; x += TTX_BLK) { const int c = x % RM; sNL[x] = (c < A.rL) ? nL[x] : 0.0; sNR[x] = (c < A.rR) ? nR[x] : 0.0; }
+    }
+    __syncthreads();
+    const int total = A.rL * n * n * A.rR;
+    for (int t = blockIdx.x * TTX_BLK + tid; t < total; t += gridDim.x * TTX_BLK) {
+        const int q = t % A.rR, k = (t / A.rR) % n, j = (t / (A.rR * n)) % n, i = t / (A.rR * n * n);
+        out[t] = (FUN == FUN_MVN) ? mvn_fast_value(P, 0, p, 1, i, j, k, q, mvn_fast_cross(P, 0, p, 1, i, q))
+                                  : de_fast_elem4(P, 0, p, 1, i, j, k, q, sNL, sNR, cap);
+    }
+}
+// fiber routes: one block per fiber.  Column fibers: block = (k, q) fixed, elements (i, j); row fibers: block = (i, j) fixed,
+// elements (k, q).  nfar: entries of the fixed side's far vector above the cut, per fiber (Ising)
+template <int FUN>
+__global__ __launch_bounds__(TTX_BLK) void k_fb_fiber(DevProb P, FbArgs A, int col, double *out, double *nfar)
+{
+    extern __shared__ __align__(16) double dyn[];
+    __shared__ int s_nfar; __shared__ double s_rfix;
+    const int tid = threadIdx.x, n = P.n[1], p = A.p, rL = A.rL, rR = A.rR, b = blockIdx.x;
+    const bool iscol = col != 0;
+    double *par = dyn, *far = dyn + ((P.npar + 1) & ~1), *Xv = far + ((max(P.FD, TTX_FNR) + 3) & ~1);
+    for (int x = tid; x < P.npar; x += TTX_BLK) par[x] = P.par[x];
+    const int vfix = iscol ? b / n : b % rL, xfix = iscol ? b % n : b / rL;
+    if (tid == 0) s_nfar = 0;
+    __syncthreads();
+    if (FUN == FUN_ISING) de_fast_fiber_stage(P, iscol ? 0 : 1, 0, p, 1, vfix, xfix, far, s_nfar, s_rfix, tid);
+    if (FUN == FUN_MVN) mvn_fast_fiber_stage(P, iscol, 0, p, 1, iscol ? rL : rR, vfix, Xv, tid);
+    __syncthreads();
+    if (tid == 0) nfar[b] = (double)s_nfar;
+    const int nf = iscol ? rL * n : n * rR;
+    for (int t = tid; t < nf; t += TTX_BLK) {
+        const int u = iscol ? t % rL : t % n, v = iscol ? t / rL : t / n;
+        const double a = (FUN == FUN_ISING) ? de_fast_fiber_elem(P, iscol, 0, p, 1, iscol ? u : v, iscol ? v : u, vfix, xfix, par, far, s_nfar, s_rfix)
+                                            : mvn_fast_fiber_elem(P, iscol, 0, p, 1, u, v, vfix, xfix, Xv);
+        const int i = iscol ? u : vfix, j = iscol ? v : xfix, k = iscol ? xfix : u, q = iscol ? vfix : v;
+        out[(((size_t)i * n + j) * n + k) * rR + q] = a;
+    }
+}
+// point route: one wave per full multi-index (1-based), as the boundary corners stage it
+template <int FUN>
+__global__ __launch_bounds__(64) void k_fb_point(DevProb P, const int *pts, double *out)
+{
+    extern __shared__ __align__(16) double dyn[];
+    const int lane = threadIdx.x, m = P.d;
+    double *xv = dyn, *wv = dyn + m + 8;
+    for (int x = lane; x < m; x += 64) {
+        const int ix = pts[(size_t)blockIdx.x * m + x] - 1;
+        if (FUN == FUN_MVN) xv[x] = P.par[ix] - P.aux[x];
+        else { xv[x] = P.par[ix]; wv[x] = P.par[P.n[1] + ix]; }
+    }
+    __syncthreads();
+    const double f = (FUN == FUN_MVN) ? mvn_fast_point_wave(P, xv, lane) : de_fast_point_wave(P.ising_id, m, xv, wv, lane);
+    if (lane == 0) out[blockIdx.x] = f;
+}
+
+template <int FUN>
+static void fb_launch(const DevProb &P, const FbArgs &A, int cap, int64_t npts, const int *dpts, double *dlot, double *dcol, double *drow, double *dnfar, double *dpnt)
+{
+    const int d = P.d, RM = P.RM;
+    hipLaunchKernelGGL(k_fb_tables<FUN>, dim3(2 * RM), dim3(64), sizeof(double) * 2 * (d + 8), 0, P, A);
+    const int nn = P.NM, total = A.rL * nn * nn * A.rR;
+    hipLaunchKernelGGL(k_fb_lottery<FUN>, dim3((total + TTX_BLK - 1) / TTX_BLK), dim3(TTX_BLK), sizeof(double) * ((2 * (size_t)cap + 1) * RM + 2), 0, P, A, cap, dlot);
+    const size_t lds = sizeof(double) * ((size_t)P.npar + 2 + std::max(P.FD, TTX_FNR) + 4 + RM + 2);
+    hipLaunchKernelGGL(k_fb_fiber<FUN>, dim3(nn * A.rR), dim3(TTX_BLK), lds, 0, P, A, 1, dcol, dnfar);
+    hipLaunchKernelGGL(k_fb_fiber<FUN>, dim3(A.rL * nn), dim3(TTX_BLK), lds, 0, P, A, 0, drow, dnfar + (size_t)nn * A.rR);
+    if (npts > 0) hipLaunchKernelGGL(k_fb_point<FUN>, dim3((unsigned)npts), dim3(64), sizeof(double) * 2 * (d + 8), 0, P, dpts, dpnt);
+}
+
+extern "C" int ttx_k_fast_block(int32_t device, int32_t fun_id, int32_t d, int32_t n, const double *par, int32_t npar, const double *aux, int32_t naux,
+                                int32_t p, int32_t rL, const int32_t *Lidx, int32_t rR, const int32_t *Ridx, int32_t cap, int32_t chain,
+                                int64_t npts, const int32_t *pts, double *near, double *dv, double *piv, double *lot, double *colf, double *rowf,
+                                double *nfar, double *pnt)
+{
+    const char *me = "ttx_k_fast_block";
+    if (fun_id != TTX_FUN_ISING && fun_id != TTX_FUN_MVN) return fail(TTX_EINVAL, "%s: fun_id %d has no table evaluator", me, fun_id);
+    if (!par || !near || !dv || !piv || !lot || !colf || !rowf || !nfar || npts < 0 || (npts > 0 && (!pts || !pnt))) return fail(TTX_EINVAL, "%s: null argument", me);
+    if (d < 2 || d > 4096 || n < 1 || n > 1024 || p < 1 || p > d - 1 || rL < 1 || rR < 1 || rL > 64 || rR > 64 || npts > 65535)
+        return fail(TTX_EINVAL, "%s: sizes out of range (d %d n %d p %d rL %d rR %d)", me, d, n, p, rL, rR);
+    const int FD = d + 1, RM = std::max(rL, rR), A_ = p - 1, B_ = d - p - 1;
+    if (cap < 0 || cap > FD) return fail(TTX_EINVAL, "%s: cap %d outside 0..d+1", me, cap);
+    if ((A_ > 0 && !Lidx) || (B_ > 0 && !Ridx)) return fail(TTX_EINVAL, "%s: null pivot table", me);
+    for (int64_t x = 0; x < (int64_t)rL * A_; x++) if (Lidx[x] < 1 || Lidx[x] > n) return fail(TTX_EINVAL, "%s: left index %d outside 1..n", me, Lidx[x]);
+    for (int64_t x = 0; x < (int64_t)rR * B_; x++) if (Ridx[x] < 1 || Ridx[x] > n) return fail(TTX_EINVAL, "%s: right index %d outside 1..n", me, Ridx[x]);
+    for (int64_t x = 0; x < npts * d; x++) if (pts[x] < 1 || pts[x] > n) return fail(TTX_EINVAL, "%s: point index %d outside 1..n", me, pts[x]);
+    DevProb P{};
+    if (fun_id == TTX_FUN_ISING) {
+        if (npar < 2 * n + 1) return fail(TTX_EINVAL, "%s: par too short", me);
+        P.ising_id = (int)par[2 * n];
+        if (P.ising_id != 2 && P.ising_id != 3) return fail(TTX_EINVAL, "%s: Ising id %d has no table evaluator", me, P.ising_id);
+        for (int j = 0; j < n; j++) if (!(par[j] >= 0.0 && par[j] <= 1.0)) return fail(TTX_EINVAL, "%s: node %g outside [0,1]", me, par[j]);
+    } else {
+        if (npar < n || !aux || naux < d + d * d + 1) return fail(TTX_EINVAL, "%s: mvn: par or aux too short", me);
+        P.mvn_norm = std::sqrt(powi(2.0 * 3.141592653589793, d) * aux[d + (size_t)d * d]);
+        if (!(P.mvn_norm > 0.0) || !std::isfinite(P.mvn_norm)) return fail(TTX_EINVAL, "%s: mvn normalisation is not a positive finite number", me);
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TTX_ENODEV, "no HIP device");
+    HIPCHECK(hipSetDevice(device));
+    const size_t tn = (size_t)FD * RM, tp = (size_t)TTX_FS * RM, nb = (size_t)rL * n * n * rR, nfib = (size_t)n * rR + (size_t)rL * n;
+    // one allocation of doubles: par | aux | auxS | 2 x (near, dv, piv) | the same again (second set) | lot | col | row | nfar | pnt
+    std::vector<double> hostd;
+    hostd.insert(hostd.end(), par, par + npar);
+    const size_t o_aux = hostd.size();
+    if (fun_id == TTX_FUN_MVN) {
+        hostd.insert(hostd.end(), aux, aux + (d + (size_t)d * d + 1));
+        const double *ic = aux + d;
+        for (int j = 0; j < d; j++) for (int i = 0; i < d; i++) hostd.push_back(0.5 * (ic[i + (size_t)d * j] + ic[j + (size_t)d * i]));   // as create_integrand_tables
+    }
+    const size_t o_S = o_aux + (fun_id == TTX_FUN_MVN ? d + (size_t)d * d + 1 : 0), o_tab = hostd.size();
+    const size_t o_out = o_tab + 4 * (2 * tn + tp), total = o_out + 3 * nb + nfib + (size_t)npts + 1;
+    double *dd = nullptr; int *di = nullptr;
+    std::vector<int> hosti(d + 2, n);
+    const size_t o_L = hosti.size();
+    hosti.insert(hosti.end(), Lidx, Lidx + (size_t)rL * A_);
+    const size_t o_R = hosti.size();
+    hosti.insert(hosti.end(), Ridx, Ridx + (size_t)rR * B_);
+    const size_t o_P = hosti.size();
+    hosti.insert(hosti.end(), pts, pts + (size_t)npts * d);
+    hosti.push_back(0);
+    HIPCHECK(hipMalloc((void **)&dd, sizeof(double) * total));
+    if (hipMalloc((void **)&di, sizeof(int) * hosti.size()) != hipSuccess) { (void)hipFree(dd); return fail(TTX_EHIP, "%s: hipMalloc failed", me); }
+    int rc = TTX_OK;
+    auto chk = [&](hipError_t e, const char *what) { if (e != hipSuccess && rc == TTX_OK) rc = fail(TTX_EHIP, "%s: %s failed: %s", me, what, hipGetErrorString(e)); };
+    chk(hipMemset(dd, 0, sizeof(double) * total), "hipMemset");
+    chk(hipMemcpy(dd, hostd.data(), sizeof(double) * hostd.size(), hipMemcpyHostToDevice), "hipMemcpy");
+    chk(hipMemcpy(di, hosti.data(), sizeof(int) * hosti.size(), hipMemcpyHostToDevice), "hipMemcpy");
+    P.d = d; P.RM = RM; P.NM = n; P.G = 1; P.NC = 1; P.fun_id = fun_id; P.npar = npar; P.arith = 1; P.FD = FD; P.fpersist = 0;
+    P.n = di; P.par = dd; P.aux = fun_id == TTX_FUN_MVN ? dd + o_aux : nullptr; P.auxS = fun_id == TTX_FUN_MVN ? dd + o_S : nullptr;
+    FbArgs A{};
+    A.Lidx = di + o_L; A.Ridx = di + o_R; A.rL = rL; A.rR = rR; A.p = p; A.chain = chain ? 1 : 0;
+    double *t = dd + o_tab;
+    for (int sd = 0; sd < 2; sd++) { P.fNear[sd] = t; t += tn; }
+    for (int sd = 0; sd < 2; sd++) { P.fDv[sd] = t; t += tn; }
+    for (int sd = 0; sd < 2; sd++) { P.fPiv[sd] = t; t += tp; }
+    for (int sd = 0; sd < 2; sd++) { A.tNear[sd] = t; t += tn; }
+    for (int sd = 0; sd < 2; sd++) { A.tDv[sd] = t; t += tn; }
+    for (int sd = 0; sd < 2; sd++) { A.tPiv[sd] = t; t += tp; }
+    double *dlot = dd + o_out, *dcol = dlot + nb, *drow = dcol + nb, *dnfar = drow + nb, *dpnt = dnfar + nfib;
+    if (rc == TTX_OK) {
+        if (fun_id == TTX_FUN_ISING) fb_launch<FUN_ISING>(P, A, cap, npts, di + o_P, dlot, dcol, drow, dnfar, dpnt);
+        else fb_launch<FUN_MVN>(P, A, cap, npts, di + o_P, dlot, dcol, drow, dnfar, dpnt);
+        chk(hipGetLastError(), "launch");
+        chk(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    }
+    if (rc == TTX_OK) {
+        chk(hipMemcpy(near, P.fNear[0], sizeof(double) * 2 * tn, hipMemcpyDeviceToHost), "hipMemcpy");
+        chk(hipMemcpy(dv, P.fDv[0], sizeof(double) * 2 * tn, hipMemcpyDeviceToHost), "hipMemcpy");
+        chk(hipMemcpy(piv, P.fPiv[0], sizeof(double) * 2 * tp, hipMemcpyDeviceToHost), "hipMemcpy");
+        chk(hipMemcpy(lot, dlot, sizeof(double) * nb, hipMemcpyDeviceToHost), "hipMemcpy");
+        chk(hipMemcpy(colf, dcol, sizeof(double) * nb, hipMemcpyDeviceToHost), "hipMemcpy");
+        chk(hipMemcpy(rowf, drow, sizeof(double) * nb, hipMemcpyDeviceToHost), "hipMemcpy");
+        chk(hipMemcpy(nfar, dnfar, sizeof(double) * nfib, hipMemcpyDeviceToHost), "hipMemcpy");
+        if (npts > 0) chk(hipMemcpy(pnt, dpnt, sizeof(double) * npts, hipMemcpyDeviceToHost), "hipMemcpy");
+    }
+    (void)hipFree(dd); (void)hipFree(di);
+    return rc;
+}
+
+// the fast evaluators' tables of one bond as a run left them (read-only): side 0 = left pivots of bond `bond` (first-1 .. last of
+// the group), side 1 = right pivots of bond `bond` (first .. last+1).  info = {live pivots r of the bond, first, last}; with idx = null
+// only info[1..2] are set (any bond).  Compact copies, r columns each: idx [d][r], near / dv [d+1][r], piv [8][r]; cols = columns the
+// caller's buffers hold
+extern "C" int ttx_fast_tables(const ttx_engine *h, int32_t group, int32_t side, int32_t bond, int32_t cols, int32_t *info, int32_t *idx, double *near,
+                               double *dv, double *piv)
+{
+    if (!h || !info) return fail(TTX_EINVAL, "ttx_fast_tables: null argument");
+    if (!h->ran) return fail(TTX_ESTATE, "ttx_fast_tables: run first");
+    const DevProb &P = h->P;
+    if (!P.arith || !P.fNear[0] || !P.fpersist) return fail(TTX_ESTATE, "ttx_fast_tables: this engine keeps no per-bond tables (TTX_ARITH=fast with Ising D/E or mvn)");
+    if (group < 0 || group >= h->G || side < 0 || side > 1) return fail(TTX_EINVAL, "ttx_fast_tables: group %d / side %d out of range", group, side);
+    const int first = h->own[h->g0 + group], last = h->own[h->g0 + group + 1] - 1;
+    info[0] = 0; info[1] = first; info[2] = last;
+    if (!idx) return TTX_OK;
+    if (!near || !piv || (P.fDv[side] && !dv)) return fail(TTX_EINVAL, "ttx_fast_tables: null argument");
+    const int lo = side == 0 ? first - 1 : first, hi = side == 0 ? last : last + 1;
+    if (bond < lo || bond > hi) return fail(TTX_EINVAL, "ttx_fast_tables: bond %d outside %d..%d of group %d, side %d", bond, lo, hi, group, side);
+    const int d = h->d;
+    const size_t RM = h->RM, slot = (size_t)group * h->NC + (size_t)(side == 0 ? bond - first + 1 : bond - first);     // fast_slot, L_ptr / R_ptr
+    std::vector<int> rr(d + 2);
+    HIPCHECK(hipMemcpy(rr.data(), P.r + (size_t)group * (d + 2), sizeof(int) * (d + 2), hipMemcpyDeviceToHost));
+    const int r = rr[bond];
+    if (r < 1 || (size_t)r > RM || r > cols) return fail(TTX_EINVAL, "ttx_fast_tables: bond %d has %d pivots, the buffers hold %d", bond, r, cols);
+    info[0] = r;
+    std::vector<short> tab((size_t)d * RM);
+    HIPCHECK(hipMemcpy(tab.data(), (side == 0 ? P.L : P.R) + slot * (size_t)d * RM, sizeof(short) * tab.size(), hipMemcpyDeviceToHost));
+    for (int x = 0; x < d; x++) for (int c = 0; c < r; c++) idx[(size_t)x * r + c] = tab[(size_t)x * RM + c];
+    const size_t w = sizeof(double) * r, pitch = sizeof(double) * RM;
+    HIPCHECK(hipMemcpy2D(near, w, P.fNear[side] + slot * (size_t)P.FD * RM, pitch, w, P.FD, hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy2D(piv, w, P.fPiv[side] + slot * (size_t)TTX_FS * RM, pitch, w, TTX_FS, hipMemcpyDeviceToHost));
+    if (P.fDv[side]) HIPCHECK(hipMemcpy2D(dv, w, P.fDv[side] + slot * (size_t)P.FD * RM, pitch, w, P.FD, hipMemcpyDeviceToHost));
+    return TTX_OK;
+}

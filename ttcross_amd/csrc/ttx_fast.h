@@ -22,8 +22,13 @@
 // dj, dk with coefficients (S dL_i)_p, (S dR_q)_p, ...).  Per pivot: Y = S d (k_fast_tables); per element O(1) plus one
 // dot product of length p per (i, q) pair.  S is symmetrised on the host ((S + S')/2: the same quadratic form).
 //
-// Parity of this mode is by tolerance (tests/test_gpu_fast.py): same sweeps, leading sweeps with identical pivots, values to
-// 2e-13, integrals to 1e-12 of the exact mode / the reference.
+// Parity of this mode is by tolerance.  tests/test_gpu_fast.py: the one-thread evaluator (de_fast_rho) to 1e-12 of the exact
+// integrand; runs against the exact mode: identical pivots over the leading sweeps, per-sweep values to 1e-11, integrals to 5e-12
+// (1e-12 of the reference's at D_256).  tests/test_gpu_fast_elements.py: every function below through ttx_k_fast_block -- every
+// table entry (FP_N for equality) and every element of a block by the lottery, column-fiber, row-fiber and point routes against an
+// mpmath reference, each at its own first-order rounding bound (tests/fast_ref.py; a few 1e-12 relative at d = 70), for tables made
+// from scratch and grown by the child updates, with decay counts on both sides of TTX_FNR and of 64, arguments exactly at the cut,
+// nodes 0 and 1; and every table entry a real run leaves behind (ttx_fast_tables).
 #pragma once
 #define TTX_FCUT 5.551115123125783e-17      // 2^-54
 // rows of fPiv
@@ -315,6 +320,64 @@ __device__ __forceinline__ double mvn_fast_value(const DevProb &P, int g, int p,
     const double sjj = S[(size_t)(p - 1) * (m + 1)], skk = S[(size_t)p * (m + 1)], sjk = S[(size_t)(p - 1) + (size_t)m * p];
     const double Q = (QL + QR + 2 * X) + 2 * (dj * yj + dk * yk) + (sjj * dj * dj + skk * dk * dk + 2 * sjk * dj * dk);
     return ttx_exp(-0.5 * Q) / P.mvn_norm;
+}
+// ---- fiber route of a half-step (k_halfstep): one side's pivot and its neighbouring mode index are FIXED (pivot vfix, mode index
+// xfix, 0-based), the other side's pivot and the free mode index vary.  fside = the varying side (0: column fiber, 1: row fiber).
+// Staging by the whole block (TTX_BLK threads, contains a barrier; the caller puts one more barrier behind it): the fixed side as
+// the decay vector far[0..s_nfar) = (1, xf * near_O[t]) in LDS, the number of its entries above the cut, and rho of the ranges of
+// the fixed side that begin / end at its mode index next to the free dim times the fixed pivot's T.
+__device__ __forceinline__ void de_fast_fiber_stage(const DevProb &P, int fside, int g, int p, int first, int vfix, int xfix, double *far, int &s_nfar,
+                                                    double &s_rfix, int tid)
+{
+    const int bO = fside == 0 ? p + 1 : p - 1;             // the bond whose pivot set holds the fixed pivot
+    const double *nearO = fast_near(P, 1 - fside, g, bO, first) + vfix, *pO = fast_piv(P, 1 - fside, g, bO, first) + vfix;
+    const int cntO = (int)pO[FP_N * P.RM];
+    const double xf = P.par[xfix];
+    if (tid == 0) far[0] = 1.0;
+    for (int b = tid; b < cntO; b += TTX_BLK) far[1 + b] = xf * nearO[(size_t)b * P.RM];
+    __syncthreads();
+    if (tid < 64) {          // ranges of the fixed side that begin / end at its mode index next to the free dim; entries above the cut
+        double N = 1.0, D = 1.0; int cnt = 0;
+        for (int b0 = 1; b0 <= cntO; b0 += 64) {
+            const int b = b0 + tid;
+            const double c = (b <= cntO) ? far[b] : 0.0;
+            const bool on = c > TTX_FCUT;
+            if (on) { N = N * (1.0 - c); D = D * (1.0 + c); }
+            cnt += __popcll(__ballot(on));
+        }
+        N = wave_prod(N); D = wave_prod(D);
+        if (tid == 0) { s_nfar = 1 + cnt; s_rfix = pO[FP_T * P.RM] * (N / D); }
+    }
+}
+// one fiber element by one thread: varying pivot pv, free mode index nd (0-based); par = the block's LDS copy of P.par
+__device__ __forceinline__ double de_fast_fiber_elem(const DevProb &P, bool iscol, int g, int p, int first, int pv, int nd, int vfix, int xfix,
+                                                     const double *par, const double *far, int s_nfar, double s_rfix)
+{
+    const int fside = iscol ? 0 : 1, n1m = P.n[1];
+    const int bV = fside == 0 ? p - 1 : p + 1;
+    const double *nearV = fast_near(P, fside, g, bV, first) + pv, *pV = fast_piv(P, fside, g, bV, first) + pv;
+    const double *pO = fast_piv(P, 1 - fside, g, fside == 0 ? p + 1 : p - 1, first) + vfix;
+    const double xn = par[nd], xf = par[xfix];
+    double N = 1.0, D = 1.0;
+    if (s_nfar <= TTX_FNR) {
+        FarReg C;
+        far_load(C, far, s_nfar);
+        de_fast_span_reg(nearV, (size_t)P.RM, (int)pV[FP_N * P.RM], xn, C, N, D);
+    } else
+        de_fast_span(nearV, (size_t)P.RM, (int)pV[FP_N * P.RM], xn, far, s_nfar, N, D);
+    const double rho = pV[FP_T * P.RM] * (N / D) * s_rfix;
+    return iscol ? de_fast_value(P.ising_id, P.RM, rho, pV, xn, par[n1m + nd], xf, par[n1m + xfix], pO)
+                 : de_fast_value(P.ising_id, P.RM, rho, pO, xf, par[n1m + xfix], xn, par[n1m + nd], pV);
+}
+// mvn: the cross terms of the nv varying pivots with the fixed pivot into Xv (LDS) by the whole block; then one element (u, v) =
+// column fiber: (left pivot, j), row fiber: (k, right pivot)
+__device__ __forceinline__ void mvn_fast_fiber_stage(const DevProb &P, bool iscol, int g, int p, int first, int nv, int vfix, double *Xv, int tid)
+{
+    for (int v_ = tid; v_ < nv; v_ += TTX_BLK) Xv[v_] = iscol ? mvn_fast_cross(P, g, p, first, v_, vfix) : mvn_fast_cross(P, g, p, first, vfix, v_);
+}
+__device__ __forceinline__ double mvn_fast_fiber_elem(const DevProb &P, bool iscol, int g, int p, int first, int u, int v, int vfix, int xfix, const double *Xv)
+{
+    return iscol ? mvn_fast_value(P, g, p, first, u, v, xfix, vfix, Xv[u]) : mvn_fast_value(P, g, p, first, vfix, xfix, u, v, Xv[v]);
 }
 // mvn table entry of ONE pivot FROM SCRATCH by one wave: xs = dv = x - mu over the pivot's len dims (LDS, visible to the wave),
 // d0 = 0-based dimension of entry 0; columns (stride RM) dvo[len], Y[m] = S dv, piv[FP_T] = dv' S dv

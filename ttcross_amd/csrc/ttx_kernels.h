@@ -1491,31 +1491,8 @@ __global__ __launch_bounds__(TTX_BLK) void k_halfstep(DevProb P, int h, int dir,
     __shared__ int s_nfar; __shared__ double s_rfix;
     const int fside = iscol ? 0 : 1;                                         // the varying side
     const int vfix = iscol ? cur.qq - 1 : cur.ii - 1, xfix = iscol ? cur.kk - 1 : cur.jj - 1;   // fixed pivot (other side), fixed mode index next to the free dim
-    if (fastp && FUN == FUN_ISING) {
-        const int bO = fside == 0 ? p + 1 : p - 1;             // the bond whose pivot set holds the fixed pivot
-        const double *nearO = fast_near(P, 1 - fside, g, bO, first) + vfix, *pO = fast_piv(P, 1 - fside, g, bO, first) + vfix;
-        const int cntO = (int)pO[FP_N * P.RM];
-        const double xf = P.par[xfix];
-        if (tid == 0) far[0] = 1.0;
-        for (int b = tid; b < cntO; b += TTX_BLK) far[1 + b] = xf * nearO[(size_t)b * P.RM];
-        __syncthreads();
-        if (tid < 64) {          // ranges of the fixed side that begin / end at its mode index next to the free dim; entries above the cut
-            double N = 1.0, D = 1.0; int cnt = 0;
-            for (int b0 = 1; b0 <= cntO; b0 += 64) {
-                const int b = b0 + tid;
-                const double c = (b <= cntO) ? far[b] : 0.0;
-                const bool on = c > TTX_FCUT;
-                if (on) { N = N * (1.0 - c); D = D * (1.0 + c); }
-                cnt += __popcll(__ballot(on));
-            }
-            N = wave_prod(N); D = wave_prod(D);
-            if (tid == 0) { s_nfar = 1 + cnt; s_rfix = pO[FP_T * P.RM] * (N / D); }
-        }
-    }
-    if (fastp && FUN == FUN_MVN) {
-        const int nv = iscol ? r0 : r2;
-        for (int v_ = tid; v_ < nv; v_ += TTX_BLK) Xv[v_] = iscol ? mvn_fast_cross(P, g, p, first, v_, vfix) : mvn_fast_cross(P, g, p, first, vfix, v_);
-    }
+    if (fastp && FUN == FUN_ISING) de_fast_fiber_stage(P, fside, g, p, first, vfix, xfix, far, s_nfar, s_rfix, tid);
+    if (fastp && FUN == FUN_MVN) mvn_fast_fiber_stage(P, iscol, g, p, first, iscol ? r0 : r2, vfix, Xv, tid);
     __syncthreads();      // par is read below when staging values
     if (usev) {
         // rows: [0 .. vcols) varying index, row vcols = fixed side; each row: VS node values then VS weight values
@@ -1570,23 +1547,9 @@ __global__ __launch_bounds__(TTX_BLK) void k_halfstep(DevProb P, int h, int dir,
     if (live) {
         if (iscol) { u = t % r0; v = t / r0; } else { u = t % n2; v = t / n2; }
         if (fastp && FUN == FUN_ISING) {
-            const int pv = iscol ? u : v, nd = iscol ? v : u;                // varying pivot, free mode index (0-based)
-            const int bV = fside == 0 ? p - 1 : p + 1;
-            const double *nearV = fast_near(P, fside, g, bV, first) + pv, *pV = fast_piv(P, fside, g, bV, first) + pv;
-            const double *pO = fast_piv(P, 1 - fside, g, fside == 0 ? p + 1 : p - 1, first) + vfix;
-            const double xn = par[nd], xf = par[xfix];
-            double N = 1.0, D = 1.0;
-            if (s_nfar <= TTX_FNR) {
-                FarReg C;
-                far_load(C, far, s_nfar);
-                de_fast_span_reg(nearV, (size_t)P.RM, (int)pV[FP_N * P.RM], xn, C, N, D);
-            } else
-                de_fast_span(nearV, (size_t)P.RM, (int)pV[FP_N * P.RM], xn, far, s_nfar, N, D);
-            const double rho = pV[FP_T * P.RM] * (N / D) * s_rfix;
-            a = iscol ? de_fast_value(P.ising_id, P.RM, rho, pV, xn, par[n1m + nd], xf, par[n1m + xfix], pO)
-                      : de_fast_value(P.ising_id, P.RM, rho, pO, xf, par[n1m + xfix], xn, par[n1m + nd], pV);
+            a = de_fast_fiber_elem(P, iscol, g, p, first, iscol ? u : v, iscol ? v : u, vfix, xfix, par, far, s_nfar, s_rfix);
         } else if (fastp && FUN == FUN_MVN) {
-            a = iscol ? mvn_fast_value(P, g, p, first, u, v, xfix, vfix, Xv[u]) : mvn_fast_value(P, g, p, first, vfix, xfix, u, v, Xv[v]);
+            a = mvn_fast_fiber_elem(P, iscol, g, p, first, u, v, vfix, xfix, Xv);
         } else if (usev) {
             const double *fn = vbase + (size_t)vcols * 2 * VS, *fw = fn + VS;
             if (iscol) { const double *rn = vbase + (size_t)u * 2 * VS; a = f_ising_c3v(m, p - 1, rn, rn + VS, par[v], par[n1m + v], fn, fw); }

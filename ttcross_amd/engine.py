@@ -577,6 +577,26 @@ class TTCross:
             _check(L.ttx_get_tapes(self._h, _ip(out), out.size))
         return out
 
+    def fast_tables(self, group, side=None, bond=None, cols=None):
+        """Tables of the fast evaluators as the run left them (include/ttx.h: ttx_fast_tables).  Without side / bond: (first, last)
+        of the local group.  Else dict(r, idx [len][r], near, dv [d+1][r], piv [8][r]) of the left (side 0) / right (side 1) pivots
+        of `bond`; cols: an upper bound of the bond's rank (default 4096)."""
+        L = load_library()
+        L.ttx_fast_tables.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32)] + [POINTER(c_double)] * 3
+        info = np.zeros(3, dtype=np.int32)
+        if side is None:
+            _check(L.ttx_fast_tables(self._h, group, 0, 0, 0, _ip(info), None, None, None, None))
+            return int(info[1]), int(info[2])
+        cols = 4096 if cols is None else int(cols)
+        d = self.d
+        idx = np.zeros(d * cols, dtype=np.int32)
+        near, dv, piv = np.zeros((d + 1) * cols), np.zeros((d + 1) * cols), np.zeros(8 * cols)
+        _check(L.ttx_fast_tables(self._h, group, side, bond, cols, _ip(info), _ip(idx), _dp(near), _dp(dv), _dp(piv)))
+        r = int(info[0])
+        ln = bond if side == 0 else d - bond
+        return dict(r=r, idx=idx[:d * r].reshape(d, r)[:ln], near=near[:(d + 1) * r].reshape(d + 1, r), dv=dv[:(d + 1) * r].reshape(d + 1, r),
+                    piv=piv[:8 * r].reshape(8, r))
+
     def ranks(self):
         r = np.zeros(self.d + 1, dtype=np.int32)
         _check(load_library().ttx_get_ranks(self._h, _ip(r)))
@@ -942,6 +962,31 @@ def k_lottery(npnt, m, n, zcol, zrow, rngpos=0, device=0):
     pts = np.zeros(2 * npnt, dtype=np.int32)
     _check(load_library().ttx_k_lottery(device, npnt, m, n, zc.size, _ip(zc), _ip(zr), rngpos, _ip(pts)))
     return pts.reshape(2, npnt)
+
+
+def k_fast_block(fun_id, d, n, par, p, left, right, cap, mode="scratch", aux=None, points=None, device=0):
+    """The table evaluators of TTX_ARITH=fast (csrc/ttx_fast.h) on one hand-made bond p (include/ttx.h: ttx_k_fast_block).
+    left [rL][p-1] / right [rR][d-p-1]: 1-based mode indices of the pivots; mode 'scratch' or 'chain'; cap: decay-table rows in
+    LDS for the lottery route.  Returns near, dv [2][d+1][RM], piv [2][8][RM], the block [rL][n][n][rR] by the three routes
+    (lottery, col, row), nfar_col [rR][n], nfar_row [n][rL] and point [npts]."""
+    par = np.ascontiguousarray(par, dtype=np.float64)
+    aux_ = None if aux is None else np.ascontiguousarray(aux, dtype=np.float64)
+    rL, rR = len(left), len(right)
+    left = np.ascontiguousarray(left, dtype=np.int32).reshape(rL, p - 1)
+    right = np.ascontiguousarray(right, dtype=np.int32).reshape(rR, d - p - 1)
+    pts = np.zeros((0, d), dtype=np.int32) if points is None else np.ascontiguousarray(points, dtype=np.int32).reshape(-1, d)
+    RM, FD = max(rL, rR), d + 1
+    near, dv, piv = np.zeros((2, FD, RM)), np.zeros((2, FD, RM)), np.zeros((2, 8, RM))
+    lot, col, row = (np.zeros((rL, n, n, rR)) for _ in range(3))
+    nfar, pnt = np.zeros(n * rR + rL * n), np.zeros(max(pts.shape[0], 1))
+    L = load_library()
+    L.ttx_k_fast_block.argtypes = ([c_int32] * 4 + [POINTER(c_double), c_int32, POINTER(c_double), c_int32, c_int32, c_int32, POINTER(c_int32), c_int32,
+                                   POINTER(c_int32), c_int32, c_int32, c_int64, POINTER(c_int32)] + [POINTER(c_double)] * 8)
+    _check(L.ttx_k_fast_block(device, fun_id, d, n, _dp(par), par.size, _dp(aux_), 0 if aux_ is None else aux_.size, p, rL, _ip(left), rR, _ip(right),
+                              cap, {"scratch": 0, "chain": 1}[mode], pts.shape[0], _ip(pts), _dp(near), _dp(dv), _dp(piv), _dp(lot), _dp(col),
+                              _dp(row), _dp(nfar), _dp(pnt)))
+    return dict(near=near, dv=dv, piv=piv, lottery=lot, col=col, row=row, nfar_col=nfar[:n * rR].reshape(rR, n),
+                nfar_row=nfar[n * rR:].reshape(n, rL), point=pnt[:pts.shape[0]])
 
 
 def k_exp(x, device=0):
