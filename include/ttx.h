@@ -384,6 +384,60 @@ int ttx_sample(ttx_engine *h, int64_t npts, const double *u /* [npts][d] */, con
 int ttx_sample_dev(ttx_engine *h, int64_t npts, const double *u, const double *w, const int32_t *fixed, int32_t *ind, double *logq, double *val);
 int ttx_sample_last(const ttx_engine *h, double *ms_head, double *bytes_head, double *ms_draw, int64_t *nfailed);
 
+/* The largest elements of the resident train by a beam search along the train, on the device (ttcross_amd/csrc/ttx_topk.h), with
+ * an upper bound on everything the search discarded.  Modes are 1-based, G_k is core k, r_0 = r_d = 1.
+ *   K     : rows wanted, 1 .. 4096, and K max n_k <= 2^24 (the score sheet of one mode is kept in work space)
+ *   which : TTX_TOPK_ABS, TTX_TOPK_MAX, TTX_TOPK_MIN: how the returned rows are ORDERED.  The search itself always ranks by absolute size
+ *   fixed : d entries, 0 = the mode is searched, f in 1..n_k = the mode is held at index f; NULL = all searched (as ttx_sample's)
+ *   mode  : TTX_EVAL_EXACT scores by plain loops (the checker), TTX_EVAL_MFMA on the fp64 matrix cores, TTX_EVAL_AUTO lets the
+ *           engine choose by the flops of the call (ttx_topk_last tells what ran)
+ *   ind   : [K][d], 1-based, the layout ttx_ijk_batch reads;  val : [K];  nfound, bound : one number each
+ * Definition.  I_k is 1..n_k for a searched mode and {f_k} for a fixed one.  Prefix Gram matrices: P_0 = [1],
+ *   P_k = sum over i in I_k of G_k(:, i, :)^T P_(k-1) G_k(:, i, :)   (r_k x r_k; ascending i).
+ * For a vector y of length r_(k-1), y^T P_(k-1) y is the squared 2-norm of the slice of the tensor over all prefixes in
+ * I_1 x .. x I_(k-1) whose suffix has the running vector y, whether or not the train was orthogonalised.
+ * Search from the LAST mode to the first, so the running state is dtt_ijk's own chain.  C_(d+1) holds one candidate, the empty
+ * suffix with x = [1].  For k = d .. 1 every candidate c of C_(k+1), in its order, and every i of I_k, ascending, give
+ *   y = G_k(:, i, :) x_c   and the score   s(c, i) = sqrt(max(0, y^T P_(k-1) y))   at the flat position c |I_k| + i.
+ * C_k is the K pairs with the largest score (all pairs if there are no more than K), kept in ascending flat position; ties go to the
+ * smaller flat position, a NaN score ranks below every number, +Inf first.  bound_k is the largest score among the pairs not
+ * kept, 0 if all were kept.  The x of a kept pair is formed by the operation sequence of ttx_ijk_batch's TTX_EVAL_EXACT (sums from
+ * 0.0 over ascending b, separate multiply and add, two rows per lane above rank 64; x_d is a copy of G_d(:, i_d, 1)) -- in BOTH
+ * modes: only the scores come from the matrix cores.  Hence val = x_1(1) equals ttx_ijk_batch(ind, TTX_EVAL_EXACT) bit for bit.
+ * At k = 1 the score is |y| (r_0 = 1, P_0 = [1]); under TTX_EVAL_EXACT y is formed in the chain's own order, so the score is |val|.
+ * TTX_EVAL_EXACT sums z = P y over ascending columns from 0.0 and adds y(a) z(a) per lane over a = lane, lane + 64 and across the
+ * lanes in xor steps 32 .. 1; TTX_EVAL_MFMA takes v_mfma_f64_16x16x4_f64's own order.  The two agree to rounding.
+ * Outputs.  nfound = |C_1| = min(K, prod |I_k|).  The first nfound rows of ind / val are ordered by `which` (ABS: |val| descending,
+ * MAX: val descending, MIN: val ascending; a NaN value after every number), ties by the lexicographically smaller index row, so
+ * the order does not depend on the internal candidate order.  The remaining rows are zeros and 0.0.  bound = max_k bound_k; if any
+ * score of the call was NaN, bound is NaN.
+ * Guarantee.  |T(prefix, suffix)| is at most the 2-norm of the slice over the prefixes, so every element of the tensor at the
+ * fixed indices that is not among the returned ones has |T(i)| <= bound, up to the rounding of the scores.  Hence bound <= |val|
+ * of the last row (ordered by TTX_TOPK_ABS) proves that the rows are the true top nfound by absolute size, and bound <= |val[0]|
+ * proves the maximum alone.  On a peaked, density-like train K = 1 may already prove the maximum; on a random train the bound
+ * proves nothing until K approaches an exhaustive search.  The rounding of the Gram route grows with the conditioning of P: a
+ * score is the root of a difference of large terms when P is ill-conditioned.  After ttx_ort P is a multiple of the identity to
+ * rounding and the scores are as accurate as the chain; nothing in the call requires ttx_ort.
+ * Safety: a selection compares 64-bit keys (the score's bit pattern + 1, NaN = 0), every index is formed from positions and counts
+ * and a stored position is range-checked where it is read: whatever the cores hold (NaN, Inf) every index written lies in range
+ * and no read leaves its table.  No floating-point atomics, no sum whose order depends on the grid: a call repeats bit for bit
+ * in either mode (integer atomics count keys and take the maximum key).
+ * TTX_EINVAL: null nfound / ind / val / bound, K outside 1..4096, unknown which or mode (all before the engine is looked at); a
+ * fixed entry outside 0..n_k, K max n_k > 2^24, ranks above 128 (before any launch).  TTX_ESTATE: an engine without a train; a
+ * multi-process engine is refused as by ttx_ijk (a replica, ttx_replicate, is accepted).  The train and the engine's other work
+ * space are not modified.  Everything is enqueued on the engine's stream; the call synchronises after every mode (the timers) and
+ * before it returns.
+ * ttx_topk_last: of the last call on this engine, the milliseconds (HIP events, summed over the modes) of the Gram chain, of the
+ * scoring launches and of the selection launches (radix select, compaction and the advance of the kept pairs),
+ * flops = 2 sum_k |C_(k+1)| |I_k| r_(k-1) (r_k + r_(k-1)), and the mode that ran (-1: none yet).  Any pointer may be NULL.
+ * Added without a new ttx_version: look the symbols up. */
+#define TTX_TOPK_ABS 0   /* rank the results by |T(i)|, largest first */
+#define TTX_TOPK_MAX 1   /* by T(i), largest first  */
+#define TTX_TOPK_MIN 2   /* by T(i), smallest first */
+int ttx_topk(ttx_engine *h, int32_t K, int32_t which, const int32_t *fixed /* [d] or NULL */, int32_t mode,
+             int32_t *nfound, int32_t *ind /* [K][d], 1-based */, double *val /* [K] */, double *bound);
+int ttx_topk_last(const ttx_engine *h, double *ms_gram, double *ms_score, double *ms_select, double *flops, int32_t *mode_ran);
+
 /* The finalised train of a MULTI-PROCESS job gathered onto EVERY process as a new single-process engine (same integrand, ranks,
  * RNG position; *out is owned by the caller: ttx_destroy).  Collective over the job's transport (each process contributes the
  * cores it holds; the others arrive by a SUM all-reduce into zero-filled slots, which is exact).  The reference's dtt_accchk,

@@ -51,6 +51,7 @@ static cluster_kernel_t cluster_kernel(int var)
 #include "ttx_modeapply.h"
 #include "ttx_algebra.h"
 #include "ttx_sample.h"
+#include "ttx_topk.h"
 #include "ttx_trainfun.h"
 
 static thread_local std::string g_err;
@@ -114,7 +115,9 @@ static int rccl_load()
 // Operations on the resident train (ttx_eval.h, ttx_contract.h, ttx_algebra.h, ttx_sample.h, ttx_modeapply.h) share one table of device work space
 // per engine, grown on demand (buf_reserve), freed in ttx_destroy.  A slot belongs to one role; two roles share a slot only where no
 // single call uses both, because a second buf_reserve of a slot may move what the first one handed out.  ttx_sample is the widest
-// call: SC_TRAIN, SC_META, SC_W, SC_M, SC_VEC, SC_H, SC_ROW, SC_CNT and the staging slots are all live in it.
+// call: SC_TRAIN, SC_META, SC_W, SC_M, SC_VEC, SC_H, SC_ROW, SC_CNT and the staging slots are all live in it.  ttx_topk keeps SC_TRAIN,
+// SC_META (its per-mode tables) and all seven SC_K* slots live from its first launch to its last copy, reserves each of them once,
+// before the first launch, and touches no other slot: what ttx_sample or ttx_marginals left in theirs stays as it was.
 enum {
     SC_TRAIN,                           // the EvTrain block (ev_train): evaluation and sampling
     SC_META,                            // a call's tables (OpMeta): contraction, marginals, sampling; the AlgBlk table of the algebra
@@ -125,6 +128,8 @@ enum {
     SC_H, SC_ROW, SC_CNT,               // sampling: head tables, global rows of long modes, the failure counter
     SC_TFUN, SC_TVAL,                   // TTX_FUN_TRAINS: the operands' blocks (core pointers, ranks) of a run, the values for a loaded combiner
     SC_MAT,                             // ttx_mode_apply: the matrices of the applied modes (its tables go to SC_META)
+    SC_KP, SC_KW, SC_KS, SC_KX,         // ttx_topk: the Gram matrices P_0 .. P_(d-1), the W of a Gram step, a mode's score sheet (keys), the two state buffers
+    SC_KREC, SC_KSEL, SC_KOUT,          // ttx_topk: the kept positions of every mode, the selection's state (words, chunk counts, histogram), the rows before and after the ordering
     SC_NBUF
 };
 struct EvBuf { void *p = nullptr; size_t bytes = 0; };
@@ -135,7 +140,8 @@ struct OpTimer {
     int stop(hipStream_t s) { HIPCHECK(hipEventRecord(ev[1], s)); return TTX_OK; }
     int ms(double *out) { float t = 0.f; HIPCHECK(hipEventElapsedTime(&t, ev[0], ev[1])); *out = t; return TTX_OK; }   // after a synchronise
 };
-enum { TM_MODESUM, TM_ALG, TM_HEAD, TM_DRAW, TM_APPLY, TM_N };    // k_ct_modesum, the algebra launch, k_sm_head, the k_sm_draw of a chunk, k_ma_apply
+enum { TM_MODESUM, TM_ALG, TM_HEAD, TM_DRAW, TM_APPLY,             // k_ct_modesum, the algebra launch, k_sm_head, the k_sm_draw of a chunk, k_ma_apply
+       TM_GRAM, TM_SCORE, TM_SELECT, TM_N };                       // ttx_topk: the Gram chain, a mode's scoring launch, a mode's selection and advance
 
 struct DevFun;                          // a loaded device integrand (TTX_FUN_DEVICE), defined with slot_eval
 struct TrainFun;                        // the operands and the combiner of TTX_FUN_TRAINS, defined with slot_eval
@@ -236,6 +242,8 @@ struct ttx_engine {
     int64_t sm_failed = 0;
     double ma_ms = 0.0, ma_rd = 0.0, ma_wr = 0.0, ma_flops = 0.0;   // the apply launch of the last ttx_mode_apply
     int ma_mode = -1;
+    double tk_ms_gram = 0.0, tk_ms_score = 0.0, tk_ms_select = 0.0, tk_flops = 0.0;   // the last ttx_topk
+    int tk_mode = -1;
 };
 
 // the process-wide pool of the host integrand (ttx_host_pool.h): engines driven from different host threads take turns on it
@@ -3426,6 +3434,154 @@ extern "C" int ttx_mode_apply_last(const ttx_engine *h, double *ms, double *byte
     if (bytes_written) *bytes_written = h->ma_wr;
     if (flops) *flops = h->ma_flops;
     if (mode_ran) *mode_ran = h->ma_mode;
+    return TTX_OK;
+}
+
+// ---- the largest elements of the resident train (ttx_topk.h) --------------------------------------------------------------------
+template <int MR>
+static int tk_score_mfma(ttx_engine *h, dim3 grid, size_t lds, const double *G, int r0, int r1, const double *P, int ldp, const double *X, int ldx, int C, int nI, int ifix,
+                         int niper, int first, tk_u64 *S)
+{
+    if (lds > 64 * 1024) { if (int rc = ensure_lds(h, reinterpret_cast<const void *>(k_tk_score_mfma<MR>), lds)) return rc; }   // rank 113 .. 128: 66560 bytes
+    hipLaunchKernelGGL(k_tk_score_mfma<MR>, grid, dim3(256), lds, h->stream, G, h->RM, h->P.SS, r0, r1, P, ldp, X, ldx, C, nI, ifix, niper, first, S);
+    return TTX_OK;
+}
+extern "C" int ttx_topk(ttx_engine *h, int32_t K, int32_t which, const int32_t *fixed, int32_t mode, int32_t *nfound, int32_t *ind, double *val, double *bound)
+{
+    const char *who = "ttx_topk";
+    if (!nfound || !ind || !val || !bound) return fail(TTX_EINVAL, "%s: null argument", who);
+    if (K < 1 || K > TTX_TK_KMAX) return fail(TTX_EINVAL, "%s: K = %d (1 .. %d expected)", who, K, TTX_TK_KMAX);
+    if (which != TTX_TOPK_ABS && which != TTX_TOPK_MAX && which != TTX_TOPK_MIN) return fail(TTX_EINVAL, "%s: unknown which %d", who, which);
+    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    int rc = check_train_one_process(h, who);
+    if (rc) return rc;
+    const int d = h->d;
+    int nmax = 1;
+    for (int k = 0; k < d; k++) {
+        if (fixed && (fixed[k] < 0 || fixed[k] > h->n1[k + 1])) return fail(TTX_EINVAL, "%s: fixed(%d) = %d (0 .. %d expected)", who, k + 1, fixed[k], h->n1[k + 1]);
+        nmax = std::max(nmax, (int)h->n1[k + 1]);
+    }
+    if ((long long)K * nmax > (long long)TTX_TK_SHEET)
+        return fail(TTX_EINVAL, "%s: K = %d times the largest mode %d is %lld, the score sheet holds up to %d", who, K, nmax, (long long)K * nmax, TTX_TK_SHEET);
+    EvTrain T;
+    if ((rc = ev_train(h, &T))) return rc;
+    // per mode (0-based): searched indices, the fixed index or -1, the sheet and the pairs kept; cnt[d] = 1, the empty suffix
+    std::vector<int> nI(d), ifx(d), cnt(d + 1, 1);
+    std::vector<long long> sheet(d);
+    double flops = 0.0;
+    size_t wmax = 1, smax = 1;
+    for (int k = d - 1; k >= 0; k--) {
+        const int f = fixed ? fixed[k] : 0, r0 = h->rfinal[k], r1 = h->rfinal[k + 1];
+        nI[k] = f ? 1 : h->n1[k + 1]; ifx[k] = f - 1;
+        sheet[k] = (long long)cnt[k + 1] * nI[k];
+        cnt[k] = (int)std::min<long long>(K, sheet[k]);
+        flops += 2.0 * cnt[k + 1] * nI[k] * r0 * ((double)r1 + r0);
+        wmax = std::max(wmax, (size_t)r0 * nI[k] * r1); smax = std::max(smax, (size_t)sheet[k]);
+    }
+    const int eff = mode == TTX_EVAL_AUTO ? (flops >= TTX_TK_AUTO_FLOPS ? TTX_EVAL_MFMA : TTX_EVAL_EXACT) : mode;
+    const int ldx = T.ldx, ldp = T.ldx, nf = cnt[0], ncu = dev_ncu(h);
+    h->tk_ms_gram = h->tk_ms_score = h->tk_ms_select = 0.0; h->tk_flops = flops; h->tk_mode = eff;
+    OpMeta meta(h->meta_host);
+    const size_t o_nI = meta.put(nI), o_ifx = meta.put(ifx), o_cnt = meta.put(cnt), o_sheet = meta.put(sheet);
+    char *dm;
+    const size_t obytes = (sizeof(int) * d + sizeof(double)) * (size_t)K;
+    if ((rc = meta.upload(h, SC_META, &dm)) || (rc = buf_reserve(h, SC_KP, sizeof(double) * (size_t)d * ldp * ldp)) || (rc = buf_reserve(h, SC_KW, sizeof(double) * wmax)) ||
+        (rc = buf_reserve(h, SC_KS, sizeof(tk_u64) * smax)) || (rc = buf_reserve(h, SC_KX, sizeof(double) * 2 * (size_t)K * ldx)) ||
+        (rc = buf_reserve(h, SC_KREC, sizeof(int) * (size_t)d * K)) ||
+        (rc = buf_reserve(h, SC_KSEL, sizeof(tk_u64) * (TKS_WORDS + TTX_TK_SHEET / TTX_TK_CHUNK) + sizeof(unsigned) * TTX_TK_BINS)) ||
+        (rc = buf_reserve(h, SC_KOUT, 2 * obytes))) return rc;
+    double *Pb = buf<double>(h, SC_KP), *W = buf<double>(h, SC_KW), *Xo = buf<double>(h, SC_KX), *Xn = Xo + (size_t)K * ldx;
+    tk_u64 *S = buf<tk_u64>(h, SC_KS), *st = buf<tk_u64>(h, SC_KSEL), *blk = st + TKS_WORDS;
+    unsigned *hist = (unsigned *)(blk + TTX_TK_SHEET / TTX_TK_CHUNK);
+    int *rec = buf<int>(h, SC_KREC);
+    double *tval = buf<double>(h, SC_KOUT), *oval = tval + K;                   // [tval K][oval K][tind K d][oind K d]
+    int *tind = (int *)(oval + K), *oind = tind + (size_t)K * d;
+    OpTimer &t_gram = h->timer[TM_GRAM], &t_score = h->timer[TM_SCORE], &t_sel = h->timer[TM_SELECT];
+    const double one = 1.0;
+    HIPCHECK(hipMemsetAsync(rec, 0, sizeof(int) * (size_t)d * K, h->stream));
+    HIPCHECK(hipMemsetAsync(tval, 0, 2 * obytes, h->stream));
+    HIPCHECK(hipMemcpyAsync(Pb, &one, sizeof one, hipMemcpyHostToDevice, h->stream));       // P_0 = [1]
+    HIPCHECK(hipMemcpyAsync(Xo, &one, sizeof one, hipMemcpyHostToDevice, h->stream));       // x of the empty suffix
+    // the Gram chain: P_k for k = 1 .. d-1 (P_(k-1) scores mode k)
+    if (d > 1) {
+        if ((rc = t_gram.start(h->stream))) return rc;
+        for (int k = 0; k + 1 < d; k++) {
+            const int r0 = h->rfinal[k], r1 = h->rfinal[k + 1];
+            const double *G = core_dev(h, k + 1), *P = Pb + (size_t)k * ldp * ldp;
+            hipLaunchKernelGGL(k_tk_gram_w, dim3((unsigned)(nI[k] * r1)), dim3(128), 0, h->stream, G, h->RM, h->P.SS, r0, nI[k], ifx[k], P, ldp, W);
+            hipLaunchKernelGGL(k_tk_gram_p, dim3((r1 + 15) / 16, (r1 + 15) / 16), dim3(256), 0, h->stream, G, h->RM, h->P.SS, r0, r1, nI[k], ifx[k], (const double *)W,
+                               Pb + (size_t)(k + 1) * ldp * ldp, ldp);
+        }
+        if ((rc = t_gram.stop(h->stream))) return rc;
+    }
+    for (int k = d - 1; k >= 0; k--) {
+        const int r0 = h->rfinal[k], r1 = h->rfinal[k + 1], C = cnt[k + 1], Cn = cnt[k], first = k == 0;
+        const long long M = sheet[k];
+        const double *G = core_dev(h, k + 1), *P = Pb + (size_t)k * ldp * ldp;
+        if ((rc = t_score.start(h->stream))) return rc;
+        if (eff == TTX_EVAL_MFMA) {
+            const int by = (C + 63) / 64, niper = (int)std::max<long long>(1, (long long)nI[k] * by / (4ll * ncu));
+            const dim3 grid((nI[k] + niper - 1) / niper, by);
+            const size_t lds = sizeof(double) * 64 * (size_t)tk_ldy(r0);
+            if (r0 <= 16) rc = tk_score_mfma<1>(h, grid, lds, G, r0, r1, P, ldp, Xo, ldx, C, nI[k], ifx[k], niper, first, S);
+            else if (r0 <= 32) rc = tk_score_mfma<2>(h, grid, lds, G, r0, r1, P, ldp, Xo, ldx, C, nI[k], ifx[k], niper, first, S);
+            else if (r0 <= 64) rc = tk_score_mfma<4>(h, grid, lds, G, r0, r1, P, ldp, Xo, ldx, C, nI[k], ifx[k], niper, first, S);
+            else rc = tk_score_mfma<8>(h, grid, lds, G, r0, r1, P, ldp, Xo, ldx, C, nI[k], ifx[k], niper, first, S);
+            if (rc) return rc;
+        } else {
+            const int grid = (int)std::min<long long>((M + 3) / 4, (long long)ncu * 8);
+            hipLaunchKernelGGL(k_tk_score_exact, dim3(grid), dim3(256), sizeof(double) * 4 * ldx, h->stream, G, h->RM, h->P.SS, r0, r1, P, ldp, (const double *)Xo, ldx,
+                               C, nI[k], ifx[k], first, S);
+        }
+        if ((rc = t_score.stop(h->stream)) || (rc = t_sel.start(h->stream))) return rc;
+        // selection: everything is kept, or the K-th largest key by six radix passes from the top (11, 11, 11, 11, 11 and 9 bits)
+        hipLaunchKernelGGL(k_tk_selinit, dim3(1), dim3(1024), 0, h->stream, st, hist, (long long)K, M, M <= K ? 1 : 0, k == d - 1 ? 1 : 0);
+        if (M > K) {
+            const int hg = (int)std::min<long long>((M + 255) / 256, (long long)ncu * 4);
+            static const int shifts[6] = {53, 42, 31, 20, 9, 0};
+            for (int shift : shifts) {
+                const int nbits = shift ? 11 : 9;
+                hipLaunchKernelGGL(k_tk_hist, dim3(hg), dim3(256), 0, h->stream, (const tk_u64 *)S, M, shift, nbits, shift == 53 ? 1 : 0, (const tk_u64 *)st, hist);
+                hipLaunchKernelGGL(k_tk_pick, dim3(1), dim3(1024), 0, h->stream, st, hist, shift);
+            }
+        }
+        const int nblk = (int)((M + TTX_TK_CHUNK - 1) / TTX_TK_CHUNK);
+        hipLaunchKernelGGL(k_tk_count, dim3(nblk), dim3(1024), 0, h->stream, (const tk_u64 *)S, M, (const tk_u64 *)st, blk);
+        hipLaunchKernelGGL(k_tk_blkscan, dim3(1), dim3(1024), 0, h->stream, blk, nblk);
+        hipLaunchKernelGGL(k_tk_scatter, dim3(nblk), dim3(1024), 0, h->stream, (const tk_u64 *)S, M, st, (const tk_u64 *)blk, rec + (size_t)k * K, Cn);
+        hipLaunchKernelGGL(k_tk_advance, dim3(std::min((Cn + 3) / 4, ncu * 8)), dim3(256), sizeof(double) * 4 * ldx, h->stream, G, h->RM, h->P.SS, r0, r1, k == d - 1 ? 1 : 0,
+                           (const int *)(rec + (size_t)k * K), Cn, M, nI[k], ifx[k], (const double *)Xo, Xn, ldx);
+        if ((rc = t_sel.stop(h->stream))) return rc;
+        HIPCHECK(hipStreamSynchronize(h->stream));
+        HIPCHECK(hipGetLastError());
+        double a = 0.0, b = 0.0;
+        if ((rc = t_score.ms(&a)) || (rc = t_sel.ms(&b))) return rc;
+        h->tk_ms_score += a; h->tk_ms_select += b;
+        std::swap(Xo, Xn);
+    }
+    hipLaunchKernelGGL(k_tk_back, dim3((nf + 255) / 256), dim3(256), 0, h->stream, d, (int)K, nf, (const int *)rec, (const int *)(dm + o_nI), (const int *)(dm + o_ifx),
+                       (const int *)(dm + o_cnt), (const long long *)(dm + o_sheet), (const double *)Xo, ldx, tind, tval);
+    hipLaunchKernelGGL(k_tk_order, dim3((nf + 255) / 256), dim3(256), 0, h->stream, d, nf, (int)which, (const int *)tind, (const double *)tval, oind, oval);
+    tk_u64 fin[TKS_WORDS];
+    HIPCHECK(hipMemcpyAsync(ind, oind, sizeof(int) * (size_t)K * d, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(val, oval, sizeof(double) * K, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(fin, st, sizeof fin, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipGetLastError());
+    *nfound = nf;
+    if (fin[TKS_NAN]) *bound = __builtin_nan("");
+    else if (!fin[TKS_BOUND]) *bound = 0.0;
+    else { const tk_u64 bits = fin[TKS_BOUND] - 1ull; memcpy(bound, &bits, sizeof bits); }
+    return d > 1 ? t_gram.ms(&h->tk_ms_gram) : TTX_OK;
+}
+extern "C" int ttx_topk_last(const ttx_engine *h, double *ms_gram, double *ms_score, double *ms_select, double *flops, int32_t *mode_ran)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_topk_last: null engine");
+    if (ms_gram) *ms_gram = h->tk_ms_gram;
+    if (ms_score) *ms_score = h->tk_ms_score;
+    if (ms_select) *ms_select = h->tk_ms_select;
+    if (flops) *flops = h->tk_flops;
+    if (mode_ran) *mode_ran = h->tk_mode;
     return TTX_OK;
 }
 

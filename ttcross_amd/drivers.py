@@ -727,6 +727,71 @@ def run_sample(argv, device=0, repeats=5, tt=None, host_npts=1000):
     return out
 
 
+def topk_train(workload, device=0):
+    """The train of a topk run: a train of the tijk sub-command, or d64diff: the difference lincomb([1, -1], [exact, fast]) of the
+    D_64 result trains in the two arithmetics, whose largest element is the max-norm error of the fast arithmetic; NAME+ort: the
+    train NAME after ort().  The raw result trains are badly conditioned (elements of 1e10 at slice norms of 1e44), so their Gram
+    scores are dominated by rounding; orthogonalise before a search that is to prove anything."""
+    if workload.endswith("+ort"):                      # orthogonalised first: P becomes a multiple of the identity, the scores are as accurate as the chain
+        return topk_train(workload[:-4], device=device).ort()
+    if workload != "d64diff":
+        return tijk_train(workload, device=device)
+    kind, m, n, r, piv = TIJK_WORKLOADS["d64"]
+    s = ising_setup(kind, m, n)
+    both = [TTCross(s["n"], s["fun_id"], s["par"], r, pivoting=piv, accuracy=s["acc"], quad=s["quad"], tru=s["tru"], nproc=8, device=device,
+                    arith=a).run() for a in ("exact", "fast")]
+    return TTCross.lincomb([1.0, -1.0], both)
+
+
+def topk_host(tt, k):
+    """what a user does without ttx_topk: every core to the host with core(k), then the numpy search of tests/topk_ref.py (of this
+    tree; None where the file is missing)"""
+    tests = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
+    if not os.path.exists(os.path.join(tests, "topk_ref.py")):
+        return None
+    if tests not in sys.path:
+        sys.path.insert(0, tests)
+    import topk_ref
+    return topk_ref.search([tt.core(j) for j in range(1, tt.d + 1)], k)
+
+
+def run_topk(argv, device=0, repeats=5, tt=None, host_kmax=4096):
+    """topk WORKLOAD K[,K...] [MODE] [HOST_KMAX]: the train of the workload (topk_train), per K one warm-up and `repeats` calls of
+    the search: the best rows, bound and certificate, the median of the call and of the three times of ttx_topk_last, the achieved
+    flop rate of the scoring launches; then, for K <= HOST_KMAX, the host route topk_host once and whether its rows are the
+    device's.  Prints one JSON line per K."""
+    import json
+    import time
+    workload, mode = argv[0], argv[2] if len(argv) > 2 else "auto"
+    if len(argv) > 3:
+        host_kmax = int(argv[3])
+    tt = tt or topk_train(workload, device=device)
+    out = []
+    for k in [int(float(x)) for x in argv[1].split(",")]:
+        res = tt.topk(k, mode=mode)
+        ms, last = [], []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            res = tt.topk(k, mode=mode)                # synchronises before it returns
+            ms.append((time.perf_counter() - t0) * 1e3)
+            last.append(tt.topk_last())
+        gram, score, sel = (float(np.median([x[key] for x in last])) for key in ("ms_gram", "ms_score", "ms_select"))
+        r = dict(workload=workload, k=k, mode_asked=mode, mode=last[-1]["mode"], d=tt.d, max_rank=int(tt.ranks().max()), nfound=int(res["ind"].shape[0]),
+                 call_ms=float(np.median(ms)), gram_ms=gram, score_ms=score, select_ms=sel, flops=last[-1]["flops"],
+                 score_flops_per_s=last[-1]["flops"] / (score * 1e-3) if score > 0 else None,
+                 best=[dict(ind=res["ind"][j].tolist(), val=float(res["val"][j])) for j in range(min(3, res["ind"].shape[0]))],
+                 bound=res["bound"], certified=res["certified"])
+        if k <= host_kmax:
+            t0 = time.perf_counter()
+            ref = topk_host(tt, k)
+            if ref is not None:
+                r.update(host_route_ms=(time.perf_counter() - t0) * 1e3, host_rows_equal_device=bool(np.array_equal(ref["ind"], res["ind"])),
+                         host_bound=ref["bound"])
+        print(json.dumps(r), flush=True)
+        out.append(r)
+    return out
+
+
 if __name__ == "__main__":
     if sys.argv[1] == "tijk":
         run_tijk(sys.argv[2:])
@@ -734,6 +799,8 @@ if __name__ == "__main__":
         run_compose(sys.argv[2:])
     elif sys.argv[1] == "sample":
         run_sample(sys.argv[2:])
+    elif sys.argv[1] == "topk":
+        run_topk(sys.argv[2:])
     elif sys.argv[1] == "contract":
         run_contract(sys.argv[2:])
     elif sys.argv[1] == "algebra":

@@ -23,6 +23,7 @@ TTX_TOP_PRODUCT, TTX_TOP_RATIO, TTX_TOP_SQRTABS, TTX_TOP_DEVICE = 1, 2, 3, 4
 TRAIN_OPS = {"product": TTX_TOP_PRODUCT, "ratio": TTX_TOP_RATIO, "sqrtabs": TTX_TOP_SQRTABS}
 TTX_EVAL_EXACT, TTX_EVAL_MFMA, TTX_EVAL_AUTO = 0, 1, 2
 EVAL_MODES = {"exact": TTX_EVAL_EXACT, "mfma": TTX_EVAL_MFMA, "auto": TTX_EVAL_AUTO}
+TOPK_WHICH = {"abs": 0, "max": 1, "min": 2}
 K_NAMES = ("lottery", "halfstep", "accept", "exchange", "quad", "other")
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -115,6 +116,8 @@ def load_library():
     L.ttx_sample.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
     L.ttx_sample_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(c_double), POINTER(c_int32), c_void_p, c_void_p, c_void_p]
     L.ttx_sample_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
+    L.ttx_topk.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_int32), c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
+    L.ttx_topk_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
     L.ttx_zquad.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
     L.ttx_accchk.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
     L.ttx_from_tt.argtypes = [POINTER(c_void_p), c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), c_int32]
@@ -813,6 +816,45 @@ class TTCross:
         a, b, c, n = c_double(), c_double(), c_double(), c_int64()
         _check(load_library().ttx_sample_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(n)))
         return dict(ms_head=a.value, bytes_head=b.value, ms_draw=c.value, failed=int(n.value))
+
+    # ---- the largest elements of the resident train (include/ttx.h: ttx_topk) ----------------------------
+    def topk(self, k, which="abs", fixed=None, mode="auto"):
+        """The k largest elements of the train found by a beam search on the device, with an upper bound on everything the search
+        discarded (include/ttx.h: ttx_topk).  which: "abs" (|T| descending), "max" (T descending) or "min" (T ascending) orders
+        the rows; fixed: d entries, 0 = searched, f = held at the 1-based index f; mode: "exact", "mfma" or "auto" for the scores
+        (topk_last() tells what ran).  Returns dict(ind (nfound, d) int32, 1-based; val, equal to tijk_batch(ind, "exact") bit for
+        bit; bound: every element not returned has |T| <= bound up to rounding, NaN if a score was NaN; certified: "all" when
+        bound <= min |val| (the rows are proven to be the top nfound by absolute size), "max" when bound <= max |val| (the largest
+        is proven; with a single row the two coincide and "max" is reported), else None)."""
+        if which not in TOPK_WHICH:
+            raise ValueError(f"topk: which must be one of {sorted(TOPK_WHICH)} (got {which!r})")
+        k, md = int(k), _eval_mode(mode)
+        if not 1 <= k <= 4096:
+            raise ValueError(f"topk: k = {k} (1 .. 4096 expected)")
+        fx = None
+        if fixed is not None:
+            fx = np.ascontiguousarray(fixed, dtype=np.int32).ravel()
+            if fx.size != self.d:
+                raise ValueError(f"topk: {self.d} fixed entries expected")
+        ind, val = np.zeros((k, self.d), dtype=np.int32), np.zeros(k)
+        nf, bound = c_int32(), c_double()
+        _check(load_library().ttx_topk(self._h, k, TOPK_WHICH[which], _ip(fx), md, ctypes.byref(nf), _ip(ind), _dp(val), ctypes.byref(bound)))
+        ind, val, b = ind[:nf.value].copy(), val[:nf.value].copy(), bound.value
+        av = np.abs(val)
+        certified = None
+        if nf.value > 1 and b <= av.min():
+            certified = "all"
+        elif nf.value and b <= av.max():
+            certified = "max"
+        return dict(ind=ind, val=val, bound=b, certified=certified)
+
+    def topk_last(self):
+        """dict(ms_gram, ms_score, ms_select, flops, mode) of the last topk() on this engine (include/ttx.h: ttx_topk_last); mode is
+        "exact" or "mfma" (None before the first call)"""
+        a, b, c, fl, md = c_double(), c_double(), c_double(), c_double(), c_int32()
+        _check(load_library().ttx_topk_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(fl), ctypes.byref(md)))
+        names = {v: k for k, v in EVAL_MODES.items()}
+        return dict(ms_gram=a.value, ms_score=b.value, ms_select=c.value, flops=fl.value, mode=names.get(md.value))
 
     # ---- tt_lib utilities on the resident TT (lib/tt.f90: ort, svd, norm, dot_product, tijk) --------------
     def ort(self):

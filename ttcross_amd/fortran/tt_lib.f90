@@ -71,6 +71,8 @@ module tt_lib
  interface modeapply;   module procedure dtt_modeapply; end interface
  ! samples drawn from the train on the device (not in the reference): sample(arg,u,ind,w,fixed,logq,val)
  interface sample;      module procedure dtt_sample;    end interface
+ ! the largest elements of the train with a bound on the rest, on the device (not in the reference): topk(arg,k,ind,val,bound,which,fixed,mode)
+ interface topk;        module procedure dtt_topk;      end interface
  ! sums and elementwise products on the device (not in the reference; its host + and * above stay as they are):
  ! axpby(alpha,x,beta,y) = alpha*x + beta*y, hadamard(x,y) = x(i)*y(i).  Both return a dtt that holds the new train on the device
  ! and, pulled, in %u; the variable the result is assigned to takes the device train over (dtt_assign)
@@ -437,6 +439,38 @@ contains
   if(temp)call ttx_destroy(h)
   ind(1:arg%m,1:npts)=ix
   deallocate(uu,ix)
+ end subroutine
+ subroutine dtt_topk(arg,k,ind,val,bound,which,fixed,mode,nfound)
+  ! the k largest elements of arg by a beam search on the device (include/ttx.h: ttx_topk): ind(:,j) and val(j), j = 1 .. nfound,
+  ! ordered by which (0: |val| descending, the default; 1: val descending; 2: val ascending), rows beyond nfound zero.  Every
+  ! element that is not returned has |arg(i)| <= bound up to rounding (NaN if a score was NaN): bound <= |val(nfound)| under
+  ! which = 0 proves the rows, bound <= |val(1)| the maximum.  fixed(k) = 0 searches mode k, f holds it at index f (absent: all
+  ! searched); mode: 0 plain loops, 1 matrix cores, 2 the engine chooses (the default).  A host train is staged for the call.
+  use ttx_c
+  type(dtt),intent(in) :: arg
+  integer,intent(in) :: k
+  integer,intent(out) :: ind(:,:)
+  double precision,intent(out) :: val(:),bound
+  integer,intent(in),optional :: which,fixed(:),mode
+  integer,intent(out),optional :: nfound
+  integer(c_int32_t),allocatable :: ix(:,:)
+  real(c_double),allocatable :: vv(:)
+  integer(c_int32_t),target :: fx(tt_size)
+  integer(c_int32_t) :: nf,wh,md
+  real(c_double) :: bd
+  type(c_ptr) :: h,fp
+  logical :: temp
+  wh=0; md=2; fp=c_null_ptr
+  if(present(which))wh=which
+  if(present(mode))md=mode
+  if(present(fixed))then; fx(1:arg%m)=fixed(1:arg%m); fp=c_loc(fx); endif
+  allocate(ix(arg%m,max(k,1)),vv(max(k,1)))
+  call dtt_stage(arg,h,temp,'dtt_topk')
+  call ttx_check(ttx_topk(h,int(k,c_int32_t),wh,fp,md,nf,ix,vv,bd),'dtt_topk')
+  if(temp)call ttx_destroy(h)
+  ind(1:arg%m,1:k)=ix(:,1:k); val(1:k)=vv(1:k); bound=bd
+  if(present(nfound))nfound=nf
+  deallocate(ix,vv)
  end subroutine
  double precision function dtt_ijk(arg,ind) result(a)
   ! lib/tt.f90:630-652: one element; a resident train is asked on the device, a host train is contracted here

@@ -168,6 +168,14 @@ module ttx_c
   function ttx_sample_last(h,ms_head,bytes_head,ms_draw,nfailed) bind(C,name='ttx_sample_last') result(rc)
    import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms_head,bytes_head,ms_draw; integer(c_int64_t),intent(out) :: nfailed; integer(c_int) :: rc
   end function
+  ! the largest elements of the resident train (include/ttx.h); ind(d,K), val(K); fixed: c_null_ptr where not wanted
+  function ttx_topk(h,k,which,fixed,mode,nfound,ind,val,bound) bind(C,name='ttx_topk') result(rc)
+   import; type(c_ptr),value :: h,fixed; integer(c_int32_t),value :: k,which,mode; integer(c_int32_t),intent(out) :: nfound,ind(*)
+   real(c_double),intent(out) :: val(*),bound; integer(c_int) :: rc
+  end function
+  function ttx_topk_last(h,ms_gram,ms_score,ms_select,flops,mode_ran) bind(C,name='ttx_topk_last') result(rc)
+   import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms_gram,ms_score,ms_select,flops; integer(c_int32_t),intent(out) :: mode_ran; integer(c_int) :: rc
+  end function
   function ttx_accchk(h,nlot,einf,efro,ainf,afro,pivot) bind(C,name='ttx_accchk') result(rc)
    import; type(c_ptr),value :: h; integer(c_int32_t),value :: nlot; real(c_double),intent(out) :: einf,efro,ainf,afro
    integer(c_int32_t),intent(out) :: pivot(*); integer(c_int) :: rc
