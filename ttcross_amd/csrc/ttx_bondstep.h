@@ -67,6 +67,26 @@ TTX_HD void pivot_range(double &pivotmax, double &pivotmin, double ap)
     pivotmin = (pivotmin < 0.0) ? ap : fmin(pivotmin, ap);
 }
 
+// The stopping rule at the end of sweep it (:1011-1019): the rank limit, or -- with accuracy >= 0 -- the third sweep in a row
+// whose largest pivot is at most accuracy * amax (a comparison with a NaN is false: such a sweep resets the strikes).  One
+// function for the device (k_sweep_end) and the host (process_sweep of run_impl), which must decide alike.
+struct StopRule { int ready, strikes; };
+TTX_HD StopRule stop_rule(int it, int maxrank, double accuracy, double pmax, double amax, int strikes_prev)
+{
+    StopRule s{(it + 1 >= maxrank) ? 1 : 0, strikes_prev};
+    if (accuracy >= 0.0) {
+        s.strikes = (pmax <= accuracy * amax) ? strikes_prev + 1 : 0;
+        s.ready = (s.ready || s.strikes >= 3) ? 1 : 0;
+    }
+    return s;
+}
+
+// Evaluations the boundary step of a sweep counts for one group (:936 and its right-going twin): n(last+1) where the right
+// neighbour sent a pivot (u_r) and the own last bond took one this sweep (upd_last), n(first) likewise on the left.  These are the
+// conditions under which corner block 0 of either side of k_exch_boundary adds them; the apply block of k_exch_tail adds the sum.
+TTX_HD long long boundary_neval(bool has_r, int u_r, int upd_last, int n_r, bool has_l, int u_l, int upd_first, int n_l)
+{ return ((has_r && u_r && upd_last) ? (long long)n_r : 0) + ((has_l && u_l && upd_first) ? (long long)n_l : 0); }
+
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------------
 // device part.  Not self-contained: it uses the address helpers (L_ptr, R_ptr, inv_ptr, vip_ptr) that ttx_kernels.h

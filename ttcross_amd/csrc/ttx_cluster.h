@@ -213,6 +213,15 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
     const int bid = blockIdx.x;
     const int g = (bid & 7) + 8 * (bid / (8 * NB)), cb = (bid >> 3) % NB;     // cluster of group g lives on XCD g % 8
     if (g >= P.G || P.ctl[0]) return;
+    // Summary on the side stream (ttx_dev.h: tail_side): the rule of sweep epoch-1 has not been written to ctl[0] for certain yet, so
+    // every block applies it itself to the same records -- the job-wide maxima of group 0's record with its corner maximum, and the
+    // strike count after sweep epoch-2 -- and all decide alike, without a word to each other.  (ctl[0] above: an abort, or a stop
+    // the summary has already recorded.)  Sweep 1 follows the initial cross: nothing to decide.
+    const int bpar = (epoch - 1) & 1;
+    if (P.tail_side && epoch >= 2) {
+        const TailRec &t0 = P.tailrec[(size_t)bpar * P.G];
+        if (stop_rule(epoch - 1, P.maxrank, P.accuracy, t0.pivotmax, max_pos(t0.amax, P.gs[0].amax_bnd[bpar]), P.strk[epoch & 1]).ready) return;
+    }
     if (P.cl_test_abort && P.cl_test_abort == epoch && g == 0 && cb == 0) {    // test hook (TTX_CLUSTER_TEST_ABORT): a block that never arrives
         if (threadIdx.x == 0) { __hip_atomic_store(P.cl_abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); P.ctl[0] = 1; }
         return;
@@ -296,6 +305,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         }
     }
     double amax = gs.amax, pivotmax = -1.0, pivotmin = -1.0;
+    if (P.tail_side && epoch >= 2) amax = max_pos(amax, gs.amax_bnd[bpar]);     // the corner maxima of the last tail launch
     const double pivotmax_prev = gs.pivotmax_prev;
     long long neval = gs.neval;
     unsigned long long rngpos = gs.rngpos;
@@ -761,6 +771,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         if (tid == 0) {
             gs.amax = amax; gs.pivotmax = pivotmax; gs.pivotmin = pivotmin; gs.neval = neval; gs.rngpos = rngpos;
             gs.bytes_half = bytes_half; gs.n_resid = n_resid;
+            if (P.tail_side) gs.amax_bnd[epoch & 1] = 0.0;      // the slot this sweep's tail launch raises (ttx_dev.h)
         }
         __syncthreads();
         exch_pack_group(P, g);          // the group's outgoing boundary messages (saves the separate k_exch_pack launch)

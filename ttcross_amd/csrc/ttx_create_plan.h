@@ -69,6 +69,8 @@ struct CreateEnv {
     bool lottery_wave_off = false;  // TTX_LOTTERY_WAVE=0
     bool lottery_rows2 = false;     // TTX_LOTTERY_ROWS=2
     bool mvn_v2_off = false;        // TTX_MVN_V2=0
+    bool tail_off = false;          // TTX_TAIL=0
+    bool tail_side_off = false;     // TTX_TAIL_SIDE=0
 };
 // the switches as `get` finds them (get(name): the value, or nullptr where unset): an integer as atoi reads it, "=0" as atoi(value) == 0
 template <class Get>
@@ -96,6 +98,7 @@ CreateEnv create_env_from(Get get)
     v.lottery_wave_off = off("TTX_LOTTERY_WAVE");
     v.lottery_rows2 = num("TTX_LOTTERY_ROWS", 0) == 2;
     v.mvn_v2_off = off("TTX_MVN_V2");
+    v.tail_off = off("TTX_TAIL"); v.tail_side_off = off("TTX_TAIL_SIDE");
     return v;
 }
 struct DevCaps { int ncu = 0; bool coop = false; };          // multiProcessorCount, hipDeviceAttributeCooperativeLaunch
@@ -154,6 +157,8 @@ struct CreatePlan {
     int cluster_var = 0;                            // its instantiation: 0 exact, remainders predicated; 1 exact, rows padded to whole chunks; 2 closed form
     int cluster_ldsinv = 0, cluster_zkeep = 0, cluster_coop = 0;
     int cl_test_abort = 0; bool dbg_waves = false;
+    bool sweep_tail = true;                         // the pipelined cluster loop ends a sweep with k_exch_tail (TTX_TAIL=0: max/apply and boundary launches)
+    bool sweep_tail_side = true;                    // ... and its summary runs on the quadrature's stream (TTX_TAIL_SIDE=0: k_sweep_end on the main stream)
     SweepWant sweep_want = SWEEP_AUTO; int ncu = 0;
     // decided by create_admit
     int fused = 0;                                  // whole-sweep kernel (ttx_fused.h) in use
@@ -364,6 +369,7 @@ inline CreatePlan create_plan(const ttx_config &cfg, bool nofun, const CreateEnv
             p.cluster_coop = caps.coop && env.cluster_coop;
         }
         p.cl_test_abort = env.cluster_test_abort; p.dbg_waves = env.dbg_waves;
+        p.sweep_tail = !env.tail_off; p.sweep_tail_side = !env.tail_side_off;
         const std::string want_sweep = env.sweep.set ? env.sweep.v : "auto";
         if (want_sweep == "cluster") p.sweep_want = SWEEP_CLUSTER;
         else if (want_sweep == "fused") p.sweep_want = SWEEP_FUSED;

@@ -63,6 +63,16 @@ struct GroupState {
     double initval;        // initial-cross value factor of this group
     double bytes_half;     // algorithmic bytes moved by the half-step kernel, for the roofline
     long long n_resid;     // half-steps that computed a residual
+    // Largest |corner entry| of the boundary blocks of k_exch_tail, by sweep parity; positive bit patterns, 0 = none.  The apply
+    // block of that launch stores the job-wide maximum into amax, so the corner blocks beside it must not touch amax: they raise
+    // slot it & 1.  A slot is 0 whenever a tail launch starts; k_reset clears both.  Who folds it into amax and clears it:
+    //  * summary on the main stream (k_sweep_end, the next launch behind the tail): k_sweep_end of the same sweep does both;
+    //  * summary on the side stream (DevProb::tail_side): slot (it-1) & 1 is read by every block of sweep kernel it at its entry
+    //    (stopping rule, and folded into its running maximum, which it stores into amax at its end) and by the summary kernel of
+    //    sweep it-1 beside it; nobody writes it then.  Block 0 of the group's cluster clears slot it & 1 at the END of sweep
+    //    kernel it: that slot was last read at the entry of sweep kernel it-1, which is over, and by the summary of sweep it-2,
+    //    which finished before the tail of sweep it-1 was launched (its wait for ev_val); its next writer is the tail of sweep it.
+    double amax_bnd[2];
 #ifdef TTX_STAMPS
     long long stamp[2][16]; long long nstamp[2];   // debug build: accumulated wall_clock64 deltas per phase
 #endif
@@ -77,6 +87,10 @@ struct LotPart { double ab, bv, ma; int il, i, j, k, q, pad; };
 #define TTX_CLMAX 16            // most workgroups one bond group's cluster may have
 #define TTX_CLREC (4 * TTX_CLMAX) // arg-max records per group and half-step parity: one per WAVE of the cluster (4 waves per workgroup)
 struct ClPart { double ab, bb, mx; int ix, pad; };
+
+// What the end of sweep it leaves of one group for the summary kernel and for the next sweep kernel's entry: written by the
+// group's apply block of k_exch_tail, job-wide maxima after the MAX, the group's counters after the boundary additions.
+struct TailRec { double amax, pivotmax, pivotmin, bytes_half, initval; long long neval, n_resid; };
 
 struct DevProb {
     int d, RM, NM, G, NC;      // cores, max rank, max mode size, local groups, max cores per group
@@ -149,6 +163,19 @@ struct DevProb {
     int *ctl;
     int *rq;                       // [G][d+2] ranks at the end of the sweep, for the forked quadrature
     double accuracy; int maxrank;
+    // Summary of a sweep on the quadrature's stream (tail_side, set per run): the main stream carries only k_exch_tail between two
+    // sweep kernels, and nothing on the side stream reads what the running sweep kernel writes (r, tape, gs.neval, gs.amax, ...).
+    //  * tailrec [2][G], tail_tape [2][G][4 (d+2)]: the records of sweep it in slot it & 1, written by the tail launch of sweep it,
+    //    read by the summary kernel of sweep it (side stream, behind an event) and at the entry of sweep kernel it+1; rewritten by
+    //    the tail of sweep it+2, which is behind sweep kernel it+1 on the main stream and waits for ev_val of sweep it+1, an
+    //    event that lies behind the summary of sweep it on the side stream.
+    //  * rq is written by the tail of sweep it (each apply block its group's row, after its apply) instead of k_sweep_end; the
+    //    summary and the quadrature of sweep it read it; the tail of sweep it+1 waits for ev_val of sweep it before it rewrites it.
+    //  * strk [2]: the strike count after sweep it in slot it & 1, written by the summary kernel of sweep it; sweep kernel it reads
+    //    slot (it-2) & 1 -- the summary of sweep it-2 finished before the tail of sweep it-1 was launched -- while the summary of
+    //    sweep it-1 writes the other slot.  ctl[1] keeps the latest count.  k_reset clears both.
+    int tail_side;
+    TailRec *tailrec; int *tail_tape; int *strk;
     // cluster sweep kernel (ttx_cluster.h): per-group barrier counters, abort flag, per-block partial arg-max records
     // lottery spread over several workgroups per group (heavy integrands): [G][lot_nb] partials + arrival counters [G]
     struct LotPart *lotp;

@@ -210,7 +210,7 @@ struct ttx_engine {
     bool cluster_aborted = false;
     double *h_svd = nullptr; double svd_seq = 0.0;   // pinned: [seq, rank, sweeps, sv...] of the core dtt_svd works on (k_svd_report)
     hipStream_t qstream = nullptr;      // forked per-sweep quadrature (single-process runs)
-    hipEvent_t ev_sum[2] = {nullptr, nullptr}, ev_val[2] = {nullptr, nullptr};
+    hipEvent_t ev_sum[2] = {nullptr, nullptr}, ev_val[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr};
     double *h_sum_base = nullptr;       // pinned [2][SB]: summaries of the two sweeps in flight
     double *h_val = nullptr;            // pinned [2]: per-sweep quadrature values
     int *h_abort = nullptr;             // pinned, device-visible: the cluster kernel's barrier-timeout flag
@@ -590,6 +590,9 @@ static int create_exchange(ttx_engine *h)
     A_(dev_alloc(h, &ctl, (size_t)4));
     A_(dev_alloc(h, &rq, G * (d + 2)));
     P.ctl = ctl; P.rq = rq;
+    // records of the end of a sweep by parity (ttx_dev.h: tail_side)
+    P.tail_side = 0;
+    A_(dev_alloc(h, &P.tailrec, 2 * G)); A_(dev_alloc(h, &P.tail_tape, 2 * G * (d + 2) * 4)); A_(dev_alloc(h, &P.strk, (size_t)2));
     return TTX_OK;
 }
 // pinned staging of the per-sweep summaries and of the host transports, the quadrature's stream, the events of the pipelined sweep
@@ -600,7 +603,7 @@ static int create_staging(ttx_engine *h)
     memset(h->h_sum_base, 0, sizeof(double) * 2 * h->SB);
     HIPCHECK(hipHostMalloc((void **)&h->h_val, sizeof(double) * 2));
     HIPCHECK(hipStreamCreateWithFlags(&h->qstream, hipStreamNonBlocking));
-    for (int x = 0; x < 2; x++) { HIPCHECK(hipEventCreateWithFlags(&h->ev_sum[x], hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&h->ev_val[x], hipEventDisableTiming)); }
+    for (int x = 0; x < 2; x++) { HIPCHECK(hipEventCreateWithFlags(&h->ev_sum[x], hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&h->ev_val[x], hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&h->ev_tail[x], hipEventDisableTiming)); }
     HIPCHECK(hipHostMalloc((void **)&h->h_msg, 4 * h->P.MSZ));
     HIPCHECK(hipHostMalloc((void **)&h->h_tmp, sizeof(double) * std::max(h->QB, h->SB)));
     if (h->W > 1) {
@@ -722,7 +725,7 @@ extern "C" void ttx_destroy(ttx_engine *h)
     if (h->h_val) (void)hipHostFree(h->h_val);
     if (h->h_svd) (void)hipHostFree(h->h_svd);
     if (h->qstream) (void)hipStreamDestroy(h->qstream);
-    for (int x = 0; x < 2; x++) { if (h->ev_sum[x]) (void)hipEventDestroy(h->ev_sum[x]); if (h->ev_val[x]) (void)hipEventDestroy(h->ev_val[x]); }
+    for (int x = 0; x < 2; x++) { if (h->ev_sum[x]) (void)hipEventDestroy(h->ev_sum[x]); if (h->ev_val[x]) (void)hipEventDestroy(h->ev_val[x]); if (h->ev_tail[x]) (void)hipEventDestroy(h->ev_tail[x]); }
     if (h->h_msg) (void)hipHostFree(h->h_msg);
     if (h->h_tmp) (void)hipHostFree(h->h_tmp);
     if (h->red_mem) (void)hipHostFree(h->red_mem);
@@ -1175,10 +1178,11 @@ struct ChainPlan {
     KLaunch base; int base_vals = 0;    // k_halfstep<FUN>: full pivoting goes through it whatever the tiers are
     enum { FP_PLAIN, FP_MFMA, FP_COLUMNS } fullpiv = FP_PLAIN;      // piv = -1: all columns at once, dense MFMA, or one column per host pass
     KLaunch accept, init_samples, init_fibers, exch_boundary, fin_luar, fin_lual;
+    KLaunch exch_tail;                  // not of the chain path: k_exch_tail<FUN> of the pipelined cluster loop, which shares exch_boundary's LDS figure
     int nfb = 0, srows = 0, fl = 0;
     std::vector<const KLaunch *> all() const
     {
-        std::vector<const KLaunch *> v = {&tables, &lottery, &lot_eval, &base, &accept, &init_samples, &init_fibers, &exch_boundary, &fin_luar, &fin_lual};
+        std::vector<const KLaunch *> v = {&tables, &lottery, &lot_eval, &base, &accept, &init_samples, &init_fibers, &exch_boundary, &exch_tail, &fin_luar, &fin_lual};
         for (int t = 0; t < ntier; t++) v.push_back(&half[t].k);
         return v;
     }
@@ -1246,6 +1250,8 @@ static ChainPlan chain_plan(const ttx_engine *h)
         const size_t lds_b = s.lds_par + 16 + sizeof(short) * 2 * VS + sizeof(double) * (64 * 64 + 4) +
                              (P.bnd_wave ? sizeof(double) * (std::max<size_t>(2 * (size_t)de_rows_stride(d), 3 * (size_t)d + 2) + 8 + (P.de_cut ? 64 * 32 : 0)) : 0);
         p.exch_boundary = kl(k_exch_boundary<FUN>, KFUN_(k_exch_boundary), dim3(2 * NM, G), dim3(TTX_BLK), lds_b, true);
+        // the same blocks plus one apply block per group, which may stage the persistent fast tables
+        if constexpr (FUN != FUN_HOST) p.exch_tail = kl(k_exch_tail<FUN>, KFUN_(k_exch_tail), dim3(2 * NM + 1, G), dim3(TTX_BLK), std::max(lds_b, lds_fpersist(P)), true);
     }
     {   // finalisation.  Threads (= columns) per workgroup: as many as fit the LDS next to the LU panel (256, 128 or 64); the columns
         // of a core are spread over grid.z (at maxrank 64 the 256-thread staging did not fit: the kernels then ran out of L2 with one
@@ -1292,6 +1298,16 @@ static int run_impl(ttx_engine *h)
     hipStream_t st = h->stream;
     h->recs.clear(); h->tapes.clear();
     int rc;
+    const bool pipe = (cluster || fused) && !h->profile && !env_off("TTX_PIPELINE");      // the pipelined loop (below, at the main loop)
+    const bool forkq = pipe && P.has_quad && h->W == 1;
+    // The end of a sweep as ONE exchange launch (k_exch_tail): single process, pipelined loop, cluster path, device integrand, at least
+    // two groups (one group has no neighbour, its boundary launch never existed).  With the forked quadrature its summary
+    // (k_sweep_summary) goes to the quadrature's stream as well, and every block of the next sweep kernel applies the stopping rule
+    // itself (`side`, DevProb::tail_side); else k_sweep_end follows on the main stream.  Everything else -- the chain path,
+    // k_sweep_fused, several processes, TTX_PIPELINE=0, profile mode, TTX_TAIL=0 -- keeps the launches it had.
+    const bool tail = pipe && cluster && h->W == 1 && nproc > 1 && FUN != FUN_HOST && h->sel.sweep_tail;
+    const bool side = tail && forkq && h->sel.sweep_tail_side;
+    P.tail_side = side ? 1 : 0;
 
     // what this run launches on the chain path; its kernels, and the whole-sweep kernel where one is used, may stage more than the
     // default 64 KB of dynamic LDS (160 KB per CU on gfx950)
@@ -1360,8 +1376,7 @@ static int run_impl(ttx_engine *h)
     // With several processes the exchange and the summary travel by stream-ordered collectives (RCCL, or the host transport's
     // host functions), so the same loop applies; only the fork of the quadrature is single-process (one communicator must
     // not be driven from two streams at once).
-    const bool pipe = (cluster || fused) && !h->profile && !env_off("TTX_PIPELINE");
-    const bool forkq = pipe && P.has_quad && h->W == 1;
+    // (pipe, forkq, tail and side are decided at the top: the first sweep kernel, already enqueued, runs with the same DevProb)
     DevProb Pq = P;
     if (pipe) Pq.r = P.rq;
 
@@ -1433,7 +1448,18 @@ static int run_impl(ttx_engine *h)
         }
         }
         if (!(part & 2)) return TTX_OK;
+        if (side) {     // one launch on the main stream; the rest of the sweep's end goes to the quadrature's stream (enqueue_side)
+            HIPCHECK(hipStreamWaitEvent(st, h->ev_val[slot ^ 1], 0));       // the previous quadrature is done with the boundaries and with rq
+            KScope ks(h, TTX_K_EXCHANGE, 1);
+            launch(st, plan.exch_tail, P, it_);
+            HIPCHECK(hipEventRecord(h->ev_tail[slot], st));
+            return TTX_OK;
+        }
         if (forkq) HIPCHECK(hipStreamWaitEvent(st, h->ev_val[slot ^ 1], 0));   // the previous quadrature is done with the boundaries
+        if (tail) {     // MAX / apply and the boundary blocks as independent blocks of one launch (the cluster kernel packed at its end)
+            KScope ks(h, TTX_K_EXCHANGE, 1);
+            launch(st, plan.exch_tail, P, it_);
+        } else
         {   // per-sweep exchange between bond groups (:763-961)
             KScope ks(h, TTX_K_EXCHANGE, (h->W > 1 ? 4 : 2) + (nproc > 1 ? 1 : 0));
             if (!cluster) hipLaunchKernelGGL(k_exch_pack, dim3(G), dim3(256), 0, st, P);     // the cluster kernel packs at its end
@@ -1445,9 +1471,9 @@ static int run_impl(ttx_engine *h)
             hipLaunchKernelGGL(k_exch_max_apply, dim3(G), dim3(256), lds_fpersist(P), st, P, h->W > 1 ? 1 : 0, nproc > 1 ? 1 : 0);
             if (nproc > 1) { if (int rc_ = EV(plan.exch_boundary)) return rc_; }
         }
-        if (pipe && h->W == 1) hipLaunchKernelGGL(k_sweep_end, dim3(1), dim3(256), 0, st, P, it_, h->h_sum_base + (size_t)slot * h->SB);
+        if (pipe && h->W == 1) hipLaunchKernelGGL(k_sweep_end, dim3(1), dim3(256), 0, st, P, it_, h->h_sum_base + (size_t)slot * h->SB, tail ? 1 : 0);
         if (pipe && h->W > 1) {      // this GPU's part -> SUM all-reduce -> pinned slot, all stream-ordered
-            hipLaunchKernelGGL(k_sweep_end, dim3(1), dim3(256), 0, st, P, it_, P.sumsend);
+            hipLaunchKernelGGL(k_sweep_end, dim3(1), dim3(256), 0, st, P, it_, P.sumsend, 0);
             if (int rc_ = allreduce_dev(h, P.sumsend, P.sumrecv, h->SB, 0)) return rc_;
             HIPCHECK(hipMemcpyAsync(h->h_sum_base + (size_t)slot * h->SB, P.sumrecv, sizeof(double) * h->SB, hipMemcpyDeviceToHost, st));
         }
@@ -1463,6 +1489,20 @@ static int run_impl(ttx_engine *h)
             }
             if (h->cb_error) return fail(TTX_EHIP, "host transport: a sendrecv / allreduce callback failed");
         }
+        return TTX_OK;
+    };
+    // `side`: what the end of sweep it_ leaves to the quadrature's stream, behind the tail launch (ev_tail) -- the summary, then the
+    // sweep's quadrature.  Enqueued AFTER the next sweep kernel: at short sweeps (C_16) the host is what the main stream waits for.
+    auto enqueue_side = [&](int it_) -> int {
+        const int slot = it_ & 1;
+        hipStream_t sq = h->qstream;
+        HIPCHECK(hipStreamWaitEvent(sq, h->ev_tail[slot], 0));
+        hipLaunchKernelGGL(k_sweep_summary, dim3(1), dim3(256), 0, sq, P, it_, h->h_sum_base + (size_t)slot * h->SB);
+        HIPCHECK(hipEventRecord(h->ev_sum[slot], sq));          // the summary of the sweep is in the pinned slot
+        KScope ks(h, TTX_K_QUAD, 2);
+        if (int rc_ = launch_quad(h, sq, Pq, 0, P.quadw)) return rc_;
+        HIPCHECK(hipMemcpyAsync(h->h_val + slot, &P.gs[0].val, sizeof(double), hipMemcpyDeviceToHost, sq));
+        HIPCHECK(hipEventRecord(h->ev_val[slot], sq));
         return TTX_OK;
     };
     // ---- finalise (:1029): dtt_lua shifts the rightmost inv of every group to its neighbour first.  Enqueued once; in the
@@ -1491,9 +1531,7 @@ static int run_impl(ttx_engine *h)
             HIPCHECK(hipEventSynchronize(h->ev_sum[slot]));
             h->h_sum = h->h_sum_base + (size_t)slot * h->SB;
             {   // the rule needs only the summary: if it fires, the finalisation goes out before the host waits for the value
-                bool rdy = (it_ + 1 >= h->cfg.maxrank);
-                if (h->cfg.accuracy >= 0.0) rdy = rdy || (((h->h_sum[SUM_PMAX] <= h->cfg.accuracy * h->h_sum[SUM_AMAX]) ? strike + 1 : 0) >= 3);
-                if (rdy) { if (int rc_ = enqueue_final(P.has_quad ? slot : -1)) return rc_; }
+                if (stop_rule(it_, h->cfg.maxrank, h->cfg.accuracy, h->h_sum[SUM_PMAX], h->h_sum[SUM_AMAX], strike).ready) { if (int rc_ = enqueue_final(P.has_quad ? slot : -1)) return rc_; }
             }
             if (P.has_quad) { HIPCHECK(hipEventSynchronize(h->ev_val[slot])); val = h->h_val[slot]; }
         } else {
@@ -1513,11 +1551,9 @@ static int run_impl(ttx_engine *h)
         }
         if (h->cfg.verbose) print_line(h, r, val_prev);
         val_prev = val;
-        ready = ready || (it_ + 1 >= h->cfg.maxrank);                             // :1011
-        if (h->cfg.accuracy >= 0.0) {                                             // :1012-1019 (rank 0's amax, global pivotmax)
-            if (r.pivotmax <= h->cfg.accuracy * r.amax) strike++; else strike = 0;
-            ready = ready || (strike >= 3);
-        }
+        const StopRule sr = stop_rule(it_, h->cfg.maxrank, h->cfg.accuracy, r.pivotmax, r.amax, strike);   // :1011-1019 (rank 0's amax, global pivotmax)
+        strike = sr.strikes;
+        ready = ready || sr.ready;
         return TTX_OK;
     };
     if (!pipe) {
@@ -1534,6 +1570,7 @@ static int run_impl(ttx_engine *h)
         for (it = 1; !ready; it++) {
             if ((rc = enqueue_sweep(it, 2))) return rc;
             if (it + 1 < h->cfg.maxrank && (rc = enqueue_sweep(it + 1, 1))) return rc;
+            if (side && (rc = enqueue_side(it))) return rc;
             if ((rc = process_sweep(it))) return rc;
         }
         it--;

@@ -755,6 +755,9 @@ __device__ __forceinline__ void atomic_max_pos(double *addr, double v)
 {   // v >= 0: the IEEE bit patterns of non-negative doubles order like unsigned integers
     atomicMax((unsigned long long *)addr, (unsigned long long)__double_as_longlong(v));
 }
+// the same order without the atomic: what atomic_max_pos(&a, b) would leave in a (a NaN's bit pattern is above every number's)
+__device__ __forceinline__ double max_pos(double a, double b)
+{ return ((unsigned long long)__double_as_longlong(b) > (unsigned long long)__double_as_longlong(a)) ? b : a; }
 
 // resolve pending partial arg-max records of the previous half-step into the step state
 // (lib/dmrgg.f90:540-546 and :573-579)
@@ -997,6 +1000,7 @@ __global__ __launch_bounds__(256) void k_reset(DevProb P, size_t SB, size_t QB)
     for (size_t x = t0; x < SB; x += nt) P.sumsend[x] = 0.0;
     for (size_t x = t0; x < QB; x += nt) P.qsend[x] = 0.0;
     if (t0 < 4) P.ctl[t0] = 0;
+    if (t0 < 2) P.strk[t0] = 0;
     if (P.lot_ctr) for (size_t x = t0; x < (size_t)P.G; x += nt) P.lot_ctr[x] = 0u;
     if (P.cl_ctr) {
         for (size_t x = t0; x < (size_t)P.G; x += nt) P.cl_ctr[x] = 0u;
@@ -1007,6 +1011,7 @@ __global__ __launch_bounds__(256) void k_reset(DevProb P, size_t SB, size_t QB)
         GroupState &gs = P.gs[g];
         gs.amax = 0.0; gs.pivotmax = -1.0; gs.pivotmin = -1.0; gs.pivotmax_prev = 0.0;
         gs.neval = 0; gs.rngpos = 0; gs.val = 0.0; gs.initval = 0.0; gs.bytes_half = 0.0; gs.n_resid = 0;
+        gs.amax_bnd[0] = 0.0; gs.amax_bnd[1] = 0.0;
 #ifdef TTX_STAMPS
         for (int a = 0; a < 2; a++) { gs.nstamp[a] = 0; for (int b = 0; b < 16; b++) gs.stamp[a][b] = 0; }
 #endif
@@ -2123,18 +2128,20 @@ __global__ __launch_bounds__(256) void k_exch_apply(DevProb P) { exch_apply_grou
 
 // MAX all-reduce result (:867-870, :961) folded into the apply launch: every block reduces the same inputs and
 // writes only its own group.  from_recv: P.redrecv already holds the job-wide maxima (after the RCCL all-reduce)
+__device__ __forceinline__ void exch_max_group(const DevProb &P, int g, int from_recv)      // one thread of the group
+{
+    double a = -1e300, b = -1e300, c = -1e300;
+    if (from_recv) { a = P.redrecv[0]; b = P.redrecv[1]; c = P.redrecv[2]; }
+    else for (int x = 0; x < P.G; x++) { a = fmax(a, P.red[4 * x]); b = fmax(b, P.red[4 * x + 1]); c = fmax(c, P.red[4 * x + 2]); }
+    GroupState &gs = P.gs[g];
+    gs.amax = a; gs.pivotmax = b; gs.pivotmin = (-c == 999e9) ? -1.0 : -c;
+    gs.pivotmax_prev = b;
+}
 __global__ __launch_bounds__(256) void k_exch_max_apply(DevProb P, int from_recv, int do_apply)
 {
     if (P.ctl[0]) return;
     const int g = blockIdx.x;
-    if (threadIdx.x == 0) {
-        double a = -1e300, b = -1e300, c = -1e300;
-        if (from_recv) { a = P.redrecv[0]; b = P.redrecv[1]; c = P.redrecv[2]; }
-        else for (int x = 0; x < P.G; x++) { a = fmax(a, P.red[4 * x]); b = fmax(b, P.red[4 * x + 1]); c = fmax(c, P.red[4 * x + 2]); }
-        GroupState &gs = P.gs[g];
-        gs.amax = a; gs.pivotmax = b; gs.pivotmin = (-c == 999e9) ? -1.0 : -c;
-        gs.pivotmax_prev = b;
-    }
+    if (threadIdx.x == 0) exch_max_group(P, g, from_recv);
     if (do_apply) exch_apply_group(P, g);
 }
 
@@ -2232,14 +2239,21 @@ __device__ __forceinline__ double mvn_corner_wave(const DevProb &P, const double
 // grow the boundary cores with the neighbours' fibers, evaluate the corner entries, LU-apply
 // blocks [0,NM): "share blocks to the LEFT" receive side (:912-952), one mode index k each;
 // blocks [NM,2NM): "share blocks to the RIGHT" receive side (dmrggmp.f90:598-627), one mode index j each
-template <int FUN>
-__global__ __launch_bounds__(TTX_BLK) void k_exch_boundary(DevProb P)
+// One boundary block (bx, g), called by every thread of the workgroup.  MSG = false (k_exch_boundary): the launch behind
+// k_exch_max_apply, which copied the neighbour's flag, rank and pivot index from the message into upd, r and the index tables.
+// MSG = true (k_exch_tail): the apply block runs BESIDE this one, so nothing it writes may be read here -- the flag hh[0], the
+// rank hh[1] and the dims beyond the bond ix[] come from the message itself (complete before the launch: the sweep kernel packs
+// it at its end), the corner maximum goes to gs.amax_bnd[par] and the evaluation count is left to the apply block
+// (boundary_neval).  What remains shared is read-only in the launch (own ranks, flags, tables, inv of the own bonds; the apply
+// block writes column hh[1] - 1 of the tables of bonds first - 1 / last + 1, a corner reads columns of older pivots there).
+template <int FUN, bool MSG>
+__device__ __forceinline__ void exch_boundary_block(const DevProb &P, int bx, int g, int par_)
 {
-    if (P.ctl[0]) return;
     extern __shared__ __align__(16) double dyn[];
     __shared__ double s_bc;
-    const int g = blockIdx.y, tid = threadIdx.x, m = P.d;
+    const int tid = threadIdx.x, m = P.d;
     GroupState &gs = P.gs[g];
+    double *amax_to = MSG ? &gs.amax_bnd[par_] : &gs.amax;
     const int first = gs.first, last = gs.last;
     const int *r = P.r + (size_t)g * (m + 2), *rr = P.rr + (size_t)g * (m + 2), *upd = P.upd + (size_t)g * (m + 2);
     double *par = dyn;
@@ -2252,10 +2266,12 @@ __global__ __launch_bounds__(TTX_BLK) void k_exch_boundary(DevProb P)
     __shared__ double s_corner;
     const bool dewave = (FUN == FUN_ISING) && P.ising_id != 1 && P.bnd_wave;
     const bool mvwave = (FUN == FUN_MVN) && P.bnd_wave;
-    if ((int)blockIdx.x < P.NM) {
-        const int k = blockIdx.x, p = last, br = last + 1;
-        if (!P.inR[g] || !upd[br] || k >= P.n[br]) return;
-        const int rp = r[p], rrp = rr[p], snew = r[br] - 1, n2 = P.n[br];
+    if (bx < P.NM) {
+        const int k = bx, p = last, br = last + 1;
+        if (!P.inR[g]) return;
+        const int *hh = (const int *)P.inR[g], *ix = hh + XH;         // the message's header and flattened pivot index (dims br+1..m)
+        if (!(MSG ? hh[0] : upd[br]) || k >= P.n[br]) return;
+        const int rp = r[p], rrp = rr[p], snew = (MSG ? hh[1] : r[br]) - 1, n2 = P.n[br];
         const double *msg = (const double *)(P.inR[g] + P.IOFF);      // (rr(p), n(p+1))
         double *A = core_ptr(P, P.arg, g, br, first), *W = core_ptr(P, P.row, g, br, first);
         double a = 0.0;
@@ -2264,7 +2280,7 @@ __global__ __launch_bounds__(TTX_BLK) void k_exch_boundary(DevProb P)
             for (int x = tid; x < P.npar; x += TTX_BLK) par[x] = P.par[x];
             const int *vp = vip_ptr(P, g, p, first) + 4 * (rp - 1);
             const short *Lt = L_ptr(P, g, p - 1, first), *Rt = R_ptr(P, g, br, first);
-            auto dimv = [&](int s) -> short { return (s < p) ? Lt[(size_t)(s - 1) * P.RM + (vp[0] - 1)] : (s == p) ? (short)vp[1] : (s == p + 1) ? (short)(k + 1) : Rt[(size_t)(s - p - 2) * P.RM + snew]; };
+            auto dimv = [&](int s) -> short { return (s < p) ? Lt[(size_t)(s - 1) * P.RM + (vp[0] - 1)] : (s == p) ? (short)vp[1] : (s == p + 1) ? (short)(k + 1) : MSG ? (short)ix[s - p - 2] : Rt[(size_t)(s - p - 2) * P.RM + snew]; };
             for (int x = tid; x < VSr; x += TTX_BLK) { rowA[x] = (x < p - 1) ? dimv(x + 1) : (short)1; rowB[x] = (x < m - p) ? dimv(p + 1 + x) : (short)1; }
             __syncthreads();
             if (dewave || mvwave) {
@@ -2278,8 +2294,8 @@ __global__ __launch_bounds__(TTX_BLK) void k_exch_boundary(DevProb P)
                 Src3 sx{rowA, p - 1, (int)vp[1], rowB};
                 a = (dewave || mvwave) ? s_corner : eval_src3<FUN, true>(P, par, sx, (long)g * P.HS + k);
                 if (!HOST_PASS1(FUN, P)) {
-                    atomic_max_pos(&gs.amax, fabs(a));
-                    if (k == 0) atomicAdd((unsigned long long *)&gs.neval, (unsigned long long)n2);   // :936
+                    atomic_max_pos(amax_to, fabs(a));
+                    if (!MSG && k == 0) atomicAdd((unsigned long long *)&gs.neval, (unsigned long long)n2);   // :936
                 }
             }
         }
@@ -2302,9 +2318,11 @@ __global__ __launch_bounds__(TTX_BLK) void k_exch_boundary(DevProb P)
         }
         if (tid < rp) W[k + (size_t)P.NM * snew + P.SW * tid] = xf;
     } else {
-        const int j = blockIdx.x - P.NM, p = first, bl = first - 1;
-        if (!P.inL[g] || !upd[bl] || j >= P.n[p]) return;
-        const int rp = r[p], rrp = rr[p], inew = r[bl] - 1, n1 = P.n[p];
+        const int j = bx - P.NM, p = first, bl = first - 1;
+        if (!P.inL[g]) return;
+        const int *hh = (const int *)P.inL[g], *ix = hh + XH;         // ... dims 1..bl
+        if (!(MSG ? hh[0] : upd[bl]) || j >= P.n[p]) return;
+        const int rp = r[p], rrp = rr[p], inew = (MSG ? hh[1] : r[bl]) - 1, n1 = P.n[p];
         const double *msg = (const double *)(P.inL[g] + P.IOFF);      // (n(p), rr(p))
         double *A = core_ptr(P, P.arg, g, p, first), *C = core_ptr(P, P.col, g, p, first);
         double y = 0.0;
@@ -2313,7 +2331,7 @@ __global__ __launch_bounds__(TTX_BLK) void k_exch_boundary(DevProb P)
             for (int x = tid; x < P.npar; x += TTX_BLK) par[x] = P.par[x];
             const int *vp = vip_ptr(P, g, p, first) + 4 * (rp - 1);
             const short *Lt = L_ptr(P, g, bl, first), *Rt = R_ptr(P, g, p + 1, first);
-            auto dimv = [&](int s) -> short { return (s < p) ? Lt[(size_t)(s - 1) * P.RM + inew] : (s == p) ? (short)(j + 1) : (s == p + 1) ? (short)vp[2] : Rt[(size_t)(s - p - 2) * P.RM + (vp[3] - 1)]; };
+            auto dimv = [&](int s) -> short { return (s < p) ? (MSG ? (short)ix[s - 1] : Lt[(size_t)(s - 1) * P.RM + inew]) : (s == p) ? (short)(j + 1) : (s == p + 1) ? (short)vp[2] : Rt[(size_t)(s - p - 2) * P.RM + (vp[3] - 1)]; };
             for (int x = tid; x < VSr; x += TTX_BLK) { rowA[x] = (x < p - 1) ? dimv(x + 1) : (short)1; rowB[x] = (x < m - p) ? dimv(p + 1 + x) : (short)1; }
             __syncthreads();
             if (dewave || mvwave) {
@@ -2327,8 +2345,8 @@ __global__ __launch_bounds__(TTX_BLK) void k_exch_boundary(DevProb P)
                 Src3 sx{rowA, p - 1, j + 1, rowB};
                 y = (dewave || mvwave) ? s_corner : eval_src3<FUN, true>(P, par, sx, (long)g * P.HS + P.NM + j);
                 if (!HOST_PASS1(FUN, P)) {
-                    atomic_max_pos(&gs.amax, fabs(y));
-                    if (j == 0) atomicAdd((unsigned long long *)&gs.neval, (unsigned long long)n1);
+                    atomic_max_pos(amax_to, fabs(y));
+                    if (!MSG && j == 0) atomicAdd((unsigned long long *)&gs.neval, (unsigned long long)n1);
                 }
             }
         }
@@ -2349,6 +2367,79 @@ __global__ __launch_bounds__(TTX_BLK) void k_exch_boundary(DevProb P)
             __syncthreads();
         }
         if (tid < rp) C[inew + (size_t)P.RM * j + P.SS * tid] = y;
+    }
+}
+template <int FUN>
+__global__ __launch_bounds__(TTX_BLK) void k_exch_boundary(DevProb P)
+{
+    if (P.ctl[0]) return;
+    exch_boundary_block<FUN, false>(P, (int)blockIdx.x, (int)blockIdx.y, 0);
+}
+// MAX / apply and the boundary blocks of sweep `it` in ONE launch (single process, device integrand): grid (2 NM + 1, G), blocks
+// x < 2 NM are the boundary blocks, block x = 2 NM is the group's apply block.  The blocks are independent: no block reads what
+// another one of the launch writes (exch_boundary_block), and nothing is counted, fenced or waited for.
+template <int FUN>
+__global__ __launch_bounds__(TTX_BLK) void k_exch_tail(DevProb P, int it)
+{
+    if (P.ctl[0]) return;
+    const int g = blockIdx.y;
+    if ((int)blockIdx.x < 2 * P.NM) { exch_boundary_block<FUN, true>(P, (int)blockIdx.x, g, it & 1); return; }
+    if (threadIdx.x == 0) {
+        exch_max_group(P, g, 0);
+        GroupState &gs = P.gs[g];
+        const int *upd = P.upd + (size_t)g * (P.d + 2);
+        const int u_r = P.inR[g] ? ((const int *)P.inR[g])[0] : 0, u_l = P.inL[g] ? ((const int *)P.inL[g])[0] : 0;
+        gs.neval += boundary_neval(P.inR[g] != nullptr, u_r, upd[gs.last], P.n[gs.last + 1], P.inL[g] != nullptr, u_l, upd[gs.first], P.n[gs.first]);
+    }
+    exch_apply_group(P, g);
+    if (!P.tail_side) return;
+    // the group's records of this sweep for the side stream and the next sweep kernel's entry (ttx_dev.h); the ranks behind the apply
+    __syncthreads();
+    const int m = P.d, tid = threadIdx.x, par = it & 1;
+    const GroupState &gs = P.gs[g];
+    const int *r = P.r + (size_t)g * (m + 2), *tp = P.tape + (size_t)g * (m + 2) * 4;
+    int *rq = P.rq + (size_t)g * (m + 2), *tq = P.tail_tape + ((size_t)par * P.G + g) * (m + 2) * 4;
+    for (int x = tid; x < m + 2; x += blockDim.x) rq[x] = r[x];
+    for (int x = 4 * gs.first + tid; x < 4 * (gs.last + 1); x += blockDim.x) tq[x] = tp[x];
+    if (tid == 0) {
+        TailRec t;
+        t.amax = gs.amax; t.pivotmax = gs.pivotmax; t.pivotmin = gs.pivotmin; t.bytes_half = gs.bytes_half; t.initval = gs.initval;
+        t.neval = gs.neval; t.n_resid = gs.n_resid;
+        P.tailrec[(size_t)par * P.G + g] = t;
+    }
+}
+// The end of sweep `it` from the records of its tail launch (single process): summary into the pinned slot `out`, stopping rule.  It
+// runs on the quadrature's stream beside sweep kernel it+1 and reads nothing that kernel writes.  It never clears the stop flag (an
+// abort of the running sweep kernel may have raised it) and raises it only where every block of that kernel decides the same at its
+// entry; then no sweep kernel runs any more and the groups' amax take the corner maxima, as k_sweep_end leaves them.
+__global__ __launch_bounds__(256) void k_sweep_summary(DevProb P, int it, double *out)
+{
+    const int m = P.d, tid = threadIdx.x, par = it & 1;
+    if (tid == 0) P.ctl[2] = P.ctl[0];
+    if (P.ctl[0]) return;
+    const TailRec *rec = P.tailrec + (size_t)par * P.G;
+    const int p_lo = P.gs[0].first, p_hi = P.gs[P.G - 1].last;
+    for (int p = p_lo + tid; p <= p_hi; p += blockDim.x) {   // owner of bond p, its rank and tape entry
+        int g = 0;
+        while (g + 1 < P.G && P.gs[g + 1].first <= p) g++;
+        const int *r = P.rq + (size_t)g * (m + 2), *tp = P.tail_tape + ((size_t)par * P.G + g) * (m + 2) * 4;
+        double *e = out + SUM_HDR + P.nprocs + 5 * p;
+        e[0] = (double)r[p]; e[1] = (double)tp[4 * p]; e[2] = (double)tp[4 * p + 1]; e[3] = (double)tp[4 * p + 2]; e[4] = (double)tp[4 * p + 3];
+    }
+    if (tid < P.G) out[SUM_HDR + P.gs[tid].gglobal] = rec[tid].initval;
+    if (tid != 0) return;
+    double nev = 0.0, by = 0.0, nr = 0.0;
+    for (int g = 0; g < P.G; g++) { nev += (double)rec[g].neval; by += rec[g].bytes_half; nr += (double)rec[g].n_resid; }
+    const double amax = max_pos(rec[0].amax, P.gs[0].amax_bnd[par]), pmax = rec[0].pivotmax;
+    out[SUM_NEVAL] = nev; out[SUM_BYTES] = by; out[SUM_NRESID] = nr;
+    out[SUM_AMAX] = amax; out[SUM_PMAX] = pmax; out[SUM_PMIN] = rec[0].pivotmin;
+    out[SUM_VAL] = 0.0;
+    const StopRule s = stop_rule(it, P.maxrank, P.accuracy, pmax, amax, P.strk[(it - 1) & 1]);
+    P.strk[par] = s.strikes;
+    P.ctl[1] = s.strikes;
+    if (s.ready) {
+        for (int g = 0; g < P.G; g++) P.gs[g].amax = max_pos(P.gs[g].amax, P.gs[g].amax_bnd[par]);
+        P.ctl[0] = 1;
     }
 }
 
@@ -2398,12 +2489,22 @@ __global__ __launch_bounds__(256) void k_collect(DevProb P)
 }
 // single-GPU end of sweep in one launch: snapshot for the forked quadrature, summary (written straight into the
 // pinned host slot `out`), stopping rule
-__global__ __launch_bounds__(256) void k_sweep_end(DevProb P, int it, double *out)
+// fold: the sweep's exchange was k_exch_tail, whose corner maxima wait in gs.amax_bnd[it & 1] (ttx_dev.h) -- they go into the
+// groups' amax first (the maximum of the same bit patterns atomic_max_pos would have combined, a NaN's included) and the slot is cleared
+__global__ __launch_bounds__(256) void k_sweep_end(DevProb P, int it, double *out, int fold)
 {
     const int n = P.G * (P.d + 2), m = P.d, tid = threadIdx.x;
     for (int x = tid; x < n; x += blockDim.x) P.rq[x] = P.r[x];
     if (tid == 0) P.ctl[2] = P.ctl[0];
     if (P.ctl[0]) return;
+    if (fold) {
+        if (tid < P.G) {
+            GroupState &gs = P.gs[tid];
+            gs.amax = max_pos(gs.amax, gs.amax_bnd[it & 1]);
+            gs.amax_bnd[it & 1] = 0.0;
+        }
+        __syncthreads();
+    }
     // multi-GPU job: `out` is this GPU's contribution to a SUM all-reduce -- only the bonds of its own groups, and the
     // job-wide scalars from the GPU that holds global group 0 (after k_exch_max_apply every GPU has the same maxima)
     const int p_lo = P.gs[0].first, p_hi = P.gs[P.G - 1].last;
@@ -2422,12 +2523,9 @@ __global__ __launch_bounds__(256) void k_sweep_end(DevProb P, int it, double *ou
     out[SUM_NEVAL] = nev; out[SUM_BYTES] = by; out[SUM_NRESID] = nr;
     if (P.g0 == 0) { out[SUM_AMAX] = amax; out[SUM_PMAX] = pmax; out[SUM_PMIN] = P.gs[0].pivotmin; }
     out[SUM_VAL] = 0.0;
-    int ready = (it + 1 >= P.maxrank);
-    if (P.accuracy >= 0.0) {
-        if (pmax <= P.accuracy * amax) P.ctl[1]++; else P.ctl[1] = 0;
-        ready = ready || (P.ctl[1] >= 3);
-    }
-    P.ctl[0] = ready;
+    const StopRule s = stop_rule(it, P.maxrank, P.accuracy, pmax, amax, P.ctl[1]);
+    P.ctl[1] = s.strikes;
+    P.ctl[0] = s.ready;
 }
 __device__ __forceinline__ void collect_summary(const DevProb &P)
 {
