@@ -27,6 +27,7 @@
 #pragma once
 #include "ttx_fused.h"
 #include "ttx_mvn.h"       // mvn_lane: one double of a wave by v_readlane
+#include "ttx_cluster_rules.h"   // cl_slice, cl_wact, cl_key: the rules a host program checks
 
 #define CB 256      // threads of a cluster workgroup
 #ifndef TTX_CL_UNR
@@ -100,9 +101,9 @@ __device__ __forceinline__ double f_ising_c4w(int cA, int cB, const double *an, 
 }
 
 // arg-max over a wave by the first-max rule (larger |.| wins, ties go to the lower position) in two cheap passes on the DPP
-// path: the maximum of |.| (an fp64 max per step), then the smallest (position, sign) key among the lanes that hold it (an
-// integer min per step) -- a third of the instructions of the three-operand compare-and-select of wave_argmax.  a is never NaN
-// (a NaN residual never replaces the start value -1), so fmax and == are exact here.  Result in every lane.
+// path: the maximum of |.| (wave_max_key below), then the smallest (position, sign) key among the lanes that hold it (an
+// integer min per step) -- a fraction of the instructions of the three-operand compare-and-select of wave_argmax.  a is never NaN
+// (a NaN residual never replaces the start value -1), so the maximum and == are exact here.  Result in every lane.
 __device__ __forceinline__ int wave_min_i(int v)
 {
     v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0xb1, 0xf, 0xf, false));
@@ -113,9 +114,41 @@ __device__ __forceinline__ int wave_min_i(int v)
     v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x143, 0xc, 0xf, false));
     return __builtin_amdgcn_readlane(v, 63);
 }
+// Maximum over a wave of the doubles the rook loop reduces, by their integer key (ttx_cluster_rules.h): the fiber maxima
+// mx (fmax of |values| from 0.0: fmax drops a NaN operand) and the residual maxima ab (|b| that compared greater than the
+// start value -1.0, or that start value: a NaN compares false) are >= +0.0 or -1.0 and never a NaN.  Two integer trees of
+// one v_max_*_dpp per step -- the high words, then the low words of the lanes that hold the largest high word -- where
+// wave_max on the register pair takes six instructions per step.  Bit for bit the value wave_max returns.
+__device__ __forceinline__ int wave_max_i(int v)
+{
+    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0xb1, 0xf, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x4e, 0xf, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x124, 0xf, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x128, 0xf, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x142, 0xa, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x143, 0xc, 0xf, false));
+    return __builtin_amdgcn_readlane(v, 63);
+}
+__device__ __forceinline__ unsigned wave_max_u(unsigned v)
+{
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xb1, 0xf, 0xf, false));
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4e, 0xf, 0xf, false));
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xf, 0xf, false));
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false));
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));
+    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
+__device__ __forceinline__ double wave_max_key(double x)
+{
+    const ClKey k = cl_key(x);
+    const int hmax = wave_max_i(k.hi);
+    const unsigned lmax = wave_max_u(cl_key_lo_at(k, hmax));
+    return cl_unkey(ClKey{hmax, lmax});
+}
 __device__ __forceinline__ void wave_argmax2(double &a, double &v, int &idx)
 {
-    const double amx = wave_max(a);
+    const double amx = wave_max_key(a);
     const int key = (a == amx && idx != INT_MAX) ? ((idx << 1) | (signbit(v) ? 1 : 0)) : INT_MAX;
     const int kmin = wave_min_i(key);
     a = amx;
@@ -200,6 +233,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
     extern __shared__ __align__(16) double dyn[];
     __shared__ int zc[128], zr[128], zcs[128], zrs[128], keepc[128], keepr[128];
     __shared__ int nzc, nzr, nsc, nsr, s_ok;
+    __shared__ int slt[2][TTX_CLMAX + 1], wtab[TTX_CLMAX];   // slice bounds of the two modes of a bond step; waves at work per workgroup
     __shared__ ttx_cdfseg segc[TTX_TABSEG], segr[TTX_TABSEG];
     __shared__ double sha[8], shv[8], shm[8]; __shared__ int shi[8];
     __shared__ double pLw[64], pLk[64], pRv[64], pRk[64];   // prefix states of the two running sums per left / right row
@@ -326,12 +360,6 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         const int p = (dir == 1) ? first + pp - 1 : last + 1 - pp;          // :330-331
         const int r0 = r[p - 1], r1 = r[p], r2 = r[p + 1], n1 = P.n[p], n2 = P.n[p + 1];
         const int nlot = r0 + n1 + n2 + r2;
-        // slice bounds floor(c * n / NB): c <= NB <= 16 and n <= NM, so the product fits 32 bits (a 64-bit division is a long
-        // per-lane instruction sequence; these are evaluated twelve times per bond step)
-        auto slice = [&](int c, int n) { return (int)((unsigned)c * (unsigned)n / (unsigned)NB); };
-        const int jlo = slice(cb, n1), jhi = slice(cb + 1, n1);   // own columns j of acol1
-        const int klo = slice(cb, n2), khi = slice(cb + 1, n2);   // own rows k of arow1
-        const int nj = jhi - jlo, nk = khi - klo;
         double *Cp = core_ptr(P, P.col, g, p, first), *Wq = core_ptr(P, P.row, g, p + 1, first);
         double *Ap = core_ptr(P, P.arg, g, p, first), *Aq = core_ptr(P, P.arg, g, p + 1, first);
         const short *Lt = L_ptr(P, g, p - 1, first), *Rt = R_ptr(P, g, p + 1, first);
@@ -386,6 +414,18 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         }
         CST(0);
         if (zkeep) seg_issue(r0 * n1 - ZN[2 * (p - first)], n2 * r2 - ZN[2 * (p - first) + 1]);
+        // The slice bounds of this bond step as a table, one division each, on a wave that has no prefix chain to run: lanes
+        // 0..16 of wave 3 hold floor(c n1 / NB), lanes 17..33 floor(c n2 / NB), c = min(lane, NB) (slices behind the last are
+        // empty); lane c then takes the participating waves of workgroup c from the widths of its two slices.  Read behind the
+        // next barrier; the last reader of the step before is its append, in front of the closing cluster_sync.
+        static_assert(2 * (TTX_CLMAX + 1) <= 64 && TTX_CLMAX + TTX_CLMAX + 2 < 64, "the two slice rows and the shuffles of the fill fit one wave");
+        if (wv == CB / 64 - 1) {
+            const int side = lane > TTX_CLMAX ? 1 : 0, c = lane - side * (TTX_CLMAX + 1);
+            const int s = cl_slice(min(c, NB), side ? n2 : n1, NB);
+            const int s1 = __shfl(s, lane + 1), t0 = __shfl(s, lane + TTX_CLMAX + 1), t1 = __shfl(s, lane + TTX_CLMAX + 2);
+            if (lane < 2 * (TTX_CLMAX + 1)) slt[side][c] = s;
+            if (lane < TTX_CLMAX) wtab[lane] = cl_wact(s1 - s, t1 - t0, r0, r2, CB / 64);
+        }
         // ---- lottery (:410-484): every block draws and scores all candidates (identical results, no traffic) ----
         // generator words of the two draw columns: 48271^(2*rngpos+1) and 48271^(2*(rngpos+nlot)+1), advanced from
         // step to step by the small power 48271^(2*nlot) (every thread keeps them; no shared state, no barrier)
@@ -446,6 +486,9 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         }
         __syncthreads();
         CST(2);
+        const int jlo = __builtin_amdgcn_readfirstlane(slt[0][cb]), jhi = __builtin_amdgcn_readfirstlane(slt[0][cb + 1]);   // own columns j of acol1
+        const int klo = __builtin_amdgcn_readfirstlane(slt[1][cb]), khi = __builtin_amdgcn_readfirstlane(slt[1][cb + 1]);   // own rows k of arow1
+        const int nj = jhi - jlo, nk = khi - klo;
         double ma = 0.0, ba = -1.0, bv = 0.0; int bi = INT_MAX;
         // list lengths as wave-uniform values: the two searches of ttx_lottery_index2 then run a uniform number of steps
         const int nscu = __builtin_amdgcn_readfirstlane(nsc), nsru = __builtin_amdgcn_readfirstlane(nsr);
@@ -473,8 +516,8 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
             const double b = f - t, aa = fabs(b);
             if (aa > ba || (aa == ba && il < bi)) { ba = aa; bv = b; bi = il; }
         }
-        ma = wave_max(ma);
-        wave_argmax(ba, bv, bi);
+        ma = wave_max_key(ma);
+        wave_argmax2(ba, bv, bi);                      // (ba is |bv| or the start value, never a NaN: the same first maximum as wave_argmax)
         if (lane == 0) { shm[wv] = ma; sha[wv] = ba; shv[wv] = bv; shi[wv] = bi; }
         __syncthreads();
         ma = shm[0]; ba = sha[0]; bv = shv[0]; bi = shi[0];
@@ -499,14 +542,9 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         // its record exchange: at low ranks that is one wave per workgroup, and 24 idle waves polling the same four cache lines for
         // the whole evaluation delayed the records of the working ones (2900 cycles from the last store to the end of the poll,
         // against ~1000 in isolation: profiles/probes/probe_exchange.hip).  The others wait at the barrier behind the loop and take
-        // the results from LDS.  wact(c): participating waves of workgroup c -- the same number on every wave of the cluster.
-        auto wact = [&](int c) {
-            const int njc = slice(c + 1, n1) - slice(c, n1), nkc = slice(c + 1, n2) - slice(c, n2);
-            const int e = max(r0 * njc, nkc * r2);
-            return min(CB / 64, max(1, (e + 63) >> 6));
-        };
-        const bool rook_active = wv < wact(cb);
-        const bool slot_on = (lane < NB * (CB / 64)) && ((lane & (CB / 64 - 1)) < wact(lane / (CB / 64)));      // lane = record slot
+        // the results from LDS.  wtab[c]: participating waves of workgroup c (cl_wact) -- the same number on every wave of the cluster.
+        const bool rook_active = wv < wtab[cb];
+        const bool slot_on = (lane < NB * (CB / 64)) && ((lane & (CB / 64 - 1)) < wtab[lane / (CB / 64)]);      // lane = record slot
         if (rook_active) {
         for (int h = 0; h < H && !done; h++) {
             // (the rook turn, the traffic count and the pivot taking below are this kernel's own copies of rook_turn,
@@ -569,8 +607,8 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
             }
             CST(7);
             WST(1);
-            mx = wave_max(mx);
-            wave_argmax2(ab, bb, ix);
+            mx = wave_max_key(mx);
+            if (resid) wave_argmax2(ab, bb, ix);         // (without a residual there is no arg-max: ix is not read)
             WST(2);
             // exchange: every WAVE publishes ONE tagged 16-byte record {|b|max, position, tag | sign} of its own elements and then
             // polls the 4 NB records of this half-step itself (L1-bypassing 16-byte loads, one per lane) and reduces them -- every
@@ -581,6 +619,15 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
             // records crosses blocks here (fibers stay in LDS, factors were published at the end of earlier bond steps).  Records
             // are double-buffered by half-step parity (a wave cannot be two exchanges ahead of another: it needs that wave's record
             // of the exchange in between); the tag carries the launch number.
+            // The turn that ends a full rook search (piv != 0, dn already true: evaluation only, no residual) has no arg-max to
+            // agree on and stores ONLY its running-maximum record; it neither stores nor polls an arg-max record.  The poll of the
+            // running maxima behind the loop waits for that very record of every participating wave, so it orders the waves as the
+            // skipped poll did: a wave that has stored its running maximum of exchange L has finished polling exchange L-1, so
+            // the parity buffers of exchange L+1 are free, and the closing cluster_sync separates the bond steps in any case.  The
+            // exchange still counts (hcount): tags and parities go on as if it had taken place.  piv = 0 has no poll behind the
+            // loop and keeps the stores and polls of both of its exchanges; like every turn without a residual it runs no arg-max
+            // reduction around them (ab, ix keep their start values and nothing reads them).
+            const bool xchg = resid || P.piv == 0;
             u4 *bufA = (u4 *)part + ((size_t)(hcount & 1) * P.G + g) * TTX_CLREC;
             u4 *bufB = bufA + (size_t)2 * P.G * TTX_CLREC;
             const unsigned gen = ((unsigned)epoch << 20) | (unsigned)(hcount + 1);
@@ -590,14 +637,16 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                 u4 ra, rb;
                 rb.x = (unsigned)um; rb.y = (unsigned)(um >> 32); rb.z = gen; rb.w = 0;
                 st16(&bufB[cb * (CB / 64) + wv], rb);
-                ra.x = (unsigned)ua; ra.y = (unsigned)(ua >> 32); ra.z = (unsigned)ix; ra.w = gen | (signbit(bb) ? 0x80000000u : 0u);
-                st16(&bufA[cb * (CB / 64) + wv], ra);
+                if (xchg) {
+                    ra.x = (unsigned)ua; ra.y = (unsigned)(ua >> 32); ra.z = (unsigned)ix; ra.w = gen | (signbit(bb) ? 0x80000000u : 0u);
+                    st16(&bufA[cb * (CB / 64) + wv], ra);
+                }
             }
             CST(8);
             WST(3);
             int ok = 1;
             ab = -1.0; bb = 0.0; ix = INT_MAX;
-            if (slot_on) {
+            if (xchg && slot_on) {
                 unsigned spins = 0;
                 for (;;) {
                     const u4 ra = ld16(&bufA[lane]);
@@ -614,7 +663,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
             }
             WST(4);
             ok = __all(ok);
-            wave_argmax2(ab, bb, ix);
+            if (resid) wave_argmax2(ab, bb, ix);
             WST(5);
             if (!ok) {                                   // aborted: the tail kernels of this sweep do nothing
                 if (lane == 0) { __hip_atomic_store(P.cl_abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); P.ctl[0] = 1; *(volatile int *)&s_ok = 0; }
@@ -653,7 +702,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                 if (lane == 0) { __hip_atomic_store(P.cl_abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); P.ctl[0] = 1; *(volatile int *)&s_ok = 0; }
                 return;
             }
-            amax = fmax(amax, wave_max(mx));
+            amax = fmax(amax, wave_max_key(mx));
         }
         if (tid == 0) {
             s_rook.ii = ii; s_rook.jj = jj; s_rook.kk = kk; s_rook.qq = qq; s_rook.hcount = hcount; s_rook.rc_k = rc_k; s_rook.rc_q = rc_q;

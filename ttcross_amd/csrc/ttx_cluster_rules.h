@@ -1,0 +1,29 @@
+// ttx_cluster_rules.h -- the two value rules of the cluster sweep kernel (ttx_cluster.h) that a host program can check
+// (tests/cluster_diet_main.cpp): the slice of the mode index a workgroup owns, and the integer key under which the kernel
+// takes wave maxima of its non-negative doubles.
+#pragma once
+#include "ttx_cdf.h"     // TTX_HD, ttx_dbits, ttx_bitsd
+
+// Workgroup c of NB owns the mode indices [cl_slice(c, n, NB), cl_slice(c + 1, n, NB)) of a mode of size n: floor(c n / NB).
+// c <= NB <= 16 and n <= NM, so the product fits 32 bits (a 64-bit division is a long per-lane instruction sequence).
+TTX_HD int cl_slice(int c, int n, int NB) { return (int)((unsigned)c * (unsigned)n / (unsigned)NB); }
+
+// Waves of a workgroup that own fiber elements of a bond step, from the widths nj, nk of its two slices: the largest fiber
+// slice in units of 64 elements, at least wave 0, at most nw waves.
+TTX_HD int cl_wact(int nj, int nk, int r0, int r2, int nw)
+{
+    const int a = r0 * nj, b = nk * r2, e = a > b ? a : b, w = (e + 63) >> 6;
+    return w < 1 ? 1 : (w > nw ? nw : w);
+}
+
+// The key of a double that is >= +0.0 (+inf included) or the start value -1.0, never -0.0 and never a NaN: its high word
+// as a SIGNED int, then its low word as an unsigned one.  Among such values the pair orders exactly like the double:
+// a non-negative double's bit pattern grows with its value and its high word is >= 0, -1.0 has the only negative high
+// word (0xbff00000), and equal keys are equal bit patterns.  A maximum over a wave is then two integer trees of one
+// DPP instruction per step (the high words, then the low words of the lanes that hold the largest high word) instead
+// of one tree of six instructions per step on register pairs.
+struct ClKey { int hi; unsigned lo; };
+TTX_HD ClKey cl_key(double x) { const uint64_t b = ttx_dbits(x); return ClKey{(int)(uint32_t)(b >> 32), (unsigned)b}; }
+TTX_HD double cl_unkey(ClKey k) { return ttx_bitsd(((uint64_t)(uint32_t)k.hi << 32) | k.lo); }
+// the low word a lane puts into the second tree once the largest high word hmax of the wave is known
+TTX_HD unsigned cl_key_lo_at(ClKey k, int hmax) { return k.hi == hmax ? k.lo : 0u; }
