@@ -310,6 +310,46 @@ int ttx_lincomb(int32_t m, const double *coef /* [m] */, ttx_engine *const *x /*
 int ttx_hadamard(ttx_engine *x, ttx_engine *y, ttx_engine **out);
 int ttx_algebra_last(const ttx_engine *h, double *ms, double *bytes_read, double *bytes_written);
 
+/* A rounded sum of resident trains, on the device (ttcross_amd/csrc/ttx_roundsum.h): sum_t coef[t] x[t] rounded by one randomized
+ * right-to-left and one left-to-right pass ("randomize-then-orthogonalize", Al Daas et al., SIAM J. Sci. Comput. 2023), without
+ * ever forming a core of rank sum_t r_t.  ttx_lincomb keeps its refusal; this is the call for sums beyond rank 128.
+ * Inputs: m trains with equal d and mode sizes n_k on one device, ranks r_t(k), S(k) = sum_t r_t(k); coefficients; a sketch rank
+ * L = rsketch (0 means 128); a seed.
+ *  1. Sketch ranks, on the host: l(0) = l(d) = 1; l(k) = min(L, S(k), prod_{j<=k} n_j, prod_{j>k} n_j), a product no longer
+ *     multiplied once it is above 128; then left to right l(k) <= l(k-1) n_k and right to left l(k-1) <= n_k l(k), so that every
+ *     matrix that is QR-factored is tall or square.
+ *  2. Sketch train Omega_k (l(k-1), n_k, l(k)), uniform on (-1, 1), generated on the device from (seed, k, x), x the flat
+ *     column-major index a + l(k-1) (i + n_k b), k = 1 .. d, by uint64 arithmetic:
+ *         z = seed + 0x9E3779B97F4A7C15 * ((k << 40) + x + 1)
+ *         z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z = z ^ (z >> 31)
+ *         value = (bit 63 of z ? -1 : +1) * ((z >> 11) & (2^52 - 1)) * 2^-52
+ *  3. Right to left: W_t(d) = [1]; W_t(k-1) = sum_i X_{t,k}(:, i, :) W_t(k) Omega_k(:, i, :)^T.  The W_t(k) of all terms are
+ *     stacked in term order; after each step the stack is multiplied by 2^-e, (f, e) = frexp(max |W|) (e = 0 for zeros or a stack
+ *     that holds an Inf or a NaN) -- one power of two per bond for all terms: it changes no bit of any Q and keeps long trains in range.
+ *  4. Left to right: Y_t(1) = coef[t] X_{t,1} (the only use of the coefficients, as in ttx_lincomb); the Y_t(k) side by side
+ *     are Y(k) (l(k-1) n_k rows, S(k) columns).  For k = 1 .. d-1: Z = Y(k) W(k); Z = Q R by the engine's QR; new core k = Q;
+ *     M = Q^T Y(k); Y_t(k+1) = M_t x_1 X_{t,k+1}.  New core d = sum_t Y_t(d) in term order.  Y is plain double without a running
+ *     exponent, as in ttx_contract.
+ *  5. tol >= 0: the truncation of ttx_svd(tol, rmax) runs on the new train; tol < 0 skips it and the result is the left-orthogonal
+ *     train of step 4 with ranks l(k).
+ *   mode : TTX_EVAL_MFMA runs steps 3 and the products of step 4 with the cores on v_mfma_f64_16x16x4_f64, TTX_EVAL_EXACT by plain
+ *          loops (the checker), TTX_EVAL_AUTO lets the engine choose by the work of the call.  Summation orders are fixed: a call
+ *          repeats bit for bit.  The two modes agree to rounding.
+ * Limits: m <= 256; S(k) <= 4096 at every bond.  TTX_EINVAL, each before any device call: null pointers, m < 1, m > 256 (the message
+ * names the value), rsketch outside 0 .. 128, rmax < 0, a NaN tol, an unknown mode, then the operand checks of ttx_lincomb, then a
+ * rank sum above 4096 (the message names the bond and the value).  TTX_ESTATE and multi-process engines as for ttx_lincomb.
+ * Everything is enqueued on x[0]'s stream, the other operands must be idle, and the call synchronises before it returns.  *out is
+ * a new single-process engine without integrand whose storage is sized by max l(k); work space comes from x[0].  The operands are
+ * not modified; the same engine may appear several times.  After a refusal *out is NULL and nothing stays allocated.
+ * ttx_roundsum_last, called with x[0]: milliseconds (HIP events) of the right-to-left pass, of the GEMMs, of the QRs (with Q's way
+ * into the new core and its transpose) and of the advance launches of the last call, summed over the steps (the three phases of the
+ * second pass alternate d - 1 times, so they are timed by a chain of events that x[0] keeps and reuses, 4 d of them); flops = the products of
+ * steps 3 and 4 (the QRs not counted); the sketch ranks l(0 .. d); the mode that ran (-1: none yet).  Any pointer may be NULL.
+ * Added without a new ttx_version: look the symbols up. */
+int ttx_lincomb_round(int32_t m, const double *coef, ttx_engine *const *x, int32_t rsketch, double tol, int32_t rmax,
+                      uint64_t seed, int32_t mode, ttx_engine **out);
+int ttx_roundsum_last(const ttx_engine *h, double *ms /* [4]: sketch, gemm, qr, advance */, double *flops, int32_t *lsk /* [d+1] */, int32_t *mode_ran);
+
 /* Matrices applied to chosen modes of the resident train, on the device (ttcross_amd/csrc/ttx_modeapply.h): the n-mode product,
  * G'_k(a, j, b) = sum_i A_k(j, i) G_k(a, i, b) with A_k of m_k x n_k (TT-Toolbox: ttm).  COS coefficients to values on a grid,
  * regridding, cumulative sums and differentiation along a mode.  ttx_contract is the case m_k = 1 followed by dropping the mode.

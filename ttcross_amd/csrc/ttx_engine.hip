@@ -50,6 +50,7 @@ static cluster_kernel_t cluster_kernel(int var)
 #include "ttx_contract.h"
 #include "ttx_modeapply.h"
 #include "ttx_algebra.h"
+#include "ttx_roundsum.h"
 #include "ttx_sample.h"
 #include "ttx_topk.h"
 #include "ttx_trainfun.h"
@@ -130,6 +131,8 @@ enum {
     SC_MAT,                             // ttx_mode_apply: the matrices of the applied modes (its tables go to SC_META)
     SC_KP, SC_KW, SC_KS, SC_KX,         // ttx_topk: the Gram matrices P_0 .. P_(d-1), the W of a Gram step, a mode's score sheet (keys), the two state buffers
     SC_KREC, SC_KSEL, SC_KOUT,          // ttx_topk: the kept positions of every mode, the selection's state (words, chunk counts, histogram), the rows before and after the ordering
+    SC_RSO, SC_RSW, SC_RSYA, SC_RSYB,   // ttx_lincomb_round: the sketch train Omega, the stacked W of all bonds, the two Y buffers
+    SC_RSM, SC_RSTAB,                   // ttx_lincomb_round: M = Q^T Y (first the coefficients), the descriptor tables (RsBlk) and Omega's offsets
     SC_NBUF
 };
 struct EvBuf { void *p = nullptr; size_t bytes = 0; };
@@ -141,7 +144,8 @@ struct OpTimer {
     int ms(double *out) { float t = 0.f; HIPCHECK(hipEventElapsedTime(&t, ev[0], ev[1])); *out = t; return TTX_OK; }   // after a synchronise
 };
 enum { TM_MODESUM, TM_ALG, TM_HEAD, TM_DRAW, TM_APPLY,             // k_ct_modesum, the algebra launch, k_sm_head, the k_sm_draw of a chunk, k_ma_apply
-       TM_GRAM, TM_SCORE, TM_SELECT, TM_N };                       // ttx_topk: the Gram chain, a mode's scoring launch, a mode's selection and advance
+       TM_GRAM, TM_SCORE, TM_SELECT,                               // ttx_topk: the Gram chain, a mode's scoring launch, a mode's selection and advance
+       TM_RS_SKETCH, TM_N };                                       // ttx_lincomb_round: the right-to-left pass (the GEMMs, QRs and advances alternate d - 1 times: RsMarks on ttx_engine::rs_ev)
 
 struct DevFun;                          // a loaded device integrand (TTX_FUN_DEVICE), defined with slot_eval
 struct TrainFun;                        // the operands and the combiner of TTX_FUN_TRAINS, defined with slot_eval
@@ -244,6 +248,10 @@ struct ttx_engine {
     int ma_mode = -1;
     double tk_ms_gram = 0.0, tk_ms_score = 0.0, tk_ms_select = 0.0, tk_flops = 0.0;   // the last ttx_topk
     int tk_mode = -1;
+    double rs_ms[4] = {0.0, 0.0, 0.0, 0.0}, rs_flops = 0.0;                    // the last ttx_lincomb_round with this engine first: sketch, gemm, qr, advance
+    std::vector<int32_t> rs_l;                                                  // its sketch ranks l(0 .. d)
+    int rs_mode = -1;
+    std::vector<hipEvent_t> rs_ev;                                              // the event chain of its left-to-right pass (RsMarks)
 };
 
 // the process-wide pool of the host integrand (ttx_host_pool.h): engines driven from different host threads take turns on it
@@ -737,6 +745,7 @@ extern "C" void ttx_destroy(ttx_engine *h)
         if (h->P.hreq) (void)hipHostFree(h->P.hreq);
     }
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
+    for (auto &e : h->rs_ev) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -3358,6 +3367,170 @@ extern "C" int ttx_algebra_last(const ttx_engine *h, double *ms, double *bytes_r
 {
     if (!h || !ms || !bytes_read || !bytes_written) return fail(TTX_EINVAL, "ttx_algebra_last: null argument");
     *ms = h->alg_ms; *bytes_read = h->alg_rd; *bytes_written = h->alg_wr;
+    return TTX_OK;
+}
+
+// ---- a rounded sum of resident trains (ttx_roundsum.h) ----------------------------------------------------------------------------
+namespace {
+// events between the phases of the left-to-right pass: mark(phase) closes the stretch since the previous mark; after a synchronise,
+// sum() adds every stretch to its phase (1 gemm, 2 qr, 3 advance).  One OpTimer pair per phase cannot do it: the phases alternate
+// d - 1 times inside one enqueued call.
+struct RsMarks {
+    std::vector<hipEvent_t> &pool;          // the engine's (ttx_engine::rs_ev): created once, reused by every call, destroyed with the engine
+    std::vector<int> phase;
+    explicit RsMarks(std::vector<hipEvent_t> &p) : pool(p) {}
+    int mark(hipStream_t s, int ph)
+    {
+        if (phase.size() == pool.size()) { hipEvent_t e; HIPCHECK(hipEventCreate(&e)); pool.push_back(e); }
+        HIPCHECK(hipEventRecord(pool[phase.size()], s));
+        phase.push_back(ph);
+        return TTX_OK;
+    }
+    int sum(double *ms)
+    {
+        for (size_t x = 1; x < phase.size(); x++) { float t = 0.f; HIPCHECK(hipEventElapsedTime(&t, pool[x - 1], pool[x])); ms[phase[x]] += t; }
+        return TTX_OK;
+    }
+};
+}
+// everything of ttx_lincomb_round that works on the new engine e (ranks l): a failure leaves e to the caller to destroy.  All launches go
+// to x[0]'s stream: e runs on it for the length of the call (qr(), unpack_core and svd_impl launch on their engine's stream).
+static int rs_fill(int m, const double *coef, ttx_engine *const *x, ttx_engine *e, const std::vector<long long> &S, const int32_t *l, double tol, int rmax,
+                   unsigned long long seed, int mode)
+{
+    ttx_engine *h = x[0];
+    const int d = h->d;
+    int rc;
+    if ((rc = tt_prepare(e, "ttx_lincomb_round"))) return rc;
+    struct OnStream { ttx_engine *e; hipStream_t own; ~OnStream() { e->stream = own; } } on{e, e->stream};
+    e->stream = h->stream;
+    // tables: RsBlk [d][m] (mode k at (k - 1) m), Omega's offsets [d + 1]; sizes
+    std::vector<RsBlk> blks((size_t)d * m);
+    std::vector<size_t> ooff(d + 1, 0), woff(d + 2, 0);
+    std::vector<long long> tS(d + 1, 0), tA(d + 1, 0);
+    size_t ymax = 1, mmax = (size_t)m;
+    double fl = 0.0;
+    for (int k = 1; k <= d; k++) {
+        const int n = h->n1[k], l0 = l[k - 1], l1 = l[k];
+        ooff[k] = ooff[k - 1] + (size_t)l0 * n * l1;
+        woff[k + 1] = woff[k] + (size_t)S[k] * l1;                              // W(k) at woff[k], k = 1 .. d
+        ymax = std::max(ymax, (size_t)l0 * n * (size_t)S[k]);
+        mmax = std::max(mmax, (size_t)l1 * (size_t)S[k]);
+        const int ntp = (l0 + 15) / 16;
+        int o0 = 0, o1 = 0;
+        for (int t = 0; t < m; t++) {
+            RsBlk &B = blks[(size_t)(k - 1) * m + t];
+            B = RsBlk{};
+            B.x = core_dev(x[t], k); B.RM = x[t]->RM; B.SS = x[t]->P.SS;
+            B.r0 = x[t]->rfinal[k - 1]; B.r1 = x[t]->rfinal[k]; B.o0 = o0; B.o1 = o1;
+            B.firstS = tS[k]; B.firstA = tA[k];
+            tS[k] += (B.r0 + 15) / 16;
+            tA[k] += (long long)ntp * (((long long)n * B.r1 + 63) / 64);
+            o0 += B.r0; o1 += B.r1;
+            if (k >= 2) fl += 2.0 * B.r0 * n * l1 * ((double)B.r1 + l0);        // the sketch step of mode k
+            fl += 2.0 * l0 * B.r0 * n * B.r1;                                   // the advance into mode k
+        }
+        if (tA[k] > 0x7fffffffll) return fail(TTX_EINVAL, "ttx_lincomb_round: too many tiles (%lld)", tA[k]);
+        if (k < d) fl += 4.0 * l0 * n * l1 * (double)S[k];                      // Z = Y W and M = Q^T Y
+    }
+    const int eff = mode == TTX_EVAL_AUTO ? (fl >= TTX_RS_AUTO_FLOPS ? TTX_EVAL_MFMA : TTX_EVAL_EXACT) : mode;
+    h->rs_ms[0] = h->rs_ms[1] = h->rs_ms[2] = h->rs_ms[3] = 0.0; h->rs_flops = fl; h->rs_mode = eff; h->rs_l.assign(l, l + d + 1);
+    OpMeta meta(h->meta_host);
+    const size_t o_blk = meta.put(blks), o_off = meta.put(ooff);
+    char *dm;
+    if ((rc = meta.upload(h, SC_RSTAB, &dm)) || (rc = buf_reserve(h, SC_RSO, sizeof(double) * std::max<size_t>(ooff[d], 1))) ||
+        (rc = buf_reserve(h, SC_RSW, sizeof(double) * woff[d + 1])) || (rc = buf_reserve(h, SC_RSYA, sizeof(double) * ymax)) ||
+        (rc = buf_reserve(h, SC_RSYB, sizeof(double) * ymax)) || (rc = buf_reserve(h, SC_RSM, sizeof(double) * mmax))) return rc;
+    const RsBlk *dblk = (const RsBlk *)(dm + o_blk);
+    double *Om = buf<double>(h, SC_RSO), *W = buf<double>(h, SC_RSW), *Y = buf<double>(h, SC_RSYA), *Yn = buf<double>(h, SC_RSYB), *M = buf<double>(h, SC_RSM);
+    hipStream_t st = h->stream;
+    size_t omax = 1;
+    for (int k = 1; k <= d; k++) omax = std::max(omax, ooff[k] - ooff[k - 1]);
+    hipLaunchKernelGGL(k_rs_omega, dim3(g1(omax).x, d), dim3(256), 0, st, seed, (const size_t *)(dm + o_off), Om);
+    // right to left: W(d) = ones, W(k-1) from W(k)
+    OpTimer &tm = h->timer[TM_RS_SKETCH];
+    if ((rc = tm.start(st))) return rc;
+    hipLaunchKernelGGL(k_fill_const, g1((size_t)m), dim3(256), 0, st, (size_t)m, W + woff[d], 1.0);
+    for (int k = d; k >= 2; k--) {
+        const int n = h->n1[k], l0 = l[k - 1], l1 = l[k];
+        if (eff == TTX_EVAL_MFMA)
+            hipLaunchKernelGGL(k_rs_sketch<true>, dim3((unsigned)tS[k]), dim3(256), 0, st, dblk + (size_t)(k - 1) * m, m, n, l0, l1, (const double *)(Om + ooff[k - 1]),
+                               (const double *)(W + woff[k]), (int)S[k], W + woff[k - 1], (int)S[k - 1]);
+        else
+            hipLaunchKernelGGL(k_rs_sketch<false>, dim3((unsigned)tS[k]), dim3(256), 0, st, dblk + (size_t)(k - 1) * m, m, n, l0, l1, (const double *)(Om + ooff[k - 1]),
+                               (const double *)(W + woff[k]), (int)S[k], W + woff[k - 1], (int)S[k - 1]);
+        hipLaunchKernelGGL(k_rs_scale, dim3(1), dim3(1024), 0, st, (size_t)S[k - 1] * l0, W + woff[k - 1]);
+    }
+    if ((rc = tm.stop(st))) return rc;
+    // left to right
+    const TtScratch s(e);
+    RsMarks marks(h->rs_ev);
+    HIPCHECK(hipMemcpyAsync(M, coef, sizeof(double) * m, hipMemcpyHostToDevice, st));
+    if ((rc = marks.mark(st, 0))) return rc;
+    auto advance = [&](int k, int lr, int ldm, double *dst) {                   // Y(k) from M (lr rows) and the cores k
+        const int n = h->n1[k];
+        if (eff == TTX_EVAL_MFMA)
+            hipLaunchKernelGGL(k_rs_advance<true>, dim3((unsigned)tA[k]), dim3(256), 0, st, dblk + (size_t)(k - 1) * m, m, n, lr, (lr + 15) / 16, (const double *)M, ldm, dst, (size_t)lr * n);
+        else
+            hipLaunchKernelGGL(k_rs_advance<false>, dim3((unsigned)tA[k]), dim3(256), 0, st, dblk + (size_t)(k - 1) * m, m, n, lr, (lr + 15) / 16, (const double *)M, ldm, dst, (size_t)lr * n);
+        return marks.mark(st, 3);
+    };
+    if ((rc = advance(1, 1, 1, Y))) return rc;
+    for (int k = 1; k < d; k++) {
+        const int rows = l[k - 1] * h->n1[k], l1 = l[k], Sk = (int)S[k];
+        gemm(e, rows, l1, Sk, Y, rows, W + woff[k], Sk, e->Wa, rows);                       // Z = Y(k) W(k)
+        if ((rc = marks.mark(st, 1)) || (rc = qr(e, rows, l1, e->Wa, s.Rm, s.tau))) return rc;
+        unpack_core(e, k, e->Wa, l[k - 1], l1);                                             // new core k = Q
+        hipLaunchKernelGGL(k_transpose, g1((size_t)rows * l1), dim3(256), 0, st, rows, l1, (const double *)e->Wa, e->Wb);
+        if ((rc = marks.mark(st, 2))) return rc;
+        gemm(e, l1, Sk, rows, e->Wb, l1, Y, rows, M, l1);                                   // M = Q^T Y(k)
+        if ((rc = marks.mark(st, 1)) || (rc = advance(k + 1, l1, l1, Yn))) return rc;
+        std::swap(Y, Yn);
+    }
+    const int lr = l[d - 1], nd = h->n1[d];
+    hipLaunchKernelGGL(k_rs_last, g1((size_t)lr * nd), dim3(256), 0, st, lr, nd, m, (const double *)Y, (size_t)lr * nd, core_dev(e, d), e->RM);
+    if ((rc = marks.mark(st, 3))) return rc;
+    HIPCHECK(hipStreamSynchronize(st));
+    HIPCHECK(hipGetLastError());
+    if ((rc = tm.ms(&h->rs_ms[0])) || (rc = marks.sum(h->rs_ms))) return rc;
+    if (tol >= 0.0 && (rc = svd_impl(e, tol, rmax))) return rc;
+    HIPCHECK(hipStreamSynchronize(st));
+    return TTX_OK;
+}
+extern "C" int ttx_lincomb_round(int32_t m, const double *coef, ttx_engine *const *x, int32_t rsketch, double tol, int32_t rmax, uint64_t seed, int32_t mode,
+                                 ttx_engine **out)
+{
+    if (out) *out = nullptr;
+    if (!coef || !x || !out) return fail(TTX_EINVAL, "ttx_lincomb_round: null argument");
+    if (m < 1) return fail(TTX_EINVAL, "ttx_lincomb_round: %d terms (at least one expected)", m);
+    if (m > TTX_RS_MAXTERMS) return fail(TTX_EINVAL, "ttx_lincomb_round: %d terms, at most %d are taken", m, TTX_RS_MAXTERMS);
+    if (rsketch < 0 || rsketch > 128) return fail(TTX_EINVAL, "ttx_lincomb_round: sketch rank %d (0 = 128, or 1 .. 128: the engine holds ranks up to 128)", rsketch);
+    if (rmax < 0) return fail(TTX_EINVAL, "ttx_lincomb_round: rmax must be >= 0 (0: absent; got %d)", (int)rmax);
+    if (tol != tol) return fail(TTX_EINVAL, "ttx_lincomb_round: tol is not a number (tol < 0 skips the truncation)");
+    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "ttx_lincomb_round: unknown mode %d", mode);
+    int rc = alg_check("ttx_lincomb_round", m, x);
+    if (rc) return rc;
+    ttx_engine *h = x[0];
+    const int d = h->d;
+    std::vector<int32_t> nn = modes_of(h), ll(d + 1, 1);
+    std::vector<long long> S(d + 1, m);
+    for (int k = 1; k < d; k++) {
+        S[k] = 0;
+        for (int t = 0; t < m; t++) S[k] += x[t]->rfinal[k];
+        if (S[k] > TTX_RS_MAXSUM) return fail(TTX_EINVAL, "ttx_lincomb_round: the ranks at bond %d add up to %lld, at most %d are taken", k, S[k], TTX_RS_MAXSUM);
+    }
+    rs_sketch_ranks(d, nn.data(), S.data(), rsketch ? rsketch : 128, ll.data());
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    return new_train(out, "ttx_lincomb_round", d, nn.data(), ll.data(), h->cfg.device,
+                     [&](ttx_engine *e) { return rs_fill(m, coef, x, e, S, ll.data(), tol, rmax, (unsigned long long)seed, mode); });
+}
+extern "C" int ttx_roundsum_last(const ttx_engine *h, double *ms, double *flops, int32_t *lsk, int32_t *mode_ran)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_roundsum_last: null engine");
+    if (ms) for (int p = 0; p < 4; p++) ms[p] = h->rs_ms[p];
+    if (flops) *flops = h->rs_flops;
+    if (lsk) for (int k = 0; k <= h->d; k++) lsk[k] = k < (int)h->rs_l.size() ? h->rs_l[k] : 0;
+    if (mode_ran) *mode_ran = h->rs_mode;
     return TTX_OK;
 }
 

@@ -7,8 +7,9 @@ runs on the GPU through ttcross_amd.engine.  Usage:
     python -m ttcross_amd.drivers mvn D N RANK PIV [NGROUPS]
     python -m ttcross_amd.drivers coscoeff D N RANK PIV [NGROUPS]
     python -m ttcross_amd.drivers devfun D N RANK PIV [NGROUPS] [device|host|wave] [SOURCE.hip NAME]
-    python -m ttcross_amd.drivers tijk WORKLOAD NPTS MODE      (batched element evaluation: c64 | d64 | rand256 | a file of dtt_write)
+    python -m ttcross_amd.drivers tijk WORKLOAD NPTS MODE      (batched element evaluation: c64 | d64 | rand256 | r16d64 | a file of dtt_write)
     python -m ttcross_amd.drivers algebra WORKLOAD [REPS]      (x + x, x - x, x o w, x o x, dist on the device and by the host route)
+    python -m ttcross_amd.drivers roundsum WORKLOAD M [RANK] [MODE] (rounded sum of M terms made from the workload's train: lincomb_round)
     python -m ttcross_amd.drivers compose WORKLOAD OP [MAXRANK] (cross approximation of product | ratio | sqrtabs of the workload's train)
 
 devfun: the rational example integrand (examples/devfun/rational.hip) as a LOADED device integrand (TTX_FUN_DEVICE), in its
@@ -275,12 +276,17 @@ TIJK_WORKLOADS = {"c64": ("c", 64, 51, 32, 2), "d64": ("d", 64, 51, 32, 2), "c8"
 def tijk_train(workload, device=0):
     """The train of a tijk measurement: the result of an Ising sweep (c64, d64, c8: 8 bond groups as the benchmark runs them
     where the train is long enough), a random train of the D_256 shape (rand256: d = 255, n = 101, r = 64, entries scaled so
-    that elements stay of order one) or a file written by dtt_write."""
+    that elements stay of order one), a random rank-16 train of the D_64 shape (r16d64) or a file written by dtt_write."""
     if workload in TIJK_WORKLOADS:
         kind, m, n, r, piv = TIJK_WORKLOADS[workload]
         s = ising_setup(kind, m, n)
         return TTCross(s["n"], s["fun_id"], s["par"], r, pivoting=piv, accuracy=s["acc"], quad=s["quad"], tru=s["tru"],
                        nproc=8 if m >= 32 else 1, device=device).run()
+    if workload == "r16d64":                               # standard normal cores of rank 16 in the D_64 shape, elements of order one
+        rng = np.random.default_rng(1)
+        d, n, r = 63, 51, 16
+        return TTCross.from_cores([rng.standard_normal(((1 if k == 0 else r), n, (1 if k == d - 1 else r))) / np.sqrt(n * r) * 2.0 for k in range(d)],
+                                  device=device)
     if workload.startswith("rand"):
         d = int(workload[4:]) - 1
         rng = np.random.default_rng(256)
@@ -792,8 +798,90 @@ def run_topk(argv, device=0, repeats=5, tt=None, host_kmax=4096):
     return out
 
 
+def roundsum_terms(tt, m):
+    """m terms from one train: the train itself, then its cyclic shifts by t along mode 1 + (t mod d) (mode_apply with a permutation
+    matrix in "exact" mode: the cores are copies), with the coefficients 2^-t"""
+    terms, coefs = [tt], [1.0]
+    for t in range(1, m):
+        k = t % tt.d
+        n = int(tt._n[k])
+        P = np.roll(np.eye(n), (t // tt.d + 1) % n, axis=0)
+        terms.append(tt.mode_apply({k + 1: P}, "exact"))
+        coefs.append(2.0 ** -t)
+    return coefs, terms
+
+
+def roundsum_tree(coefs, terms, rank):
+    """what the library could do before lincomb_round: a pairwise tree of lincomb, each result rounded to `rank` by svd(0, rank);
+    None where a pair's ranks add up to more than 128"""
+    level = [TTCross.lincomb([c], [x]) for c, x in zip(coefs, terms)]
+    while len(level) > 1:
+        if any(int((level[j].ranks() + level[j + 1].ranks())[1:-1].max()) > 128 for j in range(0, len(level) - 1, 2)):
+            for x in level:
+                x.close()
+            return None
+        nxt = []
+        for j in range(0, len(level) - 1, 2):
+            s = TTCross.lincomb([1.0, 1.0], [level[j], level[j + 1]])
+            s.svd(0.0, rank)
+            nxt.append(s)
+            level[j].close()
+            level[j + 1].close()
+        if len(level) % 2:
+            nxt.append(level[-1])
+        level = nxt
+    return level[0]
+
+
+def run_roundsum(argv, device=0, repeats=5, tt=None, tree=True):
+    """roundsum WORKLOAD M [RANK] [MODE]: M terms from the workload's train (roundsum_terms; a train of the tijk sub-command),
+    lincomb_round at sketch rank RANK (default 64) without truncation: one warm-up and `repeats` calls -- the ranks, the median of
+    the call and of the four times of ttx_roundsum_last, the achieved fp64 rate of the products; dist to the exact lincomb where
+    its ranks fit 128, relative to its norm; the pairwise lincomb + svd tree at the same rank where it fits (tree=False: left out; it takes seconds to minutes).  One JSON line."""
+    import json
+    import time
+    workload, m = argv[0], int(argv[1])
+    rank = int(argv[2]) if len(argv) > 2 else 64
+    mode = argv[3] if len(argv) > 3 else "auto"
+    tt = tt or tijk_train(workload, device=device)
+    coefs, terms = roundsum_terms(tt, m)
+    TTCross.lincomb_round(coefs, terms, rank=rank, mode=mode).close()
+    ms, last = [], []
+    for rep in range(repeats):
+        t0 = time.perf_counter()
+        res = TTCross.lincomb_round(coefs, terms, rank=rank, mode=mode)        # synchronises before it returns
+        ms.append((time.perf_counter() - t0) * 1e3)
+        last.append(tt.roundsum_last())
+        if rep < repeats - 1:
+            res.close()
+    med = {key: float(np.median([x[key] for x in last])) for key in ("ms_sketch", "ms_gemm", "ms_qr", "ms_advance")}
+    prod = med["ms_sketch"] + med["ms_gemm"] + med["ms_advance"]
+    r = dict(workload=workload, m=m, rank=rank, mode_asked=mode, mode=last[-1]["mode"], d=tt.d, term_max_rank=int(tt.ranks().max()),
+             rank_sum=int(sum(int(x.ranks().max()) for x in terms)), ranks_max=int(res.ranks().max()), call_ms=float(np.median(ms)),
+             call_ms_min=float(min(ms)), call_ms_max=float(max(ms)), flops=last[-1]["flops"],
+             product_flops_per_s=last[-1]["flops"] / (prod * 1e-3) if prod > 0 else None, **med)
+    if r["rank_sum"] + r["ranks_max"] <= 128:                                   # dist is a lincomb of the two itself
+        full = TTCross.lincomb(coefs, terms)
+        r["dist_over_norm"] = res.dist(full) / full.norm()
+        full.close()
+    t0 = time.perf_counter()
+    tree = roundsum_tree(coefs, terms, rank) if tree else None
+    if tree is not None:
+        r["tree_ms"] = (time.perf_counter() - t0) * 1e3
+        if int((res.ranks() + tree.ranks()).max()) <= 128:
+            r["tree_dist_over_norm"] = res.dist(tree) / tree.norm()
+        tree.close()
+    res.close()
+    for x in terms[1:]:
+        x.close()
+    print(json.dumps(r), flush=True)
+    return r
+
+
 if __name__ == "__main__":
-    if sys.argv[1] == "tijk":
+    if sys.argv[1] == "roundsum":
+        run_roundsum(sys.argv[2:])
+    elif sys.argv[1] == "tijk":
         run_tijk(sys.argv[2:])
     elif sys.argv[1] == "compose":
         run_compose(sys.argv[2:])

@@ -110,6 +110,8 @@ def load_library():
     L.ttx_lincomb.argtypes = [c_int32, POINTER(c_double), POINTER(c_void_p), POINTER(c_void_p)]
     L.ttx_hadamard.argtypes = [c_void_p, c_void_p, POINTER(c_void_p)]
     L.ttx_algebra_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double)]
+    L.ttx_lincomb_round.argtypes = [c_int32, POINTER(c_double), POINTER(c_void_p), c_int32, c_double, c_int32, ctypes.c_uint64, c_int32, POINTER(c_void_p)]
+    L.ttx_roundsum_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_int32)]
     L.ttx_mode_apply.argtypes = [c_void_p, POINTER(c_int32), POINTER(c_double), c_int32, POINTER(c_void_p)]
     L.ttx_mode_apply_dev.argtypes = [c_void_p, POINTER(c_int32), c_void_p, c_int32, POINTER(c_void_p)]
     L.ttx_mode_apply_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
@@ -198,6 +200,24 @@ def _eval_mode(mode):
     if mode in EVAL_MODES.values():
         return int(mode)
     raise ValueError(f"mode must be one of {sorted(EVAL_MODES)} (got {mode!r})")
+
+
+def roundsum_omega(seed, k, shape):
+    """Core k (1-based) of the sketch train of lincomb_round, shape (l(k-1), n_k, l(k)), restated in numpy uint64 arithmetic
+    (include/ttx.h: ttx_lincomb_round, step 2): bit for bit what the device generates.  Entry x = a + l(k-1) (i + n_k b):
+    z = seed + 0x9E3779B97F4A7C15 ((k << 40) + x + 1), the splitmix64 finaliser, then sign = bit 63, magnitude = the next 52 bits
+    times 2^-52: uniform on (-1, 1), every step exact."""
+    shape = tuple(int(s) for s in shape)
+    cnt = int(np.prod(shape))
+    with np.errstate(over="ignore"):
+        x = np.arange(cnt, dtype=np.uint64)
+        z = np.uint64(int(seed) & (2 ** 64 - 1)) + np.uint64(0x9E3779B97F4A7C15) * (np.uint64(int(k) << 40) + x + np.uint64(1))
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    mag = ((z >> np.uint64(11)) & np.uint64(2 ** 52 - 1)).astype(np.float64) * 2.0 ** -52
+    v = np.where((z >> np.uint64(63)) != 0, -mag, mag)
+    return v.reshape(shape, order="F")
 
 
 def value_indices(n, x):
@@ -705,6 +725,34 @@ class TTCross:
         ms, rd, wr = c_double(), c_double(), c_double()
         _check(load_library().ttx_algebra_last(self._h, ctypes.byref(ms), ctypes.byref(rd), ctypes.byref(wr)))
         return ms.value, rd.value, wr.value
+
+    # ---- a rounded sum of resident trains (include/ttx.h: ttx_lincomb_round) -----------------------------
+    @staticmethod
+    def lincomb_round(coefs, trains, rank=0, tol=-1.0, rmax=0, seed=0, mode="auto"):
+        """sum_t coefs[t] * trains[t] rounded on the device by a randomized sketch of rank `rank` (0: 128), as a new engine on
+        the same device (include/ttx.h: ttx_lincomb_round): no core of rank sum_t r_t is ever formed, so sums far beyond the
+        engine's rank cap of 128 are taken (up to 256 terms, rank sums up to 4096).  tol < 0 returns the left-orthogonal train
+        with the sketch ranks, tol >= 0 truncates it as svd(tol, rmax) does.  The same train may appear several times; a call
+        with the same seed repeats bit for bit.  mode: "exact", "mfma" or "auto"; trains[0].roundsum_last() tells what ran."""
+        trains = list(trains)
+        c = np.ascontiguousarray(np.asarray(coefs, dtype=np.float64).ravel())
+        if not trains or c.size != len(trains):
+            raise ValueError(f"lincomb_round: one coefficient per train expected (got {c.size} and {len(trains)})")
+        md = _eval_mode(mode)
+        hs = (c_void_p * len(trains))(*[t._h for t in trains])
+        h = c_void_p()
+        _check(load_library().ttx_lincomb_round(len(trains), _dp(c), hs, int(rank), float(tol), int(rmax), int(seed) & (2 ** 64 - 1), md, ctypes.byref(h)))
+        return TTCross._adopt(h, trains[0].device)
+
+    def roundsum_last(self):
+        """dict(ms_sketch, ms_gemm, ms_qr, ms_advance, flops, l, mode) of the last lincomb_round that had this engine as its first
+        operand (include/ttx.h: ttx_roundsum_last): l are the sketch ranks l(0 .. d), mode is "exact" or "mfma" (None before the
+        first call)"""
+        ms, fl, md = (c_double * 4)(), c_double(), c_int32()
+        l = np.zeros(self.d + 1, dtype=np.int32)
+        _check(load_library().ttx_roundsum_last(self._h, ms, ctypes.byref(fl), _ip(l), ctypes.byref(md)))
+        names = {v: k for k, v in EVAL_MODES.items()}
+        return dict(ms_sketch=ms[0], ms_gemm=ms[1], ms_qr=ms[2], ms_advance=ms[3], flops=fl.value, l=[int(v) for v in l], mode=names.get(md.value))
 
     # ---- matrices applied to chosen modes (include/ttx.h: ttx_mode_apply) --------------------------------
     def mode_apply(self, mats, mode="auto"):

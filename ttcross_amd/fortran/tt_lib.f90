@@ -77,6 +77,8 @@ module tt_lib
  ! axpby(alpha,x,beta,y) = alpha*x + beta*y, hadamard(x,y) = x(i)*y(i).  Both return a dtt that holds the new train on the device
  ! and, pulled, in %u; the variable the result is assigned to takes the device train over (dtt_assign)
  interface axpby;       module procedure dtt_axpby;    end interface
+ ! roundsum(c,x,res,rank,tol,rmax,seed): res = sum_t c(t) x(t) rounded on the device by a randomized sketch (ttx_lincomb_round)
+ interface roundsum;    module procedure dtt_roundsum; end interface
  interface hadamard;    module procedure dtt_hadamard; end interface
  type(c_ptr),private,save :: tt_pending=c_null_ptr      ! the device train of the last axpby / hadamard result, until it is assigned
 contains
@@ -108,6 +110,40 @@ contains
   if(ty)call ttx_destroy(hs(2))
   call dtt_result(c,hn,x)
  end function
+ subroutine dtt_roundsum(c,x,res,rank,tol,rmax,seed)
+  ! res = sum_t c(t) x(t), rounded on the device in one call (ttx_lincomb_round): no core of rank sum_t r_t is formed, so the sum may
+  ! go far beyond the rank 128 that axpby and + stop at.  rank: the sketch rank (absent or 0: 128); tol: absent or negative keeps the
+  ! left-orthogonal train with the sketch ranks, tol >= 0 truncates it as svd(res,tol,rmax) does; seed: the sketch's (default 0).
+  ! Host trains are staged for the call like for axpby.  res holds the new train on the device and, pulled, in res%u.
+  use ttx_c
+  double precision,intent(in) :: c(:)
+  type(dtt),intent(in) :: x(:)
+  type(dtt),intent(inout) :: res
+  integer,intent(in),optional :: rank,rmax,seed
+  double precision,intent(in),optional :: tol
+  type(c_ptr),allocatable :: hs(:)
+  logical,allocatable :: tmp(:)
+  real(c_double),allocatable :: cf(:)
+  type(c_ptr) :: hn
+  integer(c_int32_t) :: rk,rm
+  integer(c_int64_t) :: sd
+  real(c_double) :: tl
+  integer :: t,m
+  m=size(x)
+  if(m.lt.1 .or. size(c).ne.m)then;write(*,*)'dtt_roundsum: one coefficient per train expected; got ',size(c),m;stop;endif
+  call dtt_dealloc(res)
+  rk=0; if(present(rank))rk=rank
+  rm=0; if(present(rmax))rm=rmax
+  sd=0; if(present(seed))sd=seed
+  tl=-1.d0; if(present(tol))tl=tol
+  allocate(hs(m),tmp(m),cf(m)); cf=c
+  do t=1,m; call dtt_stage(x(t),hs(t),tmp(t),'dtt_roundsum'); end do
+  hn=c_null_ptr
+  call ttx_check(ttx_lincomb_round(int(m,c_int32_t),cf,hs,rk,tl,rm,sd,2_c_int32_t,hn),'dtt_roundsum')
+  do t=1,m; if(tmp(t))call ttx_destroy(hs(t)); end do
+  res%l=1; res%m=x(1)%m; res%n(1:res%m)=x(1)%n(1:res%m)
+  res%ttx=hn; call dtt_pull(res)
+ end subroutine
  function dtt_hadamard(x,y) result(c)
   ! c(i) = x(i)*y(i) in one call on the device (ttx_hadamard): ranks multiply, the index of x runs fastest on both bonds
   use ttx_c

@@ -149,6 +149,11 @@ module ttx_c
   function ttx_algebra_last(h,ms,bytes_read,bytes_written) bind(C,name='ttx_algebra_last') result(rc)
    import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms,bytes_read,bytes_written; integer(c_int) :: rc
   end function
+  ! a rounded sum of resident trains (include/ttx.h): rsketch 0 = 128, tol < 0 = no truncation, rmax 0 = absent, mode 0 / 1 / 2
+  function ttx_lincomb_round(m,coef,x,rsketch,tol,rmax,seed,mode,out) bind(C,name='ttx_lincomb_round') result(rc)
+   import; integer(c_int32_t),value :: m,rsketch,rmax,mode; real(c_double),intent(in) :: coef(*); type(c_ptr),intent(in) :: x(*)
+   real(c_double),value :: tol; integer(c_int64_t),value :: seed; type(c_ptr) :: out; integer(c_int) :: rc
+  end function
   ! matrices applied to chosen modes (include/ttx.h): a = the column-major blocks m(k) x n(k) of the applied modes, one after the other
   function ttx_mode_apply(h,m,a,mode,out) bind(C,name='ttx_mode_apply') result(rc)
    import; type(c_ptr),value :: h; integer(c_int32_t),intent(in) :: m(*); real(c_double),intent(in) :: a(*); integer(c_int32_t),value :: mode
