@@ -3,7 +3,9 @@ launches it replaces (k_exch_max_apply, k_exch_boundary, k_sweep_end; TTX_TAIL=0
 fresh child processes (tests/sweep_tail_worker.py), everything a run leaves compared BYTE FOR BYTE -- all cores, ranks, the per-sweep
 records (val, erank, neval, amax, pivotmax, pivotmin), tapes, the evaluation count and the integral.  TTX_TAIL=1 runs twice: with
 the summary on the quadrature's stream and the stopping rule at the sweep kernel's entry (the default), and with k_sweep_end on
-the main stream behind the one exchange launch (TTX_TAIL_SIDE=0)."""
+the main stream behind the one exchange launch (TTX_TAIL_SIDE=0).
+The forms of the sweep loop (ttx_loop_plan.h) against each other in the same way: the host-synchronised loop of one process
+(TTX_PIPELINE=0) against the pipelined one, the tail without a quadrature, and what each form launches per kind."""
 import os
 import subprocess
 import sys
@@ -20,11 +22,12 @@ WORKER = os.path.join(ROOT, "tests", "sweep_tail_worker.py")
 SWITCHES = ("TTX_TAIL", "TTX_TAIL_SIDE", "TTX_SWEEP", "TTX_ARITH", "TTX_PIPELINE", "TTX_CLUSTER_TEST_ABORT", "TTX_CLUSTER_COOP", "TTX_CLUSTER_NB", "TTX_CL_PAD")
 
 
-def _worker(tmp_path, tag, tail, m, n, r, piv, groups, acc="default", runs=1, arith="exact", env=None):
+def _worker(tmp_path, tag, tail, m, n, r, piv, groups, acc="default", runs=1, arith="exact", env=None, noquad=False):
+    """tail: the value of TTX_TAIL, or None to leave it unset"""
     out = str(tmp_path / f"{tag}_tail{tail}.npz")
     e = {k: v for k, v in os.environ.items() if k not in SWITCHES}
-    e.update({"TTX_TAIL": str(tail)}, **(env or {}))
-    p = subprocess.run([sys.executable, WORKER, out] + [str(x) for x in (m, n, r, piv, groups, acc, runs, arith)],
+    e.update({} if tail is None else {"TTX_TAIL": str(tail)}, **(env or {}))
+    p = subprocess.run([sys.executable, WORKER, out] + [str(x) for x in (m, n, r, piv, groups, acc, runs, arith)] + ["noquad"] * noquad,
                        capture_output=True, text=True, env=e, timeout=300)
     assert p.returncode == 0 and "WORKER OK" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
     return dict(np.load(out))
@@ -127,3 +130,57 @@ def test_abort_replay(tmp_path):
     assert new["path_before"][0] == "cluster" and new["path_after"][0] == "chain" and int(new["cluster_fallbacks"][0]) == 1
     assert int(old["cluster_fallbacks"][0]) == 0
     _same_bytes(old, new)
+
+
+C8 = (8, 25, 12, 2)     # Ising C_8, n = 25, r = 12, piv = 2: the shape of the loop-form tests below
+
+
+@pytest.mark.parametrize("groups,sweep", [(3, "cluster"), (1, "cluster"), (3, "fused")])
+def test_host_synchronised_loop_of_one_process(tmp_path, groups, sweep):
+    """TTX_PIPELINE=0 with one process on a whole-sweep path: the plain loop, one launch of the sweep kernel and one readback per
+    sweep, gives what the pipelined loop gives, and the cluster kernel's barriers hold (no fallback)."""
+    env = {} if sweep == "cluster" else {"TTX_SWEEP": sweep}
+    pipe = _worker(tmp_path, f"c8_{sweep}_g{groups}_pipe", None, *C8, groups, env=env)
+    host = _worker(tmp_path, f"c8_{sweep}_g{groups}_host", None, *C8, groups, env=dict(env, TTX_PIPELINE="0"))
+    for x in (pipe, host):
+        assert x["path_before"][0] == x["path_after"][0] == sweep and int(x["cluster_fallbacks"][0]) == 0
+    _same_bytes(pipe, host)
+
+
+def test_tail_without_a_quadrature(tmp_path):
+    """no quadrature weights: the one-launch tail with k_sweep_end behind it and nothing forked, against the launches it replaces"""
+    old, new = (_worker(tmp_path, "c8_noquad", t, *C8, 3, noquad=True) for t in (0, 1))
+    assert old["path_after"][0] == new["path_after"][0] == "cluster"
+    _same_bytes(old, new)
+
+
+@pytest.mark.parametrize("case,groups,env,acc,pipelined,tail", [
+    ("default", 3, {}, "default", True, True),
+    ("tail_on_the_main_stream", 3, {"TTX_TAIL_SIDE": "0"}, "default", True, True),
+    ("no_tail", 3, {"TTX_TAIL": "0"}, "default", True, False),
+    ("one_group", 1, {}, "default", True, False),
+    ("fused", 3, {"TTX_SWEEP": "fused"}, "default", True, False),
+    ("host_synchronised", 3, {"TTX_PIPELINE": "0"}, "default", False, False),
+    ("three_strikes", 3, {}, 1e-3, True, True),
+    ("rule_off", 3, {}, -1.0, True, True),
+])
+def test_launch_counts_per_kind(tmp_path, case, groups, env, acc, pipelined, tail):
+    """What a whole-sweep run launches per kind, in closed form from the brackets of the driver as it stood before the loop plan
+    (S sweeps, R = maxrank, G groups): 4 launches of the initial cross and 2 of the finalisation; one sweep kernel per sweep, plus
+    the speculative one of the pipelined loop unless the last sweep was R - 1; the end of a sweep as one exchange launch with the
+    tail, else max-apply and (cluster: packed by the sweep kernel) pack or boundary -- 2, and the boundary launch on top with
+    neighbours; the quadrature as build and chain, and the tree with several groups.  So the switch a case sets selects the form
+    that runs."""
+    R, G = C8[2], groups
+    x = _worker(tmp_path, "c8_" + case, None, *C8, groups, acc=acc, env=env)
+    S = int(x["nsweeps"][0]) - 1
+    assert 1 <= S <= R - 1 and x["path_after"][0] == env.get("TTX_SWEEP", "cluster")
+    if case == "three_strikes":
+        assert S < R - 1
+    if case == "rule_off":
+        assert S == R - 1
+    got = {k[len("launches_"):]: int(v[0]) for k, v in x.items() if k.startswith("launches_")}
+    assert got == {"lottery": 0, "accept": 0, "other": 6,
+                   "halfstep": S + (1 if S < R - 1 else 0) if pipelined else S,
+                   "exchange": S if tail else S * (2 + (1 if G > 1 else 0)),
+                   "quad": S * (3 if G > 1 else 2)}

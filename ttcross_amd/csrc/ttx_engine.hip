@@ -29,6 +29,7 @@
 #include "ttx_lds.h"
 #include "ttx_qr_plan.h"
 #include "ttx_create_plan.h"
+#include "ttx_loop_plan.h"
 #include "ttx_shm.h"
 #include "ttx_host_pool.h"
 #include "ttx_files.h"
@@ -1279,315 +1280,10 @@ static ChainPlan chain_plan(const ttx_engine *h)
 #undef KUNIT_
 #undef KUNIT2_
 
-// the whole-sweep cluster kernel: cooperative launch (the runtime guarantees -- or refuses -- co-residency of the grid)
-static int launch_cluster(ttx_engine *h, int dir, int epoch)
+#ifdef TTX_STAMPS   // debug build, after a run: the cycle stamps the kernels left
+static int dump_stamps(ttx_engine *h)
 {
-    DevProb P = h->P;
-    const CreatePlan &s = h->sel;
-    int nsteps = h->nbmax, NB = s.cluster, ldsinv = s.cluster_ldsinv, zkeep = s.cluster_zkeep;
-    const dim3 grid(8 * NB * ((h->G + 7) / 8)), block(CB);
-    if (s.cluster_coop) {
-        void *args[] = {&P, &dir, &nsteps, &NB, &ldsinv, &epoch, &zkeep};
-        HIPCHECK(hipLaunchCooperativeKernel(reinterpret_cast<const void *>(cluster_kernel(s.cluster_var)), grid, block, args, (unsigned)s.lds_cluster, h->stream));
-    } else
-        hipLaunchKernelGGL(cluster_kernel(s.cluster_var), grid, block, s.lds_cluster, h->stream, P, dir, nsteps, NB, ldsinv, epoch, zkeep);
-    return TTX_OK;
-}
-
-template <int FUN>
-static int run_impl(ttx_engine *h)
-{
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
-    auto since = [&]() { return std::chrono::duration<double>(clk::now() - t0).count(); };
-    DevProb &P = h->P;
-    const int d = h->d, G = h->G, nproc = h->cfg.nproc;
-    const int cluster = h->cluster_nb(), fused = h->sel.fused;      // the whole-sweep kernel this run uses, if any
-    const size_t lds_fused = h->sel.lds_fused;
-    hipStream_t st = h->stream;
-    h->recs.clear(); h->tapes.clear();
-    int rc;
-    const bool pipe = (cluster || fused) && !h->profile && !env_off("TTX_PIPELINE");      // the pipelined loop (below, at the main loop)
-    const bool forkq = pipe && P.has_quad && h->W == 1;
-    // The end of a sweep as ONE exchange launch (k_exch_tail): single process, pipelined loop, cluster path, device integrand, at least
-    // two groups (one group has no neighbour, its boundary launch never existed).  With the forked quadrature its summary
-    // (k_sweep_summary) goes to the quadrature's stream as well, and every block of the next sweep kernel applies the stopping rule
-    // itself (`side`, DevProb::tail_side); else k_sweep_end follows on the main stream.  Everything else -- the chain path,
-    // k_sweep_fused, several processes, TTX_PIPELINE=0, profile mode, TTX_TAIL=0 -- keeps the launches it had.
-    const bool tail = pipe && cluster && h->W == 1 && nproc > 1 && FUN != FUN_HOST && h->sel.sweep_tail;
-    const bool side = tail && forkq && h->sel.sweep_tail_side;
-    P.tail_side = side ? 1 : 0;
-
-    // what this run launches on the chain path; its kernels, and the whole-sweep kernel where one is used, may stage more than the
-    // default 64 KB of dynamic LDS (160 KB per CU on gfx950)
-    const ChainPlan plan = chain_plan<FUN>(h);
-    for (const KLaunch *k : plan.all()) if (k->raise && (rc = ensure_lds(h, k->fn, k->lds))) return rc;
-    if (fused && (rc = ensure_lds(h, reinterpret_cast<const void *>(k_sweep_fused), lds_fused))) return rc;
-    if (cluster && (rc = ensure_lds_cluster(h))) return rc;
-    if (cluster) *h->h_abort = 0;
-    // an evaluating kernel: once with the device integrand; with a host integrand twice around the host's calls
-    auto EV = [&](const KLaunch &k, auto... a) -> int {
-        if (FUN != FUN_HOST) { launch(st, k, P, a...); return TTX_OK; }
-        DevProb Q = P;
-        Q.hostpass = 1; launch(st, k, Q, a...);
-        if (int rc_ = slot_eval(h)) return rc_;
-        Q.hostpass = 2; launch(st, k, Q, a...);
-        return TTX_OK;
-    };
-    // ---- reset state (lib/dmrgg.f90:96-100, 141-148, 279-288) ----
-    hipLaunchKernelGGL(k_reset, dim3(64), dim3(256), 0, st, P, h->SB, h->QB);
-    // ---- initial cross (:151-301) ----
-    const int snum = h->sel.snum, nn = h->sel.nn;
-    {
-        KScope ks(h, TTX_K_OTHER, 4);
-        if ((rc = EV(plan.init_samples, snum, nn, FUN == FUN_HOST ? 0 : plan.srows, 0))) return rc;
-        if ((rc = EV(plan.init_fibers))) return rc;
-        hipLaunchKernelGGL(k_init_factors, dim3(h->NC, G), dim3(256), lds_fpersist(P), st, P);
-        hipLaunchKernelGGL(k_init_final, dim3(G), dim3(256), 0, st, P);
-    }
-    // Single-process whole-sweep path: the first sweep kernel is enqueued right behind the initial cross, and the host
-    // waits only for the copy of the initial summary (an event), not for the stream.
-    const bool pipe0 = (cluster || fused) && h->W == 1 && !h->profile;
-    bool head1 = false;
-    if (pipe0) {
-        hipLaunchKernelGGL(k_collect, dim3(1), dim3(256), 0, st, P);
-        h->h_sum = h->h_sum_base;
-        HIPCHECK(hipMemcpyAsync(h->h_sum, P.sumrecv, sizeof(double) * h->SB, hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipEventRecord(h->ev_sum[0], st));
-        if (1 < h->cfg.maxrank) {
-            if (cluster) { if ((rc = launch_cluster(h, 1, 1))) return rc; }
-            else hipLaunchKernelGGL(k_sweep_fused, dim3(G), dim3(FB), lds_fused, st, P, 1, h->nbmax);
-            h->k_launches[TTX_K_HALFSTEP] += 1;
-            head1 = true;
-        }
-        HIPCHECK(hipEventSynchronize(h->ev_sum[0]));
-    } else if ((rc = readback(h))) return rc;
-    HIPCHECK(hipGetLastError());
-    double val = 1.0, val_prev = 1.0;
-    for (int g = 0; g < nproc; g++) val = (g == 0) ? h->h_sum[SUM_HDR + g] : val * h->h_sum[SUM_HDR + g];   // :259-267 PROD
-    if (!P.has_quad) val = 0.0;
-    val_prev = val;
-    {
-        ttx_sweep_rec r{};
-        r.it = 0; r.dir = 0; r.erank = erank_host(h, rank0_view(h, 0).data()); r.neval = (int64_t)h->h_sum[SUM_NEVAL]; r.val = val;
-        r.amax = h->h_sum[SUM_AMAX]; r.pivotmax = -1; r.pivotmin = -1; r.seconds = since();
-        h->recs.push_back(r);
-        if (h->cfg.verbose) print_line(h, r, val_prev);
-    }
-
-    // ---- main loop (:309-1020) ----
-    int it = 0, strike = 0;
-    bool ready = (it + 1 >= h->cfg.maxrank);
-    // Pipelined mode (whole-sweep kernels, one process): the stopping rule also runs on the device (k_sweep_end), so
-    // sweep it+1 is enqueued BEFORE the host has read the summary of sweep it -- the GPU never waits for the host.  When the rule fires, the one sweep that is already enqueued finds the stop flag and does nothing.
-    // On a single GPU the per-sweep quadrature (only reported, never fed back) runs on its own stream next to the
-    // following sweep: it reads a snapshot of the ranks and only slabs that already exist (appends are in place).
-    // With several processes the exchange and the summary travel by stream-ordered collectives (RCCL, or the host transport's
-    // host functions), so the same loop applies; only the fork of the quadrature is single-process (one communicator must
-    // not be driven from two streams at once).
-    // (pipe, forkq, tail and side are decided at the top: the first sweep kernel, already enqueued, runs with the same DevProb)
-    DevProb Pq = P;
-    if (pipe) Pq.r = P.rq;
-
-    // part 1: the sweep over the own bonds; part 2: exchange, end-of-sweep work, quadrature; 3: both
-    auto enqueue_sweep = [&](int it_, int part) -> int {
-        const int dir = 2 - it_ % 2, slot = it_ & 1;
-        if (part & 1) {
-        if (cluster) {
-            KScope ks(h, TTX_K_HALFSTEP, 1);
-            if (int rc_ = launch_cluster(h, dir, it_)) return rc_;
-        } else if (fused) {
-            KScope ks(h, TTX_K_HALFSTEP, 1);
-            hipLaunchKernelGGL(k_sweep_fused, dim3(G), dim3(FB), lds_fused, st, P, dir, h->nbmax);
-        }
-        // the ranks are at most it_ + 1 in sweep it_: the units of a team half-step, and the columns of full pivoting by host passes
-        const int rb = std::min((int)h->RM, it_ + 1);
-        const int units = (h->sel.de_test_fault && it_ == h->sel.de_test_fault) ? 1 : rb * ((h->NM + 63) / 64);
-        KLaunch half = plan.half[plan.ntier - 1].k;
-        for (int t = plan.ntier - 2; t >= 0; t--) if (units * G <= plan.half[t].upto) { half = plan.half[t].k; half.grid.x = units; }
-        for (int pp = 1; pp <= h->nbmax && !fused && !cluster; pp++) {
-            if (plan.tables) { KScope ks(h, TTX_K_OTHER); launch(st, plan.tables, P, dir, pp); }
-            if (h->cfg.pivoting >= 0) {
-                if (plan.lot_eval) {
-                    KScope ks(h, TTX_K_LOTTERY, 3);
-                    launch(st, plan.lottery, P, dir, pp, plan.lot_vals, 1);
-                    launch(st, plan.lot_eval, P);
-                    launch(st, plan.lottery, P, dir, pp, plan.lot_vals, 2);
-                } else { KScope ks(h, TTX_K_LOTTERY); if (int rc_ = EV(plan.lottery, dir, pp, plan.lot_vals, 0)) return rc_; }
-                KScope ks(h, TTX_K_HALFSTEP, h->H);
-                for (int hh = 0; hh < h->H; hh++) {
-                    if (plan.half_vals < 0) launch(st, half, P, hh, dir, h->mode);
-                    else if (int rc_ = EV(half, hh, dir, h->mode, plan.half_vals)) return rc_;
-                }
-            } else {
-                // full pivoting (:341-408): every superblock column through the half-step kernel, global arg-max,
-                // then the cross through the winner (evaluation only)
-                KScope ks(h, TTX_K_HALFSTEP, 5);
-                KLaunch cols = plan.base;
-                cols.grid.z = h->NM * h->RM;
-                hipLaunchKernelGGL(k_bond_begin, dim3(G), dim3(64), 0, st, P, dir, pp);
-                if (plan.fullpiv == ChainPlan::FP_MFMA) {
-                    // one dense step: evaluate the superblock once, residual by fp64 MFMA fused with the arg-max
-                    const int side = h->RM * h->NM, gx = (side + 63) / 64;
-                    launch(st, cols, P, 0, dir, 4, plan.base_vals);
-                    hipLaunchKernelGGL(k_full_gemm_argmax, dim3(gx, gx, G), dim3(256), 0, st, P);
-                    hipLaunchKernelGGL(k_full_resolve2, dim3(G), dim3(256), 0, st, P, gx, gx);
-                } else if (plan.fullpiv == ChainPlan::FP_COLUMNS) {
-                    // the user's `fun` with full pivoting (:341-408 works with any fun): one superblock column (k,q) per launch pair --
-                    // pass 1 hands the column's multi-indices to the host, pass 2 takes the values, residual and partial arg-max;
-                    // columns beyond n2 r2 return at once
-                    for (int z = 0; z < h->NM * rb; z++) {
-                        DevProb Q = P;
-                        Q.zbase = z;
-                        Q.hostpass = 1;
-                        launch(st, plan.base, Q, 0, dir, 3, 0);
-                        if (int rc_ = slot_eval(h)) return rc_;
-                        Q.hostpass = 2;
-                        launch(st, plan.base, Q, 0, dir, 3, 0);
-                    }
-                    hipLaunchKernelGGL(k_full_resolve, dim3(G), dim3(256), 0, st, P);
-                } else {
-                    launch(st, cols, P, 0, dir, 3, plan.base_vals);
-                    hipLaunchKernelGGL(k_full_resolve, dim3(G), dim3(256), 0, st, P);
-                }
-                if (int rc_ = EV(plan.base, 0, dir, 2, plan.base_vals)) return rc_;
-                if (int rc_ = EV(plan.base, 1, dir, 2, plan.base_vals)) return rc_;
-            }
-            { KScope ks(h, TTX_K_ACCEPT); launch(st, plan.accept, P, h->H, plan.nfb); }
-        }
-        }
-        if (!(part & 2)) return TTX_OK;
-        if (side) {     // one launch on the main stream; the rest of the sweep's end goes to the quadrature's stream (enqueue_side)
-            HIPCHECK(hipStreamWaitEvent(st, h->ev_val[slot ^ 1], 0));       // the previous quadrature is done with the boundaries and with rq
-            KScope ks(h, TTX_K_EXCHANGE, 1);
-            launch(st, plan.exch_tail, P, it_);
-            HIPCHECK(hipEventRecord(h->ev_tail[slot], st));
-            return TTX_OK;
-        }
-        if (forkq) HIPCHECK(hipStreamWaitEvent(st, h->ev_val[slot ^ 1], 0));   // the previous quadrature is done with the boundaries
-        if (tail) {     // MAX / apply and the boundary blocks as independent blocks of one launch (the cluster kernel packed at its end)
-            KScope ks(h, TTX_K_EXCHANGE, 1);
-            launch(st, plan.exch_tail, P, it_);
-        } else
-        {   // per-sweep exchange between bond groups (:763-961)
-            KScope ks(h, TTX_K_EXCHANGE, (h->W > 1 ? 4 : 2) + (nproc > 1 ? 1 : 0));
-            if (!cluster) hipLaunchKernelGGL(k_exch_pack, dim3(G), dim3(256), 0, st, P);     // the cluster kernel packs at its end
-            if (h->W > 1) {
-                hipLaunchKernelGGL(k_exch_localmax, dim3(1), dim3(64), 0, st, P);
-                if (int rc_ = xfer_neighbours(h)) return rc_;
-                if (int rc_ = allreduce_dev(h, P.redsend, P.redrecv, 4, 1)) return rc_;
-            }
-            hipLaunchKernelGGL(k_exch_max_apply, dim3(G), dim3(256), lds_fpersist(P), st, P, h->W > 1 ? 1 : 0, nproc > 1 ? 1 : 0);
-            if (nproc > 1) { if (int rc_ = EV(plan.exch_boundary)) return rc_; }
-        }
-        if (pipe && h->W == 1) hipLaunchKernelGGL(k_sweep_end, dim3(1), dim3(256), 0, st, P, it_, h->h_sum_base + (size_t)slot * h->SB, tail ? 1 : 0);
-        if (pipe && h->W > 1) {      // this GPU's part -> SUM all-reduce -> pinned slot, all stream-ordered
-            hipLaunchKernelGGL(k_sweep_end, dim3(1), dim3(256), 0, st, P, it_, P.sumsend, 0);
-            if (int rc_ = allreduce_dev(h, P.sumsend, P.sumrecv, h->SB, 0)) return rc_;
-            HIPCHECK(hipMemcpyAsync(h->h_sum_base + (size_t)slot * h->SB, P.sumrecv, sizeof(double) * h->SB, hipMemcpyDeviceToHost, st));
-        }
-        if (pipe) HIPCHECK(hipEventRecord(h->ev_sum[slot], st));     // the summary of the sweep is in the pinned slot
-        if (P.has_quad) {
-            hipStream_t sq = forkq ? h->qstream : st;
-            if (forkq) HIPCHECK(hipStreamWaitEvent(sq, h->ev_sum[slot], 0));    // fork point = end of the sweep's main-stream work
-            KScope ks(h, TTX_K_QUAD, nproc > 1 ? 3 : 2);
-            if (int rc_ = launch_quad(h, sq, pipe ? Pq : P, 0, P.quadw)) return rc_;
-            if (pipe) {
-                HIPCHECK(hipMemcpyAsync(h->h_val + slot, &P.gs[0].val, sizeof(double), hipMemcpyDeviceToHost, sq));
-                HIPCHECK(hipEventRecord(h->ev_val[slot], sq));
-            }
-            if (h->cb_error) return fail(TTX_EHIP, "host transport: a sendrecv / allreduce callback failed");
-        }
-        return TTX_OK;
-    };
-    // `side`: what the end of sweep it_ leaves to the quadrature's stream, behind the tail launch (ev_tail) -- the summary, then the
-    // sweep's quadrature.  Enqueued AFTER the next sweep kernel: at short sweeps (C_16) the host is what the main stream waits for.
-    auto enqueue_side = [&](int it_) -> int {
-        const int slot = it_ & 1;
-        hipStream_t sq = h->qstream;
-        HIPCHECK(hipStreamWaitEvent(sq, h->ev_tail[slot], 0));
-        hipLaunchKernelGGL(k_sweep_summary, dim3(1), dim3(256), 0, sq, P, it_, h->h_sum_base + (size_t)slot * h->SB);
-        HIPCHECK(hipEventRecord(h->ev_sum[slot], sq));          // the summary of the sweep is in the pinned slot
-        KScope ks(h, TTX_K_QUAD, 2);
-        if (int rc_ = launch_quad(h, sq, Pq, 0, P.quadw)) return rc_;
-        HIPCHECK(hipMemcpyAsync(h->h_val + slot, &P.gs[0].val, sizeof(double), hipMemcpyDeviceToHost, sq));
-        HIPCHECK(hipEventRecord(h->ev_val[slot], sq));
-        return TTX_OK;
-    };
-    // ---- finalise (:1029): dtt_lua shifts the rightmost inv of every group to its neighbour first.  Enqueued once; in the
-    //      pipelined loop as soon as the stopping rule has fired on the host (after_val >= 0: the slot whose forked quadrature
-    //      still reads the cores the finalisation overwrites -- a stream-side wait, the host does not idle) ----
-    bool fin_enqueued = false;
-    auto enqueue_final = [&](int after_val) -> int {
-        if (fin_enqueued) return TTX_OK;
-        fin_enqueued = true;
-        if (after_val >= 0) HIPCHECK(hipStreamWaitEvent(st, h->ev_val[after_val], 0));
-        HIPCHECK(hipMemsetAsync(P.ctl, 0, sizeof(int) * 3, st));      // ctl[3] (fault counter of the team / relay half-steps) is read by ttx_run afterwards
-        KScope ks(h, TTX_K_OTHER, 2);
-        if (nproc > 1) {
-            hipLaunchKernelGGL(k_exch_pack, dim3(G), dim3(256), 0, st, P);
-            if (int rc_ = xfer_neighbours(h)) return rc_;
-            hipLaunchKernelGGL(k_exch_apply, dim3(G), dim3(256), lds_fpersist(P), st, P);
-        }
-        launch(st, plan.fin_luar, P, plan.fl);
-        launch(st, plan.fin_lual, P, plan.fl);
-        return TTX_OK;
-    };
-    // host side of a finished sweep: record, tapes, log line, stopping rule (identical to k_sweep_end)
-    auto process_sweep = [&](int it_) -> int {
-        const int dir = 2 - it_ % 2, slot = it_ & 1;
-        if (pipe) {
-            HIPCHECK(hipEventSynchronize(h->ev_sum[slot]));
-            h->h_sum = h->h_sum_base + (size_t)slot * h->SB;
-            {   // the rule needs only the summary: if it fires, the finalisation goes out before the host waits for the value
-                if (stop_rule(it_, h->cfg.maxrank, h->cfg.accuracy, h->h_sum[SUM_PMAX], h->h_sum[SUM_AMAX], strike).ready) { if (int rc_ = enqueue_final(P.has_quad ? slot : -1)) return rc_; }
-            }
-            if (P.has_quad) { HIPCHECK(hipEventSynchronize(h->ev_val[slot])); val = h->h_val[slot]; }
-        } else {
-            if (int rc_ = readback(h)) return rc_;
-            if (P.has_quad) val = h->h_sum[SUM_VAL];      // every GPU ran the same tree on the same gathered matrices
-        }
-        HIPCHECK(hipGetLastError());
-        if (cluster && *(volatile int *)h->h_abort) { h->cluster_aborted = true; return fail(TTX_EHIP, "cluster sweep kernel: barrier timed out (workgroups of a bond group were not co-resident)"); }
-        ttx_sweep_rec r{};
-        r.it = it_; r.dir = dir; r.erank = erank_host(h, rank0_view(h, it_).data()); r.neval = (int64_t)h->h_sum[SUM_NEVAL]; r.val = val;
-        r.amax = h->h_sum[SUM_AMAX]; r.pivotmax = h->h_sum[SUM_PMAX]; r.pivotmin = h->h_sum[SUM_PMIN]; r.seconds = since();
-        h->recs.push_back(r);
-        {
-            size_t o = h->tapes.size();
-            h->tapes.resize(o + (size_t)(d + 1) * 4, -1);
-            for (int p = 1; p < d; p++) for (int x = 0; x < 4; x++) h->tapes[o + (size_t)p * 4 + x] = (int32_t)sum_bond(h, p)[1 + x];
-        }
-        if (h->cfg.verbose) print_line(h, r, val_prev);
-        val_prev = val;
-        const StopRule sr = stop_rule(it_, h->cfg.maxrank, h->cfg.accuracy, r.pivotmax, r.amax, strike);   // :1011-1019 (rank 0's amax, global pivotmax)
-        strike = sr.strikes;
-        ready = ready || sr.ready;
-        return TTX_OK;
-    };
-    if (!pipe) {
-        while (!ready) {
-            it++;
-            if ((rc = enqueue_sweep(it, 3))) return rc;
-            if ((rc = process_sweep(it))) return rc;
-        }
-    } else if (!ready) {
-        // only the sweep kernel of it+1 is enqueued speculatively (it keeps the GPU busy while the host reads the summary of
-        // sweep it); once the rule has fired that one launch finds the stop flag and exits, and its tail is never enqueued
-        if (forkq) { HIPCHECK(hipEventRecord(h->ev_val[0], h->qstream)); HIPCHECK(hipEventRecord(h->ev_val[1], h->qstream)); }
-        if (!head1 && (rc = enqueue_sweep(1, 1))) return rc;
-        for (it = 1; !ready; it++) {
-            if ((rc = enqueue_sweep(it, 2))) return rc;
-            if (it + 1 < h->cfg.maxrank && (rc = enqueue_sweep(it + 1, 1))) return rc;
-            if (side && (rc = enqueue_side(it))) return rc;
-            if ((rc = process_sweep(it))) return rc;
-        }
-        it--;
-    }
-    if ((rc = enqueue_final(-1))) return rc;
-    if ((rc = readback(h))) return rc;
-    HIPCHECK(hipGetLastError());
-#ifdef TTX_STAMPS
+    const DevProb &P = h->P;
     if (P.dbg) {   // per-wave cycle stamps of one bond step of the cluster kernel (WST in ttx_cluster.h), relative to the earliest one
         std::vector<long long> hb(8 * 64 * 8);
         HIPCHECK(hipMemcpy(hb.data(), P.dbg, sizeof(long long) * hb.size(), hipMemcpyDeviceToHost));
@@ -1605,24 +1301,326 @@ static int run_impl(ttx_engine *h)
             }
         }
     }
-    {   // debug build: average wall_clock64 ticks (10 ns) per phase of the lottery (0) and half-step (1) kernels
-        GroupState g0s;
-        HIPCHECK(hipMemcpy(&g0s, P.gs, sizeof(GroupState), hipMemcpyDeviceToHost));
-        for (int k = 0; k < 2; k++) {
-            fprintf(stderr, "stamps kernel %d (n=%lld):", k, g0s.nstamp[k]);
-            for (int x = 0; x < 16; x++) fprintf(stderr, " %.2fus", g0s.nstamp[k] ? 0.01 * (double)g0s.stamp[k][x] / (double)g0s.nstamp[k] : 0.0);
-            fprintf(stderr, "\n");
-        }
+    // average wall_clock64 ticks (10 ns) per phase of the lottery (0) and half-step (1) kernels
+    GroupState g0s;
+    HIPCHECK(hipMemcpy(&g0s, P.gs, sizeof(GroupState), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 2; k++) {
+        fprintf(stderr, "stamps kernel %d (n=%lld):", k, g0s.nstamp[k]);
+        for (int x = 0; x < 16; x++) fprintf(stderr, " %.2fus", g0s.nstamp[k] ? 0.01 * (double)g0s.stamp[k][x] / (double)g0s.nstamp[k] : 0.0);
+        fprintf(stderr, "\n");
     }
-#endif
-    h->neval = (int64_t)h->h_sum[SUM_NEVAL];
-    h->k_bytes[TTX_K_HALFSTEP] += h->h_sum[SUM_BYTES];
-    h->n_resid = (int64_t)h->h_sum[SUM_NRESID];
-    h->rfinal = global_ranks(h);
-    h->seconds = since();
-    h->ran = true;
     return TTX_OK;
 }
+#endif
+
+// ---- the sweep driver: the host side of one dtt_dmrgg run ----------------------------------------------------------------------
+// The form of the loop (L, ttx_loop_plan.h: the reasons stand there) and what the chain path launches (plan) are decided once; the
+// steps read both.  Sweep it_ runs in direction 2 - it_ % 2; its summary, its value and their events use the pinned slot it_ & 1.
+template <int FUN>
+struct SweepRun {
+    using clk = std::chrono::steady_clock;
+    ttx_engine *const h; DevProb &P; const hipStream_t st;
+    const int d, G, nproc, cluster, fused;      // cluster, fused: the whole-sweep kernel this run uses, if any
+    const clk::time_point t0 = clk::now();
+    LoopPlan L; ChainPlan plan;
+    DevProb Pq;                                 // what the per-sweep quadrature sees: in the pipelined loop the snapshot of the ranks
+    double val = 1.0, val_prev = 1.0;
+    int strike = 0; bool ready = false, fin_enqueued = false;
+    explicit SweepRun(ttx_engine *h_) : h(h_), P(h_->P), st(h_->stream), d(h_->d), G(h_->G), nproc(h_->cfg.nproc), cluster(h_->cluster_nb()), fused(h_->sel.fused) {}
+    double since() const { return std::chrono::duration<double>(clk::now() - t0).count(); }
+    // an evaluating kernel: once with the device integrand; with a host integrand twice around the host's calls
+    template <class... A>
+    int EV(const KLaunch &k, A... a)
+    {
+        if (FUN != FUN_HOST) { launch(st, k, P, a...); return TTX_OK; }
+        DevProb Q = P;
+        Q.hostpass = 1; launch(st, k, Q, a...);
+        if (int rc = slot_eval(h)) return rc;
+        Q.hostpass = 2; launch(st, k, Q, a...);
+        return TTX_OK;
+    }
+    // the two plans of the run (the kernels of the chain path, and the whole-sweep kernel where one is used, may stage more than the
+    // default 64 KB of dynamic LDS, 160 KB per CU on gfx950), reset (lib/dmrgg.f90:96-100, 141-148, 279-288), initial cross (:151-301)
+    int prepare()
+    {
+        LoopIn in;
+        in.whole = cluster || fused; in.cluster = cluster != 0; in.profile = h->profile; in.pipeline_off = env_off("TTX_PIPELINE");
+        in.W = h->W; in.nproc = nproc; in.has_quad = P.has_quad; in.host_pass = FUN == FUN_HOST;
+        in.sweep_tail = h->sel.sweep_tail; in.sweep_tail_side = h->sel.sweep_tail_side; in.maxrank = h->cfg.maxrank;
+        L = loop_plan(in);
+        P.tail_side = L.side ? 1 : 0;
+        h->recs.clear(); h->tapes.clear();
+        plan = chain_plan<FUN>(h);
+        for (const KLaunch *k : plan.all()) if (k->raise) if (int rc = ensure_lds(h, k->fn, k->lds)) return rc;
+        if (fused) if (int rc = ensure_lds(h, reinterpret_cast<const void *>(k_sweep_fused), h->sel.lds_fused)) return rc;
+        if (cluster) { if (int rc = ensure_lds_cluster(h)) return rc; *h->h_abort = 0; }
+        Pq = P;
+        if (L.pipe) Pq.r = P.rq;
+        hipLaunchKernelGGL(k_reset, dim3(64), dim3(256), 0, st, P, h->SB, h->QB);
+        {
+            KScope ks(h, TTX_K_OTHER, 4);
+            if (int rc = EV(plan.init_samples, h->sel.snum, h->sel.nn, FUN == FUN_HOST ? 0 : plan.srows, 0)) return rc;
+            if (int rc = EV(plan.init_fibers)) return rc;
+            hipLaunchKernelGGL(k_init_factors, dim3(h->NC, G), dim3(256), lds_fpersist(P), st, P);
+            hipLaunchKernelGGL(k_init_final, dim3(G), dim3(256), 0, st, P);
+        }
+        if (L.head) {
+            hipLaunchKernelGGL(k_collect, dim3(1), dim3(256), 0, st, P);
+            h->h_sum = h->h_sum_base;
+            HIPCHECK(hipMemcpyAsync(h->h_sum, P.sumrecv, sizeof(double) * h->SB, hipMemcpyDeviceToHost, st));
+            HIPCHECK(hipEventRecord(h->ev_sum[0], st));
+            if (int rc = launch_sweep_kernel(1)) return rc;
+            HIPCHECK(hipEventSynchronize(h->ev_sum[0]));
+        } else if (int rc = readback(h)) return rc;
+        HIPCHECK(hipGetLastError());
+        for (int g = 0; g < nproc; g++) val = (g == 0) ? h->h_sum[SUM_HDR + g] : val * h->h_sum[SUM_HDR + g];   // :259-267 PROD
+        if (!P.has_quad) val = 0.0;
+        val_prev = val;
+        record(0, 0);
+        ready = (1 >= h->cfg.maxrank);
+        return TTX_OK;
+    }
+    // the one place that launches a whole-sweep kernel: behind the initial cross (L.head) and from both loops.  The cluster kernel can
+    // go as a cooperative launch (TTX_CLUSTER_COOP: the runtime guarantees -- or refuses -- co-residency of the grid)
+    int launch_sweep_kernel(int it_)
+    {
+        const CreatePlan &s = h->sel;
+        int dir = 2 - it_ % 2, epoch = it_, nsteps = h->nbmax, NB = s.cluster, ldsinv = s.cluster_ldsinv, zkeep = s.cluster_zkeep;
+        const dim3 grid(8 * NB * ((G + 7) / 8)), block(CB);
+        KScope ks(h, TTX_K_HALFSTEP, 1);
+        if (!cluster) hipLaunchKernelGGL(k_sweep_fused, dim3(G), dim3(FB), s.lds_fused, st, P, dir, nsteps);
+        else if (s.cluster_coop) {
+            void *args[] = {&P, &dir, &nsteps, &NB, &ldsinv, &epoch, &zkeep};
+            HIPCHECK(hipLaunchCooperativeKernel(reinterpret_cast<const void *>(cluster_kernel(s.cluster_var)), grid, block, args, (unsigned)s.lds_cluster, st));
+        } else hipLaunchKernelGGL(cluster_kernel(s.cluster_var), grid, block, s.lds_cluster, st, P, dir, nsteps, NB, ldsinv, epoch, zkeep);
+        return TTX_OK;
+    }
+    // the chain path's sweep over the own bonds: tables, lottery, half-steps (or full pivoting), accept per bond step
+    int enqueue_chain_sweep(int it_)
+    {
+        const int dir = 2 - it_ % 2;
+        // the ranks are at most it_ + 1 in sweep it_: the units of a team half-step, and the columns of full pivoting by host passes
+        const int rb = std::min((int)h->RM, it_ + 1);
+        const int units = (h->sel.de_test_fault && it_ == h->sel.de_test_fault) ? 1 : rb * ((h->NM + 63) / 64);
+        KLaunch half = plan.half[plan.ntier - 1].k;
+        for (int t = plan.ntier - 2; t >= 0; t--) if (units * G <= plan.half[t].upto) { half = plan.half[t].k; half.grid.x = units; }
+        for (int pp = 1; pp <= h->nbmax; pp++) {
+            if (plan.tables) { KScope ks(h, TTX_K_OTHER); launch(st, plan.tables, P, dir, pp); }
+            if (h->cfg.pivoting < 0) { if (int rc = enqueue_full_pivoting(dir, pp, rb)) return rc; }
+            else {
+                if (plan.lot_eval) {
+                    KScope ks(h, TTX_K_LOTTERY, 3);
+                    launch(st, plan.lottery, P, dir, pp, plan.lot_vals, 1);
+                    launch(st, plan.lot_eval, P);
+                    launch(st, plan.lottery, P, dir, pp, plan.lot_vals, 2);
+                } else { KScope ks(h, TTX_K_LOTTERY); if (int rc = EV(plan.lottery, dir, pp, plan.lot_vals, 0)) return rc; }
+                KScope ks(h, TTX_K_HALFSTEP, h->H);
+                for (int hh = 0; hh < h->H; hh++) {
+                    if (plan.half_vals < 0) launch(st, half, P, hh, dir, h->mode);
+                    else if (int rc = EV(half, hh, dir, h->mode, plan.half_vals)) return rc;
+                }
+            }
+            { KScope ks(h, TTX_K_ACCEPT); launch(st, plan.accept, P, h->H, plan.nfb); }
+        }
+        return TTX_OK;
+    }
+    // full pivoting (:341-408): every superblock column through the half-step kernel, global arg-max, then the cross through the
+    // winner (evaluation only)
+    int enqueue_full_pivoting(int dir, int pp, int rb)
+    {
+        KScope ks(h, TTX_K_HALFSTEP, 5);
+        KLaunch cols = plan.base;
+        cols.grid.z = h->NM * h->RM;
+        hipLaunchKernelGGL(k_bond_begin, dim3(G), dim3(64), 0, st, P, dir, pp);
+        if (plan.fullpiv == ChainPlan::FP_MFMA) {
+            // one dense step: evaluate the superblock once, residual by fp64 MFMA fused with the arg-max
+            const int side = h->RM * h->NM, gx = (side + 63) / 64;
+            launch(st, cols, P, 0, dir, 4, plan.base_vals);
+            hipLaunchKernelGGL(k_full_gemm_argmax, dim3(gx, gx, G), dim3(256), 0, st, P);
+            hipLaunchKernelGGL(k_full_resolve2, dim3(G), dim3(256), 0, st, P, gx, gx);
+        } else if (plan.fullpiv == ChainPlan::FP_COLUMNS) {
+            // the user's `fun` with full pivoting (:341-408 works with any fun): one superblock column (k,q) per launch pair --
+            // pass 1 hands the column's multi-indices to the host, pass 2 takes the values, residual and partial arg-max;
+            // columns beyond n2 r2 return at once
+            for (int z = 0; z < h->NM * rb; z++) {
+                DevProb Q = P;
+                Q.zbase = z;
+                Q.hostpass = 1; launch(st, plan.base, Q, 0, dir, 3, 0);
+                if (int rc = slot_eval(h)) return rc;
+                Q.hostpass = 2; launch(st, plan.base, Q, 0, dir, 3, 0);
+            }
+            hipLaunchKernelGGL(k_full_resolve, dim3(G), dim3(256), 0, st, P);
+        } else {
+            launch(st, cols, P, 0, dir, 3, plan.base_vals);
+            hipLaunchKernelGGL(k_full_resolve, dim3(G), dim3(256), 0, st, P);
+        }
+        if (int rc = EV(plan.base, 0, dir, 2, plan.base_vals)) return rc;
+        return EV(plan.base, 1, dir, 2, plan.base_vals);
+    }
+    // the end of sweep it_: exchange between the bond groups, stopping rule and summary, quadrature -- in one of three forms
+    int enqueue_sweep_end(int it_)
+    {
+        const int slot = it_ & 1;
+        if (L.side) return end_side(it_);
+        if (L.forkq) HIPCHECK(hipStreamWaitEvent(st, h->ev_val[slot ^ 1], 0));   // the previous quadrature is done with the boundaries
+        if (int rc = L.tail ? end_tail(it_) : end_classic(it_)) return rc;
+        if (L.pipe) HIPCHECK(hipEventRecord(h->ev_sum[slot], st));     // the summary of the sweep is in the pinned slot
+        if (!P.has_quad) return TTX_OK;
+        if (L.forkq) HIPCHECK(hipStreamWaitEvent(h->qstream, h->ev_sum[slot], 0));    // fork point = end of the sweep's main-stream work
+        return enqueue_quadrature(it_, L.forkq ? h->qstream : st);
+    }
+    // side: one launch on the main stream; the rest of the sweep's end goes to the quadrature's stream (enqueue_side)
+    int end_side(int it_)
+    {
+        const int slot = it_ & 1;
+        HIPCHECK(hipStreamWaitEvent(st, h->ev_val[slot ^ 1], 0));       // the previous quadrature is done with the boundaries and with rq
+        KScope ks(h, TTX_K_EXCHANGE, 1);
+        launch(st, plan.exch_tail, P, it_);
+        HIPCHECK(hipEventRecord(h->ev_tail[slot], st));
+        return TTX_OK;
+    }
+    // tail: MAX / apply and the boundary blocks as independent blocks of one launch (the cluster kernel packed at its end), then the rule
+    int end_tail(int it_)
+    {
+        { KScope ks(h, TTX_K_EXCHANGE, 1); launch(st, plan.exch_tail, P, it_); }
+        hipLaunchKernelGGL(k_sweep_end, dim3(1), dim3(256), 0, st, P, it_, h->h_sum_base + (size_t)(it_ & 1) * h->SB, 1);
+        return TTX_OK;
+    }
+    // classic: the per-sweep exchange between bond groups (:763-961) launch by launch, then in the pipelined loop the rule: with one
+    // process straight into the pinned slot, with several this GPU's part -> SUM all-reduce -> pinned slot, all stream-ordered
+    int end_classic(int it_)
+    {
+        {
+            KScope ks(h, TTX_K_EXCHANGE, (h->W > 1 ? 4 : 2) + (nproc > 1 ? 1 : 0));
+            if (!cluster) hipLaunchKernelGGL(k_exch_pack, dim3(G), dim3(256), 0, st, P);     // the cluster kernel packs at its end
+            if (h->W > 1) {
+                hipLaunchKernelGGL(k_exch_localmax, dim3(1), dim3(64), 0, st, P);
+                if (int rc = xfer_neighbours(h)) return rc;
+                if (int rc = allreduce_dev(h, P.redsend, P.redrecv, 4, 1)) return rc;
+            }
+            hipLaunchKernelGGL(k_exch_max_apply, dim3(G), dim3(256), lds_fpersist(P), st, P, h->W > 1 ? 1 : 0, nproc > 1 ? 1 : 0);
+            if (nproc > 1) { if (int rc = EV(plan.exch_boundary)) return rc; }
+        }
+        double *const pinned = h->h_sum_base + (size_t)(it_ & 1) * h->SB;
+        if (L.pipe) hipLaunchKernelGGL(k_sweep_end, dim3(1), dim3(256), 0, st, P, it_, h->W > 1 ? P.sumsend : pinned, 0);
+        if (L.pipe && h->W > 1) {
+            if (int rc = allreduce_dev(h, P.sumsend, P.sumrecv, h->SB, 0)) return rc;
+            HIPCHECK(hipMemcpyAsync(pinned, P.sumrecv, sizeof(double) * h->SB, hipMemcpyDeviceToHost, st));
+        }
+        return TTX_OK;
+    }
+    // the per-sweep quadrature on the stream sq; in the pipelined loop its value goes to the pinned slot, ev_val behind it
+    int enqueue_quadrature(int it_, hipStream_t sq)
+    {
+        const int slot = it_ & 1;
+        KScope ks(h, TTX_K_QUAD, nproc > 1 ? 3 : 2);
+        if (int rc = launch_quad(h, sq, L.pipe ? Pq : P, 0, P.quadw)) return rc;
+        if (L.pipe) {
+            HIPCHECK(hipMemcpyAsync(h->h_val + slot, &P.gs[0].val, sizeof(double), hipMemcpyDeviceToHost, sq));
+            HIPCHECK(hipEventRecord(h->ev_val[slot], sq));
+        }
+        return h->cb_error ? fail(TTX_EHIP, "host transport: a sendrecv / allreduce callback failed") : TTX_OK;
+    }
+    // side: what the end of sweep it_ leaves to the quadrature's stream behind the tail launch (ev_tail): the summary, the quadrature
+    int enqueue_side(int it_)
+    {
+        const int slot = it_ & 1;
+        hipStream_t sq = h->qstream;
+        HIPCHECK(hipStreamWaitEvent(sq, h->ev_tail[slot], 0));
+        hipLaunchKernelGGL(k_sweep_summary, dim3(1), dim3(256), 0, sq, P, it_, h->h_sum_base + (size_t)slot * h->SB);
+        HIPCHECK(hipEventRecord(h->ev_sum[slot], sq));          // the summary of the sweep is in the pinned slot
+        return enqueue_quadrature(it_, sq);
+    }
+    // finalise (:1029): dtt_lua shifts the rightmost inv of every group to its neighbour first.  Enqueued once (LoopPlan::pipe);
+    // after_val >= 0: the slot whose forked quadrature still reads the cores the finalisation overwrites
+    int enqueue_final(int after_val)
+    {
+        if (fin_enqueued) return TTX_OK;
+        fin_enqueued = true;
+        if (after_val >= 0) HIPCHECK(hipStreamWaitEvent(st, h->ev_val[after_val], 0));
+        HIPCHECK(hipMemsetAsync(P.ctl, 0, sizeof(int) * 3, st));      // ctl[3] (fault counter of the team / relay half-steps) is read by ttx_run afterwards
+        KScope ks(h, TTX_K_OTHER, 2);
+        if (nproc > 1) {
+            hipLaunchKernelGGL(k_exch_pack, dim3(G), dim3(256), 0, st, P);
+            if (int rc = xfer_neighbours(h)) return rc;
+            hipLaunchKernelGGL(k_exch_apply, dim3(G), dim3(256), lds_fpersist(P), st, P);
+        }
+        launch(st, plan.fin_luar, P, plan.fl);
+        launch(st, plan.fin_lual, P, plan.fl);
+        return TTX_OK;
+    }
+    // the record and the log line of sweep it_ (0: the initial cross) from the summary in h_sum and from val
+    void record(int it_, int dir)
+    {
+        ttx_sweep_rec r{};
+        r.it = it_; r.dir = dir; r.erank = erank_host(h, rank0_view(h, it_).data()); r.neval = (int64_t)h->h_sum[SUM_NEVAL]; r.val = val;
+        r.amax = h->h_sum[SUM_AMAX]; r.pivotmax = it_ ? h->h_sum[SUM_PMAX] : -1; r.pivotmin = it_ ? h->h_sum[SUM_PMIN] : -1; r.seconds = since();
+        h->recs.push_back(r);
+        if (h->cfg.verbose) print_line(h, r, val_prev);
+    }
+    // host side of a finished sweep: stopping rule (identical to k_sweep_end), record, tapes, log line
+    int process_sweep(int it_)
+    {
+        const int slot = it_ & 1;
+        if (L.pipe) {
+            HIPCHECK(hipEventSynchronize(h->ev_sum[slot]));
+            h->h_sum = h->h_sum_base + (size_t)slot * h->SB;
+        } else if (int rc = readback(h)) return rc;
+        const StopRule sr = stop_rule(it_, h->cfg.maxrank, h->cfg.accuracy, h->h_sum[SUM_PMAX], h->h_sum[SUM_AMAX], strike);   // :1011-1019 (rank 0's amax, global pivotmax)
+        // the rule needs only the summary: if it fires, the finalisation goes out before the host waits for the value
+        if (L.pipe && sr.ready) if (int rc = enqueue_final(P.has_quad ? slot : -1)) return rc;
+        if (P.has_quad) {
+            if (L.pipe) { HIPCHECK(hipEventSynchronize(h->ev_val[slot])); val = h->h_val[slot]; }
+            else val = h->h_sum[SUM_VAL];      // every GPU ran the same tree on the same gathered matrices
+        }
+        HIPCHECK(hipGetLastError());
+        if (cluster && *(volatile int *)h->h_abort) { h->cluster_aborted = true; return fail(TTX_EHIP, "cluster sweep kernel: barrier timed out (workgroups of a bond group were not co-resident)"); }
+        record(it_, 2 - it_ % 2);
+        const size_t o = h->tapes.size();
+        h->tapes.resize(o + (size_t)(d + 1) * 4, -1);
+        for (int p = 1; p < d; p++) for (int x = 0; x < 4; x++) h->tapes[o + (size_t)p * 4 + x] = (int32_t)sum_bond(h, p)[1 + x];
+        val_prev = val;
+        strike = sr.strikes;
+        ready = ready || sr.ready;
+        return TTX_OK;
+    }
+    // preparation, the main loop (:309-1020) host-synchronised or pipelined, finalisation
+    int run()
+    {
+        if (int rc = prepare()) return rc;
+        if (!L.pipe) {
+            for (int it = 1; !ready; it++) {
+                if (int rc = (cluster || fused) ? launch_sweep_kernel(it) : enqueue_chain_sweep(it)) return rc;
+                if (int rc = enqueue_sweep_end(it)) return rc;
+                if (int rc = process_sweep(it)) return rc;
+            }
+        } else if (!ready) {
+            if (L.forkq) { HIPCHECK(hipEventRecord(h->ev_val[0], h->qstream)); HIPCHECK(hipEventRecord(h->ev_val[1], h->qstream)); }
+            if (!L.head) if (int rc = launch_sweep_kernel(1)) return rc;
+            for (int it = 1; !ready; it++) {
+                if (int rc = enqueue_sweep_end(it)) return rc;
+                if (it + 1 < h->cfg.maxrank) if (int rc = launch_sweep_kernel(it + 1)) return rc;
+                if (L.side) if (int rc = enqueue_side(it)) return rc;
+                if (int rc = process_sweep(it)) return rc;
+            }
+        }
+        if (int rc = enqueue_final(-1)) return rc;
+        if (int rc = readback(h)) return rc;
+        HIPCHECK(hipGetLastError());
+#ifdef TTX_STAMPS
+        if (int rc = dump_stamps(h)) return rc;
+#endif
+        h->neval = (int64_t)h->h_sum[SUM_NEVAL];
+        h->k_bytes[TTX_K_HALFSTEP] += h->h_sum[SUM_BYTES];
+        h->n_resid = (int64_t)h->h_sum[SUM_NRESID];
+        h->rfinal = global_ranks(h);
+        h->seconds = since();
+        h->ran = true;
+        return TTX_OK;
+    }
+};
+template <int FUN>
+static int run_impl(ttx_engine *h) { return SweepRun<FUN>(h).run(); }
 
 // f(std::integral_constant<int, FUN>) for the instantiation an engine's integrand runs with: the host's `fun`, the COS coefficients
 // and a loaded device integrand share the two-pass kernels of FUN_HOST (slot_eval tells them apart).  `who` names the caller
