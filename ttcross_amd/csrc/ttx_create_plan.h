@@ -377,7 +377,9 @@ inline CreatePlan create_plan(const ttx_config &cfg, bool nofun, const CreateEnv
         else if (want_sweep == "chain") p.sweep_want = SWEEP_CHAIN;
         else return plan_refuse(p, TTX_EINVAL, "TTX_SWEEP must be auto, chain, fused or cluster (got %s)", want_sweep.c_str());
     }
-    if (p.lds_half > TTX_LDS_DEVICE || p.lds_lot > TTX_LDS_LOTTERY) return plan_refuse(p, TTX_EINVAL, "problem too large for LDS staging (d*maxrank)");
+    // an engine that only holds a train (nofun) never launches the half-step or the lottery: their staging does not bound its modes
+    // (the lottery's header alone, 16 (2 RM + 2 NM) bytes, would refuse every train with a mode above about 3800)
+    if (!nofun && (p.lds_half > TTX_LDS_DEVICE || p.lds_lot > TTX_LDS_LOTTERY)) return plan_refuse(p, TTX_EINVAL, "problem too large for LDS staging (d*maxrank)");
     {   // lottery: one wave of candidates per workgroup where one evaluation is a long dependent chain (Ising D/E, mvn)
         const bool heavy = p.isDE || fun == TTX_FUN_MVN;
         if (heavy && !env.lottery_one_block) p.lot_nb = std::min((nlotmax + 63) / 64, 64);
