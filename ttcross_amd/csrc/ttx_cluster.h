@@ -27,12 +27,19 @@
 #pragma once
 #include "ttx_fused.h"
 #include "ttx_mvn.h"       // mvn_lane: one double of a wave by v_readlane
-#include "ttx_cluster_rules.h"   // cl_slice, cl_wact, cl_key: the rules a host program checks
+#include "ttx_cluster_rules.h"   // cl_slice, cl_wact, cl_key, cl_ordered_sum: the rules a host program checks
 
 #define CB 256      // threads of a cluster workgroup
-#ifndef TTX_CL_UNR
-#define TTX_CL_UNR 16   // factor loads of the residual in flight per batch (8: +0.6 % run time, 32: no further gain)
-#endif
+
+// Memory operands of the residual sums (cl_ordered_sum, ttx_cluster_rules.h).  ClStrided: the entries base[at + stride * s],
+// s = 0, 1, ... of a factor -- a running wave-uniform pointer, stepped by a scalar add per term, and the lane's fixed byte
+// offset (an element's place within a slab: far below 2^32), so a load costs the vector unit no address arithmetic.
+struct ClD2 { double a, b; };
+struct ClStrided {
+    const char *p; size_t sb; unsigned at;
+    __device__ __forceinline__ ClStrided(const double *base, size_t at_, size_t stride) : p((const char *)base), sb(8 * stride), at((unsigned)(8 * at_)) {}
+    __device__ __forceinline__ double operator()() { const double v = *(const double *)(p + at); p += sb; return v; }
+};
 
 // Ising C integrand from VALUE rows, with the two running sums resumed from per-row prefix states: (pv, pvk) is the
 // state of the descending sum after the right row bn (dims A+3..m), (pw, pwk) the state of the ascending sum after
@@ -493,6 +500,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         // list lengths as wave-uniform values: the two searches of ttx_lottery_index2 then run a uniform number of steps
         const int nscu = __builtin_amdgcn_readfirstlane(nsc), nsru = __builtin_amdgcn_readfirstlane(nsr);
         const int nzcu = __builtin_amdgcn_readfirstlane(nzc), nzru = __builtin_amdgcn_readfirstlane(nzr);
+        const int r1u = __builtin_amdgcn_readfirstlane(r1);
         for (int il = tid; il < nlot; il += CB) {
             const unsigned long long bil = (il == tid) ? bil0 : ttx_minstd_pow(2ull * il);
             const double d1 = ttx_flang_from_word(ttx_mulmod31(sA0, bil)), d2 = ttx_flang_from_word(ttx_mulmod31(sA1, bil));
@@ -509,10 +517,9 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
             else f = f_ising_c4p(m, p - 1, rl, rl + VS, par[j - 1], par[n1m + j - 1], par[k - 1], par[n1m + k - 1], rq, rq + VS, pRv[q - 1], pRk[q - 1], pLw[i - 1], pLk[i - 1]);
             ma = fmax(ma, fabs(f));
             CST(4);
-            const double *c = Cp + (i - 1) + (size_t)RM * (j - 1), *w = Wq + (k - 1) + (size_t)NM * (q - 1);
+            ClStrided lc(Cp, (i - 1) + (size_t)RM * (j - 1), P.SS), lw(Wq, (k - 1) + (size_t)NM * (q - 1), P.SW);
             double t = 0.0;
-#pragma unroll 8
-            for (int s = 0; s < r1; s++) t = t + c[P.SS * s] * w[P.SW * s];
+            cl_ordered_sum<8>(r1u, [&] { const double cv = lc(); return ClD2{cv, lw()}; }, [&](int, ClD2 e) { t = t + e.a * e.b; });
             const double b = f - t, aa = fabs(b);
             if (aa > ba || (aa == ba && il < bi)) { ba = aa; bv = b; bi = il; }
         }
@@ -536,7 +543,6 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         int havecol = 0, haverow = 0, crs = 0, done = 0;
         int rc_k = -1, rc_q = -1, rr_i = -1, rr_j = -1;     // pivot at which resc / resr were computed (-1: not valid)
         const int H = (P.piv == 0) ? 2 : 2 * P.piv;
-        const int r1u = __builtin_amdgcn_readfirstlane(r1);
         double mxrun = 0.0;                                 // this wave's largest |value| over the half-steps of this bond step
         // Only the waves that own fiber elements at the current ranks (and wave 0 of every workgroup) take part in the rook loop and
         // its record exchange: at low ranks that is one wave per workgroup, and 24 idle waves polling the same four cache lines for
@@ -572,15 +578,13 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                 if (iscol) {
                     const int i = u % r0, j = jlo + u / r0, t = i + r0 * j;
                     const double *rl = XL + (size_t)i * RS, *rq = XR + (size_t)(qq - 1) * RS;
-                    const double *c = Cp + i + (size_t)RM * j;
                     if constexpr (CFAST) a = f_ising_cfast(par[j], par[n1m + j], par[kk - 1], par[n1m + kk - 1], pRv[qq - 1], pRk[qq - 1], pLw[i], pLk[i], fSL[i], fWL[i], fSR[qq - 1], fWR[qq - 1]);
                     else if constexpr (CPAD) a = f_ising_c4w(cA, cB, rl, rl + VS, par[j], par[n1m + j], par[kk - 1], par[n1m + kk - 1], rq, rq + VS, pRv[qq - 1], pRk[qq - 1], pLw[i], pLk[i]);
                     else a = f_ising_c4p(m, p - 1, rl, rl + VS, par[j], par[n1m + j], par[kk - 1], par[n1m + kk - 1], rq, rq + VS, pRv[qq - 1], pRk[qq - 1], pLw[i], pLk[i]);
                     fib[u] = a;
                     if (resid) {
                         double b = a;
-#pragma unroll TTX_CL_UNR
-                        for (int s = 0; s < r1u; s++) b = b + (-mvn_lane(xsv, s)) * c[P.SS * s];
+                        cl_ordered_sum<16>(r1u, ClStrided(Cp, i + (size_t)RM * j, P.SS), [&](int s, double cv) { b = b + (-mvn_lane(xsv, s)) * cv; });
                         resc[u] = b;
                         const double aa = fabs(b);
                         if (aa > ab || (aa == ab && t < ix)) { ab = aa; bb = b; ix = t; }
@@ -588,15 +592,13 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                 } else {
                     const int k = klo + u % nk, q = u / nk, t = k + n2 * q;
                     const double *rl = XL + (size_t)(ii - 1) * RS, *rq = XR + (size_t)q * RS;
-                    const double *w = Wq + k + (size_t)NM * q;
                     if constexpr (CFAST) a = f_ising_cfast(par[jj - 1], par[n1m + jj - 1], par[k], par[n1m + k], pRv[q], pRk[q], pLw[ii - 1], pLk[ii - 1], fSL[ii - 1], fWL[ii - 1], fSR[q], fWR[q]);
                     else if constexpr (CPAD) a = f_ising_c4w(cA, cB, rl, rl + VS, par[jj - 1], par[n1m + jj - 1], par[k], par[n1m + k], rq, rq + VS, pRv[q], pRk[q], pLw[ii - 1], pLk[ii - 1]);
                     else a = f_ising_c4p(m, p - 1, rl, rl + VS, par[jj - 1], par[n1m + jj - 1], par[k], par[n1m + k], rq, rq + VS, pRv[q], pRk[q], pLw[ii - 1], pLk[ii - 1]);
                     fib[u] = a;
                     if (resid) {
                         double tt = 0.0;
-#pragma unroll TTX_CL_UNR
-                        for (int s = 0; s < r1u; s++) tt = tt + w[P.SW * s] * mvn_lane(xsv, s);
+                        cl_ordered_sum<16>(r1u, ClStrided(Wq, k + (size_t)NM * q, P.SW), [&](int s, double wv_) { tt = tt + wv_ * mvn_lane(xsv, s); });
                         const double b = a + (-1.0) * tt;
                         resr[u] = b;
                         const double aa = fabs(b);
@@ -740,8 +742,8 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                 if (reuseA) y = resc[u];             // the same sum, in the same order, as the last column half-step
                 else {
                     y = a;
-#pragma unroll 16
-                    for (int s = 0; s < r1; s++) y = y + (-xsc[s]) * Cp[o + P.SS * s];
+                    ClStrided lc(Cp, o, P.SS); const double *xp = xsc;
+                    cl_ordered_sum<16>(r1u, [&] { const double xv = *xp++; return ClD2{xv, lc()}; }, [&](int, ClD2 e) { y = y + (-e.a) * e.b; });
                 }
                 Cp[o + P.SS * r1] = (1.0 / pivot) * y;
             }
@@ -754,8 +756,8 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                 if (reuseB) Wq[o + P.SW * r1] = resr[u];
                 else {
                     double tt = 0.0;
-#pragma unroll 16
-                    for (int s = 0; s < r1; s++) tt = tt + Wq[o + P.SW * s] * xsr[s];
+                    ClStrided lw(Wq, o, P.SW); const double *xp = xsr;
+                    cl_ordered_sum<16>(r1u, [&] { const double xv = *xp++; return ClD2{lw(), xv}; }, [&](int, ClD2 e) { tt = tt + e.a * e.b; });
                     Wq[o + P.SW * r1] = a + (-1.0) * tt;
                 }
             }

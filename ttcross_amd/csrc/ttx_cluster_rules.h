@@ -1,6 +1,6 @@
-// ttx_cluster_rules.h -- the two value rules of the cluster sweep kernel (ttx_cluster.h) that a host program can check
-// (tests/cluster_diet_main.cpp): the slice of the mode index a workgroup owns, and the integer key under which the kernel
-// takes wave maxima of its non-negative doubles.
+// ttx_cluster_rules.h -- the rules of the cluster sweep kernel (ttx_cluster.h) that a host program can check: the slice of
+// the mode index a workgroup owns and the integer key under which the kernel takes wave maxima of its non-negative doubles
+// (tests/cluster_diet_main.cpp), and the batched form of its ordered residual sums (tests/cluster_resid_main.cpp).
 #pragma once
 #include "ttx_cdf.h"     // TTX_HD, ttx_dbits, ttx_bitsd
 
@@ -27,3 +27,41 @@ TTX_HD ClKey cl_key(double x) { const uint64_t b = ttx_dbits(x); return ClKey{(i
 TTX_HD double cl_unkey(ClKey k) { return ttx_bitsd(((uint64_t)(uint32_t)k.hi << 32) | k.lo); }
 // the low word a lane puts into the second tree once the largest high word hmax of the wave is known
 TTX_HD unsigned cl_key_lo_at(ClKey k, int hmax) { return k.hi == hmax ? k.lo : 0u; }
+
+// The ordered sum of a lane's residual: tm(s, ld()) for s = 0 .. n-1 in ASCENDING s, each exactly once and none for s >= n, so a
+// functor that accumulates performs the operations of the plain loop in its order (no padding term: a 0 * inf or a -0 would
+// change bits).  ld() returns the memory operand(s) of the next term and steps its own running address; tm() adds the term.
+// The plain loop around a lane read (a convergent operation) with a run-time trip count is not unrolled by the compiler, and
+// every trip then waits for its own load: n DEPENDENT round trips to the L2.  Here the loads of a piece are all issued before
+// its first add, and every loop has a constant trip count: whole batches of B terms while they last, then pieces of B/2 .. 1
+// chosen by the bits of the wave-uniform remainder -- at most log2(B) further round trips and never a load that is not used.
+// n must be wave-uniform where tm() reads lanes.
+#if defined(__clang__)      // (the host check is built by a compiler that does not know the pragma)
+#define CL_UNROLL _Pragma("unroll")
+#define CL_NO_UNROLL _Pragma("unroll 1")
+#else
+#define CL_UNROLL
+#define CL_NO_UNROLL
+#endif
+template <int N, class LD, class TM>
+TTX_HD void cl_sum_piece(int s0, LD &ld, TM &tm)
+{
+    decltype(ld()) v[N];
+    CL_UNROLL
+    for (int k = 0; k < N; k++) v[k] = ld();
+    CL_UNROLL
+    for (int k = 0; k < N; k++) tm(s0 + k, v[k]);
+}
+template <int B, class LD, class TM>
+TTX_HD void cl_ordered_sum(int n, LD ld, TM tm)
+{
+    static_assert(B == 16 || B == 8, "batches of 16 or 8 terms");
+    int s = 0;
+    CL_NO_UNROLL
+    for (; s + B <= n; s += B) cl_sum_piece<B>(s, ld, tm);
+    const int rem = n - s;
+    if constexpr (B > 8) if (rem & 8) { cl_sum_piece<8>(s, ld, tm); s += 8; }
+    if (rem & 4) { cl_sum_piece<4>(s, ld, tm); s += 4; }
+    if (rem & 2) { cl_sum_piece<2>(s, ld, tm); s += 2; }
+    if (rem & 1) cl_sum_piece<1>(s, ld, tm);
+}
