@@ -379,6 +379,55 @@ int ttx_mode_apply    (ttx_engine *h, const int32_t *m /* [d] */, const double *
 int ttx_mode_apply_dev(ttx_engine *h, const int32_t *m, const double *A_dev, int32_t mode, ttx_engine **out);
 int ttx_mode_apply_last(const ttx_engine *h, double *ms, double *bytes_read, double *bytes_written, double *flops, int32_t *mode_ran);
 
+/* The resident train in a function basis at a batch of REAL points, on the device (ttcross_amd/csrc/ttx_basis.h):
+ *   f(x_p) = sum_i T(i_1 .. i_d) prod_m phi_(m, i_m)(x_(p, m)),
+ * e.g. the density behind a train of COS-method coefficients (test_crs_coscoeff) or the piecewise-linear interpolant of a train of
+ * grid values, at scattered points.  The train is not modified; no core crosses the host link.
+ * Definition (numpy restates it: tests/basis_ref.py).  phi_m(p, :) is the table row of mode m and point p, n_m numbers.  The chain
+ * runs from the last mode to the first, as dtt_ijk does:
+ *   x = (1);  for mode i = d .. 1:  t_j(a) = sum_k U_i(a, j, k) x(k), summed from 0.0 over ascending k;
+ *                                   z(a) = sum_j phi_j t_j(a),        summed from 0.0 over ascending j;   x = z;
+ *   the value is z(1) after mode 1.  Multiply and add are always separate (the library is built with -ffp-contract=off).
+ * With unit vectors for phi this is the chain of ttx_ijk_batch(.., TTX_EVAL_EXACT): 0.0 + 1.0 * t adds nothing to it.
+ *   mode : TTX_EVAL_EXACT  the definition's operation order, one wave per point: bit-identical to the numpy restatement
+ *          TTX_EVAL_MFMA   one chain step is the GEMM of the unfolded core r0 x (n r1) with the row-wise Kronecker product
+ *                          phi_j(p) x_k(p), on the fp64 matrix cores: equal to EXACT to rounding.  A point's value depends on its
+ *                          own table rows only, never on its neighbours, the chunk or npts; a call repeats bit for bit
+ *          TTX_EVAL_AUTO   the engine chooses by the flops of the call (ttx_basis_last tells what ran)
+ * Tables.  ttx_basis_batch forms them on the device from a ttx_basis per mode:
+ *   TTX_BASIS_COS     y = (x - a) * w with w = pi / (b - a) (pi = 3.14159265358979323846); arg_j = (double)j * y;
+ *                     phi_j = the project's own cosine (ttx_cos of ttcross_amd/csrc/ttx_coscoeff.h) of arg_j; phi_0 is multiplied by 0.5
+ *                     with TTX_BASIS_HALVE_FIRST.  A non-finite coordinate or |arg_j| > 2^19 (TTX_TRIG_MAX) makes that phi_j NaN: the
+ *                     point's value is NaN, the other points are untouched.
+ *   TTX_BASIS_LINEAR  hat functions on n strictly ascending nodes t: n = 1: phi_0 = 1; x <= t_0: phi_0 = 1; x >= t_(n-1):
+ *                     phi_(n-1) = 1; otherwise with i the last node with t_i <= x: lambda = (x - t_i) / (t_(i+1) - t_i),
+ *                     phi_(i+1) = lambda, phi_i = 1.0 - lambda; every other entry 0.  A NaN coordinate gives a NaN row.  The table
+ *                     is summed densely like any other (a two-term path is open).
+ * ttx_basis_host writes the same tables on the host (no engine, no GPU): phi[j + n p] = phi_j(x[ldx p]); the device tables equal it
+ * bit for bit.  ttx_basis_tab takes the caller's own tables, npts rows of sum n(k) numbers, mode 1 first.
+ * The _dev entries take pointers on the engine's device, enqueue on the engine's stream and synchronise before they return;
+ * ttx_basis_tab_dev reads the caller's table in place.  The basis descriptors (and their nodes) are always host memory.
+ * Batches run in chunks of TTX_BASIS_CHUNK points (environment; default 2^18, 2^17 above maxrank 64); ttx_basis_tab stages at most
+ * 2^25 table entries of host rows at a time.  The work space is the engine's own.
+ * npts = 0 succeeds and launches nothing.  TTX_EINVAL: a null pointer with npts > 0, npts < 0, an unknown mode, an unknown kind,
+ * b <= a or a non-finite a or b, nodes that are missing, not finite or not strictly ascending, ranks above 128.  TTX_ESTATE: no
+ * train.  The engines are those ttx_ijk_batch takes: a multi-process engine is refused.
+ * ttx_basis_last: of the last call on this engine, the milliseconds (HIP events) of the table launches and of the chain launches,
+ * flops = 2 npts sum r(k-1) n(k) r(k), and the mode that ran (-1: none yet).  Any pointer may be NULL.
+ * Open: the two-term LINEAR path, complex tables, derivative tables (gradients), ranks above 128.
+ * Added without a new ttx_version: look the symbols up. */
+#define TTX_BASIS_COS    1   /* phi_j(x) = c_j cos(j pi (x - a)/(b - a)), j = 0..n-1; c_0 = 0.5 with TTX_BASIS_HALVE_FIRST, else 1 */
+#define TTX_BASIS_LINEAR 2   /* hat functions on n strictly ascending nodes */
+#define TTX_BASIS_HALVE_FIRST 1
+typedef struct { int32_t kind, flags; double a, b; const double *nodes /* host, [n(k)], LINEAR only */; } ttx_basis;
+
+int ttx_basis_batch    (ttx_engine *h, int64_t npts, const double *x /* [npts][d] */, const ttx_basis *basis /* [d] */, double *out, int32_t mode);
+int ttx_basis_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, double *out_dev, int32_t mode);
+int ttx_basis_tab      (ttx_engine *h, int64_t npts, const double *phi /* [npts][sum n(k)], mode 1 first */, double *out, int32_t mode);
+int ttx_basis_tab_dev  (ttx_engine *h, int64_t npts, const double *phi_dev, double *out_dev, int32_t mode);
+int ttx_basis_host     (const ttx_basis *b, int32_t n, int64_t npts, const double *x, int64_t ldx, double *phi /* [npts][n] */);   /* no engine, no GPU */
+int ttx_basis_last     (const ttx_engine *h, double *ms_table, double *ms_chain, double *flops, int32_t *mode_ran);
+
 /* Samples drawn from the resident train by sequential conditional sampling, on the device (ttcross_amd/csrc/ttx_sample.h).
  * Modes are 1-based, G_k is core k, r_0 = r_d = 1.
  *   u     : npts rows of d uniforms, row-major [npts][d]; u_k draws mode k

@@ -50,6 +50,7 @@ static cluster_kernel_t cluster_kernel(int var)
 #include "ttx_eval.h"
 #include "ttx_contract.h"
 #include "ttx_modeapply.h"
+#include "ttx_basis.h"
 #include "ttx_algebra.h"
 #include "ttx_roundsum.h"
 #include "ttx_sample.h"
@@ -134,6 +135,7 @@ enum {
     SC_KREC, SC_KSEL, SC_KOUT,          // ttx_topk: the kept positions of every mode, the selection's state (words, chunk counts, histogram), the rows before and after the ordering
     SC_RSO, SC_RSW, SC_RSYA, SC_RSYB,   // ttx_lincomb_round: the sketch train Omega, the stacked W of all bonds, the two Y buffers
     SC_RSM, SC_RSTAB,                   // ttx_lincomb_round: M = Q^T Y (first the coefficients), the descriptor tables (RsBlk) and Omega's offsets
+    SC_BTAB,                            // ttx_basis_batch: the table of one mode for one chunk, chunk x max n (its states go to SC_XA / SC_XB, its nodes to SC_META)
     SC_NBUF
 };
 struct EvBuf { void *p = nullptr; size_t bytes = 0; };
@@ -253,6 +255,9 @@ struct ttx_engine {
     std::vector<int32_t> rs_l;                                                  // its sketch ranks l(0 .. d)
     int rs_mode = -1;
     std::vector<hipEvent_t> rs_ev;                                              // the event chain of its left-to-right pass (RsMarks)
+    double bs_ms_tab = 0.0, bs_ms_chain = 0.0, bs_flops = 0.0;                 // the last ttx_basis_batch / ttx_basis_tab: table launches, chain launches
+    int bs_mode = -1;
+    std::vector<hipEvent_t> bs_ev;                                              // its event chain: tables and chain steps alternate (bs_mark)
 };
 
 // the process-wide pool of the host integrand (ttx_host_pool.h): engines driven from different host threads take turns on it
@@ -747,6 +752,7 @@ extern "C" void ttx_destroy(ttx_engine *h)
     }
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
     for (auto &e : h->rs_ev) (void)hipEventDestroy(e);
+    for (auto &e : h->bs_ev) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -3645,7 +3651,189 @@ extern "C" int ttx_mode_apply_last(const ttx_engine *h, double *ms, double *byte
     return TTX_OK;
 }
 
-// ---- the largest elements of the resident train (ttx_topk.h) --------------------------------------------------------------------
+// ---- the train in a function basis at real points (ttx_basis.h) ------------------------------------------------------------------
+// one mode's descriptor as the header states it: a known kind, a < b both finite, n finite strictly ascending nodes
+static int bs_check_one(const char *who, int k, const ttx_basis &b, int n)
+{
+    if (b.kind == TTX_BASIS_COS) {
+        if (!std::isfinite(b.a) || !std::isfinite(b.b) || !(b.a < b.b)) return fail(TTX_EINVAL, "%s: mode %d: a finite interval a < b expected (got %g, %g)", who, k, b.a, b.b);
+        return TTX_OK;
+    }
+    if (b.kind != TTX_BASIS_LINEAR) return fail(TTX_EINVAL, "%s: mode %d: unknown basis kind %d", who, k, b.kind);
+    if (!b.nodes) return fail(TTX_EINVAL, "%s: mode %d: TTX_BASIS_LINEAR without nodes", who, k);
+    for (int j = 0; j < n; j++) {
+        if (!std::isfinite(b.nodes[j])) return fail(TTX_EINVAL, "%s: mode %d: node %d is not finite", who, k, j);
+        if (j && !(b.nodes[j - 1] < b.nodes[j])) return fail(TTX_EINVAL, "%s: mode %d: the nodes are not strictly ascending at %d", who, k, j);
+    }
+    return TTX_OK;
+}
+extern "C" int ttx_basis_host(const ttx_basis *b, int32_t n, int64_t npts, const double *x, int64_t ldx, double *phi)
+{
+    const char *who = "ttx_basis_host";
+    if (!b || n < 1 || npts < 0 || ldx < 1 || (npts > 0 && (!x || !phi))) return fail(TTX_EINVAL, "%s: null argument, n < 1, npts < 0 or ldx < 1", who);
+    if (int rc = bs_check_one(who, 1, *b, n)) return rc;
+    const double w = b->kind == TTX_BASIS_COS ? ttx_basis_cos_w(b->a, b->b) : 0.0;
+    for (int64_t p = 0; p < npts; p++)
+        for (int j = 0; j < n; j++) phi[(size_t)p * n + j] = ttx_basis_entry(b->kind, b->flags, b->a, w, b->nodes, n, x[(size_t)p * ldx], j);
+    return TTX_OK;
+}
+// the event chain of a call: every launch is followed by a mark that carries the launch's kind (0 table, 1 chain step, 2 neither)
+struct BsMarks {
+    ttx_engine *h;
+    size_t used = 0;
+    std::vector<char> kind;
+    int mark(int k)
+    {
+        if (used == h->bs_ev.size()) { hipEvent_t e; HIPCHECK(hipEventCreate(&e)); h->bs_ev.push_back(e); }
+        HIPCHECK(hipEventRecord(h->bs_ev[used++], h->stream));
+        kind.push_back((char)k);
+        return TTX_OK;
+    }
+    int collect()                           // after a synchronise
+    {
+        for (size_t t = 1; t < used; t++) {
+            if (kind[t] == 2) continue;
+            float ms = 0.f;
+            HIPCHECK(hipEventElapsedTime(&ms, h->bs_ev[t - 1], h->bs_ev[t]));
+            (kind[t] == 0 ? h->bs_ms_tab : h->bs_ms_chain) += ms;
+        }
+        used = 0; kind.clear();
+        return TTX_OK;
+    }
+};
+template <int MR>
+static void bs_gemm_launch(ttx_engine *h, const EvTrain &T, int i, int c, const double *phi, size_t ldphi, const double *X, double *Z, double *out)
+{
+    constexpr int TP = 64 * bs_ct(MR);
+    hipLaunchKernelGGL(k_bs_gemm<MR>, dim3((c + TP - 1) / TP), dim3(256), bs_gemm_lds(h->rfinal[i]), h->stream, T, i, c, phi, ldphi, X, Z, out);
+}
+enum BsSrc { BS_X_HOST, BS_X_DEV, BS_TAB_HOST, BS_TAB_DEV };
+static int bs_run(ttx_engine *h, const char *who, BsSrc src, int64_t npts, const double *in, const ttx_basis *basis, double *out, int32_t mode)
+{
+    const bool tab = src == BS_TAB_HOST || src == BS_TAB_DEV, dev = src == BS_X_DEV || src == BS_TAB_DEV;
+    int rc = tt_prepare(h, who);
+    if (rc) return rc;
+    if (npts < 0 || (npts > 0 && (!in || !out || (!tab && !basis)))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
+    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    const int d = h->d;
+    if (!tab && basis) for (int k = 1; k <= d; k++) if ((rc = bs_check_one(who, k, basis[k - 1], h->n1[k]))) return rc;
+    const int rmax = *std::max_element(h->rfinal.begin(), h->rfinal.begin() + d + 1);
+    if (rmax > 128) return fail(TTX_EINVAL, "%s: ranks up to 128 only (got %d)", who, rmax);
+    if (h->rfinal[0] != 1 || h->rfinal[d] != 1) return fail(TTX_EINVAL, "%s: boundary ranks are not 1", who);
+    double w = 0.0;
+    size_t sumn = 0, nmax = 1;
+    std::vector<size_t> off(d);
+    for (int k = 1; k <= d; k++) {
+        w += (double)h->rfinal[k - 1] * h->n1[k] * h->rfinal[k];
+        off[k - 1] = sumn; sumn += (size_t)h->n1[k]; nmax = std::max(nmax, (size_t)h->n1[k]);
+    }
+    const double flops = 2.0 * (double)npts * w;
+    const int eff = mode == TTX_EVAL_AUTO ? (flops >= TTX_BS_AUTO_FLOPS ? TTX_EVAL_MFMA : TTX_EVAL_EXACT) : mode;
+    h->bs_ms_tab = 0.0; h->bs_ms_chain = 0.0; h->bs_flops = flops; h->bs_mode = eff;
+    if (npts == 0) return TTX_OK;
+    EvTrain T;
+    if ((rc = ev_train(h, &T))) return rc;
+    size_t chunk = std::min<size_t>(env_chunk("TTX_BASIS_CHUNK", h->RM <= 64 ? (size_t)1 << 18 : (size_t)1 << 17), (size_t)npts);
+    if (src == BS_TAB_HOST) chunk = std::min(chunk, std::max<size_t>(1, ((size_t)1 << 25) / sumn));     // the staged rows of the caller's table
+    // the nodes of the LINEAR modes, one device block
+    std::vector<BsMode> M(d);
+    if (!tab) {
+        OpMeta meta(h->meta_host);
+        std::vector<size_t> o_nodes(d, 0);
+        for (int k = 0; k < d; k++)
+            if (basis[k].kind == TTX_BASIS_LINEAR) o_nodes[k] = meta.put(std::vector<double>(basis[k].nodes, basis[k].nodes + h->n1[k + 1]));
+        char *dm = nullptr;
+        if (!meta.host.empty() && (rc = meta.upload(h, SC_META, &dm))) return rc;
+        for (int k = 0; k < d; k++) {
+            const ttx_basis &b = basis[k];
+            const bool cosk = b.kind == TTX_BASIS_COS;
+            M[k] = BsMode{b.kind, b.flags, h->n1[k + 1], cosk ? b.a : 0.0, cosk ? ttx_basis_cos_w(b.a, b.b) : 0.0, cosk ? nullptr : (const double *)(dm + o_nodes[k])};
+        }
+    }
+    const size_t row = tab ? sumn : (size_t)d;                                  // doubles per point of the input
+    if ((rc = buf_reserve(h, SC_XA, sizeof(double) * chunk * T.ldx)) || (rc = buf_reserve(h, SC_XB, sizeof(double) * chunk * T.ldx))) return rc;
+    if (!tab && (rc = buf_reserve(h, SC_BTAB, sizeof(double) * chunk * nmax))) return rc;
+    if (!dev && ((rc = buf_reserve(h, SC_X, sizeof(double) * chunk * row)) || (rc = buf_reserve(h, SC_OUT, sizeof(double) * chunk)))) return rc;
+    double *btab = buf<double>(h, SC_BTAB), *sin_ = buf<double>(h, SC_X), *sout = buf<double>(h, SC_OUT);
+    const int ncu = dev_ncu(h);
+    BsMarks marks{h};
+    for (int64_t o = 0; o < npts; o += (int64_t)chunk) {
+        const int c = (int)std::min<int64_t>((int64_t)chunk, npts - o);
+        const double *cin = in + (size_t)o * row;
+        double *cout = out + o;
+        if (!dev) {
+            HIPCHECK(hipMemcpyAsync(sin_, cin, sizeof(double) * (size_t)c * row, hipMemcpyHostToDevice, h->stream));
+            cin = sin_; cout = sout;
+        }
+        double *X = buf<double>(h, SC_XA), *Z = buf<double>(h, SC_XB);
+        if ((rc = marks.mark(2))) return rc;
+        for (int i = d - 1; i >= 0; i--) {
+            const int q0 = h->rfinal[i], q1 = h->rfinal[i + 1];
+            const double *ph = cin + off[i];
+            size_t ld = sumn;
+            if (!tab) {
+                hipLaunchKernelGGL(k_bs_table, g1((size_t)c * M[i].n), dim3(256), 0, h->stream, M[i], (long long)c, cin + i, d, btab);
+                if ((rc = marks.mark(0))) return rc;
+                ph = btab; ld = (size_t)M[i].n;
+            }
+            const double *Xin = i == d - 1 ? nullptr : X;
+            double *o1 = i == 0 ? cout : nullptr;
+            if (eff == TTX_EVAL_EXACT) {
+                const int grid = (int)std::min<long long>(((long long)c + 3) / 4, (long long)ncu * 8);
+                hipLaunchKernelGGL(k_bs_exact, dim3(grid), dim3(256), 4 * sizeof(double) * (size_t)T.ldx, h->stream, T, i, (long long)c, ph, ld, Xin, Z, o1);
+            } else {
+                switch ((std::max(q0, q1) + 15) / 16) {
+                    case 1: bs_gemm_launch<1>(h, T, i, c, ph, ld, Xin, Z, o1); break;
+                    case 2: bs_gemm_launch<2>(h, T, i, c, ph, ld, Xin, Z, o1); break;
+                    case 3: bs_gemm_launch<3>(h, T, i, c, ph, ld, Xin, Z, o1); break;
+                    case 4: bs_gemm_launch<4>(h, T, i, c, ph, ld, Xin, Z, o1); break;
+                    case 5: bs_gemm_launch<5>(h, T, i, c, ph, ld, Xin, Z, o1); break;
+                    case 6: bs_gemm_launch<6>(h, T, i, c, ph, ld, Xin, Z, o1); break;
+                    case 7: bs_gemm_launch<7>(h, T, i, c, ph, ld, Xin, Z, o1); break;
+                    default: bs_gemm_launch<8>(h, T, i, c, ph, ld, Xin, Z, o1); break;
+                }
+            }
+            if ((rc = marks.mark(1))) return rc;
+            std::swap(X, Z);
+        }
+        if (!dev) HIPCHECK(hipMemcpyAsync(out + o, sout, sizeof(double) * (size_t)c, hipMemcpyDeviceToHost, h->stream));
+        if (!dev || marks.used > 4096) {                                        // the staging blocks are reused by the next chunk; the event chain stays short
+            HIPCHECK(hipStreamSynchronize(h->stream));
+            if ((rc = marks.collect())) return rc;
+        }
+    }
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    if ((rc = marks.collect())) return rc;
+    HIPCHECK(hipGetLastError());
+    return TTX_OK;
+}
+extern "C" int ttx_basis_batch(ttx_engine *h, int64_t npts, const double *x, const ttx_basis *basis, double *out, int32_t mode)
+{
+    return bs_run(h, "ttx_basis_batch", BS_X_HOST, npts, x, basis, out, mode);
+}
+extern "C" int ttx_basis_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, double *out_dev, int32_t mode)
+{
+    return bs_run(h, "ttx_basis_batch_dev", BS_X_DEV, npts, x_dev, basis, out_dev, mode);
+}
+extern "C" int ttx_basis_tab(ttx_engine *h, int64_t npts, const double *phi, double *out, int32_t mode)
+{
+    return bs_run(h, "ttx_basis_tab", BS_TAB_HOST, npts, phi, nullptr, out, mode);
+}
+extern "C" int ttx_basis_tab_dev(ttx_engine *h, int64_t npts, const double *phi_dev, double *out_dev, int32_t mode)
+{
+    return bs_run(h, "ttx_basis_tab_dev", BS_TAB_DEV, npts, phi_dev, nullptr, out_dev, mode);
+}
+extern "C" int ttx_basis_last(const ttx_engine *h, double *ms_table, double *ms_chain, double *flops, int32_t *mode_ran)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_basis_last: null engine");
+    if (ms_table) *ms_table = h->bs_ms_tab;
+    if (ms_chain) *ms_chain = h->bs_ms_chain;
+    if (flops) *flops = h->bs_flops;
+    if (mode_ran) *mode_ran = h->bs_mode;
+    return TTX_OK;
+}
+
+// ---- the largest elements of the resident train (ttx_topk.h)--------------------------------------------------------------------
 template <int MR>
 static int tk_score_mfma(ttx_engine *h, dim3 grid, size_t lds, const double *G, int r0, int r1, const double *P, int ldp, const double *X, int ldx, int C, int nI, int ifix,
                          int niper, int first, tk_u64 *S)

@@ -647,6 +647,86 @@ def run_modeapply(argv, device=0, tt=None):
     return res
 
 
+def basis_host(tt, x, basis):
+    """what a user does without ttx_basis_batch: every core to the host with core(k), the tables from basis_table, the chain of
+    include/ttx.h as one numpy product per mode (BLAS order, so equal to the device to rounding only)"""
+    from .engine import basis_table
+    x = np.asarray(x, dtype=np.float64)
+    if isinstance(basis, (tuple, list)) and basis and isinstance(basis[0], str):
+        basis = [basis] * tt.d
+    cores = [tt.core(k) for k in range(1, tt.d + 1)]
+    v = np.ones((x.shape[0], 1))
+    for k in range(tt.d - 1, -1, -1):
+        g = cores[k]
+        r0, n, r1 = g.shape
+        phi = basis_table(basis[k], n, x[:, k])
+        t = (v @ g.reshape(r0 * n, r1).T).reshape(x.shape[0], r0, n)
+        v = np.einsum("paj,pj->pa", t, phi)
+    return v[:, 0]
+
+
+def basis_train(workload, device=0):
+    """The train and the basis of a basis measurement: coscoeffD is a coscoeff_setup run of dimension D (n = 65, r = 20, piv = 1)
+    with its own [a, b] and the halved first term; everything else is a train of the tijk sub-command, None for its basis."""
+    if workload.startswith("coscoeff"):
+        s = coscoeff_setup(int(workload[8:]), 65)
+        tt = TTCross(s["n"], s["fun_id"], s["par"], 20, pivoting=1, accuracy=s["acc"], aux=s["aux"], device=device).run()
+        return tt, ("cos", float(s["aux"][-2]), float(s["aux"][-1]), True)
+    return tijk_train(workload, device=device), None
+
+
+def run_basis(argv, device=0, repeats=5, tt=None, basis=None, host_npts=1000):
+    """basis WORKLOAD NPTS [KIND] [MODE]: the trains of the tijk sub-command plus coscoeffD; KIND linear (default: hat functions on
+    n equidistant nodes of [0, 1]) or cos (on [0, 1]; coscoeffD always takes its own cosine basis); MODE exact, mfma or auto
+    (default).  NPTS seeded points drawn ON the device inside the basis' interval, one warm-up and `repeats` timed calls through
+    the device-pointer entry; prints one JSON line: the median milliseconds, flops, the chain's TF/s and the table share from
+    ttx_basis_last, and the host route (basis_host: every core pulled, numpy) on the first `host_npts` of the same points."""
+    import json
+    import time
+    import torch
+    torch.cuda.init()          # a torch that brings its own HIP runtime must initialise its device before the engine's library does
+    workload, npts = argv[0], int(float(argv[1]))
+    kind = argv[2] if len(argv) > 2 else "linear"
+    mode = argv[3] if len(argv) > 3 else "auto"
+    if tt is None:
+        tt, basis = basis_train(workload, device=device)
+    if basis is None:
+        basis = [("linear", np.linspace(0.0, 1.0, int(nk))) if kind == "linear" and nk > 1 else ("cos", 0.0, 1.0) for nk in tt._n]
+        lo, hi = 0.0, 1.0
+    else:
+        lo, hi = basis[1], basis[2]
+    dev = torch.device("cuda", device)
+    g = torch.Generator(device=dev)
+    g.manual_seed(20240607)
+    x = (lo + (hi - lo) * torch.rand((npts, tt.d), dtype=torch.float64, device=dev, generator=g)).contiguous()
+    torch.cuda.synchronize(dev)
+    out = tt.basis_batch(x, basis, mode)
+    ms, last = [], []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        out = tt.basis_batch(x, basis, mode)        # synchronises before it returns
+        ms.append((time.perf_counter() - t0) * 1e3)
+        last.append(tt.basis_last())
+    med = float(np.median(ms))
+    ch, tb = float(np.median([k["ms_chain"] for k in last])), float(np.median([k["ms_table"] for k in last]))
+    res = dict(workload=workload, npts=npts, kind=basis[0] if isinstance(basis[0], str) else kind, mode_asked=mode, mode=last[0]["mode"],
+               d=tt.d, max_rank=int(tt.ranks().max()), ms=med, ms_all=[round(v, 4) for v in ms], ms_chain=ch, ms_table=tb,
+               table_share=tb / (tb + ch) if tb + ch > 0 else None, flops=last[0]["flops"],
+               chain_tflops=last[0]["flops"] / (ch * 1e-3) / 1e12 if ch > 0 else None, checksum=float(out.sum().item()),
+               nan=int(torch.isnan(out).sum().item()))
+    hp = min(npts, host_npts)
+    if hp > 0:
+        xh = x[:hp].cpu().numpy()
+        t0 = time.perf_counter()
+        ref = basis_host(tt, xh, basis)
+        res["host_route_npts"] = hp
+        res["host_route_ms"] = (time.perf_counter() - t0) * 1e3
+        got = out[:hp].cpu().numpy()
+        res["max_rel_diff_to_host_route"] = float(np.max(np.abs(got - ref)) / max(float(np.max(np.abs(ref))), 1e-300))
+    print(json.dumps(res))
+    return tt, x, out, res
+
+
 def sample_host(tt, u, w=None):
     """what a user does without ttx_sample: every core to the host with core(k), then the conditional marginals walked in
     numpy from the last mode to the first.  Returns (ind, logq, val) of the definition in include/ttx.h, in numpy's own
@@ -895,6 +975,8 @@ if __name__ == "__main__":
         run_algebra(sys.argv[2:])
     elif sys.argv[1] == "modeapply":
         run_modeapply(sys.argv[2:])
+    elif sys.argv[1] == "basis":
+        run_basis(sys.argv[2:])
     elif sys.argv[1] == "chf":
         run_chf(sys.argv[2:])
     elif sys.argv[1] == "pdf":

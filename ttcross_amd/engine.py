@@ -24,6 +24,8 @@ TRAIN_OPS = {"product": TTX_TOP_PRODUCT, "ratio": TTX_TOP_RATIO, "sqrtabs": TTX_
 TTX_EVAL_EXACT, TTX_EVAL_MFMA, TTX_EVAL_AUTO = 0, 1, 2
 EVAL_MODES = {"exact": TTX_EVAL_EXACT, "mfma": TTX_EVAL_MFMA, "auto": TTX_EVAL_AUTO}
 TOPK_WHICH = {"abs": 0, "max": 1, "min": 2}
+TTX_BASIS_COS, TTX_BASIS_LINEAR, TTX_BASIS_HALVE_FIRST = 1, 2, 1
+BASIS_KINDS = {"cos": TTX_BASIS_COS, "linear": TTX_BASIS_LINEAR}
 K_NAMES = ("lottery", "halfstep", "accept", "exchange", "quad", "other")
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -52,6 +54,10 @@ _ALLREDUCE = ctypes.CFUNCTYPE(ctypes.c_int, c_void_p, POINTER(c_double), c_int64
 
 class _Transport(ctypes.Structure):
     _fields_ = [("ctx", c_void_p), ("sendrecv", _SENDRECV), ("allreduce", _ALLREDUCE)]
+
+
+class _Basis(ctypes.Structure):      # ttx_basis
+    _fields_ = [("kind", c_int32), ("flags", c_int32), ("a", c_double), ("b", c_double), ("nodes", POINTER(c_double))]
 
 
 class SweepRec(ctypes.Structure):
@@ -115,6 +121,12 @@ def load_library():
     L.ttx_mode_apply.argtypes = [c_void_p, POINTER(c_int32), POINTER(c_double), c_int32, POINTER(c_void_p)]
     L.ttx_mode_apply_dev.argtypes = [c_void_p, POINTER(c_int32), c_void_p, c_int32, POINTER(c_void_p)]
     L.ttx_mode_apply_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
+    L.ttx_basis_batch.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(_Basis), POINTER(c_double), c_int32]
+    L.ttx_basis_batch_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(_Basis), c_void_p, c_int32]
+    L.ttx_basis_tab.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), c_int32]
+    L.ttx_basis_tab_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_int32]
+    L.ttx_basis_host.argtypes = [POINTER(_Basis), c_int32, c_int64, POINTER(c_double), c_int64, POINTER(c_double)]
+    L.ttx_basis_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
     L.ttx_sample.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
     L.ttx_sample_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(c_double), POINTER(c_int32), c_void_p, c_void_p, c_void_p]
     L.ttx_sample_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
@@ -200,6 +212,33 @@ def _eval_mode(mode):
     if mode in EVAL_MODES.values():
         return int(mode)
     raise ValueError(f"mode must be one of {sorted(EVAL_MODES)} (got {mode!r})")
+
+
+def _basis_struct(entry, n):
+    """one basis entry, ("cos", a, b[, halve_first]) or ("linear", nodes) for a mode of n indices -> (ttx_basis, what it points to)"""
+    if not isinstance(entry, (tuple, list)) or not entry or entry[0] not in BASIS_KINDS:
+        raise ValueError(f'basis: ("cos", a, b[, halve_first]) or ("linear", nodes) expected (got {entry!r})')
+    if entry[0] == "cos":
+        if len(entry) not in (3, 4):
+            raise ValueError(f'basis: ("cos", a, b[, halve_first]) expected (got {entry!r})')
+        flags = TTX_BASIS_HALVE_FIRST if len(entry) == 4 and entry[3] else 0
+        return _Basis(TTX_BASIS_COS, flags, float(entry[1]), float(entry[2]), None), None
+    if len(entry) != 2:
+        raise ValueError(f'basis: ("linear", nodes) expected (got {entry!r})')
+    nodes = np.ascontiguousarray(entry[1], dtype=np.float64)
+    if nodes.ndim != 1 or nodes.size != int(n):
+        raise ValueError(f"basis: {int(n)} nodes expected for a mode of {int(n)} indices (got shape {nodes.shape})")
+    return _Basis(TTX_BASIS_LINEAR, 0, 0.0, 0.0, _dp(nodes)), nodes
+
+
+def basis_table(entry, n, x):
+    """The table of one mode on the host (include/ttx.h: ttx_basis_host): phi[p, j] = phi_j(x[p]), j = 0..n-1, for a basis entry
+    ("cos", a, b[, halve_first]) or ("linear", nodes).  The device forms the same numbers bit for bit.  No engine, no GPU."""
+    b, _keep = _basis_struct(entry, n)
+    xa = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    phi = np.zeros((xa.size, int(n)))
+    _check(load_library().ttx_basis_host(ctypes.byref(b), int(n), xa.size, _dp(xa), 1, _dp(phi)))
+    return phi
 
 
 def roundsum_omega(seed, k, shape):
@@ -803,6 +842,73 @@ class TTCross:
         _check(load_library().ttx_mode_apply_last(self._h, ctypes.byref(ms), ctypes.byref(rd), ctypes.byref(wr), ctypes.byref(fl), ctypes.byref(md)))
         names = {v: k for k, v in EVAL_MODES.items()}
         return dict(ms=ms.value, bytes_read=rd.value, bytes_written=wr.value, flops=fl.value, mode=names.get(md.value))
+
+    # ---- the train in a function basis at real points (include/ttx.h: ttx_basis_batch) -------------------
+    def _dev_pair(self, who, t, cols):
+        """a float64 torch tensor (npts, cols) on the engine's device and the tensor of its values; None for anything else"""
+        if type(t).__module__.split(".")[0] != "torch" or not t.is_cuda:
+            return None
+        import torch
+        if t.device.index != self.device:
+            raise ValueError(f"{who}: the tensor lies on {t.device}, the engine on device {self.device}")
+        if t.dtype != torch.float64 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != cols:
+            raise ValueError(f"{who}: a contiguous float64 tensor of shape (npts, {cols}) expected")
+        out = torch.empty(t.shape[0], dtype=torch.float64, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()            # the engine runs on a stream of its own
+        return out
+
+    def basis_batch(self, x, basis, mode="auto"):
+        """f(x_p) = sum_i T(i) prod_m phi_(m, i_m)(x[p, m]) at real points x (npts, d) (include/ttx.h: ttx_basis_batch).  basis: a
+        list of d entries ("cos", a, b[, halve_first]) or ("linear", nodes), or one entry for all modes; the tables are formed on
+        the device (basis_table gives the same numbers on the host).  mode "exact", "mfma" or "auto"; basis_last() tells what ran.
+        A host array gives a numpy array; a contiguous float64 torch tensor on the engine's device goes by pointer
+        (ttx_basis_batch_dev) and gives a tensor on that device."""
+        L, md = load_library(), _eval_mode(mode)
+        if isinstance(basis, (tuple, list)) and basis and isinstance(basis[0], str):
+            basis = [basis] * self.d
+        basis = list(basis)
+        if len(basis) != self.d:
+            raise ValueError(f"basis_batch: {self.d} basis entries expected (got {len(basis)})")
+        pairs = [_basis_struct(e, self._n[k]) for k, e in enumerate(basis)]
+        arr = (_Basis * self.d)(*[p[0] for p in pairs])          # pairs keeps the node arrays alive
+        out = self._dev_pair("basis_batch", x, self.d)
+        if out is not None:
+            _check(L.ttx_basis_batch_dev(self._h, x.shape[0], c_void_p(x.data_ptr()), arr, c_void_p(out.data_ptr()), md))
+            return out
+        if type(x).__module__.split(".")[0] == "torch":
+            x = x.numpy()
+        xa = np.ascontiguousarray(x, dtype=np.float64)
+        if xa.ndim != 2 or xa.shape[1] != self.d:
+            raise ValueError(f"basis_batch: an array of shape (npts, {self.d}) expected")
+        res = np.zeros(xa.shape[0])
+        _check(L.ttx_basis_batch(self._h, xa.shape[0], _dp(xa), arr, _dp(res), md))
+        return res
+
+    def basis_tab(self, phi, mode="auto"):
+        """The same with the caller's own tables (include/ttx.h: ttx_basis_tab): phi (npts, sum n), the n(k) numbers of mode 1
+        first.  Host arrays and torch tensors on the engine's device (read in place, ttx_basis_tab_dev) as for basis_batch."""
+        L, md = load_library(), _eval_mode(mode)
+        sumn = int(self._n.sum())
+        out = self._dev_pair("basis_tab", phi, sumn)
+        if out is not None:
+            _check(L.ttx_basis_tab_dev(self._h, phi.shape[0], c_void_p(phi.data_ptr()), c_void_p(out.data_ptr()), md))
+            return out
+        if type(phi).__module__.split(".")[0] == "torch":
+            phi = phi.numpy()
+        pa = np.ascontiguousarray(phi, dtype=np.float64)
+        if pa.ndim != 2 or pa.shape[1] != sumn:
+            raise ValueError(f"basis_tab: an array of shape (npts, {sumn}) expected")
+        res = np.zeros(pa.shape[0])
+        _check(L.ttx_basis_tab(self._h, pa.shape[0], _dp(pa), _dp(res), md))
+        return res
+
+    def basis_last(self):
+        """dict(ms_table, ms_chain, flops, mode) of the last basis_batch / basis_tab on this engine (include/ttx.h: ttx_basis_last);
+        mode is "exact" or "mfma" (None before the first call)"""
+        mt, mc, fl, md = c_double(), c_double(), c_double(), c_int32()
+        _check(load_library().ttx_basis_last(self._h, ctypes.byref(mt), ctypes.byref(mc), ctypes.byref(fl), ctypes.byref(md)))
+        names = {v: k for k, v in EVAL_MODES.items()}
+        return dict(ms_table=mt.value, ms_chain=mc.value, flops=fl.value, mode=names.get(md.value))
 
     # ---- samples from the resident train (include/ttx.h: ttx_sample) -------------------------------------
     def sample(self, u_or_npts, w=None, fixed=None, seed=None, want=("ind", "logq", "val")):

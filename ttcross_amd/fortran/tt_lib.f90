@@ -69,6 +69,8 @@ module tt_lib
  interface marginals;   module procedure dtt_marginals; end interface
  ! matrices applied to chosen modes on the device (not in the reference): modeapply(arg,m,a,res,mode)
  interface modeapply;   module procedure dtt_modeapply; end interface
+ ! the train in a function basis at real points on the device (not in the reference): basisval(arg,x,kind,a,b,res,mode,halve)
+ interface basisval;    module procedure dtt_basisval; end interface
  ! samples drawn from the train on the device (not in the reference): sample(arg,u,ind,w,fixed,logq,val)
  interface sample;      module procedure dtt_sample;    end interface
  ! the largest elements of the train with a bound on the rest, on the device (not in the reference): topk(arg,k,ind,val,bound,which,fixed,mode)
@@ -420,6 +422,44 @@ contains
    res%n(k)=arg%n(k); if(m(k).gt.0)res%n(k)=m(k)
   end do
   res%ttx=hn; call dtt_pull(res)
+ end subroutine
+ subroutine dtt_basisval(arg,x,kind,a,b,res,mode,halve)
+  ! res(p) = sum_i arg(i) prod_k phi_(i_k)(x(k,p)): the train in one function basis on all modes at the real points x(m,npts).
+  ! kind 1: phi_j(t) = cos(j pi (t-a)/(b-a)), j = 0..n(k)-1, the first term halved where halve is present and true (a train of
+  ! COS-method coefficients gives its density); kind 2: hat functions on n(k) equidistant nodes a + (b-a)(j-1)/(n(k)-1) (a train
+  ! of grid values gives its piecewise-linear interpolant, constant outside [a,b]).  mode: 0 the definition's operation order, 1 the
+  ! fp64 matrix cores, 2 (the default) the engine chooses.  One call on the device (ttx_basis_batch); a host train is staged for
+  ! the call like for norm / dot_product.
+  use ttx_c
+  type(dtt),intent(in) :: arg
+  double precision,intent(in) :: x(:,:)
+  integer,intent(in) :: kind
+  double precision,intent(in) :: a,b
+  double precision,intent(out) :: res(:)
+  integer,intent(in),optional :: mode
+  logical,intent(in),optional :: halve
+  type(ttx_basis_t) :: bs(tt_size)
+  real(c_double),allocatable,target :: nodes(:,:)
+  real(c_double),allocatable :: xx(:,:)
+  integer(c_int32_t) :: md
+  type(c_ptr) :: h
+  logical :: temp
+  integer :: k,j
+  if(size(x,2).eq.0)return
+  md=2; if(present(mode))md=mode
+  allocate(nodes(maxval(arg%n(1:arg%m)),arg%m),xx(arg%m,size(x,2))); xx=x(1:arg%m,:)
+  do k=1,arg%m
+   bs(k)%kind=kind; bs(k)%flags=0; bs(k)%a=a; bs(k)%b=b; bs(k)%nodes=c_null_ptr
+   if(present(halve))then; if(halve)bs(k)%flags=TTX_BASIS_HALVE_FIRST; endif
+   if(kind.eq.TTX_BASIS_LINEAR)then
+    do j=1,arg%n(k); nodes(j,k)=a+(b-a)*dble(j-1)/dble(max(arg%n(k)-1,1)); end do
+    bs(k)%nodes=c_loc(nodes(1,k))
+   end if
+  end do
+  call dtt_stage(arg,h,temp,'dtt_basisval')
+  call ttx_check(ttx_basis_batch(h,int(size(x,2),c_int64_t),xx,bs,res,md),'dtt_basisval')
+  if(temp)call ttx_destroy(h)
+  deallocate(nodes,xx)
  end subroutine
  subroutine dtt_marginals(arg,marg,w)
   ! marg(i,k), i = 1..n(k): arg summed over every mode but k against the weights (w absent: plain sums); marg has at least

@@ -5,6 +5,12 @@ module ttx_c
  implicit none
  integer(c_int32_t),parameter :: TTX_FUN_ISING=1, TTX_FUN_STDNORM=2, TTX_FUN_MVN=3, TTX_FUN_HOST=4, TTX_FUN_COSCOEFF=5, TTX_FUN_DEVICE=6, TTX_FUN_TRAINS=7
  integer(c_int32_t),parameter :: TTX_TRAINS_MAX=8, TTX_TOP_PRODUCT=1, TTX_TOP_RATIO=2, TTX_TOP_SQRTABS=3, TTX_TOP_DEVICE=4
+ integer(c_int32_t),parameter :: TTX_BASIS_COS=1, TTX_BASIS_LINEAR=2, TTX_BASIS_HALVE_FIRST=1
+ type,bind(C) :: ttx_basis_t            ! ttx_basis: one mode's basis; nodes = c_loc of n(k) ascending nodes (LINEAR) or c_null_ptr
+  integer(c_int32_t) :: kind,flags
+  real(c_double) :: a,b
+  type(c_ptr) :: nodes
+ end type
  type,bind(C) :: ttx_config
   integer(c_int32_t) :: d
   type(c_ptr) :: n
@@ -161,6 +167,14 @@ module ttx_c
   end function
   function ttx_mode_apply_last(h,ms,bytes_read,bytes_written,flops,mode_ran) bind(C,name='ttx_mode_apply_last') result(rc)
    import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms,bytes_read,bytes_written,flops; integer(c_int32_t),intent(out) :: mode_ran; integer(c_int) :: rc
+  end function
+  ! the train in a function basis at real points (include/ttx.h): x(d,npts), basis(d) of type ttx_basis_t; mode 0 / 1 / 2
+  function ttx_basis_batch(h,npts,x,basis,out,mode) bind(C,name='ttx_basis_batch') result(rc)
+   import; type(c_ptr),value :: h; integer(c_int64_t),value :: npts; real(c_double),intent(in) :: x(*); type(ttx_basis_t),intent(in) :: basis(*)
+   real(c_double),intent(out) :: out(*); integer(c_int32_t),value :: mode; integer(c_int) :: rc
+  end function
+  function ttx_basis_last(h,ms_table,ms_chain,flops,mode_ran) bind(C,name='ttx_basis_last') result(rc)
+   import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms_table,ms_chain,flops; integer(c_int32_t),intent(out) :: mode_ran; integer(c_int) :: rc
   end function
   ! samples drawn from the resident train (include/ttx.h); u(d,npts), ind(d,npts); w, fixed, logq, val: c_null_ptr where not wanted
   function ttx_sample(h,npts,u,w,fixed,ind,logq,val) bind(C,name='ttx_sample') result(rc)
