@@ -473,6 +473,64 @@ int ttx_sample(ttx_engine *h, int64_t npts, const double *u /* [npts][d] */, con
 int ttx_sample_dev(ttx_engine *h, int64_t npts, const double *u, const double *w, const int32_t *fixed, int32_t *ind, double *logq, double *val);
 int ttx_sample_last(const ttx_engine *h, double *ms_head, double *bytes_head, double *ms_draw, int64_t *nfailed);
 
+/* REAL-valued samples drawn from the piecewise-linear interpolant of a resident train of grid values, on the device
+ * (ttcross_amd/csrc/ttx_sample_real.h): the inverse Rosenblatt transform of the interpolant that ttx_basis_batch evaluates with
+ * TTX_BASIS_LINEAR, the conditional-distribution sampler of Dolgov, Anaya-Izquierdo, Fox and Scheichl (2020).  Uniforms in
+ * [0, 1]^d go in; real points, the log-density of the proposal and the interpolant's value come out; no core leaves the device.
+ * Modes are 1-based, G_k is core k, t_k are the n_k strictly ascending nodes of mode k, r_0 = r_d = 1.
+ *   u     : npts rows of d uniforms, row-major [npts][d]; u_k draws mode k
+ *   nodes : d host pointers, row k holds the n_k nodes of mode k
+ *   cond  : d entries or NULL.  NaN (or cond NULL): the mode is drawn; finite: the mode is HELD at that real coordinate, on a node,
+ *           between nodes or outside the node range alike (its u_k is not looked at).  A mode with n_k = 1 is always held (at its
+ *           node, or at cond_k where that is finite: its hat row is (1) either way)
+ *   x     : [npts][d] the samples;  cell : [npts][d] or NULL, the 1-based cell of a drawn mode, 0 for a held one;
+ *   logq, val : [npts], each may be NULL
+ * Definition (numpy restates it: tests/sample_real_ref.py).  phi_k(x) is the row of TTX_BASIS_LINEAR at x by the rule above
+ * (ttx_basis_host is its restatement).  Effective weights e_k: for a drawn mode the trapezoid weights of the nodes, om(0) = 0.5 (t_1 -
+ * t_0), om(i) = 0.5 (t_(i+1) - t_(i-1)), om(n-1) = 0.5 (t_(n-1) - t_(n-2)); for a held mode phi_k(cond_k).  Prefix vectors l_0 = [1],
+ * l_k = l_(k-1) M_k with M_k = sum_i e_k(i) G_k(:, i, :), formed by the kernels of ttx_marginals in their summation order, as for
+ * ttx_sample.  Head table of a drawn mode: H_k(i, b) = sum_a l_(k-1)(a) G_k(a, i, b), ttx_sample's with weights of 1.0.
+ * Draw.  x_(d+1) = [1]; for k = d .. 1 of a drawn mode, with h_j = t_(j+1) - t_j:
+ *   p(i) = |sum_b H_k(i, b) x_(k+1)(b)|  (ascending b from 0.0, separate multiply and add), i = 0 .. n-1: the nodal conditional
+ *   A(j) = (0.5 * (p(j) + p(j+1))) * h_j, j = 0 .. n-2: the mass of cell j under the interpolated conditional
+ *   C    = the inclusive running sum of A in ttx_sample's association order (blocks of 64, six doubling steps inside a block)
+ *   T = u_k * C(n-2);  j = the smallest cell with A(j) > 0 and T < C(j).  If there is none, or u_k >= 1: the largest cell with
+ *   A > 0 and lambda = 1.  Otherwise s = min(max(T - C(j-1), 0), A(j)) (C(-1) = 0), s' = s / h_j, D = p(j+1) - p(j),
+ *   disc = max(p(j) * p(j) + (2 * D) * s', 0), den = p(j) + sqrt(disc), lambda = den > 0 ? (2 * s') / den : 0, clamped to [0, 1]:
+ *   the root of p(j) l + D l^2 / 2 = s' in the form that has no cancellation.  p(j), p(j+1) and s' are first multiplied by the
+ *   power of two that takes max(p(j), p(j+1)) into [0.5, 1): exact, and the same bits wherever p(j)^2 neither under- nor overflows.
+ *   x_k = t_j + lambda * h_j, clamped to [t_j, t_(j+1)];  cell = j + 1.
+ * Chain step, all modes.  phi = phi_k(x_k) is formed again from the rounded x_k by the basis rule (for a held mode x_k = cond_k); where
+ * x_k rounded onto the node t_(j+1) it therefore names cell j + 1.  With i, i + 1 the at most two nonzero entries (i the rule's cell,
+ * at most n_k - 2):  z(a) = (0.0 + phi_i * tau_i(a)) + phi_(i+1) * tau_(i+1)(a),  tau_i(a) = sum_b G_k(a, i, b) x_(k+1)(b) in the
+ * operation sequence of TTX_EVAL_EXACT;  x_k-state = z.  For a finite train this is ttx_basis_batch's TTX_EVAL_EXACT chain, whose
+ * other terms are products with 0.0.  The log term of a drawn mode is log((phi_i * p(i) + phi_(i+1) * p(i+1)) / C(n-2)).
+ * Outputs: x; cell; logq = the sum of the log terms over the drawn modes, k = d .. 1: the log of the proposal's density at x with
+ * respect to Lebesgue measure on the drawn modes (-inf where that density vanishes at x); val = z(1) after mode 1, the interpolant
+ * at x: equal to ttx_basis_batch(x, TTX_BASIS_LINEAR on nodes, TTX_EVAL_EXACT) element for element (up to the sign of a zero).
+ * Distribution: for a train without sign changes the samples follow the multilinear interpolant f(x) / Z exactly, up to rounding,
+ * and exp(logq) = val / Z with Z = ttx_quad with the trapezoid weights (1.0 for a mode of one node; for held modes their hat
+ * rows).  For a signed train they follow the product of the interpolated ABSOLUTE nodal conditionals; exp(logq) is the proposal
+ * density to reweight with.
+ * Failed samples: C(n-2) is 0, NaN or Inf at some mode, or the u_k of a drawn mode is NaN or negative (-0.0 counts as 0).  The whole
+ * row of x is NaN, cell is 0, logq NaN and val 0.0; the sample is counted (ttx_sample_real_last); the others are untouched.
+ * Safety, as for ttx_sample: a cell index is formed from lane numbers, never from a value; x_k is clamped into its cell before the
+ * hat row is looked up, whose cell is j or j + 1, capped at n_k - 2; the cell of a held mode is found on the host.  Whatever cores,
+ * nodes and u hold, no read leaves its table.  Arithmetic is plain double without a running exponent.
+ * A sample depends neither on its neighbours nor on the chunk (TTX_SAMPLE_CHUNK); a call repeats bit for bit.  The train is not
+ * modified; the work space is the engine's own.  ttx_sample_real_dev: u, x, cell, logq and val are pointers on the engine's
+ * device, nodes and cond stay host pointers; it enqueues on the engine's stream and synchronises before it returns.
+ * npts = 0 succeeds and launches nothing.  TTX_EINVAL: npts < 0, null u / x / nodes with npts > 0 (before the engine is looked
+ * at); a node row that is missing, not finite or not strictly ascending, cond_k = +-Inf (before any device call); ranks above 128.
+ * TTX_ESTATE: an engine without a train; a multi-process engine is refused as by ttx_sample.
+ * ttx_sample_real_last: as ttx_sample_last, for k_sm_head and k_sr_draw of the last ttx_sample_real on this engine.
+ * Open: a direct COS-basis sampler (root finding on a density that may go negative), the squared-density (SIRT) variant, an MFMA
+ * path for the rows of p, extra per-mode weights, ranks above 128.  Added without a new ttx_version: look the symbols up. */
+int ttx_sample_real    (ttx_engine *h, int64_t npts, const double *u /* [npts][d] */, const double *const *nodes /* [d] host rows of n_k */,
+                        const double *cond /* [d] or NULL */, double *x /* [npts][d] */, int32_t *cell /* [npts][d] or NULL */, double *logq, double *val);
+int ttx_sample_real_dev(ttx_engine *h, int64_t npts, const double *u, const double *const *nodes, const double *cond, double *x, int32_t *cell, double *logq, double *val);
+int ttx_sample_real_last(const ttx_engine *h, double *ms_head, double *bytes_head, double *ms_draw, int64_t *nfailed);
+
 /* The largest elements of the resident train by a beam search along the train, on the device (ttcross_amd/csrc/ttx_topk.h), with
  * an upper bound on everything the search discarded.  Modes are 1-based, G_k is core k, r_0 = r_d = 1.
  *   K     : rows wanted, 1 .. 4096, and K max n_k <= 2^24 (the score sheet of one mode is kept in work space)

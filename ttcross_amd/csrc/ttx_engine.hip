@@ -54,6 +54,7 @@ static cluster_kernel_t cluster_kernel(int var)
 #include "ttx_algebra.h"
 #include "ttx_roundsum.h"
 #include "ttx_sample.h"
+#include "ttx_sample_real.h"
 #include "ttx_topk.h"
 #include "ttx_trainfun.h"
 
@@ -117,8 +118,8 @@ static int rccl_load()
 
 // Operations on the resident train (ttx_eval.h, ttx_contract.h, ttx_algebra.h, ttx_sample.h, ttx_modeapply.h) share one table of device work space
 // per engine, grown on demand (buf_reserve), freed in ttx_destroy.  A slot belongs to one role; two roles share a slot only where no
-// single call uses both, because a second buf_reserve of a slot may move what the first one handed out.  ttx_sample is the widest
-// call: SC_TRAIN, SC_META, SC_W, SC_M, SC_VEC, SC_H, SC_ROW, SC_CNT and the staging slots are all live in it.  ttx_topk keeps SC_TRAIN,
+// single call uses both, because a second buf_reserve of a slot may move what the first one handed out.  ttx_sample_real is the widest
+// call, then ttx_sample: SC_TRAIN, SC_META, SC_W, SC_M, SC_VEC, SC_H, SC_ROW, SC_CNT and the staging slots (with SC_SRX) are all live in it.  ttx_topk keeps SC_TRAIN,
 // SC_META (its per-mode tables) and all seven SC_K* slots live from its first launch to its last copy, reserves each of them once,
 // before the first launch, and touches no other slot: what ttx_sample or ttx_marginals left in theirs stays as it was.
 enum {
@@ -129,6 +130,7 @@ enum {
     SC_XA, SC_XB, SC_SORT,              // MFMA evaluation: the two state buffers, the bucket sort
     SC_W, SC_M, SC_P, SC_SCR, SC_VEC,   // contraction: weights, M matrices, run products, their overflow, the l and s vectors
     SC_H, SC_ROW, SC_CNT,               // sampling: head tables, global rows of long modes, the failure counter
+    SC_SRX,                             // ttx_sample_real: staging of the drawn coordinates (its uniforms go to SC_X, cell rows to SC_IND, nodes to SC_META)
     SC_TFUN, SC_TVAL,                   // TTX_FUN_TRAINS: the operands' blocks (core pointers, ranks) of a run, the values for a loaded combiner
     SC_MAT,                             // ttx_mode_apply: the matrices of the applied modes (its tables go to SC_META)
     SC_KP, SC_KW, SC_KS, SC_KX,         // ttx_topk: the Gram matrices P_0 .. P_(d-1), the W of a Gram step, a mode's score sheet (keys), the two state buffers
@@ -146,7 +148,7 @@ struct OpTimer {
     int stop(hipStream_t s) { HIPCHECK(hipEventRecord(ev[1], s)); return TTX_OK; }
     int ms(double *out) { float t = 0.f; HIPCHECK(hipEventElapsedTime(&t, ev[0], ev[1])); *out = t; return TTX_OK; }   // after a synchronise
 };
-enum { TM_MODESUM, TM_ALG, TM_HEAD, TM_DRAW, TM_APPLY,             // k_ct_modesum, the algebra launch, k_sm_head, the k_sm_draw of a chunk, k_ma_apply
+enum { TM_MODESUM, TM_ALG, TM_HEAD, TM_DRAW, TM_APPLY,             // k_ct_modesum, the algebra launch, k_sm_head, the k_sm_draw / k_sr_draw of a chunk, k_ma_apply
        TM_GRAM, TM_SCORE, TM_SELECT,                               // ttx_topk: the Gram chain, a mode's scoring launch, a mode's selection and advance
        TM_RS_SKETCH, TM_N };                                       // ttx_lincomb_round: the right-to-left pass (the GEMMs, QRs and advances alternate d - 1 times: RsMarks on ttx_engine::rs_ev)
 
@@ -247,6 +249,8 @@ struct ttx_engine {
     double alg_ms = 0.0, alg_rd = 0.0, alg_wr = 0.0;    // the last ttx_lincomb / ttx_hadamard with this engine first
     double sm_ms_head = 0.0, sm_bytes = 0.0, sm_ms_draw = 0.0;  // the last ttx_sample
     int64_t sm_failed = 0;
+    double sr_ms_head = 0.0, sr_bytes = 0.0, sr_ms_draw = 0.0;  // the last ttx_sample_real
+    int64_t sr_failed = 0;
     double ma_ms = 0.0, ma_rd = 0.0, ma_wr = 0.0, ma_flops = 0.0;   // the apply launch of the last ttx_mode_apply
     int ma_mode = -1;
     double tk_ms_gram = 0.0, tk_ms_score = 0.0, tk_ms_select = 0.0, tk_flops = 0.0;   // the last ttx_topk
@@ -3109,7 +3113,122 @@ extern "C" int ttx_contract_modesum(const ttx_engine *h, double *ms, double *byt
     return TTX_OK;
 }
 
-// ---- samples from the resident train (ttx_sample.h) -------------------------------------------------------------------------------
+// ---- samples from the resident train (ttx_sample.h, ttx_sample_real.h) -----------------------------------------------------------
+// What ttx_sample and ttx_sample_real share.  sm_prepare: the plan, the call's tables, the prefix vectors from the effective weights
+// (ct_modesum untimed, k_ct_chains), the head tables of the drawn modes (k_sm_head between TM_HEAD's events) and the shape of the draw
+// launches.  sm_chunks: the chunk loop with the staging of the host entry, the draw between TM_DRAW's events, the failure count.
+namespace {
+struct SmPrep {                             // what sm_prepare leaves for the chunk loop and the draw launches: outputs only
+    EvTrain T;
+    std::vector<size_t> hoff;               // where the head table of a drawn mode starts in SC_H
+    std::vector<SmTile> tiles;
+    size_t hsize = 0;
+    int nrow = 0;                           // the longest drawn mode
+    double bytes = 0.0;                     // of the cores k_sm_head reads
+    char *dm = nullptr;                     // the call's tables on the device (SC_META)
+    size_t o_hoff = 0;
+    double *H = nullptr, *grow = nullptr;
+    long long *dcnt = nullptr;
+    size_t chunk = 0, growlen = 0, lds = 0;
+    int gridmax = 0, ldsrow = 0;
+};
+struct SmStage { void *user; size_t bytes; int slot; void *dev; };    // an output: the caller's array (may be null), bytes per sample, its staging slot; dev: where the chunk's part lies
+}
+// Inputs: pl, the caller's plan of all modes (ct_plan); held[k] != 0: mode k gets no head table; eff: the effective weights of all modes
+// (pl.wsize numbers); hw_ones: k_sm_head multiplies by 1.0 (a block of ones in the call's tables), not by eff; draw_kernel and wave_extra:
+// the draw kernel and the doubles of dynamic LDS one of its waves owns on top of 2 ldx + ldsrow.  extra(meta) appends the caller's own
+// tables to the call's image before it is uploaded.  Output: P.
+template <class Extra>
+static int sm_prepare(ttx_engine *h, const char *who, int64_t npts, const CtPlan &pl, const std::vector<char> &held, const std::vector<double> &eff, bool hw_ones,
+                      const void *draw_kernel, size_t wave_extra, Extra extra, SmPrep &P)
+{
+    int rc;
+    const int d = h->d;
+    if ((rc = ev_train(h, &P.T))) return rc;
+    P.hoff.assign(d, 0);
+    for (int k = 0; k < d; k++) {
+        const CtCore &c = pl.cores[k];
+        if (held[k]) continue;
+        P.hoff[k] = P.hsize; P.hsize += (size_t)c.n * c.r1;
+        P.nrow = std::max(P.nrow, c.n);
+        P.bytes += 8.0 * c.r0 * c.n * c.r1;
+        const int ti = sm_tile_rows(c.r0);
+        for (int b = 0; b < c.r1; b++) for (int i0 = 0; i0 < c.n; i0 += ti) P.tiles.push_back(SmTile{k, b, i0, std::min(ti, c.n - i0)});
+    }
+    if (P.tiles.size() > 0x7fffffffull) return fail(TTX_EINVAL, "%s: too many head tiles (%zu)", who, P.tiles.size());
+    const int ldv = h->RM;
+    OpMeta meta(h->meta_host);
+    const size_t o_cores = meta.put(pl.cores), o_tiles = meta.put(pl.tiles), o_r = meta.put(pl.r), o_moff = meta.put(pl.moff), o_sm = meta.put(P.tiles);
+    P.o_hoff = meta.put(P.hoff);
+    extra(meta);
+    const size_t o_ones = hw_ones ? meta.put(std::vector<double>(pl.wsize, 1.0)) : 0;
+    if ((rc = meta.upload(h, SC_META, &P.dm)) || (rc = buf_reserve(h, SC_VEC, sizeof(double) * (2 * (size_t)d + 4) * ldv)) ||
+        (rc = buf_reserve(h, SC_H, sizeof(double) * std::max<size_t>(P.hsize, 1))) || (rc = buf_reserve(h, SC_CNT, sizeof(long long))) ||
+        (rc = ct_modesum(h, pl, eff.data(), (const CtCore *)(P.dm + o_cores), (const CtTile *)(P.dm + o_tiles), nullptr))) return rc;   // untimed: ttx_contract_modesum keeps its own last call
+    double *L = buf<double>(h, SC_VEC), *S = L + (size_t)d * ldv;
+    P.H = buf<double>(h, SC_H);
+    P.dcnt = buf<long long>(h, SC_CNT);
+    OpTimer &t_head = h->timer[TM_HEAD];
+    hipLaunchKernelGGL(k_ct_chains, dim3(2), dim3(1024), 0, h->stream, d, (const int *)(P.dm + o_r), (const size_t *)(P.dm + o_moff), (const double *)buf<double>(h, SC_M), L, S, ldv);
+    HIPCHECK(hipMemsetAsync(P.dcnt, 0, sizeof(long long), h->stream));
+    if (!P.tiles.empty()) {
+        if ((rc = t_head.start(h->stream))) return rc;
+        hipLaunchKernelGGL(k_sm_head, dim3((unsigned)P.tiles.size()), dim3(256), 0, h->stream, (const CtCore *)(P.dm + o_cores), (const SmTile *)(P.dm + o_sm), h->RM, h->P.SS,
+                           hw_ones ? (const double *)(P.dm + o_ones) : (const double *)buf<double>(h, SC_W), (const double *)L, ldv, (const size_t *)(P.dm + P.o_hoff), P.H);
+        if ((rc = t_head.stop(h->stream))) return rc;
+    }
+    // the draw: one wave per sample, 4 waves per workgroup, the grid capped at 8 workgroups per CU as k_ev_exact's
+    P.chunk = std::min<size_t>(env_chunk("TTX_SAMPLE_CHUNK", (size_t)1 << 18), (size_t)npts);
+    P.gridmax = (int)std::min<long long>(((long long)P.chunk + 3) / 4, (long long)dev_ncu(h) * 8);
+    P.ldsrow = std::min(P.nrow, TTX_SM_LDSROW);
+    P.growlen = P.nrow > TTX_SM_LDSROW ? (size_t)P.nrow : 0;
+    P.lds = 4 * sizeof(double) * (2 * (size_t)P.T.ldx + wave_extra + P.ldsrow);
+    if (P.lds > TTX_LDS_DEVICE) return fail(TTX_EINVAL, "%s: %d modes need %zu bytes of LDS per workgroup (160 KB at most)", who, d, P.lds);
+    if (P.lds > 64 * 1024 && (rc = ensure_lds(h, draw_kernel, P.lds))) return rc;
+    if (P.growlen && (rc = buf_reserve(h, SC_ROW, sizeof(double) * P.growlen * 4 * P.gridmax))) return rc;
+    P.grow = P.growlen ? buf<double>(h, SC_ROW) : nullptr;
+    return TTX_OK;
+}
+// draw(c, grid, du): the draw launch of a chunk of c samples whose uniforms lie at du; count(c): the launch that adds its failed samples to
+// P.dcnt.  Both find the chunk's outputs in out[.].dev (null for an output the caller did not ask for).  *ms_draw, *nfailed: the call's figures
+template <class Draw, class Count>
+static int sm_chunks(ttx_engine *h, const SmPrep &P, int64_t npts, const double *u, bool dev, SmStage *out, int nout, Draw draw, Count count, double *ms_draw, int64_t *nfailed)
+{
+    int rc;
+    const int d = h->d;
+    OpTimer &t_draw = h->timer[TM_DRAW];
+    if (!dev) {
+        if ((rc = buf_reserve(h, SC_X, sizeof(double) * P.chunk * d))) return rc;
+        for (int t = 0; t < nout; t++) if ((rc = buf_reserve(h, out[t].slot, out[t].bytes * P.chunk))) return rc;
+    }
+    for (int64_t o = 0; o < npts; o += (int64_t)P.chunk) {
+        const size_t c = (size_t)std::min<int64_t>((int64_t)P.chunk, npts - o);
+        const double *du = u + (size_t)o * d;
+        for (int t = 0; t < nout; t++) out[t].dev = out[t].user ? (char *)out[t].user + out[t].bytes * (size_t)o : nullptr;
+        if (!dev) {
+            HIPCHECK(hipMemcpyAsync(buf<double>(h, SC_X), du, sizeof(double) * c * d, hipMemcpyHostToDevice, h->stream));
+            du = buf<double>(h, SC_X);
+            for (int t = 0; t < nout; t++) if (out[t].user) out[t].dev = buf<char>(h, out[t].slot);
+        }
+        const int grid = (int)std::min<long long>(((long long)c + 3) / 4, (long long)P.gridmax);
+        if ((rc = t_draw.start(h->stream))) return rc;
+        draw(c, grid, du);
+        if ((rc = t_draw.stop(h->stream))) return rc;
+        count(c);
+        if (!dev)
+            for (int t = 0; t < nout; t++)
+                if (out[t].user) HIPCHECK(hipMemcpyAsync((char *)out[t].user + out[t].bytes * (size_t)o, out[t].dev, out[t].bytes * c, hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(hipStreamSynchronize(h->stream));
+        HIPCHECK(hipGetLastError());
+        double ms = 0.0;
+        if ((rc = t_draw.ms(&ms))) return rc;
+        *ms_draw += ms;
+    }
+    long long nf = 0;
+    HIPCHECK(hipMemcpy(&nf, P.dcnt, sizeof(long long), hipMemcpyDeviceToHost));
+    *nfailed = nf;
+    return TTX_OK;
+}
 // both entries: u, ind, logq, val are host pointers (dev false: staged chunk by chunk) or pointers on the engine's device
 static int sm_run(ttx_engine *h, const char *who, int64_t npts, const double *u, const double *w, const int32_t *fixed, int32_t *ind, double *logq, double *val, bool dev)
 {
@@ -3120,95 +3239,34 @@ static int sm_run(ttx_engine *h, const char *who, int64_t npts, const double *u,
     if (fixed) for (int k = 0; k < d; k++) if (fixed[k] < 0 || fixed[k] > h->n1[k + 1]) return fail(TTX_EINVAL, "%s: fixed(%d) = %d (0 .. %d expected)", who, k + 1, fixed[k], h->n1[k + 1]);
     h->sm_ms_head = h->sm_ms_draw = h->sm_bytes = 0.0; h->sm_failed = 0;
     if (npts == 0) return TTX_OK;
-    EvTrain T;
-    if ((rc = ev_train(h, &T))) return rc;
-    // the prefix vectors: mode sums with the effective weights (a fixed mode: the unit vector of its index), then the l chain
+    // the effective weights: a fixed mode has the unit vector of its index
+    SmPrep P;
     CtPlan pl;
     ct_plan(h, std::vector<char>(d, 1), pl);
     std::vector<double> eff(pl.wsize, 1.0);
     if (w) memcpy(eff.data(), w, sizeof(double) * pl.wsize);
     std::vector<int> fx(d, 0);
-    std::vector<size_t> hoff(d, 0);
-    std::vector<SmTile> tiles;
-    size_t hsize = 0;
-    int nrow = 0;
+    std::vector<char> held(d, 0);
     for (int k = 0; k < d; k++) {
         const CtCore &c = pl.cores[k];
-        if (fixed && fixed[k]) {
-            fx[k] = fixed[k];
-            for (int i = 0; i < c.n; i++) eff[c.woff + i] = i == fixed[k] - 1 ? 1.0 : 0.0;
-            continue;
-        }
-        hoff[k] = hsize; hsize += (size_t)c.n * c.r1;
-        nrow = std::max(nrow, c.n);
-        h->sm_bytes += 8.0 * c.r0 * c.n * c.r1;
-        const int ti = sm_tile_rows(c.r0);
-        for (int b = 0; b < c.r1; b++) for (int i0 = 0; i0 < c.n; i0 += ti) tiles.push_back(SmTile{k, b, i0, std::min(ti, c.n - i0)});
+        if (!fixed || !fixed[k]) continue;
+        fx[k] = fixed[k]; held[k] = 1;
+        for (int i = 0; i < c.n; i++) eff[c.woff + i] = i == fixed[k] - 1 ? 1.0 : 0.0;
     }
-    if (tiles.size() > 0x7fffffffull) return fail(TTX_EINVAL, "%s: too many head tiles (%zu)", who, tiles.size());
-    const int ldv = h->RM;
-    OpMeta meta(h->meta_host);
-    const size_t o_cores = meta.put(pl.cores), o_tiles = meta.put(pl.tiles), o_r = meta.put(pl.r), o_moff = meta.put(pl.moff),
-                 o_sm = meta.put(tiles), o_hoff = meta.put(hoff), o_fx = meta.put(fx);
-    char *dm;
-    if ((rc = meta.upload(h, SC_META, &dm)) || (rc = buf_reserve(h, SC_VEC, sizeof(double) * (2 * (size_t)d + 4) * ldv)) ||
-        (rc = buf_reserve(h, SC_H, sizeof(double) * std::max<size_t>(hsize, 1))) || (rc = buf_reserve(h, SC_CNT, sizeof(long long))) ||
-        (rc = ct_modesum(h, pl, eff.data(), (const CtCore *)(dm + o_cores), (const CtTile *)(dm + o_tiles), nullptr))) return rc;   // untimed: ttx_contract_modesum keeps its own last call
-    double *L = buf<double>(h, SC_VEC), *S = L + (size_t)d * ldv, *H = buf<double>(h, SC_H);
-    long long *dcnt = buf<long long>(h, SC_CNT);
-    OpTimer &t_head = h->timer[TM_HEAD], &t_draw = h->timer[TM_DRAW];
-    hipLaunchKernelGGL(k_ct_chains, dim3(2), dim3(1024), 0, h->stream, d, (const int *)(dm + o_r), (const size_t *)(dm + o_moff), (const double *)buf<double>(h, SC_M), L, S, ldv);
-    HIPCHECK(hipMemsetAsync(dcnt, 0, sizeof(long long), h->stream));
-    if (!tiles.empty()) {
-        if ((rc = t_head.start(h->stream))) return rc;
-        hipLaunchKernelGGL(k_sm_head, dim3((unsigned)tiles.size()), dim3(256), 0, h->stream, (const CtCore *)(dm + o_cores), (const SmTile *)(dm + o_sm), h->RM, h->P.SS,
-                           (const double *)buf<double>(h, SC_W), (const double *)L, ldv, (const size_t *)(dm + o_hoff), H);
-        if ((rc = t_head.stop(h->stream))) return rc;
-    }
-    // the draw: one wave per sample, 4 waves per workgroup, the grid capped at 8 workgroups per CU as k_ev_exact's
-    const size_t chunk = std::min<size_t>(env_chunk("TTX_SAMPLE_CHUNK", (size_t)1 << 18), (size_t)npts);
-    const int gridmax = (int)std::min<long long>(((long long)chunk + 3) / 4, (long long)dev_ncu(h) * 8);
-    const int ldsrow = std::min(nrow, TTX_SM_LDSROW);
-    const size_t growlen = nrow > TTX_SM_LDSROW ? (size_t)nrow : 0;
-    const size_t lds = 4 * sizeof(double) * (2 * (size_t)T.ldx + d + (((size_t)d + 1) >> 1) + ldsrow);
-    if (lds > TTX_LDS_DEVICE) return fail(TTX_EINVAL, "%s: %d modes need %zu bytes of LDS per workgroup (160 KB at most)", who, d, lds);
-    if (lds > 64 * 1024 && (rc = ensure_lds(h, reinterpret_cast<const void *>(k_sm_draw), lds))) return rc;
-    if (growlen && (rc = buf_reserve(h, SC_ROW, sizeof(double) * growlen * 4 * gridmax))) return rc;
-    double *grow = growlen ? buf<double>(h, SC_ROW) : nullptr;
-    if (!dev && ((rc = buf_reserve(h, SC_X, sizeof(double) * chunk * d)) || (rc = buf_reserve(h, SC_IND, sizeof(int) * chunk * d)) ||
-                 (rc = buf_reserve(h, SC_LQ, sizeof(double) * chunk)) || (rc = buf_reserve(h, SC_OUT, sizeof(double) * chunk)))) return rc;
-    for (int64_t o = 0; o < npts; o += (int64_t)chunk) {
-        const size_t c = (size_t)std::min<int64_t>((int64_t)chunk, npts - o);
-        const double *du = u + (size_t)o * d;
-        int *di = ind + (size_t)o * d;
-        double *dl = logq ? logq + o : nullptr, *dv = val ? val + o : nullptr;
-        if (!dev) {
-            HIPCHECK(hipMemcpyAsync(buf<double>(h, SC_X), du, sizeof(double) * c * d, hipMemcpyHostToDevice, h->stream));
-            du = buf<double>(h, SC_X); di = buf<int>(h, SC_IND);
-            if (logq) dl = buf<double>(h, SC_LQ);
-            if (val) dv = buf<double>(h, SC_OUT);
-        }
-        const int grid = (int)std::min<long long>(((long long)c + 3) / 4, (long long)gridmax);
-        if ((rc = t_draw.start(h->stream))) return rc;
-        hipLaunchKernelGGL(k_sm_draw, dim3(grid), dim3(256), lds, h->stream, T, (const size_t *)(dm + o_hoff), (const int *)(dm + o_fx), (const double *)H, ldsrow, grow, growlen,
-                           (long long)c, du, di, dl, dv);
-        if ((rc = t_draw.stop(h->stream))) return rc;
-        hipLaunchKernelGGL(k_sm_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const int *)di, dcnt);
-        if (!dev) {
-            HIPCHECK(hipMemcpyAsync(ind + (size_t)o * d, di, sizeof(int) * c * d, hipMemcpyDeviceToHost, h->stream));
-            if (logq) HIPCHECK(hipMemcpyAsync(logq + o, dl, sizeof(double) * c, hipMemcpyDeviceToHost, h->stream));
-            if (val) HIPCHECK(hipMemcpyAsync(val + o, dv, sizeof(double) * c, hipMemcpyDeviceToHost, h->stream));
-        }
-        HIPCHECK(hipStreamSynchronize(h->stream));
-        HIPCHECK(hipGetLastError());
-        double ms = 0.0;
-        if ((rc = t_draw.ms(&ms))) return rc;
-        h->sm_ms_draw += ms;
-    }
-    long long nf = 0;
-    HIPCHECK(hipMemcpy(&nf, dcnt, sizeof(long long), hipMemcpyDeviceToHost));
-    h->sm_failed = nf;
-    return tiles.empty() ? TTX_OK : t_head.ms(&h->sm_ms_head);
+    size_t o_fx = 0;
+    if ((rc = sm_prepare(h, who, npts, pl, held, eff, false, reinterpret_cast<const void *>(k_sm_draw), (size_t)d + (((size_t)d + 1) >> 1),
+                         [&](OpMeta &meta) { o_fx = meta.put(fx); }, P))) return rc;
+    h->sm_bytes = P.bytes;
+    SmStage out[3] = {{ind, sizeof(int) * (size_t)d, SC_IND, nullptr}, {logq, sizeof(double), SC_LQ, nullptr}, {val, sizeof(double), SC_OUT, nullptr}};
+    rc = sm_chunks(h, P, npts, u, dev, out, 3,
+        [&](size_t c, int grid, const double *du) {
+            hipLaunchKernelGGL(k_sm_draw, dim3(grid), dim3(256), P.lds, h->stream, P.T, (const size_t *)(P.dm + P.o_hoff), (const int *)(P.dm + o_fx), (const double *)P.H, P.ldsrow,
+                               P.grow, P.growlen, (long long)c, du, (int *)out[0].dev, (double *)out[1].dev, (double *)out[2].dev);
+        },
+        [&](size_t c) { hipLaunchKernelGGL(k_sm_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const int *)out[0].dev, P.dcnt); },
+        &h->sm_ms_draw, &h->sm_failed);
+    if (rc) return rc;
+    return P.tiles.empty() ? TTX_OK : h->timer[TM_HEAD].ms(&h->sm_ms_head);
 }
 extern "C" int ttx_sample(ttx_engine *h, int64_t npts, const double *u, const double *w, const int32_t *fixed, int32_t *ind, double *logq, double *val)
 {
@@ -3225,6 +3283,83 @@ extern "C" int ttx_sample_last(const ttx_engine *h, double *ms_head, double *byt
     if (bytes_head) *bytes_head = h->sm_bytes;
     if (ms_draw) *ms_draw = h->sm_ms_draw;
     if (nfailed) *nfailed = h->sm_failed;
+    return TTX_OK;
+}
+
+
+// ---- real-valued samples from the interpolant of the resident train (ttx_sample_real.h) ------------------------------------------
+// both entries: u, x, cell, logq, val are host pointers (dev false: staged chunk by chunk) or pointers on the engine's device
+static int bs_check_one(const char *who, int k, const ttx_basis &b, int n);     // the node rows are TTX_BASIS_LINEAR's: one check (below, with ttx_basis_batch)
+static int sr_run(ttx_engine *h, const char *who, int64_t npts, const double *u, const double *const *nodes, const double *cond, double *x, int32_t *cell, double *logq,
+                  double *val, bool dev)
+{
+    if (npts < 0 || (npts > 0 && (!u || !x || !nodes))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
+    int rc = check_train_one_process(h, who);
+    if (rc) return rc;
+    const int d = h->d;
+    if (nodes) {
+        for (int k = 0; k < d; k++) {
+            ttx_basis b{TTX_BASIS_LINEAR, 0, 0.0, 0.0, nodes[k]};
+            if ((rc = bs_check_one(who, k + 1, b, h->n1[k + 1]))) return rc;
+        }
+    }
+    if (cond) for (int k = 0; k < d; k++) if (std::isinf(cond[k])) return fail(TTX_EINVAL, "%s: cond(%d) is infinite (a coordinate, or NaN for a drawn mode, expected)", who, k + 1);
+    h->sr_ms_head = h->sr_ms_draw = h->sr_bytes = 0.0; h->sr_failed = 0;
+    if (npts == 0) return TTX_OK;
+    // the effective weights: trapezoid weights of a drawn mode, the hat row of a held one (a mode of one node is held at its node)
+    SmPrep P;
+    CtPlan pl;
+    ct_plan(h, std::vector<char>(d, 1), pl);
+    std::vector<double> eff(pl.wsize, 0.0), tnodes;
+    std::vector<char> held(d, 0);
+    std::vector<SrMode> modes(d);
+    for (int k = 0; k < d; k++) {
+        const CtCore &c = pl.cores[k];
+        const double *t = nodes[k];
+        SrMode &M = modes[k];
+        M = SrMode{0, 0, 1.0, 0.0, 0.0, tnodes.size()};
+        tnodes.insert(tnodes.end(), t, t + c.n);
+        const bool given = cond && cond[k] == cond[k];
+        if (!given && c.n > 1) { sr_trapezoid(t, c.n, eff.data() + c.woff); continue; }
+        held[k] = 1;
+        M.held = 1; M.xh = given ? cond[k] : t[0];
+        M.cell = sr_hat_cell(t, c.n, M.xh);
+        for (int i = 0; i < c.n; i++) eff[c.woff + i] = ttx_basis_entry(TTX_BASIS_LINEAR, 0, 0.0, 0.0, t, c.n, M.xh, i);
+        M.phi0 = eff[c.woff + M.cell];
+        M.phi1 = c.n > 1 ? eff[c.woff + M.cell + 1] : 0.0;
+    }
+    size_t o_modes = 0, o_nodes = 0;
+    if ((rc = sm_prepare(h, who, npts, pl, held, eff, true, reinterpret_cast<const void *>(k_sr_draw), 2 * (size_t)d + (((size_t)d + 1) >> 1),
+                         [&](OpMeta &meta) { o_modes = meta.put(modes); o_nodes = meta.put(tnodes); }, P))) return rc;
+    h->sr_bytes = P.bytes;
+    SmStage out[4] = {{x, sizeof(double) * (size_t)d, SC_SRX, nullptr}, {cell, sizeof(int) * (size_t)d, SC_IND, nullptr}, {logq, sizeof(double), SC_LQ, nullptr},
+                      {val, sizeof(double), SC_OUT, nullptr}};
+    rc = sm_chunks(h, P, npts, u, dev, out, 4,
+        [&](size_t c, int grid, const double *du) {
+            hipLaunchKernelGGL(k_sr_draw, dim3(grid), dim3(256), P.lds, h->stream, P.T, (const size_t *)(P.dm + P.o_hoff), (const SrMode *)(P.dm + o_modes),
+                               (const double *)(P.dm + o_nodes), (const double *)P.H, P.ldsrow, P.grow, P.growlen, (long long)c, du, (double *)out[0].dev, (int *)out[1].dev,
+                               (double *)out[2].dev, (double *)out[3].dev);
+        },
+        [&](size_t c) { hipLaunchKernelGGL(k_sr_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const double *)out[0].dev, P.dcnt); },
+        &h->sr_ms_draw, &h->sr_failed);
+    if (rc) return rc;
+    return P.tiles.empty() ? TTX_OK : h->timer[TM_HEAD].ms(&h->sr_ms_head);
+}
+extern "C" int ttx_sample_real(ttx_engine *h, int64_t npts, const double *u, const double *const *nodes, const double *cond, double *x, int32_t *cell, double *logq, double *val)
+{
+    return sr_run(h, "ttx_sample_real", npts, u, nodes, cond, x, cell, logq, val, false);
+}
+extern "C" int ttx_sample_real_dev(ttx_engine *h, int64_t npts, const double *u, const double *const *nodes, const double *cond, double *x, int32_t *cell, double *logq, double *val)
+{
+    return sr_run(h, "ttx_sample_real_dev", npts, u, nodes, cond, x, cell, logq, val, true);
+}
+extern "C" int ttx_sample_real_last(const ttx_engine *h, double *ms_head, double *bytes_head, double *ms_draw, int64_t *nfailed)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_sample_real_last: null engine");
+    if (ms_head) *ms_head = h->sr_ms_head;
+    if (bytes_head) *bytes_head = h->sr_bytes;
+    if (ms_draw) *ms_draw = h->sr_ms_draw;
+    if (nfailed) *nfailed = h->sr_failed;
     return TTX_OK;
 }
 

@@ -11,6 +11,7 @@ runs on the GPU through ttcross_amd.engine.  Usage:
     python -m ttcross_amd.drivers algebra WORKLOAD [REPS]      (x + x, x - x, x o w, x o x, dist on the device and by the host route)
     python -m ttcross_amd.drivers roundsum WORKLOAD M [RANK] [MODE] (rounded sum of M terms made from the workload's train: lincomb_round)
     python -m ttcross_amd.drivers compose WORKLOAD OP [MAXRANK] (cross approximation of product | ratio | sqrtabs of the workload's train)
+    python -m ttcross_amd.drivers samplereal WORKLOAD NPTS[,NPTS...] (real-valued samples from the interpolant of the workload's train: sample_real)
 
 devfun: the rational example integrand (examples/devfun/rational.hip) as a LOADED device integrand (TTX_FUN_DEVICE), in its
 wave form, or -- host -- its C twin through the host callback (TTX_FUN_HOST; needs gcc); SOURCE.hip NAME loads another
@@ -813,6 +814,112 @@ def run_sample(argv, device=0, repeats=5, tt=None, host_npts=1000):
     return out
 
 
+def sample_real_host(tt, u, nodes):
+    """what a user does without ttx_sample_real: every core to the host with core(k), then the interpolated conditionals walked in
+    numpy from the last mode to the first and inverted cell by cell.  Returns (x, logq, val) of the definition in include/ttx.h,
+    in numpy's own summation order (all modes drawn, at least two nodes each)."""
+    cores = [tt.core(k) for k in range(1, tt.d + 1)]
+    nodes = [np.asarray(t, dtype=np.float64) for t in nodes]
+    u = np.asarray(u, dtype=np.float64)
+    npts, d = u.shape
+    lv, heads = np.ones(1), []
+    for c, t in zip(cores, nodes):
+        om = np.concatenate([[t[1] - t[0]], t[2:] - t[:-2], [t[-1] - t[-2]]]) * 0.5
+        heads.append(np.einsum("a,aib->ib", lv, c))
+        lv = lv @ np.einsum("aib,i->ab", c, om)
+    st = np.ones((npts, 1))
+    x, logq, rows = np.zeros((npts, d)), np.zeros(npts), np.arange(npts)
+    for k in range(d - 1, -1, -1):
+        t = nodes[k]
+        h = np.diff(t)
+        p = np.abs(st @ heads[k].T)
+        A = 0.5 * (p[:, :-1] + p[:, 1:]) * h
+        C = np.cumsum(A, axis=1)
+        T = u[:, k] * C[:, -1]
+        hit = (A > 0) & (T[:, None] < C)
+        j = np.where(hit.any(1), hit.argmax(1), A.shape[1] - 1 - (A[:, ::-1] > 0).argmax(1))
+        p0, p1 = p[rows, j], p[rows, j + 1]
+        sp = np.clip(T - np.where(j > 0, C[rows, np.maximum(j - 1, 0)], 0.0), 0.0, A[rows, j]) / h[j]
+        den = p0 + np.sqrt(np.maximum(p0 * p0 + 2.0 * (p1 - p0) * sp, 0.0))
+        lam = np.where(hit.any(1), np.clip(2.0 * sp / np.where(den > 0, den, 1.0), 0.0, 1.0), 1.0)
+        xk = np.clip(t[j] + lam * h[j], t[j], t[j + 1])
+        i = np.clip(np.searchsorted(t, xk, side="right") - 1, 0, t.size - 2)
+        f1 = (xk - t[i]) / (t[i + 1] - t[i])
+        f0 = 1.0 - f1
+        logq += np.log((f0 * p[rows, i] + f1 * p[rows, i + 1]) / C[:, -1])
+        x[:, k] = xk
+        st = f0[:, None] * np.einsum("asb,sb->sa", cores[k][:, i, :], st) + f1[:, None] * np.einsum("asb,sb->sa", cores[k][:, i + 1, :], st)
+    return x, logq, st[:, 0]
+
+
+def run_samplereal(argv, device=0, repeats=5, tt=None, host_npts=1000):
+    """samplereal WORKLOAD NPTS[,NPTS...]: the trains of the sample sub-command on equidistant nodes of [0, 1], seeded uniforms made
+    ON the device; per sample count one warm-up and the median of `repeats` calls through the device-pointer entry: the call and
+    its two kernels (HIP events, ttx_sample_real_last); sample() on the same u with its two kernels, k_sr_draw over k_sm_draw
+    next to the derived work ratio sum (n r1 + 2 r0 r1) / sum (n r1 + r0 r1); basis_batch(x, linear, "exact") on the drawn points
+    (one call after a small warm-up, on as many of them as 2e13 flops of its dense chain allow), the cost of forming val separately; then the host route sample_real_host once at host_npts samples.  Prints one JSON line
+    per sample count."""
+    import json
+    import time
+    import torch
+    torch.cuda.init()          # a torch that brings its own HIP runtime must initialise its device before the engine's library does
+    workload = argv[0]
+    tt = tt or tijk_train(workload, device=device)
+    dev = torch.device("cuda", device)
+    nodes = [np.linspace(0.0, 1.0, int(nk)) for nk in tt._n]
+    lin = [("linear", t) for t in nodes]
+    w = [np.full(int(nk), 1.0 / int(nk)) for nk in tt._n]
+    r = [int(q) for q in tt.ranks()]
+    flops_pt = 2.0 * sum(r[k] * int(nk) * r[k + 1] for k, nk in enumerate(tt._n))
+    work = sum(int(nk) * r[k + 1] + 2 * r[k] * r[k + 1] for k, nk in enumerate(tt._n)) / sum(int(nk) * r[k + 1] + r[k] * r[k + 1] for k, nk in enumerate(tt._n))
+    out = []
+    for npts in [int(float(x)) for x in argv[1].split(",")]:
+        g = torch.Generator(device=dev)
+        g.manual_seed(20240607)
+        u = torch.rand((npts, tt.d), dtype=torch.float64, device=dev, generator=g)
+        torch.cuda.synchronize(dev)
+        res = tt.sample_real(u, nodes)
+        ms, last = [], []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            res = tt.sample_real(u, nodes)             # synchronises before it returns
+            ms.append((time.perf_counter() - t0) * 1e3)
+            last.append(tt.sample_real_last())
+        tt.sample(u, w)
+        sm = []
+        for _ in range(repeats):
+            tt.sample(u, w)
+            sm.append(tt.sample_last())
+        fin = ~torch.isnan(res["x"][:, 0])
+        nb = min(int(fin.sum().item()), max(1000, int(2e13 / flops_pt)))     # the dense exact chain costs flops_pt per point: at most 2e13 flops are timed
+        xs, vs = res["x"][fin][:nb].contiguous(), res["val"][fin][:nb]
+        tt.basis_batch(xs[:64].contiguous(), lin, "exact")
+        t0 = time.perf_counter()
+        val = tt.basis_batch(xs, lin, "exact")
+        basis = (time.perf_counter() - t0) * 1e3
+        head, draw = float(np.median([x["ms_head"] for x in last])), float(np.median([x["ms_draw"] for x in last]))
+        sm_head, sm_draw = float(np.median([x["ms_head"] for x in sm])), float(np.median([x["ms_draw"] for x in sm]))
+        rec = dict(workload=workload, npts=npts, d=tt.d, max_rank=max(r), call_ms=float(np.median(ms)), head_ms=head, draw_ms=draw,
+                   draw_samples_per_s=npts / (draw * 1e-3) if draw > 0 else None, sample_head_ms=sm_head, sample_draw_ms=sm_draw,
+                   draw_over_sample_draw=draw / sm_draw if sm_draw > 0 else None, work_ratio=work,
+                   time_over_work=draw / sm_draw / work if sm_draw > 0 else None, basis_exact_npts=nb, basis_exact_ms=basis,
+                   draw_us_per_sample=draw * 1e3 / npts, basis_exact_us_per_point=basis * 1e3 / nb if nb else None, failed=last[-1]["failed"],
+                   val_is_basis=bool(torch.all(val == vs).item()), mean_logq=float(res["logq"][fin].mean().item()))
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+    uh = np.random.default_rng(7).random((host_npts, tt.d))
+    t0 = time.perf_counter()
+    hx, hq, hv = sample_real_host(tt, uh, nodes)
+    host_ms = (time.perf_counter() - t0) * 1e3
+    dx = tt.sample_real(uh, nodes)
+    with np.errstate(all="ignore"):
+        rec = dict(workload=workload, host_route_npts=host_npts, host_route_ms=host_ms, host_samples_per_s=host_npts / (host_ms * 1e-3),
+                   host_max_abs_dx=float(np.nanmax(np.abs(hx - dx["x"]))), host_max_abs_dlogq=float(np.nanmax(np.abs(hq - dx["logq"]))))
+    print(json.dumps(rec), flush=True)
+    out.append(rec)
+    return out
+
+
 def topk_train(workload, device=0):
     """The train of a topk run: a train of the tijk sub-command, or d64diff: the difference lincomb([1, -1], [exact, fast]) of the
     D_64 result trains in the two arithmetics, whose largest element is the max-norm error of the fast arithmetic; NAME+ort: the
@@ -967,6 +1074,8 @@ if __name__ == "__main__":
         run_compose(sys.argv[2:])
     elif sys.argv[1] == "sample":
         run_sample(sys.argv[2:])
+    elif sys.argv[1] == "samplereal":
+        run_samplereal(sys.argv[2:])
     elif sys.argv[1] == "topk":
         run_topk(sys.argv[2:])
     elif sys.argv[1] == "contract":

@@ -130,6 +130,10 @@ def load_library():
     L.ttx_sample.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
     L.ttx_sample_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(c_double), POINTER(c_int32), c_void_p, c_void_p, c_void_p]
     L.ttx_sample_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
+    L.ttx_sample_real.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(POINTER(c_double)), POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_double),
+                                  POINTER(c_double)]
+    L.ttx_sample_real_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(POINTER(c_double)), POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p]
+    L.ttx_sample_real_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
     L.ttx_topk.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_int32), c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
     L.ttx_topk_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
     L.ttx_zquad.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
@@ -239,6 +243,23 @@ def basis_table(entry, n, x):
     phi = np.zeros((xa.size, int(n)))
     _check(load_library().ttx_basis_host(ctypes.byref(b), int(n), xa.size, _dp(xa), 1, _dp(phi)))
     return phi
+
+
+def trapezoid_weights(nodes):
+    """The trapezoid weights of strictly ascending nodes, the weights sample_real gives a drawn mode (include/ttx.h:
+    ttx_sample_real): om[0] = 0.5 (t[1] - t[0]), om[i] = 0.5 (t[i+1] - t[i-1]), om[n-1] = 0.5 (t[n-1] - t[n-2]); a single node carries
+    1.0.  One array of nodes gives one array, a list of arrays a list: quad(trapezoid_weights(nodes)) is the Z of sample_real."""
+    if isinstance(nodes, (list, tuple)) and len(nodes) and np.ndim(nodes[0]) == 1:
+        return [trapezoid_weights(t) for t in nodes]
+    t = np.ascontiguousarray(nodes, dtype=np.float64)
+    if t.ndim != 1 or t.size < 1:
+        raise ValueError("trapezoid_weights: a one-dimensional array of nodes expected")
+    if t.size == 1:
+        return np.ones(1)
+    om = np.empty(t.size)
+    om[0], om[-1] = 0.5 * (t[1] - t[0]), 0.5 * (t[-1] - t[-2])
+    om[1:-1] = 0.5 * (t[2:] - t[:-2])
+    return om
 
 
 def roundsum_omega(seed, k, shape):
@@ -969,6 +990,83 @@ class TTCross:
         """dict(ms_head, bytes_head, ms_draw, failed) of the last sample() on this engine (include/ttx.h: ttx_sample_last)"""
         a, b, c, n = c_double(), c_double(), c_double(), c_int64()
         _check(load_library().ttx_sample_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(n)))
+        return dict(ms_head=a.value, bytes_head=b.value, ms_draw=c.value, failed=int(n.value))
+
+    # ---- real-valued samples from the interpolant of the train (include/ttx.h: ttx_sample_real) -----------
+    def _node_rows(self, nodes, who):
+        """nodes: one array for all modes or a list of d -> (the d arrays, the ctypes row pointers)"""
+        if not isinstance(nodes, (list, tuple)) or (len(nodes) and np.ndim(nodes[0]) == 0):
+            nodes = [nodes] * self.d
+        if len(nodes) != self.d:
+            raise ValueError(f"{who}: {self.d} node rows expected (got {len(nodes)})")
+        rows = [np.ascontiguousarray(t, dtype=np.float64) for t in nodes]
+        for k, t in enumerate(rows):
+            if t.ndim != 1 or t.size != int(self._n[k]):
+                raise ValueError(f"{who}: {int(self._n[k])} nodes expected for mode {k + 1} (got shape {t.shape})")
+        return rows, (POINTER(c_double) * self.d)(*[_dp(t) for t in rows])
+
+    def sample_real(self, u_or_npts, nodes, cond=None, seed=None, want=("x", "cell", "logq", "val")):
+        """Real points drawn from the piecewise-linear interpolant of the train of grid values, on the device (include/ttx.h:
+        ttx_sample_real): for a train without sign changes they follow the interpolant f(x) / Z that basis_batch(x, ("linear",
+        nodes)) evaluates, Z = quad(trapezoid_weights(nodes)).  u_or_npts: uniforms of shape (npts, d), or a count, for which the
+        uniforms come from numpy.random.default_rng(seed); nodes: one array for all modes or a list of d; cond: d entries, NaN =
+        drawn, a finite number = the mode is held at that coordinate.  Returns a dict with the entries named in want: x (npts, d);
+        cell (npts, d) int32, the 1-based cell of a drawn mode and 0 for a held one; logq, the log of the proposal's density at x;
+        val, the interpolant at x (basis_batch(x, linear, "exact")).  A failed sample (a conditional without mass, a NaN or
+        negative u) has a row of NaN in x, cell 0, logq NaN and val 0; sample_real_last() counts them.  A contiguous float64 torch
+        tensor on the engine's device is passed by pointer (ttx_sample_real_dev) and gives torch tensors on that device: x can go
+        straight into basis_batch."""
+        L, names = load_library(), ("x", "cell", "logq", "val")
+        bad = set(want) - set(names)
+        if bad:
+            raise ValueError(f"sample_real: unknown output {sorted(bad)}")
+        rows, rowp = self._node_rows(nodes, "sample_real")
+        ca = None
+        if cond is not None:
+            ca = np.ascontiguousarray(cond, dtype=np.float64).ravel()
+            if ca.size != self.d:
+                raise ValueError(f"sample_real: {self.d} cond entries expected")
+        if type(u_or_npts).__module__.split(".")[0] == "torch":
+            import torch
+            u = u_or_npts
+            if not u.is_cuda:
+                return {k: torch.from_numpy(v) for k, v in self.sample_real(u.numpy(), nodes, cond, seed, want).items()}
+            if u.device.index != self.device:
+                raise ValueError(f"sample_real: the tensor lies on {u.device}, the engine on device {self.device}")
+            if u.dtype != torch.float64 or not u.is_contiguous() or u.dim() != 2 or u.shape[1] != self.d:
+                raise ValueError(f"sample_real: a contiguous float64 tensor of shape (npts, {self.d}) expected")
+            npts = u.shape[0]
+            x = torch.empty((npts, self.d), dtype=torch.float64, device=u.device)
+            ce = torch.empty((npts, self.d), dtype=torch.int32, device=u.device) if "cell" in want else None
+            lq = torch.empty(npts, dtype=torch.float64, device=u.device) if "logq" in want else None
+            va = torch.empty(npts, dtype=torch.float64, device=u.device) if "val" in want else None
+            torch.cuda.current_stream(u.device).synchronize()        # the engine runs on a stream of its own
+            _check(L.ttx_sample_real_dev(self._h, npts, c_void_p(u.data_ptr()), rowp, _dp(ca), c_void_p(x.data_ptr()), *[
+                c_void_p(t.data_ptr()) if t is not None else None for t in (ce, lq, va)]))
+            out = dict(x=x, cell=ce, logq=lq, val=va)
+            return {k: out[k] for k in names if k in want}
+        if np.ndim(u_or_npts) == 0:
+            npts = int(u_or_npts)
+            if npts < 0:
+                raise ValueError("sample_real: a negative count")
+            u = np.random.default_rng(seed).random((npts, self.d))
+        else:
+            u = np.ascontiguousarray(u_or_npts, dtype=np.float64)
+            if u.ndim != 2 or u.shape[1] != self.d:
+                raise ValueError(f"sample_real: an array of shape (npts, {self.d}) expected")
+        npts = u.shape[0]
+        x = np.zeros((npts, self.d))
+        ce = np.zeros((npts, self.d), dtype=np.int32) if "cell" in want else None
+        lq = np.zeros(npts) if "logq" in want else None
+        va = np.zeros(npts) if "val" in want else None
+        _check(L.ttx_sample_real(self._h, npts, _dp(u), rowp, _dp(ca), _dp(x), _ip(ce), _dp(lq), _dp(va)))
+        out = dict(x=x, cell=ce, logq=lq, val=va)
+        return {k: out[k] for k in names if k in want}
+
+    def sample_real_last(self):
+        """dict(ms_head, bytes_head, ms_draw, failed) of the last sample_real() on this engine (include/ttx.h: ttx_sample_real_last)"""
+        a, b, c, n = c_double(), c_double(), c_double(), c_int64()
+        _check(load_library().ttx_sample_real_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(n)))
         return dict(ms_head=a.value, bytes_head=b.value, ms_draw=c.value, failed=int(n.value))
 
     # ---- the largest elements of the resident train (include/ttx.h: ttx_topk) ----------------------------

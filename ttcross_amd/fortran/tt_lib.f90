@@ -73,6 +73,9 @@ module tt_lib
  interface basisval;    module procedure dtt_basisval; end interface
  ! samples drawn from the train on the device (not in the reference): sample(arg,u,ind,w,fixed,logq,val)
  interface sample;      module procedure dtt_sample;    end interface
+ ! real points drawn from the piecewise-linear interpolant of the train on the device (not in the reference):
+ ! sample_real(arg,u,nodes,x,cond,cell,logq,val)
+ interface sample_real; module procedure dtt_sample_real; end interface
  ! the largest elements of the train with a bound on the rest, on the device (not in the reference): topk(arg,k,ind,val,bound,which,fixed,mode)
  interface topk;        module procedure dtt_topk;      end interface
  ! sums and elementwise products on the device (not in the reference; its host + and * above stay as they are):
@@ -515,6 +518,45 @@ contains
   if(temp)call ttx_destroy(h)
   ind(1:arg%m,1:npts)=ix
   deallocate(uu,ix)
+ end subroutine
+ subroutine dtt_sample_real(arg,u,nodes,x,cond,cell,logq,val)
+  ! x(:,p) = a real point drawn with the uniforms u(:,p) from the piecewise-linear interpolant of the grid values arg on the nodes
+  ! nodes(1:n(k),k), strictly ascending, by the inverse Rosenblatt transform, the last mode first (include/ttx.h: ttx_sample_real):
+  ! for a train without sign changes the points follow the interpolant / Z.  cond(k): a NaN draws mode k, a number holds it at that
+  ! coordinate (absent: all drawn); cell(k,p) = the cell of a drawn mode, 0 for a held one; logq(p) = log of the proposal's density at
+  ! x(:,p); val(p) = the interpolant there (basisval with kind 2 on the same nodes).  A failed sample has x(:,p) NaN, cell 0, logq NaN,
+  ! val 0.  With no samples (size(u,2) = 0) nothing is called and no output is touched.  One call on the device; a host train is
+  ! staged for the call like for norm / dot_product.
+  use ttx_c
+  type(dtt),intent(in) :: arg
+  double precision,intent(in) :: u(:,:)
+  double precision,intent(in) :: nodes(:,:)
+  double precision,intent(out) :: x(:,:)
+  double precision,intent(in),optional :: cond(:)
+  integer,intent(out),optional :: cell(:,:)
+  double precision,intent(out),target,optional :: logq(:),val(:)
+  real(c_double),allocatable,target :: tt(:,:)
+  real(c_double),allocatable :: uu(:,:),xx(:,:)
+  integer(c_int32_t),allocatable,target :: cx(:,:)
+  real(c_double),target :: cc(tt_size)
+  type(c_ptr) :: h,cp,ip,lp,vp,rows(tt_size)
+  logical :: temp
+  integer :: npts,k
+  npts=size(u,2)
+  if(npts.eq.0)return
+  cp=c_null_ptr; ip=c_null_ptr; lp=c_null_ptr; vp=c_null_ptr
+  if(present(cond))then; cc(1:arg%m)=cond(1:arg%m); cp=c_loc(cc); endif
+  if(present(logq))lp=c_loc(logq)
+  if(present(val))vp=c_loc(val)
+  allocate(uu(arg%m,npts),xx(arg%m,npts),tt(maxval(arg%n(1:arg%m)),arg%m)); uu=u(1:arg%m,1:npts)
+  if(present(cell))then; allocate(cx(arg%m,npts)); ip=c_loc(cx); endif
+  do k=1,arg%m; tt(1:arg%n(k),k)=nodes(1:arg%n(k),k); rows(k)=c_loc(tt(1,k)); end do
+  call dtt_stage(arg,h,temp,'dtt_sample_real')
+  call ttx_check(ttx_sample_real(h,int(npts,c_int64_t),uu,rows,cp,xx,ip,lp,vp),'dtt_sample_real')
+  if(temp)call ttx_destroy(h)
+  x(1:arg%m,1:npts)=xx
+  if(present(cell))then; cell(1:arg%m,1:npts)=cx; deallocate(cx); endif
+  deallocate(uu,xx,tt)
  end subroutine
  subroutine dtt_topk(arg,k,ind,val,bound,which,fixed,mode,nfound)
   ! the k largest elements of arg by a beam search on the device (include/ttx.h: ttx_topk): ind(:,j) and val(j), j = 1 .. nfound,

@@ -187,6 +187,18 @@ module ttx_c
   function ttx_sample_last(h,ms_head,bytes_head,ms_draw,nfailed) bind(C,name='ttx_sample_last') result(rc)
    import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms_head,bytes_head,ms_draw; integer(c_int64_t),intent(out) :: nfailed; integer(c_int) :: rc
   end function
+  ! real-valued samples from the interpolant of the resident train (include/ttx.h); u(d,npts), x(d,npts), nodes(d) = the addresses
+  ! of the node rows; cond, cell, logq, val: c_null_ptr where not wanted
+  function ttx_sample_real(h,npts,u,nodes,cond,x,cell,logq,val) bind(C,name='ttx_sample_real') result(rc)
+   import; type(c_ptr),value :: h,cond,cell,logq,val; integer(c_int64_t),value :: npts; real(c_double),intent(in) :: u(*)
+   type(c_ptr),intent(in) :: nodes(*); real(c_double),intent(out) :: x(*); integer(c_int) :: rc
+  end function
+  function ttx_sample_real_dev(h,npts,u,nodes,cond,x,cell,logq,val) bind(C,name='ttx_sample_real_dev') result(rc)
+   import; type(c_ptr),value :: h,u,cond,x,cell,logq,val; integer(c_int64_t),value :: npts; type(c_ptr),intent(in) :: nodes(*); integer(c_int) :: rc
+  end function
+  function ttx_sample_real_last(h,ms_head,bytes_head,ms_draw,nfailed) bind(C,name='ttx_sample_real_last') result(rc)
+   import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms_head,bytes_head,ms_draw; integer(c_int64_t),intent(out) :: nfailed; integer(c_int) :: rc
+  end function
   ! the largest elements of the resident train (include/ttx.h); ind(d,K), val(K); fixed: c_null_ptr where not wanted
   function ttx_topk(h,k,which,fixed,mode,nfound,ind,val,bound) bind(C,name='ttx_topk') result(rc)
    import; type(c_ptr),value :: h,fixed; integer(c_int32_t),value :: k,which,mode; integer(c_int32_t),intent(out) :: nfound,ind(*)
