@@ -473,6 +473,54 @@ int ttx_sample(ttx_engine *h, int64_t npts, const double *u /* [npts][d] */, con
 int ttx_sample_dev(ttx_engine *h, int64_t npts, const double *u, const double *w, const int32_t *fixed, int32_t *ind, double *logq, double *val);
 int ttx_sample_last(const ttx_engine *h, double *ms_head, double *bytes_head, double *ms_draw, int64_t *nfailed);
 
+/* Samples drawn from the SQUARE of the resident train on the device (ttcross_amd/csrc/ttx_sample_sq.h): the squared-density sampler
+ * (SIRT: Cui and Dolgov, 2022) on grid indices.  ttx_sample draws from the product of the absolute conditional marginals, which is
+ * the target only for a train without sign changes; here the train approximates the square ROOT of the density (TTX_FUN_TRAINS
+ * builds it), every marginal of its square is a quadratic form with a Gram matrix, and every conditional is a sum of squares:
+ * non-negative whatever the signs of the cores.  u, fixed, ind, logq, val, the chunking (TTX_SAMPLE_CHUNK), the failed-sample
+ * convention and the refusal of multi-process engines are ttx_sample's.  The differences:
+ *   w     : NULL for all ones, or d blocks of n_k weights, finite and >= 0 (their square roots enter)
+ *   gamma : finite and >= 0, the defensive term below
+ *   mode  : TTX_EVAL_EXACT, TTX_EVAL_MFMA or TTX_EVAL_AUTO, as in ttx_topk: only the rows of p depend on it
+ * Definition (numpy restates it: tests/sample_sq_ref.py).  Modes are 1-based, r_0 = r_d = 1.  Effective weights e_k as for
+ * ttx_sample: w_k for a drawn mode, the indicator of f_k for a fixed one.  W_k = sum_i w_k(i) for a drawn mode (ascending i from
+ * 0.0) and 1 for a fixed one.  Weighted prefix Gram matrices: P_0 = [1], P_k = sum_i e_k(i) G_k(:, i, :)^T P_(k-1) G_k(:, i, :).
+ * They are never formed (y^T P y squares the conditioning); the call holds factors F_k of l_k = min(l_(k-1) n_k, r_k) rows with
+ * F_k^T F_k = 2^(-2 s_k) P_k, F_0 = [1], from one left-to-right pass:
+ *   H_k(a, i, b) = sum_a' F_(k-1)(a, a') G_k(a', i, b) (the engine's fp64 matrix-core GEMM; H_1 is a copy of G_1);
+ *   F_k = the R factor (the engine's Householder QR) of the matrix whose rows (a, i) are sqrt(e_k(i)) * H_k(a, i, :); where that
+ *   matrix has no more rows than columns, F_k is the matrix itself.  F_k is then multiplied by the power of two that takes its
+ *   largest entry into [0.5, 1) (none where that entry is 0 or not finite); s_k is the sum of these exponents up to k.  The
+ *   scaling is exact and cancels in every ratio below.
+ * Draw, from the LAST mode to the first, with the state x of dtt_ijk's chain, x_(d+1) = [1].  For a drawn mode k:
+ *   m(a, i) = sum_b H_k(a, i, b) x_(k+1)(b),  s(i) = sum_a m(a, i)^2.  TTX_EVAL_EXACT: both sums ascending from 0.0 with a separate
+ *   multiply and add.  TTX_EVAL_MFMA: the sum over b in the order of v_mfma_f64_16x16x4_f64 (steps of four b, ascending), the sum
+ *   over a ascending from 0.0 in a register (the 16 indices of a tile are the rows of the matrix operand, so no shuffle is needed);
+ *   p(i) = w_k(i) * (s(i) + g_k),  g_k = gamma * prod_(j<k) W_j * 2^(-2 s_(k-1)): the defensive term in the units of F_(k-1).
+ *   p >= 0 by construction, there is no absolute value.  The running sum c, t = u_k c(n_k), the search, "never an index with
+ *   p = 0", the state update in TTX_EVAL_EXACT's operation sequence and logq += log(p(i_k) / c(n_k)) are ttx_sample's, in both
+ *   modes: val equals ttx_ijk_batch(ind, TTX_EVAL_EXACT) bit for bit in both.  A fixed mode takes i_k = f_k and computes no p.
+ * Distribution, for ANY train, signed or not: the samples follow (T(i)^2 + gamma) prod w_k(i_k) / (Z + gamma prod W_k) exactly, up
+ * to rounding, over the drawn modes at the fixed indices, Z = sum_i T(i)^2 prod w.  Hence exp(logq) (Z + gamma prod W_k) =
+ * (val^2 + gamma) prod w_k(i_k), and with gamma > 0 the importance weight val^2 prod w / exp(logq) is bounded by Z + gamma prod W_k.
+ * Failed samples, safety, determinism: as for ttx_sample.  The sums s(i) of a chunk lie in a sheet [chunk][n_k] of the engine's work
+ * space; a sample's state, logq and failure flag stay there between the per-mode launches.  No floating-point atomics; a sample
+ * depends neither on its neighbours nor on the chunk; a call repeats bit for bit.  The train is not modified.
+ * TTX_EVAL_AUTO takes the matrix cores from TTX_SQ_AUTO_FLOPS flops of the call on (2 sum_k npts n_k l_(k-1) r_k, drawn modes).
+ * ttx_sample_sq_dev: u, ind, logq and val are pointers on the engine's device, w and fixed stay host pointers.
+ * npts = 0 succeeds and launches nothing.  TTX_EINVAL: npts < 0, null u / ind with npts > 0, an unknown mode, gamma negative or not
+ * finite (all before the engine is looked at); a fixed entry outside 0..n_k, a weight that is negative or not finite, ranks above
+ * 128, a chunk times the largest mode above 2^28 sheet entries (before any launch); TTX_ESTATE: an engine without a train; a
+ * multi-process engine is refused as by ttx_sample.
+ * ttx_sample_sq_last: of the last call on this engine, the milliseconds (HIP events) of the head pass, of the rows kernels and of
+ * k_sq_pick with k_sq_step (summed over modes and chunks), the flops of the rows, the failed samples and the mode that ran; any pointer may be
+ * NULL.  Open: the real-valued variant, per-sample weights, ranks above 128.  Added without a new ttx_version: look the symbols up. */
+int ttx_sample_sq    (ttx_engine *h, int64_t npts, const double *u /* [npts][d] */, const double *w, const int32_t *fixed,
+                      double gamma, int32_t mode, int32_t *ind, double *logq, double *val);
+int ttx_sample_sq_dev(ttx_engine *h, int64_t npts, const double *u, const double *w, const int32_t *fixed,
+                      double gamma, int32_t mode, int32_t *ind, double *logq, double *val);
+int ttx_sample_sq_last(const ttx_engine *h, double *ms_head, double *ms_rows, double *ms_pick, double *flops, int64_t *nfailed, int32_t *mode_ran);
+
 /* REAL-valued samples drawn from the piecewise-linear interpolant of a resident train of grid values, on the device
  * (ttcross_amd/csrc/ttx_sample_real.h): the inverse Rosenblatt transform of the interpolant that ttx_basis_batch evaluates with
  * TTX_BASIS_LINEAR, the conditional-distribution sampler of Dolgov, Anaya-Izquierdo, Fox and Scheichl (2020).  Uniforms in
@@ -524,7 +572,7 @@ int ttx_sample_last(const ttx_engine *h, double *ms_head, double *bytes_head, do
  * at); a node row that is missing, not finite or not strictly ascending, cond_k = +-Inf (before any device call); ranks above 128.
  * TTX_ESTATE: an engine without a train; a multi-process engine is refused as by ttx_sample.
  * ttx_sample_real_last: as ttx_sample_last, for k_sm_head and k_sr_draw of the last ttx_sample_real on this engine.
- * Open: a direct COS-basis sampler (root finding on a density that may go negative), the squared-density (SIRT) variant, an MFMA
+ * Open: a direct COS-basis sampler (root finding on a density that may go negative), the real-valued squared-density (SIRT) variant (ttx_sample_sq draws grid indices), an MFMA
  * path for the rows of p, extra per-mode weights, ranks above 128.  Added without a new ttx_version: look the symbols up. */
 int ttx_sample_real    (ttx_engine *h, int64_t npts, const double *u /* [npts][d] */, const double *const *nodes /* [d] host rows of n_k */,
                         const double *cond /* [d] or NULL */, double *x /* [npts][d] */, int32_t *cell /* [npts][d] or NULL */, double *logq, double *val);

@@ -56,6 +56,7 @@ static cluster_kernel_t cluster_kernel(int var)
 #include "ttx_sample.h"
 #include "ttx_sample_real.h"
 #include "ttx_topk.h"
+#include "ttx_sample_sq.h"
 #include "ttx_trainfun.h"
 
 static thread_local std::string g_err;
@@ -121,7 +122,8 @@ static int rccl_load()
 // single call uses both, because a second buf_reserve of a slot may move what the first one handed out.  ttx_sample_real is the widest
 // call, then ttx_sample: SC_TRAIN, SC_META, SC_W, SC_M, SC_VEC, SC_H, SC_ROW, SC_CNT and the staging slots (with SC_SRX) are all live in it.  ttx_topk keeps SC_TRAIN,
 // SC_META (its per-mode tables) and all seven SC_K* slots live from its first launch to its last copy, reserves each of them once,
-// before the first launch, and touches no other slot: what ttx_sample or ttx_marginals left in theirs stays as it was.
+// before the first launch, and touches no other slot: what ttx_sample or ttx_marginals left in theirs stays as it was.  ttx_sample_sq keeps
+// SC_META (weights, fixed), its four SC_Q* slots, SC_CNT and the staging slots of ttx_sample live, each reserved once before its first use.
 enum {
     SC_TRAIN,                           // the EvTrain block (ev_train): evaluation and sampling
     SC_META,                            // a call's tables (OpMeta): contraction, marginals, sampling; the AlgBlk table of the algebra
@@ -137,6 +139,7 @@ enum {
     SC_KREC, SC_KSEL, SC_KOUT,          // ttx_topk: the kept positions of every mode, the selection's state (words, chunk counts, histogram), the rows before and after the ordering
     SC_RSO, SC_RSW, SC_RSYA, SC_RSYB,   // ttx_lincomb_round: the sketch train Omega, the stacked W of all bonds, the two Y buffers
     SC_RSM, SC_RSTAB,                   // ttx_lincomb_round: M = Q^T Y (first the coefficients), the descriptor tables (RsBlk) and Omega's offsets
+    SC_QH, SC_QF, SC_QS, SC_QX,         // ttx_sample_sq: the tables H_k, the factors F_k (then the exponent and the d defensive terms), a mode's sheet, the states (two buffers, logq, flags)
     SC_BTAB,                            // ttx_basis_batch: the table of one mode for one chunk, chunk x max n (its states go to SC_XA / SC_XB, its nodes to SC_META)
     SC_NBUF
 };
@@ -255,10 +258,13 @@ struct ttx_engine {
     int ma_mode = -1;
     double tk_ms_gram = 0.0, tk_ms_score = 0.0, tk_ms_select = 0.0, tk_flops = 0.0;   // the last ttx_topk
     int tk_mode = -1;
+    double sq_ms_head = 0.0, sq_ms_rows = 0.0, sq_ms_pick = 0.0, sq_flops = 0.0;      // the last ttx_sample_sq
+    int64_t sq_failed = 0;
+    int sq_mode = -1;
     double rs_ms[4] = {0.0, 0.0, 0.0, 0.0}, rs_flops = 0.0;                    // the last ttx_lincomb_round with this engine first: sketch, gemm, qr, advance
     std::vector<int32_t> rs_l;                                                  // its sketch ranks l(0 .. d)
     int rs_mode = -1;
-    std::vector<hipEvent_t> rs_ev;                                              // the event chain of its left-to-right pass (RsMarks)
+    std::vector<hipEvent_t> rs_ev;                                              // the event chain of its left-to-right pass (RsMarks); ttx_sample_sq's rows and picks use it too
     double bs_ms_tab = 0.0, bs_ms_chain = 0.0, bs_flops = 0.0;                 // the last ttx_basis_batch / ttx_basis_tab: table launches, chain launches
     int bs_mode = -1;
     std::vector<hipEvent_t> bs_ev;                                              // its event chain: tables and chain steps alternate (bs_mark)
@@ -4113,6 +4119,163 @@ extern "C" int ttx_topk_last(const ttx_engine *h, double *ms_gram, double *ms_sc
     if (ms_select) *ms_select = h->tk_ms_select;
     if (flops) *flops = h->tk_flops;
     if (mode_ran) *mode_ran = h->tk_mode;
+    return TTX_OK;
+}
+
+// ---- samples from the square of the resident train (ttx_sample_sq.h) -----------------------------------------------------------
+namespace {
+struct SqHead {                             // what sq_head leaves for the draw (and, later, for a real-valued variant): tables on the device
+    double *H = nullptr, *F = nullptr, *g = nullptr;    // SqPlan's H and F tables; g[k]: the defensive term of 0-based mode k in the units of F_k
+    const double *w = nullptr;              // the effective weights
+    const int *fixed = nullptr;
+};
+}
+// The one left-to-right pass: F_k and H_k by the plan pl for the effective weights eff (mode k at pl.woff[k]) and gw[k] = gamma prod_(j < k) W_j.
+// Between TM_HEAD's events; the resident train is only read.
+static int sq_head(ttx_engine *h, const SqPlan &pl, const std::vector<double> &eff, const std::vector<int> &fx, const std::vector<double> &gw, SqHead &Q)
+{
+    int rc;
+    const int d = h->d;
+    const std::vector<int32_t> &r = h->rfinal;
+    OpMeta meta(h->meta_host);
+    const size_t o_w = meta.put(eff), o_fx = meta.put(fx);
+    char *dm;
+    if ((rc = meta.upload(h, SC_META, &dm)) || (rc = buf_reserve(h, SC_QH, sizeof(double) * pl.hoff[d])) ||
+        (rc = buf_reserve(h, SC_QF, sizeof(double) * (pl.foff[d] + (size_t)d + 2)))) return rc;
+    Q.w = (const double *)(dm + o_w); Q.fixed = (const int *)(dm + o_fx);
+    Q.H = buf<double>(h, SC_QH); Q.F = buf<double>(h, SC_QF); Q.g = Q.F + pl.foff[d];
+    int *st = (int *)(Q.g + d);
+    const TtScratch s(h);
+    OpTimer &t_head = h->timer[TM_HEAD];
+    if ((rc = t_head.start(h->stream))) return rc;
+    hipLaunchKernelGGL(k_sq_init, dim3(1), dim3(64), 0, h->stream, Q.F, Q.g, st, gw[0]);      // F_0 = [1], no exponent yet
+    for (int k = 1; k <= d; k++) {
+        const int r0 = r[k - 1], n = h->n1[k], r1 = r[k], r1p = (r1 + 3) & ~3, l = pl.l[k - 1], mm = l * n;
+        pack_core(h->stream, h, k, h->Wb);
+        gemm(h, l, n * r1, r0, Q.F + pl.foff[k - 1], l, h->Wb, r0, h->Wc, l);
+        hipLaunchKernelGGL(k_sq_split, g1((size_t)mm * r1p), dim3(256), 0, h->stream, (const double *)h->Wc, l, n, r1, r1p, Q.w + pl.woff[k - 1], Q.H + pl.hoff[k - 1],
+                           k < d ? h->Wa : (double *)nullptr);
+        if (k == d) break;
+        const double *R = h->Wa;
+        int ldr = mm;
+        if (mm > r1) { if ((rc = qr(h, mm, r1, h->Wa, s.Rm, s.tau))) return rc; R = s.Rm; ldr = r1; }
+        hipLaunchKernelGGL(k_sq_pow2, dim3(1), dim3(1024), 0, h->stream, pl.l[k], r1, R, ldr, Q.F + pl.foff[k], st, gw[k], Q.g + k);
+    }
+    if ((rc = t_head.stop(h->stream))) return rc;
+    HIPCHECK(hipGetLastError());
+    return TTX_OK;
+}
+template <int KS>
+static void sq_rows_mfma(ttx_engine *h, dim3 grid, const double *H, int l, int n, int r1, const double *X, int ldx, int C, int tper, double *S)
+{
+    hipLaunchKernelGGL(k_sq_rows_mfma<KS>, grid, dim3(256), 0, h->stream, H, l, n, r1, X, ldx, C, tper, S);
+}
+// both entries: u, ind, logq, val are host pointers (dev false: staged chunk by chunk) or pointers on the engine's device
+static int sq_run(ttx_engine *h, const char *who, int64_t npts, const double *u, const double *w, const int32_t *fixed, double gamma, int32_t mode, int32_t *ind,
+                  double *logq, double *val, bool dev)
+{
+    if (npts < 0 || (npts > 0 && (!u || !ind))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
+    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    if (!(gamma >= 0.0) || !std::isfinite(gamma)) return fail(TTX_EINVAL, "%s: gamma must be a finite number >= 0 (got %g)", who, gamma);
+    int rc = check_train_one_process(h, who);
+    if (rc) return rc;
+    const int d = h->d;
+    std::vector<int> fx(d, 0);
+    for (int k = 0; k < d; k++) {
+        if (fixed && (fixed[k] < 0 || fixed[k] > h->n1[k + 1])) return fail(TTX_EINVAL, "%s: fixed(%d) = %d (0 .. %d expected)", who, k + 1, fixed[k], h->n1[k + 1]);
+        if (fixed) fx[k] = fixed[k];
+    }
+    SqPlan pl;
+    sq_plan(d, h->n1.data() + 1, h->rfinal.data(), fx.data(), pl);
+    const int rmax = pl.rmax, nmax = pl.nmax;
+    if (rmax > 128) return fail(TTX_EINVAL, "%s: ranks up to 128 only (got %d)", who, rmax);
+    if (w) { const long long j = sq_bad_weight(w, pl.woff[d]); if (j >= 0) return fail(TTX_EINVAL, "%s: weight %lld is %g (finite and >= 0 expected: its square root enters)", who, j + 1, w[j]); }
+    const size_t chunk = std::min<size_t>(env_chunk("TTX_SAMPLE_CHUNK", (size_t)1 << 18), (size_t)std::max<int64_t>(npts, 1));
+    if ((long long)chunk * nmax > TTX_SQ_SHEET)
+        return fail(TTX_EINVAL, "%s: a chunk of %zu samples times the largest mode %d is %lld, the sheet holds up to %lld (lower TTX_SAMPLE_CHUNK)", who, chunk, nmax,
+                    (long long)chunk * nmax, (long long)TTX_SQ_SHEET);
+    h->sq_ms_head = h->sq_ms_rows = h->sq_ms_pick = h->sq_flops = 0.0; h->sq_failed = 0; h->sq_mode = -1;
+    if (npts == 0) return TTX_OK;
+    if ((rc = tt_prepare(h, who))) return rc;
+    std::vector<double> eff, gw;
+    sq_effective(d, h->n1.data() + 1, fx.data(), w, gamma, eff, gw);
+    SqHead Q;
+    if ((rc = sq_head(h, pl, eff, fx, gw, Q))) return rc;
+    const double flops = pl.flops * (double)npts;
+    const int eff_mode = mode == TTX_EVAL_AUTO ? (flops >= TTX_SQ_AUTO_FLOPS ? TTX_EVAL_MFMA : TTX_EVAL_EXACT) : mode;
+    h->sq_flops = flops; h->sq_mode = eff_mode;
+    const int ldx = (rmax + 3) & ~3, ncu = dev_ncu(h);
+    if ((rc = buf_reserve(h, SC_QS, sizeof(double) * chunk * nmax)) || (rc = buf_reserve(h, SC_QX, (sizeof(double) * (2 * (size_t)ldx + 1) + sizeof(int)) * chunk)) ||
+        (rc = buf_reserve(h, SC_CNT, sizeof(long long)))) return rc;
+    double *S = buf<double>(h, SC_QS), *Xa = buf<double>(h, SC_QX), *Xb = Xa + chunk * ldx;
+    SqState st{Xb + chunk * ldx, nullptr};
+    st.fail = (int *)(st.lq + chunk);
+    SmPrep P;
+    P.chunk = chunk; P.gridmax = (int)std::min<long long>(((long long)chunk + 3) / 4, (long long)ncu * 8);
+    P.dcnt = buf<long long>(h, SC_CNT);
+    HIPCHECK(hipMemsetAsync(P.dcnt, 0, sizeof(long long), h->stream));
+    SmStage out[3] = {{ind, sizeof(int) * (size_t)d, SC_IND, nullptr}, {logq, sizeof(double), SC_LQ, nullptr}, {val, sizeof(double), SC_OUT, nullptr}};
+    RsMarks marks(h->rs_ev);                // phase 0: between the chunks, 1: rows, 2: picks
+    int lrc = TTX_OK;
+    double ms_all = 0.0;
+    rc = sm_chunks(h, P, npts, u, dev, out, 3,
+        [&](size_t c, int grid, const double *du) {
+            const int C = (int)c;
+            double *Xo = Xa, *Xn = Xb;
+            hipLaunchKernelGGL(k_sq_ones, g1(c), dim3(256), 0, h->stream, Xo, ldx, C);          // x of the empty suffix
+            if (!lrc) lrc = marks.mark(h->stream, 0);
+            for (int k = d - 1; k >= 0; k--) {
+                const int r0 = h->rfinal[k], r1 = h->rfinal[k + 1], n = h->n1[k + 1], l = pl.l[k];
+                if (!fx[k]) {
+                    const double *Hk = Q.H + pl.hoff[k];
+                    if (eff_mode == TTX_EVAL_MFMA) {
+                        const int by = (C + 63) / 64, nt = (n + 15) / 16, tper = (int)std::max<long long>(1, (long long)nt * by / (4ll * ncu));
+                        const dim3 g((nt + tper - 1) / tper, by);
+                        if (r1 <= 16) sq_rows_mfma<4>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S);
+                        else if (r1 <= 32) sq_rows_mfma<8>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S);
+                        else if (r1 <= 64) sq_rows_mfma<16>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S);
+                        else sq_rows_mfma<32>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S);
+                    } else {
+                        const int g = (int)std::min<long long>(((long long)C * n + 255) / 256, (long long)ncu * 16);
+                        hipLaunchKernelGGL(k_sq_rows_exact, dim3(g), dim3(256), 0, h->stream, Hk, l, n, r1, (const double *)Xo, ldx, C, S);
+                    }
+                    if (!lrc) lrc = marks.mark(h->stream, 1);
+                }
+                hipLaunchKernelGGL(k_sq_pick, dim3(grid), dim3(256), 0, h->stream, n, k, d, fx[k] - 1, Q.fixed, Q.w + pl.woff[k], (const double *)(Q.g + k), (const double *)S, st,
+                                   (long long)c, du, k == d - 1 ? 1 : 0, k == 0 ? 1 : 0, (int *)out[0].dev, (double *)out[1].dev);
+                hipLaunchKernelGGL(k_sq_step, dim3(grid), dim3(256), 0, h->stream, (const double *)core_dev(h, k + 1), h->RM, h->P.SS, r0, r1, n, k, d, (const int *)out[0].dev,
+                                   (const int *)st.fail, (const double *)Xo, Xn, ldx, (long long)c, k == d - 1 ? 1 : 0, k == 0 ? 1 : 0, (double *)out[2].dev);
+                if (!lrc) lrc = marks.mark(h->stream, 2);
+                std::swap(Xo, Xn);
+            }
+        },
+        [&](size_t c) { hipLaunchKernelGGL(k_sm_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const int *)out[0].dev, P.dcnt); },
+        &ms_all, &h->sq_failed);
+    if (rc || (rc = lrc)) return rc;
+    double ms[3] = {0.0, 0.0, 0.0};
+    if ((rc = marks.sum(ms))) return rc;
+    h->sq_ms_rows = ms[1]; h->sq_ms_pick = ms[2];
+    return h->timer[TM_HEAD].ms(&h->sq_ms_head);
+}
+extern "C" int ttx_sample_sq(ttx_engine *h, int64_t npts, const double *u, const double *w, const int32_t *fixed, double gamma, int32_t mode, int32_t *ind, double *logq,
+                             double *val)
+{
+    return sq_run(h, "ttx_sample_sq", npts, u, w, fixed, gamma, mode, ind, logq, val, false);
+}
+extern "C" int ttx_sample_sq_dev(ttx_engine *h, int64_t npts, const double *u, const double *w, const int32_t *fixed, double gamma, int32_t mode, int32_t *ind, double *logq,
+                                 double *val)
+{
+    return sq_run(h, "ttx_sample_sq_dev", npts, u, w, fixed, gamma, mode, ind, logq, val, true);
+}
+extern "C" int ttx_sample_sq_last(const ttx_engine *h, double *ms_head, double *ms_rows, double *ms_pick, double *flops, int64_t *nfailed, int32_t *mode_ran)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_sample_sq_last: null engine");
+    if (ms_head) *ms_head = h->sq_ms_head;
+    if (ms_rows) *ms_rows = h->sq_ms_rows;
+    if (ms_pick) *ms_pick = h->sq_ms_pick;
+    if (flops) *flops = h->sq_flops;
+    if (nfailed) *nfailed = h->sq_failed;
+    if (mode_ran) *mode_ran = h->sq_mode;
     return TTX_OK;
 }
 

@@ -12,6 +12,7 @@ runs on the GPU through ttcross_amd.engine.  Usage:
     python -m ttcross_amd.drivers roundsum WORKLOAD M [RANK] [MODE] (rounded sum of M terms made from the workload's train: lincomb_round)
     python -m ttcross_amd.drivers compose WORKLOAD OP [MAXRANK] (cross approximation of product | ratio | sqrtabs of the workload's train)
     python -m ttcross_amd.drivers samplereal WORKLOAD NPTS[,NPTS...] (real-valued samples from the interpolant of the workload's train: sample_real)
+    python -m ttcross_amd.drivers samplesq WORKLOAD NPTS [MODE] [REPEATS] (samples from the square of the workload's train: sample_sq; WORKLOAD signed: importance weights)
 
 devfun: the rational example integrand (examples/devfun/rational.hip) as a LOADED device integrand (TTX_FUN_DEVICE), in its
 wave form, or -- host -- its C twin through the host callback (TTX_FUN_HOST; needs gcc); SOURCE.hip NAME loads another
@@ -814,6 +815,119 @@ def run_sample(argv, device=0, repeats=5, tt=None, host_npts=1000):
     return out
 
 
+def signed_density_train(device=0, d=6, n=33):
+    """A density with the sign changes a cross approximation leaves in its tails: two separable Gaussian bumps on [0, 1]^d minus a
+    small constant, as a rank-3 train.  Negative on most of the grid by count, positive where the mass is."""
+    t = np.linspace(0.0, 1.0, n)
+    parts = [[np.exp(-0.5 * ((t - 0.35) / 0.08) ** 2)] * d, [0.6 * np.exp(-0.5 * ((t - 0.7) / 0.06) ** 2)] + [np.exp(-0.5 * ((t - 0.7) / 0.06) ** 2)] * (d - 1),
+             [-2e-3 * np.ones(n)] + [np.ones(n)] * (d - 1)]
+    cores = []
+    for k in range(d):
+        r0, r1 = (1 if k == 0 else 3), (1 if k == d - 1 else 3)
+        c = np.zeros((r0, n, r1))
+        for j in range(3):
+            c[0 if k == 0 else j, :, 0 if k == d - 1 else j] = parts[j][k]
+        cores.append(c)
+    return TTCross.from_cores(cores, device=device)
+
+
+def sample_sq_host(tt, u, w=None, gamma=0.0):
+    """what a user does without ttx_sample_sq: every core to the host with core(k), the factors of the weighted prefix Gram matrices by
+    numpy's QR, then the conditionals of the square walked in numpy from the last mode to the first.  Returns (ind, logq, val)."""
+    cores = [tt.core(k) for k in range(1, tt.d + 1)]
+    w = [np.ones(c.shape[1]) for c in cores] if w is None else [np.asarray(q, dtype=np.float64) for q in w]
+    u = np.asarray(u, dtype=np.float64)
+    npts, d = u.shape
+    F, g, H, gs = np.ones((1, 1)), float(gamma), [], []
+    for c, q in zip(cores, w):
+        H.append(np.tensordot(F, c, axes=([1], [0])))
+        gs.append(g)
+        A = (np.sqrt(q)[None, :, None] * H[-1]).reshape(-1, c.shape[2])
+        F = np.linalg.qr(A, mode="r") if A.shape[0] > A.shape[1] else A
+        m = np.abs(F).max()
+        ex = int(np.frexp(m)[1]) if m > 0 and np.isfinite(m) else 0
+        F, g = np.ldexp(F, -ex), g * q.sum() * 4.0 ** -ex
+    x = np.ones((npts, 1))
+    ind, logq, rows = np.zeros((npts, d), dtype=np.int32), np.zeros(npts), np.arange(npts)
+    for k in range(d - 1, -1, -1):
+        m = np.tensordot(H[k], x, axes=([2], [1]))                 # (a, i, sample)
+        p = w[k][None, :] * ((m * m).sum(0).T + gs[k])
+        c = np.cumsum(p, axis=1)
+        hit = (p > 0) & (u[:, k:k + 1] * c[:, -1:] < c)
+        i = np.where(hit.any(1), hit.argmax(1), p.shape[1] - 1 - (p[:, ::-1] > 0).argmax(1))
+        logq += np.log(p[rows, i] / c[:, -1])
+        ind[:, k] = i + 1
+        x = np.einsum("asb,sb->sa", cores[k][:, i, :], x)
+    return ind, logq, x[:, 0]
+
+
+def run_samplesq(argv, device=0, repeats=5, tt=None, host_npts=1000):
+    """samplesq WORKLOAD NPTS [MODE] [REPEATS]: the trains of the sample sub-command (or "signed": signed_density_train), weights 1 / n, seeded
+    uniforms made ON the device; one warm-up and the median of `repeats` calls of sample_sq through the device-pointer entry: the
+    call, the head pass, the rows kernels and the picks (HIP events, ttx_sample_sq_last), samples per second and the fp64 rate of
+    the rows; sample() on the same uniforms and train next to it; then the host route sample_sq_host once at host_npts samples.
+    On the signed workload the target is |T| / Z: the largest importance weight |T| / q over its mean under sample() on T and under
+    sample_sq() on the cross approximation of sqrt |T| (of_trains, sqrtabs), with and without a defensive term.  One JSON line each."""
+    import json
+    import time
+    import torch
+    torch.cuda.init()          # a torch that brings its own HIP runtime must initialise its device before the engine's library does
+    workload, npts = argv[0], int(float(argv[1]))
+    mode = argv[2] if len(argv) > 2 else "auto"
+    repeats = int(argv[3]) if len(argv) > 3 else repeats
+    tt = tt or (signed_density_train(device) if workload == "signed" else tijk_train(workload, device=device))
+    dev = torch.device("cuda", device)
+    w = [np.full(int(nk), 1.0 / int(nk)) for nk in tt._n]
+    g = torch.Generator(device=dev)
+    g.manual_seed(20240607)
+    u = torch.rand((npts, tt.d), dtype=torch.float64, device=dev, generator=g)
+    torch.cuda.synchronize(dev)
+
+    def timed(call, last):
+        call()
+        ms, figs = [], []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            res = call()                          # synchronises before it returns
+            ms.append((time.perf_counter() - t0) * 1e3)
+            figs.append(last())
+        return res, float(np.median(ms)), {k: float(np.median([f[k] for f in figs])) for k in figs[0] if isinstance(figs[0][k], float)}, figs[-1]
+
+    res, call_ms, med, last = timed(lambda: tt.sample_sq(u, w, mode=mode), tt.sample_sq_last)
+    val = tt.tijk_batch(res["ind"], "exact")
+    _, s_ms, s_med, s_last = timed(lambda: tt.sample(u, w), tt.sample_last)
+    rows_ms = med["ms_rows"]
+    out = [dict(workload=workload, npts=npts, d=tt.d, max_rank=int(tt.ranks().max()), mode_asked=mode, mode=last["mode"], call_ms=call_ms,
+                head_ms=med["ms_head"], rows_ms=rows_ms, pick_ms=med["ms_pick"], samples_per_s=npts / (call_ms * 1e-3), rows_flops=last["flops"],
+                rows_flops_per_s=last["flops"] / (rows_ms * 1e-3) if rows_ms > 0 else None, failed=last["failed"],
+                val_is_tijk=bool(torch.equal(val, res["val"])), mean_logq=float(res["logq"].mean().item()),
+                sample_call_ms=s_ms, sample_head_ms=s_med["ms_head"], sample_draw_ms=s_med["ms_draw"], time_ratio_to_sample=call_ms / s_ms if s_ms > 0 else None)]
+    print(json.dumps(out[0]), flush=True)
+    uh = np.random.default_rng(7).random((host_npts, tt.d))
+    t0 = time.perf_counter()
+    hi, hq, hv = sample_sq_host(tt, uh, w)
+    host_ms = (time.perf_counter() - t0) * 1e3
+    di = tt.sample_sq(uh, w, mode="exact")["ind"]
+    out.append(dict(workload=workload, host_route_npts=host_npts, host_route_ms=host_ms, host_samples_per_s=host_npts / (host_ms * 1e-3),
+                    host_rows_equal_device=int(np.all(hi == di, axis=1).sum())))
+    print(json.dumps(out[-1]), flush=True)
+    if workload == "signed":
+        def spread(ind, logq):
+            iw = torch.abs(tt.tijk_batch(ind, "exact")) / torch.exp(logq)
+            return float((iw.max() / iw.mean()).item()), float((iw.sum() ** 2 / (iw * iw).sum() / iw.numel()).item())
+        plain = tt.sample(u, w)
+        root = TTCross.of_trains([tt], "sqrtabs", 12, accuracy=500 * EPS, pivoting=2, quad=w, device=device).run()
+        r = dict(workload=workload, npts=npts, root_max_rank=int(root.ranks().max()))
+        r["sample_max_over_mean"], r["sample_ess_fraction"] = spread(plain["ind"], plain["logq"])
+        for gam in (0.0, 1e-6):
+            sq = root.sample_sq(u, w, gamma=gam, mode=mode)
+            key = "sample_sq" if gam == 0.0 else "sample_sq_gamma_%g" % gam
+            r[key + "_max_over_mean"], r[key + "_ess_fraction"] = spread(sq["ind"], sq["logq"])
+        print(json.dumps(r), flush=True)
+        out.append(r)
+    return out
+
+
 def sample_real_host(tt, u, nodes):
     """what a user does without ttx_sample_real: every core to the host with core(k), then the interpolated conditionals walked in
     numpy from the last mode to the first and inverted cell by cell.  Returns (x, logq, val) of the definition in include/ttx.h,
@@ -1076,6 +1190,8 @@ if __name__ == "__main__":
         run_sample(sys.argv[2:])
     elif sys.argv[1] == "samplereal":
         run_samplereal(sys.argv[2:])
+    elif sys.argv[1] == "samplesq":
+        run_samplesq(sys.argv[2:])
     elif sys.argv[1] == "topk":
         run_topk(sys.argv[2:])
     elif sys.argv[1] == "contract":

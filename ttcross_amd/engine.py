@@ -134,6 +134,10 @@ def load_library():
                                   POINTER(c_double)]
     L.ttx_sample_real_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(POINTER(c_double)), POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p]
     L.ttx_sample_real_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
+    L.ttx_sample_sq.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_int32), c_double, c_int32, POINTER(c_int32), POINTER(c_double),
+                                POINTER(c_double)]
+    L.ttx_sample_sq_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(c_double), POINTER(c_int32), c_double, c_int32, c_void_p, c_void_p, c_void_p]
+    L.ttx_sample_sq_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64), POINTER(c_int32)]
     L.ttx_topk.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_int32), c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
     L.ttx_topk_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
     L.ttx_zquad.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
@@ -991,6 +995,69 @@ class TTCross:
         a, b, c, n = c_double(), c_double(), c_double(), c_int64()
         _check(load_library().ttx_sample_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(n)))
         return dict(ms_head=a.value, bytes_head=b.value, ms_draw=c.value, failed=int(n.value))
+
+    # ---- samples from the square of the resident train (include/ttx.h: ttx_sample_sq) ---------------------
+    def sample_sq(self, u_or_npts, w=None, fixed=None, gamma=0.0, mode="auto", seed=None, want=("ind", "logq", "val")):
+        """Indices drawn from the SQUARE of the train on the device, the squared-density sampler (include/ttx.h: ttx_sample_sq):
+        for any train, signed or not, they follow (T(i)^2 + gamma) w(i) / (Z + gamma prod W_k).  The train is meant to
+        approximate the square root of a density (of_trains with a sqrt-abs combiner builds it).  u_or_npts, fixed, seed, want and
+        the returned dict are sample()'s; w as for quad, finite and non-negative; gamma >= 0 is the defensive term; mode is
+        "exact", "mfma" or "auto" (only the rows of p depend on it; val is tijk_batch(ind, "exact") bit for bit either way).
+        sample_sq_last() counts the failed samples.  A contiguous float64 torch tensor on the engine's device is passed by
+        pointer (ttx_sample_sq_dev) and gives torch tensors on that device."""
+        L = load_library()
+        bad = set(want) - {"ind", "logq", "val"}
+        if bad:
+            raise ValueError(f"sample_sq: unknown output {sorted(bad)}")
+        md = _eval_mode(mode)
+        wa = self._weights(w, "sample_sq")
+        fx = None
+        if fixed is not None:
+            fx = np.ascontiguousarray(fixed, dtype=np.int32).ravel()
+            if fx.size != self.d:
+                raise ValueError(f"sample_sq: {self.d} fixed entries expected")
+        if type(u_or_npts).__module__.split(".")[0] == "torch":
+            import torch
+            u = u_or_npts
+            if not u.is_cuda:
+                return {k: torch.from_numpy(v) for k, v in self.sample_sq(u.numpy(), w, fixed, gamma, mode, seed, want).items()}
+            if u.device.index != self.device:
+                raise ValueError(f"sample_sq: the tensor lies on {u.device}, the engine on device {self.device}")
+            if u.dtype != torch.float64 or not u.is_contiguous() or u.dim() != 2 or u.shape[1] != self.d:
+                raise ValueError(f"sample_sq: a contiguous float64 tensor of shape (npts, {self.d}) expected")
+            npts = u.shape[0]
+            ind = torch.empty((npts, self.d), dtype=torch.int32, device=u.device)
+            lq = torch.empty(npts, dtype=torch.float64, device=u.device) if "logq" in want else None
+            va = torch.empty(npts, dtype=torch.float64, device=u.device) if "val" in want else None
+            torch.cuda.current_stream(u.device).synchronize()        # the engine runs on a stream of its own
+            _check(L.ttx_sample_sq_dev(self._h, npts, c_void_p(u.data_ptr()), _dp(wa), _ip(fx), float(gamma), md, c_void_p(ind.data_ptr()),
+                                       c_void_p(lq.data_ptr()) if lq is not None else None, c_void_p(va.data_ptr()) if va is not None else None))
+            out = dict(ind=ind, logq=lq, val=va)
+            return {k: out[k] for k in ("ind", "logq", "val") if k in want}
+        if np.ndim(u_or_npts) == 0:
+            npts = int(u_or_npts)
+            if npts < 0:
+                raise ValueError("sample_sq: a negative count")
+            u = np.random.default_rng(seed).random((npts, self.d))
+        else:
+            u = np.ascontiguousarray(u_or_npts, dtype=np.float64)
+            if u.ndim != 2 or u.shape[1] != self.d:
+                raise ValueError(f"sample_sq: an array of shape (npts, {self.d}) expected")
+        npts = u.shape[0]
+        ind = np.zeros((npts, self.d), dtype=np.int32)
+        lq = np.zeros(npts) if "logq" in want else None
+        va = np.zeros(npts) if "val" in want else None
+        _check(L.ttx_sample_sq(self._h, npts, _dp(u), _dp(wa), _ip(fx), float(gamma), md, _ip(ind), _dp(lq), _dp(va)))
+        out = dict(ind=ind, logq=lq, val=va)
+        return {k: out[k] for k in ("ind", "logq", "val") if k in want}
+
+    def sample_sq_last(self):
+        """dict(ms_head, ms_rows, ms_pick, flops, failed, mode) of the last sample_sq() on this engine (include/ttx.h:
+        ttx_sample_sq_last); mode is "exact" or "mfma" (None before the first call)"""
+        a, b, c, fl, n, md = c_double(), c_double(), c_double(), c_double(), c_int64(), c_int32()
+        _check(load_library().ttx_sample_sq_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(fl), ctypes.byref(n), ctypes.byref(md)))
+        names = {v: k for k, v in EVAL_MODES.items()}
+        return dict(ms_head=a.value, ms_rows=b.value, ms_pick=c.value, flops=fl.value, failed=int(n.value), mode=names.get(md.value))
 
     # ---- real-valued samples from the interpolant of the train (include/ttx.h: ttx_sample_real) -----------
     def _node_rows(self, nodes, who):

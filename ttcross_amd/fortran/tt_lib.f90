@@ -76,6 +76,8 @@ module tt_lib
  ! real points drawn from the piecewise-linear interpolant of the train on the device (not in the reference):
  ! sample_real(arg,u,nodes,x,cond,cell,logq,val)
  interface sample_real; module procedure dtt_sample_real; end interface
+ ! samples from the square of the train, the squared-density sampler: sample_sq(arg,u,ind,w,fixed,gamma,mode,logq,val)
+ interface sample_sq;   module procedure dtt_sample_sq;   end interface
  ! the largest elements of the train with a bound on the rest, on the device (not in the reference): topk(arg,k,ind,val,bound,which,fixed,mode)
  interface topk;        module procedure dtt_topk;      end interface
  ! sums and elementwise products on the device (not in the reference; its host + and * above stay as they are):
@@ -515,6 +517,43 @@ contains
   allocate(uu(arg%m,npts),ix(arg%m,npts)); uu=u(1:arg%m,1:npts)
   call dtt_stage(arg,h,temp,'dtt_sample')
   call ttx_check(ttx_sample(h,int(npts,c_int64_t),uu,wp,fp,ix,lp,vp),'dtt_sample')
+  if(temp)call ttx_destroy(h)
+  ind(1:arg%m,1:npts)=ix
+  deallocate(uu,ix)
+ end subroutine
+ subroutine dtt_sample_sq(arg,u,ind,w,fixed,gamma,mode,logq,val)
+  ! ind(:,p) = a multi-index drawn from the SQUARE of arg with the uniforms u(:,p), the squared-density sampler (include/ttx.h:
+  ! ttx_sample_sq): for any train, signed or not, the indices follow (arg(i)^2 + gamma) w(i) / (Z + gamma prod W).  arg is meant to
+  ! approximate the square root of a density.  w, fixed, logq, val as for sample, the weights non-negative; gamma >= 0 the defensive
+  ! term (absent: 0); mode 0 = exact, 1 = MFMA, 2 = auto (absent: auto).  val(p) = arg at ind(:,p), not its square.
+  use ttx_c
+  type(dtt),intent(in) :: arg
+  double precision,intent(in) :: u(:,:)
+  integer,intent(out) :: ind(:,:)
+  type(dtt),intent(in),optional :: w
+  integer,intent(in),optional :: fixed(:),mode
+  double precision,intent(in),optional :: gamma
+  double precision,intent(out),target,optional :: logq(:),val(:)
+  real(c_double),allocatable,target :: ww(:)
+  real(c_double),allocatable :: uu(:,:)
+  integer(c_int32_t),allocatable :: ix(:,:)
+  integer(c_int32_t),target :: fx(tt_size)
+  type(c_ptr) :: h,wp,fp,lp,vp
+  real(c_double) :: gm
+  logical :: temp
+  integer :: npts,md
+  npts=size(u,2)
+  if(npts.eq.0)return
+  wp=c_null_ptr; fp=c_null_ptr; lp=c_null_ptr; vp=c_null_ptr
+  gm=0.d0; if(present(gamma))gm=gamma
+  md=2; if(present(mode))md=mode
+  if(present(w))then; call dtt_weights(arg,w,ww); wp=c_loc(ww); endif
+  if(present(fixed))then; fx(1:arg%m)=fixed(1:arg%m); fp=c_loc(fx); endif
+  if(present(logq))lp=c_loc(logq)
+  if(present(val))vp=c_loc(val)
+  allocate(uu(arg%m,npts),ix(arg%m,npts)); uu=u(1:arg%m,1:npts)
+  call dtt_stage(arg,h,temp,'dtt_sample_sq')
+  call ttx_check(ttx_sample_sq(h,int(npts,c_int64_t),uu,wp,fp,gm,int(md,c_int32_t),ix,lp,vp),'dtt_sample_sq')
   if(temp)call ttx_destroy(h)
   ind(1:arg%m,1:npts)=ix
   deallocate(uu,ix)

@@ -187,6 +187,19 @@ module ttx_c
   function ttx_sample_last(h,ms_head,bytes_head,ms_draw,nfailed) bind(C,name='ttx_sample_last') result(rc)
    import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms_head,bytes_head,ms_draw; integer(c_int64_t),intent(out) :: nfailed; integer(c_int) :: rc
   end function
+  ! samples drawn from the square of the resident train (include/ttx.h); as ttx_sample, with gamma and mode by value
+  function ttx_sample_sq(h,npts,u,w,fixed,gamma,mode,ind,logq,val) bind(C,name='ttx_sample_sq') result(rc)
+   import; type(c_ptr),value :: h,w,fixed,logq,val; integer(c_int64_t),value :: npts; real(c_double),intent(in) :: u(*)
+   real(c_double),value :: gamma; integer(c_int32_t),value :: mode; integer(c_int32_t),intent(out) :: ind(*); integer(c_int) :: rc
+  end function
+  function ttx_sample_sq_dev(h,npts,u,w,fixed,gamma,mode,ind,logq,val) bind(C,name='ttx_sample_sq_dev') result(rc)
+   import; type(c_ptr),value :: h,u,w,fixed,ind,logq,val; integer(c_int64_t),value :: npts; real(c_double),value :: gamma
+   integer(c_int32_t),value :: mode; integer(c_int) :: rc
+  end function
+  function ttx_sample_sq_last(h,ms_head,ms_rows,ms_pick,flops,nfailed,mode_ran) bind(C,name='ttx_sample_sq_last') result(rc)
+   import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms_head,ms_rows,ms_pick,flops; integer(c_int64_t),intent(out) :: nfailed
+   integer(c_int32_t),intent(out) :: mode_ran; integer(c_int) :: rc
+  end function
   ! real-valued samples from the interpolant of the resident train (include/ttx.h); u(d,npts), x(d,npts), nodes(d) = the addresses
   ! of the node rows; cond, cell, logq, val: c_null_ptr where not wanted
   function ttx_sample_real(h,npts,u,nodes,cond,x,cell,logq,val) bind(C,name='ttx_sample_real') result(rc)
