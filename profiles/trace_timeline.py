@@ -2,11 +2,17 @@
 
 usage: python3 profiles/trace_timeline.py DIR [START [COUNT]]
        python3 profiles/trace_timeline.py DIR tail
+       python3 profiles/trace_timeline.py DIR ends
 START: index into the list of k_sweep_cluster launches (negative counts from the end) at which to begin, or the word
 `run` to begin at the k_init_samples launch of the 3rd complete run; COUNT: rows to print (default 40).
 `tail`: the critical path between two sweep kernels of one run -- from the end of a k_sweep_cluster launch to the start of the
 next one, split into the kernels of the same queue in between (what runs on the quadrature's stream, beside the next sweep, is left
-out) and the gaps in front of each of them and of the next sweep kernel; medians over all such pairs of the trace, in us."""
+out) and the gaps in front of each of them and of the next sweep kernel; medians over all such pairs of the trace, in us.
+`ends`: the two ends of a run around its sweep kernels, with the kernels of BOTH queues -- the head from the start of k_reset to the
+start of the first k_sweep_cluster, and the end from the finish of the last k_sweep_cluster that sweeps to the finish of the run's
+last kernel (a kernel trace holds no copies: the copy behind the last kernel is not in it; the distance to the next run's k_reset,
+which holds that copy and the host's work between two runs, is printed beside it).  Medians over the runs of the trace that
+launch the same kernels in the same order, in us; every kernel with its queue, its start and its end relative to the segment."""
 import csv
 import glob
 import statistics
@@ -55,6 +61,39 @@ if start == "tail":
         for k, nm in enumerate(names):
             print(f"    gap {med(p[3][k][1] for p in ps):6.1f}  dur {med(p[3][k][2] for p in ps):6.1f}  {nm}")
         print(f"    gap {med(p[4] for p in ps):6.1f}  k_sweep_cluster (next)")
+    sys.exit(0)
+if start == "ends":
+    med = statistics.median
+    resets = [i for i, r in enumerate(rows) if 'k_reset' in r['Kernel_Name']]
+    heads, tails = {}, {}
+    for a, b in zip(resets, resets[1:]):
+        run = rows[a:b]
+        sw = [i for i, r in enumerate(run) if 'k_sweep_cluster' in r['Kernel_Name']]
+        real = [i for i in sw if int(run[i]['End_Timestamp']) - int(run[i]['Start_Timestamp']) > 20000]
+        if not real:
+            continue
+        main = run[0]['Queue_Id']
+        q = lambda r: 'main' if r['Queue_Id'] == main else 'side'
+        t0 = int(run[0]['Start_Timestamp'])
+        seg = [(q(r), short(r['Kernel_Name']), (int(r['Start_Timestamp']) - t0) / 1e3, (int(r['End_Timestamp']) - t0) / 1e3) for r in run[:sw[0]]]
+        seg.append(('main', 'k_sweep_cluster (first) starts', (int(run[sw[0]]['Start_Timestamp']) - t0) / 1e3, (int(run[sw[0]]['Start_Timestamp']) - t0) / 1e3))
+        heads.setdefault(tuple(x[:2] for x in seg), []).append(seg)
+        t1 = int(run[real[-1]]['End_Timestamp'])
+        rest = [r for r in run[real[-1] + 1:] if int(r['End_Timestamp']) > t1]
+        seg = [(q(r), short(r['Kernel_Name']), (int(r['Start_Timestamp']) - t1) / 1e3, (int(r['End_Timestamp']) - t1) / 1e3) for r in rest]
+        seg.append(('main', 'k_reset (next run) starts', (int(rows[b]['Start_Timestamp']) - t1) / 1e3, (int(rows[b]['Start_Timestamp']) - t1) / 1e3))
+        tails.setdefault(tuple(x[:2] for x in seg), []).append(seg)
+    for title, shapes in (("head: start of k_reset -> start of the first k_sweep_cluster", heads),
+                          ("end: finish of the last sweeping k_sweep_cluster -> finish of the last kernel", tails)):
+        for names, segs in sorted(shapes.items(), key=lambda kv: -len(kv[1]))[:2]:
+            total = [max(x[3] for x in s[:-1]) if len(s) > 1 else 0.0 for s in segs] if title[0] == 'e' else [s[-1][3] for s in segs]
+            print(f"{title}: {len(segs)} runs, median {med(total):.1f} us (min {min(total):.1f}, max {max(total):.1f})")
+            busy = {'main': 0.0, 'side': 0.0}
+            for k, (qq, nm) in enumerate(names):
+                st_, en_ = med(s[k][2] for s in segs), med(s[k][3] for s in segs)
+                gap = st_ - busy[qq]
+                busy[qq] = max(busy[qq], en_)
+                print(f"    {qq}  start {st_:7.1f}  end {en_:7.1f}  dur {med(s[k][3] - s[k][2] for s in segs):6.1f}  gap on its queue {gap:6.1f}  {nm}")
     sys.exit(0)
 if start == "run":
     inits = [i for i, r in enumerate(rows) if 'k_init_samples' in r['Kernel_Name']]

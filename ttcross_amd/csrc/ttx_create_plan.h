@@ -71,6 +71,12 @@ struct CreateEnv {
     bool mvn_v2_off = false;        // TTX_MVN_V2=0
     bool tail_off = false;          // TTX_TAIL=0
     bool tail_side_off = false;     // TTX_TAIL_SIDE=0
+    bool head_direct_off = false;   // TTX_HEAD_DIRECT=0
+    bool init_wave_off = false;     // TTX_INIT_WAVE=0
+    bool fin_early_off = false;     // TTX_FIN_EARLY=0
+    bool fin_skip_exch_off = false; // TTX_FIN_SKIP_EXCH=0
+    bool init_wide_off = false;     // TTX_INIT_WIDE=0
+    bool quad_lds_off = false;      // TTX_QUAD_LDS=0
 };
 // the switches as `get` finds them (get(name): the value, or nullptr where unset): an integer as atoi reads it, "=0" as atoi(value) == 0
 template <class Get>
@@ -99,6 +105,9 @@ CreateEnv create_env_from(Get get)
     v.lottery_rows2 = num("TTX_LOTTERY_ROWS", 0) == 2;
     v.mvn_v2_off = off("TTX_MVN_V2");
     v.tail_off = off("TTX_TAIL"); v.tail_side_off = off("TTX_TAIL_SIDE");
+    v.head_direct_off = off("TTX_HEAD_DIRECT"); v.init_wave_off = off("TTX_INIT_WAVE");
+    v.fin_early_off = off("TTX_FIN_EARLY"); v.fin_skip_exch_off = off("TTX_FIN_SKIP_EXCH");
+    v.init_wide_off = off("TTX_INIT_WIDE"); v.quad_lds_off = off("TTX_QUAD_LDS");
     return v;
 }
 struct DevCaps { int ncu = 0; bool coop = false; };          // multiProcessorCount, hipDeviceAttributeCooperativeLaunch
@@ -159,11 +168,43 @@ struct CreatePlan {
     int cl_test_abort = 0; bool dbg_waves = false;
     bool sweep_tail = true;                         // the pipelined cluster loop ends a sweep with k_exch_tail (TTX_TAIL=0: max/apply and boundary launches)
     bool sweep_tail_side = true;                    // ... and its summary runs on the quadrature's stream (TTX_TAIL_SIDE=0: k_sweep_end on the main stream)
+    // the two ends of a run around its sweeps (ttx_loop_plan.h says where each applies)
+    bool head_direct = true;                        // the initial summary goes from k_init_final into the pinned slot (TTX_HEAD_DIRECT=0: k_collect and a copy in front of sweep kernel 1)
+    size_t lds_qtree = 0;                           // k_quad_tree multiplies in LDS: the bytes of its two regions of nproc matrices (quad_tree_lds); 0 (also TTX_QUAD_LDS=0): in the global scratch
+    bool init_wide = true;                          // k_init_samples stages the mode sizes in LDS and takes the samples in one pass (TTX_INIT_WIDE=0: 256 threads, two passes)
+    bool init_wave = true;                          // k_init_final runs one wave per core (TTX_INIT_WAVE=0: one thread per core)
+    bool fin_early = true;                          // the finalisation waits for the last quadrature's k_quad_build only, its collect and copy go out before the host waits for the value (TTX_FIN_EARLY=0: behind the value's copy)
+    bool fin_skip_exch = true;                      // no final exchange behind a sweep of one process, whose end has made it already (TTX_FIN_SKIP_EXCH=0: always)
     SweepWant sweep_want = SWEEP_AUTO; int ncu = 0;
     // decided by create_admit
     int fused = 0;                                  // whole-sweep kernel (ttx_fused.h) in use
     int cluster = 0;                                // workgroups per bond group of the cluster sweep kernel (ttx_cluster.h); 0: not used
 };
+
+// The launch of k_init_samples (ttx_kernels.h).  rows 0: the index rows of 256 threads do not fit the LDS, the generic accessor runs.
+// rows 1: one row of VS shorts per thread behind the staged parameters, 256 threads -- the samples beyond 256 (408 with 8 groups at
+// n = 51) take a second, part-empty pass, and every thread reads the mode sizes from global memory.  rows 2, where `wide` allows it
+// and the kernel walks its own rows (own_rows: not the wave-per-sample evaluator of the fast Ising D/E, not the host's two passes):
+// whole waves for all samples up to 512 threads, so one pass, and the d mode sizes staged once behind the rows.
+// k_quad_tree in LDS: two regions of nproc RM x RM matrices, where they fit the working-set ceiling; one group has no tree
+inline size_t quad_tree_lds(int nproc, size_t RM, bool on)
+{
+    const size_t need = sizeof(double) * 2 * (size_t)nproc * RM * RM;
+    return on && nproc > 1 && need <= TTX_LDS_WORK ? need : 0;
+}
+struct InitSamplesPlan { int threads = 256, rows = 0; size_t lds = 0; };
+inline InitSamplesPlan init_samples_plan(size_t lds_par, size_t VS, int d, long nsamples, bool own_rows, bool wide)
+{
+    InitSamplesPlan p;
+    const size_t lds1 = lds_par + 16 + sizeof(short) * 256 * VS;
+    p.rows = lds1 <= TTX_LDS_WORK ? 1 : 0;
+    p.lds = p.rows ? lds1 : lds_par;
+    if (!p.rows || !wide || !own_rows) return p;
+    const int threads = (int)std::min<long>(512, std::max<long>(256, (nsamples + 63) / 64 * 64));
+    const size_t lds2 = lds_par + 16 + sizeof(short) * (size_t)threads * VS + 16 + sizeof(int) * (size_t)(d + 1);
+    if (lds2 <= TTX_LDS_WORK) { p.threads = threads; p.rows = 2; p.lds = lds2; }
+    return p;
+}
 
 // lib/default.f90:78-97 share(): own(p) = first + int(dble(last-first+1)*dble(p)/nproc)
 inline void share(int first, int last, int nproc, std::vector<int32_t> &own)
@@ -261,6 +302,7 @@ inline CreatePlan create_plan(const ttx_config &cfg, bool nofun, const CreateEnv
     p.IOFF = (sizeof(int) * (XH + d + 2) + 15) & ~(size_t)15;
     p.MSZ = (p.IOFF + sizeof(double) * p.XD + 15) & ~(size_t)15;
     p.QB = (size_t)nproc * RM * RM + 2 * nproc;
+    p.lds_qtree = quad_tree_lds(nproc, RM, !env.quad_lds_off);
     p.SB = SUM_HDR + nproc + 5 * (size_t)(d + 1);
     p.qscr = 2 * sizeof(double) * (RM * RM + 2) > TTX_LDS_WORK;
     p.nn = cfg.n[0];
@@ -370,6 +412,8 @@ inline CreatePlan create_plan(const ttx_config &cfg, bool nofun, const CreateEnv
         }
         p.cl_test_abort = env.cluster_test_abort; p.dbg_waves = env.dbg_waves;
         p.sweep_tail = !env.tail_off; p.sweep_tail_side = !env.tail_side_off;
+        p.head_direct = !env.head_direct_off; p.init_wave = !env.init_wave_off; p.init_wide = !env.init_wide_off;
+        p.fin_early = !env.fin_early_off; p.fin_skip_exch = !env.fin_skip_exch_off;
         const std::string want_sweep = env.sweep.set ? env.sweep.v : "auto";
         if (want_sweep == "cluster") p.sweep_want = SWEEP_CLUSTER;
         else if (want_sweep == "fused") p.sweep_want = SWEEP_FUSED;

@@ -222,7 +222,7 @@ struct ttx_engine {
     bool cluster_aborted = false;
     double *h_svd = nullptr; double svd_seq = 0.0;   // pinned: [seq, rank, sweeps, sv...] of the core dtt_svd works on (k_svd_report)
     hipStream_t qstream = nullptr;      // forked per-sweep quadrature (single-process runs)
-    hipEvent_t ev_sum[2] = {nullptr, nullptr}, ev_val[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr};
+    hipEvent_t ev_sum[2] = {nullptr, nullptr}, ev_val[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr}, ev_qb[2] = {nullptr, nullptr}, ev_fin[2] = {nullptr, nullptr};
     double *h_sum_base = nullptr;       // pinned [2][SB]: summaries of the two sweeps in flight
     double *h_val = nullptr;            // pinned [2]: per-sweep quadrature values
     int *h_abort = nullptr;             // pinned, device-visible: the cluster kernel's barrier-timeout flag
@@ -627,7 +627,8 @@ static int create_staging(ttx_engine *h)
     memset(h->h_sum_base, 0, sizeof(double) * 2 * h->SB);
     HIPCHECK(hipHostMalloc((void **)&h->h_val, sizeof(double) * 2));
     HIPCHECK(hipStreamCreateWithFlags(&h->qstream, hipStreamNonBlocking));
-    for (int x = 0; x < 2; x++) { HIPCHECK(hipEventCreateWithFlags(&h->ev_sum[x], hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&h->ev_val[x], hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&h->ev_tail[x], hipEventDisableTiming)); }
+    if (h->sel.lds_qtree) if (int rc = ensure_lds(h, reinterpret_cast<const void *>(k_quad_tree), h->sel.lds_qtree)) return rc;
+    for (int x = 0; x < 2; x++) { HIPCHECK(hipEventCreateWithFlags(&h->ev_sum[x], hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&h->ev_val[x], hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&h->ev_tail[x], hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&h->ev_qb[x], hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&h->ev_fin[x], hipEventDisableTiming)); }
     HIPCHECK(hipHostMalloc((void **)&h->h_msg, 4 * h->P.MSZ));
     HIPCHECK(hipHostMalloc((void **)&h->h_tmp, sizeof(double) * std::max(h->QB, h->SB)));
     if (h->W > 1) {
@@ -749,7 +750,7 @@ extern "C" void ttx_destroy(ttx_engine *h)
     if (h->h_val) (void)hipHostFree(h->h_val);
     if (h->h_svd) (void)hipHostFree(h->h_svd);
     if (h->qstream) (void)hipStreamDestroy(h->qstream);
-    for (int x = 0; x < 2; x++) { if (h->ev_sum[x]) (void)hipEventDestroy(h->ev_sum[x]); if (h->ev_val[x]) (void)hipEventDestroy(h->ev_val[x]); if (h->ev_tail[x]) (void)hipEventDestroy(h->ev_tail[x]); }
+    for (int x = 0; x < 2; x++) { if (h->ev_sum[x]) (void)hipEventDestroy(h->ev_sum[x]); if (h->ev_val[x]) (void)hipEventDestroy(h->ev_val[x]); if (h->ev_tail[x]) (void)hipEventDestroy(h->ev_tail[x]); if (h->ev_qb[x]) (void)hipEventDestroy(h->ev_qb[x]); if (h->ev_fin[x]) (void)hipEventDestroy(h->ev_fin[x]); }
     if (h->h_msg) (void)hipHostFree(h->h_msg);
     if (h->h_tmp) (void)hipHostFree(h->h_tmp);
     if (h->red_mem) (void)hipHostFree(h->red_mem);
@@ -1112,18 +1113,27 @@ static void print_line(const ttx_engine *h, const ttx_sweep_rec &r, double val_p
 }
 
 // job-wide summary of the sweep -> h->h_sum (one all-reduce, one stream synchronisation)
-static int readback(ttx_engine *h)
+// in two halves, so that the end of a pipelined run can enqueue the first one ahead of its other waits (LoopPlan::fin_early: one
+// process, where the all-reduce is empty, on the quadrature's stream sq)
+static int readback_enqueue(ttx_engine *h, double *dst, hipStream_t sq)
 {
-    hipLaunchKernelGGL(k_collect, dim3(1), dim3(256), 0, h->stream, h->P);
-    {
-        int rc = allreduce_dev(h, h->P.sumsend, h->P.sumrecv, h->SB, 0);
-        if (rc) return rc;
-        HIPCHECK(hipMemcpyAsync(h->h_sum, h->P.sumrecv, sizeof(double) * h->SB, hipMemcpyDeviceToHost, h->stream));
-        HIPCHECK(hipStreamSynchronize(h->stream));
-        if (h->cb_error) return fail(TTX_EHIP, "host transport: a sendrecv / allreduce callback failed");
-    }
+    hipLaunchKernelGGL(k_collect, dim3(1), dim3(256), 0, sq, h->P);
+    int rc = allreduce_dev(h, h->P.sumsend, h->P.sumrecv, h->SB, 0);
+    if (rc) return rc;
+    HIPCHECK(hipMemcpyAsync(dst, h->P.sumrecv, sizeof(double) * h->SB, hipMemcpyDeviceToHost, sq));
+    return TTX_OK;
+}
+static int readback_wait(ttx_engine *h)
+{
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    if (h->cb_error) return fail(TTX_EHIP, "host transport: a sendrecv / allreduce callback failed");
     if (h->profile) ev_collect(h);
     return TTX_OK;
+}
+static int readback(ttx_engine *h)
+{
+    if (int rc = readback_enqueue(h, h->h_sum, h->stream)) return rc;
+    return readback_wait(h);
 }
 static inline const double *sum_bond(const ttx_engine *h, int p) { return h->h_sum + SUM_HDR + h->cfg.nproc + 5 * (size_t)p; }
 
@@ -1158,15 +1168,17 @@ static inline size_t lds_fpersist(const DevProb &P) { return (P.arith && P.fpers
 
 // quadrature of the cores as Q sees them, with the weights w, on the stream sq: per-core matrices, per-group chains, gather over
 // GPUs, tree (the gather travels on the engine's stream: with several processes sq is that stream)
-static int launch_quad(ttx_engine *h, hipStream_t sq, const DevProb &Q, int mode, const double *w)
+// built: recorded behind k_quad_build, the only kernel of the three that reads the cores
+static int launch_quad(ttx_engine *h, hipStream_t sq, const DevProb &Q, int mode, const double *w, hipEvent_t built = nullptr)
 {
     const size_t lds_q = sizeof(double) * ((size_t)h->RM * h->RM + 2);
     hipLaunchKernelGGL(k_quad_build, dim3(h->NC, h->G), dim3(256), lds_q, sq, Q, mode, w);
+    if (built) HIPCHECK(hipEventRecord(built, sq));
     hipLaunchKernelGGL(k_quad_chain, dim3(h->G), dim3(256), Q.qscr ? 0 : 2 * lds_q, sq, Q);
     if (h->cfg.nproc > 1) {
         int rc = allreduce_dev(h, Q.qsend, Q.qall, h->QB, 0);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_quad_tree, dim3(1), dim3(256), 0, sq, Q);
+        hipLaunchKernelGGL(k_quad_tree, dim3(1), dim3(256), h->sel.lds_qtree, sq, Q, h->sel.lds_qtree ? 1 : 0);
     }
     return TTX_OK;
 }
@@ -1261,9 +1273,10 @@ static ChainPlan chain_plan(const ttx_engine *h)
     // roles A/B of k_accept: x[RM]; C/D: the staged LU
     p.accept = kl(k_accept, "k_accept", dim3(2 * p.nfb + 2 * NM + 1, G), dim3(TTX_BLK), sizeof(double) * std::max<size_t>(RM + 2, (size_t)std::min<int>(RM, 64) * std::min<int>(RM, 64)));
     {   // initial samples: index rows in LDS where they fit
-        const size_t lds_s = s.lds_par + 16 + sizeof(short) * 256 * VS;
-        p.srows = lds_s <= TTX_LDS_WORK ? 1 : 0;
-        p.init_samples = kl(k_init_samples<FUN>, KFUN_(k_init_samples), dim3(G), dim3(256), p.srows ? lds_s : s.lds_par, p.srows != 0);
+        const bool own_rows = FUN != FUN_HOST && !(FUN == FUN_ISING && P.arith && P.ising_id != 1);
+        const InitSamplesPlan ip = init_samples_plan(s.lds_par, VS, h->d, (long)s.nn * s.snum, own_rows, s.init_wide);
+        p.srows = ip.rows;
+        p.init_samples = kl(k_init_samples<FUN>, KFUN_(k_init_samples), dim3(G), dim3(ip.threads), ip.lds, ip.rows != 0);
         p.init_fibers = kl(k_init_fibers<FUN>, KFUN_(k_init_fibers), dim3(h->NC, G), dim3(256), s.lds_par);
     }
     // before a bond step's lottery.  Ising D/E: pair factors of the bond that do not span it (shared by all elements through a pivot),
@@ -1341,7 +1354,8 @@ struct SweepRun {
     LoopPlan L; ChainPlan plan;
     DevProb Pq;                                 // what the per-sweep quadrature sees: in the pipelined loop the snapshot of the ranks
     double val = 1.0, val_prev = 1.0;
-    int strike = 0; bool ready = false, fin_enqueued = false;
+    int strike = 0, sweeps = 0; bool ready = false, fin_enqueued = false;
+    double *sum_final = nullptr;                // where the final summary was enqueued to ahead of the run's end (LoopPlan::fin_early)
     explicit SweepRun(ttx_engine *h_) : h(h_), P(h_->P), st(h_->stream), d(h_->d), G(h_->G), nproc(h_->cfg.nproc), cluster(h_->cluster_nb()), fused(h_->sel.fused) {}
     double since() const { return std::chrono::duration<double>(clk::now() - t0).count(); }
     // an evaluating kernel: once with the device integrand; with a host integrand twice around the host's calls
@@ -1363,6 +1377,7 @@ struct SweepRun {
         in.whole = cluster || fused; in.cluster = cluster != 0; in.profile = h->profile; in.pipeline_off = env_off("TTX_PIPELINE");
         in.W = h->W; in.nproc = nproc; in.has_quad = P.has_quad; in.host_pass = FUN == FUN_HOST;
         in.sweep_tail = h->sel.sweep_tail; in.sweep_tail_side = h->sel.sweep_tail_side; in.maxrank = h->cfg.maxrank;
+        in.head_direct = h->sel.head_direct; in.fin_early = h->sel.fin_early; in.fin_skip_exch = h->sel.fin_skip_exch;
         L = loop_plan(in);
         P.tail_side = L.side ? 1 : 0;
         h->recs.clear(); h->tapes.clear();
@@ -1378,12 +1393,14 @@ struct SweepRun {
             if (int rc = EV(plan.init_samples, h->sel.snum, h->sel.nn, FUN == FUN_HOST ? 0 : plan.srows, 0)) return rc;
             if (int rc = EV(plan.init_fibers)) return rc;
             hipLaunchKernelGGL(k_init_factors, dim3(h->NC, G), dim3(256), lds_fpersist(P), st, P);
-            hipLaunchKernelGGL(k_init_final, dim3(G), dim3(256), 0, st, P);
+            hipLaunchKernelGGL(k_init_final, dim3(G), dim3(256), 0, st, P, h->sel.init_wave ? 1 : 0, L.head_direct ? h->h_sum_base : (double *)nullptr);
         }
         if (L.head) {
-            hipLaunchKernelGGL(k_collect, dim3(1), dim3(256), 0, st, P);
             h->h_sum = h->h_sum_base;
-            HIPCHECK(hipMemcpyAsync(h->h_sum, P.sumrecv, sizeof(double) * h->SB, hipMemcpyDeviceToHost, st));
+            if (!L.head_direct) {
+                hipLaunchKernelGGL(k_collect, dim3(1), dim3(256), 0, st, P);
+                HIPCHECK(hipMemcpyAsync(h->h_sum, P.sumrecv, sizeof(double) * h->SB, hipMemcpyDeviceToHost, st));
+            }
             HIPCHECK(hipEventRecord(h->ev_sum[0], st));
             if (int rc = launch_sweep_kernel(1)) return rc;
             HIPCHECK(hipEventSynchronize(h->ev_sum[0]));
@@ -1508,7 +1525,7 @@ struct SweepRun {
     {
         {
             KScope ks(h, TTX_K_EXCHANGE, (h->W > 1 ? 4 : 2) + (nproc > 1 ? 1 : 0));
-            if (!cluster) hipLaunchKernelGGL(k_exch_pack, dim3(G), dim3(256), 0, st, P);     // the cluster kernel packs at its end
+            if (!cluster) hipLaunchKernelGGL(k_exch_pack, dim3(G), dim3(256), 0, st, P, 0);     // the cluster kernel packs at its end
             if (h->W > 1) {
                 hipLaunchKernelGGL(k_exch_localmax, dim3(1), dim3(64), 0, st, P);
                 if (int rc = xfer_neighbours(h)) return rc;
@@ -1530,7 +1547,7 @@ struct SweepRun {
     {
         const int slot = it_ & 1;
         KScope ks(h, TTX_K_QUAD, nproc > 1 ? 3 : 2);
-        if (int rc = launch_quad(h, sq, L.pipe ? Pq : P, 0, P.quadw)) return rc;
+        if (int rc = launch_quad(h, sq, L.pipe ? Pq : P, 0, P.quadw, L.fin_early ? h->ev_qb[slot] : nullptr)) return rc;
         if (L.pipe) {
             HIPCHECK(hipMemcpyAsync(h->h_val + slot, &P.gs[0].val, sizeof(double), hipMemcpyDeviceToHost, sq));
             HIPCHECK(hipEventRecord(h->ev_val[slot], sq));
@@ -1547,22 +1564,40 @@ struct SweepRun {
         HIPCHECK(hipEventRecord(h->ev_sum[slot], sq));          // the summary of the sweep is in the pinned slot
         return enqueue_quadrature(it_, sq);
     }
-    // finalise (:1029): dtt_lua shifts the rightmost inv of every group to its neighbour first.  Enqueued once (LoopPlan::pipe);
-    // after_val >= 0: the slot whose forked quadrature still reads the cores the finalisation overwrites
+    // finalise (:1029): dtt_lua shifts the rightmost inv of every group to its neighbour first (LoopPlan::final_exchange).  Enqueued
+    // once (LoopPlan::pipe); after_val >= 0: the slot whose forked quadrature still reads the cores the finalisation overwrites.
+    // With LoopPlan::fin_early that wait is for the quadrature's k_quad_build only.  The clearing of ctl[0..2], the final k_collect and
+    // its copy (into the other pinned slot) are enqueued at once on the QUADRATURE's stream: there they stand behind k_quad_tree, which
+    // reads ctl[2], and behind the value's copy by stream order, with no hop between two streams at the very end (a hop costs 11-12 us
+    // here).  The one thing of the main stream they must follow is the speculative sweep kernel, which may read ctl[0]: an event
+    // recorded behind it, in front of the main stream's own wait, has long fired by then.  They do not wait for the LU kernels or a
+    // final exchange: k_collect reads the own bonds' ranks, the tapes and the groups' counters, none of which those write.
+    // The run ends when both streams have: readback_wait and ev_fin.
     int enqueue_final(int after_val)
     {
         if (fin_enqueued) return TTX_OK;
         fin_enqueued = true;
-        if (after_val >= 0) HIPCHECK(hipStreamWaitEvent(st, h->ev_val[after_val], 0));
-        HIPCHECK(hipMemsetAsync(P.ctl, 0, sizeof(int) * 3, st));      // ctl[3] (fault counter of the team / relay half-steps) is read by ttx_run afterwards
-        KScope ks(h, TTX_K_OTHER, 2);
-        if (nproc > 1) {
-            hipLaunchKernelGGL(k_exch_pack, dim3(G), dim3(256), 0, st, P);
-            if (int rc = xfer_neighbours(h)) return rc;
-            hipLaunchKernelGGL(k_exch_apply, dim3(G), dim3(256), lds_fpersist(P), st, P);
+        const bool early = L.fin_early && after_val >= 0;
+        if (early) HIPCHECK(hipEventRecord(h->ev_fin[0], st));      // behind the speculative sweep kernel, in front of the wait below
+        if (after_val >= 0) HIPCHECK(hipStreamWaitEvent(st, early ? h->ev_qb[after_val] : h->ev_val[after_val], 0));
+        if (!early) HIPCHECK(hipMemsetAsync(P.ctl, 0, sizeof(int) * 3, st));      // ctl[3] (fault counter of the team / relay half-steps) is read by ttx_run afterwards
+        {
+            KScope ks(h, TTX_K_OTHER, 2);
+            if (L.final_exchange(sweeps)) {
+                hipLaunchKernelGGL(k_exch_pack, dim3(G), dim3(256), 0, st, P, 1);
+                if (int rc = xfer_neighbours(h)) return rc;
+                hipLaunchKernelGGL(k_exch_apply, dim3(G), dim3(256), lds_fpersist(P), st, P);
+            }
+            launch(st, plan.fin_luar, P, plan.fl);
+            launch(st, plan.fin_lual, P, plan.fl);
         }
-        launch(st, plan.fin_luar, P, plan.fl);
-        launch(st, plan.fin_lual, P, plan.fl);
+        if (!early) return TTX_OK;
+        const hipStream_t sq = h->qstream;
+        HIPCHECK(hipStreamWaitEvent(sq, h->ev_fin[0], 0));
+        HIPCHECK(hipMemsetAsync(P.ctl, 0, sizeof(int) * 3, sq));
+        sum_final = h->h_sum_base + (size_t)(after_val ^ 1) * h->SB;   // the finished sweep's slot is still to be read by process_sweep
+        if (int rc = readback_enqueue(h, sum_final, sq)) return rc;
+        HIPCHECK(hipEventRecord(h->ev_fin[1], sq));
         return TTX_OK;
     }
     // the record and the log line of sweep it_ (0: the initial cross) from the summary in h_sum and from val
@@ -1578,6 +1613,7 @@ struct SweepRun {
     int process_sweep(int it_)
     {
         const int slot = it_ & 1;
+        sweeps = it_;
         if (L.pipe) {
             HIPCHECK(hipEventSynchronize(h->ev_sum[slot]));
             h->h_sum = h->h_sum_base + (size_t)slot * h->SB;
@@ -1621,7 +1657,9 @@ struct SweepRun {
             }
         }
         if (int rc = enqueue_final(-1)) return rc;
-        if (int rc = readback(h)) return rc;
+        if (sum_final) h->h_sum = sum_final;
+        if (int rc = sum_final ? readback_wait(h) : readback(h)) return rc;
+        if (sum_final) HIPCHECK(hipEventSynchronize(h->ev_fin[1]));
         HIPCHECK(hipGetLastError());
 #ifdef TTX_STAMPS
         if (int rc = dump_stamps(h)) return rc;

@@ -803,12 +803,16 @@ struct FixIdx { const int *ind; int self, selfval; __device__ __forceinline__ in
 
 // every group evaluates all nn*snum shifted-diagonal samples (a few hundred) so that the MAXLOC of :196
 // needs no exchange; each group is charged only its own share of evaluations (:160,181)
+// ldsrows: 0 the generic accessor; 1 one index row per thread in LDS, the mode sizes read from global memory by every thread, 256
+// threads; 2 (InitSamplesPlan, ttx_create_plan.h) the same rows with the mode sizes staged in LDS once behind them, and a block of
+// up to 512 threads so that the few hundred samples take ONE pass instead of a full and a part-empty one.  The sample a thread
+// takes, its row, its evaluation and the first-maximum rule on the sample number are the same in every form.
 template <int FUN>
-__global__ __launch_bounds__(256) void k_init_samples(DevProb P, int snum, int nn, int ldsrows, int shift_hi)
+__global__ __launch_bounds__(512) void k_init_samples(DevProb P, int snum, int nn, int ldsrows, int shift_hi)
 {
     extern __shared__ __align__(16) double dyn[];
     double *par = dyn;
-    __shared__ double sha[4], shv[4]; __shared__ int shi[4];
+    __shared__ double sha[8], shv[8]; __shared__ int shi[8];
     const int g = blockIdx.x, tid = threadIdx.x;
     GroupState &gs = P.gs[g];
     for (int x = tid; x < P.npar; x += blockDim.x) par[x] = P.par[x];
@@ -845,10 +849,17 @@ __global__ __launch_bounds__(256) void k_init_samples(DevProb P, int snum, int n
             double a = fabs(f);
             if (a > ba || (a == ba && il < bi)) { ba = a; bv = f; bi = il; }
         }
-    else
+    else {
+    const int *nl = P.n + 1;                                  // nl[p - 1]: the size of mode p
+    if (ldsrows == 2) {
+        int *nls = (int *)(((size_t)(rows + (size_t)blockDim.x * VSr) + 15) & ~(size_t)15);
+        for (int x = tid; x < m; x += blockDim.x) nls[x] = P.n[x + 1];
+        __syncthreads();
+        nl = nls;
+    }
     for (int il = tid; il < nn * snum; il += blockDim.x) {
         const int k = il % nn + 1, sft = il / nn;
-        for (int p = 1; p <= m; p++) row[p - 1] = (short)((k - 1 + sft * (p - 1)) % P.n[p] + 1);
+        for (int p = 1; p <= m; p++) row[p - 1] = (short)((k - 1 + sft * (p - 1)) % nl[p - 1] + 1);
         for (int x = m; x < VSr; x++) row[x] = 1;
         row[m - 1 + 0] = row[m - 1];                          // (dim m stays readable as `self`)
         const int self = row[m - 1];
@@ -857,6 +868,7 @@ __global__ __launch_bounds__(256) void k_init_samples(DevProb P, int snum, int n
         double f = eval_src3<FUN, true>(P, par, sx, (long)g * P.HS + il);
         double a = fabs(f);
         if (a > ba || (a == ba && il < bi)) { ba = a; bv = f; bi = il; }
+    }
     }
     if (HOST_PASS1(FUN, P)) return;
     block_argmax(ba, bv, bi, sha, shv, shi);
@@ -956,11 +968,26 @@ __global__ __launch_bounds__(256) void k_init_factors(DevProb P)
     }
 }
 
-// pivotmax_prev (:234) and the group's factor of the initial quadrature value (:250-258); one block per group,
-// one thread per core for the ddot, then the ordered product
-__global__ __launch_bounds__(256) void k_init_final(DevProb P)
+// pivotmax_prev (:234) and the group's factor of the initial quadrature value (:250-258); one block per group: the ddot of every
+// core, then the ordered product.
+// wave = 0: one THREAD per core for the ddot, then thread 0 multiplies with one global load per core (the form the kernel had).
+// wave = 1: one WAVE per core.  The lanes load A_j and w_j and multiply, one product per lane; the ordered sum t = t + A_j * w_j
+// takes the products in j order out of the lanes' registers (two v_readlane_b32 per term, as mvn_lane of ttx_mvn.h does), so every
+// lane adds the same operands in the same order as the one thread did: the bits stay.  The divisors of the serial product are
+// loaded by all threads ahead of it.
+// out != nullptr (the head of the single-process pipelined loop, LoopPlan::head_direct): the initial summary goes straight into the
+// pinned slot `out` from this launch, as k_sweep_end writes a sweep's -- everything collect_summary would read is final here
+// (ranks 1 and tapes -1 from k_reset, the groups' counters and maxima after k_init_fibers, the value 0), and every entry of the
+// slot is written: block g its bonds and its factor, block 0 the scalars and the zeros of the entries nobody owns.
+__device__ __forceinline__ double lane_value(double x, int k)      // lane k's x, k wave-uniform
 {
-    __shared__ double dots[256];
+    const long long b = __double_as_longlong(x);
+    const int lo = __builtin_amdgcn_readlane((int)b, k), hi = __builtin_amdgcn_readlane((int)(b >> 32), k);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+__global__ __launch_bounds__(256) void k_init_final(DevProb P, int wave, double *out)
+{
+    __shared__ double dots[256], divs[256];
     const int g = blockIdx.x, tid = threadIdx.x;
     GroupState &gs = P.gs[g];
     const bool lastgroup = (gs.last + 1 == P.d && gs.gglobal == P.nprocs - 1);
@@ -968,6 +995,21 @@ __global__ __launch_bounds__(256) void k_init_final(DevProb P)
     double val = 1.0;
     if (P.has_quad) {
         for (int c0 = 0; c0 < ncore; c0 += 256) {
+            if (wave) {
+                const int lane = tid & 63, nw = blockDim.x >> 6, cend = min(ncore, c0 + 256);
+                for (int c = c0 + (tid >> 6); c < cend; c += nw) {
+                    const int p = gs.first + c, np_ = P.n[p];
+                    const double *A = core_ptr(P, P.arg, g, p, gs.first), *w = P.quadw + (size_t)p * P.NM;
+                    double t = 0.0;
+                    for (int b = 0; b < np_; b += 64) {
+                        const int j = b + lane, nb = min(64, np_ - b);
+                        const double pr = j < np_ ? A[(size_t)P.RM * j] * w[j] : 0.0;
+                        for (int k = 0; k < nb; k++) t = t + lane_value(pr, k);
+                    }
+                    if (lane == 0) dots[c - c0] = t;
+                }
+                if (c0 + tid < cend) { const int p = gs.first + c0 + tid; divs[tid] = p <= gs.last ? inv_ptr(P, g, p, gs.first)[0] : 0.0; }
+            } else {
             const int c = c0 + tid;
             if (c < ncore) {
                 const int p = gs.first + c;
@@ -976,17 +1018,37 @@ __global__ __launch_bounds__(256) void k_init_final(DevProb P)
                 for (int j = 0; j < P.n[p]; j++) t = t + A[(size_t)P.RM * j] * w[j];
                 dots[tid] = t;
             }
+            }
             __syncthreads();
             if (tid == 0)
                 for (int c2 = c0; c2 < min(ncore, c0 + 256); c2++) {
                     const int p = gs.first + c2;
-                    if (p <= gs.last) val = val * dots[c2 - c0] / inv_ptr(P, g, p, gs.first)[0];
+                    if (p <= gs.last) val = val * dots[c2 - c0] / (wave ? divs[c2 - c0] : inv_ptr(P, g, p, gs.first)[0]);
                     else val = val * dots[c2 - c0];
                 }
             __syncthreads();
         }
     }
     if (tid == 0) { gs.pivotmax_prev = gs.amax; gs.pivotmax = -1.0; gs.pivotmin = -1.0; gs.initval = val; }
+    if (!out) return;
+    const int m = P.d;
+    const int *r = P.r + (size_t)g * (m + 2), *tp = P.tape + (size_t)g * (m + 2) * 4;
+    for (int p = gs.first + tid; p <= gs.last; p += blockDim.x) {
+        double *e = out + SUM_HDR + P.nprocs + 5 * p;
+        e[0] = (double)r[p]; e[1] = (double)tp[4 * p]; e[2] = (double)tp[4 * p + 1]; e[3] = (double)tp[4 * p + 2]; e[4] = (double)tp[4 * p + 3];
+    }
+    if (g == 0)
+        for (int p = tid; p <= m; p += blockDim.x)
+            if (p < P.gs[0].first || p > P.gs[P.G - 1].last) { double *e = out + SUM_HDR + P.nprocs + 5 * p; for (int x = 0; x < 5; x++) e[x] = 0.0; }
+    if (tid != 0) return;
+    out[SUM_HDR + gs.gglobal] = val;
+    if (gs.gglobal == 0) { out[SUM_AMAX] = gs.amax; out[SUM_PMAX] = -1.0; out[SUM_PMIN] = -1.0; }
+    if (g != 0) return;
+    double nev = 0.0, by = 0.0, nr = 0.0;
+    for (int x = 0; x < P.G; x++) { const GroupState &o = P.gs[x]; nev += (double)o.neval; by += o.bytes_half; nr += (double)o.n_resid; }
+    out[SUM_NEVAL] = nev; out[SUM_BYTES] = by; out[SUM_NRESID] = nr;
+    out[SUM_VAL] = P.gs[0].val;
+    for (int x = SUM_VAL + 1; x < SUM_HDR; x++) out[x] = 0.0;
 }
 
 // start of a run (lib/dmrgg.f90:96-100, 141-148, 279-288): every per-run quantity back to its initial value in ONE launch
@@ -2123,7 +2185,8 @@ __device__ __forceinline__ void exch_apply_group(const DevProb &P, int g)
     }
 }
 
-__global__ __launch_bounds__(256) void k_exch_pack(DevProb P) { if (P.ctl[0]) return; exch_pack_group(P, blockIdx.x); }
+// force: the finalisation's pack, which runs behind the stop flag without clearing it first
+__global__ __launch_bounds__(256) void k_exch_pack(DevProb P, int force) { if (P.ctl[0] && !force) return; exch_pack_group(P, blockIdx.x); }
 __global__ __launch_bounds__(256) void k_exch_apply(DevProb P) { exch_apply_group(P, blockIdx.x); }
 
 // MAX all-reduce result (:867-870, :961) folded into the apply launch: every block reduces the same inputs and
@@ -2445,7 +2508,11 @@ __global__ __launch_bounds__(256) void k_sweep_summary(DevProb P, int it, double
 
 // binary-tree product of the partial quadrature matrices of ALL groups (lib/dmrgg.f90:1355-1405); single
 // block, run redundantly by every GPU on the all-reduced P.qall so that every rank holds the same value
-__global__ __launch_bounds__(256) void k_quad_tree(DevProb P)
+// lds != 0 (CreatePlan::lds_qtree): the matrices live in LDS, in two regions of ng matrices -- a product reads its two factors from
+// the region each of them is in and writes the other region of the left one, so the products of a level need no copy back and no
+// barrier between them.  Every entry is the same sum c = c + B(l,j) A(i,l) in the same l order as below: the bits stay.  What is
+// gone are the loads of the dependent sums out of L2 (56 of the 57 us of this kernel at C_16) and two of three barriers per product.
+__global__ __launch_bounds__(256) void k_quad_tree(DevProb P, int lds)
 {
     if (P.ctl[2]) return;
     const int tid = threadIdx.x, RM = P.RM, ng = P.nprocs;
@@ -2454,6 +2521,34 @@ __global__ __launch_bounds__(256) void k_quad_tree(DevProb P)
     double *work = P.qwork;
     for (int g = tid; g < ng; g += blockDim.x) { mym[g] = (int)dims[2 * g]; myn[g] = (int)dims[2 * g + 1]; }
     __syncthreads();
+    if (lds) {
+        extern __shared__ double qsh[];
+        __shared__ int wh[256];                         // the region group g's matrix is in
+        const size_t MS = (size_t)RM * RM, REG = (size_t)ng * MS;
+        for (int g = tid; g < ng; g += blockDim.x) wh[g] = 0;
+        for (int g = 0; g < ng; g++)
+            for (int x = tid; x < mym[g] * myn[g]; x += blockDim.x) qsh[(size_t)g * MS + (x % mym[g]) + RM * (x / mym[g])] = part[(size_t)g * MS + (x % mym[g]) + RM * (x / mym[g])];
+        __syncthreads();
+        for (int q = 1; q < ng; q *= 2) {
+            for (int me = 0; me + q < ng; me += 2 * q) {
+                const int her = me + q;
+                const double *Aa = qsh + (size_t)wh[me] * REG + (size_t)me * MS, *Bb = qsh + (size_t)wh[her] * REG + (size_t)her * MS;
+                double *dst = qsh + (size_t)(wh[me] ^ 1) * REG + (size_t)me * MS;
+                const int mm = mym[me], kk = myn[me], nn = myn[her];
+                for (int x = tid; x < mm * nn; x += blockDim.x) {
+                    int i = x % mm, j = x / mm;
+                    double c = 0.0;
+                    for (int l = 0; l < kk; l++) c = c + Bb[l + RM * j] * Aa[i + RM * l];     // dgemm 'n','n', :1381
+                    dst[i + RM * j] = c;
+                }
+            }
+            __syncthreads();
+            if (tid == 0) for (int me = 0; me + q < ng; me += 2 * q) { myn[me] = myn[me + q]; wh[me] ^= 1; }
+            __syncthreads();
+        }
+        if (tid == 0) { const double v = qsh[(size_t)wh[0] * REG]; for (int g = 0; g < P.G; g++) P.gs[g].val = v; }
+        return;
+    }
     for (int g = 0; g < ng; g++)
         for (int x = tid; x < mym[g] * myn[g]; x += blockDim.x) work[(size_t)g * RM * RM + (x % mym[g]) + RM * (x / mym[g])] = part[(size_t)g * RM * RM + (x % mym[g]) + RM * (x / mym[g])];
     __syncthreads();

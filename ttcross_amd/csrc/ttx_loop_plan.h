@@ -19,6 +19,9 @@ struct LoopIn {
     bool sweep_tail = false;        // sel.sweep_tail (TTX_TAIL)
     bool sweep_tail_side = false;   // sel.sweep_tail_side (TTX_TAIL_SIDE)
     int maxrank = 1;
+    bool head_direct = false;       // sel.head_direct (TTX_HEAD_DIRECT)
+    bool fin_early = false;         // sel.fin_early (TTX_FIN_EARLY)
+    bool fin_skip_exch = false;     // sel.fin_skip_exch (TTX_FIN_SKIP_EXCH)
 };
 
 struct LoopPlan {
@@ -50,6 +53,28 @@ struct LoopPlan {
     // (DevProb::tail_side).  That side work is enqueued AFTER the next sweep kernel: at short sweeps (C_16) the host is what the
     // main stream waits for.
     bool side = false;
+    // `head` without k_collect and the copy in front of sweep kernel 1, which reads nothing of either: k_init_final knows the whole
+    // initial summary (ranks 1, tapes -1, the groups' counters and maxima final after k_init_fibers) and writes it into the pinned slot
+    // itself, as k_sweep_end writes a sweep's.  A k_collect beside sweep kernel 1 would race with its writes of r and tape.  Every
+    // other form keeps readback().
+    bool head_direct = false;
+    // The finalisation overwrites arg in place, and of the forked quadrature's kernels only k_quad_build reads arg (k_quad_chain reads
+    // Tq, k_quad_tree qall): with `fin_early` the finalisation waits for an event behind the last quadrature's k_quad_build instead of
+    // the value's copy, and runs beside the chain, the tree and the copy.  The clearing of ctl[0..2] no longer stands in front of the
+    // LU kernels, which do not read ctl: it goes to the quadrature's stream behind k_quad_tree (which reads ctl[2]) and the value's
+    // copy, in front of the final k_collect (which reads ctl[0]) and its copy on the same stream; the pack of a final exchange is
+    // told to run behind the raised stop flag.  All of this is enqueued at once, the summary into the pinned slot the finished
+    // sweep does not use, BEFORE the host blocks for the value: its last waits overlap.  Only where the quadrature is forked
+    // (without it nothing waits, and with several processes it shares the main stream).
+    bool fin_early = false;
+    // The final exchange (k_exch_pack, k_exch_apply: dtt_lua shifts the rightmost inv of every group to its neighbour) repeats what
+    // the end of the last sweep did: every sweep end packs inv(last) unconditionally and applies it, and nothing writes inv, r or upd
+    // afterwards (the speculative sweep launch returns at its entry).  In one process it is left out behind at least one sweep --
+    // final_exchange().  A run without a sweep needs it (the initial cross leaves inv(first-1) = 1), several processes keep it.
+    bool fin_skip_exch = false;
+    int nproc = 1;
+    // does the finalisation of a run that made `sweeps` sweeps exchange first?
+    bool final_exchange(int sweeps) const { return nproc > 1 && !(fin_skip_exch && sweeps >= 1); }
 };
 
 inline LoopPlan loop_plan(const LoopIn &in)
@@ -60,5 +85,9 @@ inline LoopPlan loop_plan(const LoopIn &in)
     p.forkq = p.pipe && in.has_quad && in.W == 1;
     p.tail = p.pipe && in.cluster && in.W == 1 && in.nproc > 1 && !in.host_pass && in.sweep_tail;
     p.side = p.tail && p.forkq && in.sweep_tail_side;
+    p.head_direct = p.head && in.head_direct;
+    p.fin_early = p.forkq && in.fin_early;
+    p.fin_skip_exch = in.W == 1 && in.fin_skip_exch;
+    p.nproc = in.nproc;
     return p;
 }
