@@ -16,6 +16,7 @@
 #include <limits.h>
 #include <math.h>
 #include "ttx_cdf.h"     // TTX_HD
+#include "ttx_wave_solve.h"   // the two triangular wave solves of the append (host + device)
 
 // ------------------------------------------------------------------------------------------------
 // rule part (host + device)
@@ -150,34 +151,9 @@ __device__ __forceinline__ void bond_zero_lists(const int *vp, int r1, int r0, i
     __syncthreads();
 }
 
-// The two triangular solves of the append along the rank index as shuffle wavefronts: lane l of a group of lw lanes
-// (lw = 64, or 32 with two solves per wave) holds entry l, lu is the packed LU of the neighbour bond (LDS or global).
-// Every lane of the wave calls them; lanes at or beyond the rank pass 0 and get nothing of use back.
-// role C, x = L^-1 a (:715-728, d2_luar)
-__device__ __forceinline__ double wave_solve_L(const double *lu, int r, double a, int l, int lw)
-{
-    double tmp = 0.0, xf = 0.0;
-    for (int s = 0; s < r; s++) {
-        const double cand = (s == 0) ? a : a + (-1.0) * tmp;
-        const double xsv = __shfl(cand, s, lw);
-        if (l == s) xf = xsv;
-        if (l > s && l < r) tmp = tmp + xsv * lu[l * l + s];
-    }
-    return xf;
-}
-// role D, y U^-1 (:730-749, d2_lual); rdg = wave_solve_rdg(lu, r, l), taken once for all solves against the same lu
-__device__ __forceinline__ double wave_solve_rdg(const double *lu, int r, int l)
-{ return (l < r) ? 1.0 / lu[(l + 1) * (l + 1) - 1] : 0.0; }       // 1/U(s,s) held by lane s
-__device__ __forceinline__ double wave_solve_U(const double *lu, int r, double y, double rdg, int l, int lw)
-{
-    for (int s = 0; s < r; s++) {
-        const double cand = rdg * y;          // only lane s's product is used: (1.0 / U(s,s)) * y_s
-        const double ys = __shfl(cand, s, lw);
-        if (l == s) y = ys;
-        if (l > s && l < r) y = y + (-lu[l * l + l + s]) * ys;
-    }
-    return y;
-}
+// The two triangular solves of the append along the rank index (roles C and D: dev_solve_L, dev_solve_rdg, dev_solve_U) are
+// ttx_wave_solve.h, included above: the value of lane s by lane reads instead of a shuffle, the LU entries requested ahead of
+// their step, the update by a select -- checked on the host by tests/wave_solve_main.cpp.
 
 // role E of an accepted pivot (ii, jj, kk, qq: 1-based) at bond p of rank r1 (:604-635).
 // index tables of the new pivot (replaces the vip walk of :1062-1075); threads tid, tid + nthr, ...
@@ -187,6 +163,26 @@ __device__ __forceinline__ void append_tables(const DevProb &P, int g, int p, in
     const short *Lo = L_ptr(P, g, p - 1, first), *Ro = R_ptr(P, g, p + 1, first);
     for (int x = tid; x < p; x += nthr) Ln[(size_t)x * P.RM + r1] = (x < p - 1) ? Lo[(size_t)x * P.RM + (ii - 1)] : (short)jj;
     for (int x = tid; x < P.d - p; x += nthr) Rn[(size_t)x * P.RM + r1] = (x == 0) ? (short)kk : Ro[(size_t)(x - 1) * P.RM + (qq - 1)];
+}
+// The same in two parts (k_sweep_cluster): thread tid requests its entry of either table (x = tid) ahead of the work that does not
+// need it, and stores it later; entries beyond the first nthr (d > nthr) are copied at the store as above.
+struct AppendTab { short l, r; };
+__device__ __forceinline__ AppendTab append_tables_fetch(const DevProb &P, int g, int p, int first, int ii, int qq, int tid)
+{
+    const short *Lo = L_ptr(P, g, p - 1, first), *Ro = R_ptr(P, g, p + 1, first);
+    AppendTab t{0, 0};
+    if (tid < p - 1) t.l = Lo[(size_t)tid * P.RM + (ii - 1)];
+    if (tid >= 1 && tid < P.d - p) t.r = Ro[(size_t)(tid - 1) * P.RM + (qq - 1)];
+    return t;
+}
+__device__ __forceinline__ void append_tables_store(const DevProb &P, int g, int p, int first, int r1, int ii, int jj, int kk, int qq, int tid, int nthr, AppendTab t)
+{
+    short *Ln = L_ptr(P, g, p, first), *Rn = R_ptr(P, g, p, first);
+    const short *Lo = L_ptr(P, g, p - 1, first), *Ro = R_ptr(P, g, p + 1, first);
+    if (tid < p) Ln[(size_t)tid * P.RM + r1] = (tid < p - 1) ? t.l : (short)jj;
+    if (tid < P.d - p) Rn[(size_t)tid * P.RM + r1] = (tid == 0) ? (short)kk : t.r;
+    for (int x = tid + nthr; x < p; x += nthr) Ln[(size_t)x * P.RM + r1] = (x < p - 1) ? Lo[(size_t)x * P.RM + (ii - 1)] : (short)jj;
+    for (int x = tid + nthr; x < P.d - p; x += nthr) Rn[(size_t)x * P.RM + r1] = (x == 0) ? (short)kk : Ro[(size_t)(x - 1) * P.RM + (qq - 1)];
 }
 // corner of the packed LU, pivot set, tape, update flag and the new rank; one thread
 __device__ __forceinline__ void append_scalars(const DevProb &P, int g, int p, int first, int r1, int ii, int jj, int kk, int qq, double pivot)

@@ -26,7 +26,7 @@
 // first-max rule is applied on global fiber positions, reused partial results are bit-identical by construction.
 #pragma once
 #include "ttx_fused.h"
-#include "ttx_mvn.h"       // mvn_lane: one double of a wave by v_readlane
+#include "ttx_mvn.h"
 #include "ttx_cluster_rules.h"   // cl_slice, cl_wact, cl_key, cl_ordered_sum: the rules a host program checks
 
 #define CB 256      // threads of a cluster workgroup
@@ -726,14 +726,28 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         } else {
             const int i0 = ii - 1, j0 = jj - 1, k0 = kk - 1, q0 = qq - 1;
             double *gI = inv_ptr(P, g, p, first);
-            // the factor entries at the final pivot (the half-steps keep theirs in registers)
-            for (int s = tid; s < r1; s += CB) { xsc[s] = Wq[k0 + (size_t)NM * q0 + P.SW * s]; xsr[s] = Cp[i0 + (size_t)RM * j0 + P.SS * s]; }
-            __syncthreads();
+            const bool reuseA = (rc_k == kk && rc_q == qq), reuseB = (rr_i == ii && rr_j == jj);    // block-uniform (s_rook)
+            // role E, tables: the entries of the new pivot's column are requested here and stored behind role D, so that block 0
+            // does not end its bond step with a dependent load (nobody reads the column before the closing cluster_sync)
+            AppendTab tab{0, 0};
+            if (cb == 0) tab = append_tables_fetch(P, g, p, first, ii, qq, tid);
+            // The factor entries at the final pivot (the half-steps keep theirs in registers) go through LDS only where the
+            // fall-back sums of roles A and B read them; where both residuals are reused, block 0's packed-LU copy is their one
+            // reader and takes them from global memory -- no staging and no barrier in any block.
             // role E first part: packed LU from the OLD factors (:649-660)
-            if (cb == 0)
-                for (int s = tid; s < r1; s += CB) { gI[r1 * r1 + s] = xsr[s]; gI[r1 * r1 + r1 + s] = xsc[s]; }
+            if (reuseA && reuseB) {
+                if (cb == 0)
+                    for (int s = tid; s < r1; s += CB) {
+                        const double c = Wq[k0 + (size_t)NM * q0 + P.SW * s], w = Cp[i0 + (size_t)RM * j0 + P.SS * s];
+                        gI[r1 * r1 + s] = w; gI[r1 * r1 + r1 + s] = c;
+                    }
+            } else {
+                for (int s = tid; s < r1; s += CB) { xsc[s] = Wq[k0 + (size_t)NM * q0 + P.SW * s]; xsr[s] = Cp[i0 + (size_t)RM * j0 + P.SS * s]; }
+                __syncthreads();
+                if (cb == 0)
+                    for (int s = tid; s < r1; s += CB) { gI[r1 * r1 + s] = xsr[s]; gI[r1 * r1 + r1 + s] = xsc[s]; }
+            }
             // role A: arg(p), col(p) new slab (:662-668, :701)
-            const bool reuseA = (rc_k == kk && rc_q == qq), reuseB = (rr_i == ii && rr_j == jj);
             for (int u = tid; u < r0 * nj; u += CB) {
                 const int i = u % r0, j = jlo + u / r0; const size_t o = i + (size_t)RM * j;
                 const double a = acol[u];
@@ -763,7 +777,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
             }
             CST(11);
             // roles C and D are triangular solves along the rank index, one per own column j / row k.  A solve occupies
-            // r0 (r2) lanes: with ranks up to 32 two of them share a wave (shuffles of width 32).
+            // r0 (r2) lanes: with ranks up to 32 two of them share a wave (ttx_wave_solve.h, PK = 2).
             // role C: row(p)(:, j, r1+1) = L(p-1)^-1 acol1(:, j)  (:715-728)
             if (p > first) {
                 const double *gL = ldsinv ? GL : inv_ptr(P, g, p - 1, first);
@@ -772,7 +786,8 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                 for (int base = wv * pk; base < nj; base += (CB / 64) * pk) {
                     const int jl = base + sub, j = jlo + jl;
                     const bool on = (jl < nj) && (l < r0);
-                    const double xf = wave_solve_L(gL, r0, on ? acol[l + r0 * jl] : 0.0, l, lw);
+                    const double a = on ? acol[l + r0 * jl] : 0.0;
+                    const double xf = (pk == 2) ? dev_solve_L<2>(gL, r0, a, l, sub) : dev_solve_L<1>(gL, r0, a, l, 0);
                     if (on) Wp[j + (size_t)NM * r1 + P.SW * l] = xf;
                 }
             }
@@ -782,18 +797,19 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                 const double *gU = ldsinv ? GU : inv_ptr(P, g, p + 1, first);
                 double *Cq = core_ptr(P, P.col, g, p + 1, first);
                 const int pk = (r2 <= 32) ? 2 : 1, lw = 64 / pk, l = lane & (lw - 1), sub = lane / lw;
-                const double rdg = wave_solve_rdg(gU, r2, l);
+                const double rdg = dev_solve_rdg(gU, r2, l);
                 for (int base = wv * pk; base < nk; base += (CB / 64) * pk) {
                     const int kl = base + sub, k = klo + kl;
                     const bool on = (kl < nk) && (l < r2);
-                    const double y = wave_solve_U(gU, r2, on ? arow[kl + nk * l] : 0.0, rdg, l, lw);
+                    const double y0 = on ? arow[kl + nk * l] : 0.0;
+                    const double y = (pk == 2) ? dev_solve_U<2>(gU, r2, y0, rdg, l, sub) : dev_solve_U<1>(gU, r2, y0, rdg, l, 0);
                     if (on) Cq[r1 + (size_t)RM * k + P.SS * l] = y;
                 }
             }
             CST(13);
             // role E: index tables, pivot set, scalars (:604-635)
             if (cb == 0) {
-                append_tables(P, g, p, first, r1, ii, jj, kk, qq, tid, CB);
+                append_tables_store(P, g, p, first, r1, ii, jj, kk, qq, tid, CB, tab);
                 if (tid == 0) append_scalars(P, g, p, first, r1, ii, jj, kk, qq, pivot);
             }
             if (zkeep && wv < 2) {                     // keep the sorted distinct lists of this bond current:

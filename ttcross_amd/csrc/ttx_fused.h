@@ -7,7 +7,7 @@
 //   * the node/weight VALUES of both pivot tables (bond p-1 left, bond p+1 right) are staged once per bond in LDS
 //     and serve the lottery candidates and every rook half-step;
 //   * fibers (acol1 / arow1), the factor vector, the lottery lists and all arg-max reductions live in LDS;
-//   * the neighbour fix-ups run as wave-shuffle wavefronts (no block barrier per LU step).
+//   * the neighbour fix-ups run as wavefronts over the lanes of a wave (ttx_wave_solve.h; no block barrier per LU step).
 // Arithmetic and its order are identical to the multi-kernel path (and to the oracle): same device functions.
 #pragma once
 #include "ttx_kernels.h"
@@ -228,29 +228,22 @@ __global__ __launch_bounds__(FB) void k_sweep_fused(DevProb P, int dir, int nste
                 for (int s = 0; s < r1; s++) tt = tt + Wq[o + P.SW * s] * xs[s];
                 Wq[o + P.SW * r1] = a + (-1.0) * tt;
             }
-            // role C: row(p)(:, j, r1+1) = L(p-1)^-1 acol1(:, j)  (:715-728): one wave per column, shuffle wavefront
+            // role C: row(p)(:, j, r1+1) = L(p-1)^-1 acol1(:, j)  (:715-728): one wave per column (ttx_wave_solve.h)
             if (p > first) {
                 const double *gL = inv_ptr(P, g, p - 1, first);
                 double *Wp = core_ptr(P, P.row, g, p, first);
                 for (int j = wv; j < n1; j += FB / 64) {
-                    const double xf = wave_solve_L(gL, r0, (lane < r0) ? acol[lane + r0 * j] : 0.0, lane, 64);
+                    const double xf = dev_solve_L<1>(gL, r0, (lane < r0) ? acol[lane + r0 * j] : 0.0, lane, 0);
                     if (lane < r0) Wp[j + (size_t)NM * r1 + P.SW * lane] = xf;
                 }
             }
-            // role D: col(p+1)(r1+1, k, :) = arow1(k, :) U(p+1)^-1  (:730-749).  Own copy of wave_solve_U (ttx_bondstep.h) with
-            // the reciprocal taken per step: holding it per lane across the loop costs this kernel another spilled register
+            // role D: col(p+1)(r1+1, k, :) = arow1(k, :) U(p+1)^-1  (:730-749)
             if (p < last) {
                 const double *gU = inv_ptr(P, g, p + 1, first);
                 double *Cq = core_ptr(P, P.col, g, p + 1, first);
+                const double rdg = dev_solve_rdg(gU, r2, lane);
                 for (int k = wv; k < n2; k += FB / 64) {
-                    double y = (lane < r2) ? arow[k + n2 * lane] : 0.0;
-                    for (int s = 0; s < r2; s++) {
-                        const double dg = gU[(s + 1) * (s + 1) - 1];
-                        const double cand = (1.0 / dg) * y;
-                        const double ys = __shfl(cand, s, 64);
-                        if (lane == s) y = ys;
-                        if (lane > s && lane < r2) y = y + (-gU[lane * lane + lane + s]) * ys;
-                    }
+                    const double y = dev_solve_U<1>(gU, r2, (lane < r2) ? arow[k + n2 * lane] : 0.0, rdg, lane, 0);
                     if (lane < r2) Cq[r1 + (size_t)RM * k + P.SS * lane] = y;
                 }
             }

@@ -1763,11 +1763,11 @@ __global__ __launch_bounds__(TTX_BLK) void k_accept(DevProb P, int H, int nA)
         const double *gI = inv_ptr(P, g, p - 1, first);
         double *Wp = core_ptr(P, P.row, g, p, first);
         double a = (tid < r0) ? acol[tid + r0 * j] : 0.0, tmp = 0.0, xf = 0.0;
-        if (r0 <= 64) {                               // one wave: the solve runs as a shuffle wavefront over the LDS-staged LU (as k_exch_boundary)
+        if (r0 <= 64) {                               // one wave: the solve runs as a lane-read wavefront over the LDS-staged LU (as k_exch_boundary)
             double *lu = dyn;
             for (int x = tid; x < r0 * r0; x += TTX_BLK) lu[x] = gI[x];
             __syncthreads();
-            if (tid < 64) xf = wave_solve_L(lu, r0, a, tid, 64);
+            if (tid < 64) xf = dev_solve_L<1>(lu, r0, a, tid, 0);
         } else
         for (int s = 0; s < r0; s++) {
             if (tid == s) { xf = a + (-1.0) * tmp; if (s == 0) xf = a; s_bc = xf; }
@@ -1787,7 +1787,7 @@ __global__ __launch_bounds__(TTX_BLK) void k_accept(DevProb P, int H, int nA)
             double *lu = dyn;
             for (int x = tid; x < r2 * r2; x += TTX_BLK) lu[x] = gI[x];
             __syncthreads();
-            if (tid < 64) y = wave_solve_U(lu, r2, y, wave_solve_rdg(lu, r2, tid), tid, 64);
+            if (tid < 64) y = dev_solve_U<1>(lu, r2, y, dev_solve_rdg(lu, r2, tid), tid, 0);
         } else
         for (int s = 0; s < r2; s++) {
             if (tid == s) { y = (1.0 / gI[(s + 1) * (s + 1) - 1]) * y; s_bc = y; }
@@ -2367,11 +2367,11 @@ __device__ __forceinline__ void exch_boundary_block(const DevProb &P, int bx, in
         // row(p+1)(:, k, new) = L(p)^-1 * column : d2_luar(n(p+1), r(p), inv(p), .) :940-951
         const double *gI = inv_ptr(P, g, p, first);
         double tmp = 0.0, xf = 0.0;
-        if (rp <= 64) {                               // one wave: the solve runs as a shuffle wavefront over LDS-staged LU
+        if (rp <= 64) {                               // one wave: the solve runs as a lane-read wavefront over LDS-staged LU
             __syncthreads();
             for (int x = tid; x < rp * rp; x += TTX_BLK) lu[x] = gI[x];
             __syncthreads();
-            if (tid < 64) xf = wave_solve_L(lu, rp, a, tid, 64);
+            if (tid < 64) xf = dev_solve_L<1>(lu, rp, a, tid, 0);
         } else
         for (int s = 0; s < rp; s++) {
             if (tid == s) { xf = (s == 0) ? a : a + (-1.0) * tmp; s_bc = xf; }
@@ -2421,7 +2421,7 @@ __device__ __forceinline__ void exch_boundary_block(const DevProb &P, int bx, in
             __syncthreads();
             for (int x = tid; x < rp * rp; x += TTX_BLK) lu[x] = gI[x];
             __syncthreads();
-            if (tid < 64) y = wave_solve_U(lu, rp, y, wave_solve_rdg(lu, rp, tid), tid, 64);
+            if (tid < 64) y = dev_solve_U<1>(lu, rp, y, dev_solve_rdg(lu, rp, tid), tid, 0);
         } else
         for (int s = 0; s < rp; s++) {
             if (tid == s) { y = (1.0 / gI[(s + 1) * (s + 1) - 1]) * y; s_bc = y; }

@@ -71,12 +71,7 @@ __device__ __forceinline__ double mvn_quadform_wave(int m, const double *dv, int
 // with two v_readlane_b32 into an SGPR pair (independent of the running sum) and a v_add_f64 with a scalar operand: three
 // VALU instructions per term, no LDS traffic, no barrier.  The per-lane term of the free dimension replaces lane L's at its place
 // in the order by a uniform select.  Operations and their order per lane are unchanged: bit-identical.
-__device__ __forceinline__ double mvn_lane(double x, int k)
-{
-    const long long b = __double_as_longlong(x);
-    const int lo = __builtin_amdgcn_readlane((int)b, k), hi = __builtin_amdgcn_readlane((int)(b >> 32), k);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
+// (mvn_lane itself is ttx_wave_solve.h: the append's triangular solves take their lane values the same way.)
 // sixteen lane values at a time into scalar registers first (so that the reads run ahead of the dependent adds), then the adds.
 // The term of lane kL is replaced by `special`: the batch of sixteen that contains it (BL, a template parameter: one straight
 // line of code per position, chosen by ONE wave-uniform branch per row) pays for the selects; a branch per batch instead kept the
