@@ -514,7 +514,7 @@ int ttx_sample_last(const ttx_engine *h, double *ms_head, double *bytes_head, do
  * multi-process engine is refused as by ttx_sample.
  * ttx_sample_sq_last: of the last call on this engine, the milliseconds (HIP events) of the head pass, of the rows kernels and of
  * k_sq_pick with k_sq_step (summed over modes and chunks), the flops of the rows, the failed samples and the mode that ran; any pointer may be
- * NULL.  Open: the real-valued variant, per-sample weights, ranks above 128.  Added without a new ttx_version: look the symbols up. */
+ * NULL.  The real-valued variant is ttx_sample_sq_real.  Open: per-sample weights, ranks above 128.  Added without a new ttx_version: look the symbols up. */
 int ttx_sample_sq    (ttx_engine *h, int64_t npts, const double *u /* [npts][d] */, const double *w, const int32_t *fixed,
                       double gamma, int32_t mode, int32_t *ind, double *logq, double *val);
 int ttx_sample_sq_dev(ttx_engine *h, int64_t npts, const double *u, const double *w, const int32_t *fixed,
@@ -572,12 +572,72 @@ int ttx_sample_sq_last(const ttx_engine *h, double *ms_head, double *ms_rows, do
  * at); a node row that is missing, not finite or not strictly ascending, cond_k = +-Inf (before any device call); ranks above 128.
  * TTX_ESTATE: an engine without a train; a multi-process engine is refused as by ttx_sample.
  * ttx_sample_real_last: as ttx_sample_last, for k_sm_head and k_sr_draw of the last ttx_sample_real on this engine.
- * Open: a direct COS-basis sampler (root finding on a density that may go negative), the real-valued squared-density (SIRT) variant (ttx_sample_sq draws grid indices), an MFMA
+ * For a signed train ttx_sample_sq_real draws from the squared interpolant.  Open: a direct COS-basis sampler (root finding on a density that may go negative), an MFMA
  * path for the rows of p, extra per-mode weights, ranks above 128.  Added without a new ttx_version: look the symbols up. */
 int ttx_sample_real    (ttx_engine *h, int64_t npts, const double *u /* [npts][d] */, const double *const *nodes /* [d] host rows of n_k */,
                         const double *cond /* [d] or NULL */, double *x /* [npts][d] */, int32_t *cell /* [npts][d] or NULL */, double *logq, double *val);
 int ttx_sample_real_dev(ttx_engine *h, int64_t npts, const double *u, const double *const *nodes, const double *cond, double *x, int32_t *cell, double *logq, double *val);
 int ttx_sample_real_last(const ttx_engine *h, double *ms_head, double *bytes_head, double *ms_draw, int64_t *nfailed);
+
+/* REAL-valued samples drawn from the SQUARE of the interpolant of the resident train, on the device
+ * (ttcross_amd/csrc/ttx_sample_sq_real.h): ttx_sample_sq's squared-density sampler (SIRT: Cui and Dolgov, 2022) on the continuous
+ * domain of ttx_sample_real.  The resident train holds grid values of g at the nodes t_k; g(x) is its piecewise-multilinear
+ * interpolant, what ttx_basis_batch evaluates with TTX_BASIS_LINEAR and TTX_EVAL_EXACT.  The call draws from
+ *   (g(x)^2 + gamma) / (Z + gamma V)
+ * over the drawn modes: Z is the integral of g^2 over the box of the drawn modes at the held coordinates, V the product of
+ * t_(n-1) - t_0 over the drawn modes.  Every conditional is a sum of squares, so this holds for ANY train, signed or not.
+ * u, nodes, cond, x, cell, logq, val and the held-mode rules (a finite cond_k holds the mode at that real coordinate, n_k = 1 is
+ * always held) are ttx_sample_real's; gamma and mode are ttx_sample_sq's.
+ * Definition (numpy restates it: tests/sample_sq_real_ref.py).  h_i = t_(i+1) - t_i.
+ * Mass factors, on the host.  For a drawn mode the hat functions' mass matrix M_k is tridiagonal: M(i, i) = (h_(i-1) + h_i) / 3.0
+ * with one term at each end, M(i, i+1) = h_i / 6.0.  Its Cholesky factor M_k = U_k^T U_k is upper bidiagonal:
+ *   dg(0) = sqrt(M(0,0)),  sp(i) = M(i,i+1) / dg(i),  dg(i+1) = sqrt(M(i+1,i+1) - sp(i) * sp(i)),  sp(n-1) = 0,
+ * in plain double with separate operations.  For a held mode dg and sp are zero except dg(ci) = phi0 and sp(ci) = phi1, the hat row
+ * of cond_k by ttx_basis_host's rule (ci its cell).
+ * Head pass: ttx_sample_sq's, with the rows handed to the QR generalised to dg(i) H_k(a, i, :) + sp(i) H_k(a, i+1, :) (the last
+ * index has the first term only).  F_k, the power-of-two scaling and s_k are unchanged;
+ *   g_k = gamma * prod_(j<k) L_j * 2^(-2 s_(k-1)),  L_j = t_(n-1) - t_0 for a drawn mode and 1 for a held one.
+ * Draw, from the LAST mode to the first, with the state x of dtt_ijk's chain, x_(d+1) = [1].  For a drawn mode k:
+ *   m(a, i) = sum_b H_k(a, i, b) x_(k+1)(b),  s(i) = sum_a m(a, i)^2 (i = 0 .. n-1),  c(j) = sum_a m(a, j) m(a, j+1) (j = 0 .. n-2).
+ *   TTX_EVAL_EXACT: all sums ascending from 0.0 with a separate multiply and add.  TTX_EVAL_MFMA: the sum over b in the order of
+ *   v_mfma_f64_16x16x4_f64, the sums over a ascending from 0.0 in a register.
+ *   lim = sqrt(s(j)) * sqrt(s(j+1)); c(j) is clamped into [-lim, lim] (a NaN passes through): the conditional cannot go negative
+ *   inside a cell.  q0 = s(j) + g_k, qm = c(j) + g_k, q1 = s(j+1) + g_k: the density along the cell is
+ *   q(l) = q0 (1-l)^2 + 2 qm l (1-l) + q1 l^2.  Cell mass A(j) = (((q0 + qm) + q1) / 3.0) * h_j.
+ *   The running sum C, T = u_k * C(n-2), the search "smallest cell with A > 0 and T < C", the rule "u >= 1 or none: the largest
+ *   cell with A > 0, lambda = 1" and s = min(max(T - C(j-1), 0), A(j)) are ttx_sample_real's.  Inside the cell lambda in [0, 1]
+ *   solves Q(l) = s / h_j, Q the cubic with Bernstein coefficients 0, q0/3, (q0 + qm)/3, (q0 + qm + q1)/3, by sqr_invert: the four
+ *   numbers are scaled by the power of two that takes max(q0, |qm|, q1) into [0.5, 1); then, from l = 0.5 on the bracket [0, 1], at
+ *   most 64 times: f = l * (q0 + l * ((qm - q0) + l * (((q0 - 2.0 * qm) + q1) / 3.0))) - s'; f > 0 lowers the upper end to l,
+ *   otherwise the lower end rises to l; the Newton step l - f / q(l), q(l) = q0 + l * (2.0 * (qm - q0) + l * ((q0 - 2.0 * qm) + q1)),
+ *   is taken if q(l) > 0 and it lies strictly inside the bracket, else the bracket's midpoint; it ends when l no longer changes.
+ *   s' <= 0 gives 0, s' >= Q(1) gives 1, anything that is not a number 0.  It holds where q touches zero inside the cell (a sign
+ *   change of g: qm = -sqrt(q0 q1), Q is flat).
+ *   x_k, its clamp into the cell, the cell of the rounded x_k and the hat values f0, f1 formed again from the rounded x_k are
+ *   ttx_sample_real's.  Log term, with i the hat cell: log(max((((f0*f0)*s(i) + ((2.0*f0)*f1)*c(i)) + (f1*f1)*s(i+1)) + g_k, 0) / C(n-2)).
+ * Chain step, all modes: ttx_sample_real's.  val equals ttx_basis_batch(x, TTX_BASIS_LINEAR on nodes, TTX_EVAL_EXACT) element for
+ * element in both modes; logq is the log of the proposal's density at x with respect to Lebesgue measure on the drawn modes, and
+ * for any train exp(logq) (Z + gamma V) = val^2 + gamma up to rounding: with gamma > 0 the importance weight val^2 / exp(logq)
+ * is bounded by Z + gamma V.
+ * Failed samples (row of NaN in x, cell 0, logq NaN, val 0.0, counted), safety, determinism and chunking (TTX_SAMPLE_CHUNK): as
+ * for ttx_sample_real and ttx_sample_sq.  The sums s and c of a chunk lie in two sheets [chunk][n_k] of the engine's work space; a
+ * sample's state, logq, failure flag and hat values stay there between the per-mode launches.  Every index comes from lane
+ * numbers, never from a value; the hat cell is range-checked again where the chain step reads it.  The train is not modified.
+ * TTX_EVAL_AUTO uses ttx_sample_sq's TTX_SQ_AUTO_FLOPS: on the D_64 train the two modes of this entry part in the same bracket, between
+ * 1.9e9 flops per call (a tie) and 1.9e10 (the matrix cores 2.5 times faster); profiles/sample_sq_real_mi355x.txt.
+ * ttx_sample_sq_real_dev: u, x, cell, logq and val are pointers on the engine's device, nodes and cond stay host pointers.
+ * npts = 0 succeeds and launches nothing.  TTX_EINVAL: npts < 0, null u / x / nodes with npts > 0, an unknown mode, gamma negative
+ * or not finite (all before the engine is looked at); a node row that is missing, not finite or not strictly ascending, cond_k =
+ * +-Inf, ranks above 128, two sheets of a chunk times the largest mode above 2^28 entries (before any launch).  TTX_ESTATE: an
+ * engine without a train; a multi-process engine is refused as by ttx_sample.
+ * ttx_sample_sq_real_last: as ttx_sample_sq_last, for the head pass, the rows kernels and k_sqr_pick with k_sqr_step.
+ * Open: per-sample weights, ranks above 128.  Added without a new ttx_version: look the symbols up. */
+int ttx_sample_sq_real    (ttx_engine *h, int64_t npts, const double *u /* [npts][d] */, const double *const *nodes /* [d] host rows of n_k */,
+                           const double *cond /* [d] or NULL */, double gamma, int32_t mode, double *x /* [npts][d] */, int32_t *cell /* [npts][d] or NULL */,
+                           double *logq, double *val);
+int ttx_sample_sq_real_dev(ttx_engine *h, int64_t npts, const double *u, const double *const *nodes, const double *cond, double gamma, int32_t mode, double *x,
+                           int32_t *cell, double *logq, double *val);
+int ttx_sample_sq_real_last(const ttx_engine *h, double *ms_head, double *ms_rows, double *ms_pick, double *flops, int64_t *nfailed, int32_t *mode_ran);
 
 /* The largest elements of the resident train by a beam search along the train, on the device (ttcross_amd/csrc/ttx_topk.h), with
  * an upper bound on everything the search discarded.  Modes are 1-based, G_k is core k, r_0 = r_d = 1.

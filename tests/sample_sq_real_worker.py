@@ -1,0 +1,79 @@
+"""Child of test_gpu_sample_sq_real.py, in a process of its own.
+  chunk NAME MODE : the samples of case NAME (signed) under whatever TTX_SAMPLE_CHUNK the parent set; prints a digest of x, cell, logq, val
+  dev             : the device-pointer entry (ttx_sample_sq_real_dev) with torch tensors against the host entry -- torch brings a HIP
+                    runtime of its own and has to initialise its device before the engine's library does (tijk_dev_worker.py)
+  nan             : a NaN and an Inf in a core, both modes: the range of the cells written and the count of failed samples
+Prints one JSON line."""
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+NAMES = ("x", "cell", "logq", "val")
+
+
+def digest(res):
+    return hashlib.sha256(b"".join(res[k].tobytes() for k in NAMES)).hexdigest()
+
+
+def main():
+    what = sys.argv[1]
+    if what == "dev":
+        import torch
+        torch.cuda.init()
+    import sample_sq_real_ref as Q
+    from ttcross_amd import engine as E
+    if what == "chunk":
+        cores, u, nodes = Q.case(sys.argv[2], True)
+        tt = E.TTCross.from_cores(cores)
+        print(json.dumps(dict(digest=digest(tt.sample_sq_real(u, nodes, gamma=0.125, mode=sys.argv[3])), failed=tt.sample_sq_real_last()["failed"])))
+        return
+    if what == "nan":
+        cores, u, nodes = Q.case("d3", True)
+        u = u[:500]
+        ncell = np.array([c.shape[1] - 1 for c in cores])
+        out = {}
+        for tag, bad in (("nan", np.nan), ("inf", np.inf)):
+            cs = [c.copy() for c in cores]
+            cs[1][1, 4, 0] = bad
+            tt = E.TTCross.from_cores(cs)
+            for mode in ("exact", "mfma"):
+                res = tt.sample_sq_real(u, nodes, mode=mode)
+                failed = np.isnan(res["x"][:, 0])
+                good = ~failed
+                inside = all(np.all((res["x"][good, k] >= nodes[k][0]) & (res["x"][good, k] <= nodes[k][-1])) for k in range(3))
+                out[tag + "_" + mode] = dict(in_range=bool(np.all(res["cell"] >= 0) and np.all(res["cell"] <= ncell[None, :]) and inside),
+                                             whole_rows=bool(np.all(np.isnan(res["x"][failed])) and np.all(res["cell"][failed] == 0) and np.all((res["cell"] > 0)[good])),
+                                             failed=int(failed.sum()), counted=tt.sample_sq_real_last()["failed"],
+                                             marked=bool(np.all(np.isnan(res["logq"][failed])) and np.all(res["val"][failed] == 0.0)))
+        print(json.dumps(out))
+        return
+    cores, u, nodes = Q.case("d8_unequal", True)
+    tt = E.TTCross.from_cores(cores)
+    cond = [np.nan, np.nan, float(nodes[2][0]), np.nan, np.nan, np.nan, 0.5 * float(nodes[6][0] + nodes[6][1]), np.nan]
+    u[7, 3] = np.nan
+    res = {}
+    for mode in ("exact", "mfma"):
+        host = tt.sample_sq_real(u, nodes, cond, 0.125, mode)
+        t = torch.from_numpy(u).to("cuda:0")
+        dev = tt.sample_sq_real(t, nodes, cond, 0.125, mode)
+        same = all(np.array_equal(dev[k].cpu().numpy(), host[k], equal_nan=(k != "cell")) for k in NAMES)
+        chain = tt.basis_batch(dev["x"][:7].contiguous(), [("linear", tk) for tk in nodes], "exact")
+        res[mode] = dict(is_cuda=all(bool(v.is_cuda) for v in dev.values()), dtypes=[str(dev[k].dtype) for k in NAMES], equal=bool(same),
+                         failed=tt.sample_sq_real_last()["failed"], only_x=sorted(tt.sample_sq_real(t, nodes, cond, 0.125, mode, want=("x",))),
+                         chain=bool(np.array_equal(chain.cpu().numpy(), host["val"][:7])), empty=list(tt.sample_sq_real(t[:0].contiguous(), nodes)["x"].shape))
+    try:
+        tt.sample_sq_real(t.to(torch.float32), nodes)
+        res["float32_refused"] = False
+    except ValueError:
+        res["float32_refused"] = True
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -57,6 +57,7 @@ static cluster_kernel_t cluster_kernel(int var)
 #include "ttx_sample_real.h"
 #include "ttx_topk.h"
 #include "ttx_sample_sq.h"
+#include "ttx_sample_sq_real.h"
 #include "ttx_trainfun.h"
 
 static thread_local std::string g_err;
@@ -261,6 +262,9 @@ struct ttx_engine {
     double sq_ms_head = 0.0, sq_ms_rows = 0.0, sq_ms_pick = 0.0, sq_flops = 0.0;      // the last ttx_sample_sq
     int64_t sq_failed = 0;
     int sq_mode = -1;
+    double sqr_ms_head = 0.0, sqr_ms_rows = 0.0, sqr_ms_pick = 0.0, sqr_flops = 0.0;  // the last ttx_sample_sq_real
+    int64_t sqr_failed = 0;
+    int sqr_mode = -1;
     double rs_ms[4] = {0.0, 0.0, 0.0, 0.0}, rs_flops = 0.0;                    // the last ttx_lincomb_round with this engine first: sketch, gemm, qr, advance
     std::vector<int32_t> rs_l;                                                  // its sketch ranks l(0 .. d)
     int rs_mode = -1;
@@ -4162,25 +4166,29 @@ extern "C" int ttx_topk_last(const ttx_engine *h, double *ms_gram, double *ms_sc
 
 // ---- samples from the square of the resident train (ttx_sample_sq.h) -----------------------------------------------------------
 namespace {
-struct SqHead {                             // what sq_head leaves for the draw (and, later, for a real-valued variant): tables on the device
+struct SqHead {                             // what sq_head leaves for the draw of ttx_sample_sq and of ttx_sample_sq_real: tables on the device
     double *H = nullptr, *F = nullptr, *g = nullptr;    // SqPlan's H and F tables; g[k]: the defensive term of 0-based mode k in the units of F_k
     const double *w = nullptr;              // the effective weights
     const int *fixed = nullptr;
+    const double *sp = nullptr, *nodes = nullptr;       // ttx_sample_sq_real: the superdiagonals beside w (the diagonals), the node block
 };
 }
 // The one left-to-right pass: F_k and H_k by the plan pl for the effective weights eff (mode k at pl.woff[k]) and gw[k] = gamma prod_(j < k) W_j.
-// Between TM_HEAD's events; the resident train is only read.
-static int sq_head(ttx_engine *h, const SqPlan &pl, const std::vector<double> &eff, const std::vector<int> &fx, const std::vector<double> &gw, SqHead &Q)
+// Between TM_HEAD's events; the resident train is only read.  sp and nodes (ttx_sample_sq_real): eff holds the diagonals dg of the modes' bidiagonal
+// factors, sp their superdiagonals, and the rows of the QR are dg(i) H_k(a, i, :) + sp(i) H_k(a, i+1, :); nodes is uploaded beside them.
+static int sq_head(ttx_engine *h, const SqPlan &pl, const std::vector<double> &eff, const std::vector<int> &fx, const std::vector<double> &gw, SqHead &Q,
+                   const std::vector<double> *sp = nullptr, const std::vector<double> *nodes = nullptr)
 {
     int rc;
     const int d = h->d;
     const std::vector<int32_t> &r = h->rfinal;
     OpMeta meta(h->meta_host);
-    const size_t o_w = meta.put(eff), o_fx = meta.put(fx);
+    const size_t o_w = meta.put(eff), o_fx = meta.put(fx), o_sp = sp ? meta.put(*sp) : 0, o_nodes = nodes ? meta.put(*nodes) : 0;
     char *dm;
     if ((rc = meta.upload(h, SC_META, &dm)) || (rc = buf_reserve(h, SC_QH, sizeof(double) * pl.hoff[d])) ||
         (rc = buf_reserve(h, SC_QF, sizeof(double) * (pl.foff[d] + (size_t)d + 2)))) return rc;
     Q.w = (const double *)(dm + o_w); Q.fixed = (const int *)(dm + o_fx);
+    Q.sp = sp ? (const double *)(dm + o_sp) : nullptr; Q.nodes = nodes ? (const double *)(dm + o_nodes) : nullptr;
     Q.H = buf<double>(h, SC_QH); Q.F = buf<double>(h, SC_QF); Q.g = Q.F + pl.foff[d];
     int *st = (int *)(Q.g + d);
     const TtScratch s(h);
@@ -4191,8 +4199,8 @@ static int sq_head(ttx_engine *h, const SqPlan &pl, const std::vector<double> &e
         const int r0 = r[k - 1], n = h->n1[k], r1 = r[k], r1p = (r1 + 3) & ~3, l = pl.l[k - 1], mm = l * n;
         pack_core(h->stream, h, k, h->Wb);
         gemm(h, l, n * r1, r0, Q.F + pl.foff[k - 1], l, h->Wb, r0, h->Wc, l);
-        hipLaunchKernelGGL(k_sq_split, g1((size_t)mm * r1p), dim3(256), 0, h->stream, (const double *)h->Wc, l, n, r1, r1p, Q.w + pl.woff[k - 1], Q.H + pl.hoff[k - 1],
-                           k < d ? h->Wa : (double *)nullptr);
+        hipLaunchKernelGGL(k_sq_split, g1((size_t)mm * r1p), dim3(256), 0, h->stream, (const double *)h->Wc, l, n, r1, r1p, Q.w + pl.woff[k - 1],
+                           Q.sp ? Q.sp + pl.woff[k - 1] : (const double *)nullptr, Q.H + pl.hoff[k - 1], k < d ? h->Wa : (double *)nullptr);
         if (k == d) break;
         const double *R = h->Wa;
         int ldr = mm;
@@ -4314,6 +4322,144 @@ extern "C" int ttx_sample_sq_last(const ttx_engine *h, double *ms_head, double *
     if (flops) *flops = h->sq_flops;
     if (nfailed) *nfailed = h->sq_failed;
     if (mode_ran) *mode_ran = h->sq_mode;
+    return TTX_OK;
+}
+
+// ---- real-valued samples from the square of the interpolant of the resident train (ttx_sample_sq_real.h) -------------------------
+template <int KS>
+static void sqr_rows_mfma(ttx_engine *h, dim3 grid, const double *H, int l, int n, int r1, const double *X, int ldx, int C, int tper, double *S, double *Cs)
+{
+    hipLaunchKernelGGL(k_sqr_rows_mfma<KS>, grid, dim3(256), 0, h->stream, H, l, n, r1, X, ldx, C, tper, S, Cs);
+}
+// both entries: u, x, cell, logq, val are host pointers (dev false: staged chunk by chunk) or pointers on the engine's device
+static int sqr_run(ttx_engine *h, const char *who, int64_t npts, const double *u, const double *const *nodes, const double *cond, double gamma, int32_t mode, double *x,
+                   int32_t *cell, double *logq, double *val, bool dev)
+{
+    if (npts < 0 || (npts > 0 && (!u || !x || !nodes))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
+    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    if (!(gamma >= 0.0) || !std::isfinite(gamma)) return fail(TTX_EINVAL, "%s: gamma must be a finite number >= 0 (got %g)", who, gamma);
+    int rc = check_train_one_process(h, who);
+    if (rc) return rc;
+    const int d = h->d;
+    if (nodes) {
+        for (int k = 0; k < d; k++) {
+            ttx_basis b{TTX_BASIS_LINEAR, 0, 0.0, 0.0, nodes[k]};
+            if ((rc = bs_check_one(who, k + 1, b, h->n1[k + 1]))) return rc;
+        }
+    }
+    if (cond) for (int k = 0; k < d; k++) if (std::isinf(cond[k])) return fail(TTX_EINVAL, "%s: cond(%d) is infinite (a coordinate, or NaN for a drawn mode, expected)", who, k + 1);
+    std::vector<int> fx(d, 0);
+    if (nodes) for (int k = 0; k < d; k++) fx[k] = (cond && cond[k] == cond[k]) || h->n1[k + 1] == 1;
+    SqPlan pl;
+    sq_plan(d, h->n1.data() + 1, h->rfinal.data(), fx.data(), pl);
+    const int rmax = pl.rmax, nmax = pl.nmax;
+    if (rmax > 128) return fail(TTX_EINVAL, "%s: ranks up to 128 only (got %d)", who, rmax);
+    const size_t chunk = std::min<size_t>(env_chunk("TTX_SAMPLE_CHUNK", (size_t)1 << 18), (size_t)std::max<int64_t>(npts, 1));
+    if (2ll * (long long)chunk * nmax > TTX_SQ_SHEET)
+        return fail(TTX_EINVAL, "%s: two sheets of a chunk of %zu samples times the largest mode %d are %lld, they hold up to %lld (lower TTX_SAMPLE_CHUNK)", who, chunk, nmax,
+                    2ll * (long long)chunk * nmax, (long long)TTX_SQ_SHEET);
+    h->sqr_ms_head = h->sqr_ms_rows = h->sqr_ms_pick = h->sqr_flops = 0.0; h->sqr_failed = 0; h->sqr_mode = -1;
+    if (npts == 0) return TTX_OK;
+    if ((rc = tt_prepare(h, who))) return rc;
+    // the bidiagonal factors: the mass matrix's Cholesky factor of a drawn mode, the hat row of a held one (a mode of one node is held at its node)
+    std::vector<double> dg(pl.woff[d], 0.0), sp(pl.woff[d], 0.0), tnodes, gw(d + 1, gamma);
+    std::vector<SqrMode> modes(d);
+    for (int k = 0; k < d; k++) {
+        const int n = h->n1[k + 1];
+        const double *t = nodes[k];
+        SqrMode &M = modes[k];
+        M = SqrMode{0, 0, 1.0, 0.0, 0.0, tnodes.size()};
+        tnodes.insert(tnodes.end(), t, t + n);
+        double *dk = dg.data() + pl.woff[k], *sk = sp.data() + pl.woff[k];
+        if (!fx[k]) { sqr_mass_cholesky(t, n, dk, sk); gw[k + 1] = gw[k] * (t[n - 1] - t[0]); continue; }
+        const bool given = cond && cond[k] == cond[k];
+        M.held = 1; M.xh = given ? cond[k] : t[0];
+        M.cell = sr_hat_cell(t, n, M.xh);
+        M.phi0 = ttx_basis_entry(TTX_BASIS_LINEAR, 0, 0.0, 0.0, t, n, M.xh, M.cell);
+        M.phi1 = n > 1 ? ttx_basis_entry(TTX_BASIS_LINEAR, 0, 0.0, 0.0, t, n, M.xh, M.cell + 1) : 0.0;
+        dk[M.cell] = M.phi0; sk[M.cell] = M.phi1;
+        gw[k + 1] = gw[k];
+    }
+    SqHead Q;
+    if ((rc = sq_head(h, pl, dg, fx, gw, Q, &sp, &tnodes))) return rc;
+    const double flops = pl.flops * (double)npts;
+    // ttx_sample_sq's threshold: this entry's modes part in the same bracket on the D_64 train (profiles/sample_sq_real_mi355x.txt)
+    const int eff_mode = mode == TTX_EVAL_AUTO ? (flops >= TTX_SQ_AUTO_FLOPS ? TTX_EVAL_MFMA : TTX_EVAL_EXACT) : mode;
+    h->sqr_flops = flops; h->sqr_mode = eff_mode;
+    const int ldx = (rmax + 3) & ~3, ncu = dev_ncu(h);
+    if ((rc = buf_reserve(h, SC_QS, sizeof(double) * 2 * chunk * nmax)) || (rc = buf_reserve(h, SC_QX, (sizeof(double) * (2 * (size_t)ldx + 3) + 2 * sizeof(int)) * chunk)) ||
+        (rc = buf_reserve(h, SC_CNT, sizeof(long long)))) return rc;
+    double *S = buf<double>(h, SC_QS), *Cs = S + chunk * nmax, *Xa = buf<double>(h, SC_QX), *Xb = Xa + chunk * ldx;
+    SqrState st{Xb + chunk * ldx, nullptr, nullptr, nullptr, nullptr};
+    st.f0 = st.lq + chunk; st.f1 = st.f0 + chunk;
+    st.fail = (int *)(st.f1 + chunk); st.ci = st.fail + chunk;
+    SmPrep P;
+    P.chunk = chunk; P.gridmax = (int)std::min<long long>(((long long)chunk + 3) / 4, (long long)ncu * 8);
+    P.dcnt = buf<long long>(h, SC_CNT);
+    HIPCHECK(hipMemsetAsync(P.dcnt, 0, sizeof(long long), h->stream));
+    SmStage out[4] = {{x, sizeof(double) * (size_t)d, SC_SRX, nullptr}, {cell, sizeof(int) * (size_t)d, SC_IND, nullptr}, {logq, sizeof(double), SC_LQ, nullptr},
+                      {val, sizeof(double), SC_OUT, nullptr}};
+    RsMarks marks(h->rs_ev);                // phase 0: between the chunks, 1: rows, 2: picks and steps
+    int lrc = TTX_OK;
+    double ms_all = 0.0;
+    rc = sm_chunks(h, P, npts, u, dev, out, 4,
+        [&](size_t c, int grid, const double *du) {
+            const int C = (int)c;
+            double *Xo = Xa, *Xn = Xb;
+            hipLaunchKernelGGL(k_sq_ones, g1(c), dim3(256), 0, h->stream, Xo, ldx, C);          // x of the empty suffix
+            if (!lrc) lrc = marks.mark(h->stream, 0);
+            for (int k = d - 1; k >= 0; k--) {
+                const int r0 = h->rfinal[k], r1 = h->rfinal[k + 1], n = h->n1[k + 1], l = pl.l[k];
+                if (!fx[k]) {
+                    const double *Hk = Q.H + pl.hoff[k];
+                    if (eff_mode == TTX_EVAL_MFMA) {
+                        const int by = (C + 63) / 64, nt = (n + 13) / 15, tper = (int)std::max<long long>(1, (long long)nt * by / (4ll * ncu));
+                        const dim3 g((nt + tper - 1) / tper, by);
+                        if (r1 <= 16) sqr_rows_mfma<4>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S, Cs);
+                        else if (r1 <= 32) sqr_rows_mfma<8>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S, Cs);
+                        else if (r1 <= 64) sqr_rows_mfma<16>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S, Cs);
+                        else sqr_rows_mfma<32>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S, Cs);
+                    } else {
+                        const int g = (int)std::min<long long>(((long long)C * n + 255) / 256, (long long)ncu * 16);
+                        hipLaunchKernelGGL(k_sqr_rows_exact, dim3(g), dim3(256), 0, h->stream, Hk, l, n, r1, (const double *)Xo, ldx, C, S, Cs);
+                    }
+                    if (!lrc) lrc = marks.mark(h->stream, 1);
+                }
+                hipLaunchKernelGGL(k_sqr_pick, dim3(grid), dim3(256), 0, h->stream, n, k, d, modes[k], Q.fixed, Q.nodes, (const double *)(Q.g + k), (const double *)S,
+                                   (const double *)Cs, st, (long long)c, du, k == d - 1 ? 1 : 0, k == 0 ? 1 : 0, (double *)out[0].dev, (int *)out[1].dev, (double *)out[2].dev);
+                hipLaunchKernelGGL(k_sqr_step, dim3(grid), dim3(256), 0, h->stream, (const double *)core_dev(h, k + 1), h->RM, h->P.SS, r0, r1, n, st, (const double *)Xo, Xn, ldx,
+                                   (long long)c, k == 0 ? 1 : 0, (double *)out[3].dev);
+                if (!lrc) lrc = marks.mark(h->stream, 2);
+                std::swap(Xo, Xn);
+            }
+        },
+        [&](size_t c) { hipLaunchKernelGGL(k_sr_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const double *)out[0].dev, P.dcnt); },
+        &ms_all, &h->sqr_failed);
+    if (rc || (rc = lrc)) return rc;
+    double ms[3] = {0.0, 0.0, 0.0};
+    if ((rc = marks.sum(ms))) return rc;
+    h->sqr_ms_rows = ms[1]; h->sqr_ms_pick = ms[2];
+    return h->timer[TM_HEAD].ms(&h->sqr_ms_head);
+}
+extern "C" int ttx_sample_sq_real(ttx_engine *h, int64_t npts, const double *u, const double *const *nodes, const double *cond, double gamma, int32_t mode, double *x,
+                                  int32_t *cell, double *logq, double *val)
+{
+    return sqr_run(h, "ttx_sample_sq_real", npts, u, nodes, cond, gamma, mode, x, cell, logq, val, false);
+}
+extern "C" int ttx_sample_sq_real_dev(ttx_engine *h, int64_t npts, const double *u, const double *const *nodes, const double *cond, double gamma, int32_t mode, double *x,
+                                      int32_t *cell, double *logq, double *val)
+{
+    return sqr_run(h, "ttx_sample_sq_real_dev", npts, u, nodes, cond, gamma, mode, x, cell, logq, val, true);
+}
+extern "C" int ttx_sample_sq_real_last(const ttx_engine *h, double *ms_head, double *ms_rows, double *ms_pick, double *flops, int64_t *nfailed, int32_t *mode_ran)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_sample_sq_real_last: null engine");
+    if (ms_head) *ms_head = h->sqr_ms_head;
+    if (ms_rows) *ms_rows = h->sqr_ms_rows;
+    if (ms_pick) *ms_pick = h->sqr_ms_pick;
+    if (flops) *flops = h->sqr_flops;
+    if (nfailed) *nfailed = h->sqr_failed;
+    if (mode_ran) *mode_ran = h->sqr_mode;
     return TTX_OK;
 }
 

@@ -11,7 +11,7 @@
 //               the chain ends exactly where k_bs_exact (ttx_basis.h) would: val is the interpolant at x
 //   k_sr_count  the failed samples of a chunk (their rows of x start with a NaN), added to the call's counter by one workgroup
 // The first part of this file is plain C++ a host compiler accepts (tests/sample_real_main.cpp runs it on the CPU).
-// Open: a direct COS-basis sampler (root finding on a density that may go negative), the real-valued squared-density (SIRT) variant (ttx_sample_sq draws grid indices), an MFMA
+// Open: a direct COS-basis sampler (root finding on a density that may go negative; for a signed train ttx_sample_sq_real draws from the squared interpolant), an MFMA
 // path for the rows of p, extra per-mode weights, ranks above 128.
 #pragma once
 #include <math.h>

@@ -16,8 +16,8 @@
 //   k_sq_step          one wave per sample: the chain step of the picked index (sm_chain_step); the states stay in work space
 // then k_sm_count (ttx_sample.h) counts the failed samples.  No atomics and no sum whose order depends on the grid, the chunk or
 // the other samples: a call repeats bit for bit.  Every index comes from lane numbers and counts, never from a value.
-// Open: the real-valued variant (squared interpolant, mass-matrix factors, a cubic CDF inversion per cell) will reuse sq_head's
-// tables; per-sample weights; ranks above 128.
+// The real-valued variant (squared interpolant, mass-matrix factors, a cubic CDF inversion per cell) is ttx_sample_sq_real.h; it
+// reuses sq_head's tables.  Open: per-sample weights; ranks above 128.
 // The first part of this file is plain C++ a host compiler accepts (tests/sample_sq_main.cpp runs it on the CPU).
 #pragma once
 #include <math.h>
@@ -97,15 +97,16 @@ __global__ __launch_bounds__(256) void k_sq_ones(double *X, int ldx, int C)
 
 // C is the l x (n r1) product of the gemm, (a, i, b) at a + l (i + n b).  H: the same numbers with i contiguous, and r1p - r1 slabs
 // of zeros behind them (r1p = r1 rounded up to four: k_sq_rows_mfma's last step reads them).  A (null for the last mode): the rows
-// sqrt(e(i)) C(a, i, :) in C's own layout, the (l n) x r1 matrix the QR takes
-__global__ __launch_bounds__(256) void k_sq_split(const double *C, int l, int n, int r1, int r1p, const double *e, double *H, double *A)
+// sqrt(e(i)) C(a, i, :) in C's own layout, the (l n) x r1 matrix the QR takes.  sp (null for the grid sampler): e holds the diagonal dg
+// of a bidiagonal factor as it is and the rows are dg(i) C(a, i, :) + sp(i) C(a, i+1, :) (ttx_sample_sq_real.h); sp(n-1) is not read
+__global__ __launch_bounds__(256) void k_sq_split(const double *C, int l, int n, int r1, int r1p, const double *e, const double *sp, double *H, double *A)
 {
     const size_t M = (size_t)l * n * r1p, M1 = (size_t)l * n * r1;
     for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < M; q += (size_t)gridDim.x * 256) {
         const int a = (int)(q % l), i = (int)((q / l) % n), b = (int)(q / ((size_t)l * n));
         const double v = q < M1 ? C[q] : 0.0;
         H[i + (size_t)n * (a + (size_t)l * b)] = v;
-        if (A && q < M1) A[q] = sqrt(e[i]) * v;
+        if (A && q < M1) A[q] = !sp ? sqrt(e[i]) * v : i + 1 < n ? e[i] * v + sp[i] * C[q + l] : e[i] * v;
     }
 }
 

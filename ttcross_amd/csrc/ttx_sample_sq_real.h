@@ -1,0 +1,292 @@
+// ttx_sample_sq_real.h -- REAL-valued samples drawn from the SQUARE of the piecewise-multilinear interpolant of the resident train
+// (ttx_sample_sq_real / ttx_sample_sq_real_dev): the squared-density sampler (SIRT) of Cui and Dolgov (2022) on a continuous
+// domain.  Every conditional is the square of a piecewise-linear vector function, a quadratic per cell, so it is non-negative
+// whatever the signs of the cores; its CDF is a cubic per cell.
+//
+// The definition is in include/ttx.h.  The head pass is ttx_sample_sq's (sq_head) with the rows of the QR generalised from
+// sqrt(e(i)) H_k(a, i, :) to dg(i) H_k(a, i, :) + sp(i) H_k(a, i+1, :): dg and sp are the upper bidiagonal Cholesky factor of the hat
+// functions' mass matrix (sqr_mass_cholesky, on the host) for a drawn mode and the hat row of the coordinate for a held one.  Per
+// chunk and per mode k = d .. 1:
+//   k_sqr_rows_mfma / _exact   s(c, i) = sum_a m(a, i)^2 and c(c, j) = sum_a m(a, j) m(a, j+1), m(a, i) = sum_b H_k(a, i, b) x_c(b), to
+//                      two sheets [chunk][n_k]
+//   k_sqr_pick         one wave per sample: the cell masses from the sheets, the scan and the search of k_sr_draw, the root of the
+//                      cubic inside the cell (sqr_invert), x_k, the cell and the hat values of the rounded x_k, the log term
+//   k_sqr_step         one wave per sample: the two-term chain step of k_sr_draw (sr_chain_step); the states stay in work space
+// then k_sr_count (ttx_sample_real.h) counts the failed samples.  No atomics and no sum whose order depends on the grid, the chunk
+// or the other samples: a call repeats bit for bit.  Every index comes from lane numbers and counts, never from a value.
+// Open: per-sample weights, ranks above 128.
+// The first part of this file is plain C++ a host compiler accepts (tests/sample_sq_real_main.cpp runs it on the CPU).
+#pragma once
+#include <math.h>
+#include <stddef.h>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define TTX_SQR_HD __host__ __device__ inline
+#else
+#define TTX_SQR_HD static inline
+#endif
+
+// The upper bidiagonal Cholesky factor U (M = U^T U, U(i, i) = dg(i), U(i, i+1) = sp(i)) of the mass matrix of the hat functions on n
+// strictly ascending nodes: M(i, i) = (h_(i-1) + h_i) / 3 with one term at each end, M(i, i+1) = h_i / 6, h_i = t_(i+1) - t_i.  Plain
+// double, one operation at a time: numpy restates it bit for bit.  A single node has no cell: dg = 1, sp = 0 (the mode is held).
+TTX_SQR_HD void sqr_mass_cholesky(const double *t, int n, double *dg, double *sp)
+{
+    if (n == 1) { dg[0] = 1.0; sp[0] = 0.0; return; }
+    double diag = (t[1] - t[0]) / 3.0;
+    dg[0] = sqrt(diag);
+    for (int i = 0; i < n - 1; i++) {
+        const double h = t[i + 1] - t[i], off = h / 6.0;
+        sp[i] = off / dg[i];
+        diag = i + 1 < n - 1 ? (h + (t[i + 2] - t[i + 1])) / 3.0 : h / 3.0;
+        dg[i + 1] = sqrt(diag - sp[i] * sp[i]);
+    }
+    sp[n - 1] = 0.0;
+}
+
+// lambda in [0, 1] with Q(lambda) = sp, Q(l) = q0 l + (qm - q0) l^2 + (q0 - 2 qm + q1) l^3 / 3: the position inside a cell whose
+// density is q(l) = q0 (1-l)^2 + 2 qm l (1-l) + q1 l^2 (q0, q1 >= 0, |qm| <= sqrt(q0 q1) up to the defensive term, so q >= 0) at
+// which the mass per unit length sp = s / h is reached, 0 <= sp <= Q(1) = (q0 + qm + q1) / 3.  The four numbers are first scaled by
+// the power of two that takes max(q0, |qm|, q1) into [0.5, 1): lambda has no scale and the scaling is exact.  Then a safeguarded
+// Newton iteration on the bracket [0, 1]: the bracket shrinks with the sign of Q(l) - sp at every iterate, and a step that leaves
+// its interior, or starts where q <= 0, is replaced by the bracket's midpoint.  At most 64 iterations; it ends when lambda no
+// longer changes.  Where q touches zero inside the cell (a sign change of the interpolant, qm = -sqrt(q0 q1)) Q is flat and Newton
+// converges linearly with ratio 2/3: the residual Q - sp, of third order in the distance, is below 1e-30 max(q) after 64 steps.
+// sp <= 0 gives 0, sp >= Q(1) gives 1; anything that is not a number ends as 0.
+TTX_SQR_HD double sqr_invert(double q0, double qm, double q1, double sp)
+{
+    if (!(q0 == q0) || !(qm == qm) || !(q1 == q1) || !(sp == sp)) return 0.0;
+    double m = q0 > q1 ? q0 : q1;
+    const double am = fabs(qm);
+    m = am > m ? am : m;
+    if (!(m > 0.0) || m > 1.7976931348623157e308) return 0.0;
+    int e;
+    (void)frexp(m, &e);
+    q0 = ldexp(q0, -e); qm = ldexp(qm, -e); q1 = ldexp(q1, -e); sp = ldexp(sp, -e);
+    if (!(sp > 0.0)) return 0.0;
+    if (sp >= ((q0 + qm) + q1) / 3.0) return 1.0;
+    const double d1 = qm - q0, d2 = ((q0 - 2.0 * qm) + q1), d3 = d2 / 3.0;
+    double lo = 0.0, hi = 1.0, l = 0.5;
+    for (int it = 0; it < 64; it++) {
+        const double f = l * (q0 + l * (d1 + l * d3)) - sp;
+        if (f > 0.0) hi = l; else lo = l;
+        if (f == 0.0) break;
+        const double ql = q0 + l * (2.0 * d1 + l * d2);
+        double ln = l - f / ql;
+        if (!(ql > 0.0) || !(ln > lo && ln < hi)) ln = 0.5 * (lo + hi);
+        if (ln == l) break;
+        l = ln;
+    }
+    return l;
+}
+
+#if defined(__HIPCC__)
+#include "ttx_sample_real.h"   // sr_chain_step, k_sr_count
+#include "ttx_sample_sq.h"     // SqPlan, the head pass kernels, TTX_SQ_SHEET, TTX_SQ_AUTO_FLOPS
+#include "ttx_ttops.h"         // dbl4
+
+// EXACT: one thread per pair (c, i), grid-stride.  m(a, i) and m(a, i+1) by sums over ascending b from 0.0, s = sum_a m(a, i)^2 and
+// c = sum_a m(a, i) m(a, i+1) over ascending a from 0.0, separate multiplies and adds.  The thread of i + 1 forms m(a, i+1) again by
+// the same operations.  c(n-1) is not written and never read.
+__global__ __launch_bounds__(256) void k_sqr_rows_exact(const double *H, int l, int n, int r1, const double *X, int ldx, int C, double *S, double *Cs)
+{
+    const long long M = (long long)C * n;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < M; q += (long long)gridDim.x * 256) {
+        const int c = (int)(q / n), i = (int)(q % n);
+        const bool nb = i + 1 < n;
+        const double *x = X + (size_t)c * ldx, *Hi = H + i, *Hj = H + (nb ? i + 1 : i);
+        double s = 0.0, cr = 0.0;
+        for (int a = 0; a < l; a++) {
+            double m = 0.0, mn = 0.0;
+#pragma unroll 4
+            for (int b = 0; b < r1; b++) { const double xb = x[b]; m = m + Hi[(size_t)n * (a + (size_t)l * b)] * xb; mn = mn + Hj[(size_t)n * (a + (size_t)l * b)] * xb; }
+            s = s + m * m;
+            cr = cr + m * mn;
+        }
+        S[q] = s;
+        if (nb) Cs[q] = cr;
+    }
+}
+
+// MFMA: k_sq_rows_mfma's frame and lane maps (ttx_sample_sq.h).  A tile still feeds 16 consecutive indices to the A operand, but
+// the tiles advance by 15, so that every cell has both of its nodes in one tile: tile t holds the indices 15 t .. 15 t + 15 and the
+// cells 15 t .. 15 t + 14.  A lane holds the result rows kq + 4 reg of its column; the accumulator of the next row is, for kq < 3,
+// the same register of lane + 16 and, for kq = 3, the next register of lane - 48.  Both are lane (lane + 16) mod 64: a lane with
+// kq = 0 hands out its next register, every other lane the same one, and one cross-lane move (ds_bpermute, no LDS memory) per
+// register fetches the neighbour.  Products and sums over a stay in registers.  s(i) is stored by the tile whose cell i is (rows 0
+// .. 14) and, for the last index, by the tile that ends there; c(j) by rows 0 .. 14.  Rows >= n load index 0 and are never stored.
+template <int KS>
+__global__ __launch_bounds__(256) void k_sqr_rows_mfma(const double *H, int l, int n, int r1, const double *X, int ldx, int C, int tper, double *S, double *Cs)
+{
+    const int wave = threadIdx.x >> 6, ln = threadIdx.x & 63, col = ln & 15, kq = ln >> 4;
+    const int c0 = 64 * blockIdx.y + 16 * wave;
+    if (c0 >= C) return;
+    const int c = c0 + col;
+    const bool cok = c < C;
+    const double *xp = X + (size_t)(cok ? c : 0) * ldx;
+    double xb[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ks++) { const int b = 4 * ks + kq; xb[ks] = (cok && b < r1) ? xp[b] : 0.0; }
+    const int nt = n > 1 ? (n + 13) / 15 : 1, t1 = min(nt, (int)(blockIdx.x + 1) * tper);
+    const int src = (ln + 16) & 63;
+    const unsigned ln_ = (unsigned)l * (unsigned)n;
+    for (int t = blockIdx.x * tper; t < t1; t++) {
+        const int ia = 15 * t + col;                                            // the index this lane loads for the A operand
+        const double *Hi = H + (ia < n ? ia : 0);
+        dbl4 sq = dbl4{0.0, 0.0, 0.0, 0.0}, cr = dbl4{0.0, 0.0, 0.0, 0.0};
+        for (int a = 0; a < l; a++) {
+            const double *Ha = Hi + (size_t)n * a;
+            dbl4 acc = dbl4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int ks = 0; ks < KS; ks++)
+                if (4 * ks < r1) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ha[(unsigned)(4 * ks + kq) * ln_], xb[ks], acc, 0, 0, 0);
+#pragma unroll
+            for (int reg = 0; reg < 4; reg++) {
+                const double give = (kq == 0 && reg < 3) ? acc[reg < 3 ? reg + 1 : 3] : acc[reg];
+                const double nb = __shfl(give, src);
+                sq[reg] = sq[reg] + acc[reg] * acc[reg];
+                cr[reg] = cr[reg] + acc[reg] * nb;
+            }
+        }
+        if (cok) {
+#pragma unroll
+            for (int reg = 0; reg < 4; reg++) {
+                const int rw = kq + 4 * reg, i = 15 * t + rw;
+                if (i < n && (rw < 15 || i == n - 1)) S[(size_t)c * n + i] = sq[reg];
+                if (rw < 15 && i < n - 1) Cs[(size_t)c * n + i] = cr[reg];
+            }
+        }
+    }
+}
+
+// one mode as k_sqr_pick and k_sqr_step take it.  held != 0: the mode is not drawn; its coordinate xh, its cell and the two hat
+// values were formed on the host (ttx_basis_entry).  noff: where the mode's nodes start in the call's node block
+struct SqrMode { int held, cell; double phi0, phi1, xh; size_t noff; };
+// what a sample carries from one launch to the next: logq, the failure flag, and from k_sqr_pick to k_sqr_step the hat cell and values
+struct SqrState { double *lq, *f0, *f1; int *fail, *ci; };
+
+// the Bernstein coefficients of the density along cell j and the cell's mass: c(j) clamped into [-lim, lim], lim = sqrt(s(j))
+// sqrt(s(j+1)) (Cauchy-Schwarz; a NaN passes through), q0 = s(j) + g, qm = c(j) + g, q1 = s(j+1) + g, A = (((q0 + qm) + q1) / 3) h_j
+__device__ inline double sqr_cell(const double *Sc, const double *Cc, const double *t, double g, int j, double &q0, double &qm, double &q1)
+{
+    const double s0 = Sc[j], s1 = Sc[j + 1], lim = sqrt(s0) * sqrt(s1);
+    double cc = Cc[j];
+    cc = cc > lim ? lim : cc;
+    cc = cc < -lim ? -lim : cc;
+    q0 = s0 + g; qm = cc + g; q1 = s1 + g;
+    return (((q0 + qm) + q1) / 3.0) * (t[j + 1] - t[j]);
+}
+__device__ inline double sqr_mass(const double *Sc, const double *Cc, const double *t, double g, int j, int nc)
+{
+    double q0, qm, q1;
+    return j < nc ? sqr_cell(Sc, Cc, t, g, j, q0, qm, q1) : 0.0;
+}
+
+// One wave per sample, grid-stride, one launch per mode (0-based k), in the frame of k_sq_pick.  A held mode forms nothing: its
+// coordinate goes to x and 0 to cell.  Otherwise the cell masses from the two sheets with lanes along j, the scan, the total, the
+// search and the clamps exactly as in k_sr_draw; a cell's mass is formed again in the search from the same numbers by the same
+// expression.  The hat cell and values of the rounded x_k go to work space, where k_sqr_step finds them.  first also checks the
+// sample's uniforms and clears its state; last writes logq and, for a failed sample, the row of NaN in x and of zeros in cell.
+__global__ __launch_bounds__(256) void k_sqr_pick(int n, int k, int d, SqrMode M, const int *held, const double *nodes, const double *gk, const double *S, const double *Cs,
+                                                  SqrState st, long long npts, const double *u, int first, int last, double *xo, int *cell, double *logq)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const double *t = nodes + M.noff;
+    const int nc = n - 1;
+    for (long long p = (long long)blockIdx.x * nw + wave; p < npts; p += (long long)gridDim.x * nw) {
+        bool fail;
+        double lq = 0.0;
+        if (first) {
+            bool badu = false;
+            for (int i = lane; i < d; i += 64) { const double uu = u[(size_t)p * d + i]; badu |= !held[i] && !(uu >= 0.0); }   // NaN or negative
+            fail = __ballot(badu) != 0;
+        } else { fail = st.fail[p] != 0; lq = st.lq[p]; }
+        int ci = M.cell, cj = -1;
+        double f0 = M.phi0, f1 = M.phi1, xk = M.xh;
+        if (!fail && !M.held) {
+            const double *Sc = S + (size_t)p * n, *Cc = Cs + (size_t)p * n;
+            const double uk = u[(size_t)p * d + k], g = gk[0];
+            double carry = 0.0;
+            int lastc = -1;
+            for (int j0 = 0; j0 < nc; j0 += 64) {                               // the cell masses and their total C(n-2)
+                const double a = sqr_mass(Sc, Cc, t, g, j0 + lane, nc);
+                carry = __shfl(carry + sm_wave_scan(a, lane), 63);
+                const unsigned long long pos = __ballot(a > 0.0);
+                if (pos) lastc = j0 + 63 - __builtin_clzll(pos);
+            }
+            const double total = carry;
+            if (!(total > 0.0) || total == __builtin_inf() || lastc < 0) fail = true;       // 0, NaN or Inf
+            else {
+                const double tt = uk * total;
+                cj = lastc;                                                     // u >= 1, or no cell with tt < C(j): the largest cell with A > 0, lambda = 1
+                double lam = 1.0;
+                if (uk < 1.0) {
+                    carry = 0.0;
+                    for (int j0 = 0; j0 < nc; j0 += 64) {
+                        const int j = j0 + lane;
+                        const double a = sqr_mass(Sc, Cc, t, g, j, nc), c = carry + sm_wave_scan(a, lane);
+                        const unsigned long long hit = __ballot(j < nc && a > 0.0 && tt < c);
+                        if (hit) {
+                            const int fl = __builtin_ctzll(hit);
+                            cj = j0 + fl;
+                            const double cprev = fl ? __shfl(c, fl - 1) : carry, aj = __shfl(a, fl);
+                            double s = tt - cprev;
+                            s = s > 0.0 ? s : 0.0;
+                            s = s < aj ? s : aj;
+                            double q0, qm, q1;
+                            (void)sqr_cell(Sc, Cc, t, g, cj, q0, qm, q1);
+                            lam = sqr_invert(q0, qm, q1, s / (t[cj + 1] - t[cj]));
+                            break;
+                        }
+                        carry = __shfl(c, 63);
+                    }
+                }
+                const double tl = t[cj], tr = t[cj + 1];
+                xk = tl + lam * (tr - tl);
+                xk = xk > tl ? xk : tl;                                         // into the closed cell before the hat row is looked up
+                xk = xk < tr ? xk : tr;
+                ci = cj + ((cj + 1 <= n - 2 && xk >= tr) ? 1 : 0);             // TTX_BASIS_LINEAR's cell of the rounded x: it may be the next one
+                const double t0 = t[ci], t1 = t[ci + 1];
+                f1 = (xk - t0) / (t1 - t0);
+                f0 = 1.0 - f1;
+                const double s0 = Sc[ci], s1 = Sc[ci + 1], lim = sqrt(s0) * sqrt(s1);
+                double cc = Cc[ci];
+                cc = cc > lim ? lim : cc;
+                cc = cc < -lim ? -lim : cc;
+                double dens = (((f0 * f0) * s0 + ((2.0 * f0) * f1) * cc) + (f1 * f1) * s1) + g;
+                dens = dens > 0.0 ? dens : 0.0;
+                lq = lq + log(dens / total);
+            }
+        }
+        if (lane == 0) {
+            st.fail[p] = fail ? 1 : 0; st.lq[p] = lq;
+            if (!fail) {
+                st.ci[p] = ci; st.f0[p] = f0; st.f1[p] = f1;
+                xo[(size_t)p * d + k] = xk;
+                if (cell) cell[(size_t)p * d + k] = cj + 1;
+            }
+            if (last && logq) logq[p] = fail ? __builtin_nan("") : lq;
+        }
+        if (last && fail)
+            for (int i = lane; i < d; i += 64) { xo[(size_t)p * d + i] = __builtin_nan(""); if (cell) cell[(size_t)p * d + i] = 0; }
+    }
+}
+
+// The chain step of mode k, one wave per sample: z = (0.0 + f0 A0 x) + f1 A1 x (sr_chain_step) with the hat cell and values
+// k_sqr_pick left in work space; the cell is range-checked again here where it is read.  A failed sample is skipped.  last writes val.
+__global__ __launch_bounds__(256) void k_sqr_step(const double *G, int RM, size_t SS, int r0, int r1, int n, SqrState st, const double *Xo, double *Xn, int ldx,
+                                                  long long npts, int last, double *val)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    for (long long p = (long long)blockIdx.x * nw + wave; p < npts; p += (long long)gridDim.x * nw) {
+        const bool fail = st.fail[p] != 0;
+        double *z = Xn + (size_t)p * ldx;
+        if (!fail) {
+            int ci = st.ci[p];
+            const int top = n > 2 ? n - 2 : 0;
+            ci = ci < 0 ? 0 : ci > top ? top : ci;
+            sr_chain_step(G + (size_t)RM * ci, (size_t)RM, SS, r0, r1, n > 1, st.f0[p], st.f1[p], Xo + (size_t)p * ldx, z, lane);
+        }
+        if (last && val && lane == 0) val[p] = fail ? 0.0 : z[0];
+    }
+}
+#endif

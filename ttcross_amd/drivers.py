@@ -13,6 +13,7 @@ runs on the GPU through ttcross_amd.engine.  Usage:
     python -m ttcross_amd.drivers compose WORKLOAD OP [MAXRANK] (cross approximation of product | ratio | sqrtabs of the workload's train)
     python -m ttcross_amd.drivers samplereal WORKLOAD NPTS[,NPTS...] (real-valued samples from the interpolant of the workload's train: sample_real)
     python -m ttcross_amd.drivers samplesq WORKLOAD NPTS [MODE] [REPEATS] (samples from the square of the workload's train: sample_sq; WORKLOAD signed: importance weights)
+    python -m ttcross_amd.drivers samplesqreal WORKLOAD NPTS [MODE] [REPEATS] (real-valued samples from the square of the interpolant: sample_sq_real; WORKLOAD signed: importance weights)
 
 devfun: the rational example integrand (examples/devfun/rational.hip) as a LOADED device integrand (TTX_FUN_DEVICE), in its
 wave form, or -- host -- its C twin through the host callback (TTX_FUN_HOST; needs gcc); SOURCE.hip NAME loads another
@@ -1034,6 +1035,75 @@ def run_samplereal(argv, device=0, repeats=5, tt=None, host_npts=1000):
     return out
 
 
+def run_samplesqreal(argv, device=0, repeats=5, tt=None):
+    """samplesqreal WORKLOAD NPTS [MODE] [REPEATS]: the trains of the sample sub-command (or "signed": signed_density_train) on equidistant
+    nodes of [0, 1], seeded uniforms made ON the device; one warm-up and the median of `repeats` calls of sample_sq_real through the
+    device-pointer entry: the call, the head pass, the rows kernels and the picks with the chain steps (HIP events,
+    ttx_sample_sq_real_last), samples per second and the fp64 rate of the rows; sample_sq (weights 1 / n) and sample_real on the same
+    uniforms and train next to it, with the time ratios.  On the signed workload the target is |g| / Z on the box: the largest
+    importance weight |g(x)| / q(x) over its mean and the effective sample size under sample_real() on the train and under
+    sample_sq_real() on the cross approximation of sqrt |T| (of_trains, sqrtabs), with and without a defensive term.  One JSON line each."""
+    import json
+    import time
+    import torch
+    torch.cuda.init()          # a torch that brings its own HIP runtime must initialise its device before the engine's library does
+    workload, npts = argv[0], int(float(argv[1]))
+    mode = argv[2] if len(argv) > 2 else "auto"
+    repeats = int(argv[3]) if len(argv) > 3 else repeats
+    tt = tt or (signed_density_train(device) if workload == "signed" else tijk_train(workload, device=device))
+    dev = torch.device("cuda", device)
+    nodes = [np.linspace(0.0, 1.0, int(nk)) for nk in tt._n]
+    lin = [("linear", t) for t in nodes]
+    w = [np.full(int(nk), 1.0 / int(nk)) for nk in tt._n]
+    g = torch.Generator(device=dev)
+    g.manual_seed(20240607)
+    u = torch.rand((npts, tt.d), dtype=torch.float64, device=dev, generator=g)
+    torch.cuda.synchronize(dev)
+
+    def timed(call, last):
+        call()
+        ms, figs = [], []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            res = call()                          # synchronises before it returns
+            ms.append((time.perf_counter() - t0) * 1e3)
+            figs.append(last())
+        return res, float(np.median(ms)), {k: float(np.median([f[k] for f in figs])) for k in figs[0] if isinstance(figs[0][k], float)}, figs[-1]
+
+    res, call_ms, med, last = timed(lambda: tt.sample_sq_real(u, nodes, mode=mode), tt.sample_sq_real_last)
+    fin = ~torch.isnan(res["x"][:, 0])
+    nb = min(int(fin.sum().item()), 100000)
+    val = tt.basis_batch(res["x"][fin][:nb].contiguous(), lin, "exact")
+    _, q_ms, q_med, q_last = timed(lambda: tt.sample_sq(u, w, mode=mode), tt.sample_sq_last)
+    _, r_ms, r_med, r_last = timed(lambda: tt.sample_real(u, nodes), tt.sample_real_last)
+    rows_ms, q_rows_ms = med["ms_rows"], q_med["ms_rows"]
+    out = [dict(workload=workload, npts=npts, d=tt.d, max_rank=int(tt.ranks().max()), mode_asked=mode, mode=last["mode"], call_ms=call_ms,
+                head_ms=med["ms_head"], rows_ms=rows_ms, pick_ms=med["ms_pick"], samples_per_s=npts / (call_ms * 1e-3), rows_flops=last["flops"],
+                rows_flops_per_s=last["flops"] / (rows_ms * 1e-3) if rows_ms > 0 else None, failed=last["failed"],
+                val_is_basis=bool(torch.all(val == res["val"][fin][:nb]).item()), mean_logq=float(res["logq"][fin].mean().item()),
+                sample_sq_call_ms=q_ms, sample_sq_rows_ms=q_rows_ms, sample_sq_mode=q_last["mode"],
+                sample_sq_rows_flops_per_s=q_last["flops"] / (q_rows_ms * 1e-3) if q_rows_ms > 0 else None,
+                rows_rate_over_sample_sq=(q_rows_ms / rows_ms) if rows_ms > 0 else None, time_ratio_to_sample_sq=call_ms / q_ms if q_ms > 0 else None,
+                sample_real_call_ms=r_ms, sample_real_draw_ms=r_med["ms_draw"], time_ratio_to_sample_real=call_ms / r_ms if r_ms > 0 else None)]
+    print(json.dumps(out[0]), flush=True)
+    if workload == "signed":
+        def spread(x, logq):
+            ok = torch.isfinite(logq)
+            iw = torch.abs(tt.basis_batch(x[ok].contiguous(), lin, "exact")) / torch.exp(logq[ok])
+            return float((iw.max() / iw.mean()).item()), float((iw.sum() ** 2 / (iw * iw).sum() / iw.numel()).item())
+        plain = tt.sample_real(u, nodes)
+        root = TTCross.of_trains([tt], "sqrtabs", 12, accuracy=500 * EPS, pivoting=2, quad=w, device=device).run()
+        r = dict(workload=workload, npts=npts, root_max_rank=int(root.ranks().max()))
+        r["sample_real_max_over_mean"], r["sample_real_ess_fraction"] = spread(plain["x"], plain["logq"])
+        for gam in (0.0, 1e-6):
+            sq = root.sample_sq_real(u, nodes, gamma=gam, mode=mode)
+            key = "sample_sq_real" if gam == 0.0 else "sample_sq_real_gamma_%g" % gam
+            r[key + "_max_over_mean"], r[key + "_ess_fraction"] = spread(sq["x"], sq["logq"])
+        print(json.dumps(r), flush=True)
+        out.append(r)
+    return out
+
+
 def topk_train(workload, device=0):
     """The train of a topk run: a train of the tijk sub-command, or d64diff: the difference lincomb([1, -1], [exact, fast]) of the
     D_64 result trains in the two arithmetics, whose largest element is the max-norm error of the fast arithmetic; NAME+ort: the
@@ -1192,6 +1262,8 @@ if __name__ == "__main__":
         run_samplereal(sys.argv[2:])
     elif sys.argv[1] == "samplesq":
         run_samplesq(sys.argv[2:])
+    elif sys.argv[1] == "samplesqreal":
+        run_samplesqreal(sys.argv[2:])
     elif sys.argv[1] == "topk":
         run_topk(sys.argv[2:])
     elif sys.argv[1] == "contract":

@@ -138,6 +138,10 @@ def load_library():
                                 POINTER(c_double)]
     L.ttx_sample_sq_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(c_double), POINTER(c_int32), c_double, c_int32, c_void_p, c_void_p, c_void_p]
     L.ttx_sample_sq_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64), POINTER(c_int32)]
+    L.ttx_sample_sq_real.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(POINTER(c_double)), POINTER(c_double), c_double, c_int32, POINTER(c_double),
+                                     POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
+    L.ttx_sample_sq_real_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(POINTER(c_double)), POINTER(c_double), c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.ttx_sample_sq_real_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64), POINTER(c_int32)]
     L.ttx_topk.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_int32), c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
     L.ttx_topk_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
     L.ttx_zquad.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
@@ -264,6 +268,33 @@ def trapezoid_weights(nodes):
     om[0], om[-1] = 0.5 * (t[1] - t[0]), 0.5 * (t[-1] - t[-2])
     om[1:-1] = 0.5 * (t[2:] - t[:-2])
     return om
+
+
+def mass_cholesky(nodes):
+    """The upper bidiagonal Cholesky factor (dg, sp) of the hat functions' mass matrix on strictly ascending nodes, the factor
+    sample_sq_real gives a drawn mode (include/ttx.h: ttx_sample_sq_real): M = U^T U with U[i, i] = dg[i], U[i, i+1] = sp[i],
+    M[i, i] = (h[i-1] + h[i]) / 3 with one term at each end, M[i, i+1] = h[i] / 6.  Plain float64, one operation at a time: the
+    engine's host code forms the same bits.  A single node gives ([1.], [0.]).  One array of nodes gives one pair, a list of arrays
+    a list of pairs."""
+    if isinstance(nodes, (list, tuple)) and len(nodes) and np.ndim(nodes[0]) == 1:
+        return [mass_cholesky(t) for t in nodes]
+    t = np.ascontiguousarray(nodes, dtype=np.float64)
+    if t.ndim != 1 or t.size < 1:
+        raise ValueError("mass_cholesky: a one-dimensional array of nodes expected")
+    n = t.size
+    if n == 1:
+        return np.ones(1), np.zeros(1)
+    h = t[1:] - t[:-1]
+    diag = np.empty(n)
+    diag[0], diag[-1] = h[0] / 3.0, h[-1] / 3.0
+    diag[1:-1] = (h[:-1] + h[1:]) / 3.0
+    off = h / 6.0
+    dg, sp = np.zeros(n), np.zeros(n)
+    dg[0] = np.sqrt(diag[0])
+    for i in range(n - 1):
+        sp[i] = off[i] / dg[i]
+        dg[i + 1] = np.sqrt(diag[i + 1] - sp[i] * sp[i])
+    return dg, sp
 
 
 def roundsum_omega(seed, k, shape):
@@ -1135,6 +1166,72 @@ class TTCross:
         a, b, c, n = c_double(), c_double(), c_double(), c_int64()
         _check(load_library().ttx_sample_real_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(n)))
         return dict(ms_head=a.value, bytes_head=b.value, ms_draw=c.value, failed=int(n.value))
+
+    # ---- real-valued samples from the square of the interpolant (include/ttx.h: ttx_sample_sq_real) -------
+    def sample_sq_real(self, u_or_npts, nodes, cond=None, gamma=0.0, mode="auto", seed=None, want=("x", "cell", "logq", "val")):
+        """Real points drawn from the SQUARE of the piecewise-multilinear interpolant g of the train of grid values, on the device
+        (include/ttx.h: ttx_sample_sq_real): for any train, signed or not, they follow (g(x)^2 + gamma) / (Z + gamma V) over the
+        drawn modes, Z the integral of g^2 and V the volume of the drawn modes' box.  The train is meant to approximate the square
+        root of a density (of_trains with a sqrt-abs combiner builds it).  u_or_npts, nodes, cond, seed, want and the returned dict
+        are sample_real()'s: val is basis_batch(x, ("linear", nodes), "exact"), and exp(logq) (Z + gamma V) = val^2 + gamma.
+        gamma >= 0 is the defensive term; mode is "exact", "mfma" or "auto" (only the sums of the rows depend on it).
+        sample_sq_real_last() counts the failed samples.  A contiguous float64 torch tensor on the engine's device is passed by
+        pointer (ttx_sample_sq_real_dev) and gives torch tensors on that device."""
+        L, names = load_library(), ("x", "cell", "logq", "val")
+        bad = set(want) - set(names)
+        if bad:
+            raise ValueError(f"sample_sq_real: unknown output {sorted(bad)}")
+        md = _eval_mode(mode)
+        rows, rowp = self._node_rows(nodes, "sample_sq_real")
+        ca = None
+        if cond is not None:
+            ca = np.ascontiguousarray(cond, dtype=np.float64).ravel()
+            if ca.size != self.d:
+                raise ValueError(f"sample_sq_real: {self.d} cond entries expected")
+        if type(u_or_npts).__module__.split(".")[0] == "torch":
+            import torch
+            u = u_or_npts
+            if not u.is_cuda:
+                return {k: torch.from_numpy(v) for k, v in self.sample_sq_real(u.numpy(), nodes, cond, gamma, mode, seed, want).items()}
+            if u.device.index != self.device:
+                raise ValueError(f"sample_sq_real: the tensor lies on {u.device}, the engine on device {self.device}")
+            if u.dtype != torch.float64 or not u.is_contiguous() or u.dim() != 2 or u.shape[1] != self.d:
+                raise ValueError(f"sample_sq_real: a contiguous float64 tensor of shape (npts, {self.d}) expected")
+            npts = u.shape[0]
+            x = torch.empty((npts, self.d), dtype=torch.float64, device=u.device)
+            ce = torch.empty((npts, self.d), dtype=torch.int32, device=u.device) if "cell" in want else None
+            lq = torch.empty(npts, dtype=torch.float64, device=u.device) if "logq" in want else None
+            va = torch.empty(npts, dtype=torch.float64, device=u.device) if "val" in want else None
+            torch.cuda.current_stream(u.device).synchronize()        # the engine runs on a stream of its own
+            _check(L.ttx_sample_sq_real_dev(self._h, npts, c_void_p(u.data_ptr()), rowp, _dp(ca), float(gamma), md, c_void_p(x.data_ptr()), *[
+                c_void_p(t.data_ptr()) if t is not None else None for t in (ce, lq, va)]))
+            out = dict(x=x, cell=ce, logq=lq, val=va)
+            return {k: out[k] for k in names if k in want}
+        if np.ndim(u_or_npts) == 0:
+            npts = int(u_or_npts)
+            if npts < 0:
+                raise ValueError("sample_sq_real: a negative count")
+            u = np.random.default_rng(seed).random((npts, self.d))
+        else:
+            u = np.ascontiguousarray(u_or_npts, dtype=np.float64)
+            if u.ndim != 2 or u.shape[1] != self.d:
+                raise ValueError(f"sample_sq_real: an array of shape (npts, {self.d}) expected")
+        npts = u.shape[0]
+        x = np.zeros((npts, self.d))
+        ce = np.zeros((npts, self.d), dtype=np.int32) if "cell" in want else None
+        lq = np.zeros(npts) if "logq" in want else None
+        va = np.zeros(npts) if "val" in want else None
+        _check(L.ttx_sample_sq_real(self._h, npts, _dp(u), rowp, _dp(ca), float(gamma), md, _dp(x), _ip(ce), _dp(lq), _dp(va)))
+        out = dict(x=x, cell=ce, logq=lq, val=va)
+        return {k: out[k] for k in names if k in want}
+
+    def sample_sq_real_last(self):
+        """dict(ms_head, ms_rows, ms_pick, flops, failed, mode) of the last sample_sq_real() on this engine (include/ttx.h:
+        ttx_sample_sq_real_last); mode is "exact" or "mfma" (None before the first call)"""
+        a, b, c, fl, n, md = c_double(), c_double(), c_double(), c_double(), c_int64(), c_int32()
+        _check(load_library().ttx_sample_sq_real_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(fl), ctypes.byref(n), ctypes.byref(md)))
+        names = {v: k for k, v in EVAL_MODES.items()}
+        return dict(ms_head=a.value, ms_rows=b.value, ms_pick=c.value, flops=fl.value, failed=int(n.value), mode=names.get(md.value))
 
     # ---- the largest elements of the resident train (include/ttx.h: ttx_topk) ----------------------------
     def topk(self, k, which="abs", fixed=None, mode="auto"):
