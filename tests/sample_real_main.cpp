@@ -1,4 +1,4 @@
-// Stand-alone host program for the host-callable part of ttcross_amd/csrc/ttx_sample_real.h: sr_invert, sr_trapezoid, sr_hat_cell.
+// Stand-alone host program for the host-callable part of ttcross_amd/csrc/ttx_sample_real.h: sr_invert, sr_trapezoid, sr_hat_cell, sr_held_mode.
 // Prints "bad ninvert nchecks" on its last line; bad = 0 when every check held.
 #include <cmath>
 #include <cstdint>
@@ -80,6 +80,26 @@ int main()
     double one = 3.25, w1 = 0.0;
     sr_trapezoid(&one, 1, &w1);
     CHECK(w1 == 1.0 && sr_hat_cell(&one, 1, 7.0) == 0 && sr_hat_cell(&one, 1, nan) == 0, "a mode of one node");
+    // the record of a held mode: sr_hat_cell's cell and ttx_basis_entry's two hat values there, every other entry of the row 0 and the row summing to 1;
+    // a coordinate below the first node, above the last, on a node (an inner one, the first, the last), inside a cell
+    for (int n : {2, 3, 17, 66}) {
+        std::vector<double> t(n);
+        double x = -2.25;
+        for (int i = 0; i < n; i++) { x += 0.01 + rnd(); t[i] = x; }
+        for (double q : {t[0] - 1.0, -1e300, t[n - 1] + 0.5, 1e300, t[n / 2], t[0], t[n - 1], 0.25 * t[n / 2 - 1] + 0.75 * t[n / 2], std::nextafter(t[n - 1], -inf)}) {
+            const SrMode M = sr_held_mode(t.data(), n, q, 40 + (size_t)n);
+            CHECK(M.held == 1 && M.xh == q && M.noff == 40 + (size_t)n, "held mode of %d nodes at %.17g: held %d xh %.17g noff %zu", n, q, M.held, M.xh, M.noff);
+            CHECK(M.cell == sr_hat_cell(t.data(), n, q) && M.cell >= 0 && M.cell <= n - 2, "held mode of %d nodes at %.17g: cell %d", n, q, M.cell);
+            CHECK(M.phi0 == ttx_basis_entry(2, 0, 0.0, 0.0, t.data(), n, q, M.cell) && M.phi1 == ttx_basis_entry(2, 0, 0.0, 0.0, t.data(), n, q, M.cell + 1),
+                  "held mode of %d nodes at %.17g: hat values %.17g %.17g", n, q, M.phi0, M.phi1);
+            for (int j = 0; j < n; j++)
+                if (j != M.cell && j != M.cell + 1) CHECK(ttx_basis_entry(2, 0, 0.0, 0.0, t.data(), n, q, j) == 0.0, "held mode of %d nodes at %.17g: entry %d outside the cell", n, q, j);
+            CHECK(M.phi0 >= 0.0 && M.phi1 >= 0.0 && fabs(M.phi0 + M.phi1 - 1.0) <= 0x1.0p-52, "held mode of %d nodes at %.17g: %.17g + %.17g", n, q, M.phi0, M.phi1);
+        }
+    }
+    const SrMode M1 = sr_held_mode(&one, 1, 7.0, 3);
+    CHECK(M1.held == 1 && M1.cell == 0 && M1.phi0 == 1.0 && M1.phi1 == 0.0 && M1.xh == 7.0 && M1.noff == 3, "the held record of a mode of one node");
+    CHECK(M1.phi0 == ttx_basis_entry(2, 0, 0.0, 0.0, &one, 1, 7.0, 0), "a mode of one node: the entry");
     printf("%d %d %d\n", bad, ninv, nchk);
     return bad != 0;
 }

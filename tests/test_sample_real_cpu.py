@@ -170,3 +170,37 @@ def test_inversion_and_weights_under_address_and_undefined_sanitizers(tmp_path):
     exe = _build(tmp_path, "sample_real_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
     _check(subprocess.run([str(exe)], capture_output=True, text=True, env=env))
+
+
+@pytest.mark.parametrize("method, entry, extra", [("sample_real", "ttx_sample_real", ()), ("sample_sq_real", "ttx_sample_sq_real", (0.125, "exact"))])
+def test_node_rows_made_for_the_call_live_through_it(monkeypatch, method, entry, extra):
+    """Nodes given as lists (or float32, or a strided view) become new float64 arrays whose addresses go to the C entry in a ctypes
+    pointer array, and a ctypes array holds addresses only.  The entry, a stand-in here, must find every such array alive and its
+    numbers in place; once the call is over they are released."""
+    import gc
+    import types
+    import weakref
+    nodes = [[0.0, 0.25, 1.0], np.array([0.0, 2.0], dtype=np.float32), np.linspace(0.0, 3.0, 7)[::2]]
+    refs, seen = [], []
+    rows_of = E.TTCross._node_rows
+
+    def spy(self, nd, who):
+        rows, rowp = rows_of(self, nd, who)
+        refs.extend(weakref.ref(r) for r in rows)
+        return rows, rowp
+
+    def stand_in(h, npts, u, rowp, cond, *rest):
+        gc.collect()
+        seen.append([r() is not None for r in refs])
+        seen.append([[rowp[k][j] for j in range(len(nodes[k]))] for k in range(3)])
+        return 0
+
+    monkeypatch.setattr(E.TTCross, "_node_rows", spy)
+    monkeypatch.setattr(E, "load_library", lambda: types.SimpleNamespace(**{entry: stand_in, entry + "_dev": stand_in}))
+    tt = object.__new__(E.TTCross)
+    tt.d, tt._n, tt._h = 3, [3, 2, 4], None
+    out = getattr(tt, method)(np.full((2, 3), 0.5), nodes, None, *extra)
+    assert seen[0] == [True] * 3 and seen[1] == [[0.0, 0.25, 1.0], [0.0, 2.0], [0.0, 1.0, 2.0, 3.0]]
+    assert sorted(out) == ["cell", "logq", "val", "x"] and out["x"].shape == (2, 3)
+    gc.collect()
+    assert [r() for r in refs] == [None] * 3

@@ -140,7 +140,7 @@ enum {
     SC_KREC, SC_KSEL, SC_KOUT,          // ttx_topk: the kept positions of every mode, the selection's state (words, chunk counts, histogram), the rows before and after the ordering
     SC_RSO, SC_RSW, SC_RSYA, SC_RSYB,   // ttx_lincomb_round: the sketch train Omega, the stacked W of all bonds, the two Y buffers
     SC_RSM, SC_RSTAB,                   // ttx_lincomb_round: M = Q^T Y (first the coefficients), the descriptor tables (RsBlk) and Omega's offsets
-    SC_QH, SC_QF, SC_QS, SC_QX,         // ttx_sample_sq: the tables H_k, the factors F_k (then the exponent and the d defensive terms), a mode's sheet, the states (two buffers, logq, flags)
+    SC_QH, SC_QF, SC_QS, SC_QX,         // ttx_sample_sq: the tables H_k, the factors F_k (then the exponent and the d defensive terms), a mode's sheet (two for ttx_sample_sq_real), the states (two buffers, logq, flags)
     SC_BTAB,                            // ttx_basis_batch: the table of one mode for one chunk, chunk x max n (its states go to SC_XA / SC_XB, its nodes to SC_META)
     SC_NBUF
 };
@@ -155,6 +155,11 @@ struct OpTimer {
 enum { TM_MODESUM, TM_ALG, TM_HEAD, TM_DRAW, TM_APPLY,             // k_ct_modesum, the algebra launch, k_sm_head, the k_sm_draw / k_sr_draw of a chunk, k_ma_apply
        TM_GRAM, TM_SCORE, TM_SELECT,                               // ttx_topk: the Gram chain, a mode's scoring launch, a mode's selection and advance
        TM_RS_SKETCH, TM_N };                                       // ttx_lincomb_round: the right-to-left pass (the GEMMs, QRs and advances alternate d - 1 times: RsMarks on ttx_engine::rs_ev)
+
+// the figures of a sampler's last call: ttx_sample and ttx_sample_real fill head, bytes and draw, the squared samplers head, rows, pick,
+// flops and mode
+enum { SMP_GRID, SMP_REAL, SMP_SQ, SMP_SQ_REAL, SMP_N };
+struct SampleLast { double ms_head = 0.0, bytes = 0.0, ms_draw = 0.0, ms_rows = 0.0, ms_pick = 0.0, flops = 0.0; int64_t failed = 0; int mode = -1; };
 
 struct DevFun;                          // a loaded device integrand (TTX_FUN_DEVICE), defined with slot_eval
 struct TrainFun;                        // the operands and the combiner of TTX_FUN_TRAINS, defined with slot_eval
@@ -251,20 +256,11 @@ struct ttx_engine {
     int ev_last_mode = -1;              // TTX_EVAL_* the last batch ran with
     double ct_ms = 0.0, ct_bytes = 0.0;                 // the mode-sum kernel of the last ttx_contract / ttx_marginals
     double alg_ms = 0.0, alg_rd = 0.0, alg_wr = 0.0;    // the last ttx_lincomb / ttx_hadamard with this engine first
-    double sm_ms_head = 0.0, sm_bytes = 0.0, sm_ms_draw = 0.0;  // the last ttx_sample
-    int64_t sm_failed = 0;
-    double sr_ms_head = 0.0, sr_bytes = 0.0, sr_ms_draw = 0.0;  // the last ttx_sample_real
-    int64_t sr_failed = 0;
+    SampleLast smp[SMP_N];                              // the last call of each of the four samplers, each its own
     double ma_ms = 0.0, ma_rd = 0.0, ma_wr = 0.0, ma_flops = 0.0;   // the apply launch of the last ttx_mode_apply
     int ma_mode = -1;
     double tk_ms_gram = 0.0, tk_ms_score = 0.0, tk_ms_select = 0.0, tk_flops = 0.0;   // the last ttx_topk
     int tk_mode = -1;
-    double sq_ms_head = 0.0, sq_ms_rows = 0.0, sq_ms_pick = 0.0, sq_flops = 0.0;      // the last ttx_sample_sq
-    int64_t sq_failed = 0;
-    int sq_mode = -1;
-    double sqr_ms_head = 0.0, sqr_ms_rows = 0.0, sqr_ms_pick = 0.0, sqr_flops = 0.0;  // the last ttx_sample_sq_real
-    int64_t sqr_failed = 0;
-    int sqr_mode = -1;
     double rs_ms[4] = {0.0, 0.0, 0.0, 0.0}, rs_flops = 0.0;                    // the last ttx_lincomb_round with this engine first: sketch, gemm, qr, advance
     std::vector<int32_t> rs_l;                                                  // its sketch ranks l(0 .. d)
     int rs_mode = -1;
@@ -3164,9 +3160,12 @@ extern "C" int ttx_contract_modesum(const ttx_engine *h, double *ms, double *byt
 // ---- samples from the resident train (ttx_sample.h, ttx_sample_real.h) -----------------------------------------------------------
 // What ttx_sample and ttx_sample_real share.  sm_prepare: the plan, the call's tables, the prefix vectors from the effective weights
 // (ct_modesum untimed, k_ct_chains), the head tables of the drawn modes (k_sm_head between TM_HEAD's events) and the shape of the draw
-// launches.  sm_chunks: the chunk loop with the staging of the host entry, the draw between TM_DRAW's events, the failure count.
+// launches.  sm_chunks: the chunk loop with the staging of the host entry, the draw between TM_DRAW's events, the failure count; the squared
+// samplers (sq_frame) run their per-mode launches inside it.  The argument checks the four samplers share come first.
 namespace {
+struct SmLoop { size_t chunk = 0; int gridmax = 0; long long *dcnt = nullptr; };   // what sm_chunks needs: the chunk, the cap of a draw's grid, the failure counter (SC_CNT)
 struct SmPrep {                             // what sm_prepare leaves for the chunk loop and the draw launches: outputs only
+    SmLoop loop;
     EvTrain T;
     std::vector<size_t> hoff;               // where the head table of a drawn mode starts in SC_H
     std::vector<SmTile> tiles;
@@ -3176,11 +3175,49 @@ struct SmPrep {                             // what sm_prepare leaves for the ch
     char *dm = nullptr;                     // the call's tables on the device (SC_META)
     size_t o_hoff = 0;
     double *H = nullptr, *grow = nullptr;
-    long long *dcnt = nullptr;
-    size_t chunk = 0, growlen = 0, lds = 0;
-    int gridmax = 0, ldsrow = 0;
+    size_t growlen = 0, lds = 0;
+    int ldsrow = 0;
 };
 struct SmStage { void *user; size_t bytes; int slot; void *dev; };    // an output: the caller's array (may be null), bytes per sample, its staging slot; dev: where the chunk's part lies
+}
+// fixed of ttx_sample and ttx_sample_sq (may be null): 0 for a drawn mode, or the 1-based index a mode is held at
+static int sm_check_fixed(const ttx_engine *h, const char *who, const int32_t *fixed)
+{
+    if (fixed) for (int k = 0; k < h->d; k++) if (fixed[k] < 0 || fixed[k] > h->n1[k + 1]) return fail(TTX_EINVAL, "%s: fixed(%d) = %d (0 .. %d expected)", who, k + 1, fixed[k], h->n1[k + 1]);
+    return TTX_OK;
+}
+// nodes (may be null with npts = 0) and cond (may be null) of the real samplers
+static int bs_check_one(const char *who, int k, const ttx_basis &b, int n);     // the node rows are TTX_BASIS_LINEAR's: one check (below, with ttx_basis_batch)
+static int sr_check_nodes_cond(const ttx_engine *h, const char *who, const double *const *nodes, const double *cond)
+{
+    int rc;
+    const int d = h->d;
+    if (nodes) {
+        for (int k = 0; k < d; k++) {
+            ttx_basis b{TTX_BASIS_LINEAR, 0, 0.0, 0.0, nodes[k]};
+            if ((rc = bs_check_one(who, k + 1, b, h->n1[k + 1]))) return rc;
+        }
+    }
+    if (cond) for (int k = 0; k < d; k++) if (std::isinf(cond[k])) return fail(TTX_EINVAL, "%s: cond(%d) is infinite (a coordinate, or NaN for a drawn mode, expected)", who, k + 1);
+    return TTX_OK;
+}
+// mode and gamma of the squared samplers
+static int sq_check_mode_gamma(const char *who, int32_t mode, double gamma)
+{
+    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    if (!(gamma >= 0.0) || !std::isfinite(gamma)) return fail(TTX_EINVAL, "%s: gamma must be a finite number >= 0 (got %g)", who, gamma);
+    return TTX_OK;
+}
+// the chunk of a call of npts >= 1 samples (TTX_SAMPLE_CHUNK, 2^18 by default); asks the device nothing
+static size_t sm_chunk(int64_t npts) { return std::min<size_t>(env_chunk("TTX_SAMPLE_CHUNK", (size_t)1 << 18), (size_t)npts); }
+// That chunk and the cap of the grid of a draw: one wave per sample, 4 waves per workgroup, 8 workgroups per CU as k_ev_exact's.  dcnt
+// stays with the caller, who reserves SC_CNT
+static SmLoop sm_loop(ttx_engine *h, int64_t npts)
+{
+    SmLoop L;
+    L.chunk = sm_chunk(npts);
+    L.gridmax = (int)std::min<long long>(((long long)L.chunk + 3) / 4, (long long)dev_ncu(h) * 8);
+    return L;
 }
 // Inputs: pl, the caller's plan of all modes (ct_plan); held[k] != 0: mode k gets no head table; eff: the effective weights of all modes
 // (pl.wsize numbers); hw_ones: k_sm_head multiplies by 1.0 (a block of ones in the call's tables), not by eff; draw_kernel and wave_extra:
@@ -3215,32 +3252,30 @@ static int sm_prepare(ttx_engine *h, const char *who, int64_t npts, const CtPlan
         (rc = ct_modesum(h, pl, eff.data(), (const CtCore *)(P.dm + o_cores), (const CtTile *)(P.dm + o_tiles), nullptr))) return rc;   // untimed: ttx_contract_modesum keeps its own last call
     double *L = buf<double>(h, SC_VEC), *S = L + (size_t)d * ldv;
     P.H = buf<double>(h, SC_H);
-    P.dcnt = buf<long long>(h, SC_CNT);
+    P.loop = sm_loop(h, npts);
+    P.loop.dcnt = buf<long long>(h, SC_CNT);
     OpTimer &t_head = h->timer[TM_HEAD];
     hipLaunchKernelGGL(k_ct_chains, dim3(2), dim3(1024), 0, h->stream, d, (const int *)(P.dm + o_r), (const size_t *)(P.dm + o_moff), (const double *)buf<double>(h, SC_M), L, S, ldv);
-    HIPCHECK(hipMemsetAsync(P.dcnt, 0, sizeof(long long), h->stream));
+    HIPCHECK(hipMemsetAsync(P.loop.dcnt, 0, sizeof(long long), h->stream));
     if (!P.tiles.empty()) {
         if ((rc = t_head.start(h->stream))) return rc;
         hipLaunchKernelGGL(k_sm_head, dim3((unsigned)P.tiles.size()), dim3(256), 0, h->stream, (const CtCore *)(P.dm + o_cores), (const SmTile *)(P.dm + o_sm), h->RM, h->P.SS,
                            hw_ones ? (const double *)(P.dm + o_ones) : (const double *)buf<double>(h, SC_W), (const double *)L, ldv, (const size_t *)(P.dm + P.o_hoff), P.H);
         if ((rc = t_head.stop(h->stream))) return rc;
     }
-    // the draw: one wave per sample, 4 waves per workgroup, the grid capped at 8 workgroups per CU as k_ev_exact's
-    P.chunk = std::min<size_t>(env_chunk("TTX_SAMPLE_CHUNK", (size_t)1 << 18), (size_t)npts);
-    P.gridmax = (int)std::min<long long>(((long long)P.chunk + 3) / 4, (long long)dev_ncu(h) * 8);
     P.ldsrow = std::min(P.nrow, TTX_SM_LDSROW);
     P.growlen = P.nrow > TTX_SM_LDSROW ? (size_t)P.nrow : 0;
     P.lds = 4 * sizeof(double) * (2 * (size_t)P.T.ldx + wave_extra + P.ldsrow);
     if (P.lds > TTX_LDS_DEVICE) return fail(TTX_EINVAL, "%s: %d modes need %zu bytes of LDS per workgroup (160 KB at most)", who, d, P.lds);
     if (P.lds > 64 * 1024 && (rc = ensure_lds(h, draw_kernel, P.lds))) return rc;
-    if (P.growlen && (rc = buf_reserve(h, SC_ROW, sizeof(double) * P.growlen * 4 * P.gridmax))) return rc;
+    if (P.growlen && (rc = buf_reserve(h, SC_ROW, sizeof(double) * P.growlen * 4 * P.loop.gridmax))) return rc;
     P.grow = P.growlen ? buf<double>(h, SC_ROW) : nullptr;
     return TTX_OK;
 }
 // draw(c, grid, du): the draw launch of a chunk of c samples whose uniforms lie at du; count(c): the launch that adds its failed samples to
-// P.dcnt.  Both find the chunk's outputs in out[.].dev (null for an output the caller did not ask for).  *ms_draw, *nfailed: the call's figures
+// P.dcnt (P: sm_loop's figures and the counter).  Both find the chunk's outputs in out[.].dev (null for an output the caller did not ask for).  *ms_draw, *nfailed: the call's figures
 template <class Draw, class Count>
-static int sm_chunks(ttx_engine *h, const SmPrep &P, int64_t npts, const double *u, bool dev, SmStage *out, int nout, Draw draw, Count count, double *ms_draw, int64_t *nfailed)
+static int sm_chunks(ttx_engine *h, const SmLoop &P, int64_t npts, const double *u, bool dev, SmStage *out, int nout, Draw draw, Count count, double *ms_draw, int64_t *nfailed)
 {
     int rc;
     const int d = h->d;
@@ -3277,6 +3312,17 @@ static int sm_chunks(ttx_engine *h, const SmPrep &P, int64_t npts, const double 
     *nfailed = nf;
     return TTX_OK;
 }
+// the last-call figures of ttx_sample and ttx_sample_real (which) as their _last entries hand them out; any pointer may be null
+static int sm_last(const ttx_engine *h, const char *who, int which, double *ms_head, double *bytes_head, double *ms_draw, int64_t *nfailed)
+{
+    if (!h) return fail(TTX_EINVAL, "%s: null engine", who);
+    const SampleLast &L = h->smp[which];
+    if (ms_head) *ms_head = L.ms_head;
+    if (bytes_head) *bytes_head = L.bytes;
+    if (ms_draw) *ms_draw = L.ms_draw;
+    if (nfailed) *nfailed = L.failed;
+    return TTX_OK;
+}
 // both entries: u, ind, logq, val are host pointers (dev false: staged chunk by chunk) or pointers on the engine's device
 static int sm_run(ttx_engine *h, const char *who, int64_t npts, const double *u, const double *w, const int32_t *fixed, int32_t *ind, double *logq, double *val, bool dev)
 {
@@ -3284,8 +3330,9 @@ static int sm_run(ttx_engine *h, const char *who, int64_t npts, const double *u,
     int rc = check_train_one_process(h, who);
     if (rc) return rc;
     const int d = h->d;
-    if (fixed) for (int k = 0; k < d; k++) if (fixed[k] < 0 || fixed[k] > h->n1[k + 1]) return fail(TTX_EINVAL, "%s: fixed(%d) = %d (0 .. %d expected)", who, k + 1, fixed[k], h->n1[k + 1]);
-    h->sm_ms_head = h->sm_ms_draw = h->sm_bytes = 0.0; h->sm_failed = 0;
+    if ((rc = sm_check_fixed(h, who, fixed))) return rc;
+    SampleLast &last = h->smp[SMP_GRID];
+    last = SampleLast();
     if (npts == 0) return TTX_OK;
     // the effective weights: a fixed mode has the unit vector of its index
     SmPrep P;
@@ -3304,17 +3351,17 @@ static int sm_run(ttx_engine *h, const char *who, int64_t npts, const double *u,
     size_t o_fx = 0;
     if ((rc = sm_prepare(h, who, npts, pl, held, eff, false, reinterpret_cast<const void *>(k_sm_draw), (size_t)d + (((size_t)d + 1) >> 1),
                          [&](OpMeta &meta) { o_fx = meta.put(fx); }, P))) return rc;
-    h->sm_bytes = P.bytes;
+    last.bytes = P.bytes;
     SmStage out[3] = {{ind, sizeof(int) * (size_t)d, SC_IND, nullptr}, {logq, sizeof(double), SC_LQ, nullptr}, {val, sizeof(double), SC_OUT, nullptr}};
-    rc = sm_chunks(h, P, npts, u, dev, out, 3,
+    rc = sm_chunks(h, P.loop, npts, u, dev, out, 3,
         [&](size_t c, int grid, const double *du) {
             hipLaunchKernelGGL(k_sm_draw, dim3(grid), dim3(256), P.lds, h->stream, P.T, (const size_t *)(P.dm + P.o_hoff), (const int *)(P.dm + o_fx), (const double *)P.H, P.ldsrow,
                                P.grow, P.growlen, (long long)c, du, (int *)out[0].dev, (double *)out[1].dev, (double *)out[2].dev);
         },
-        [&](size_t c) { hipLaunchKernelGGL(k_sm_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const int *)out[0].dev, P.dcnt); },
-        &h->sm_ms_draw, &h->sm_failed);
+        [&](size_t c) { hipLaunchKernelGGL(k_sm_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const int *)out[0].dev, P.loop.dcnt); },
+        &last.ms_draw, &last.failed);
     if (rc) return rc;
-    return P.tiles.empty() ? TTX_OK : h->timer[TM_HEAD].ms(&h->sm_ms_head);
+    return P.tiles.empty() ? TTX_OK : h->timer[TM_HEAD].ms(&last.ms_head);
 }
 extern "C" int ttx_sample(ttx_engine *h, int64_t npts, const double *u, const double *w, const int32_t *fixed, int32_t *ind, double *logq, double *val)
 {
@@ -3326,18 +3373,12 @@ extern "C" int ttx_sample_dev(ttx_engine *h, int64_t npts, const double *u, cons
 }
 extern "C" int ttx_sample_last(const ttx_engine *h, double *ms_head, double *bytes_head, double *ms_draw, int64_t *nfailed)
 {
-    if (!h) return fail(TTX_EINVAL, "ttx_sample_last: null engine");
-    if (ms_head) *ms_head = h->sm_ms_head;
-    if (bytes_head) *bytes_head = h->sm_bytes;
-    if (ms_draw) *ms_draw = h->sm_ms_draw;
-    if (nfailed) *nfailed = h->sm_failed;
-    return TTX_OK;
+    return sm_last(h, "ttx_sample_last", SMP_GRID, ms_head, bytes_head, ms_draw, nfailed);
 }
 
 
 // ---- real-valued samples from the interpolant of the resident train (ttx_sample_real.h) ------------------------------------------
 // both entries: u, x, cell, logq, val are host pointers (dev false: staged chunk by chunk) or pointers on the engine's device
-static int bs_check_one(const char *who, int k, const ttx_basis &b, int n);     // the node rows are TTX_BASIS_LINEAR's: one check (below, with ttx_basis_batch)
 static int sr_run(ttx_engine *h, const char *who, int64_t npts, const double *u, const double *const *nodes, const double *cond, double *x, int32_t *cell, double *logq,
                   double *val, bool dev)
 {
@@ -3345,14 +3386,9 @@ static int sr_run(ttx_engine *h, const char *who, int64_t npts, const double *u,
     int rc = check_train_one_process(h, who);
     if (rc) return rc;
     const int d = h->d;
-    if (nodes) {
-        for (int k = 0; k < d; k++) {
-            ttx_basis b{TTX_BASIS_LINEAR, 0, 0.0, 0.0, nodes[k]};
-            if ((rc = bs_check_one(who, k + 1, b, h->n1[k + 1]))) return rc;
-        }
-    }
-    if (cond) for (int k = 0; k < d; k++) if (std::isinf(cond[k])) return fail(TTX_EINVAL, "%s: cond(%d) is infinite (a coordinate, or NaN for a drawn mode, expected)", who, k + 1);
-    h->sr_ms_head = h->sr_ms_draw = h->sr_bytes = 0.0; h->sr_failed = 0;
+    if ((rc = sr_check_nodes_cond(h, who, nodes, cond))) return rc;
+    SampleLast &last = h->smp[SMP_REAL];
+    last = SampleLast();
     if (npts == 0) return TTX_OK;
     // the effective weights: trapezoid weights of a drawn mode, the hat row of a held one (a mode of one node is held at its node)
     SmPrep P;
@@ -3370,28 +3406,25 @@ static int sr_run(ttx_engine *h, const char *who, int64_t npts, const double *u,
         const bool given = cond && cond[k] == cond[k];
         if (!given && c.n > 1) { sr_trapezoid(t, c.n, eff.data() + c.woff); continue; }
         held[k] = 1;
-        M.held = 1; M.xh = given ? cond[k] : t[0];
-        M.cell = sr_hat_cell(t, c.n, M.xh);
+        M = sr_held_mode(t, c.n, given ? cond[k] : t[0], M.noff);
         for (int i = 0; i < c.n; i++) eff[c.woff + i] = ttx_basis_entry(TTX_BASIS_LINEAR, 0, 0.0, 0.0, t, c.n, M.xh, i);
-        M.phi0 = eff[c.woff + M.cell];
-        M.phi1 = c.n > 1 ? eff[c.woff + M.cell + 1] : 0.0;
     }
     size_t o_modes = 0, o_nodes = 0;
     if ((rc = sm_prepare(h, who, npts, pl, held, eff, true, reinterpret_cast<const void *>(k_sr_draw), 2 * (size_t)d + (((size_t)d + 1) >> 1),
                          [&](OpMeta &meta) { o_modes = meta.put(modes); o_nodes = meta.put(tnodes); }, P))) return rc;
-    h->sr_bytes = P.bytes;
+    last.bytes = P.bytes;
     SmStage out[4] = {{x, sizeof(double) * (size_t)d, SC_SRX, nullptr}, {cell, sizeof(int) * (size_t)d, SC_IND, nullptr}, {logq, sizeof(double), SC_LQ, nullptr},
                       {val, sizeof(double), SC_OUT, nullptr}};
-    rc = sm_chunks(h, P, npts, u, dev, out, 4,
+    rc = sm_chunks(h, P.loop, npts, u, dev, out, 4,
         [&](size_t c, int grid, const double *du) {
             hipLaunchKernelGGL(k_sr_draw, dim3(grid), dim3(256), P.lds, h->stream, P.T, (const size_t *)(P.dm + P.o_hoff), (const SrMode *)(P.dm + o_modes),
                                (const double *)(P.dm + o_nodes), (const double *)P.H, P.ldsrow, P.grow, P.growlen, (long long)c, du, (double *)out[0].dev, (int *)out[1].dev,
                                (double *)out[2].dev, (double *)out[3].dev);
         },
-        [&](size_t c) { hipLaunchKernelGGL(k_sr_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const double *)out[0].dev, P.dcnt); },
-        &h->sr_ms_draw, &h->sr_failed);
+        [&](size_t c) { hipLaunchKernelGGL(k_sr_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const double *)out[0].dev, P.loop.dcnt); },
+        &last.ms_draw, &last.failed);
     if (rc) return rc;
-    return P.tiles.empty() ? TTX_OK : h->timer[TM_HEAD].ms(&h->sr_ms_head);
+    return P.tiles.empty() ? TTX_OK : h->timer[TM_HEAD].ms(&last.ms_head);
 }
 extern "C" int ttx_sample_real(ttx_engine *h, int64_t npts, const double *u, const double *const *nodes, const double *cond, double *x, int32_t *cell, double *logq, double *val)
 {
@@ -3403,12 +3436,7 @@ extern "C" int ttx_sample_real_dev(ttx_engine *h, int64_t npts, const double *u,
 }
 extern "C" int ttx_sample_real_last(const ttx_engine *h, double *ms_head, double *bytes_head, double *ms_draw, int64_t *nfailed)
 {
-    if (!h) return fail(TTX_EINVAL, "ttx_sample_real_last: null engine");
-    if (ms_head) *ms_head = h->sr_ms_head;
-    if (bytes_head) *bytes_head = h->sr_bytes;
-    if (ms_draw) *ms_draw = h->sr_ms_draw;
-    if (nfailed) *nfailed = h->sr_failed;
-    return TTX_OK;
+    return sm_last(h, "ttx_sample_real_last", SMP_REAL, ms_head, bytes_head, ms_draw, nfailed);
 }
 
 // ---- sums and elementwise products of resident trains (ttx_algebra.h) -----------------------------------------------------------
@@ -4211,97 +4239,150 @@ static int sq_head(ttx_engine *h, const SqPlan &pl, const std::vector<double> &e
     HIPCHECK(hipGetLastError());
     return TTX_OK;
 }
-template <int KS>
-static void sq_rows_mfma(ttx_engine *h, dim3 grid, const double *H, int l, int n, int r1, const double *X, int ldx, int C, int tper, double *S)
-{
-    hipLaunchKernelGGL(k_sq_rows_mfma<KS>, grid, dim3(256), 0, h->stream, H, l, n, r1, X, ldx, C, tper, S);
+namespace {
+// What tells the two squared samplers apart beside their launches and outputs.  which: SMP_SQ or SMP_SQ_REAL; sheets: the sheets of
+// chunk x nmax doubles in SC_QS; tile: what the 16 indices of an index tile of the MFMA rows advance by (16, or 15: every cell has both
+// of its nodes in one tile); state: the bytes a sample keeps in SC_QX between the launches, behind the two state buffers
+struct SqKind { int which, sheets, tile; size_t state; };
+// one mode of one chunk as sq_frame hands it to the callers' launches
+struct SqAt {
+    int k, r0, r1, n, l, ldx, C, grid;      // the 0-based mode, its ranks, size and the rows l of its table; the chunk's C samples and the grid of a launch with one wave per sample
+    int first, last;                        // k == d - 1, k == 0
+    const double *Hk, *Xo, *du;             // the mode's table H_k, the states before the step, the chunk's uniforms
+    double *Xn, *S, *state;                 // the states after the step, the sheets (sheet doubles each), the samples' own state (chunk of each array)
+    size_t sheet, chunk, woff;              // woff: where the mode's weights start in Q's tables
+    const SqHead *Q;                        // the head pass's tables
+};
+template <int KS> struct SqKs { static constexpr int value = KS; };
 }
-// both entries: u, ind, logq, val are host pointers (dev false: staged chunk by chunk) or pointers on the engine's device
-static int sq_run(ttx_engine *h, const char *who, int64_t npts, const double *u, const double *w, const int32_t *fixed, double gamma, int32_t mode, int32_t *ind,
-                  double *logq, double *val, bool dev)
+// The frame of ttx_sample_sq and ttx_sample_sq_real behind their own argument checks; fx[k] != 0: mode k is held.  It holds the plan,
+// the sheet check, the reset of the sampler's last-call figures, the head pass, the AUTO decision, the work space, the chunk loop
+// (sm_chunks) with the rows, pick and step of every mode between the marks, and the readout of the times.  The callers supply:
+//   check(pl)          their last argument check, between the rank check and the sheet check
+//   head(pl, Q)        their effective weights or factors, and sq_head with them
+//   rows_mfma(ks, a, g, tper), rows_exact(a, g)     the rows launch of a drawn mode on the grid g; ks: SqKs<KS>, KS quads of the rank
+//   pick_step(a)       the pick and the step launch of a mode
+//   count(c, dcnt)     the launch that adds the chunk's failed samples to dcnt
+// and out[0 .. nout-1], the outputs (sm_chunks), whose dev their launches read.
+template <class Check, class Head, class RowsMfma, class RowsExact, class PickStep, class Count>
+static int sq_frame(ttx_engine *h, const char *who, const SqKind &kind, int64_t npts, const double *u, int32_t mode, bool dev, const std::vector<int> &fx, SmStage *out,
+                    int nout, Check check, Head head, RowsMfma rows_mfma, RowsExact rows_exact, PickStep pick_step, Count count)
 {
-    if (npts < 0 || (npts > 0 && (!u || !ind))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
-    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
-    if (!(gamma >= 0.0) || !std::isfinite(gamma)) return fail(TTX_EINVAL, "%s: gamma must be a finite number >= 0 (got %g)", who, gamma);
-    int rc = check_train_one_process(h, who);
-    if (rc) return rc;
+    int rc;
     const int d = h->d;
-    std::vector<int> fx(d, 0);
-    for (int k = 0; k < d; k++) {
-        if (fixed && (fixed[k] < 0 || fixed[k] > h->n1[k + 1])) return fail(TTX_EINVAL, "%s: fixed(%d) = %d (0 .. %d expected)", who, k + 1, fixed[k], h->n1[k + 1]);
-        if (fixed) fx[k] = fixed[k];
-    }
     SqPlan pl;
     sq_plan(d, h->n1.data() + 1, h->rfinal.data(), fx.data(), pl);
     const int rmax = pl.rmax, nmax = pl.nmax;
     if (rmax > 128) return fail(TTX_EINVAL, "%s: ranks up to 128 only (got %d)", who, rmax);
-    if (w) { const long long j = sq_bad_weight(w, pl.woff[d]); if (j >= 0) return fail(TTX_EINVAL, "%s: weight %lld is %g (finite and >= 0 expected: its square root enters)", who, j + 1, w[j]); }
-    const size_t chunk = std::min<size_t>(env_chunk("TTX_SAMPLE_CHUNK", (size_t)1 << 18), (size_t)std::max<int64_t>(npts, 1));
-    if ((long long)chunk * nmax > TTX_SQ_SHEET)
-        return fail(TTX_EINVAL, "%s: a chunk of %zu samples times the largest mode %d is %lld, the sheet holds up to %lld (lower TTX_SAMPLE_CHUNK)", who, chunk, nmax,
-                    (long long)chunk * nmax, (long long)TTX_SQ_SHEET);
-    h->sq_ms_head = h->sq_ms_rows = h->sq_ms_pick = h->sq_flops = 0.0; h->sq_failed = 0; h->sq_mode = -1;
+    if ((rc = check(pl))) return rc;
+    const size_t chunk = sm_chunk(std::max<int64_t>(npts, 1)), sheet = chunk * nmax;   // at least 1: this check comes before the early return of an empty call
+    const long long held_sheets = (long long)kind.sheets * (long long)chunk * nmax;
+    if (held_sheets > TTX_SQ_SHEET)
+        return fail(TTX_EINVAL, kind.sheets == 1 ? "%s: a chunk of %zu samples times the largest mode %d is %lld, the sheet holds up to %lld (lower TTX_SAMPLE_CHUNK)"
+                                                 : "%s: two sheets of a chunk of %zu samples times the largest mode %d are %lld, they hold up to %lld (lower TTX_SAMPLE_CHUNK)",
+                    who, chunk, nmax, held_sheets, (long long)TTX_SQ_SHEET);
+    SampleLast &last = h->smp[kind.which];
+    last = SampleLast();
     if (npts == 0) return TTX_OK;
     if ((rc = tt_prepare(h, who))) return rc;
-    std::vector<double> eff, gw;
-    sq_effective(d, h->n1.data() + 1, fx.data(), w, gamma, eff, gw);
+    SmLoop P = sm_loop(h, npts);
     SqHead Q;
-    if ((rc = sq_head(h, pl, eff, fx, gw, Q))) return rc;
+    if ((rc = head(pl, Q))) return rc;
     const double flops = pl.flops * (double)npts;
+    // measured for ttx_sample_sq (ttx_sample_sq.h); ttx_sample_sq_real's modes part in the same bracket on the D_64 train (profiles/sample_sq_real_mi355x.txt)
     const int eff_mode = mode == TTX_EVAL_AUTO ? (flops >= TTX_SQ_AUTO_FLOPS ? TTX_EVAL_MFMA : TTX_EVAL_EXACT) : mode;
-    h->sq_flops = flops; h->sq_mode = eff_mode;
+    last.flops = flops; last.mode = eff_mode;
     const int ldx = (rmax + 3) & ~3, ncu = dev_ncu(h);
-    if ((rc = buf_reserve(h, SC_QS, sizeof(double) * chunk * nmax)) || (rc = buf_reserve(h, SC_QX, (sizeof(double) * (2 * (size_t)ldx + 1) + sizeof(int)) * chunk)) ||
+    if ((rc = buf_reserve(h, SC_QS, sizeof(double) * kind.sheets * sheet)) || (rc = buf_reserve(h, SC_QX, (sizeof(double) * 2 * (size_t)ldx + kind.state) * chunk)) ||
         (rc = buf_reserve(h, SC_CNT, sizeof(long long)))) return rc;
-    double *S = buf<double>(h, SC_QS), *Xa = buf<double>(h, SC_QX), *Xb = Xa + chunk * ldx;
-    SqState st{Xb + chunk * ldx, nullptr};
-    st.fail = (int *)(st.lq + chunk);
-    SmPrep P;
-    P.chunk = chunk; P.gridmax = (int)std::min<long long>(((long long)chunk + 3) / 4, (long long)ncu * 8);
+    double *Xa = buf<double>(h, SC_QX), *Xb = Xa + chunk * ldx;
     P.dcnt = buf<long long>(h, SC_CNT);
     HIPCHECK(hipMemsetAsync(P.dcnt, 0, sizeof(long long), h->stream));
-    SmStage out[3] = {{ind, sizeof(int) * (size_t)d, SC_IND, nullptr}, {logq, sizeof(double), SC_LQ, nullptr}, {val, sizeof(double), SC_OUT, nullptr}};
-    RsMarks marks(h->rs_ev);                // phase 0: between the chunks, 1: rows, 2: picks
+    RsMarks marks(h->rs_ev);                // phase 0: between the chunks, 1: rows, 2: picks and steps
     int lrc = TTX_OK;
     double ms_all = 0.0;
-    rc = sm_chunks(h, P, npts, u, dev, out, 3,
+    rc = sm_chunks(h, P, npts, u, dev, out, nout,
         [&](size_t c, int grid, const double *du) {
-            const int C = (int)c;
+            SqAt a{};
+            a.ldx = ldx; a.C = (int)c; a.grid = grid; a.du = du; a.S = buf<double>(h, SC_QS); a.state = Xb + chunk * ldx; a.sheet = sheet; a.chunk = chunk; a.Q = &Q;
             double *Xo = Xa, *Xn = Xb;
-            hipLaunchKernelGGL(k_sq_ones, g1(c), dim3(256), 0, h->stream, Xo, ldx, C);          // x of the empty suffix
+            hipLaunchKernelGGL(k_sq_ones, g1(c), dim3(256), 0, h->stream, Xo, ldx, a.C);        // x of the empty suffix
             if (!lrc) lrc = marks.mark(h->stream, 0);
             for (int k = d - 1; k >= 0; k--) {
-                const int r0 = h->rfinal[k], r1 = h->rfinal[k + 1], n = h->n1[k + 1], l = pl.l[k];
+                a.k = k; a.r0 = h->rfinal[k]; a.r1 = h->rfinal[k + 1]; a.n = h->n1[k + 1]; a.l = pl.l[k]; a.first = k == d - 1 ? 1 : 0; a.last = k == 0 ? 1 : 0;
+                a.Hk = Q.H + pl.hoff[k]; a.woff = pl.woff[k]; a.Xo = Xo; a.Xn = Xn;
                 if (!fx[k]) {
-                    const double *Hk = Q.H + pl.hoff[k];
                     if (eff_mode == TTX_EVAL_MFMA) {
-                        const int by = (C + 63) / 64, nt = (n + 15) / 16, tper = (int)std::max<long long>(1, (long long)nt * by / (4ll * ncu));
+                        const int lap = 16 - kind.tile, by = (a.C + 63) / 64, nt = (a.n - lap + kind.tile - 1) / kind.tile;
+                        const int tper = (int)std::max<long long>(1, (long long)nt * by / (4ll * ncu));
                         const dim3 g((nt + tper - 1) / tper, by);
-                        if (r1 <= 16) sq_rows_mfma<4>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S);
-                        else if (r1 <= 32) sq_rows_mfma<8>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S);
-                        else if (r1 <= 64) sq_rows_mfma<16>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S);
-                        else sq_rows_mfma<32>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S);
-                    } else {
-                        const int g = (int)std::min<long long>(((long long)C * n + 255) / 256, (long long)ncu * 16);
-                        hipLaunchKernelGGL(k_sq_rows_exact, dim3(g), dim3(256), 0, h->stream, Hk, l, n, r1, (const double *)Xo, ldx, C, S);
-                    }
+                        if (a.r1 <= 16) rows_mfma(SqKs<4>(), a, g, tper);
+                        else if (a.r1 <= 32) rows_mfma(SqKs<8>(), a, g, tper);
+                        else if (a.r1 <= 64) rows_mfma(SqKs<16>(), a, g, tper);
+                        else rows_mfma(SqKs<32>(), a, g, tper);
+                    } else rows_exact(a, dim3((unsigned)std::min<long long>(((long long)a.C * a.n + 255) / 256, (long long)ncu * 16)));
                     if (!lrc) lrc = marks.mark(h->stream, 1);
                 }
-                hipLaunchKernelGGL(k_sq_pick, dim3(grid), dim3(256), 0, h->stream, n, k, d, fx[k] - 1, Q.fixed, Q.w + pl.woff[k], (const double *)(Q.g + k), (const double *)S, st,
-                                   (long long)c, du, k == d - 1 ? 1 : 0, k == 0 ? 1 : 0, (int *)out[0].dev, (double *)out[1].dev);
-                hipLaunchKernelGGL(k_sq_step, dim3(grid), dim3(256), 0, h->stream, (const double *)core_dev(h, k + 1), h->RM, h->P.SS, r0, r1, n, k, d, (const int *)out[0].dev,
-                                   (const int *)st.fail, (const double *)Xo, Xn, ldx, (long long)c, k == d - 1 ? 1 : 0, k == 0 ? 1 : 0, (double *)out[2].dev);
+                pick_step(a);
                 if (!lrc) lrc = marks.mark(h->stream, 2);
                 std::swap(Xo, Xn);
             }
         },
-        [&](size_t c) { hipLaunchKernelGGL(k_sm_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const int *)out[0].dev, P.dcnt); },
-        &ms_all, &h->sq_failed);
+        [&](size_t c) { count(c, P.dcnt); }, &ms_all, &last.failed);
     if (rc || (rc = lrc)) return rc;
     double ms[3] = {0.0, 0.0, 0.0};
     if ((rc = marks.sum(ms))) return rc;
-    h->sq_ms_rows = ms[1]; h->sq_ms_pick = ms[2];
-    return h->timer[TM_HEAD].ms(&h->sq_ms_head);
+    last.ms_rows = ms[1]; last.ms_pick = ms[2];
+    return h->timer[TM_HEAD].ms(&last.ms_head);
+}
+// the last-call figures of a squared sampler (which) as its _last entry hands them out; any pointer may be null
+static int sq_last(const ttx_engine *h, const char *who, int which, double *ms_head, double *ms_rows, double *ms_pick, double *flops, int64_t *nfailed, int32_t *mode_ran)
+{
+    if (!h) return fail(TTX_EINVAL, "%s: null engine", who);
+    const SampleLast &L = h->smp[which];
+    if (ms_head) *ms_head = L.ms_head;
+    if (ms_rows) *ms_rows = L.ms_rows;
+    if (ms_pick) *ms_pick = L.ms_pick;
+    if (flops) *flops = L.flops;
+    if (nfailed) *nfailed = L.failed;
+    if (mode_ran) *mode_ran = L.mode;
+    return TTX_OK;
+}
+// both entries: u, ind, logq, val are host pointers (dev false: staged chunk by chunk) or pointers on the engine's device.  One sheet, index
+// tiles of 16, per sample logq and the failure flag (SqState)
+static int sq_run(ttx_engine *h, const char *who, int64_t npts, const double *u, const double *w, const int32_t *fixed, double gamma, int32_t mode, int32_t *ind,
+                  double *logq, double *val, bool dev)
+{
+    if (npts < 0 || (npts > 0 && (!u || !ind))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
+    int rc = sq_check_mode_gamma(who, mode, gamma);
+    if (rc || (rc = check_train_one_process(h, who)) || (rc = sm_check_fixed(h, who, fixed))) return rc;
+    const int d = h->d;
+    std::vector<int> fx(d, 0);
+    if (fixed) fx.assign(fixed, fixed + d);
+    SmStage out[3] = {{ind, sizeof(int) * (size_t)d, SC_IND, nullptr}, {logq, sizeof(double), SC_LQ, nullptr}, {val, sizeof(double), SC_OUT, nullptr}};
+    const auto state = [](const SqAt &a) { SqState st{a.state, nullptr}; st.fail = (int *)(st.lq + a.chunk); return st; };
+    return sq_frame(h, who, SqKind{SMP_SQ, 1, 16, sizeof(double) + sizeof(int)}, npts, u, mode, dev, fx, out, 3,
+        [&](const SqPlan &pl) {
+            if (w) { const long long j = sq_bad_weight(w, pl.woff[d]); if (j >= 0) return fail(TTX_EINVAL, "%s: weight %lld is %g (finite and >= 0 expected: its square root enters)", who, j + 1, w[j]); }
+            return (int)TTX_OK;
+        },
+        [&](const SqPlan &pl, SqHead &Qh) {
+            std::vector<double> eff, gw;
+            sq_effective(d, h->n1.data() + 1, fx.data(), w, gamma, eff, gw);
+            return sq_head(h, pl, eff, fx, gw, Qh);
+        },
+        [&](auto ks, const SqAt &a, dim3 g, int tper) {
+            hipLaunchKernelGGL(k_sq_rows_mfma<decltype(ks)::value>, g, dim3(256), 0, h->stream, a.Hk, a.l, a.n, a.r1, a.Xo, a.ldx, a.C, tper, a.S);
+        },
+        [&](const SqAt &a, dim3 g) { hipLaunchKernelGGL(k_sq_rows_exact, g, dim3(256), 0, h->stream, a.Hk, a.l, a.n, a.r1, a.Xo, a.ldx, a.C, a.S); },
+        [&](const SqAt &a) {
+            const SqState st = state(a);
+            hipLaunchKernelGGL(k_sq_pick, dim3(a.grid), dim3(256), 0, h->stream, a.n, a.k, d, fx[a.k] - 1, a.Q->fixed, a.Q->w + a.woff, (const double *)(a.Q->g + a.k),
+                               (const double *)a.S, st, (long long)a.C, a.du, a.first, a.last, (int *)out[0].dev, (double *)out[1].dev);
+            hipLaunchKernelGGL(k_sq_step, dim3(a.grid), dim3(256), 0, h->stream, (const double *)core_dev(h, a.k + 1), h->RM, h->P.SS, a.r0, a.r1, a.n, a.k, d,
+                               (const int *)out[0].dev, (const int *)st.fail, a.Xo, a.Xn, a.ldx, (long long)a.C, a.first, a.last, (double *)out[2].dev);
+        },
+        [&](size_t c, long long *dcnt) { hipLaunchKernelGGL(k_sm_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const int *)out[0].dev, dcnt); });
 }
 extern "C" int ttx_sample_sq(ttx_engine *h, int64_t npts, const double *u, const double *w, const int32_t *fixed, double gamma, int32_t mode, int32_t *ind, double *logq,
                              double *val)
@@ -4315,131 +4396,61 @@ extern "C" int ttx_sample_sq_dev(ttx_engine *h, int64_t npts, const double *u, c
 }
 extern "C" int ttx_sample_sq_last(const ttx_engine *h, double *ms_head, double *ms_rows, double *ms_pick, double *flops, int64_t *nfailed, int32_t *mode_ran)
 {
-    if (!h) return fail(TTX_EINVAL, "ttx_sample_sq_last: null engine");
-    if (ms_head) *ms_head = h->sq_ms_head;
-    if (ms_rows) *ms_rows = h->sq_ms_rows;
-    if (ms_pick) *ms_pick = h->sq_ms_pick;
-    if (flops) *flops = h->sq_flops;
-    if (nfailed) *nfailed = h->sq_failed;
-    if (mode_ran) *mode_ran = h->sq_mode;
-    return TTX_OK;
+    return sq_last(h, "ttx_sample_sq_last", SMP_SQ, ms_head, ms_rows, ms_pick, flops, nfailed, mode_ran);
 }
 
 // ---- real-valued samples from the square of the interpolant of the resident train (ttx_sample_sq_real.h) -------------------------
-template <int KS>
-static void sqr_rows_mfma(ttx_engine *h, dim3 grid, const double *H, int l, int n, int r1, const double *X, int ldx, int C, int tper, double *S, double *Cs)
-{
-    hipLaunchKernelGGL(k_sqr_rows_mfma<KS>, grid, dim3(256), 0, h->stream, H, l, n, r1, X, ldx, C, tper, S, Cs);
-}
-// both entries: u, x, cell, logq, val are host pointers (dev false: staged chunk by chunk) or pointers on the engine's device
+// both entries: u, x, cell, logq, val are host pointers (dev false: staged chunk by chunk) or pointers on the engine's device.  Two sheets
+// (squares and neighbour products), index tiles that advance by 15, per sample logq, the two hat values, the failure flag and the hat cell (SqrState)
 static int sqr_run(ttx_engine *h, const char *who, int64_t npts, const double *u, const double *const *nodes, const double *cond, double gamma, int32_t mode, double *x,
                    int32_t *cell, double *logq, double *val, bool dev)
 {
     if (npts < 0 || (npts > 0 && (!u || !x || !nodes))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
-    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
-    if (!(gamma >= 0.0) || !std::isfinite(gamma)) return fail(TTX_EINVAL, "%s: gamma must be a finite number >= 0 (got %g)", who, gamma);
-    int rc = check_train_one_process(h, who);
-    if (rc) return rc;
+    int rc = sq_check_mode_gamma(who, mode, gamma);
+    if (rc || (rc = check_train_one_process(h, who)) || (rc = sr_check_nodes_cond(h, who, nodes, cond))) return rc;
     const int d = h->d;
-    if (nodes) {
-        for (int k = 0; k < d; k++) {
-            ttx_basis b{TTX_BASIS_LINEAR, 0, 0.0, 0.0, nodes[k]};
-            if ((rc = bs_check_one(who, k + 1, b, h->n1[k + 1]))) return rc;
-        }
-    }
-    if (cond) for (int k = 0; k < d; k++) if (std::isinf(cond[k])) return fail(TTX_EINVAL, "%s: cond(%d) is infinite (a coordinate, or NaN for a drawn mode, expected)", who, k + 1);
     std::vector<int> fx(d, 0);
     if (nodes) for (int k = 0; k < d; k++) fx[k] = (cond && cond[k] == cond[k]) || h->n1[k + 1] == 1;
-    SqPlan pl;
-    sq_plan(d, h->n1.data() + 1, h->rfinal.data(), fx.data(), pl);
-    const int rmax = pl.rmax, nmax = pl.nmax;
-    if (rmax > 128) return fail(TTX_EINVAL, "%s: ranks up to 128 only (got %d)", who, rmax);
-    const size_t chunk = std::min<size_t>(env_chunk("TTX_SAMPLE_CHUNK", (size_t)1 << 18), (size_t)std::max<int64_t>(npts, 1));
-    if (2ll * (long long)chunk * nmax > TTX_SQ_SHEET)
-        return fail(TTX_EINVAL, "%s: two sheets of a chunk of %zu samples times the largest mode %d are %lld, they hold up to %lld (lower TTX_SAMPLE_CHUNK)", who, chunk, nmax,
-                    2ll * (long long)chunk * nmax, (long long)TTX_SQ_SHEET);
-    h->sqr_ms_head = h->sqr_ms_rows = h->sqr_ms_pick = h->sqr_flops = 0.0; h->sqr_failed = 0; h->sqr_mode = -1;
-    if (npts == 0) return TTX_OK;
-    if ((rc = tt_prepare(h, who))) return rc;
-    // the bidiagonal factors: the mass matrix's Cholesky factor of a drawn mode, the hat row of a held one (a mode of one node is held at its node)
-    std::vector<double> dg(pl.woff[d], 0.0), sp(pl.woff[d], 0.0), tnodes, gw(d + 1, gamma);
-    std::vector<SqrMode> modes(d);
-    for (int k = 0; k < d; k++) {
-        const int n = h->n1[k + 1];
-        const double *t = nodes[k];
-        SqrMode &M = modes[k];
-        M = SqrMode{0, 0, 1.0, 0.0, 0.0, tnodes.size()};
-        tnodes.insert(tnodes.end(), t, t + n);
-        double *dk = dg.data() + pl.woff[k], *sk = sp.data() + pl.woff[k];
-        if (!fx[k]) { sqr_mass_cholesky(t, n, dk, sk); gw[k + 1] = gw[k] * (t[n - 1] - t[0]); continue; }
-        const bool given = cond && cond[k] == cond[k];
-        M.held = 1; M.xh = given ? cond[k] : t[0];
-        M.cell = sr_hat_cell(t, n, M.xh);
-        M.phi0 = ttx_basis_entry(TTX_BASIS_LINEAR, 0, 0.0, 0.0, t, n, M.xh, M.cell);
-        M.phi1 = n > 1 ? ttx_basis_entry(TTX_BASIS_LINEAR, 0, 0.0, 0.0, t, n, M.xh, M.cell + 1) : 0.0;
-        dk[M.cell] = M.phi0; sk[M.cell] = M.phi1;
-        gw[k + 1] = gw[k];
-    }
-    SqHead Q;
-    if ((rc = sq_head(h, pl, dg, fx, gw, Q, &sp, &tnodes))) return rc;
-    const double flops = pl.flops * (double)npts;
-    // ttx_sample_sq's threshold: this entry's modes part in the same bracket on the D_64 train (profiles/sample_sq_real_mi355x.txt)
-    const int eff_mode = mode == TTX_EVAL_AUTO ? (flops >= TTX_SQ_AUTO_FLOPS ? TTX_EVAL_MFMA : TTX_EVAL_EXACT) : mode;
-    h->sqr_flops = flops; h->sqr_mode = eff_mode;
-    const int ldx = (rmax + 3) & ~3, ncu = dev_ncu(h);
-    if ((rc = buf_reserve(h, SC_QS, sizeof(double) * 2 * chunk * nmax)) || (rc = buf_reserve(h, SC_QX, (sizeof(double) * (2 * (size_t)ldx + 3) + 2 * sizeof(int)) * chunk)) ||
-        (rc = buf_reserve(h, SC_CNT, sizeof(long long)))) return rc;
-    double *S = buf<double>(h, SC_QS), *Cs = S + chunk * nmax, *Xa = buf<double>(h, SC_QX), *Xb = Xa + chunk * ldx;
-    SqrState st{Xb + chunk * ldx, nullptr, nullptr, nullptr, nullptr};
-    st.f0 = st.lq + chunk; st.f1 = st.f0 + chunk;
-    st.fail = (int *)(st.f1 + chunk); st.ci = st.fail + chunk;
-    SmPrep P;
-    P.chunk = chunk; P.gridmax = (int)std::min<long long>(((long long)chunk + 3) / 4, (long long)ncu * 8);
-    P.dcnt = buf<long long>(h, SC_CNT);
-    HIPCHECK(hipMemsetAsync(P.dcnt, 0, sizeof(long long), h->stream));
+    std::vector<SrMode> modes(d);
     SmStage out[4] = {{x, sizeof(double) * (size_t)d, SC_SRX, nullptr}, {cell, sizeof(int) * (size_t)d, SC_IND, nullptr}, {logq, sizeof(double), SC_LQ, nullptr},
                       {val, sizeof(double), SC_OUT, nullptr}};
-    RsMarks marks(h->rs_ev);                // phase 0: between the chunks, 1: rows, 2: picks and steps
-    int lrc = TTX_OK;
-    double ms_all = 0.0;
-    rc = sm_chunks(h, P, npts, u, dev, out, 4,
-        [&](size_t c, int grid, const double *du) {
-            const int C = (int)c;
-            double *Xo = Xa, *Xn = Xb;
-            hipLaunchKernelGGL(k_sq_ones, g1(c), dim3(256), 0, h->stream, Xo, ldx, C);          // x of the empty suffix
-            if (!lrc) lrc = marks.mark(h->stream, 0);
-            for (int k = d - 1; k >= 0; k--) {
-                const int r0 = h->rfinal[k], r1 = h->rfinal[k + 1], n = h->n1[k + 1], l = pl.l[k];
-                if (!fx[k]) {
-                    const double *Hk = Q.H + pl.hoff[k];
-                    if (eff_mode == TTX_EVAL_MFMA) {
-                        const int by = (C + 63) / 64, nt = (n + 13) / 15, tper = (int)std::max<long long>(1, (long long)nt * by / (4ll * ncu));
-                        const dim3 g((nt + tper - 1) / tper, by);
-                        if (r1 <= 16) sqr_rows_mfma<4>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S, Cs);
-                        else if (r1 <= 32) sqr_rows_mfma<8>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S, Cs);
-                        else if (r1 <= 64) sqr_rows_mfma<16>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S, Cs);
-                        else sqr_rows_mfma<32>(h, g, Hk, l, n, r1, Xo, ldx, C, tper, S, Cs);
-                    } else {
-                        const int g = (int)std::min<long long>(((long long)C * n + 255) / 256, (long long)ncu * 16);
-                        hipLaunchKernelGGL(k_sqr_rows_exact, dim3(g), dim3(256), 0, h->stream, Hk, l, n, r1, (const double *)Xo, ldx, C, S, Cs);
-                    }
-                    if (!lrc) lrc = marks.mark(h->stream, 1);
-                }
-                hipLaunchKernelGGL(k_sqr_pick, dim3(grid), dim3(256), 0, h->stream, n, k, d, modes[k], Q.fixed, Q.nodes, (const double *)(Q.g + k), (const double *)S,
-                                   (const double *)Cs, st, (long long)c, du, k == d - 1 ? 1 : 0, k == 0 ? 1 : 0, (double *)out[0].dev, (int *)out[1].dev, (double *)out[2].dev);
-                hipLaunchKernelGGL(k_sqr_step, dim3(grid), dim3(256), 0, h->stream, (const double *)core_dev(h, k + 1), h->RM, h->P.SS, r0, r1, n, st, (const double *)Xo, Xn, ldx,
-                                   (long long)c, k == 0 ? 1 : 0, (double *)out[3].dev);
-                if (!lrc) lrc = marks.mark(h->stream, 2);
-                std::swap(Xo, Xn);
+    const auto state = [](const SqAt &a) {
+        SqrState st{a.state, nullptr, nullptr, nullptr, nullptr};
+        st.f0 = st.lq + a.chunk; st.f1 = st.f0 + a.chunk;
+        st.fail = (int *)(st.f1 + a.chunk); st.ci = st.fail + a.chunk;
+        return st;
+    };
+    return sq_frame(h, who, SqKind{SMP_SQ_REAL, 2, 15, 3 * sizeof(double) + 2 * sizeof(int)}, npts, u, mode, dev, fx, out, 4,
+        [](const SqPlan &) { return (int)TTX_OK; },
+        [&](const SqPlan &pl, SqHead &Qh) {
+            // the bidiagonal factors: the mass matrix's Cholesky factor of a drawn mode, the hat row of a held one (a mode of one node is held at its node)
+            std::vector<double> dg(pl.woff[d], 0.0), sp(pl.woff[d], 0.0), tnodes, gw(d + 1, gamma);
+            for (int k = 0; k < d; k++) {
+                const int n = h->n1[k + 1];
+                const double *t = nodes[k];
+                SrMode &M = modes[k];
+                M = SrMode{0, 0, 1.0, 0.0, 0.0, tnodes.size()};
+                tnodes.insert(tnodes.end(), t, t + n);
+                double *dk = dg.data() + pl.woff[k], *sk = sp.data() + pl.woff[k];
+                if (!fx[k]) { sqr_mass_cholesky(t, n, dk, sk); gw[k + 1] = gw[k] * (t[n - 1] - t[0]); continue; }
+                M = sr_held_mode(t, n, cond && cond[k] == cond[k] ? cond[k] : t[0], M.noff);
+                dk[M.cell] = M.phi0; sk[M.cell] = M.phi1;
+                gw[k + 1] = gw[k];
             }
+            return sq_head(h, pl, dg, fx, gw, Qh, &sp, &tnodes);
         },
-        [&](size_t c) { hipLaunchKernelGGL(k_sr_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const double *)out[0].dev, P.dcnt); },
-        &ms_all, &h->sqr_failed);
-    if (rc || (rc = lrc)) return rc;
-    double ms[3] = {0.0, 0.0, 0.0};
-    if ((rc = marks.sum(ms))) return rc;
-    h->sqr_ms_rows = ms[1]; h->sqr_ms_pick = ms[2];
-    return h->timer[TM_HEAD].ms(&h->sqr_ms_head);
+        [&](auto ks, const SqAt &a, dim3 g, int tper) {
+            hipLaunchKernelGGL(k_sqr_rows_mfma<decltype(ks)::value>, g, dim3(256), 0, h->stream, a.Hk, a.l, a.n, a.r1, a.Xo, a.ldx, a.C, tper, a.S, a.S + a.sheet);
+        },
+        [&](const SqAt &a, dim3 g) { hipLaunchKernelGGL(k_sqr_rows_exact, g, dim3(256), 0, h->stream, a.Hk, a.l, a.n, a.r1, a.Xo, a.ldx, a.C, a.S, a.S + a.sheet); },
+        [&](const SqAt &a) {
+            const SqrState st = state(a);
+            hipLaunchKernelGGL(k_sqr_pick, dim3(a.grid), dim3(256), 0, h->stream, a.n, a.k, d, modes[a.k], a.Q->fixed, a.Q->nodes, (const double *)(a.Q->g + a.k), (const double *)a.S,
+                               (const double *)(a.S + a.sheet), st, (long long)a.C, a.du, a.first, a.last, (double *)out[0].dev, (int *)out[1].dev, (double *)out[2].dev);
+            hipLaunchKernelGGL(k_sqr_step, dim3(a.grid), dim3(256), 0, h->stream, (const double *)core_dev(h, a.k + 1), h->RM, h->P.SS, a.r0, a.r1, a.n, st, a.Xo, a.Xn, a.ldx,
+                               (long long)a.C, a.last, (double *)out[3].dev);
+        },
+        [&](size_t c, long long *dcnt) { hipLaunchKernelGGL(k_sr_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const double *)out[0].dev, dcnt); });
 }
 extern "C" int ttx_sample_sq_real(ttx_engine *h, int64_t npts, const double *u, const double *const *nodes, const double *cond, double gamma, int32_t mode, double *x,
                                   int32_t *cell, double *logq, double *val)
@@ -4453,14 +4464,7 @@ extern "C" int ttx_sample_sq_real_dev(ttx_engine *h, int64_t npts, const double 
 }
 extern "C" int ttx_sample_sq_real_last(const ttx_engine *h, double *ms_head, double *ms_rows, double *ms_pick, double *flops, int64_t *nfailed, int32_t *mode_ran)
 {
-    if (!h) return fail(TTX_EINVAL, "ttx_sample_sq_real_last: null engine");
-    if (ms_head) *ms_head = h->sqr_ms_head;
-    if (ms_rows) *ms_rows = h->sqr_ms_rows;
-    if (ms_pick) *ms_pick = h->sqr_ms_pick;
-    if (flops) *flops = h->sqr_flops;
-    if (nfailed) *nfailed = h->sqr_failed;
-    if (mode_ran) *mode_ran = h->sqr_mode;
-    return TTX_OK;
+    return sq_last(h, "ttx_sample_sq_real_last", SMP_SQ_REAL, ms_head, ms_rows, ms_pick, flops, nfailed, mode_ran);
 }
 
 extern "C" int ttx_kernel_stats(const ttx_engine *h, int64_t launches[TTX_K_NKINDS], double ms[TTX_K_NKINDS], double bytes[TTX_K_NKINDS])

@@ -78,6 +78,61 @@ __device__ inline double sm_wave_scan(double c, int lane)
     return c;
 }
 
+// A sample's row of uniforms u[0 .. d-1]: true if a drawn mode (held(i) false) has a NaN or a negative u, which refuses the sample.
+// us (may be null): the wave's copy of the row
+template <class Held>
+__device__ inline bool sm_bad_u(const double *u, int d, int lane, Held held, double *us)
+{
+    bool badu = false;
+    for (int i = lane; i < d; i += 64) { const double uu = u[i]; if (us) us[i] = uu; badu |= !held(i) && !(uu >= 0.0); }   // NaN or negative
+    return __ballot(badu) != 0;
+}
+
+// The search of the cell samplers (k_sr_draw, k_sqr_pick) among the masses e(0 .. n-1) >= 0 of a sample's cells, lanes along i in rounds
+// of 64, by the rules of the index search in k_sm_draw and k_sq_pick.  first(i) and again(i) give e(i), and 0.0 for i >= n, in the first
+// and in the second pass.  Pass one: the total and the last positive entry.  Pass two (u < 1): the first i with e(i) > 0 and t < c(i),
+// t = u total, c the inclusive running sum.  Where there is none, or u >= 1, the largest i with e(i) > 0 is chosen.  A total that is
+// 0, NaN or Inf, or no positive entry, fails the sample.  Every lane of the wave takes part and gets the same answer; a position
+// comes from lane numbers alone, never from a value.  The running sum is carried from round to round through lane 63.
+// k_sm_draw and k_sq_pick keep these loops written out: through a shared helper k_sm_draw kept eight more scalars in vector lanes
+// and its draws took 0.2 % longer, k_sq_pick's picks 0.15 % (profiles/sampler_frame_mi355x.txt); a change of a rule is made in all three.
+//
+// ok: false if the sample fails (nothing else is set then).  pos: the chosen cell; hit: it came from the second pass, and then
+// at = e(pos) and before = c(pos - 1), from which the cell samplers invert inside the cell (sr_mass_within).
+struct SmFound { bool ok, hit; int pos; double total, t, at, before; };
+
+template <class First, class Again>
+__device__ inline SmFound sm_wave_search(int n, double u, int lane, First first, Again again)
+{
+    SmFound f{false, false, -1, 0.0, 0.0, 0.0, 0.0};
+    double carry = 0.0;
+    for (int i0 = 0; i0 < n; i0 += 64) {                                        // e, and the total c(n-1)
+        const double e = first(i0 + lane);
+        carry = __shfl(carry + sm_wave_scan(e, lane), 63);
+        const unsigned long long pos = __ballot(e > 0.0);
+        if (pos) f.pos = i0 + 63 - __builtin_clzll(pos);
+    }
+    f.total = carry;
+    if (!(f.total > 0.0) || f.total == __builtin_inf() || f.pos < 0) return f;  // 0, NaN or Inf
+    f.ok = true;
+    f.t = u * f.total;
+    if (u < 1.0) {                                                              // else, or with no i with t < c(i): the largest i with e > 0
+        carry = 0.0;
+        for (int i0 = 0; i0 < n; i0 += 64) {
+            const int i = i0 + lane;
+            const double e = again(i), c = carry + sm_wave_scan(e, lane);
+            const unsigned long long hit = __ballot(i < n && e > 0.0 && f.t < c);
+            if (hit) {
+                const int fl = __builtin_ctzll(hit);
+                f.hit = true; f.pos = i0 + fl; f.at = __shfl(e, fl); f.before = fl ? __shfl(c, fl - 1) : carry;
+                break;
+            }
+            carry = __shfl(c, 63);
+        }
+    }
+    return f;
+}
+
 // One wave per sample, grid-stride.  Dynamic LDS per wave: x[ldx], z[ldx], the sample's row of u [d], its index row [d] and the
 // row of p of the current mode [ldsrow]; nothing is shared between waves, so there is no workgroup barrier.  A mode longer than
 // ldsrow keeps its row in grow (growlen doubles per wave of the grid).  A lane reads back only the entries of the row it wrote

@@ -6,8 +6,8 @@
 // k_ct_chains form the prefix vectors from the effective weights (trapezoid weights of a drawn mode, the hat row of a held one),
 // k_sm_head the head tables with weights of 1.0.  Then
 //   k_sr_draw   one wave per sample: per drawn mode the row p(i) = |sum_b H_k(i, b) x(b)| with lanes along i, the cell masses
-//               A(j) = (0.5 (p(j) + p(j+1))) h_j with lanes along j, their wave scan, the search for the cell, the root of the
-//               quadratic inside the cell (sr_invert), and the two-term chain step with the hat row of the rounded coordinate;
+//               A(j) = (0.5 (p(j) + p(j+1))) h_j with lanes along j, the search for the cell (sm_wave_search, ttx_sample.h), the
+//               root of the quadratic inside the cell (sr_invert), the placement of x (sr_place), and the two-term chain step with the hat row of the rounded coordinate;
 //               the chain ends exactly where k_bs_exact (ttx_basis.h) would: val is the interpolant at x
 //   k_sr_count  the failed samples of a chunk (their rows of x start with a NaN), added to the call's counter by one workgroup
 // The first part of this file is plain C++ a host compiler accepts (tests/sample_real_main.cpp runs it on the CPU).
@@ -15,6 +15,8 @@
 // path for the rows of p, extra per-mode weights, ranks above 128.
 #pragma once
 #include <math.h>
+#include <stddef.h>
+#include "ttx_basis.h"     // ttx_basis_entry: host and device
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define TTX_SR_HD __host__ __device__ inline
@@ -62,12 +64,23 @@ TTX_SR_HD int sr_hat_cell(const double *t, int n, double x)
     return lo > 0 ? lo : 0;
 }
 
-#if defined(__HIPCC__)
-#include "ttx_sample.h"    // TTX_SM_LDSROW, sm_wave_scan, k_sm_head
-
-// one mode as k_sr_draw takes it.  held != 0: the mode is not drawn, its coordinate xh, cell and the two hat values were formed on the
-// host (ttx_basis_entry, the function of ttx_basis_host).  noff: where the mode's nodes start in the call's node block
+// one mode as k_sr_draw, k_sqr_pick and k_sqr_step take it.  held != 0: the mode is not drawn, its coordinate xh, cell and the two hat
+// values were formed on the host (ttx_basis_entry, the function of ttx_basis_host).  noff: where the mode's nodes start in the call's
+// node block
 struct SrMode { int held, cell; double phi0, phi1, xh; size_t noff; };
+
+// the record of a mode of n nodes t held at the coordinate x (a number): TTX_BASIS_LINEAR's cell and its two hat values, entry by entry
+// from ttx_basis_entry (a mode of one node has the first only)
+TTX_SR_HD SrMode sr_held_mode(const double *t, int n, double x, size_t noff)
+{
+    SrMode M{1, sr_hat_cell(t, n, x), 0.0, 0.0, x, noff};
+    M.phi0 = ttx_basis_entry(2, 0, 0.0, 0.0, t, n, x, M.cell);                  // kind 2: TTX_BASIS_LINEAR
+    M.phi1 = n > 1 ? ttx_basis_entry(2, 0, 0.0, 0.0, t, n, x, M.cell + 1) : 0.0;
+    return M;
+}
+
+#if defined(__HIPCC__)
+#include "ttx_sample.h"    // TTX_SM_LDSROW, sm_wave_search, k_sm_head
 
 // z = (0.0 + f0 A0 x) + f1 A1 x for the slices A0 = G(:, i, :) and A1 = G(:, i + 1, :) (two; a mode of one node has the first term
 // only).  Both products are k_ev_exact's: sums from 0.0 over ascending b, separate multiply and add, two rows per lane above rank 64
@@ -100,6 +113,29 @@ __device__ inline void sr_chain_step(const double *A, size_t RM, size_t SS, int 
     }
 }
 
+// the mass to invert inside the cell a search has hit: t minus the running sum before the cell, clamped into [0, the cell's mass]
+__device__ inline double sr_mass_within(const SmFound &f)
+{
+    double s = f.t - f.before;
+    s = s > 0.0 ? s : 0.0;
+    return s < f.at ? s : f.at;
+}
+
+// x = t_cj + lam h_cj placed into the closed cell cj before the hat row is looked up; ci: TTX_BASIS_LINEAR's cell of the rounded x (it may
+// be the next one, capped at n - 2), f0 and f1: the two hat values of x there
+__device__ inline double sr_place(const double *t, int n, int cj, double lam, int &ci, double &f0, double &f1)
+{
+    const double tl = t[cj], tr = t[cj + 1];
+    double xk = tl + lam * (tr - tl);
+    xk = xk > tl ? xk : tl;
+    xk = xk < tr ? xk : tr;
+    ci = cj + ((cj + 1 <= n - 2 && xk >= tr) ? 1 : 0);
+    const double t0 = t[ci], t1 = t[ci + 1];
+    f1 = (xk - t0) / (t1 - t0);
+    f0 = 1.0 - f1;
+    return xk;
+}
+
 // One wave per sample, grid-stride, in the frame of k_sm_draw.  Dynamic LDS per wave: x[ldx], z[ldx], the sample's row of u [d], its
 // coordinates [d], its cell row [d] and the row of p of the current mode [ldsrow]; nothing is shared between waves, so there is no
 // workgroup barrier.  A mode longer than ldsrow keeps its row in grow (growlen doubles per wave of the grid).  The row is complete,
@@ -117,9 +153,7 @@ __global__ __launch_bounds__(256) void k_sr_draw(EvTrain T, const size_t *hoff, 
     for (long long p = (long long)blockIdx.x * nw + wave; p < npts; p += (long long)gridDim.x * nw) {
         double *x = xb, *z = xb + T.ldx;
         __builtin_amdgcn_wave_barrier();
-        bool badu = false;
-        for (int i = lane; i < d; i += 64) { const double uu = u[(size_t)p * d + i]; us[i] = uu; badu |= !modes[i].held && !(uu >= 0.0); }   // NaN or negative
-        bool fail = __ballot(badu) != 0;
+        bool fail = sm_bad_u(u + (size_t)p * d, d, lane, [&](int i) { return modes[i].held != 0; }, us);
         if (lane == 0) x[0] = 1.0;                                              // x_(d+1) = [1]
         double lq = 0.0;
         __builtin_amdgcn_wave_barrier();
@@ -131,7 +165,6 @@ __global__ __launch_bounds__(256) void k_sr_draw(EvTrain T, const size_t *hoff, 
             if (!M.held) {
                 const double *Hk = H + hoff[k], *t = nodes + M.noff;
                 double *row = n <= ldsrow ? lrow : wrow;
-                const double uk = us[k];
                 const int nc = n - 1;                                           // cells; a drawn mode has n >= 2
                 for (int i = lane; i < n; i += 64) {                            // the row of p
                     double m = 0.0;
@@ -142,48 +175,13 @@ __global__ __launch_bounds__(256) void k_sr_draw(EvTrain T, const size_t *hoff, 
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                double carry = 0.0;
-                int last = -1;
-                for (int j0 = 0; j0 < nc; j0 += 64) {                           // the cell masses and their total C(n-2)
-                    const int j = j0 + lane;
-                    const double a = j < nc ? (0.5 * (row[j] + row[j + 1])) * (t[j + 1] - t[j]) : 0.0;
-                    carry = __shfl(carry + sm_wave_scan(a, lane), 63);
-                    const unsigned long long pos = __ballot(a > 0.0);
-                    if (pos) last = j0 + 63 - __builtin_clzll(pos);
-                }
-                const double total = carry;
-                if (!(total > 0.0) || total == __builtin_inf() || last < 0) { fail = true; break; }   // 0, NaN or Inf
-                const double tt = uk * total;
-                cj = last;                                                      // u >= 1, or no cell with tt < C(j): the largest cell with A > 0, lambda = 1
-                double lam = 1.0;
-                if (uk < 1.0) {
-                    carry = 0.0;
-                    for (int j0 = 0; j0 < nc; j0 += 64) {
-                        const int j = j0 + lane;
-                        const double a = j < nc ? (0.5 * (row[j] + row[j + 1])) * (t[j + 1] - t[j]) : 0.0, c = carry + sm_wave_scan(a, lane);
-                        const unsigned long long hit = __ballot(j < nc && a > 0.0 && tt < c);
-                        if (hit) {
-                            const int fl = __builtin_ctzll(hit);
-                            cj = j0 + fl;
-                            const double cprev = fl ? __shfl(c, fl - 1) : carry, aj = __shfl(a, fl);
-                            double s = tt - cprev;
-                            s = s > 0.0 ? s : 0.0;
-                            s = s < aj ? s : aj;
-                            lam = sr_invert(row[cj], row[cj + 1], s / (t[cj + 1] - t[cj]));
-                            break;
-                        }
-                        carry = __shfl(c, 63);
-                    }
-                }
-                const double tl = t[cj], tr = t[cj + 1];
-                xk = tl + lam * (tr - tl);
-                xk = xk > tl ? xk : tl;                                         // into the closed cell before the hat row is looked up
-                xk = xk < tr ? xk : tr;
-                ci = cj + ((cj + 1 <= n - 2 && xk >= tr) ? 1 : 0);             // TTX_BASIS_LINEAR's cell of the rounded x: it may be the next one
-                const double t0 = t[ci], t1 = t[ci + 1];
-                f1 = (xk - t0) / (t1 - t0);
-                f0 = 1.0 - f1;
-                lq = lq + log((f0 * row[ci] + f1 * row[ci + 1]) / total);
+                const auto mass = [&](int j) { return j < nc ? (0.5 * (row[j] + row[j + 1])) * (t[j + 1] - t[j]) : 0.0; };   // the cell masses A(j)
+                const SmFound f = sm_wave_search(nc, us[k], lane, mass, mass);
+                if (!f.ok) { fail = true; break; }
+                cj = f.pos;
+                const double lam = f.hit ? sr_invert(row[cj], row[cj + 1], sr_mass_within(f) / (t[cj + 1] - t[cj])) : 1.0;
+                xk = sr_place(t, n, cj, lam, ci, f0, f1);
+                lq = lq + log((f0 * row[ci] + f1 * row[ci + 1]) / f.total);
             }
             if (lane == 0) { id[k] = cj + 1; xs[k] = xk; }
             sr_chain_step(T.core[k] + (size_t)T.RM * ci, (size_t)T.RM, T.SS, q0, q1, n > 1, f0, f1, x, z, lane);

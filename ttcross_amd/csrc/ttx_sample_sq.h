@@ -204,7 +204,8 @@ __device__ inline double sq_p(const double *w, const double *Sc, double g, int i
 
 // One wave per sample, grid-stride, one launch per mode (0-based k).  ifix >= 0: the mode is held at that index and no p is formed.
 // Otherwise p(i) = w(i) (s(i) + g) from the sheet with lanes along i, the scan, the total, the search and the log term exactly
-// as in k_sm_draw; p is formed again in the search from the same numbers by the same expression.  The index goes to the sample's
+// as in k_sm_draw; p is formed again in the search from the same numbers by the same expression.  Both kernels keep the loops
+// written out, the cell samplers share them as sm_wave_search (ttx_sample.h says why).  The index goes to the sample's
 // row of ind, where k_sq_step finds it.  first also checks the sample's uniforms and clears its state; last writes logq and, for
 // a failed sample, the index row of zeros.  A failed sample is skipped by every later launch.
 __global__ __launch_bounds__(256) void k_sq_pick(int n, int k, int d, int ifix, const int *fixed, const double *w, const double *gk, const double *S, SqState st,

@@ -80,7 +80,7 @@ TTX_SQR_HD double sqr_invert(double q0, double qm, double q1, double sp)
 }
 
 #if defined(__HIPCC__)
-#include "ttx_sample_real.h"   // sr_chain_step, k_sr_count
+#include "ttx_sample_real.h"   // SrMode, sr_chain_step, sr_place, k_sr_count
 #include "ttx_sample_sq.h"     // SqPlan, the head pass kernels, TTX_SQ_SHEET, TTX_SQ_AUTO_FLOPS
 #include "ttx_ttops.h"         // dbl4
 
@@ -158,9 +158,6 @@ __global__ __launch_bounds__(256) void k_sqr_rows_mfma(const double *H, int l, i
     }
 }
 
-// one mode as k_sqr_pick and k_sqr_step take it.  held != 0: the mode is not drawn; its coordinate xh, its cell and the two hat
-// values were formed on the host (ttx_basis_entry).  noff: where the mode's nodes start in the call's node block
-struct SqrMode { int held, cell; double phi0, phi1, xh; size_t noff; };
 // what a sample carries from one launch to the next: logq, the failure flag, and from k_sqr_pick to k_sqr_step the hat cell and values
 struct SqrState { double *lq, *f0, *f1; int *fail, *ci; };
 
@@ -182,11 +179,12 @@ __device__ inline double sqr_mass(const double *Sc, const double *Cc, const doub
 }
 
 // One wave per sample, grid-stride, one launch per mode (0-based k), in the frame of k_sq_pick.  A held mode forms nothing: its
-// coordinate goes to x and 0 to cell.  Otherwise the cell masses from the two sheets with lanes along j, the scan, the total, the
-// search and the clamps exactly as in k_sr_draw; a cell's mass is formed again in the search from the same numbers by the same
-// expression.  The hat cell and values of the rounded x_k go to work space, where k_sqr_step finds them.  first also checks the
-// sample's uniforms and clears its state; last writes logq and, for a failed sample, the row of NaN in x and of zeros in cell.
-__global__ __launch_bounds__(256) void k_sqr_pick(int n, int k, int d, SqrMode M, const int *held, const double *nodes, const double *gk, const double *S, const double *Cs,
+// coordinate goes to x and 0 to cell.  Otherwise the cell masses from the two sheets with lanes along j, then k_sr_draw's
+// search, clamps and placement (sm_wave_search, sr_mass_within, sr_place); a cell's mass is formed again in the search's second pass
+// from the same numbers by the same expression.  The hat cell and values of the rounded x_k go to work space, where k_sqr_step finds
+// them.  first also checks the sample's uniforms and clears its state; last writes logq and, for a failed sample, the row of NaN in
+// x and of zeros in cell.
+__global__ __launch_bounds__(256) void k_sqr_pick(int n, int k, int d, SrMode M, const int *held, const double *nodes, const double *gk, const double *S, const double *Cs,
                                                   SqrState st, long long npts, const double *u, int first, int last, double *xo, int *cell, double *logq)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -195,66 +193,32 @@ __global__ __launch_bounds__(256) void k_sqr_pick(int n, int k, int d, SqrMode M
     for (long long p = (long long)blockIdx.x * nw + wave; p < npts; p += (long long)gridDim.x * nw) {
         bool fail;
         double lq = 0.0;
-        if (first) {
-            bool badu = false;
-            for (int i = lane; i < d; i += 64) { const double uu = u[(size_t)p * d + i]; badu |= !held[i] && !(uu >= 0.0); }   // NaN or negative
-            fail = __ballot(badu) != 0;
-        } else { fail = st.fail[p] != 0; lq = st.lq[p]; }
+        if (first) fail = sm_bad_u(u + (size_t)p * d, d, lane, [&](int i) { return held[i] != 0; }, (double *)nullptr);
+        else { fail = st.fail[p] != 0; lq = st.lq[p]; }
         int ci = M.cell, cj = -1;
         double f0 = M.phi0, f1 = M.phi1, xk = M.xh;
         if (!fail && !M.held) {
             const double *Sc = S + (size_t)p * n, *Cc = Cs + (size_t)p * n;
-            const double uk = u[(size_t)p * d + k], g = gk[0];
-            double carry = 0.0;
-            int lastc = -1;
-            for (int j0 = 0; j0 < nc; j0 += 64) {                               // the cell masses and their total C(n-2)
-                const double a = sqr_mass(Sc, Cc, t, g, j0 + lane, nc);
-                carry = __shfl(carry + sm_wave_scan(a, lane), 63);
-                const unsigned long long pos = __ballot(a > 0.0);
-                if (pos) lastc = j0 + 63 - __builtin_clzll(pos);
-            }
-            const double total = carry;
-            if (!(total > 0.0) || total == __builtin_inf() || lastc < 0) fail = true;       // 0, NaN or Inf
+            const double g = gk[0];
+            const auto mass = [&](int j) { return sqr_mass(Sc, Cc, t, g, j, nc); };
+            const SmFound f = sm_wave_search(nc, u[(size_t)p * d + k], lane, mass, mass);
+            if (!f.ok) fail = true;
             else {
-                const double tt = uk * total;
-                cj = lastc;                                                     // u >= 1, or no cell with tt < C(j): the largest cell with A > 0, lambda = 1
+                cj = f.pos;
                 double lam = 1.0;
-                if (uk < 1.0) {
-                    carry = 0.0;
-                    for (int j0 = 0; j0 < nc; j0 += 64) {
-                        const int j = j0 + lane;
-                        const double a = sqr_mass(Sc, Cc, t, g, j, nc), c = carry + sm_wave_scan(a, lane);
-                        const unsigned long long hit = __ballot(j < nc && a > 0.0 && tt < c);
-                        if (hit) {
-                            const int fl = __builtin_ctzll(hit);
-                            cj = j0 + fl;
-                            const double cprev = fl ? __shfl(c, fl - 1) : carry, aj = __shfl(a, fl);
-                            double s = tt - cprev;
-                            s = s > 0.0 ? s : 0.0;
-                            s = s < aj ? s : aj;
-                            double q0, qm, q1;
-                            (void)sqr_cell(Sc, Cc, t, g, cj, q0, qm, q1);
-                            lam = sqr_invert(q0, qm, q1, s / (t[cj + 1] - t[cj]));
-                            break;
-                        }
-                        carry = __shfl(c, 63);
-                    }
+                if (f.hit) {
+                    double q0, qm, q1;
+                    (void)sqr_cell(Sc, Cc, t, g, cj, q0, qm, q1);
+                    lam = sqr_invert(q0, qm, q1, sr_mass_within(f) / (t[cj + 1] - t[cj]));
                 }
-                const double tl = t[cj], tr = t[cj + 1];
-                xk = tl + lam * (tr - tl);
-                xk = xk > tl ? xk : tl;                                         // into the closed cell before the hat row is looked up
-                xk = xk < tr ? xk : tr;
-                ci = cj + ((cj + 1 <= n - 2 && xk >= tr) ? 1 : 0);             // TTX_BASIS_LINEAR's cell of the rounded x: it may be the next one
-                const double t0 = t[ci], t1 = t[ci + 1];
-                f1 = (xk - t0) / (t1 - t0);
-                f0 = 1.0 - f1;
+                xk = sr_place(t, n, cj, lam, ci, f0, f1);
                 const double s0 = Sc[ci], s1 = Sc[ci + 1], lim = sqrt(s0) * sqrt(s1);
                 double cc = Cc[ci];
                 cc = cc > lim ? lim : cc;
                 cc = cc < -lim ? -lim : cc;
                 double dens = (((f0 * f0) * s0 + ((2.0 * f0) * f1) * cc) + (f1 * f1) * s1) + g;
                 dens = dens > 0.0 ? dens : 0.0;
-                lq = lq + log(dens / total);
+                lq = lq + log(dens / f.total);
             }
         }
         if (lane == 0) {

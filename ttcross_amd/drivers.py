@@ -755,6 +755,30 @@ def sample_host(tt, u, w=None):
     return ind, logq, x[:, 0]
 
 
+def _seeded_uniforms(npts, d, dev):
+    """the (npts, d) uniforms of the sampling sub-commands, made ON the device from their fixed seed"""
+    import torch
+    g = torch.Generator(device=dev)
+    g.manual_seed(20240607)
+    u = torch.rand((npts, d), dtype=torch.float64, device=dev, generator=g)
+    torch.cuda.synchronize(dev)
+    return u
+
+
+def _timed_calls(call, last, repeats):
+    """One warm-up of call(), then `repeats` timed calls, each followed by last() (a sampler's *_last): the last result, the median
+    of the calls' ms, the medians of last()'s float figures, and the last record."""
+    import time
+    call()
+    ms, figs = [], []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        res = call()                          # synchronises before it returns
+        ms.append((time.perf_counter() - t0) * 1e3)
+        figs.append(last())
+    return res, float(np.median(ms)), {k: float(np.median([f[k] for f in figs])) for k in figs[0] if isinstance(figs[0][k], float)}, figs[-1]
+
+
 def run_sample(argv, device=0, repeats=5, tt=None, host_npts=1000):
     """sample WORKLOAD NPTS[,NPTS...]: the trains of the tijk sub-command, weights 1 / n, seeded uniforms made ON the device; per
     sample count one warm-up and the median of `repeats` calls through the device-pointer entry: the call, the two kernels
@@ -772,20 +796,9 @@ def run_sample(argv, device=0, repeats=5, tt=None, host_npts=1000):
     w = [np.full(int(nk), 1.0 / int(nk)) for nk in tt._n]
     out = []
     for npts in [int(float(x)) for x in argv[1].split(",")]:
-        g = torch.Generator(device=dev)
-        g.manual_seed(20240607)
-        u = torch.rand((npts, tt.d), dtype=torch.float64, device=dev, generator=g)
-        torch.cuda.synchronize(dev)
-        res = tt.sample(u, w)
-        ms, last = [], []
-        for _ in range(repeats):
-            t0 = time.perf_counter()
-            res = tt.sample(u, w)                  # synchronises before it returns
-            ms.append((time.perf_counter() - t0) * 1e3)
-            last.append(tt.sample_last())
-        head = float(np.median([x["ms_head"] for x in last]))
-        draw = float(np.median([x["ms_draw"] for x in last]))
-        by = last[0]["bytes_head"]
+        u = _seeded_uniforms(npts, tt.d, dev)
+        res, call_ms, med, last = _timed_calls(lambda: tt.sample(u, w), tt.sample_last, repeats)
+        head, draw, by = med["ms_head"], med["ms_draw"], last["bytes_head"]
         probe_ms, probe_by = E.k_residual_bench(max(int(by // 512), 1), 64, 20, device=device)
         tt.tijk_batch(res["ind"], "exact")
         tj = []
@@ -794,12 +807,12 @@ def run_sample(argv, device=0, repeats=5, tt=None, host_npts=1000):
             val = tt.tijk_batch(res["ind"], "exact")
             tj.append((time.perf_counter() - t0) * 1e3)
         tijk = float(np.median(tj))
-        r = dict(workload=workload, npts=npts, d=tt.d, max_rank=int(tt.ranks().max()), call_ms=float(np.median(ms)), head_ms=head,
+        r = dict(workload=workload, npts=npts, d=tt.d, max_rank=int(tt.ranks().max()), call_ms=call_ms, head_ms=head,
                  head_bytes=by, head_bytes_per_s=by / (head * 1e-3) if head > 0 else None,
                  probe_bytes_per_s=probe_by / (probe_ms * 1e-3) if probe_ms > 0 else None, draw_ms=draw,
                  draw_samples_per_s=npts / (draw * 1e-3) if draw > 0 else None, tijk_exact_ms=tijk,
                  tijk_points_per_s=npts / (tijk * 1e-3) if tijk > 0 else None, draw_over_tijk=draw / tijk if tijk > 0 else None,
-                 failed=last[-1]["failed"], val_is_tijk=bool(torch.equal(val, res["val"])), mean_logq=float(res["logq"].mean().item()))
+                 failed=last["failed"], val_is_tijk=bool(torch.equal(val, res["val"])), mean_logq=float(res["logq"].mean().item()))
         if r["head_bytes_per_s"] and r["probe_bytes_per_s"]:
             r["head_fraction_of_probe"] = r["head_bytes_per_s"] / r["probe_bytes_per_s"]
         print(json.dumps(r), flush=True)
@@ -879,24 +892,11 @@ def run_samplesq(argv, device=0, repeats=5, tt=None, host_npts=1000):
     tt = tt or (signed_density_train(device) if workload == "signed" else tijk_train(workload, device=device))
     dev = torch.device("cuda", device)
     w = [np.full(int(nk), 1.0 / int(nk)) for nk in tt._n]
-    g = torch.Generator(device=dev)
-    g.manual_seed(20240607)
-    u = torch.rand((npts, tt.d), dtype=torch.float64, device=dev, generator=g)
-    torch.cuda.synchronize(dev)
+    u = _seeded_uniforms(npts, tt.d, dev)
 
-    def timed(call, last):
-        call()
-        ms, figs = [], []
-        for _ in range(repeats):
-            t0 = time.perf_counter()
-            res = call()                          # synchronises before it returns
-            ms.append((time.perf_counter() - t0) * 1e3)
-            figs.append(last())
-        return res, float(np.median(ms)), {k: float(np.median([f[k] for f in figs])) for k in figs[0] if isinstance(figs[0][k], float)}, figs[-1]
-
-    res, call_ms, med, last = timed(lambda: tt.sample_sq(u, w, mode=mode), tt.sample_sq_last)
+    res, call_ms, med, last = _timed_calls(lambda: tt.sample_sq(u, w, mode=mode), tt.sample_sq_last, repeats)
     val = tt.tijk_batch(res["ind"], "exact")
-    _, s_ms, s_med, s_last = timed(lambda: tt.sample(u, w), tt.sample_last)
+    _, s_ms, s_med, s_last = _timed_calls(lambda: tt.sample(u, w), tt.sample_last, repeats)
     rows_ms = med["ms_rows"]
     out = [dict(workload=workload, npts=npts, d=tt.d, max_rank=int(tt.ranks().max()), mode_asked=mode, mode=last["mode"], call_ms=call_ms,
                 head_ms=med["ms_head"], rows_ms=rows_ms, pick_ms=med["ms_pick"], samples_per_s=npts / (call_ms * 1e-3), rows_flops=last["flops"],
@@ -989,22 +989,9 @@ def run_samplereal(argv, device=0, repeats=5, tt=None, host_npts=1000):
     work = sum(int(nk) * r[k + 1] + 2 * r[k] * r[k + 1] for k, nk in enumerate(tt._n)) / sum(int(nk) * r[k + 1] + r[k] * r[k + 1] for k, nk in enumerate(tt._n))
     out = []
     for npts in [int(float(x)) for x in argv[1].split(",")]:
-        g = torch.Generator(device=dev)
-        g.manual_seed(20240607)
-        u = torch.rand((npts, tt.d), dtype=torch.float64, device=dev, generator=g)
-        torch.cuda.synchronize(dev)
-        res = tt.sample_real(u, nodes)
-        ms, last = [], []
-        for _ in range(repeats):
-            t0 = time.perf_counter()
-            res = tt.sample_real(u, nodes)             # synchronises before it returns
-            ms.append((time.perf_counter() - t0) * 1e3)
-            last.append(tt.sample_real_last())
-        tt.sample(u, w)
-        sm = []
-        for _ in range(repeats):
-            tt.sample(u, w)
-            sm.append(tt.sample_last())
+        u = _seeded_uniforms(npts, tt.d, dev)
+        res, call_ms, med, last = _timed_calls(lambda: tt.sample_real(u, nodes), tt.sample_real_last, repeats)
+        _, _, sm, _ = _timed_calls(lambda: tt.sample(u, w), tt.sample_last, repeats)
         fin = ~torch.isnan(res["x"][:, 0])
         nb = min(int(fin.sum().item()), max(1000, int(2e13 / flops_pt)))     # the dense exact chain costs flops_pt per point: at most 2e13 flops are timed
         xs, vs = res["x"][fin][:nb].contiguous(), res["val"][fin][:nb]
@@ -1012,13 +999,12 @@ def run_samplereal(argv, device=0, repeats=5, tt=None, host_npts=1000):
         t0 = time.perf_counter()
         val = tt.basis_batch(xs, lin, "exact")
         basis = (time.perf_counter() - t0) * 1e3
-        head, draw = float(np.median([x["ms_head"] for x in last])), float(np.median([x["ms_draw"] for x in last]))
-        sm_head, sm_draw = float(np.median([x["ms_head"] for x in sm])), float(np.median([x["ms_draw"] for x in sm]))
-        rec = dict(workload=workload, npts=npts, d=tt.d, max_rank=max(r), call_ms=float(np.median(ms)), head_ms=head, draw_ms=draw,
+        head, draw, sm_head, sm_draw = med["ms_head"], med["ms_draw"], sm["ms_head"], sm["ms_draw"]
+        rec = dict(workload=workload, npts=npts, d=tt.d, max_rank=max(r), call_ms=call_ms, head_ms=head, draw_ms=draw,
                    draw_samples_per_s=npts / (draw * 1e-3) if draw > 0 else None, sample_head_ms=sm_head, sample_draw_ms=sm_draw,
                    draw_over_sample_draw=draw / sm_draw if sm_draw > 0 else None, work_ratio=work,
                    time_over_work=draw / sm_draw / work if sm_draw > 0 else None, basis_exact_npts=nb, basis_exact_ms=basis,
-                   draw_us_per_sample=draw * 1e3 / npts, basis_exact_us_per_point=basis * 1e3 / nb if nb else None, failed=last[-1]["failed"],
+                   draw_us_per_sample=draw * 1e3 / npts, basis_exact_us_per_point=basis * 1e3 / nb if nb else None, failed=last["failed"],
                    val_is_basis=bool(torch.all(val == vs).item()), mean_logq=float(res["logq"][fin].mean().item()))
         print(json.dumps(rec), flush=True)
         out.append(rec)
@@ -1044,7 +1030,6 @@ def run_samplesqreal(argv, device=0, repeats=5, tt=None):
     importance weight |g(x)| / q(x) over its mean and the effective sample size under sample_real() on the train and under
     sample_sq_real() on the cross approximation of sqrt |T| (of_trains, sqrtabs), with and without a defensive term.  One JSON line each."""
     import json
-    import time
     import torch
     torch.cuda.init()          # a torch that brings its own HIP runtime must initialise its device before the engine's library does
     workload, npts = argv[0], int(float(argv[1]))
@@ -1055,27 +1040,14 @@ def run_samplesqreal(argv, device=0, repeats=5, tt=None):
     nodes = [np.linspace(0.0, 1.0, int(nk)) for nk in tt._n]
     lin = [("linear", t) for t in nodes]
     w = [np.full(int(nk), 1.0 / int(nk)) for nk in tt._n]
-    g = torch.Generator(device=dev)
-    g.manual_seed(20240607)
-    u = torch.rand((npts, tt.d), dtype=torch.float64, device=dev, generator=g)
-    torch.cuda.synchronize(dev)
+    u = _seeded_uniforms(npts, tt.d, dev)
 
-    def timed(call, last):
-        call()
-        ms, figs = [], []
-        for _ in range(repeats):
-            t0 = time.perf_counter()
-            res = call()                          # synchronises before it returns
-            ms.append((time.perf_counter() - t0) * 1e3)
-            figs.append(last())
-        return res, float(np.median(ms)), {k: float(np.median([f[k] for f in figs])) for k in figs[0] if isinstance(figs[0][k], float)}, figs[-1]
-
-    res, call_ms, med, last = timed(lambda: tt.sample_sq_real(u, nodes, mode=mode), tt.sample_sq_real_last)
+    res, call_ms, med, last = _timed_calls(lambda: tt.sample_sq_real(u, nodes, mode=mode), tt.sample_sq_real_last, repeats)
     fin = ~torch.isnan(res["x"][:, 0])
     nb = min(int(fin.sum().item()), 100000)
     val = tt.basis_batch(res["x"][fin][:nb].contiguous(), lin, "exact")
-    _, q_ms, q_med, q_last = timed(lambda: tt.sample_sq(u, w, mode=mode), tt.sample_sq_last)
-    _, r_ms, r_med, r_last = timed(lambda: tt.sample_real(u, nodes), tt.sample_real_last)
+    _, q_ms, q_med, q_last = _timed_calls(lambda: tt.sample_sq(u, w, mode=mode), tt.sample_sq_last, repeats)
+    _, r_ms, r_med, r_last = _timed_calls(lambda: tt.sample_real(u, nodes), tt.sample_real_last, repeats)
     rows_ms, q_rows_ms = med["ms_rows"], q_med["ms_rows"]
     out = [dict(workload=workload, npts=npts, d=tt.d, max_rank=int(tt.ranks().max()), mode_asked=mode, mode=last["mode"], call_ms=call_ms,
                 head_ms=med["ms_head"], rows_ms=rows_ms, pick_ms=med["ms_pick"], samples_per_s=npts / (call_ms * 1e-3), rows_flops=last["flops"],

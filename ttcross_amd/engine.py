@@ -966,7 +966,77 @@ class TTCross:
         names = {v: k for k, v in EVAL_MODES.items()}
         return dict(ms_table=mt.value, ms_chain=mc.value, flops=fl.value, mode=names.get(md.value))
 
-    # ---- samples from the resident train (include/ttx.h: ttx_sample) -------------------------------------
+    # ---- samples from the resident train (include/ttx.h: ttx_sample and its three siblings) --------------
+    # the outputs of the index samplers and of the real samplers: name, a row of d per sample (else one number), dtype, always allocated
+    _SAMPLE_IND = (("ind", True, "int32", True), ("logq", False, "float64", False), ("val", False, "float64", False))
+    _SAMPLE_REAL = (("x", True, "float64", True), ("cell", True, "int32", False), ("logq", False, "float64", False), ("val", False, "float64", False))
+
+    def _sample_call(self, who, host, dev, table, u_or_npts, seed, want, middle):
+        """The one call path of sample, sample_sq, sample_real and sample_sq_real (who: the public method's name, the prefix of
+        every message).  host, dev: the C entry for host arrays and its _dev form; table: the outputs (_SAMPLE_IND, _SAMPLE_REAL),
+        those not always allocated only when named in want; middle(): the ctypes arguments between u and the outputs, formed
+        after the check of want.  u_or_npts: a count (uniforms from numpy.random.default_rng(seed)), an array, or a torch tensor:
+        one on the engine's device is passed by pointer and gives torch tensors there, one on the host goes through numpy."""
+        names = tuple(t[0] for t in table)
+        bad = set(want) - set(names)
+        if bad:
+            raise ValueError(f"{who}: unknown output {sorted(bad)}")
+        mid = middle()
+        on_torch = type(u_or_npts).__module__.split(".")[0] == "torch"
+        if on_torch and u_or_npts.is_cuda:
+            import torch
+            u = u_or_npts
+            if u.device.index != self.device:
+                raise ValueError(f"{who}: the tensor lies on {u.device}, the engine on device {self.device}")
+            if u.dtype != torch.float64 or not u.is_contiguous() or u.dim() != 2 or u.shape[1] != self.d:
+                raise ValueError(f"{who}: a contiguous float64 tensor of shape (npts, {self.d}) expected")
+            npts = u.shape[0]
+            out = {name: torch.empty((npts, self.d) if row else npts, dtype=getattr(torch, dt), device=u.device) if always or name in want else None
+                   for name, row, dt, always in table}
+            torch.cuda.current_stream(u.device).synchronize()        # the engine runs on a stream of its own
+            _check(dev(self._h, npts, c_void_p(u.data_ptr()), *mid, *[c_void_p(out[k].data_ptr()) if out[k] is not None else None for k in names]))
+            return {k: out[k] for k in names if k in want}
+        if on_torch:
+            u_or_npts = u_or_npts.numpy()
+        if np.ndim(u_or_npts) == 0:
+            npts = int(u_or_npts)
+            if npts < 0:
+                raise ValueError(f"{who}: a negative count")
+            u = np.random.default_rng(seed).random((npts, self.d))
+        else:
+            u = np.ascontiguousarray(u_or_npts, dtype=np.float64)
+            if u.ndim != 2 or u.shape[1] != self.d:
+                raise ValueError(f"{who}: an array of shape (npts, {self.d}) expected")
+        npts = u.shape[0]
+        out = {name: np.zeros((npts, self.d) if row else npts, dtype=dt) if always or name in want else None for name, row, dt, always in table}
+        _check(host(self._h, npts, _dp(u), *mid, *[(_ip if dt == "int32" else _dp)(out[name]) for name, _, dt, _ in table]))
+        if on_torch:
+            import torch
+            return {k: torch.from_numpy(out[k]) for k in names if k in want}
+        return {k: out[k] for k in names if k in want}
+
+    def _held_entries(self, v, who, what, dtype):
+        """fixed (int32) or cond (float64) of a sampler: None, or d entries"""
+        if v is None:
+            return None
+        a = np.ascontiguousarray(v, dtype=dtype).ravel()
+        if a.size != self.d:
+            raise ValueError(f"{who}: {self.d} {what} entries expected")
+        return a
+
+    def _draw_last(self, entry):
+        """dict(ms_head, bytes_head, ms_draw, failed) from ttx_sample_last or ttx_sample_real_last"""
+        a, b, c, n = c_double(), c_double(), c_double(), c_int64()
+        _check(entry(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(n)))
+        return dict(ms_head=a.value, bytes_head=b.value, ms_draw=c.value, failed=int(n.value))
+
+    def _rows_last(self, entry):
+        """dict(ms_head, ms_rows, ms_pick, flops, failed, mode) from ttx_sample_sq_last or ttx_sample_sq_real_last"""
+        a, b, c, fl, n, md = c_double(), c_double(), c_double(), c_double(), c_int64(), c_int32()
+        _check(entry(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(fl), ctypes.byref(n), ctypes.byref(md)))
+        names = {v: k for k, v in EVAL_MODES.items()}
+        return dict(ms_head=a.value, ms_rows=b.value, ms_pick=c.value, flops=fl.value, failed=int(n.value), mode=names.get(md.value))
+
     def sample(self, u_or_npts, w=None, fixed=None, seed=None, want=("ind", "logq", "val")):
         """Indices drawn from the train by sequential conditional sampling on the device (include/ttx.h: ttx_sample): for a train
         and weights without sign changes they follow |T(i)| w(i) / Z.  u_or_npts: uniforms of shape (npts, d), or a count, for
@@ -977,55 +1047,12 @@ class TTCross:
         A contiguous float64 torch tensor on the engine's device is passed by pointer (ttx_sample_dev) and gives torch tensors
         on that device: ind can go straight into tijk_batch."""
         L = load_library()
-        bad = set(want) - {"ind", "logq", "val"}
-        if bad:
-            raise ValueError(f"sample: unknown output {sorted(bad)}")
-        wa = self._weights(w, "sample")
-        fx = None
-        if fixed is not None:
-            fx = np.ascontiguousarray(fixed, dtype=np.int32).ravel()
-            if fx.size != self.d:
-                raise ValueError(f"sample: {self.d} fixed entries expected")
-        if type(u_or_npts).__module__.split(".")[0] == "torch":
-            import torch
-            u = u_or_npts
-            if not u.is_cuda:
-                return {k: torch.from_numpy(v) for k, v in self.sample(u.numpy(), w, fixed, seed, want).items()}
-            if u.device.index != self.device:
-                raise ValueError(f"sample: the tensor lies on {u.device}, the engine on device {self.device}")
-            if u.dtype != torch.float64 or not u.is_contiguous() or u.dim() != 2 or u.shape[1] != self.d:
-                raise ValueError(f"sample: a contiguous float64 tensor of shape (npts, {self.d}) expected")
-            npts = u.shape[0]
-            ind = torch.empty((npts, self.d), dtype=torch.int32, device=u.device)
-            lq = torch.empty(npts, dtype=torch.float64, device=u.device) if "logq" in want else None
-            va = torch.empty(npts, dtype=torch.float64, device=u.device) if "val" in want else None
-            torch.cuda.current_stream(u.device).synchronize()        # the engine runs on a stream of its own
-            _check(L.ttx_sample_dev(self._h, npts, c_void_p(u.data_ptr()), _dp(wa), _ip(fx), c_void_p(ind.data_ptr()),
-                                    c_void_p(lq.data_ptr()) if lq is not None else None, c_void_p(va.data_ptr()) if va is not None else None))
-            out = dict(ind=ind, logq=lq, val=va)
-            return {k: out[k] for k in ("ind", "logq", "val") if k in want}
-        if np.ndim(u_or_npts) == 0:
-            npts = int(u_or_npts)
-            if npts < 0:
-                raise ValueError("sample: a negative count")
-            u = np.random.default_rng(seed).random((npts, self.d))
-        else:
-            u = np.ascontiguousarray(u_or_npts, dtype=np.float64)
-            if u.ndim != 2 or u.shape[1] != self.d:
-                raise ValueError(f"sample: an array of shape (npts, {self.d}) expected")
-        npts = u.shape[0]
-        ind = np.zeros((npts, self.d), dtype=np.int32)
-        lq = np.zeros(npts) if "logq" in want else None
-        va = np.zeros(npts) if "val" in want else None
-        _check(L.ttx_sample(self._h, npts, _dp(u), _dp(wa), _ip(fx), _ip(ind), _dp(lq), _dp(va)))
-        out = dict(ind=ind, logq=lq, val=va)
-        return {k: out[k] for k in ("ind", "logq", "val") if k in want}
+        return self._sample_call("sample", L.ttx_sample, L.ttx_sample_dev, self._SAMPLE_IND, u_or_npts, seed, want,
+                                 lambda: (_dp(self._weights(w, "sample")), _ip(self._held_entries(fixed, "sample", "fixed", np.int32))))
 
     def sample_last(self):
         """dict(ms_head, bytes_head, ms_draw, failed) of the last sample() on this engine (include/ttx.h: ttx_sample_last)"""
-        a, b, c, n = c_double(), c_double(), c_double(), c_int64()
-        _check(load_library().ttx_sample_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(n)))
-        return dict(ms_head=a.value, bytes_head=b.value, ms_draw=c.value, failed=int(n.value))
+        return self._draw_last(load_library().ttx_sample_last)
 
     # ---- samples from the square of the resident train (include/ttx.h: ttx_sample_sq) ---------------------
     def sample_sq(self, u_or_npts, w=None, fixed=None, gamma=0.0, mode="auto", seed=None, want=("ind", "logq", "val")):
@@ -1037,62 +1064,21 @@ class TTCross:
         sample_sq_last() counts the failed samples.  A contiguous float64 torch tensor on the engine's device is passed by
         pointer (ttx_sample_sq_dev) and gives torch tensors on that device."""
         L = load_library()
-        bad = set(want) - {"ind", "logq", "val"}
-        if bad:
-            raise ValueError(f"sample_sq: unknown output {sorted(bad)}")
-        md = _eval_mode(mode)
-        wa = self._weights(w, "sample_sq")
-        fx = None
-        if fixed is not None:
-            fx = np.ascontiguousarray(fixed, dtype=np.int32).ravel()
-            if fx.size != self.d:
-                raise ValueError(f"sample_sq: {self.d} fixed entries expected")
-        if type(u_or_npts).__module__.split(".")[0] == "torch":
-            import torch
-            u = u_or_npts
-            if not u.is_cuda:
-                return {k: torch.from_numpy(v) for k, v in self.sample_sq(u.numpy(), w, fixed, gamma, mode, seed, want).items()}
-            if u.device.index != self.device:
-                raise ValueError(f"sample_sq: the tensor lies on {u.device}, the engine on device {self.device}")
-            if u.dtype != torch.float64 or not u.is_contiguous() or u.dim() != 2 or u.shape[1] != self.d:
-                raise ValueError(f"sample_sq: a contiguous float64 tensor of shape (npts, {self.d}) expected")
-            npts = u.shape[0]
-            ind = torch.empty((npts, self.d), dtype=torch.int32, device=u.device)
-            lq = torch.empty(npts, dtype=torch.float64, device=u.device) if "logq" in want else None
-            va = torch.empty(npts, dtype=torch.float64, device=u.device) if "val" in want else None
-            torch.cuda.current_stream(u.device).synchronize()        # the engine runs on a stream of its own
-            _check(L.ttx_sample_sq_dev(self._h, npts, c_void_p(u.data_ptr()), _dp(wa), _ip(fx), float(gamma), md, c_void_p(ind.data_ptr()),
-                                       c_void_p(lq.data_ptr()) if lq is not None else None, c_void_p(va.data_ptr()) if va is not None else None))
-            out = dict(ind=ind, logq=lq, val=va)
-            return {k: out[k] for k in ("ind", "logq", "val") if k in want}
-        if np.ndim(u_or_npts) == 0:
-            npts = int(u_or_npts)
-            if npts < 0:
-                raise ValueError("sample_sq: a negative count")
-            u = np.random.default_rng(seed).random((npts, self.d))
-        else:
-            u = np.ascontiguousarray(u_or_npts, dtype=np.float64)
-            if u.ndim != 2 or u.shape[1] != self.d:
-                raise ValueError(f"sample_sq: an array of shape (npts, {self.d}) expected")
-        npts = u.shape[0]
-        ind = np.zeros((npts, self.d), dtype=np.int32)
-        lq = np.zeros(npts) if "logq" in want else None
-        va = np.zeros(npts) if "val" in want else None
-        _check(L.ttx_sample_sq(self._h, npts, _dp(u), _dp(wa), _ip(fx), float(gamma), md, _ip(ind), _dp(lq), _dp(va)))
-        out = dict(ind=ind, logq=lq, val=va)
-        return {k: out[k] for k in ("ind", "logq", "val") if k in want}
+
+        def middle():
+            md = _eval_mode(mode)
+            return _dp(self._weights(w, "sample_sq")), _ip(self._held_entries(fixed, "sample_sq", "fixed", np.int32)), float(gamma), md
+        return self._sample_call("sample_sq", L.ttx_sample_sq, L.ttx_sample_sq_dev, self._SAMPLE_IND, u_or_npts, seed, want, middle)
 
     def sample_sq_last(self):
         """dict(ms_head, ms_rows, ms_pick, flops, failed, mode) of the last sample_sq() on this engine (include/ttx.h:
         ttx_sample_sq_last); mode is "exact" or "mfma" (None before the first call)"""
-        a, b, c, fl, n, md = c_double(), c_double(), c_double(), c_double(), c_int64(), c_int32()
-        _check(load_library().ttx_sample_sq_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(fl), ctypes.byref(n), ctypes.byref(md)))
-        names = {v: k for k, v in EVAL_MODES.items()}
-        return dict(ms_head=a.value, ms_rows=b.value, ms_pick=c.value, flops=fl.value, failed=int(n.value), mode=names.get(md.value))
+        return self._rows_last(load_library().ttx_sample_sq_last)
 
     # ---- real-valued samples from the interpolant of the train (include/ttx.h: ttx_sample_real) -----------
     def _node_rows(self, nodes, who):
-        """nodes: one array for all modes or a list of d -> (the d arrays, the ctypes row pointers)"""
+        """nodes: one array for all modes or a list of d -> (the d arrays, the ctypes row pointers).  A ctypes array holds addresses,
+        not numpy's owners, so the pointers carry the arrays along (rowp.rows): they live as long as the pointers do."""
         if not isinstance(nodes, (list, tuple)) or (len(nodes) and np.ndim(nodes[0]) == 0):
             nodes = [nodes] * self.d
         if len(nodes) != self.d:
@@ -1101,7 +1087,9 @@ class TTCross:
         for k, t in enumerate(rows):
             if t.ndim != 1 or t.size != int(self._n[k]):
                 raise ValueError(f"{who}: {int(self._n[k])} nodes expected for mode {k + 1} (got shape {t.shape})")
-        return rows, (POINTER(c_double) * self.d)(*[_dp(t) for t in rows])
+        rowp = (POINTER(c_double) * self.d)(*[_dp(t) for t in rows])
+        rowp.rows = rows
+        return rows, rowp
 
     def sample_real(self, u_or_npts, nodes, cond=None, seed=None, want=("x", "cell", "logq", "val")):
         """Real points drawn from the piecewise-linear interpolant of the train of grid values, on the device (include/ttx.h:
@@ -1114,58 +1102,16 @@ class TTCross:
         negative u) has a row of NaN in x, cell 0, logq NaN and val 0; sample_real_last() counts them.  A contiguous float64 torch
         tensor on the engine's device is passed by pointer (ttx_sample_real_dev) and gives torch tensors on that device: x can go
         straight into basis_batch."""
-        L, names = load_library(), ("x", "cell", "logq", "val")
-        bad = set(want) - set(names)
-        if bad:
-            raise ValueError(f"sample_real: unknown output {sorted(bad)}")
-        rows, rowp = self._node_rows(nodes, "sample_real")
-        ca = None
-        if cond is not None:
-            ca = np.ascontiguousarray(cond, dtype=np.float64).ravel()
-            if ca.size != self.d:
-                raise ValueError(f"sample_real: {self.d} cond entries expected")
-        if type(u_or_npts).__module__.split(".")[0] == "torch":
-            import torch
-            u = u_or_npts
-            if not u.is_cuda:
-                return {k: torch.from_numpy(v) for k, v in self.sample_real(u.numpy(), nodes, cond, seed, want).items()}
-            if u.device.index != self.device:
-                raise ValueError(f"sample_real: the tensor lies on {u.device}, the engine on device {self.device}")
-            if u.dtype != torch.float64 or not u.is_contiguous() or u.dim() != 2 or u.shape[1] != self.d:
-                raise ValueError(f"sample_real: a contiguous float64 tensor of shape (npts, {self.d}) expected")
-            npts = u.shape[0]
-            x = torch.empty((npts, self.d), dtype=torch.float64, device=u.device)
-            ce = torch.empty((npts, self.d), dtype=torch.int32, device=u.device) if "cell" in want else None
-            lq = torch.empty(npts, dtype=torch.float64, device=u.device) if "logq" in want else None
-            va = torch.empty(npts, dtype=torch.float64, device=u.device) if "val" in want else None
-            torch.cuda.current_stream(u.device).synchronize()        # the engine runs on a stream of its own
-            _check(L.ttx_sample_real_dev(self._h, npts, c_void_p(u.data_ptr()), rowp, _dp(ca), c_void_p(x.data_ptr()), *[
-                c_void_p(t.data_ptr()) if t is not None else None for t in (ce, lq, va)]))
-            out = dict(x=x, cell=ce, logq=lq, val=va)
-            return {k: out[k] for k in names if k in want}
-        if np.ndim(u_or_npts) == 0:
-            npts = int(u_or_npts)
-            if npts < 0:
-                raise ValueError("sample_real: a negative count")
-            u = np.random.default_rng(seed).random((npts, self.d))
-        else:
-            u = np.ascontiguousarray(u_or_npts, dtype=np.float64)
-            if u.ndim != 2 or u.shape[1] != self.d:
-                raise ValueError(f"sample_real: an array of shape (npts, {self.d}) expected")
-        npts = u.shape[0]
-        x = np.zeros((npts, self.d))
-        ce = np.zeros((npts, self.d), dtype=np.int32) if "cell" in want else None
-        lq = np.zeros(npts) if "logq" in want else None
-        va = np.zeros(npts) if "val" in want else None
-        _check(L.ttx_sample_real(self._h, npts, _dp(u), rowp, _dp(ca), _dp(x), _ip(ce), _dp(lq), _dp(va)))
-        out = dict(x=x, cell=ce, logq=lq, val=va)
-        return {k: out[k] for k in names if k in want}
+        L = load_library()
+
+        def middle():
+            _, rowp = self._node_rows(nodes, "sample_real")       # rowp holds the node arrays until the call is over
+            return rowp, _dp(self._held_entries(cond, "sample_real", "cond", np.float64))
+        return self._sample_call("sample_real", L.ttx_sample_real, L.ttx_sample_real_dev, self._SAMPLE_REAL, u_or_npts, seed, want, middle)
 
     def sample_real_last(self):
         """dict(ms_head, bytes_head, ms_draw, failed) of the last sample_real() on this engine (include/ttx.h: ttx_sample_real_last)"""
-        a, b, c, n = c_double(), c_double(), c_double(), c_int64()
-        _check(load_library().ttx_sample_real_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(n)))
-        return dict(ms_head=a.value, bytes_head=b.value, ms_draw=c.value, failed=int(n.value))
+        return self._draw_last(load_library().ttx_sample_real_last)
 
     # ---- real-valued samples from the square of the interpolant (include/ttx.h: ttx_sample_sq_real) -------
     def sample_sq_real(self, u_or_npts, nodes, cond=None, gamma=0.0, mode="auto", seed=None, want=("x", "cell", "logq", "val")):
@@ -1177,61 +1123,18 @@ class TTCross:
         gamma >= 0 is the defensive term; mode is "exact", "mfma" or "auto" (only the sums of the rows depend on it).
         sample_sq_real_last() counts the failed samples.  A contiguous float64 torch tensor on the engine's device is passed by
         pointer (ttx_sample_sq_real_dev) and gives torch tensors on that device."""
-        L, names = load_library(), ("x", "cell", "logq", "val")
-        bad = set(want) - set(names)
-        if bad:
-            raise ValueError(f"sample_sq_real: unknown output {sorted(bad)}")
-        md = _eval_mode(mode)
-        rows, rowp = self._node_rows(nodes, "sample_sq_real")
-        ca = None
-        if cond is not None:
-            ca = np.ascontiguousarray(cond, dtype=np.float64).ravel()
-            if ca.size != self.d:
-                raise ValueError(f"sample_sq_real: {self.d} cond entries expected")
-        if type(u_or_npts).__module__.split(".")[0] == "torch":
-            import torch
-            u = u_or_npts
-            if not u.is_cuda:
-                return {k: torch.from_numpy(v) for k, v in self.sample_sq_real(u.numpy(), nodes, cond, gamma, mode, seed, want).items()}
-            if u.device.index != self.device:
-                raise ValueError(f"sample_sq_real: the tensor lies on {u.device}, the engine on device {self.device}")
-            if u.dtype != torch.float64 or not u.is_contiguous() or u.dim() != 2 or u.shape[1] != self.d:
-                raise ValueError(f"sample_sq_real: a contiguous float64 tensor of shape (npts, {self.d}) expected")
-            npts = u.shape[0]
-            x = torch.empty((npts, self.d), dtype=torch.float64, device=u.device)
-            ce = torch.empty((npts, self.d), dtype=torch.int32, device=u.device) if "cell" in want else None
-            lq = torch.empty(npts, dtype=torch.float64, device=u.device) if "logq" in want else None
-            va = torch.empty(npts, dtype=torch.float64, device=u.device) if "val" in want else None
-            torch.cuda.current_stream(u.device).synchronize()        # the engine runs on a stream of its own
-            _check(L.ttx_sample_sq_real_dev(self._h, npts, c_void_p(u.data_ptr()), rowp, _dp(ca), float(gamma), md, c_void_p(x.data_ptr()), *[
-                c_void_p(t.data_ptr()) if t is not None else None for t in (ce, lq, va)]))
-            out = dict(x=x, cell=ce, logq=lq, val=va)
-            return {k: out[k] for k in names if k in want}
-        if np.ndim(u_or_npts) == 0:
-            npts = int(u_or_npts)
-            if npts < 0:
-                raise ValueError("sample_sq_real: a negative count")
-            u = np.random.default_rng(seed).random((npts, self.d))
-        else:
-            u = np.ascontiguousarray(u_or_npts, dtype=np.float64)
-            if u.ndim != 2 or u.shape[1] != self.d:
-                raise ValueError(f"sample_sq_real: an array of shape (npts, {self.d}) expected")
-        npts = u.shape[0]
-        x = np.zeros((npts, self.d))
-        ce = np.zeros((npts, self.d), dtype=np.int32) if "cell" in want else None
-        lq = np.zeros(npts) if "logq" in want else None
-        va = np.zeros(npts) if "val" in want else None
-        _check(L.ttx_sample_sq_real(self._h, npts, _dp(u), rowp, _dp(ca), float(gamma), md, _dp(x), _ip(ce), _dp(lq), _dp(va)))
-        out = dict(x=x, cell=ce, logq=lq, val=va)
-        return {k: out[k] for k in names if k in want}
+        L = load_library()
+
+        def middle():
+            md = _eval_mode(mode)
+            _, rowp = self._node_rows(nodes, "sample_sq_real")
+            return rowp, _dp(self._held_entries(cond, "sample_sq_real", "cond", np.float64)), float(gamma), md
+        return self._sample_call("sample_sq_real", L.ttx_sample_sq_real, L.ttx_sample_sq_real_dev, self._SAMPLE_REAL, u_or_npts, seed, want, middle)
 
     def sample_sq_real_last(self):
         """dict(ms_head, ms_rows, ms_pick, flops, failed, mode) of the last sample_sq_real() on this engine (include/ttx.h:
         ttx_sample_sq_real_last); mode is "exact" or "mfma" (None before the first call)"""
-        a, b, c, fl, n, md = c_double(), c_double(), c_double(), c_double(), c_int64(), c_int32()
-        _check(load_library().ttx_sample_sq_real_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(fl), ctypes.byref(n), ctypes.byref(md)))
-        names = {v: k for k, v in EVAL_MODES.items()}
-        return dict(ms_head=a.value, ms_rows=b.value, ms_pick=c.value, flops=fl.value, failed=int(n.value), mode=names.get(md.value))
+        return self._rows_last(load_library().ttx_sample_sq_real_last)
 
     # ---- the largest elements of the resident train (include/ttx.h: ttx_topk) ----------------------------
     def topk(self, k, which="abs", fixed=None, mode="auto"):
