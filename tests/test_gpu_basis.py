@@ -27,6 +27,7 @@ SHAPES = {
     "mixed": ([7, 2, 51, 1, 9], [1, 3, 17, 5, 4, 1]),
     "two_rows_mr5": ([4, 5, 3, 2], [1, 16, 33, 65, 1]),           # rank 65: two rows per lane in exact mode, MR = 5 in MFMA mode
     "bond128": ([2, 2, 2], [1, 128, 128, 1]),
+    "mr6_mr8": ([3, 2, 3], [1, 96, 113, 1]),                      # MR = 6 and, below 128, MR = 8
     "d2": ([5, 7], [1, 3, 1]),
 }
 NPTS = (1, 15, 17, 255, 257, 300)

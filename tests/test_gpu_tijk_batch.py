@@ -58,6 +58,7 @@ RANDOM_TRAINS = {
     "r64": ([5] * 6, _chain(6, 64)),
     "r65": ([4] * 5, _chain(5, 65)),
     "r128": ([4] * 4, _chain(4, 128)),
+    "r80_81": ([3, 3, 3, 3], [1, 80, 81, 80, 1]),                     # one step below and one above the 64 KB slice image
     "unequal_ranks": ([3, 5, 2, 7, 4, 6, 3, 5], [1, 3, 17, 64, 65, 9, 128, 2, 1]),
 }
 

@@ -1,5 +1,5 @@
 """The operations on the resident train share one table of device work space, one table uploader and one set of timers per engine
-(ttcross_amd/csrc/ttx_engine.hip: SC_*, OpMeta, OpTimer).  Whatever ran before on an engine, and whatever size it left a slot at,
+(ttcross_amd/csrc/ttx_engine.hip: SC_*, OpMeta, OpTimer; what a call reserves and launches: ttx_op_plan.h).  Whatever ran before on an engine, and whatever size it left a slot at,
 must not enter a result: every call of an interleaved sequence equals the same call on fresh engines bit for bit, and the figures
 a family reports (contract_modesum, algebra_last, eval_last_mode) are those of its own last call.
 

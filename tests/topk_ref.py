@@ -160,6 +160,8 @@ SHAPES = {
     "d3_r128": ((20, 130, 20), (1, 128, 128, 1)),
     "rank1": ((9,) * 5, (1,) * 6),
     "peaked": ((9,) * 5, (1, 3, 3, 3, 3, 1)),
+    "d3_r17_33": ((4, 3, 4), (1, 17, 33, 1)),                   # left ranks in 17..32 and 33..64: the score kernel's tiers 2 and 4
+    "d3_r112_113": ((3, 3, 3), (1, 112, 113, 1)),               # either side of the score kernel's 64 KB of LDS
 }
 SEEDS = {name: 100 + j for j, name in enumerate(SHAPES)}
 KS = (1, 4, 5, 16, 17, 64, 100, 256)

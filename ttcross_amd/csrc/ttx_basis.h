@@ -16,12 +16,6 @@
 #pragma once
 #include "ttx_coscoeff.h"   // ttx_cos, TTX_TRIG_MAX, TTX_COSCOEFF_PI, TTX_CC_HD: host and device
 
-// break-even of TTX_EVAL_AUTO in flops per call (2 npts sum r0 n r1).  Measured (profiles/basis_mi355x.txt): on the coscoeff6 train
-// (d = 6) exact wins at 2.1e8 flops and MFMA at 2.1e9; on the D_64 train (d = 63) MFMA wins at 6.3e8 already.  The value lies inside
-// the first bracket and below the second figure.  Provisional for long chains: below 6.3e8 flops the D_64 crossover is not measured
-// (both modes are then bound by their 2 d launches, not by the flops).
-#define TTX_BS_AUTO_FLOPS 4.0e8
-
 // w of a TTX_BASIS_COS mode
 TTX_CC_HD double ttx_basis_cos_w(double a, double b) { return TTX_COSCOEFF_PI / (b - a); }
 
@@ -118,9 +112,7 @@ __global__ __launch_bounds__(256) void k_bs_exact(EvTrain T, int i, long long c,
 // next panel are issued before the MFMAs of the current one and stored to the other buffer after them, one barrier per panel.
 // Every MFMA takes a = U(16 m + col, j, k) from LDS and b = phi_j(pt) * x_k(pt), formed in registers; the accumulators run over all
 // j and k of the mode, the new state is written once.  Lanes of padded points carry b = 0 and store nothing.
-#define TTX_BS_KPAN 16
-__host__ __device__ constexpr int bs_ct(int MR) { return MR <= 2 ? 4 : MR <= 4 ? 2 : 1; }
-__host__ __device__ inline size_t bs_gemm_lds(int q0) { return sizeof(double) * 2 * (size_t)ev_lda(q0) * TTX_BS_KPAN; }
+// TTX_BS_KPAN, bs_ct and bs_gemm_lds are in ttx_op_plan.h, shared with the call's plan
 
 template <int MR>
 __global__ __launch_bounds__(256) void k_bs_gemm(EvTrain T, int i, int c, const double *phi, size_t ldphi, const double *X, double *Z, double *out)

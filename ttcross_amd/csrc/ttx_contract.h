@@ -13,9 +13,9 @@
 // Plain fp64, no running exponent (as k_quad_*): a train whose partial products leave the double range over- or underflows.
 // Every sum has a fixed order (no atomics, no dependence on the order in which workgroups finish): results repeat bit for bit.
 #pragma once
-#include <hip/hip_runtime.h>
-#include "ttx_ttops.h"     // dbl4
+#include <stddef.h>
 
+// the tables are plain C++ a host compiler accepts (ttx_op_plan.h fills them)
 struct CtCore {                     // one source core (0-based mode k)
     const double *src;
     size_t moff, woff;              // offset of M_k (compact, leading dimension r0) in the M buffer; of the mode's weights / outputs
@@ -35,6 +35,10 @@ struct CtKeep {                     // one kept core: dst (q0 x n x q1) = P (q0 
 
 #define TTX_CT_WCH 1024             // weights staged per pass of k_ct_modesum (one pass for modes up to this size)
 #define TTX_CT_LDS 8192             // doubles of LDS k_ct_runs owns (64 KB)
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#include "ttx_ttops.h"     // dbl4
 
 // M_k(a, b) = sum_j w_k(j) G_k(a, j, b) for every contracted core: 256 threads = ta lanes along a x 256 / ta columns b.
 // Four partial sums per element (j mod 4) keep four loads in flight; they are added in a fixed order.
@@ -245,3 +249,4 @@ __global__ __launch_bounds__(256) void k_ct_marg(int d, const CtCore *cores, lon
     for (int o = 32; o; o >>= 1) acc = acc + __shfl_xor(acc, o);
     if (lane == 0) out[item] = acc;
 }
+#endif

@@ -154,12 +154,49 @@ struct OpTimer {
 };
 enum { TM_MODESUM, TM_ALG, TM_HEAD, TM_DRAW, TM_APPLY,             // k_ct_modesum, the algebra launch, k_sm_head, the k_sm_draw / k_sr_draw of a chunk, k_ma_apply
        TM_GRAM, TM_SCORE, TM_SELECT,                               // ttx_topk: the Gram chain, a mode's scoring launch, a mode's selection and advance
-       TM_RS_SKETCH, TM_N };                                       // ttx_lincomb_round: the right-to-left pass (the GEMMs, QRs and advances alternate d - 1 times: RsMarks on ttx_engine::rs_ev)
+       TM_RS_SKETCH, TM_N };                                       // ttx_lincomb_round: the right-to-left pass (the GEMMs, QRs and advances alternate d - 1 times: OpMarks)
+// Events between the phases of a call whose phases alternate many times inside one enqueued stretch, which one OpTimer pair per phase
+// cannot time: mark(phase) closes the stretch since the previous mark; after a synchronise, sum() adds every stretch to ms[its phase]
+// (DISCARD: to nothing) and empties the chain.  The events are the engine's (ttx_engine::op_ev): created once, reused by every call.
+struct OpMarks {
+    enum { DISCARD = -1 };
+    std::vector<hipEvent_t> &pool;
+    std::vector<int> phase;
+    explicit OpMarks(std::vector<hipEvent_t> &p) : pool(p) {}
+    int mark(hipStream_t s, int ph)
+    {
+        if (phase.size() == pool.size()) { hipEvent_t e; HIPCHECK(hipEventCreate(&e)); pool.push_back(e); }
+        HIPCHECK(hipEventRecord(pool[phase.size()], s));
+        phase.push_back(ph);
+        return TTX_OK;
+    }
+    int sum(double *ms)
+    {
+        for (size_t x = 1; x < phase.size(); x++) {
+            if (phase[x] == DISCARD) continue;
+            float t = 0.f;
+            HIPCHECK(hipEventElapsedTime(&t, pool[x - 1], pool[x]));
+            ms[phase[x]] += t;
+        }
+        phase.clear();
+        return TTX_OK;
+    }
+};
 
-// the figures of a sampler's last call: ttx_sample and ttx_sample_real fill head, bytes and draw, the squared samplers head, rows, pick,
-// flops and mode
+// the figures of an operation's last call, one record each, handed out by the operation's _last entry
+// samplers: ttx_sample and ttx_sample_real fill head, bytes and draw, the squared samplers head, rows, pick, flops and mode
 enum { SMP_GRID, SMP_REAL, SMP_SQ, SMP_SQ_REAL, SMP_N };
 struct SampleLast { double ms_head = 0.0, bytes = 0.0, ms_draw = 0.0, ms_rows = 0.0, ms_pick = 0.0, flops = 0.0; int64_t failed = 0; int mode = -1; };
+struct CtLast { double ms = 0.0, bytes = 0.0; };                               // the mode-sum kernel of ttx_contract / ttx_marginals
+struct AlgLast { double ms = 0.0, rd = 0.0, wr = 0.0; };                       // ttx_lincomb / ttx_hadamard with this engine first
+struct MaLast { double ms = 0.0, rd = 0.0, wr = 0.0, flops = 0.0; int mode = -1; };    // the apply launch of ttx_mode_apply
+struct TkLast { double ms_gram = 0.0, ms_score = 0.0, ms_select = 0.0, flops = 0.0; int mode = -1; };
+struct RsLast {                                                                 // ttx_lincomb_round with this engine first
+    double ms[4] = {0.0, 0.0, 0.0, 0.0}, flops = 0.0;                           // sketch, gemm, qr, advance
+    std::vector<int32_t> l;                                                     // its sketch ranks l(0 .. d)
+    int mode = -1;
+};
+struct BsLast { double ms[2] = {0.0, 0.0}, flops = 0.0; int mode = -1; };      // ttx_basis_batch / ttx_basis_tab: table launches, chain launches
 
 struct DevFun;                          // a loaded device integrand (TTX_FUN_DEVICE), defined with slot_eval
 struct TrainFun;                        // the operands and the combiner of TTX_FUN_TRAINS, defined with slot_eval
@@ -254,20 +291,14 @@ struct ttx_engine {
     OpTimer timer[TM_N];
     int ncu = 0;                        // compute units of the device, asked for once (dev_ncu)
     int ev_last_mode = -1;              // TTX_EVAL_* the last batch ran with
-    double ct_ms = 0.0, ct_bytes = 0.0;                 // the mode-sum kernel of the last ttx_contract / ttx_marginals
-    double alg_ms = 0.0, alg_rd = 0.0, alg_wr = 0.0;    // the last ttx_lincomb / ttx_hadamard with this engine first
     SampleLast smp[SMP_N];                              // the last call of each of the four samplers, each its own
-    double ma_ms = 0.0, ma_rd = 0.0, ma_wr = 0.0, ma_flops = 0.0;   // the apply launch of the last ttx_mode_apply
-    int ma_mode = -1;
-    double tk_ms_gram = 0.0, tk_ms_score = 0.0, tk_ms_select = 0.0, tk_flops = 0.0;   // the last ttx_topk
-    int tk_mode = -1;
-    double rs_ms[4] = {0.0, 0.0, 0.0, 0.0}, rs_flops = 0.0;                    // the last ttx_lincomb_round with this engine first: sketch, gemm, qr, advance
-    std::vector<int32_t> rs_l;                                                  // its sketch ranks l(0 .. d)
-    int rs_mode = -1;
-    std::vector<hipEvent_t> rs_ev;                                              // the event chain of its left-to-right pass (RsMarks); ttx_sample_sq's rows and picks use it too
-    double bs_ms_tab = 0.0, bs_ms_chain = 0.0, bs_flops = 0.0;                 // the last ttx_basis_batch / ttx_basis_tab: table launches, chain launches
-    int bs_mode = -1;
-    std::vector<hipEvent_t> bs_ev;                                              // its event chain: tables and chain steps alternate (bs_mark)
+    CtLast ct;
+    AlgLast alg;
+    MaLast ma;
+    TkLast tk;
+    RsLast rs;
+    BsLast bs;
+    std::vector<hipEvent_t> op_ev;                      // OpMarks' events: ttx_lincomb_round, the squared samplers, the basis evaluations
 };
 
 // the process-wide pool of the host integrand (ttx_host_pool.h): engines driven from different host threads take turns on it
@@ -762,8 +793,7 @@ extern "C" void ttx_destroy(ttx_engine *h)
         if (h->P.hreq) (void)hipHostFree(h->P.hreq);
     }
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
-    for (auto &e : h->rs_ev) (void)hipEventDestroy(e);
-    for (auto &e : h->bs_ev) (void)hipEventDestroy(e);
+    for (auto &e : h->op_ev) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -2621,6 +2651,28 @@ static int buf_reserve(ttx_engine *h, int slot, size_t bytes)
     return TTX_OK;
 }
 template <class T> static T *buf(ttx_engine *h, int slot) { return (T *)h->scratch[slot].p; }
+// the slots a plan names, in its order; a plan gives 0 bytes to a slot its call does not use
+struct SlotBytes { int slot; size_t bytes; };
+static int buf_reserve(ttx_engine *h, std::initializer_list<SlotBytes> slots)
+{
+    for (const SlotBytes &s : slots) if (s.bytes) if (int rc = buf_reserve(h, s.slot, s.bytes)) return rc;
+    return TTX_OK;
+}
+// the one place a launch's dynamic LDS goes above the default ceiling: where its plan says so
+static int op_lds_raise(ttx_engine *h, const void *kernel, const OpLds &l) { return l.raise ? ensure_lds(h, kernel, l.bytes) : TTX_OK; }
+// A plan's tier as the template argument of a launch: f(Tier<MR>()).  The kernels exist for MR = 1, 2, 4 and 8 (rank_tier); EVERY: for
+// each MR of 1 .. 8 (k_bs_gemm)
+template <int MR> using Tier = std::integral_constant<int, MR>;
+template <bool EVERY = false, class F> static int with_tier(int tier, F f)
+{
+    if constexpr (EVERY) {
+        if (tier == 3) return f(Tier<3>());
+        if (tier == 5) return f(Tier<5>());
+        if (tier == 6) return f(Tier<6>());
+        if (tier == 7) return f(Tier<7>());
+    }
+    return tier == 1 ? f(Tier<1>()) : tier == 2 ? f(Tier<2>()) : tier == 4 ? f(Tier<4>()) : f(Tier<8>());
+}
 namespace {
 // device image of a call's tables: arrays appended at 16-byte boundaries in a host vector of the engine, uploaded in one copy
 struct OpMeta {
@@ -2853,17 +2905,6 @@ static int tf_eval_list(ttx_engine *h, int64_t npts, const int32_t *ind, double 
 }
 
 // ---- the train at a batch of multi-indices (ttx_eval.h) -------------------------------------------------------------------------
-// TTX_EVAL_AUTO, a cost model fitted to the measurement in DESIGN.md 4.5, with w = sum r(k-1) r(k) (slice elements a point touches).
-// The MFMA path pays a fixed cost whatever the batch (four launches per mode and the staging of the slices): 1.46 / 1.47 / 9.2 ms at
-// (d, w) = (63, 6.8 k) / (63, 62 k) / (255, 1.04 M), modelled as 23 us d + 3.2 ns w.  Per point it saves 27.7 / 106 / 1317 ns against
-// the exact kernel, modelled as 1.25 ps w + 0.286 ns d.  MFMA is taken where the saving covers the fixed cost; the model's break-evens
-// are 55 k / 17 k / 6.7 k points on the three trains, the measured ones 52 k / 14 k / 7 k.
-static int ev_auto(const ttx_engine *h, int64_t npts)
-{
-    double w = 0.0;
-    for (int k = 1; k <= h->d; k++) w += (double)h->rfinal[k - 1] * h->rfinal[k];
-    return (double)npts * (1.25e-12 * w + 0.286e-9 * h->d) >= 23.0e-6 * h->d + 3.2e-9 * w ? TTX_EVAL_MFMA : TTX_EVAL_EXACT;
-}
 // core pointers, ranks and mode sizes of the train as it stands now, in one device block
 static int ev_train(ttx_engine *h, EvTrain *T)
 {
@@ -2872,7 +2913,7 @@ static int ev_train(ttx_engine *h, EvTrain *T)
     std::vector<int> r(h->rfinal.begin(), h->rfinal.begin() + d + 1), n(h->n1.begin() + 1, h->n1.begin() + 1 + d);
     for (int k = 1; k <= d; k++) cp[k - 1] = core_dev(h, k);
     const int rmax = std::max(1, *std::max_element(r.begin(), r.end()));
-    if (rmax > 128) return fail(TTX_EINVAL, "ttx_ijk_batch: ranks up to 128 only (got %d)", rmax);
+    if (rmax > 128) return fail(TTX_EINVAL, "ttx_ijk_batch: ranks up to 128 only (got %d)", rmax);      // kept: this name, whichever entry called
     OpMeta meta(h->train_host);
     const size_t o_core = meta.put(cp), o_r = meta.put(r), o_n = meta.put(n);
     char *m;
@@ -2881,88 +2922,72 @@ static int ev_train(ttx_engine *h, EvTrain *T)
     T->core = (const double *const *)(m + o_core); T->r = (const int *)(m + o_r); T->n = (const int *)(m + o_n);
     return TTX_OK;
 }
-template <int MR>
-static int ev_gemm_launch(ttx_engine *h, const EvTrain &T, int i, int nmode, int grid, size_t lds, const int *off, const int *tile, const int *perm, const double *X, double *Z)
+static EvPlan ev_plan(ttx_engine *h, EvStage st, int64_t npts, int32_t dd, int32_t mode)
 {
-    if (lds > 64 * 1024) { if (int rc = ensure_lds(h, reinterpret_cast<const void *>(k_ev_gemm<MR>), lds)) return rc; }     // a slice image above the default 64 KB
-    hipLaunchKernelGGL(k_ev_gemm<MR>, dim3(grid), dim3(256), lds, h->stream, T, i, nmode, off, tile, perm, X, Z);
-    return TTX_OK;
+    return ev_plan(h->d, h->n1.data() + 1, h->rfinal.data(), h->NM, dev_ncu(h), st, npts, dd, mode, env_chunk("TTX_IJK_CHUNK", op_chunk_default(h->RM)));
 }
 // c points whose index rows (and, for ttx_value_batch, flags) are on the device -> out (device), enqueued on the engine's stream
-static int ev_run(ttx_engine *h, const EvTrain &T, int mode, int c, const int *ind, const int *flag, double *out)
+static int ev_run(ttx_engine *h, const EvPlan &pl, const EvTrain &T, int c, const int *ind, const int *flag, double *out)
 {
-    const int d = h->d, ncu = dev_ncu(h);
-    if (mode == TTX_EVAL_EXACT) {
-        // one wave per point, 4 waves per workgroup; the grid is capped at 8 workgroups per CU and strides over the batch (66 VGPRs:
-        // 7 waves per SIMD are resident); the chain is a dependent sequence, throughput comes from the waves in flight
-        const size_t lds = 4 * sizeof(double) * (2 * (size_t)T.ldx + (((size_t)d + 1) >> 1));
-        const int grid = (int)std::min<long long>(((long long)c + 3) / 4, (long long)ncu * 8);
-        hipLaunchKernelGGL(k_ev_exact, dim3(grid), dim3(256), lds, h->stream, T, (long long)c, ind, flag, out);
+    const int d = h->d;
+    if (pl.eff == TTX_EVAL_EXACT) {
+        // the grid strides over the batch (66 VGPRs: 7 waves per SIMD are resident); the chain is a dependent sequence, throughput
+        // comes from the waves in flight
+        hipLaunchKernelGGL(k_ev_exact, dim3(pl.g_wave(c)), dim3(256), pl.exact_lds, h->stream, T, (long long)c, ind, flag, out);
         return TTX_OK;
     }
     const size_t NM = h->NM;
-    int rc;
-    if ((rc = buf_reserve(h, SC_XA, sizeof(double) * (size_t)c * T.ldx)) || (rc = buf_reserve(h, SC_XB, sizeof(double) * (size_t)c * T.ldx)) ||
-        (rc = buf_reserve(h, SC_SORT, sizeof(int) * (2 * (size_t)c + 4 * NM + 8)))) return rc;
     double *X = buf<double>(h, SC_XA), *Z = buf<double>(h, SC_XB);
     int *valid = buf<int>(h, SC_SORT), *perm = valid + c, *cnt = perm + c, *off = cnt + NM, *tile = off + NM + 1, *cur = tile + NM + 1;
-    hipLaunchKernelGGL(k_ev_init, dim3(std::min((c + 3) / 4, ncu * 8)), dim3(256), 0, h->stream, T, c, ind, flag, valid, X, out);
-    const int nb = std::max(1, std::min((c + 1023) / 1024, 1024));
+    hipLaunchKernelGGL(k_ev_init, dim3(pl.g_wave(c)), dim3(256), 0, h->stream, T, c, ind, flag, valid, X, out);
+    const int nb = pl.g_sort(c);
     for (int i = d - 2; i >= 0; i--) {
-        const int nmode = h->n1[i + 1], q0 = h->rfinal[i], q1 = h->rfinal[i + 1];
-        const size_t hl = nmode <= TTX_EV_LDSHIST ? sizeof(int) * nmode : 0;
-        HIPCHECK(hipMemsetAsync(cnt, 0, sizeof(int) * nmode, h->stream));
-        hipLaunchKernelGGL(k_ev_hist, dim3(nb), dim3(256), hl, h->stream, d, i, nmode, c, ind, (const int *)valid, cnt);
-        hipLaunchKernelGGL(k_ev_scan, dim3(1), dim3(1024), 0, h->stream, nmode, (const int *)cnt, off, tile, cur);
-        hipLaunchKernelGGL(k_ev_scatter, dim3(nb), dim3(256), hl, h->stream, d, i, nmode, c, ind, (const int *)valid, cur, perm);
-        const int grid = c / TTX_EV_TP + std::min(nmode, c);
-        const size_t lds = ev_gemm_lds(q0, q1);
-        if ((rc = q0 <= 16 ? ev_gemm_launch<1>(h, T, i, nmode, grid, lds, off, tile, perm, X, Z)
-                : q0 <= 32 ? ev_gemm_launch<2>(h, T, i, nmode, grid, lds, off, tile, perm, X, Z)
-                : q0 <= 64 ? ev_gemm_launch<4>(h, T, i, nmode, grid, lds, off, tile, perm, X, Z)
-                           : ev_gemm_launch<8>(h, T, i, nmode, grid, lds, off, tile, perm, X, Z))) return rc;
+        const EvStep &s = pl.step[i];
+        HIPCHECK(hipMemsetAsync(cnt, 0, sizeof(int) * s.nmode, h->stream));
+        hipLaunchKernelGGL(k_ev_hist, dim3(nb), dim3(256), s.hist_lds, h->stream, d, i, s.nmode, c, ind, (const int *)valid, cnt);
+        hipLaunchKernelGGL(k_ev_scan, dim3(1), dim3(1024), 0, h->stream, s.nmode, (const int *)cnt, off, tile, cur);
+        hipLaunchKernelGGL(k_ev_scatter, dim3(nb), dim3(256), s.hist_lds, h->stream, d, i, s.nmode, c, ind, (const int *)valid, cur, perm);
+        if (int rc = with_tier(s.tier, [&](auto mr) {
+                constexpr int MR = decltype(mr)::value;
+                if (int rc = op_lds_raise(h, reinterpret_cast<const void *>(k_ev_gemm<MR>), s.lds)) return rc;
+                hipLaunchKernelGGL(k_ev_gemm<MR>, dim3(pl.g_gemm(i, c)), dim3(256), s.lds.bytes, h->stream, T, i, s.nmode, (const int *)off, (const int *)tile, (const int *)perm,
+                                   (const double *)X, Z);
+                return (int)TTX_OK;
+            })) return rc;
         std::swap(X, Z);
     }
-    hipLaunchKernelGGL(k_ev_final, dim3(std::max(1, std::min((c + 255) / 256, 1024))), dim3(256), 0, h->stream, c, T.ldx, (const int *)valid, (const double *)X, out);
-    return TTX_OK;
-}
-static int ev_mode(ttx_engine *h, const char *who, int64_t npts, int32_t mode, int *eff)
-{
-    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
-    *eff = mode == TTX_EVAL_AUTO ? ev_auto(h, npts) : mode;
+    hipLaunchKernelGGL(k_ev_final, dim3(pl.g_final(c)), dim3(256), 0, h->stream, c, T.ldx, (const int *)valid, (const double *)X, out);
     return TTX_OK;
 }
 extern "C" int ttx_eval_last_mode(const ttx_engine *h) { return h ? h->ev_last_mode : -1; }
 
-// the three entries differ in where a chunk's index rows come from and where its values go
-enum EvStage { EV_ON_DEVICE, EV_HOST_INDEX, EV_HOST_COORD };   // caller's device pointers; host rows staged; host coordinates -> k_ev_digits
+// the three entries differ in where a chunk's index rows come from and where its values go (EvStage)
 // `in`: npts x d index rows (int32) or, EV_HOST_COORD, npts x dd coordinates (double); lib/tt.f90:702-728 forms the digits, then dtt_ijk
 static int ev_batch(ttx_engine *h, const char *who, EvStage st, int64_t npts, int32_t dd, const void *in, double *out, int32_t mode)
 {
-    int rc = tt_prepare(h, st == EV_HOST_COORD ? "dtt_value" : "dtt_ijk"), eff = 0;
+    int rc = tt_prepare(h, st == EV_HOST_COORD ? "dtt_value" : "dtt_ijk");
     if (rc) return rc;
     if (npts < 0 || (npts > 0 && (!in || !out))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
     if (st == EV_HOST_COORD && dd < 1) return fail(TTX_EINVAL, "%s: %d coordinates per point", who, dd);
-    if ((rc = ev_mode(h, who, npts, mode, &eff))) return rc;
+    if (!op_mode_known(mode)) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    const EvPlan pl = ev_plan(h, st, npts, dd, mode);
     // an asymmetry of the entries, kept: an empty ttx_value_batch leaves ev_last_mode as it was, the two index entries record theirs
-    if (npts == 0) { if (st != EV_HOST_COORD) h->ev_last_mode = eff; return TTX_OK; }
+    if (npts == 0) { if (st != EV_HOST_COORD) h->ev_last_mode = pl.eff; return TTX_OK; }
     const int32_t *ind = (const int32_t *)in;
     const double *x = (const double *)in;
     // int(xx) of the reference is defined below 2^31 only
     if (st == EV_HOST_COORD)
         for (size_t e = 0; e < (size_t)npts * dd; e++) if (!(x[e] < 2147483648.0)) return fail(TTX_EINVAL, "%s: coordinate %g of point %lld is not below 2^31", who, x[e], (long long)(e / dd));
     EvTrain T;
-    if ((rc = ev_train(h, &T))) return rc;
-    const size_t chunk = std::min<size_t>(env_chunk("TTX_IJK_CHUNK", h->RM <= 64 ? (size_t)1 << 18 : (size_t)1 << 17), (size_t)npts), d = h->d;
-    // the chunk bounds the work space: two state buffers of chunk x max rank doubles on the MFMA path, the staging blocks of the host entries
-    if (st != EV_ON_DEVICE && ((rc = buf_reserve(h, SC_IND, sizeof(int) * chunk * d)) || (rc = buf_reserve(h, SC_OUT, sizeof(double) * chunk)))) return rc;
-    if (st == EV_HOST_COORD && ((rc = buf_reserve(h, SC_FLAG, sizeof(int) * chunk)) || (rc = buf_reserve(h, SC_X, sizeof(double) * chunk * dd)))) return rc;
+    if ((rc = ev_train(h, &T)) ||
+        (rc = buf_reserve(h, {{SC_IND, pl.b_ind}, {SC_OUT, pl.b_out}, {SC_FLAG, pl.b_flag}, {SC_X, pl.b_x}, {SC_XA, pl.b_xa}, {SC_XB, pl.b_xb}, {SC_SORT, pl.b_sort}}))) return rc;
+    const size_t d = h->d;
     int *sind = buf<int>(h, SC_IND), *sflag = st == EV_HOST_COORD ? buf<int>(h, SC_FLAG) : nullptr;
     double *sout = buf<double>(h, SC_OUT), *sx = buf<double>(h, SC_X);
-    for (int64_t o = 0; o < npts; o += (int64_t)chunk) {
-        const int c = (int)std::min<int64_t>((int64_t)chunk, npts - o);
+    for (int64_t o = 0; o < npts; o += (int64_t)pl.chunk) {
+        const int c = (int)std::min<int64_t>((int64_t)pl.chunk, npts - o);
         if (st == EV_ON_DEVICE) {
-            if ((rc = ev_run(h, T, eff, c, ind + (size_t)o * d, nullptr, out + o))) return rc;
+            if ((rc = ev_run(h, pl, T, c, ind + (size_t)o * d, nullptr, out + o))) return rc;
             continue;                                                           // one wait after the last chunk
         }
         if (st == EV_HOST_INDEX) HIPCHECK(hipMemcpyAsync(sind, ind + (size_t)o * d, sizeof(int) * (size_t)c * d, hipMemcpyHostToDevice, h->stream));
@@ -2970,13 +2995,13 @@ static int ev_batch(ttx_engine *h, const char *who, EvStage st, int64_t npts, in
             HIPCHECK(hipMemcpyAsync(sx, x + (size_t)o * dd, sizeof(double) * (size_t)c * dd, hipMemcpyHostToDevice, h->stream));
             hipLaunchKernelGGL(k_ev_digits, g1((size_t)c), dim3(256), 0, h->stream, (int)d, T.n, (int)dd, (long long)c, (const double *)sx, sind, sflag);
         }
-        if ((rc = ev_run(h, T, eff, c, sind, sflag, sout))) return rc;
+        if ((rc = ev_run(h, pl, T, c, sind, sflag, sout))) return rc;
         HIPCHECK(hipMemcpyAsync(out + o, sout, sizeof(double) * c, hipMemcpyDeviceToHost, h->stream));
         HIPCHECK(hipStreamSynchronize(h->stream));                              // the staging blocks are reused by the next chunk
     }
     if (st == EV_ON_DEVICE) HIPCHECK(hipStreamSynchronize(h->stream));
     HIPCHECK(hipGetLastError());
-    h->ev_last_mode = eff;
+    h->ev_last_mode = pl.eff;
     return TTX_OK;
 }
 extern "C" int ttx_ijk_batch_dev(ttx_engine *h, int64_t npts, const int32_t *ind_dev, double *out_dev, int32_t mode)
@@ -3002,33 +3027,11 @@ extern "C" int ttx_det_fallbacks(const ttx_engine *h) { return h ? h->det_fallba
 extern "C" int ttx_fun_id(const ttx_engine *h) { return h ? h->cfg.fun_id : -1; }
 extern "C" int ttx_set_profile(ttx_engine *h, int on) { if (!h) return fail(TTX_EINVAL, "null"); h->profile = on != 0; return TTX_OK; }
 // ---- chosen modes contracted with rank-1 weights (ttx_contract.h) ---------------------------------------------------------------
-namespace {
-struct CtPlan {
-    std::vector<CtCore> cores;          // every source core
-    std::vector<CtTile> tiles;          // mode-sum tiles of the contracted ones
-    std::vector<int> r;                 // r(0:d)
-    std::vector<size_t> moff;
-    size_t msize = 0, wsize = 0;
-    double bytes = 0.0;                 // 8 sum r0 n r1 over the contracted cores
-};
-}
+// the plan of all modes (ttx_op_plan.h) with the cores' addresses as they stand now
 static void ct_plan(ttx_engine *h, const std::vector<char> &contracted, CtPlan &pl)
 {
-    const int d = h->d;
-    pl.r.assign(h->rfinal.begin(), h->rfinal.begin() + d + 1);
-    pl.cores.resize(d); pl.moff.assign(d, 0);
-    for (int k = 0; k < d; k++) {
-        CtCore &c = pl.cores[k];
-        c.src = core_dev(h, k + 1); c.r0 = pl.r[k]; c.n = h->n1[k + 1]; c.r1 = pl.r[k + 1];
-        c.ta = 1; while (c.ta < 64 && c.ta < c.r0) c.ta <<= 1;
-        c.woff = pl.wsize; pl.wsize += c.n;
-        c.moff = 0;
-        if (!contracted[k]) continue;
-        c.moff = pl.moff[k] = pl.msize; pl.msize += (size_t)c.r0 * c.r1;
-        pl.bytes += 8.0 * c.r0 * c.n * c.r1;
-        const int tb = 256 / c.ta;
-        for (int b0 = 0; b0 < c.r1; b0 += tb) for (int a0 = 0; a0 < c.r0; a0 += c.ta) pl.tiles.push_back(CtTile{k, a0, b0, 0});
-    }
+    ct_plan(h->d, h->n1.data() + 1, h->rfinal.data(), contracted, pl);
+    for (int k = 0; k < h->d; k++) pl.cores[k].src = core_dev(h, k + 1);
 }
 // weights to the device (NULL: ones) and the mode-sum launch, between the timer's events where the caller reports its time
 static int ct_modesum(ttx_engine *h, const CtPlan &pl, const double *w, const CtCore *dcores, const CtTile *dtiles, OpTimer *tm)
@@ -3050,8 +3053,8 @@ static int ct_finish(ttx_engine *h, const CtPlan &pl)
 {
     HIPCHECK(hipStreamSynchronize(h->stream));
     HIPCHECK(hipGetLastError());
-    h->ct_ms = 0.0; h->ct_bytes = pl.bytes;
-    return pl.tiles.empty() ? TTX_OK : h->timer[TM_MODESUM].ms(&h->ct_ms);
+    h->ct = CtLast{0.0, pl.bytes};
+    return pl.tiles.empty() ? TTX_OK : h->timer[TM_MODESUM].ms(&h->ct.ms);
 }
 // everything of ttx_contract that works on the new engine e: a failure leaves e to the caller to destroy
 static int ct_fill(ttx_engine *h, ttx_engine *e, const std::vector<int> &kept, const double *w)
@@ -3153,7 +3156,7 @@ extern "C" int ttx_marginals(ttx_engine *h, const double *w, double *out)
 extern "C" int ttx_contract_modesum(const ttx_engine *h, double *ms, double *bytes)
 {
     if (!h || !ms || !bytes) return fail(TTX_EINVAL, "ttx_contract_modesum: null argument");
-    *ms = h->ct_ms; *bytes = h->ct_bytes;
+    *ms = h->ct.ms; *bytes = h->ct.bytes;
     return TTX_OK;
 }
 
@@ -3204,19 +3207,19 @@ static int sr_check_nodes_cond(const ttx_engine *h, const char *who, const doubl
 // mode and gamma of the squared samplers
 static int sq_check_mode_gamma(const char *who, int32_t mode, double gamma)
 {
-    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    if (!op_mode_known(mode)) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
     if (!(gamma >= 0.0) || !std::isfinite(gamma)) return fail(TTX_EINVAL, "%s: gamma must be a finite number >= 0 (got %g)", who, gamma);
     return TTX_OK;
 }
 // the chunk of a call of npts >= 1 samples (TTX_SAMPLE_CHUNK, 2^18 by default); asks the device nothing
 static size_t sm_chunk(int64_t npts) { return std::min<size_t>(env_chunk("TTX_SAMPLE_CHUNK", (size_t)1 << 18), (size_t)npts); }
-// That chunk and the cap of the grid of a draw: one wave per sample, 4 waves per workgroup, 8 workgroups per CU as k_ev_exact's.  dcnt
+// That chunk and the cap of the grid of a draw: one wave per sample (wave_grid).  dcnt
 // stays with the caller, who reserves SC_CNT
 static SmLoop sm_loop(ttx_engine *h, int64_t npts)
 {
     SmLoop L;
     L.chunk = sm_chunk(npts);
-    L.gridmax = (int)std::min<long long>(((long long)L.chunk + 3) / 4, (long long)dev_ncu(h) * 8);
+    L.gridmax = wave_grid((long long)L.chunk, dev_ncu(h));
     return L;
 }
 // Inputs: pl, the caller's plan of all modes (ct_plan); held[k] != 0: mode k gets no head table; eff: the effective weights of all modes
@@ -3267,7 +3270,7 @@ static int sm_prepare(ttx_engine *h, const char *who, int64_t npts, const CtPlan
     P.growlen = P.nrow > TTX_SM_LDSROW ? (size_t)P.nrow : 0;
     P.lds = 4 * sizeof(double) * (2 * (size_t)P.T.ldx + wave_extra + P.ldsrow);
     if (P.lds > TTX_LDS_DEVICE) return fail(TTX_EINVAL, "%s: %d modes need %zu bytes of LDS per workgroup (160 KB at most)", who, d, P.lds);
-    if (P.lds > 64 * 1024 && (rc = ensure_lds(h, draw_kernel, P.lds))) return rc;
+    if ((rc = op_lds_raise(h, draw_kernel, op_lds(P.lds)))) return rc;
     if (P.growlen && (rc = buf_reserve(h, SC_ROW, sizeof(double) * P.growlen * 4 * P.loop.gridmax))) return rc;
     P.grow = P.growlen ? buf<double>(h, SC_ROW) : nullptr;
     return TTX_OK;
@@ -3475,14 +3478,14 @@ static int alg_launch(ttx_engine *h, ttx_engine *e, const std::vector<AlgBlk> &b
     char *dm;
     if ((rc = meta.upload(h, SC_META, &dm))) return rc;
     OpTimer &tm = h->timer[TM_ALG];
-    h->alg_ms = 0.0; h->alg_rd = rd; h->alg_wr = wr;
+    h->alg = AlgLast{0.0, rd, wr};
     if ((rc = tm.start(h->stream))) return rc;
     if (hadamard) hipLaunchKernelGGL(k_alg_hadamard, dim3((unsigned)tiles), dim3(256), 0, h->stream, (const AlgBlk *)dm, (int)blks.size(), e->RM, e->P.SS);
     else hipLaunchKernelGGL(k_alg_lincomb, dim3((unsigned)tiles), dim3(256), 0, h->stream, (const AlgBlk *)dm, (int)blks.size(), e->RM, e->P.SS);
     if ((rc = tm.stop(h->stream))) return rc;
     HIPCHECK(hipStreamSynchronize(h->stream));
     HIPCHECK(hipGetLastError());
-    return tm.ms(&h->alg_ms);
+    return tm.ms(&h->alg.ms);
 }
 static int alg_lincomb_fill(int m, const double *coef, ttx_engine *const *x, ttx_engine *e)
 {
@@ -3581,33 +3584,11 @@ extern "C" int ttx_hadamard(ttx_engine *x, ttx_engine *y, ttx_engine **out)
 extern "C" int ttx_algebra_last(const ttx_engine *h, double *ms, double *bytes_read, double *bytes_written)
 {
     if (!h || !ms || !bytes_read || !bytes_written) return fail(TTX_EINVAL, "ttx_algebra_last: null argument");
-    *ms = h->alg_ms; *bytes_read = h->alg_rd; *bytes_written = h->alg_wr;
+    *ms = h->alg.ms; *bytes_read = h->alg.rd; *bytes_written = h->alg.wr;
     return TTX_OK;
 }
 
 // ---- a rounded sum of resident trains (ttx_roundsum.h) ----------------------------------------------------------------------------
-namespace {
-// events between the phases of the left-to-right pass: mark(phase) closes the stretch since the previous mark; after a synchronise,
-// sum() adds every stretch to its phase (1 gemm, 2 qr, 3 advance).  One OpTimer pair per phase cannot do it: the phases alternate
-// d - 1 times inside one enqueued call.
-struct RsMarks {
-    std::vector<hipEvent_t> &pool;          // the engine's (ttx_engine::rs_ev): created once, reused by every call, destroyed with the engine
-    std::vector<int> phase;
-    explicit RsMarks(std::vector<hipEvent_t> &p) : pool(p) {}
-    int mark(hipStream_t s, int ph)
-    {
-        if (phase.size() == pool.size()) { hipEvent_t e; HIPCHECK(hipEventCreate(&e)); pool.push_back(e); }
-        HIPCHECK(hipEventRecord(pool[phase.size()], s));
-        phase.push_back(ph);
-        return TTX_OK;
-    }
-    int sum(double *ms)
-    {
-        for (size_t x = 1; x < phase.size(); x++) { float t = 0.f; HIPCHECK(hipEventElapsedTime(&t, pool[x - 1], pool[x])); ms[phase[x]] += t; }
-        return TTX_OK;
-    }
-};
-}
 // everything of ttx_lincomb_round that works on the new engine e (ranks l): a failure leaves e to the caller to destroy.  All launches go
 // to x[0]'s stream: e runs on it for the length of the call (qr(), unpack_core and svd_impl launch on their engine's stream).
 static int rs_fill(int m, const double *coef, ttx_engine *const *x, ttx_engine *e, const std::vector<long long> &S, const int32_t *l, double tol, int rmax,
@@ -3619,49 +3600,28 @@ static int rs_fill(int m, const double *coef, ttx_engine *const *x, ttx_engine *
     if ((rc = tt_prepare(e, "ttx_lincomb_round"))) return rc;
     struct OnStream { ttx_engine *e; hipStream_t own; ~OnStream() { e->stream = own; } } on{e, e->stream};
     e->stream = h->stream;
-    // tables: RsBlk [d][m] (mode k at (k - 1) m), Omega's offsets [d + 1]; sizes
-    std::vector<RsBlk> blks((size_t)d * m);
-    std::vector<size_t> ooff(d + 1, 0), woff(d + 2, 0);
-    std::vector<long long> tS(d + 1, 0), tA(d + 1, 0);
-    size_t ymax = 1, mmax = (size_t)m;
-    double fl = 0.0;
-    for (int k = 1; k <= d; k++) {
-        const int n = h->n1[k], l0 = l[k - 1], l1 = l[k];
-        ooff[k] = ooff[k - 1] + (size_t)l0 * n * l1;
-        woff[k + 1] = woff[k] + (size_t)S[k] * l1;                              // W(k) at woff[k], k = 1 .. d
-        ymax = std::max(ymax, (size_t)l0 * n * (size_t)S[k]);
-        mmax = std::max(mmax, (size_t)l1 * (size_t)S[k]);
-        const int ntp = (l0 + 15) / 16;
-        int o0 = 0, o1 = 0;
-        for (int t = 0; t < m; t++) {
-            RsBlk &B = blks[(size_t)(k - 1) * m + t];
-            B = RsBlk{};
-            B.x = core_dev(x[t], k); B.RM = x[t]->RM; B.SS = x[t]->P.SS;
-            B.r0 = x[t]->rfinal[k - 1]; B.r1 = x[t]->rfinal[k]; B.o0 = o0; B.o1 = o1;
-            B.firstS = tS[k]; B.firstA = tA[k];
-            tS[k] += (B.r0 + 15) / 16;
-            tA[k] += (long long)ntp * (((long long)n * B.r1 + 63) / 64);
-            o0 += B.r0; o1 += B.r1;
-            if (k >= 2) fl += 2.0 * B.r0 * n * l1 * ((double)B.r1 + l0);        // the sketch step of mode k
-            fl += 2.0 * l0 * B.r0 * n * B.r1;                                   // the advance into mode k
-        }
-        if (tA[k] > 0x7fffffffll) return fail(TTX_EINVAL, "ttx_lincomb_round: too many tiles (%lld)", tA[k]);
-        if (k < d) fl += 4.0 * l0 * n * l1 * (double)S[k];                      // Z = Y W and M = Q^T Y
-    }
-    const int eff = mode == TTX_EVAL_AUTO ? (fl >= TTX_RS_AUTO_FLOPS ? TTX_EVAL_MFMA : TTX_EVAL_EXACT) : mode;
-    h->rs_ms[0] = h->rs_ms[1] = h->rs_ms[2] = h->rs_ms[3] = 0.0; h->rs_flops = fl; h->rs_mode = eff; h->rs_l.assign(l, l + d + 1);
+    std::vector<const int32_t *> rt(m);
+    for (int t = 0; t < m; t++) rt[t] = x[t]->rfinal.data();
+    RsPlan pl = rs_plan(d, h->n1.data() + 1, m, rt.data(), S.data(), l, mode);
+    if (pl.refused) return fail(TTX_EINVAL, "ttx_lincomb_round: too many tiles (%lld)", pl.refused);
+    for (int k = 1; k <= d; k++)
+        for (int t = 0; t < m; t++) { RsBlk &B = pl.blks[(size_t)(k - 1) * m + t]; B.x = core_dev(x[t], k); B.RM = x[t]->RM; B.SS = x[t]->P.SS; }
+    const std::vector<RsBlk> &blks = pl.blks;
+    const std::vector<size_t> &ooff = pl.ooff, &woff = pl.woff;
+    const std::vector<long long> &tS = pl.tS, &tA = pl.tA;
+    const int eff = pl.eff;
+    h->rs = RsLast();
+    h->rs.flops = pl.fl; h->rs.mode = eff; h->rs.l.assign(l, l + d + 1);
     OpMeta meta(h->meta_host);
     const size_t o_blk = meta.put(blks), o_off = meta.put(ooff);
     char *dm;
     if ((rc = meta.upload(h, SC_RSTAB, &dm)) || (rc = buf_reserve(h, SC_RSO, sizeof(double) * std::max<size_t>(ooff[d], 1))) ||
-        (rc = buf_reserve(h, SC_RSW, sizeof(double) * woff[d + 1])) || (rc = buf_reserve(h, SC_RSYA, sizeof(double) * ymax)) ||
-        (rc = buf_reserve(h, SC_RSYB, sizeof(double) * ymax)) || (rc = buf_reserve(h, SC_RSM, sizeof(double) * mmax))) return rc;
+        (rc = buf_reserve(h, SC_RSW, sizeof(double) * woff[d + 1])) || (rc = buf_reserve(h, SC_RSYA, sizeof(double) * pl.ymax)) ||
+        (rc = buf_reserve(h, SC_RSYB, sizeof(double) * pl.ymax)) || (rc = buf_reserve(h, SC_RSM, sizeof(double) * pl.mmax))) return rc;
     const RsBlk *dblk = (const RsBlk *)(dm + o_blk);
     double *Om = buf<double>(h, SC_RSO), *W = buf<double>(h, SC_RSW), *Y = buf<double>(h, SC_RSYA), *Yn = buf<double>(h, SC_RSYB), *M = buf<double>(h, SC_RSM);
     hipStream_t st = h->stream;
-    size_t omax = 1;
-    for (int k = 1; k <= d; k++) omax = std::max(omax, ooff[k] - ooff[k - 1]);
-    hipLaunchKernelGGL(k_rs_omega, dim3(g1(omax).x, d), dim3(256), 0, st, seed, (const size_t *)(dm + o_off), Om);
+    hipLaunchKernelGGL(k_rs_omega, dim3(g1(pl.omax).x, d), dim3(256), 0, st, seed, (const size_t *)(dm + o_off), Om);
     // right to left: W(d) = ones, W(k-1) from W(k)
     OpTimer &tm = h->timer[TM_RS_SKETCH];
     if ((rc = tm.start(st))) return rc;
@@ -3679,7 +3639,7 @@ static int rs_fill(int m, const double *coef, ttx_engine *const *x, ttx_engine *
     if ((rc = tm.stop(st))) return rc;
     // left to right
     const TtScratch s(e);
-    RsMarks marks(h->rs_ev);
+    OpMarks marks(h->op_ev);                // phases 1 gemm, 2 qr, 3 advance; 0 is the sketch's (TM_RS_SKETCH)
     HIPCHECK(hipMemcpyAsync(M, coef, sizeof(double) * m, hipMemcpyHostToDevice, st));
     if ((rc = marks.mark(st, 0))) return rc;
     auto advance = [&](int k, int lr, int ldm, double *dst) {                   // Y(k) from M (lr rows) and the cores k
@@ -3707,7 +3667,7 @@ static int rs_fill(int m, const double *coef, ttx_engine *const *x, ttx_engine *
     if ((rc = marks.mark(st, 3))) return rc;
     HIPCHECK(hipStreamSynchronize(st));
     HIPCHECK(hipGetLastError());
-    if ((rc = tm.ms(&h->rs_ms[0])) || (rc = marks.sum(h->rs_ms))) return rc;
+    if ((rc = tm.ms(&h->rs.ms[0])) || (rc = marks.sum(h->rs.ms))) return rc;
     if (tol >= 0.0 && (rc = svd_impl(e, tol, rmax))) return rc;
     HIPCHECK(hipStreamSynchronize(st));
     return TTX_OK;
@@ -3722,7 +3682,7 @@ extern "C" int ttx_lincomb_round(int32_t m, const double *coef, ttx_engine *cons
     if (rsketch < 0 || rsketch > 128) return fail(TTX_EINVAL, "ttx_lincomb_round: sketch rank %d (0 = 128, or 1 .. 128: the engine holds ranks up to 128)", rsketch);
     if (rmax < 0) return fail(TTX_EINVAL, "ttx_lincomb_round: rmax must be >= 0 (0: absent; got %d)", (int)rmax);
     if (tol != tol) return fail(TTX_EINVAL, "ttx_lincomb_round: tol is not a number (tol < 0 skips the truncation)");
-    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "ttx_lincomb_round: unknown mode %d", mode);
+    if (!op_mode_known(mode)) return fail(TTX_EINVAL, "ttx_lincomb_round: unknown mode %d", mode);
     int rc = alg_check("ttx_lincomb_round", m, x);
     if (rc) return rc;
     ttx_engine *h = x[0];
@@ -3742,73 +3702,41 @@ extern "C" int ttx_lincomb_round(int32_t m, const double *coef, ttx_engine *cons
 extern "C" int ttx_roundsum_last(const ttx_engine *h, double *ms, double *flops, int32_t *lsk, int32_t *mode_ran)
 {
     if (!h) return fail(TTX_EINVAL, "ttx_roundsum_last: null engine");
-    if (ms) for (int p = 0; p < 4; p++) ms[p] = h->rs_ms[p];
-    if (flops) *flops = h->rs_flops;
-    if (lsk) for (int k = 0; k <= h->d; k++) lsk[k] = k < (int)h->rs_l.size() ? h->rs_l[k] : 0;
-    if (mode_ran) *mode_ran = h->rs_mode;
+    if (ms) for (int p = 0; p < 4; p++) ms[p] = h->rs.ms[p];
+    if (flops) *flops = h->rs.flops;
+    if (lsk) for (int k = 0; k <= h->d; k++) lsk[k] = k < (int)h->rs.l.size() ? h->rs.l[k] : 0;
+    if (mode_ran) *mode_ran = h->rs.mode;
     return TTX_OK;
 }
 
 // ---- matrices applied to chosen modes (ttx_modeapply.h) -------------------------------------------------------------------------
-// TTX_EVAL_AUTO: a break-even in flops per call (TTX_MA_AUTO_FLOPS, ttx_modeapply.h; profiles/modeapply_mi355x.txt)
-static int ma_auto(double flops)
-{
-    return flops >= TTX_MA_AUTO_FLOPS ? TTX_EVAL_MFMA : TTX_EVAL_EXACT;
-}
-static void ma_core(MaCore &c, long long *tiles)
-{
-    c.nab = (c.r0 + 15) / 16; c.npan = (c.m + TTX_MA_JP - 1) / TTX_MA_JP;
-    c.ngrp = (int)(((long long)c.nab * c.r1 + TTX_MA_UNITS - 1) / TTX_MA_UNITS); c.pad = 0;
-    c.first = *tiles;
-    *tiles += (long long)c.ngrp * c.npan;
-}
 // everything of ttx_mode_apply that works on the new engine e: a failure leaves e to the caller to destroy
 static int ma_fill(ttx_engine *h, ttx_engine *e, const int32_t *m, const double *A, bool dev, int mode)
 {
-    const int d = h->d;
-    std::vector<MaCore> app, cpy;
-    long long tapp = 0, tcpy = 0;
-    std::vector<size_t> aoff;                                                   // of every applied mode's block in the matrices
-    size_t asize = 0;
-    double rd = 0.0, wr = 0.0, fl = 0.0;
-    for (int k = 0; k < d; k++) {
-        MaCore c{};
-        c.src = core_dev(h, k + 1); c.dst = core_dev(e, k + 1);
-        c.r0 = h->rfinal[k]; c.n = h->n1[k + 1]; c.r1 = h->rfinal[k + 1];
-        if (m[k] > 0) {
-            c.m = m[k];
-            aoff.push_back(asize);
-            asize += (size_t)c.m * c.n;
-            rd += 8.0 * c.r0 * c.n * c.r1 + 8.0 * c.m * c.n; wr += 8.0 * c.r0 * c.m * c.r1; fl += 2.0 * c.r0 * c.r1 * c.n * c.m;
-            ma_core(c, &tapp);
-            app.push_back(c);
-        } else {
-            c.m = c.n; c.A = nullptr;
-            ma_core(c, &tcpy);
-            cpy.push_back(c);
-        }
-    }
-    if (tapp > 0x7fffffffll || tcpy > 0x7fffffffll) return fail(TTX_EINVAL, "ttx_mode_apply: too many tiles (%lld)", std::max(tapp, tcpy));
+    MaPlan pl = ma_plan(h->d, h->n1.data() + 1, h->rfinal.data(), m, mode);
+    if (pl.refused) return fail(TTX_EINVAL, "ttx_mode_apply: too many tiles (%lld)", std::max(pl.tapp, pl.tcpy));
+    std::vector<MaCore> &app = pl.app, &cpy = pl.cpy;
+    const long long tapp = pl.tapp, tcpy = pl.tcpy;
     int rc;
     const double *dA = A;
-    if (!dev && asize) {
-        if ((rc = buf_reserve(h, SC_MAT, sizeof(double) * asize))) return rc;
-        HIPCHECK(hipMemcpyAsync(buf<double>(h, SC_MAT), A, sizeof(double) * asize, hipMemcpyHostToDevice, h->stream));
+    if (!dev && pl.asize) {
+        if ((rc = buf_reserve(h, SC_MAT, sizeof(double) * pl.asize))) return rc;
+        HIPCHECK(hipMemcpyAsync(buf<double>(h, SC_MAT), A, sizeof(double) * pl.asize, hipMemcpyHostToDevice, h->stream));
         dA = buf<double>(h, SC_MAT);
     }
-    for (size_t t = 0; t < app.size(); t++) app[t].A = dA + aoff[t];
-    const int eff = mode == TTX_EVAL_AUTO ? ma_auto(fl) : mode;
+    for (size_t t = 0; t < app.size(); t++) { app[t].src = core_dev(h, pl.app_k[t] + 1); app[t].dst = core_dev(e, pl.app_k[t] + 1); app[t].A = dA + pl.aoff[t]; }
+    for (size_t t = 0; t < cpy.size(); t++) { cpy[t].src = core_dev(h, pl.cpy_k[t] + 1); cpy[t].dst = core_dev(e, pl.cpy_k[t] + 1); }
     OpMeta meta(h->meta_host);
     const size_t o_app = meta.put(app), o_cpy = meta.put(cpy);
     char *dm;
     if ((rc = meta.upload(h, SC_META, &dm))) return rc;
-    h->ma_ms = 0.0; h->ma_rd = rd; h->ma_wr = wr; h->ma_flops = fl; h->ma_mode = eff;
+    h->ma = MaLast{0.0, pl.rd, pl.wr, pl.fl, pl.eff};
     if (!cpy.empty())
         hipLaunchKernelGGL(k_ma_copy, dim3((unsigned)tcpy), dim3(256), 0, h->stream, (const MaCore *)(dm + o_cpy), (int)cpy.size(), h->RM, h->P.SS, e->RM, e->P.SS);
     OpTimer &tm = h->timer[TM_APPLY];
     if (!app.empty()) {
         if ((rc = tm.start(h->stream))) return rc;
-        if (eff == TTX_EVAL_MFMA)
+        if (pl.eff == TTX_EVAL_MFMA)
             hipLaunchKernelGGL(k_ma_apply<true>, dim3((unsigned)tapp), dim3(256), 0, h->stream, (const MaCore *)(dm + o_app), (int)app.size(), h->RM, h->P.SS, e->RM, e->P.SS);
         else
             hipLaunchKernelGGL(k_ma_apply<false>, dim3((unsigned)tapp), dim3(256), 0, h->stream, (const MaCore *)(dm + o_app), (int)app.size(), h->RM, h->P.SS, e->RM, e->P.SS);
@@ -3816,13 +3744,13 @@ static int ma_fill(ttx_engine *h, ttx_engine *e, const int32_t *m, const double 
     }
     HIPCHECK(hipStreamSynchronize(h->stream));
     HIPCHECK(hipGetLastError());
-    return app.empty() ? TTX_OK : tm.ms(&h->ma_ms);
+    return app.empty() ? TTX_OK : tm.ms(&h->ma.ms);
 }
 static int ma_run(ttx_engine *h, const int32_t *m, const double *A, int32_t mode, ttx_engine **out, bool dev, const char *who)
 {
     if (out) *out = nullptr;
     if (!h || !m || !out) return fail(TTX_EINVAL, "%s: null argument", who);
-    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    if (!op_mode_known(mode)) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
     const int d = h->d;
     bool any = false;
     for (int k = 0; k < d; k++) {
@@ -3854,11 +3782,11 @@ extern "C" int ttx_mode_apply_dev(ttx_engine *h, const int32_t *m, const double 
 extern "C" int ttx_mode_apply_last(const ttx_engine *h, double *ms, double *bytes_read, double *bytes_written, double *flops, int32_t *mode_ran)
 {
     if (!h) return fail(TTX_EINVAL, "ttx_mode_apply_last: null engine");
-    if (ms) *ms = h->ma_ms;
-    if (bytes_read) *bytes_read = h->ma_rd;
-    if (bytes_written) *bytes_written = h->ma_wr;
-    if (flops) *flops = h->ma_flops;
-    if (mode_ran) *mode_ran = h->ma_mode;
+    if (ms) *ms = h->ma.ms;
+    if (bytes_read) *bytes_read = h->ma.rd;
+    if (bytes_written) *bytes_written = h->ma.wr;
+    if (flops) *flops = h->ma.flops;
+    if (mode_ran) *mode_ran = h->ma.mode;
     return TTX_OK;
 }
 
@@ -3888,64 +3816,24 @@ extern "C" int ttx_basis_host(const ttx_basis *b, int32_t n, int64_t npts, const
         for (int j = 0; j < n; j++) phi[(size_t)p * n + j] = ttx_basis_entry(b->kind, b->flags, b->a, w, b->nodes, n, x[(size_t)p * ldx], j);
     return TTX_OK;
 }
-// the event chain of a call: every launch is followed by a mark that carries the launch's kind (0 table, 1 chain step, 2 neither)
-struct BsMarks {
-    ttx_engine *h;
-    size_t used = 0;
-    std::vector<char> kind;
-    int mark(int k)
-    {
-        if (used == h->bs_ev.size()) { hipEvent_t e; HIPCHECK(hipEventCreate(&e)); h->bs_ev.push_back(e); }
-        HIPCHECK(hipEventRecord(h->bs_ev[used++], h->stream));
-        kind.push_back((char)k);
-        return TTX_OK;
-    }
-    int collect()                           // after a synchronise
-    {
-        for (size_t t = 1; t < used; t++) {
-            if (kind[t] == 2) continue;
-            float ms = 0.f;
-            HIPCHECK(hipEventElapsedTime(&ms, h->bs_ev[t - 1], h->bs_ev[t]));
-            (kind[t] == 0 ? h->bs_ms_tab : h->bs_ms_chain) += ms;
-        }
-        used = 0; kind.clear();
-        return TTX_OK;
-    }
-};
-template <int MR>
-static void bs_gemm_launch(ttx_engine *h, const EvTrain &T, int i, int c, const double *phi, size_t ldphi, const double *X, double *Z, double *out)
-{
-    constexpr int TP = 64 * bs_ct(MR);
-    hipLaunchKernelGGL(k_bs_gemm<MR>, dim3((c + TP - 1) / TP), dim3(256), bs_gemm_lds(h->rfinal[i]), h->stream, T, i, c, phi, ldphi, X, Z, out);
-}
-enum BsSrc { BS_X_HOST, BS_X_DEV, BS_TAB_HOST, BS_TAB_DEV };
+enum { BSM_TABLE, BSM_CHAIN };             // OpMarks phases of a call: every launch is followed by the mark of its kind, BsLast::ms takes the sums
 static int bs_run(ttx_engine *h, const char *who, BsSrc src, int64_t npts, const double *in, const ttx_basis *basis, double *out, int32_t mode)
 {
     const bool tab = src == BS_TAB_HOST || src == BS_TAB_DEV, dev = src == BS_X_DEV || src == BS_TAB_DEV;
     int rc = tt_prepare(h, who);
     if (rc) return rc;
     if (npts < 0 || (npts > 0 && (!in || !out || (!tab && !basis)))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
-    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    if (!op_mode_known(mode)) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
     const int d = h->d;
     if (!tab && basis) for (int k = 1; k <= d; k++) if ((rc = bs_check_one(who, k, basis[k - 1], h->n1[k]))) return rc;
-    const int rmax = *std::max_element(h->rfinal.begin(), h->rfinal.begin() + d + 1);
-    if (rmax > 128) return fail(TTX_EINVAL, "%s: ranks up to 128 only (got %d)", who, rmax);
-    if (h->rfinal[0] != 1 || h->rfinal[d] != 1) return fail(TTX_EINVAL, "%s: boundary ranks are not 1", who);
-    double w = 0.0;
-    size_t sumn = 0, nmax = 1;
-    std::vector<size_t> off(d);
-    for (int k = 1; k <= d; k++) {
-        w += (double)h->rfinal[k - 1] * h->n1[k] * h->rfinal[k];
-        off[k - 1] = sumn; sumn += (size_t)h->n1[k]; nmax = std::max(nmax, (size_t)h->n1[k]);
-    }
-    const double flops = 2.0 * (double)npts * w;
-    const int eff = mode == TTX_EVAL_AUTO ? (flops >= TTX_BS_AUTO_FLOPS ? TTX_EVAL_MFMA : TTX_EVAL_EXACT) : mode;
-    h->bs_ms_tab = 0.0; h->bs_ms_chain = 0.0; h->bs_flops = flops; h->bs_mode = eff;
+    const BsPlan pl = bs_plan(d, h->n1.data() + 1, h->rfinal.data(), dev_ncu(h), src, npts, mode, env_chunk("TTX_BASIS_CHUNK", op_chunk_default(h->RM)));
+    if (pl.refusal == BS_RANK) return fail(TTX_EINVAL, "%s: ranks up to 128 only (got %d)", who, pl.rmax);
+    if (pl.refusal == BS_BOUNDARY) return fail(TTX_EINVAL, "%s: boundary ranks are not 1", who);
+    h->bs = BsLast();
+    h->bs.flops = pl.flops; h->bs.mode = pl.eff;
     if (npts == 0) return TTX_OK;
     EvTrain T;
     if ((rc = ev_train(h, &T))) return rc;
-    size_t chunk = std::min<size_t>(env_chunk("TTX_BASIS_CHUNK", h->RM <= 64 ? (size_t)1 << 18 : (size_t)1 << 17), (size_t)npts);
-    if (src == BS_TAB_HOST) chunk = std::min(chunk, std::max<size_t>(1, ((size_t)1 << 25) / sumn));     // the staged rows of the caller's table
     // the nodes of the LINEAR modes, one device block
     std::vector<BsMode> M(d);
     if (!tab) {
@@ -3961,60 +3849,47 @@ static int bs_run(ttx_engine *h, const char *who, BsSrc src, int64_t npts, const
             M[k] = BsMode{b.kind, b.flags, h->n1[k + 1], cosk ? b.a : 0.0, cosk ? ttx_basis_cos_w(b.a, b.b) : 0.0, cosk ? nullptr : (const double *)(dm + o_nodes[k])};
         }
     }
-    const size_t row = tab ? sumn : (size_t)d;                                  // doubles per point of the input
-    if ((rc = buf_reserve(h, SC_XA, sizeof(double) * chunk * T.ldx)) || (rc = buf_reserve(h, SC_XB, sizeof(double) * chunk * T.ldx))) return rc;
-    if (!tab && (rc = buf_reserve(h, SC_BTAB, sizeof(double) * chunk * nmax))) return rc;
-    if (!dev && ((rc = buf_reserve(h, SC_X, sizeof(double) * chunk * row)) || (rc = buf_reserve(h, SC_OUT, sizeof(double) * chunk)))) return rc;
+    if ((rc = buf_reserve(h, {{SC_XA, pl.b_xa}, {SC_XB, pl.b_xb}, {SC_BTAB, pl.b_btab}, {SC_X, pl.b_x}, {SC_OUT, pl.b_out}}))) return rc;
     double *btab = buf<double>(h, SC_BTAB), *sin_ = buf<double>(h, SC_X), *sout = buf<double>(h, SC_OUT);
-    const int ncu = dev_ncu(h);
-    BsMarks marks{h};
-    for (int64_t o = 0; o < npts; o += (int64_t)chunk) {
-        const int c = (int)std::min<int64_t>((int64_t)chunk, npts - o);
-        const double *cin = in + (size_t)o * row;
+    OpMarks marks(h->op_ev);
+    for (int64_t o = 0; o < npts; o += (int64_t)pl.chunk) {
+        const int c = (int)std::min<int64_t>((int64_t)pl.chunk, npts - o);
+        const double *cin = in + (size_t)o * pl.row;
         double *cout = out + o;
         if (!dev) {
-            HIPCHECK(hipMemcpyAsync(sin_, cin, sizeof(double) * (size_t)c * row, hipMemcpyHostToDevice, h->stream));
+            HIPCHECK(hipMemcpyAsync(sin_, cin, sizeof(double) * (size_t)c * pl.row, hipMemcpyHostToDevice, h->stream));
             cin = sin_; cout = sout;
         }
         double *X = buf<double>(h, SC_XA), *Z = buf<double>(h, SC_XB);
-        if ((rc = marks.mark(2))) return rc;
+        if ((rc = marks.mark(h->stream, OpMarks::DISCARD))) return rc;
         for (int i = d - 1; i >= 0; i--) {
-            const int q0 = h->rfinal[i], q1 = h->rfinal[i + 1];
-            const double *ph = cin + off[i];
-            size_t ld = sumn;
+            const double *ph = cin + pl.off[i];
+            size_t ld = pl.sumn;
             if (!tab) {
                 hipLaunchKernelGGL(k_bs_table, g1((size_t)c * M[i].n), dim3(256), 0, h->stream, M[i], (long long)c, cin + i, d, btab);
-                if ((rc = marks.mark(0))) return rc;
+                if ((rc = marks.mark(h->stream, BSM_TABLE))) return rc;
                 ph = btab; ld = (size_t)M[i].n;
             }
             const double *Xin = i == d - 1 ? nullptr : X;
             double *o1 = i == 0 ? cout : nullptr;
-            if (eff == TTX_EVAL_EXACT) {
-                const int grid = (int)std::min<long long>(((long long)c + 3) / 4, (long long)ncu * 8);
-                hipLaunchKernelGGL(k_bs_exact, dim3(grid), dim3(256), 4 * sizeof(double) * (size_t)T.ldx, h->stream, T, i, (long long)c, ph, ld, Xin, Z, o1);
-            } else {
-                switch ((std::max(q0, q1) + 15) / 16) {
-                    case 1: bs_gemm_launch<1>(h, T, i, c, ph, ld, Xin, Z, o1); break;
-                    case 2: bs_gemm_launch<2>(h, T, i, c, ph, ld, Xin, Z, o1); break;
-                    case 3: bs_gemm_launch<3>(h, T, i, c, ph, ld, Xin, Z, o1); break;
-                    case 4: bs_gemm_launch<4>(h, T, i, c, ph, ld, Xin, Z, o1); break;
-                    case 5: bs_gemm_launch<5>(h, T, i, c, ph, ld, Xin, Z, o1); break;
-                    case 6: bs_gemm_launch<6>(h, T, i, c, ph, ld, Xin, Z, o1); break;
-                    case 7: bs_gemm_launch<7>(h, T, i, c, ph, ld, Xin, Z, o1); break;
-                    default: bs_gemm_launch<8>(h, T, i, c, ph, ld, Xin, Z, o1); break;
-                }
-            }
-            if ((rc = marks.mark(1))) return rc;
+            if (pl.eff == TTX_EVAL_EXACT)
+                hipLaunchKernelGGL(k_bs_exact, dim3(pl.g_exact(c)), dim3(256), pl.exact_lds, h->stream, T, i, (long long)c, ph, ld, Xin, Z, o1);
+            else
+                with_tier<true>(pl.step[i].tier, [&](auto mr) {
+                    hipLaunchKernelGGL(k_bs_gemm<decltype(mr)::value>, dim3(pl.g_gemm(i, c)), dim3(256), pl.step[i].lds, h->stream, T, i, c, ph, ld, Xin, Z, o1);
+                    return 0;
+                });
+            if ((rc = marks.mark(h->stream, BSM_CHAIN))) return rc;
             std::swap(X, Z);
         }
         if (!dev) HIPCHECK(hipMemcpyAsync(out + o, sout, sizeof(double) * (size_t)c, hipMemcpyDeviceToHost, h->stream));
-        if (!dev || marks.used > 4096) {                                        // the staging blocks are reused by the next chunk; the event chain stays short
+        if (!dev || marks.phase.size() > 4096) {                                // the staging blocks are reused by the next chunk; the event chain stays short
             HIPCHECK(hipStreamSynchronize(h->stream));
-            if ((rc = marks.collect())) return rc;
+            if ((rc = marks.sum(h->bs.ms))) return rc;
         }
     }
     HIPCHECK(hipStreamSynchronize(h->stream));
-    if ((rc = marks.collect())) return rc;
+    if ((rc = marks.sum(h->bs.ms))) return rc;
     HIPCHECK(hipGetLastError());
     return TTX_OK;
 }
@@ -4037,21 +3912,128 @@ extern "C" int ttx_basis_tab_dev(ttx_engine *h, int64_t npts, const double *phi_
 extern "C" int ttx_basis_last(const ttx_engine *h, double *ms_table, double *ms_chain, double *flops, int32_t *mode_ran)
 {
     if (!h) return fail(TTX_EINVAL, "ttx_basis_last: null engine");
-    if (ms_table) *ms_table = h->bs_ms_tab;
-    if (ms_chain) *ms_chain = h->bs_ms_chain;
-    if (flops) *flops = h->bs_flops;
-    if (mode_ran) *mode_ran = h->bs_mode;
+    if (ms_table) *ms_table = h->bs.ms[BSM_TABLE];
+    if (ms_chain) *ms_chain = h->bs.ms[BSM_CHAIN];
+    if (flops) *flops = h->bs.flops;
+    if (mode_ran) *mode_ran = h->bs.mode;
     return TTX_OK;
 }
 
 // ---- the largest elements of the resident train (ttx_topk.h)--------------------------------------------------------------------
-template <int MR>
-static int tk_score_mfma(ttx_engine *h, dim3 grid, size_t lds, const double *G, int r0, int r1, const double *P, int ldp, const double *X, int ldx, int C, int nI, int ifix,
-                         int niper, int first, tk_u64 *S)
+namespace {
+struct TkWork {                             // where the plan's slots and tables lie on the device
+    char *dm = nullptr;                     // SC_META: nI, ifx, cnt, sheet
+    size_t o_nI = 0, o_ifx = 0, o_cnt = 0, o_sheet = 0;
+    double *Pb = nullptr, *W = nullptr, *Xo = nullptr, *Xn = nullptr;           // the Gram matrices, the W of a Gram step, the states before and after a mode
+    tk_u64 *S = nullptr, *st = nullptr, *blk = nullptr;                         // a mode's keys; the selection's words and chunk counts
+    unsigned *hist = nullptr;
+    int *rec = nullptr, *tind = nullptr, *oind = nullptr;                       // the kept positions [d][K]; the index rows before and after the ordering
+    double *tval = nullptr, *oval = nullptr;
+};
+}
+// the tables to the device, every slot reserved once, the outputs cleared, P_0 = [1] and the x of the empty suffix
+static int tk_begin(ttx_engine *h, const TkPlan &pl, int K, TkWork &w)
 {
-    if (lds > 64 * 1024) { if (int rc = ensure_lds(h, reinterpret_cast<const void *>(k_tk_score_mfma<MR>), lds)) return rc; }   // rank 113 .. 128: 66560 bytes
-    hipLaunchKernelGGL(k_tk_score_mfma<MR>, grid, dim3(256), lds, h->stream, G, h->RM, h->P.SS, r0, r1, P, ldp, X, ldx, C, nI, ifix, niper, first, S);
+    int rc;
+    const int d = h->d;
+    OpMeta meta(h->meta_host);
+    w.o_nI = meta.put(pl.nI); w.o_ifx = meta.put(pl.ifx); w.o_cnt = meta.put(pl.cnt); w.o_sheet = meta.put(pl.sheet);
+    if ((rc = meta.upload(h, SC_META, &w.dm)) ||
+        (rc = buf_reserve(h, {{SC_KP, pl.b_kp}, {SC_KW, pl.b_kw}, {SC_KS, pl.b_ks}, {SC_KX, pl.b_kx}, {SC_KREC, pl.b_krec}, {SC_KSEL, pl.b_ksel}, {SC_KOUT, pl.b_kout}}))) return rc;
+    w.Pb = buf<double>(h, SC_KP); w.W = buf<double>(h, SC_KW); w.Xo = buf<double>(h, SC_KX); w.Xn = w.Xo + (size_t)K * pl.ldx;
+    w.S = buf<tk_u64>(h, SC_KS); w.st = buf<tk_u64>(h, SC_KSEL); w.blk = w.st + TKS_WORDS;
+    w.hist = (unsigned *)(w.blk + TTX_TK_SHEET / TTX_TK_CHUNK);
+    w.rec = buf<int>(h, SC_KREC);
+    w.tval = buf<double>(h, SC_KOUT); w.oval = w.tval + K;                      // [tval K][oval K][tind K d][oind K d]
+    w.tind = (int *)(w.oval + K); w.oind = w.tind + (size_t)K * d;
+    const double one = 1.0;
+    HIPCHECK(hipMemsetAsync(w.rec, 0, pl.b_krec, h->stream));
+    HIPCHECK(hipMemsetAsync(w.tval, 0, pl.b_kout, h->stream));
+    HIPCHECK(hipMemcpyAsync(w.Pb, &one, sizeof one, hipMemcpyHostToDevice, h->stream));     // P_0 = [1]
+    HIPCHECK(hipMemcpyAsync(w.Xo, &one, sizeof one, hipMemcpyHostToDevice, h->stream));     // x of the empty suffix
     return TTX_OK;
+}
+// the Gram chain: P_k for k = 1 .. d-1 (P_(k-1) scores mode k), between TM_GRAM's events
+static int tk_gram(ttx_engine *h, const TkPlan &pl, const TkWork &w)
+{
+    int rc;
+    const int d = h->d, ldp = pl.ldx;
+    if (d < 2) return TTX_OK;
+    OpTimer &t_gram = h->timer[TM_GRAM];
+    if ((rc = t_gram.start(h->stream))) return rc;
+    for (int k = 0; k + 1 < d; k++) {
+        const int r0 = h->rfinal[k], r1 = h->rfinal[k + 1];
+        const double *G = core_dev(h, k + 1), *P = w.Pb + (size_t)k * ldp * ldp;
+        hipLaunchKernelGGL(k_tk_gram_w, dim3((unsigned)(pl.nI[k] * r1)), dim3(128), 0, h->stream, G, h->RM, h->P.SS, r0, pl.nI[k], pl.ifx[k], P, ldp, w.W);
+        hipLaunchKernelGGL(k_tk_gram_p, dim3((r1 + 15) / 16, (r1 + 15) / 16), dim3(256), 0, h->stream, G, h->RM, h->P.SS, r0, r1, pl.nI[k], pl.ifx[k], (const double *)w.W,
+                           w.Pb + (size_t)(k + 1) * ldp * ldp, ldp);
+    }
+    return t_gram.stop(h->stream);
+}
+// 0-based mode k: its sheet scored (TM_SCORE), the K largest keys selected and their pairs advanced (TM_SELECT), the wait, the times
+static int tk_mode(ttx_engine *h, const TkPlan &pl, int K, int k, TkWork &w)
+{
+    int rc;
+    const int d = h->d, ldx = pl.ldx, ldp = pl.ldx, r0 = h->rfinal[k], r1 = h->rfinal[k + 1], C = pl.cnt[k + 1], Cn = pl.cnt[k], first = k == 0, nI = pl.nI[k], ifx = pl.ifx[k];
+    const TkStep &s = pl.step[k];
+    const long long M = pl.sheet[k];
+    const double *G = core_dev(h, k + 1), *P = w.Pb + (size_t)k * ldp * ldp;
+    OpTimer &t_score = h->timer[TM_SCORE], &t_sel = h->timer[TM_SELECT];
+    if ((rc = t_score.start(h->stream))) return rc;
+    if (pl.eff == TTX_EVAL_MFMA) {
+        if ((rc = with_tier(s.tier, [&](auto mr) {
+                constexpr int MR = decltype(mr)::value;
+                if (int rc = op_lds_raise(h, reinterpret_cast<const void *>(k_tk_score_mfma<MR>), s.lds)) return rc;      // rank 113 .. 128: 66560 bytes
+                hipLaunchKernelGGL(k_tk_score_mfma<MR>, dim3(s.gx, s.gy), dim3(256), s.lds.bytes, h->stream, G, h->RM, h->P.SS, r0, r1, P, ldp, (const double *)w.Xo, ldx, C, nI, ifx,
+                                   s.niper, first, w.S);
+                return (int)TTX_OK;
+            }))) return rc;
+    } else
+        hipLaunchKernelGGL(k_tk_score_exact, dim3(s.g_exact), dim3(256), sizeof(double) * 4 * ldx, h->stream, G, h->RM, h->P.SS, r0, r1, P, ldp, (const double *)w.Xo, ldx, C, nI, ifx,
+                           first, w.S);
+    if ((rc = t_score.stop(h->stream)) || (rc = t_sel.start(h->stream))) return rc;
+    // selection: everything is kept, or the K-th largest key by six radix passes from the top (11, 11, 11, 11, 11 and 9 bits)
+    hipLaunchKernelGGL(k_tk_selinit, dim3(1), dim3(1024), 0, h->stream, w.st, w.hist, (long long)K, M, s.radix ? 0 : 1, k == d - 1 ? 1 : 0);
+    if (s.radix) {
+        static const int shifts[6] = {53, 42, 31, 20, 9, 0};
+        for (int shift : shifts) {
+            const int nbits = shift ? 11 : 9;
+            hipLaunchKernelGGL(k_tk_hist, dim3(s.hg), dim3(256), 0, h->stream, (const tk_u64 *)w.S, M, shift, nbits, shift == 53 ? 1 : 0, (const tk_u64 *)w.st, w.hist);
+            hipLaunchKernelGGL(k_tk_pick, dim3(1), dim3(1024), 0, h->stream, w.st, w.hist, shift);
+        }
+    }
+    hipLaunchKernelGGL(k_tk_count, dim3(s.nblk), dim3(1024), 0, h->stream, (const tk_u64 *)w.S, M, (const tk_u64 *)w.st, w.blk);
+    hipLaunchKernelGGL(k_tk_blkscan, dim3(1), dim3(1024), 0, h->stream, w.blk, s.nblk);
+    hipLaunchKernelGGL(k_tk_scatter, dim3(s.nblk), dim3(1024), 0, h->stream, (const tk_u64 *)w.S, M, w.st, (const tk_u64 *)w.blk, w.rec + (size_t)k * K, Cn);
+    hipLaunchKernelGGL(k_tk_advance, dim3(s.g_adv), dim3(256), sizeof(double) * 4 * ldx, h->stream, G, h->RM, h->P.SS, r0, r1, k == d - 1 ? 1 : 0,
+                       (const int *)(w.rec + (size_t)k * K), Cn, M, nI, ifx, (const double *)w.Xo, w.Xn, ldx);
+    if ((rc = t_sel.stop(h->stream))) return rc;
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipGetLastError());
+    double a = 0.0, b = 0.0;
+    if ((rc = t_score.ms(&a)) || (rc = t_sel.ms(&b))) return rc;
+    h->tk.ms_score += a; h->tk.ms_select += b;
+    std::swap(w.Xo, w.Xn);
+    return TTX_OK;
+}
+// the index rows by back-tracking the kept positions, their ordering by `which`, the read-back and the bound
+static int tk_finish(ttx_engine *h, const TkPlan &pl, int K, int which, const TkWork &w, int32_t *nfound, int32_t *ind, double *val, double *bound)
+{
+    const int d = h->d, nf = pl.cnt[0];
+    hipLaunchKernelGGL(k_tk_back, dim3((nf + 255) / 256), dim3(256), 0, h->stream, d, K, nf, (const int *)w.rec, (const int *)(w.dm + w.o_nI), (const int *)(w.dm + w.o_ifx),
+                       (const int *)(w.dm + w.o_cnt), (const long long *)(w.dm + w.o_sheet), (const double *)w.Xo, pl.ldx, w.tind, w.tval);
+    hipLaunchKernelGGL(k_tk_order, dim3((nf + 255) / 256), dim3(256), 0, h->stream, d, nf, which, (const int *)w.tind, (const double *)w.tval, w.oind, w.oval);
+    tk_u64 fin[TKS_WORDS];
+    HIPCHECK(hipMemcpyAsync(ind, w.oind, sizeof(int) * (size_t)K * d, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(val, w.oval, sizeof(double) * K, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(fin, w.st, sizeof fin, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipGetLastError());
+    *nfound = nf;
+    if (fin[TKS_NAN]) *bound = __builtin_nan("");
+    else if (!fin[TKS_BOUND]) *bound = 0.0;
+    else { const tk_u64 bits = fin[TKS_BOUND] - 1ull; memcpy(bound, &bits, sizeof bits); }
+    return d > 1 ? h->timer[TM_GRAM].ms(&h->tk.ms_gram) : TTX_OK;
 }
 extern "C" int ttx_topk(ttx_engine *h, int32_t K, int32_t which, const int32_t *fixed, int32_t mode, int32_t *nfound, int32_t *ind, double *val, double *bound)
 {
@@ -4059,136 +4041,28 @@ extern "C" int ttx_topk(ttx_engine *h, int32_t K, int32_t which, const int32_t *
     if (!nfound || !ind || !val || !bound) return fail(TTX_EINVAL, "%s: null argument", who);
     if (K < 1 || K > TTX_TK_KMAX) return fail(TTX_EINVAL, "%s: K = %d (1 .. %d expected)", who, K, TTX_TK_KMAX);
     if (which != TTX_TOPK_ABS && which != TTX_TOPK_MAX && which != TTX_TOPK_MIN) return fail(TTX_EINVAL, "%s: unknown which %d", who, which);
-    if (mode != TTX_EVAL_EXACT && mode != TTX_EVAL_MFMA && mode != TTX_EVAL_AUTO) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    if (!op_mode_known(mode)) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
     int rc = check_train_one_process(h, who);
-    if (rc) return rc;
-    const int d = h->d;
-    int nmax = 1;
-    for (int k = 0; k < d; k++) {
-        if (fixed && (fixed[k] < 0 || fixed[k] > h->n1[k + 1])) return fail(TTX_EINVAL, "%s: fixed(%d) = %d (0 .. %d expected)", who, k + 1, fixed[k], h->n1[k + 1]);
-        nmax = std::max(nmax, (int)h->n1[k + 1]);
-    }
-    if ((long long)K * nmax > (long long)TTX_TK_SHEET)
-        return fail(TTX_EINVAL, "%s: K = %d times the largest mode %d is %lld, the score sheet holds up to %d", who, K, nmax, (long long)K * nmax, TTX_TK_SHEET);
-    EvTrain T;
+    if (rc || (rc = sm_check_fixed(h, who, fixed))) return rc;
+    const TkPlan pl = tk_plan(h->d, h->n1.data() + 1, h->rfinal.data(), dev_ncu(h), K, fixed, mode);
+    if (pl.refused)
+        return fail(TTX_EINVAL, "%s: K = %d times the largest mode %d is %lld, the score sheet holds up to %d", who, K, pl.nmax, (long long)K * pl.nmax, TTX_TK_SHEET);
+    EvTrain T;                              // not read by the kernels: the call keeps ev_train's rank check and its block in SC_TRAIN
     if ((rc = ev_train(h, &T))) return rc;
-    // per mode (0-based): searched indices, the fixed index or -1, the sheet and the pairs kept; cnt[d] = 1, the empty suffix
-    std::vector<int> nI(d), ifx(d), cnt(d + 1, 1);
-    std::vector<long long> sheet(d);
-    double flops = 0.0;
-    size_t wmax = 1, smax = 1;
-    for (int k = d - 1; k >= 0; k--) {
-        const int f = fixed ? fixed[k] : 0, r0 = h->rfinal[k], r1 = h->rfinal[k + 1];
-        nI[k] = f ? 1 : h->n1[k + 1]; ifx[k] = f - 1;
-        sheet[k] = (long long)cnt[k + 1] * nI[k];
-        cnt[k] = (int)std::min<long long>(K, sheet[k]);
-        flops += 2.0 * cnt[k + 1] * nI[k] * r0 * ((double)r1 + r0);
-        wmax = std::max(wmax, (size_t)r0 * nI[k] * r1); smax = std::max(smax, (size_t)sheet[k]);
-    }
-    const int eff = mode == TTX_EVAL_AUTO ? (flops >= TTX_TK_AUTO_FLOPS ? TTX_EVAL_MFMA : TTX_EVAL_EXACT) : mode;
-    const int ldx = T.ldx, ldp = T.ldx, nf = cnt[0], ncu = dev_ncu(h);
-    h->tk_ms_gram = h->tk_ms_score = h->tk_ms_select = 0.0; h->tk_flops = flops; h->tk_mode = eff;
-    OpMeta meta(h->meta_host);
-    const size_t o_nI = meta.put(nI), o_ifx = meta.put(ifx), o_cnt = meta.put(cnt), o_sheet = meta.put(sheet);
-    char *dm;
-    const size_t obytes = (sizeof(int) * d + sizeof(double)) * (size_t)K;
-    if ((rc = meta.upload(h, SC_META, &dm)) || (rc = buf_reserve(h, SC_KP, sizeof(double) * (size_t)d * ldp * ldp)) || (rc = buf_reserve(h, SC_KW, sizeof(double) * wmax)) ||
-        (rc = buf_reserve(h, SC_KS, sizeof(tk_u64) * smax)) || (rc = buf_reserve(h, SC_KX, sizeof(double) * 2 * (size_t)K * ldx)) ||
-        (rc = buf_reserve(h, SC_KREC, sizeof(int) * (size_t)d * K)) ||
-        (rc = buf_reserve(h, SC_KSEL, sizeof(tk_u64) * (TKS_WORDS + TTX_TK_SHEET / TTX_TK_CHUNK) + sizeof(unsigned) * TTX_TK_BINS)) ||
-        (rc = buf_reserve(h, SC_KOUT, 2 * obytes))) return rc;
-    double *Pb = buf<double>(h, SC_KP), *W = buf<double>(h, SC_KW), *Xo = buf<double>(h, SC_KX), *Xn = Xo + (size_t)K * ldx;
-    tk_u64 *S = buf<tk_u64>(h, SC_KS), *st = buf<tk_u64>(h, SC_KSEL), *blk = st + TKS_WORDS;
-    unsigned *hist = (unsigned *)(blk + TTX_TK_SHEET / TTX_TK_CHUNK);
-    int *rec = buf<int>(h, SC_KREC);
-    double *tval = buf<double>(h, SC_KOUT), *oval = tval + K;                   // [tval K][oval K][tind K d][oind K d]
-    int *tind = (int *)(oval + K), *oind = tind + (size_t)K * d;
-    OpTimer &t_gram = h->timer[TM_GRAM], &t_score = h->timer[TM_SCORE], &t_sel = h->timer[TM_SELECT];
-    const double one = 1.0;
-    HIPCHECK(hipMemsetAsync(rec, 0, sizeof(int) * (size_t)d * K, h->stream));
-    HIPCHECK(hipMemsetAsync(tval, 0, 2 * obytes, h->stream));
-    HIPCHECK(hipMemcpyAsync(Pb, &one, sizeof one, hipMemcpyHostToDevice, h->stream));       // P_0 = [1]
-    HIPCHECK(hipMemcpyAsync(Xo, &one, sizeof one, hipMemcpyHostToDevice, h->stream));       // x of the empty suffix
-    // the Gram chain: P_k for k = 1 .. d-1 (P_(k-1) scores mode k)
-    if (d > 1) {
-        if ((rc = t_gram.start(h->stream))) return rc;
-        for (int k = 0; k + 1 < d; k++) {
-            const int r0 = h->rfinal[k], r1 = h->rfinal[k + 1];
-            const double *G = core_dev(h, k + 1), *P = Pb + (size_t)k * ldp * ldp;
-            hipLaunchKernelGGL(k_tk_gram_w, dim3((unsigned)(nI[k] * r1)), dim3(128), 0, h->stream, G, h->RM, h->P.SS, r0, nI[k], ifx[k], P, ldp, W);
-            hipLaunchKernelGGL(k_tk_gram_p, dim3((r1 + 15) / 16, (r1 + 15) / 16), dim3(256), 0, h->stream, G, h->RM, h->P.SS, r0, r1, nI[k], ifx[k], (const double *)W,
-                               Pb + (size_t)(k + 1) * ldp * ldp, ldp);
-        }
-        if ((rc = t_gram.stop(h->stream))) return rc;
-    }
-    for (int k = d - 1; k >= 0; k--) {
-        const int r0 = h->rfinal[k], r1 = h->rfinal[k + 1], C = cnt[k + 1], Cn = cnt[k], first = k == 0;
-        const long long M = sheet[k];
-        const double *G = core_dev(h, k + 1), *P = Pb + (size_t)k * ldp * ldp;
-        if ((rc = t_score.start(h->stream))) return rc;
-        if (eff == TTX_EVAL_MFMA) {
-            const int by = (C + 63) / 64, niper = (int)std::max<long long>(1, (long long)nI[k] * by / (4ll * ncu));
-            const dim3 grid((nI[k] + niper - 1) / niper, by);
-            const size_t lds = sizeof(double) * 64 * (size_t)tk_ldy(r0);
-            if (r0 <= 16) rc = tk_score_mfma<1>(h, grid, lds, G, r0, r1, P, ldp, Xo, ldx, C, nI[k], ifx[k], niper, first, S);
-            else if (r0 <= 32) rc = tk_score_mfma<2>(h, grid, lds, G, r0, r1, P, ldp, Xo, ldx, C, nI[k], ifx[k], niper, first, S);
-            else if (r0 <= 64) rc = tk_score_mfma<4>(h, grid, lds, G, r0, r1, P, ldp, Xo, ldx, C, nI[k], ifx[k], niper, first, S);
-            else rc = tk_score_mfma<8>(h, grid, lds, G, r0, r1, P, ldp, Xo, ldx, C, nI[k], ifx[k], niper, first, S);
-            if (rc) return rc;
-        } else {
-            const int grid = (int)std::min<long long>((M + 3) / 4, (long long)ncu * 8);
-            hipLaunchKernelGGL(k_tk_score_exact, dim3(grid), dim3(256), sizeof(double) * 4 * ldx, h->stream, G, h->RM, h->P.SS, r0, r1, P, ldp, (const double *)Xo, ldx,
-                               C, nI[k], ifx[k], first, S);
-        }
-        if ((rc = t_score.stop(h->stream)) || (rc = t_sel.start(h->stream))) return rc;
-        // selection: everything is kept, or the K-th largest key by six radix passes from the top (11, 11, 11, 11, 11 and 9 bits)
-        hipLaunchKernelGGL(k_tk_selinit, dim3(1), dim3(1024), 0, h->stream, st, hist, (long long)K, M, M <= K ? 1 : 0, k == d - 1 ? 1 : 0);
-        if (M > K) {
-            const int hg = (int)std::min<long long>((M + 255) / 256, (long long)ncu * 4);
-            static const int shifts[6] = {53, 42, 31, 20, 9, 0};
-            for (int shift : shifts) {
-                const int nbits = shift ? 11 : 9;
-                hipLaunchKernelGGL(k_tk_hist, dim3(hg), dim3(256), 0, h->stream, (const tk_u64 *)S, M, shift, nbits, shift == 53 ? 1 : 0, (const tk_u64 *)st, hist);
-                hipLaunchKernelGGL(k_tk_pick, dim3(1), dim3(1024), 0, h->stream, st, hist, shift);
-            }
-        }
-        const int nblk = (int)((M + TTX_TK_CHUNK - 1) / TTX_TK_CHUNK);
-        hipLaunchKernelGGL(k_tk_count, dim3(nblk), dim3(1024), 0, h->stream, (const tk_u64 *)S, M, (const tk_u64 *)st, blk);
-        hipLaunchKernelGGL(k_tk_blkscan, dim3(1), dim3(1024), 0, h->stream, blk, nblk);
-        hipLaunchKernelGGL(k_tk_scatter, dim3(nblk), dim3(1024), 0, h->stream, (const tk_u64 *)S, M, st, (const tk_u64 *)blk, rec + (size_t)k * K, Cn);
-        hipLaunchKernelGGL(k_tk_advance, dim3(std::min((Cn + 3) / 4, ncu * 8)), dim3(256), sizeof(double) * 4 * ldx, h->stream, G, h->RM, h->P.SS, r0, r1, k == d - 1 ? 1 : 0,
-                           (const int *)(rec + (size_t)k * K), Cn, M, nI[k], ifx[k], (const double *)Xo, Xn, ldx);
-        if ((rc = t_sel.stop(h->stream))) return rc;
-        HIPCHECK(hipStreamSynchronize(h->stream));
-        HIPCHECK(hipGetLastError());
-        double a = 0.0, b = 0.0;
-        if ((rc = t_score.ms(&a)) || (rc = t_sel.ms(&b))) return rc;
-        h->tk_ms_score += a; h->tk_ms_select += b;
-        std::swap(Xo, Xn);
-    }
-    hipLaunchKernelGGL(k_tk_back, dim3((nf + 255) / 256), dim3(256), 0, h->stream, d, (int)K, nf, (const int *)rec, (const int *)(dm + o_nI), (const int *)(dm + o_ifx),
-                       (const int *)(dm + o_cnt), (const long long *)(dm + o_sheet), (const double *)Xo, ldx, tind, tval);
-    hipLaunchKernelGGL(k_tk_order, dim3((nf + 255) / 256), dim3(256), 0, h->stream, d, nf, (int)which, (const int *)tind, (const double *)tval, oind, oval);
-    tk_u64 fin[TKS_WORDS];
-    HIPCHECK(hipMemcpyAsync(ind, oind, sizeof(int) * (size_t)K * d, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipMemcpyAsync(val, oval, sizeof(double) * K, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipMemcpyAsync(fin, st, sizeof fin, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    HIPCHECK(hipGetLastError());
-    *nfound = nf;
-    if (fin[TKS_NAN]) *bound = __builtin_nan("");
-    else if (!fin[TKS_BOUND]) *bound = 0.0;
-    else { const tk_u64 bits = fin[TKS_BOUND] - 1ull; memcpy(bound, &bits, sizeof bits); }
-    return d > 1 ? t_gram.ms(&h->tk_ms_gram) : TTX_OK;
+    TkWork w;
+    h->tk = TkLast{0.0, 0.0, 0.0, pl.flops, pl.eff};
+    if ((rc = tk_begin(h, pl, K, w)) || (rc = tk_gram(h, pl, w))) return rc;
+    for (int k = h->d - 1; k >= 0; k--) if ((rc = tk_mode(h, pl, K, k, w))) return rc;
+    return tk_finish(h, pl, K, which, w, nfound, ind, val, bound);
 }
 extern "C" int ttx_topk_last(const ttx_engine *h, double *ms_gram, double *ms_score, double *ms_select, double *flops, int32_t *mode_ran)
 {
     if (!h) return fail(TTX_EINVAL, "ttx_topk_last: null engine");
-    if (ms_gram) *ms_gram = h->tk_ms_gram;
-    if (ms_score) *ms_score = h->tk_ms_score;
-    if (ms_select) *ms_select = h->tk_ms_select;
-    if (flops) *flops = h->tk_flops;
-    if (mode_ran) *mode_ran = h->tk_mode;
+    if (ms_gram) *ms_gram = h->tk.ms_gram;
+    if (ms_score) *ms_score = h->tk.ms_score;
+    if (ms_select) *ms_select = h->tk.ms_select;
+    if (flops) *flops = h->tk.flops;
+    if (mode_ran) *mode_ran = h->tk.mode;
     return TTX_OK;
 }
 
@@ -4290,7 +4164,7 @@ static int sq_frame(ttx_engine *h, const char *who, const SqKind &kind, int64_t 
     if ((rc = head(pl, Q))) return rc;
     const double flops = pl.flops * (double)npts;
     // measured for ttx_sample_sq (ttx_sample_sq.h); ttx_sample_sq_real's modes part in the same bracket on the D_64 train (profiles/sample_sq_real_mi355x.txt)
-    const int eff_mode = mode == TTX_EVAL_AUTO ? (flops >= TTX_SQ_AUTO_FLOPS ? TTX_EVAL_MFMA : TTX_EVAL_EXACT) : mode;
+    const int eff_mode = op_mode_eff(mode, flops, TTX_SQ_AUTO_FLOPS);
     last.flops = flops; last.mode = eff_mode;
     const int ldx = (rmax + 3) & ~3, ncu = dev_ncu(h);
     if ((rc = buf_reserve(h, SC_QS, sizeof(double) * kind.sheets * sheet)) || (rc = buf_reserve(h, SC_QX, (sizeof(double) * 2 * (size_t)ldx + kind.state) * chunk)) ||
@@ -4298,7 +4172,7 @@ static int sq_frame(ttx_engine *h, const char *who, const SqKind &kind, int64_t 
     double *Xa = buf<double>(h, SC_QX), *Xb = Xa + chunk * ldx;
     P.dcnt = buf<long long>(h, SC_CNT);
     HIPCHECK(hipMemsetAsync(P.dcnt, 0, sizeof(long long), h->stream));
-    RsMarks marks(h->rs_ev);                // phase 0: between the chunks, 1: rows, 2: picks and steps
+    OpMarks marks(h->op_ev);                // phase 0: between the chunks, 1: rows, 2: picks and steps
     int lrc = TTX_OK;
     double ms_all = 0.0;
     rc = sm_chunks(h, P, npts, u, dev, out, nout,
@@ -4316,10 +4190,7 @@ static int sq_frame(ttx_engine *h, const char *who, const SqKind &kind, int64_t 
                         const int lap = 16 - kind.tile, by = (a.C + 63) / 64, nt = (a.n - lap + kind.tile - 1) / kind.tile;
                         const int tper = (int)std::max<long long>(1, (long long)nt * by / (4ll * ncu));
                         const dim3 g((nt + tper - 1) / tper, by);
-                        if (a.r1 <= 16) rows_mfma(SqKs<4>(), a, g, tper);
-                        else if (a.r1 <= 32) rows_mfma(SqKs<8>(), a, g, tper);
-                        else if (a.r1 <= 64) rows_mfma(SqKs<16>(), a, g, tper);
-                        else rows_mfma(SqKs<32>(), a, g, tper);
+                        with_tier(rank_tier(a.r1), [&](auto mr) { rows_mfma(SqKs<4 * decltype(mr)::value>(), a, g, tper); return 0; });
                     } else rows_exact(a, dim3((unsigned)std::min<long long>(((long long)a.C * a.n + 255) / 256, (long long)ncu * 16)));
                     if (!lrc) lrc = marks.mark(h->stream, 1);
                 }

@@ -10,6 +10,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ttx_ttops.h"     // the dbl4 vector type only; included by ttx_engine.hip after the headers ttx_ttops.h itself needs
+#include "ttx_op_plan.h"   // TTX_EV_TP, TTX_EV_LDSHIST, ev_lda, ev_gemm_lds: shared with the call's plan
 
 // the train as the evaluation kernels see it: one device block [d core pointers][r(0:d)][n(1:d)], rebuilt per call (ort / svd move ranks)
 struct EvTrain {
@@ -19,9 +20,6 @@ struct EvTrain {
     const int *r;                   // [d+1]
     const int *n;                   // [d]
 };
-
-#define TTX_EV_TP 256               // points per work item of k_ev_gemm: 4 waves x 4 column tiles of 16
-#define TTX_EV_LDSHIST 8192         // modes up to this size are histogrammed in LDS
 
 // ---- exact: one wave per point, grid-stride --------------------------------------------------------------------------------------
 // dynamic LDS per wave: x[ldx], z[ldx], the point's index row [d]; nothing is shared between waves, so no workgroup barrier.
@@ -163,10 +161,6 @@ __global__ __launch_bounds__(256) void k_ev_scatter(int d, int i, int nmode, int
     __syncthreads();
     for (int p = lo + threadIdx.x; p < hi; p += blockDim.x) if (valid[p]) perm[atomicAdd(&ev_h[ind[(size_t)p * d + i] - 1], 1)] = p;
 }
-// leading dimension (doubles) of the slice image in LDS: rows rounded up to 16, and = 16 mod 32 so that the two k columns a
-// half-wave reads (A[row l&15][k l>>4]) fall into different banks
-__host__ __device__ inline int ev_lda(int q0) { const int m = (q0 + 15) & ~15; return (m & 31) == 16 ? m : m + 16; }
-__host__ __device__ inline size_t ev_gemm_lds(int q0, int q1) { return sizeof(double) * (size_t)ev_lda(q0) * ((q1 + 3) & ~3); }
 // Z[:, pts] = U_i(:, j, :) X[:, pts] for one work item = (index j, up to TTX_EV_TP points of bucket j).  The slice is staged in
 // LDS once (zero-padded to 16 rows x 4 columns); each wave takes column tiles of 16 points, gathers their states through perm
 // (B[k l>>4][col l&15]) and keeps all q0/16 row tiles of the result in registers (MR = row tiles, q0 <= 16 MR).

@@ -26,9 +26,8 @@
 // Neither kernel has atomics or a split of K across workgroups: an element depends on its own row of A_k and its own fibre of G_k
 // alone, not on the tiling of other cores or the grid, and a call repeats bit for bit.
 #pragma once
-#include <hip/hip_runtime.h>
-#include "ttx_ttops.h"     // dbl4
 
+// the sizes and the core table are plain C++ a host compiler accepts (ttx_op_plan.h fills the table)
 #define TTX_MA_JP 64                // columns j of a workgroup's panel
 #define TTX_MA_KC 32                // steps i per staged chunk of A_k
 #define TTX_MA_LDA 80               // row stride of the staged chunk in LDS (doubles)
@@ -44,6 +43,10 @@ struct MaCore {                     // one core of a launch (applied: k_ma_apply
     int r0, n, r1, m;               // m: columns of the result (n for a copy)
     int nab, npan, ngrp, pad;       // blocks of 16 rows a, panels of 64 columns j, groups of four units
 };
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#include "ttx_ttops.h"     // dbl4
 
 // the workgroup's core by bisection over MaCore::first, and its place in it: group of units and panel
 __device__ inline const MaCore *ma_find(const MaCore *cores, int ncore, int *grp, int *pan)
@@ -159,3 +162,4 @@ __global__ __launch_bounds__(256) void k_ma_copy(const MaCore *cores, int ncore,
     double *o = c.dst + a + SSd * (size_t)b;
     for (int jj = q; jj < jn; jj += 4) o[(size_t)RMd * (j0 + jj)] = g[(size_t)RMs * (j0 + jj)];
 }
+#endif

@@ -1,0 +1,326 @@
+// ttx_op_plan.h -- what a call of an operation on the resident train reserves and launches, decided before anything is launched
+// (host only: no HIP in here beyond the qualifiers of the formulas the kernels share).
+//
+// Every plan is a pure function of the train's shape (d, the mode sizes, the ranks, RM), of the device's CU count, of the call's
+// arguments and of the chunk the engine read from the call's TTX_*_CHUNK variable.  The host functions of ttx_engine.hip check their
+// arguments, build the plan, reserve its byte counts, upload tables and launch in its order; device pointers are theirs to fill in.
+// tests/op_plan_main.cpp prints and checks plans on the CPU.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <algorithm>
+#include <vector>
+
+#include "../../include/ttx.h"      // TTX_EVAL_*
+#include "ttx_contract.h"           // CtCore, CtTile (the kernels of these three are behind __HIPCC__)
+#include "ttx_modeapply.h"          // MaCore, TTX_MA_*
+#include "ttx_roundsum.h"           // RsBlk, TTX_RS_*
+#include "ttx_qr_plan.h"            // TTX_LDS_DEVICE
+
+#if defined(__HIPCC__)
+#define TTX_OP_HD __host__ __device__ inline
+#else
+#define TTX_OP_HD inline
+#endif
+
+// ---- rules every operation shares ------------------------------------------------------------------------------------------------
+inline bool op_mode_known(int mode) { return mode == TTX_EVAL_EXACT || mode == TTX_EVAL_MFMA || mode == TTX_EVAL_AUTO; }
+// TTX_EVAL_AUTO takes the matrix cores where the call's work reaches the operation's break-even
+inline int op_mode_eff(int mode, double work, double threshold) { return mode != TTX_EVAL_AUTO ? mode : work >= threshold ? TTX_EVAL_MFMA : TTX_EVAL_EXACT; }
+// row tiles of 16 of the kernels instantiated for 1, 2, 4 and 8 (k_ev_gemm, k_tk_score_mfma; the squared samplers' quads are four times that)
+inline int rank_tier(int r) { return r <= 16 ? 1 : r <= 32 ? 2 : r <= 64 ? 4 : 8; }
+// one wave per item, 4 waves per workgroup, at most 8 workgroups per CU: the kernels stride over the rest
+inline int wave_grid(long long items, int ncu) { return (int)std::min<long long>((items + 3) / 4, (long long)ncu * 8); }
+// dynamic LDS of a launch; above the default ceiling of 64 KB the kernel's attribute has to be raised first
+struct OpLds { size_t bytes = 0; bool raise = false; };
+inline OpLds op_lds(size_t bytes) { OpLds l; l.bytes = bytes; l.raise = bytes > 64 * 1024; return l; }
+// doubles of a point's state: the largest rank rounded up to four
+inline int op_ldx(int d, const int *r) { return (std::max(1, *std::max_element(r, r + d + 1)) + 3) & ~3; }
+// points per chunk of the batched evaluations where the environment names none
+inline size_t op_chunk_default(int RM) { return RM <= 64 ? (size_t)1 << 18 : (size_t)1 << 17; }
+
+// ---- ttx_ijk_batch, ttx_ijk_batch_dev, ttx_value_batch (ttx_eval.h) ----------------------------------------------------------------
+#define TTX_EV_TP 256               // points per work item of k_ev_gemm: 4 waves x 4 column tiles of 16
+#define TTX_EV_LDSHIST 8192         // modes up to this size are histogrammed in LDS
+// leading dimension (doubles) of k_ev_gemm's slice image in LDS: rows rounded up to 16, and = 16 mod 32 so that the two k columns a
+// half-wave reads (A[row l&15][k l>>4]) fall into different banks
+TTX_OP_HD int ev_lda(int q0) { const int m = (q0 + 15) & ~15; return (m & 31) == 16 ? m : m + 16; }
+TTX_OP_HD size_t ev_gemm_lds(int q0, int q1) { return sizeof(double) * (size_t)ev_lda(q0) * ((q1 + 3) & ~3); }
+
+// TTX_EVAL_AUTO, a cost model fitted to the measurement in DESIGN.md 4.5, with w = sum r(k-1) r(k) (slice elements a point touches).
+// The MFMA path pays a fixed cost whatever the batch (four launches per mode and the staging of the slices): 1.46 / 1.47 / 9.2 ms at
+// (d, w) = (63, 6.8 k) / (63, 62 k) / (255, 1.04 M), modelled as 23 us d + 3.2 ns w.  Per point it saves 27.7 / 106 / 1317 ns against
+// the exact kernel, modelled as 1.25 ps w + 0.286 ns d.  MFMA is taken where the saving covers the fixed cost; the model's break-evens
+// are 55 k / 17 k / 6.7 k points on the three trains, the measured ones 52 k / 14 k / 7 k.
+inline int ev_mode_eff(int mode, int d, const int *r, int64_t npts)
+{
+    double w = 0.0;
+    for (int k = 1; k <= d; k++) w += (double)r[k - 1] * r[k];
+    return op_mode_eff(mode, (double)npts * (1.25e-12 * w + 0.286e-9 * d), 23.0e-6 * d + 3.2e-9 * w);
+}
+enum EvStage { EV_ON_DEVICE, EV_HOST_INDEX, EV_HOST_COORD };   // caller's device pointers; host rows staged; host coordinates -> k_ev_digits
+struct EvStep { int nmode = 0, q0 = 0, q1 = 0, tier = 1; size_t hist_lds = 0; OpLds lds; };    // 0-based mode i of the MFMA path: sort by index, k_ev_gemm<tier>
+struct EvPlan {
+    int eff = TTX_EVAL_EXACT, ldx = 4, ncu = 0;
+    size_t chunk = 0;
+    size_t b_ind = 0, b_out = 0, b_flag = 0, b_x = 0, b_xa = 0, b_xb = 0, b_sort = 0;   // bytes of SC_*; 0: the call does not use the slot
+    size_t exact_lds = 0;                   // k_ev_exact: per wave x, z and the index row
+    std::vector<EvStep> step;               // modes 0 .. d-2, walked from the last to the first
+    // the grids of a chunk of c points
+    int g_wave(int c) const { return wave_grid(c, ncu); }                                       // k_ev_exact, k_ev_init
+    int g_sort(int c) const { return std::max(1, std::min((c + 1023) / 1024, 1024)); }          // k_ev_hist, k_ev_scatter
+    int g_gemm(int i, int c) const { return c / TTX_EV_TP + std::min(step[i].nmode, c); }       // a work item per index and TTX_EV_TP of its points
+    int g_final(int c) const { return std::max(1, std::min((c + 255) / 256, 1024)); }
+};
+// n[0 .. d-1], r[0 .. d]; NM: the engine's largest mode; dd: coordinates per point of EV_HOST_COORD; chunk: TTX_IJK_CHUNK or the default
+inline EvPlan ev_plan(int d, const int *n, const int *r, int NM, int ncu, EvStage st, int64_t npts, int dd, int mode, size_t chunk)
+{
+    EvPlan p;
+    p.eff = ev_mode_eff(mode, d, r, npts); p.ldx = op_ldx(d, r); p.ncu = ncu;
+    p.chunk = std::min<size_t>(chunk, (size_t)std::max<int64_t>(npts, 0));
+    if (!p.chunk) return p;                                                     // an empty call reserves and launches nothing
+    // the chunk bounds the work space: the staging blocks of the host entries, two state buffers of chunk x ldx doubles and the sort on the MFMA path
+    if (st != EV_ON_DEVICE) { p.b_ind = sizeof(int) * p.chunk * d; p.b_out = sizeof(double) * p.chunk; }
+    if (st == EV_HOST_COORD) { p.b_flag = sizeof(int) * p.chunk; p.b_x = sizeof(double) * p.chunk * dd; }
+    p.exact_lds = 4 * sizeof(double) * (2 * (size_t)p.ldx + (((size_t)d + 1) >> 1));
+    if (p.eff != TTX_EVAL_MFMA) return p;
+    p.b_xa = p.b_xb = sizeof(double) * p.chunk * p.ldx;
+    p.b_sort = sizeof(int) * (2 * p.chunk + 4 * (size_t)NM + 8);                // valid, perm [chunk]; cnt [NM]; off, tile [NM + 1]; cur [NM]
+    p.step.resize(d > 1 ? d - 1 : 0);
+    for (int i = 0; i + 1 < d; i++) {
+        EvStep &s = p.step[i];
+        s.nmode = n[i]; s.q0 = r[i]; s.q1 = r[i + 1]; s.tier = rank_tier(s.q0);
+        s.hist_lds = s.nmode <= TTX_EV_LDSHIST ? sizeof(int) * s.nmode : 0;
+        s.lds = op_lds(ev_gemm_lds(s.q0, s.q1));
+    }
+    return p;
+}
+
+// ---- ttx_basis_batch, ttx_basis_tab and their _dev forms (ttx_basis.h) -------------------------------------------------------------
+// break-even of TTX_EVAL_AUTO in flops per call (2 npts sum r0 n r1).  Measured (profiles/basis_mi355x.txt): on the coscoeff6 train
+// (d = 6) exact wins at 2.1e8 flops and MFMA at 2.1e9; on the D_64 train (d = 63) MFMA wins at 6.3e8 already.  The value lies inside
+// the first bracket and below the second figure.  Provisional for long chains: below 6.3e8 flops the D_64 crossover is not measured
+// (both modes are then bound by their 2 d launches, not by the flops).
+#define TTX_BS_AUTO_FLOPS 4.0e8
+#define TTX_BS_KPAN 16              // columns k of a panel of k_bs_gemm
+TTX_OP_HD constexpr int bs_ct(int MR) { return MR <= 2 ? 4 : MR <= 4 ? 2 : 1; }                // column tiles of 16 per wave
+TTX_OP_HD size_t bs_gemm_lds(int q0) { return sizeof(double) * 2 * (size_t)ev_lda(q0) * TTX_BS_KPAN; }
+
+enum BsSrc { BS_X_HOST, BS_X_DEV, BS_TAB_HOST, BS_TAB_DEV };
+enum BsRefusal { BS_OK, BS_RANK, BS_BOUNDARY };                // ranks above 128; boundary ranks not 1
+struct BsStep { int tier = 1, tp = 256; size_t lds = 0; };      // k_bs_gemm<tier> of a 0-based mode: 16 tier >= max(r0, r1), tp points per workgroup
+struct BsPlan {
+    BsRefusal refusal = BS_OK;
+    int rmax = 1, eff = TTX_EVAL_EXACT, ldx = 4, ncu = 0;
+    std::vector<size_t> off;                // where a mode's rows start in a point's row of the caller's table
+    size_t sumn = 0, nmax = 1, chunk = 0, row = 0;                              // row: doubles per point of the input
+    double flops = 0.0;
+    size_t b_xa = 0, b_xb = 0, b_btab = 0, b_x = 0, b_out = 0;                  // bytes of SC_*; 0: the call does not use the slot
+    size_t exact_lds = 0;                   // k_bs_exact: per wave x
+    std::vector<BsStep> step;
+    int g_exact(int c) const { return wave_grid(c, ncu); }
+    int g_gemm(int i, int c) const { return (c + step[i].tp - 1) / step[i].tp; }
+};
+// n[0 .. d-1], r[0 .. d]; chunk: TTX_BASIS_CHUNK or the default
+inline BsPlan bs_plan(int d, const int *n, const int *r, int ncu, BsSrc src, int64_t npts, int mode, size_t chunk)
+{
+    const bool tab = src == BS_TAB_HOST || src == BS_TAB_DEV, dev = src == BS_X_DEV || src == BS_TAB_DEV;
+    BsPlan p;
+    p.rmax = *std::max_element(r, r + d + 1); p.ncu = ncu;
+    if (p.rmax > 128) { p.refusal = BS_RANK; return p; }
+    if (r[0] != 1 || r[d] != 1) { p.refusal = BS_BOUNDARY; return p; }
+    double w = 0.0;
+    p.off.resize(d); p.step.resize(d);
+    for (int k = 0; k < d; k++) {
+        w += (double)r[k] * n[k] * r[k + 1];
+        p.off[k] = p.sumn; p.sumn += (size_t)n[k]; p.nmax = std::max(p.nmax, (size_t)n[k]);
+        BsStep &s = p.step[k];
+        s.tier = (std::max(r[k], r[k + 1]) + 15) / 16; s.tp = 64 * bs_ct(s.tier); s.lds = bs_gemm_lds(r[k]);
+    }
+    p.flops = 2.0 * (double)npts * w;
+    p.eff = op_mode_eff(mode, p.flops, TTX_BS_AUTO_FLOPS);
+    p.ldx = op_ldx(d, r);
+    p.chunk = std::min<size_t>(chunk, (size_t)std::max<int64_t>(npts, 0));
+    if (src == BS_TAB_HOST) p.chunk = std::min(p.chunk, std::max<size_t>(1, ((size_t)1 << 25) / p.sumn));     // the staged rows of the caller's table
+    p.row = tab ? p.sumn : (size_t)d;
+    p.b_xa = p.b_xb = sizeof(double) * p.chunk * p.ldx;
+    if (!tab) p.b_btab = sizeof(double) * p.chunk * p.nmax;
+    if (!dev) { p.b_x = sizeof(double) * p.chunk * p.row; p.b_out = sizeof(double) * p.chunk; }
+    p.exact_lds = 4 * sizeof(double) * (size_t)p.ldx;
+    return p;
+}
+
+// ---- ttx_topk (ttx_topk.h) -----------------------------------------------------------------------------------------------------------
+#define TTX_TK_KMAX 4096            // largest K
+#define TTX_TK_SHEET (1 << 24)      // largest sheet K max n_k
+#define TTX_TK_BINS 2048            // bins of a radix pass (11 bits)
+#define TTX_TK_CHUNK 4096           // positions per workgroup of the compaction kernels: 1024 threads x 4
+// TTX_EVAL_AUTO scores on the matrix cores from this many flops per call on.  Measured on the D_64 trains (profiles/topk_mi355x.txt):
+// EXACT is faster at 2.0e8 and 8.1e8 flops per call, MFMA at 3.2e9 and 1.3e10; the break-even lies between 8.1e8 and 3.2e9
+#define TTX_TK_AUTO_FLOPS 3.0e9
+// the selection's state on the device, 64-bit words
+enum { TKS_PREFIX, TKS_KREM, TKS_T, TKS_NEED, TKS_BOUND, TKS_NAN, TKS_WORDS = 8 };
+typedef unsigned long long tk_u64;
+TTX_OP_HD int tk_ldy(int r0) { return ((r0 + 15) & ~15) + 2; }     // = 2 or 18 mod 32: a half-wave's 16 columns x 2 rows meet 32 different bank pairs
+
+struct TkStep {                             // 0-based mode k: the sheet of cnt[k + 1] x nI[k] pairs is scored, cnt[k] of them are kept
+    int gx = 1, gy = 1, niper = 1, tier = 1;                                    // k_tk_score_mfma<tier> on (gx, gy), niper indices per workgroup
+    OpLds lds;
+    int g_exact = 1;                        // k_tk_score_exact
+    bool radix = false;                     // more pairs than K: the six radix passes run, k_tk_hist on hg workgroups
+    int hg = 0, nblk = 1, g_adv = 1;        // the compaction kernels, k_tk_advance
+};
+struct TkPlan {
+    bool refused = false;                   // K times the largest mode is more than the score sheet holds
+    int nmax = 1, eff = TTX_EVAL_EXACT, ldx = 4;
+    // per mode (0-based): searched indices, the fixed index or -1, the sheet and the pairs kept; cnt[d] = 1, the empty suffix
+    std::vector<int> nI, ifx, cnt;
+    std::vector<long long> sheet;
+    double flops = 0.0;
+    size_t wmax = 1, smax = 1;
+    size_t obytes = 0, b_kp = 0, b_kw = 0, b_ks = 0, b_kx = 0, b_krec = 0, b_ksel = 0, b_kout = 0;     // K rows of output; bytes of SC_K*
+    std::vector<TkStep> step;
+};
+// n[0 .. d-1], r[0 .. d]; fixed (may be null): 0 or the 1-based index a mode is held at
+inline TkPlan tk_plan(int d, const int *n, const int *r, int ncu, int K, const int32_t *fixed, int mode)
+{
+    TkPlan p;
+    for (int k = 0; k < d; k++) p.nmax = std::max(p.nmax, n[k]);
+    if ((long long)K * p.nmax > (long long)TTX_TK_SHEET) { p.refused = true; return p; }
+    p.nI.resize(d); p.ifx.resize(d); p.cnt.assign(d + 1, 1); p.sheet.resize(d); p.step.resize(d);
+    for (int k = d - 1; k >= 0; k--) {
+        const int f = fixed ? fixed[k] : 0, r0 = r[k], r1 = r[k + 1];
+        p.nI[k] = f ? 1 : n[k]; p.ifx[k] = f - 1;
+        p.sheet[k] = (long long)p.cnt[k + 1] * p.nI[k];
+        p.cnt[k] = (int)std::min<long long>(K, p.sheet[k]);
+        p.flops += 2.0 * p.cnt[k + 1] * p.nI[k] * r0 * ((double)r1 + r0);
+        p.wmax = std::max(p.wmax, (size_t)r0 * p.nI[k] * r1); p.smax = std::max(p.smax, (size_t)p.sheet[k]);
+    }
+    p.eff = op_mode_eff(mode, p.flops, TTX_TK_AUTO_FLOPS);
+    p.ldx = op_ldx(d, r);
+    for (int k = 0; k < d; k++) {
+        TkStep &s = p.step[k];
+        const long long M = p.sheet[k];
+        s.gy = (p.cnt[k + 1] + 63) / 64;
+        s.niper = (int)std::max<long long>(1, (long long)p.nI[k] * s.gy / (4ll * ncu));
+        s.gx = (p.nI[k] + s.niper - 1) / s.niper;
+        s.tier = rank_tier(r[k]);
+        s.lds = op_lds(sizeof(double) * 64 * (size_t)tk_ldy(r[k]));
+        s.g_exact = wave_grid(M, ncu);
+        s.radix = M > K;
+        s.hg = (int)std::min<long long>((M + 255) / 256, (long long)ncu * 4);
+        s.nblk = (int)((M + TTX_TK_CHUNK - 1) / TTX_TK_CHUNK);
+        s.g_adv = wave_grid(p.cnt[k], ncu);
+    }
+    p.obytes = (sizeof(int) * d + sizeof(double)) * (size_t)K;
+    p.b_kp = sizeof(double) * (size_t)d * p.ldx * p.ldx; p.b_kw = sizeof(double) * p.wmax; p.b_ks = sizeof(tk_u64) * p.smax;
+    p.b_kx = sizeof(double) * 2 * (size_t)K * p.ldx; p.b_krec = sizeof(int) * (size_t)d * K;
+    p.b_ksel = sizeof(tk_u64) * (TKS_WORDS + TTX_TK_SHEET / TTX_TK_CHUNK) + sizeof(unsigned) * TTX_TK_BINS;
+    p.b_kout = 2 * p.obytes;                                                    // [tval K][oval K][tind K d][oind K d]
+    return p;
+}
+
+// ---- ttx_contract, ttx_marginals and the prefix vectors of the samplers (ttx_contract.h) -------------------------------------------
+struct CtPlan {
+    std::vector<CtCore> cores;          // every source core; src is the engine's to fill in
+    std::vector<CtTile> tiles;          // mode-sum tiles of the contracted ones
+    std::vector<int> r;                 // r(0:d)
+    std::vector<size_t> moff;
+    size_t msize = 0, wsize = 0;
+    double bytes = 0.0;                 // 8 sum r0 n r1 over the contracted cores
+};
+// n[0 .. d-1], r[0 .. d]
+inline void ct_plan(int d, const int *n, const int *r, const std::vector<char> &contracted, CtPlan &pl)
+{
+    pl.r.assign(r, r + d + 1);
+    pl.cores.resize(d); pl.moff.assign(d, 0);
+    for (int k = 0; k < d; k++) {
+        CtCore &c = pl.cores[k];
+        c.src = nullptr; c.r0 = r[k]; c.n = n[k]; c.r1 = r[k + 1];
+        c.ta = 1; while (c.ta < 64 && c.ta < c.r0) c.ta <<= 1;
+        c.woff = pl.wsize; pl.wsize += c.n;
+        c.moff = 0;
+        if (!contracted[k]) continue;
+        c.moff = pl.moff[k] = pl.msize; pl.msize += (size_t)c.r0 * c.r1;
+        pl.bytes += 8.0 * c.r0 * c.n * c.r1;
+        const int tb = 256 / c.ta;
+        for (int b0 = 0; b0 < c.r1; b0 += tb) for (int a0 = 0; a0 < c.r0; a0 += c.ta) pl.tiles.push_back(CtTile{k, a0, b0, 0});
+    }
+}
+
+// ---- ttx_mode_apply, ttx_mode_apply_dev (ttx_modeapply.h) ---------------------------------------------------------------------------
+struct MaPlan {
+    std::vector<MaCore> app, cpy;       // the applied and the copied cores; src, dst and A are the engine's to fill in
+    std::vector<int> app_k, cpy_k;      // the 0-based mode of every entry
+    std::vector<size_t> aoff;           // of every applied mode's block in the matrices
+    size_t asize = 0;
+    long long tapp = 0, tcpy = 0;       // workgroups of k_ma_apply, k_ma_copy
+    double rd = 0.0, wr = 0.0, fl = 0.0;
+    int eff = TTX_EVAL_EXACT;
+    bool refused = false;               // more workgroups than a launch takes
+};
+// n[0 .. d-1], r[0 .. d]; m[k]: 0 = mode k is left alone, or the rows of its matrix
+inline MaPlan ma_plan(int d, const int *n, const int *r, const int32_t *m, int mode)
+{
+    MaPlan p;
+    for (int k = 0; k < d; k++) {
+        const bool applied = m[k] > 0;
+        MaCore c{};
+        c.r0 = r[k]; c.n = n[k]; c.r1 = r[k + 1]; c.m = applied ? m[k] : c.n;
+        c.nab = (c.r0 + 15) / 16; c.npan = (c.m + TTX_MA_JP - 1) / TTX_MA_JP;
+        c.ngrp = (int)(((long long)c.nab * c.r1 + TTX_MA_UNITS - 1) / TTX_MA_UNITS);
+        long long &tiles = applied ? p.tapp : p.tcpy;
+        c.first = tiles; tiles += (long long)c.ngrp * c.npan;
+        if (applied) {
+            p.aoff.push_back(p.asize); p.asize += (size_t)c.m * c.n;
+            p.rd += 8.0 * c.r0 * c.n * c.r1 + 8.0 * c.m * c.n; p.wr += 8.0 * c.r0 * c.m * c.r1; p.fl += 2.0 * c.r0 * c.r1 * c.n * c.m;
+        }
+        (applied ? p.app : p.cpy).push_back(c); (applied ? p.app_k : p.cpy_k).push_back(k);
+    }
+    p.refused = p.tapp > 0x7fffffffll || p.tcpy > 0x7fffffffll;
+    p.eff = op_mode_eff(mode, p.fl, TTX_MA_AUTO_FLOPS);
+    return p;
+}
+
+// ---- ttx_lincomb_round (ttx_roundsum.h) ----------------------------------------------------------------------------------------------
+struct RsPlan {
+    std::vector<RsBlk> blks;            // [d][m], mode k at (k - 1) m; x, RM and SS -- where a term's core lies -- are the engine's to fill in
+    std::vector<size_t> ooff, woff;     // Omega's cores [d + 1]; W(k) at woff[k], k = 1 .. d
+    std::vector<long long> tS, tA;      // workgroups of mode k's sketch and advance launches
+    size_t ymax = 1, mmax = 1, omax = 1;
+    double fl = 0.0;
+    int eff = TTX_EVAL_EXACT;
+    long long refused = 0;              // the advance launch of a mode that has more workgroups than a launch takes, 0 if none
+};
+// n[0 .. d-1]; rt[t][0 .. d]: the ranks of term t; S[0 .. d]: their sums (m at both ends); l[0 .. d]: the sketch ranks
+inline RsPlan rs_plan(int d, const int *n, int m, const int32_t *const *rt, const long long *S, const int32_t *l, int mode)
+{
+    RsPlan p;
+    p.blks.resize((size_t)d * m); p.ooff.assign(d + 1, 0); p.woff.assign(d + 2, 0); p.tS.assign(d + 1, 0); p.tA.assign(d + 1, 0);
+    p.mmax = (size_t)m;
+    for (int k = 1; k <= d; k++) {
+        const int nk = n[k - 1], l0 = l[k - 1], l1 = l[k];
+        p.ooff[k] = p.ooff[k - 1] + (size_t)l0 * nk * l1;
+        p.woff[k + 1] = p.woff[k] + (size_t)S[k] * l1;
+        p.omax = std::max(p.omax, p.ooff[k] - p.ooff[k - 1]);
+        p.ymax = std::max(p.ymax, (size_t)l0 * nk * (size_t)S[k]);
+        p.mmax = std::max(p.mmax, (size_t)l1 * (size_t)S[k]);
+        const int ntp = (l0 + 15) / 16;
+        int o0 = 0, o1 = 0;
+        for (int t = 0; t < m; t++) {
+            RsBlk &B = p.blks[(size_t)(k - 1) * m + t];
+            B = RsBlk{};
+            B.r0 = rt[t][k - 1]; B.r1 = rt[t][k]; B.o0 = o0; B.o1 = o1;
+            B.firstS = p.tS[k]; B.firstA = p.tA[k];
+            p.tS[k] += (B.r0 + 15) / 16;
+            p.tA[k] += (long long)ntp * (((long long)nk * B.r1 + 63) / 64);
+            o0 += B.r0; o1 += B.r1;
+            if (k >= 2) p.fl += 2.0 * B.r0 * nk * l1 * ((double)B.r1 + l0);     // the sketch step of mode k
+            p.fl += 2.0 * l0 * B.r0 * nk * B.r1;                                // the advance into mode k
+        }
+        if (p.tA[k] > 0x7fffffffll) { p.refused = p.tA[k]; return p; }
+        if (k < d) p.fl += 4.0 * l0 * nk * l1 * (double)S[k];                   // Z = Y W and M = Q^T Y
+    }
+    p.eff = op_mode_eff(mode, p.fl, TTX_RS_AUTO_FLOPS);
+    return p;
+}

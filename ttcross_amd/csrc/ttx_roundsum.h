@@ -38,11 +38,12 @@
 // Neither has atomics or a split of a sum across workgroups: a call repeats bit for bit.
 // Z = Y W and M = Q^T Y run on k_gemm_mfma in both modes (Q^T by k_transpose).
 #pragma once
-#include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <algorithm>
 #include <vector>
-#include "ttx_ttops.h"     // dbl4, tt_block_max, tt_pow2_above
+
+// the sizes, the term table and step 1 are plain C++ a host compiler accepts (ttx_op_plan.h fills the table)
 
 #define TTX_RS_MAXTERMS 256         // m
 #define TTX_RS_MAXSUM 4096          // sum_t r_t(k) at any bond
@@ -71,6 +72,10 @@ inline void rs_sketch_ranks(int d, const int32_t *n, const long long *S, int L, 
     for (int k = 1; k < d; k++) l[k] = (int32_t)std::min<long long>(l[k], (long long)l[k - 1] * n[k - 1]);
     for (int k = d - 1; k >= 1; k--) l[k] = (int32_t)std::min<long long>(l[k], (long long)n[k] * l[k + 1]);
 }
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#include "ttx_ttops.h"     // dbl4, tt_block_max, tt_pow2_above
 
 // step 2
 __host__ __device__ inline double rs_uniform(unsigned long long seed, int k, unsigned long long x)
@@ -259,3 +264,4 @@ __global__ __launch_bounds__(256) void k_rs_last(int lr, int n, int m, const dou
         core[(x % lr) + (size_t)RM * (x / lr)] = s;
     }
 }
+#endif

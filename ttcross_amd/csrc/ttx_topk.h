@@ -20,17 +20,7 @@
 #include "ttx_sample.h"    // sm_chain_step
 #include "ttx_ttops.h"     // dbl4
 
-#define TTX_TK_KMAX 4096            // largest K
-#define TTX_TK_SHEET (1 << 24)      // largest sheet K max n_k
-#define TTX_TK_BINS 2048            // bins of a radix pass (11 bits)
-#define TTX_TK_CHUNK 4096           // positions per workgroup of the compaction kernels: 1024 threads x 4
-// TTX_EVAL_AUTO scores on the matrix cores from this many flops per call on.  Measured on the D_64 trains (profiles/topk_mi355x.txt):
-// EXACT is faster at 2.0e8 and 8.1e8 flops per call, MFMA at 3.2e9 and 1.3e10; the break-even lies between 8.1e8 and 3.2e9
-#define TTX_TK_AUTO_FLOPS 3.0e9
-
-// the selection's state on the device, 64-bit words
-enum { TKS_PREFIX, TKS_KREM, TKS_T, TKS_NEED, TKS_BOUND, TKS_NAN, TKS_WORDS = 8 };
-typedef unsigned long long tk_u64;
+// the sizes TTX_TK_*, the selection's state words TKS_*, tk_u64 and tk_ldy are in ttx_op_plan.h (through ttx_eval.h), shared with the call's plan
 
 __device__ inline tk_u64 tk_key(double s2)
 {
@@ -39,7 +29,6 @@ __device__ inline tk_u64 tk_key(double s2)
     return (tk_u64)__double_as_longlong(s) + 1ull;
 }
 __device__ inline tk_u64 tk_key_abs(double y) { return y != y ? 0ull : (tk_u64)__double_as_longlong(fabs(y)) + 1ull; }
-__host__ __device__ inline int tk_ldy(int r0) { return ((r0 + 15) & ~15) + 2; }     // = 2 or 18 mod 32: a half-wave's 16 columns x 2 rows meet 32 different bank pairs
 
 // ---- Gram chain -----------------------------------------------------------------------------------------------------------------
 // W(a, ii, b) = sum_a' P(a, a') G(a', i, b), ascending a' from 0.0; one workgroup per (ii, b), threads along a.  W is compact:
