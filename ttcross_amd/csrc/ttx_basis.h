@@ -42,6 +42,8 @@ TTX_CC_HD double ttx_basis_entry(int kind, int flags, double a, double w, const 
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#include "ttx_eval.h"      // EvTrain
+#include "ttx_op_plan.h"   // TTX_BS_KPAN, bs_ct, ev_lda
 
 // one mode's basis as the table kernel takes it
 struct BsMode { int kind, flags, n; double a, w; const double *nodes; };

@@ -11,7 +11,7 @@
 // keeps a copy of that frame: measured, see ttx_mvn.h).
 //
 // The rule part is plain functions of values and compiles on the host (tests/bondstep_main.cpp); values that must be
-// wave-uniform are made so by the caller.  The device part is included by ttx_kernels.h behind its address helpers.
+// wave-uniform are made so by the caller.  The device part follows behind __HIPCC__.
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -90,10 +90,9 @@ TTX_HD long long boundary_neval(bool has_r, int u_r, int upd_last, int n_r, bool
 
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------------
-// device part.  Not self-contained: it uses the address helpers (L_ptr, R_ptr, inv_ptr, vip_ptr) that ttx_kernels.h
-// defines ahead of its #include of this file, and UNI stays defined for every header ttx_kernels.h includes after it.
+// device part.  UNI stays defined for every header that includes this one.
 // ------------------------------------------------------------------------------------------------
-#include "ttx_dev.h"
+#include "ttx_addr.h"
 #define UNI(x) __builtin_amdgcn_readfirstlane(x)
 
 // sweep start (:325-327); one thread of the group

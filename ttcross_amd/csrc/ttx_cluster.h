@@ -107,45 +107,11 @@ __device__ __forceinline__ double f_ising_c4w(int cA, int cB, const double *an, 
     return f;
 }
 
-// arg-max over a wave by the first-max rule (larger |.| wins, ties go to the lower position) in two cheap passes on the DPP
-// path: the maximum of |.| (wave_max_key below), then the smallest (position, sign) key among the lanes that hold it (an
-// integer min per step) -- a fraction of the instructions of the three-operand compare-and-select of wave_argmax.  a is never NaN
-// (a NaN residual never replaces the start value -1), so the maximum and == are exact here.  Result in every lane.
-__device__ __forceinline__ int wave_min_i(int v)
-{
-    v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0xb1, 0xf, 0xf, false));
-    v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x4e, 0xf, 0xf, false));
-    v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x124, 0xf, 0xf, false));
-    v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x128, 0xf, 0xf, false));
-    v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x142, 0xa, 0xf, false));
-    v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x143, 0xc, 0xf, false));
-    return __builtin_amdgcn_readlane(v, 63);
-}
 // Maximum over a wave of the doubles the rook loop reduces, by their integer key (ttx_cluster_rules.h): the fiber maxima
 // mx (fmax of |values| from 0.0: fmax drops a NaN operand) and the residual maxima ab (|b| that compared greater than the
 // start value -1.0, or that start value: a NaN compares false) are >= +0.0 or -1.0 and never a NaN.  Two integer trees of
-// one v_max_*_dpp per step -- the high words, then the low words of the lanes that hold the largest high word -- where
-// wave_max on the register pair takes six instructions per step.  Bit for bit the value wave_max returns.
-__device__ __forceinline__ int wave_max_i(int v)
-{
-    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0xb1, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x4e, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x124, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x128, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x142, 0xa, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x143, 0xc, 0xf, false));
-    return __builtin_amdgcn_readlane(v, 63);
-}
-__device__ __forceinline__ unsigned wave_max_u(unsigned v)
-{
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xb1, 0xf, 0xf, false));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4e, 0xf, 0xf, false));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xf, 0xf, false));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
+// one v_max_*_dpp per step (wave_max_i, wave_max_u) -- the high words, then the low words of the lanes that hold the largest high
+// word -- where wave_max on the register pair takes six instructions per step.  Bit for bit the value wave_max returns.
 __device__ __forceinline__ double wave_max_key(double x)
 {
     const ClKey k = cl_key(x);
@@ -153,6 +119,10 @@ __device__ __forceinline__ double wave_max_key(double x)
     const unsigned lmax = wave_max_u(cl_key_lo_at(k, hmax));
     return cl_unkey(ClKey{hmax, lmax});
 }
+// arg-max over a wave by the first-max rule (larger |.| wins, ties go to the lower position) in two cheap passes on the DPP
+// path: the maximum of |.| (wave_max_key), then the smallest (position, sign) key among the lanes that hold it (wave_min_i of
+// ttx_wave.h, an integer min per step) -- a fraction of the instructions of the three-operand compare-and-select of wave_argmax.  a
+// is never NaN (a NaN residual never replaces the start value -1), so the maximum and == are exact here.  Result in every lane.
 __device__ __forceinline__ void wave_argmax2(double &a, double &v, int &idx)
 {
     const double amx = wave_max_key(a);
@@ -191,7 +161,6 @@ __device__ __forceinline__ u4 ld16(const void *p)
 
 // XCC_ID hardware register (id 20, 4 bits): the XCD this wave runs on
 __device__ __forceinline__ int xcc_id() { return (int)__builtin_amdgcn_s_getreg(((4 - 1) << 11) | 20) & 15; }
-__global__ void k_xcc_probe(int *out) { if (threadIdx.x == 0) out[blockIdx.x] = xcc_id(); }
 
 // Barrier across the workgroups of one cluster with release/acquire semantics for ordinary global data; false: timed
 // out / aborted (every thread of the block gets the same answer).  Every wave first waits for its own stores to be
@@ -584,7 +553,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                     fib[u] = a;
                     if (resid) {
                         double b = a;
-                        cl_ordered_sum<16>(r1u, ClStrided(Cp, i + (size_t)RM * j, P.SS), [&](int s, double cv) { b = b + (-mvn_lane(xsv, s)) * cv; });
+                        cl_ordered_sum<16>(r1u, ClStrided(Cp, i + (size_t)RM * j, P.SS), [&](int s, double cv) { b = b + (-lane_get(xsv, s)) * cv; });
                         resc[u] = b;
                         const double aa = fabs(b);
                         if (aa > ab || (aa == ab && t < ix)) { ab = aa; bb = b; ix = t; }
@@ -598,7 +567,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                     fib[u] = a;
                     if (resid) {
                         double tt = 0.0;
-                        cl_ordered_sum<16>(r1u, ClStrided(Wq, k + (size_t)NM * q, P.SW), [&](int s, double wv_) { tt = tt + wv_ * mvn_lane(xsv, s); });
+                        cl_ordered_sum<16>(r1u, ClStrided(Wq, k + (size_t)NM * q, P.SW), [&](int s, double wv_) { tt = tt + wv_ * lane_get(xsv, s); });
                         const double b = a + (-1.0) * tt;
                         resr[u] = b;
                         const double aa = fabs(b);

@@ -77,7 +77,7 @@ __device__ inline void ct_vecmat(const double *v, const double *M, int r0, int r
     for (int b = wave; b < r1; b += nw) {
         double s = 0.0;
         for (int a = lane; a < r0; a += 64) s = s + v[a] * M[a + (size_t)r0 * b];
-        for (int o = 32; o; o >>= 1) s = s + __shfl_xor(s, o);
+        s = wave_sum_xor(s);
         if (lane == 0) vo[b] = s;
     }
 }
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(256) void k_ct_marg(int d, const CtCore *cores, lon
 #pragma unroll 4
         for (int b = 0; b < c.r1; b++) acc = acc + (la * G[a + SS * b]) * sv[b];
     }
-    for (int o = 32; o; o >>= 1) acc = acc + __shfl_xor(acc, o);
+    acc = wave_sum_xor(acc);
     if (lane == 0) out[item] = acc;
 }
 #endif

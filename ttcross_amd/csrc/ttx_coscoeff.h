@@ -246,4 +246,32 @@ __global__ __launch_bounds__(64 * TTX_CC_WAVES) void k_coscoeff_list(int d, cons
         if (lane == 0) out[p] = v;
     }
 }
+
+// ---- host: what is refused before anything reaches the device -------------------------------------------------------------------
+#include <cmath>
+#include <algorithm>
+#include "ttx_err.h"
+// TTX_FUN_COSCOEFF: aux = [mu(1:d), Sigma(1:d,1:d), a, b].  Refused before anything reaches the device: a wrong naux, non-finite
+// data, a >= b, d > TTX_COSCOEFF_MAXD, and an index box on which |t'mu| or |a sum t| could leave the range of ttx_sin / ttx_cos.
+static int coscoeff_check(const char *who, int d, const int32_t *n, const double *aux, int naux)
+{
+    if (d > TTX_COSCOEFF_MAXD) return fail(TTX_EINVAL, "%s: coscoeff: at most %d dimensions (2^(d-1) sign vectors per element), got %d", who, TTX_COSCOEFF_MAXD, d);
+    if (!aux || naux != d + d * d + 2) return fail(TTX_EINVAL, "%s: coscoeff: aux must hold mu(1:d), Sigma(1:d,1:d), a, b: %d values (got %d)", who, d + d * d + 2, naux);
+    for (int k = 0; k < naux; k++) if (!std::isfinite(aux[k])) return fail(TTX_EINVAL, "%s: coscoeff: aux(%d) is not finite", who, k + 1);
+    const double a = aux[d + d * d], b = aux[d + d * d + 1];
+    if (!(a < b)) return fail(TTX_EINVAL, "%s: coscoeff: lower bound %g must be below upper bound %g", who, a, b);
+    const double ob = 1.0 / (b - a);
+    if (!std::isfinite(ob)) return fail(TTX_EINVAL, "%s: coscoeff: 1/(b-a) is not finite", who);
+    // |t_j| <= pi (n_j - 1) / (b - a): bounds of |dot_mu| and |a sum t| (and of every partial sum), with room for rounding
+    double bmu = 0.0, bst = 0.0;
+    for (int j = 0; j < d; j++) {
+        const double tj = TTX_COSCOEFF_PI * (double)std::max(n[j] - 1, 0) * ob;
+        bmu += tj * std::fabs(aux[j]); bst += tj;
+    }
+    bst *= std::fabs(a);
+    if (!(bmu * (1 + 1e-9) <= TTX_TRIG_MAX) || !(bst * (1 + 1e-9) <= TTX_TRIG_MAX))
+        return fail(TTX_EINVAL, "%s: coscoeff: the arguments of sin/cos can reach %g (|t'mu|) and %g (|a sum t|), beyond the supported %g",
+                    who, bmu, bst, (double)TTX_TRIG_MAX);
+    return TTX_OK;
+}
 #endif

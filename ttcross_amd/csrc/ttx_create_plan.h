@@ -181,7 +181,7 @@ struct CreatePlan {
     int cluster = 0;                                // workgroups per bond group of the cluster sweep kernel (ttx_cluster.h); 0: not used
 };
 
-// The launch of k_init_samples (ttx_kernels.h).  rows 0: the index rows of 256 threads do not fit the LDS, the generic accessor runs.
+// The launch of k_init_samples (ttx_init.h).  rows 0: the index rows of 256 threads do not fit the LDS, the generic accessor runs.
 // rows 1: one row of VS shorts per thread behind the staged parameters, 256 threads -- the samples beyond 256 (408 with 8 groups at
 // n = 51) take a second, part-empty pass, and every thread reads the mode sizes from global memory.  rows 2, where `wide` allows it
 // and the kernel walks its own rows (own_rows: not the wave-per-sample evaluator of the fast Ising D/E, not the host's two passes):

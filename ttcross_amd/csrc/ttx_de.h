@@ -419,6 +419,68 @@ __global__ __launch_bounds__(64) void k_lottery_eval_dec(DevProb P)
     if (lane == 0) P.lotf[(size_t)g * P.lot_max + il] = f;
 }
 
+// b-part (id 2) and weights (test_crs_ising.f90:197-218) from per-dimension value arrays xv / wv (0-based dims)
+__device__ __forceinline__ double de_finish_vals(int id, double a, int m, const double *xv, const double *wv)
+{
+    double b = 0.0;
+    if (id == 2) {
+        double v = 1.0, w = 1.0, vk = 1.0, wk = 1.0;
+        for (int j = m - 1; j >= 0; j--) { vk = vk * xv[j]; v = v + vk; }
+        for (int j = 0; j < m; j++) { wk = wk * xv[j]; w = w + wk; }
+        b = 1.0 / (v * w);
+    }
+    double f = (id == 2) ? 2 * a * b : 2 * a;
+    for (int j = 0; j < m; j++) f = f * wv[j];
+    return f;
+}
+
+// Pair product a = prod ((u_ij-1)/(u_ij+1))^2 of ONE multi-index by one wave, exact, rows ended at the unit cut (nodes in [0,1]); xv = its m
+// node values in LDS, sf = 64 x 32 doubles of LDS.  64 rows of the pair triangle per step: lane l walks row base+l left to right (its
+// own running product, the reference's; one division per pair above the cut) and writes the factors, compacted by a wave prefix sum
+// of the row lengths, to LDS; then the factors of the 64 rows go into `a` in order, sixteen LDS broadcasts ahead of sixteen dependent
+// multiplies.  A row that is still above the cut after 32 pairs (nodes close to 1) sends the whole step down a plain serial walk.
+// The factors left out are exactly 1: the product has the reference's bits.  (Boundary corners, lottery candidates.)
+__device__ __forceinline__ double de_pairs_point_wave_cut(int m, const double *xv, double *sf, int lane)
+{
+        double a = 1.0;
+        for (int base = 0; base < m; base += 64) {
+            const int row = base + lane;
+            double u = 1.0, fr[32];
+            int L = 0; bool on = row < m;
+#pragma unroll
+            for (int c = 0; c < 32; c++) {
+                fr[c] = 1.0;
+                if (on && row + c < m) { u = u * xv[row + c]; if (u > 0x1p-54) { fr[c] = de_t2<true>(u); L = c + 1; } else on = false; }
+                else on = false;
+            }
+            const bool lng = (L == 32) && (row + 32 < m) && (u > 0x1p-54);
+            if (__builtin_amdgcn_ballot_w64(lng) != 0ull) {                 // rare: serial walk of these rows by every lane
+                const int rend = (base + 64 < m) ? base + 64 : m;
+                for (int r = base; r < rend; r++) {
+                    double uu = 1.0;
+                    for (int j = r; j < m; j++) { uu = uu * xv[j]; if (uu <= 0x1p-54) break; a = a * de_t2<true>(uu); }
+                }
+                continue;
+            }
+            const int inc = wave_scan(L, lane);
+            const int off = inc - L, total = __shfl(inc, 63, 64);
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int c = 0; c < 32; c++) if (c < L) sf[off + c] = fr[c];
+            __builtin_amdgcn_wave_barrier();
+            int t = 0;
+            for (; t + 16 <= total; t += 16) {                              // two factors per ds_read_b128 (sf is 16-byte aligned)
+                double f16[16];
+#pragma unroll
+                for (int k = 0; k < 8; k++) { const Double2 q2 = *reinterpret_cast<const Double2 *>(sf + t + 2 * k); f16[2 * k] = q2.a; f16[2 * k + 1] = q2.b; }
+#pragma unroll
+                for (int k = 0; k < 16; k++) a = a * f16[k];
+            }
+            for (; t < total; t++) a = a * sf[t];
+        }
+        return a;
+}
+
 // lottery candidates of the unit-cut path: one wave per candidate, no tables -- a candidate is ONE multi-index, whose pair product a
 // wave forms row-parallel (de_pairs_point_wave_cut: every lane walks a row of the triangle, the factors above the cut are then
 // multiplied in order out of LDS); b-part and weights by de_finish_vals.  The chain of ~3 900 ordered multiplies is what remains.
@@ -466,21 +528,6 @@ __global__ __launch_bounds__(64) void k_halfstep_dec(DevProb P, int h, int dir, 
     if (s.w >= s.npart) return;
     const double a = dec_value<DEC_HALF_STREAM>(P, g, s.p, s.first, s.pl, s.qr, s.i1, s.i2, dyn, lane);
     wave_finish(P, gs, g, s, h, mode, a, lane);
-}
-
-// b-part (id 2) and weights (test_crs_ising.f90:197-218) from per-dimension value arrays xv / wv (0-based dims)
-__device__ __forceinline__ double de_finish_vals(int id, double a, int m, const double *xv, const double *wv)
-{
-    double b = 0.0;
-    if (id == 2) {
-        double v = 1.0, w = 1.0, vk = 1.0, wk = 1.0;
-        for (int j = m - 1; j >= 0; j--) { vk = vk * xv[j]; v = v + vk; }
-        for (int j = 0; j < m; j++) { wk = wk * xv[j]; w = w + wk; }
-        b = 1.0 / (v * w);
-    }
-    double f = (id == 2) ? 2 * a * b : 2 * a;
-    for (int j = 0; j < m; j++) f = f * wv[j];
-    return f;
 }
 
 
@@ -1038,4 +1085,26 @@ __global__ __launch_bounds__(64 * (4 * NBK + 2)) void k_halfstep_det(DevProb P, 
     a = de_finish_split(P.ising_id, a, A, B, x1, x2, weights[s.i1], weights[s.i2], xl, wl, xr, wr);
     wave_finish(P, gs, g, s, h, mode, a, lane);
     DET_ACC(9);
+}
+
+// corner entry of the Ising D / E integrands by the first wave of the block: multi-index = rowA (dims 1..p-1) | self | rowB.
+// Every pair by division with the row-wise evaluator of the lottery (ttx_de.h): the four DPP rows of the wave work on the same
+// element (lane n of a row = column n of a 16-column chunk of the pair triangle), the result is identical in all lanes.
+__device__ __forceinline__ double de_corner_wave(const DevProb &P, const double *par, const short *rowA, int p, int self, const short *rowB,
+                                                 double *scratch, int lane)
+{
+    const int m = P.d, RSW = de_rows_stride(m), n1m = P.n[1], n = lane & 15;
+    double *xv = scratch, *wv = xv + RSW;
+    for (int x = lane; x < m; x += 64) {
+        const int ix = ((x < p - 1) ? (int)rowA[x] : (x == p - 1) ? self : (int)rowB[x - p]) - 1;
+        xv[x] = par[ix]; wv[x] = par[n1m + ix];
+    }
+    if (lane < 56) xv[m + lane] = 1.0;                      // the evaluator's running products read up to 47 columns past a row's end
+    __builtin_amdgcn_wave_barrier();
+    if (P.arith) return de_fast_point_wave(P.ising_id, m, xv, wv, lane);      // TTX_ARITH=fast (ttx_fast.h)
+    if (P.de_cut) return de_finish_vals(P.ising_id, de_pairs_point_wave_cut(m, xv, (double *)(((size_t)(wv + RSW) + 15) & ~(size_t)15), lane), m, xv, wv);   // (the host sized the scratch for the 64 x 32 factors)
+    double a = 1.0;
+    if (P.de_unit) for (int i = 0; i < m; i++) a = rows_span<true>(a, 1.0, xv + i, m - i, false, n);
+    else for (int i = 0; i < m; i++) a = rows_span<false>(a, 1.0, xv + i, m - i, false, n);
+    return de_finish_vals(P.ising_id, a, m, xv, wv);
 }

@@ -202,3 +202,18 @@ struct DevProb {
     struct ClPart *cl_part;        // [2][G][TTX_CLREC]
     long long *dbg;                // -DTTX_STAMPS builds: per-wave cycle stamps of one bond step of the cluster kernel (group 0)
 };
+
+// per-phase wall-clock stamps of the debug build (GroupState::stamp) and the ids of the built-in integrands
+#ifdef TTX_STAMPS
+#define STAMP_DECL const bool t_me = (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0); long long t_prev = wall_clock64(); int t_slot = 0
+#define STAMP(gs, k) do { __syncthreads(); if (t_me) { long long t_now = wall_clock64(); (gs).stamp[k][t_slot++] += t_now - t_prev; t_prev = t_now; } } while (0)
+#define STAMP_END(gs, k) do { if (t_me) (gs).nstamp[k]++; } while (0)
+#else
+#define STAMP_DECL
+#define STAMP(gs, k)
+#define STAMP_END(gs, k)
+#endif
+#define FUN_ISING 1
+#define FUN_STDNORM 2
+#define FUN_MVN 3
+#define FUN_HOST 4     // values come from the host (the user callback of lib/dmrgg.f90:18), see DevProb::hostpass

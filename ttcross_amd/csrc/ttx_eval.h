@@ -9,7 +9,7 @@
 //          A point's value depends on its own column and the fixed k order of v_mfma_f64_16x16x4_f64 only, never on its neighbours.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "ttx_ttops.h"     // the dbl4 vector type only; included by ttx_engine.hip after the headers ttx_ttops.h itself needs
+#include "ttx_ttops.h"     // the dbl4 vector type only
 #include "ttx_op_plan.h"   // TTX_EV_TP, TTX_EV_LDSHIST, ev_lda, ev_gemm_lds: shared with the call's plan
 
 // the train as the evaluation kernels see it: one device block [d core pointers][r(0:d)][n(1:d)], rebuilt per call (ort / svd move ranks)

@@ -21,6 +21,7 @@
 #include "ttx_exp_tab.h"
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>     // (the device overload of memcpy)
 #define TTX_EXP_HD __host__ __device__ inline
 __device__ static const uint64_t ttx_exp_tab_dev[256] = TTX_EXP_TAB_INIT;
 #else

@@ -1,5 +1,4 @@
 // ttx_fast.h -- TTX_ARITH=fast: the heavy integrands evaluated in O(d) per fiber element instead of O(d^2).
-// Included by ttx_kernels.h (after its address helpers and wave reductions); no other includes.
 //
 // The exact mode (default, the checker) performs every product and sum of the reference's integrand in the reference's
 // order: test_crs_ising.f90:186-195 is one dependent chain of d(d+1)/2 divisions and multiplies per evaluation (32 640 at
@@ -30,6 +29,11 @@
 // from scratch and grown by the child updates, with decay counts on both sides of TTX_FNR and of 64, arguments exactly at the cut,
 // nodes 0 and 1; and every table entry a real run leaves behind (ttx_fast_tables).
 #pragma once
+#include <hip/hip_runtime.h>
+#include "ttx_addr.h"
+#include "ttx_bondstep.h"
+#include "ttx_exp.h"
+#include "ttx_wave.h"
 #define TTX_FCUT 5.551115123125783e-17      // 2^-54
 // rows of fPiv
 #define FP_T 0      // Ising: rho of the ranges inside the pivot's dims        mvn: Q = d' S d of the pivot's dims
@@ -38,19 +42,6 @@
 #define FP_P 3      // Ising: left: sum of prefix products from dim 1; right: sum of suffix products from dim d
 #define FP_F 4      // Ising: product of all nodes of the pivot
 #define FP_N 5      // Ising: number of leading entries of near (t = 0 included) above the cut
-
-__device__ __forceinline__ double wave_prod(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v * __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-    return v;
-}
 
 // rho of one arbitrary multi-index by ONE thread: for every end e the ranges [s,e], s = e, e-1, ... until the cut.
 // nodes: 1-based (par - 1); idx(s) = mode index of dim s.  O(d * L) with L ~ 16 instead of d(d+1)/2 divisions.
@@ -144,7 +135,7 @@ __device__ __forceinline__ double de_fast_point_wave(int id, int m, const double
         }
         W = W * wv[e];
     }
-    N = wave_prod(N); D = wave_prod(D); W = wave_prod(W);
+    N = wave_prod_xor(N); D = wave_prod_xor(D); W = wave_prod_xor(W);
     const double rho = N / D;
     double b = 1.0;
     if (id == 2) {
@@ -195,7 +186,7 @@ __device__ __forceinline__ void fast_entry_scratch(const double *xs, const doubl
     }
     double W = 1.0, F = 1.0;
     for (int k = lane; k < len; k += 64) { W = W * ws[k]; F = F * xs[k]; }
-    W = wave_prod(W); F = wave_prod(F);
+    W = wave_prod_xor(W); F = wave_prod_xor(F);
     // ranges inside the pivot's dims: lane = end position, walk the start towards smaller positions until the cut
     double N = 1.0, D = 1.0;
     for (int e = lane; e < len; e += 64) {
@@ -206,7 +197,7 @@ __device__ __forceinline__ void fast_entry_scratch(const double *xs, const doubl
             N = N * (1.0 - u); D = D * (1.0 + u);
         }
     }
-    N = wave_prod(N); D = wave_prod(D);
+    N = wave_prod_xor(N); D = wave_prod_xor(D);
     if (lane == 0) {
         piv[FP_T * RM] = N / D; piv[FP_W * RM] = W; piv[FP_S * RM] = S1; piv[FP_P * RM] = S2;
         piv[FP_F * RM] = F; piv[FP_N * RM] = (double)cnt;
@@ -228,7 +219,7 @@ __device__ __forceinline__ void fast_entry_child(const double *pnear, const doub
         if (on) { cnear[(size_t)t * RM] = v; N = N * (1.0 - v); D = D * (1.0 + v); S1 = S1 + v; }
         cnt += __popcll(__ballot(on));
     }
-    N = wave_prod(N); D = wave_prod(D); S1 = wave_sum(S1);
+    N = wave_prod_xor(N); D = wave_prod_xor(D); S1 = wave_sum_xor(S1);
     if (lane == 0) {
         const double F = ppiv[FP_F * RM] * x;
         cpiv[FP_T * RM] = ppiv[FP_T * RM] * (N / D); cpiv[FP_W * RM] = ppiv[FP_W * RM] * w; cpiv[FP_S * RM] = S1;
@@ -345,7 +336,7 @@ __device__ __forceinline__ void de_fast_fiber_stage(const DevProb &P, int fside,
             if (on) { N = N * (1.0 - c); D = D * (1.0 + c); }
             cnt += __popcll(__ballot(on));
         }
-        N = wave_prod(N); D = wave_prod(D);
+        N = wave_prod_xor(N); D = wave_prod_xor(D);
         if (tid == 0) { s_nfar = 1 + cnt; s_rfix = pO[FP_T * P.RM] * (N / D); }
     }
 }
@@ -394,7 +385,7 @@ __device__ __forceinline__ void mvn_entry_scratch(const DevProb &P, const double
         Y[(size_t)row * RM] = y;
         if (row >= d0 && row < d0 + len) q = __builtin_fma(xs[row - d0], y, q);
     }
-    q = wave_sum(q);
+    q = wave_sum_xor(q);
     if (lane == 0) piv[FP_T * RM] = q;
 }
 // ... and of a pivot that is its PARENT extended by one dimension (0-based dnew, deviation dval) next to the bond: side 0 appends
@@ -421,7 +412,7 @@ __device__ __forceinline__ double mvn_fast_point_wave(const DevProb &P, const do
         for (int k = 0; k < m; k++) y = __builtin_fma(S[(size_t)row + (size_t)m * k], dv[k], y);
         q = __builtin_fma(dv[row], y, q);
     }
-    q = wave_sum(q);
+    q = wave_sum_xor(q);
     return ttx_exp(-0.5 * q) / P.mvn_norm;
 }
 

@@ -11,6 +11,8 @@
 // Arithmetic and its order are identical to the multi-kernel path (and to the oracle): same device functions.
 #pragma once
 #include "ttx_kernels.h"
+#include "ttx_exchange.h"    // exch_pack_group, exch_apply_group
+#include "ttx_sweep_end.h"   // collect_summary
 
 // 4-part index source as VALUES: dims 1..A from row (an, aw); dim A+1 = (s1n, s1w); dim A+2 = (s2n, s2w);
 // dims A+3..m from row (bn, bw)

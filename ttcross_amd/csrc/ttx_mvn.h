@@ -71,7 +71,7 @@ __device__ __forceinline__ double mvn_quadform_wave(int m, const double *dv, int
 // with two v_readlane_b32 into an SGPR pair (independent of the running sum) and a v_add_f64 with a scalar operand: three
 // VALU instructions per term, no LDS traffic, no barrier.  The per-lane term of the free dimension replaces lane L's at its place
 // in the order by a uniform select.  Operations and their order per lane are unchanged: bit-identical.
-// (mvn_lane itself is ttx_wave_solve.h: the append's triangular solves take their lane values the same way.)
+// (The read is lane_get of ttx_wave.h: the append's triangular solves take their lane values the same way.)
 // sixteen lane values at a time into scalar registers first (so that the reads run ahead of the dependent adds), then the adds.
 // The term of lane kL is replaced by `special`: the batch of sixteen that contains it (BL, a template parameter: one straight
 // line of code per position, chosen by ONE wave-uniform branch per row) pays for the selects; a branch per batch instead kept the
@@ -83,7 +83,7 @@ __device__ __forceinline__ double mvn_add64_at(double ex, double t, int kLL, dou
     for (int b = 0; b < 64; b += 16) {
         double sv[16];
 #pragma unroll
-        for (int k = 0; k < 16; k++) sv[k] = mvn_lane(t, b + k);
+        for (int k = 0; k < 16; k++) sv[k] = lane_get(t, b + k);
 #pragma unroll
         for (int k = 0; k < 16; k++) ex = ex + ((b == 16 * BL && k == kLL) ? special : sv[k]);
     }
@@ -105,7 +105,7 @@ __device__ __forceinline__ double mvn_add64_plain(double ex, double t)
     for (int b = 0; b < 64; b += 16) {
         double sv[16];
 #pragma unroll
-        for (int k = 0; k < 16; k++) sv[k] = mvn_lane(t, b + k);
+        for (int k = 0; k < 16; k++) sv[k] = lane_get(t, b + k);
 #pragma unroll
         for (int k = 0; k < 16; k++) ex = ex + sv[k];
     }
@@ -137,7 +137,7 @@ __device__ __forceinline__ double mvn_quadform_lanes(int m, const double *dv, in
             if (L >= 0) {                              // S_iL sits in lane kL of this row's registers
                 double siL = 0.0;
 #pragma unroll
-                for (int q = 0; q < NQ; q++) if (q == qL) siL = mvn_lane(s0[q], kL);
+                for (int q = 0; q < NQ; q++) if (q == qL) siL = lane_get(s0[q], kL);
                 special = di * siL * dL;               // the free dimension: this lane's own difference
             }
 #pragma unroll
@@ -151,7 +151,7 @@ __device__ __forceinline__ double mvn_quadform_lanes(int m, const double *dv, in
             for (int j = 0; j < m; j++) {
                 double sj = 0.0, dj = 0.0;
 #pragma unroll
-                for (int q = 0; q < NQ; q++) if (q == (j >> 6)) { sj = mvn_lane(s0[q], j & 63); dj = mvn_lane(dreg[q], j & 63); }
+                for (int q = 0; q < NQ; q++) if (q == (j >> 6)) { sj = lane_get(s0[q], j & 63); dj = lane_get(dreg[q], j & 63); }
                 if (j == L) dj = dL;
                 ex = ex + dL * sj * dj;
             }
@@ -273,4 +273,20 @@ __global__ __launch_bounds__(64) void k_lottery_eval_mvn(DevProb P)
     __syncthreads();
     const double ex = mvn_quadform(m, dv, -1, 0.0, P.auxT, tb, lane);
     if (lane == 0) P.lotf[(size_t)g * P.lot_max + il] = ttx_exp(-0.5 * ex) / P.mvn_norm;
+}
+
+// corner entry of the mvn integrand by the first wave of the block (ttx_mvn.h)
+__device__ __forceinline__ double mvn_corner_wave(const DevProb &P, const double *par, const short *rowA, int p, int self, const short *rowB,
+                                                  double *scratch, int lane)
+{
+    const int m = P.d;
+    double *dv = scratch, *tb = scratch + ((m + 1) & ~1);
+    for (int x = lane; x < m; x += 64) {
+        const int ix = ((x < p - 1) ? (int)rowA[x] : (x == p - 1) ? self : (int)rowB[x - p]) - 1;
+        dv[x] = par[ix] - P.aux[x];
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (P.arith) return mvn_fast_point_wave(P, dv, lane);                     // TTX_ARITH=fast (ttx_fast.h)
+    const double ex = mvn_quadform_wave(m, dv, -1, 0.0, P.auxT, tb, lane);
+    return ttx_exp(-0.5 * ex) / P.mvn_norm;
 }

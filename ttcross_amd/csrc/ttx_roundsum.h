@@ -75,7 +75,7 @@ inline void rs_sketch_ranks(int d, const int32_t *n, const long long *S, int L, 
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
-#include "ttx_ttops.h"     // dbl4, tt_block_max, tt_pow2_above
+#include "ttx_ttops.h"     // dbl4, block_max_xor, tt_pow2_above
 
 // step 2
 __host__ __device__ inline double rs_uniform(unsigned long long seed, int k, unsigned long long x)
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(1024) void k_rs_scale(size_t cnt, double *W)
     __shared__ double red[16];
     double mx = 0.0;
     for (size_t x = threadIdx.x; x < cnt; x += blockDim.x) { const double v = fabs(W[x]); mx = v != v ? INFINITY : fmax(mx, v); }   // fmax would drop a NaN
-    const int e = tt_pow2_above(tt_block_max(mx, red));
+    const int e = tt_pow2_above(block_max_xor(mx, red));
     if (e == 0) return;
     const double s = ldexp(1.0, -e);
     for (size_t x = threadIdx.x; x < cnt; x += blockDim.x) W[x] *= s;

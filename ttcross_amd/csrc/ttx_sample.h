@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include "ttx_eval.h"      // EvTrain
 #include "ttx_contract.h"  // CtCore
+#include "ttx_wave.h"      // wave_scan
 
 #define TTX_SM_LDSROW 1024          // modes up to this size keep their row of p in LDS (8 KB per wave); longer ones use the call's global rows
 #define TTX_SM_TILE 4096            // products one work item of k_sm_head stages in LDS (before the odd row padding)
@@ -70,14 +71,6 @@ __device__ inline void sm_chain_step(const double *A, size_t SS, int q0, int q1,
     }
 }
 
-// inclusive sum over the lanes of a wave in log steps: after step o lane l holds the sum of lanes max(0, l - 2 o + 1) .. l
-__device__ inline double sm_wave_scan(double c, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const double v = __shfl_up(c, o); if (lane >= o) c = c + v; }
-    return c;
-}
-
 // A sample's row of uniforms u[0 .. d-1]: true if a drawn mode (held(i) false) has a NaN or a negative u, which refuses the sample.
 // us (may be null): the wave's copy of the row
 template <class Held>
@@ -108,7 +101,7 @@ __device__ inline SmFound sm_wave_search(int n, double u, int lane, First first,
     double carry = 0.0;
     for (int i0 = 0; i0 < n; i0 += 64) {                                        // e, and the total c(n-1)
         const double e = first(i0 + lane);
-        carry = __shfl(carry + sm_wave_scan(e, lane), 63);
+        carry = __shfl(carry + wave_scan(e, lane), 63);
         const unsigned long long pos = __ballot(e > 0.0);
         if (pos) f.pos = i0 + 63 - __builtin_clzll(pos);
     }
@@ -120,7 +113,7 @@ __device__ inline SmFound sm_wave_search(int n, double u, int lane, First first,
         carry = 0.0;
         for (int i0 = 0; i0 < n; i0 += 64) {
             const int i = i0 + lane;
-            const double e = again(i), c = carry + sm_wave_scan(e, lane);
+            const double e = again(i), c = carry + wave_scan(e, lane);
             const unsigned long long hit = __ballot(i < n && e > 0.0 && f.t < c);
             if (hit) {
                 const int fl = __builtin_ctzll(hit);
@@ -175,7 +168,7 @@ __global__ __launch_bounds__(256) void k_sm_draw(EvTrain T, const size_t *hoff, 
                         pi = fabs(m);
                         row[i] = pi;
                     }
-                    carry = __shfl(carry + sm_wave_scan(pi, lane), 63);
+                    carry = __shfl(carry + wave_scan(pi, lane), 63);
                     const unsigned long long pos = __ballot(pi > 0.0);
                     if (pos) { const int hl = 63 - __builtin_clzll(pos); last = i0 + hl; plast = __shfl(pi, hl); }
                 }
@@ -188,7 +181,7 @@ __global__ __launch_bounds__(256) void k_sm_draw(EvTrain T, const size_t *hoff, 
                     carry = 0.0;
                     for (int i0 = 0; i0 < n; i0 += 64) {
                         const int i = i0 + lane;
-                        const double pi = i < n ? row[i] : 0.0, c = carry + sm_wave_scan(pi, lane);
+                        const double pi = i < n ? row[i] : 0.0, c = carry + wave_scan(pi, lane);
                         const unsigned long long hit = __ballot(i < n && pi > 0.0 && t < c);
                         if (hit) { const int fl = __builtin_ctzll(hit); ik = i0 + fl; psel = __shfl(pi, fl); break; }
                         carry = __shfl(c, 63);

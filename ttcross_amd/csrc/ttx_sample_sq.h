@@ -75,7 +75,7 @@ inline void sq_effective(int d, const int *n, const int *fx, const double *w, do
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
-#include "ttx_sample.h"    // sm_chain_step, sm_wave_scan, k_sm_count
+#include "ttx_sample.h"    // sm_chain_step, wave_scan, k_sm_count
 #include "ttx_ttops.h"     // dbl4
 
 // TTX_EVAL_AUTO forms the rows on the matrix cores from this many flops per call on (2 sum_k npts n_k l_(k-1) r_k).  Measured on the
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void k_sq_pick(int n, int k, int d, int ifix, 
             int lastp = -1;
             for (int i0 = 0; i0 < n; i0 += 64) {                                // the total c(n)
                 const double pi = sq_p(w, Sc, g, i0 + lane, n);
-                carry = __shfl(carry + sm_wave_scan(pi, lane), 63);
+                carry = __shfl(carry + wave_scan(pi, lane), 63);
                 const unsigned long long pos = __ballot(pi > 0.0);
                 if (pos) { const int hl = 63 - __builtin_clzll(pos); lastp = i0 + hl; plast = __shfl(pi, hl); }
             }
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(256) void k_sq_pick(int n, int k, int d, int ifix, 
                     carry = 0.0;
                     for (int i0 = 0; i0 < n; i0 += 64) {
                         const int i = i0 + lane;
-                        const double pi = sq_p(w, Sc, g, i, n), c = carry + sm_wave_scan(pi, lane);
+                        const double pi = sq_p(w, Sc, g, i, n), c = carry + wave_scan(pi, lane);
                         const unsigned long long hit = __ballot(i < n && pi > 0.0 && t < c);
                         if (hit) { const int fl = __builtin_ctzll(hit); ik = i0 + fl; psel = __shfl(pi, fl); break; }
                         carry = __shfl(c, 63);

@@ -162,8 +162,7 @@ __global__ __launch_bounds__(256) void k_tk_score_exact(const double *G, int RM,
                 for (int q = 0; q < r0; q++) z = z + P[a + (size_t)ldp * q] * y[q];
                 part = part + y[a] * z;
             }
-#pragma unroll
-            for (int o = 32; o; o >>= 1) part = part + __shfl_xor(part, o);
+            part = wave_sum_xor(part);
             key = tk_key(part);
         }
         if (lane == 0) S[pr] = key;

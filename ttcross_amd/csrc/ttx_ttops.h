@@ -7,6 +7,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ttx_dev.h"
+#include "ttx_exp.h"
+#include "ttx_wave.h"
 
 typedef double dbl4 __attribute__((ext_vector_type(4)));
 
@@ -30,29 +32,6 @@ __global__ void k_unpack_core(double *core, const double *w, int r0, int n, int 
     }
 }
 
-__device__ __forceinline__ double tt_block_sum(double v, double *sh)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    double r = 0.0;
-    for (int x = 0; x < nw; x++) r += sh[x];
-    return r;
-}
-
-__device__ __forceinline__ double tt_block_max(double v, double *sh)
-{
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    double r = 0.0;
-    for (int x = 0; x < nw; x++) r = fmax(r, sh[x]);
-    return r;
-}
 // Scale: a plain sum of squares is used while it lies inside [1e-280, 1e280] -- no square that matters can have
 // over- or underflowed there.  Outside, the sum is taken again of x * 2^-e, 2^e the power of two just above max |x| (LAPACK's
 // dnrm2 scales the same way), and the norm is sqrt(sum) * 2^e.  A power of two is exact, so the plain path and every result on
@@ -64,10 +43,10 @@ __device__ __forceinline__ double tt_block_norm_scaled(const double *x, size_t l
 {
     double m = 0.0;
     for (size_t i = threadIdx.x; i < len; i += blockDim.x) m = fmax(m, fabs(x[i]));
-    const int e = tt_pow2_above(tt_block_max(m, sh));
+    const int e = tt_pow2_above(block_max_xor(m, sh));
     double p = 0.0;
     for (size_t i = threadIdx.x; i < len; i += blockDim.x) { const double y = ldexp(x[i], -e); p += y * y; }
-    p = tt_block_sum(p, sh);
+    p = block_sum_xor(p, sh);
     if (e_out) *e_out = e;
     return ldexp(sqrt(p), e);
 }
@@ -76,11 +55,11 @@ __device__ __forceinline__ double tt_wave_norm_scaled(const double *x, int len, 
 {
     double m = 0.0;
     for (int i = lane; i < len; i += 64) m = fmax(m, fabs(x[i]));
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+    m = wave_max_xor(m);
     const int e = tt_pow2_above(m);
     double p = 0.0;
     for (int i = lane; i < len; i += 64) { const double y = ldexp(x[i], -e); p += y * y; }
-    for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
+    p = wave_sum_xor(p);
     return ldexp(sqrt(p), e);
 }
 
@@ -111,8 +90,7 @@ __device__ __forceinline__ void qr_apply_reflector(double *A, int m, int i, int 
 #pragma unroll
         for (int k = 0; k < QR_CH; k++) {
             if (k < nc) {
-                double q = acc[k];
-                for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+                const double q = wave_sum_xor(acc[k]);
                 if (lane == 0) part[wv][k] = q;
             }
         }
@@ -136,7 +114,7 @@ __device__ __forceinline__ void qr_apply_reflector_cols(double *A, int m, int i,
         const double *cc = A + i + (size_t)m * c;
         double q = 0.0;
         for (int r = lane; r < len; r += 64) q += vsh[r] * cc[r];
-        for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+        q = wave_sum_xor(q);
         if (lane == 0) wsh[c] = q * tau;
     }
     __syncthreads();
@@ -147,6 +125,25 @@ __device__ __forceinline__ void qr_apply_reflector_cols(double *A, int m, int i,
     }
     __syncthreads();
 }
+// sum over the tpp (16, 32 or 64) consecutive lanes of a thread group on the DPP data path: the steps of dpp_tree (ttx_wave.h), left
+// early for the smaller groups -- quad butterflies, two row rotations, then the row broadcasts.  A __shfl_xor of a double is two
+// ds_bpermute round trips, 36 of them in sequence per rotation round of the Jacobi SVD made a round last ~2.8 us
+__device__ __forceinline__ double jac_group_sum(double v, int tpp, int lane)
+{
+    v = v + dpp_src<0xb1, 0xf>(v, v);
+    v = v + dpp_src<0x4e, 0xf>(v, v);
+    v = v + dpp_src<0x124, 0xf>(v, v);
+    v = v + dpp_src<0x128, 0xf>(v, v);                     // every lane: a sum of its row of 16 (association differs from quad to quad)
+    if (tpp == 16)                                          // one value for the whole group: lane 15's
+        return __longlong_as_double(__builtin_amdgcn_mov_dpp(__double_as_longlong(v), 0x15f, 0xf, 0xf, false));
+    v = v + dpp_src<0x142, 0xa>(v, v);                     // rows 1 and 3: + the row before
+    if (tpp == 32) {
+        const double lo = lane_get(v, 31), hi = lane_get(v, 63);
+        return lane < 32 ? lo : hi;
+    }
+    v = v + dpp_src<0x143, 0xc>(v, v);                     // rows 2 and 3: + the first half
+    return lane_get(v, 63);
+}
 // Householder QR of an LDS-RESIDENT m x n matrix (column-major, ld = m; dgeqr2 / dlarfg / dlarf, then dorg2r) with THREE workgroup
 // barriers per reflector of the factorisation and TWO per reflector of the generation (round 3; the phases used to be separated by
 // seven and five).  The kernels are chains of short phases, so the barriers were most of their time:
@@ -156,7 +153,6 @@ __device__ __forceinline__ void qr_apply_reflector_cols(double *A, int m, int i,
 //   * column i is rewritten (v below the diagonal, beta on it; in dorg2r: the column of Q) during the update phase, which reads vsh.
 // One wave per column in both phases.  After the first part the upper triangle holds R (emit(r, c, value) receives it, zeros
 // below the diagonal), after the second A holds the first min(m, n) columns of Q.  tauv: n doubles of LDS.
-__device__ __forceinline__ double jac_group_sum(double v, int tpp, int lane);
 template <class EMIT>
 __device__ __forceinline__ void qr_lds3(double *A, int m, int n, double *vsh, double *wsh, double *tauv, EMIT emit)
 {
@@ -282,9 +278,7 @@ __global__ __launch_bounds__(1024) void k_qr_own(int rows, int n, int rbs, const
         // alpha from its lane (the index is wave-uniform: v_readlane, no LDS round trip), the norm by one DPP wave sum; dlapy2 as
         // a plain sqrt(alpha^2 + xn2) while that cannot over- or underflow (hypot costs more than the rest of the scalar chain)
         const int al_lane = i & 63;
-        const long long cb = __double_as_longlong(cand);
-        const double alpha = __longlong_as_double(((long long)__builtin_amdgcn_readlane((int)(cb >> 32), al_lane) << 32) |
-                                                  (unsigned int)__builtin_amdgcn_readlane((int)cb, al_lane));
+        const double alpha = lane_get(cand, al_lane);
         const double xn2 = jac_group_sum(q, 64, lane);
         double tau = 0.0, beta = alpha, sc = 0.0;
         const double s2 = alpha * alpha + xn2;
@@ -296,12 +290,12 @@ __global__ __launch_bounds__(1024) void k_qr_own(int rows, int n, int rbs, const
             double mx = 0.0;
 #pragma unroll
             for (int j = 0; j < MR; j++) { const int r = lane + 64 * j; if (r > i) mx = fmax(mx, fabs(col[j])); }
-            for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+            mx = wave_max_xor(mx);
             const int e = tt_pow2_above(mx);
             double p = 0.0;
 #pragma unroll
             for (int j = 0; j < MR; j++) { const int r = lane + 64 * j; if (r > i) { const double y = ldexp(col[j], -e); p += y * y; } }
-            for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
+            p = wave_sum_xor(p);
             const double xn = ldexp(sqrt(p), e);
             if (xn != 0.0) nrm = hypot(alpha, xn);
         }
@@ -412,7 +406,7 @@ __global__ __launch_bounds__(1024) void k_qr(int m, int n, double *Ag, double *R
         const int len = m - i;
         double p = 0.0;
         for (int r = 1 + tid; r < len; r += nt) p += x[r] * x[r];
-        const double xn2 = tt_block_sum(p, red);
+        const double xn2 = block_sum_xor(p, red);
         double xn = sqrt(xn2);
         if (!tt_sumsq_in_range(xn2)) xn = tt_block_norm_scaled(x + 1, (size_t)(len - 1), red, nullptr);   // (uniform branch)
         if (tid == 0) {
@@ -530,15 +524,15 @@ __global__ __launch_bounds__(1024) void k_sumsq(size_t n, const double *x, doubl
     __shared__ double red[16];
     double p = 0.0;
     for (size_t i = threadIdx.x; i < n; i += blockDim.x) p += x[i] * x[i];
-    p = tt_block_sum(p, red);
+    p = block_sum_xor(p, red);
     int e = 0;
     if (!tt_sumsq_in_range(p)) {
         double m = 0.0;
         for (size_t i = threadIdx.x; i < n; i += blockDim.x) m = fmax(m, fabs(x[i]));
-        e = tt_pow2_above(tt_block_max(m, red));
+        e = tt_pow2_above(block_max_xor(m, red));
         p = 0.0;
         for (size_t i = threadIdx.x; i < n; i += blockDim.x) { const double y = ldexp(x[i], -e); p += y * y; }
-        p = tt_block_sum(p, red);
+        p = block_sum_xor(p, red);
     }
     if (threadIdx.x == 0) { out[0] = p; out[1] = (double)e; }
 }
@@ -550,7 +544,7 @@ __global__ __launch_bounds__(1024) void k_norm_log(size_t n, double *x, double *
     __shared__ double s_inv;
     double p = 0.0;
     for (size_t i = threadIdx.x; i < n; i += blockDim.x) p += x[i] * x[i];
-    p = tt_block_sum(p, red);
+    p = block_sum_xor(p, red);
     const double nrm = tt_sumsq_in_range(p) ? sqrt(p) : tt_block_norm_scaled(x, n, red, nullptr);
     if (threadIdx.x == 0) {
         s_inv = (nrm != 0.0) ? 1.0 / nrm : 1.0;
@@ -592,27 +586,7 @@ __global__ void k_scal_core(double *core, int r0, int n, int r1, int RM, size_t 
 // ordering (perm[j] = column holding the j-th largest singular value) and the reference's chop (lib/mat.f90:433-458)
 // info[0] = kept rank rr, info[1] = sweeps; sout[q] sorted singular values; one 1024-thread workgroup, the
 // q/2 disjoint column pairs of a round-robin round rotate concurrently.
-// sum over the tpp (16, 32 or 64) consecutive lanes of a pair's thread group on the DPP data path (ttx_kernels.h is included
-// before this header): quad butterflies, two row rotations, then the row broadcasts -- a __shfl_xor of a double is two
-// ds_bpermute round trips, 36 of them in sequence per rotation round made a round last ~2.8 us
-__device__ __forceinline__ double jac_group_sum(double v, int tpp, int lane)
-{
-    v = v + dpp_d<0xb1, 0xf>(v);
-    v = v + dpp_d<0x4e, 0xf>(v);
-    v = v + dpp_d<0x124, 0xf>(v);
-    v = v + dpp_d<0x128, 0xf>(v);                          // every lane: a sum of its row of 16 (association differs from quad to quad)
-    if (tpp == 16)                                          // one value for the whole group: lane 15's
-        return __longlong_as_double(__builtin_amdgcn_mov_dpp(__double_as_longlong(v), 0x15f, 0xf, 0xf, false));
-    v = v + dpp_d<0x142, 0xa>(v);                          // rows 1 and 3: + the row before
-    if (tpp == 32) {
-        const double lo = __longlong_as_double(((long long)__builtin_amdgcn_readlane((int)(__double_as_longlong(v) >> 32), 31) << 32) |
-                                               (unsigned int)__builtin_amdgcn_readlane((int)__double_as_longlong(v), 31));
-        const double hi = readlane63(v);
-        return lane < 32 ? lo : hi;
-    }
-    v = v + dpp_d<0x143, 0xc>(v);                          // rows 2 and 3: + the first half
-    return readlane63(v);
-}
+// (the sums over a pair's thread group are jac_group_sum, above)
 __device__ __noinline__ bool jac_orth_scaled(double al, double be, double ga, double jtol) { return fabs(ga) <= jtol * sqrt(al) * sqrt(be); }
 __device__ __noinline__ double jac_tan_scaled(double dd, double g2) { return (dd >= 0.0 ? g2 : -g2) / (fabs(dd) + hypot(dd, g2)); }
 // in_lds: X and V live in dynamic LDS ((p + q) q doubles) for the whole iteration -- a rotation round is a dependent chain of
@@ -695,7 +669,7 @@ __global__ __launch_bounds__(1024) void k_jacobi_svd(int p, int q, double *Xg, d
     for (int j = tid / 64; j < q; j += nt / 64) {
         double *xj = X + (size_t)p * j; double s2 = 0.0;
         for (int i = tid & 63; i < p; i += 64) s2 += xj[i] * xj[i];
-        for (int o = 32; o > 0; o >>= 1) s2 += __shfl_xor(s2, o, 64);
+        s2 = wave_sum_xor(s2);
         const double s = tt_sumsq_in_range(s2) ? sqrt(s2) : tt_wave_norm_scaled(xj, p, tid & 63);
         if ((tid & 63) == 0) ssh[j] = s;
         if (s > 0.0) for (int i = tid & 63; i < p; i += 64) xj[i] /= s;

@@ -9,7 +9,7 @@
 //
 // What a step must not wait for is taken off the chain:
 //  - the value of lane s is a "value of lane k" operation lane(x, k), k wave-uniform: on the device two v_readlane_b32 into a
-//    scalar pair (mvn_lane below; with PK = 2 one pair per half and a select), on the host an array lookup;
+//    scalar pair (lane_get of ttx_wave.h; with PK = 2 one pair per half and a select), on the host an array lookup;
 //  - the LU entries do not depend on the chain: a lane's WS_B entries of the next WS_B steps are requested while the current WS_B
 //    steps run (lu(index, used): on the device a load, on the host a counted lookup).  A lane outside s < l < r requests a clamped
 //    index inside the packed r x r block -- its own last entry, or entry 0 -- and never uses what comes back;
@@ -119,15 +119,9 @@ TTX_HD double wave_solve_U(LU lu, int r, double y, double rdg, int l, int sub, L
 }
 
 #if defined(__HIPCC__)
-// one double of a wave, lane k wave-uniform: two v_readlane_b32 into a scalar pair, no LDS traffic (ttx_mvn.h, ttx_cluster.h)
-__device__ __forceinline__ double mvn_lane(double x, int k)
-{
-    const long long b = __double_as_longlong(x);
-    const int lo = __builtin_amdgcn_readlane((int)b, k), hi = __builtin_amdgcn_readlane((int)(b >> 32), k);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
+#include "ttx_wave.h"    // lane_get
 // the device's two operations, lane value and LU load (LDS or global), and the solves with them: dev_solve_*
-struct WsLane { __device__ __forceinline__ double operator()(double x, int k) const { return mvn_lane(x, k); } };
+struct WsLane { __device__ __forceinline__ double operator()(double x, int k) const { return lane_get(x, k); } };
 struct WsLoad { const double *lu; __device__ __forceinline__ double operator()(int i, bool) const { return lu[i]; } };
 template <int PK>
 __device__ __forceinline__ double dev_solve_L(const double *lu, int r, double a, int l, int sub)

@@ -12,8 +12,8 @@
 // The kernels keep, in their own text: the thread-0 load with resolve_state, the barrier, the inactive-or-done exit, the publish by
 // slot 0 and the exit of a slot past the fiber (k_halfstep_det's fault count ahead of them), and the evaluation.
 //
-// A header of its own rather than a section of ttx_bondstep.h: it needs wave_max, wave_argmax, atomic_max_pos and core_ptr, which
-// ttx_kernels.h defines behind its #include of ttx_bondstep.h.  ttx_engine.hip includes it behind ttx_kernels.h, ahead of ttx_de.h.
+// A header of its own rather than a section of ttx_bondstep.h: that one is rules and cold code, this one is a kernel's frame on
+// top of the reductions of ttx_wave.h and resolve_state of ttx_kernels.h.
 // k_halfstep (a block per 256 entries), k_sweep_fused and k_sweep_cluster reduce differently and are not served.
 #pragma once
 #include "ttx_kernels.h"
