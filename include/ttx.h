@@ -639,6 +639,55 @@ int ttx_sample_sq_real_dev(ttx_engine *h, int64_t npts, const double *u, const d
                            int32_t *cell, double *logq, double *val);
 int ttx_sample_sq_real_last(const ttx_engine *h, double *ms_head, double *ms_rows, double *ms_pick, double *flops, int64_t *nfailed, int32_t *mode_ran);
 
+/* The way back: the FORWARD Rosenblatt map of the squared interpolant, x -> u, on the device (k_sqr_cdf,
+ * ttcross_amd/csrc/ttx_sample_sq_real.h).  ttx_sample_sq_real takes uniforms u to points x; this entry takes points x the sampler
+ * did not draw to the uniforms u that map to them, with logq, the log of the proposal's density (g(x)^2 + gamma) / (Z + gamma V)
+ * at x, and val = g(x): the acceptance ratio of an independence Metropolis step, logq for mixtures over several trains, the
+ * probability integral transform of held-out data, the forward half of a layered transport (DIRT: Cui and Dolgov, 2022).
+ * nodes, cond, gamma, mode, the held-mode rules, the chunking (TTX_SAMPLE_CHUNK), TTX_EVAL_AUTO's threshold (TTX_SQ_AUTO_FLOPS) and
+ * the sheet limit are ttx_sample_sq_real's.  x is [npts][d] where the sampler has u; u is [npts][d] where it has x.
+ * Definition (numpy restates it: tests/rosenblatt_ref.py).  The mass factors, the head pass, g_k, the rows s(i) and c(j), the clamp
+ * of c, q0, qm, q1 and A(j) are those of ttx_sample_sq_real, word for word.  The modes are walked k = d .. 1 with the state
+ * x_(d+1) = [1].
+ * A held mode: x[:, k] is not looked at, u_k = 0.0 and cell = 0; the chain step uses the host-made hat row of cond_k, as in the
+ * sampler.  u_k is 0.0 and not NaN, so that a failed row stays recognisable by its first entry.
+ * A drawn mode: ci = sr_hat_cell(t, n, x_k), TTX_BASIS_LINEAR's cell: the last node with t_ci <= x_k, at most n - 2.
+ *   f1 = (x_k - t_ci) / (t_(ci+1) - t_ci), f0 = 1.0 - f1: the sampler's expressions for its rounded x_k.
+ *   C is the inclusive running sum of A in the sampler's association: lanes along j in rounds of 64, inside a round added in
+ *   ascending distance 1, 2, .. 32, the carry from round to round through lane 63.  C(n-2) is the total, C(-1) = 0.
+ *   The mass inside the cell is min(max(h_ci * sqr_cdf(q0, qm, q1, f1), 0), A(ci)) with the q of cell ci.  sqr_cdf scales q0, qm, q1
+ *   by sqr_invert's power of two, evaluates the Horner form the inversion iterates on,
+ *     l * (q0 + l * ((qm - q0) + l * (((q0 - 2.0 * qm) + q1) / 3.0))),
+ *   returns 0 for l <= 0 and ((q0 + qm) + q1) / 3.0 for l >= 1, and scales back by ldexp; anything that is not a number gives 0.
+ *   u_k = (C(ci-1) + mass inside) / C(n-2), clamped into [0, 1];  cell = ci + 1.
+ *   Log term: the sampler's, on ci, f0, f1: log(max((((f0*f0)*s(ci) + ((2.0*f0)*f1)*c(ci)) + (f1*f1)*s(ci+1)) + g_k, 0) / C(n-2)).
+ *   A cell without mass is no failure: the term is -inf and u_k is the running sum before it.  (Inside such a cell g is 0 along the
+ *   whole cell, so the state after the chain step is 0: in a mode walked before the last the next mode finds C(n-2) = 0 and the point
+ *   fails there, unless gamma > 0.  Mode 1, walked last, shows the -inf.)
+ * Chain step, all modes: the sampler's (k_sqr_step, unchanged).  val = z(1) after mode 1, ttx_basis_batch(x, TTX_BASIS_LINEAR on
+ * nodes, TTX_EVAL_EXACT) element for element.  The sampler forms cell, hat values and log term from its ROUNDED x, so at the
+ * sampler's own x, in the same mode, logq and val repeat bit for bit; cell is the sampler's, or one more exactly where x sits on
+ * the right node of its cell; u comes back within the rounding of the cubic and of the sums (tests/rosenblatt_ref.py derives it).
+ * A failed point: a drawn coordinate is NaN or lies outside [t_0, t_(n-1)], or C(n-2) is 0, NaN or Inf at some mode.  The
+ * convention is the samplers': the whole row of u is NaN, cell 0, logq NaN, val 0.0, and the point is counted.  Safety,
+ * determinism and work space are the sampler's: every index comes from lane numbers or from a count of nodes, the cell is
+ * range-checked where it is read, no read leaves its table whatever x holds; a call repeats bit for bit.  The train is not modified.
+ * ttx_rosenblatt_sq_real_dev: x, u, cell, logq and val are pointers on the engine's device, nodes and cond stay host pointers.
+ * npts = 0 succeeds and launches nothing.  TTX_EINVAL: npts < 0, null x / u / nodes with npts > 0, an unknown mode, gamma negative
+ * or not finite (all before the engine is looked at); a node row that is missing, not finite or not strictly ascending, cond_k =
+ * +-Inf, ranks above 128, two sheets of a chunk times the largest mode above 2^28 entries (before any launch).  TTX_ESTATE: an
+ * engine without a train; a multi-process engine is refused as by ttx_sample.
+ * ttx_rosenblatt_sq_real_last: as ttx_sample_sq_real_last, in a slot of its own (the sampler's figures stay), for the head pass, the
+ * rows kernels and k_sqr_cdf with k_sqr_step.
+ * Open: points outside the box as density 0 (logq = -inf) rather than as failures, per-point weights, ranks above 128.  Added
+ * without a new ttx_version: look the symbols up. */
+int ttx_rosenblatt_sq_real    (ttx_engine *h, int64_t npts, const double *x /* [npts][d] */, const double *const *nodes /* [d] host rows of n_k */,
+                               const double *cond /* [d] or NULL */, double gamma, int32_t mode, double *u /* [npts][d] */, int32_t *cell /* [npts][d] or NULL */,
+                               double *logq, double *val);
+int ttx_rosenblatt_sq_real_dev(ttx_engine *h, int64_t npts, const double *x, const double *const *nodes, const double *cond, double gamma, int32_t mode, double *u,
+                               int32_t *cell, double *logq, double *val);
+int ttx_rosenblatt_sq_real_last(const ttx_engine *h, double *ms_head, double *ms_rows, double *ms_cdf, double *flops, int64_t *nfailed, int32_t *mode_ran);
+
 /* The largest elements of the resident train by a beam search along the train, on the device (ttcross_amd/csrc/ttx_topk.h), with
  * an upper bound on everything the search discarded.  Modes are 1-based, G_k is core k, r_0 = r_d = 1.
  *   K     : rows wanted, 1 .. 4096, and K max n_k <= 2^24 (the score sheet of one mode is kept in work space)

@@ -181,7 +181,7 @@ struct OpMarks {
 
 // the figures of an operation's last call, one record each, handed out by the operation's _last entry
 // samplers: ttx_sample and ttx_sample_real fill head, bytes and draw, the squared samplers head, rows, pick, flops and mode
-enum { SMP_GRID, SMP_REAL, SMP_SQ, SMP_SQ_REAL, SMP_N };
+enum { SMP_GRID, SMP_REAL, SMP_SQ, SMP_SQ_REAL, SMP_ROS_SQ_REAL, SMP_N };
 struct SampleLast { double ms_head = 0.0, bytes = 0.0, ms_draw = 0.0, ms_rows = 0.0, ms_pick = 0.0, flops = 0.0; int64_t failed = 0; int mode = -1; };
 struct CtLast { double ms = 0.0, bytes = 0.0; };                               // the mode-sum kernel of ttx_contract / ttx_marginals
 struct AlgLast { double ms = 0.0, rd = 0.0, wr = 0.0; };                       // ttx_lincomb / ttx_hadamard with this engine first
@@ -287,7 +287,7 @@ struct ttx_engine {
     OpTimer timer[TM_N];
     int ncu = 0;                        // compute units of the device, asked for once (dev_ncu)
     int ev_last_mode = -1;              // TTX_EVAL_* the last batch ran with
-    SampleLast smp[SMP_N];                              // the last call of each of the four samplers, each its own
+    SampleLast smp[SMP_N];                              // the last call of each of the four samplers and of ttx_rosenblatt_sq_real, each its own
     CtLast ct;
     AlgLast alg;
     MaLast ma;
@@ -4087,7 +4087,7 @@ static int sq_head(ttx_engine *h, const SqPlan &pl, const std::vector<double> &e
     return TTX_OK;
 }
 namespace {
-// What tells the two squared samplers apart beside their launches and outputs.  which: SMP_SQ or SMP_SQ_REAL; sheets: the sheets of
+// What tells the two squared samplers apart beside their launches and outputs.  which: SMP_SQ, SMP_SQ_REAL or SMP_ROS_SQ_REAL (the way back shares the real sampler's); sheets: the sheets of
 // chunk x nmax doubles in SC_QS; tile: what the 16 indices of an index tile of the MFMA rows advance by (16, or 15: every cell has both
 // of its nodes in one tile); state: the bytes a sample keeps in SC_QX between the launches, behind the two state buffers
 struct SqKind { int which, sheets, tile; size_t state; };
@@ -4244,19 +4244,24 @@ extern "C" int ttx_sample_sq_last(const ttx_engine *h, double *ms_head, double *
 }
 
 // ---- real-valued samples from the square of the interpolant of the resident train (ttx_sample_sq_real.h) -------------------------
-// both entries: u, x, cell, logq, val are host pointers (dev false: staged chunk by chunk) or pointers on the engine's device.  Two sheets
-// (squares and neighbour products), index tiles that advance by 15, per sample logq, the two hat values, the failure flag and the hat cell (SqrState)
-static int sqr_run(ttx_engine *h, const char *who, int64_t npts, const double *u, const double *const *nodes, const double *cond, double gamma, int32_t mode, double *x,
-                   int32_t *cell, double *logq, double *val, bool dev)
+// What ttx_sample_sq_real and its way back ttx_rosenblatt_sq_real share: everything but one launch.  in: the [npts][d] input (u, or x on the
+// way back); rows: the [npts][d] output of doubles (x, or u on the way back), whose NaN rows k_sr_count counts; all five with cell, logq
+// and val are host pointers (dev false: staged chunk by chunk) or pointers on the engine's device.  which: the caller's SampleLast slot.
+// pick(a, M, st, out): the caller's launch between the rows and the step of a mode (k_sqr_pick, k_sqr_cdf), out[0 .. 2] = rows, cell, logq.
+// Two sheets (squares and neighbour products), index tiles that advance by 15, per sample logq, the two hat values, the failure flag and
+// the hat cell (SqrState)
+template <class Pick>
+static int sqr_frame(ttx_engine *h, const char *who, int which, int64_t npts, const double *in, const double *const *nodes, const double *cond, double gamma, int32_t mode,
+                     double *rows, int32_t *cell, double *logq, double *val, bool dev, Pick pick)
 {
-    if (npts < 0 || (npts > 0 && (!u || !x || !nodes))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
+    if (npts < 0 || (npts > 0 && (!in || !rows || !nodes))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
     int rc = sq_check_mode_gamma(who, mode, gamma);
     if (rc || (rc = check_train_one_process(h, who)) || (rc = sr_check_nodes_cond(h, who, nodes, cond))) return rc;
     const int d = h->d;
     std::vector<int> fx(d, 0);
     if (nodes) for (int k = 0; k < d; k++) fx[k] = (cond && cond[k] == cond[k]) || h->n1[k + 1] == 1;
     std::vector<SrMode> modes(d);
-    SmStage out[4] = {{x, sizeof(double) * (size_t)d, SC_SRX, nullptr}, {cell, sizeof(int) * (size_t)d, SC_IND, nullptr}, {logq, sizeof(double), SC_LQ, nullptr},
+    SmStage out[4] = {{rows, sizeof(double) * (size_t)d, SC_SRX, nullptr}, {cell, sizeof(int) * (size_t)d, SC_IND, nullptr}, {logq, sizeof(double), SC_LQ, nullptr},
                       {val, sizeof(double), SC_OUT, nullptr}};
     const auto state = [](const SqAt &a) {
         SqrState st{a.state, nullptr, nullptr, nullptr, nullptr};
@@ -4264,7 +4269,7 @@ static int sqr_run(ttx_engine *h, const char *who, int64_t npts, const double *u
         st.fail = (int *)(st.f1 + a.chunk); st.ci = st.fail + a.chunk;
         return st;
     };
-    return sq_frame(h, who, SqKind{SMP_SQ_REAL, 2, 15, 3 * sizeof(double) + 2 * sizeof(int)}, npts, u, mode, dev, fx, out, 4,
+    return sq_frame(h, who, SqKind{which, 2, 15, 3 * sizeof(double) + 2 * sizeof(int)}, npts, in, mode, dev, fx, out, 4,
         [](const SqPlan &) { return (int)TTX_OK; },
         [&](const SqPlan &pl, SqHead &Qh) {
             // the bidiagonal factors: the mass matrix's Cholesky factor of a drawn mode, the hat row of a held one (a mode of one node is held at its node)
@@ -4289,12 +4294,19 @@ static int sqr_run(ttx_engine *h, const char *who, int64_t npts, const double *u
         [&](const SqAt &a, dim3 g) { hipLaunchKernelGGL(k_sqr_rows_exact, g, dim3(256), 0, h->stream, a.Hk, a.l, a.n, a.r1, a.Xo, a.ldx, a.C, a.S, a.S + a.sheet); },
         [&](const SqAt &a) {
             const SqrState st = state(a);
-            hipLaunchKernelGGL(k_sqr_pick, dim3(a.grid), dim3(256), 0, h->stream, a.n, a.k, d, modes[a.k], a.Q->fixed, a.Q->nodes, (const double *)(a.Q->g + a.k), (const double *)a.S,
-                               (const double *)(a.S + a.sheet), st, (long long)a.C, a.du, a.first, a.last, (double *)out[0].dev, (int *)out[1].dev, (double *)out[2].dev);
+            pick(a, modes[a.k], st, out);
             hipLaunchKernelGGL(k_sqr_step, dim3(a.grid), dim3(256), 0, h->stream, (const double *)core_dev(h, a.k + 1), h->RM, h->P.SS, a.r0, a.r1, a.n, st, a.Xo, a.Xn, a.ldx,
                                (long long)a.C, a.last, (double *)out[3].dev);
         },
         [&](size_t c, long long *dcnt) { hipLaunchKernelGGL(k_sr_count, dim3(1), dim3(1024), 0, h->stream, (long long)c, d, (const double *)out[0].dev, dcnt); });
+}
+static int sqr_run(ttx_engine *h, const char *who, int64_t npts, const double *u, const double *const *nodes, const double *cond, double gamma, int32_t mode, double *x,
+                   int32_t *cell, double *logq, double *val, bool dev)
+{
+    return sqr_frame(h, who, SMP_SQ_REAL, npts, u, nodes, cond, gamma, mode, x, cell, logq, val, dev, [&](const SqAt &a, const SrMode &M, const SqrState &st, const SmStage *out) {
+        hipLaunchKernelGGL(k_sqr_pick, dim3(a.grid), dim3(256), 0, h->stream, a.n, a.k, h->d, M, a.Q->fixed, a.Q->nodes, (const double *)(a.Q->g + a.k), (const double *)a.S,
+                           (const double *)(a.S + a.sheet), st, (long long)a.C, a.du, a.first, a.last, (double *)out[0].dev, (int *)out[1].dev, (double *)out[2].dev);
+    });
 }
 extern "C" int ttx_sample_sq_real(ttx_engine *h, int64_t npts, const double *u, const double *const *nodes, const double *cond, double gamma, int32_t mode, double *x,
                                   int32_t *cell, double *logq, double *val)
@@ -4309,6 +4321,31 @@ extern "C" int ttx_sample_sq_real_dev(ttx_engine *h, int64_t npts, const double 
 extern "C" int ttx_sample_sq_real_last(const ttx_engine *h, double *ms_head, double *ms_rows, double *ms_pick, double *flops, int64_t *nfailed, int32_t *mode_ran)
 {
     return sq_last(h, "ttx_sample_sq_real_last", SMP_SQ_REAL, ms_head, ms_rows, ms_pick, flops, nfailed, mode_ran);
+}
+
+// ---- the way back: the forward Rosenblatt map of the squared interpolant (k_sqr_cdf, ttx_sample_sq_real.h) -----------------------
+// x goes where the sampler's u goes; u is the output whose NaN rows are counted
+static int ros_run(ttx_engine *h, const char *who, int64_t npts, const double *x, const double *const *nodes, const double *cond, double gamma, int32_t mode, double *u,
+                   int32_t *cell, double *logq, double *val, bool dev)
+{
+    return sqr_frame(h, who, SMP_ROS_SQ_REAL, npts, x, nodes, cond, gamma, mode, u, cell, logq, val, dev, [&](const SqAt &a, const SrMode &M, const SqrState &st, const SmStage *out) {
+        hipLaunchKernelGGL(k_sqr_cdf, dim3(a.grid), dim3(256), 0, h->stream, a.n, a.k, h->d, M, a.Q->nodes, (const double *)(a.Q->g + a.k), (const double *)a.S,
+                           (const double *)(a.S + a.sheet), st, (long long)a.C, a.du, a.first, a.last, (double *)out[0].dev, (int *)out[1].dev, (double *)out[2].dev);
+    });
+}
+extern "C" int ttx_rosenblatt_sq_real(ttx_engine *h, int64_t npts, const double *x, const double *const *nodes, const double *cond, double gamma, int32_t mode, double *u,
+                                      int32_t *cell, double *logq, double *val)
+{
+    return ros_run(h, "ttx_rosenblatt_sq_real", npts, x, nodes, cond, gamma, mode, u, cell, logq, val, false);
+}
+extern "C" int ttx_rosenblatt_sq_real_dev(ttx_engine *h, int64_t npts, const double *x, const double *const *nodes, const double *cond, double gamma, int32_t mode, double *u,
+                                          int32_t *cell, double *logq, double *val)
+{
+    return ros_run(h, "ttx_rosenblatt_sq_real_dev", npts, x, nodes, cond, gamma, mode, u, cell, logq, val, true);
+}
+extern "C" int ttx_rosenblatt_sq_real_last(const ttx_engine *h, double *ms_head, double *ms_rows, double *ms_cdf, double *flops, int64_t *nfailed, int32_t *mode_ran)
+{
+    return sq_last(h, "ttx_rosenblatt_sq_real_last", SMP_ROS_SQ_REAL, ms_head, ms_rows, ms_cdf, flops, nfailed, mode_ran);
 }
 
 extern "C" int ttx_kernel_stats(const ttx_engine *h, int64_t launches[TTX_K_NKINDS], double ms[TTX_K_NKINDS], double bytes[TTX_K_NKINDS])

@@ -126,6 +126,27 @@ __device__ inline SmFound sm_wave_search(int n, double u, int lane, First first,
     return f;
 }
 
+// The way back (k_sqr_cdf): for a given position pos in 0 .. n-1, the same in every lane, total = c(n-1) and before = c(pos - 1)
+// (0.0 for pos = 0) of the inclusive running sum c of e(0 .. n-1), in sm_wave_search's association: a wave scan per round of 64, the
+// carry through lane 63.  total has the bits of the search's f.total and before those of its f.before for the same e.  One pass,
+// no search: every lane takes part and gets the same answer.  A pos outside 0 .. n-1 leaves before at 0.0.
+struct SmBefore { double total, before; };
+
+template <class Mass>
+__device__ inline SmBefore sm_wave_before(int n, int pos, int lane, Mass mass)
+{
+    SmBefore f{0.0, 0.0};
+    double carry = 0.0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const double c = carry + wave_scan(mass(i0 + lane), lane);
+        const int fl = pos - i0;                                                // wave-uniform: no lane diverges
+        if (fl >= 0 && fl < 64) f.before = fl ? __shfl(c, fl - 1) : carry;
+        carry = __shfl(c, 63);
+    }
+    f.total = carry;
+    return f;
+}
+
 // One wave per sample, grid-stride.  Dynamic LDS per wave: x[ldx], z[ldx], the sample's row of u [d], its index row [d] and the
 // row of p of the current mode [ldsrow]; nothing is shared between waves, so there is no workgroup barrier.  A mode longer than
 // ldsrow keeps its row in grow (growlen doubles per wave of the grid).  A lane reads back only the entries of the row it wrote

@@ -12,10 +12,14 @@
 //   k_sqr_pick         one wave per sample: the cell masses from the sheets, the scan and the search of k_sr_draw, the root of the
 //                      cubic inside the cell (sqr_invert), x_k, the cell and the hat values of the rounded x_k, the log term
 //   k_sqr_step         one wave per sample: the two-term chain step of k_sr_draw (sr_chain_step); the states stay in work space
+// The way back, ttx_rosenblatt_sq_real / _dev (x -> u, logq, val: the forward Rosenblatt map), is the same frame with one kernel exchanged:
+//   k_sqr_cdf          in k_sqr_pick's place, one wave per point: the hat cell and values of the GIVEN x_k, one pass of running sums over
+//                      the cell masses (sm_wave_before), the cubic inside the cell evaluated, not inverted (sqr_cdf), u_k, the log term
 // then k_sr_count (ttx_sample_real.h) counts the failed samples.  No atomics and no sum whose order depends on the grid, the chunk
 // or the other samples: a call repeats bit for bit.  Every index comes from lane numbers and counts, never from a value.
 // Open: per-sample weights, ranks above 128.
-// The first part of this file is plain C++ a host compiler accepts (tests/sample_sq_real_main.cpp runs it on the CPU).
+// The first part of this file is plain C++ a host compiler accepts (tests/sample_sq_real_main.cpp and tests/rosenblatt_main.cpp run it on
+// the CPU).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -77,6 +81,25 @@ TTX_SQR_HD double sqr_invert(double q0, double qm, double q1, double sp)
         l = ln;
     }
     return l;
+}
+
+// Q(l) h^-1 the other way round: the mass per unit length of the cell's density q (sqr_invert's q0, qm, q1) from the cell's left
+// node up to the position l, Q(l) = l (q0 + l ((qm - q0) + l (((q0 - 2 qm) + q1) / 3))) in the Horner form sqr_invert iterates on.
+// The three coefficients are scaled by sqr_invert's power of two, the result is scaled back by ldexp: the relative error has no
+// scale.  l <= 0 gives 0, l >= 1 the whole cell ((q0 + qm) + q1) / 3; anything that is not a number ends as 0.
+TTX_SQR_HD double sqr_cdf(double q0, double qm, double q1, double l)
+{
+    if (!(q0 == q0) || !(qm == qm) || !(q1 == q1) || !(l == l)) return 0.0;
+    double m = q0 > q1 ? q0 : q1;
+    const double am = fabs(qm);
+    m = am > m ? am : m;
+    if (!(m > 0.0) || m > 1.7976931348623157e308) return 0.0;
+    int e;
+    (void)frexp(m, &e);
+    q0 = ldexp(q0, -e); qm = ldexp(qm, -e); q1 = ldexp(q1, -e);
+    if (!(l > 0.0)) return 0.0;
+    const double Q = l >= 1.0 ? ((q0 + qm) + q1) / 3.0 : l * (q0 + l * ((qm - q0) + l * (((q0 - 2.0 * qm) + q1) / 3.0)));
+    return ldexp(Q, e);
 }
 
 #if defined(__HIPCC__)
@@ -178,6 +201,18 @@ __device__ inline double sqr_mass(const double *Sc, const double *Cc, const doub
     return j < nc ? sqr_cell(Sc, Cc, t, g, j, q0, qm, q1) : 0.0;
 }
 
+// the log term of a mode: the density at the hat values f0, f1 of the hat cell ci, with c(ci) clamped as in sqr_cell, over the total mass
+__device__ inline double sqr_log_term(const double *Sc, const double *Cc, double g, int ci, double f0, double f1, double total)
+{
+    const double s0 = Sc[ci], s1 = Sc[ci + 1], lim = sqrt(s0) * sqrt(s1);
+    double cc = Cc[ci];
+    cc = cc > lim ? lim : cc;
+    cc = cc < -lim ? -lim : cc;
+    double dens = (((f0 * f0) * s0 + ((2.0 * f0) * f1) * cc) + (f1 * f1) * s1) + g;
+    dens = dens > 0.0 ? dens : 0.0;
+    return log(dens / total);
+}
+
 // One wave per sample, grid-stride, one launch per mode (0-based k), in the frame of k_sq_pick.  A held mode forms nothing: its
 // coordinate goes to x and 0 to cell.  Otherwise the cell masses from the two sheets with lanes along j, then k_sr_draw's
 // search, clamps and placement (sm_wave_search, sr_mass_within, sr_place); a cell's mass is formed again in the search's second pass
@@ -212,13 +247,7 @@ __global__ __launch_bounds__(256) void k_sqr_pick(int n, int k, int d, SrMode M,
                     lam = sqr_invert(q0, qm, q1, sr_mass_within(f) / (t[cj + 1] - t[cj]));
                 }
                 xk = sr_place(t, n, cj, lam, ci, f0, f1);
-                const double s0 = Sc[ci], s1 = Sc[ci + 1], lim = sqrt(s0) * sqrt(s1);
-                double cc = Cc[ci];
-                cc = cc > lim ? lim : cc;
-                cc = cc < -lim ? -lim : cc;
-                double dens = (((f0 * f0) * s0 + ((2.0 * f0) * f1) * cc) + (f1 * f1) * s1) + g;
-                dens = dens > 0.0 ? dens : 0.0;
-                lq = lq + log(dens / f.total);
+                lq = lq + sqr_log_term(Sc, Cc, g, ci, f0, f1, f.total);
             }
         }
         if (lane == 0) {
@@ -232,6 +261,67 @@ __global__ __launch_bounds__(256) void k_sqr_pick(int n, int k, int d, SrMode M,
         }
         if (last && fail)
             for (int i = lane; i < d; i += 64) { xo[(size_t)p * d + i] = __builtin_nan(""); if (cell) cell[(size_t)p * d + i] = 0; }
+    }
+}
+
+// The way back (ttx_rosenblatt_sq_real), in k_sqr_pick's place and frame: one wave per point, grid-stride, one launch per mode.  The
+// coordinate x_k is given; a held mode forms nothing and writes u_k = 0.0 and cell 0.  Otherwise the hat cell ci of x_k
+// (sr_hat_cell; the wave's copy of x_k is made uniform first, so the search runs once on the scalar unit), its hat values by
+// sr_place's expressions, the cell masses from the two sheets with lanes along j, one pass of running sums (sm_wave_before), the
+// mass inside the cell (sqr_cdf) and the log term.  A coordinate that is NaN or outside [t_0, t_(n-1)], or a total that is 0, NaN or
+// Inf, fails the point.  ci lies in 0 .. n - 2 whatever x_k holds and is clamped again before the sheets are read.  The hat cell
+// and values go to work space, where k_sqr_step finds them.  first clears the point's state; last writes logq and, for a failed
+// point, the row of NaN in u and of zeros in cell.
+__global__ __launch_bounds__(256) void k_sqr_cdf(int n, int k, int d, SrMode M, const double *nodes, const double *gk, const double *S, const double *Cs, SqrState st,
+                                                 long long npts, const double *x, int first, int last, double *uo, int *cell, double *logq)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const double *t = nodes + M.noff;
+    const int nc = n - 1;
+    for (long long p = (long long)blockIdx.x * nw + wave; p < npts; p += (long long)gridDim.x * nw) {
+        bool fail = false;
+        double lq = 0.0;
+        if (!first) { fail = st.fail[p] != 0; lq = st.lq[p]; }
+        int ci = M.cell, co = 0;
+        double f0 = M.phi0, f1 = M.phi1, uk = 0.0;
+        if (!fail && !M.held) {
+            const double xk = lane_get(x[(size_t)p * d + k], 0);
+            if (!(xk >= t[0] && xk <= t[n - 1])) fail = true;                   // NaN, or outside the box
+            else {
+                const double *Sc = S + (size_t)p * n, *Cc = Cs + (size_t)p * n;
+                const double g = gk[0];
+                ci = sr_hat_cell(t, n, xk);
+                ci = ci < 0 ? 0 : ci > n - 2 ? n - 2 : ci;
+                const double t0 = t[ci], t1 = t[ci + 1];
+                f1 = (xk - t0) / (t1 - t0);
+                f0 = 1.0 - f1;
+                const SmBefore b = sm_wave_before(nc, ci, lane, [&](int j) { return sqr_mass(Sc, Cc, t, g, j, nc); });
+                if (!(b.total > 0.0) || b.total == __builtin_inf()) fail = true;    // 0, NaN or Inf
+                else {
+                    double q0, qm, q1;
+                    const double at = sqr_cell(Sc, Cc, t, g, ci, q0, qm, q1);
+                    double in = (t1 - t0) * sqr_cdf(q0, qm, q1, f1);
+                    in = in > 0.0 ? in : 0.0;
+                    in = in < at ? in : at;
+                    uk = (b.before + in) / b.total;
+                    uk = uk > 0.0 ? uk : 0.0;
+                    uk = uk < 1.0 ? uk : 1.0;
+                    co = ci + 1;
+                    lq = lq + sqr_log_term(Sc, Cc, g, ci, f0, f1, b.total);
+                }
+            }
+        }
+        if (lane == 0) {
+            st.fail[p] = fail ? 1 : 0; st.lq[p] = lq;
+            if (!fail) {
+                st.ci[p] = ci; st.f0[p] = f0; st.f1[p] = f1;
+                uo[(size_t)p * d + k] = uk;
+                if (cell) cell[(size_t)p * d + k] = co;
+            }
+            if (last && logq) logq[p] = fail ? __builtin_nan("") : lq;
+        }
+        if (last && fail)
+            for (int i = lane; i < d; i += 64) { uo[(size_t)p * d + i] = __builtin_nan(""); if (cell) cell[(size_t)p * d + i] = 0; }
     }
 }
 

@@ -14,6 +14,7 @@ runs on the GPU through ttcross_amd.engine.  Usage:
     python -m ttcross_amd.drivers samplereal WORKLOAD NPTS[,NPTS...] (real-valued samples from the interpolant of the workload's train: sample_real)
     python -m ttcross_amd.drivers samplesq WORKLOAD NPTS [MODE] [REPEATS] (samples from the square of the workload's train: sample_sq; WORKLOAD signed: importance weights)
     python -m ttcross_amd.drivers samplesqreal WORKLOAD NPTS [MODE] [REPEATS] (real-valued samples from the square of the interpolant: sample_sq_real; WORKLOAD signed: importance weights)
+    python -m ttcross_amd.drivers rosenblatt WORKLOAD NPTS [MODE] [REPEATS] (the way back: rosenblatt_sq_real at sample_sq_real's own points, timed next to it)
 
 devfun: the rational example integrand (examples/devfun/rational.hip) as a LOADED device integrand (TTX_FUN_DEVICE), in its
 wave form, or -- host -- its C twin through the host callback (TTX_FUN_HOST; needs gcc); SOURCE.hip NAME loads another
@@ -1076,6 +1077,42 @@ def run_samplesqreal(argv, device=0, repeats=5, tt=None):
     return out
 
 
+def run_rosenblatt(argv, device=0, repeats=5, tt=None):
+    """rosenblatt WORKLOAD NPTS [MODE] [REPEATS]: the way back of samplesqreal on the same trains, nodes and seeded device-made uniforms.
+    The points x are drawn with sample_sq_real (one warm-up and the median of `repeats` calls: the yardstick of the same session), then
+    rosenblatt_sq_real maps them back through the device-pointer entry, timed alike: the call, the head pass, the rows kernels and
+    k_sqr_cdf with the chain steps (HIP events, ttx_rosenblatt_sq_real_last), points per second, the fp64 rate of the rows next to the
+    sampler's, ms_cdf over the sampler's ms_pick, the largest |u' - min(u, 1)| over the points that did not fail and whether logq and
+    val repeated bit for bit.  One JSON line."""
+    import json
+    import torch
+    torch.cuda.init()          # a torch that brings its own HIP runtime must initialise its device before the engine's library does
+    workload, npts = argv[0], int(float(argv[1]))
+    mode = argv[2] if len(argv) > 2 else "auto"
+    repeats = int(argv[3]) if len(argv) > 3 else repeats
+    tt = tt or (signed_density_train(device) if workload == "signed" else tijk_train(workload, device=device))
+    dev = torch.device("cuda", device)
+    nodes = [np.linspace(0.0, 1.0, int(nk)) for nk in tt._n]
+    u = _seeded_uniforms(npts, tt.d, dev)
+    s, s_ms, s_med, s_last = _timed_calls(lambda: tt.sample_sq_real(u, nodes, mode=mode), tt.sample_sq_real_last, repeats)
+    x = s["x"].contiguous()
+    f, call_ms, med, last = _timed_calls(lambda: tt.rosenblatt_sq_real(x, nodes, mode=mode), tt.rosenblatt_sq_real_last, repeats)
+    ok = ~torch.isnan(f["u"][:, 0])
+    drawn = torch.tensor([int(nk) > 1 for nk in tt._n], device=dev)
+    err = torch.abs(f["u"] - torch.clamp(u, max=1.0))[ok][:, drawn]
+    same = lambda a, b: bool(torch.equal(a.view(torch.int64), b.view(torch.int64)))
+    rows_ms, s_rows_ms = med["ms_rows"], s_med["ms_rows"]
+    rec = dict(workload=workload, npts=npts, d=tt.d, max_rank=int(tt.ranks().max()), mode_asked=mode, mode=last["mode"], call_ms=call_ms,
+               ms_head=med["ms_head"], ms_rows=rows_ms, ms_cdf=med["ms_cdf"], points_per_s=npts / (call_ms * 1e-3), rows_flops=last["flops"],
+               rows_flops_per_s=last["flops"] / (rows_ms * 1e-3) if rows_ms > 0 else None, failed=last["failed"],
+               max_round_trip_error=float(err.max().item()) if err.numel() else None, logq_repeats=same(f["logq"], s["logq"]), val_repeats=same(f["val"], s["val"]),
+               sample_sq_real_call_ms=s_ms, sample_sq_real_ms_head=s_med["ms_head"], sample_sq_real_ms_rows=s_rows_ms, sample_sq_real_ms_pick=s_med["ms_pick"],
+               sample_sq_real_rows_flops_per_s=s_last["flops"] / (s_rows_ms * 1e-3) if s_rows_ms > 0 else None, sample_sq_real_failed=s_last["failed"],
+               cdf_over_pick=med["ms_cdf"] / s_med["ms_pick"] if s_med["ms_pick"] > 0 else None, time_ratio_to_sample_sq_real=call_ms / s_ms if s_ms > 0 else None)
+    print(json.dumps(rec), flush=True)
+    return [rec]
+
+
 def topk_train(workload, device=0):
     """The train of a topk run: a train of the tijk sub-command, or d64diff: the difference lincomb([1, -1], [exact, fast]) of the
     D_64 result trains in the two arithmetics, whose largest element is the max-norm error of the fast arithmetic; NAME+ort: the
@@ -1236,6 +1273,8 @@ if __name__ == "__main__":
         run_samplesq(sys.argv[2:])
     elif sys.argv[1] == "samplesqreal":
         run_samplesqreal(sys.argv[2:])
+    elif sys.argv[1] == "rosenblatt":
+        run_rosenblatt(sys.argv[2:])
     elif sys.argv[1] == "topk":
         run_topk(sys.argv[2:])
     elif sys.argv[1] == "contract":

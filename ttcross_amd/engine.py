@@ -142,6 +142,9 @@ def load_library():
                                      POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
     L.ttx_sample_sq_real_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(POINTER(c_double)), POINTER(c_double), c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
     L.ttx_sample_sq_real_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64), POINTER(c_int32)]
+    L.ttx_rosenblatt_sq_real.argtypes = L.ttx_sample_sq_real.argtypes
+    L.ttx_rosenblatt_sq_real_dev.argtypes = L.ttx_sample_sq_real_dev.argtypes
+    L.ttx_rosenblatt_sq_real_last.argtypes = L.ttx_sample_sq_real_last.argtypes
     L.ttx_topk.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_int32), c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
     L.ttx_topk_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
     L.ttx_zquad.argtypes = [c_void_p, c_int32, POINTER(c_double), POINTER(c_double)]
@@ -1135,6 +1138,36 @@ class TTCross:
         """dict(ms_head, ms_rows, ms_pick, flops, failed, mode) of the last sample_sq_real() on this engine (include/ttx.h:
         ttx_sample_sq_real_last); mode is "exact" or "mfma" (None before the first call)"""
         return self._rows_last(load_library().ttx_sample_sq_real_last)
+
+    # ---- the way back: the forward Rosenblatt map of the squared interpolant (include/ttx.h: ttx_rosenblatt_sq_real) -------
+    _ROSENBLATT = (("u", True, "float64", True), ("cell", True, "int32", False), ("logq", False, "float64", False), ("val", False, "float64", False))
+
+    def rosenblatt_sq_real(self, x, nodes, cond=None, gamma=0.0, mode="auto", want=("u", "cell", "logq", "val")):
+        """The forward Rosenblatt map of sample_sq_real()'s proposal at given points, on the device (include/ttx.h:
+        ttx_rosenblatt_sq_real): x (npts, d) -> the uniforms u that sample_sq_real maps to x, with logq, the log of the proposal's
+        density (g(x)^2 + gamma) / (Z + gamma V) at x, and val = g(x) = basis_batch(x, ("linear", nodes), "exact").  nodes, cond,
+        gamma and mode are sample_sq_real()'s and must be the ones the points are judged under.  Returns a dict with the entries
+        named in want: u (npts, d), 0.0 on a held mode; cell (npts, d) int32, the 1-based cell of x on a drawn mode and 0 on a held
+        one; logq (-inf in a cell without mass); val.  At sample_sq_real()'s own x, in the same mode, logq and val repeat bit for
+        bit.  A failed point (a drawn coordinate that is NaN or outside the nodes' range, a conditional without mass) has a row of
+        NaN in u, cell 0, logq NaN and val 0; rosenblatt_sq_real_last() counts them.  A contiguous float64 torch tensor on the
+        engine's device is passed by pointer (ttx_rosenblatt_sq_real_dev) and gives torch tensors on that device."""
+        L = load_library()
+        if type(x).__module__.split(".")[0] != "torch" and np.ndim(x) == 0:
+            raise ValueError(f"rosenblatt_sq_real: an array of shape (npts, {self.d}) expected")
+
+        def middle():
+            md = _eval_mode(mode)
+            _, rowp = self._node_rows(nodes, "rosenblatt_sq_real")
+            return rowp, _dp(self._held_entries(cond, "rosenblatt_sq_real", "cond", np.float64)), float(gamma), md
+        return self._sample_call("rosenblatt_sq_real", L.ttx_rosenblatt_sq_real, L.ttx_rosenblatt_sq_real_dev, self._ROSENBLATT, x, None, want, middle)
+
+    def rosenblatt_sq_real_last(self):
+        """dict(ms_head, ms_rows, ms_cdf, flops, failed, mode) of the last rosenblatt_sq_real() on this engine (include/ttx.h:
+        ttx_rosenblatt_sq_real_last), kept apart from sample_sq_real_last(); mode is "exact" or "mfma" (None before the first call)"""
+        r = self._rows_last(load_library().ttx_rosenblatt_sq_real_last)
+        r["ms_cdf"] = r.pop("ms_pick")
+        return {k: r[k] for k in ("ms_head", "ms_rows", "ms_cdf", "flops", "failed", "mode")}
 
     # ---- the largest elements of the resident train (include/ttx.h: ttx_topk) ----------------------------
     def topk(self, k, which="abs", fixed=None, mode="auto"):

@@ -80,6 +80,8 @@ module tt_lib
  interface sample_sq;   module procedure dtt_sample_sq;   end interface
  ! real points from the square of the interpolant: sample_sq_real(arg,u,nodes,x,cond,gamma,mode,cell,logq,val)
  interface sample_sq_real; module procedure dtt_sample_sq_real; end interface
+ ! the way back: the uniforms of given points under sample_sq_real's proposal: rosenblatt_sq_real(arg,x,nodes,u,cond,gamma,mode,cell,logq,val)
+ interface rosenblatt_sq_real; module procedure dtt_rosenblatt_sq_real; end interface
  ! the largest elements of the train with a bound on the rest, on the device (not in the reference): topk(arg,k,ind,val,bound,which,fixed,mode)
  interface topk;        module procedure dtt_topk;      end interface
  ! sums and elementwise products on the device (not in the reference; its host + and * above stay as they are):
@@ -637,6 +639,46 @@ contains
   call ttx_check(ttx_sample_sq_real(h,int(npts,c_int64_t),uu,rows,cp,gm,int(md,c_int32_t),xx,ip,lp,vp),'dtt_sample_sq_real')
   if(temp)call ttx_destroy(h)
   x(1:arg%m,1:npts)=xx
+  if(present(cell))then; cell(1:arg%m,1:npts)=cx; deallocate(cx); endif
+  deallocate(uu,xx,tt)
+ end subroutine
+ subroutine dtt_rosenblatt_sq_real(arg,x,nodes,u,cond,gamma,mode,cell,logq,val)
+  ! u(:,p) = the uniforms that sample_sq_real maps to the given point x(:,p): the forward Rosenblatt map of the squared interpolant
+  ! (include/ttx.h: ttx_rosenblatt_sq_real), with logq(p) the log of the proposal's density (g(x)^2 + gamma) / (Z + gamma V) at the
+  ! point and val(p) = g there.  nodes, cond, gamma, mode as for sample_sq_real.  u is 0 and cell 0 on a held mode; a point with a
+  ! drawn coordinate outside the nodes' range has a column of NaN in u.  A host train is staged for the call like for norm / dot_product.
+  use ttx_c
+  type(dtt),intent(in) :: arg
+  double precision,intent(in) :: x(:,:)
+  double precision,intent(in) :: nodes(:,:)
+  double precision,intent(out) :: u(:,:)
+  double precision,intent(in),optional :: cond(:),gamma
+  integer,intent(in),optional :: mode
+  integer,intent(out),optional :: cell(:,:)
+  double precision,intent(out),target,optional :: logq(:),val(:)
+  real(c_double),allocatable,target :: tt(:,:)
+  real(c_double),allocatable :: uu(:,:),xx(:,:)
+  integer(c_int32_t),allocatable,target :: cx(:,:)
+  real(c_double),target :: cc(tt_size)
+  type(c_ptr) :: h,cp,ip,lp,vp,rows(tt_size)
+  real(c_double) :: gm
+  logical :: temp
+  integer :: npts,k,md
+  npts=size(x,2)
+  if(npts.eq.0)return
+  cp=c_null_ptr; ip=c_null_ptr; lp=c_null_ptr; vp=c_null_ptr
+  gm=0.d0; if(present(gamma))gm=gamma
+  md=2; if(present(mode))md=mode
+  if(present(cond))then; cc(1:arg%m)=cond(1:arg%m); cp=c_loc(cc); endif
+  if(present(logq))lp=c_loc(logq)
+  if(present(val))vp=c_loc(val)
+  allocate(uu(arg%m,npts),xx(arg%m,npts),tt(maxval(arg%n(1:arg%m)),arg%m)); xx=x(1:arg%m,1:npts)
+  if(present(cell))then; allocate(cx(arg%m,npts)); ip=c_loc(cx); endif
+  do k=1,arg%m; tt(1:arg%n(k),k)=nodes(1:arg%n(k),k); rows(k)=c_loc(tt(1,k)); end do
+  call dtt_stage(arg,h,temp,'dtt_rosenblatt_sq_real')
+  call ttx_check(ttx_rosenblatt_sq_real(h,int(npts,c_int64_t),xx,rows,cp,gm,int(md,c_int32_t),uu,ip,lp,vp),'dtt_rosenblatt_sq_real')
+  if(temp)call ttx_destroy(h)
+  u(1:arg%m,1:npts)=uu
   if(present(cell))then; cell(1:arg%m,1:npts)=cx; deallocate(cx); endif
   deallocate(uu,xx,tt)
  end subroutine

@@ -226,6 +226,19 @@ module ttx_c
    import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms_head,ms_rows,ms_pick,flops; integer(c_int64_t),intent(out) :: nfailed
    integer(c_int32_t),intent(out) :: mode_ran; integer(c_int) :: rc
   end function
+  ! the way back of ttx_sample_sq_real (include/ttx.h): the points x in, the uniforms u out
+  function ttx_rosenblatt_sq_real(h,npts,x,nodes,cond,gamma,mode,u,cell,logq,val) bind(C,name='ttx_rosenblatt_sq_real') result(rc)
+   import; type(c_ptr),value :: h,cond,cell,logq,val; integer(c_int64_t),value :: npts; real(c_double),intent(in) :: x(*)
+   type(c_ptr),intent(in) :: nodes(*); real(c_double),value :: gamma; integer(c_int32_t),value :: mode; real(c_double),intent(out) :: u(*); integer(c_int) :: rc
+  end function
+  function ttx_rosenblatt_sq_real_dev(h,npts,x,nodes,cond,gamma,mode,u,cell,logq,val) bind(C,name='ttx_rosenblatt_sq_real_dev') result(rc)
+   import; type(c_ptr),value :: h,x,cond,u,cell,logq,val; integer(c_int64_t),value :: npts; type(c_ptr),intent(in) :: nodes(*)
+   real(c_double),value :: gamma; integer(c_int32_t),value :: mode; integer(c_int) :: rc
+  end function
+  function ttx_rosenblatt_sq_real_last(h,ms_head,ms_rows,ms_cdf,flops,nfailed,mode_ran) bind(C,name='ttx_rosenblatt_sq_real_last') result(rc)
+   import; type(c_ptr),value :: h; real(c_double),intent(out) :: ms_head,ms_rows,ms_cdf,flops; integer(c_int64_t),intent(out) :: nfailed
+   integer(c_int32_t),intent(out) :: mode_ran; integer(c_int) :: rc
+  end function
   ! the largest elements of the resident train (include/ttx.h); ind(d,K), val(K); fixed: c_null_ptr where not wanted
   function ttx_topk(h,k,which,fixed,mode,nfound,ind,val,bound) bind(C,name='ttx_topk') result(rc)
    import; type(c_ptr),value :: h,fixed; integer(c_int32_t),value :: k,which,mode; integer(c_int32_t),intent(out) :: nfound,ind(*)
