@@ -414,7 +414,7 @@ int ttx_mode_apply_last(const ttx_engine *h, double *ms, double *bytes_read, dou
  * train.  The engines are those ttx_ijk_batch takes: a multi-process engine is refused.
  * ttx_basis_last: of the last call on this engine, the milliseconds (HIP events) of the table launches and of the chain launches,
  * flops = 2 npts sum r(k-1) n(k) r(k), and the mode that ran (-1: none yet).  Any pointer may be NULL.
- * Open: the two-term LINEAR path, complex tables, derivative tables (gradients), ranks above 128.
+ * Open: the two-term LINEAR path, complex tables, ranks above 128.  The gradient is ttx_basis_grad_batch, below.
  * Added without a new ttx_version: look the symbols up. */
 #define TTX_BASIS_COS    1   /* phi_j(x) = c_j cos(j pi (x - a)/(b - a)), j = 0..n-1; c_0 = 0.5 with TTX_BASIS_HALVE_FIRST, else 1 */
 #define TTX_BASIS_LINEAR 2   /* hat functions on n strictly ascending nodes */
@@ -427,6 +427,50 @@ int ttx_basis_tab      (ttx_engine *h, int64_t npts, const double *phi /* [npts]
 int ttx_basis_tab_dev  (ttx_engine *h, int64_t npts, const double *phi_dev, double *out_dev, int32_t mode);
 int ttx_basis_host     (const ttx_basis *b, int32_t n, int64_t npts, const double *x, int64_t ldx, double *phi /* [npts][n] */);   /* no engine, no GPU */
 int ttx_basis_last     (const ttx_engine *h, double *ms_table, double *ms_chain, double *flops, int32_t *mode_ran);
+
+/* Value and gradient of the same f at a batch of real points, on the device (ttcross_amd/csrc/ttx_basis_grad.h).  f is linear in every
+ * table, so df/dx_m is the chain with mode m's table phi replaced by its derivative table dphi; with the states of one backward and
+ * one forward pass all d partial derivatives cost about three value chains.  E.g. the score of the ttx_sample_sq_real proposal,
+ * grad log q = 2 g grad g / (g^2 + gamma), from val = g and grad.
+ * Definition (numpy restates it: tests/basis_grad_ref.py).  phi_i(p, :) and dphi_i(p, :) are the table rows of mode i, U_i(a, j, k) is
+ * core i, r(i-1) x n(i) x r(i).  Multiply and add are always separate.
+ *   Backward, i = d .. 1, from x = (1):  t_j(a) = sum_k U_i(a, j, k) x(k),                    summed from 0.0 over ascending k;
+ *                                        z(a) = sum_j phi_j t_j(a), e(a) = sum_j dphi_j t_j(a), summed from 0.0 over ascending j;
+ *                                        D_i = e;  x = z;   val = z(1) after mode 1: the operation sequence of ttx_basis_batch.
+ *   Forward, i = 1 .. d, from l = (1):   grad_i = sum_a l(a) D_i(a),        summed from 0.0 over ascending a;
+ *                                        s_j(k) = sum_a l(a) U_i(a, j, k),  summed from 0.0 over ascending a;
+ *                                        l(k) <- sum_j phi_j s_j(k),        summed from 0.0 over ascending j (not formed after mode d).
+ * val[npts] (may be NULL) is bit-identical to ttx_basis_batch / ttx_basis_tab on the same tables in the same effective mode, in
+ * both modes.  grad[npts][d], mode 1 first (may not be NULL).
+ *   mode : TTX_EVAL_EXACT  the order above, one wave per point: bit-identical to the numpy restatement
+ *          TTX_EVAL_MFMA   both passes on the fp64 matrix cores: equal to EXACT to rounding.  A point's results depend on its own table
+ *                          rows and on a fixed order only, never on its neighbours, the chunk, the store budget or npts; a call
+ *                          repeats bit for bit
+ *          TTX_EVAL_AUTO   by the flops of the call, 6 npts sum r(k-1) n(k) r(k) (ttx_basis_grad_last tells what ran)
+ * Derivative tables.  ttx_basis_grad_batch forms phi as ttx_basis_batch does and dphi beside it:
+ *   TTX_BASIS_COS     y, arg_j and the NaN rule of phi_j (a non-finite coordinate or |arg_j| > 2^19 makes dphi_j NaN); dphi_0 = 0.0;
+ *                     otherwise dphi_j = -(((double)j * w) * sin(arg_j)) with the project's own sine (ttx_sin).  TTX_BASIS_HALVE_FIRST
+ *                     touches j = 0 only, which is 0.0 anyway.
+ *   TTX_BASIS_LINEAR  the derivative of the branch phi takes: a NaN coordinate gives a NaN row; n = 1, x <= t_0 or x >= t_(n-1): all
+ *                     0.0; otherwise with i the last node with t_i <= x and s = 1.0 / (t_(i+1) - t_i): dphi_(i+1) = s, dphi_i = -s,
+ *                     every other entry 0.0.  At an interior node this is the RIGHT-HAND derivative; on and outside the end nodes
+ *                     the interpolant is constant and the derivative 0.
+ * ttx_basis_host_d writes the same derivative tables on the host (no engine, no GPU), dphi[j + n p] = dphi_j(x[ldx p]); the device
+ * tables equal it bit for bit.  ttx_basis_grad_tab takes the caller's own tables, two arrays in ttx_basis_tab's layout: any
+ * differentiable basis works.  The _dev entries are as for ttx_basis_batch_dev.
+ * The backward pass keeps D_i of every mode of a chunk, S = sum_k r(k-1) doubles per point.  A chunk is the smaller of
+ * TTX_BASIS_CHUNK (or its default) and the largest multiple of 256 points with 8 S chunk <= TTX_BASIS_GRAD_STORE bytes (environment;
+ * default 2^32), at least 256.  Argument checks and refusals are those of ttx_basis_batch.
+ * ttx_basis_grad_last: of the last call on this engine, the milliseconds (HIP events) of the table, backward and forward launches,
+ * flops = 6 npts sum r(k-1) n(k) r(k), the mode that ran (-1: none yet) and the points per chunk.  Any pointer may be NULL.
+ * Open: second derivatives, gradients with respect to cores, a fused score entry for the samplers, ranks above 128.
+ * Added without a new ttx_version: look the symbols up. */
+int ttx_basis_grad_batch    (ttx_engine *h, int64_t npts, const double *x /* [npts][d] */, const ttx_basis *basis /* [d] */, double *val, double *grad /* [npts][d] */, int32_t mode);
+int ttx_basis_grad_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, double *val_dev, double *grad_dev, int32_t mode);
+int ttx_basis_grad_tab      (ttx_engine *h, int64_t npts, const double *phi, const double *dphi /* [npts][sum n(k)] each */, double *val, double *grad, int32_t mode);
+int ttx_basis_grad_tab_dev  (ttx_engine *h, int64_t npts, const double *phi_dev, const double *dphi_dev, double *val_dev, double *grad_dev, int32_t mode);
+int ttx_basis_host_d        (const ttx_basis *b, int32_t n, int64_t npts, const double *x, int64_t ldx, double *dphi /* [npts][n] */);   /* no engine, no GPU */
+int ttx_basis_grad_last     (const ttx_engine *h, double *ms_table, double *ms_back, double *ms_fwd, double *flops, int32_t *mode_ran, int64_t *chunk_ran);
 
 /* Samples drawn from the resident train by sequential conditional sampling, on the device (ttcross_amd/csrc/ttx_sample.h).
  * Modes are 1-based, G_k is core k, r_0 = r_d = 1.

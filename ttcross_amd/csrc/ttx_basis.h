@@ -12,7 +12,8 @@
 //   MFMA  (k_bs_gemm<MR>): one step is the GEMM Z = U_(r0 x (n r1)) B with B = the row-wise Kronecker product phi_j(p) x_k(p), formed
 //          in registers; v_mfma_f64_16x16x4_f64.  A point's value depends on its own column and on the fixed order (j ascending, k
 //          ascending in quads) only: never on its neighbours, the tile, the chunk or npts.
-// Open: a two-term path for TTX_BASIS_LINEAR (version one sums its table densely), complex tables, derivative tables, ranks > 128.
+// Open: a two-term path for TTX_BASIS_LINEAR (version one sums its table densely), complex tables, ranks > 128.
+// The gradient (derivative tables, ttx_basis_dentry below) is ttx_basis_grad.h.
 #pragma once
 #include "ttx_coscoeff.h"   // ttx_cos, TTX_TRIG_MAX, TTX_COSCOEFF_PI, TTX_CC_HD: host and device
 
@@ -37,6 +38,27 @@ TTX_CC_HD double ttx_basis_entry(int kind, int flags, double a, double w, const 
     if (x >= nodes[n - 1]) return j == n - 1 ? 1.0 : 0.0;
     if (j >= 1 && nodes[j - 1] <= x && x < nodes[j]) return (x - nodes[j - 1]) / (nodes[j] - nodes[j - 1]);           // i = j - 1: lambda
     if (j <= n - 2 && nodes[j] <= x && x < nodes[j + 1]) return 1.0 - (x - nodes[j]) / (nodes[j + 1] - nodes[j]);   // i = j: 1 - lambda
+    return 0.0;
+}
+
+// dphi_j / dx of one mode, the derivative tables of include/ttx.h (ttx_basis_grad_batch, ttx_basis_host_d), the arguments of
+// ttx_basis_entry.  COS: the y, arg and NaN rule of ttx_basis_entry; TTX_BASIS_HALVE_FIRST touches j = 0 only, which is 0.0 anyway.
+// LINEAR: the derivative of the branch ttx_basis_entry takes, so at an interior node the right-hand derivative
+TTX_CC_HD double ttx_basis_dentry(int kind, int flags, double a, double w, const double *nodes, int n, double x, int j)
+{
+    (void)flags;
+    if (kind == 1) {                                    // TTX_BASIS_COS
+        const double y = (x - a) * w;
+        const double arg = (double)j * y;
+        const double aa = arg < 0.0 ? -arg : arg;
+        if (!(aa <= TTX_TRIG_MAX)) return __builtin_nan("");
+        if (j == 0) return 0.0;
+        return -(((double)j * w) * ttx_sin(arg));
+    }
+    if (x != x) return __builtin_nan("");
+    if (n == 1 || x <= nodes[0] || x >= nodes[n - 1]) return 0.0;
+    if (j >= 1 && nodes[j - 1] <= x && x < nodes[j]) return 1.0 / (nodes[j] - nodes[j - 1]);           // i = j - 1: d lambda
+    if (j <= n - 2 && nodes[j] <= x && x < nodes[j + 1]) return -(1.0 / (nodes[j + 1] - nodes[j]));   // i = j: d (1 - lambda)
     return 0.0;
 }
 

@@ -50,6 +50,7 @@
 #include "ttx_contract.h"
 #include "ttx_modeapply.h"
 #include "ttx_basis.h"
+#include "ttx_basis_grad.h"
 #include "ttx_algebra.h"
 #include "ttx_roundsum.h"
 #include "ttx_sample.h"
@@ -138,6 +139,7 @@ enum {
     SC_RSM, SC_RSTAB,                   // ttx_lincomb_round: M = Q^T Y (first the coefficients), the descriptor tables (RsBlk) and Omega's offsets
     SC_QH, SC_QF, SC_QS, SC_QX,         // ttx_sample_sq: the tables H_k, the factors F_k (then the exponent and the d defensive terms), a mode's sheet (two for ttx_sample_sq_real), the states (two buffers, logq, flags)
     SC_BTAB,                            // ttx_basis_batch: the table of one mode for one chunk, chunk x max n (its states go to SC_XA / SC_XB, its nodes to SC_META)
+    SC_GST,                             // ttx_basis_grad_batch: the state store, the rows D_i of all modes of a chunk (its tables go to SC_BTAB, its states to SC_XA / SC_XB)
     SC_NBUF
 };
 struct EvBuf { void *p = nullptr; size_t bytes = 0; };
@@ -193,6 +195,7 @@ struct RsLast {                                                                 
     int mode = -1;
 };
 struct BsLast { double ms[2] = {0.0, 0.0}, flops = 0.0; int mode = -1; };      // ttx_basis_batch / ttx_basis_tab: table launches, chain launches
+struct BgLast { double ms[3] = {0.0, 0.0, 0.0}, flops = 0.0; int mode = -1; int64_t chunk = 0; };     // ttx_basis_grad_batch / ttx_basis_grad_tab: table, backward, forward launches
 
 struct DevFun;                          // a loaded device integrand (TTX_FUN_DEVICE), defined with slot_eval
 struct TrainFun;                        // the operands and the combiner of TTX_FUN_TRAINS, defined with slot_eval
@@ -294,6 +297,7 @@ struct ttx_engine {
     TkLast tk;
     RsLast rs;
     BsLast bs;
+    BgLast bg;
     std::vector<hipEvent_t> op_ev;                      // OpMarks' events: ttx_lincomb_round, the squared samplers, the basis evaluations
 };
 
@@ -3889,6 +3893,161 @@ extern "C" int ttx_basis_last(const ttx_engine *h, double *ms_table, double *ms_
     if (ms_chain) *ms_chain = h->bs.ms[BSM_CHAIN];
     if (flops) *flops = h->bs.flops;
     if (mode_ran) *mode_ran = h->bs.mode;
+    return TTX_OK;
+}
+
+// ---- value and gradient of the train in a function basis (ttx_basis_grad.h) ------------------------------------------------------
+extern "C" int ttx_basis_host_d(const ttx_basis *b, int32_t n, int64_t npts, const double *x, int64_t ldx, double *dphi)
+{
+    const char *who = "ttx_basis_host_d";
+    if (!b || n < 1 || npts < 0 || ldx < 1 || (npts > 0 && (!x || !dphi))) return fail(TTX_EINVAL, "%s: null argument, n < 1, npts < 0 or ldx < 1", who);
+    if (int rc = bs_check_one(who, 1, *b, n)) return rc;
+    const double w = b->kind == TTX_BASIS_COS ? ttx_basis_cos_w(b->a, b->b) : 0.0;
+    for (int64_t p = 0; p < npts; p++)
+        for (int j = 0; j < n; j++) dphi[(size_t)p * n + j] = ttx_basis_dentry(b->kind, b->flags, b->a, w, b->nodes, n, x[(size_t)p * ldx], j);
+    return TTX_OK;
+}
+// bytes of the state store of a gradient call, from the environment (read on every call) or the default
+static size_t env_grad_store()
+{
+    if (const char *e = getenv("TTX_BASIS_GRAD_STORE")) { const long long v = atoll(e); if (v >= 1) return (size_t)v; }
+    return TTX_BG_STORE_DEFAULT;
+}
+enum { BGM_TABLE, BGM_BACK, BGM_FWD };      // OpMarks phases of a call, BgLast::ms takes the sums
+// in: the coordinates, or the caller's phi with din its dphi; val may be null
+static int bg_run(ttx_engine *h, const char *who, BsSrc src, int64_t npts, const double *in, const double *din, const ttx_basis *basis, double *val, double *grad, int32_t mode)
+{
+    const bool tab = src == BS_TAB_HOST || src == BS_TAB_DEV, dev = src == BS_X_DEV || src == BS_TAB_DEV;
+    int rc = tt_prepare(h, who);
+    if (rc) return rc;
+    if (npts < 0 || (npts > 0 && (!in || !grad || (tab ? !din : !basis)))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
+    if (!op_mode_known(mode)) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    const int d = h->d;
+    if (!tab && basis) for (int k = 1; k <= d; k++) if ((rc = bs_check_one(who, k, basis[k - 1], h->n1[k]))) return rc;
+    const BgPlan pl = bg_plan(d, h->n1.data() + 1, h->rfinal.data(), dev_ncu(h), src, npts, mode, env_chunk("TTX_BASIS_CHUNK", op_chunk_default(h->RM)), env_grad_store());
+    if (pl.refusal == BS_RANK) return fail(TTX_EINVAL, "%s: ranks up to 128 only (got %d)", who, pl.rmax);
+    if (pl.refusal == BS_BOUNDARY) return fail(TTX_EINVAL, "%s: boundary ranks are not 1", who);
+    h->bg = BgLast();
+    h->bg.flops = pl.flops; h->bg.mode = pl.eff; h->bg.chunk = (int64_t)pl.chunk;
+    if (npts == 0) return TTX_OK;
+    EvTrain T;
+    if ((rc = ev_train(h, &T))) return rc;
+    // the nodes of the LINEAR modes, one device block
+    std::vector<BsMode> M(d);
+    if (!tab) {
+        OpMeta meta(h->meta_host);
+        std::vector<size_t> o_nodes(d, 0);
+        for (int k = 0; k < d; k++)
+            if (basis[k].kind == TTX_BASIS_LINEAR) o_nodes[k] = meta.put(std::vector<double>(basis[k].nodes, basis[k].nodes + h->n1[k + 1]));
+        char *dm = nullptr;
+        if (!meta.host.empty() && (rc = meta.upload(h, SC_META, &dm))) return rc;
+        for (int k = 0; k < d; k++) {
+            const ttx_basis &b = basis[k];
+            const bool cosk = b.kind == TTX_BASIS_COS;
+            M[k] = BsMode{b.kind, b.flags, h->n1[k + 1], cosk ? b.a : 0.0, cosk ? ttx_basis_cos_w(b.a, b.b) : 0.0, cosk ? nullptr : (const double *)(dm + o_nodes[k])};
+        }
+    }
+    if ((rc = buf_reserve(h, {{SC_XA, pl.b_xa}, {SC_XB, pl.b_xb}, {SC_BTAB, pl.b_btab}, {SC_X, pl.b_x}, {SC_OUT, pl.b_out}, {SC_GST, pl.b_gst}}))) return rc;
+    double *btab = buf<double>(h, SC_BTAB), *dtab = btab + pl.chunk * pl.nmax, *sin_ = buf<double>(h, SC_X), *sout = buf<double>(h, SC_OUT);
+    double *gst = buf<double>(h, SC_GST), *XA = buf<double>(h, SC_XA), *XB = buf<double>(h, SC_XB);
+    OpMarks marks(h->op_ev);
+    for (int64_t o = 0; o < npts; o += (int64_t)pl.chunk) {
+        const int c = (int)std::min<int64_t>((int64_t)pl.chunk, npts - o);
+        const double *cin = in + (size_t)o * pl.row, *cdin = tab ? din + (size_t)o * pl.row : nullptr;
+        double *cval = val ? val + o : nullptr, *cgrad = grad + (size_t)o * d;
+        if (!dev) {
+            HIPCHECK(hipMemcpyAsync(sin_, cin, sizeof(double) * (size_t)c * pl.row, hipMemcpyHostToDevice, h->stream));
+            cin = sin_;
+            if (tab) {
+                HIPCHECK(hipMemcpyAsync(sin_ + pl.chunk * pl.row, cdin, sizeof(double) * (size_t)c * pl.row, hipMemcpyHostToDevice, h->stream));
+                cdin = sin_ + pl.chunk * pl.row;
+            }
+            cval = val ? sout : nullptr; cgrad = sout + pl.chunk;
+        }
+        if ((rc = marks.mark(h->stream, OpMarks::DISCARD))) return rc;
+        // the table of mode i where the call forms it (dphi only on the way back), else the caller's rows
+        const double *ph = nullptr, *dh = nullptr;
+        size_t ld = 0;
+        auto tables = [&](int i, bool both) {
+            ph = cin + pl.off[i]; dh = tab ? cdin + pl.off[i] : nullptr; ld = pl.sumn;
+            if (tab) return TTX_OK;
+            hipLaunchKernelGGL(k_bg_table, g1((size_t)c * M[i].n), dim3(256), 0, h->stream, M[i], (long long)c, cin + i, d, btab, both ? dtab : (double *)nullptr);
+            ph = btab; dh = dtab; ld = (size_t)M[i].n;
+            return marks.mark(h->stream, BGM_TABLE);
+        };
+        double *X = XA, *Z = XB;
+        for (int i = d - 1; i >= 0; i--) {                                      // backward: z and e of every mode, D_i into the store
+            if ((rc = tables(i, true))) return rc;
+            const double *Xin = i == d - 1 ? nullptr : X;
+            double *Di = gst + pl.soff[i] * pl.chunk;
+            const int last = i == 0;
+            if (pl.eff == TTX_EVAL_EXACT)
+                hipLaunchKernelGGL(k_bg_exact_back, dim3(pl.g_exact(c)), dim3(256), pl.lds_back, h->stream, T, i, (long long)c, ph, dh, ld, Xin, Z, Di, cval, last);
+            else
+                with_tier<true>(pl.step[i].tier, [&](auto mr) {
+                    hipLaunchKernelGGL((k_bg_gemm<decltype(mr)::value, false>), dim3(pl.g_back(i, c)), dim3(256), pl.step[i].lds_back, h->stream,
+                                       T, i, c, ph, dh, ld, Xin, Z, Di, cval, (double *)nullptr, d, last);
+                    return 0;
+                });
+            if ((rc = marks.mark(h->stream, BGM_BACK))) return rc;
+            std::swap(X, Z);
+        }
+        X = XA; Z = XB;
+        for (int i = 0; i < d; i++) {                                           // forward: grad_i = l . D_i, then l through mode i
+            const int last = i == d - 1;
+            if (!last) { if ((rc = tables(i, false))) return rc; } else { ph = cin; ld = 0; }     // mode d forms no new state: no table is read
+            const double *Lin = i == 0 ? nullptr : X;
+            double *Di = gst + pl.soff[i] * pl.chunk;
+            if (pl.eff == TTX_EVAL_EXACT)
+                hipLaunchKernelGGL(k_bg_exact_fwd, dim3(pl.g_exact(c)), dim3(256), pl.lds_fwd, h->stream, T, i, (long long)c, ph, ld, Lin, Z, Di, cgrad, d, last);
+            else
+                with_tier<true>(pl.step[i].tier, [&](auto mr) {
+                    hipLaunchKernelGGL((k_bg_gemm<decltype(mr)::value, true>), dim3(pl.g_fwd(i, c)), dim3(256), pl.step[i].lds_fwd, h->stream,
+                                       T, i, c, ph, (const double *)nullptr, ld, Lin, Z, Di, (double *)nullptr, cgrad, d, last);
+                    return 0;
+                });
+            if ((rc = marks.mark(h->stream, BGM_FWD))) return rc;
+            std::swap(X, Z);
+        }
+        if (!dev) {
+            if (val) HIPCHECK(hipMemcpyAsync(val + o, sout, sizeof(double) * (size_t)c, hipMemcpyDeviceToHost, h->stream));
+            HIPCHECK(hipMemcpyAsync(grad + (size_t)o * d, sout + pl.chunk, sizeof(double) * (size_t)c * d, hipMemcpyDeviceToHost, h->stream));
+        }
+        if (!dev || marks.phase.size() > 4096) {                                // the staging blocks are reused by the next chunk; the event chain stays short
+            HIPCHECK(hipStreamSynchronize(h->stream));
+            if ((rc = marks.sum(h->bg.ms))) return rc;
+        }
+    }
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    if ((rc = marks.sum(h->bg.ms))) return rc;
+    HIPCHECK(hipGetLastError());
+    return TTX_OK;
+}
+extern "C" int ttx_basis_grad_batch(ttx_engine *h, int64_t npts, const double *x, const ttx_basis *basis, double *val, double *grad, int32_t mode)
+{
+    return bg_run(h, "ttx_basis_grad_batch", BS_X_HOST, npts, x, nullptr, basis, val, grad, mode);
+}
+extern "C" int ttx_basis_grad_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, double *val_dev, double *grad_dev, int32_t mode)
+{
+    return bg_run(h, "ttx_basis_grad_batch_dev", BS_X_DEV, npts, x_dev, nullptr, basis, val_dev, grad_dev, mode);
+}
+extern "C" int ttx_basis_grad_tab(ttx_engine *h, int64_t npts, const double *phi, const double *dphi, double *val, double *grad, int32_t mode)
+{
+    return bg_run(h, "ttx_basis_grad_tab", BS_TAB_HOST, npts, phi, dphi, nullptr, val, grad, mode);
+}
+extern "C" int ttx_basis_grad_tab_dev(ttx_engine *h, int64_t npts, const double *phi_dev, const double *dphi_dev, double *val_dev, double *grad_dev, int32_t mode)
+{
+    return bg_run(h, "ttx_basis_grad_tab_dev", BS_TAB_DEV, npts, phi_dev, dphi_dev, nullptr, val_dev, grad_dev, mode);
+}
+extern "C" int ttx_basis_grad_last(const ttx_engine *h, double *ms_table, double *ms_back, double *ms_fwd, double *flops, int32_t *mode_ran, int64_t *chunk_ran)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_basis_grad_last: null engine");
+    if (ms_table) *ms_table = h->bg.ms[BGM_TABLE];
+    if (ms_back) *ms_back = h->bg.ms[BGM_BACK];
+    if (ms_fwd) *ms_fwd = h->bg.ms[BGM_FWD];
+    if (flops) *flops = h->bg.flops;
+    if (mode_ran) *mode_ran = h->bg.mode;
+    if (chunk_ran) *chunk_ran = h->bg.chunk;
     return TTX_OK;
 }
 

@@ -150,6 +150,74 @@ inline BsPlan bs_plan(int d, const int *n, const int *r, int ncu, BsSrc src, int
     return p;
 }
 
+// ---- ttx_basis_grad_batch, ttx_basis_grad_tab and their _dev forms (ttx_basis_grad.h) ---------------------------------------------
+// break-even of TTX_EVAL_AUTO in flops per call (6 npts sum r0 n r1).  PROVISIONAL: equal to TTX_BS_AUTO_FLOPS until the break-even of
+// the gradient call itself is measured (profiles/basis_grad_mi355x.txt says what was and what was not).
+#define TTX_BG_AUTO_FLOPS TTX_BS_AUTO_FLOPS
+#define TTX_BG_LDT 20               // leading dimension of the forward step's panel image, (k, ac) at TTX_BG_LDT k + ac: 16 columns, and
+                                    // 20 col + kq (col < 8, kq < 4) meets every residue mod 32 once
+#define TTX_BG_STORE_DEFAULT ((size_t)1 << 32)      // bytes of the state store where TTX_BASIS_GRAD_STORE names none (provisional: 32768 points per chunk at S = 16 k)
+// column tiles of 16 per wave of the backward step, whose accumulators are two sets (states 8 MR CT registers, accumulators 16 MR CT):
+// chosen per tier from the compiler's resource report (profiles/basis_grad_mi355x.txt) so that no tier has scratch.  An a fragment from
+// LDS already feeds two MFMAs per column tile, so the narrower tiles cost no LDS bandwidth that the matrix cores would wait for.  No tier
+// needs a second pass for the dphi operand.  bg_waves: the waves per SIMD the register allocator is held to -- two wherever the kernel
+// then still has no scratch.  The backward step of MR = 4 is the exception: with one column tile and two waves it spills (956 bytes per
+// lane), so it keeps two column tiles and one wave (299 registers); MR >= 6 (forward: 7) needs more than 256 registers in any case.
+TTX_OP_HD constexpr int bg_ct(int MR) { return MR <= 1 ? 4 : MR <= 4 ? 2 : 1; }
+TTX_OP_HD constexpr int bg_waves(int MR, bool fwd) { return fwd ? (MR <= 6 ? 2 : 1) : (MR <= 3 || MR == 5) ? 2 : 1; }
+TTX_OP_HD size_t bg_fwd_lds(int q1) { return sizeof(double) * 2 * (size_t)TTX_BG_LDT * ((q1 + 15) & ~15); }
+
+// k_bg_gemm<tier, *> of a 0-based mode: 16 tier >= max(r0, r1); points per workgroup and LDS of the backward and of the forward step
+struct BgStep { int tier = 1, tp_back = 256, tp_fwd = 256; size_t lds_back = 0, lds_fwd = 0; };
+struct BgPlan {
+    BsRefusal refusal = BS_OK;
+    int rmax = 1, eff = TTX_EVAL_EXACT, ldx = 4, ncu = 0;
+    std::vector<size_t> off;                // where a mode's rows start in a point's row of the caller's tables
+    std::vector<size_t> soff;               // where a mode's row D_i starts among the S doubles of a point in the state store
+    size_t sumn = 0, nmax = 1, S = 0, chunk = 0, row = 0;                       // row: doubles per point of the input (of each table)
+    double flops = 0.0;
+    size_t b_xa = 0, b_xb = 0, b_btab = 0, b_x = 0, b_out = 0, b_gst = 0;       // bytes of SC_*; 0: the call does not use the slot
+    size_t lds_back = 0, lds_fwd = 0;       // k_bg_exact_back: per wave x; k_bg_exact_fwd: per wave l and D_i's row
+    std::vector<BgStep> step;
+    int g_exact(int c) const { return wave_grid(c, ncu); }
+    int g_back(int i, int c) const { return (c + step[i].tp_back - 1) / step[i].tp_back; }
+    int g_fwd(int i, int c) const { return (c + step[i].tp_fwd - 1) / step[i].tp_fwd; }
+};
+// n[0 .. d-1], r[0 .. d]; chunk: TTX_BASIS_CHUNK or the default; store: TTX_BASIS_GRAD_STORE or the default, bytes
+inline BgPlan bg_plan(int d, const int *n, const int *r, int ncu, BsSrc src, int64_t npts, int mode, size_t chunk, size_t store)
+{
+    const bool tab = src == BS_TAB_HOST || src == BS_TAB_DEV, dev = src == BS_X_DEV || src == BS_TAB_DEV;
+    BgPlan p;
+    p.rmax = *std::max_element(r, r + d + 1); p.ncu = ncu;
+    if (p.rmax > 128) { p.refusal = BS_RANK; return p; }
+    if (r[0] != 1 || r[d] != 1) { p.refusal = BS_BOUNDARY; return p; }
+    double w = 0.0;
+    p.off.resize(d); p.soff.resize(d); p.step.resize(d);
+    for (int k = 0; k < d; k++) {
+        w += (double)r[k] * n[k] * r[k + 1];
+        p.off[k] = p.sumn; p.sumn += (size_t)n[k]; p.nmax = std::max(p.nmax, (size_t)n[k]);
+        p.soff[k] = p.S; p.S += (size_t)r[k];
+        BgStep &s = p.step[k];
+        s.tier = (std::max(r[k], r[k + 1]) + 15) / 16;
+        s.tp_back = 64 * bg_ct(s.tier); s.tp_fwd = 64 * bs_ct(s.tier);
+        s.lds_back = bs_gemm_lds(r[k]); s.lds_fwd = bg_fwd_lds(r[k + 1]);
+    }
+    p.flops = 6.0 * (double)npts * w;
+    p.eff = op_mode_eff(mode, p.flops, TTX_BG_AUTO_FLOPS);
+    p.ldx = op_ldx(d, r);
+    // the store holds S doubles per point: the largest multiple of 256 points under the budget, at least one tile of 256
+    const size_t fit = std::max<size_t>(256, store / (sizeof(double) * p.S) / 256 * 256);
+    p.chunk = std::min<size_t>(std::min(chunk, fit), (size_t)std::max<int64_t>(npts, 0));
+    if (src == BS_TAB_HOST) p.chunk = std::min(p.chunk, std::max<size_t>(1, ((size_t)1 << 25) / p.sumn));     // the staged rows of each of the caller's tables
+    p.row = tab ? p.sumn : (size_t)d;
+    p.b_xa = p.b_xb = sizeof(double) * p.chunk * p.ldx;
+    p.b_gst = sizeof(double) * p.chunk * p.S;
+    if (!tab) p.b_btab = sizeof(double) * 2 * p.chunk * p.nmax;                 // phi, then dphi
+    if (!dev) { p.b_x = sizeof(double) * (tab ? 2 : 1) * p.chunk * p.row; p.b_out = sizeof(double) * p.chunk * ((size_t)d + 1); }    // val, then grad
+    p.lds_back = 4 * sizeof(double) * (size_t)p.ldx; p.lds_fwd = 2 * p.lds_back;
+    return p;
+}
+
 // ---- ttx_topk (ttx_topk.h) -----------------------------------------------------------------------------------------------------------
 #define TTX_TK_KMAX 4096            // largest K
 #define TTX_TK_SHEET (1 << 24)      // largest sheet K max n_k

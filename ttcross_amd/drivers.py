@@ -731,6 +731,107 @@ def run_basis(argv, device=0, repeats=5, tt=None, basis=None, host_npts=1000):
     return tt, x, out, res
 
 
+def basis_grad_host(tt, x, basis):
+    """what a user does without ttx_basis_grad_batch, the host route: every core to the host with core(k), the tables from
+    basis_table and basis_dtable, the chain of basis_host right to left with the rows D_k kept (the same product summed against
+    dphi), then the prefix vectors left to right and grad_k = prefix_k . D_k, one numpy product per mode and pass (BLAS order, so
+    equal to the device to rounding only).  Returns (val, grad)."""
+    from .engine import basis_dtable, basis_table
+    x = np.asarray(x, dtype=np.float64)
+    if isinstance(basis, (tuple, list)) and basis and isinstance(basis[0], str):
+        basis = [basis] * tt.d
+    cores = [tt.core(k) for k in range(1, tt.d + 1)]
+    phis = [basis_table(basis[k], g.shape[1], x[:, k]) for k, g in enumerate(cores)]
+    v = np.ones((x.shape[0], 1))
+    D = [None] * tt.d
+    for k in range(tt.d - 1, -1, -1):
+        g = cores[k]
+        r0, n, r1 = g.shape
+        t = (v @ g.reshape(r0 * n, r1).T).reshape(x.shape[0], r0, n)
+        D[k] = np.einsum("paj,pj->pa", t, basis_dtable(basis[k], n, x[:, k]))
+        v = np.einsum("paj,pj->pa", t, phis[k])
+    grad = np.zeros((x.shape[0], tt.d))
+    pre = np.ones((x.shape[0], 1))
+    for k in range(tt.d):
+        g = cores[k]
+        r0, n, r1 = g.shape
+        grad[:, k] = np.einsum("pa,pa->p", pre, D[k])
+        if k + 1 < tt.d:
+            pre = np.einsum("pjk,pj->pk", (pre @ g.reshape(r0, n * r1)).reshape(x.shape[0], n, r1), phis[k])
+    return v[:, 0], grad
+
+
+def run_basisgrad(argv, device=0, repeats=5, tt=None, basis=None, host_npts=1000, subst_npts=10000, subst_repeats=None):
+    """basisgrad WORKLOAD NPTS [KIND] [MODE]: the workloads, kinds and modes of the basis sub-command.  On the same seeded points
+    (drawn on the device) and in the same session: one warm-up and `repeats` timed basis_grad_batch calls through the
+    device-pointer entry, the same for one basis_batch call, the substitution route (d basis_tab calls, each with one mode's table
+    replaced by its derivative table, tables formed on the host beforehand and not timed) on the first `subst_npts` points, and the
+    host route (basis_grad_host) on the first `host_npts`.  Prints one JSON line with the medians and the ratios
+    (subst_over_grad_same_npts: the substitution route's time per point over the gradient call's time per point;
+    max_rel_diff_to_subst compares the modes listed in subst_modes_checked only, the ones whose tables were built)."""
+    import json
+    import time
+    import torch
+    from .engine import basis_dtable, basis_table
+    torch.cuda.init()          # a torch that brings its own HIP runtime must initialise its device before the engine's library does
+    workload, npts = argv[0], int(float(argv[1]))
+    kind = argv[2] if len(argv) > 2 else "linear"
+    mode = argv[3] if len(argv) > 3 else "auto"
+    if tt is None:
+        tt, basis = basis_train(workload, device=device)
+    if basis is None:
+        basis = [("linear", np.linspace(0.0, 1.0, int(nk))) if kind == "linear" and nk > 1 else ("cos", 0.0, 1.0) for nk in tt._n]
+        lo, hi = 0.0, 1.0
+    else:
+        lo, hi = basis[1], basis[2]
+    entries = [basis] * tt.d if isinstance(basis[0], str) else list(basis)
+    dev = torch.device("cuda", device)
+    g = torch.Generator(device=dev)
+    g.manual_seed(20240607)
+    x = (lo + (hi - lo) * torch.rand((npts, tt.d), dtype=torch.float64, device=dev, generator=g)).contiguous()
+    torch.cuda.synchronize(dev)
+
+    def timed(call, reps=repeats):
+        out = call()                                # warm-up
+        ms = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            out = call()                            # synchronises before it returns
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return out, float(np.median(ms)), [round(v, 4) for v in ms]
+
+    (val, grad), ms_grad, all_grad = timed(lambda: tt.basis_grad_batch(x, basis, mode))
+    last = tt.basis_grad_last()
+    vb, ms_val, all_val = timed(lambda: tt.basis_batch(x, basis, last["mode"]))
+    res = dict(workload=workload, npts=npts, kind=entries[0][0], mode_asked=mode, mode=last["mode"], chunk=last["chunk"], d=tt.d,
+               max_rank=int(tt.ranks().max()), ms_grad=ms_grad, ms_grad_all=all_grad, ms_table=last["ms_table"], ms_back=last["ms_back"],
+               ms_fwd=last["ms_fwd"], flops=last["flops"], ms_basis_batch=ms_val, ms_basis_batch_all=all_val, ratio_to_basis_batch=ms_grad / ms_val,
+               val_is_basis_batch=bool(torch.equal(val, vb)), nan=int(torch.isnan(grad).sum().item()), checksum=float(grad.sum().item()))
+    sp = min(npts, subst_npts)
+    if sp > 0:
+        xs = x[:sp].cpu().numpy()
+        phis = [basis_table(e, int(nk), xs[:, k]) for k, (e, nk) in enumerate(zip(entries, tt._n))]
+        dphis = [basis_dtable(e, int(nk), xs[:, k]) for k, (e, nk) in enumerate(zip(entries, tt._n))]
+        tabs = [torch.from_numpy(np.ascontiguousarray(np.hstack([dphis[k] if k == m else phis[k] for k in range(tt.d)]))).to(dev) for m in range(min(tt.d, 2))]
+        torch.cuda.synchronize(dev)
+        # every call of the route costs the same: two distinct substituted tables are cycled through the d calls
+        _, ms_sub, _ = timed(lambda: [tt.basis_tab(tabs[m % len(tabs)], last["mode"]) for m in range(tt.d)][-1], subst_repeats or repeats)
+        gs = grad[:sp].cpu().numpy()
+        first = np.stack([tt.basis_tab(tabs[m], last["mode"]).cpu().numpy() for m in range(len(tabs))], axis=1)
+        res.update(subst_npts=sp, ms_subst_route=ms_sub, subst_modes_checked=list(range(1, len(tabs) + 1)), subst_over_grad_same_npts=(ms_sub / sp) / (ms_grad / npts),
+                   max_rel_diff_to_subst=float(np.max(np.abs(gs[:, :len(tabs)] - first)) / max(float(np.max(np.abs(first))), 1e-300)))
+    hp = min(npts, host_npts)
+    if hp > 0:
+        xh = x[:hp].cpu().numpy()
+        t0 = time.perf_counter()
+        _, ref = basis_grad_host(tt, xh, basis)
+        res["host_route_npts"] = hp
+        res["host_route_ms"] = (time.perf_counter() - t0) * 1e3
+        res["max_rel_diff_to_host_route"] = float(np.max(np.abs(grad[:hp].cpu().numpy() - ref)) / max(float(np.max(np.abs(ref))), 1e-300))
+    print(json.dumps(res))
+    return tt, x, (val, grad), res
+
+
 def sample_host(tt, u, w=None):
     """what a user does without ttx_sample: every core to the host with core(k), then the conditional marginals walked in
     numpy from the last mode to the first.  Returns (ind, logq, val) of the definition in include/ttx.h, in numpy's own
@@ -1285,6 +1386,8 @@ if __name__ == "__main__":
         run_modeapply(sys.argv[2:])
     elif sys.argv[1] == "basis":
         run_basis(sys.argv[2:])
+    elif sys.argv[1] == "basisgrad":
+        run_basisgrad(sys.argv[2:])
     elif sys.argv[1] == "chf":
         run_chf(sys.argv[2:])
     elif sys.argv[1] == "pdf":

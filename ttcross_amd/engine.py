@@ -127,6 +127,12 @@ def load_library():
     L.ttx_basis_tab_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_int32]
     L.ttx_basis_host.argtypes = [POINTER(_Basis), c_int32, c_int64, POINTER(c_double), c_int64, POINTER(c_double)]
     L.ttx_basis_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
+    L.ttx_basis_grad_batch.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(_Basis), POINTER(c_double), POINTER(c_double), c_int32]
+    L.ttx_basis_grad_batch_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(_Basis), c_void_p, c_void_p, c_int32]
+    L.ttx_basis_grad_tab.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), c_int32]
+    L.ttx_basis_grad_tab_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32]
+    L.ttx_basis_host_d.argtypes = [POINTER(_Basis), c_int32, c_int64, POINTER(c_double), c_int64, POINTER(c_double)]
+    L.ttx_basis_grad_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_int64)]
     L.ttx_sample.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
     L.ttx_sample_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(c_double), POINTER(c_int32), c_void_p, c_void_p, c_void_p]
     L.ttx_sample_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
@@ -254,6 +260,17 @@ def basis_table(entry, n, x):
     phi = np.zeros((xa.size, int(n)))
     _check(load_library().ttx_basis_host(ctypes.byref(b), int(n), xa.size, _dp(xa), 1, _dp(phi)))
     return phi
+
+
+def basis_dtable(entry, n, x):
+    """The derivative table of one mode on the host (include/ttx.h: ttx_basis_host_d): dphi[p, j] = dphi_j/dx (x[p]) for a basis
+    entry as basis_table takes it; for "linear" the right-hand derivative at an interior node, 0 on and outside the end nodes.
+    The device forms the same numbers bit for bit.  No engine, no GPU."""
+    b, _keep = _basis_struct(entry, n)
+    xa = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    dphi = np.zeros((xa.size, int(n)))
+    _check(load_library().ttx_basis_host_d(ctypes.byref(b), int(n), xa.size, _dp(xa), 1, _dp(dphi)))
+    return dphi
 
 
 def trapezoid_weights(nodes):
@@ -968,6 +985,71 @@ class TTCross:
         _check(load_library().ttx_basis_last(self._h, ctypes.byref(mt), ctypes.byref(mc), ctypes.byref(fl), ctypes.byref(md)))
         names = {v: k for k, v in EVAL_MODES.items()}
         return dict(ms_table=mt.value, ms_chain=mc.value, flops=fl.value, mode=names.get(md.value))
+
+    # ---- its gradient (include/ttx.h: ttx_basis_grad_batch) ----------------------------------------------
+    def basis_grad_batch(self, x, basis, mode="auto"):
+        """(val, grad) of f at real points x (npts, d) (include/ttx.h: ttx_basis_grad_batch): val (npts,) is basis_batch(x, basis)
+        bit for bit in the mode that ran, grad (npts, d) holds df/dx_m, mode 1 first.  basis, mode and the two kinds of x (host
+        array -> numpy arrays, float64 tensor on the engine's device -> tensors, by pointer) are basis_batch's; basis_grad_last()
+        tells what ran.  The score of the sample_sq_real proposal is 2 val grad / (val^2 + gamma)."""
+        L, md = load_library(), _eval_mode(mode)
+        if isinstance(basis, (tuple, list)) and basis and isinstance(basis[0], str):
+            basis = [basis] * self.d
+        basis = list(basis)
+        if len(basis) != self.d:
+            raise ValueError(f"basis_grad_batch: {self.d} basis entries expected (got {len(basis)})")
+        pairs = [_basis_struct(e, self._n[k]) for k, e in enumerate(basis)]
+        arr = (_Basis * self.d)(*[p[0] for p in pairs])          # pairs keeps the node arrays alive
+        val = self._dev_pair("basis_grad_batch", x, self.d)
+        if val is not None:
+            import torch
+            grad = torch.empty((x.shape[0], self.d), dtype=torch.float64, device=x.device)
+            _check(L.ttx_basis_grad_batch_dev(self._h, x.shape[0], c_void_p(x.data_ptr()), arr, c_void_p(val.data_ptr()), c_void_p(grad.data_ptr()), md))
+            return val, grad
+        if type(x).__module__.split(".")[0] == "torch":
+            x = x.numpy()
+        xa = np.ascontiguousarray(x, dtype=np.float64)
+        if xa.ndim != 2 or xa.shape[1] != self.d:
+            raise ValueError(f"basis_grad_batch: an array of shape (npts, {self.d}) expected")
+        val, grad = np.zeros(xa.shape[0]), np.zeros((xa.shape[0], self.d))
+        _check(L.ttx_basis_grad_batch(self._h, xa.shape[0], _dp(xa), arr, _dp(val), _dp(grad), md))
+        return val, grad
+
+    def basis_grad_tab(self, phi, dphi, mode="auto"):
+        """The same with the caller's own tables (include/ttx.h: ttx_basis_grad_tab): phi and dphi (npts, sum n) each, in
+        basis_tab's layout; any differentiable basis works.  Host arrays, or two torch tensors on the engine's device (read in
+        place, ttx_basis_grad_tab_dev)."""
+        L, md = load_library(), _eval_mode(mode)
+        sumn = int(self._n.sum())
+        val = self._dev_pair("basis_grad_tab", phi, sumn)
+        if val is not None:
+            import torch
+            if self._dev_pair("basis_grad_tab", dphi, sumn) is None or dphi.shape != phi.shape:
+                raise ValueError("basis_grad_tab: phi and dphi must be tensors of one shape on the engine's device")
+            grad = torch.empty((phi.shape[0], self.d), dtype=torch.float64, device=phi.device)
+            _check(L.ttx_basis_grad_tab_dev(self._h, phi.shape[0], c_void_p(phi.data_ptr()), c_void_p(dphi.data_ptr()), c_void_p(val.data_ptr()),
+                                            c_void_p(grad.data_ptr()), md))
+            return val, grad
+        tabs = []
+        for t in (phi, dphi):
+            if type(t).__module__.split(".")[0] == "torch":
+                t = t.cpu().numpy()
+            tabs.append(np.ascontiguousarray(t, dtype=np.float64))
+        pa, da = tabs
+        if pa.ndim != 2 or pa.shape[1] != sumn or da.shape != pa.shape:
+            raise ValueError(f"basis_grad_tab: two arrays of shape (npts, {sumn}) expected")
+        val, grad = np.zeros(pa.shape[0]), np.zeros((pa.shape[0], self.d))
+        _check(L.ttx_basis_grad_tab(self._h, pa.shape[0], _dp(pa), _dp(da), _dp(val), _dp(grad), md))
+        return val, grad
+
+    def basis_grad_last(self):
+        """dict(ms_table, ms_back, ms_fwd, flops, mode, chunk) of the last basis_grad_batch / basis_grad_tab on this engine
+        (include/ttx.h: ttx_basis_grad_last); mode is "exact" or "mfma" (None before the first call), chunk the points per chunk"""
+        mt, mb, mf, fl, md, ck = c_double(), c_double(), c_double(), c_double(), c_int32(), c_int64()
+        _check(load_library().ttx_basis_grad_last(self._h, ctypes.byref(mt), ctypes.byref(mb), ctypes.byref(mf), ctypes.byref(fl), ctypes.byref(md),
+                                                  ctypes.byref(ck)))
+        names = {v: k for k, v in EVAL_MODES.items()}
+        return dict(ms_table=mt.value, ms_back=mb.value, ms_fwd=mf.value, flops=fl.value, mode=names.get(md.value), chunk=ck.value)
 
     # ---- samples from the resident train (include/ttx.h: ttx_sample and its three siblings) --------------
     # the outputs of the index samplers and of the real samplers: name, a row of d per sample (else one number), dtype, always allocated
