@@ -848,6 +848,11 @@ int ttx_arith(const ttx_engine *h);
  * (its workgroups must all be resident at once; the launch is cooperative and gated by the occupancy calculator, so this
  * is a safety net: after a fallback the engine stays on the chain path; results are identical on every path) */
 int ttx_cluster_fallbacks(const ttx_engine *h);
+/* the entry of a cluster launch: out[0] the forms in force as bits -- 1 the generator's jump powers from a table (TTX_CL_POWTAB=0
+ * turns it off), 2 the generator word carried from the launch before (TTX_CL_WORD=0), 4 the sorted pivot lists carried from the
+ * launch before (TTX_CL_LISTS=0) -- and, of the last run's launches of local group 0, out[1] those that took the carried lists and
+ * out[2] those that took the carried word.  All 0 off the cluster path.  Results are identical in every form. */
+int ttx_cluster_entry(const ttx_engine *h, int64_t out[3]);
 /* runs of this engine that were repeated without the wave teams / the wave relay of the Ising D/E half-step because a launch
  * reported a fault (more units than the grid the host sized, a broken hand-over); results are identical on every path */
 int ttx_det_fallbacks(const ttx_engine *h);

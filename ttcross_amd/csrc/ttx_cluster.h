@@ -191,6 +191,13 @@ __device__ __forceinline__ bool cluster_sync(unsigned *ctr, unsigned target, int
 #define CST_DECL const bool t_me = (threadIdx.x == 0 && g == 0 && cb == 0); long long t_prev = wall_clock64()
 #define CST(k) do { if (t_me) { long long t_now = wall_clock64(); gs.stamp[0][k] += t_now - t_prev; t_prev = t_now; } } while (0)
 #define CST_END() do { if (t_me) gs.nstamp[0]++; } while (0)
+// the entry and the exit of a launch, thread 0 of blocks 0 and 1 of group 0: GroupState::stamp[1][8 cb + k] of group 0 -- k = 0 kernel
+// start to behind the staging of par, the start of the sweep and their barrier, 1 the pivot lists (rebuilt or loaded), 2 the generator powers and the
+// state loads (top of the first bond step), 3 (block 0) from behind the last cluster_sync to behind exch_pack_group
+#define CSE_DECL const int t_eb = (threadIdx.x == 0 && g == 0 && cb <= 1) ? cb : -1; long long t_eprev = wall_clock64()
+#define CSE_MARK() do { if (t_eb >= 0) t_eprev = wall_clock64(); } while (0)
+#define CSE(k) do { if (t_eb >= 0) { long long t_now = wall_clock64(); P.gs[0].stamp[1][8 * t_eb + (k)] += t_now - t_eprev; t_eprev = t_now; } } while (0)
+#define CSE_END() do { if (t_eb == 0) P.gs[0].nstamp[1]++; } while (0)
 // per-wave timeline of ONE bond step (launch 8, step 4, group 0): slot k of half-step h of wave (cb, wv)
 #define WST(k) do { if (P.dbg && g == 0 && epoch == 8 && pp == 4 && lane == 0 && h < 8) P.dbg[((size_t)(h * 64 + cb * 4 + wv)) * 8 + (k)] = (long long)__builtin_readcyclecounter(); } while (0)
 #else
@@ -198,7 +205,25 @@ __device__ __forceinline__ bool cluster_sync(unsigned *ctr, unsigned target, int
 #define CST_DECL
 #define CST(k)
 #define CST_END()
+#define CSE_DECL
+#define CSE_MARK()
+#define CSE(k)
+#define CSE_END()
 #endif
+
+// The forms of the launch entry, bits of the kernel's argument `zkeep` (the host sets them: launch_sweep_kernel):
+#define CL_ZKEEP 1      // the sorted distinct pivot lists of every own bond stay in LDS for the whole launch
+#define CL_ZCARRY 2     // ... and travel from launch to launch through the group's image in global memory (TTX_CL_LISTS=0: rebuilt per launch)
+#define CL_WORD 4       // the generator word is taken from the launch before (TTX_CL_WORD=0: raised from rngpos per launch)
+#define CL_POWTAB 8     // the generator's jump powers come from cl_powtab (TTX_CL_POWTAB=0: three square-and-multiply loops per launch)
+static_assert(CL_POWTAB_N == CB, "one table entry per thread of a workgroup");
+__device__ const ClPowTab cl_powtab = cl_make_powtab();
+// the kernel's argument block as the launch lays it out (k_sweep_cluster's parameter list): the exit reads it afresh
+struct ClArgs { DevProb P; int dir, nsteps, NB, ldsinv, epoch, zkeep; };
+// Image of a group's pivot lists, the LDS layout word for word ([nsteps][2][RM] keys, [nsteps][2] counts): behind the record buffers
+// of cl_part, so that the kernel takes no further argument and DevProb no further field (its scalar registers are short as it is)
+__device__ __forceinline__ int *cl_zimage(const DevProb &P, int g, int nsteps)
+{ return (int *)(P.cl_part + (size_t)2 * P.G * TTX_CLREC) + (size_t)g * cl_zimage_ints(nsteps, P.RM); }
 
 // CFAST: the closed form of TTX_ARITH=fast (f_ising_cfast) instead of the chains; CPAD: rows padded to whole chunks with neutral
 // elements and f_ising_c4w instead of f_ising_c4p.  Both are fixed for the life of an engine, so they are compiled in: the exact
@@ -222,6 +247,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
     __shared__ struct { int ii, jj, kk, qq, hcount, rc_k, rc_q, rr_i, rr_j; double pivot, amax, bytes_half; long long neval, n_resid; } s_rook;
     const int bid = blockIdx.x;
     const int g = (bid & 7) + 8 * (bid / (8 * NB)), cb = (bid >> 3) % NB;     // cluster of group g lives on XCD g % 8
+    CSE_DECL;
     if (g >= P.G || P.ctl[0]) return;
     // Summary on the side stream (ttx_dev.h: tail_side): the rule of sweep epoch-1 has not been written to ctl[0] for certain yet, so
     // every block applies it itself to the same records -- the job-wide maxima of group 0's record with its corner maximum, and the
@@ -274,9 +300,27 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
     for (int x = tid; x < P.npar; x += CB) par[x] = P.par[x];
     // (sweep_start also puts -1 into gs.pivotmax / gs.pivotmin, which this kernel keeps in registers and writes at its end: they
     // differ from before only after an aborted launch, whose run is replayed from k_reset on the chain path)
-    if (cb == 0 && tid == 0) sweep_start(P, g);
+    // The start of the sweep (sweep_start of ttx_bondstep.h) by the whole of block 0, one rank per thread: one thread's loop over the
+    // d + 1 ranks held block 0 -- and with it every block of the cluster at the first record exchange -- for about 6.5 us per launch
+    // at d = 63.  r[] is first rewritten behind further barriers of this block (append_scalars).
+    if (cb == 0) {
+        if (tid == 0) { gs.pivotmax = -1.0; gs.pivotmin = -1.0; }
+        int *rr = P.rr + (size_t)g * (m + 2);
+        for (int s = tid; s <= m; s += CB) rr[s] = r[s];
+    }
     __syncthreads();
-    if (zkeep) {
+    CSE(0);
+    // The lists are exactly what this workgroup held when the launch before ended (built once, extended at every accepted pivot; nobody
+    // else writes the pivot sets of own bonds between two launches of a run), and block 0 left them in the group's image with its launch
+    // number: taken from there, one round trip.  The first launch of a run, a launch behind one that did not end regularly, and
+    // TTX_CL_LISTS=0 rebuild them from vip.  (Block 0 rewrites image and tag at its END, behind a cluster_sync every block has passed.)
+    if ((zkeep & CL_ZCARRY) && cl_lists_valid(gs.zk_epoch, epoch)) {
+        const int *img = cl_zimage(P, g, nsteps);
+        for (int x = tid; x < nbonds * 2 * RM; x += CB) ZK[x] = img[x];
+        for (int x = tid; x < 2 * nbonds; x += CB) ZN[x] = img[(size_t)nsteps * 2 * RM + x];
+        if (cb == 0 && tid == 0) gs.n_zload++;
+        __syncthreads();
+    } else if (zkeep & CL_ZKEEP) {
         int *TMP = (int *)XL;                          // XL is staged later; free scratch for now: [nsteps][2][RM]
         const int E = nbonds * 2 * RM;
         for (int x = tid; x < E; x += CB) {            // raw keys
@@ -321,14 +365,24 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
     unsigned long long rngpos = gs.rngpos;
     double bytes_half = gs.bytes_half; long long n_resid = gs.n_resid;
     int hcount = 0;                                    // half-steps exchanged so far (selects the record buffer)
-    const unsigned long long bil0 = ttx_minstd_pow(2ull * tid);     // RNG jump of this thread's first lottery candidate
-    unsigned long long sA0 = ttx_minstd_pow(2 * rngpos + 1);
+    CSE(1);
+    // The generator's powers: 48271^(2 t) from the compile-time table (cl_powtab), and the running word 48271^(2 rngpos + 1) from the
+    // launch before, which held it in a register when it wrote gs.rngpos (cl_word_valid).  Else by square-and-multiply, as before.
+    const bool ptab = (zkeep & CL_POWTAB) != 0;
+    const unsigned long long bil0 = ptab ? cl_powtab.v[tid] : ttx_minstd_pow(2ull * tid);     // RNG jump of this thread's first lottery candidate
+    unsigned long long sA0;
+    {
+        const unsigned long long cw = gs.rngword, cwpos = gs.rngword_pos;
+        if ((zkeep & CL_WORD) && cl_word_valid(cw, cwpos, rngpos)) { sA0 = cw; if (cb == 0 && tid == 0) gs.n_wload++; }
+        else sA0 = ttx_minstd_pow(2 * rngpos + 1);
+    }
     // the generator step of a bond step, 48271^(2 nlot), without the square-and-multiply loop per step (8 rounds of two 64-bit
     // products on every lane): lane l keeps 48271^(2 l), and 48271^(2 (64 a + b)) = 48271^(2 b) * (48271^128)^a -- one lane
     // exchange and a <= 7 products below 512 candidates (the same residue: modular products are exact).  The bound 512 is
     // reasoned, not measured: the loop runs about ten rounds of two products for such nlot, so seven products are still fewer.
-    const int bl0 = (int)ttx_minstd_pow(2ull * lane);
-    const unsigned long long c64 = ttx_minstd_pow(128);
+    const int bl0 = ptab ? (int)cl_powtab.v[lane] : (int)ttx_minstd_pow(2ull * lane);
+    constexpr unsigned long long c64 = cl_minstd_pow_c(128);        // entry 64 of the table, a literal in every form
+    CSE(2);
     CST_DECL;
 
     for (int pp = 1; pp <= nsteps; pp++) {
@@ -389,7 +443,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
             if (p < last)  { const double *gU = inv_ptr(P, g, p + 1, first); for (int x = tid; x < r2 * r2; x += CB) GU[x] = gU[x]; }
         }
         CST(0);
-        if (zkeep) seg_issue(r0 * n1 - ZN[2 * (p - first)], n2 * r2 - ZN[2 * (p - first) + 1]);
+        if (zkeep & CL_ZKEEP) seg_issue(r0 * n1 - ZN[2 * (p - first)], n2 * r2 - ZN[2 * (p - first) + 1]);
         // The slice bounds of this bond step as a table, one division each, on a wave that has no prefix chain to run: lanes
         // 0..16 of wave 3 hold floor(c n1 / NB), lanes 17..33 floor(c n2 / NB), c = min(lane, NB) (slices behind the last are
         // empty); lane c then takes the participating waves of workgroup c from the widths of its two slices.  Read behind the
@@ -406,13 +460,9 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         // generator words of the two draw columns: 48271^(2*rngpos+1) and 48271^(2*(rngpos+nlot)+1), advanced from
         // step to step by the small power 48271^(2*nlot) (every thread keeps them; no shared state, no barrier)
         if (tid == 0) s_ok = 1;                            // (read behind the rook loop; several barriers lie in between)
-        unsigned long long stepmul;
-        if (nlot < 512) {
-            stepmul = (unsigned long long)(unsigned)__shfl(bl0, nlot & 63);
-            for (int a = 0; a < (nlot >> 6); a++) stepmul = ttx_mulmod31(stepmul, c64);
-        } else stepmul = ttx_minstd_pow(2ull * nlot);       // (modes in the hundreds: as before)
+        const unsigned long long stepmul = cl_stepmul(nlot, [&](int b) { return (unsigned long long)(unsigned)__shfl(bl0, b); }, c64);
         const unsigned long long sA1 = ttx_mulmod31(sA0, stepmul);
-        if (zkeep) {
+        if (zkeep & CL_ZKEEP) {
             const int b = p - first;
             const int *kc = ZK + (size_t)b * 2 * RM, *kr = kc + RM;
             if (tid == 0) { nzc = ZN[2 * b]; nzr = ZN[2 * b + 1]; }
@@ -424,7 +474,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         const int Kc = r0 * n1 - nzc, Kr = n2 * r2 - nzr;
         // (waves 2 and 3 store their segment while waves 0 and 1 run the prefix chains; without zkeep the lengths are known only
         // here, so nothing is hidden, but count and row still come in one round trip instead of two)
-        if (!zkeep) seg_issue(Kc, Kr);
+        if (!(zkeep & CL_ZKEEP)) seg_issue(Kc, Kr);
         if (tid >= 128) {
             ttx_cdfseg *dst = sside ? segr : segc;
             if (sseg < myns) { dst[sseg].a0 = sg_a0; dst[sseg].alast = sg_al; dst[sseg].delta = sg_de; dst[sseg].k0 = sg_k0; dst[sseg].cnt = sg_cn; }
@@ -781,7 +831,7 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
                 append_tables_store(P, g, p, first, r1, ii, jj, kk, qq, tid, CB, tab);
                 if (tid == 0) append_scalars(P, g, p, first, r1, ii, jj, kk, qq, pivot);
             }
-            if (zkeep && wv < 2) {                     // keep the sorted distinct lists of this bond current:
+            if ((zkeep & CL_ZKEEP) && wv < 2) {                     // keep the sorted distinct lists of this bond current:
                 const int b = p - first;               // wave 0 inserts the pivot row, wave 1 the pivot column (RM <= 64)
                 int *kl = ZK + (size_t)b * 2 * RM + (size_t)wv * RM;
                 const int nl = ZN[2 * b + wv];
@@ -803,13 +853,31 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         CST(15);
         CST_END();
     }
+    CSE_MARK();
     if (cb == 0) {
+        // what the next launch's entry takes instead of recomputing it: the pivot lists as they stand (the last insertion lies in front of
+        // the closing cluster_sync) with this launch's number, and the generator word of the position written below.  Reached only by a
+        // launch that ran all its bond steps: an abort, the stopping rule and ctl[0] return above.
+        // (The arguments are read afresh from the kernel's argument block here: taken from the registers of the bond loop they lengthen
+        // live ranges across it, and every instantiation spills 10 scalar registers more: profiles/cluster_entry_mi355x.txt.)
+        const ClArgs *K = (const ClArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(K));
+        if (K->zkeep & CL_ZCARRY) {
+            const int ns = K->nsteps, rm = K->P.RM;
+            int *img = cl_zimage(K->P, g, ns);
+            for (int x = tid; x < nbonds * 2 * rm; x += CB) img[x] = ZK[x];
+            for (int x = tid; x < 2 * nbonds; x += CB) img[(size_t)ns * 2 * rm + x] = ZN[x];
+        }
         if (tid == 0) {
             gs.amax = amax; gs.pivotmax = pivotmax; gs.pivotmin = pivotmin; gs.neval = neval; gs.rngpos = rngpos;
             gs.bytes_half = bytes_half; gs.n_resid = n_resid;
+            if (K->zkeep & CL_WORD) { gs.rngword = sA0; gs.rngword_pos = rngpos; }
+            if (K->zkeep & CL_ZCARRY) gs.zk_epoch = K->epoch;
             if (P.tail_side) gs.amax_bnd[epoch & 1] = 0.0;      // the slot this sweep's tail launch raises (ttx_dev.h)
         }
         __syncthreads();
         exch_pack_group(P, g);          // the group's outgoing boundary messages (saves the separate k_exch_pack launch)
+        CSE(3);
+        CSE_END();
     }
 }

@@ -65,3 +65,51 @@ TTX_HD void cl_ordered_sum(int n, LD ld, TM tm)
     if (rem & 2) { cl_sum_piece<2>(s, ld, tm); s += 2; }
     if (rem & 1) cl_sum_piece<1>(s, ld, tm);
 }
+
+// ---- what the kernel carries from launch to launch instead of recomputing it at its entry (tests/cluster_entry_main.cpp) ----
+// Powers of the lottery's generator, 48271^e mod (2^31 - 1): ttx_minstd_pow's rule (ttx_cdf.h) as a constant expression, and the
+// table of 48271^(2 t), t = 0 .. CL_POWTAB_N - 1, made from it by the compiler.  Thread t's first lottery candidate jumps by entry
+// t, lane l keeps entry l for the generator step of a bond step, and entry 64 is 48271^128, the factor of cl_stepmul.
+#define CL_POWTAB_N 256
+constexpr uint64_t cl_mulmod31_c(uint64_t a, uint64_t b)
+{
+    uint64_t x = a * b;
+    x = (x & 2147483647ULL) + (x >> 31);
+    x = (x & 2147483647ULL) + (x >> 31);
+    return (x >= 2147483647ULL) ? x - 2147483647ULL : x;
+}
+constexpr uint64_t cl_minstd_pow_c(uint64_t e)
+{
+    uint64_t base = 48271ULL, w = 1;
+    while (e) { if (e & 1) w = cl_mulmod31_c(w, base); base = cl_mulmod31_c(base, base); e >>= 1; }
+    return w;
+}
+struct ClPowTab { uint32_t v[CL_POWTAB_N]; };
+constexpr ClPowTab cl_make_powtab()
+{
+    ClPowTab t{};
+    for (int k = 0; k < CL_POWTAB_N; k++) t.v[k] = (uint32_t)cl_minstd_pow_c(2ULL * (uint64_t)k);
+    return t;
+}
+
+// The generator step of a bond step, 48271^(2 nlot): below 512 candidates from lane(b) = 48271^(2 b), b < 64, and
+// c64 = 48271^128 as 48271^(2 (64 a + b)) = 48271^(2 b) * (48271^128)^a -- one lookup and a <= 7 products (the same residue:
+// modular products are exact); the square-and-multiply loop from there on.
+template <class LANE>
+TTX_HD uint64_t cl_stepmul(int nlot, LANE lane, uint64_t c64)
+{
+    if (nlot >= 512) return ttx_minstd_pow(2ull * (uint64_t)nlot);
+    uint64_t s = lane(nlot & 63);
+    for (int a = 0; a < (nlot >> 6); a++) s = ttx_mulmod31(s, c64);
+    return s;
+}
+
+// The generator word 48271^(2 rngpos + 1) a launch leaves next to the position it belongs to (GroupState::rngword, rngword_pos):
+// the next launch takes it where the word is one (a power of 48271 is never 0 modulo a prime: a zeroed state and a reset hold
+// none) and its position is still the group's -- a kernel that advances rngpos without knowing of the word invalidates it.
+TTX_HD bool cl_word_valid(uint64_t word, uint64_t wpos, uint64_t rngpos) { return word != 0 && wpos == rngpos; }
+// The sorted pivot lists a launch leaves in global memory carry the number of the launch that wrote them (GroupState::zk_epoch;
+// 0 after a reset: launches count from 1).  Launch `epoch` of a run takes them only from launch epoch - 1 of the same run.
+TTX_HD bool cl_lists_valid(int tag, int epoch) { return tag != 0 && tag == epoch - 1; }
+// ints of one group's image: [nsteps][2][RM] keys and [nsteps][2] counts, as they lie in LDS, rounded up to 16 bytes
+TTX_HD size_t cl_zimage_ints(int nsteps, int RM) { return ((size_t)nsteps * 2 * (size_t)RM + 2 * (size_t)nsteps + 3) & ~(size_t)3; }

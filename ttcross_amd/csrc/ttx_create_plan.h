@@ -77,6 +77,9 @@ struct CreateEnv {
     bool fin_skip_exch_off = false; // TTX_FIN_SKIP_EXCH=0
     bool init_wide_off = false;     // TTX_INIT_WIDE=0
     bool quad_lds_off = false;      // TTX_QUAD_LDS=0
+    bool cl_powtab_off = false;     // TTX_CL_POWTAB=0
+    bool cl_word_off = false;       // TTX_CL_WORD=0
+    bool cl_lists_off = false;      // TTX_CL_LISTS=0
 };
 // the switches as `get` finds them (get(name): the value, or nullptr where unset): an integer as atoi reads it, "=0" as atoi(value) == 0
 template <class Get>
@@ -108,6 +111,7 @@ CreateEnv create_env_from(Get get)
     v.head_direct_off = off("TTX_HEAD_DIRECT"); v.init_wave_off = off("TTX_INIT_WAVE");
     v.fin_early_off = off("TTX_FIN_EARLY"); v.fin_skip_exch_off = off("TTX_FIN_SKIP_EXCH");
     v.init_wide_off = off("TTX_INIT_WIDE"); v.quad_lds_off = off("TTX_QUAD_LDS");
+    v.cl_powtab_off = off("TTX_CL_POWTAB"); v.cl_word_off = off("TTX_CL_WORD"); v.cl_lists_off = off("TTX_CL_LISTS");
     return v;
 }
 struct DevCaps { int ncu = 0; bool coop = false; };          // multiProcessorCount, hipDeviceAttributeCooperativeLaunch
@@ -165,6 +169,10 @@ struct CreatePlan {
     int cluster_cand = 0;                           // workgroups per bond group the cluster kernel would run with; 0: not eligible
     int cluster_var = 0;                            // its instantiation: 0 exact, remainders predicated; 1 exact, rows padded to whole chunks; 2 closed form
     int cluster_ldsinv = 0, cluster_zkeep = 0, cluster_coop = 0;
+    // the entry of a cluster launch (ttx_cluster.h): the generator's jump powers from a compile-time table (TTX_CL_POWTAB=0: three
+    // square-and-multiply loops per launch), the generator word carried from the launch before (TTX_CL_WORD=0: raised from rngpos),
+    // the sorted pivot lists carried through a global image (TTX_CL_LISTS=0, or no cluster_zkeep: rebuilt from vip per launch)
+    bool cl_powtab = true, cl_word = true, cl_lists = false;
     int cl_test_abort = 0; bool dbg_waves = false;
     bool sweep_tail = true;                         // the pipelined cluster loop ends a sweep with k_exch_tail (TTX_TAIL=0: max/apply and boundary launches)
     bool sweep_tail_side = true;                    // ... and its summary runs on the quadrature's stream (TTX_TAIL_SIDE=0: k_sweep_end on the main stream)
@@ -396,6 +404,7 @@ inline CreatePlan create_plan(const ttx_config &cfg, bool nofun, const CreateEnv
         if (p.lds_cluster + sizeof(double) * 2 * RM * RM <= TTX_LDS_WORK) { p.cluster_ldsinv = 1; p.lds_cluster += sizeof(double) * 2 * RM * RM; }
         const size_t zk = sizeof(int) * ((size_t)p.nbmax * 2 * RM + 2 * p.nbmax + 4);
         if (p.lds_cluster + zk <= TTX_LDS_WORK) { p.cluster_zkeep = 1; p.lds_cluster += zk; }
+        p.cl_powtab = !env.cl_powtab_off; p.cl_word = !env.cl_word_off; p.cl_lists = p.cluster_zkeep && !env.cl_lists_off;
         // instantiation of the cluster kernel: the closed form where fast arithmetic was asked for; else rows padded to whole chunks
         // (f_ising_c4w) where the pad is neutral -- every node in [0,1], so that no running product overflows (inf * 0.0 is NaN) --
         // unless TTX_CL_PAD=0 asks for the predicated remainders (f_ising_c4p), which hold for any node (ttx_cluster_eval tells)

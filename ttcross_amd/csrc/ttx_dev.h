@@ -73,6 +73,14 @@ struct GroupState {
     //    kernel it: that slot was last read at the entry of sweep kernel it-1, which is over, and by the summary of sweep it-2,
     //    which finished before the tail of sweep it-1 was launched (its wait for ev_val); its next writer is the tail of sweep it.
     double amax_bnd[2];
+    // What a launch of the cluster sweep kernel leaves for the entry of the next one (ttx_cluster.h; the rules are cl_word_valid and
+    // cl_lists_valid of ttx_cluster_rules.h).  rngword = 48271^(2 rngword_pos + 1), the generator word at position rngword_pos: taken
+    // where it is non-zero and rngword_pos == rngpos, so a kernel that advances rngpos alone (chain, fused) invalidates it.  zk_epoch:
+    // the launch number whose sorted pivot lists stand in the group's image behind cl_part (cl_zimage); 0: none.  k_reset clears
+    // word and tag; a launch that aborts or returns early writes neither.  n_zload, n_wload count the launches of a run that took
+    // the carried lists / the carried word (block 0 of the group; read by ttx_cluster_entry).
+    unsigned long long rngword, rngword_pos;
+    int zk_epoch, n_zload, n_wload, pad1;
 #ifdef TTX_STAMPS
     long long stamp[2][16]; long long nstamp[2];   // debug build: accumulated wall_clock64 deltas per phase
 #endif
@@ -199,7 +207,7 @@ struct DevProb {
     unsigned *cl_ctr;              // [G]
     int *cl_abort;                 // [1]
     int cl_test_abort;             // test hook: block (group 0, block 0) raises the abort flag in launch number cl_test_abort (0: never)
-    struct ClPart *cl_part;        // [2][G][TTX_CLREC]
+    struct ClPart *cl_part;        // [2][G][TTX_CLREC] records, then the groups' images of their sorted pivot lists (cl_zimage, ttx_cluster.h)
     long long *dbg;                // -DTTX_STAMPS builds: per-wave cycle stamps of one bond step of the cluster kernel (group 0)
 };
 

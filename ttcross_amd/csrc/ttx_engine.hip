@@ -581,7 +581,8 @@ static int create_cores(ttx_engine *h)
     if (s.cluster) {
         unsigned *ctr; ClPart *cp;
         A_(dev_alloc(h, &ctr, G));
-        A_(dev_alloc(h, &cp, 2 * G * TTX_CLREC));
+        // (behind the records: every group's image of its sorted pivot lists, cl_zimage of ttx_cluster.h)
+        A_(dev_alloc(h, &cp, 2 * G * TTX_CLREC + (s.cl_lists ? (G * cl_zimage_ints(s.nbmax, s.RM) * sizeof(int) + sizeof(ClPart) - 1) / sizeof(ClPart) : 0)));
         P.cl_ctr = ctr; P.cl_part = cp;
 #ifdef TTX_STAMPS
         if (s.dbg_waves) { long long *dbg; A_(dev_alloc(h, &dbg, (size_t)8 * 64 * 8)); P.dbg = dbg; }
@@ -1425,7 +1426,8 @@ struct SweepRun {
     int launch_sweep_kernel(int it_)
     {
         const CreatePlan &s = h->sel;
-        int dir = 2 - it_ % 2, epoch = it_, nsteps = h->nbmax, NB = s.cluster, ldsinv = s.cluster_ldsinv, zkeep = s.cluster_zkeep;
+        int dir = 2 - it_ % 2, epoch = it_, nsteps = h->nbmax, NB = s.cluster, ldsinv = s.cluster_ldsinv;
+        int zkeep = (s.cluster_zkeep ? CL_ZKEEP : 0) | (s.cl_lists ? CL_ZCARRY : 0) | (s.cl_word ? CL_WORD : 0) | (s.cl_powtab ? CL_POWTAB : 0);     // the forms of the entry
         const dim3 grid(8 * NB * ((G + 7) / 8)), block(CB);
         KScope ks(h, TTX_K_HALFSTEP, 1);
         if (!cluster) hipLaunchKernelGGL(k_sweep_fused, dim3(G), dim3(FB), s.lds_fused, st, P, dir, nsteps);
@@ -3000,6 +3002,20 @@ extern "C" int ttx_sweep_path(const ttx_engine *h) { return !h ? -1 : h->cluster
 extern "C" int64_t ttx_resid_halfsteps(const ttx_engine *h) { return h ? h->n_resid : 0; }
 extern "C" int ttx_cluster_eval(const ttx_engine *h) { return !h ? -1 : h->cluster_nb() ? 1 + h->sel.cluster_var : 0; }
 extern "C" int ttx_cluster_fallbacks(const ttx_engine *h) { return h ? h->cluster_fallbacks : 0; }
+extern "C" int ttx_cluster_entry(const ttx_engine *h, int64_t out[3])
+{
+    if (!h || !out) return fail(TTX_EINVAL, "ttx_cluster_entry: null argument");
+    out[0] = out[1] = out[2] = 0;
+    if (!h->cluster_nb()) return TTX_OK;
+    const CreatePlan &s = h->sel;
+    out[0] = (s.cl_powtab ? 1 : 0) | (s.cl_word ? 2 : 0) | (s.cl_lists ? 4 : 0);
+    GroupState g0s;
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipMemcpy(&g0s, h->P.gs, offsetof(GroupState, S), hipMemcpyDeviceToHost));
+    out[1] = g0s.n_zload; out[2] = g0s.n_wload;
+    return TTX_OK;
+}
 extern "C" int ttx_det_fallbacks(const ttx_engine *h) { return h ? h->det_fallbacks + h->de5_fallbacks : 0; }
 extern "C" int ttx_fun_id(const ttx_engine *h) { return h ? h->cfg.fun_id : -1; }
 extern "C" int ttx_set_profile(ttx_engine *h, int on) { if (!h) return fail(TTX_EINVAL, "null"); h->profile = on != 0; return TTX_OK; }

@@ -276,6 +276,7 @@ __global__ __launch_bounds__(256) void k_reset(DevProb P, size_t SB, size_t QB)
         gs.amax = 0.0; gs.pivotmax = -1.0; gs.pivotmin = -1.0; gs.pivotmax_prev = 0.0;
         gs.neval = 0; gs.rngpos = 0; gs.val = 0.0; gs.initval = 0.0; gs.bytes_half = 0.0; gs.n_resid = 0;
         gs.amax_bnd[0] = 0.0; gs.amax_bnd[1] = 0.0;
+        gs.rngword = 0; gs.rngword_pos = 0; gs.zk_epoch = 0; gs.n_zload = 0; gs.n_wload = 0;     // nothing carried into a run (ttx_dev.h)
 #ifdef TTX_STAMPS
         for (int a = 0; a < 2; a++) { gs.nstamp[a] = 0; for (int b = 0; b < 16; b++) gs.stamp[a][b] = 0; }
 #endif

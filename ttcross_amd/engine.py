@@ -676,6 +676,15 @@ class TTCross:
         L.ttx_cluster_fallbacks.argtypes = [c_void_p]
         return int(L.ttx_cluster_fallbacks(self._h))
 
+    def cluster_entry(self):
+        """The entry of a cluster launch (include/ttx.h: ttx_cluster_entry): the forms in force ('powtab', 'word', 'lists') and how
+        many launches of the last run took the carried pivot lists and the carried generator word (local group 0)."""
+        L = load_library()
+        L.ttx_cluster_entry.argtypes = [c_void_p, ctypes.POINTER(c_int64)]
+        out = (c_int64 * 3)()
+        _check(L.ttx_cluster_entry(self._h, out))
+        return {"powtab": bool(out[0] & 1), "word": bool(out[0] & 2), "lists": bool(out[0] & 4), "lists_taken": int(out[1]), "word_taken": int(out[2])}
+
     @property
     def det_fallbacks(self):
         """Runs repeated without the wave teams / relay of the Ising D/E half-step after a reported fault (include/ttx.h)."""
