@@ -39,6 +39,7 @@ extern "C" {
 #define TTX_FUN_COSCOEFF 5
 #define TTX_FUN_DEVICE 6   /* any user `fun`, evaluated on the DEVICE by a code object the caller supplies: ttx_set_integrand_device */
 #define TTX_FUN_TRAINS 7   /* fun(i) = g(x_1(i), ..., x_m(i)), x_t resident trains on the engine's device: ttx_set_integrand_trains */
+#define TTX_FUN_PULLBACK 8 /* fun(i) = h(x, logq, val), the grid point of i pulled back through resident squared-train transports: ttx_set_integrand_pullback */
 
 #define TTX_ARITH_EXACT 0
 #define TTX_ARITH_FAST 1
@@ -186,6 +187,54 @@ int ttx_set_integrand_trains_device(ttx_engine *h, int32_t m, ttx_engine *const 
 int ttx_set_integrand_trains_device_file(ttx_engine *h, int32_t m, ttx_engine *const *x, const char *path,
                                          const char *name, const double *par, int32_t npar);
 int ttx_trainfun_last(const ttx_engine *h, double *ms, int64_t *launches, int64_t *elements);
+
+/* Cross approximation of a device function PULLED BACK THROUGH RESIDENT SQUARED-TRAIN TRANSPORTS, for an engine created with fun_id =
+ * TTX_FUN_PULLBACK (ttx_config.par / npar are not used; d <= 2048; one process, any number of bond groups): the next layer of a
+ * layered (deep inverse Rosenblatt) transport, built without a point leaving the device.  The engine's grid is a reference grid in
+ * [0,1]^d: for a multi-index i, u^(m)_k = ref_k[i_k - 1].  Then, for t = m, m-1, .., 1, as a sequence of operations,
+ *     (x^(t), lq_t, val_t) = ttx_sample_sq_real(layer[t-1].x, u = u^(t), layer[t-1].nodes, cond = NULL, layer[t-1].gamma, TTX_EVAL_EXACT)
+ *     u^(t-1) = x^(t)
+ * and the results are x = x^(1); logq = lq_m, then logq = logq + lq_t for t = m-1 .. 1; val = val_1.  Layer 1 is the outermost layer,
+ * the one built first: its nodes span the physical box.  A sample that fails at any layer gives the sampler's failed row -- x NaN,
+ * logq NaN, val 0.0 -- and is counted in nfailed.  x, logq and val are, bit for bit, what that chain of public calls returns.
+ * The integrand's value is what the loaded function returns: a TTX_DEVICE_COMBINER(name) of include/ttx_device_fun.h, called with
+ * m = d + 2 and v = [x_1 .. x_d, logq, val].  The sweep is the one of TTX_FUN_TRAINS: between the two passes of every evaluating
+ * kernel one kernel (k_pb_slots, ttcross_amd/csrc/ttx_pullback.h) transports the requested points, one wave per element, and the
+ * combiner's slot kernel runs behind it; ttx_host_calls stays 0, nothing is synchronised.
+ *   m, layer : 1 <= m <= TTX_PULLBACK_MAX layers.  layer[t].x holds a train on the engine's device with d modes of at least two
+ *           indices each (all modes are drawn) and ranks up to 128; layer[t].nodes[k] are the n_k(x) finite, strictly ascending nodes
+ *           of its mode k, for t >= 1 (layers 2 and up) from exactly 0.0 to exactly 1.0, because the layer's output is the next
+ *           layer's uniforms; layer[t].gamma >= 0 is its defensive term.  The same engine may appear as several layers, with the same
+ *           nodes and gamma (both layers read one head; other nodes or gamma for one engine are refused).  The node rows are COPIED,
+ *           the engine HANDLES are recorded: at the start of every ttx_run, ttx_accchk, ttx_eval_device and ttx_pullback_points the
+ *           engine looks at the layers again (a layer that was ttx_ort-ed or ttx_svd-ed in between is seen with its new ranks), runs
+ *           the sampler's head pass on each distinct layer engine and waits for it once.
+ *           LIFETIME: as for ttx_set_integrand_trains; in addition the caller makes no call on a layer's engine while a run of this
+ *           engine is in flight: the layer's head tables live in the layer's own work space.
+ *   ref   : ref[k] are the n_k(h) entries of the reference grid of mode k, each in [0, 1] (COPIED)
+ *   image, nbytes / path, name, par, npar : the combiner, with the conventions and refusals of ttx_set_integrand_trains_device.
+ *           image == NULL (path == NULL) records the layers only: ttx_pullback_points works, ttx_run, ttx_accchk and ttx_eval_device
+ *           answer TTX_ESTATE.
+ * ttx_pullback_points: x, logq, val at npts multi-indices (ind row-major, 1-based; out of range: TTX_EINVAL); logq, val may be NULL.
+ * ttx_eval_device on such an engine: the combiner's value at the listed indices.
+ * TTX_ESTATE: engine not created with TTX_FUN_PULLBACK.  TTX_EINVAL, each before any launch and with the engine as before: m outside
+ * 1..TTX_PULLBACK_MAX; a null layer or the engine itself; a layer without a train, spread over processes or on another device; with
+ * another d; with a rank above 128; with a mode of one index; a node row that is missing, not finite or not strictly ascending, or
+ * for t >= 2 does not run from 0.0 to 1.0; a ref row that is missing or has an entry outside [0, 1]; gamma negative or not finite;
+ * the combiner's refusals; more LDS per wave (two states, two sheets of the largest layer mode, the point, the index row) than a
+ * workgroup can have.  Every message names the layer and the mode.  Creation, ttx_comm_init*, ttx_set_transport, replicas: as for
+ * TTX_FUN_TRAINS.  TTX_PB_GRID (environment) caps the grid of the transport kernels.
+ * ttx_pullback_last: of the last ttx_run, ttx_eval_device or ttx_pullback_points, the launches of the transport kernel, the elements it
+ * evaluated, the failed samples among them and, with ttx_set_profile on, its milliseconds with the combiner's (HIP events; 0
+ * otherwise).  Any pointer may be NULL.  Added without a new ttx_version: look the symbols up. */
+#define TTX_PULLBACK_MAX 8
+typedef struct { ttx_engine *x; const double *const *nodes; double gamma; } ttx_layer;   /* nodes: [d] host rows of n_k(x) */
+int ttx_set_integrand_pullback     (ttx_engine *h, int32_t m, const ttx_layer *layer, const double *const *ref /* [d] host rows of n_k(h) */,
+                                    const void *image, int64_t nbytes, const char *name, const double *par, int32_t npar);
+int ttx_set_integrand_pullback_file(ttx_engine *h, int32_t m, const ttx_layer *layer, const double *const *ref,
+                                    const char *path, const char *name, const double *par, int32_t npar);
+int ttx_pullback_points(ttx_engine *h, int64_t npts, const int32_t *ind /* [npts][d], 1-based */, double *x /* [npts][d] */, double *logq, double *val);
+int ttx_pullback_last(const ttx_engine *h, double *ms, int64_t *launches, int64_t *elements, int64_t *nfailed);
 
 /* dtt_dmrgg itself: initial cross, sweeps until maxrank / 3 strikes, finalisation dtt_lua (lib/dmrgg.f90:151-1049) */
 int ttx_run(ttx_engine *h);

@@ -211,8 +211,15 @@ __device__ __forceinline__ unsigned ttx_devfun_flags16(const unsigned char *hreq
  *   ttx_devcomb_list_NAME   (int m, int d, const int *n, const double *par, long long npts, const int *ind, const double *tval,
  *                            double *out): the 32-bit list twin, tval[npts][m]
  * and the file is handed to ttx_set_integrand_trains_device[_file] (include/ttx.h).  For a pivot sequence equal to a host run keep
- * to + - * / and sqrt, in the host code's order (BIT REPRODUCIBILITY above). */
-#define TTX_DEVICE_COMBINER(NAME)                                                                                                 \
+ * to + - * / and sqrt, in the host code's order (BIT REPRODUCIBILITY above).
+ *
+ * The same macro serves a pulled-back integrand (TTX_FUN_PULLBACK, ttx_set_integrand_pullback[_file] of include/ttx.h): there the
+ * engine calls the function with m = d + 2 and v = [x_1 .. x_d, logq, val] -- the point of the multi-index ind pulled back through the
+ * layers, the log density of the transport's push-forward of the uniform at x, and the value of the outermost layer's train at x.  A
+ * sample that failed arrives as x = NaN, logq = NaN, val = 0.0; what the function returns for it is the integrand's value.  A target
+ * density enters as h = sqrt(exp(logpi(x) - logq)) (examples/devfun/pullback_tempered.hip); exp and log are not IEEE operations, so
+ * such a combiner agrees with a host evaluation to a few units in the last place, not bit for bit. */
+#define TTX_DEVICE_COMBINER(NAME)                                                                                                \
     extern "C" __device__ __attribute__((used, visibility("default"))) const ttx_devfun_info ttx_devcomb_info_##NAME =             \
         {TTX_DEVFUN_ABI, TTX_DEVFUN_KIND_LANE, TTX_DEVFUN_BLOCK, 0};                                                              \
     extern "C" __global__ __launch_bounds__(TTX_DEVFUN_BLOCK) void ttx_devcomb_slots_##NAME(                                      \

@@ -453,7 +453,7 @@ inline CreatePlan create_plan(const ttx_config &cfg, bool nofun, const CreateEnv
             p.lot_rows = p.lot_wave ? (env.lottery_rows2 ? 2 : 1) : 0;
         }
     }
-    if (fun == TTX_FUN_HOST || fun == TTX_FUN_COSCOEFF || fun == TTX_FUN_DEVICE || fun == TTX_FUN_TRAINS) {
+    if (fun == TTX_FUN_HOST || fun == TTX_FUN_COSCOEFF || fun == TTX_FUN_DEVICE || fun == TTX_FUN_TRAINS || fun == TTX_FUN_PULLBACK) {
         // slots of one group: the largest point set any evaluating kernel asks for in one launch.  The host's `fun` reads pinned
         // slots; the others are evaluated on the stream between the two passes, from device slots
         p.HS = std::max<size_t>({RM * NM, (size_t)p.nn * p.snum, (size_t)p.NC * NM, (size_t)nlotmax, (size_t)2 * NM, (size_t)256});

@@ -59,6 +59,7 @@
 #include "ttx_sample_sq.h"
 #include "ttx_sample_sq_real.h"
 #include "ttx_trainfun.h"
+#include "ttx_pullback.h"
 
 // the instantiation of the cluster kernel an engine runs (ttx_engine::cluster_var)
 typedef void (*cluster_kernel_t)(DevProb, int, int, int, int, int, int);
@@ -132,6 +133,7 @@ enum {
     SC_H, SC_ROW, SC_CNT,               // sampling: head tables, global rows of long modes, the failure counter
     SC_SRX,                             // ttx_sample_real: staging of the drawn coordinates (its uniforms go to SC_X, cell rows to SC_IND, nodes to SC_META)
     SC_TFUN, SC_TVAL,                   // TTX_FUN_TRAINS: the operands' blocks (core pointers, ranks) of a run, the values for a loaded combiner
+    SC_PB, SC_PBREF, SC_PBVAL,          // TTX_FUN_PULLBACK: the layers' blocks of a call (plan rows, offsets, core pointers, ranks), the reference rows of the set, the rows x, logq, val for the combiner
     SC_MAT,                             // ttx_mode_apply: the matrices of the applied modes (its tables go to SC_META)
     SC_KP, SC_KW, SC_KS, SC_KX,         // ttx_topk: the Gram matrices P_0 .. P_(d-1), the W of a Gram step, a mode's score sheet (keys), the two state buffers
     SC_KREC, SC_KSEL, SC_KOUT,          // ttx_topk: the kept positions of every mode, the selection's state (words, chunk counts, histogram), the rows before and after the ordering
@@ -199,6 +201,7 @@ struct BgLast { double ms[3] = {0.0, 0.0, 0.0}, flops = 0.0; int mode = -1; int6
 
 struct DevFun;                          // a loaded device integrand (TTX_FUN_DEVICE), defined with slot_eval
 struct TrainFun;                        // the operands and the combiner of TTX_FUN_TRAINS, defined with slot_eval
+struct PullFun;                         // the layers, the reference grid and the combiner of TTX_FUN_PULLBACK, defined with slot_eval
 struct ttx_engine {
     ttx_config cfg;
     std::vector<int32_t> n1;            // 1-based n, size d+2
@@ -282,6 +285,15 @@ struct ttx_engine {
     bool tf_figures = false;            // the call in flight records the figures of ttx_trainfun_last (ttx_run, ttx_eval_device; not ttx_accchk)
     int64_t tf_launches = 0, tf_elements = 0;
     double tf_ms = 0.0;
+    // integrand of a point pulled back through resident transports (TTX_FUN_PULLBACK): layer handles, node rows, reference grid and
+    // combiner, shared with replicas; the layers' device blocks and the launch shape as this engine's call sees them (pb_prepare).  The
+    // figures of ttx_pullback_last are TTX_FUN_TRAINS's (tf_*; an engine is one or the other) and the failed count
+    std::shared_ptr<PullFun> pfun;
+    const PullFun *pb_ref_of = nullptr; // whose reference rows SC_PBREF holds
+    PbOps pb_ops{};
+    PbPlan pb_pl;
+    std::vector<char> pb_host;
+    int64_t pb_failed = 0;
     int64_t host_calls = 0;
     int64_t n_resid = 0;                // rook half-steps of the last run that took a residual (all groups)
     // operations on the resident train: work space (SC_*), the host images behind SC_TRAIN and SC_META, timers (TM_*), last figures
@@ -379,6 +391,20 @@ static int tf_grid(ttx_engine *h, long long items);
 static int tf_prepare(ttx_engine *h, const char *who, bool figures);
 static int tf_finish(ttx_engine *h);
 static int tf_eval_list(ttx_engine *h, int64_t npts, const int32_t *ind, double *out);
+// ---- TTX_FUN_PULLBACK: fun(i) = h(x, logq, val) at the grid point of i pulled back through resident transports (ttx_pullback.h) -----
+// Layers are recorded as handles with copies of their node rows; their heads and device blocks are rebuilt by pb_prepare at the start
+// of every call that evaluates.
+struct PullFun {
+    struct Layer { ttx_engine *x; std::vector<std::vector<double>> nodes; double gamma; };
+    std::vector<Layer> layer;
+    std::vector<double> ref;                // the reference rows, mode k at roff[k]
+    std::vector<size_t> roff;
+    std::shared_ptr<DevFun> comb;           // null: the layers only (ttx_pullback_points)
+};
+static int pb_prepare(ttx_engine *h, const char *who, bool figures, bool need_comb);
+static int pb_slots(ttx_engine *h);
+static int pb_finish(ttx_engine *h);
+static int pb_eval_list(ttx_engine *h, int64_t npts, const int32_t *ind, double *out);
 // with ttx_set_profile on, an event pair around the launches of one slot evaluation (collected by tf_finish)
 struct TfScope {
     ttx_engine *h; hipEvent_t a = nullptr, b = nullptr;
@@ -426,6 +452,7 @@ static int slot_eval(ttx_engine *h)
     if (!P.slot_dev) return host_eval(h);
     if (h->cfg.fun_id == TTX_FUN_DEVICE) return devfun_slots(h);
     if (h->cfg.fun_id == TTX_FUN_TRAINS) return tf_slots(h);
+    if (h->cfg.fun_id == TTX_FUN_PULLBACK) return pb_slots(h);
     const long long nslot = (long long)h->G * h->sel.HS;
     const unsigned grid = (unsigned)std::min<long long>((nslot + TTX_CC_WAVES - 1) / TTX_CC_WAVES, 1024);
     hipLaunchKernelGGL(k_coscoeff_slots, dim3(grid), dim3(64 * TTX_CC_WAVES), sizeof(double) * TTX_CC_WAVES * TTX_CC_LDS(P.d), h->stream,
@@ -678,22 +705,24 @@ static int create_impl(ttx_engine **out, const ttx_config *cfg, bool nofun)
     if (cfg->maxrank < 1 || cfg->maxrank > 128) return fail(TTX_EINVAL, "ttx_create: maxrank must be in 1..128 (got %d)", cfg->maxrank);
     if (cfg->pivoting < -1) return fail(TTX_EINVAL, "dtt_dmrgg: unknown pivoting: %d", cfg->pivoting);   // lib/dmrgg.f90:590-592
     if (2 * cfg->pivoting + 2 > TTX_MAXH) return fail(TTX_EINVAL, "dtt_dmrgg: pivoting %d too large", cfg->pivoting);
-    if (!(nofun && cfg->fun_id == 0) && (cfg->fun_id < 1 || cfg->fun_id > TTX_FUN_TRAINS)) return fail(TTX_EINVAL, "ttx_create: unknown fun_id %d", cfg->fun_id);
+    if (!(nofun && cfg->fun_id == 0) && (cfg->fun_id < 1 || cfg->fun_id > TTX_FUN_PULLBACK)) return fail(TTX_EINVAL, "ttx_create: unknown fun_id %d", cfg->fun_id);
     if (cfg->npar < 0 || (cfg->npar > 0 && !cfg->par)) return fail(TTX_EINVAL, "ttx_create: par missing");
     if (cfg->fun_id == TTX_FUN_ISING && (cfg->npar < 2 * cfg->n[0] + 1)) return fail(TTX_EINVAL, "ttx_create: the Ising integrand needs par(1:2n+1) (nodes, weights, id)");
     if ((cfg->fun_id == TTX_FUN_STDNORM || cfg->fun_id == TTX_FUN_MVN) && cfg->npar < cfg->n[0]) return fail(TTX_EINVAL, "ttx_create: the integrand needs the nodes par(1:n)");
     // the built-in integrands address par(ind) (and the Ising weights par(n(1) + ind)): no mode may be larger than the first
     // (test_crs_ising.f90:181-183); with the reference this is the caller's business, here it would be a read outside the parameter vector
     // (the COS coefficients do not index par)
-    if (cfg->fun_id != TTX_FUN_HOST && cfg->fun_id != TTX_FUN_COSCOEFF && cfg->fun_id != TTX_FUN_DEVICE && cfg->fun_id != TTX_FUN_TRAINS && cfg->fun_id != 0)
+    if (cfg->fun_id != TTX_FUN_HOST && cfg->fun_id != TTX_FUN_COSCOEFF && cfg->fun_id != TTX_FUN_DEVICE && cfg->fun_id != TTX_FUN_TRAINS && cfg->fun_id != TTX_FUN_PULLBACK && cfg->fun_id != 0)
         for (int k = 1; k < cfg->d; k++)
             if (cfg->n[k] > cfg->n[0]) return fail(TTX_EINVAL, "ttx_create: mode %d has %d points, more than the first mode (%d): the built-in integrands index par by n(1)", k + 1, cfg->n[k], cfg->n[0]);
     if (cfg->fun_id == TTX_FUN_HOST && cfg->d > 2048) return fail(TTX_EINVAL, "ttx_create: host integrand: at most 2048 dimensions (tt_size)");
     if (cfg->fun_id == TTX_FUN_DEVICE && cfg->d > 2048) return fail(TTX_EINVAL, "ttx_create: device integrand: at most 2048 dimensions (tt_size)");
     if (cfg->fun_id == TTX_FUN_TRAINS && cfg->d > 2048) return fail(TTX_EINVAL, "ttx_create: integrand of trains: at most 2048 dimensions (tt_size)");
+    if (cfg->fun_id == TTX_FUN_PULLBACK && cfg->d > 2048) return fail(TTX_EINVAL, "ttx_create: pulled-back integrand: at most 2048 dimensions (tt_size)");
     if (cfg->fun_id == TTX_FUN_COSCOEFF) { if (int rc0 = coscoeff_check("ttx_create", cfg->d, cfg->n, cfg->aux, cfg->naux)) return rc0; }
     const int W = cfg->world_size < 1 ? 1 : cfg->world_size;
     if (cfg->fun_id == TTX_FUN_TRAINS && W > 1) return fail(TTX_EINVAL, "ttx_create: an integrand of trains (TTX_FUN_TRAINS) runs in one process: bond groups (nproc) work, world_size %d does not", W);
+    if (cfg->fun_id == TTX_FUN_PULLBACK && W > 1) return fail(TTX_EINVAL, "ttx_create: a pulled-back integrand (TTX_FUN_PULLBACK) runs in one process: bond groups (nproc) work, world_size %d does not", W);
     const int nproc = std::max(cfg->nproc < 1 ? 1 : cfg->nproc, 1);
     if (nproc >= cfg->d) return fail(TTX_EINVAL, "nproc exceeds or equal dimension, cannot proceed");   // lib/dmrgg.f90:114-117
     if (nproc < W) return fail(TTX_EINVAL, "ttx_create: %d bond groups cannot be spread over %d GPUs", nproc, W);
@@ -750,6 +779,7 @@ extern "C" void ttx_destroy(ttx_engine *h)
     if (!h) return;
     if (h->dfun) { (void)hipSetDevice(h->cfg.device); if (h->stream) (void)hipStreamSynchronize(h->stream); h->dfun.reset(); }   // the last owner unloads the module
     if (h->tfun) { (void)hipSetDevice(h->cfg.device); if (h->stream) (void)hipStreamSynchronize(h->stream); h->tfun.reset(); }   // ... and a loaded combiner's
+    if (h->pfun) { (void)hipSetDevice(h->cfg.device); if (h->stream) (void)hipStreamSynchronize(h->stream); h->pfun.reset(); }
     if (h->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(h->comm);
     for (void *p : h->allocs) (void)hipFree(p);
     for (auto &b : h->scratch) if (b.p) (void)hipFree(b.p);
@@ -790,6 +820,7 @@ extern "C" int ttx_comm_init(ttx_engine *h, const uint8_t id[128])
 {
     if (!h) return fail(TTX_EINVAL, "ttx_comm_init: null handle");
     if (h->cfg.fun_id == TTX_FUN_TRAINS) return fail(TTX_ESTATE, "ttx_comm_init: an engine with an integrand of trains (TTX_FUN_TRAINS) runs in one process");
+    if (h->cfg.fun_id == TTX_FUN_PULLBACK) return fail(TTX_ESTATE, "ttx_comm_init: an engine with a pulled-back integrand (TTX_FUN_PULLBACK) runs in one process");
     if (h->W == 1) return TTX_OK;
     int rc = rccl_load();
     if (rc) return rc;
@@ -858,6 +889,7 @@ extern "C" int ttx_comm_init_shm(ttx_engine *h, const char *name)
 {
     if (!h || !name || !*name) return fail(TTX_EINVAL, "ttx_comm_init_shm: null argument");
     if (h->cfg.fun_id == TTX_FUN_TRAINS) return fail(TTX_ESTATE, "ttx_comm_init_shm: an engine with an integrand of trains (TTX_FUN_TRAINS) runs in one process");
+    if (h->cfg.fun_id == TTX_FUN_PULLBACK) return fail(TTX_ESTATE, "ttx_comm_init_shm: an engine with a pulled-back integrand (TTX_FUN_PULLBACK) runs in one process");
     if (h->W == 1) return TTX_OK;
     if (h->shm) return fail(TTX_ESTATE, "ttx_comm_init_shm: already initialised");
     ShmTransport *T = new ShmTransport();
@@ -877,6 +909,7 @@ extern "C" int ttx_set_transport(ttx_engine *h, const ttx_transport *t)
 {
     if (!h || !t || !t->sendrecv || !t->allreduce) return fail(TTX_EINVAL, "ttx_set_transport: null argument");
     if (h->cfg.fun_id == TTX_FUN_TRAINS) return fail(TTX_ESTATE, "ttx_set_transport: an engine with an integrand of trains (TTX_FUN_TRAINS) runs in one process");
+    if (h->cfg.fun_id == TTX_FUN_PULLBACK) return fail(TTX_ESTATE, "ttx_set_transport: an engine with a pulled-back integrand (TTX_FUN_PULLBACK) runs in one process");
     h->cb = *t; h->have_cb = true;
     return TTX_OK;
 }
@@ -958,6 +991,7 @@ extern "C" int ttx_eval_device(ttx_engine *h, int64_t npts, const int32_t *ind, 
 {
     if (!h) return fail(TTX_EINVAL, "ttx_eval_device: null handle");
     if (h->cfg.fun_id == TTX_FUN_TRAINS) return tf_eval_list(h, npts, ind, out);
+    if (h->cfg.fun_id == TTX_FUN_PULLBACK) return pb_eval_list(h, npts, ind, out);
     if (h->cfg.fun_id != TTX_FUN_DEVICE) return fail(TTX_ESTATE, "ttx_eval_device: the engine was not created with fun_id = TTX_FUN_DEVICE");
     if (!h->dfun) return fail(TTX_ESTATE, "ttx_eval_device: call ttx_set_integrand_device first");
     if (npts < 0 || (npts > 0 && (!ind || !out))) return fail(TTX_EINVAL, "ttx_eval_device: null argument");
@@ -1704,6 +1738,9 @@ static int with_fun(const ttx_engine *h, const char *who, F f)
         case TTX_FUN_TRAINS:
             if (who && !h->tfun) return fail(TTX_ESTATE, "%s: call ttx_set_integrand_trains first", who);
             return f(std::integral_constant<int, FUN_HOST>());
+        case TTX_FUN_PULLBACK:
+            if (who && !(h->pfun && h->pfun->comb)) return fail(TTX_ESTATE, "%s: call ttx_set_integrand_pullback with a combiner first", who);
+            return f(std::integral_constant<int, FUN_HOST>());
         default: return f(std::integral_constant<int, FUN_MVN>());
     }
 }
@@ -1744,6 +1781,12 @@ extern "C" int ttx_run(ttx_engine *h)
         if (int rc = tf_prepare(h, "ttx_run", true)) return rc;
         if (int rc = run_impl<FUN_HOST>(h)) return rc;
         return tf_finish(h);
+    }
+    if (h->cfg.fun_id == TTX_FUN_PULLBACK) {
+        // the layers' heads and blocks as they stand now, then the sweep of a device integrand; the figures of ttx_pullback_last at the end
+        if (int rc = pb_prepare(h, "ttx_run", true, true)) return rc;
+        if (int rc = run_impl<FUN_HOST>(h)) return rc;
+        return pb_finish(h);
     }
     if (h->cfg.fun_id != TTX_FUN_ISING)
         return with_fun(h, "ttx_run", [&](auto fun) { h->host_calls = 0; return run_impl<decltype(fun)::value>(h); });
@@ -1877,6 +1920,7 @@ extern "C" int ttx_replicate(ttx_engine *h, ttx_engine **out)
     e->hfun = h->hfun; e->hfun_par = h->hfun_par;
     e->dfun = h->dfun;                              // same process, same device: the replica shares the module and the par copy
     e->tfun = h->tfun;                              // ... and the operand list of TTX_FUN_TRAINS
+    e->pfun = h->pfun;                              // ... and the layers, reference grid and combiner of TTX_FUN_PULLBACK
     if (e->RM != h->RM || e->NM != h->NM) { ttx_destroy(e); return fail(TTX_EHIP, "ttx_replicate: layout mismatch"); }
     const size_t CS = h->P.CS;
     // slots of the other processes' cores hold -0.0: x + (-0.0) = x for EVERY x, also for x = -0.0 (x + (+0.0) would turn it into +0.0)
@@ -2148,6 +2192,7 @@ static int accchk_impl(ttx_engine *h, int nlot, double *einf, double *efro, doub
 extern "C" int ttx_accchk(ttx_engine *h, int32_t nlot, double *einf, double *efro, double *ainf, double *afro, int32_t *pivot)
 {
     if (h && h->cfg.fun_id == TTX_FUN_TRAINS && !h->tfun) return fail(TTX_ESTATE, "ttx_accchk: call ttx_set_integrand_trains first");
+    if (h && h->cfg.fun_id == TTX_FUN_PULLBACK && !(h->pfun && h->pfun->comb)) return fail(TTX_ESTATE, "ttx_accchk: call ttx_set_integrand_pullback with a combiner first");
     if (!h || !einf || !efro || !ainf || !afro || !h->ran) return fail(TTX_ESTATE, "ttx_accchk: run first");
     if (h->W > 1)       // every rank needs all cores: the check runs on a replica of the job's train (identical result on every process)
         return with_replica(h, [&](ttx_engine *e) { return ttx_accchk(e, nlot, einf, efro, ainf, afro, pivot); });
@@ -2155,6 +2200,7 @@ extern "C" int ttx_accchk(ttx_engine *h, int32_t nlot, double *einf, double *efr
     if (h->cfg.fun_id == 0) return fail(TTX_ESTATE, "dtt_accchk: this engine holds a loaded tensor train and has no integrand");
     HIPCHECK(hipSetDevice(h->cfg.device));
     if (h->cfg.fun_id == TTX_FUN_TRAINS) if (int rc = tf_prepare(h, "dtt_accchk", false)) return rc;
+    if (h->cfg.fun_id == TTX_FUN_PULLBACK) if (int rc = pb_prepare(h, "dtt_accchk", false, true)) return rc;
     return with_fun(h, "dtt_accchk", [&](auto fun) { return accchk_impl<decltype(fun)::value>(h, nlot, einf, efro, ainf, afro, pivot); });
 }
 
@@ -4425,6 +4471,28 @@ extern "C" int ttx_sample_sq_last(const ttx_engine *h, double *ms_head, double *
 // pick(a, M, st, out): the caller's launch between the rows and the step of a mode (k_sqr_pick, k_sqr_cdf), out[0 .. 2] = rows, cell, logq.
 // Two sheets (squares and neighbour products), index tiles that advance by 15, per sample logq, the two hat values, the failure flag and
 // the hat cell (SqrState)
+// The head of ttx_sample_sq_real, of its way back and of a layer of TTX_FUN_PULLBACK (pb_prepare): the bidiagonal factors -- the mass
+// matrix's Cholesky factor of a drawn mode, the hat row of a held one (a mode of one node is held at its node) --, the modes' records
+// and sq_head with them
+static int sqr_head(ttx_engine *h, const SqPlan &pl, const std::vector<int> &fx, const double *const *nodes, const double *cond, double gamma, std::vector<SrMode> &modes,
+                    SqHead &Qh)
+{
+    const int d = h->d;
+    std::vector<double> dg(pl.woff[d], 0.0), sp(pl.woff[d], 0.0), tnodes, gw(d + 1, gamma);
+    for (int k = 0; k < d; k++) {
+        const int n = h->n1[k + 1];
+        const double *t = nodes[k];
+        SrMode &M = modes[k];
+        M = SrMode{0, 0, 1.0, 0.0, 0.0, tnodes.size()};
+        tnodes.insert(tnodes.end(), t, t + n);
+        double *dk = dg.data() + pl.woff[k], *sk = sp.data() + pl.woff[k];
+        if (!fx[k]) { sqr_mass_cholesky(t, n, dk, sk); gw[k + 1] = gw[k] * (t[n - 1] - t[0]); continue; }
+        M = sr_held_mode(t, n, cond && cond[k] == cond[k] ? cond[k] : t[0], M.noff);
+        dk[M.cell] = M.phi0; sk[M.cell] = M.phi1;
+        gw[k + 1] = gw[k];
+    }
+    return sq_head(h, pl, dg, fx, gw, Qh, &sp, &tnodes);
+}
 template <class Pick>
 static int sqr_frame(ttx_engine *h, const char *who, int which, int64_t npts, const double *in, const double *const *nodes, const double *cond, double gamma, int32_t mode,
                      double *rows, int32_t *cell, double *logq, double *val, bool dev, Pick pick)
@@ -4446,23 +4514,7 @@ static int sqr_frame(ttx_engine *h, const char *who, int which, int64_t npts, co
     };
     return sq_frame(h, who, SqKind{which, 2, 15, 3 * sizeof(double) + 2 * sizeof(int)}, npts, in, mode, dev, fx, out, 4,
         [](const SqPlan &) { return (int)TTX_OK; },
-        [&](const SqPlan &pl, SqHead &Qh) {
-            // the bidiagonal factors: the mass matrix's Cholesky factor of a drawn mode, the hat row of a held one (a mode of one node is held at its node)
-            std::vector<double> dg(pl.woff[d], 0.0), sp(pl.woff[d], 0.0), tnodes, gw(d + 1, gamma);
-            for (int k = 0; k < d; k++) {
-                const int n = h->n1[k + 1];
-                const double *t = nodes[k];
-                SrMode &M = modes[k];
-                M = SrMode{0, 0, 1.0, 0.0, 0.0, tnodes.size()};
-                tnodes.insert(tnodes.end(), t, t + n);
-                double *dk = dg.data() + pl.woff[k], *sk = sp.data() + pl.woff[k];
-                if (!fx[k]) { sqr_mass_cholesky(t, n, dk, sk); gw[k + 1] = gw[k] * (t[n - 1] - t[0]); continue; }
-                M = sr_held_mode(t, n, cond && cond[k] == cond[k] ? cond[k] : t[0], M.noff);
-                dk[M.cell] = M.phi0; sk[M.cell] = M.phi1;
-                gw[k + 1] = gw[k];
-            }
-            return sq_head(h, pl, dg, fx, gw, Qh, &sp, &tnodes);
-        },
+        [&](const SqPlan &pl, SqHead &Qh) { return sqr_head(h, pl, fx, nodes, cond, gamma, modes, Qh); },
         [&](auto ks, const SqAt &a, dim3 g, int tper) {
             hipLaunchKernelGGL(k_sqr_rows_mfma<decltype(ks)::value>, g, dim3(256), 0, h->stream, a.Hk, a.l, a.n, a.r1, a.Xo, a.ldx, a.C, tper, a.S, a.S + a.sheet);
         },
@@ -4521,6 +4573,285 @@ extern "C" int ttx_rosenblatt_sq_real_dev(ttx_engine *h, int64_t npts, const dou
 extern "C" int ttx_rosenblatt_sq_real_last(const ttx_engine *h, double *ms_head, double *ms_rows, double *ms_cdf, double *flops, int64_t *nfailed, int32_t *mode_ran)
 {
     return sq_last(h, "ttx_rosenblatt_sq_real_last", SMP_ROS_SQ_REAL, ms_head, ms_rows, ms_cdf, flops, nfailed, mode_ran);
+}
+
+// ---- TTX_FUN_PULLBACK: layers, their heads and device blocks, the list entries (kernels in ttx_pullback.h, rules in ttx_pullback_plan.h) ----
+// What the layers must be, for the set call and again before every evaluation (the caller may have changed a layer in between):
+// pb_check on their shapes as they stand now, then the launch shape for the largest rank and mode over the layers against a
+// workgroup's LDS.  x, nodes, gamma: the m layers (null lists: pb_check refuses them)
+static int pb_check_layers(ttx_engine *h, const char *who, int m, ttx_engine *const *x, const double *const *const *nodes, const double *gamma, const double *const *ref,
+                           PbPlan *plan, int *ldx_out, int *nmax_out)
+{
+    const int d = h->d, mm = (x && nodes && gamma && m >= 1 && m <= TTX_PULLBACK_MAX) ? m : 0;
+    std::vector<PbLayer> L(std::max(mm, 1));
+    std::vector<std::vector<int>> nn(mm), rr(mm);
+    for (int t = 0; t < mm; t++) {
+        const ttx_engine *y = x[t];
+        L[t].x = y; L[t].nodes = nodes[t]; L[t].gamma = gamma[t];
+        if (!y) continue;
+        L[t].has_train = y->ran; L[t].one_process = y->W == 1; L[t].device = y->cfg.device; L[t].d = y->d;
+        if (!y->ran) continue;
+        nn[t].assign(y->n1.begin() + 1, y->n1.begin() + 1 + y->d); rr[t].assign(y->rfinal.begin(), y->rfinal.begin() + y->d + 1);
+        L[t].n = nn[t].data(); L[t].r = rr[t].data();
+    }
+    std::string msg;
+    if (int rc = pb_check(who, m, mm ? L.data() : nullptr, h, h->cfg.device, d, h->n1.data() + 1, ref, &msg)) return fail(rc, "%s", msg.c_str());
+    int rmax = 1, nmax = 2;
+    for (int t = 0; t < m; t++) { rmax = std::max(rmax, *std::max_element(rr[t].begin(), rr[t].end())); nmax = std::max(nmax, *std::max_element(nn[t].begin(), nn[t].end())); }
+    const int ldx = (rmax + 3) & ~3;
+    const PbPlan pl = pb_plan(ldx, nmax, d, dev_ncu(h), pb_env_grid(getenv("TTX_PB_GRID")));
+    if (int rc = pb_check_lds(who, pl, ldx, nmax, d, &msg)) return fail(rc, "%s", msg.c_str());
+    if (plan) *plan = pl;
+    if (ldx_out) *ldx_out = ldx;
+    if (nmax_out) *nmax_out = nmax;
+    return TTX_OK;
+}
+extern "C" int ttx_set_integrand_pullback(ttx_engine *h, int32_t m, const ttx_layer *layer, const double *const *ref, const void *image, int64_t nbytes, const char *name,
+                                          const double *par, int32_t npar)
+{
+    const char *who = "ttx_set_integrand_pullback";
+    if (!h) return fail(TTX_EINVAL, "%s: null handle", who);
+    if (h->cfg.fun_id != TTX_FUN_PULLBACK) return fail(TTX_ESTATE, "%s: the engine was not created with fun_id = TTX_FUN_PULLBACK", who);
+    const int d = h->d, mm = (layer && m >= 1 && m <= TTX_PULLBACK_MAX) ? m : 0;
+    std::vector<ttx_engine *> xs(mm);
+    std::vector<const double *const *> nd(mm);
+    std::vector<double> gm(mm);
+    for (int t = 0; t < mm; t++) { xs[t] = layer[t].x; nd[t] = layer[t].nodes; gm[t] = layer[t].gamma; }
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    if (int rc = pb_check_layers(h, who, m, layer ? xs.data() : nullptr, nd.data(), gm.data(), ref, nullptr, nullptr, nullptr)) return rc;   // before the code object is loaded
+    std::shared_ptr<DevFun> c;
+    if (image) {
+        if (int rc = devfun_load(who, "ttx_devcomb_", "TTX_DEVICE_COMBINER", "combiner", h, image, nbytes, name, par, npar, &c)) return rc;
+        if (c->info.kind != TTX_DEVFUN_KIND_LANE) return fail(TTX_EINVAL, "%s: combiner '%s' is not of the lane form", who, name);
+    }
+    auto f = std::make_shared<PullFun>();
+    f->layer.resize(m);
+    for (int t = 0; t < m; t++) {
+        PullFun::Layer &Y = f->layer[t];
+        Y.x = layer[t].x; Y.gamma = layer[t].gamma; Y.nodes.resize(d);
+        for (int k = 0; k < d; k++) Y.nodes[k].assign(layer[t].nodes[k], layer[t].nodes[k] + Y.x->n1[k + 1]);
+    }
+    f->roff.resize(d);
+    for (int k = 0; k < d; k++) { f->roff[k] = f->ref.size(); f->ref.insert(f->ref.end(), ref[k], ref[k] + h->n1[k + 1]); }
+    f->comb = std::move(c);
+    HIPCHECK(hipStreamSynchronize(h->stream));          // nothing of an earlier combiner is in flight when its module goes
+    h->pfun = std::move(f);
+    h->pb_ref_of = nullptr;
+    return TTX_OK;
+}
+extern "C" int ttx_set_integrand_pullback_file(ttx_engine *h, int32_t m, const ttx_layer *layer, const double *const *ref, const char *path, const char *name,
+                                               const double *par, int32_t npar)
+{
+    const char *who = "ttx_set_integrand_pullback_file";
+    if (!h) return fail(TTX_EINVAL, "%s: null handle", who);
+    if (h->cfg.fun_id != TTX_FUN_PULLBACK) return fail(TTX_ESTATE, "%s: the engine was not created with fun_id = TTX_FUN_PULLBACK", who);
+    if (!path) return ttx_set_integrand_pullback(h, m, layer, ref, nullptr, 0, name, par, npar);
+    std::vector<unsigned char> img;
+    std::string text;
+    if (int rc = devfun_read_file(who, path, img, &text)) return fail(rc, "%s", text.c_str());
+    return ttx_set_integrand_pullback(h, m, layer, ref, img.data(), (int64_t)img.size(), name, par, npar);
+}
+// At the start of every call that evaluates: the layers checked again as they stand NOW; on each distinct layer engine sqr_frame's head
+// (the mass matrices' Cholesky factors, gw and sq_head with sp and the nodes), on that engine's stream and in its own work space, and
+// one wait per such engine; then the layers' blocks -- the plan's rows and offsets, core pointers, ranks, mode sizes -- into this
+// engine's scratch (SC_PB), the reference rows once per set (SC_PBREF), the two counters (SC_CNT) and with a combiner the rows x, logq,
+// val (SC_PBVAL).  figures: the call records what ttx_pullback_last reports (ttx_accchk leaves the last run's figures as they are).
+static int pb_prepare(ttx_engine *h, const char *who, bool figures, bool need_comb)
+{
+    if (!h->pfun) return fail(TTX_ESTATE, "%s: call ttx_set_integrand_pullback first", who);
+    const PullFun &f = *h->pfun;
+    if (need_comb && !f.comb) return fail(TTX_ESTATE, "%s: call ttx_set_integrand_pullback with a combiner first (the layers alone serve ttx_pullback_points)", who);
+    const int m = (int)f.layer.size(), d = h->d;
+    int rc, ldx = 4, nmax = 2;
+    PbPlan plan;
+    std::vector<ttx_engine *> xs(m);
+    std::vector<std::vector<const double *>> rows(m, std::vector<const double *>(d));
+    std::vector<const double *const *> nd(m);
+    std::vector<double> gm(m);
+    std::vector<const double *> refp(d);
+    for (int t = 0; t < m; t++) {
+        xs[t] = f.layer[t].x; gm[t] = f.layer[t].gamma;
+        for (int k = 0; k < d; k++) rows[t][k] = f.layer[t].nodes[k].data();
+        nd[t] = rows[t].data();
+    }
+    for (int k = 0; k < d; k++) refp[k] = f.ref.data() + f.roff[k];
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    if ((rc = pb_check_layers(h, who, m, xs.data(), nd.data(), gm.data(), refp.data(), &plan, &ldx, &nmax))) return rc;
+    // the heads: one per distinct layer engine
+    std::vector<SqPlan> pls(m);
+    std::vector<SqHead> Qs(m);
+    std::vector<int> head_of(m);
+    const std::vector<int> fx(d, 0);
+    for (int t = 0; t < m; t++) {
+        head_of[t] = t;
+        for (int s = 0; s < t; s++) if (xs[s] == xs[t]) { head_of[t] = s; break; }
+        if (head_of[t] != t) continue;
+        ttx_engine *y = xs[t];
+        std::vector<SrMode> modes(d);
+        sq_plan(d, y->n1.data() + 1, y->rfinal.data(), fx.data(), pls[t]);
+        if ((rc = tt_prepare(y, who)) || (rc = sqr_head(y, pls[t], fx, nd[t], nullptr, gm[t], modes, Qs[t]))) return rc;
+    }
+    for (int t = 0; t < m; t++) if (head_of[t] == t) HIPCHECK(hipStreamSynchronize(xs[t]->stream));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipSetDevice(h->cfg.device));
+    OpMeta meta(h->pb_host);
+    size_t o_l[TTX_PULLBACK_MAX], o_hoff[TTX_PULLBACK_MAX], o_woff[TTX_PULLBACK_MAX], o_core[TTX_PULLBACK_MAX], o_r[TTX_PULLBACK_MAX], o_n[TTX_PULLBACK_MAX];
+    for (int t = 0; t < m; t++) {
+        const ttx_engine *y = xs[t];
+        const SqPlan &pl = pls[head_of[t]];
+        std::vector<const double *> cp(d);
+        for (int k = 1; k <= d; k++) cp[k - 1] = core_dev(y, k);
+        o_l[t] = meta.put(pl.l); o_hoff[t] = meta.put(pl.hoff); o_woff[t] = meta.put(pl.woff); o_core[t] = meta.put(cp);
+        o_r[t] = meta.put(std::vector<int>(y->rfinal.begin(), y->rfinal.begin() + d + 1));
+        o_n[t] = meta.put(std::vector<int>(y->n1.begin() + 1, y->n1.begin() + 1 + d));
+    }
+    const size_t o_en = meta.put(std::vector<int>(h->n1.begin() + 1, h->n1.begin() + 1 + d));
+    char *dm;
+    if ((rc = meta.upload(h, SC_PB, &dm)) || (rc = buf_reserve(h, SC_CNT, 2 * sizeof(long long)))) return rc;
+    const size_t refbytes = sizeof(double) * f.ref.size(), roffat = (refbytes + 15) & ~(size_t)15;
+    if ((rc = buf_reserve(h, SC_PBREF, roffat + sizeof(size_t) * d))) return rc;
+    if (h->pb_ref_of != &f) {
+        HIPCHECK(hipMemcpyAsync(buf<char>(h, SC_PBREF), f.ref.data(), refbytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHECK(hipMemcpyAsync(buf<char>(h, SC_PBREF) + roffat, f.roff.data(), sizeof(size_t) * d, hipMemcpyHostToDevice, h->stream));
+        h->pb_ref_of = &f;
+    }
+    if (f.comb && (rc = buf_reserve(h, SC_PBVAL, sizeof(double) * (size_t)h->G * h->sel.HS * (d + 2)))) return rc;
+    HIPCHECK(hipMemsetAsync(buf<char>(h, SC_CNT), 0, 2 * sizeof(long long), h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    if ((rc = op_lds_raise(h, reinterpret_cast<const void *>(k_pb_slots), op_lds(plan.lds))) || (rc = op_lds_raise(h, reinterpret_cast<const void *>(k_pb_list), op_lds(plan.lds))))
+        return rc;
+    PbOps &O = h->pb_ops;
+    O = PbOps{};
+    O.m = m; O.d = d; O.ldx = ldx; O.nmax = nmax; O.n = (const int *)(dm + o_en);
+    O.ref = (const double *)buf<char>(h, SC_PBREF); O.roff = (const size_t *)(buf<char>(h, SC_PBREF) + roffat);
+    for (int t = 0; t < m; t++) {
+        const SqHead &Q = Qs[head_of[t]];
+        PbLayerDev &Y = O.t[t];
+        Y.H = Q.H; Y.g = Q.g; Y.nodes = Q.nodes;
+        Y.l = (const int *)(dm + o_l[t]); Y.hoff = (const size_t *)(dm + o_hoff[t]); Y.woff = (const size_t *)(dm + o_woff[t]);
+        Y.core = (const double *const *)(dm + o_core[t]); Y.r = (const int *)(dm + o_r[t]); Y.n = (const int *)(dm + o_n[t]);
+        Y.RM = xs[t]->RM; Y.SS = xs[t]->P.SS;
+    }
+    h->pb_pl = plan;
+    h->tf_figures = figures;
+    if (!figures) return TTX_OK;
+    h->tf_launches = 0; h->tf_elements = 0; h->tf_ms = 0.0; h->pb_failed = 0;
+    for (auto &e : h->tf_evs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    h->tf_evs.clear();
+    return TTX_OK;
+}
+// k_pb_slots over all slots of this process behind pass 1, and the loaded combiner's slot kernel behind that over tval [nslot][d+2]: no
+// synchronisation
+static int pb_slots(ttx_engine *h)
+{
+    DevFun &c = *h->pfun->comb;
+    DevProb &P = h->P;
+    long long nslot = (long long)h->G * h->sel.HS;
+    const PbOps &O = h->pb_ops;
+    const PbPlan &pl = h->pb_pl;
+    const short *hidx = P.hidx; unsigned char *hreq = P.hreq; double *hval = P.hval;
+    double *tval = buf<double>(h, SC_PBVAL);
+    unsigned long long *cnt = buf<unsigned long long>(h, SC_CNT);
+    if (h->tf_figures) h->tf_launches++;
+    TfScope timed(h);
+    hipLaunchKernelGGL(k_pb_slots, dim3(pl.grid(nslot)), dim3(64 * pl.waves), pl.lds, h->stream, O, nslot, hidx, (const unsigned char *)hreq, tval, cnt);
+    int m = O.d + 2, d = O.d;
+    const int *n = P.n + 1;
+    const double *par = c.par, *tv = tval;
+    const unsigned cg = (unsigned)std::max<long long>(1, std::min<long long>((nslot + c.info.block - 1) / c.info.block, 4096));
+    void *args[] = {&m, &d, &n, &par, &nslot, &hidx, &hreq, &tv, &hval};
+    DEVFUN_LAUNCHCHECK(hipModuleLaunchKernel(c.slots, cg, 1, 1, (unsigned)c.info.block, 1, 1, 0, h->stream, args, nullptr));
+    return TTX_OK;
+}
+// after the last launch of a call: the elements the transport kernel evaluated, the failed ones and, with ttx_set_profile on, its milliseconds
+static int pb_finish(ttx_engine *h)
+{
+    unsigned long long c[2] = {0, 0};
+    HIPCHECK(hipMemcpyAsync(c, buf<char>(h, SC_CNT), sizeof c, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    h->tf_elements = (int64_t)c[0]; h->pb_failed = (int64_t)c[1];
+    for (auto &e : h->tf_evs) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) h->tf_ms += ms;
+        (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second);
+    }
+    h->tf_evs.clear();
+    return TTX_OK;
+}
+// the two list entries: k_pb_list over the staged rows, in chunks; out != null: the combiner's list kernel behind it (ttx_eval_device),
+// otherwise x, logq, val themselves (ttx_pullback_points; logq, val may be null)
+static int pb_list(ttx_engine *h, const char *who, int64_t npts, const int32_t *ind, double *out, double *x, double *logq, double *val)
+{
+    const bool comb = out != nullptr;
+    if (npts < 0 || (npts > 0 && (!ind || !(out || x)))) return fail(TTX_EINVAL, "%s: null argument", who);
+    int rc = pb_prepare(h, who, true, comb);
+    if (rc) return rc;
+    if (npts == 0) return TTX_OK;
+    const int d = h->d;
+    for (int64_t p = 0; p < npts; p++)
+        for (int k = 0; k < d; k++)
+            if (ind[p * d + k] < 1 || ind[p * d + k] > h->n1[k + 1])
+                return fail(TTX_EINVAL, "%s: point %lld: index %d of mode %d is outside 1..%d", who, (long long)p, ind[p * d + k], k + 1, h->n1[k + 1]);
+    const PbOps &O = h->pb_ops;
+    const PbPlan &pl = h->pb_pl;
+    const size_t chunk = (size_t)std::min<int64_t>(npts, 1 << 16);
+    if ((rc = buf_reserve(h, SC_IND, sizeof(int) * chunk * d)) || (rc = buf_reserve(h, SC_OUT, sizeof(double) * chunk))) return rc;
+    if (comb) { if ((rc = buf_reserve(h, SC_PBVAL, sizeof(double) * std::max(chunk, (size_t)h->G * h->sel.HS) * (d + 2)))) return rc; }
+    else if ((rc = buf_reserve(h, SC_SRX, sizeof(double) * chunk * d)) || (rc = buf_reserve(h, SC_LQ, sizeof(double) * chunk))) return rc;
+    int *sind = buf<int>(h, SC_IND);
+    double *sout = buf<double>(h, SC_OUT), *sx = comb ? nullptr : buf<double>(h, SC_SRX), *slq = comb ? nullptr : buf<double>(h, SC_LQ), *tval = comb ? buf<double>(h, SC_PBVAL) : nullptr;
+    unsigned long long *cnt = buf<unsigned long long>(h, SC_CNT);
+    for (int64_t o = 0; o < npts; o += (int64_t)chunk) {
+        long long c = std::min<int64_t>((int64_t)chunk, npts - o);
+        HIPCHECK(hipMemcpyAsync(sind, ind + (size_t)o * d, sizeof(int) * (size_t)c * d, hipMemcpyHostToDevice, h->stream));
+        h->tf_launches++;
+        {
+            TfScope timed(h);
+            hipLaunchKernelGGL(k_pb_list, dim3(pl.grid(c)), dim3(64 * pl.waves), pl.lds, h->stream, O, c, (const int *)sind, sx, slq, sout, tval, cnt);
+            if (comb) {
+                DevFun &cb = *h->pfun->comb;
+                int m = d + 2, dd = d;
+                const int *n = h->P.n + 1, *ip = sind;
+                const double *par = cb.par, *tv = tval;
+                const unsigned cg = (unsigned)std::max<long long>(1, std::min<long long>((c + cb.info.block - 1) / cb.info.block, 4096));
+                void *args[] = {&m, &dd, &n, &par, &c, &ip, &tv, &sout};
+                DEVFUN_LAUNCHCHECK(hipModuleLaunchKernel(cb.list, cg, 1, 1, (unsigned)cb.info.block, 1, 1, 0, h->stream, args, nullptr));
+            }
+        }
+        if (comb) HIPCHECK(hipMemcpyAsync(out + o, sout, sizeof(double) * (size_t)c, hipMemcpyDeviceToHost, h->stream));
+        else {
+            HIPCHECK(hipMemcpyAsync(x + (size_t)o * d, sx, sizeof(double) * (size_t)c * d, hipMemcpyDeviceToHost, h->stream));
+            if (logq) HIPCHECK(hipMemcpyAsync(logq + o, slq, sizeof(double) * (size_t)c, hipMemcpyDeviceToHost, h->stream));
+            if (val) HIPCHECK(hipMemcpyAsync(val + o, sout, sizeof(double) * (size_t)c, hipMemcpyDeviceToHost, h->stream));
+        }
+        HIPCHECK(hipStreamSynchronize(h->stream));
+    }
+    HIPCHECK(hipGetLastError());
+    return pb_finish(h);
+}
+static int pb_eval_list(ttx_engine *h, int64_t npts, const int32_t *ind, double *out)
+{
+    if (npts > 0 && !out) return fail(TTX_EINVAL, "ttx_eval_device: null argument");
+    double none = 0.0;
+    return pb_list(h, "ttx_eval_device", npts, ind, out ? out : &none, nullptr, nullptr, nullptr);
+}
+extern "C" int ttx_pullback_points(ttx_engine *h, int64_t npts, const int32_t *ind, double *x, double *logq, double *val)
+{
+    const char *who = "ttx_pullback_points";
+    if (!h) return fail(TTX_EINVAL, "%s: null handle", who);
+    if (h->cfg.fun_id != TTX_FUN_PULLBACK) return fail(TTX_ESTATE, "%s: the engine was not created with fun_id = TTX_FUN_PULLBACK", who);
+    if (npts > 0 && !x) return fail(TTX_EINVAL, "%s: null argument", who);
+    double none = 0.0;
+    return pb_list(h, who, npts, ind, nullptr, x ? x : &none, logq, val);
+}
+extern "C" int ttx_pullback_last(const ttx_engine *h, double *ms, int64_t *launches, int64_t *elements, int64_t *nfailed)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_pullback_last: null handle");
+    if (ms) *ms = h->tf_ms;
+    if (launches) *launches = h->tf_launches;
+    if (elements) *elements = h->tf_elements;
+    if (nfailed) *nfailed = h->pb_failed;
+    return TTX_OK;
 }
 
 extern "C" int ttx_kernel_stats(const ttx_engine *h, int64_t launches[TTX_K_NKINDS], double ms[TTX_K_NKINDS], double bytes[TTX_K_NKINDS])

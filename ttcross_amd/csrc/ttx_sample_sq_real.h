@@ -107,26 +107,33 @@ TTX_SQR_HD double sqr_cdf(double q0, double qm, double q1, double l)
 #include "ttx_sample_sq.h"     // SqPlan, the head pass kernels, TTX_SQ_SHEET, TTX_SQ_AUTO_FLOPS
 #include "ttx_ttops.h"         // dbl4
 
-// EXACT: one thread per pair (c, i), grid-stride.  m(a, i) and m(a, i+1) by sums over ascending b from 0.0, s = sum_a m(a, i)^2 and
-// c = sum_a m(a, i) m(a, i+1) over ascending a from 0.0, separate multiplies and adds.  The thread of i + 1 forms m(a, i+1) again by
-// the same operations.  c(n-1) is not written and never read.
+// EXACT, one index i of one sample with the state x: m(a, i) and m(a, i+1) by sums over ascending b from 0.0, s = sum_a m(a, i)^2 and
+// c = sum_a m(a, i) m(a, i+1) over ascending a from 0.0, separate multiplies and adds.  The caller of i + 1 forms m(a, i+1) again by
+// the same operations.  For i = n - 1 the neighbour is i itself and cr is not to be used.  One text for k_sqr_rows_exact and for the
+// one-wave transport of ttx_pullback.h.
+__device__ inline void sqr_rows_one(const double *H, int l, int n, int r1, const double *x, int i, double &s, double &cr)
+{
+    const bool nb = i + 1 < n;
+    const double *Hi = H + i, *Hj = H + (nb ? i + 1 : i);
+    s = 0.0; cr = 0.0;
+    for (int a = 0; a < l; a++) {
+        double m = 0.0, mn = 0.0;
+#pragma unroll 4
+        for (int b = 0; b < r1; b++) { const double xb = x[b]; m = m + Hi[(size_t)n * (a + (size_t)l * b)] * xb; mn = mn + Hj[(size_t)n * (a + (size_t)l * b)] * xb; }
+        s = s + m * m;
+        cr = cr + m * mn;
+    }
+}
+// EXACT: one thread per pair (c, i), grid-stride, sqr_rows_one each.  c(n-1) is not written and never read.
 __global__ __launch_bounds__(256) void k_sqr_rows_exact(const double *H, int l, int n, int r1, const double *X, int ldx, int C, double *S, double *Cs)
 {
     const long long M = (long long)C * n;
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < M; q += (long long)gridDim.x * 256) {
         const int c = (int)(q / n), i = (int)(q % n);
-        const bool nb = i + 1 < n;
-        const double *x = X + (size_t)c * ldx, *Hi = H + i, *Hj = H + (nb ? i + 1 : i);
-        double s = 0.0, cr = 0.0;
-        for (int a = 0; a < l; a++) {
-            double m = 0.0, mn = 0.0;
-#pragma unroll 4
-            for (int b = 0; b < r1; b++) { const double xb = x[b]; m = m + Hi[(size_t)n * (a + (size_t)l * b)] * xb; mn = mn + Hj[(size_t)n * (a + (size_t)l * b)] * xb; }
-            s = s + m * m;
-            cr = cr + m * mn;
-        }
+        double s, cr;
+        sqr_rows_one(H, l, n, r1, X + (size_t)c * ldx, i, s, cr);
         S[q] = s;
-        if (nb) Cs[q] = cr;
+        if (i + 1 < n) Cs[q] = cr;
     }
 }
 
@@ -213,6 +220,36 @@ __device__ inline double sqr_log_term(const double *Sc, const double *Cc, double
     return log(dens / total);
 }
 
+// The draw of one mode for one sample by one wave, from the sample's rows Sc and Cc of the two sheets, the mode's n nodes t, its
+// defensive term g and the uniform uk: the cell masses with lanes along j, then k_sr_draw's search, clamps and placement
+// (sm_wave_search, sr_mass_within, sr_place); a cell's mass is formed again in the search's second pass from the same numbers by the
+// same expression.  A failed search sets fail and nothing else; otherwise cj is the drawn cell, xk the rounded coordinate, ci, f0, f1
+// its hat cell and values, and the mode's log term is added to lq.  One text for k_sqr_pick and for ttx_pullback.h.
+__device__ inline void sqr_pick_one(int n, const double *t, double g, const double *Sc, const double *Cc, double uk, int lane, bool &fail, double &lq, int &ci, int &cj,
+                                    double &f0, double &f1, double &xk)
+{
+    const int nc = n - 1;
+    const auto mass = [&](int j) { return sqr_mass(Sc, Cc, t, g, j, nc); };
+    const SmFound f = sm_wave_search(nc, uk, lane, mass, mass);
+    if (!f.ok) { fail = true; return; }
+    cj = f.pos;
+    double lam = 1.0;
+    if (f.hit) {
+        double q0, qm, q1;
+        (void)sqr_cell(Sc, Cc, t, g, cj, q0, qm, q1);
+        lam = sqr_invert(q0, qm, q1, sr_mass_within(f) / (t[cj + 1] - t[cj]));
+    }
+    xk = sr_place(t, n, cj, lam, ci, f0, f1);
+    lq = lq + sqr_log_term(Sc, Cc, g, ci, f0, f1, f.total);
+}
+// the chain step of one sample by one wave: sr_chain_step with the hat cell range-checked where it is read (k_sqr_step, ttx_pullback.h)
+__device__ inline void sqr_step_one(const double *G, int RM, size_t SS, int r0, int r1, int n, int ci, double f0, double f1, const double *x, double *z, int lane)
+{
+    const int top = n > 2 ? n - 2 : 0;
+    ci = ci < 0 ? 0 : ci > top ? top : ci;
+    sr_chain_step(G + (size_t)RM * ci, (size_t)RM, SS, r0, r1, n > 1, f0, f1, x, z, lane);
+}
+
 // One wave per sample, grid-stride, one launch per mode (0-based k), in the frame of k_sq_pick.  A held mode forms nothing: its
 // coordinate goes to x and 0 to cell.  Otherwise the cell masses from the two sheets with lanes along j, then k_sr_draw's
 // search, clamps and placement (sm_wave_search, sr_mass_within, sr_place); a cell's mass is formed again in the search's second pass
@@ -224,7 +261,6 @@ __global__ __launch_bounds__(256) void k_sqr_pick(int n, int k, int d, SrMode M,
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const double *t = nodes + M.noff;
-    const int nc = n - 1;
     for (long long p = (long long)blockIdx.x * nw + wave; p < npts; p += (long long)gridDim.x * nw) {
         bool fail;
         double lq = 0.0;
@@ -232,24 +268,7 @@ __global__ __launch_bounds__(256) void k_sqr_pick(int n, int k, int d, SrMode M,
         else { fail = st.fail[p] != 0; lq = st.lq[p]; }
         int ci = M.cell, cj = -1;
         double f0 = M.phi0, f1 = M.phi1, xk = M.xh;
-        if (!fail && !M.held) {
-            const double *Sc = S + (size_t)p * n, *Cc = Cs + (size_t)p * n;
-            const double g = gk[0];
-            const auto mass = [&](int j) { return sqr_mass(Sc, Cc, t, g, j, nc); };
-            const SmFound f = sm_wave_search(nc, u[(size_t)p * d + k], lane, mass, mass);
-            if (!f.ok) fail = true;
-            else {
-                cj = f.pos;
-                double lam = 1.0;
-                if (f.hit) {
-                    double q0, qm, q1;
-                    (void)sqr_cell(Sc, Cc, t, g, cj, q0, qm, q1);
-                    lam = sqr_invert(q0, qm, q1, sr_mass_within(f) / (t[cj + 1] - t[cj]));
-                }
-                xk = sr_place(t, n, cj, lam, ci, f0, f1);
-                lq = lq + sqr_log_term(Sc, Cc, g, ci, f0, f1, f.total);
-            }
-        }
+        if (!fail && !M.held) sqr_pick_one(n, t, gk[0], S + (size_t)p * n, Cs + (size_t)p * n, u[(size_t)p * d + k], lane, fail, lq, ci, cj, f0, f1, xk);
         if (lane == 0) {
             st.fail[p] = fail ? 1 : 0; st.lq[p] = lq;
             if (!fail) {
@@ -334,12 +353,7 @@ __global__ __launch_bounds__(256) void k_sqr_step(const double *G, int RM, size_
     for (long long p = (long long)blockIdx.x * nw + wave; p < npts; p += (long long)gridDim.x * nw) {
         const bool fail = st.fail[p] != 0;
         double *z = Xn + (size_t)p * ldx;
-        if (!fail) {
-            int ci = st.ci[p];
-            const int top = n > 2 ? n - 2 : 0;
-            ci = ci < 0 ? 0 : ci > top ? top : ci;
-            sr_chain_step(G + (size_t)RM * ci, (size_t)RM, SS, r0, r1, n > 1, st.f0[p], st.f1[p], Xo + (size_t)p * ldx, z, lane);
-        }
+        if (!fail) sqr_step_one(G, RM, SS, r0, r1, n, st.ci[p], st.f0[p], st.f1[p], Xo + (size_t)p * ldx, z, lane);
         if (last && val && lane == 0) val[p] = fail ? 0.0 : z[0];
     }
 }

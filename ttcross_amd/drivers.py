@@ -15,6 +15,7 @@ runs on the GPU through ttcross_amd.engine.  Usage:
     python -m ttcross_amd.drivers samplesq WORKLOAD NPTS [MODE] [REPEATS] (samples from the square of the workload's train: sample_sq; WORKLOAD signed: importance weights)
     python -m ttcross_amd.drivers samplesqreal WORKLOAD NPTS [MODE] [REPEATS] (real-valued samples from the square of the interpolant: sample_sq_real; WORKLOAD signed: importance weights)
     python -m ttcross_amd.drivers rosenblatt WORKLOAD NPTS [MODE] [REPEATS] (the way back: rosenblatt_sq_real at sample_sq_real's own points, timed next to it)
+    python -m ttcross_amd.drivers dirt D N R NLAYERS           (a layered transport over a beta ladder: layer 1 a device integrand, layers 2 and up pulled back on the device)
 
 devfun: the rational example integrand (examples/devfun/rational.hip) as a LOADED device integrand (TTX_FUN_DEVICE), in its
 wave form, or -- host -- its C twin through the host callback (TTX_FUN_HOST; needs gcc); SOURCE.hip NAME loads another
@@ -28,7 +29,7 @@ import numpy as np
 import os
 
 from .engine import (DEVFUN_DIR, TTX_FUN_COSCOEFF, TTX_FUN_DEVICE, TTX_FUN_HOST, TTX_FUN_ISING, TTX_FUN_MVN, TTX_FUN_STDNORM, TTCross,
-                     TTXError, compile_device_fun)
+                     TTXError, compile_device_fun, transport_sample)
 
 EPS = 2.220446049250313e-16
 TPI = 6.283185307179586476925286766559
@@ -1359,8 +1360,63 @@ def run_roundsum(argv, device=0, repeats=5, tt=None, tree=True):
     return r
 
 
+def run_dirt(argv, device=0, npts=1 << 14, gamma=1e-4, keep=False):
+    """dirt D N R NLAYERS: a layered (deep inverse Rosenblatt) transport towards the target of examples/devfun/pullback_tempered.hip,
+    built over the ladder beta_j = 4^(j - NLAYERS), without a point leaving the device.  Layer 1 is the cross approximation of
+    sqrt(pi^beta_1) on the physical grid (TTX_FUN_DEVICE, tempered_root); layer j + 1 is TTCross.pullback of sqrt(exp(beta_(j+1) logpi(x)
+    - logq)) through the layers so far, on a reference grid of N nodes in [0, 1].  After each layer: the effective sample size of
+    transport_sample at npts uniforms against the FINAL target, as a fraction of npts.  Prints a line per layer and one JSON line.  A
+    worked example, not a test.  keep: the layers stay open and are returned with the result."""
+    import json
+    import torch
+    torch.cuda.init()          # as run_tijk: torch's device first
+    d, n, r, nl = (int(a) for a in argv[:4])
+    mu, sigma, c, rho, lo, hi = 0.4, 0.8, 2.0, 0.1, -2.5, 3.5
+    co = compile_device_fun(os.path.join(DEVFUN_DIR, "pullback_tempered.hip"))
+    box, unit = lo + (hi - lo) * np.arange(n) / (n - 1.0), np.arange(n) / (n - 1.0)
+    box[-1], unit[-1] = hi, 1.0
+    kw = dict(accuracy=500 * EPS, pivoting=2, device=device)
+    dev = torch.device("cuda", device)
+    u = torch.from_numpy(np.random.default_rng(1).random((npts, d))).to(dev)
+
+    def ess(layers):
+        x, logq, _ = transport_sample(layers, u)
+        z = (x - mu) / sigma
+        logw = -0.5 * (z * z).sum(dim=1) - c * (x[:, 0] * x[:, 1] - rho) ** 2 - logq
+        logw = logw[torch.isfinite(logw)]
+        w = torch.exp(logw - logw.max())
+        return float(w.sum() ** 2 / (w * w).sum() / npts)
+
+    betas = [4.0 ** (j + 1 - nl) for j in range(nl)]
+    first = TTCross([n] * d, TTX_FUN_DEVICE, [], r, **kw).set_integrand_device(co, "tempered_root", [betas[0], mu, sigma, c, rho, lo, hi]).run()
+    layers, rows = [(first, [box] * d, gamma)], []
+    rows.append(dict(layer=1, beta=betas[0], run_ms=first.seconds * 1e3, neval=first.neval, ranks_max=int(first.ranks().max()), ess=ess(layers)))
+    print(f"layer 1 beta {betas[0]:.4f}: {rows[-1]['run_ms']:.2f} ms, neval {first.neval}, ESS/N {rows[-1]['ess']:.4f}", flush=True)
+    for j in range(1, nl):
+        tt = TTCross.pullback(layers, [unit] * d, (co, "pullback_tempered"), r, par=[betas[j], mu, sigma, c, rho], **kw).run()
+        tt.run()                                        # the timed run: the first one carries the first-launch costs
+        run_ms = tt.seconds * 1e3
+        tt.set_profile(True)
+        tt.run()
+        last = tt.pullback_last()
+        layers.append((tt, [unit] * d, gamma))
+        rows.append(dict(layer=j + 1, beta=betas[j], run_ms=run_ms, neval=tt.neval, ranks_max=int(tt.ranks().max()), slot_ms=last["ms"], slot_launches=last["launches"],
+                         slot_elements=last["elements"], slot_failed=last["failed"], slot_ms_per_launch=last["ms"] / max(last["launches"], 1), ess=ess(layers)))
+        print(f"layer {j + 1} beta {betas[j]:.4f}: {run_ms:.2f} ms, neval {tt.neval}, slot kernels {last['ms']:.2f} ms in {last['launches']} launches "
+              f"({last['elements']} elements, {last['failed']} failed), ESS/N {rows[-1]['ess']:.4f}", flush=True)
+    res = dict(d=d, n=n, maxrank=r, layers=nl, npts=npts, gamma=gamma, rows=rows)
+    print(json.dumps(res), flush=True)
+    if keep:                                            # the caller goes on with the layers (and closes them)
+        return dict(res, transport=layers, betas=betas, target=(mu, sigma, c, rho))
+    for y, _, _ in reversed(layers):
+        y.close()
+    return res
+
+
 if __name__ == "__main__":
-    if sys.argv[1] == "roundsum":
+    if sys.argv[1] == "dirt":
+        run_dirt(sys.argv[2:])
+    elif sys.argv[1] == "roundsum":
         run_roundsum(sys.argv[2:])
     elif sys.argv[1] == "tijk":
         run_tijk(sys.argv[2:])

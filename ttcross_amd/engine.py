@@ -18,6 +18,8 @@ TTX_FUN_ISING, TTX_FUN_STDNORM, TTX_FUN_MVN, TTX_FUN_HOST = 1, 2, 3, 4
 TTX_FUN_COSCOEFF = 5       # calc_coefficient of test_crs_coscoeff.f90: aux = [mu, Sigma column-major, a, b], par unused
 TTX_FUN_DEVICE = 6         # any user `fun` on the device: a code object written against include/ttx_device_fun.h (set_integrand_device)
 TTX_FUN_TRAINS = 7         # fun(i) = g(x_1(i), .., x_m(i)) of resident trains (TTCross.of_trains, set_integrand_trains)
+TTX_FUN_PULLBACK = 8       # fun(i) = h(x, logq, val) at the grid point of i pulled back through resident transports (TTCross.pullback)
+TTX_PULLBACK_MAX = 8
 TTX_TRAINS_MAX = 8
 TTX_TOP_PRODUCT, TTX_TOP_RATIO, TTX_TOP_SQRTABS, TTX_TOP_DEVICE = 1, 2, 3, 4
 TRAIN_OPS = {"product": TTX_TOP_PRODUCT, "ratio": TTX_TOP_RATIO, "sqrtabs": TTX_TOP_SQRTABS}
@@ -34,6 +36,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 def lib_path():
     """libttx.so of this tree; TTX_LIB names another build of the same sources (e.g. the -DTTX_STAMPS phase-timing build)."""
     return os.environ.get("TTX_LIB") or os.path.join(_HERE, "lib", "libttx.so")
+
+
+class _Layer(ctypes.Structure):
+    """ttx_layer of include/ttx.h: one layer of a pulled-back integrand"""
+    _fields_ = [("x", c_void_p), ("nodes", POINTER(POINTER(c_double))), ("gamma", c_double)]
 
 
 class TTXError(RuntimeError):
@@ -177,6 +184,10 @@ def load_library():
     L.ttx_set_integrand_trains_device.argtypes = [c_void_p, c_int32, POINTER(c_void_p), c_char_p, c_int64, c_char_p, POINTER(c_double), c_int32]
     L.ttx_set_integrand_trains_device_file.argtypes = [c_void_p, c_int32, POINTER(c_void_p), c_char_p, c_char_p, POINTER(c_double), c_int32]
     L.ttx_trainfun_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int64), POINTER(c_int64)]
+    L.ttx_set_integrand_pullback.argtypes = [c_void_p, c_int32, POINTER(_Layer), POINTER(POINTER(c_double)), c_char_p, c_int64, c_char_p, POINTER(c_double), c_int32]
+    L.ttx_set_integrand_pullback_file.argtypes = [c_void_p, c_int32, POINTER(_Layer), POINTER(POINTER(c_double)), c_char_p, c_char_p, POINTER(c_double), c_int32]
+    L.ttx_pullback_points.argtypes = [c_void_p, c_int64, POINTER(c_int32), POINTER(c_double), POINTER(c_double), POINTER(c_double)]
+    L.ttx_pullback_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]
     L.ttx_k_exp.argtypes = [c_int32, c_int64, POINTER(c_double), POINTER(c_double)]
     L.ttx_exp_host.argtypes = [c_int64, POINTER(c_double), POINTER(c_double)]
     _lib = L
@@ -376,6 +387,30 @@ def neighbour_ranks(nproc, world_rank, world_size):
     """(left, right) process ranks the boundary groups exchange with; -1 where the chain ends."""
     g0, G = split_groups(nproc, world_rank, world_size)
     return (world_rank - 1 if g0 > 0 else -1), (world_rank + 1 if g0 + G < nproc else -1)
+
+
+def transport_sample(layers, u, mode="exact"):
+    """The composed inverse Rosenblatt map of a layered transport: layers = [(train, nodes, gamma), ..], layer 1 first; u (npts, d) in
+    [0, 1], a host array or a float64 torch tensor on the layers' device, which then never leaves it (sample_sq_real's _dev entry).
+    The layers are applied in the order m .. 1.  Returns x, logq (lq_m, then + lq_t for t = m-1 .. 1) and val of layer 1."""
+    logq = val = None
+    for x, nodes, gamma in reversed(list(layers)):
+        o = x.sample_sq_real(u, nodes, gamma=gamma, mode=mode, want=("x", "logq", "val"))
+        u, val = o["x"], o["val"]
+        logq = o["logq"] if logq is None else logq + o["logq"]
+    return u, logq, val
+
+
+def transport_rosenblatt(layers, x, mode="exact"):
+    """The way back of transport_sample: the layers' forward Rosenblatt maps in the order 1 .. m (rosenblatt_sq_real, its _dev entry
+    for a tensor on the device).  Returns u, the summed logq and val of layer 1 at x."""
+    logq = val = None
+    for y, nodes, gamma in layers:
+        o = y.rosenblatt_sq_real(x, nodes, gamma=gamma, mode=mode, want=("u", "logq", "val"))
+        x = o["u"]
+        val = o["val"] if val is None else val
+        logq = o["logq"] if logq is None else logq + o["logq"]
+    return x, logq, val
 
 
 def make_dist_transport(dist, group=None):
@@ -613,9 +648,80 @@ class TTCross:
         _check(load_library().ttx_trainfun_last(self._h, ctypes.byref(ms), ctypes.byref(nl), ctypes.byref(ne)))
         return dict(ms=ms.value, launches=nl.value, elements=ne.value)
 
+    @classmethod
+    def pullback(cls, layers, ref, fun, maxrank, accuracy=None, pivoting=3, quad=None, nproc=1, par=None, device=None):
+        """An engine whose integrand is a loaded device function of a point pulled back through resident squared-train transports
+        (include/ttx.h: TTX_FUN_PULLBACK): the next layer of a layered transport.  layers: a list of (train, nodes, gamma), layer 1
+        first (the outermost, built first; its nodes span the physical box, the others run from 0 to 1); ref: the reference grid in
+        [0, 1], one array for all modes or a list of d -- its sizes are the engine's mode sizes; fun: (image_or_path, name) of a
+        TTX_DEVICE_COMBINER called with v = [x_1 .. x_d, logq, val], or None to record the layers only (pullback_points works, run
+        does not).  .run() is the cross sweep."""
+        layers = list(layers)
+        if not layers:
+            raise ValueError("pullback: at least one layer")
+        d = layers[0][0].d
+        refs = [ref] * d if not isinstance(ref, (list, tuple)) or (len(ref) and np.ndim(ref[0]) == 0) else list(ref)
+        refs = [np.ascontiguousarray(r, dtype=np.float64).ravel() for r in refs]
+        tt = cls([r.size for r in refs], TTX_FUN_PULLBACK, [], maxrank, pivoting=pivoting, accuracy=accuracy, quad=quad, nproc=nproc,
+                 device=layers[0][0].device if device is None else device)
+        try:
+            return tt.set_integrand_pullback(layers, refs, fun, par)
+        except Exception:
+            tt.close()
+            raise
+
+    def set_integrand_pullback(self, layers, ref, fun=None, par=None):
+        """The layers, the reference grid and the combiner of an engine created with fun_id = TTX_FUN_PULLBACK (include/ttx.h).
+        layers: a list of (train, nodes, gamma); ref: one array for all modes or a list of d; fun: (image_or_path, name) or None; par
+        is COPIED to the device.  The engine records the layers' handles and looks at them again at the start of every run / accchk /
+        eval_device / pullback_points; this wrapper keeps the layer objects referenced."""
+        L = load_library()
+        layers = [tuple(y) for y in layers]
+        arr = (_Layer * max(len(layers), 1))()
+        keep = []
+        for t, (x, nodes, gamma) in enumerate(layers):
+            arr[t].x = x._h if x is not None else None
+            arr[t].gamma = float(gamma)
+            if x is not None and nodes is not None:
+                _, rowp = x._node_rows(nodes, f"set_integrand_pullback: layer {t + 1}")
+                arr[t].nodes = ctypes.cast(rowp, POINTER(POINTER(c_double)))
+                keep.append(rowp)
+        refs = [ref] * self.d if not isinstance(ref, (list, tuple)) or (len(ref) and np.ndim(ref[0]) == 0) else list(ref)
+        _, refp = self._node_rows(refs, "set_integrand_pullback: ref")
+        p = np.zeros(0) if par is None else np.ascontiguousarray(par, dtype=np.float64)
+        pp = _dp(p) if p.size else None
+        if fun is None:
+            _check(L.ttx_set_integrand_pullback(self._h, len(layers), arr, refp, None, 0, None, pp, p.size))
+        else:
+            image_or_path, name = fun
+            if isinstance(image_or_path, (bytes, bytearray, memoryview)):
+                img = bytes(image_or_path)
+                _check(L.ttx_set_integrand_pullback(self._h, len(layers), arr, refp, img, len(img), name.encode(), pp, p.size))
+            else:
+                _check(L.ttx_set_integrand_pullback_file(self._h, len(layers), arr, refp, os.fsencode(image_or_path), name.encode(), pp, p.size))
+        self._operands = [y[0] for y in layers]
+        return self
+
+    def pullback_points(self, ind):
+        """x (npts, d), logq and val of a TTX_FUN_PULLBACK engine at the multi-indices ind (npts x d, 1-based): the reference grid's
+        points pulled back through the layers, bit for bit the chain of sample_sq_real(.., mode="exact") calls (include/ttx.h:
+        ttx_pullback_points).  A failed sample has x NaN, logq NaN and val 0."""
+        ind = np.ascontiguousarray(ind, dtype=np.int32).reshape(-1, self.d)
+        x, lq, v = np.zeros((ind.shape[0], self.d)), np.zeros(ind.shape[0]), np.zeros(ind.shape[0])
+        _check(load_library().ttx_pullback_points(self._h, ind.shape[0], _ip(ind), _dp(x), _dp(lq), _dp(v)))
+        return x, lq, v
+
+    def pullback_last(self):
+        """Of the last run / eval_device / pullback_points of a TTX_FUN_PULLBACK engine: {'ms', 'launches', 'elements', 'failed'} of
+        the transport kernel (ms needs set_profile(True)) (include/ttx.h: ttx_pullback_last)."""
+        ms, nl, ne, nf = c_double(), c_int64(), c_int64(), c_int64()
+        _check(load_library().ttx_pullback_last(self._h, ctypes.byref(ms), ctypes.byref(nl), ctypes.byref(ne), ctypes.byref(nf)))
+        return dict(ms=ms.value, launches=nl.value, elements=ne.value, failed=nf.value)
+
     def eval_device(self, ind):
         """The loaded device integrand at the multi-indices ind (npts x d, 1-based), through the code object's list kernel; for a
-        TTX_FUN_TRAINS engine the operands at those indices and the combiner."""
+        TTX_FUN_TRAINS engine the operands at those indices and the combiner, for a TTX_FUN_PULLBACK engine the combiner at the
+        pulled-back points."""
         ind = np.ascontiguousarray(ind, dtype=np.int32).reshape(-1, self.d)
         out = np.zeros(ind.shape[0])
         _check(load_library().ttx_eval_device(self._h, ind.shape[0], _ip(ind), _dp(out)))
