@@ -902,6 +902,13 @@ int ttx_cluster_fallbacks(const ttx_engine *h);
  * launch before (TTX_CL_LISTS=0) -- and, of the last run's launches of local group 0, out[1] those that took the carried lists and
  * out[2] those that took the carried word.  All 0 off the cluster path.  Results are identical in every form. */
 int ttx_cluster_entry(const ttx_engine *h, int64_t out[3]);
+/* the stretch between two sweeps of the pipelined cluster loop, the forms in force: out[0] 1 the tail launch's event is the launch's
+ * own completion signal, 0 it is recorded behind the launch (TTX_TAIL_EVENT=marker asks for that; the engine also goes back to it
+ * for the rest of its life once the runtime refuses the extended launch, counted in out[1]); out[2] the boundary blocks of the
+ * exchange request their header words together and evaluate the corner of Ising C over staged values (TTX_TAIL_LEAN=0 turns it
+ * off); out[3] the cluster kernel's exit packs the left-going message on workgroup 1 (TTX_CL_PACK2=0).  Results are identical in
+ * every form. */
+int ttx_sweep_gap(const ttx_engine *h, int32_t out[4]);
 /* runs of this engine that were repeated without the wave teams / the wave relay of the Ising D/E half-step because a launch
  * reported a fault (more units than the grid the host sized, a broken hand-over); results are identical on every path */
 int ttx_det_fallbacks(const ttx_engine *h);

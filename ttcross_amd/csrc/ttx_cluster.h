@@ -216,6 +216,7 @@ __device__ __forceinline__ bool cluster_sync(unsigned *ctr, unsigned target, int
 #define CL_ZCARRY 2     // ... and travel from launch to launch through the group's image in global memory (TTX_CL_LISTS=0: rebuilt per launch)
 #define CL_WORD 4       // the generator word is taken from the launch before (TTX_CL_WORD=0: raised from rngpos per launch)
 #define CL_POWTAB 8     // the generator's jump powers come from cl_powtab (TTX_CL_POWTAB=0: three square-and-multiply loops per launch)
+#define CL_PACK2 16     // exit: block 1 packs the left-going boundary message beside block 0 (TTX_CL_PACK2=0: block 0 packs both)
 static_assert(CL_POWTAB_N == CB, "one table entry per thread of a workgroup");
 __device__ const ClPowTab cl_powtab = cl_make_powtab();
 // the kernel's argument block as the launch lays it out (k_sweep_cluster's parameter list): the exit reads it afresh
@@ -854,6 +855,14 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
         CST_END();
     }
     CSE_MARK();
+    if (cb == 1) {
+        // the left-going boundary message, beside block 0's list image, scalars and right-going message (cl_pack_block): all it reads lies
+        // in front of the closing cluster_sync.  Reached, like block 0's exit, only by a launch that ran all its bond steps.
+        const ClArgs *K = (const ClArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(K));
+        if (cl_pack_block(CL_PACK_LEFT, K->NB, (K->zkeep & CL_PACK2) != 0) == 1) exch_pack_left(K->P, g);
+        CSE(3);
+    }
     if (cb == 0) {
         // what the next launch's entry takes instead of recomputing it: the pivot lists as they stand (the last insertion lies in front of
         // the closing cluster_sync) with this launch's number, and the generator word of the position written below.  Reached only by a
@@ -876,7 +885,9 @@ __global__ __launch_bounds__(CB) void k_sweep_cluster(DevProb P, int dir, int ns
             if (P.tail_side) gs.amax_bnd[epoch & 1] = 0.0;      // the slot this sweep's tail launch raises (ttx_dev.h)
         }
         __syncthreads();
-        exch_pack_group(P, g);          // the group's outgoing boundary messages (saves the separate k_exch_pack launch)
+        // the group's outgoing boundary messages (saves the separate k_exch_pack launch): the left-going one only where block 1 does not
+        exch_pack_right(P, g);
+        if (cl_pack_block(CL_PACK_LEFT, K->NB, (K->zkeep & CL_PACK2) != 0) == 0) exch_pack_left(P, g);
         CSE(3);
         CSE_END();
     }

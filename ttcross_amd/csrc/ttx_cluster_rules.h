@@ -111,5 +111,12 @@ TTX_HD bool cl_word_valid(uint64_t word, uint64_t wpos, uint64_t rngpos) { retur
 // The sorted pivot lists a launch leaves in global memory carry the number of the launch that wrote them (GroupState::zk_epoch;
 // 0 after a reset: launches count from 1).  Launch `epoch` of a run takes them only from launch epoch - 1 of the same run.
 TTX_HD bool cl_lists_valid(int tag, int epoch) { return tag != 0 && tag == epoch - 1; }
+// Who packs what at the exit of a launch (tests/sweep_gap_main.cpp).  Everything the pack reads was published in front of the closing
+// cluster_sync of the last bond step, which every workgroup has passed, so any of them may pack.  Part CL_PACK_RIGHT is red[] with
+// the right-going message (exch_pack_right), part CL_PACK_LEFT the left-going message (exch_pack_left): workgroup 0 writes the group
+// scalars red[] reads and packs the right part, workgroup 1 -- where the cluster has one and `split` (TTX_CL_PACK2) allows -- the left.
+#define CL_PACK_RIGHT 0
+#define CL_PACK_LEFT 1
+TTX_HD int cl_pack_block(int part, int NB, bool split) { return (part == CL_PACK_LEFT && split && NB >= 2) ? 1 : 0; }
 // ints of one group's image: [nsteps][2][RM] keys and [nsteps][2] counts, as they lie in LDS, rounded up to 16 bytes
 TTX_HD size_t cl_zimage_ints(int nsteps, int RM) { return ((size_t)nsteps * 2 * (size_t)RM + 2 * (size_t)nsteps + 3) & ~(size_t)3; }

@@ -80,6 +80,9 @@ struct CreateEnv {
     bool cl_powtab_off = false;     // TTX_CL_POWTAB=0
     bool cl_word_off = false;       // TTX_CL_WORD=0
     bool cl_lists_off = false;      // TTX_CL_LISTS=0
+    EnvText tail_event;             // TTX_TAIL_EVENT = marker | kernel
+    bool tail_lean_off = false;     // TTX_TAIL_LEAN=0
+    bool cl_pack2_off = false;      // TTX_CL_PACK2=0
 };
 // the switches as `get` finds them (get(name): the value, or nullptr where unset): an integer as atoi reads it, "=0" as atoi(value) == 0
 template <class Get>
@@ -112,6 +115,8 @@ CreateEnv create_env_from(Get get)
     v.fin_early_off = off("TTX_FIN_EARLY"); v.fin_skip_exch_off = off("TTX_FIN_SKIP_EXCH");
     v.init_wide_off = off("TTX_INIT_WIDE"); v.quad_lds_off = off("TTX_QUAD_LDS");
     v.cl_powtab_off = off("TTX_CL_POWTAB"); v.cl_word_off = off("TTX_CL_WORD"); v.cl_lists_off = off("TTX_CL_LISTS");
+    v.tail_event = text("TTX_TAIL_EVENT"); v.tail_lean_off = off("TTX_TAIL_LEAN");
+    v.cl_pack2_off = off("TTX_CL_PACK2");
     return v;
 }
 struct DevCaps { int ncu = 0; bool coop = false; };          // multiProcessorCount, hipDeviceAttributeCooperativeLaunch
@@ -176,6 +181,10 @@ struct CreatePlan {
     int cl_test_abort = 0; bool dbg_waves = false;
     bool sweep_tail = true;                         // the pipelined cluster loop ends a sweep with k_exch_tail (TTX_TAIL=0: max/apply and boundary launches)
     bool sweep_tail_side = true;                    // ... and its summary runs on the quadrature's stream (TTX_TAIL_SIDE=0: k_sweep_end on the main stream)
+    // the stretch between the last bond step of one sweep and the first of the next (profiles/sweep_gap_mi355x.txt)
+    bool tail_event_kernel = true;                  // ev_tail is the tail launch's own completion signal (TTX_TAIL_EVENT=marker: an event recorded behind it)
+    bool tail_lean = true;                          // boundary blocks request their header words together and the LU ahead of the corner (TTX_TAIL_LEAN=0: one by one)
+    bool cl_pack2 = true;                           // the cluster kernel's exit packs the left-going message on block 1 (TTX_CL_PACK2=0: block 0 packs both)
     // the two ends of a run around its sweeps (ttx_loop_plan.h says where each applies)
     bool head_direct = true;                        // the initial summary goes from k_init_final into the pinned slot (TTX_HEAD_DIRECT=0: k_collect and a copy in front of sweep kernel 1)
     size_t lds_qtree = 0;                           // k_quad_tree multiplies in LDS: the bytes of its two regions of nproc matrices (quad_tree_lds); 0 (also TTX_QUAD_LDS=0): in the global scratch
@@ -421,6 +430,10 @@ inline CreatePlan create_plan(const ttx_config &cfg, bool nofun, const CreateEnv
         }
         p.cl_test_abort = env.cluster_test_abort; p.dbg_waves = env.dbg_waves;
         p.sweep_tail = !env.tail_off; p.sweep_tail_side = !env.tail_side_off;
+        if (env.tail_event.set && env.tail_event.v != "marker" && env.tail_event.v != "kernel")
+            return plan_refuse(p, TTX_EINVAL, "TTX_TAIL_EVENT must be marker or kernel (got %s)", env.tail_event.v.c_str());
+        p.tail_event_kernel = !(env.tail_event.set && env.tail_event.v == "marker");
+        p.tail_lean = !env.tail_lean_off; p.cl_pack2 = !env.cl_pack2_off;
         p.head_direct = !env.head_direct_off; p.init_wave = !env.init_wave_off; p.init_wide = !env.init_wide_off;
         p.fin_early = !env.fin_early_off; p.fin_skip_exch = !env.fin_skip_exch_off;
         const std::string want_sweep = env.sweep.set ? env.sweep.v : "auto";

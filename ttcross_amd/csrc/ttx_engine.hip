@@ -6,6 +6,7 @@
 // previous kernel's partial arg-max records.  The host synchronises once per sweep to read the
 // reference's per-sweep report line and to apply the stop rule (lib/dmrgg.f90:1010-1019).
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>    // hipExtLaunchKernel: a launch whose completion signal is an event (end_side)
 
 #include <chrono>
 #include <cmath>
@@ -265,6 +266,9 @@ struct ttx_engine {
     int cluster_fallbacks = 0;          // runs replayed on the chain path after a cluster abort
     int det_fallbacks = 0, de5_fallbacks = 0;   // ... without teams, without the relay
     bool cluster_aborted = false;
+    // ev_tail as the tail launch's own completion signal (sel.tail_event_kernel): once the extended launch is refused, the engine records
+    // the event behind a plain launch for the rest of its life
+    bool tail_event_retired = false; int tail_event_fallbacks = 0;
     double *h_svd = nullptr; double svd_seq = 0.0;   // pinned: [seq, rank, sweeps, sv...] of the core dtt_svd works on (k_svd_report)
     hipStream_t qstream = nullptr;      // forked per-sweep quadrature (single-process runs)
     hipEvent_t ev_sum[2] = {nullptr, nullptr}, ev_val[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr}, ev_qb[2] = {nullptr, nullptr}, ev_fin[2] = {nullptr, nullptr};
@@ -1461,7 +1465,8 @@ struct SweepRun {
     {
         const CreatePlan &s = h->sel;
         int dir = 2 - it_ % 2, epoch = it_, nsteps = h->nbmax, NB = s.cluster, ldsinv = s.cluster_ldsinv;
-        int zkeep = (s.cluster_zkeep ? CL_ZKEEP : 0) | (s.cl_lists ? CL_ZCARRY : 0) | (s.cl_word ? CL_WORD : 0) | (s.cl_powtab ? CL_POWTAB : 0);     // the forms of the entry
+        int zkeep = (s.cluster_zkeep ? CL_ZKEEP : 0) | (s.cl_lists ? CL_ZCARRY : 0) | (s.cl_word ? CL_WORD : 0) | (s.cl_powtab ? CL_POWTAB : 0)     // the forms of the entry
+                    | (s.cl_pack2 ? CL_PACK2 : 0);      // ... and of the exit
         const dim3 grid(8 * NB * ((G + 7) / 8)), block(CB);
         KScope ks(h, TTX_K_HALFSTEP, 1);
         if (!cluster) hipLaunchKernelGGL(k_sweep_fused, dim3(G), dim3(FB), s.lds_fused, st, P, dir, nsteps);
@@ -1545,20 +1550,30 @@ struct SweepRun {
         if (L.forkq) HIPCHECK(hipStreamWaitEvent(h->qstream, h->ev_sum[slot], 0));    // fork point = end of the sweep's main-stream work
         return enqueue_quadrature(it_, L.forkq ? h->qstream : st);
     }
+    int tail_lean() const { return h->sel.tail_lean ? 1 : 0; }      // the form of the boundary blocks (ttx_exchange.h)
     // side: one launch on the main stream; the rest of the sweep's end goes to the quadrature's stream (enqueue_side)
     int end_side(int it_)
     {
         const int slot = it_ & 1;
         HIPCHECK(hipStreamWaitEvent(st, h->ev_val[slot ^ 1], 0));       // the previous quadrature is done with the boundaries and with rq
         KScope ks(h, TTX_K_EXCHANGE, 1);
-        launch(st, plan.exch_tail, P, it_);
+        // ev_tail is the dispatch packet's own completion signal: no marker packet stands between the tail and the next sweep kernel
+        if (h->sel.tail_event_kernel && !h->tail_event_retired) {
+            const KLaunch &k = plan.exch_tail;
+            int lean = tail_lean();
+            void *args[] = {(void *)&P, (void *)&it_, (void *)&lean};
+            if (hipExtLaunchKernel(k.fn, k.grid, k.block, args, k.lds, st, nullptr, h->ev_tail[slot], 0) == hipSuccess) return TTX_OK;
+            (void)hipGetLastError();
+            h->tail_event_retired = true; h->tail_event_fallbacks++;
+        }
+        launch(st, plan.exch_tail, P, it_, tail_lean());
         HIPCHECK(hipEventRecord(h->ev_tail[slot], st));
         return TTX_OK;
     }
     // tail: MAX / apply and the boundary blocks as independent blocks of one launch (the cluster kernel packed at its end), then the rule
     int end_tail(int it_)
     {
-        { KScope ks(h, TTX_K_EXCHANGE, 1); launch(st, plan.exch_tail, P, it_); }
+        { KScope ks(h, TTX_K_EXCHANGE, 1); launch(st, plan.exch_tail, P, it_, tail_lean()); }
         hipLaunchKernelGGL(k_sweep_end, dim3(1), dim3(256), 0, st, P, it_, h->h_sum_base + (size_t)(it_ & 1) * h->SB, 1);
         return TTX_OK;
     }
@@ -1575,7 +1590,7 @@ struct SweepRun {
                 if (int rc = allreduce_dev(h, P.redsend, P.redrecv, 4, 1)) return rc;
             }
             hipLaunchKernelGGL(k_exch_max_apply, dim3(G), dim3(256), lds_fpersist(P), st, P, h->W > 1 ? 1 : 0, nproc > 1 ? 1 : 0);
-            if (nproc > 1) { if (int rc = EV(plan.exch_boundary)) return rc; }
+            if (nproc > 1) { if (int rc = EV(plan.exch_boundary, tail_lean())) return rc; }
         }
         double *const pinned = h->h_sum_base + (size_t)(it_ & 1) * h->SB;
         if (L.pipe) hipLaunchKernelGGL(k_sweep_end, dim3(1), dim3(256), 0, st, P, it_, h->W > 1 ? P.sumsend : pinned, 0);
@@ -3060,6 +3075,14 @@ extern "C" int ttx_cluster_entry(const ttx_engine *h, int64_t out[3])
     HIPCHECK(hipStreamSynchronize(h->stream));
     HIPCHECK(hipMemcpy(&g0s, h->P.gs, offsetof(GroupState, S), hipMemcpyDeviceToHost));
     out[1] = g0s.n_zload; out[2] = g0s.n_wload;
+    return TTX_OK;
+}
+extern "C" int ttx_sweep_gap(const ttx_engine *h, int32_t out[4])
+{
+    if (!h || !out) return fail(TTX_EINVAL, "ttx_sweep_gap: null argument");
+    const CreatePlan &s = h->sel;
+    out[0] = (s.tail_event_kernel && !h->tail_event_retired) ? 1 : 0; out[1] = h->tail_event_fallbacks;
+    out[2] = s.tail_lean ? 1 : 0; out[3] = s.cl_pack2 ? 1 : 0;
     return TTX_OK;
 }
 extern "C" int ttx_det_fallbacks(const ttx_engine *h) { return h ? h->det_fallbacks + h->de5_fallbacks : 0; }

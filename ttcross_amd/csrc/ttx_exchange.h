@@ -11,8 +11,11 @@
 // through every rank (which makes far bonds lag by one sweep per hop), the owner ships the FLATTENED
 // multi-index of its new boundary pivot to its direct neighbour -- the only rank that ever evaluates with it.
 // ------------------------------------------------------------------------------------------------
-// pack both outgoing messages of group g and its entry of the MAX all-reduce (called by every thread of a block)
-__device__ __forceinline__ void exch_pack_group(const DevProb &P, int g)
+// The two outgoing messages of group g and its entry of the MAX all-reduce, each half called by every thread of a block.  The halves
+// write disjoint memory and read nothing the other writes, so two blocks may run them side by side (the cluster kernel's exit,
+// cl_pack_block of ttx_cluster_rules.h).  The flag, the ranks and the mode size of a half are requested together, ahead of the copies.
+// right: red[] and the message to the right neighbour -- own last bond q = last, boundary core q+1
+__device__ __forceinline__ void exch_pack_right(const DevProb &P, int g)
 {
     const int tid = threadIdx.x, m = P.d;
     GroupState &gs = P.gs[g];
@@ -22,39 +25,39 @@ __device__ __forceinline__ void exch_pack_group(const DevProb &P, int g)
         double *red = P.red + (size_t)g * 4;
         red[0] = gs.amax; red[1] = gs.pivotmax; red[2] = (gs.pivotmin > 0.0) ? -gs.pivotmin : -999e9;   // :853-859
     }
-    {   // to the right neighbour: own last bond q = last, boundary core q+1
-        const int q = last, u = upd[q];
-        char *base = P.msgR + (size_t)g * P.MSZ;
-        int *hh = (int *)base; int *ix = hh + XH; double *dd = (double *)(base + P.IOFF);
-        if (tid == 0) { hh[0] = u; hh[1] = r[q]; }
-        const int rq = r[q];
-        const double *gI = inv_ptr(P, g, q, first);
-        for (int x = tid; x < rq * rq; x += blockDim.x) dd[(size_t)P.RM * P.NM + x] = gI[x];           // inv(q) for dtt_lua, :1225
-        if (u) {
-            const short *Lt = L_ptr(P, g, q, first);
-            for (int x = tid; x < q; x += blockDim.x) ix[x] = Lt[(size_t)x * P.RM + (rq - 1)];
-            // newest row of core q+1: arg(q+1)(r(q), :, 1:rr(q+1))  (dmrggmp.f90:580)
-            const double *A = core_ptr(P, P.arg, g, q + 1, first);
-            const int n2 = P.n[q + 1], rrq1 = rr[q + 1];
-            for (int x = tid; x < n2 * rrq1; x += blockDim.x) dd[x] = A[(rq - 1) + (size_t)P.RM * (x % n2) + P.SS * (x / n2)];
-        }
-    }
-    {   // to the left neighbour: own first bond q = first, boundary core q
-        const int q = first, u = upd[q];
-        char *base = P.msgL + (size_t)g * P.MSZ;
-        int *hh = (int *)base; int *ix = hh + XH; double *dd = (double *)(base + P.IOFF);
-        if (tid == 0) { hh[0] = u; hh[1] = r[q]; }
-        if (u) {
-            const int rq = r[q];
-            const short *Rt = R_ptr(P, g, q, first);
-            for (int x = tid; x < m - q; x += blockDim.x) ix[x] = Rt[(size_t)x * P.RM + (rq - 1)];
-            // newest column of core q: arg(q)(1:rr(q-1), :, r(q))  (dmrgg.f90:889)
-            const double *A = core_ptr(P, P.arg, g, q, first);
-            const int n1 = P.n[q], rr0 = rr[q - 1];
-            for (int x = tid; x < rr0 * n1; x += blockDim.x) dd[x] = A[(x % rr0) + (size_t)P.RM * (x / rr0) + P.SS * (rq - 1)];
-        }
+    const int q = last, u = upd[q], rq = r[q], rrq1 = rr[q + 1], n2 = P.n[q + 1];
+    char *base = P.msgR + (size_t)g * P.MSZ;
+    int *hh = (int *)base; int *ix = hh + XH; double *dd = (double *)(base + P.IOFF);
+    if (tid == 0) { hh[0] = u; hh[1] = rq; }
+    const double *gI = inv_ptr(P, g, q, first);
+    for (int x = tid; x < rq * rq; x += blockDim.x) dd[(size_t)P.RM * P.NM + x] = gI[x];           // inv(q) for dtt_lua, :1225
+    if (u) {
+        const short *Lt = L_ptr(P, g, q, first);
+        for (int x = tid; x < q; x += blockDim.x) ix[x] = Lt[(size_t)x * P.RM + (rq - 1)];
+        // newest row of core q+1: arg(q+1)(r(q), :, 1:rr(q+1))  (dmrggmp.f90:580)
+        const double *A = core_ptr(P, P.arg, g, q + 1, first);
+        for (int x = tid; x < n2 * rrq1; x += blockDim.x) dd[x] = A[(rq - 1) + (size_t)P.RM * (x % n2) + P.SS * (x / n2)];
     }
 }
+// left: the message to the left neighbour -- own first bond q = first, boundary core q
+__device__ __forceinline__ void exch_pack_left(const DevProb &P, int g)
+{
+    const int tid = threadIdx.x, m = P.d;
+    const int first = P.gs[g].first;
+    const int *r = P.r + (size_t)g * (m + 2), *rr = P.rr + (size_t)g * (m + 2), *upd = P.upd + (size_t)g * (m + 2);
+    const int q = first, u = upd[q], rq = r[q], rr0 = rr[q - 1], n1 = P.n[q];
+    char *base = P.msgL + (size_t)g * P.MSZ;
+    int *hh = (int *)base; int *ix = hh + XH; double *dd = (double *)(base + P.IOFF);
+    if (tid == 0) { hh[0] = u; hh[1] = rq; }
+    if (u) {
+        const short *Rt = R_ptr(P, g, q, first);
+        for (int x = tid; x < m - q; x += blockDim.x) ix[x] = Rt[(size_t)x * P.RM + (rq - 1)];
+        // newest column of core q: arg(q)(1:rr(q-1), :, r(q))  (dmrgg.f90:889)
+        const double *A = core_ptr(P, P.arg, g, q, first);
+        for (int x = tid; x < rr0 * n1; x += blockDim.x) dd[x] = A[(x % rr0) + (size_t)P.RM * (x / rr0) + P.SS * (rq - 1)];
+    }
+}
+__device__ __forceinline__ void exch_pack_group(const DevProb &P, int g) { exch_pack_right(P, g); exch_pack_left(P, g); }
 
 // MAX all-reduce (:861), stage 1: combine the groups of this GPU into redsend[0..2]
 __global__ void k_exch_localmax(DevProb P)
@@ -151,7 +154,7 @@ __global__ __launch_bounds__(256) void k_exch_max_apply(DevProb P, int from_recv
 // (boundary_neval).  What remains shared is read-only in the launch (own ranks, flags, tables, inv of the own bonds; the apply
 // block writes column hh[1] - 1 of the tables of bonds first - 1 / last + 1, a corner reads columns of older pivots there).
 template <int FUN, bool MSG>
-__device__ __forceinline__ void exch_boundary_block(const DevProb &P, int bx, int g, int par_)
+__device__ __forceinline__ void exch_boundary_block(const DevProb &P, int bx, int g, int par_, int lean)
 {
     extern __shared__ __align__(16) double dyn[];
     __shared__ double s_bc;
@@ -170,22 +173,51 @@ __device__ __forceinline__ void exch_boundary_block(const DevProb &P, int bx, in
     __shared__ double s_corner;
     const bool dewave = (FUN == FUN_ISING) && P.ising_id != 1 && P.bnd_wave;
     const bool mvwave = (FUN == FUN_MVN) && P.bnd_wave;
+    // lean (TTX_TAIL_LEAN, profiles/sweep_gap_mi355x.txt): the words a block decides on -- the message's address, then its header, the
+    // own ranks, flag and mode size -- are requested together, each batch one round trip, from addresses that are valid whatever the
+    // decisions turn out to be; a block that returns early still returns before it writes anything.  And the corner of Ising C is
+    // evaluated as in the cluster kernel: all threads stage the node and weight VALUES of the multi-index (in the region of lu, which
+    // is staged behind the evaluation), and the one thread runs the same chains over them (f_ising_c3v: the operations of
+    // f_ising_c3 in its order) without an index and a table lookup in front of every step.
+    const char *in_r = nullptr, *in_l = nullptr;
+    if (lean) { in_r = P.inR[g]; in_l = P.inL[g]; }
+    const bool cval = (FUN == FUN_ISING) && lean && P.ising_id == 1 && 4 * VSr <= 64 * 64;
+    double *cAn = lu, *cAw = cAn + VSr, *cBn = cAw + VSr, *cBw = cBn + VSr;
+    const double *gnodes = P.par - 1, *gweights = gnodes + (cval ? P.n[1] : 0);       // node / weight of index i: gnodes[i], gweights[i]
     if (bx < P.NM) {
         const int k = bx, p = last, br = last + 1;
-        if (!P.inR[g]) return;
-        const int *hh = (const int *)P.inR[g], *ix = hh + XH;         // the message's header and flattened pivot index (dims br+1..m)
-        if (!(MSG ? hh[0] : upd[br]) || k >= P.n[br]) return;
-        const int rp = r[p], rrp = rr[p], snew = (MSG ? hh[1] : r[br]) - 1, n2 = P.n[br];
-        const double *msg = (const double *)(P.inR[g] + P.IOFF);      // (rr(p), n(p+1))
+        const char *in = lean ? in_r : P.inR[g];
+        const int *hh = (const int *)in, *ix = hh + XH;               // the message's header and flattened pivot index (dims br+1..m)
+        int rp, rrp, snew, n2, up = 0;
+        if (lean) {
+            const int *hq = in ? hh : &gs.first;                      // no message: two ints that are there
+            const int u_in = MSG ? hq[0] : upd[br];
+            rp = r[p]; rrp = rr[p]; snew = (MSG ? hq[1] : r[br]) - 1; n2 = P.n[br]; up = upd[p];
+            asm volatile("" ::: "memory");                            // the requests stay in front of the decisions
+            if (!in || !u_in || k >= n2) return;
+        } else {
+            if (!in) return;
+            if (!(MSG ? hh[0] : upd[br]) || k >= P.n[br]) return;
+            rp = r[p]; rrp = rr[p]; snew = (MSG ? hh[1] : r[br]) - 1; n2 = P.n[br];
+        }
+        const double *msg = (const double *)(in + P.IOFF);            // (rr(p), n(p+1))
         double *A = core_ptr(P, P.arg, g, br, first), *W = core_ptr(P, P.row, g, br, first);
         double a = 0.0;
         if (tid < rrp) a = msg[tid + (size_t)rrp * k];
-        if (upd[p]) {                                                // corner arg(p+1)(r(p), k, r(p+1)), :925-937
-            for (int x = tid; x < P.npar; x += TTX_BLK) par[x] = P.par[x];
+        if (!lean) up = upd[p];
+        if (up) {                                                    // corner arg(p+1)(r(p), k, r(p+1)), :925-937
             const int *vp = vip_ptr(P, g, p, first) + 4 * (rp - 1);
             const short *Lt = L_ptr(P, g, p - 1, first), *Rt = R_ptr(P, g, br, first);
             auto dimv = [&](int s) -> short { return (s < p) ? Lt[(size_t)(s - 1) * P.RM + (vp[0] - 1)] : (s == p) ? (short)vp[1] : (s == p + 1) ? (short)(k + 1) : MSG ? (short)ix[s - p - 2] : Rt[(size_t)(s - p - 2) * P.RM + snew]; };
-            for (int x = tid; x < VSr; x += TTX_BLK) { rowA[x] = (x < p - 1) ? dimv(x + 1) : (short)1; rowB[x] = (x < m - p) ? dimv(p + 1 + x) : (short)1; }
+            if (cval) {
+                for (int x = tid; x < VSr; x += TTX_BLK) {
+                    const int ia = (x < p - 1) ? dimv(x + 1) : 0, ib = (x < m - p) ? dimv(p + 1 + x) : 0;
+                    cAn[x] = ia ? gnodes[ia] : 0.0; cAw[x] = ia ? gweights[ia] : 0.0; cBn[x] = ib ? gnodes[ib] : 0.0; cBw[x] = ib ? gweights[ib] : 0.0;
+                }
+            } else {
+                for (int x = tid; x < P.npar; x += TTX_BLK) par[x] = P.par[x];
+                for (int x = tid; x < VSr; x += TTX_BLK) { rowA[x] = (x < p - 1) ? dimv(x + 1) : (short)1; rowB[x] = (x < m - p) ? dimv(p + 1 + x) : (short)1; }
+            }
             __syncthreads();
             if (dewave || mvwave) {
                 if (tid < 64) {
@@ -196,7 +228,8 @@ __device__ __forceinline__ void exch_boundary_block(const DevProb &P, int bx, in
             }
             if (tid == rrp) {
                 Src3 sx{rowA, p - 1, (int)vp[1], rowB};
-                a = (dewave || mvwave) ? s_corner : eval_src3<FUN, true>(P, par, sx, (long)g * P.HS + k);
+                if (cval) a = f_ising_c3v(m, p - 1, cAn, cAw, gnodes[vp[1]], gweights[vp[1]], cBn, cBw);
+                else a = (dewave || mvwave) ? s_corner : eval_src3<FUN, true>(P, par, sx, (long)g * P.HS + k);
                 if (!HOST_PASS1(FUN, P)) {
                     atomic_max_pos(amax_to, fabs(a));
                     if (!MSG && k == 0) atomicAdd((unsigned long long *)&gs.neval, (unsigned long long)n2);   // :936
@@ -223,20 +256,38 @@ __device__ __forceinline__ void exch_boundary_block(const DevProb &P, int bx, in
         if (tid < rp) W[k + (size_t)P.NM * snew + P.SW * tid] = xf;
     } else {
         const int j = bx - P.NM, p = first, bl = first - 1;
-        if (!P.inL[g]) return;
-        const int *hh = (const int *)P.inL[g], *ix = hh + XH;         // ... dims 1..bl
-        if (!(MSG ? hh[0] : upd[bl]) || j >= P.n[p]) return;
-        const int rp = r[p], rrp = rr[p], inew = (MSG ? hh[1] : r[bl]) - 1, n1 = P.n[p];
-        const double *msg = (const double *)(P.inL[g] + P.IOFF);      // (n(p), rr(p))
+        const char *in = lean ? in_l : P.inL[g];
+        const int *hh = (const int *)in, *ix = hh + XH;               // ... dims 1..bl
+        int rp, rrp, inew, n1, up = 0;
+        if (lean) {
+            const int *hq = in ? hh : &gs.first;
+            const int u_in = MSG ? hq[0] : upd[bl];
+            rp = r[p]; rrp = rr[p]; inew = (MSG ? hq[1] : r[bl]) - 1; n1 = P.n[p]; up = upd[p];
+            asm volatile("" ::: "memory");
+            if (!in || !u_in || j >= n1) return;
+        } else {
+            if (!in) return;
+            if (!(MSG ? hh[0] : upd[bl]) || j >= P.n[p]) return;
+            rp = r[p]; rrp = rr[p]; inew = (MSG ? hh[1] : r[bl]) - 1; n1 = P.n[p];
+        }
+        const double *msg = (const double *)(in + P.IOFF);            // (n(p), rr(p))
         double *A = core_ptr(P, P.arg, g, p, first), *C = core_ptr(P, P.col, g, p, first);
         double y = 0.0;
         if (tid < rrp) y = msg[j + (size_t)n1 * tid];
-        if (upd[p]) {                                                // corner arg(p)(r(p-1), j, r(p)), dmrggmp.f90:608-616
-            for (int x = tid; x < P.npar; x += TTX_BLK) par[x] = P.par[x];
+        if (!lean) up = upd[p];
+        if (up) {                                                    // corner arg(p)(r(p-1), j, r(p)), dmrggmp.f90:608-616
             const int *vp = vip_ptr(P, g, p, first) + 4 * (rp - 1);
             const short *Lt = L_ptr(P, g, bl, first), *Rt = R_ptr(P, g, p + 1, first);
             auto dimv = [&](int s) -> short { return (s < p) ? (MSG ? (short)ix[s - 1] : Lt[(size_t)(s - 1) * P.RM + inew]) : (s == p) ? (short)(j + 1) : (s == p + 1) ? (short)vp[2] : Rt[(size_t)(s - p - 2) * P.RM + (vp[3] - 1)]; };
-            for (int x = tid; x < VSr; x += TTX_BLK) { rowA[x] = (x < p - 1) ? dimv(x + 1) : (short)1; rowB[x] = (x < m - p) ? dimv(p + 1 + x) : (short)1; }
+            if (cval) {
+                for (int x = tid; x < VSr; x += TTX_BLK) {
+                    const int ia = (x < p - 1) ? dimv(x + 1) : 0, ib = (x < m - p) ? dimv(p + 1 + x) : 0;
+                    cAn[x] = ia ? gnodes[ia] : 0.0; cAw[x] = ia ? gweights[ia] : 0.0; cBn[x] = ib ? gnodes[ib] : 0.0; cBw[x] = ib ? gweights[ib] : 0.0;
+                }
+            } else {
+                for (int x = tid; x < P.npar; x += TTX_BLK) par[x] = P.par[x];
+                for (int x = tid; x < VSr; x += TTX_BLK) { rowA[x] = (x < p - 1) ? dimv(x + 1) : (short)1; rowB[x] = (x < m - p) ? dimv(p + 1 + x) : (short)1; }
+            }
             __syncthreads();
             if (dewave || mvwave) {
                 if (tid < 64) {
@@ -247,7 +298,8 @@ __device__ __forceinline__ void exch_boundary_block(const DevProb &P, int bx, in
             }
             if (tid == rrp) {
                 Src3 sx{rowA, p - 1, j + 1, rowB};
-                y = (dewave || mvwave) ? s_corner : eval_src3<FUN, true>(P, par, sx, (long)g * P.HS + P.NM + j);
+                if (cval) y = f_ising_c3v(m, p - 1, cAn, cAw, gnodes[j + 1], gweights[j + 1], cBn, cBw);
+                else y = (dewave || mvwave) ? s_corner : eval_src3<FUN, true>(P, par, sx, (long)g * P.HS + P.NM + j);
                 if (!HOST_PASS1(FUN, P)) {
                     atomic_max_pos(amax_to, fabs(y));
                     if (!MSG && j == 0) atomicAdd((unsigned long long *)&gs.neval, (unsigned long long)n1);
@@ -274,20 +326,20 @@ __device__ __forceinline__ void exch_boundary_block(const DevProb &P, int bx, in
     }
 }
 template <int FUN>
-__global__ __launch_bounds__(TTX_BLK) void k_exch_boundary(DevProb P)
+__global__ __launch_bounds__(TTX_BLK) void k_exch_boundary(DevProb P, int lean)
 {
     if (P.ctl[0]) return;
-    exch_boundary_block<FUN, false>(P, (int)blockIdx.x, (int)blockIdx.y, 0);
+    exch_boundary_block<FUN, false>(P, (int)blockIdx.x, (int)blockIdx.y, 0, lean);
 }
 // MAX / apply and the boundary blocks of sweep `it` in ONE launch (single process, device integrand): grid (2 NM + 1, G), blocks
 // x < 2 NM are the boundary blocks, block x = 2 NM is the group's apply block.  The blocks are independent: no block reads what
 // another one of the launch writes (exch_boundary_block), and nothing is counted, fenced or waited for.
 template <int FUN>
-__global__ __launch_bounds__(TTX_BLK) void k_exch_tail(DevProb P, int it)
+__global__ __launch_bounds__(TTX_BLK) void k_exch_tail(DevProb P, int it, int lean)
 {
     if (P.ctl[0]) return;
     const int g = blockIdx.y;
-    if ((int)blockIdx.x < 2 * P.NM) { exch_boundary_block<FUN, true>(P, (int)blockIdx.x, g, it & 1); return; }
+    if ((int)blockIdx.x < 2 * P.NM) { exch_boundary_block<FUN, true>(P, (int)blockIdx.x, g, it & 1, lean); return; }
     if (threadIdx.x == 0) {
         exch_max_group(P, g, 0);
         GroupState &gs = P.gs[g];

@@ -791,6 +791,16 @@ class TTCross:
         _check(L.ttx_cluster_entry(self._h, out))
         return {"powtab": bool(out[0] & 1), "word": bool(out[0] & 2), "lists": bool(out[0] & 4), "lists_taken": int(out[1]), "word_taken": int(out[2])}
 
+    def sweep_gap(self):
+        """The forms of the stretch between two sweeps in force (include/ttx.h: ttx_sweep_gap): 'tail_event' is 'kernel' or 'marker',
+        'tail_event_fallbacks' counts the refusals of the extended launch."""
+        L = load_library()
+        L.ttx_sweep_gap.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_int32)]
+        out = (ctypes.c_int32 * 4)()
+        _check(L.ttx_sweep_gap(self._h, out))
+        return {"tail_event": "kernel" if out[0] else "marker", "tail_event_fallbacks": int(out[1]), "tail_lean": bool(out[2]),
+                "cl_pack2": bool(out[3])}
+
     @property
     def det_fallbacks(self):
         """Runs repeated without the wave teams / relay of the Ising D/E half-step after a reported fault (include/ttx.h)."""
