@@ -512,7 +512,8 @@ int ttx_basis_last     (const ttx_engine *h, double *ms_table, double *ms_chain,
  * default 2^32), at least 256.  Argument checks and refusals are those of ttx_basis_batch.
  * ttx_basis_grad_last: of the last call on this engine, the milliseconds (HIP events) of the table, backward and forward launches,
  * flops = 6 npts sum r(k-1) n(k) r(k), the mode that ran (-1: none yet) and the points per chunk.  Any pointer may be NULL.
- * Open: second derivatives, gradients with respect to cores, a fused score entry for the samplers, ranks above 128.
+ * Open: second derivatives, a fused score entry for the samplers, ranks above 128.  The gradient with respect to the cores is
+ * ttx_basis_core_grad_batch, below.
  * Added without a new ttx_version: look the symbols up. */
 int ttx_basis_grad_batch    (ttx_engine *h, int64_t npts, const double *x /* [npts][d] */, const ttx_basis *basis /* [d] */, double *val, double *grad /* [npts][d] */, int32_t mode);
 int ttx_basis_grad_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, double *val_dev, double *grad_dev, int32_t mode);
@@ -520,6 +521,58 @@ int ttx_basis_grad_tab      (ttx_engine *h, int64_t npts, const double *phi, con
 int ttx_basis_grad_tab_dev  (ttx_engine *h, int64_t npts, const double *phi_dev, const double *dphi_dev, double *val_dev, double *grad_dev, int32_t mode);
 int ttx_basis_host_d        (const ttx_basis *b, int32_t n, int64_t npts, const double *x, int64_t ldx, double *dphi /* [npts][n] */);   /* no engine, no GPU */
 int ttx_basis_grad_last     (const ttx_engine *h, double *ms_table, double *ms_back, double *ms_fwd, double *flops, int32_t *mode_ran, int64_t *chunk_ran);
+
+/* Gradient of the same f with respect to the CORES at a batch of real points, on the device (ttcross_amd/csrc/ttx_basis_core_grad.h):
+ * what fitting or correcting the resident train from scattered data (x_p, y_p) needs, without a core leaving the device.  f is linear in
+ * every core; c[p] is the caller's weight, the derivative of their loss with respect to f(x_p) (e.g. f(x_p) - y_p for least squares).
+ * Definition (numpy restates it: tests/basis_core_grad_ref.py).  phi_i(p, :) is the table row of mode i and point p, U_i(a, j, k) is core
+ * i, r(i-1) x n(i) x r(i).  Multiply and add are always separate.
+ *   Backward, i = d .. 1, from X_d = (1):  t_j(a) = sum_k U_i(a, j, k) X_i(k),   summed from 0.0 over ascending k;
+ *                                          X_(i-1)(a) = sum_j phi_j t_j(a),     summed from 0.0 over ascending j;
+ *                                          val = X_0(1): the operation sequence of ttx_basis_batch, every X_i kept.
+ *   Forward, i = 1 .. d, from L_1 = (1):   s_j(k) = sum_a L_i(a) U_i(a, j, k),   summed from 0.0 over ascending a;
+ *                                          L_(i+1)(k) = sum_j phi_j s_j(k),     summed from 0.0 over ascending j: the forward step of
+ *                                          ttx_basis_grad_batch; L_(d+1) is not formed.
+ *   Gradient:  G_i(a, j, k) = G0_i(a, j, k) + sum_p ((c[p] * L_i(p, a)) * (phi_(i, j)(p) * X_i(p, k))),  the terms added one by one over
+ *              ascending p onto G0, the three multiplies bracketed as written.  G0 is 0.0 (accumulate == 0) or the contents of g on
+ *              entry (accumulate == 1).
+ * For any block E of core i's shape, sum_p c[p] f_(U_i <- E)(x_p) = <G_i, E>: the gradient of sum_p c[p] f(x_p), free of differences.
+ * g holds the blocks in the layout of ttx_from_tt's cores: compact column-major, (a, j, k) at a + r(i-1) (j + n(i) k), mode 1 first,
+ * sum_i ttx_core_size(h, i) doubles, all offsets 64-bit.  val[npts] may be NULL.
+ *   mode : TTX_EVAL_EXACT  val and every G_i bit-identical to the numpy restatement: independent of the chunk, of the grid and of
+ *                          repetition (each chunk continues from the buffer)
+ *          TTX_EVAL_MFMA   both chains and the accumulation on the fp64 matrix cores.  val is bit-identical to ttx_basis_batch in MFMA
+ *                          mode; G equals EXACT to rounding (tests/basis_core_grad_ref.py derives the allowance), in a fixed summation
+ *                          order: no floating-point atomics, a call repeats bit for bit.  The order -- the chunks, and inside a chunk
+ *                          segments of points whose partial blocks are added in ascending order -- depends on the train's shape and on
+ *                          the points per chunk (TTX_BASIS_CHUNK, TTX_BASIS_GRAD_STORE), so G MAY DEPEND ON THE POINTS PER CHUNK, and on
+ *                          nothing else the caller does not control: not on the device, and on npts only where npts is the points per chunk
+ *          TTX_EVAL_AUTO   by the flops of the call, 6 npts sum r(k-1) n(k) r(k) (ttx_basis_core_grad_last tells what ran); the
+ *                          break-even is provisional, not measured
+ * Arguments, refusals and engine kinds are those of ttx_basis_batch (ranks up to 128, boundary ranks 1, no multi-process engine,
+ * TTX_ESTATE without a train); in addition a NULL c or g with npts > 0 and an accumulate other than 0 or 1 are refused.  A refused call
+ * leaves g untouched.  npts == 0 with accumulate == 0 writes 0.0 to all of g, with accumulate == 1 it touches nothing; neither launches
+ * a chain.  A point with a NaN table entry or a NaN c[p] makes every entry of G it reaches NaN; 0 * NaN is NaN, so a point masked
+ * with c[p] = 0 still needs finite coordinates (finite tables).
+ * The backward chain keeps X_1 .. X_(d-1) of a chunk at the row stride of the value chain's kernels, S = (d - 1) ldx doubles per point
+ * (ldx: the largest rank rounded up to four); the chunk rule is ttx_basis_grad_batch's with this S.
+ * ttx_basis_core_grad_last: of the last call on this engine, the milliseconds (HIP events) of the table, backward, forward and
+ * accumulation launches, the flops, the mode that ran (-1: none yet) and the points per chunk.  Any pointer may be NULL.
+ * ttx_cores_axpy: U_i <- U_i + alpha[i-1] * G_i for all cores in one launch, multiply and add separate, g in the layout above.
+ * alpha[i-1] == 0.0 skips core i without reading G_i: its bits stay even where G_i holds NaN.  The engine keeps nothing between calls
+ * that is derived from the cores -- every operation (evaluation, norm, quadrature, sampling tables, Gram matrices) rebuilds what it
+ * needs from the cores it finds, which is why ttx_ort and ttx_svd drop nothing either -- so nothing stale survives an update.  Refusals
+ * as above, and a NULL alpha or g.
+ * Open: the gradient of the normaliser Z of the squared density (maximum likelihood for ttx_sample_sq_real needs it as well), a
+ * Gauss-Newton or ALS solver, second derivatives, ranks above 128, the Fortran layer.
+ * Added without a new ttx_version: look the symbols up. */
+int ttx_basis_core_grad_batch    (ttx_engine *h, int64_t npts, const double *x /* [npts][d] */, const ttx_basis *basis /* [d] */, const double *c /* [npts] */, double *val, double *g, int32_t accumulate, int32_t mode);
+int ttx_basis_core_grad_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, const double *c_dev, double *val_dev, double *g_dev, int32_t accumulate, int32_t mode);
+int ttx_basis_core_grad_tab      (ttx_engine *h, int64_t npts, const double *phi /* [npts][sum n(k)] */, const double *c, double *val, double *g, int32_t accumulate, int32_t mode);
+int ttx_basis_core_grad_tab_dev  (ttx_engine *h, int64_t npts, const double *phi_dev, const double *c_dev, double *val_dev, double *g_dev, int32_t accumulate, int32_t mode);
+int ttx_basis_core_grad_last     (const ttx_engine *h, double *ms_table, double *ms_back, double *ms_fwd, double *ms_acc, double *flops, int32_t *mode_ran, int64_t *chunk_ran);
+int ttx_cores_axpy    (ttx_engine *h, const double *alpha /* [d], host */, const double *g);
+int ttx_cores_axpy_dev(ttx_engine *h, const double *alpha /* [d], host */, const double *g_dev);
 
 /* Samples drawn from the resident train by sequential conditional sampling, on the device (ttcross_amd/csrc/ttx_sample.h).
  * Modes are 1-based, G_k is core k, r_0 = r_d = 1.

@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void k_bg_exact_back(EvTrain T, int i, long lo
 }
 
 // forward step of mode i.  dynamic LDS per wave: l[ldx], D_i's row [ldx].  Lin = null: mode 1, l = (1).  grad_i goes to
-// grad[i + d p]; last (mode d): no new state.  Lane k (and k + 64) owns l_new(k) and walks a ascending, contiguous in memory.
+// grad[i + d p] (D = null: no grad_i is formed, the advance alone: ttx_basis_core_grad.h); last (mode d): no new state.  Lane k (and k + 64) owns l_new(k) and walks a ascending, contiguous in memory.
 __global__ __launch_bounds__(256) void k_bg_exact_fwd(EvTrain T, int i, long long c, const double *phi, size_t ldphi, const double *Lin, double *Lout,
                                                       const double *D, double *grad, int d, int last)
 {
@@ -104,9 +104,9 @@ __global__ __launch_bounds__(256) void k_bg_exact_fwd(EvTrain T, int i, long lon
         __builtin_amdgcn_wave_barrier();
         if (Lin) { for (int t = lane; t < q0; t += 64) l[t] = Lin[(size_t)p * T.ldx + t]; }
         else if (lane == 0) l[0] = 1.0;
-        for (int t = lane; t < q0; t += 64) dd[t] = D[(size_t)p * q0 + t];
+        if (D) for (int t = lane; t < q0; t += 64) dd[t] = D[(size_t)p * q0 + t];
         __builtin_amdgcn_wave_barrier();
-        if (lane == 0) {
+        if (D && lane == 0) {
             double g = 0.0;
             for (int a = 0; a < q0; a++) g = g + l[a] * dd[a];
             grad[(size_t)p * d + i] = g;
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void k_bg_exact_fwd(EvTrain T, int i, long lon
 //   FWD = false (backward step): rows a < r0, contraction k < r1; the panel image is (a, kc) at a + lda kc as in k_bs_gemm.  Two
 //         operands per MFMA pair, b = phi_j x_k and b' = dphi_j x_k, two accumulator sets (z and e) from one a fragment: CT = bg_ct(MR).
 //   FWD = true (forward step): rows k < r1, contraction a < r0; the panel image is (k, ac) at TTX_BG_LDT k + ac, read from global
-//         memory along a.  One operand b = phi_j l(a), one accumulator set: CT = bs_ct(MR).  Before the GEMM the kernel forms grad_i.
+//         memory along a.  One operand b = phi_j l(a), one accumulator set: CT = bs_ct(MR).  Before the GEMM the kernel forms grad_i (not where D is null).
 // The figures per MR (registers, LDS, occupancy; no scratch at any MR) are in profiles/basis_grad_mi355x.txt.
 // Where both accumulator sets fit into 256 registers the allocator is held to two waves per SIMD (bg_waves, ttx_op_plan.h).
 template <int MR, bool FWD>
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(bg_waves(MR
     if constexpr (FWD) {
         // grad_i = l . D_i: every lane group sums its own a = 4 kk + kq ascending, the four groups are paired (0 + 1) + (2 + 3)
 #pragma unroll
-        for (int ct = 0; ct < CT; ct++) {
+        for (int ct = 0; D && ct < CT; ct++) {
             const double *Dp = D + (size_t)(pt[ct] >= 0 ? pt[ct] : 0) * q0;
             double g = 0.0;
 #pragma unroll

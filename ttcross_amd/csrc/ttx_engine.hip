@@ -52,6 +52,7 @@
 #include "ttx_modeapply.h"
 #include "ttx_basis.h"
 #include "ttx_basis_grad.h"
+#include "ttx_basis_core_grad.h"
 #include "ttx_algebra.h"
 #include "ttx_roundsum.h"
 #include "ttx_sample.h"
@@ -143,6 +144,7 @@ enum {
     SC_QH, SC_QF, SC_QS, SC_QX,         // ttx_sample_sq: the tables H_k, the factors F_k (then the exponent and the d defensive terms), a mode's sheet (two for ttx_sample_sq_real), the states (two buffers, logq, flags)
     SC_BTAB,                            // ttx_basis_batch: the table of one mode for one chunk, chunk x max n (its states go to SC_XA / SC_XB, its nodes to SC_META)
     SC_GST,                             // ttx_basis_grad_batch: the state store, the rows D_i of all modes of a chunk (its tables go to SC_BTAB, its states to SC_XA / SC_XB)
+    SC_CGG, SC_CGP,                     // ttx_basis_core_grad_batch: the packed gradient of a host caller (also ttx_cores_axpy's), the partial blocks of a core's segments (its states X_i go to SC_GST, L to SC_XA / SC_XB)
     SC_NBUF
 };
 struct EvBuf { void *p = nullptr; size_t bytes = 0; };
@@ -199,6 +201,8 @@ struct RsLast {                                                                 
 };
 struct BsLast { double ms[2] = {0.0, 0.0}, flops = 0.0; int mode = -1; };      // ttx_basis_batch / ttx_basis_tab: table launches, chain launches
 struct BgLast { double ms[3] = {0.0, 0.0, 0.0}, flops = 0.0; int mode = -1; int64_t chunk = 0; };     // ttx_basis_grad_batch / ttx_basis_grad_tab: table, backward, forward launches
+
+struct CgLast { double ms[4] = {0.0, 0.0, 0.0, 0.0}, flops = 0.0; int mode = -1; int64_t chunk = 0; };     // ttx_basis_core_grad_batch / _tab: table, backward, forward, accumulation launches
 
 struct DevFun;                          // a loaded device integrand (TTX_FUN_DEVICE), defined with slot_eval
 struct TrainFun;                        // the operands and the combiner of TTX_FUN_TRAINS, defined with slot_eval
@@ -314,6 +318,7 @@ struct ttx_engine {
     RsLast rs;
     BsLast bs;
     BgLast bg;
+    CgLast cg;
     std::vector<hipEvent_t> op_ev;                      // OpMarks' events: ttx_lincomb_round, the squared samplers, the basis evaluations
 };
 
@@ -4135,6 +4140,204 @@ extern "C" int ttx_basis_grad_last(const ttx_engine *h, double *ms_table, double
     if (chunk_ran) *chunk_ran = h->bg.chunk;
     return TTX_OK;
 }
+
+// ---- gradient with respect to the cores of the train in a function basis (ttx_basis_core_grad.h) ---------------------------------
+enum { CGM_TABLE, CGM_BACK, CGM_FWD, CGM_ACC };     // OpMarks phases of a call, CgLast::ms takes the sums
+// what ttx_basis_batch refuses of the train itself, asked before anything is touched
+static int cg_check_train(ttx_engine *h, const char *who)
+{
+    const int rmax = *std::max_element(h->rfinal.begin(), h->rfinal.begin() + h->d + 1);
+    if (rmax > 128) return fail(TTX_EINVAL, "%s: ranks up to 128 only (got %d)", who, rmax);
+    if (h->rfinal[0] != 1 || h->rfinal[h->d] != 1) return fail(TTX_EINVAL, "%s: boundary ranks are not 1", who);
+    return TTX_OK;
+}
+// in: the coordinates or the caller's phi; cw: the weights c; val may be null; g: the packed gradient, on the host unless dev
+static int cg_run(ttx_engine *h, const char *who, BsSrc src, int64_t npts, const double *in, const ttx_basis *basis, const double *cw, double *val, double *g,
+                  int32_t accumulate, int32_t mode)
+{
+    const bool tab = src == BS_TAB_HOST || src == BS_TAB_DEV, dev = src == BS_X_DEV || src == BS_TAB_DEV;
+    int rc = tt_prepare(h, who);
+    if (rc) return rc;
+    if (npts < 0 || (npts > 0 && (!in || !cw || !g || (!tab && !basis)))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
+    if (!op_mode_known(mode)) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    if (accumulate != 0 && accumulate != 1) return fail(TTX_EINVAL, "%s: accumulate is 0 or 1 (got %d)", who, accumulate);
+    const int d = h->d;
+    if (!tab && basis) for (int k = 1; k <= d; k++) if ((rc = bs_check_one(who, k, basis[k - 1], h->n1[k]))) return rc;
+    const CgPlan pl = cg_plan(d, h->n1.data() + 1, h->rfinal.data(), dev_ncu(h), src, !dev, npts, mode, env_chunk("TTX_BASIS_CHUNK", op_chunk_default(h->RM)), env_grad_store());
+    if (pl.refusal == BS_RANK) return fail(TTX_EINVAL, "%s: ranks up to 128 only (got %d)", who, pl.rmax);
+    if (pl.refusal == BS_BOUNDARY) return fail(TTX_EINVAL, "%s: boundary ranks are not 1", who);
+    h->cg = CgLast();
+    h->cg.flops = pl.flops; h->cg.mode = pl.eff; h->cg.chunk = (int64_t)pl.chunk;
+    if (npts == 0) {                                                            // no chain: accumulate == 0 writes 0.0 to all of g, accumulate == 1 touches nothing
+        if (accumulate || !g) return TTX_OK;
+        if (!dev) { std::fill(g, g + pl.gsize, 0.0); return TTX_OK; }
+        HIPCHECK(hipMemsetAsync(g, 0, sizeof(double) * pl.gsize, h->stream));
+        HIPCHECK(hipStreamSynchronize(h->stream));
+        return TTX_OK;
+    }
+    EvTrain T;
+    if ((rc = ev_train(h, &T))) return rc;
+    // the nodes of the LINEAR modes, one device block
+    std::vector<BsMode> M(d);
+    if (!tab) {
+        OpMeta meta(h->meta_host);
+        std::vector<size_t> o_nodes(d, 0);
+        for (int k = 0; k < d; k++)
+            if (basis[k].kind == TTX_BASIS_LINEAR) o_nodes[k] = meta.put(std::vector<double>(basis[k].nodes, basis[k].nodes + h->n1[k + 1]));
+        char *dm = nullptr;
+        if (!meta.host.empty() && (rc = meta.upload(h, SC_META, &dm))) return rc;
+        for (int k = 0; k < d; k++) {
+            const ttx_basis &b = basis[k];
+            const bool cosk = b.kind == TTX_BASIS_COS;
+            M[k] = BsMode{b.kind, b.flags, h->n1[k + 1], cosk ? b.a : 0.0, cosk ? ttx_basis_cos_w(b.a, b.b) : 0.0, cosk ? nullptr : (const double *)(dm + o_nodes[k])};
+        }
+    }
+    if ((rc = buf_reserve(h, {{SC_XA, pl.b_xa}, {SC_XB, pl.b_xb}, {SC_BTAB, pl.b_btab}, {SC_X, pl.b_x}, {SC_OUT, pl.b_out}, {SC_GST, pl.b_gst}, {SC_CGG, pl.b_cgg}, {SC_CGP, pl.b_part}}))) return rc;
+    double *btab = buf<double>(h, SC_BTAB), *sin_ = buf<double>(h, SC_X), *sout = buf<double>(h, SC_OUT);
+    double *gst = buf<double>(h, SC_GST), *XA = buf<double>(h, SC_XA), *XB = buf<double>(h, SC_XB), *part = buf<double>(h, SC_CGP);
+    double *G = dev ? g : buf<double>(h, SC_CGG);
+    // G0: the caller's block, or 0.0; every chunk then continues from the buffer
+    if (!accumulate) HIPCHECK(hipMemsetAsync(G, 0, sizeof(double) * pl.gsize, h->stream));
+    else if (!dev) HIPCHECK(hipMemcpyAsync(G, g, sizeof(double) * pl.gsize, hipMemcpyHostToDevice, h->stream));
+    OpMarks marks(h->op_ev);
+    for (int64_t o = 0; o < npts; o += (int64_t)pl.chunk) {
+        const int c = (int)std::min<int64_t>((int64_t)pl.chunk, npts - o);
+        const double *cin = in + (size_t)o * pl.row, *cc = cw + o;
+        double *cval = val ? val + o : XA;                                      // nobody's val: mode 1's launch still writes one number per point, into a state buffer the forward pass overwrites
+        if (!dev) {
+            HIPCHECK(hipMemcpyAsync(sin_, cin, sizeof(double) * (size_t)c * pl.row, hipMemcpyHostToDevice, h->stream));
+            HIPCHECK(hipMemcpyAsync(sin_ + pl.chunk * pl.row, cc, sizeof(double) * (size_t)c, hipMemcpyHostToDevice, h->stream));
+            cin = sin_; cc = sin_ + pl.chunk * pl.row;
+            if (val) cval = sout;
+        }
+        if ((rc = marks.mark(h->stream, OpMarks::DISCARD))) return rc;
+        const double *ph = nullptr;
+        size_t ld = 0;
+        auto tables = [&](int i) {
+            ph = cin + pl.off[i]; ld = pl.sumn;
+            if (tab) return TTX_OK;
+            hipLaunchKernelGGL(k_bg_table, g1((size_t)c * M[i].n), dim3(256), 0, h->stream, M[i], (long long)c, cin + i, d, btab, (double *)nullptr);
+            ph = btab; ld = (size_t)M[i].n;
+            return marks.mark(h->stream, CGM_TABLE);
+        };
+        auto Xof = [&](int bond) { return gst + pl.soff(bond) * pl.chunk; };     // X_bond, bond = 1 .. d-1
+        for (int i = d - 1; i >= 0; i--) {                                      // backward: the value chain, every state into the store
+            if ((rc = tables(i))) return rc;
+            const double *Xin = i == d - 1 ? nullptr : Xof(i + 1);
+            double *Z = i == 0 ? XB : Xof(i), *o1 = i == 0 ? cval : nullptr;    // mode 1 writes no state
+            if (pl.eff == TTX_EVAL_EXACT)
+                hipLaunchKernelGGL(k_bs_exact, dim3(pl.g_exact(c)), dim3(256), pl.lds_back, h->stream, T, i, (long long)c, ph, ld, Xin, Z, o1);
+            else
+                with_tier<true>(pl.back[i].tier, [&](auto mr) {
+                    hipLaunchKernelGGL(k_bs_gemm<decltype(mr)::value>, dim3(pl.g_back(i, c)), dim3(256), pl.back[i].lds, h->stream, T, i, c, ph, ld, Xin, Z, o1);
+                    return 0;
+                });
+            if ((rc = marks.mark(h->stream, CGM_BACK))) return rc;
+        }
+        double *X = XA, *Z = XB;
+        for (int i = 0; i < d; i++) {                                           // forward: G_i from L_i and X_i, then L through mode i
+            if ((rc = tables(i))) return rc;
+            const double *Lin = i == 0 ? nullptr : X, *Xi = i == d - 1 ? nullptr : Xof(i + 1);
+            const int r0 = h->rfinal[i], n = h->n1[i + 1], r1 = h->rfinal[i + 1];
+            const CgStep &st = pl.step[i];
+            double *Gi = G + st.goff;
+            if (pl.eff == TTX_EVAL_EXACT)
+                hipLaunchKernelGGL(k_cg_exact, dim3((unsigned)((st.size + 255) / 256)), dim3(256), 0, h->stream, r0, n, r1, (long long)c, cc, ph, ld, Lin, Xi, pl.ldx, Gi);
+            else {
+                const int ns = pl.nsplit(i, c);
+                with_tier<true>(st.tier, [&](auto mr) {
+                    hipLaunchKernelGGL(k_cg_gemm<decltype(mr)::value>, dim3(st.ngrp, ns), dim3(256), st.lds, h->stream, r0, n, r1, c, st.seg, cc, ph, ld, Lin, Xi, pl.ldx, part);
+                    return 0;
+                });
+                hipLaunchKernelGGL(k_cg_reduce, g1(st.size), dim3(256), 0, h->stream, (long long)st.size, ns, part, Gi);
+            }
+            if ((rc = marks.mark(h->stream, CGM_ACC))) return rc;
+            if (i == d - 1) break;                                              // L_(d+1) is not formed
+            if (pl.eff == TTX_EVAL_EXACT)
+                hipLaunchKernelGGL(k_bg_exact_fwd, dim3(pl.g_exact(c)), dim3(256), pl.lds_fwd, h->stream, T, i, (long long)c, ph, ld, Lin, Z, (const double *)nullptr, (double *)nullptr, d, 0);
+            else
+                with_tier<true>(pl.fwd[i].tier, [&](auto mr) {
+                    hipLaunchKernelGGL((k_bg_gemm<decltype(mr)::value, true>), dim3(pl.g_fwd(i, c)), dim3(256), pl.fwd[i].lds_fwd, h->stream,
+                                       T, i, c, ph, (const double *)nullptr, ld, Lin, Z, (double *)nullptr, (double *)nullptr, (double *)nullptr, d, 0);
+                    return 0;
+                });
+            if ((rc = marks.mark(h->stream, CGM_FWD))) return rc;
+            std::swap(X, Z);
+        }
+        if (!dev && val) HIPCHECK(hipMemcpyAsync(val + o, sout, sizeof(double) * (size_t)c, hipMemcpyDeviceToHost, h->stream));
+        if (!dev || marks.phase.size() > 4096) {                                // the staging blocks are reused by the next chunk; the event chain stays short
+            HIPCHECK(hipStreamSynchronize(h->stream));
+            if ((rc = marks.sum(h->cg.ms))) return rc;
+        }
+    }
+    if (!dev) HIPCHECK(hipMemcpyAsync(g, G, sizeof(double) * pl.gsize, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    if ((rc = marks.sum(h->cg.ms))) return rc;
+    HIPCHECK(hipGetLastError());
+    return TTX_OK;
+}
+extern "C" int ttx_basis_core_grad_batch(ttx_engine *h, int64_t npts, const double *x, const ttx_basis *basis, const double *c, double *val, double *g, int32_t accumulate, int32_t mode)
+{
+    return cg_run(h, "ttx_basis_core_grad_batch", BS_X_HOST, npts, x, basis, c, val, g, accumulate, mode);
+}
+extern "C" int ttx_basis_core_grad_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, const double *c_dev, double *val_dev, double *g_dev, int32_t accumulate, int32_t mode)
+{
+    return cg_run(h, "ttx_basis_core_grad_batch_dev", BS_X_DEV, npts, x_dev, basis, c_dev, val_dev, g_dev, accumulate, mode);
+}
+extern "C" int ttx_basis_core_grad_tab(ttx_engine *h, int64_t npts, const double *phi, const double *c, double *val, double *g, int32_t accumulate, int32_t mode)
+{
+    return cg_run(h, "ttx_basis_core_grad_tab", BS_TAB_HOST, npts, phi, nullptr, c, val, g, accumulate, mode);
+}
+extern "C" int ttx_basis_core_grad_tab_dev(ttx_engine *h, int64_t npts, const double *phi_dev, const double *c_dev, double *val_dev, double *g_dev, int32_t accumulate, int32_t mode)
+{
+    return cg_run(h, "ttx_basis_core_grad_tab_dev", BS_TAB_DEV, npts, phi_dev, nullptr, c_dev, val_dev, g_dev, accumulate, mode);
+}
+extern "C" int ttx_basis_core_grad_last(const ttx_engine *h, double *ms_table, double *ms_back, double *ms_fwd, double *ms_acc, double *flops, int32_t *mode_ran, int64_t *chunk_ran)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_basis_core_grad_last: null engine");
+    if (ms_table) *ms_table = h->cg.ms[CGM_TABLE];
+    if (ms_back) *ms_back = h->cg.ms[CGM_BACK];
+    if (ms_fwd) *ms_fwd = h->cg.ms[CGM_FWD];
+    if (ms_acc) *ms_acc = h->cg.ms[CGM_ACC];
+    if (flops) *flops = h->cg.flops;
+    if (mode_ran) *mode_ran = h->cg.mode;
+    if (chunk_ran) *chunk_ran = h->cg.chunk;
+    return TTX_OK;
+}
+// U_i <- U_i + alpha[i - 1] G_i for every core in one launch; g: the packed blocks, on the host unless dev.  The engine keeps nothing
+// that is derived from the cores between two calls (every operation rebuilds its tables from the cores it finds), so nothing is dropped
+static int ca_run(ttx_engine *h, const char *who, const double *alpha, const double *g, bool dev)
+{
+    int rc = tt_prepare(h, who);
+    if (rc) return rc;
+    if (!alpha || !g) return fail(TTX_EINVAL, "%s: null argument", who);
+    if ((rc = cg_check_train(h, who))) return rc;
+    const int d = h->d;
+    std::vector<CaCore> cs(d);
+    long long tot = 0;
+    for (int k = 1; k <= d; k++) {
+        cs[k - 1] = CaCore{core_dev(h, k), tot, tot, h->rfinal[k - 1], h->n1[k], h->rfinal[k], alpha[k - 1]};
+        tot += (long long)core_elems(h, k);
+    }
+    OpMeta meta(h->meta_host);
+    const size_t o_cs = meta.put(cs);
+    char *dm = nullptr;
+    if ((rc = meta.upload(h, SC_META, &dm))) return rc;
+    const double *G = g;
+    if (!dev) {
+        if ((rc = buf_reserve(h, SC_CGG, sizeof(double) * (size_t)tot))) return rc;
+        double *sg = buf<double>(h, SC_CGG);
+        for (int k = 0; k < d; k++)                                             // a skipped core's block is not read, not even on the host
+            if (cs[k].alpha != 0.0) HIPCHECK(hipMemcpyAsync(sg + cs[k].goff, g + cs[k].goff, sizeof(double) * core_elems(h, k + 1), hipMemcpyHostToDevice, h->stream));
+        G = sg;
+    }
+    hipLaunchKernelGGL(k_cores_axpy, g1((size_t)tot), dim3(256), 0, h->stream, (const CaCore *)(dm + o_cs), d, tot, h->RM, h->P.SS, G);
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipGetLastError());
+    return TTX_OK;
+}
+extern "C" int ttx_cores_axpy(ttx_engine *h, const double *alpha, const double *g) { return ca_run(h, "ttx_cores_axpy", alpha, g, false); }
+extern "C" int ttx_cores_axpy_dev(ttx_engine *h, const double *alpha, const double *g_dev) { return ca_run(h, "ttx_cores_axpy_dev", alpha, g_dev, true); }
 
 // ---- the largest elements of the resident train (ttx_topk.h)--------------------------------------------------------------------
 namespace {

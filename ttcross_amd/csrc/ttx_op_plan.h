@@ -218,6 +218,96 @@ inline BgPlan bg_plan(int d, const int *n, const int *r, int ncu, BsSrc src, int
     return p;
 }
 
+// ---- ttx_basis_core_grad_batch, ttx_basis_core_grad_tab and their _dev forms (ttx_basis_core_grad.h) -----------------------------
+// break-even of TTX_EVAL_AUTO in flops per call (6 npts sum r0 n r1).  PROVISIONAL, NOT MEASURED: equal to TTX_BS_AUTO_FLOPS until the
+// break-even of the core-gradient call itself is measured (profiles/basis_core_grad_mi355x.txt says what was and what was not).
+#define TTX_CG_AUTO_FLOPS TTX_BS_AUTO_FLOPS
+#define TTX_CG_PB 16                // points of a staged block of k_cg_gemm: four MFMA steps of four points
+#define TTX_CG_WG 512               // workgroups a core's accumulation launch aims at (a constant, not the device's CU count: the
+                                    // summation order of MFMA mode must not depend on the device)
+#define TTX_CG_SEGMIN 256           // fewest points of a workgroup's segment of a chunk
+// column tiles of 16 per wave of k_cg_gemm<MR> (the accumulators are 8 MR CT registers, nothing else is held across the point loop)
+// and the waves per SIMD its register allocator is held to, from the compiler's resource report (profiles/basis_core_grad_mi355x.txt):
+// no tier has scratch
+TTX_OP_HD constexpr int cg_ct(int MR) { return MR <= 2 ? 4 : 2; }
+TTX_OP_HD constexpr int cg_waves(int MR) { return MR <= 8 ? 2 : 1; }
+// leading dimensions (doubles) of the staged rows: c L (= 16 mod 32, ev_lda), the table window of the workgroup's 64 CT columns
+// (= 16 mod 32: the two point rows a half-wave reads fall into different banks) and the state X (odd: a half-wave's two broadcasts differ)
+TTX_OP_HD constexpr int cg_lda(int MR) { return (16 * MR & 31) == 16 ? 16 * MR : 16 * MR + 16; }
+TTX_OP_HD constexpr int cg_ldw(int MR) { return 64 * cg_ct(MR) + 16; }
+TTX_OP_HD int cg_ldq(int q1) { return ((q1 + 3) & ~3) + 1; }
+inline size_t cg_gemm_lds(int MR, int q1) { return sizeof(double) * TTX_CG_PB * ((size_t)cg_lda(MR) + cg_ldw(MR) + cg_ldq(q1)); }
+
+// a 0-based mode's accumulation: k_cg_gemm<tier> on (ngrp, nsplit(c)) workgroups, 16 tier >= r0; seg points per workgroup
+struct CgStep { int tier = 1, ngrp = 1, seg = TTX_CG_SEGMIN; size_t lds = 0, size = 0, goff = 0; };
+struct CgPlan {
+    BsRefusal refusal = BS_OK;
+    int rmax = 1, eff = TTX_EVAL_EXACT, ldx = 4, ncu = 0;
+    std::vector<size_t> off;                // where a mode's rows start in a point's row of the caller's table
+    size_t sumn = 0, nmax = 1, S = 0, cap = 0, chunk = 0, row = 0;              // S: doubles per point of the state store; cap: the chunk before npts bounds it; chunk: the points per chunk
+    size_t gsize = 0;                       // doubles of the packed gradient
+    double flops = 0.0;
+    size_t b_xa = 0, b_xb = 0, b_btab = 0, b_x = 0, b_out = 0, b_gst = 0, b_cgg = 0, b_part = 0;     // bytes of SC_*; 0: the call does not use the slot
+    size_t lds_back = 0, lds_fwd = 0;       // k_bs_exact: per wave x; k_bg_exact_fwd: per wave l and a row it does not use here
+    std::vector<BsStep> back;               // k_bs_gemm<tier> of the backward chain (bs_plan's)
+    std::vector<BgStep> fwd;                // k_bg_gemm<tier, true> of the forward advance (bg_plan's)
+    std::vector<CgStep> step;
+    int g_exact(int c) const { return wave_grid(c, ncu); }
+    int g_back(int i, int c) const { return (c + back[i].tp - 1) / back[i].tp; }
+    int g_fwd(int i, int c) const { return (c + fwd[i].tp_fwd - 1) / fwd[i].tp_fwd; }
+    int nsplit(int i, int c) const { return (c + step[i].seg - 1) / step[i].seg; }
+    size_t soff(int i) const { return (size_t)(i - 1) * ldx; }                  // bond i = 1 .. d-1: X_i's block starts at soff(i) chunk doubles
+};
+// n[0 .. d-1], r[0 .. d]; chunk: TTX_BASIS_CHUNK or the default; store: TTX_BASIS_GRAD_STORE or the default, bytes; host_g: the
+// gradient is the caller's host array.  The segments depend on the shapes and on the points per chunk only, never on the device.
+inline CgPlan cg_plan(int d, const int *n, const int *r, int ncu, BsSrc src, bool host_g, int64_t npts, int mode, size_t chunk, size_t store)
+{
+    const bool tab = src == BS_TAB_HOST || src == BS_TAB_DEV, dev = src == BS_X_DEV || src == BS_TAB_DEV;
+    CgPlan p;
+    p.rmax = *std::max_element(r, r + d + 1); p.ncu = ncu;
+    if (p.rmax > 128) { p.refusal = BS_RANK; return p; }
+    if (r[0] != 1 || r[d] != 1) { p.refusal = BS_BOUNDARY; return p; }
+    double w = 0.0;
+    p.off.resize(d); p.back.resize(d); p.fwd.resize(d); p.step.resize(d);
+    p.ldx = op_ldx(d, r);
+    // the store holds X_1 .. X_(d-1) at the row stride of the value chain's kernels: the largest multiple of 256 points under the budget, at least 256
+    p.S = (size_t)(d - 1) * p.ldx;
+    const size_t fit = p.S ? std::max<size_t>(256, store / (sizeof(double) * p.S) / 256 * 256) : chunk;
+    p.cap = std::max<size_t>(1, std::min(chunk, fit));
+    for (int k = 0; k < d; k++) p.sumn += (size_t)n[k];
+    p.chunk = std::min<size_t>(p.cap, (size_t)std::max<int64_t>(npts, 0));
+    if (src == BS_TAB_HOST) p.chunk = std::min(p.chunk, std::max<size_t>(1, ((size_t)1 << 25) / p.sumn));     // the staged rows of the caller's table
+    p.sumn = 0;
+    for (int k = 0; k < d; k++) {
+        w += (double)r[k] * n[k] * r[k + 1];
+        p.off[k] = p.sumn; p.sumn += (size_t)n[k]; p.nmax = std::max(p.nmax, (size_t)n[k]);
+        const int tb = (std::max(r[k], r[k + 1]) + 15) / 16;
+        p.back[k].tier = tb; p.back[k].tp = 64 * bs_ct(tb); p.back[k].lds = bs_gemm_lds(r[k]);
+        p.fwd[k].tier = tb; p.fwd[k].tp_fwd = 64 * bs_ct(tb); p.fwd[k].lds_fwd = bg_fwd_lds(r[k + 1]);
+        CgStep &s = p.step[k];
+        s.tier = (r[k] + 15) / 16;
+        s.size = (size_t)r[k] * n[k] * r[k + 1]; s.goff = p.gsize; p.gsize += s.size;
+        const size_t ncol = (size_t)n[k] * r[k + 1], wcol = (size_t)64 * cg_ct(s.tier);
+        s.ngrp = (int)((ncol + wcol - 1) / wcol);
+        const size_t want = std::max<size_t>(1, (size_t)TTX_CG_WG / (size_t)s.ngrp);
+        s.seg = (int)std::max<size_t>(TTX_CG_SEGMIN, ((p.chunk + want - 1) / want + TTX_CG_PB - 1) / TTX_CG_PB * TTX_CG_PB);
+        s.lds = cg_gemm_lds(s.tier, r[k + 1]);
+    }
+    p.flops = 6.0 * (double)npts * w;
+    p.eff = op_mode_eff(mode, p.flops, TTX_CG_AUTO_FLOPS);
+    p.row = tab ? p.sumn : (size_t)d;
+    if (host_g) p.b_cgg = sizeof(double) * p.gsize;
+    if (!p.chunk) return p;                                                     // an empty call launches no chain
+    p.b_xa = p.b_xb = sizeof(double) * p.chunk * p.ldx;
+    p.b_gst = sizeof(double) * p.chunk * p.S;
+    if (!tab) p.b_btab = sizeof(double) * p.chunk * p.nmax;
+    if (!dev) { p.b_x = sizeof(double) * p.chunk * (p.row + 1); p.b_out = sizeof(double) * p.chunk; }      // the rows, then c; val
+    if (p.eff == TTX_EVAL_MFMA)
+        for (int k = 0; k < d; k++) p.b_part = std::max(p.b_part, sizeof(double) * p.step[k].size * (size_t)p.nsplit(k, (int)p.chunk));
+    p.lds_back = 4 * sizeof(double) * (size_t)p.ldx; p.lds_fwd = 2 * p.lds_back;
+    return p;
+}
+
 // ---- ttx_topk (ttx_topk.h) -----------------------------------------------------------------------------------------------------------
 #define TTX_TK_KMAX 4096            // largest K
 #define TTX_TK_SHEET (1 << 24)      // largest sheet K max n_k

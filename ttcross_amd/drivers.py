@@ -833,6 +833,92 @@ def run_basisgrad(argv, device=0, repeats=5, tt=None, basis=None, host_npts=1000
     return tt, x, (val, grad), res
 
 
+def basis_core_grad_host(tt, x, basis, c):
+    """what a user does without ttx_basis_core_grad_batch, the host route: every core to the host with core(k), the tables from
+    basis_table, the suffix states right to left and the prefix states left to right as in basis_grad_host, then one einsum per
+    core over the points (BLAS order, so equal to the device to rounding only).  Returns (val, [G_1 .. G_d])."""
+    from .engine import basis_table
+    x, c = np.asarray(x, dtype=np.float64), np.asarray(c, dtype=np.float64)
+    if isinstance(basis, (tuple, list)) and basis and isinstance(basis[0], str):
+        basis = [basis] * tt.d
+    cores = [tt.core(k) for k in range(1, tt.d + 1)]
+    phis = [basis_table(basis[k], g.shape[1], x[:, k]) for k, g in enumerate(cores)]
+    X = [None] * (tt.d + 1)
+    X[tt.d] = np.ones((x.shape[0], 1))
+    for k in range(tt.d - 1, -1, -1):
+        g = cores[k]
+        r0, n, r1 = g.shape
+        t = (X[k + 1] @ g.reshape(r0 * n, r1).T).reshape(x.shape[0], r0, n)
+        X[k] = np.einsum("paj,pj->pa", t, phis[k])
+    G = []
+    pre = np.ones((x.shape[0], 1))
+    for k in range(tt.d):
+        g = cores[k]
+        r0, n, r1 = g.shape
+        G.append(np.einsum("pa,pj,pk->ajk", c[:, None] * pre, phis[k], X[k + 1], optimize=True))
+        if k + 1 < tt.d:
+            pre = np.einsum("pjk,pj->pk", (pre @ g.reshape(r0, n * r1)).reshape(x.shape[0], n, r1), phis[k])
+    return X[0][:, 0], G
+
+
+def run_coregrad(argv, device=0, repeats=5, tt=None, basis=None, host_npts=1000):
+    """coregrad WORKLOAD NPTS [KIND] [MODE]: the workloads, kinds and modes of the basis sub-command.  On the same seeded points and
+    weights (drawn on the device) and in the same session: one warm-up and `repeats` timed basis_core_grad calls through the
+    device-pointer entry, the same for basis_grad_batch (the same flop count, so ratio_to_basis_grad is the figure of merit), and
+    the host route (basis_core_grad_host) on the first `host_npts`.  Prints one JSON line with the medians, the phases of
+    ttx_basis_core_grad_last (table, back, fwd, acc) and the ratios."""
+    import json
+    import time
+    import torch
+    torch.cuda.init()          # a torch that brings its own HIP runtime must initialise its device before the engine's library does
+    workload, npts = argv[0], int(float(argv[1]))
+    kind = argv[2] if len(argv) > 2 else "linear"
+    mode = argv[3] if len(argv) > 3 else "auto"
+    if tt is None:
+        tt, basis = basis_train(workload, device=device)
+    if basis is None:
+        basis = [("linear", np.linspace(0.0, 1.0, int(nk))) if kind == "linear" and nk > 1 else ("cos", 0.0, 1.0) for nk in tt._n]
+        lo, hi = 0.0, 1.0
+    else:
+        lo, hi = basis[1], basis[2]
+    entries = [basis] * tt.d if isinstance(basis[0], str) else list(basis)
+    dev = torch.device("cuda", device)
+    g = torch.Generator(device=dev)
+    g.manual_seed(20240607)
+    x = (lo + (hi - lo) * torch.rand((npts, tt.d), dtype=torch.float64, device=dev, generator=g)).contiguous()
+    c = torch.randn(npts, dtype=torch.float64, device=dev, generator=g).contiguous()
+    torch.cuda.synchronize(dev)
+
+    def timed(call):
+        out = call()                                # warm-up
+        ms = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            out = call()                            # synchronises before it returns
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return out, float(np.median(ms)), [round(v, 4) for v in ms]
+
+    (val, G), ms_cg, all_cg = timed(lambda: tt.basis_core_grad(x, basis, c, mode))
+    last = tt.basis_core_grad_last()
+    (vg, _), ms_bg, all_bg = timed(lambda: tt.basis_grad_batch(x, basis, last["mode"]))
+    res = dict(workload=workload, npts=npts, kind=entries[0][0], mode_asked=mode, mode=last["mode"], chunk=last["chunk"], d=tt.d,
+               max_rank=int(tt.ranks().max()), ms_core_grad=ms_cg, ms_core_grad_all=all_cg, ms_table=last["ms_table"], ms_back=last["ms_back"],
+               ms_fwd=last["ms_fwd"], ms_acc=last["ms_acc"], flops=last["flops"], tflops=last["flops"] / (ms_cg * 1e-3) / 1e12,
+               ms_basis_grad=ms_bg, ms_basis_grad_all=all_bg, ratio_to_basis_grad=ms_cg / ms_bg, val_is_basis_grads=bool(torch.equal(val, vg)),
+               nan=int(torch.isnan(G).sum().item()), checksum=float(G.sum().item()))
+    hp = min(npts, host_npts)
+    if hp > 0:
+        xh, ch = x[:hp].cpu().numpy(), c[:hp].cpu().numpy()
+        t0 = time.perf_counter()
+        _, ref = basis_core_grad_host(tt, xh, basis, ch)
+        res["host_route_npts"] = hp
+        res["host_route_ms"] = (time.perf_counter() - t0) * 1e3
+        _, got = tt.basis_core_grad(xh, basis, ch, last["mode"])
+        res["max_rel_diff_to_host_route"] = max(float(np.max(np.abs(a - b)) / max(float(np.max(np.abs(b))), 1e-300)) for a, b in zip(got, ref))
+    print(json.dumps(res))
+    return tt, x, (val, G), res
+
+
 def sample_host(tt, u, w=None):
     """what a user does without ttx_sample: every core to the host with core(k), then the conditional marginals walked in
     numpy from the last mode to the first.  Returns (ind, logq, val) of the definition in include/ttx.h, in numpy's own
@@ -1444,6 +1530,8 @@ if __name__ == "__main__":
         run_basis(sys.argv[2:])
     elif sys.argv[1] == "basisgrad":
         run_basisgrad(sys.argv[2:])
+    elif sys.argv[1] == "coregrad":
+        run_coregrad(sys.argv[2:])
     elif sys.argv[1] == "chf":
         run_chf(sys.argv[2:])
     elif sys.argv[1] == "pdf":

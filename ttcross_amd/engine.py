@@ -140,6 +140,14 @@ def load_library():
     L.ttx_basis_grad_tab_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32]
     L.ttx_basis_host_d.argtypes = [POINTER(_Basis), c_int32, c_int64, POINTER(c_double), c_int64, POINTER(c_double)]
     L.ttx_basis_grad_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_int64)]
+    L.ttx_basis_core_grad_batch.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(_Basis), POINTER(c_double), POINTER(c_double), POINTER(c_double), c_int32, c_int32]
+    L.ttx_basis_core_grad_batch_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(_Basis), c_void_p, c_void_p, c_void_p, c_int32, c_int32]
+    L.ttx_basis_core_grad_tab.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), c_int32, c_int32]
+    L.ttx_basis_core_grad_tab_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32]
+    L.ttx_basis_core_grad_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32),
+                                           POINTER(c_int64)]
+    L.ttx_cores_axpy.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double)]
+    L.ttx_cores_axpy_dev.argtypes = [c_void_p, POINTER(c_double), c_void_p]
     L.ttx_sample.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
     L.ttx_sample_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(c_double), POINTER(c_int32), c_void_p, c_void_p, c_void_p]
     L.ttx_sample_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
@@ -1175,6 +1183,114 @@ class TTCross:
                                                   ctypes.byref(ck)))
         names = {v: k for k, v in EVAL_MODES.items()}
         return dict(ms_table=mt.value, ms_back=mb.value, ms_fwd=mf.value, flops=fl.value, mode=names.get(md.value), chunk=ck.value)
+
+    # ---- the gradient with respect to the cores (include/ttx.h: ttx_basis_core_grad_batch) ----------------
+    def core_offsets(self):
+        """where every core's block starts in the packed gradient (and, last, its length): d + 1 numbers, mode 1 first"""
+        r, n = self.ranks().astype(np.int64), self._n.astype(np.int64)
+        return np.concatenate([[0], np.cumsum(r[:-1] * n * r[1:])])
+
+    def _core_blocks(self, flat):
+        """the packed gradient as a list of (r(k-1), n(k), r(k)) arrays (views of flat)"""
+        off, r = self.core_offsets(), self.ranks()
+        return [flat[off[k]:off[k + 1]].reshape((r[k], self._n[k], r[k + 1]), order="F") for k in range(self.d)]
+
+    def _core_pack(self, who, g):
+        """a list of blocks, or one flat array, as the packed host array"""
+        off, r = self.core_offsets(), self.ranks()
+        if isinstance(g, (list, tuple)):
+            if len(g) != self.d or any(np.shape(b) != (r[k], self._n[k], r[k + 1]) for k, b in enumerate(g)):
+                raise ValueError(f"{who}: {self.d} blocks of the cores' shapes expected")
+            return np.ascontiguousarray(np.concatenate([np.asarray(b, dtype=np.float64).ravel(order="F") for b in g]))
+        flat = np.ascontiguousarray(g, dtype=np.float64).reshape(-1)
+        if flat.size != off[-1]:
+            raise ValueError(f"{who}: {off[-1]} numbers expected (got {flat.size})")
+        return flat
+
+    def _core_grad(self, who, host, dev, head, t, cols, c, mode, out, accumulate):
+        L, md, acc = load_library(), _eval_mode(mode), int(bool(accumulate))
+        total = int(self.core_offsets()[-1])
+        val = self._dev_pair(who, t, cols)
+        if val is not None:
+            import torch
+            if type(c).__module__.split(".")[0] != "torch" or c.device != t.device or c.dtype != torch.float64 or not c.is_contiguous() or c.shape != (t.shape[0],):
+                raise ValueError(f"{who}: c must be a contiguous float64 tensor of shape (npts,) on the engine's device")
+            if out is None:
+                if acc:
+                    raise ValueError(f"{who}: accumulate needs out")
+                out = torch.empty(total, dtype=torch.float64, device=t.device)
+            elif type(out).__module__.split(".")[0] != "torch" or out.device != t.device or out.dtype != torch.float64 or not out.is_contiguous() or out.shape != (total,):
+                raise ValueError(f"{who}: out must be a contiguous float64 tensor of {total} numbers on the engine's device")
+            torch.cuda.current_stream(t.device).synchronize()
+            _check(dev(self._h, t.shape[0], c_void_p(t.data_ptr()), *head, c_void_p(c.data_ptr()), c_void_p(val.data_ptr()), c_void_p(out.data_ptr()), acc, md))
+            return val, out
+        if type(t).__module__.split(".")[0] == "torch":
+            t = t.cpu().numpy()
+        if type(c).__module__.split(".")[0] == "torch":
+            c = c.cpu().numpy()
+        ta, ca = np.ascontiguousarray(t, dtype=np.float64), np.ascontiguousarray(c, dtype=np.float64)
+        if ta.ndim != 2 or ta.shape[1] != cols or ca.shape != (ta.shape[0],):
+            raise ValueError(f"{who}: an array of shape (npts, {cols}) and npts weights expected")
+        if out is None:
+            if acc:
+                raise ValueError(f"{who}: accumulate needs out")
+            flat = np.zeros(total)
+        else:
+            flat = self._core_pack(who, out)
+        val = np.zeros(ta.shape[0])
+        _check(host(self._h, ta.shape[0], _dp(ta), *head, _dp(ca), _dp(val), _dp(flat), acc, md))
+        return val, self._core_blocks(flat)
+
+    def basis_core_grad(self, x, basis, c, mode="auto", out=None, accumulate=False):
+        """(val, g) at real points x (npts, d) with weights c (npts,) (include/ttx.h: ttx_basis_core_grad_batch): val is
+        basis_batch(x, basis) bit for bit in the mode that ran; g holds G_i = sum_p c[p] d f(x_p) / d U_i for every core -- for
+        c = dLoss/df the gradient of the loss with respect to the cores.  basis and mode as for basis_batch.  Host arrays in give
+        numpy out: g is a list of (r(k-1), n(k), r(k)) arrays.  Contiguous float64 torch tensors on the engine's device go by
+        pointer (ttx_basis_core_grad_batch_dev) and give one flat device tensor; core_offsets() gives the block starts.  out: a
+        gradient to write into (a list of blocks or a flat array on the host, a flat tensor on the device); accumulate=True adds
+        onto it.  A point masked with c = 0 still needs finite coordinates.  basis_core_grad_last() tells what ran."""
+        L = load_library()
+        if isinstance(basis, (tuple, list)) and basis and isinstance(basis[0], str):
+            basis = [basis] * self.d
+        basis = list(basis)
+        if len(basis) != self.d:
+            raise ValueError(f"basis_core_grad: {self.d} basis entries expected (got {len(basis)})")
+        pairs = [_basis_struct(e, self._n[k]) for k, e in enumerate(basis)]
+        arr = (_Basis * self.d)(*[p[0] for p in pairs])          # pairs keeps the node arrays alive
+        return self._core_grad("basis_core_grad", L.ttx_basis_core_grad_batch, L.ttx_basis_core_grad_batch_dev, (arr,), x, self.d, c, mode, out, accumulate)
+
+    def basis_core_grad_tab(self, phi, c, mode="auto", out=None, accumulate=False):
+        """The same with the caller's own tables (include/ttx.h: ttx_basis_core_grad_tab): phi (npts, sum n) in basis_tab's layout."""
+        L = load_library()
+        return self._core_grad("basis_core_grad_tab", L.ttx_basis_core_grad_tab, L.ttx_basis_core_grad_tab_dev, (), phi, int(self._n.sum()), c, mode, out, accumulate)
+
+    def basis_core_grad_last(self):
+        """dict(ms_table, ms_back, ms_fwd, ms_acc, flops, mode, chunk) of the last basis_core_grad / basis_core_grad_tab on this engine
+        (include/ttx.h: ttx_basis_core_grad_last); mode is "exact" or "mfma" (None before the first call), chunk the points per chunk"""
+        mt, mb, mf, ma, fl, md, ck = c_double(), c_double(), c_double(), c_double(), c_double(), c_int32(), c_int64()
+        _check(load_library().ttx_basis_core_grad_last(self._h, ctypes.byref(mt), ctypes.byref(mb), ctypes.byref(mf), ctypes.byref(ma), ctypes.byref(fl),
+                                                       ctypes.byref(md), ctypes.byref(ck)))
+        names = {v: k for k, v in EVAL_MODES.items()}
+        return dict(ms_table=mt.value, ms_back=mb.value, ms_fwd=mf.value, ms_acc=ma.value, flops=fl.value, mode=names.get(md.value), chunk=ck.value)
+
+    def cores_axpy(self, alpha, g):
+        """U_i <- U_i + alpha_i G_i for every core in one launch (include/ttx.h: ttx_cores_axpy).  alpha: a scalar or d numbers;
+        alpha_i = 0 leaves core i alone, whatever G_i holds.  g: what basis_core_grad returned (a list of blocks or a flat host
+        array; a flat float64 tensor on the engine's device goes by pointer)."""
+        L = load_library()
+        al = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, dtype=np.float64), (self.d,)))
+        if type(g).__module__.split(".")[0] == "torch" and g.is_cuda:
+            import torch
+            total = int(self.core_offsets()[-1])
+            if g.device.index != self.device or g.dtype != torch.float64 or not g.is_contiguous() or g.shape != (total,):
+                raise ValueError(f"cores_axpy: a contiguous float64 tensor of {total} numbers on the engine's device expected")
+            torch.cuda.current_stream(g.device).synchronize()
+            _check(L.ttx_cores_axpy_dev(self._h, _dp(al), c_void_p(g.data_ptr())))
+            return self
+        if type(g).__module__.split(".")[0] == "torch":
+            g = g.numpy()
+        _check(L.ttx_cores_axpy(self._h, _dp(al), _dp(self._core_pack("cores_axpy", g))))
+        return self
 
     # ---- samples from the resident train (include/ttx.h: ttx_sample and its three siblings) --------------
     # the outputs of the index samplers and of the real samplers: name, a row of d per sample (else one number), dtype, always allocated
