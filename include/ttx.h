@@ -563,8 +563,8 @@ int ttx_basis_grad_last     (const ttx_engine *h, double *ms_table, double *ms_b
  * that is derived from the cores -- every operation (evaluation, norm, quadrature, sampling tables, Gram matrices) rebuilds what it
  * needs from the cores it finds, which is why ttx_ort and ttx_svd drop nothing either -- so nothing stale survives an update.  Refusals
  * as above, and a NULL alpha or g.
- * Open: the gradient of the normaliser Z of the squared density (maximum likelihood for ttx_sample_sq_real needs it as well), a
- * Gauss-Newton or ALS solver, second derivatives, ranks above 128, the Fortran layer.
+ * Open: the gradient of the normaliser Z of the squared density (maximum likelihood for ttx_sample_sq_real needs it as well),
+ * second derivatives, ranks above 128, the Fortran layer.  The Gauss-Newton solver is ttx_basis_fit_batch, below.
  * Added without a new ttx_version: look the symbols up. */
 int ttx_basis_core_grad_batch    (ttx_engine *h, int64_t npts, const double *x /* [npts][d] */, const ttx_basis *basis /* [d] */, const double *c /* [npts] */, double *val, double *g, int32_t accumulate, int32_t mode);
 int ttx_basis_core_grad_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, const double *c_dev, double *val_dev, double *g_dev, int32_t accumulate, int32_t mode);
@@ -573,6 +573,85 @@ int ttx_basis_core_grad_tab_dev  (ttx_engine *h, int64_t npts, const double *phi
 int ttx_basis_core_grad_last     (const ttx_engine *h, double *ms_table, double *ms_back, double *ms_fwd, double *ms_acc, double *flops, int32_t *mode_ran, int64_t *chunk_ran);
 int ttx_cores_axpy    (ttx_engine *h, const double *alpha /* [d], host */, const double *g);
 int ttx_cores_axpy_dev(ttx_engine *h, const double *alpha /* [d], host */, const double *g_dev);
+
+/* Derivative of the same f along a direction V in core space, at a batch of real points (ttcross_amd/csrc/ttx_basis_jvp.h): J V, cores
+ * to points, the other half of ttx_basis_core_grad_batch (J^T c, points to cores).  With both, a Gauss-Newton or Levenberg-Marquardt
+ * step is solved matrix-free; a JVP keeps no states, so its point count is not limited by a state store.
+ *     dval_p = sum_i f_(U_i <- V_i)(x_p)
+ * v has the packed layout of g in ttx_basis_core_grad_batch (mode 1 first, (a, j, k) at a + r(i-1) (j + n(i) k)); it is read in place.
+ * Definition (numpy restates it: tests/basis_jvp_ref.py).  Multiply and add are always separate.  Backward, i = d .. 1, from X = (1),
+ * Y = (0.0):
+ *     t_j(a) = sum_k U_i(a,j,k) X(k),  s_j(a) = sum_k U_i(a,j,k) Y(k),  v_j(a) = sum_k V_i(a,j,k) X(k)   each from 0.0 over ascending k
+ *     z(a)   = sum_j phi_j t_j(a),     y(a)   = sum_j phi_j (s_j(a) + v_j(a))                            each from 0.0 over ascending j
+ *     X <- z,  Y <- y;   val = z(1) and dval = y(1) after mode 1.  The Y term of mode d is formed like any other.
+ * val[npts] may be NULL; it is the operation sequence of ttx_basis_batch and bit-identical to it in the same effective mode.
+ *   mode : TTX_EVAL_EXACT  the order above, one wave per point: bit-identical to the restatement
+ *          TTX_EVAL_MFMA   equal to EXACT to rounding (tests/basis_jvp_ref.py derives the bound).  A point's results depend on its own
+ *                          table rows only: never on its neighbours, the chunk (TTX_BASIS_CHUNK) or npts.  A call repeats bit for bit.
+ *          TTX_EVAL_AUTO   by 6 npts sum r(k-1) n(k) r(k) against a PROVISIONAL break-even (that of ttx_basis_batch; not measured)
+ * Arguments, refusals and engine kinds are those of ttx_basis_batch; in addition a NULL v or dval with npts > 0 is refused.  npts == 0
+ * launches nothing.  A point with a NaN table entry has val = dval = NaN, and no other point has.
+ * ttx_basis_jvp_last: of the last call on this engine, the milliseconds of the table and chain launches, the flops, the mode that ran.
+ *
+ * Vector operations on packed core-space buffers, for a caller's own optimiser (momentum, Adam, a line search) and the solver below.
+ * ttx_cores_dot: sum_e a_e * b_e in a fixed order that does not depend on the device and repeats bit for bit (numpy restates it).
+ *   With tot = sum_i ttx_core_size(h, i) the buffer is cut into 256 segments of L = 256 * ceil(tot / 65536) elements (the last ones may
+ *   be short or empty); inside a segment lane t sums the products of its elements e = t (mod 256) in ascending order from 0.0; the 256
+ *   lane sums are halved (t, t + 128), (t, t + 64), .. (0, 1); the 256 segment sums are added in ascending order from 0.0.
+ * ttx_cores_axpby_dev: y_e <- (alpha * x_e) + (beta * y_e), two multiplies and one add, no special cases; x and y on the engine's device.
+ * ttx_cores_get_dev / ttx_cores_set_dev (ttx_cores_get / ttx_cores_set: a host buffer): the engine's cores to and from a packed
+ *   buffer of the present ranks, bit for bit.  After a set
+ *   nothing stale survives, as after ttx_cores_axpy: the engine keeps nothing between calls that is derived from the cores.
+ * Refusals: those of ttx_cores_axpy, and a NULL buffer or out.
+ *
+ * ttx_basis_fit_batch / _tab: minimise loss = 1/2 sum_p w_p (f(x_p) - y_p)^2 over all cores of the resident train, in place, by a
+ * matrix-free Levenberg-Marquardt iteration (the controller is ttcross_amd/csrc/ttx_fit_plan.h; tests/basis_jvp_ref.py: fit_numpy
+ * restates the whole solver).  Every scalar operation is one host double operation in the order written; sums over core space are
+ * ttx_cores_dot's, sums over the points the same rule with tot = npts.
+ *   1. val = f(x_p), res = val - y, c = w * res, loss = 0.5 * dot_n(c, res); g = J^T c; rho0 = dot(g, g); rho0 == 0 stops (reason 3).
+ *      A rejected step leaves the cores, and so g and loss, as they were: they are kept, not formed again.
+ *   2. CG on (J^T W J + lambda I) s = -g:  s = 0, r = (-1 * g) + (1 * 0), p = r, rho = rho0.
+ *   3. For k < cg_max:  q = J p;  Ap = J^T (w * q);  Ap <- (lambda * p) + (1 * Ap);  pAp = dot(p, Ap);  leave the loop unless pAp is a
+ *      positive finite number;  alpha = rho / pAp;  s <- (alpha * p) + (1 * s);  r <- (-alpha * Ap) + (1 * r);  rho_new = dot(r, r);
+ *      stop the loop where rho_new <= (cg_tol * cg_tol) * rho0;  p <- (1 * r) + ((rho_new / rho) * p);  rho = rho_new.
+ *   4. Snapshot the cores (ttx_cores_get_dev), ttx_cores_axpy(1.0, s), the trial loss by the value chain.
+ *   5. Accepted where the trial loss is finite and strictly smaller: lambda *= lambda_down.  Otherwise the snapshot is copied back
+ *      (not subtracted: that would not give the bits back) and lambda *= lambda_up.  A loop that ended with s = 0 is a rejection.
+ * w NULL means all ones (c = res, Ap = J^T q); a negative or non-finite w (host forms) is refused.  The host forms upload x (or the
+ * table), y and w once; every pass then runs the _dev paths.  History, each array may be NULL: loss[max_iter + 1] (loss[0] at entry,
+ * loss[i + 1] after iteration i), lambda[max_iter] (what iteration i solved with), cg_iters[max_iter] (its J V products),
+ * accepted[max_iter]; entries past result->iters repeat the last loss and lambda with cg_iters = accepted = 0.
+ * TTX_EVAL_EXACT follows fit_numpy bit for bit; TTX_EVAL_MFMA runs every chain on the matrix cores; TTX_EVAL_AUTO decides per call.
+ * Refusals: those of ttx_basis_core_grad_batch (multi-process engines, ranks, TTX_ESTATE), a NULL opts, y or input with npts > 0,
+ * npts < 1, options out of range (max_iter < 0, cg_max < 1, max_reject < 1, lambda0 <= 0, lambda_down outside (0, 1], lambda_up < 1,
+ * negative tolerances); work space that cannot be allocated is TTX_EHIP, nothing faults.  A refused call leaves the cores untouched.
+ * ttx_basis_fit_last: of the last fit on this engine, the milliseconds in JVP, core-gradient, value and vector launches, the counts of
+ * JVP and core-gradient calls, the mode the last JVP ran in (-1: none).
+ * Open: an ALS sweep, rank adaptation during the fit, a preconditioner for CG, the gradient of the normaliser Z, ranks above 128.
+ * Added without a new ttx_version: look the symbols up. */
+typedef struct { int32_t max_iter, cg_max, max_reject, mode; double lambda0, lambda_down, lambda_up, cg_tol, loss_tol; } ttx_fit_opts;
+typedef struct { int32_t iters, stop; /* 1 max_iter, 2 loss_tol, 3 zero gradient, 4 max_reject consecutive rejections, 5 non-finite loss at entry */ } ttx_fit_result;
+int ttx_basis_jvp_batch    (ttx_engine *h, int64_t npts, const double *x /* [npts][d] */, const ttx_basis *basis /* [d] */, const double *v, double *val, double *dval, int32_t mode);
+int ttx_basis_jvp_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, const double *v_dev, double *val_dev, double *dval_dev, int32_t mode);
+int ttx_basis_jvp_tab      (ttx_engine *h, int64_t npts, const double *phi /* [npts][sum n(k)] */, const double *v, double *val, double *dval, int32_t mode);
+int ttx_basis_jvp_tab_dev  (ttx_engine *h, int64_t npts, const double *phi_dev, const double *v_dev, double *val_dev, double *dval_dev, int32_t mode);
+int ttx_basis_jvp_last     (const ttx_engine *h, double *ms_table, double *ms_chain, double *flops, int32_t *mode_ran);
+int ttx_cores_dot      (ttx_engine *h, const double *a, const double *b, double *out);
+int ttx_cores_dot_dev  (ttx_engine *h, const double *a_dev, const double *b_dev, double *out /* host */);
+int ttx_cores_axpby_dev(ttx_engine *h, double alpha, const double *x_dev, double beta, double *y_dev);
+int ttx_cores_get      (ttx_engine *h, double *g);
+int ttx_cores_set      (ttx_engine *h, const double *g);
+int ttx_cores_get_dev  (ttx_engine *h, double *g_dev);
+int ttx_cores_set_dev  (ttx_engine *h, const double *g_dev);
+int ttx_basis_fit_batch    (ttx_engine *h, int64_t npts, const double *x, const ttx_basis *basis, const double *y, const double *w, const ttx_fit_opts *opts,
+                            double *loss, double *lambda, int32_t *cg_iters, int32_t *accepted, ttx_fit_result *result);
+int ttx_basis_fit_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, const double *y_dev, const double *w_dev, const ttx_fit_opts *opts,
+                            double *loss, double *lambda, int32_t *cg_iters, int32_t *accepted, ttx_fit_result *result);
+int ttx_basis_fit_tab      (ttx_engine *h, int64_t npts, const double *phi, const double *y, const double *w, const ttx_fit_opts *opts,
+                            double *loss, double *lambda, int32_t *cg_iters, int32_t *accepted, ttx_fit_result *result);
+int ttx_basis_fit_tab_dev  (ttx_engine *h, int64_t npts, const double *phi_dev, const double *y_dev, const double *w_dev, const ttx_fit_opts *opts,
+                            double *loss, double *lambda, int32_t *cg_iters, int32_t *accepted, ttx_fit_result *result);
+int ttx_basis_fit_last     (const ttx_engine *h, double *ms_jvp, double *ms_core_grad, double *ms_value, double *ms_vector, int64_t *n_jvp, int64_t *n_core_grad, int32_t *mode_ran);
 
 /* Samples drawn from the resident train by sequential conditional sampling, on the device (ttcross_amd/csrc/ttx_sample.h).
  * Modes are 1-based, G_k is core k, r_0 = r_d = 1.

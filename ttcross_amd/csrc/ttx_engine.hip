@@ -53,6 +53,8 @@
 #include "ttx_basis.h"
 #include "ttx_basis_grad.h"
 #include "ttx_basis_core_grad.h"
+#include "ttx_basis_jvp.h"
+#include "ttx_fit_plan.h"
 #include "ttx_algebra.h"
 #include "ttx_roundsum.h"
 #include "ttx_sample.h"
@@ -145,6 +147,8 @@ enum {
     SC_BTAB,                            // ttx_basis_batch: the table of one mode for one chunk, chunk x max n (its states go to SC_XA / SC_XB, its nodes to SC_META)
     SC_GST,                             // ttx_basis_grad_batch: the state store, the rows D_i of all modes of a chunk (its tables go to SC_BTAB, its states to SC_XA / SC_XB)
     SC_CGG, SC_CGP,                     // ttx_basis_core_grad_batch: the packed gradient of a host caller (also ttx_cores_axpy's), the partial blocks of a core's segments (its states X_i go to SC_GST, L to SC_XA / SC_XB)
+    SC_JVV, SC_VDP, SC_VIN,             // ttx_basis_jvp_batch: the packed direction of a host caller; ttx_cores_dot: the segment sums, the two buffers of a host caller
+    SC_FITV, SC_FITP,                   // ttx_basis_fit_batch: the core-space work vectors and the snapshot; the point vectors, then the uploaded inputs of a host caller
     SC_NBUF
 };
 struct EvBuf { void *p = nullptr; size_t bytes = 0; };
@@ -203,6 +207,9 @@ struct BsLast { double ms[2] = {0.0, 0.0}, flops = 0.0; int mode = -1; };      /
 struct BgLast { double ms[3] = {0.0, 0.0, 0.0}, flops = 0.0; int mode = -1; int64_t chunk = 0; };     // ttx_basis_grad_batch / ttx_basis_grad_tab: table, backward, forward launches
 
 struct CgLast { double ms[4] = {0.0, 0.0, 0.0, 0.0}, flops = 0.0; int mode = -1; int64_t chunk = 0; };     // ttx_basis_core_grad_batch / _tab: table, backward, forward, accumulation launches
+
+struct JvLast { double ms[2] = {0.0, 0.0}, flops = 0.0; int mode = -1; };      // ttx_basis_jvp_batch / ttx_basis_jvp_tab: table launches, chain launches
+struct FitLast { double ms[4] = {0.0, 0.0, 0.0, 0.0}; int64_t n_jvp = 0, n_cg = 0; int mode = -1; };      // ttx_basis_fit_batch / _tab: JVP, core-gradient, value, vector launches
 
 struct DevFun;                          // a loaded device integrand (TTX_FUN_DEVICE), defined with slot_eval
 struct TrainFun;                        // the operands and the combiner of TTX_FUN_TRAINS, defined with slot_eval
@@ -319,6 +326,8 @@ struct ttx_engine {
     BsLast bs;
     BgLast bg;
     CgLast cg;
+    JvLast jv;
+    FitLast fit;
     std::vector<hipEvent_t> op_ev;                      // OpMarks' events: ttx_lincomb_round, the squared samplers, the basis evaluations
 };
 
@@ -4338,6 +4347,336 @@ static int ca_run(ttx_engine *h, const char *who, const double *alpha, const dou
 }
 extern "C" int ttx_cores_axpy(ttx_engine *h, const double *alpha, const double *g) { return ca_run(h, "ttx_cores_axpy", alpha, g, false); }
 extern "C" int ttx_cores_axpy_dev(ttx_engine *h, const double *alpha, const double *g_dev) { return ca_run(h, "ttx_cores_axpy_dev", alpha, g_dev, true); }
+
+// ---- the derivative along a direction in core space (ttx_basis_jvp.h) ------------------------------------------------------------
+enum { JVM_TABLE, JVM_CHAIN };             // OpMarks phases of a call, JvLast::ms takes the sums
+// in: the coordinates or the caller's phi; v: the packed direction, on the host unless dev; val may be null
+static int jv_run(ttx_engine *h, const char *who, BsSrc src, int64_t npts, const double *in, const ttx_basis *basis, const double *v, double *val, double *dval, int32_t mode)
+{
+    const bool tab = src == BS_TAB_HOST || src == BS_TAB_DEV, dev = src == BS_X_DEV || src == BS_TAB_DEV;
+    int rc = tt_prepare(h, who);
+    if (rc) return rc;
+    if (npts < 0 || (npts > 0 && (!in || !v || !dval || (!tab && !basis)))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
+    if (!op_mode_known(mode)) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    const int d = h->d;
+    if (!tab && basis) for (int k = 1; k <= d; k++) if ((rc = bs_check_one(who, k, basis[k - 1], h->n1[k]))) return rc;
+    const JvPlan pl = jv_plan(d, h->n1.data() + 1, h->rfinal.data(), dev_ncu(h), src, !dev, npts, mode, env_chunk("TTX_BASIS_CHUNK", op_chunk_default(h->RM)));
+    if (pl.refusal == BS_RANK) return fail(TTX_EINVAL, "%s: ranks up to 128 only (got %d)", who, pl.rmax);
+    if (pl.refusal == BS_BOUNDARY) return fail(TTX_EINVAL, "%s: boundary ranks are not 1", who);
+    h->jv = JvLast();
+    h->jv.flops = pl.flops; h->jv.mode = pl.eff;
+    if (npts == 0) return TTX_OK;
+    EvTrain T;
+    if ((rc = ev_train(h, &T))) return rc;
+    std::vector<BsMode> M(d);
+    if (!tab) {                                                                 // the nodes of the LINEAR modes, one device block
+        OpMeta meta(h->meta_host);
+        std::vector<size_t> o_nodes(d, 0);
+        for (int k = 0; k < d; k++)
+            if (basis[k].kind == TTX_BASIS_LINEAR) o_nodes[k] = meta.put(std::vector<double>(basis[k].nodes, basis[k].nodes + h->n1[k + 1]));
+        char *dm = nullptr;
+        if (!meta.host.empty() && (rc = meta.upload(h, SC_META, &dm))) return rc;
+        for (int k = 0; k < d; k++) {
+            const ttx_basis &b = basis[k];
+            const bool cosk = b.kind == TTX_BASIS_COS;
+            M[k] = BsMode{b.kind, b.flags, h->n1[k + 1], cosk ? b.a : 0.0, cosk ? ttx_basis_cos_w(b.a, b.b) : 0.0, cosk ? nullptr : (const double *)(dm + o_nodes[k])};
+        }
+    }
+    if ((rc = buf_reserve(h, {{SC_XA, pl.b_xa}, {SC_XB, pl.b_xb}, {SC_BTAB, pl.b_btab}, {SC_X, pl.b_x}, {SC_OUT, pl.b_out}, {SC_JVV, pl.b_v}}))) return rc;
+    double *btab = buf<double>(h, SC_BTAB), *sin_ = buf<double>(h, SC_X), *sout = buf<double>(h, SC_OUT);
+    const double *V = v;
+    if (!dev) {
+        HIPCHECK(hipMemcpyAsync(buf<double>(h, SC_JVV), v, sizeof(double) * pl.vsize, hipMemcpyHostToDevice, h->stream));
+        V = buf<double>(h, SC_JVV);
+    }
+    if (pl.eff == TTX_EVAL_MFMA)
+        for (int i = 0; i < d; i++)
+            if ((rc = with_tier<true>(pl.step[i].tier, [&](auto mr) { return op_lds_raise(h, reinterpret_cast<const void *>(&k_jv_gemm<decltype(mr)::value>), pl.step[i].lds); }))) return rc;
+    OpMarks marks(h->op_ev);
+    for (int64_t o = 0; o < npts; o += (int64_t)pl.chunk) {
+        const int c = (int)std::min<int64_t>((int64_t)pl.chunk, npts - o);
+        const double *cin = in + (size_t)o * pl.row;
+        double *cval = val ? val + o : nullptr, *cd = dval + o;
+        if (!dev) {
+            HIPCHECK(hipMemcpyAsync(sin_, cin, sizeof(double) * (size_t)c * pl.row, hipMemcpyHostToDevice, h->stream));
+            cin = sin_; cval = val ? sout : nullptr; cd = sout + pl.chunk;
+        }
+        double *X = buf<double>(h, SC_XA), *Z = buf<double>(h, SC_XB);
+        if ((rc = marks.mark(h->stream, OpMarks::DISCARD))) return rc;
+        for (int i = d - 1; i >= 0; i--) {
+            const double *ph = cin + pl.off[i];
+            size_t ld = pl.sumn;
+            if (!tab) {
+                hipLaunchKernelGGL(k_bs_table, g1((size_t)c * M[i].n), dim3(256), 0, h->stream, M[i], (long long)c, cin + i, d, btab);
+                if ((rc = marks.mark(h->stream, JVM_TABLE))) return rc;
+                ph = btab; ld = (size_t)M[i].n;
+            }
+            const double *Xin = i == d - 1 ? nullptr : X, *Vi = V + pl.voff[i];
+            const int last = i == 0;
+            if (pl.eff == TTX_EVAL_EXACT)
+                hipLaunchKernelGGL(k_jv_exact, dim3(pl.g_exact(c)), dim3(256), pl.exact_lds, h->stream, T, i, (long long)c, ph, ld, Vi, Xin, Z, pl.ystr, cval, cd, last);
+            else
+                with_tier<true>(pl.step[i].tier, [&](auto mr) {
+                    hipLaunchKernelGGL(k_jv_gemm<decltype(mr)::value>, dim3(pl.g_gemm(i, c), pl.step[i].gy), dim3(256), pl.step[i].lds.bytes, h->stream, T, i, c, ph, ld, Vi, Xin, Z, pl.ystr, cval, cd, last);
+                    return 0;
+                });
+            if ((rc = marks.mark(h->stream, JVM_CHAIN))) return rc;
+            std::swap(X, Z);
+        }
+        if (!dev) {
+            if (val) HIPCHECK(hipMemcpyAsync(val + o, sout, sizeof(double) * (size_t)c, hipMemcpyDeviceToHost, h->stream));
+            HIPCHECK(hipMemcpyAsync(dval + o, sout + pl.chunk, sizeof(double) * (size_t)c, hipMemcpyDeviceToHost, h->stream));
+        }
+        if (!dev || marks.phase.size() > 4096) {                                // the staging blocks are reused by the next chunk; the event chain stays short
+            HIPCHECK(hipStreamSynchronize(h->stream));
+            if ((rc = marks.sum(h->jv.ms))) return rc;
+        }
+    }
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    if ((rc = marks.sum(h->jv.ms))) return rc;
+    HIPCHECK(hipGetLastError());
+    return TTX_OK;
+}
+extern "C" int ttx_basis_jvp_batch(ttx_engine *h, int64_t npts, const double *x, const ttx_basis *basis, const double *v, double *val, double *dval, int32_t mode)
+{
+    return jv_run(h, "ttx_basis_jvp_batch", BS_X_HOST, npts, x, basis, v, val, dval, mode);
+}
+extern "C" int ttx_basis_jvp_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, const double *v_dev, double *val_dev, double *dval_dev, int32_t mode)
+{
+    return jv_run(h, "ttx_basis_jvp_batch_dev", BS_X_DEV, npts, x_dev, basis, v_dev, val_dev, dval_dev, mode);
+}
+extern "C" int ttx_basis_jvp_tab(ttx_engine *h, int64_t npts, const double *phi, const double *v, double *val, double *dval, int32_t mode)
+{
+    return jv_run(h, "ttx_basis_jvp_tab", BS_TAB_HOST, npts, phi, nullptr, v, val, dval, mode);
+}
+extern "C" int ttx_basis_jvp_tab_dev(ttx_engine *h, int64_t npts, const double *phi_dev, const double *v_dev, double *val_dev, double *dval_dev, int32_t mode)
+{
+    return jv_run(h, "ttx_basis_jvp_tab_dev", BS_TAB_DEV, npts, phi_dev, nullptr, v_dev, val_dev, dval_dev, mode);
+}
+extern "C" int ttx_basis_jvp_last(const ttx_engine *h, double *ms_table, double *ms_chain, double *flops, int32_t *mode_ran)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_basis_jvp_last: null engine");
+    if (ms_table) *ms_table = h->jv.ms[JVM_TABLE];
+    if (ms_chain) *ms_chain = h->jv.ms[JVM_CHAIN];
+    if (flops) *flops = h->jv.flops;
+    if (mode_ran) *mode_ran = h->jv.mode;
+    return TTX_OK;
+}
+
+// ---- vector operations on packed core-space buffers (ttx_basis_jvp.h) ------------------------------------------------------------
+static size_t cores_total(const ttx_engine *h) { size_t t = 0; for (int k = 1; k <= h->d; k++) t += core_elems(h, k); return t; }
+// the fixed-order dot product of two device buffers of tot doubles: the segment sums on the device, their sum on the host
+static int vec_dot(ttx_engine *h, long long tot, const double *a, const double *b, double *out)
+{
+    if (int rc = buf_reserve(h, SC_VDP, sizeof(double) * TTX_DOT_SEGS)) return rc;
+    double *part = buf<double>(h, SC_VDP), hp[TTX_DOT_SEGS];
+    hipLaunchKernelGGL(k_vec_dot, dim3(TTX_DOT_SEGS), dim3(256), 0, h->stream, tot, dot_seg(tot), a, b, part);
+    HIPCHECK(hipMemcpyAsync(hp, part, sizeof(hp), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    double s = 0.0;
+    for (int k = 0; k < TTX_DOT_SEGS; k++) s = s + hp[k];
+    *out = s;
+    return TTX_OK;
+}
+static int cd_run(ttx_engine *h, const char *who, const double *a, const double *b, double *out, bool dev)
+{
+    int rc = tt_prepare(h, who);
+    if (rc) return rc;
+    if (!a || !b || !out) return fail(TTX_EINVAL, "%s: null argument", who);
+    if ((rc = cg_check_train(h, who))) return rc;
+    const size_t tot = cores_total(h);
+    if (!dev) {
+        if ((rc = buf_reserve(h, SC_VIN, sizeof(double) * 2 * tot))) return rc;
+        double *s = buf<double>(h, SC_VIN);
+        HIPCHECK(hipMemcpyAsync(s, a, sizeof(double) * tot, hipMemcpyHostToDevice, h->stream));
+        HIPCHECK(hipMemcpyAsync(s + tot, b, sizeof(double) * tot, hipMemcpyHostToDevice, h->stream));
+        a = s; b = s + tot;
+    }
+    if ((rc = vec_dot(h, (long long)tot, a, b, out))) return rc;
+    HIPCHECK(hipGetLastError());
+    return TTX_OK;
+}
+extern "C" int ttx_cores_dot(ttx_engine *h, const double *a, const double *b, double *out) { return cd_run(h, "ttx_cores_dot", a, b, out, false); }
+extern "C" int ttx_cores_dot_dev(ttx_engine *h, const double *a_dev, const double *b_dev, double *out) { return cd_run(h, "ttx_cores_dot_dev", a_dev, b_dev, out, true); }
+extern "C" int ttx_cores_axpby_dev(ttx_engine *h, double alpha, const double *x_dev, double beta, double *y_dev)
+{
+    const char *who = "ttx_cores_axpby_dev";
+    int rc = tt_prepare(h, who);
+    if (rc) return rc;
+    if (!x_dev || !y_dev) return fail(TTX_EINVAL, "%s: null argument", who);
+    if ((rc = cg_check_train(h, who))) return rc;
+    const size_t tot = cores_total(h);
+    hipLaunchKernelGGL(k_vec_axpby, g1(tot), dim3(256), 0, h->stream, (long long)tot, alpha, x_dev, beta, y_dev);
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipGetLastError());
+    return TTX_OK;
+}
+// the cores to (set: from) a packed device buffer, core by core on the shared pack/push helpers; bit for bit
+static int cores_copy_dev(ttx_engine *h, const char *who, double *g, bool set, bool dev = true)
+{
+    int rc = tt_prepare(h, who);
+    if (rc) return rc;
+    if (!g) return fail(TTX_EINVAL, "%s: null argument", who);
+    if ((rc = cg_check_train(h, who))) return rc;
+    size_t off = 0;
+    double *hg = g;
+    if (!dev) {                                                                 // a host caller's buffer goes through the staging block of ttx_cores_axpy
+        if ((rc = buf_reserve(h, SC_CGG, sizeof(double) * cores_total(h)))) return rc;
+        g = buf<double>(h, SC_CGG);
+        if (set) HIPCHECK(hipMemcpyAsync(g, hg, sizeof(double) * cores_total(h), hipMemcpyHostToDevice, h->stream));
+    }
+    for (int k = 1; k <= h->d; k++) {
+        if (set) unpack_core(h, k, g + off, h->rfinal[k - 1], h->rfinal[k]);
+        else pack_core(h->stream, h, k, g + off);
+        off += core_elems(h, k);
+    }
+    if (!dev && !set) HIPCHECK(hipMemcpyAsync(hg, g, sizeof(double) * cores_total(h), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipGetLastError());
+    return TTX_OK;
+}
+extern "C" int ttx_cores_get(ttx_engine *h, double *g) { return cores_copy_dev(h, "ttx_cores_get", g, false, false); }
+extern "C" int ttx_cores_set(ttx_engine *h, const double *g) { return cores_copy_dev(h, "ttx_cores_set", const_cast<double *>(g), true, false); }
+extern "C" int ttx_cores_get_dev(ttx_engine *h, double *g_dev) { return cores_copy_dev(h, "ttx_cores_get_dev", g_dev, false); }
+extern "C" int ttx_cores_set_dev(ttx_engine *h, const double *g_dev) { return cores_copy_dev(h, "ttx_cores_set_dev", const_cast<double *>(g_dev), true); }
+
+// ---- the Gauss-Newton solver (ttx_fit_plan.h holds the controller; this is its backend on the device) ----------------------------
+enum { FTM_JVP, FTM_CG, FTM_VAL, FTM_VEC };
+namespace {
+struct FitDev {
+    ttx_engine *h; const char *who; BsSrc src; int64_t npts; const double *in; const ttx_basis *basis; const double *y, *w; int mode;
+    size_t tot = 0;
+    double *vec[FIT_NVEC] = {}, *snap = nullptr, *val = nullptr, *q = nullptr, *c = nullptr;     // q: the residual inside loss(), else J p
+    std::vector<double> ones;
+    // a vector launch between two marks of the engine's event pool
+    template <class F> int timed(F f)
+    {
+        OpMarks marks(h->op_ev);
+        int rc;
+        if ((rc = marks.mark(h->stream, OpMarks::DISCARD))) return rc;
+        if ((rc = f())) return rc;
+        if ((rc = marks.mark(h->stream, FTM_VEC))) return rc;
+        HIPCHECK(hipStreamSynchronize(h->stream));
+        return marks.sum(h->fit.ms);
+    }
+    int loss(double *l)
+    {
+        int rc = bs_run(h, who, src, npts, in, basis, val, mode);
+        if (rc) return rc;
+        h->fit.ms[FTM_VAL] += h->bs.ms[BSM_TABLE] + h->bs.ms[BSM_CHAIN];
+        double s = 0.0;
+        if ((rc = timed([&] {
+                hipLaunchKernelGGL(k_fit_residual, g1((size_t)npts), dim3(256), 0, h->stream, (long long)npts, val, y, w, q, c);
+                return vec_dot(h, (long long)npts, c, q, &s);
+            }))) return rc;
+        *l = 0.5 * s;
+        return TTX_OK;
+    }
+    int core_grad(int from_q, int dst)
+    {
+        const double *cw = c;
+        int rc;
+        if (from_q) {
+            if (!w) cw = q;
+            else if ((rc = timed([&] { hipLaunchKernelGGL(k_fit_weigh, g1((size_t)npts), dim3(256), 0, h->stream, (long long)npts, w, q, c); return 0; }))) return rc;
+        }
+        if ((rc = cg_run(h, who, src, npts, in, basis, cw, nullptr, vec[dst], 0, mode))) return rc;
+        h->fit.n_cg++;
+        for (int k = 0; k < 4; k++) h->fit.ms[FTM_CG] += h->cg.ms[k];
+        return TTX_OK;
+    }
+    int jvp(int v)
+    {
+        int rc = jv_run(h, who, src, npts, in, basis, vec[v], nullptr, q, mode);
+        if (rc) return rc;
+        h->fit.n_jvp++; h->fit.mode = h->jv.mode;
+        h->fit.ms[FTM_JVP] += h->jv.ms[JVM_TABLE] + h->jv.ms[JVM_CHAIN];
+        return TTX_OK;
+    }
+    int dot(int a, int b, double *s) { return timed([&] { return vec_dot(h, (long long)tot, vec[a], vec[b], s); }); }
+    int axpby(double al, int x, double be, int yv)
+    {
+        return timed([&] { hipLaunchKernelGGL(k_vec_axpby, g1(tot), dim3(256), 0, h->stream, (long long)tot, al, vec[x], be, vec[yv]); return 0; });
+    }
+    int zero(int v) { return timed([&] { HIPCHECK(hipMemsetAsync(vec[v], 0, sizeof(double) * tot, h->stream)); return 0; }); }
+    int copy(int dst, int s) { return timed([&] { HIPCHECK(hipMemcpyAsync(vec[dst], vec[s], sizeof(double) * tot, hipMemcpyDeviceToDevice, h->stream)); return 0; }); }
+    int snapshot() { return timed([&] { return cores_copy_dev(h, who, snap, false); }); }
+    int restore() { return timed([&] { return cores_copy_dev(h, who, snap, true); }); }
+    int apply(int s) { return timed([&] { return ca_run(h, who, ones.data(), vec[s], true); }); }
+};
+}
+static int fit_run_dev(ttx_engine *h, const char *who, BsSrc src, int64_t npts, const double *in, const ttx_basis *basis, const double *y, const double *w,
+                       const ttx_fit_opts *opts, double *loss, double *lambda, int32_t *cg_iters, int32_t *accepted, ttx_fit_result *result)
+{
+    const bool tab = src == BS_TAB_HOST || src == BS_TAB_DEV, dev = src == BS_X_DEV || src == BS_TAB_DEV;
+    int rc = tt_prepare(h, who);
+    if (rc) return rc;
+    if (!opts || npts < 1 || !in || !y || (!tab && !basis)) return fail(TTX_EINVAL, "%s: null argument or npts < 1", who);
+    if (const char *bad = fit_opts_problem(*opts)) return fail(TTX_EINVAL, "%s: %s", who, bad);
+    if ((rc = cg_check_train(h, who))) return rc;
+    const int d = h->d;
+    if (!tab) for (int k = 1; k <= d; k++) if ((rc = bs_check_one(who, k, basis[k - 1], h->n1[k]))) return rc;
+    if (!dev && w) for (int64_t p = 0; p < npts; p++) if (!(w[p] >= 0.0) || !std::isfinite(w[p])) return fail(TTX_EINVAL, "%s: w[%lld] is negative or not finite", who, (long long)p);
+    size_t row = (size_t)d;
+    double work = 0.0;
+    if (tab) { row = 0; for (int k = 1; k <= d; k++) row += (size_t)h->n1[k]; }
+    for (int k = 1; k <= d; k++) work += (double)core_elems(h, k);
+    FitDev b{h, who, tab ? BS_TAB_DEV : BS_X_DEV, npts, in, basis, y, w, op_mode_eff(opts->mode, 6.0 * (double)npts * work, TTX_JV_AUTO_FLOPS)};
+    b.tot = cores_total(h);
+    b.ones.assign(d, 1.0);
+    // the work vectors g, s, r, p, Ap and the snapshot; the three point vectors, then what a host caller's arrays are uploaded into, once
+    const size_t np = (size_t)npts, nin = dev ? 0 : np * row + np + (w ? np : 0);
+    if ((rc = buf_reserve(h, {{SC_FITV, sizeof(double) * (FIT_NVEC + 1) * b.tot}, {SC_FITP, sizeof(double) * (3 * np + nin)}}))) return rc;
+    double *fv = buf<double>(h, SC_FITV), *fp = buf<double>(h, SC_FITP);
+    for (int k = 0; k < FIT_NVEC; k++) b.vec[k] = fv + (size_t)k * b.tot;
+    b.snap = fv + (size_t)FIT_NVEC * b.tot;
+    b.val = fp; b.q = fp + np; b.c = fp + 2 * np;
+    if (!dev) {
+        double *ui = fp + 3 * np, *uy = ui + np * row, *uw = uy + np;
+        HIPCHECK(hipMemcpyAsync(ui, in, sizeof(double) * np * row, hipMemcpyHostToDevice, h->stream));
+        HIPCHECK(hipMemcpyAsync(uy, y, sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
+        if (w) HIPCHECK(hipMemcpyAsync(uw, w, sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
+        HIPCHECK(hipStreamSynchronize(h->stream));
+        b.in = ui; b.y = uy; b.w = w ? uw : nullptr;
+    }
+    h->fit = FitLast();
+    h->fit.mode = b.mode;
+    FitHistory hist;
+    hist.loss = loss; hist.lambda = lambda; hist.cg_iters = cg_iters; hist.accepted = accepted;
+    return fit_run(b, *opts, hist, result);
+}
+extern "C" int ttx_basis_fit_batch(ttx_engine *h, int64_t npts, const double *x, const ttx_basis *basis, const double *y, const double *w, const ttx_fit_opts *opts,
+                                   double *loss, double *lambda, int32_t *cg_iters, int32_t *accepted, ttx_fit_result *result)
+{
+    return fit_run_dev(h, "ttx_basis_fit_batch", BS_X_HOST, npts, x, basis, y, w, opts, loss, lambda, cg_iters, accepted, result);
+}
+extern "C" int ttx_basis_fit_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, const double *y_dev, const double *w_dev, const ttx_fit_opts *opts,
+                                       double *loss, double *lambda, int32_t *cg_iters, int32_t *accepted, ttx_fit_result *result)
+{
+    return fit_run_dev(h, "ttx_basis_fit_batch_dev", BS_X_DEV, npts, x_dev, basis, y_dev, w_dev, opts, loss, lambda, cg_iters, accepted, result);
+}
+extern "C" int ttx_basis_fit_tab(ttx_engine *h, int64_t npts, const double *phi, const double *y, const double *w, const ttx_fit_opts *opts,
+                                 double *loss, double *lambda, int32_t *cg_iters, int32_t *accepted, ttx_fit_result *result)
+{
+    return fit_run_dev(h, "ttx_basis_fit_tab", BS_TAB_HOST, npts, phi, nullptr, y, w, opts, loss, lambda, cg_iters, accepted, result);
+}
+extern "C" int ttx_basis_fit_tab_dev(ttx_engine *h, int64_t npts, const double *phi_dev, const double *y_dev, const double *w_dev, const ttx_fit_opts *opts,
+                                     double *loss, double *lambda, int32_t *cg_iters, int32_t *accepted, ttx_fit_result *result)
+{
+    return fit_run_dev(h, "ttx_basis_fit_tab_dev", BS_TAB_DEV, npts, phi_dev, nullptr, y_dev, w_dev, opts, loss, lambda, cg_iters, accepted, result);
+}
+extern "C" int ttx_basis_fit_last(const ttx_engine *h, double *ms_jvp, double *ms_core_grad, double *ms_value, double *ms_vector, int64_t *n_jvp, int64_t *n_core_grad, int32_t *mode_ran)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_basis_fit_last: null engine");
+    if (ms_jvp) *ms_jvp = h->fit.ms[FTM_JVP];
+    if (ms_core_grad) *ms_core_grad = h->fit.ms[FTM_CG];
+    if (ms_value) *ms_value = h->fit.ms[FTM_VAL];
+    if (ms_vector) *ms_vector = h->fit.ms[FTM_VEC];
+    if (n_jvp) *n_jvp = h->fit.n_jvp;
+    if (n_core_grad) *n_core_grad = h->fit.n_cg;
+    if (mode_ran) *mode_ran = h->fit.mode;
+    return TTX_OK;
+}
 
 // ---- the largest elements of the resident train (ttx_topk.h)--------------------------------------------------------------------
 namespace {

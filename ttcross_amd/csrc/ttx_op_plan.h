@@ -308,6 +308,74 @@ inline CgPlan cg_plan(int d, const int *n, const int *r, int ncu, BsSrc src, boo
     return p;
 }
 
+// ---- ttx_basis_jvp_batch, ttx_basis_jvp_tab and their _dev forms, the vector operations (ttx_basis_jvp.h) -------------------------
+// break-even of TTX_EVAL_AUTO in flops per call (6 npts sum r0 n r1).  PROVISIONAL, NOT MEASURED: equal to TTX_BS_AUTO_FLOPS until the
+// break-even of the JVP itself is bracketed (profiles/basis_fit_mi355x.txt says what was and what was not measured).
+#define TTX_JV_AUTO_FLOPS TTX_BS_AUTO_FLOPS
+// column tiles of 16 per wave of k_jv_gemm<MR>, the row tiles a workgroup owns and the waves per SIMD its register allocator is held
+// to, from the compiler's resource report (profiles/basis_fit_mi355x.txt): no tier has scratch.  A lane holds two states (16 MR CT
+// registers) and two accumulator sets (16 MH CT).  An a fragment pair from LDS feeds 3 CT MFMAs, so CT = 2 is kept wherever it fits
+// into the 512 registers of one wave per SIMD (MR <= 6; MR = 6 with its rows split over two workgroups); at MR = 7 and 8 the states
+// alone are 224 / 256 registers per column tile pair, two column tiles spill (120 / 324 bytes per lane), and CT = 1 is taken
+TTX_OP_HD constexpr int jv_ct(int MR) { return MR <= 1 ? 4 : MR <= 6 ? 2 : 1; }
+TTX_OP_HD constexpr int jv_waves(int MR) { return MR <= 2 ? 2 : 1; }
+// row tiles of 16 a workgroup owns: all MR up to 5; above, all rows spill even with one column tile, so the rows go to two workgroups
+TTX_OP_HD constexpr int jv_mh(int MR) { return MR <= 5 ? MR : MR == 6 ? 3 : 4; }
+// two buffers of two panel images (U's and V's) of a workgroup's rows
+TTX_OP_HD size_t jv_gemm_lds(int q0, int MR) { return 2 * bs_gemm_lds(std::min(q0, 16 * jv_mh(MR))); }
+// ttx_cores_dot: the buffer is cut into TTX_DOT_SEGS segments of dot_seg(tot) elements, a multiple of 256
+#define TTX_DOT_SEGS 256
+inline long long dot_seg(long long tot) { return 256 * ((tot + 65535) / 65536); }
+
+struct JvStep { int tier = 1, tp = 256, gy = 1; OpLds lds; };           // k_jv_gemm<tier> of a 0-based mode: 16 tier >= max(r0, r1), tp points per workgroup, gy row groups
+struct JvPlan {
+    BsRefusal refusal = BS_OK;
+    int rmax = 1, eff = TTX_EVAL_EXACT, ldx = 4, ncu = 0;
+    std::vector<size_t> off;                // where a mode's rows start in a point's row of the caller's table
+    std::vector<size_t> voff;               // where a mode's block starts in the packed direction
+    size_t sumn = 0, nmax = 1, chunk = 0, row = 0, vsize = 0;                   // row: doubles per point of the input; vsize: doubles of the packed direction
+    double flops = 0.0;
+    size_t ystr = 0;                        // from a point's X row to its Y row in a state buffer: chunk ldx doubles
+    size_t b_xa = 0, b_xb = 0, b_btab = 0, b_x = 0, b_out = 0, b_v = 0;         // bytes of SC_*; 0: the call does not use the slot
+    size_t exact_lds = 0;                   // k_jv_exact: per wave x and y
+    std::vector<JvStep> step;
+    int g_exact(int c) const { return wave_grid(c, ncu); }
+    int g_gemm(int i, int c) const { return (c + step[i].tp - 1) / step[i].tp; }
+};
+// n[0 .. d-1], r[0 .. d]; chunk: TTX_BASIS_CHUNK or the default; host_v: the direction is the caller's host array
+inline JvPlan jv_plan(int d, const int *n, const int *r, int ncu, BsSrc src, bool host_v, int64_t npts, int mode, size_t chunk)
+{
+    const bool tab = src == BS_TAB_HOST || src == BS_TAB_DEV, dev = src == BS_X_DEV || src == BS_TAB_DEV;
+    JvPlan p;
+    p.rmax = *std::max_element(r, r + d + 1); p.ncu = ncu;
+    if (p.rmax > 128) { p.refusal = BS_RANK; return p; }
+    if (r[0] != 1 || r[d] != 1) { p.refusal = BS_BOUNDARY; return p; }
+    double w = 0.0;
+    p.off.resize(d); p.voff.resize(d); p.step.resize(d);
+    for (int k = 0; k < d; k++) {
+        w += (double)r[k] * n[k] * r[k + 1];
+        p.off[k] = p.sumn; p.sumn += (size_t)n[k]; p.nmax = std::max(p.nmax, (size_t)n[k]);
+        p.voff[k] = p.vsize; p.vsize += (size_t)r[k] * n[k] * r[k + 1];
+        JvStep &s = p.step[k];
+        s.tier = (std::max(r[k], r[k + 1]) + 15) / 16; s.tp = 64 * jv_ct(s.tier); s.lds = op_lds(jv_gemm_lds(r[k], s.tier));
+        s.gy = (std::min((r[k] + 15) / 16, s.tier) + jv_mh(s.tier) - 1) / jv_mh(s.tier);                // row groups that hold rows of this mode
+    }
+    p.flops = 6.0 * (double)npts * w;
+    p.eff = op_mode_eff(mode, p.flops, TTX_JV_AUTO_FLOPS);
+    p.ldx = op_ldx(d, r);
+    p.chunk = std::min<size_t>(chunk, (size_t)std::max<int64_t>(npts, 0));
+    if (src == BS_TAB_HOST) p.chunk = std::min(p.chunk, std::max<size_t>(1, ((size_t)1 << 25) / p.sumn));     // the staged rows of the caller's table
+    p.row = tab ? p.sumn : (size_t)d;
+    p.ystr = p.chunk * p.ldx;
+    if (!p.chunk) return p;                                                     // an empty call reserves and launches nothing
+    p.b_xa = p.b_xb = sizeof(double) * 2 * p.ystr;
+    if (!tab) p.b_btab = sizeof(double) * p.chunk * p.nmax;
+    if (!dev) { p.b_x = sizeof(double) * p.chunk * p.row; p.b_out = sizeof(double) * 2 * p.chunk; }         // val, then dval
+    if (host_v) p.b_v = sizeof(double) * p.vsize;
+    p.exact_lds = 4 * sizeof(double) * 2 * (size_t)p.ldx;
+    return p;
+}
+
 // ---- ttx_topk (ttx_topk.h) -----------------------------------------------------------------------------------------------------------
 #define TTX_TK_KMAX 4096            // largest K
 #define TTX_TK_SHEET (1 << 24)      // largest sheet K max n_k

@@ -919,6 +919,79 @@ def run_coregrad(argv, device=0, repeats=5, tt=None, basis=None, host_npts=1000)
     return tt, x, (val, G), res
 
 
+def run_fit(argv, device=0, repeats=3, tt=None, basis=None, max_iter=4, cg_max=10):
+    """fit WORKLOAD NPTS [MODE] [MAX_ITER] [CG_MAX]: the workloads and modes of the basis sub-command.  Takes the workload's train, evaluates it at NPTS
+    seeded points (the targets), perturbs every entry of every core by up to 1 % (seeded) and fits it back with TTCross.fit on device
+    tensors (max_iter iterations of at most cg_max CG passes).  Prints one JSON line: the history, the split of fit_last, the
+    milliseconds per Gauss-Newton iteration, and -- in the same session, on the same points -- the medians of basis_batch,
+    basis_grad_batch, basis_core_grad and basis_jvp (by flops the JVP is 3 value chains; the backward pass of basis_grad_batch is 2,
+    with the same two accumulator sets)."""
+    import json
+    import time
+    import torch
+    torch.cuda.init()          # a torch that brings its own HIP runtime must initialise its device before the engine's library does
+    workload, npts = argv[0], int(float(argv[1]))
+    mode = argv[2] if len(argv) > 2 else "auto"
+    max_iter = int(argv[3]) if len(argv) > 3 else max_iter
+    cg_max = int(argv[4]) if len(argv) > 4 else cg_max
+    if tt is None:
+        tt, basis = basis_train(workload, device=device)
+    if basis is None:
+        basis = [("linear", np.linspace(0.0, 1.0, int(nk))) if nk > 1 else ("cos", 0.0, 1.0) for nk in tt._n]
+        lo, hi = 0.0, 1.0
+    else:
+        lo, hi = basis[1], basis[2]
+    dev = torch.device("cuda", device)
+    g = torch.Generator(device=dev)
+    g.manual_seed(20240607)
+    x = (lo + (hi - lo) * torch.rand((npts, tt.d), dtype=torch.float64, device=dev, generator=g)).contiguous()
+    total = int(tt.core_offsets()[-1])
+    truth = tt.cores_get(torch.empty(total, dtype=torch.float64, device=dev))
+    v = torch.randn(total, dtype=torch.float64, device=dev, generator=g).contiguous()
+    c = torch.randn(npts, dtype=torch.float64, device=dev, generator=g).contiguous()
+    torch.cuda.synchronize(dev)
+
+    def timed(call):
+        out = call()                                # warm-up
+        ms = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            out = call()                            # synchronises before it returns
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return out, float(np.median(ms))
+
+    # the values of some workloads' trains are tiny at real points (their squares underflow): the first core is scaled so that the
+    # largest value at the points is 1, here and in `truth`; the train is put back as it was found at the end
+    found = truth.clone()
+    scale = 1.0 / float(tt.basis_batch(x, basis, mode).abs().max().item())
+    truth[:int(tt.core_offsets()[1])] *= scale
+    torch.cuda.synchronize(dev)
+    tt.cores_set(truth)
+    (_, dval), ms_jvp = timed(lambda: tt.basis_jvp(x, basis, v, mode))
+    ran = tt.basis_jvp_last()["mode"]
+    y, ms_val = timed(lambda: tt.basis_batch(x, basis, ran))
+    _, ms_bg = timed(lambda: tt.basis_grad_batch(x, basis, ran))
+    bg = tt.basis_grad_last()
+    _, ms_cg = timed(lambda: tt.basis_core_grad(x, basis, c, ran))
+    start = (truth * (1.0 + 0.01 * (2.0 * torch.rand(total, dtype=torch.float64, device=dev, generator=g) - 1.0))).contiguous()
+    torch.cuda.synchronize(dev)
+    tt.cores_set(start)
+    t0 = time.perf_counter()
+    h = tt.fit(x, basis, y, None, mode=ran, max_iter=max_iter, cg_max=cg_max, lambda0=1e-2, cg_tol=1e-3)
+    ms_fit = (time.perf_counter() - t0) * 1e3
+    last = tt.fit_last()
+    tt.cores_set(found)                             # the workload's train is left as it was found
+    res = dict(workload=workload, npts=npts, mode_asked=mode, mode=last["mode"], d=tt.d, max_rank=int(tt.ranks().max()), core_elements=total, scale=scale,
+               loss=[float(t) for t in h["loss"]], lambda_=[float(t) for t in h["lambda_"]], cg_iters=[int(t) for t in h["cg_iters"]],
+               accepted=[int(t) for t in h["accepted"]], iters=h["iters"], stop=h["stop"], ms_fit=ms_fit, ms_per_iteration=ms_fit / max(h["iters"], 1),
+               ms_fit_jvp=last["ms_jvp"], ms_fit_core_grad=last["ms_core_grad"], ms_fit_value=last["ms_value"], ms_fit_vector=last["ms_vector"],
+               n_jvp=last["n_jvp"], n_core_grad=last["n_core_grad"], ms_basis_jvp=ms_jvp, ms_basis_batch=ms_val, ms_basis_grad=ms_bg,
+               ms_basis_grad_back=bg["ms_back"], ms_basis_core_grad=ms_cg, jvp_to_value=ms_jvp / ms_val, jvp_to_grad_back=ms_jvp / max(bg["ms_back"], 1e-300),
+               nan=int(torch.isnan(dval).sum().item()))
+    print(json.dumps(res))
+    return tt, h, res
+
+
 def sample_host(tt, u, w=None):
     """what a user does without ttx_sample: every core to the host with core(k), then the conditional marginals walked in
     numpy from the last mode to the first.  Returns (ind, logq, val) of the definition in include/ttx.h, in numpy's own
@@ -1532,6 +1605,8 @@ if __name__ == "__main__":
         run_basisgrad(sys.argv[2:])
     elif sys.argv[1] == "coregrad":
         run_coregrad(sys.argv[2:])
+    elif sys.argv[1] == "fit":
+        run_fit(sys.argv[2:])
     elif sys.argv[1] == "chf":
         run_chf(sys.argv[2:])
     elif sys.argv[1] == "pdf":

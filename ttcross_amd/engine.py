@@ -67,6 +67,19 @@ class _Basis(ctypes.Structure):      # ttx_basis
     _fields_ = [("kind", c_int32), ("flags", c_int32), ("a", c_double), ("b", c_double), ("nodes", POINTER(c_double))]
 
 
+class _FitOpts(ctypes.Structure):    # ttx_fit_opts
+    _fields_ = [("max_iter", c_int32), ("cg_max", c_int32), ("max_reject", c_int32), ("mode", c_int32), ("lambda0", c_double),
+                ("lambda_down", c_double), ("lambda_up", c_double), ("cg_tol", c_double), ("loss_tol", c_double)]
+
+
+class _FitResult(ctypes.Structure):  # ttx_fit_result
+    _fields_ = [("iters", c_int32), ("stop", c_int32)]
+
+
+FIT_STOPS = {1: "max_iter", 2: "loss_tol", 3: "zero_gradient", 4: "max_reject", 5: "non_finite"}
+FIT_DEFAULTS = dict(max_iter=20, cg_max=40, max_reject=8, mode="auto", lambda0=1.0, lambda_down=0.3, lambda_up=4.0, cg_tol=1e-2, loss_tol=0.0)
+
+
 class SweepRec(ctypes.Structure):
     _fields_ = [("it", c_int32), ("dir", c_int32), ("erank", c_double), ("neval", c_int64), ("val", c_double),
                 ("amax", c_double), ("pivotmax", c_double), ("pivotmin", c_double), ("seconds", c_double)]
@@ -148,6 +161,24 @@ def load_library():
                                            POINTER(c_int64)]
     L.ttx_cores_axpy.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double)]
     L.ttx_cores_axpy_dev.argtypes = [c_void_p, POINTER(c_double), c_void_p]
+    L.ttx_basis_jvp_batch.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(_Basis), POINTER(c_double), POINTER(c_double), POINTER(c_double), c_int32]
+    L.ttx_basis_jvp_batch_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(_Basis), c_void_p, c_void_p, c_void_p, c_int32]
+    L.ttx_basis_jvp_tab.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), c_int32]
+    L.ttx_basis_jvp_tab_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32]
+    L.ttx_basis_jvp_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
+    L.ttx_cores_dot.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double)]
+    L.ttx_cores_dot_dev.argtypes = [c_void_p, c_void_p, c_void_p, POINTER(c_double)]
+    L.ttx_cores_axpby_dev.argtypes = [c_void_p, c_double, c_void_p, c_double, c_void_p]
+    L.ttx_cores_get_dev.argtypes = [c_void_p, c_void_p]
+    L.ttx_cores_get.argtypes = [c_void_p, POINTER(c_double)]
+    L.ttx_cores_set.argtypes = [c_void_p, POINTER(c_double)]
+    L.ttx_cores_set_dev.argtypes = [c_void_p, c_void_p]
+    _hist = [POINTER(_FitOpts), POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_int32), POINTER(_FitResult)]
+    L.ttx_basis_fit_batch.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(_Basis), POINTER(c_double), POINTER(c_double)] + _hist
+    L.ttx_basis_fit_batch_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(_Basis), c_void_p, c_void_p] + _hist
+    L.ttx_basis_fit_tab.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_double)] + _hist
+    L.ttx_basis_fit_tab_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p] + _hist
+    L.ttx_basis_fit_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64), POINTER(c_int64), POINTER(c_int32)]
     L.ttx_sample.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
     L.ttx_sample_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(c_double), POINTER(c_int32), c_void_p, c_void_p, c_void_p]
     L.ttx_sample_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
@@ -1291,6 +1322,175 @@ class TTCross:
             g = g.numpy()
         _check(L.ttx_cores_axpy(self._h, _dp(al), _dp(self._core_pack("cores_axpy", g))))
         return self
+
+    # ---- the derivative along a direction in core space, vector operations, the solver (include/ttx.h: ttx_basis_jvp_batch) ----
+    def _flat_dev(self, who, t):
+        """a flat float64 tensor of core_offsets()[-1] numbers on the engine's device, or None for anything else"""
+        if type(t).__module__.split(".")[0] != "torch" or not t.is_cuda:
+            return None
+        import torch
+        total = int(self.core_offsets()[-1])
+        if t.device.index != self.device or t.dtype != torch.float64 or not t.is_contiguous() or t.shape != (total,):
+            raise ValueError(f"{who}: a contiguous float64 tensor of {total} numbers on the engine's device expected")
+        torch.cuda.current_stream(t.device).synchronize()
+        return t
+
+    def _jvp(self, who, host, dev, head, t, cols, v, mode):
+        md = _eval_mode(mode)
+        val = self._dev_pair(who, t, cols)
+        if val is not None:
+            import torch
+            if self._flat_dev(who, v) is None:
+                raise ValueError(f"{who}: with points on the device, V must be a flat float64 tensor on the engine's device")
+            dval = torch.empty_like(val)
+            _check(dev(self._h, t.shape[0], c_void_p(t.data_ptr()), *head, c_void_p(v.data_ptr()), c_void_p(val.data_ptr()), c_void_p(dval.data_ptr()), md))
+            return val, dval
+        if type(t).__module__.split(".")[0] == "torch":
+            t = t.cpu().numpy()
+        if type(v).__module__.split(".")[0] == "torch":
+            v = v.cpu().numpy()
+        ta = np.ascontiguousarray(t, dtype=np.float64)
+        if ta.ndim != 2 or ta.shape[1] != cols:
+            raise ValueError(f"{who}: an array of shape (npts, {cols}) expected")
+        flat = self._core_pack(who, v)
+        val, dval = np.zeros(ta.shape[0]), np.zeros(ta.shape[0])
+        _check(host(self._h, ta.shape[0], _dp(ta), *head, _dp(flat), _dp(val), _dp(dval), md))
+        return val, dval
+
+    def _basis_arr(self, who, basis):
+        if isinstance(basis, (tuple, list)) and basis and isinstance(basis[0], str):
+            basis = [basis] * self.d
+        basis = list(basis)
+        if len(basis) != self.d:
+            raise ValueError(f"{who}: {self.d} basis entries expected (got {len(basis)})")
+        pairs = [_basis_struct(e, self._n[k]) for k, e in enumerate(basis)]
+        return (_Basis * self.d)(*[p[0] for p in pairs]), pairs          # pairs keeps the node arrays alive
+
+    def basis_jvp(self, x, basis, V, mode="auto"):
+        """(val, dval) at real points x (npts, d) (include/ttx.h: ttx_basis_jvp_batch): dval_p = sum_i f_(U_i <- V_i)(x_p), the
+        derivative of f(x_p) along the direction V in core space -- J V, where basis_core_grad is J^T c.  val is basis_batch(x, basis)
+        bit for bit in the mode that ran.  V: a list of blocks of the cores' shapes or a flat array, as cores_axpy takes g; with
+        points on the device, a flat float64 tensor on that device (read in place).  basis_jvp_last() tells what ran."""
+        L = load_library()
+        arr, keep = self._basis_arr("basis_jvp", basis)
+        return self._jvp("basis_jvp", L.ttx_basis_jvp_batch, L.ttx_basis_jvp_batch_dev, (arr,), x, self.d, V, mode)
+
+    def basis_jvp_tab(self, phi, V, mode="auto"):
+        """The same with the caller's own tables (include/ttx.h: ttx_basis_jvp_tab): phi (npts, sum n) in basis_tab's layout."""
+        L = load_library()
+        return self._jvp("basis_jvp_tab", L.ttx_basis_jvp_tab, L.ttx_basis_jvp_tab_dev, (), phi, int(self._n.sum()), V, mode)
+
+    def basis_jvp_last(self):
+        """dict(ms_table, ms_chain, flops, mode) of the last basis_jvp / basis_jvp_tab on this engine (include/ttx.h: ttx_basis_jvp_last)"""
+        mt, mc, fl, md = c_double(), c_double(), c_double(), c_int32()
+        _check(load_library().ttx_basis_jvp_last(self._h, ctypes.byref(mt), ctypes.byref(mc), ctypes.byref(fl), ctypes.byref(md)))
+        names = {v: k for k, v in EVAL_MODES.items()}
+        return dict(ms_table=mt.value, ms_chain=mc.value, flops=fl.value, mode=names.get(md.value))
+
+    def cores_dot(self, a, b):
+        """sum_e a_e * b_e of two packed core-space buffers in the fixed order of include/ttx.h (ttx_cores_dot): lists of blocks or
+        flat host arrays, or two flat float64 tensors on the engine's device (by pointer).  A Python float."""
+        L, out = load_library(), c_double()
+        da, db = self._flat_dev("cores_dot", a), self._flat_dev("cores_dot", b)
+        if (da is None) != (db is None):
+            raise ValueError("cores_dot: both buffers on the host or both on the engine's device")
+        if da is not None:
+            _check(L.ttx_cores_dot_dev(self._h, c_void_p(a.data_ptr()), c_void_p(b.data_ptr()), ctypes.byref(out)))
+            return out.value
+        a, b = (t.numpy() if type(t).__module__.split(".")[0] == "torch" else t for t in (a, b))
+        _check(L.ttx_cores_dot(self._h, _dp(self._core_pack("cores_dot", a)), _dp(self._core_pack("cores_dot", b)), ctypes.byref(out)))
+        return out.value
+
+    def cores_axpby(self, alpha, x, beta, y):
+        """y <- (alpha * x) + (beta * y) on packed core-space buffers (include/ttx.h: ttx_cores_axpby_dev).  Two flat float64 tensors
+        on the engine's device are updated in place on the device (y is returned); host arrays (lists of blocks or flat) give a new
+        flat numpy array by the same three operations."""
+        dx, dy = self._flat_dev("cores_axpby", x), self._flat_dev("cores_axpby", y)
+        if (dx is None) != (dy is None):
+            raise ValueError("cores_axpby: both buffers on the host or both on the engine's device")
+        if dx is not None:
+            _check(load_library().ttx_cores_axpby_dev(self._h, float(alpha), c_void_p(x.data_ptr()), float(beta), c_void_p(y.data_ptr())))
+            return y
+        x, y = (t.numpy() if type(t).__module__.split(".")[0] == "torch" else t for t in (x, y))
+        return (float(alpha) * self._core_pack("cores_axpby", x)) + (float(beta) * self._core_pack("cores_axpby", y))
+
+    def cores_get(self, out=None):
+        """the engine's cores as one packed buffer, bit for bit (include/ttx.h: ttx_cores_get_dev): into the flat float64 device
+        tensor out where one is given (and returned), otherwise a flat numpy array (ttx_cores_get)"""
+        L = load_library()
+        if out is not None:
+            if self._flat_dev("cores_get", out) is None:
+                raise ValueError("cores_get: out must be a flat float64 tensor on the engine's device")
+            _check(L.ttx_cores_get_dev(self._h, c_void_p(out.data_ptr())))
+            return out
+        flat = np.zeros(int(self.core_offsets()[-1]))
+        _check(L.ttx_cores_get(self._h, _dp(flat)))
+        return flat
+
+    def cores_set(self, g):
+        """the engine's cores from a packed buffer of the present ranks, bit for bit (include/ttx.h: ttx_cores_set_dev): a flat float64
+        tensor on the engine's device by pointer; a list of blocks or a flat host array through ttx_cores_set"""
+        L = load_library()
+        if self._flat_dev("cores_set", g) is not None:
+            _check(L.ttx_cores_set_dev(self._h, c_void_p(g.data_ptr())))
+            return self
+        if type(g).__module__.split(".")[0] == "torch":
+            g = g.numpy()
+        _check(L.ttx_cores_set(self._h, _dp(self._core_pack("cores_set", g))))
+        return self
+
+    def _fit(self, who, host, dev, head, t, cols, y, w, opts):
+        o = dict(FIT_DEFAULTS)
+        unknown = set(opts) - set(o)
+        if unknown:
+            raise ValueError(f"{who}: unknown options {sorted(unknown)}")
+        o.update(opts)
+        fo = _FitOpts(int(o["max_iter"]), int(o["cg_max"]), int(o["max_reject"]), _eval_mode(o["mode"]), float(o["lambda0"]), float(o["lambda_down"]),
+                      float(o["lambda_up"]), float(o["cg_tol"]), float(o["loss_tol"]))
+        mi = max(fo.max_iter, 0)
+        loss, lam, cg, acc, res = np.zeros(mi + 1), np.zeros(max(mi, 1)), np.zeros(max(mi, 1), dtype=np.int32), np.zeros(max(mi, 1), dtype=np.int32), _FitResult()
+        tail = (ctypes.byref(fo), _dp(loss), _dp(lam), cg.ctypes.data_as(POINTER(c_int32)), acc.ctypes.data_as(POINTER(c_int32)), ctypes.byref(res))
+        if self._dev_pair(who, t, cols) is not None:
+            import torch
+            for name, a in (("y", y), ("w", w)):
+                if a is None and name == "w":
+                    continue
+                if type(a).__module__.split(".")[0] != "torch" or a.device != t.device or a.dtype != torch.float64 or not a.is_contiguous() or a.shape != (t.shape[0],):
+                    raise ValueError(f"{who}: {name} must be a contiguous float64 tensor of shape (npts,) on the engine's device")
+            torch.cuda.current_stream(t.device).synchronize()
+            _check(dev(self._h, t.shape[0], c_void_p(t.data_ptr()), *head, c_void_p(y.data_ptr()), c_void_p(w.data_ptr()) if w is not None else None, *tail))
+        else:
+            t, y, w = (a.cpu().numpy() if type(a).__module__.split(".")[0] == "torch" else a for a in (t, y, w))
+            ta, ya = np.ascontiguousarray(t, dtype=np.float64), np.ascontiguousarray(y, dtype=np.float64)
+            wa = None if w is None else np.ascontiguousarray(w, dtype=np.float64)
+            if ta.ndim != 2 or ta.shape[1] != cols or ya.shape != (ta.shape[0],) or (wa is not None and wa.shape != ya.shape):
+                raise ValueError(f"{who}: an array of shape (npts, {cols}), npts targets and (or no) npts weights expected")
+            _check(host(self._h, ta.shape[0], _dp(ta), *head, _dp(ya), _dp(wa) if wa is not None else None, *tail))
+        return dict(loss=loss, lambda_=lam[:mi], cg_iters=cg[:mi], accepted=acc[:mi], iters=res.iters, stop=FIT_STOPS.get(res.stop, res.stop))
+
+    def fit(self, x, basis, y, w=None, **opts):
+        """Fit the resident train to data in place (include/ttx.h: ttx_basis_fit_batch): minimise 1/2 sum_p w_p (f(x_p) - y_p)^2 over
+        all cores by a matrix-free Levenberg-Marquardt iteration on the device.  x (npts, d), basis as for basis_batch, y (npts,),
+        w (npts,) or None for all ones; host arrays, or float64 tensors on the engine's device (by pointer).  opts: max_iter, cg_max,
+        max_reject, mode, lambda0, lambda_down, lambda_up, cg_tol, loss_tol (FIT_DEFAULTS).  Returns the history: dict(loss
+        (max_iter + 1), lambda_, cg_iters, accepted (max_iter each), iters, stop).  fit_last() reads the figures."""
+        L = load_library()
+        arr, keep = self._basis_arr("fit", basis)
+        return self._fit("fit", L.ttx_basis_fit_batch, L.ttx_basis_fit_batch_dev, (arr,), x, self.d, y, w, opts)
+
+    def fit_tab(self, phi, y, w=None, **opts):
+        """The same with the caller's own tables (include/ttx.h: ttx_basis_fit_tab): phi (npts, sum n) in basis_tab's layout."""
+        L = load_library()
+        return self._fit("fit_tab", L.ttx_basis_fit_tab, L.ttx_basis_fit_tab_dev, (), phi, int(self._n.sum()), y, w, opts)
+
+    def fit_last(self):
+        """dict(ms_jvp, ms_core_grad, ms_value, ms_vector, n_jvp, n_core_grad, mode) of the last fit / fit_tab on this engine
+        (include/ttx.h: ttx_basis_fit_last)"""
+        mj, mc, mv, mx, nj, nc, md = c_double(), c_double(), c_double(), c_double(), c_int64(), c_int64(), c_int32()
+        _check(load_library().ttx_basis_fit_last(self._h, ctypes.byref(mj), ctypes.byref(mc), ctypes.byref(mv), ctypes.byref(mx), ctypes.byref(nj),
+                                                 ctypes.byref(nc), ctypes.byref(md)))
+        names = {v: k for k, v in EVAL_MODES.items()}
+        return dict(ms_jvp=mj.value, ms_core_grad=mc.value, ms_value=mv.value, ms_vector=mx.value, n_jvp=nj.value, n_core_grad=nc.value, mode=names.get(md.value))
 
     # ---- samples from the resident train (include/ttx.h: ttx_sample and its three siblings) --------------
     # the outputs of the index samplers and of the real samplers: name, a row of d per sample (else one number), dtype, always allocated
