@@ -563,8 +563,8 @@ int ttx_basis_grad_last     (const ttx_engine *h, double *ms_table, double *ms_b
  * that is derived from the cores -- every operation (evaluation, norm, quadrature, sampling tables, Gram matrices) rebuilds what it
  * needs from the cores it finds, which is why ttx_ort and ttx_svd drop nothing either -- so nothing stale survives an update.  Refusals
  * as above, and a NULL alpha or g.
- * Open: the gradient of the normaliser Z of the squared density (maximum likelihood for ttx_sample_sq_real needs it as well),
- * second derivatives, ranks above 128, the Fortran layer.  The Gauss-Newton solver is ttx_basis_fit_batch, below.
+ * Open: second derivatives, ranks above 128, the Fortran layer.  The Gauss-Newton solver is ttx_basis_fit_batch, below; the gradient
+ * of the normaliser Z of the squared density (maximum likelihood for ttx_sample_sq_real) is ttx_sq_lognorm_grad, further below.
  * Added without a new ttx_version: look the symbols up. */
 int ttx_basis_core_grad_batch    (ttx_engine *h, int64_t npts, const double *x /* [npts][d] */, const ttx_basis *basis /* [d] */, const double *c /* [npts] */, double *val, double *g, int32_t accumulate, int32_t mode);
 int ttx_basis_core_grad_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, const double *c_dev, double *val_dev, double *g_dev, int32_t accumulate, int32_t mode);
@@ -627,7 +627,8 @@ int ttx_cores_axpy_dev(ttx_engine *h, const double *alpha /* [d], host */, const
  * negative tolerances); work space that cannot be allocated is TTX_EHIP, nothing faults.  A refused call leaves the cores untouched.
  * ttx_basis_fit_last: of the last fit on this engine, the milliseconds in JVP, core-gradient, value and vector launches, the counts of
  * JVP and core-gradient calls, the mode the last JVP ran in (-1: none).
- * Open: an ALS sweep, rank adaptation during the fit, a preconditioner for CG, the gradient of the normaliser Z, ranks above 128.
+ * Open: an ALS sweep, rank adaptation during the fit, a preconditioner for CG, ranks above 128.  (Maximum likelihood for the squared
+ * density: ttx_sq_nll_batch, below.)
  * Added without a new ttx_version: look the symbols up. */
 typedef struct { int32_t max_iter, cg_max, max_reject, mode; double lambda0, lambda_down, lambda_up, cg_tol, loss_tol; } ttx_fit_opts;
 typedef struct { int32_t iters, stop; /* 1 max_iter, 2 loss_tol, 3 zero gradient, 4 max_reject consecutive rejections, 5 non-finite loss at entry */ } ttx_fit_result;
@@ -652,6 +653,62 @@ int ttx_basis_fit_tab      (ttx_engine *h, int64_t npts, const double *phi, cons
 int ttx_basis_fit_tab_dev  (ttx_engine *h, int64_t npts, const double *phi_dev, const double *y_dev, const double *w_dev, const ttx_fit_opts *opts,
                             double *loss, double *lambda, int32_t *cg_iters, int32_t *accepted, ttx_fit_result *result);
 int ttx_basis_fit_last     (const ttx_engine *h, double *ms_jvp, double *ms_core_grad, double *ms_value, double *ms_vector, int64_t *n_jvp, int64_t *n_core_grad, int32_t *mode_ran);
+
+/* The normaliser of the squared density q(x) = (f(x)^2 + gamma) / (Z + gamma V), its logarithm and its gradient with respect to the
+ * cores, on the device (ttcross_amd/csrc/ttx_sq_norm.h): the half of a maximum-likelihood step that ttx_basis_core_grad_batch does not
+ * give.  Z = <f, f>_M = sum T(i_1 .. i_d) M_1(i_1, i'_1) .. M_d(i_d, i'_d) T(i'_1 .. i'_d) with one symmetric tridiagonal matrix per mode:
+ *   md[k][0 .. n_k-1] its diagonal, mo[k][i] = M_k(i, i+1), i = 0 .. n_k-2; a NULL mo or a NULL mo[k] means a diagonal matrix.  Host rows.
+ * That covers the diagonal weights of ttx_sample_sq, the hat functions' mass matrix of ttx_sample_sq_real, a held mode (phi phi^T of its
+ * two adjacent hat values) and the identity of an orthonormal basis.  gvol >= 0 is the caller's gamma * V.
+ * Definition (numpy restates it: tests/sq_norm_ref.py).  U_k(a, i, b) is core k; multiply and add are always separate; every sum
+ * starts from 0.0 and runs over ascending indices.
+ *   V_k(a, i, b) = ((0.0 + mo(i-1) * U_k(a, i-1, b)) + md(i) * U_k(a, i, b)) + mo(i) * U_k(a, i+1, b): the terms i-1, i, i+1 in this order,
+ *                  a term that does not exist (i = 0, i = n-1, a diagonal matrix) is left out
+ *   Right chain, k = d .. 2, from PR_d = [1], eR(d) = 0:
+ *       Y(a', i, b) = sum_b' PR_k(b, b') * V_k(a', i, b');   p_i(a, a') = sum_b U_k(a, i, b) * Y(a', i, b);   PR_(k-1) = sum_i p_i
+ *   Left chain, k = 1 .. d, from PL_0 = [1], eL(0) = 0:
+ *       W_k(a, i, b') = sum_a' PL_(k-1)(a, a') * V_k(a', i, b');   p_i(b, b') = sum_a U_k(a, i, b) * W_k(a, i, b');   PL_k = sum_i p_i
+ *   (every p_i is summed on its own from 0.0, then the p_i are added over ascending i from 0.0: a step is as wide as the core is long)
+ *   After every step the new matrix is multiplied by 2^-ex, ex the exponent that takes its largest entry in magnitude into [0.5, 1)
+ *   (frexp; ex = 0 where that entry is 0 or not finite: ttx_sample_sq's rule), and eR(k-1) = eR(k) + ex, eL(k) = eL(k-1) + ex.
+ *   z_mant = PL_d, z_exp = eL(d):  Z = z_mant 2^z_exp.   den = z_mant + ldexp(gvol, -z_exp);   logz = z_exp * ln 2 + log(den) = log(Z + gvol).
+ *   D_k(a, i, b) = sum_b' W_k(a, i, b') * PR_k(b, b');   s_k = ldexp((2 * coef) / den, eL(k-1) + eR(k) - z_exp);
+ *   G_k(a, i, b) = G0_k(a, i, b) + s_k * D_k(a, i, b)  =  G0_k + (coef / (Z + gvol)) dZ/dU_k,  formed from the scaled quantities: nothing
+ *   overflows where Z does.  G0 is 0.0 (accumulate == 0) or the contents of g on entry (accumulate == 1); g in the packed layout of
+ *   ttx_basis_core_grad_batch.  coef = 1 gives the gradient of log(Z + gvol).
+ * Euler: <dZ/dU_k, U_k> = 2 Z for every k.  For a block E of core k's shape <dZ/dU_k, E> = 2 <T, T_(U_k <- E)>_M.
+ *   mode : TTX_EVAL_EXACT  z_mant, z_exp and every G_k bit-identical to the restatement
+ *          TTX_EVAL_MFMA   the assembly D_k = W_k PR_k^T of all cores on the fp64 matrix cores, one launch; the chains are EXACT's, so
+ *                          z_mant, z_exp and logz are the same bits and G equals EXACT to rounding (sq_norm_ref.py derives the
+ *                          allowance); no floating-point atomics, a call repeats bit for bit
+ *          TTX_EVAL_AUTO   by the flops of the call, sum 4 r0^2 n r1 + 6 r0 n r1^2, against a PROVISIONAL break-even
+ * No special cases: a Z + gvol that is zero, negative or not finite gives what the arithmetic gives; a NaN core gives NaN; nothing
+ * faults.  Work space: one buffer of the size of g (every W_k), sum r_k^2 doubles (every PR_k), one core (Y), max n_k r^2 doubles (the p_i of a step).
+ * Refusals: those of ttx_cores_axpy (no train: TTX_ESTATE; a multi-process engine; ranks above 128; boundary ranks; a NULL g), a NULL md
+ * or md[k], a non-finite entry of md or mo, gvol negative or not finite, coef not finite, accumulate not 0 or 1, an unknown mode.  A
+ * refused call leaves g untouched.  z_mant, z_exp and logz may be NULL.
+ * ttx_sq_lognorm_grad_last: of the last call on this engine, the milliseconds of the right chain, the left chain and the assembly, the
+ * flops and the mode that ran (-1: none yet).
+ *
+ * ttx_sq_nll_batch: the negative log-likelihood of weighted points under q and its gradient with respect to the cores, in one call.
+ *   val_p = f(x_p): ttx_basis_batch's value chain, bit for bit (a value chain of its own: c depends on val, and the core gradient's
+ *           backward pass forms val only together with the states its forward pass consumes, so the call costs one extra value chain);
+ *   c_p = -((2 * w_p) * val_p) / (val_p * val_p + gamma);   l_p = log(val_p * val_p + gamma);   w NULL: all ones;
+ *   S = sum_p w_p * l_p and Wsum = sum_p w_p * 1.0 by ttx_cores_dot's rule with tot = npts;
+ *   G = J^T c (ttx_basis_core_grad_batch_dev, accumulate 0), then ttx_sq_lognorm_grad_dev with coef = Wsum and accumulate = 1;
+ *   nll = -S + Wsum * logz.
+ * val may be NULL.  A point with val^2 + gamma = 0 makes nll +inf and G NaN by the arithmetic: an optimiser rejects the step.
+ * npts == 0 gives nll = 0 * logz and G = 0 * D.  Each of the three parts takes mode on its own (AUTO by its own flops).
+ * Refusals: those of ttx_basis_core_grad_batch and of ttx_sq_lognorm_grad, a NULL nll, g or basis, a negative or non-finite gamma,
+ * and in the host form a negative or non-finite w.  Open: a table form, per-call reuse of the chains in a line search, a Hessian of Z,
+ * ranks above 128, the Fortran layer.  Added without a new ttx_version: look the symbols up. */
+int ttx_sq_lognorm_grad     (ttx_engine *h, const double *const *md, const double *const *mo, double gvol, double coef, double *g, int32_t accumulate, int32_t mode, double *z_mant, int64_t *z_exp, double *logz);
+int ttx_sq_lognorm_grad_dev (ttx_engine *h, const double *const *md, const double *const *mo, double gvol, double coef, double *g_dev, int32_t accumulate, int32_t mode, double *z_mant, int64_t *z_exp, double *logz);
+int ttx_sq_lognorm_grad_last(const ttx_engine *h, double *ms_right, double *ms_left, double *ms_asm, double *flops, int32_t *mode_ran);
+int ttx_sq_nll_batch    (ttx_engine *h, int64_t npts, const double *x /* [npts][d] */, const ttx_basis *basis /* [d] */, const double *w, double gamma, const double *const *md, const double *const *mo,
+                         double gvol, int32_t mode, double *nll, double *logz, double *val, double *g);
+int ttx_sq_nll_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, const double *w_dev, double gamma, const double *const *md, const double *const *mo,
+                         double gvol, int32_t mode, double *nll, double *logz, double *val_dev, double *g_dev);
 
 /* Samples drawn from the resident train by sequential conditional sampling, on the device (ttcross_amd/csrc/ttx_sample.h).
  * Modes are 1-based, G_k is core k, r_0 = r_d = 1.

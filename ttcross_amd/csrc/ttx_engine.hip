@@ -53,6 +53,7 @@
 #include "ttx_basis.h"
 #include "ttx_basis_grad.h"
 #include "ttx_basis_core_grad.h"
+#include "ttx_sq_norm.h"
 #include "ttx_basis_jvp.h"
 #include "ttx_fit_plan.h"
 #include "ttx_algebra.h"
@@ -149,6 +150,7 @@ enum {
     SC_CGG, SC_CGP,                     // ttx_basis_core_grad_batch: the packed gradient of a host caller (also ttx_cores_axpy's), the partial blocks of a core's segments (its states X_i go to SC_GST, L to SC_XA / SC_XB)
     SC_JVV, SC_VDP, SC_VIN,             // ttx_basis_jvp_batch: the packed direction of a host caller; ttx_cores_dot: the segment sums, the two buffers of a host caller
     SC_FITV, SC_FITP,                   // ttx_basis_fit_batch: the core-space work vectors and the snapshot; the point vectors, then the uploaded inputs of a host caller
+    SC_SQNW, SC_SQNP, SC_SQNY, SC_SQNPT, // ttx_sq_lognorm_grad: the W store; the PR store, the two PL and the exponents; Y of a right step and the per-index partial matrices of a step; ttx_sq_nll_batch: the point vectors, then the uploaded inputs of a host caller
     SC_NBUF
 };
 struct EvBuf { void *p = nullptr; size_t bytes = 0; };
@@ -210,6 +212,8 @@ struct CgLast { double ms[4] = {0.0, 0.0, 0.0, 0.0}, flops = 0.0; int mode = -1;
 
 struct JvLast { double ms[2] = {0.0, 0.0}, flops = 0.0; int mode = -1; };      // ttx_basis_jvp_batch / ttx_basis_jvp_tab: table launches, chain launches
 struct FitLast { double ms[4] = {0.0, 0.0, 0.0, 0.0}; int64_t n_jvp = 0, n_cg = 0; int mode = -1; };      // ttx_basis_fit_batch / _tab: JVP, core-gradient, value, vector launches
+
+struct SqnLast { double ms[3] = {0.0, 0.0, 0.0}, flops = 0.0; int mode = -1; };               // ttx_sq_lognorm_grad: right chain, left chain, assembly
 
 struct DevFun;                          // a loaded device integrand (TTX_FUN_DEVICE), defined with slot_eval
 struct TrainFun;                        // the operands and the combiner of TTX_FUN_TRAINS, defined with slot_eval
@@ -328,6 +332,7 @@ struct ttx_engine {
     CgLast cg;
     JvLast jv;
     FitLast fit;
+    SqnLast sqn;
     std::vector<hipEvent_t> op_ev;                      // OpMarks' events: ttx_lincomb_round, the squared samplers, the basis evaluations
 };
 
@@ -4676,6 +4681,188 @@ extern "C" int ttx_basis_fit_last(const ttx_engine *h, double *ms_jvp, double *m
     if (n_core_grad) *n_core_grad = h->fit.n_cg;
     if (mode_ran) *mode_ran = h->fit.mode;
     return TTX_OK;
+}
+
+// ---- the normaliser of the squared density and its gradient (ttx_sq_norm.h) ------------------------------------------------------
+enum { SQM_RIGHT, SQM_LEFT, SQM_ASM };
+// what ttx_sq_lognorm_grad refuses of md, mo, gvol, coef, accumulate and mode, asked before anything is touched
+static int sqn_check(ttx_engine *h, const char *who, const double *const *md, const double *const *mo, double gvol, double coef, int32_t accumulate, int32_t mode)
+{
+    if (!md) return fail(TTX_EINVAL, "%s: null md", who);
+    if (!op_mode_known(mode)) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    if (accumulate != 0 && accumulate != 1) return fail(TTX_EINVAL, "%s: accumulate is 0 or 1 (got %d)", who, accumulate);
+    if (!(gvol >= 0.0) || !std::isfinite(gvol)) return fail(TTX_EINVAL, "%s: gvol is negative or not finite", who);
+    if (!std::isfinite(coef)) return fail(TTX_EINVAL, "%s: coef is not finite", who);
+    for (int k = 1; k <= h->d; k++) {
+        if (!md[k - 1]) return fail(TTX_EINVAL, "%s: null md[%d]", who, k - 1);
+        for (int i = 0; i < h->n1[k]; i++) if (!std::isfinite(md[k - 1][i])) return fail(TTX_EINVAL, "%s: md[%d][%d] is not finite", who, k - 1, i);
+        if (mo && mo[k - 1]) for (int i = 0; i + 1 < h->n1[k]; i++) if (!std::isfinite(mo[k - 1][i])) return fail(TTX_EINVAL, "%s: mo[%d][%d] is not finite", who, k - 1, i);
+    }
+    return TTX_OK;
+}
+// g: the packed gradient, on the host unless dev; z_mant, z_exp, logz may be null
+static int sqn_run(ttx_engine *h, const char *who, const double *const *md, const double *const *mo, double gvol, double coef, double *g, int32_t accumulate, int32_t mode,
+                   bool dev, double *z_mant, int64_t *z_exp, double *logz)
+{
+    int rc = tt_prepare(h, who);
+    if (rc) return rc;
+    if (!g) return fail(TTX_EINVAL, "%s: null argument", who);
+    if ((rc = cg_check_train(h, who)) || (rc = sqn_check(h, who, md, mo, gvol, coef, accumulate, mode))) return rc;
+    const int d = h->d;
+    const std::vector<int32_t> &r = h->rfinal;
+    const SqnPlan pl = sqn_plan(d, h->n1.data() + 1, r.data(), !dev, mode);
+    if (pl.refusal == BS_RANK) return fail(TTX_EINVAL, "%s: ranks up to 128 only (got %d)", who, pl.rmax);
+    if (pl.refusal == BS_BOUNDARY) return fail(TTX_EINVAL, "%s: boundary ranks are not 1", who);
+    h->sqn = SqnLast();
+    h->sqn.flops = pl.flops; h->sqn.mode = pl.eff;
+    // the diagonals and the off-diagonals of all modes, one device block each; a mode without an off-diagonal gets a null pointer
+    std::vector<double> hd(pl.nsum), ho(pl.nsum, 0.0);
+    for (int k = 0; k < d; k++) {
+        std::copy(md[k], md[k] + h->n1[k + 1], hd.begin() + pl.noff[k]);
+        if (mo && mo[k] && h->n1[k + 1] > 1) std::copy(mo[k], mo[k] + h->n1[k + 1] - 1, ho.begin() + pl.noff[k]);
+    }
+    OpMeta meta(h->meta_host);
+    const size_t o_d = meta.put(hd), o_o = meta.put(ho);
+    char *dm = nullptr;
+    if ((rc = meta.upload(h, SC_META, &dm))) return rc;
+    const double *Dd = (const double *)(dm + o_d), *Do = (const double *)(dm + o_o);
+    if ((rc = buf_reserve(h, {{SC_SQNW, pl.b_w}, {SC_SQNP, pl.b_pr + pl.b_pl + pl.b_ex}, {SC_SQNY, pl.b_y + pl.b_part}, {SC_CGG, pl.b_g}}))) return rc;
+    double *W = buf<double>(h, SC_SQNW), *PR = buf<double>(h, SC_SQNP), *PL[2] = {PR + pl.proff[d + 1], PR + pl.proff[d + 1] + (size_t)pl.rmax * pl.rmax};
+    double *Y = buf<double>(h, SC_SQNY), *Part = Y + pl.b_y / sizeof(double);
+    int *eL = (int *)(PL[1] + (size_t)pl.rmax * pl.rmax), *eR = eL + d + 1;
+    const int RM = h->RM;
+    const size_t SS = h->P.SS;
+    OpMarks marks(h->op_ev);
+    if ((rc = marks.mark(h->stream, OpMarks::DISCARD))) return rc;
+    hipLaunchKernelGGL(k_sqn_init, dim3(1), dim3(64), 0, h->stream, PL[0], PR + pl.proff[d], eL, eR + d);
+    for (int k = d; k >= 2; k--) {                                              // right chain: PR_(k-1) from PR_k
+        const int r0 = r[k - 1], n = h->n1[k], r1 = r[k];
+        const double *U = core_dev(h, k), *mdk = Dd + pl.noff[k - 1], *mok = (mo && mo[k - 1]) ? Do + pl.noff[k - 1] : nullptr;
+        double *Pn = PR + pl.proff[k - 1];
+        hipLaunchKernelGGL(k_sqn_w, dim3((unsigned)(n * r0)), dim3(128), 0, h->stream, U, RM, SS, (size_t)1, r1, n, mdk, mok, (const double *)(PR + pl.proff[k]), Y);
+        hipLaunchKernelGGL(k_sqn_p, dim3((r0 + 15) / 16, (r0 + 15) / 16, n), dim3(256), 0, h->stream, U, RM, SS, (size_t)1, r1, r0, (const double *)Y, n, Part);
+        hipLaunchKernelGGL(k_sqn_pow2, dim3(1), dim3(1024), 0, h->stream, r0 * r0, n, (const double *)Part, Pn, (const int *)(eR + k), eR + k - 1);
+    }
+    if ((rc = marks.mark(h->stream, SQM_RIGHT))) return rc;
+    for (int k = 1; k <= d; k++) {                                              // left chain: W_k and PL_k from PL_(k-1)
+        const int r0 = r[k - 1], n = h->n1[k], r1 = r[k];
+        const double *U = core_dev(h, k), *mdk = Dd + pl.noff[k - 1], *mok = (mo && mo[k - 1]) ? Do + pl.noff[k - 1] : nullptr;
+        double *Wk = W + pl.goff[k - 1], *Pn = PL[k & 1];
+        hipLaunchKernelGGL(k_sqn_w, dim3((unsigned)(n * r1)), dim3(128), 0, h->stream, U, RM, (size_t)1, SS, r0, n, mdk, mok, (const double *)PL[(k - 1) & 1], Wk);
+        hipLaunchKernelGGL(k_sqn_p, dim3((r1 + 15) / 16, (r1 + 15) / 16, n), dim3(256), 0, h->stream, U, RM, (size_t)1, SS, r0, r1, (const double *)Wk, n, Part);
+        hipLaunchKernelGGL(k_sqn_pow2, dim3(1), dim3(1024), 0, h->stream, r1 * r1, n, (const double *)Part, Pn, (const int *)(eL + k - 1), eL + k);
+    }
+    if ((rc = marks.mark(h->stream, SQM_LEFT))) return rc;
+    double zm = 0.0;
+    std::vector<int> he(2 * (size_t)(d + 1));
+    HIPCHECK(hipMemcpyAsync(&zm, PL[d & 1], sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(he.data(), eL, sizeof(int) * he.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    const long long ze = he[d];
+    if (z_mant) *z_mant = zm;
+    if (z_exp) *z_exp = ze;
+    if (logz) *logz = sqn_logz(zm, ze, gvol);
+    // the assembly: every core in one launch
+    const bool mfma = pl.eff == TTX_EVAL_MFMA;
+    double *G = dev ? g : buf<double>(h, SC_CGG);
+    if (!dev && accumulate) HIPCHECK(hipMemcpyAsync(G, g, sizeof(double) * pl.gsize, hipMemcpyHostToDevice, h->stream));
+    std::vector<SqnCore> cs(d);
+    for (int k = 1; k <= d; k++)
+        cs[k - 1] = SqnCore{W + pl.goff[k - 1], PR + pl.proff[k], G + pl.goff[k - 1], mfma ? pl.first_wg[k - 1] : pl.first_e[k - 1], r[k - 1], h->n1[k], r[k], 0,
+                            sqn_scale(zm, ze, gvol, coef, he[k - 1], he[(size_t)(d + 1) + k])};
+    OpMeta meta2(h->meta_host);
+    const size_t o_cs = meta2.put(cs);
+    if ((rc = meta2.upload(h, SC_META, &dm))) return rc;
+    const SqnCore *dcs = (const SqnCore *)(dm + o_cs);
+    if ((rc = marks.mark(h->stream, OpMarks::DISCARD))) return rc;
+    if (!mfma)
+        hipLaunchKernelGGL((k_sqn_asm<false, 1>), dim3(pl.grid_exact), dim3(256), 0, h->stream, dcs, d, (long long)pl.gsize, (int)accumulate);
+    else
+        with_tier(pl.tier, [&](auto mr) {
+            hipLaunchKernelGGL((k_sqn_asm<true, decltype(mr)::value>), dim3((unsigned)pl.tot_wg), dim3(256), 0, h->stream, dcs, d, (long long)pl.gsize, (int)accumulate);
+            return 0;
+        });
+    if ((rc = marks.mark(h->stream, SQM_ASM))) return rc;
+    if (!dev) HIPCHECK(hipMemcpyAsync(g, G, sizeof(double) * pl.gsize, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    if ((rc = marks.sum(h->sqn.ms))) return rc;
+    HIPCHECK(hipGetLastError());
+    return TTX_OK;
+}
+extern "C" int ttx_sq_lognorm_grad(ttx_engine *h, const double *const *md, const double *const *mo, double gvol, double coef, double *g, int32_t accumulate, int32_t mode,
+                                   double *z_mant, int64_t *z_exp, double *logz)
+{
+    return sqn_run(h, "ttx_sq_lognorm_grad", md, mo, gvol, coef, g, accumulate, mode, false, z_mant, z_exp, logz);
+}
+extern "C" int ttx_sq_lognorm_grad_dev(ttx_engine *h, const double *const *md, const double *const *mo, double gvol, double coef, double *g_dev, int32_t accumulate, int32_t mode,
+                                       double *z_mant, int64_t *z_exp, double *logz)
+{
+    return sqn_run(h, "ttx_sq_lognorm_grad_dev", md, mo, gvol, coef, g_dev, accumulate, mode, true, z_mant, z_exp, logz);
+}
+extern "C" int ttx_sq_lognorm_grad_last(const ttx_engine *h, double *ms_right, double *ms_left, double *ms_asm, double *flops, int32_t *mode_ran)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_sq_lognorm_grad_last: null engine");
+    if (ms_right) *ms_right = h->sqn.ms[SQM_RIGHT];
+    if (ms_left) *ms_left = h->sqn.ms[SQM_LEFT];
+    if (ms_asm) *ms_asm = h->sqn.ms[SQM_ASM];
+    if (flops) *flops = h->sqn.flops;
+    if (mode_ran) *mode_ran = h->sqn.mode;
+    return TTX_OK;
+}
+// the negative log-likelihood of the squared density at weighted points and its gradient: the value chain, the point kernel, J^T c,
+// then the normaliser's term onto it.  val comes from a value chain of its own: c depends on val, and the core gradient's backward
+// pass forms val only together with the states that its forward pass, which needs c, consumes chunk by chunk
+static int nll_run(ttx_engine *h, const char *who, bool dev, int64_t npts, const double *x, const ttx_basis *basis, const double *w, double gamma,
+                   const double *const *md, const double *const *mo, double gvol, int32_t mode, double *nll, double *logz, double *val, double *g)
+{
+    int rc = tt_prepare(h, who);
+    if (rc) return rc;
+    if (npts < 0 || !g || !nll || !basis || (npts > 0 && !x)) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
+    if ((rc = cg_check_train(h, who)) || (rc = sqn_check(h, who, md, mo, gvol, 1.0, 0, mode))) return rc;
+    if (!(gamma >= 0.0) || !std::isfinite(gamma)) return fail(TTX_EINVAL, "%s: gamma is negative or not finite", who);
+    const int d = h->d;
+    for (int k = 1; k <= d; k++) if ((rc = bs_check_one(who, k, basis[k - 1], h->n1[k]))) return rc;
+    if (!dev && w) for (int64_t p = 0; p < npts; p++) if (!(w[p] >= 0.0) || !std::isfinite(w[p])) return fail(TTX_EINVAL, "%s: w[%lld] is negative or not finite", who, (long long)p);
+    const size_t np = (size_t)npts, tot = cores_total(h), nin = dev ? 0 : np * d + (w ? np : 0);
+    if ((rc = buf_reserve(h, {{SC_SQNPT, sizeof(double) * (5 * np + nin + 1)}, {SC_CGG, dev ? 0 : sizeof(double) * tot}}))) return rc;
+    double *pv = buf<double>(h, SC_SQNPT), *dval = pv, *c = pv + np, *lt = pv + 2 * np, *wv = pv + 3 * np, *one = pv + 4 * np;
+    double *G = dev ? g : buf<double>(h, SC_CGG);
+    if (dev && val) dval = val;
+    if (!dev && npts > 0) {
+        double *ux = pv + 5 * np, *uw = ux + np * d;
+        HIPCHECK(hipMemcpyAsync(ux, x, sizeof(double) * np * d, hipMemcpyHostToDevice, h->stream));
+        if (w) HIPCHECK(hipMemcpyAsync(uw, w, sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
+        HIPCHECK(hipStreamSynchronize(h->stream));
+        x = ux; w = w ? uw : nullptr;
+    }
+    double s1 = 0.0, wsum = 0.0;
+    if (npts > 0) {
+        if ((rc = bs_run(h, who, BS_X_DEV, npts, x, basis, dval, mode))) return rc;
+        hipLaunchKernelGGL(k_sqn_points, g1(np), dim3(256), 0, h->stream, (long long)npts, (const double *)dval, w, gamma, c, lt, wv, one);
+        if ((rc = vec_dot(h, (long long)npts, wv, lt, &s1)) || (rc = vec_dot(h, (long long)npts, wv, one, &wsum))) return rc;
+    }
+    if ((rc = cg_run(h, who, BS_X_DEV, npts, x, basis, c, nullptr, G, 0, mode))) return rc;
+    double lz = 0.0;
+    if ((rc = sqn_run(h, who, md, mo, gvol, wsum, G, 1, mode, true, nullptr, nullptr, &lz))) return rc;
+    *nll = -s1 + wsum * lz;
+    if (logz) *logz = lz;
+    if (!dev) {
+        if (val && npts > 0) HIPCHECK(hipMemcpyAsync(val, dval, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(hipMemcpyAsync(g, G, sizeof(double) * tot, hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(hipStreamSynchronize(h->stream));
+    }
+    HIPCHECK(hipGetLastError());
+    return TTX_OK;
+}
+extern "C" int ttx_sq_nll_batch(ttx_engine *h, int64_t npts, const double *x, const ttx_basis *basis, const double *w, double gamma, const double *const *md, const double *const *mo,
+                                double gvol, int32_t mode, double *nll, double *logz, double *val, double *g)
+{
+    return nll_run(h, "ttx_sq_nll_batch", false, npts, x, basis, w, gamma, md, mo, gvol, mode, nll, logz, val, g);
+}
+extern "C" int ttx_sq_nll_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, const double *w_dev, double gamma, const double *const *md, const double *const *mo,
+                                    double gvol, int32_t mode, double *nll, double *logz, double *val_dev, double *g_dev)
+{
+    return nll_run(h, "ttx_sq_nll_batch_dev", true, npts, x_dev, basis, w_dev, gamma, md, mo, gvol, mode, nll, logz, val_dev, g_dev);
 }
 
 // ---- the largest elements of the resident train (ttx_topk.h)--------------------------------------------------------------------

@@ -8,6 +8,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <math.h>
 #include <algorithm>
 #include <vector>
 
@@ -16,6 +17,7 @@
 #include "ttx_modeapply.h"          // MaCore, TTX_MA_*
 #include "ttx_roundsum.h"           // RsBlk, TTX_RS_*
 #include "ttx_qr_plan.h"            // TTX_LDS_DEVICE
+#include "ttx_sq_norm.h"            // SqnCore, TTX_SQN_*
 
 #if defined(__HIPCC__)
 #define TTX_OP_HD __host__ __device__ inline
@@ -549,4 +551,66 @@ inline RsPlan rs_plan(int d, const int *n, int m, const int32_t *const *rt, cons
     }
     p.eff = op_mode_eff(mode, p.fl, TTX_RS_AUTO_FLOPS);
     return p;
+}
+
+// ---- ttx_sq_lognorm_grad (ttx_sq_norm.h) -------------------------------------------------------------------------------------------
+// break-even of TTX_EVAL_AUTO in flops per call (sum 4 r0^2 n r1 + 6 r0 n r1^2).  PROVISIONAL until the two modes have been timed against
+// each other on the device: profiles/sq_norm_mi355x.txt has the runs that give the crossing
+#define TTX_SQN_AUTO_FLOPS 2.0e7
+struct SqnPlan {
+    BsRefusal refusal = BS_OK;
+    int rmax = 0, eff = TTX_EVAL_EXACT, tier = 1;       // tier: rank_tier of the largest right rank, the instantiation of k_sqn_asm<true>
+    size_t gsize = 0, nsum = 0;                         // doubles of g; sum n(k), the doubles of the md block (and of the mo block)
+    std::vector<size_t> goff, proff, noff;              // [d + 1] core k's block in g and in W; PR_k in the PR store (k = 0 .. d; PR_0 is not formed); mode k's row in the md block
+    std::vector<long long> first_e, first_wg;           // [d] SqnCore::first of the two assembly kernels
+    long long tot_wg = 0;                               // workgroups of k_sqn_asm<true>
+    unsigned grid_exact = 1;                            // workgroups of k_sqn_asm<false> (grid-stride)
+    size_t b_w = 0, b_pr = 0, b_pl = 0, b_y = 0, b_part = 0, b_ex = 0, b_g = 0;      // bytes: the W store, the PR store, the two PL, Y, a step's partial matrices (n of them), the exponents, a host caller's g
+    size_t lds_asm = sizeof(double) * TTX_SQN_KC * TTX_SQN_LDA;         // static LDS of k_sqn_asm<true>
+    double flops = 0.0;
+};
+// n[0 .. d-1], r[0 .. d]
+inline SqnPlan sqn_plan(int d, const int *n, const int *r, bool host_g, int mode)
+{
+    SqnPlan p;
+    p.rmax = *std::max_element(r, r + d + 1);
+    if (p.rmax > 128) { p.refusal = BS_RANK; return p; }
+    if (r[0] != 1 || r[d] != 1) { p.refusal = BS_BOUNDARY; return p; }
+    p.goff.assign(d + 1, 0); p.proff.assign(d + 2, 0); p.noff.assign(d + 1, 0); p.first_e.assign(d, 0); p.first_wg.assign(d, 0);
+    size_t ymax = 1, pmax = 1;
+    int r1max = 1;
+    for (int k = 0; k < d; k++) {
+        const size_t r0 = (size_t)r[k], nk = (size_t)n[k], r1 = (size_t)r[k + 1], sz = r0 * nk * r1;
+        p.goff[k + 1] = p.goff[k] + sz;
+        p.noff[k + 1] = p.noff[k] + nk;
+        p.first_e[k] = (long long)p.goff[k];
+        p.first_wg[k] = p.tot_wg;
+        p.tot_wg += (long long)((r0 * nk + TTX_SQN_ROWS - 1) / TTX_SQN_ROWS);
+        ymax = std::max(ymax, sz);
+        pmax = std::max(pmax, nk * std::max(r0 * r0, r1 * r1));
+        r1max = std::max(r1max, r[k + 1]);
+        p.flops += 4.0 * (double)r0 * (double)r0 * (double)nk * (double)r1 + 6.0 * (double)r0 * (double)nk * (double)r1 * (double)r1;
+    }
+    for (int k = 0; k <= d; k++) p.proff[k + 1] = p.proff[k] + (size_t)r[k] * (size_t)r[k];
+    p.gsize = p.goff[d]; p.nsum = p.noff[d];
+    p.tier = rank_tier(r1max);
+    p.grid_exact = (unsigned)std::min<size_t>((p.gsize + 255) / 256, 4096);
+    p.b_w = sizeof(double) * p.gsize;
+    p.b_pr = sizeof(double) * p.proff[d + 1];
+    p.b_pl = sizeof(double) * 2 * (size_t)p.rmax * (size_t)p.rmax;
+    p.b_y = sizeof(double) * ymax;
+    p.b_part = sizeof(double) * pmax;
+    p.b_ex = sizeof(int) * 2 * (size_t)(d + 1);
+    p.b_g = host_g ? sizeof(double) * p.gsize : 0;
+    p.eff = op_mode_eff(mode, p.flops, TTX_SQN_AUTO_FLOPS);
+    return p;
+}
+// what the host forms from the chains' results (every step one double operation; numpy restates it): Z = z_mant 2^z_exp,
+// den = z_mant + gvol 2^-z_exp, logz = z_exp ln 2 + log(den), s_k = ldexp((2 * coef) / den, eL(k-1) + eR(k) - z_exp)
+inline int sqn_clamp_exp(long long e) { return (int)(e > 100000 ? 100000 : e < -100000 ? -100000 : e); }
+inline double sqn_den(double z_mant, long long z_exp, double gvol) { return z_mant + ldexp(gvol, sqn_clamp_exp(-z_exp)); }
+inline double sqn_logz(double z_mant, long long z_exp, double gvol) { return (double)z_exp * 0.6931471805599453 + log(sqn_den(z_mant, z_exp, gvol)); }
+inline double sqn_scale(double z_mant, long long z_exp, double gvol, double coef, long long el, long long er)
+{
+    return ldexp((2.0 * coef) / sqn_den(z_mant, z_exp, gvol), sqn_clamp_exp(el + er - z_exp));
 }

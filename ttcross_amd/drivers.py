@@ -992,6 +992,137 @@ def run_fit(argv, device=0, repeats=3, tt=None, basis=None, max_iter=4, cg_max=1
     return tt, h, res
 
 
+def sq_lognorm_grad_host(tt, md, mo=None, gvol=0.0, coef=1.0):
+    """what a user does without ttx_sq_lognorm_grad: every core to the host with core(k), then the two Gram chains and the assembly
+    as numpy einsums (each step scaled by its largest entry, so that long trains stay in range).  Returns (logz, [G_k])."""
+    cores = [tt.core(k) for k in range(1, tt.d + 1)]
+    d = len(cores)
+    M = []
+    for k in range(d):
+        m = np.diag(np.asarray(md[k], dtype=np.float64))
+        if mo is not None and mo[k] is not None and m.shape[0] > 1:
+            o = np.asarray(mo[k], dtype=np.float64)[:m.shape[0] - 1]
+            m = m + np.diag(o, 1) + np.diag(o, -1)
+        M.append(m)
+    V = [np.einsum("aib,ij->ajb", c, m) for c, m in zip(cores, M)]
+    PL, PR, lL, lR = [np.ones((1, 1))], [None] * d + [np.ones((1, 1))], [0.0], [0.0] * (d + 1)
+    for k in range(d):
+        p = np.einsum("ac,aib,cid->bd", PL[k], cores[k], V[k], optimize=True)
+        s = np.abs(p).max()
+        PL.append(p / s)
+        lL.append(lL[k] + np.log(s))
+    for k in range(d - 1, 0, -1):
+        p = np.einsum("bd,aib,cid->ac", PR[k + 1], cores[k], V[k], optimize=True)
+        s = np.abs(p).max()
+        PR[k] = p / s
+        lR[k] = lR[k + 1] + np.log(s)
+    logZ = lL[d] + np.log(PL[d][0, 0])
+    logden = np.logaddexp(logZ, np.log(gvol)) if gvol > 0.0 else logZ
+    G = [2.0 * coef * np.exp(lL[k] + lR[k + 1] - logden) * np.einsum("ac,cid,bd->aib", PL[k], V[k], PR[k + 1], optimize=True) for k in range(d)]
+    return float(logden), G
+
+
+def run_mle(argv, device=0, repeats=3, tt=None, max_iter=3, history=2):
+    """mle WORKLOAD NPTS [MODE] [MAX_ITER]: the trains of the tijk sub-command, taken as the square root of a density on equidistant
+    nodes of [0, 1].  First one JSON line of timings on the train as found: sq_lognorm_grad (call, the two chains and the assembly from
+    sq_lognorm_grad_last, the assembly's traffic in bytes per second and as a share of the bandwidth probe at the same byte count), sq_nll at NPTS points drawn with sample_sq_real (the call, the
+    normaliser's share of it), and in the same session the Gram chain of topk, the head pass of sample_sq_real and the host route
+    (sq_lognorm_grad_host).  Then the fit: a weighted sample is drawn from the train with sample_sq_real (weights 1 +- 10 %, seeded),
+    every core entry is perturbed by up to 1 % and fit_density refits it; one JSON line per trial with the nll, the normaliser's share
+    of the call and the times, and a last line with the held-out nll before and after.  The train is put back as it was found."""
+    import json
+    import time
+    import torch
+    from .engine import mass_tridiag
+    torch.cuda.init()          # a torch that brings its own HIP runtime must initialise its device before the engine's library does
+    workload, npts = argv[0], int(float(argv[1]))
+    mode = argv[2] if len(argv) > 2 else "auto"
+    max_iter = int(argv[3]) if len(argv) > 3 else max_iter
+    tt = tt or tijk_train(workload, device=device)
+    dev = torch.device("cuda", device)
+    nodes = [np.linspace(0.0, 1.0, int(nk)) for nk in tt._n]
+    lin = [("linear", t) for t in nodes]
+    md, mo = mass_tridiag(nodes)
+    gamma = 0.0
+    total = int(tt.core_offsets()[-1])
+    out = torch.empty(total, dtype=torch.float64, device=dev)
+
+    def timed(call, last=None):
+        res = call()                                # warm-up
+        ms, lasts = [], []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            res = call()                            # synchronises before it returns
+            ms.append((time.perf_counter() - t0) * 1e3)
+            lasts.append(last() if last else None)
+        return res, float(np.median(ms)), lasts
+
+    res, ms_call, lasts = timed(lambda: tt.sq_lognorm_grad(md, mo, 0.0, 1.0, out=out, mode=mode), tt.sq_lognorm_grad_last)
+    med = {k: float(np.median([x[k] for x in lasts])) for k in ("ms_right", "ms_left", "ms_asm")}
+    r = tt.ranks().astype(np.int64)
+    asm_bytes = 8.0 * (2.0 * total + float(np.sum(r[1:] ** 2)))                 # W read, g written, every PR_k read once
+    u = _seeded_uniforms(2 * npts, tt.d, dev)
+    smp, ms_smp, slast = timed(lambda: tt.sample_sq_real(u, nodes, gamma=gamma, mode=mode), tt.sample_sq_real_last)
+    fin = ~torch.isnan(smp["x"][:, 0])
+    pts = smp["x"][fin]
+    x, xh = pts[:npts].contiguous(), pts[npts:2 * npts].contiguous()
+    g = torch.Generator(device=dev)
+    g.manual_seed(20240611)
+    w = (1.0 + 0.1 * (2.0 * torch.rand(x.shape[0], dtype=torch.float64, device=dev, generator=g) - 1.0)).contiguous()
+    nres, ms_nll, nlast = timed(lambda: tt.sq_nll(x, lin, gamma, md, mo, 0.0, w, mode, out), tt.sq_lognorm_grad_last)
+    ms_norm = float(np.median([sum(v[k] for k in ("ms_right", "ms_left", "ms_asm")) for v in nlast]))
+    from .engine import k_residual_bench
+    probe_ms, probe_bytes = k_residual_bench(max(1, int(asm_bytes / (8 * 64))), 64, 20, device=device)
+    line = dict(workload=workload, npts=int(x.shape[0]), d=tt.d, max_rank=int(r.max()), core_elements=total, mode_asked=mode, mode=lasts[-1]["mode"],
+                probe_bytes_per_s=probe_bytes / (probe_ms * 1e-3), asm_fraction_of_probe=(asm_bytes / (med["ms_asm"] * 1e-3)) / (probe_bytes / (probe_ms * 1e-3)) if med["ms_asm"] > 0 else None,
+                flops=lasts[-1]["flops"], ms_lognorm_grad=ms_call, **med, asm_bytes_per_s=asm_bytes / (med["ms_asm"] * 1e-3) if med["ms_asm"] > 0 else None,
+                logz=res["logz"], z_exp=res["z_exp"], ms_nll=ms_nll, nll=nres["nll"], ms_normaliser_in_nll=ms_norm, normaliser_share_of_nll=ms_norm / ms_nll,
+                ms_sample_sq_real_head=float(np.median([v["ms_head"] for v in slast])), ms_sample_sq_real=ms_smp)
+    try:
+        _, ms_topk, tlast = timed(lambda: tt.topk(16, mode=mode), tt.topk_last)
+        line["ms_topk_gram"] = float(np.median([v["ms_gram"] for v in tlast]))
+    except Exception as e:                          # a train the search refuses still gives the other figures
+        line["topk_error"] = str(e)[:200]
+    t0 = time.perf_counter()
+    hlz, hG = sq_lognorm_grad_host(tt, md, mo)
+    line["host_route_ms"] = (time.perf_counter() - t0) * 1e3
+    got = tt.sq_lognorm_grad(md, mo, 0.0, 1.0, mode=lasts[-1]["mode"])
+    line["max_rel_diff_to_host_route"] = max(float(np.max(np.abs(a - b)) / max(float(np.max(np.abs(b))), 1e-300)) for a, b in zip(got["g"], hG))
+    line["logz_diff_to_host_route"] = abs(got["logz"] - hlz)
+    print(json.dumps(line))
+    if max_iter > 0:
+        found = tt.cores_get(torch.empty(total, dtype=torch.float64, device=dev))
+        held = lambda: tt.sq_nll(xh, lin, gamma, md, mo, 0.0, None, mode, out)["nll"]          # noqa: E731
+        start = (found * (1.0 + 0.01 * (2.0 * torch.rand(total, dtype=torch.float64, device=dev, generator=g) - 1.0))).contiguous()
+        torch.cuda.synchronize(dev)
+        held_true = held()
+        tt.cores_set(start)
+        held_start = held()
+        trials = []
+        inner = tt.sq_nll
+
+        def traced(*a, **k):
+            t0 = time.perf_counter()
+            rr = inner(*a, **k)
+            ms = (time.perf_counter() - t0) * 1e3
+            ll = tt.sq_lognorm_grad_last()
+            trials.append(dict(nll=rr["nll"], ms_call=ms, ms_normaliser=ll["ms_right"] + ll["ms_left"] + ll["ms_asm"]))
+            return rr
+        tt.sq_nll = traced
+        try:
+            t0 = time.perf_counter()
+            h = tt.fit_density(x, lin, gamma, md, mo, 0.0, w, mode, max_iter=max_iter, history=history)
+            ms_fit = (time.perf_counter() - t0) * 1e3
+        finally:
+            del tt.sq_nll
+        for j, t in enumerate(trials):
+            acc = None if j == 0 else bool(h["hist"][j - 1][1])
+            print(json.dumps(dict(trial=j, accepted=acc, nll=t["nll"], ms_call=t["ms_call"], ms_normaliser=t["ms_normaliser"], normaliser_share=t["ms_normaliser"] / t["ms_call"])))
+        print(json.dumps(dict(workload=workload, iters=h["iters"], nll=h["nll"], ms_fit=ms_fit, held_out_nll_truth=held_true, held_out_nll_start=held_start, held_out_nll_end=held())))
+        tt.cores_set(found)
+    return tt, line
+
+
 def sample_host(tt, u, w=None):
     """what a user does without ttx_sample: every core to the host with core(k), then the conditional marginals walked in
     numpy from the last mode to the first.  Returns (ind, logq, val) of the definition in include/ttx.h, in numpy's own
@@ -1607,6 +1738,8 @@ if __name__ == "__main__":
         run_coregrad(sys.argv[2:])
     elif sys.argv[1] == "fit":
         run_fit(sys.argv[2:])
+    elif sys.argv[1] == "mle":
+        run_mle(sys.argv[2:])
     elif sys.argv[1] == "chf":
         run_chf(sys.argv[2:])
     elif sys.argv[1] == "pdf":

@@ -179,6 +179,15 @@ def load_library():
     L.ttx_basis_fit_tab.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_double)] + _hist
     L.ttx_basis_fit_tab_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p] + _hist
     L.ttx_basis_fit_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64), POINTER(c_int64), POINTER(c_int32)]
+    _rows = POINTER(POINTER(c_double))
+    _zout = [POINTER(c_double), POINTER(c_int64), POINTER(c_double)]
+    L.ttx_sq_lognorm_grad.argtypes = [c_void_p, _rows, _rows, c_double, c_double, POINTER(c_double), c_int32, c_int32] + _zout
+    L.ttx_sq_lognorm_grad_dev.argtypes = [c_void_p, _rows, _rows, c_double, c_double, c_void_p, c_int32, c_int32] + _zout
+    L.ttx_sq_lognorm_grad_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32)]
+    L.ttx_sq_nll_batch.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(_Basis), POINTER(c_double), c_double, _rows, _rows, c_double, c_int32,
+                                   POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double)]
+    L.ttx_sq_nll_batch_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(_Basis), c_void_p, c_double, _rows, _rows, c_double, c_int32,
+                                       POINTER(c_double), POINTER(c_double), c_void_p, c_void_p]
     L.ttx_sample.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
     L.ttx_sample_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(c_double), POINTER(c_int32), c_void_p, c_void_p, c_void_p]
     L.ttx_sample_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
@@ -365,6 +374,44 @@ def mass_cholesky(nodes):
         sp[i] = off[i] / dg[i]
         dg[i + 1] = np.sqrt(diag[i + 1] - sp[i] * sp[i])
     return dg, sp
+
+
+def mass_tridiag(nodes, cond=None):
+    """(md, mo) of the symmetric tridiagonal matrices sq_lognorm_grad and sq_nll take (include/ttx.h: ttx_sq_lognorm_grad) for the
+    hat functions on strictly ascending nodes: the mass matrix M[i, i] = (h[i-1] + h[i]) / 3 with one term at each end,
+    M[i, i+1] = h[i] / 6 -- U^T U of mass_cholesky(nodes) to rounding.  A single node gives ([1.], []).  One array of nodes gives
+    one pair; a list of arrays gives (list of md, list of mo).  cond (with a list): per mode None or NaN for a drawn mode, else the
+    coordinate the mode is held at, whose matrix is phi phi^T of its two adjacent hat values (zero elsewhere)."""
+    if isinstance(nodes, (list, tuple)) and len(nodes) and np.ndim(nodes[0]) == 1:
+        cond = [None] * len(nodes) if cond is None else list(cond)
+        if len(cond) != len(nodes):
+            raise ValueError("mass_tridiag: one cond entry per mode expected")
+        pairs = [mass_tridiag(t, c) for t, c in zip(nodes, cond)]
+        return [p[0] for p in pairs], [p[1] for p in pairs]
+    t = np.ascontiguousarray(nodes, dtype=np.float64)
+    if t.ndim != 1 or t.size < 1:
+        raise ValueError("mass_tridiag: a one-dimensional array of nodes expected")
+    n = t.size
+    if cond is not None and not np.isnan(cond):
+        x = float(cond)
+        md, mo = np.zeros(n), np.zeros(max(n - 1, 0))
+        if n == 1:
+            md[0] = 1.0
+            return md, mo
+        if not t[0] <= x <= t[-1]:
+            raise ValueError("mass_tridiag: a held coordinate lies outside the nodes")
+        c = min(max(int(np.searchsorted(t, x, side="right")) - 1, 0), n - 2)
+        p1 = (x - t[c]) / (t[c + 1] - t[c])
+        p0 = 1.0 - p1
+        md[c], md[c + 1], mo[c] = p0 * p0, p1 * p1, p0 * p1
+        return md, mo
+    if n == 1:
+        return np.ones(1), np.zeros(0)
+    h = t[1:] - t[:-1]
+    md = np.empty(n)
+    md[0], md[-1] = h[0] / 3.0, h[-1] / 3.0
+    md[1:-1] = (h[:-1] + h[1:]) / 3.0
+    return md, h / 6.0
 
 
 def roundsum_omega(seed, k, shape):
@@ -1491,6 +1538,168 @@ class TTCross:
                                                  ctypes.byref(nc), ctypes.byref(md)))
         names = {v: k for k, v in EVAL_MODES.items()}
         return dict(ms_jvp=mj.value, ms_core_grad=mc.value, ms_value=mv.value, ms_vector=mx.value, n_jvp=nj.value, n_core_grad=nc.value, mode=names.get(md.value))
+
+    # ---- the normaliser of the squared density, maximum likelihood (include/ttx.h: ttx_sq_lognorm_grad) ---------
+    def _tridiag_rows(self, who, md, mo):
+        """(md rows, mo rows or None, what keeps them alive) as the arrays of d row pointers the C calls take"""
+        if len(md) != self.d or (mo is not None and len(mo) != self.d):
+            raise ValueError(f"{who}: {self.d} rows of md (and of mo, or mo=None) expected")
+        keep = []
+        dp, op = (POINTER(c_double) * self.d)(), (POINTER(c_double) * self.d)()
+        for k in range(self.d):
+            a = np.ascontiguousarray(md[k], dtype=np.float64)
+            if a.shape != (self._n[k],):
+                raise ValueError(f"{who}: md[{k}] must hold {self._n[k]} numbers")
+            keep.append(a)
+            dp[k] = _dp(a)
+            if mo is not None and mo[k] is not None:
+                b = np.ascontiguousarray(mo[k], dtype=np.float64)
+                if b.shape != (max(self._n[k] - 1, 0),):
+                    raise ValueError(f"{who}: mo[{k}] must hold {self._n[k] - 1} numbers")
+                b = np.concatenate([b, np.zeros(1)])                    # never an empty array behind a non-null pointer
+                keep.append(b)
+                dp_b = _dp(b)
+                op[k] = dp_b
+        return dp, (op if mo is not None else None), keep
+
+    def sq_lognorm_grad(self, md, mo=None, gvol=0.0, coef=1.0, out=None, accumulate=False, mode="auto"):
+        """dict(z_mant, z_exp, logz, g) (include/ttx.h: ttx_sq_lognorm_grad): Z = <f, f>_M = z_mant 2^z_exp for the symmetric
+        tridiagonal matrices M_k (md[k] the diagonal, mo[k] the off-diagonal or None for a diagonal matrix: mass_tridiag gives the
+        hat functions' mass matrices), logz = log(Z + gvol) and g = out + (coef / (Z + gvol)) dZ/dU_k for every core.  out: None, a
+        list of blocks or a flat host array (g is a list of blocks), or a flat float64 tensor on the engine's device (written in
+        place, by pointer); accumulate=True adds onto it.  sq_lognorm_grad_last() tells what ran."""
+        L, m, acc = load_library(), _eval_mode(mode), int(bool(accumulate))
+        dp, op, keep = self._tridiag_rows("sq_lognorm_grad", md, mo)
+        zm, ze, lz = c_double(), c_int64(), c_double()
+        tail = (acc, m, ctypes.byref(zm), ctypes.byref(ze), ctypes.byref(lz))
+        if out is not None and self._flat_dev("sq_lognorm_grad", out) is not None:
+            _check(L.ttx_sq_lognorm_grad_dev(self._h, dp, op, float(gvol), float(coef), c_void_p(out.data_ptr()), *tail))
+            g = out
+        else:
+            if out is None:
+                if acc:
+                    raise ValueError("sq_lognorm_grad: accumulate needs out")
+                flat = np.zeros(int(self.core_offsets()[-1]))
+            else:
+                flat = self._core_pack("sq_lognorm_grad", out.numpy() if type(out).__module__.split(".")[0] == "torch" else out)
+                flat = flat if flat.flags.writeable else flat.copy()
+            _check(L.ttx_sq_lognorm_grad(self._h, dp, op, float(gvol), float(coef), _dp(flat), *tail))
+            g = self._core_blocks(flat)
+        return dict(z_mant=zm.value, z_exp=ze.value, logz=lz.value, g=g)
+
+    def sq_lognorm_grad_last(self):
+        """dict(ms_right, ms_left, ms_asm, flops, mode) of the last sq_lognorm_grad (also the one inside sq_nll) on this engine
+        (include/ttx.h: ttx_sq_lognorm_grad_last)"""
+        mr, ml, ma, fl, md = c_double(), c_double(), c_double(), c_double(), c_int32()
+        _check(load_library().ttx_sq_lognorm_grad_last(self._h, ctypes.byref(mr), ctypes.byref(ml), ctypes.byref(ma), ctypes.byref(fl), ctypes.byref(md)))
+        names = {v: k for k, v in EVAL_MODES.items()}
+        return dict(ms_right=mr.value, ms_left=ml.value, ms_asm=ma.value, flops=fl.value, mode=names.get(md.value))
+
+    def sq_nll(self, x, basis, gamma, md, mo=None, gvol=0.0, w=None, mode="auto", out=None):
+        """dict(nll, logz, val, g) (include/ttx.h: ttx_sq_nll_batch): the negative log-likelihood -sum_p w_p log(f(x_p)^2 + gamma) +
+        (sum_p w_p) log(Z + gvol) of the points x (npts, d) under the squared density of the resident train, and its gradient with
+        respect to the cores.  basis as for basis_batch, md and mo as for sq_lognorm_grad, w (npts,) >= 0 or None for all ones.  Host
+        arrays give numpy out (g a list of blocks); float64 tensors on the engine's device go by pointer, g is then the flat device
+        tensor out (allocated where None)."""
+        L, m = load_library(), _eval_mode(mode)
+        arr, keepb = self._basis_arr("sq_nll", basis)
+        dp, op, keep = self._tridiag_rows("sq_nll", md, mo)
+        nll, lz = c_double(), c_double()
+        val = self._dev_pair("sq_nll", x, self.d)
+        if val is not None:
+            import torch
+            if w is not None and (type(w).__module__.split(".")[0] != "torch" or w.device != x.device or w.dtype != torch.float64 or not w.is_contiguous() or w.shape != (x.shape[0],)):
+                raise ValueError("sq_nll: w must be a contiguous float64 tensor of shape (npts,) on the engine's device")
+            if out is None:
+                out = torch.empty(int(self.core_offsets()[-1]), dtype=torch.float64, device=x.device)
+            elif self._flat_dev("sq_nll", out) is None:
+                raise ValueError("sq_nll: out must be a flat float64 tensor on the engine's device")
+            torch.cuda.current_stream(x.device).synchronize()
+            _check(L.ttx_sq_nll_batch_dev(self._h, x.shape[0], c_void_p(x.data_ptr()), arr, c_void_p(w.data_ptr()) if w is not None else None, float(gamma), dp, op,
+                                          float(gvol), m, ctypes.byref(nll), ctypes.byref(lz), c_void_p(val.data_ptr()), c_void_p(out.data_ptr())))
+            return dict(nll=nll.value, logz=lz.value, val=val, g=out)
+        x, w = (a.cpu().numpy() if type(a).__module__.split(".")[0] == "torch" else a for a in (x, w))
+        xa = np.ascontiguousarray(x, dtype=np.float64)
+        wa = None if w is None else np.ascontiguousarray(w, dtype=np.float64)
+        if xa.ndim != 2 or xa.shape[1] != self.d or (wa is not None and wa.shape != (xa.shape[0],)):
+            raise ValueError(f"sq_nll: an array of shape (npts, {self.d}) and (or no) npts weights expected")
+        flat, hv = np.zeros(int(self.core_offsets()[-1])), np.zeros(xa.shape[0])
+        _check(L.ttx_sq_nll_batch(self._h, xa.shape[0], _dp(xa), arr, _dp(wa), float(gamma), dp, op, float(gvol), m, ctypes.byref(nll), ctypes.byref(lz), _dp(hv), _dp(flat)))
+        return dict(nll=nll.value, logz=lz.value, val=hv, g=self._core_blocks(flat))
+
+    def fit_density(self, x, basis, gamma, md, mo=None, gvol=0.0, w=None, mode="auto", max_iter=20, history=5, c1=1e-4, shrink=0.5, max_back=20):
+        """Fit the squared density of the resident train to weighted points by maximum likelihood, in place: L-BFGS with a fixed
+        history and Armijo backtracking on sq_nll (tests/sq_norm_ref.py: lbfgs restates it operation by operation).  x (npts, d) and
+        w are float64 tensors on the engine's device (host arrays are uploaded once); every core-space vector is a flat device
+        tensor handled by cores_dot, cores_axpby, cores_get and cores_set, only scalars reach the host.  A rejected trial puts the
+        cores back from the kept buffer.  Returns dict(nll (the accepted values, the start first), hist (every trial: (nll, accepted,
+        the Armijo bound)), iters)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        xt = x if (type(x).__module__.split(".")[0] == "torch" and x.is_cuda) else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device=dev)
+        wt = w if (w is None or (type(w).__module__.split(".")[0] == "torch" and w.is_cuda)) else torch.as_tensor(np.ascontiguousarray(w, dtype=np.float64), device=dev)
+        total = int(self.core_offsets()[-1])
+        new = lambda: torch.empty(total, dtype=torch.float64, device=dev)          # noqa: E731
+
+        def fun(out):
+            return self.sq_nll(xt, basis, gamma, md, mo, gvol, wt, mode, out)["nll"]
+        xc, g, q, p, xn, gn = new(), new(), new(), new(), new(), new()
+        self.cores_get(xc)
+        f = fun(g)
+        S, Y, R = [], [], []
+        hist, fs = [], [f]
+        for _ in range(int(max_iter)):
+            q.copy_(g)
+            al = []
+            for s_, y_, rho in zip(reversed(S), reversed(Y), reversed(R)):
+                a = rho * self.cores_dot(s_, q)
+                al.append(a)
+                self.cores_axpby(-a, y_, 1.0, q)
+            if S:
+                gam = self.cores_dot(S[-1], Y[-1]) / self.cores_dot(Y[-1], Y[-1])
+                self.cores_axpby(gam, q, 0.0, q)
+            for (s_, y_, rho), a in zip(zip(S, Y, R), reversed(al)):
+                be = rho * self.cores_dot(y_, q)
+                self.cores_axpby(a - be, s_, 1.0, q)
+            self.cores_axpby(-1.0, q, 0.0, p.copy_(q))
+            slope = self.cores_dot(g, p)
+            if not slope < 0.0:
+                S, Y, R = [], [], []
+                self.cores_axpby(-1.0, g, 0.0, p.copy_(g))
+                slope = self.cores_dot(g, p)
+                if not slope < 0.0:
+                    break
+            t = 1.0
+            if not S:
+                gnorm = float(np.sqrt(self.cores_dot(g, g)))
+                t = 1.0 / gnorm if gnorm > 1.0 else 1.0
+            done = False
+            for _b in range(int(max_back)):
+                self.cores_axpby(t, p, 1.0, xn.copy_(xc))
+                self.cores_set(xn)
+                fn = fun(gn)
+                ok = bool(np.isfinite(fn) and fn <= f + c1 * t * slope)
+                hist.append((fn, ok, f + c1 * t * slope))
+                if ok:
+                    done = True
+                    break
+                t = shrink * t
+            if not done:
+                self.cores_set(xc)
+                break
+            s_, y_ = new(), new()
+            self.cores_axpby(-1.0, xc, 1.0, s_.copy_(xn))
+            self.cores_axpby(-1.0, g, 1.0, y_.copy_(gn))
+            sy = self.cores_dot(s_, y_)
+            if sy > 0.0:
+                S.append(s_); Y.append(y_); R.append(1.0 / sy)
+                if len(S) > int(history):
+                    S.pop(0); Y.pop(0); R.pop(0)
+            xc, xn = xn, xc
+            g, gn = gn, g
+            f = fn
+            fs.append(f)
+        return dict(nll=fs, hist=hist, iters=len(fs) - 1)
 
     # ---- samples from the resident train (include/ttx.h: ttx_sample and its three siblings) --------------
     # the outputs of the index samplers and of the real samplers: name, a row of d per sample (else one number), dtype, always allocated
