@@ -710,6 +710,53 @@ int ttx_sq_nll_batch    (ttx_engine *h, int64_t npts, const double *x /* [npts][
 int ttx_sq_nll_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, const double *w_dev, double gamma, const double *const *md, const double *const *mo,
                          double gvol, int32_t mode, double *nll, double *logz, double *val_dev, double *g_dev);
 
+/* Moments and one-mode reduced density matrices of the squared density, on the device (ttcross_amd/csrc/ttx_sq_moments.h): what reads a
+ * fitted q = (f^2 + gamma) / (Z + gamma V).  With symmetric tridiagonal observables A_k (ad, ao) and A2_k (a2d, a2o), rows as md and mo:
+ *   m1[l]    = <f, A_l f>_M / Z                 (A_l at mode l, M_j at every other mode)
+ *   c2[k][l] = <f, (A_k x A_l) f>_M / Z, k != l;  c2[k][k] = <f, A2_k f>_M / Z (0.0 where A2_k is not given)
+ *   bd, bo   = the band of B_k / Z, B_k(i, i') = sum PL_(k-1)(a, a') U_k(a', i, b') PR_k(b, b') U_k(a, i', b): sum_ii' B_k(i, i') X(i, i') / Z is
+ *              the moment of any one-mode X, and phi(x)^T B_k phi(x) / Z the marginal density of f^2 / Z in mode k for hat functions phi
+ * all ratios that stay O(1) where Z leaves the double range.  ad NULL: no moments asked (m1 and c2, where given, are filled with 0.0);
+ * ad[k] NULL: mode k is not selected, its m1 and its rows and columns of c2 are 0.0; ao or ao[k] NULL: A_k is diagonal; the same for a2d, a2o.
+ * bd and bo are [sum n_k] each, mode k's row at n_1 + .. + n_(k-1), bo[k][n_k - 1] = 0.0; the band is formed only where both are given.
+ * m1 is [d], c2 [d][d]; each of z_mant, z_exp, bd / bo, m1, c2 may be NULL, not all of them.
+ * Definition (numpy restates it: tests/sq_moments_ref.py), in the terms of ttx_sq_lognorm_grad above; "left step with X from P" is one step
+ * of its left chain with X in place of M_k and P in place of PL_(k-1), "right step" the same for the right chain; every p_i on its own, the
+ * p_i added over ascending i from 0.0.
+ *   1. The chains of ttx_sq_lognorm_grad: PL_k, eL(k), PR_k, eR(k), z_mant, z_exp -- the same bits.
+ *   2. RA_(l-1) for a selected l: the right step with A_l from PR_l, the sum of the p_i NOT rescaled; exponent eR(l).
+ *   3. m1[l] = ldexp(dot(PL_(l-1), RA_(l-1)) / z_mant, eL(l-1) + eR(l) - z_exp), dot the sum of the entrywise products of the two column-major
+ *      matrices by ttx_cores_dot's rule with tot = r_(l-1)^2; the exponent clamped to +-100000.  c2[l][l]: the same with A2_l.
+ *   4. C^(k)_k for a selected k below the largest selected mode: the left step with A_k from PL_(k-1), then the power-of-two rule, exponent
+ *      e^(k)_k = eL(k-1) + ex; C^(k)_j, j = k+1 .. l_max - 1 (l_max the largest selected mode): the left step with M_j from C^(k)_(j-1), the rule,
+ *      e^(k)_j = e^(k)_(j-1) + ex.
+ *   5. c2[k][l] = c2[l][k] = ldexp(dot(C^(k)_(l-1), RA_(l-1)) / z_mant, e^(k)_(l-1) + eR(l) - z_exp) for selected k < l.
+ *   6. T(a, i, b') = sum_a' PL_(k-1)(a, a') * U_k(a', i, b');  D0(a, i, b) = sum_b' T(a, i, b') * PR_k(b, b');
+ *      B_k(i, i') = sum_b [ sum_a U_k(a, i, b) * D0(a, i', b) ];  bd[k][i] = ldexp(B_k(i, i) / z_mant, eL(k-1) + eR(k) - z_exp), bo[k][i] of B_k(i, i+1).
+ *   mode : TTX_EVAL_EXACT  every output bit-identical to the restatement
+ *          TTX_EVAL_MFMA   the left steps of item 4 on the fp64 matrix cores: W = C V for all carried matrices of a mode in one launch,
+ *                          P = U^T W summed over (a, i) in one accumulation; items 1, 2, 3, 6, the power-of-two rule and every dot are
+ *                          EXACT's kernels, so z_mant, z_exp, m1, the diagonal of c2, bd and bo are the same bits and the off-diagonal of c2
+ *                          agrees to rounding (sq_moments_ref.py derives the allowance); no floating-point atomics, a call repeats bit for bit
+ *          TTX_EVAL_AUTO   by the flops of the call against a PROVISIONAL break-even (TTX_SQM_AUTO_FLOPS, also read from the environment)
+ * The carried matrices of a mode go through one launch per kernel, cut into batches so that the work space of a launch stays under
+ * TTX_SQM_CAP_BYTES (ttx_op_plan.h); TTX_SQM_BATCH in the environment lowers the batch.  A carried matrix does not depend on the cut.
+ * A NaN core gives NaN; nothing faults; work space that cannot be allocated is TTX_EHIP.
+ * Refusals: those of ttx_sq_lognorm_grad (no train: TTX_ESTATE; a multi-process engine; ranks above 128; boundary ranks; a NULL md or md[k];
+ * a non-finite entry of md or mo), a non-finite entry of ad, ao, a2d or a2o, an unknown mode, every output NULL.  A refused call writes nothing.
+ * ttx_sq_moments_last: of the last call on this engine, the milliseconds of the chains, the band, the carried steps and the closing
+ * products (with the right matrices), the flops, the number of carried chain steps sum_k (l_max - k) and the mode that ran (-1: none yet).
+ * Open: two-mode marginal densities, higher moments, ranks above 128.  Added without a new ttx_version: look the symbols up. */
+int ttx_sq_moments(ttx_engine *h,
+    const double *const *md, const double *const *mo,
+    const double *const *ad, const double *const *ao,
+    const double *const *a2d, const double *const *a2o,
+    int32_t mode,
+    double *z_mant, int64_t *z_exp,
+    double *bd, double *bo,
+    double *m1 /* [d] */, double *c2 /* [d][d] */);
+int ttx_sq_moments_last(const ttx_engine *h, double *ms_chains, double *ms_band, double *ms_carry, double *ms_close, double *flops, int64_t *steps, int32_t *mode_ran);
+
 /* Samples drawn from the resident train by sequential conditional sampling, on the device (ttcross_amd/csrc/ttx_sample.h).
  * Modes are 1-based, G_k is core k, r_0 = r_d = 1.
  *   u     : npts rows of d uniforms, row-major [npts][d]; u_k draws mode k

@@ -151,6 +151,7 @@ enum {
     SC_JVV, SC_VDP, SC_VIN,             // ttx_basis_jvp_batch: the packed direction of a host caller; ttx_cores_dot: the segment sums, the two buffers of a host caller
     SC_FITV, SC_FITP,                   // ttx_basis_fit_batch: the core-space work vectors and the snapshot; the point vectors, then the uploaded inputs of a host caller
     SC_SQNW, SC_SQNP, SC_SQNY, SC_SQNPT, // ttx_sq_lognorm_grad: the W store; the PR store, the two PL and the exponents; Y of a right step and the per-index partial matrices of a step; ttx_sq_nll_batch: the point vectors, then the uploaded inputs of a host caller
+    SC_SQMP, SC_SQMC, SC_SQMW,          // ttx_sq_moments: the PR and PL stores, the exponents, RA, the products and the band; the carried matrices (two sets) and their exponents; the W and partial matrices of a batched launch (its unbatched steps use SC_SQNY)
     SC_NBUF
 };
 struct EvBuf { void *p = nullptr; size_t bytes = 0; };
@@ -214,6 +215,7 @@ struct JvLast { double ms[2] = {0.0, 0.0}, flops = 0.0; int mode = -1; };      /
 struct FitLast { double ms[4] = {0.0, 0.0, 0.0, 0.0}; int64_t n_jvp = 0, n_cg = 0; int mode = -1; };      // ttx_basis_fit_batch / _tab: JVP, core-gradient, value, vector launches
 
 struct SqnLast { double ms[3] = {0.0, 0.0, 0.0}, flops = 0.0; int mode = -1; };               // ttx_sq_lognorm_grad: right chain, left chain, assembly
+struct SqmLast { double ms[4] = {0.0, 0.0, 0.0, 0.0}, flops = 0.0; int64_t steps = 0; int mode = -1; };    // ttx_sq_moments: chains, band, carry, close
 
 struct DevFun;                          // a loaded device integrand (TTX_FUN_DEVICE), defined with slot_eval
 struct TrainFun;                        // the operands and the combiner of TTX_FUN_TRAINS, defined with slot_eval
@@ -333,6 +335,7 @@ struct ttx_engine {
     JvLast jv;
     FitLast fit;
     SqnLast sqn;
+    SqmLast sqm;
     std::vector<hipEvent_t> op_ev;                      // OpMarks' events: ttx_lincomb_round, the squared samplers, the basis evaluations
 };
 
@@ -4863,6 +4866,216 @@ extern "C" int ttx_sq_nll_batch_dev(ttx_engine *h, int64_t npts, const double *x
                                     double gvol, int32_t mode, double *nll, double *logz, double *val_dev, double *g_dev)
 {
     return nll_run(h, "ttx_sq_nll_batch_dev", true, npts, x_dev, basis, w_dev, gamma, md, mo, gvol, mode, nll, logz, val_dev, g_dev);
+}
+
+// ---- moments and reduced density matrices of the squared density (ttx_sq_moments.h) ----------------------------------------------
+enum { SQT_CHAINS, SQT_BAND, SQT_CARRY, SQT_CLOSE };
+// a non-finite entry of an optional observable (rows that are null are not looked at; an off-diagonal counts only where its diagonal is given)
+static int sqm_check_rows(ttx_engine *h, const char *who, const char *nd, const char *no, const double *const *dg, const double *const *of)
+{
+    if (!dg) return TTX_OK;
+    for (int k = 1; k <= h->d; k++) {
+        if (!dg[k - 1]) continue;
+        for (int i = 0; i < h->n1[k]; i++) if (!std::isfinite(dg[k - 1][i])) return fail(TTX_EINVAL, "%s: %s[%d][%d] is not finite", who, nd, k - 1, i);
+        if (of && of[k - 1]) for (int i = 0; i + 1 < h->n1[k]; i++) if (!std::isfinite(of[k - 1][i])) return fail(TTX_EINVAL, "%s: %s[%d][%d] is not finite", who, no, k - 1, i);
+    }
+    return TTX_OK;
+}
+extern "C" int ttx_sq_moments(ttx_engine *h, const double *const *md, const double *const *mo, const double *const *ad, const double *const *ao,
+                              const double *const *a2d, const double *const *a2o, int32_t mode, double *z_mant, int64_t *z_exp, double *bd, double *bo, double *m1, double *c2)
+{
+    const char *who = "ttx_sq_moments";
+    int rc = tt_prepare(h, who);
+    if (rc) return rc;
+    if ((rc = cg_check_train(h, who)) || (rc = sqn_check(h, who, md, mo, 0.0, 1.0, 0, mode))) return rc;
+    if ((rc = sqm_check_rows(h, who, "ad", "ao", ad, ao)) || (rc = sqm_check_rows(h, who, "a2d", "a2o", a2d, a2o))) return rc;
+    const int d = h->d;
+    const std::vector<int32_t> &r = h->rfinal;
+    const bool want_band = bd && bo, want_out = m1 || c2, want_mom = want_out && ad;
+    std::vector<unsigned char> selected(d, 0);
+    if (ad) for (int k = 0; k < d; k++) selected[k] = ad[k] != nullptr;
+    double auto_flops = TTX_SQM_AUTO_FLOPS;
+    if (const char *e = getenv("TTX_SQM_AUTO_FLOPS")) { const double v = atof(e); if (v > 0.0) auto_flops = v; }
+    const SqmPlan pl = sqm_plan(d, h->n1.data() + 1, r.data(), selected.data(), want_band, want_mom, z_mant || z_exp || want_out, mode, env_int("TTX_SQM_BATCH", 0), auto_flops);
+    if (pl.refusal == SQM_RANK) return fail(TTX_EINVAL, "%s: ranks up to 128 only (got %d)", who, pl.rmax);
+    if (pl.refusal == SQM_BOUNDARY) return fail(TTX_EINVAL, "%s: boundary ranks are not 1", who);
+    if (pl.refusal == SQM_NOTHING) return fail(TTX_EINVAL, "%s: every output is null", who);
+    h->sqm = SqmLast();
+    h->sqm.flops = pl.flops; h->sqm.mode = pl.eff; h->sqm.steps = pl.steps;
+    const int nsel = (int)pl.sel.size();
+    const bool mfma = pl.eff == TTX_EVAL_MFMA;
+    // the rows of M, A and A2, one device block each; a row that is not given stays 0.0 and is never read
+    std::vector<double> rows[6];
+    const double *const *src[6] = {md, mo, ad, ao, a2d, a2o};
+    for (int x = 0; x < 6; x++) {
+        rows[x].assign(pl.nsum, 0.0);
+        if (!src[x]) continue;
+        for (int k = 0; k < d; k++) {
+            const int cnt = (x & 1) ? h->n1[k + 1] - 1 : h->n1[k + 1];
+            if (src[x][k] && cnt > 0) std::copy(src[x][k], src[x][k] + cnt, rows[x].begin() + pl.noff[k]);
+        }
+    }
+    OpMeta meta(h->meta_host);
+    size_t off[6];
+    for (int x = 0; x < 6; x++) off[x] = meta.put(rows[x]);
+    char *dm = nullptr;
+    if ((rc = meta.upload(h, SC_META, &dm))) return rc;
+    auto row = [&](int x, int k) -> const double * { return (src[x] && src[x][k]) ? (const double *)(dm + off[x]) + pl.noff[k] : nullptr; };   // k 0-based
+    const size_t RR = (size_t)pl.rmax * pl.rmax, npr = pl.proff[d + 1];
+    if ((rc = buf_reserve(h, {{SC_SQMP, pl.b_pr + pl.b_pl + pl.b_ra + pl.b_band + pl.b_dots + pl.b_ex}, {SC_SQNY, pl.b_y + pl.b_part}, {SC_SQMC, nsel > 1 ? pl.b_carry : 0},
+                              {SC_SQMW, pl.b_w + pl.b_cpart}}))) return rc;
+    double *PR = buf<double>(h, SC_SQMP), *PLs = PR + npr, *RA = PLs + npr, *RA2 = RA + RR, *band = RA2 + RR, *dots = band + pl.b_band / sizeof(double);
+    int *eL = (int *)(dots + std::max<size_t>(1, pl.ndots)), *eR = eL + d + 1, *edots = eR + d + 1;
+    double *Y = buf<double>(h, SC_SQNY), *Y2 = Y + pl.b_y / (2 * sizeof(double)), *Part = Y + pl.b_y / sizeof(double);
+    double *Cc[2] = {buf<double>(h, SC_SQMC), buf<double>(h, SC_SQMC) + (size_t)pl.members * RR};
+    int *ce = (int *)(Cc[1] + (size_t)pl.members * RR);
+    double *Wb = buf<double>(h, SC_SQMW), *CPart = Wb + pl.b_w / sizeof(double);
+    const int RM = h->RM;
+    const size_t SS = h->P.SS;
+    OpMarks marks(h->op_ev);
+    if ((rc = marks.mark(h->stream, OpMarks::DISCARD))) return rc;
+    // the chains of ttx_sq_lognorm_grad, launch for launch; every PL_k is kept as every PR_k is
+    hipLaunchKernelGGL(k_sqn_init, dim3(1), dim3(64), 0, h->stream, PLs, PR + pl.proff[d], eL, eR + d);
+    for (int k = d; k >= 2; k--) {
+        const int r0 = r[k - 1], n = h->n1[k], r1 = r[k];
+        const double *U = core_dev(h, k);
+        hipLaunchKernelGGL(k_sqn_w, dim3((unsigned)(n * r0)), dim3(128), 0, h->stream, U, RM, SS, (size_t)1, r1, n, row(0, k - 1), row(1, k - 1), (const double *)(PR + pl.proff[k]), Y);
+        hipLaunchKernelGGL(k_sqn_p, dim3((r0 + 15) / 16, (r0 + 15) / 16, n), dim3(256), 0, h->stream, U, RM, SS, (size_t)1, r1, r0, (const double *)Y, n, Part);
+        hipLaunchKernelGGL(k_sqn_pow2, dim3(1), dim3(1024), 0, h->stream, r0 * r0, n, (const double *)Part, PR + pl.proff[k - 1], (const int *)(eR + k), eR + k - 1);
+    }
+    for (int k = 1; k <= d; k++) {
+        const int r0 = r[k - 1], n = h->n1[k], r1 = r[k];
+        const double *U = core_dev(h, k);
+        hipLaunchKernelGGL(k_sqn_w, dim3((unsigned)(n * r1)), dim3(128), 0, h->stream, U, RM, (size_t)1, SS, r0, n, row(0, k - 1), row(1, k - 1), (const double *)(PLs + pl.proff[k - 1]), Y);
+        hipLaunchKernelGGL(k_sqn_p, dim3((r1 + 15) / 16, (r1 + 15) / 16, n), dim3(256), 0, h->stream, U, RM, (size_t)1, SS, r0, r1, (const double *)Y, n, Part);
+        hipLaunchKernelGGL(k_sqn_pow2, dim3(1), dim3(1024), 0, h->stream, r1 * r1, n, (const double *)Part, PLs + pl.proff[k], (const int *)(eL + k - 1), eL + k);
+    }
+    if ((rc = marks.mark(h->stream, SQT_CHAINS))) return rc;
+    // the band of every mode's reduced density matrix: the exact kernels in both modes
+    if (want_band) {
+        for (int k = 1; k <= d; k++) {
+            const int r0 = r[k - 1], n = h->n1[k], r1 = r[k];
+            const double *U = core_dev(h, k);
+            const long long tot = (long long)r0 * n * r1;
+            hipLaunchKernelGGL(k_sqm_w, dim3((unsigned)(n * r1), 1), dim3(128), 0, h->stream, U, RM, (size_t)1, SS, r0, n, (const double *)nullptr, (const double *)nullptr,
+                               (const double *)(PLs + pl.proff[k - 1]), (size_t)0, Y, (size_t)0);
+            hipLaunchKernelGGL(k_sqm_d0, dim3((unsigned)std::min<long long>((tot + 255) / 256, 4096)), dim3(256), 0, h->stream, (long long)r0 * n, r1, (const double *)Y,
+                               (const double *)(PR + pl.proff[k]), Y2);
+            hipLaunchKernelGGL(k_sqm_band, dim3(n, 2), dim3(128), 0, h->stream, U, RM, SS, r0, n, r1, (const double *)Y2, band + 2 * pl.noff[k - 1]);
+        }
+        if ((rc = marks.mark(h->stream, SQT_BAND))) return rc;
+    }
+    // one left step of bc members: P (member stride pst) through mode k with the rows (xd, xo) into dst (compact r1 x r1 each), the
+    // exponents ein[c * est] + ex into eout[c]
+    auto left_step = [&](int k, const double *xd, const double *xo, const double *P, size_t pst, int bc, double *dst, const int *ein, int est, int *eout) {
+        const int r0 = r[k - 1], n = h->n1[k], r1 = r[k];
+        const double *U = core_dev(h, k);
+        const size_t ost = (size_t)r0 * n * r1;
+        if (!mfma) {
+            hipLaunchKernelGGL(k_sqm_w, dim3((unsigned)(n * r1), bc), dim3(128), 0, h->stream, U, RM, (size_t)1, SS, r0, n, xd, xo, P, pst, Wb, ost);
+            hipLaunchKernelGGL(k_sqm_p, dim3((r1 + 15) / 16, (r1 + 15) / 16, n * bc), dim3(256), 0, h->stream, U, RM, (size_t)1, SS, r0, r1, (const double *)Wb, ost, n, CPart);
+            hipLaunchKernelGGL(k_sqm_pow2, dim3(bc), dim3(1024), 0, h->stream, r1 * r1, n, (const double *)CPart, dst, ein, est, eout, 1, 1);
+        } else {
+            const int nt = (r1 + 15) / 16;
+            hipLaunchKernelGGL(k_sqm_w_mfma, dim3((unsigned)((n * r1 + TTX_SQM_TILE_COLS - 1) / TTX_SQM_TILE_COLS), (r0 + 15) / 16, bc), dim3(256), 0, h->stream, U, RM, (size_t)1, SS, r0, n, r1,
+                               xd, xo, P, pst, Wb, ost);
+            hipLaunchKernelGGL(k_sqm_p_mfma, dim3((nt * nt + 3) / 4, bc), dim3(256), 0, h->stream, U, RM, (size_t)1, SS, r0, r1, (const double *)Wb, ost, n, CPart, (size_t)r1 * r1);
+            hipLaunchKernelGGL(k_sqm_pow2, dim3(bc), dim3(1024), 0, h->stream, r1 * r1, 1, (const double *)CPart, dst, ein, est, eout, 1, 1);
+        }
+    };
+    // the right matrix RA_(j-1): the right step with the rows (xd, xo) from PR_j, the sum alone
+    auto right_matrix = [&](int j, const double *xd, const double *xo, double *out) {
+        const int r0 = r[j - 1], n = h->n1[j], r1 = r[j];
+        const double *U = core_dev(h, j);
+        hipLaunchKernelGGL(k_sqn_w, dim3((unsigned)(n * r0)), dim3(128), 0, h->stream, U, RM, SS, (size_t)1, r1, n, xd, xo, (const double *)(PR + pl.proff[j]), Y);
+        hipLaunchKernelGGL(k_sqn_p, dim3((r0 + 15) / 16, (r0 + 15) / 16, n), dim3(256), 0, h->stream, U, RM, SS, (size_t)1, r1, r0, (const double *)Y, n, Part);
+        hipLaunchKernelGGL(k_sqm_pow2, dim3(1), dim3(1024), 0, h->stream, r0 * r0, n, (const double *)Part, out, (const int *)nullptr, 0, (int *)nullptr, 0, 0);
+    };
+    std::vector<size_t> doff(nsel + 1, 0);                                      // per selected l: m1's product, the diagonal's, then the pairs below it
+    for (int x = 0; x < nsel; x++) doff[x + 1] = doff[x] + 2 + (size_t)x;
+    if (nsel) {
+        const int smax = pl.sel.back() + 1;                                     // 1-based
+        int cnt = 0, cur = 0;
+        for (int j = pl.sel[0] + 1; j <= smax; j++) {
+            const bool is_sel = selected[j - 1] != 0;
+            const int r0 = r[j - 1], r1 = r[j];
+            if (is_sel) {
+                const size_t o = doff[cnt];
+                right_matrix(j, row(2, j - 1), row(3, j - 1), RA);
+                hipLaunchKernelGGL(k_sqm_dot, dim3(1), dim3(256), 0, h->stream, r0 * r0, (const double *)(PLs + pl.proff[j - 1]), (size_t)0, (const double *)RA, (const int *)nullptr, dots + o, edots + o);
+                if (cnt) hipLaunchKernelGGL(k_sqm_dot, dim3(cnt), dim3(256), 0, h->stream, r0 * r0, (const double *)Cc[cur], (size_t)r0 * r0, (const double *)RA, (const int *)ce, dots + o + 2, edots + o + 2);
+                if (row(4, j - 1)) {
+                    right_matrix(j, row(4, j - 1), row(5, j - 1), RA2);
+                    hipLaunchKernelGGL(k_sqm_dot, dim3(1), dim3(256), 0, h->stream, r0 * r0, (const double *)(PLs + pl.proff[j - 1]), (size_t)0, (const double *)RA2, (const int *)nullptr, dots + o + 1, edots + o + 1);
+                }
+                if ((rc = marks.mark(h->stream, SQT_CLOSE))) return rc;
+            }
+            if (j == smax) break;
+            for (int c0 = 0; c0 < cnt; c0 += pl.batch) {
+                const int bc = std::min(pl.batch, cnt - c0);
+                left_step(j, row(0, j - 1), row(1, j - 1), Cc[cur] + (size_t)c0 * r0 * r0, (size_t)r0 * r0, bc, Cc[cur ^ 1] + (size_t)c0 * r1 * r1, ce + c0, 1, ce + c0);
+            }
+            if (is_sel) {
+                left_step(j, row(2, j - 1), row(3, j - 1), PLs + pl.proff[j - 1], 0, 1, Cc[cur ^ 1] + (size_t)cnt * r1 * r1, eL + j - 1, 0, ce + cnt);
+                cnt++;
+            }
+            cur ^= 1;
+            if ((rc = marks.mark(h->stream, SQT_CARRY))) return rc;
+        }
+    }
+    double zm = 0.0;
+    std::vector<int> he(2 * (size_t)(d + 1)), hed(std::max<size_t>(1, pl.ndots), 0);
+    std::vector<double> hdots(std::max<size_t>(1, pl.ndots), 0.0), hband(want_band ? 2 * pl.nsum : 0);
+    HIPCHECK(hipMemcpyAsync(&zm, PLs + pl.proff[d], sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(he.data(), eL, sizeof(int) * he.size(), hipMemcpyDeviceToHost, h->stream));
+    if (pl.ndots) {
+        HIPCHECK(hipMemcpyAsync(hdots.data(), dots, sizeof(double) * pl.ndots, hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(hipMemcpyAsync(hed.data(), edots, sizeof(int) * pl.ndots, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (want_band) HIPCHECK(hipMemcpyAsync(hband.data(), band, sizeof(double) * hband.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    if ((rc = marks.sum(h->sqm.ms))) return rc;
+    HIPCHECK(hipGetLastError());
+    // nothing has been written so far; from here on nothing can fail
+    const long long ze = he[d];
+    const int *heL = he.data(), *heR = he.data() + d + 1;
+    if (z_mant) *z_mant = zm;
+    if (z_exp) *z_exp = ze;
+    if (want_band)
+        for (int k = 0; k < d; k++) {
+            const int n = h->n1[k + 1];
+            const double *b = hband.data() + 2 * pl.noff[k];
+            for (int i = 0; i < n; i++) {
+                bd[pl.noff[k] + i] = sqm_ratio(b[i], zm, heL[k], heR[k + 1], ze);
+                bo[pl.noff[k] + i] = i + 1 < n ? sqm_ratio(b[n + i], zm, heL[k], heR[k + 1], ze) : 0.0;
+            }
+        }
+    if (m1) std::fill(m1, m1 + d, 0.0);
+    if (c2) std::fill(c2, c2 + (size_t)d * d, 0.0);
+    for (int x = 0; x < nsel; x++) {
+        const int l = pl.sel[x];
+        const size_t o = doff[x];
+        if (m1) m1[l] = sqm_ratio(hdots[o], zm, heL[l], heR[l + 1], ze);
+        if (!c2) continue;
+        if (a2d && a2d[l]) c2[(size_t)l * d + l] = sqm_ratio(hdots[o + 1], zm, heL[l], heR[l + 1], ze);
+        for (int y = 0; y < x; y++) {
+            const int k = pl.sel[y];
+            c2[(size_t)k * d + l] = c2[(size_t)l * d + k] = sqm_ratio(hdots[o + 2 + y], zm, hed[o + 2 + y], heR[l + 1], ze);
+        }
+    }
+    return TTX_OK;
+}
+extern "C" int ttx_sq_moments_last(const ttx_engine *h, double *ms_chains, double *ms_band, double *ms_carry, double *ms_close, double *flops, int64_t *steps, int32_t *mode_ran)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_sq_moments_last: null engine");
+    if (ms_chains) *ms_chains = h->sqm.ms[SQT_CHAINS];
+    if (ms_band) *ms_band = h->sqm.ms[SQT_BAND];
+    if (ms_carry) *ms_carry = h->sqm.ms[SQT_CARRY];
+    if (ms_close) *ms_close = h->sqm.ms[SQT_CLOSE];
+    if (flops) *flops = h->sqm.flops;
+    if (steps) *steps = h->sqm.steps;
+    if (mode_ran) *mode_ran = h->sqm.mode;
+    return TTX_OK;
 }
 
 // ---- the largest elements of the resident train (ttx_topk.h)--------------------------------------------------------------------

@@ -18,6 +18,7 @@
 #include "ttx_roundsum.h"           // RsBlk, TTX_RS_*
 #include "ttx_qr_plan.h"            // TTX_LDS_DEVICE
 #include "ttx_sq_norm.h"            // SqnCore, TTX_SQN_*
+#include "ttx_sq_moments.h"         // TTX_SQM_*
 
 #if defined(__HIPCC__)
 #define TTX_OP_HD __host__ __device__ inline
@@ -614,3 +615,85 @@ inline double sqn_scale(double z_mant, long long z_exp, double gvol, double coef
 {
     return ldexp((2.0 * coef) / sqn_den(z_mant, z_exp, gvol), sqn_clamp_exp(el + er - z_exp));
 }
+
+// ---- ttx_sq_moments (ttx_sq_moments.h) -----------------------------------------------------------------------------------------------
+// break-even of TTX_EVAL_AUTO in flops per call (chains, right matrices, carried steps and band, SqmPlan::flops).  PROVISIONAL: measured
+// (profiles/sq_moments_mi355x.txt), the batched exact kernels are faster than the present MFMA kernels on both trains timed, at 1.5e10 and
+// at 3.6e12 flops, so no crossing has been seen and the value lies above both; TTX_SQM_AUTO_FLOPS in the environment replaces it
+#define TTX_SQM_AUTO_FLOPS 1.0e13
+// what the W buffer and the stored partial matrices of one batched launch may take.  An all-pairs call on d = 255, r = 64, n = 101 would
+// want 0.8 GB for W alone; under the cap it is cut into batches of 38 carried matrices
+#define TTX_SQM_CAP_BYTES ((size_t)256 << 20)
+enum SqmRefusal { SQM_OK, SQM_RANK, SQM_BOUNDARY, SQM_NOTHING };        // SQM_NOTHING: every output null
+struct SqmPlan {
+    SqmRefusal refusal = SQM_OK;
+    int rmax = 0, nmax = 1, eff = TTX_EVAL_EXACT;
+    std::vector<int> sel;                               // the selected modes, 0-based, ascending (empty: no moments asked)
+    std::vector<size_t> proff, noff;                    // [d + 2], [d + 1]: as SqnPlan's; the PL store has the PR store's layout
+    size_t nsum = 0;
+    long long steps = 0;                                // carried chain steps: sum over selected k below the largest of (l_max(k) - k)
+    int members = 0, batch = 1;                         // the most carried matrices alive at once; members per launch
+    size_t per_member = 0;                              // bytes of W and partial matrices of one member
+    size_t ndots = 0;                                   // closing products: per selected l the pairs below it, m1 and the diagonal of c2
+    size_t b_pr = 0, b_pl = 0, b_ex = 0, b_y = 0, b_part = 0, b_carry = 0, b_w = 0, b_cpart = 0, b_ra = 0, b_dots = 0, b_band = 0;
+    double flops = 0.0;
+    // members [first, first + count) of the launch number x over m alive members
+    int cuts(int m) const { return (m + batch - 1) / batch; }
+};
+// n[0 .. d-1], r[0 .. d]; selected[k] != 0: mode k has an observable (null: no moments); want_band, want_mom: which outputs are asked;
+// batch_env: TTX_SQM_BATCH (0: not set); auto_flops: the break-even in force
+inline SqmPlan sqm_plan(int d, const int *n, const int *r, const unsigned char *selected, bool want_band, bool want_mom, bool want_z, int mode, long long batch_env,
+                        double auto_flops = TTX_SQM_AUTO_FLOPS)
+{
+    SqmPlan p;
+    p.rmax = *std::max_element(r, r + d + 1);
+    if (p.rmax > 128) { p.refusal = SQM_RANK; return p; }
+    if (r[0] != 1 || r[d] != 1) { p.refusal = SQM_BOUNDARY; return p; }
+    if (!want_band && !want_mom && !want_z) { p.refusal = SQM_NOTHING; return p; }
+    if (selected && want_mom) for (int k = 0; k < d; k++) if (selected[k]) p.sel.push_back(k);
+    p.proff.assign(d + 2, 0); p.noff.assign(d + 1, 0);
+    size_t ymax = 1, pmax = 1, p1max = 1;
+    for (int k = 0; k < d; k++) {
+        const size_t r0 = (size_t)r[k], nk = (size_t)n[k], r1 = (size_t)r[k + 1];
+        p.noff[k + 1] = p.noff[k] + nk;
+        p.nmax = std::max(p.nmax, n[k]);
+        ymax = std::max(ymax, r0 * nk * r1);
+        pmax = std::max(pmax, nk * std::max(r0 * r0, r1 * r1));
+        p1max = std::max(p1max, r1 * r1);
+        const double fw = 2.0 * (double)r0 * (double)r0 * (double)nk * (double)r1, fp = 2.0 * (double)r0 * (double)nk * (double)r1 * (double)r1;
+        p.flops += 2.0 * (fw + fp);                                             // the two chains
+        if (want_band) p.flops += fw + 2.0 * fp;                                // T, D0 and the band's brackets (at most)
+    }
+    for (int k = 0; k <= d; k++) p.proff[k + 1] = p.proff[k] + (size_t)r[k] * (size_t)r[k];
+    p.nsum = p.noff[d];
+    const int nsel = (int)p.sel.size(), smax = nsel ? p.sel.back() : -1;
+    for (int x = 0; x < nsel; x++) {
+        const int k = p.sel[x];
+        const double fr = 2.0 * (double)r[k] * n[k] * r[k + 1] * ((double)r[k] + r[k + 1]);
+        p.flops += 2.0 * fr;                                                    // RA and RA2
+        p.ndots += 2 + (size_t)x;
+        if (k == smax) continue;
+        p.steps += smax - k;
+        for (int j = k; j < smax; j++) p.flops += 2.0 * (double)r[j] * n[j] * r[j + 1] * ((double)r[j] + r[j + 1]);
+    }
+    p.members = nsel > 1 ? nsel - 1 : 0;
+    p.eff = op_mode_eff(mode, p.flops, auto_flops);
+    p.per_member = sizeof(double) * (ymax + (p.eff == TTX_EVAL_MFMA ? p1max : pmax));
+    long long b = std::max<long long>(1, (long long)(TTX_SQM_CAP_BYTES / p.per_member));
+    b = std::min<long long>(b, 65535 / p.nmax);                                 // k_sqm_p's grid: n members on the z axis
+    if (batch_env >= 1) b = std::min(b, batch_env);
+    p.batch = (int)std::max<long long>(1, std::min<long long>(b, std::max(1, p.members)));
+    p.b_pr = p.b_pl = sizeof(double) * p.proff[d + 1];
+    p.b_ex = sizeof(int) * 2 * (size_t)(d + 1);
+    p.b_y = sizeof(double) * 2 * ymax;                                          // Y / W of an unbatched step; T and D0 of the band
+    p.b_part = sizeof(double) * pmax;
+    p.b_carry = sizeof(double) * 2 * (size_t)p.members * p.rmax * p.rmax + sizeof(int) * (size_t)std::max(1, p.members);
+    p.b_w = p.members ? (size_t)p.batch * sizeof(double) * ymax : 0;
+    p.b_cpart = p.members ? (size_t)p.batch * (p.per_member - sizeof(double) * ymax) : 0;
+    p.b_ra = sizeof(double) * 2 * (size_t)p.rmax * p.rmax;
+    p.b_dots = (sizeof(double) + sizeof(int)) * std::max<size_t>(1, p.ndots);
+    p.b_band = want_band ? sizeof(double) * 2 * p.nsum : 0;
+    return p;
+}
+// what the host forms from a product and its exponents: ldexp(dot / z_mant, e_left + e_right - z_exp), the exponent clamped
+inline double sqm_ratio(double dot, double z_mant, long long el, long long er, long long z_exp) { return ldexp(dot / z_mant, sqn_clamp_exp(el + er - z_exp)); }

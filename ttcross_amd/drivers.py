@@ -1703,8 +1703,92 @@ def run_dirt(argv, device=0, npts=1 << 14, gamma=1e-4, keep=False):
     return res
 
 
+def run_moments(argv, device=0, repeats=3, tt=None, nsample=100000):
+    """moments WORKLOAD [NSEL] [MODE]: the trains of the tijk sub-command, taken as the square root of a density on equidistant nodes
+    of [0, 1].  NSEL modes spread evenly over the train are selected (0 or absent: all).  One JSON line: the sq_moments call with the
+    hat functions' moment matrices (the median call and the chains, band, carry and close parts from sq_moments_last, the carried
+    steps and the flops per second of the carry part), the same call with TTX_SQM_BATCH = 1 (a launch per carried matrix), the host
+    route (every core to the host, the time of numpy einsum chain steps on the widest core times the steps of the call: an estimate, the
+    full route is not run), and the mean and covariance of density_moments against those of NSAMPLE points of sample_sq_real in
+    standard errors."""
+    import json
+    import os
+    import time
+    import torch
+    from .engine import mass_tridiag, moment_tridiag
+    torch.cuda.init()          # a torch that brings its own HIP runtime must initialise its device before the engine's library does
+    workload = argv[0]
+    nsel = int(argv[1]) if len(argv) > 1 else 0
+    mode = argv[2] if len(argv) > 2 else "auto"
+    tt = tt or tijk_train(workload, device=device)
+    d = tt.d
+    nodes = [np.linspace(0.0, 1.0, int(nk)) for nk in tt._n]
+    sel = list(range(d)) if nsel <= 0 or nsel >= d else sorted(set(int(round(v)) for v in np.linspace(0, d - 1, nsel)))
+    md, mo = mass_tridiag(nodes)
+    ad, ao, a2d, a2o = [None] * d, [None] * d, [None] * d, [None] * d
+    for k in sel:
+        ad[k], ao[k] = moment_tridiag(nodes[k], 1)
+        a2d[k], a2o[k] = moment_tridiag(nodes[k], 2)
+
+    def timed():
+        tt.sq_moments(md, mo, ad, ao, a2d, a2o, mode=mode)                      # warm-up
+        ms, lasts = [], []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            res = tt.sq_moments(md, mo, ad, ao, a2d, a2o, mode=mode)
+            ms.append((time.perf_counter() - t0) * 1e3)
+            lasts.append(tt.sq_moments_last())
+        med = {k: float(np.median([x[k] for x in lasts])) for k in ("ms_chains", "ms_band", "ms_carry", "ms_close")}
+        return res, float(np.median(ms)), med, lasts[-1]
+
+    res, ms_call, med, last = timed()
+    r = tt.ranks().astype(np.int64)
+    n = np.asarray(tt._n, dtype=np.int64)
+    smax = max(sel)
+    carry_flops = float(sum(2.0 * r[j] * n[j] * r[j + 1] * (r[j] + r[j + 1]) for k in sel if k < smax for j in range(k, smax)))
+    line = dict(workload=workload, d=d, max_rank=int(r.max()), selected=len(sel), mode_asked=mode, mode=last["mode"], steps=last["steps"], flops=last["flops"],
+                ms_call=ms_call, **med, carry_flops=carry_flops, carry_tflops=carry_flops / (med["ms_carry"] * 1e-3) / 1e12 if med["ms_carry"] > 0 else None, z_exp=res["z_exp"])
+    old = os.environ.get("TTX_SQM_BATCH")
+    os.environ["TTX_SQM_BATCH"] = "1"
+    try:
+        res1, ms1, med1, _ = timed()
+    finally:
+        if old is None:
+            del os.environ["TTX_SQM_BATCH"]
+        else:
+            os.environ["TTX_SQM_BATCH"] = old
+    line.update(ms_call_batch1=ms1, ms_carry_batch1=med1["ms_carry"], batch1_equal=bool(np.array_equal(res["c2"], res1["c2"]) and np.array_equal(res["m1"], res1["m1"])))
+    t0 = time.perf_counter()
+    cores = [tt.core(k + 1) for k in range(d)]
+    ms_get = (time.perf_counter() - t0) * 1e3
+    kw = int(np.argmax(r[:-1] * n * r[1:]))
+    c, M = cores[kw], np.diag(md[kw]) + np.diag(mo[kw], 1) + np.diag(mo[kw], -1)
+    P = np.ones((c.shape[0], c.shape[0]))
+    t0 = time.perf_counter()
+    for _ in range(3):
+        np.einsum("ac,aib,ij,cjd->bd", P, c, M, c, optimize=True)
+    ms_step = (time.perf_counter() - t0) * 1e3 / 3.0
+    line.update(host_cores_get_ms=ms_get, host_step_ms_widest_core=ms_step, host_route_ms_estimated=ms_get + ms_step * (2 * d + last["steps"]))
+    dm = tt.density_moments(nodes, select=sel, mode=mode)
+    u = _seeded_uniforms(nsample, d, torch.device("cuda", device))
+    x = tt.sample_sq_real(u, nodes, mode=mode, want=("x",))["x"].cpu().numpy()
+    x = x[~np.isnan(x[:, 0])][:, sel]
+    sm = x.mean(axis=0)
+    y = x - sm
+    sc = (y.T @ y) / x.shape[0]
+    se_m = np.sqrt(np.maximum(np.diag(dm["cov"]), 0.0) / x.shape[0])
+    se_c = np.sqrt(np.maximum(np.einsum("pk,pl->kl", y * y, y * y) / x.shape[0] - sc * sc, 0.0) / x.shape[0])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        line.update(samples=int(x.shape[0]), alpha=dm["alpha"], logz=dm["logz"], mean_worst_se=float(np.nanmax(np.abs(sm - dm["mean"]) / se_m)),
+                    cov_worst_se=float(np.nanmax(np.abs(sc - dm["cov"]) / se_c)), cov_finite=bool(np.isfinite(dm["cov"]).all()))
+    print(json.dumps(line))
+    return line
+
+
 if __name__ == "__main__":
-    if sys.argv[1] == "dirt":
+    if sys.argv[1] == "moments":
+        run_moments(sys.argv[2:])
+    elif sys.argv[1] == "dirt":
         run_dirt(sys.argv[2:])
     elif sys.argv[1] == "roundsum":
         run_roundsum(sys.argv[2:])

@@ -188,6 +188,8 @@ def load_library():
                                    POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double)]
     L.ttx_sq_nll_batch_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(_Basis), c_void_p, c_double, _rows, _rows, c_double, c_int32,
                                        POINTER(c_double), POINTER(c_double), c_void_p, c_void_p]
+    L.ttx_sq_moments.argtypes = [c_void_p] + [_rows] * 6 + [c_int32, POINTER(c_double), POINTER(c_int64)] + [POINTER(c_double)] * 4
+    L.ttx_sq_moments_last.argtypes = [c_void_p] + [POINTER(c_double)] * 5 + [POINTER(c_int64), POINTER(c_int32)]
     L.ttx_sample.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]
     L.ttx_sample_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(c_double), POINTER(c_int32), c_void_p, c_void_p, c_void_p]
     L.ttx_sample_last.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64)]
@@ -412,6 +414,46 @@ def mass_tridiag(nodes, cond=None):
     md[0], md[-1] = h[0] / 3.0, h[-1] / 3.0
     md[1:-1] = (h[:-1] + h[1:]) / 3.0
     return md, h / 6.0
+
+
+def moment_tridiag(nodes, power, cond=None):
+    """(d, o) of the symmetric tridiagonal matrix of int x^power phi_i(x) phi_j(x) dx for the hat functions on strictly ascending
+    nodes, power 0, 1 or 2: the observables sq_moments takes for the mean (power 1) and the second moments (power 2).  Power 0 is
+    mass_tridiag(nodes, cond), bit for bit.  Closed forms, one operation at a time; on the cell [a, b] of width h:
+        power 1:  int x phi_a^2 = h (3 a + b) / 12,          int x phi_b^2 = h (a + 3 b) / 12,          int x phi_a phi_b = h (a + b) / 12
+        power 2:  int x^2 phi_a^2 = h (6 a^2 + 3 a b + b^2) / 30,  int x^2 phi_b^2 = h (a^2 + 3 a b + 6 b^2) / 30,  int x^2 phi_a phi_b = h (3 a^2 + 4 a b + 3 b^2) / 60
+    and a diagonal entry is the left cell's term plus the right cell's.  A single node t gives ([t^power], []).  Lists and cond as
+    for mass_tridiag; a mode held at x0 gives x0^power times its mass_tridiag matrix."""
+    if power not in (0, 1, 2):
+        raise ValueError("moment_tridiag: power is 0, 1 or 2")
+    if isinstance(nodes, (list, tuple)) and len(nodes) and np.ndim(nodes[0]) == 1:
+        cond = [None] * len(nodes) if cond is None else list(cond)
+        if len(cond) != len(nodes):
+            raise ValueError("moment_tridiag: one cond entry per mode expected")
+        pairs = [moment_tridiag(t, power, c) for t, c in zip(nodes, cond)]
+        return [p[0] for p in pairs], [p[1] for p in pairs]
+    if power == 0:
+        return mass_tridiag(nodes, cond)
+    t = np.ascontiguousarray(nodes, dtype=np.float64)
+    if t.ndim != 1 or t.size < 1:
+        raise ValueError("moment_tridiag: a one-dimensional array of nodes expected")
+    held = cond is not None and not np.isnan(cond)
+    if held or t.size == 1:
+        md, mo = mass_tridiag(t, cond)
+        x0 = float(cond) if held else float(t[0])
+        f = x0 if power == 1 else x0 * x0
+        return f * md, f * mo
+    a, b = t[:-1], t[1:]
+    h = b - a
+    if power == 1:
+        lo, hi, of = h * (3.0 * a + b) / 12.0, h * (a + 3.0 * b) / 12.0, h * (a + b) / 12.0
+    else:
+        aa, ab, bb = a * a, a * b, b * b
+        lo, hi, of = h * (6.0 * aa + 3.0 * ab + bb) / 30.0, h * (aa + 3.0 * ab + 6.0 * bb) / 30.0, h * (3.0 * aa + 4.0 * ab + 3.0 * bb) / 60.0
+    dg = np.empty(t.size)
+    dg[0], dg[-1] = lo[0], hi[-1]
+    dg[1:-1] = hi[:-1] + lo[1:]
+    return dg, of
 
 
 def roundsum_omega(seed, k, shape):
@@ -1594,6 +1636,126 @@ class TTCross:
         _check(load_library().ttx_sq_lognorm_grad_last(self._h, ctypes.byref(mr), ctypes.byref(ml), ctypes.byref(ma), ctypes.byref(fl), ctypes.byref(md)))
         names = {v: k for k, v in EVAL_MODES.items()}
         return dict(ms_right=mr.value, ms_left=ml.value, ms_asm=ma.value, flops=fl.value, mode=names.get(md.value))
+
+    # ---- moments and marginals of the squared density (include/ttx.h: ttx_sq_moments) ---------
+    def _opt_rows(self, who, name, dg, of):
+        """(diagonal rows, off-diagonal rows, keep) of an optional observable: a None entry of dg leaves the mode out"""
+        if dg is None:
+            return None, None, []
+        if len(dg) != self.d or (of is not None and len(of) != self.d):
+            raise ValueError(f"{who}: {self.d} rows of {name} (entries may be None) expected")
+        keep = []
+        dp, op = (POINTER(c_double) * self.d)(), (POINTER(c_double) * self.d)()
+        for k in range(self.d):
+            if dg[k] is None:
+                continue
+            a = np.ascontiguousarray(dg[k], dtype=np.float64)
+            if a.shape != (self._n[k],):
+                raise ValueError(f"{who}: {name}[{k}] must hold {self._n[k]} numbers")
+            keep.append(a)
+            dp[k] = _dp(a)
+            if of is not None and of[k] is not None:
+                b = np.ascontiguousarray(of[k], dtype=np.float64)
+                if b.shape != (max(self._n[k] - 1, 0),):
+                    raise ValueError(f"{who}: the off-diagonal of {name}[{k}] must hold {self._n[k] - 1} numbers")
+                b = np.concatenate([b, np.zeros(1)])
+                keep.append(b)
+                op[k] = _dp(b)
+        return dp, (op if of is not None else None), keep
+
+    def sq_moments(self, md, mo=None, ad=None, ao=None, a2d=None, a2o=None, mode="auto", band=True):
+        """dict(z_mant, z_exp, bd, bo, m1, c2) (include/ttx.h: ttx_sq_moments): ratios over Z = <f, f>_M = z_mant 2^z_exp of the squared
+        train.  md, mo as for sq_lognorm_grad.  ad, ao: per mode the diagonal and off-diagonal of a symmetric tridiagonal observable A_k
+        (moment_tridiag gives those of x and x^2), an entry None where the mode is not selected; m1[k] = <f, A_k f>_M / Z, c2[k][l] =
+        <f, (A_k x A_l) f>_M / Z for selected k != l, c2[k][k] = <f, A2_k f>_M / Z with A2 from a2d, a2o (0.0 where not given); unselected
+        entries are 0.0 (ad=None: m1 and c2 are None).  bd, bo: per mode the diagonal and off-diagonal of the reduced density matrix
+        B_k / Z (band=False: None).  sq_moments_last() tells what ran."""
+        L, m = load_library(), _eval_mode(mode)
+        dp, op, keep = self._tridiag_rows("sq_moments", md, mo)
+        adp, aop, keep_a = self._opt_rows("sq_moments", "ad", ad, ao)
+        a2p, a2op, keep_b = self._opt_rows("sq_moments", "a2d", a2d, a2o)
+        zm, ze = c_double(), c_int64()
+        nsum = int(sum(self._n))
+        bd = np.zeros(nsum) if band else None
+        bo = np.zeros(nsum) if band else None
+        m1 = np.zeros(self.d) if ad is not None else None
+        c2 = np.zeros((self.d, self.d)) if ad is not None else None
+        _check(L.ttx_sq_moments(self._h, dp, op, adp, aop, a2p, a2op, m, ctypes.byref(zm), ctypes.byref(ze),
+                                _dp(bd) if band else None, _dp(bo) if band else None, _dp(m1) if ad is not None else None, _dp(c2) if ad is not None else None))
+        cut = np.cumsum([int(v) for v in self._n])[:-1]
+        return dict(z_mant=zm.value, z_exp=ze.value, bd=np.split(bd, cut) if band else None, bo=np.split(bo, cut) if band else None, m1=m1, c2=c2)
+
+    def sq_moments_last(self):
+        """dict(ms_chains, ms_band, ms_carry, ms_close, flops, steps, mode) of the last sq_moments on this engine (include/ttx.h:
+        ttx_sq_moments_last); steps counts the carried chain steps"""
+        a, b, c, e, fl, st, md = c_double(), c_double(), c_double(), c_double(), c_double(), c_int64(), c_int32()
+        _check(load_library().ttx_sq_moments_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(e), ctypes.byref(fl), ctypes.byref(st), ctypes.byref(md)))
+        names = {v: k for k, v in EVAL_MODES.items()}
+        return dict(ms_chains=a.value, ms_band=b.value, ms_carry=c.value, ms_close=e.value, flops=fl.value, steps=int(st.value), mode=names.get(md.value))
+
+    def _density_frame(self, who, nodes, gamma, cond):
+        """(node rows, cond as floats with NaN for a drawn mode, the drawn modes, V) for the density over the hat functions on nodes"""
+        rows, _ = self._node_rows(nodes, who)
+        c = np.full(self.d, np.nan) if cond is None else np.array([np.nan if v is None else float(v) for v in cond], dtype=np.float64)
+        if c.size != self.d:
+            raise ValueError(f"{who}: {self.d} cond entries expected")
+        if not (gamma >= 0.0 and np.isfinite(gamma)):
+            raise ValueError(f"{who}: gamma is negative or not finite")
+        drawn = [k for k in range(self.d) if np.isnan(c[k]) and rows[k].size > 1]
+        vol = float(np.prod([rows[k][-1] - rows[k][0] for k in drawn]))
+        return rows, c, drawn, vol
+
+    @staticmethod
+    def _alpha_logz(z_mant, z_exp, gvol):
+        """alpha = z_mant / (z_mant + ldexp(gvol, -z_exp)), the weight of f^2 in q, and log(Z + gvol)"""
+        den = z_mant + float(np.ldexp(gvol, int(max(-100000, min(100000, -z_exp)))))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return float(np.float64(z_mant) / np.float64(den)), float(z_exp * 0.6931471805599453 + np.log(np.float64(den)))
+
+    def density_moments(self, nodes, gamma=0.0, cond=None, select=None, mode="auto"):
+        """dict(mean, cov, alpha, logz, modes) of q = (f^2 + gamma) / (Z + gamma V) itself, f the piecewise-multilinear interpolant of
+        the train of grid values on nodes (sample_sq_real's density): the exact mean and covariance of the drawn modes named in select
+        (0-based; None: every drawn mode; held modes and modes of one node are left out), from one sq_moments call with the hat
+        functions' moment matrices.  alpha = Z / (Z + gamma V) weighs the f^2 part, the uniform box's analytic moments take the rest:
+        E_q[g] = alpha E_f2[g] + (1 - alpha) E_unif[g]; cov = E[x_k x_l] - E[x_k] E[x_l].  logz = log(Z + gamma V)."""
+        rows, c, drawn, vol = self._density_frame("density_moments", nodes, gamma, cond)
+        sel = drawn if select is None else [int(k) for k in select]
+        if any(k not in drawn for k in sel) or len(set(sel)) != len(sel) or not sel:
+            raise ValueError("density_moments: select names drawn modes, each once")
+        sel = sorted(sel)
+        md, mo = mass_tridiag(rows, list(c))
+        ad, ao, a2d, a2o = [None] * self.d, [None] * self.d, [None] * self.d, [None] * self.d
+        for k in sel:
+            ad[k], ao[k] = moment_tridiag(rows[k], 1)
+            a2d[k], a2o[k] = moment_tridiag(rows[k], 2)
+        res = self.sq_moments(md, mo, ad, ao, a2d, a2o, mode=mode, band=False)
+        alpha, logz = self._alpha_logz(res["z_mant"], res["z_exp"], gamma * vol)
+        lo, hi = np.array([rows[k][0] for k in sel]), np.array([rows[k][-1] for k in sel])
+        um, u2 = 0.5 * (lo + hi), (lo * lo + lo * hi + hi * hi) / 3.0
+        ix = np.ix_(sel, sel)
+        usec = np.outer(um, um)
+        usec[np.diag_indices(len(sel))] = u2
+        mean = alpha * res["m1"][sel] + (1.0 - alpha) * um
+        sec = alpha * res["c2"][ix] + (1.0 - alpha) * usec
+        return dict(mean=mean, cov=sec - np.outer(mean, mean), alpha=alpha, logz=logz, modes=sel)
+
+    def sq_marginal_pdf(self, k, x, nodes, gamma=0.0, cond=None):
+        """The one-mode marginal density of q (density_moments' q) in the drawn mode k (0-based) at the real points x: from the band of
+        the reduced density matrix, alpha phi(x)^T (B_k / Z) phi(x) with the two hat functions phi of x's cell, plus the uniform part
+        (1 - alpha) / (b_k - a_k).  0.0 outside the nodes' range."""
+        rows, c, drawn, vol = self._density_frame("sq_marginal_pdf", nodes, gamma, cond)
+        if k not in drawn:
+            raise ValueError("sq_marginal_pdf: k names a drawn mode")
+        md, mo = mass_tridiag(rows, list(c))
+        res = self.sq_moments(md, mo, mode="exact", band=True)
+        alpha, _ = self._alpha_logz(res["z_mant"], res["z_exp"], gamma * vol)
+        t, bd, bo = rows[k], res["bd"][k], res["bo"][k]
+        x = np.asarray(x, dtype=np.float64)
+        cell = np.clip(np.searchsorted(t, x, side="right") - 1, 0, t.size - 2)
+        p1 = (x - t[cell]) / (t[cell + 1] - t[cell])
+        p0 = 1.0 - p1
+        pdf = alpha * (bd[cell] * p0 * p0 + 2.0 * bo[cell] * p0 * p1 + bd[cell + 1] * p1 * p1) + (1.0 - alpha) / (t[-1] - t[0])
+        return np.where((x >= t[0]) & (x <= t[-1]), pdf, 0.0)
 
     def sq_nll(self, x, basis, gamma, md, mo=None, gvol=0.0, w=None, mode="auto", out=None):
         """dict(nll, logz, val, g) (include/ttx.h: ttx_sq_nll_batch): the negative log-likelihood -sum_p w_p log(f(x_p)^2 + gamma) +
