@@ -574,6 +574,62 @@ int ttx_basis_core_grad_last     (const ttx_engine *h, double *ms_table, double 
 int ttx_cores_axpy    (ttx_engine *h, const double *alpha /* [d], host */, const double *g);
 int ttx_cores_axpy_dev(ttx_engine *h, const double *alpha /* [d], host */, const double *g_dev);
 
+/* Ranks grown from data: gradient enrichment (ttcross_amd/csrc/ttx_basis_enrich.h).  Everything above works at the ranks the train has;
+ * this call appends to every bond the dominant directions of the TWO-SITE gradient that lie outside the range of the bond's left core,
+ * and pads the right neighbour with zeros: the function does not change, and the next fit step can move into the new directions (the
+ * enrichment of AMEn-style solvers and of rank-adaptive Riemannian completion).  The result is a NEW single-process engine without
+ * integrand, as ttx_lincomb's; the source is untouched.  d >= 2.  phi, X_i, L_i and their operation orders are those of
+ * ttx_basis_core_grad_batch; c[p] is the derivative of the caller's loss with respect to f(x_p); numpy restates all of it
+ * (tests/enrich_ref.py).
+ *  1. Directions per bond i = 1 .. d-1, on the host before any launch:
+ *       k_i = max(0, min(add[i-1], r(i-1) n(i) - r(i), n(i+1) r(i+1), 128 - r(i))).
+ *     (r(i) + k_i) times the largest mode must not exceed what a new engine stores (maxrank*n); a violation refuses the call.
+ *  2. Sketch matrix Omega_i (k_i, n(i+1), r(i+1)), uniform on (-1, 1): entry (q, j, b) is ttx_lincomb_round's step-2 formula at
+ *     (seed, k = i, x = q + k_i (j + n(i+1) b)).  It is generated where it is used and never stored.
+ *  3. Sketch state z_q(p) = sum_j phi_(i+1, j)(p) t_j(q), t_j(q) = sum_b Omega_i(q, j, b) X_(i+1)(p, b): both sums from 0.0, over
+ *     ascending b and ascending j -- the backward step of the value chain with Omega_i in place of a core.  X_d = (1).
+ *  4. Sketch of the two-site gradient: Y_i(a, j, q) = sum_p ((c[p] * L_i(p, a)) * (phi_(i, j)(p) * z_q(p))), the terms added over ascending
+ *     p from 0.0, brackets as written: G_i's formula with z for X_i.  Y_i = G2_i Omega_i^T for the two-site gradient
+ *     G2_i = sum_p c_p (L_i (x) phi_i)(phi_(i+1) (x) X_(i+1))^T, which is never formed.
+ *  5. Per bond, on the device: max |Y_i|, whether every entry is finite, ynorm2_i = sum Y^2 by ttx_cores_dot's rule with
+ *     tot = r(i-1) n(i) k_i.  A bond whose sketch is all zero or not finite takes no direction: added = 0, its gain row 0.0 for a zero
+ *     sketch and NaN for one that is not finite.  Otherwise added = k_i.
+ *  6. New directions: Q_i = the columns r(i) + 1 .. r(i) + k_i of the explicit Householder Q of the tall matrix [U_i^L | 2^-e Y_i]
+ *     (U_i^L the r(i-1) n(i) x r(i) unfolding, (f, e) = frexp(max |Y_i|)), by the engine's own QR, the one of ttx_lincomb_round's step 4.
+ *     gain_i[q] = ldexp(|R(r(i) + q, r(i) + q)|, e).  The first r(i) columns of Q span a space that contains range(U_i^L), so Q_i is
+ *     orthonormal and orthogonal to it, also when U_i^L is rank-deficient.
+ *  7. New core i, shape (r(i-1) + added(i-1), n(i), r(i) + added(i)): block [:r(i-1), :, :r(i)] is U_i bit for bit, block
+ *     [:r(i-1), :, r(i):] is Q_i, all rows from r(i-1) on are 0.0.
+ * The new train is the same function: in exact mode its value chain equals the source's at any point with a finite chain, the
+ * enlargement adds only x + 0.0 and 0.0 * y terms.  At a stationary point of a fixed-rank fit Y_i is already orthogonal to
+ * range(U_i^L), so sum_q gain_i[q]^2 is about ynorm2_i; away from one, step 6 removes the part the one-site gradient already reaches.
+ * Q_i is defined up to what a Householder QR leaves open (signs, and the basis inside the span when k_i > 1 matters only through R).
+ *   mode : TTX_EVAL_EXACT  Y, ynorm2 and the copied blocks bit for bit the numpy restatement; independent of TTX_BASIS_CHUNK /
+ *                          TTX_BASIS_GRAD_STORE, of the grid and of repetition
+ *          TTX_EVAL_MFMA   steps 3 and 4 on v_mfma_f64_16x16x4_f64; segment sums in a fixed order, no atomics, a call repeats bit for
+ *                          bit; Y within the allowance of tests/enrich_ref.py (ttx_basis_core_grad's count with the Omega step)
+ *          TTX_EVAL_AUTO   by the flops of the call, npts (4 sum r n r + 2 sum_i k_i (n(i+1) r(i+1) + r(i-1) n(i))), against a
+ *                          PROVISIONAL break-even (TTX_EN_AUTO_FLOPS; TTX_ENRICH_AUTO_FLOPS in the environment replaces it)
+ * Steps 5 - 7 are the same in both modes.  Every state row of the call (X, L, z) has the stride ldx = max(r, k) rounded up to four; the
+ * chunk rule is ttx_basis_core_grad_batch's with S = d ldx doubles per point (the states and the chunk's z block).
+ * added[d-1], gain[d-1][128] (unused entries 0), ynorm2[d-1] and y (the packed Y_i in bond order, (a, j, q) at a + r(i-1) (j + n(i) q),
+ * with the k_i of step 1 also where added is 0; on the device for the _dev entries) may each be NULL.
+ * Refusals: those of ttx_basis_core_grad_batch; a NULL add or out; a NULL c with npts > 0; a negative add; the storage check of step 1.
+ * After a refusal *out is NULL.  npts == 0 gives a zero sketch on every bond: out is a plain copy.
+ * ttx_basis_enrich_last: of the last call on this engine, the milliseconds (HIP events) of the table, backward, sketch (forward
+ * advance, z, Y and statistics), QR and assembly launches, the flops, the mode that ran (-1: none yet), the points per chunk.
+ * Open: growth of the source engine in place, the normaliser's two-site term for the squared density, power iterations on the sketch,
+ * ranks above 128.  Added without a new ttx_version: look the symbols up. */
+int ttx_basis_enrich_batch    (ttx_engine *h, int64_t npts, const double *x /* [npts][d] */, const ttx_basis *basis /* [d] */, const double *c /* [npts] */, const int32_t *add /* [d-1] */,
+                               uint64_t seed, int32_t mode, ttx_engine **out, int32_t *added /* [d-1] */, double *gain /* [d-1][128] */, double *ynorm2 /* [d-1] */, double *y);
+int ttx_basis_enrich_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, const double *c_dev, const int32_t *add,
+                               uint64_t seed, int32_t mode, ttx_engine **out, int32_t *added, double *gain, double *ynorm2, double *y_dev);
+int ttx_basis_enrich_tab      (ttx_engine *h, int64_t npts, const double *phi /* [npts][sum n(k)] */, const double *c, const int32_t *add,
+                               uint64_t seed, int32_t mode, ttx_engine **out, int32_t *added, double *gain, double *ynorm2, double *y);
+int ttx_basis_enrich_tab_dev  (ttx_engine *h, int64_t npts, const double *phi_dev, const double *c_dev, const int32_t *add,
+                               uint64_t seed, int32_t mode, ttx_engine **out, int32_t *added, double *gain, double *ynorm2, double *y_dev);
+int ttx_basis_enrich_last     (const ttx_engine *h, double *ms_table, double *ms_back, double *ms_sketch, double *ms_qr, double *ms_asm, double *flops, int32_t *mode_ran, int64_t *chunk_ran);
+
 /* Derivative of the same f along a direction V in core space, at a batch of real points (ttcross_amd/csrc/ttx_basis_jvp.h): J V, cores
  * to points, the other half of ttx_basis_core_grad_batch (J^T c, points to cores).  With both, a Gauss-Newton or Levenberg-Marquardt
  * step is solved matrix-free; a JVP keeps no states, so its point count is not limited by a state store.

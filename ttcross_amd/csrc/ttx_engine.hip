@@ -55,6 +55,7 @@
 #include "ttx_basis_core_grad.h"
 #include "ttx_sq_norm.h"
 #include "ttx_basis_jvp.h"
+#include "ttx_basis_enrich.h"
 #include "ttx_fit_plan.h"
 #include "ttx_algebra.h"
 #include "ttx_roundsum.h"
@@ -152,6 +153,7 @@ enum {
     SC_FITV, SC_FITP,                   // ttx_basis_fit_batch: the core-space work vectors and the snapshot; the point vectors, then the uploaded inputs of a host caller
     SC_SQNW, SC_SQNP, SC_SQNY, SC_SQNPT, // ttx_sq_lognorm_grad: the W store; the PR store, the two PL and the exponents; Y of a right step and the per-index partial matrices of a step; ttx_sq_nll_batch: the point vectors, then the uploaded inputs of a host caller
     SC_SQMP, SC_SQMC, SC_SQMW,          // ttx_sq_moments: the PR and PL stores, the exponents, RA, the products and the band; the carried matrices (two sets) and their exponents; the W and partial matrices of a batched launch (its unbatched steps use SC_SQNY)
+    SC_ENY, SC_ENS,                     // ttx_basis_enrich_batch: the packed sketches Y_i (then the new directions Q_i); the segment sums and maxima of every bond, then the descriptor tables
     SC_NBUF
 };
 struct EvBuf { void *p = nullptr; size_t bytes = 0; };
@@ -210,6 +212,8 @@ struct BsLast { double ms[2] = {0.0, 0.0}, flops = 0.0; int mode = -1; };      /
 struct BgLast { double ms[3] = {0.0, 0.0, 0.0}, flops = 0.0; int mode = -1; int64_t chunk = 0; };     // ttx_basis_grad_batch / ttx_basis_grad_tab: table, backward, forward launches
 
 struct CgLast { double ms[4] = {0.0, 0.0, 0.0, 0.0}, flops = 0.0; int mode = -1; int64_t chunk = 0; };     // ttx_basis_core_grad_batch / _tab: table, backward, forward, accumulation launches
+
+struct EnLast { double ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, flops = 0.0; int mode = -1; int64_t chunk = 0; };     // ttx_basis_enrich_batch / _tab: table, backward, sketch (forward advance, z, Y, statistics), QR, assembly launches
 
 struct JvLast { double ms[2] = {0.0, 0.0}, flops = 0.0; int mode = -1; };      // ttx_basis_jvp_batch / ttx_basis_jvp_tab: table launches, chain launches
 struct FitLast { double ms[4] = {0.0, 0.0, 0.0, 0.0}; int64_t n_jvp = 0, n_cg = 0; int mode = -1; };      // ttx_basis_fit_batch / _tab: JVP, core-gradient, value, vector launches
@@ -332,6 +336,7 @@ struct ttx_engine {
     BsLast bs;
     BgLast bg;
     CgLast cg;
+    EnLast en;
     JvLast jv;
     FitLast fit;
     SqnLast sqn;
@@ -502,6 +507,7 @@ static int dev_alloc(ttx_engine *h, T **p, size_t count)
 }
 
 // the restated figures of ttx_create_plan.h against the kernel headers'
+static_assert(TTX_EN_STORAGE == TTX_MAXPART * TTX_BLK, "ttx_op_plan.h restates TTX_MAXPART * TTX_BLK");
 static_assert(TTX_PLAN_FB == FB && TTX_PLAN_FNR == TTX_FNR && TTX_PLAN_MVN_MAXQ == MVN_MAXQ, "ttx_create_plan.h restates FB, TTX_FNR, MVN_MAXQ");
 
 static int ensure_lds(const ttx_engine *h, const void *fn, size_t need) { return ensure_lds(h->cfg.device, fn, need); }
@@ -4319,6 +4325,274 @@ extern "C" int ttx_basis_core_grad_last(const ttx_engine *h, double *ms_table, d
     if (flops) *flops = h->cg.flops;
     if (mode_ran) *mode_ran = h->cg.mode;
     if (chunk_ran) *chunk_ran = h->cg.chunk;
+    return TTX_OK;
+}
+
+// ---- ranks grown from data: gradient enrichment (ttx_basis_enrich.h) --------------------------------------------------------------
+enum { ENM_TABLE, ENM_BACK, ENM_SKETCH, ENM_QR, ENM_ASM };      // OpMarks phases of a call, EnLast::ms takes the sums
+// the passes of a call: Y (the packed sketches, zeroed by the caller) takes every bond's sum over all points
+static int en_sketch(ttx_engine *h, const EnPlan &pl, BsSrc src, int64_t npts, const double *in, const ttx_basis *basis, const double *cw, unsigned long long seed, double *Y)
+{
+    const bool tab = src == BS_TAB_HOST || src == BS_TAB_DEV, dev = src == BS_X_DEV || src == BS_TAB_DEV;
+    const CgPlan &g = pl.cg;
+    const int d = h->d;
+    int rc;
+    EvTrain T;
+    if ((rc = ev_train(h, &T))) return rc;
+    T.ldx = g.ldx;                                                              // every state row of this call at the plan's stride
+    std::vector<BsMode> M(d);
+    if (!tab) {
+        OpMeta meta(h->meta_host);
+        std::vector<size_t> o_nodes(d, 0);
+        for (int k = 0; k < d; k++)
+            if (basis[k].kind == TTX_BASIS_LINEAR) o_nodes[k] = meta.put(std::vector<double>(basis[k].nodes, basis[k].nodes + h->n1[k + 1]));
+        char *dm = nullptr;
+        if (!meta.host.empty() && (rc = meta.upload(h, SC_META, &dm))) return rc;
+        for (int k = 0; k < d; k++) {
+            const ttx_basis &b = basis[k];
+            const bool cosk = b.kind == TTX_BASIS_COS;
+            M[k] = BsMode{b.kind, b.flags, h->n1[k + 1], cosk ? b.a : 0.0, cosk ? ttx_basis_cos_w(b.a, b.b) : 0.0, cosk ? nullptr : (const double *)(dm + o_nodes[k])};
+        }
+    }
+    if ((rc = buf_reserve(h, {{SC_XA, g.b_xa}, {SC_XB, g.b_xb}, {SC_BTAB, g.b_btab}, {SC_X, g.b_x}, {SC_GST, g.b_gst}, {SC_CGP, pl.b_part}}))) return rc;
+    double *btab = buf<double>(h, SC_BTAB), *sin_ = buf<double>(h, SC_X);
+    double *gst = buf<double>(h, SC_GST), *XA = buf<double>(h, SC_XA), *XB = buf<double>(h, SC_XB), *part = buf<double>(h, SC_CGP);
+    double *zb = gst + pl.zoff() * g.chunk;
+    OpMarks marks(h->op_ev);
+    for (int64_t o = 0; o < npts; o += (int64_t)g.chunk) {
+        const int c = (int)std::min<int64_t>((int64_t)g.chunk, npts - o);
+        const double *cin = in + (size_t)o * g.row, *cc = cw + o;
+        if (!dev) {
+            HIPCHECK(hipMemcpyAsync(sin_, cin, sizeof(double) * (size_t)c * g.row, hipMemcpyHostToDevice, h->stream));
+            HIPCHECK(hipMemcpyAsync(sin_ + g.chunk * g.row, cc, sizeof(double) * (size_t)c, hipMemcpyHostToDevice, h->stream));
+            cin = sin_; cc = sin_ + g.chunk * g.row;
+        }
+        if ((rc = marks.mark(h->stream, OpMarks::DISCARD))) return rc;
+        const double *ph = nullptr;
+        size_t ld = 0;
+        auto tables = [&](int i) {
+            ph = cin + g.off[i]; ld = g.sumn;
+            if (tab) return TTX_OK;
+            hipLaunchKernelGGL(k_bg_table, g1((size_t)c * M[i].n), dim3(256), 0, h->stream, M[i], (long long)c, cin + i, d, btab, (double *)nullptr);
+            ph = btab; ld = (size_t)M[i].n;
+            return marks.mark(h->stream, ENM_TABLE);
+        };
+        auto Xof = [&](int bond) { return gst + g.soff(bond) * g.chunk; };      // X_bond, bond = 1 .. d-1
+        for (int i = d - 1; i >= 1; i--) {                                      // backward: the value chain down to X_1, every state into the store
+            if ((rc = tables(i))) return rc;
+            const double *Xin = i == d - 1 ? nullptr : Xof(i + 1);
+            if (pl.eff == TTX_EVAL_EXACT)
+                hipLaunchKernelGGL(k_bs_exact, dim3(g.g_exact(c)), dim3(256), g.lds_back, h->stream, T, i, (long long)c, ph, ld, Xin, Xof(i), (double *)nullptr);
+            else
+                with_tier<true>(g.back[i].tier, [&](auto mr) {
+                    hipLaunchKernelGGL(k_bs_gemm<decltype(mr)::value>, dim3(g.g_back(i, c)), dim3(256), g.back[i].lds, h->stream, T, i, c, ph, ld, Xin, Xof(i), (double *)nullptr);
+                    return 0;
+                });
+            if ((rc = marks.mark(h->stream, ENM_BACK))) return rc;
+        }
+        int last = 0;                                                           // the last bond that takes a direction: L is advanced no further
+        for (int b = 1; b < d; b++) if (pl.step[b].k) last = b;
+        double *X = XA, *Z = XB;
+        for (int i = 0; i < last; i++) {                                        // forward, bond b = i + 1: z, then Y_b from L_b and z, then L through mode i
+            const int b = i + 1;
+            const EnStep &st = pl.step[b];
+            const double *Lin = i == 0 ? nullptr : X;
+            if (st.k) {
+                const int n2 = h->n1[b + 1], r2 = h->rfinal[b + 1];
+                const double *X2 = b == d - 1 ? nullptr : Xof(b + 1);
+                if ((rc = tables(b))) return rc;
+                if (pl.eff == TTX_EVAL_EXACT)
+                    hipLaunchKernelGGL(k_en_z_exact, dim3(g.g_exact(c)), dim3(256), 0, h->stream, seed, b, st.k, n2, r2, (long long)c, ph, ld, X2, g.ldx, zb);
+                else
+                    with_tier(st.qt, [&](auto qt) {
+                        hipLaunchKernelGGL(k_en_z_gemm<decltype(qt)::value>, dim3(pl.g_z(b, c)), dim3(256), 0, h->stream, seed, b, st.k, n2, r2, c, ph, ld, X2, g.ldx, zb);
+                        return 0;
+                    });
+                if ((rc = marks.mark(h->stream, ENM_SKETCH)) || (rc = tables(i))) return rc;
+                const int r0 = h->rfinal[i], n = h->n1[i + 1];
+                double *Yb = Y + st.acc.goff;
+                if (pl.eff == TTX_EVAL_EXACT)
+                    hipLaunchKernelGGL(k_cg_exact, dim3((unsigned)((st.acc.size + 255) / 256)), dim3(256), 0, h->stream, r0, n, st.k, (long long)c, cc, ph, ld, Lin, (const double *)zb, g.ldx, Yb);
+                else {
+                    const int ns = pl.nsplit(b, c);
+                    with_tier<true>(st.acc.tier, [&](auto mr) {
+                        hipLaunchKernelGGL(k_cg_gemm<decltype(mr)::value>, dim3(st.acc.ngrp, ns), dim3(256), st.acc.lds, h->stream, r0, n, st.k, c, st.acc.seg, cc, ph, ld, Lin, (const double *)zb, g.ldx, part);
+                        return 0;
+                    });
+                    hipLaunchKernelGGL(k_cg_reduce, g1(st.acc.size), dim3(256), 0, h->stream, (long long)st.acc.size, ns, part, Yb);
+                }
+                if ((rc = marks.mark(h->stream, ENM_SKETCH))) return rc;
+            }
+            if (b == last) break;
+            if (!st.k && (rc = tables(i))) return rc;
+            if (pl.eff == TTX_EVAL_EXACT)
+                hipLaunchKernelGGL(k_bg_exact_fwd, dim3(g.g_exact(c)), dim3(256), g.lds_fwd, h->stream, T, i, (long long)c, ph, ld, Lin, Z, (const double *)nullptr, (double *)nullptr, d, 0);
+            else
+                with_tier<true>(g.fwd[i].tier, [&](auto mr) {
+                    hipLaunchKernelGGL((k_bg_gemm<decltype(mr)::value, true>), dim3(g.g_fwd(i, c)), dim3(256), g.fwd[i].lds_fwd, h->stream,
+                                       T, i, c, ph, (const double *)nullptr, ld, Lin, Z, (double *)nullptr, (double *)nullptr, (double *)nullptr, d, 0);
+                    return 0;
+                });
+            if ((rc = marks.mark(h->stream, ENM_SKETCH))) return rc;
+            std::swap(X, Z);
+        }
+        if (!dev || marks.phase.size() > 4096) {                                // the staging blocks are reused by the next chunk; the event chain stays short
+            HIPCHECK(hipStreamSynchronize(h->stream));
+            if ((rc = marks.sum(h->en.ms))) return rc;
+        }
+    }
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return marks.sum(h->en.ms);
+}
+// everything of the call that works on the new engine e: the QR of every bond that takes directions, then all cores in one launch.  The
+// launches go to h's stream (e runs on it for the length of the call); Y gives way to the new directions bond by bond
+static int en_fill(ttx_engine *h, ttx_engine *e, const EnPlan &pl, const std::vector<int> &added, const std::vector<int> &ex, double *Y, double *gain)
+{
+    const int d = h->d;
+    int rc;
+    if ((rc = tt_prepare(e, "ttx_basis_enrich"))) return rc;
+    struct OnStream { ttx_engine *e; hipStream_t own; ~OnStream() { e->stream = own; } } on{e, e->stream};
+    e->stream = h->stream;
+    hipStream_t st = h->stream;
+    const TtScratch s(e);
+    OpMarks marks(h->op_ev);
+    if ((rc = marks.mark(st, OpMarks::DISCARD))) return rc;
+    std::vector<double> rdiag((size_t)(d - 1) * 128, 0.0);
+    for (int b = 1; b < d; b++) {
+        if (!added[b]) continue;
+        const EnStep &sp = pl.step[b];
+        double *Yb = Y + sp.acc.goff;
+        hipLaunchKernelGGL(k_en_pack, g1((size_t)sp.rows * sp.cols), dim3(256), 0, st, (const double *)core_dev(h, b), h->RM, h->P.SS, h->rfinal[b - 1], h->n1[b], h->rfinal[b], sp.k,
+                           (const double *)Yb, ex[b], e->Wa);
+        if ((rc = qr(e, sp.rows, sp.cols, e->Wa, s.Rm, s.tau))) return rc;
+        const int r1 = h->rfinal[b];
+        HIPCHECK(hipMemcpyAsync(Yb, e->Wa + (size_t)sp.rows * r1, sizeof(double) * sp.acc.size, hipMemcpyDeviceToDevice, st));       // Q_b = the columns r1 .. r1 + k - 1
+        HIPCHECK(hipMemcpy2DAsync(rdiag.data() + (size_t)(b - 1) * 128, sizeof(double), s.Rm + (size_t)r1 * (sp.cols + 1), sizeof(double) * (sp.cols + 1), sizeof(double), sp.k,
+                                  hipMemcpyDeviceToHost, st));                  // R(r1 + q, r1 + q), R with the leading dimension cols
+        HIPCHECK(hipStreamSynchronize(st));                                     // the pageable rows have landed before Rm is written again
+    }
+    if ((rc = marks.mark(st, ENM_QR))) return rc;
+    std::vector<EnCore> cs(d);
+    long long tot = 0;
+    for (int k = 1; k <= d; k++) {
+        EnCore &C = cs[k - 1];
+        C.U = core_dev(h, k); C.dst = core_dev(e, k); C.Q = k < d ? Y + pl.step[k].acc.goff : nullptr;
+        C.first = tot; C.r0 = h->rfinal[k - 1]; C.n = h->n1[k]; C.r1 = h->rfinal[k]; C.R0 = e->rfinal[k - 1]; C.R1 = e->rfinal[k];
+        tot += (long long)C.R0 * C.n * C.R1;
+    }
+    OpMeta meta(h->meta_host);
+    meta.put(cs);
+    char *dm;
+    if ((rc = meta.upload(h, SC_META, &dm))) return rc;
+    hipLaunchKernelGGL(k_en_assemble, g1((size_t)tot), dim3(256), 0, st, (const EnCore *)dm, d, tot, h->RM, h->P.SS, e->RM, e->P.SS);
+    if ((rc = marks.mark(st, ENM_ASM))) return rc;
+    HIPCHECK(hipStreamSynchronize(st));
+    HIPCHECK(hipGetLastError());
+    if ((rc = marks.sum(h->en.ms))) return rc;
+    if (gain) for (int b = 1; b < d; b++) for (int q = 0; q < added[b]; q++) gain[(size_t)(b - 1) * 128 + q] = ldexp(fabs(rdiag[(size_t)(b - 1) * 128 + q]), ex[b]);
+    return TTX_OK;
+}
+// in: the coordinates or the caller's phi; cw: the weights c; y (optional): on the device where dev, the other outputs on the host
+static int en_run(ttx_engine *h, const char *who, BsSrc src, int64_t npts, const double *in, const ttx_basis *basis, const double *cw, const int32_t *add, uint64_t seed,
+                  int32_t mode, ttx_engine **out, int32_t *added_out, double *gain, double *ynorm2, double *y)
+{
+    const bool tab = src == BS_TAB_HOST || src == BS_TAB_DEV, dev = src == BS_X_DEV || src == BS_TAB_DEV;
+    if (out) *out = nullptr;
+    int rc = tt_prepare(h, who);
+    if (rc) return rc;
+    if (!out || !add) return fail(TTX_EINVAL, "%s: null add or out", who);
+    if (npts < 0 || (npts > 0 && (!in || !cw || (!tab && !basis)))) return fail(TTX_EINVAL, "%s: null argument or negative npts", who);
+    if (!op_mode_known(mode)) return fail(TTX_EINVAL, "%s: unknown mode %d", who, mode);
+    const int d = h->d;
+    if (d < 2) return fail(TTX_EINVAL, "%s: at least two cores are needed (got %d)", who, d);
+    for (int b = 1; b < d; b++) if (add[b - 1] < 0) return fail(TTX_EINVAL, "%s: add(%d)=%d is negative", who, b, (int)add[b - 1]);
+    if (!tab && basis) for (int k = 1; k <= d; k++) if ((rc = bs_check_one(who, k, basis[k - 1], h->n1[k]))) return rc;
+    double auto_flops = TTX_EN_AUTO_FLOPS;
+    if (const char *e = getenv("TTX_ENRICH_AUTO_FLOPS")) { const double v = atof(e); if (v > 0.0) auto_flops = v; }
+    const EnPlan pl = en_plan(d, h->n1.data() + 1, h->rfinal.data(), add, dev_ncu(h), src, npts, mode, env_chunk("TTX_BASIS_CHUNK", op_chunk_default(h->RM)), env_grad_store(), auto_flops);
+    if (pl.refusal == BS_RANK) return fail(TTX_EINVAL, "%s: ranks up to 128 only (got %d)", who, pl.cg.rmax);
+    if (pl.refusal == BS_BOUNDARY) return fail(TTX_EINVAL, "%s: boundary ranks are not 1", who);
+    if (pl.storage_bond)
+        return fail(TTX_EINVAL, "%s: the rank at bond %d grows to %d, and %d times the largest mode is more than a new engine stores (maxrank*n too large: lower add)", who,
+                    pl.storage_bond, pl.storage_rank, pl.storage_rank);
+    h->en = EnLast();
+    h->en.flops = pl.flops; h->en.mode = pl.eff; h->en.chunk = (int64_t)pl.cg.chunk;
+    const int nb = d - 1;
+    if ((rc = buf_reserve(h, {{SC_ENY, pl.b_y}, {SC_ENS, pl.b_stat}}))) return rc;
+    double *Y = buf<double>(h, SC_ENY), *stat = buf<double>(h, SC_ENS);
+    HIPCHECK(hipMemsetAsync(Y, 0, pl.b_y, h->stream));
+    std::vector<int> added(d + 1, 0), ex(d + 1, 0);
+    std::vector<double> norm2(nb, 0.0), mx(nb, 0.0);
+    if (pl.sketch) {
+        if ((rc = en_sketch(h, pl, src, npts, in, basis, cw, (unsigned long long)seed, Y))) return rc;
+        // step 5: per bond the sum of squares by ttx_cores_dot's rule and the largest |Y|, the 256 segment results folded here
+        std::vector<size_t> off(d, 0);
+        for (int b = 1; b < d; b++) off[b] = off[b - 1] + pl.step[b].acc.size;
+        OpMeta meta(h->meta_host);
+        meta.put(off);
+        char *dm;
+        if ((rc = meta.upload(h, SC_META, &dm))) return rc;
+        OpMarks marks(h->op_ev);
+        if ((rc = marks.mark(h->stream, OpMarks::DISCARD))) return rc;
+        hipLaunchKernelGGL(k_en_stat, dim3(256, nb), dim3(256), 0, h->stream, (const size_t *)dm, (const double *)Y, stat, stat + (size_t)256 * nb);
+        if ((rc = marks.mark(h->stream, ENM_SKETCH))) return rc;
+        std::vector<double> hs((size_t)2 * 256 * nb);
+        HIPCHECK(hipMemcpyAsync(hs.data(), stat, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(hipStreamSynchronize(h->stream));
+        HIPCHECK(hipGetLastError());
+        if ((rc = marks.sum(h->en.ms))) return rc;
+        for (int b = 1; b < d; b++) {
+            double s = 0.0, m = 0.0;
+            for (int k = 0; k < 256; k++) { s = s + hs[(size_t)256 * (b - 1) + k]; m = std::max(m, hs[(size_t)256 * (nb + b - 1) + k]); }
+            norm2[b - 1] = s; mx[b - 1] = m;
+            if (m > 0.0 && std::isfinite(m)) { added[b] = pl.step[b].k; (void)frexp(m, &ex[b]); }
+        }
+    }
+    if (y && pl.ysize) HIPCHECK(hipMemcpyAsync(y, Y, sizeof(double) * pl.ysize, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    std::vector<double> hgain((size_t)nb * 128, 0.0);
+    for (int b = 1; b < d; b++) if (pl.step[b].k && !std::isfinite(mx[b - 1])) std::fill(hgain.begin() + (size_t)(b - 1) * 128, hgain.begin() + (size_t)b * 128, NAN);
+    std::vector<int32_t> nn = modes_of(h), rr(d + 1, 1);
+    for (int b = 1; b < d; b++) rr[b] = h->rfinal[b] + added[b];
+    rc = new_train(out, who, d, nn.data(), rr.data(), h->cfg.device, [&](ttx_engine *e) { return en_fill(h, e, pl, added, ex, Y, hgain.data()); });
+    if (rc) return rc;
+    if (added_out) for (int b = 1; b < d; b++) added_out[b - 1] = added[b];
+    if (gain) std::copy(hgain.begin(), hgain.end(), gain);
+    if (ynorm2) std::copy(norm2.begin(), norm2.end(), ynorm2);
+    return TTX_OK;
+}
+extern "C" int ttx_basis_enrich_batch(ttx_engine *h, int64_t npts, const double *x, const ttx_basis *basis, const double *c, const int32_t *add, uint64_t seed, int32_t mode,
+                                      ttx_engine **out, int32_t *added, double *gain, double *ynorm2, double *y)
+{
+    return en_run(h, "ttx_basis_enrich_batch", BS_X_HOST, npts, x, basis, c, add, seed, mode, out, added, gain, ynorm2, y);
+}
+extern "C" int ttx_basis_enrich_batch_dev(ttx_engine *h, int64_t npts, const double *x_dev, const ttx_basis *basis, const double *c_dev, const int32_t *add, uint64_t seed, int32_t mode,
+                                          ttx_engine **out, int32_t *added, double *gain, double *ynorm2, double *y_dev)
+{
+    return en_run(h, "ttx_basis_enrich_batch_dev", BS_X_DEV, npts, x_dev, basis, c_dev, add, seed, mode, out, added, gain, ynorm2, y_dev);
+}
+extern "C" int ttx_basis_enrich_tab(ttx_engine *h, int64_t npts, const double *phi, const double *c, const int32_t *add, uint64_t seed, int32_t mode,
+                                    ttx_engine **out, int32_t *added, double *gain, double *ynorm2, double *y)
+{
+    return en_run(h, "ttx_basis_enrich_tab", BS_TAB_HOST, npts, phi, nullptr, c, add, seed, mode, out, added, gain, ynorm2, y);
+}
+extern "C" int ttx_basis_enrich_tab_dev(ttx_engine *h, int64_t npts, const double *phi_dev, const double *c_dev, const int32_t *add, uint64_t seed, int32_t mode,
+                                        ttx_engine **out, int32_t *added, double *gain, double *ynorm2, double *y_dev)
+{
+    return en_run(h, "ttx_basis_enrich_tab_dev", BS_TAB_DEV, npts, phi_dev, nullptr, c_dev, add, seed, mode, out, added, gain, ynorm2, y_dev);
+}
+extern "C" int ttx_basis_enrich_last(const ttx_engine *h, double *ms_table, double *ms_back, double *ms_sketch, double *ms_qr, double *ms_asm, double *flops, int32_t *mode_ran,
+                                     int64_t *chunk_ran)
+{
+    if (!h) return fail(TTX_EINVAL, "ttx_basis_enrich_last: null engine");
+    if (ms_table) *ms_table = h->en.ms[ENM_TABLE];
+    if (ms_back) *ms_back = h->en.ms[ENM_BACK];
+    if (ms_sketch) *ms_sketch = h->en.ms[ENM_SKETCH];
+    if (ms_qr) *ms_qr = h->en.ms[ENM_QR];
+    if (ms_asm) *ms_asm = h->en.ms[ENM_ASM];
+    if (flops) *flops = h->en.flops;
+    if (mode_ran) *mode_ran = h->en.mode;
+    if (chunk_ran) *chunk_ran = h->en.chunk;
     return TTX_OK;
 }
 // U_i <- U_i + alpha[i - 1] G_i for every core in one launch; g: the packed blocks, on the host unless dev.  The engine keeps nothing

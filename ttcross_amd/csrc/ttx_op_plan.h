@@ -379,6 +379,97 @@ inline JvPlan jv_plan(int d, const int *n, const int *r, int ncu, BsSrc src, boo
     return p;
 }
 
+// ---- ttx_basis_enrich_batch, ttx_basis_enrich_tab and their _dev forms (ttx_basis_enrich.h) ----------------------------------------
+// break-even of TTX_EVAL_AUTO in flops per call (EnPlan::flops).  PROVISIONAL, NOT MEASURED: equal to TTX_BS_AUTO_FLOPS until the two
+// modes of the enrichment itself have been timed against each other (profiles/basis_enrich_mi355x.txt has the commands that give the
+// crossing); TTX_ENRICH_AUTO_FLOPS in the environment replaces it
+#define TTX_EN_AUTO_FLOPS TTX_BS_AUTO_FLOPS
+#define TTX_EN_STORAGE (512 * 256)  // what maxrank * n of a new engine may reach: TTX_MAXPART * TTX_BLK of ttx_create_plan.h (ttx_engine.hip asserts it)
+// point tiles of 16 per wave of k_en_z_gemm<QT> (the accumulators are 8 PT QT registers; a hashed b operand feeds PT MFMAs)
+TTX_OP_HD constexpr int en_pt(int QT) { return QT <= 4 ? 4 : 2; }
+// directions a bond takes: add, the complement of the left unfolding, the rows of the right unfolding, the engine's rank cap
+inline int en_k(int add, int r0, int n, int r1, int n2, int r2)
+{
+    const long long comp = (long long)r0 * n - r1, right = (long long)n2 * r2;
+    return (int)std::max<long long>(0, std::min(std::min<long long>(add, comp), std::min<long long>(right, 128 - r1)));
+}
+// bond b = 1 .. d-1 (between the 0-based modes b-1 and b): k_en_z_gemm<qt> on tp points per workgroup, then the accumulation launch of
+// ttx_basis_core_grad.h with r1 = k (acc.goff: Y_b's start in the packed sketches); the QR of [U^L | Y] is rows x cols
+struct EnStep { int k = 0, qt = 1, tp = 256, rows = 0, cols = 0; CgStep acc; };
+struct EnPlan {
+    BsRefusal refusal = BS_OK;
+    int storage_bond = 0, storage_rank = 0; // a bond whose new rank times the largest mode is more than a new engine stores (0: none)
+    CgPlan cg;                              // the pass structure: tables, backward and forward chain; ldx, S, chunk and the bytes are this call's
+    int kmax = 0, eff = TTX_EVAL_EXACT;
+    std::vector<EnStep> step;               // [d], entry b for bond b (entry 0 is not used)
+    size_t ysize = 0;                       // doubles of the packed sketches Y_1 .. Y_(d-1)
+    size_t b_y = 0, b_stat = 0, b_part = 0; // bytes: the sketches (then the new directions), the segment sums and maxima, the partial blocks
+    double flops = 0.0;
+    bool sketch = false;                    // any bond takes a direction and npts > 0: the passes run
+    int g_z(int b, int c) const { return (c + step[b].tp - 1) / step[b].tp; }
+    int nsplit(int b, int c) const { return (c + step[b].acc.seg - 1) / step[b].acc.seg; }
+    size_t zoff() const { return (size_t)(cg.ldx) * (size_t)(step.size() - 1); }   // the chunk's z block starts at zoff chunk doubles of the state store
+};
+// n[0 .. d-1], r[0 .. d], add[0 .. d-2]; NM: the largest mode; chunk, store: as cg_plan's; auto_flops: the break-even in force
+inline EnPlan en_plan(int d, const int *n, const int *r, const int32_t *add, int ncu, BsSrc src, int64_t npts, int mode, size_t chunk, size_t store,
+                      double auto_flops = TTX_EN_AUTO_FLOPS)
+{
+    const bool tab = src == BS_TAB_HOST || src == BS_TAB_DEV, dev = src == BS_X_DEV || src == BS_TAB_DEV;
+    EnPlan p;
+    p.cg = cg_plan(d, n, r, ncu, src, false, npts, mode, chunk, store);
+    p.refusal = p.cg.refusal;
+    if (p.refusal != BS_OK) return p;
+    CgPlan &g = p.cg;
+    p.step.resize(d);
+    int NM = 1;
+    for (int k = 0; k < d; k++) NM = std::max(NM, n[k]);
+    double w = 0.0, ws = 0.0;
+    for (int k = 0; k < d; k++) w += (double)r[k] * n[k] * r[k + 1];
+    for (int b = 1; b < d; b++) {
+        EnStep &s = p.step[b];
+        s.k = en_k(add[b - 1], r[b - 1], n[b - 1], r[b], n[b], r[b + 1]);
+        if (!p.storage_bond && (long long)(r[b] + s.k) * NM > (long long)TTX_EN_STORAGE) { p.storage_bond = b; p.storage_rank = r[b] + s.k; }
+        p.kmax = std::max(p.kmax, s.k);
+        s.qt = rank_tier(std::max(s.k, 1)); s.tp = 64 * en_pt(s.qt);
+        s.rows = r[b - 1] * n[b - 1]; s.cols = r[b] + s.k;
+        s.acc.tier = (r[b - 1] + 15) / 16;
+        s.acc.size = (size_t)s.rows * s.k; s.acc.goff = p.ysize; p.ysize += s.acc.size;
+        ws += (double)s.k * ((double)n[b] * r[b + 1] + (double)s.rows);
+    }
+    if (p.storage_bond) return p;
+    p.flops = (double)npts * (4.0 * w + 2.0 * ws);                              // the two chains; z and Y of every bond
+    p.eff = op_mode_eff(mode, p.flops, auto_flops);
+    g.eff = p.eff; g.flops = p.flops; g.b_cgg = 0; g.b_part = 0;
+    p.b_y = sizeof(double) * std::max<size_t>(p.ysize, 1);
+    p.b_stat = sizeof(double) * 2 * 256 * (size_t)(d - 1);
+    p.sketch = p.kmax > 0 && npts > 0;
+    // every state row -- X, L, z -- at one stride that also holds the k_i; the store takes X_1 .. X_(d-1) and the chunk's z block
+    g.ldx = (std::max(g.rmax, p.kmax) + 3) & ~3;
+    g.S = (size_t)d * g.ldx;
+    const size_t fit = std::max<size_t>(256, store / (sizeof(double) * g.S) / 256 * 256);
+    g.cap = std::max<size_t>(1, std::min(chunk, fit));
+    g.chunk = std::min<size_t>(g.cap, (size_t)std::max<int64_t>(npts, 0));
+    if (src == BS_TAB_HOST) g.chunk = std::min(g.chunk, std::max<size_t>(1, ((size_t)1 << 25) / g.sumn));
+    if (!p.sketch) { g.chunk = 0; g.b_xa = g.b_xb = g.b_gst = g.b_btab = g.b_x = g.b_out = 0; return p; }
+    g.b_xa = g.b_xb = sizeof(double) * g.chunk * g.ldx;
+    g.b_gst = sizeof(double) * g.chunk * g.S;
+    g.b_btab = tab ? 0 : sizeof(double) * g.chunk * g.nmax;
+    g.b_x = dev ? 0 : sizeof(double) * g.chunk * (g.row + 1);                   // the rows, then c
+    g.b_out = 0;
+    g.lds_back = 4 * sizeof(double) * (size_t)g.ldx; g.lds_fwd = 2 * g.lds_back;
+    for (int b = 1; b < d; b++) {
+        EnStep &s = p.step[b];
+        if (!s.k) continue;
+        const size_t ncol = (size_t)n[b - 1] * s.k, wcol = (size_t)64 * cg_ct(s.acc.tier);
+        s.acc.ngrp = (int)((ncol + wcol - 1) / wcol);
+        const size_t want = std::max<size_t>(1, (size_t)TTX_CG_WG / (size_t)s.acc.ngrp);
+        s.acc.seg = (int)std::max<size_t>(TTX_CG_SEGMIN, ((g.chunk + want - 1) / want + TTX_CG_PB - 1) / TTX_CG_PB * TTX_CG_PB);
+        s.acc.lds = cg_gemm_lds(s.acc.tier, s.k);
+        if (p.eff == TTX_EVAL_MFMA) p.b_part = std::max(p.b_part, sizeof(double) * s.acc.size * (size_t)p.nsplit(b, (int)g.chunk));
+    }
+    return p;
+}
+
 // ---- ttx_topk (ttx_topk.h) -----------------------------------------------------------------------------------------------------------
 #define TTX_TK_KMAX 4096            // largest K
 #define TTX_TK_SHEET (1 << 24)      // largest sheet K max n_k

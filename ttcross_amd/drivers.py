@@ -919,6 +919,58 @@ def run_coregrad(argv, device=0, repeats=5, tt=None, basis=None, host_npts=1000)
     return tt, x, (val, G), res
 
 
+def run_enrich(argv, device=0, repeats=5, tt=None):
+    """enrich WORKLOAD NPTS [ADD] [MODE]: the workloads and modes of the basis sub-command, hat functions on every mode.  On seeded
+    points and weights drawn on the device and in the same session: one warm-up and `repeats` timed TTCross.enrich calls through the
+    device-pointer entry (each makes and destroys a new engine) and the same for basis_core_grad in the mode that ran -- the yardstick:
+    one product over all points per core.  Prints one JSON line with the medians, the phases of ttx_basis_enrich_last (table, back,
+    sketch, qr, asm), the share of the QR, the measured ratio and the ratio the flop counts predict."""
+    import json
+    import time
+    import torch
+    torch.cuda.init()          # a torch that brings its own HIP runtime must initialise its device before the engine's library does
+    workload, npts = argv[0], int(float(argv[1]))
+    add = int(argv[2]) if len(argv) > 2 else 4
+    mode = argv[3] if len(argv) > 3 else "auto"
+    if tt is None:
+        tt, _ = basis_train(workload, device=device)
+    basis = [("linear", np.linspace(0.0, 1.0, int(nk))) if nk > 1 else ("cos", 0.0, 1.0) for nk in tt._n]
+    dev = torch.device("cuda", device)
+    g = torch.Generator(device=dev)
+    g.manual_seed(20240607)
+    x = torch.rand((npts, tt.d), dtype=torch.float64, device=dev, generator=g).contiguous()
+    c = torch.randn(npts, dtype=torch.float64, device=dev, generator=g).contiguous()
+    torch.cuda.synchronize(dev)
+    info = {}
+
+    def once():
+        new, inf = tt.enrich(x, basis, c, add, 1, mode)
+        info.update(inf)
+        info["ranks"] = [int(v) for v in new.ranks()]
+        new.close()
+
+    def timed(call):
+        call()                                      # warm-up
+        ms = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            call()                                  # synchronises before it returns
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ms)), [round(v, 4) for v in ms]
+
+    ms_en, all_en = timed(once)
+    last = tt.enrich_last()
+    ms_cg, all_cg = timed(lambda: tt.basis_core_grad(x, basis, c, last["mode"]))
+    cg = tt.basis_core_grad_last()
+    phases = {k: last[k] for k in ("ms_table", "ms_back", "ms_sketch", "ms_qr", "ms_asm")}
+    res = dict(workload=workload, npts=npts, add=add, mode_asked=mode, mode=last["mode"], chunk=last["chunk"], d=tt.d, max_rank=int(tt.ranks().max()),
+               added=int(sum(info["added"])), max_new_rank=max(info["ranks"]), ms_enrich=ms_en, ms_enrich_all=all_en, **phases,
+               qr_share=last["ms_qr"] / max(sum(phases.values()), 1e-300), flops=last["flops"], ms_core_grad=ms_cg, ms_core_grad_all=all_cg,
+               core_grad_chunk=cg["chunk"], ratio_to_core_grad=ms_en / ms_cg, ratio_by_flops=last["flops"] / max(cg["flops"], 1e-300))
+    print(json.dumps(res))
+    return res
+
+
 def run_fit(argv, device=0, repeats=3, tt=None, basis=None, max_iter=4, cg_max=10):
     """fit WORKLOAD NPTS [MODE] [MAX_ITER] [CG_MAX]: the workloads and modes of the basis sub-command.  Takes the workload's train, evaluates it at NPTS
     seeded points (the targets), perturbs every entry of every core by up to 1 % (seeded) and fits it back with TTCross.fit on device
@@ -1822,6 +1874,8 @@ if __name__ == "__main__":
         run_coregrad(sys.argv[2:])
     elif sys.argv[1] == "fit":
         run_fit(sys.argv[2:])
+    elif sys.argv[1] == "enrich":
+        run_enrich(sys.argv[2:])
     elif sys.argv[1] == "mle":
         run_mle(sys.argv[2:])
     elif sys.argv[1] == "chf":

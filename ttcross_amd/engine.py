@@ -161,6 +161,13 @@ def load_library():
                                            POINTER(c_int64)]
     L.ttx_cores_axpy.argtypes = [c_void_p, POINTER(c_double), POINTER(c_double)]
     L.ttx_cores_axpy_dev.argtypes = [c_void_p, POINTER(c_double), c_void_p]
+    _en_host = [POINTER(c_int32), ctypes.c_uint64, c_int32, POINTER(c_void_p), POINTER(c_int32), POINTER(c_double), POINTER(c_double), POINTER(c_double)]
+    _en_dev = _en_host[:-1] + [c_void_p]
+    L.ttx_basis_enrich_batch.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(_Basis), POINTER(c_double)] + _en_host
+    L.ttx_basis_enrich_batch_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(_Basis), c_void_p] + _en_dev
+    L.ttx_basis_enrich_tab.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double)] + _en_host
+    L.ttx_basis_enrich_tab_dev.argtypes = [c_void_p, c_int64, c_void_p, c_void_p] + _en_dev
+    L.ttx_basis_enrich_last.argtypes = [c_void_p] + [POINTER(c_double)] * 6 + [POINTER(c_int32), POINTER(c_int64)]
     L.ttx_basis_jvp_batch.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(_Basis), POINTER(c_double), POINTER(c_double), POINTER(c_double), c_int32]
     L.ttx_basis_jvp_batch_dev.argtypes = [c_void_p, c_int64, c_void_p, POINTER(_Basis), c_void_p, c_void_p, c_void_p, c_int32]
     L.ttx_basis_jvp_tab.argtypes = [c_void_p, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), c_int32]
@@ -1862,6 +1869,134 @@ class TTCross:
             f = fn
             fs.append(f)
         return dict(nll=fs, hist=hist, iters=len(fs) - 1)
+
+    # ---- ranks grown from data: gradient enrichment (include/ttx.h: ttx_basis_enrich_batch) ---------------
+    def enrich_ranks(self, add):
+        """k_i of include/ttx.h (ttx_basis_enrich_batch, step 1) for add (a number or d - 1 numbers): what each bond can take"""
+        r, n = self.ranks().astype(np.int64), self._n.astype(np.int64)
+        a = np.broadcast_to(np.asarray(add, dtype=np.int64), (self.d - 1,))
+        if (a < 0).any():
+            raise ValueError(f"enrich: add must not be negative (got {a.tolist()})")
+        return [int(max(0, min(a[i], r[i] * n[i] - r[i + 1], n[i + 1] * r[i + 2], 128 - r[i + 1]))) for i in range(self.d - 1)]
+
+    def _enrich(self, who, host, dev, head, t, cols, c, add, seed, mode, want_sketch):
+        md, nb = _eval_mode(mode), self.d - 1
+        k = self.enrich_ranks(add)
+        aa = np.ascontiguousarray(np.broadcast_to(np.asarray(add, dtype=np.int64), (nb,)), dtype=np.int32)
+        r, n = self.ranks(), self._n
+        shapes = [(int(r[i]), int(n[i]), k[i]) for i in range(nb)]
+        total = int(sum(int(np.prod(s)) for s in shapes))
+        added, gain, yn, h = np.zeros(nb, dtype=np.int32), np.zeros((nb, 128)), np.zeros(nb), c_void_p()
+        mid = (_ip(aa), int(seed) & (2 ** 64 - 1), md, ctypes.byref(h), _ip(added), _dp(gain), _dp(yn))
+        if self._dev_pair(who, t, cols) is not None:
+            import torch
+            if type(c).__module__.split(".")[0] != "torch" or c.device != t.device or c.dtype != torch.float64 or not c.is_contiguous() or c.shape != (t.shape[0],):
+                raise ValueError(f"{who}: c must be a contiguous float64 tensor of shape (npts,) on the engine's device")
+            y = torch.empty(max(total, 1), dtype=torch.float64, device=t.device) if want_sketch else None
+            _check(dev(self._h, t.shape[0], c_void_p(t.data_ptr()), *head, c_void_p(c.data_ptr()), *mid, c_void_p(y.data_ptr()) if want_sketch else None))
+            flat = y.cpu().numpy() if want_sketch else None
+        else:
+            t, c = (a.cpu().numpy() if type(a).__module__.split(".")[0] == "torch" else a for a in (t, c))
+            ta, ca = np.ascontiguousarray(t, dtype=np.float64), np.ascontiguousarray(c, dtype=np.float64)
+            if ta.ndim != 2 or ta.shape[1] != cols or ca.shape != (ta.shape[0],):
+                raise ValueError(f"{who}: an array of shape (npts, {cols}) and npts weights expected")
+            flat = np.zeros(max(total, 1)) if want_sketch else None
+            _check(host(self._h, ta.shape[0], _dp(ta), *head, _dp(ca), *mid, _dp(flat) if want_sketch else None))
+        ys = None
+        if want_sketch:
+            off = np.concatenate([[0], np.cumsum([int(np.prod(s)) for s in shapes])])
+            ys = [flat[off[i]:off[i + 1]].reshape(shapes[i], order="F") for i in range(nb)]
+        info = dict(added=[int(v) for v in added], k=k, gain=[gain[i, :k[i]].copy() for i in range(nb)], ynorm2=yn, y=ys)
+        return TTCross._adopt(h, self.device), info
+
+    def enrich(self, x, basis, c, add, seed=0, mode="auto", want_sketch=False):
+        """(new train, info): the train with up to add new directions per bond taken from the two-site gradient of a loss at real
+        points x (npts, d) (include/ttx.h: ttx_basis_enrich_batch).  c (npts,) is dLoss/df at the points, e.g. w (f - y) for least
+        squares.  The new train is a new engine on the same device and the SAME function: the new columns of core i are orthonormal
+        directions outside the range of its left unfolding, the new rows of core i + 1 are zeros, so the next fit() can move into
+        them.  add: a number or d - 1 numbers; seed picks the sketch; mode "exact", "mfma" or "auto".  info: added (directions every
+        bond took; 0 where its sketch was zero or not finite), k (what it could take), gain (per bond the k_i sizes of the new
+        directions in the sketch, NaN for a sketch that is not finite), ynorm2 (the sketches' sums of squares) and y (want_sketch:
+        the sketches Y_i, (r(i-1), n(i), k_i) each).  Host arrays, or float64 tensors on the engine's device by pointer."""
+        L = load_library()
+        arr, keep = self._basis_arr("enrich", basis)
+        return self._enrich("enrich", L.ttx_basis_enrich_batch, L.ttx_basis_enrich_batch_dev, (arr,), x, self.d, c, add, seed, mode, want_sketch)
+
+    def enrich_tab(self, phi, c, add, seed=0, mode="auto", want_sketch=False):
+        """The same with the caller's own tables (include/ttx.h: ttx_basis_enrich_tab): phi (npts, sum n) in basis_tab's layout."""
+        L = load_library()
+        return self._enrich("enrich_tab", L.ttx_basis_enrich_tab, L.ttx_basis_enrich_tab_dev, (), phi, int(self._n.sum()), c, add, seed, mode, want_sketch)
+
+    def enrich_last(self):
+        """dict(ms_table, ms_back, ms_sketch, ms_qr, ms_asm, flops, mode, chunk) of the last enrich / enrich_tab on this engine
+        (include/ttx.h: ttx_basis_enrich_last)"""
+        ms = [c_double() for _ in range(6)]
+        md, ck = c_int32(), c_int64()
+        _check(load_library().ttx_basis_enrich_last(self._h, *[ctypes.byref(m) for m in ms], ctypes.byref(md), ctypes.byref(ck)))
+        names = {v: k for k, v in EVAL_MODES.items()}
+        return dict(ms_table=ms[0].value, ms_back=ms[1].value, ms_sketch=ms[2].value, ms_qr=ms[3].value, ms_asm=ms[4].value, flops=ms[5].value,
+                    mode=names.get(md.value), chunk=ck.value)
+
+    def fit_adaptive(self, x, basis, y, w=None, add=1, rmax=None, rounds=4, holdout=None, seed=0, mode="auto", **fit_opts):
+        """(train, history): fit with ranks grown from the data.  Each round runs fit() (this engine is fitted in place in the first
+        round, every later train is a new engine), forms c = w (f - y) with basis_batch and calls enrich() with add clipped so that
+        no rank passes rmax (a number or d - 1 numbers; None: the engine's 128).  It stops after `rounds` fits, when nothing was
+        added, when the fit reached its loss_tol, or when the loss on holdout = (x, y[, w]) rose -- and then returns the train of
+        the round before.  No second solver: everything is fit, basis_batch and enrich.  history: per round dict(ranks, loss,
+        holdout, added).  The train returned is this engine itself where no round added anything and a new engine otherwise; every
+        engine in between is closed here, this one never:
+            grown, hist = tt.fit_adaptive(x, basis, y, add=2, rmax=16)
+            ...
+            if grown is not tt:
+                grown.close()"""
+        nb = self.d - 1
+        cap = np.broadcast_to(np.asarray(128 if rmax is None else rmax, dtype=np.int64), (nb,))
+        want = np.broadcast_to(np.asarray(add, dtype=np.int64), (nb,))
+
+        def held(tt):
+            if holdout is None:
+                return None
+            res = tt.basis_batch(holdout[0], basis, mode) - holdout[1]
+            sq = res * res if len(holdout) < 3 or holdout[2] is None else holdout[2] * (res * res)
+            return 0.5 * float(sq.sum())
+        cur, prev, prev_ho, hist = self, None, None, []
+
+        def drop(tt):
+            if tt is not None and tt is not self:
+                tt.close()
+        for rd in range(int(rounds)):
+            h = cur.fit(x, basis, y, w, mode=mode, **fit_opts)
+            ho = held(cur)
+            hist.append(dict(ranks=[int(v) for v in cur.ranks()], loss=float(h["loss"][h["iters"]]), holdout=ho, added=None))
+            if prev is not None and ho is not None and ho > prev_ho:
+                drop(cur)
+                return prev, hist
+            if rd == int(rounds) - 1 or h["stop"] == "loss_tol":
+                break
+            res = cur.basis_batch(x, basis, mode) - y
+            c = res if w is None else w * res
+            room = np.maximum(cap - cur.ranks().astype(np.int64)[1:-1], 0)
+            new, info = cur.enrich(x, basis, c, np.minimum(want, room), seed + rd, mode)
+            hist[-1]["added"] = info["added"]
+            if not any(info["added"]):
+                new.close()
+                break
+            drop(prev)
+            prev, prev_ho, cur = cur, ho, new
+        if prev is not None and prev is not cur:
+            drop(prev)
+        return cur, hist
+
+    def enrich_density(self, x, basis, gamma, add, w=None, seed=0, mode="auto", want_sketch=False):
+        """enrich() with the data term of sq_nll as the loss: c_p = -2 w_p f_p / (f_p^2 + gamma) / sum_p w_p, f = basis_batch(x,
+        basis).  The normaliser log(Z + gvol) also has a two-site gradient; that term is LEFT OUT here and stays open, so the
+        directions are those along which the data term alone falls fastest."""
+        f = self.basis_batch(x, basis, mode)
+        wsum = float(f.shape[0]) if w is None else float(w.sum())
+        c = (-2.0 / wsum) * (f / (f * f + gamma))
+        if w is not None:
+            c = w * c
+        return self.enrich(x, basis, c, add, seed, mode, want_sketch)
 
     # ---- samples from the resident train (include/ttx.h: ttx_sample and its three siblings) --------------
     # the outputs of the index samplers and of the real samplers: name, a row of d per sample (else one number), dtype, always allocated
